@@ -11,6 +11,10 @@ every rank refines `steps` images); the only collective is the final all_gather 
     python bench.py                                   # 1 GPU, cfg2 (1M points, 2048x1024, 32 candidates)
     python bench.py --gpus 8 --steps K --warmup W     # starts 8 fresh rank processes itself (self_launch) and relays rank 0's line
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 --steps K --warmup W     # or under torchrun
+    python bench.py --steps K --warmup W --dump-outputs DIR   # + what the last timed step returned, DIR/*.npy (dump_outputs)
+
+The timed region is ONE pass of exactly K steps (--min-seconds > 0 repeats it and reports the median pass); ms_per_step is its
+wall time / K.
 
 Output.  The LAST line of stdout is ONE compact JSON record below 4 KB (compact_line: what the driver parses — BENCH_r05.parsed was null
 for a 24.5 KB line); the COMPLETE record (the `also` block, per-kernel roofs, notes) goes to the side file --also-json (bench_also.json).
@@ -534,6 +538,23 @@ class Measure:
         return times, times[mid], kernels[mid]
 
 
+def dump_outputs(out_dir, m, item, results):
+    """--dump-outputs: what the timed path handed back in its LAST step — the last image of the last timed launch group of the
+    last pass — as float32 .npy files, a few KB in all.  The inputs are seeded (synth: room, ground truth and starting poses per
+    image id), so two builds run with the same arguments can be compared array for array.
+      candidates.npy  (B, 16)  GradientDescent.result() of the image's B candidates: fwd t(3), fwd ypr(3), leaf t(3), leaf ypr(3),
+                               last loss, lr, scheduler num_bad_epochs, scheduler best
+      trans.npy (3,), ypr.npy (3,), loss.npy (1,)  the winner (smallest last loss) Measure.refine keeps for the image"""
+    rows, grp = item[0], item[1]
+    cand = m.gd_by_size[len(grp)].result().reshape(len(grp), m.B, -1)[-1]      # (state of the group's last refine, unchanged since)
+    win = results[rows[-1], :7]
+    arrays = {"candidates": cand, "trans": win[0:3], "ypr": win[3:6], "loss": win[6:7]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    print("bench.py: outputs of the last timed step (image %d) written to %s" % (grp[-1], out_dir), file=sys.stderr, flush=True)
+
+
 def kernel_figures(N, B, groups, timed_per_run, kernel_ms, launches, pair_ms):
     """Live loss-kernel figures of one measurement: average launch time (HIP events on the launch stream, minus what an empty
     event pair reads) and SURVEY.md 8(d)'s algorithmic bytes over it."""
@@ -910,7 +931,8 @@ def emit(full, also_path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (query images refined) per rank; default 8, cfg4: 64 / ranks")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -921,10 +943,10 @@ def main():
                     help="query images whose candidates share one launch chain (0 = auto: 256 // B, at most --steps); "
                          "they share the cloud, each candidate samples its own image's panorama")
     ap.add_argument("--timer-stride", type=int, default=10, help="HIP-event pair around every n-th loss-kernel launch")
-    ap.add_argument("--min-seconds", type=float, default=2.0,
+    ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="repeat the whole timed pass (exactly --steps steps, barrier + synchronize on both sides) until this "
-                         "much time has been measured and report the MEDIAN pass: the timed region of one cfg-2 pass is "
-                         "0.08 s, too short for an outside observer (GPU-busy sampling) to corroborate; 0 = one pass")
+                         "much time has been measured and report the MEDIAN pass; 0 (default) = one pass, i.e. exactly "
+                         "--steps timed steps (size --steps from ms_per_step for a longer timed region)")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed GPU activity before the W warm-up steps: a fresh box needs ~0.2 s of load to leave its idle "
                          "clocks (first run after boot measured 3137 vs 3300 candidate-poses/s with --warmup 2)")
@@ -933,6 +955,8 @@ def main():
     ap.add_argument("--also-json", default=os.path.join(REPO, "bench_also.json"),
                     help="side file for the COMPLETE record (the `also` block, per-kernel roofs, notes); the last stdout line is the compact "
                          "line only ('' = no side file)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32; see dump_outputs)")
     args = ap.parse_args()
 
     ranks = Ranks(args)
@@ -941,8 +965,8 @@ def main():
     lib_hash = lib.pcl_source_hash().decode()
 
     N, H, W, B, batch_mode = WORKLOADS[args.workload]
-    if args.workload == "cfg4":
-        args.steps = max(1, 64 // world)
+    if args.steps is None:
+        args.steps = max(1, 64 // world) if args.workload == "cfg4" else 8
     K, Wm = args.steps, args.warmup
 
     # Images are refined in groups of `ipl`: the group's ipl * B candidates go through ONE chain of launches (shared
@@ -988,6 +1012,8 @@ def main():
     pair_ms = timer.calibrate(64)                              # what an event pair reads with nothing in between
     results[:, 14] = float(rank)                                # stamp: which rank produced the row
     pass_times, elapsed, (kernel_ms, launches) = m.repeated(timed_items, results, K, timer, args.min_seconds)
+    if rank == 0 and args.dump_outputs:                        # untimed, before anything else runs on the GD state
+        dump_outputs(args.dump_outputs, m, timed_items[-1], results)
     # proof that the collective really spanned N ranks: distinct rank stamps among the gathered rows
     ranks_seen = int(torch.unique(ranks.gather(results[:K])[:, 14]).numel())
     # every rank's OWN time for the median pass's K steps (before it waited for the others): a straggler shows as max >> min

@@ -533,6 +533,33 @@ def test_bench_rccl_path_at_world_size_one():
     assert d["checks"]["kernel_time_within_step"] and "also" not in full and "also_brief" not in d
 
 
+def test_bench_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """--steps K times exactly K steps (one pass unless --min-seconds asks for more) and --dump-outputs DIR writes what the last
+    timed step returned: the B candidates' final state and the winner Measure.refine keeps, float32, bit for bit the same from a
+    second run with the same arguments (seeded inputs, no float atomics in the refinement).  The shipped shape (6 candidates),
+    3 images in one launch chain: the last step is the last image of a multi-image group."""
+    import os
+    import sys
+    from conftest import REPO
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "shipped",
+           "--no-cpu-baseline", "--no-also", "--no-single-image"]
+    names = {"candidates.npy", "trans.npy", "ypr.npy", "loss.npy"}
+    runs = []
+    for i in range(2):
+        out = tmp_path / str(i)
+        d, full = _run_bench(cmd + ["--dump-outputs", str(out)], {})
+        assert d["steps"] == 3 and d["passes"] == 1 and full["config"]["images_per_launch"] == 3
+        assert set(os.listdir(out)) == names and sum(os.path.getsize(out / n) for n in names) < 64 << 20
+        runs.append({n[:-4]: np.load(out / n) for n in names})
+    a, b = runs
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
+    c = a["candidates"]
+    assert c.shape == (6, 16) and a["trans"].shape == a["ypr"].shape == (3,) and a["loss"].shape == (1,)
+    w = int(np.argmin(c[:, 12]))
+    assert np.array_equal(a["trans"], c[w, 0:3]) and np.array_equal(a["ypr"], c[w, 3:6]) and a["loss"][0] == c[w, 12]
+
+
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2 ...` as the driver calls the N = 1 bench, no torchrun around it (localize.py:143,357: the query
     images are what is sharded): the launcher process starts two fresh ranks before it has touched the GPU, the ranks share the
