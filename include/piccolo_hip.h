@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define PCL_ABI_VERSION 9 /* 9: pcl_gd_hyper.fuse, pcl_loss_depth_workspace_bytes takes the occluder stride, pcl_trim_order + the `order` argument of pcl_trim_loss[_images], the library reads no environment variable; 8: PCL_PANO_U8V / pcl_pano_pack_u8v; 7: depth mask on its own grid (pcl_gd_hyper.depth_h / depth_w, pcl_depth_default, pcl_sampling_loss_depth), refresh rule and pcl_gd_depth_refresh_counts removed, pcl_gd_step_from_grads; 6: pcl_select_poses, pcl_gd_set_pano_groups, pcl_gd_winner; 2: fp16-level texels, colour preprocessing, histograms, dataset text reader; 3: backward of the stand-alone ops; 4: pcl_hist_trim_workspace_bytes_n; 5: pcl_source_hash, pcl_timer_calibrate, pcl_trim_*, pcl_gd_plan */
+#define PCL_ABI_VERSION 10 /* 10: per-image colour sets (pcl_cloud_sets_bytes / pcl_cloud_pack_sets, pcl_gd_hyper.color_sets, pcl_trim_loss_images_sets, pcl_hist_trim_*_sets); 9: pcl_gd_hyper.fuse, pcl_loss_depth_workspace_bytes takes the occluder stride, pcl_trim_order + the `order` argument of pcl_trim_loss[_images], the library reads no environment variable; 8: PCL_PANO_U8V / pcl_pano_pack_u8v; 7: depth mask on its own grid (pcl_gd_hyper.depth_h / depth_w, pcl_depth_default, pcl_sampling_loss_depth), refresh rule and pcl_gd_depth_refresh_counts removed, pcl_gd_step_from_grads; 6: pcl_select_poses, pcl_gd_set_pano_groups, pcl_gd_winner; 2: fp16-level texels, colour preprocessing, histograms, dataset text reader; 3: backward of the stand-alone ops; 4: pcl_hist_trim_workspace_bytes_n; 5: pcl_source_hash, pcl_timer_calibrate, pcl_trim_*, pcl_gd_plan */
 
 #define PCL_EINVAL (-1)   /* bad size / null pointer / unsupported argument */
 #define PCL_EWORKSPACE (-2) /* workspace too small */
@@ -84,6 +84,15 @@ const char *pcl_library_hash(void);
 int64_t pcl_cloud_stride(int64_t n);
 size_t pcl_cloud_bytes(int64_t n);
 int pcl_cloud_pack(const float *xyz, const float *rgb, const int64_t *order, int64_t n, float *cloud, void *stream);
+/* Per-image colour sets (ABI 10): ONE point set with nsets colourings — e.g. the reference's color_mod, which gives every query image its
+ * own equalised cloud colours (localize.py:173-179) — as planes x, y, z, then nsets x (-r, -g, -b), each pcl_cloud_stride(n) floats.
+ * nsets = 1 is pcl_cloud_pack's 6-plane cloud, byte for byte.  rgb_host = HOST array of nsets device addresses of (n, 3) colours; the
+ * same Morton `order` gathers every plane.  Colour set k is a scalar plane offset on the cloud's one 32-bit buffer descriptor, so the whole
+ * cloud must stay below 2^31 bytes: (3 + 3 nsets) x 4 x pcl_cloud_stride(n) < 2^31 — 177 sets at 1M points (stride 1,000,192), 16 at 10M.
+ * pcl_cloud_sets_bytes answers 0 beyond that (or for n > PCL_MAX_POINTS, nsets < 1) and every entry point that takes a set count answers
+ * PCL_EINVAL: the caller splits its images into groups. */
+size_t pcl_cloud_sets_bytes(int64_t n, int nsets);
+int pcl_cloud_pack_sets(const float *xyz, const float *const *rgb_host, int nsets, const int64_t *order, int64_t n, float *cloud, void *stream);
 /* The Morton order in one call, entirely on the device: bounding box, 63-bit keys, stable radix sort of (key, index);
  * order[i] = index of the point for packed slot i.  workspace: pcl_cloud_order_workspace_bytes(n). */
 size_t pcl_cloud_order_workspace_bytes(int64_t n);
@@ -167,6 +176,11 @@ typedef struct pcl_gd_hyper {
                            /* image i's candidates a contiguous range).  0 / 1: one image.  A hint for the block -> XCD mapping only    */
                            /* (with several panoramas every XCD takes a range of pose groups, i.e. of images, over the whole cloud      */
                            /* instead of a slice of the cloud for all of them): results do not depend on it.                            */
+    int32_t color_sets;    /* 0 / 1: the cloud's one colour set.  k > 1: `cloud` holds k colour sets (pcl_cloud_pack_sets), the B candidates */
+                           /* are k images of B / k (image i's a contiguous range) and image i's candidates read set i.  The chain then runs */
+                           /* the SINGLE-IMAGE plan pcl_gd_plan(n, B / k) — its chunks, poses per block and steps per chunk — for all B: */
+                           /* every image's results are those of a one-image run with its own colours, bit for bit.  pcl_gd_init writes */
+                           /* the sets into the pose records; B % k != 0 or depth_mask: PCL_EINVAL (sizing functions: 0).                */
 } pcl_gd_hyper;
 
 size_t pcl_gd_state_bytes(int B);
@@ -288,6 +302,13 @@ size_t pcl_hist_trim_images_workspace_bytes(int64_t n, int nimages, int cand_per
 int pcl_hist_trim_scores_images(const float *cloud, int64_t n, const float *const *imgs_host, int nimages, int cand_per_image, int H, int W,
                                 const float *trans, const float *rot, int nsh, int nsw, float *inter, int32_t *nproj, int32_t *nimg,
                                 void *workspace, size_t workspace_bytes, void *stream);
+/* The same over a cloud of `color_sets` colour sets (pcl_cloud_pack_sets): color_sets == nimages renders image i's candidates with set i,
+ * color_sets == 1 is pcl_hist_trim_scores_images.  The workspace of the tile-binned path holds one row of colour codes per set (size it
+ * with the same color_sets; the size for n = 0 selects the z-buffer splat path). */
+size_t pcl_hist_trim_images_sets_workspace_bytes(int64_t n, int color_sets, int nimages, int cand_per_image, int H, int W, int nsh, int nsw);
+int pcl_hist_trim_scores_images_sets(const float *cloud, int64_t n, int color_sets, const float *const *imgs_host, int nimages, int cand_per_image,
+                                     int H, int W, const float *trans, const float *rot, int nsh, int nsw, float *inter, int32_t *nproj,
+                                     int32_t *nimg, void *workspace, size_t workspace_bytes, void *stream);
 int pcl_hist_trim_reduce_images(const float *inter, const int32_t *nproj, const int32_t *nimg, int nimages, int cand_per_image, int nsh,
                                 int nsw, float *score, void *stream);
 /* First trimming stage of the initialisation, utils.py:462-507 trim_input_loss: the forward-only sampling loss
@@ -342,6 +363,12 @@ size_t pcl_trim_loss_images_workspace_bytes(int64_t n, int K, int ngroups, int n
 int pcl_trim_loss_images(const float *cloud, int64_t n, const void *const *panos_host, int nimages, int pano_format, int H, int W,
                          const float *trans, int K, const float *rot, int R, const void *groups, int ngroups, const void *order,
                          float *loss_tables, float *count_tables, void *workspace, size_t workspace_bytes, void *stream);
+/* The same over a cloud of `color_sets` colour sets (pcl_cloud_pack_sets): color_sets == nimages makes image i's blocks read set i (a
+ * scalar plane offset), color_sets == 1 is pcl_trim_loss_images.  Same chunks, same work list (it does not depend on the colours), same
+ * workspace: image i's table has the bits pcl_trim_loss gives it over pcl_cloud_pack(xyz, rgb_i). */
+int pcl_trim_loss_images_sets(const float *cloud, int64_t n, int color_sets, const void *const *panos_host, int nimages, int pano_format, int H,
+                              int W, const float *trans, int K, const float *rot, int R, const void *groups, int ngroups, const void *order,
+                              float *loss_tables, float *count_tables, void *workspace, size_t workspace_bytes, void *stream);
 /* Scatter-min depth mask on the PACKED cloud for B poses (build-defined: the reference imports torch_scatter.scatter_min at
  * utils.py:6 and never calls it; off by default in the loss).  Seen from pose b, every point falls into one cell of an H x W grid by
  * make_pano's pixel formula (utils.py:158-165) — the DEPTH grid, chosen by point density, not the panorama's resolution: a z-buffer

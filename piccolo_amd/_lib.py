@@ -11,7 +11,7 @@ from . import build as _build
 _c = ctypes
 _vp, _i64, _int, _sz, _dbl = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_size_t, _c.c_double
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 RESULT_STRIDE = 8
 GD_RESULT_STRIDE = 16
 GD_SEQUENTIAL, GD_BATCH = 0, 1
@@ -21,7 +21,7 @@ PANO_F32, PANO_U8, PANO_F16, PANO_U8P, PANO_U8V = 0, 1, 2, 3, 4
 class GdHyper(_c.Structure):
     _fields_ = [("lr", _dbl), ("factor", _dbl), ("patience", _c.c_int32), ("mode", _c.c_int32),
                 ("depth_mask", _c.c_int32), ("depth_tau", _c.c_float), ("depth_h", _c.c_int32), ("depth_w", _c.c_int32),
-                ("depth_stride", _c.c_int32), ("fuse", _c.c_int32), ("images", _c.c_int32)]
+                ("depth_stride", _c.c_int32), ("fuse", _c.c_int32), ("images", _c.c_int32), ("color_sets", _c.c_int32)]
 
 
 # name -> (restype, argtypes); every symbol include/piccolo_hip.h declares
@@ -33,6 +33,8 @@ SIGNATURES = {
     "pcl_cloud_stride": (_i64, [_i64]),
     "pcl_cloud_bytes": (_sz, [_i64]),
     "pcl_cloud_pack": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "pcl_cloud_sets_bytes": (_sz, [_i64, _int]),
+    "pcl_cloud_pack_sets": (_int, [_vp, _c.POINTER(_vp), _int, _vp, _i64, _vp, _vp]),
     "pcl_morton_keys": (_int, [_vp, _i64, _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _vp, _vp]),
     "pcl_pano_bytes": (_sz, [_int, _int, _int]),
     "pcl_pano_pack": (_int, [_vp, _int, _int, _vp, _vp]),
@@ -67,6 +69,8 @@ SIGNATURES = {
     "pcl_hist_trim_images_workspace_bytes": (_sz, [_i64, _int, _int, _int, _int, _int, _int]),
     "pcl_hist_trim_scores_images": (_int, [_vp, _i64, _c.POINTER(_vp), _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcl_hist_trim_reduce_images": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
+    "pcl_hist_trim_images_sets_workspace_bytes": (_sz, [_i64, _int, _int, _int, _int, _int, _int, _int]),
+    "pcl_hist_trim_scores_images_sets": (_int, [_vp, _i64, _int, _c.POINTER(_vp), _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcl_trim_groups_bytes": (_sz, [_int]),
     "pcl_trim_groups": (_int, [_vp, _int, _vp, _vp]),
     "pcl_trim_loss_workspace_bytes": (_sz, [_i64, _int, _int]),
@@ -76,6 +80,7 @@ SIGNATURES = {
     "pcl_trim_order": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _vp, _int, _vp, _int, _vp, _vp, _sz, _vp]),
     "pcl_trim_loss_images_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
     "pcl_trim_loss_images": (_int, [_vp, _i64, _c.POINTER(_vp), _int, _int, _int, _int, _vp, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pcl_trim_loss_images_sets": (_int, [_vp, _i64, _int, _c.POINTER(_vp), _int, _int, _int, _int, _vp, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcl_depth_workspace_bytes": (_sz, [_int, _int, _int]),
     "pcl_depth_mask": (_int, [_vp, _i64, _vp, _vp, _int, _int, _int, _c.c_float, _int, _vp, _vp, _sz, _vp]),
     "pcl_gd_init": (_int, [_vp, _vp, _vp, _int, _c.POINTER(GdHyper), _vp]),

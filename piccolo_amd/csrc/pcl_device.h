@@ -37,7 +37,9 @@ struct PclPoseRec {
     float t[3];
     uint32_t pano_lo, pano_hi;   // this pose's panorama (device address) when poses of several query images share a
                                  // launch; 0 = the launch's default panorama
-    float pad[2];
+    uint32_t cset;               // this pose's colour set when the cloud holds one per query image (pcl_gd_hyper.color_sets > 1:
+                                 // written by pcl_gd_init); read only by the loss kernels' colour-set instances
+    float pad;
 };
 static_assert(sizeof(PclPoseRec) == 64, "pose record is one 64-byte scalar-load line");
 // pcl_project2 (pcl_loss.hip) reads R and t as six consecutive 64-bit SGPR pairs (R0,R1) ... (R8,t0) (t1,t2)
@@ -137,7 +139,7 @@ __device__ inline void pcl_write_pose_rec(PclPoseRec* rec, const float p[6])
     for (int k = 0; k < 9; k++) rec->R[k] = R[k];
     rec->t[0] = p[0]; rec->t[1] = p[1]; rec->t[2] = p[2];
     rec->pano_lo = 0u; rec->pano_hi = 0u;
-    rec->pad[0] = rec->pad[1] = 0.f;
+    rec->cset = 0u; rec->pad = 0.f;
 }
 
 // Same R for the GD epilogue, which runs once per iteration on ONE lane per candidate: fp32 sincosf (<= 2 ulp, the

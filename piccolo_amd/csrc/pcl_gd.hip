@@ -13,11 +13,12 @@
 
 int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses,
                     int B, bool grad, const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse,
-                    const PclDepthLook* depth);
-size_t pcl_partials_bytes(int64_t n, int B);
-int pcl_plan_nchunks(int64_t n, int B);
-int pcl_plan_nblocks(int64_t n, int B);
-int pcl_plan_G(int64_t n, int B);
+                    const PclDepthLook* depth, int color_sets = 1);
+// (sets > 1: the single-image plan of B / sets candidates for all B — pcl_plan_sets, pcl_loss.hip)
+size_t pcl_partials_bytes(int64_t n, int B, int sets = 1);
+int pcl_plan_nchunks(int64_t n, int B, int sets = 1);
+int pcl_plan_nblocks(int64_t n, int B, int sets = 1);
+int pcl_plan_G(int64_t n, int B, int sets = 1);
 size_t pcl_depth_zbuf_bytes(int B, int Hd, int Wd);
 int pcl_launch_zbuffers(const float* cloud, int64_t n, const PclPoseRec* poses, int B, const PclDepthGrid& g, int zstride, uint32_t* zbuf, bool fill,
                         hipStream_t s);
@@ -162,8 +163,9 @@ static inline PclPoseRec* gd_recs(void* state, int B, int copy = 0)
     return (PclPoseRec*)((char*)state + (size_t)copy * gd_copy_bytes(B) + (size_t)B * sizeof(PclGdPose));
 }
 
+// per_image > 0 (pcl_gd_hyper.color_sets > 1): candidate b reads colour set b / per_image
 __global__ void pcl_gd_init_kernel(PclGdPose* st, PclPoseRec* recs, PclPoseRec* recs_shadow, const float* __restrict__ trans,
-                                   const float* __restrict__ rot, int B, double lr)
+                                   const float* __restrict__ rot, int B, double lr, int per_image)
 {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -174,7 +176,7 @@ __global__ void pcl_gd_init_kernel(PclGdPose* st, PclPoseRec* recs, PclPoseRec* 
     for (int k = 0; k < 6; k++) { g.fwd[k] = g.leaf[k]; g.m[k] = 0.f; g.v[k] = 0.f; }
     g.last_loss = 0.f; g.num_bad = 0; g.step = 0; g.pad = 0;
     g.beta1_pow = 1.0; g.beta2_pow = 1.0;
-    recs[b].pano_lo = 0u; recs[b].pano_hi = 0u; recs[b].pad[0] = recs[b].pad[1] = 0.f;
+    recs[b].pano_lo = 0u; recs[b].pano_hi = 0u; recs[b].cset = per_image > 0 ? (uint32_t)(b / per_image) : 0u; recs[b].pad = 0.f;
     pcl_write_pose_rec_fast(&recs[b], g.fwd, g.sc);
     recs_shadow[b] = recs[b];
     st[b] = g;
@@ -218,10 +220,21 @@ __global__ void pcl_gd_result_kernel(const PclGdPose* __restrict__ st, int B, fl
 
 extern "C" size_t pcl_gd_state_bytes(int B) { return B > 0 ? 2 * gd_copy_bytes(B) : 0; }
 
+// colour sets of a run: 1 (the cloud's one set, or 0 / 1 in the hyper-parameters) or hyper->color_sets; -1 when that does not split B
+// or is combined with the depth mask (whose loss pass has no colour-set instance)
+static int gd_sets(int B, const pcl_gd_hyper* hyper_host)
+{
+    if (!hyper_host || hyper_host->color_sets <= 1) return hyper_host && hyper_host->color_sets < 0 ? -1 : 1;
+    return B % hyper_host->color_sets || hyper_host->depth_mask ? -1 : hyper_host->color_sets;
+}
+
 extern "C" size_t pcl_gd_workspace_bytes(int64_t n, int B, int H, int W, const pcl_gd_hyper* hyper_host)
 {
     if (n <= 0 || B <= 0 || !hyper_host) return 0;
-    size_t bytes = 2 * gd_align(pcl_partials_bytes(n, B));         // (two: fused iterations read one while they write the other)
+    const int sets = gd_sets(B, hyper_host);
+    if (sets < 0) return 0;
+    // (with colour sets the single-image plan: more chunks than the plan of B candidates may have, hence larger partials)
+    size_t bytes = 2 * gd_align(pcl_partials_bytes(n, B, sets));   // (two: fused iterations read one while they write the other)
     if (hyper_host->depth_mask) {
         PclDepthGrid g;
         if (gd_depth_grid(n, H, W, hyper_host->depth_h, hyper_host->depth_w, 0.f, hyper_host->depth_stride, &g, nullptr)) return 0;
@@ -235,8 +248,10 @@ extern "C" size_t pcl_gd_workspace_bytes(int64_t n, int B, int H, int W, const p
 extern "C" int pcl_gd_init(void* state, const float* trans, const float* rot, int B, const pcl_gd_hyper* hyper_host, void* stream)
 {
     if (!state || !trans || !rot || !hyper_host || B <= 0) return PCL_EINVAL;
+    const int sets = gd_sets(B, hyper_host);
+    if (sets < 0) return PCL_EINVAL;
     hipLaunchKernelGGL(pcl_gd_init_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, gd_poses(state),
-                       gd_recs(state, B), gd_recs(state, B, 1), trans, rot, B, hyper_host->lr);
+                       gd_recs(state, B), gd_recs(state, B, 1), trans, rot, B, hyper_host->lr, sets > 1 ? B / sets : 0);
     PCL_LAUNCH_CHECK();
     return 0;
 }
@@ -305,11 +320,13 @@ static int gd_fuse_limit(const pcl_gd_hyper* hyper_host)
 extern "C" int pcl_gd_plan_hyper(int64_t n, int B, const pcl_gd_hyper* hyper_host, int* nchunks_host, int* poses_per_block_host, int* fused_host)
 {
     if (n <= 0 || n > PCL_MAX_POINTS || B <= 0) return PCL_EINVAL;
-    if (nchunks_host) *nchunks_host = pcl_plan_nchunks(n, B);
-    if (poses_per_block_host) *poses_per_block_host = pcl_plan_G(n, B);
+    const int sets = gd_sets(B, hyper_host);
+    if (sets < 0) return PCL_EINVAL;
+    if (nchunks_host) *nchunks_host = pcl_plan_nchunks(n, B, sets);
+    if (poses_per_block_host) *poses_per_block_host = pcl_plan_G(n, B, sets);
     // (the depth-masked loss pass reads a byte mask the fused prologue knows nothing about: pcl_gd_run keeps two launches there)
     const bool depth = hyper_host && hyper_host->depth_mask;
-    if (fused_host) *fused_host = (!depth && pcl_plan_nblocks(n, B) <= gd_fuse_limit(hyper_host)) ? 1 : 0;
+    if (fused_host) *fused_host = (!depth && pcl_plan_nblocks(n, B, sets) <= gd_fuse_limit(hyper_host)) ? 1 : 0;
     return 0;
 }
 
@@ -358,8 +375,12 @@ extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int p
         return PCL_EINVAL;
     if (n > PCL_MAX_POINTS) return PCL_EINVAL;
     if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
+    // colour sets: `cloud` holds hyper->color_sets of them (pcl_cloud_pack_sets) and candidate b reads set b / (B / color_sets), as
+    // pcl_gd_init wrote into its pose record; the chain runs the single-image plan of B / color_sets candidates (pcl_plan_sets)
+    const int sets = gd_sets(B, hyper_host);
+    if (sets < 0 || (sets > 1 && pcl_cloud_sets_bytes(n, sets) == 0)) return PCL_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* partials2[2] = {(float*)workspace, (float*)((char*)workspace + gd_align(pcl_partials_bytes(n, B)))};
+    float* partials2[2] = {(float*)workspace, (float*)((char*)workspace + gd_align(pcl_partials_bytes(n, B, sets)))};
     PclDepthLook look;
     look.zbuf = nullptr;
     int zstride = 1;
@@ -371,13 +392,13 @@ extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int p
     if (need == 0 || workspace_bytes < need) return PCL_EWORKSPACE;
     uint32_t* zbuf2[2] = {nullptr, nullptr};
     if (hyper_host->depth_mask) {
-        zbuf2[0] = (uint32_t*)((char*)workspace + 2 * gd_align(pcl_partials_bytes(n, B)));
+        zbuf2[0] = (uint32_t*)((char*)workspace + 2 * gd_align(pcl_partials_bytes(n, B, sets)));
         zbuf2[1] = (uint32_t*)((char*)zbuf2[0] + gd_align(pcl_depth_zbuf_bytes(B, look.grid.Hd, look.grid.Wd)));
         look.zclear_vec4 = (int64_t)(pcl_depth_zbuf_bytes(B, look.grid.Hd, look.grid.Wd) / 16);
     }
     const bool depth_on = zbuf2[0] != nullptr;
     static const int pingpong_env = PCL_KNOB(ZPINGPONG, 1);      // 0: a fill launch per iteration (A/B)
-    const int nchunks = pcl_plan_nchunks(n, B);
+    const int nchunks = pcl_plan_nchunks(n, B, sets);
     // odd iterations walk every XCD's chunks backwards: the first blocks of a launch then read the chunks the previous launch
     // finished with, still in that XCD's L2 (PCL_FLIP=0 turns it off; +0.3 % at cfg 2 in two A/B alternations on one box —
     // the first round of a launch stays 6 us slower than the later ones, so cold L2 is not what makes it slow)
@@ -394,8 +415,8 @@ extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int p
     // 10 groups per XCD straddling the images, every XCD walking the whole 24 MB cloud) -1.5 % (3 533 -> 3 479).
     const int xcd_bit = hyper_host->images > 1 && n * 24 <= ((int64_t)6 << 20) ? 2 : 0;
     const int fuse_blocks = gd_fuse_limit(hyper_host);
-    const bool fused = !depth_on && pcl_plan_nblocks(n, B) <= fuse_blocks;
-    const int G = pcl_plan_G(n, B);
+    const bool fused = !depth_on && pcl_plan_nblocks(n, B, sets) <= fuse_blocks;
+    const int G = pcl_plan_G(n, B, sets);
     auto epilogue = [&](int it, int copy_in, float* partials) {
         const PclGdPose* si = gd_poses(state, B, copy_in);
         const PclPoseRec* ri = gd_recs(state, B, copy_in);
@@ -437,10 +458,10 @@ extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int p
             f.box = box; f.factor = hyper_host->factor; f.patience = (int)hyper_host->patience; f.mode = (int)hyper_host->mode;
             f.loss_out = loss_history ? loss_history + (int64_t)(it - 1) * B : nullptr;
             rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, f.recs_in, B, true, nullptr, partials2[cout], s, (flip_env ? (it & 1) : 0) | xcd_bit, &f,
-                                 nullptr);
+                                 nullptr, sets);
         } else {
             rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, gd_recs(state, B), B, true, nullptr, partials2[0], s, (flip_env ? (it & 1) : 0) | xcd_bit,
-                                 nullptr, depth);
+                                 nullptr, depth, sets);
         }
         if (rc) return rc;
         if (timed) {

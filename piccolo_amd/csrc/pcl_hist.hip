@@ -426,10 +426,13 @@ extern "C" int pcl_debug_set_hist_trace(unsigned long long* buf)
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(pcl_hist_trace_buf), &buf, sizeof(buf));
 }
 #endif
-template <int PCL_RESOLVE_THREADS>
-__global__ void __launch_bounds__(PCL_RESOLVE_THREADS) pcl_tile_resolve_hist_kernel(PclBinArgs a, const uint8_t* __restrict__ qmask, const uint16_t* __restrict__ codes, int cpi,
-                                                                          int nsh, int nsw, unsigned int* __restrict__ ghist)
+// CS: per-image colour sets — the colour codes are [nimages][code_stride], candidate c reads row c / cpi (a template parameter: the
+// shared-colour kernel keeps its code)
+template <int PCL_RESOLVE_THREADS, bool CS>
+__device__ __forceinline__ void pcl_tile_resolve_hist_body(const PclBinArgs& a, const uint8_t* __restrict__ qmask, const uint16_t* __restrict__ codes_all,
+                                                           int cpi, int nsh, int nsw, unsigned int* __restrict__ ghist, int64_t code_stride)
 {
+    const uint16_t* __restrict__ codes = CS ? codes_all + (int64_t)((int)blockIdx.x / cpi) * code_stride : codes_all;
     const uint8_t* __restrict__ qm = qmask + (int64_t)((int)blockIdx.x / cpi) * a.H * a.W;      // (blockIdx.x = candidate)
     // the tile with a halo of two pixels: every splat pixel of every listed entry has a cell (an entry is listed when its 3 x 3
     // splat touches the tile, so its centre is at most one pixel outside), and the nine writes need no membership test
@@ -603,6 +606,21 @@ __global__ void __launch_bounds__(PCL_RESOLVE_THREADS) pcl_tile_resolve_hist_ker
 #endif
 }
 
+template <int PCL_RESOLVE_THREADS>
+__global__ void __launch_bounds__(PCL_RESOLVE_THREADS) pcl_tile_resolve_hist_kernel(PclBinArgs a, const uint8_t* __restrict__ qmask, const uint16_t* __restrict__ codes, int cpi,
+                                                                          int nsh, int nsw, unsigned int* __restrict__ ghist)
+{
+    pcl_tile_resolve_hist_body<PCL_RESOLVE_THREADS, false>(a, qmask, codes, cpi, nsh, nsw, ghist, 0);
+}
+
+template <int PCL_RESOLVE_THREADS>
+__global__ void __launch_bounds__(PCL_RESOLVE_THREADS) pcl_tile_resolve_hist_sets_kernel(PclBinArgs a, const uint8_t* __restrict__ qmask,
+                                                                                         const uint16_t* __restrict__ codes, int cpi, int nsh, int nsw,
+                                                                                         unsigned int* __restrict__ ghist, int64_t code_stride)
+{
+    pcl_tile_resolve_hist_body<PCL_RESOLVE_THREADS, true>(a, qmask, codes, cpi, nsh, nsw, ghist, code_stride);
+}
+
 
 // Histograms in two steps so that a handful of image blocks still fills the chip: every (block, candidate) is cut into
 // PCL_HSUB pixel ranges, each range is histogrammed in LDS by its own workgroup and its non-empty bins are added to a
@@ -612,10 +630,11 @@ __global__ void __launch_bounds__(PCL_RESOLVE_THREADS) pcl_tile_resolve_hist_ker
                                 // 25 MB image at 1.5 TB/s, 16 us per call; round 6)
 
 // MODE 0: query image (zbuf unused, cand = 0)   MODE 1: candidate renders
-template <int MODE>
-__global__ void __launch_bounds__(PCL_BLOCK) pcl_hist_accum_kernel(const unsigned long long* __restrict__ zbuf, const float* __restrict__ cloud,
-                                                                   int64_t stride, PclImgList imgs, int cpi, int H, int W, int nsh,
-                                                                   int nsw, unsigned int* __restrict__ ghist, uint8_t* __restrict__ qmask)
+// CS (MODE 1): per-image colour sets — candidate c reads the colour planes of set c / cpi (pcl_cloud_pack_sets)
+template <int MODE, bool CS>
+__device__ __forceinline__ void pcl_hist_accum_body(const unsigned long long* __restrict__ zbuf, const float* __restrict__ cloud, int64_t stride,
+                                                    const PclImgList& imgs, int cpi, int H, int W, int nsh, int nsw, unsigned int* __restrict__ ghist,
+                                                    uint8_t* __restrict__ qmask)
 {
     // MODE 0: blockIdx.y = query image (its own histograms);  MODE 1: blockIdx.y = candidate, scored against image cand / cpi
     const float* __restrict__ img = imgs.p[MODE == 0 ? (int)blockIdx.y : (int)blockIdx.y / cpi];
@@ -642,8 +661,9 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_hist_accum_kernel(const unsigne
             unsigned long long k = zb[pix];
             if (qm && k != ~0ull) {
                 int64_t j = (int64_t)(0x1fffffffu - (uint32_t)(k & 0x1fffffffull));
-                // image * 255 (utils.py:200); the packed cloud holds -rgb in planes 3..5
-                float p0 = -cloud[3 * stride + j] * 255.f, p1 = -cloud[4 * stride + j] * 255.f, p2 = -cloud[5 * stride + j] * 255.f;
+                // image * 255 (utils.py:200); the packed cloud holds -rgb in planes 3..5 (CS: in the planes of the candidate's set)
+                const float* __restrict__ col = CS ? cloud + (3 + 3 * (int64_t)(cand / cpi)) * stride : cloud + 3 * stride;
+                float p0 = -col[j] * 255.f, p1 = -col[stride + j] * 255.f, p2 = -col[2 * stride + j] * 255.f;
                 if (!(p0 == 0.f && p1 == 0.f && p2 == 0.f)) atomicAdd(&hist[pcl_hist_code(p0, p1, p2)], 1u);
             }
         }
@@ -652,6 +672,21 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_hist_accum_kernel(const unsigne
     unsigned int* g = ghist + ((int64_t)cand * nblk + blk) * PCL_HBINS;
     for (int i = threadIdx.x; i < PCL_HBINS; i += PCL_BLOCK)
         if (hist[i]) atomicAdd(&g[i], hist[i]);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_hist_accum_kernel(const unsigned long long* __restrict__ zbuf, const float* __restrict__ cloud,
+                                                                   int64_t stride, PclImgList imgs, int cpi, int H, int W, int nsh,
+                                                                   int nsw, unsigned int* __restrict__ ghist, uint8_t* __restrict__ qmask)
+{
+    pcl_hist_accum_body<MODE, false>(zbuf, cloud, stride, imgs, cpi, H, W, nsh, nsw, ghist, qmask);
+}
+
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_hist_accum_sets_kernel(const unsigned long long* __restrict__ zbuf, const float* __restrict__ cloud,
+                                                                        int64_t stride, PclImgList imgs, int cpi, int H, int W, int nsh,
+                                                                        int nsw, unsigned int* __restrict__ ghist, uint8_t* __restrict__ qmask)
+{
+    pcl_hist_accum_body<1, true>(zbuf, cloud, stride, imgs, cpi, H, W, nsh, nsw, ghist, qmask);
 }
 
 // inter[cand][blk] = sum min(h / h.sum(), q / q.sum()) (torch.min(h1, h2).sum(), color_utils.py:122-144), nproj[cand][blk] = h.sum(),
@@ -718,6 +753,20 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_hist_prepare_kernel(const float
         }
 }
 
+// the same with per-image colour sets: the colour codes of every set, codes[k][code_stride] from planes 3 + 3 k .. 5 + 3 k (the kernel
+// above with codes = nullptr did everything else).  blockIdx.y = set k, grid-stride over the points of that set.
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_hist_codes_sets_kernel(const float* __restrict__ cloud, int64_t n, int64_t stride,
+                                                                        uint16_t* __restrict__ codes, int64_t code_stride)
+{
+    const int64_t k = blockIdx.y;
+    const float* __restrict__ col = cloud + (3 + 3 * k) * stride;
+    uint16_t* __restrict__ out = codes + k * code_stride;
+    for (int64_t j = (int64_t)blockIdx.x * PCL_BLOCK + threadIdx.x; j < n; j += (int64_t)gridDim.x * PCL_BLOCK) {
+        const float p0 = -col[j] * 255.f, p1 = -col[stride + j] * 255.f, p2 = -col[2 * stride + j] * 255.f;
+        out[j] = (p0 == 0.f && p1 == 0.f && p2 == 0.f) ? (uint16_t)0xffffu : (uint16_t)pcl_hist_code(p0, p1, p2);
+    }
+}
+
 static size_t hist_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // can the tile-binned render be used at all for this cloud / panorama (16-bit pixel fields, 28-bit slots, <= 4096 tiles)?
@@ -741,14 +790,18 @@ static size_t hist_render_bytes(int64_t n, int H, int W)
     return binned > zb ? binned : zb;
 }
 
-static size_t hist_workspace_bytes(int64_t n, int ncand, int H, int W, int nsh, int nsw, int nimages = 1)
+// words per colour set of the colour codes (per-image colour sets: every set's codes start on a 256-byte boundary)
+static int64_t hist_code_stride(int64_t n) { return (n + 127) & ~(int64_t)127; }
+
+static size_t hist_workspace_bytes(int64_t n, int ncand, int H, int W, int nsh, int nsw, int nimages = 1, int nsets = 1)
 {
     if (ncand <= 0 || nimages <= 0 || H <= 0 || W <= 0 || nsh < 3 || nsw < 1) return 0;
     const size_t nblk = (size_t)(nsh - 2) * nsw;
+    const size_t code_bytes = nsets > 1 ? (size_t)nsets * hist_code_stride(n) * sizeof(uint16_t) : (size_t)n * sizeof(uint16_t);
     return hist_align((size_t)ncand * sizeof(PclPoseRec)) + hist_align((size_t)ncand * hist_render_bytes(n, H, W)) +
            hist_align((size_t)nimages * nblk * PCL_HBINS * sizeof(float)) +
            hist_align((size_t)(ncand + nimages) * nblk * PCL_HBINS * sizeof(unsigned int)) +
-           (n > 0 ? hist_align((size_t)nimages * H * W) + hist_align((size_t)n * sizeof(uint16_t)) : 0);     // query masks, colour codes
+           (n > 0 ? hist_align((size_t)nimages * H * W) + hist_align(code_bytes) : 0);     // query masks, colour codes (one row per colour set)
 }
 
 extern "C" size_t pcl_hist_trim_workspace_bytes_n(int64_t n, int ncand, int H, int W, int nsh, int nsw)
@@ -767,13 +820,24 @@ extern "C" size_t pcl_hist_trim_images_workspace_bytes(int64_t n, int nimages, i
     return hist_workspace_bytes(n, nimages * cand_per_image, H, W, nsh, nsw, nimages);
 }
 
+// color_sets 1: the cloud's colours for every image; nimages: image i's candidates render colour set i (pcl_cloud_pack_sets) — the tile-binned
+// path then keeps one row of colour codes per set.  n = 0: the smaller workspace that selects the z-buffer splat path for these images.
+extern "C" size_t pcl_hist_trim_images_sets_workspace_bytes(int64_t n, int color_sets, int nimages, int cand_per_image, int H, int W, int nsh, int nsw)
+{
+    if (n < 0 || nimages <= 0 || nimages > PCL_HIST_MAX_IMAGES || cand_per_image <= 0) return 0;
+    if (color_sets != 1 && (color_sets != nimages || (n > 0 && pcl_cloud_sets_bytes(n, color_sets) == 0))) return 0;
+    return hist_workspace_bytes(n, nimages * cand_per_image, H, W, nsh, nsw, nimages, color_sets);
+}
+
 // candidates [i * cand_per_image, (i + 1) * cand_per_image) are scored against imgs_host[i]; nimg [nimages][nblk]
-extern "C" int pcl_hist_trim_scores_images(const float* cloud, int64_t n, const float* const* imgs_host, int nimages, int cand_per_image, int H,
-                                           int W, const float* trans, const float* rot, int nsh, int nsw, float* inter, int* nproj,
-                                           int* nimg, void* workspace, size_t workspace_bytes, void* stream)
+extern "C" int pcl_hist_trim_scores_images_sets(const float* cloud, int64_t n, int color_sets, const float* const* imgs_host, int nimages,
+                                                int cand_per_image, int H, int W, const float* trans, const float* rot, int nsh, int nsw, float* inter,
+                                                int* nproj, int* nimg, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!cloud || !imgs_host || !trans || !rot || !inter || !nproj || !nimg || !workspace) return PCL_EINVAL;
     if (nimages <= 0 || nimages > PCL_HIST_MAX_IMAGES || cand_per_image <= 0) return PCL_EINVAL;
+    if (color_sets != 1 && (color_sets != nimages || pcl_cloud_sets_bytes(n, color_sets) == 0)) return PCL_EINVAL;
+    const bool sets = color_sets > 1;
     const int ncand = nimages * cand_per_image, cpi = cand_per_image;
     PclImgList imgs;
     for (int i = 0; i < PCL_HIST_MAX_IMAGES; i++) {
@@ -785,7 +849,7 @@ extern "C" int pcl_hist_trim_scores_images(const float* cloud, int64_t n, const 
     if (workspace_bytes < hist_workspace_bytes(0, ncand, H, W, nsh, nsw, nimages)) return PCL_EWORKSPACE;
     // a workspace sized with n (pcl_hist_trim_workspace_bytes_n / pcl_hist_trim_images_workspace_bytes) selects the tile-binned
     // path, the smaller one of pcl_hist_trim_workspace_bytes(...) the z-buffer splat
-    const bool roomy = workspace_bytes >= hist_workspace_bytes(n, ncand, H, W, nsh, nsw, nimages);
+    const bool roomy = workspace_bytes >= hist_workspace_bytes(n, ncand, H, W, nsh, nsw, nimages, color_sets);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     PclPoseRec* recs = (PclPoseRec*)ws;
@@ -812,7 +876,12 @@ extern "C" int pcl_hist_trim_scores_images(const float* cloud, int64_t n, const 
         if (work < ncand) work = ncand;
         const int64_t blocks = (work + PCL_BLOCK - 1) / PCL_BLOCK;
         hipLaunchKernelGGL(pcl_hist_prepare_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(PCL_BLOCK), 0, s, trans, rot, ncand, recs, ghist_q,
-                           ghist_words, stat, stat_words, cloud, n, stride, binned ? codes : (uint16_t*)nullptr);
+                           ghist_words, stat, stat_words, cloud, n, stride, binned && !sets ? codes : (uint16_t*)nullptr);
+        if (binned && sets) {
+            const int64_t cb = (n + PCL_BLOCK - 1) / PCL_BLOCK, per_set = (4096 + color_sets - 1) / color_sets;
+            hipLaunchKernelGGL(pcl_hist_codes_sets_kernel, dim3((unsigned)(cb < per_set ? cb : per_set), (unsigned)color_sets), dim3(PCL_BLOCK), 0, s,
+                               cloud, n, stride, codes, hist_code_stride(n));
+        }
     }
     hipLaunchKernelGGL(pcl_hist_accum_kernel<0>, dim3(nblk * PCL_HSUB_QUERY, nimages), dim3(PCL_BLOCK), 0, s, (const unsigned long long*)nullptr,
                        cloud, stride, imgs, cpi, H, W, nsh, nsw, ghist_q, qmask);
@@ -847,7 +916,12 @@ extern "C" int pcl_hist_trim_scores_images(const float* cloud, int64_t n, const 
         hipLaunchKernelGGL(pcl_bin_rank_kernel, dim3(ncand, (nt + 63) / 64), dim3(PCL_BLOCK), (size_t)(((nt + 3) & ~3) + PCL_BLOCK) * sizeof(int), s, b);
         const int rt_env = PCL_KNOB(RESOLVE_THREADS, 0);
         const int rt = rt_env == 256 ? 256 : 1024;      // measured: 256 threads LOSE at both shapes (0.434 -> 0.489 ms at 167k x 50, 1.35 -> 1.53 at 1M x 64)
-        if (rt == 1024) hipLaunchKernelGGL(pcl_tile_resolve_hist_kernel<1024>, dim3(ncand, nt), dim3(1024), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c);
+        if (sets) {
+            if (rt == 1024) hipLaunchKernelGGL(pcl_tile_resolve_hist_sets_kernel<1024>, dim3(ncand, nt), dim3(1024), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c,
+                                               hist_code_stride(n));
+            else hipLaunchKernelGGL(pcl_tile_resolve_hist_sets_kernel<256>, dim3(ncand, nt), dim3(256), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c,
+                                    hist_code_stride(n));
+        } else if (rt == 1024) hipLaunchKernelGGL(pcl_tile_resolve_hist_kernel<1024>, dim3(ncand, nt), dim3(1024), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c);
         else hipLaunchKernelGGL(pcl_tile_resolve_hist_kernel<256>, dim3(ncand, nt), dim3(256), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c);
     } else {
         hipLaunchKernelGGL(pcl_fill_u64b_kernel, dim3(2048), dim3(PCL_BLOCK), 0, s, zbuf, (int64_t)ncand * H * W, ~0ull);
@@ -859,13 +933,25 @@ extern "C" int pcl_hist_trim_scores_images(const float* cloud, int64_t n, const 
         constexpr int TH = 64, TW = 64, PTS = 256;
         hipLaunchKernelGGL((pcl_splat_poses_kernel<TH, TW, PTS>), dim3((unsigned)((n + PTS - 1) / PTS), (unsigned)ncand),
                            dim3(PCL_BLOCK), 0, s, cloud, n, stride, recs, H, W, zbuf);
-        hipLaunchKernelGGL(pcl_hist_accum_kernel<1>, dim3(nblk * PCL_HSUB, ncand), dim3(PCL_BLOCK), 0, s, zbuf, cloud, stride, imgs, cpi, H, W,
-                           nsh, nsw, ghist_c, (uint8_t*)nullptr);
+        if (sets)
+            hipLaunchKernelGGL(pcl_hist_accum_sets_kernel, dim3(nblk * PCL_HSUB, ncand), dim3(PCL_BLOCK), 0, s, zbuf, cloud, stride, imgs, cpi, H, W,
+                               nsh, nsw, ghist_c, (uint8_t*)nullptr);
+        else
+            hipLaunchKernelGGL(pcl_hist_accum_kernel<1>, dim3(nblk * PCL_HSUB, ncand), dim3(PCL_BLOCK), 0, s, zbuf, cloud, stride, imgs, cpi, H, W,
+                               nsh, nsw, ghist_c, (uint8_t*)nullptr);
     }
     hipLaunchKernelGGL(pcl_hist_final_kernel, dim3(nblk, ncand), dim3(PCL_BLOCK), 0, s, (const unsigned int*)ghist_c, (const unsigned int*)ghist_q, nimg, inter,
                        nproj, cpi);
     PCL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int pcl_hist_trim_scores_images(const float* cloud, int64_t n, const float* const* imgs_host, int nimages, int cand_per_image, int H,
+                                           int W, const float* trans, const float* rot, int nsh, int nsw, float* inter, int* nproj,
+                                           int* nimg, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return pcl_hist_trim_scores_images_sets(cloud, n, 1, imgs_host, nimages, cand_per_image, H, W, trans, rot, nsh, nsw, inter, nproj, nimg, workspace,
+                                            workspace_bytes, stream);
 }
 
 extern "C" int pcl_hist_trim_scores(const float* cloud, int64_t n, const float* img_hwc, int H, int W,

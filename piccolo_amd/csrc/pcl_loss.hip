@@ -44,6 +44,7 @@ struct PclLossArgs {
     int seg_len;                 // chunks per contiguous run of one XCD (see the mapping at the top of pcl_loss_kernel)
     int xcd_groups;              // 1: the XCDs split the pose groups (ngroups % 8 == 0), every XCD walks all chunks
     int steps_base, steps_rem;   // the cloud's ceil(n / PCL_STEP) steps are dealt out evenly: chunk c has steps_base + (c < steps_rem)
+    int color_sets;              // colour sets of the cloud (pcl_cloud_pack_sets; read by the CS instances only): 3 + 3 color_sets planes
 };
 
 #define PCL_STEP (2 * PCL_BLOCK)   // points per block iteration: two per lane
@@ -74,7 +75,10 @@ extern "C" int pcl_debug_stamp(unsigned long long* slot, void* stream)
 // (Forcing more resident blocks per CU through __launch_bounds__ was tried: the register allocator spills, 2-4x slower.)
 // FUSED: the block first finishes the PREVIOUS GD iteration for its own poses (PclFuseArgs, pcl_gd_device.h) and evaluates the
 // poses that come out of it; the block of chunk 0 also stores the optimiser state.  No block waits for another one.
-template <int G, bool GRAD, int VIS, int FMT, bool FUSED>
+// CS: the cloud holds one colour set per query image (pcl_cloud_pack_sets) and the block's G poses read the set their first pose
+// record names (PclPoseRec.cset, one image's poses per group): a scalar plane offset on the same buffer resource — no VGPR, no
+// branch in the load loop.  A template parameter, not a runtime select: the instances without it compile to the loop they always had.
+template <int G, bool GRAD, int VIS, int FMT, bool FUSED, bool CS = false>
 __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a, const PclFuseArgs& f)
 {
     // XCD-aware mapping: blocks b and b+8 share an XCD (round-robin dispatch) and each XCD has its own 4 MiB L2.  Within an
@@ -110,8 +114,12 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a, const PclFus
     unsigned PANO[G][2];                          // FUSED: the poses' panorama addresses as uniform values
     __amdgpu_buffer_rsrc_t tex = pcl_tex_rsrc(a.pano, a.dims.H, a.dims.W, pcl_texel_bytes(FMT));
     // the cloud through a buffer resource too: 32-bit lane offsets + scalar plane offsets, no 64-bit address math
-    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, (int)(a.stride * 6 * 4), 0x00020000);
+    // (CS: 3 + 3 color_sets planes, below 2^31 bytes — pcl_cloud_sets_bytes)
+    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, CS ? (int)(a.stride * (3 + 3 * a.color_sets) * 4) : (int)(a.stride * 6 * 4),
+                                                                   0x00020000);
     const int plane = (int)a.stride * 4;
+    int cplane = 3 * plane;                       // byte offset of the first colour plane (CS: of this block's colour set), wave-uniform
+    if constexpr (CS) cplane = (int)(3u + 3u * (unsigned)__builtin_amdgcn_readfirstlane((int)(a.poses + pose0)->cset)) * plane;
     __amdgpu_buffer_rsrc_t zb = __amdgpu_buffer_rsrc_t();
     if constexpr (VIS == 2) zb = __builtin_amdgcn_make_buffer_rsrc((void*)a.zbuf, 0, (int)((unsigned)a.B * (unsigned)(a.dgrid.last + 1) * 4u), 0x00020000);
 
@@ -149,8 +157,9 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a, const PclFus
         int j0 = min(base + (int)threadIdx.x, last), j1 = min(base + PCL_BLOCK + (int)threadIdx.x, last);
 #pragma unroll
         for (int k = 0; k < 6; k++) {
-            dst[0][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j0 * 4, k * plane, 0));
-            dst[1][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j1 * 4, k * plane, 0));
+            const int soff = (CS && k >= 3) ? cplane + (k - 3) * plane : k * plane;
+            dst[0][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j0 * 4, soff, 0));
+            dst[1][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j1 * 4, soff, 0));
         }
     };
     auto eval_step = [&](int base, const float (&src)[2][6]) {
@@ -313,6 +322,20 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_kernel(PclLossArgs a
     pcl_loss_body<G, true, 0, FMT, true>(a, f);
 }
 
+// the GD chain over a cloud with per-image colour sets (loss + gradient, no visibility mask): own kernel names, so that the instances
+// above keep theirs (tools/roof_mix.py, profiles/ look them up)
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_sets_kernel(PclLossArgs a)
+{
+    pcl_loss_body<G, true, 0, FMT, false, true>(a, PclFuseArgs{});
+}
+
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_sets_kernel(PclLossArgs a, PclFuseArgs f)
+{
+    pcl_loss_body<G, true, 0, FMT, true, true>(a, f);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launch planning (shared with the GD loop)
 
@@ -324,6 +347,20 @@ struct PclPlan {
     int seg_len;
     int steps_base, steps_rem;
 };
+
+// contiguous chunk runs per XCD (PCL_XCD_RUNS, experiments) of a launch of nchunks chunks and nblocks blocks -> chunks per run.  Default: every
+// chunk its own run (chunk c on XCD c mod 8) when the launch takes several rounds of resident blocks — the XCDs then finish together; ONE run
+// per XCD when all blocks are resident at once (the shipped 167k-point / 6-candidate shape: 984 one-step blocks): nothing to balance there,
+// and with its chunks side by side an XCD touches an eighth of the panorama instead of all of it (loss kernel 9.5 vs 10.8 us).  Otherwise the
+// largest divisor of the XCD's chunk count not above the target.
+static int pcl_xcd_seg_len(int nchunks, int64_t nblocks)
+{
+    static const int runs_env = PCL_KNOB(XCD_RUNS, 0);
+    int cpx = nchunks / 8, runs = runs_env < 1 || runs_env > cpx ? cpx : runs_env;
+    if (runs_env < 1 && nblocks <= 1024) runs = 1;       // 256 CUs x 4 resident 256-thread blocks
+    while (cpx % runs) runs--;
+    return cpx / runs;
+}
 
 static PclPlan pcl_plan(int64_t n, int B)
 {
@@ -358,28 +395,33 @@ static PclPlan pcl_plan(int64_t n, int B)
     p.nchunks = (int)want;
     p.steps_base = (int)(steps / want);
     p.steps_rem = (int)(steps % want);
-    // contiguous chunk runs per XCD (PCL_XCD_RUNS, experiments).  Default: every chunk its own run (chunk c on XCD c mod 8)
-    // when the launch takes several rounds of resident blocks — the XCDs then finish together; ONE run per XCD when all blocks
-    // are resident at once (the shipped 167k-point / 6-candidate shape: 984 one-step blocks): nothing to balance there, and
-    // with its chunks side by side an XCD touches an eighth of the panorama instead of all of it (loss kernel 9.5 vs 10.8 us).
-    // Otherwise the largest divisor of the XCD's chunk count not above the target.
-    static const int runs_env = PCL_KNOB(XCD_RUNS, 0);
-    int cpx = p.nchunks / 8, runs = runs_env < 1 || runs_env > cpx ? cpx : runs_env;
-    if (runs_env < 1 && (int64_t)p.nchunks * p.ngroups <= 1024) runs = 1;       // 256 CUs x 4 resident 256-thread blocks
-    while (cpx % runs) runs--;
-    p.seg_len = cpx / runs;
+    p.seg_len = pcl_xcd_seg_len(p.nchunks, (int64_t)p.nchunks * p.ngroups);
     return p;
 }
 
-size_t pcl_partials_bytes(int64_t n, int B)
+// The plan of a launch whose B poses are `sets` images of B / sets candidates, each image reading its own colour set: the SINGLE-IMAGE
+// plan pcl_plan(n, B / sets) — its chunks, poses per block and steps per chunk — for all of them.  Every (pose, chunk) partial sum and
+// the epilogue's reduction over the chunks are then those of the one-image call with that image's colours, bit for bit (the plan of
+// the whole launch would cut the cloud into other chunks: 120k points, 3 images x 8 candidates, 88 chunks instead of 240).  Only the
+// XCD runs are chosen for the whole launch (scheduling).  sets <= 1: pcl_plan(n, B).
+static PclPlan pcl_plan_sets(int64_t n, int B, int sets)
 {
-    PclPlan p = pcl_plan(n, B);
+    if (sets <= 1) return pcl_plan(n, B);
+    PclPlan p = pcl_plan(n, B / sets);
+    p.ngroups = B / p.G;
+    p.seg_len = pcl_xcd_seg_len(p.nchunks, (int64_t)p.nchunks * p.ngroups);
+    return p;
+}
+
+size_t pcl_partials_bytes(int64_t n, int B, int sets)
+{
+    PclPlan p = pcl_plan_sets(n, B, sets);
     return (size_t)p.nchunks * (size_t)B * PCL_NACC * sizeof(float);
 }
 
-int pcl_plan_nchunks(int64_t n, int B) { return pcl_plan(n, B).nchunks; }
-int pcl_plan_nblocks(int64_t n, int B) { PclPlan p = pcl_plan(n, B); return p.nchunks * p.ngroups; }
-int pcl_plan_G(int64_t n, int B) { return pcl_plan(n, B).G; }
+int pcl_plan_nchunks(int64_t n, int B, int sets) { return pcl_plan_sets(n, B, sets).nchunks; }
+int pcl_plan_nblocks(int64_t n, int B, int sets) { PclPlan p = pcl_plan_sets(n, B, sets); return p.nchunks * p.ngroups; }
+int pcl_plan_G(int64_t n, int B, int sets) { return pcl_plan_sets(n, B, sets).G; }
 
 // the same decomposition for a kernel with its own notion of a pose group (pcl_trim.hip: one block = one chunk x one
 // (translation, rotation class) slot): chunks, XCD runs and balanced steps as for `ngroups` groups of two poses
@@ -442,16 +484,34 @@ static void pcl_launch_fused(const PclLossArgs& a, const PclFuseArgs& f, int G, 
     else hipLaunchKernelGGL((pcl_loss_fused_kernel<1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, f);
 }
 
+template <int FMT>
+static void pcl_launch_sets(const PclLossArgs& a, const PclFuseArgs* f, int G, int nblk, hipStream_t s)
+{
+    if (f) {
+        if (G == 4) hipLaunchKernelGGL((pcl_loss_fused_sets_kernel<4, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, *f);
+        else if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_sets_kernel<2, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, *f);
+        else hipLaunchKernelGGL((pcl_loss_fused_sets_kernel<1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, *f);
+    } else {
+        if (G == 4) hipLaunchKernelGGL((pcl_loss_sets_kernel<4, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
+        else if (G == 2) hipLaunchKernelGGL((pcl_loss_sets_kernel<2, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
+        else hipLaunchKernelGGL((pcl_loss_sets_kernel<1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
+    }
+}
+
 // `fuse` (nullable): finish the previous GD iteration in the prologue of every block (gradient pass without visibility only)
 // `depth` (nullable): the poses' z-buffers and their grid — the scatter-min depth mask looked up inside the kernel (VIS == 2)
+// `color_sets` > 1: the cloud holds that many colour sets (pcl_cloud_pack_sets), the poses are color_sets images of B / color_sets
+// candidates, and each pose record names its set (PclPoseRec.cset): the single-image plan (pcl_plan_sets), gradient pass only
 int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses,
                     int B, bool grad, const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse,
-                    const PclDepthLook* depth)
+                    const PclDepthLook* depth, int color_sets)
 {
     if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;
     // 32-bit buffer addressing: 6 planes x 4 B x n must stay below 4 GiB, the padded panorama below 2 GiB
     if (n > PCL_MAX_POINTS || (int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
-    PclPlan p = pcl_plan(n, B);
+    const bool sets = color_sets > 1;
+    if (sets && (B % color_sets || !grad || visible || depth || pcl_cloud_sets_bytes(n, color_sets) == 0)) return PCL_EINVAL;
+    PclPlan p = pcl_plan_sets(n, B, color_sets);
     PclLossArgs a;
     a.cloud = cloud; a.n = n; a.stride = pcl_cloud_stride(n);
     a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
@@ -470,6 +530,7 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
         }
     }
     a.nchunks = p.nchunks; a.ngroups = p.ngroups; a.seg_len = p.seg_len; a.flip = flip & 1; a.steps_base = p.steps_base; a.steps_rem = p.steps_rem;
+    a.color_sets = sets ? color_sets : 1;
     // bit 1 of `flip`: the poses of this launch read several panoramas (pcl_gd_hyper.images > 1) — the XCDs split the pose groups
     // instead of the chunks when they divide evenly.  Measured per iteration (tools/iter_latency.py, ITER_IMAGES=8): 167k points x 48
     // candidates of 8 images 64.0 -> 49.8 us (poses all over the room) / 51.3 -> 41.7 us (near the ground truth), 1M points x 256
@@ -479,6 +540,13 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
     a.xcd_groups = ((flip & 2) != 0 || xg_env == 1) && xg_env != 0 && p.ngroups % 8 == 0 ? 1 : 0;
     int nblk = p.nchunks * p.ngroups;
     const int vis = depth ? 2 : visible != nullptr ? 1 : 0;
+    if (sets) {
+        if (pano_format == PCL_PANO_U8) pcl_launch_sets<PCL_PANO_U8>(a, fuse, p.G, nblk, s);
+        else if (pano_format == PCL_PANO_F16) pcl_launch_sets<PCL_PANO_F16>(a, fuse, p.G, nblk, s);
+        else pcl_launch_sets<PCL_PANO_F32>(a, fuse, p.G, nblk, s);
+        PCL_LAUNCH_CHECK();
+        return 0;
+    }
     if (fuse) {
         if (!grad || vis) return PCL_EINVAL;
         if (pano_format == PCL_PANO_U8) pcl_launch_fused<PCL_PANO_U8>(a, *fuse, p.G, nblk, s);

@@ -63,6 +63,54 @@ extern "C" int pcl_cloud_pack(const float* xyz, const float* rgb, const int64_t*
     return 0;
 }
 
+// ---- per-image colour sets (ABI 10): planes x, y, z, then nsets x (-r, -g, -b), each pcl_cloud_stride(n) floats.  Set k is the
+// scalar plane offset (3 + 3 k) x plane of the one buffer resource the kernels already build; the whole cloud stays below 2^31 bytes
+// so that every plane offset is a non-negative int.  One set is the 6-plane cloud of pcl_cloud_pack (and its limits).
+extern "C" size_t pcl_cloud_sets_bytes(int64_t n, int nsets)
+{
+    if (n <= 0 || n > PCL_MAX_POINTS || nsets <= 0) return 0;
+    if (nsets == 1) return pcl_cloud_bytes(n);
+    const int64_t bytes = (int64_t)pcl_cloud_stride(n) * 4 * (3 + 3 * (int64_t)nsets);
+    return bytes < ((int64_t)1 << 31) ? (size_t)bytes : 0;
+}
+
+#define PCL_PACK_SETS 16        // colour sets per launch of the set-packing kernel (their addresses travel as kernel arguments)
+struct PclRgbList { const float* p[PCL_PACK_SETS]; };
+
+// the xyz planes (k0 == 0 only) and the colour planes of sets [k0, k0 + m): every thread one packed slot
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_cloud_pack_sets_kernel(const float* __restrict__ xyz, PclRgbList rgb, int k0, int m,
+                                                                        const int64_t* __restrict__ order, int64_t n, int64_t stride,
+                                                                        float* __restrict__ cloud)
+{
+    int64_t i = (int64_t)blockIdx.x * PCL_BLOCK + threadIdx.x;
+    if (i >= stride) return;
+    const int64_t j = i < n ? (order ? order[i] : i) : 0;
+    if (k0 == 0)
+        for (int c = 0; c < 3; c++) cloud[c * stride + i] = i < n ? xyz[3 * j + c] : 0.f;
+    for (int k = 0; k < m; k++)
+        for (int c = 0; c < 3; c++) cloud[(3 + 3 * (int64_t)(k0 + k) + c) * stride + i] = i < n ? -rgb.p[k][3 * j + c] : 0.f;   // -rgb, as pcl_cloud_pack
+}
+
+extern "C" int pcl_cloud_pack_sets(const float* xyz, const float* const* rgb_host, int nsets, const int64_t* order, int64_t n, float* cloud,
+                                   void* stream)
+{
+    if (!xyz || !rgb_host || !cloud || n <= 0 || nsets <= 0) return PCL_EINVAL;
+    if (pcl_cloud_sets_bytes(n, nsets) == 0) return PCL_EINVAL;
+    for (int k = 0; k < nsets; k++)
+        if (!rgb_host[k]) return PCL_EINVAL;
+    if (nsets == 1) return pcl_cloud_pack(xyz, rgb_host[0], order, n, cloud, stream);
+    const int64_t stride = pcl_cloud_stride(n);
+    for (int k0 = 0; k0 < nsets; k0 += PCL_PACK_SETS) {
+        const int m = nsets - k0 < PCL_PACK_SETS ? nsets - k0 : PCL_PACK_SETS;
+        PclRgbList l;
+        for (int k = 0; k < PCL_PACK_SETS; k++) l.p[k] = k < m ? rgb_host[k0 + k] : nullptr;
+        hipLaunchKernelGGL(pcl_cloud_pack_sets_kernel, dim3((unsigned)(stride / PCL_BLOCK)), dim3(PCL_BLOCK), 0, (hipStream_t)stream, xyz, l, k0, m,
+                           order, n, stride, cloud);
+        PCL_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 __device__ inline uint64_t pcl_spread21(uint32_t v)
 {
     uint64_t x = v & 0x1fffffu;

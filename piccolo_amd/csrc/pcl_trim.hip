@@ -271,8 +271,10 @@ __device__ __forceinline__ void pcl_issue_taps_row<PCL_PANO_F32>(__amdgpu_buffer
 // (The U8P variant allocates 129 VGPRs — three waves per SIMD where the row-major one, 109, runs four.  Bounding it to four
 //  (__launch_bounds__(PCL_BLOCK, 4): 127 VGPRs, three dwords spilled outside the loop) was measured A/B on one box, tables
 //  identical: 0.834 -> 0.874 ms at 167k points, 3.336 -> 3.316 ms at 1M — more waves only queue at the texture unit.)
-template <int FMT>
-__global__ void __launch_bounds__(PCL_BLOCK) pcl_trim_kernel(PclTrimArgs a)
+// CS: the cloud holds one colour set per image (pcl_cloud_pack_sets, nimages sets) and the block reads its image's: a scalar plane offset
+// on the same buffer resource (a template parameter: pcl_trim_kernel's instances compile to the loop they always had)
+template <int FMT, bool CS>
+__device__ __forceinline__ void pcl_trim_body(const PclTrimArgs& a)
 {
     // same XCD-aware mapping as pcl_loss_kernel: blocks b and b + 8 share an XCD; within an XCD the slot varies fastest, so the
     // blocks resident together read the same cloud chunk; consecutive slots are neighbouring translations of one class
@@ -319,8 +321,10 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_trim_kernel(PclTrimArgs a)
         ? __builtin_amdgcn_make_buffer_rsrc((void*)a.pano[image], 0, (int)((size_t)((a.dims.H + 3) >> 1) * (size_t)a.dims.Wp * 8), 0x00020000)
         : FMT == PCL_PANO_U8V ? pcl_tex_rsrc(a.pano[image], a.dims.H, a.dims.W, 8)
         : pcl_tex_rsrc(a.pano[image], a.dims.H, a.dims.W, pcl_texel_bytes(FMT));
-    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, (int)(a.stride * 6 * 4), 0x00020000);
+    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, CS ? (int)(a.stride * (3 + 3 * a.nimages) * 4) : (int)(a.stride * 6 * 4),
+                                                                   0x00020000);
     const int plane = (int)a.stride * 4;
+    const int cplane = CS ? (3 + 3 * image) * plane : 3 * plane;          // byte offset of the block's first colour plane
 
     f2 acc[PCL_TRIM_Y][PCL_NACC];          // only [y][0] is used by the forward-only sampler
     int count[PCL_TRIM_Y];
@@ -338,8 +342,9 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_trim_kernel(PclTrimArgs a)
         int j0 = min(base + (int)threadIdx.x, last), j1 = min(base + PCL_BLOCK + (int)threadIdx.x, last);
 #pragma unroll
         for (int k = 0; k < 6; k++) {
-            dst[0][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j0 * 4, k * plane, 0));
-            dst[1][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j1 * 4, k * plane, 0));
+            const int soff = (CS && k >= 3) ? cplane + (k - 3) * plane : k * plane;
+            dst[0][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j0 * 4, soff, 0));
+            dst[1][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j1 * 4, soff, 0));
         }
     };
     const float inv_two_pi = 0.15915494309189533577f;
@@ -445,6 +450,19 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_trim_kernel(PclTrimArgs a)
     }
     __syncthreads();
     if (threadIdx.x < PCL_NACC) out[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+template <int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_trim_kernel(PclTrimArgs a)
+{
+    pcl_trim_body<FMT, false>(a);
+}
+
+// per-image colour sets (image i reads set i): own kernel names, the instances above keep theirs
+template <int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_trim_sets_kernel(PclTrimArgs a)
+{
+    pcl_trim_body<FMT, true>(a);
 }
 
 // loss_table[k][rot] = sum ||d|| / count over the chunks (fixed order, double): one thread per (slot, yaw)
@@ -673,12 +691,15 @@ extern "C" size_t pcl_trim_loss_images_workspace_bytes(int64_t n, int K, int ngr
     return nimages <= PCL_TRIM_MAX_IMAGES ? trim_workspace_bytes(n, K, ngroups, nimages) : 0;
 }
 
-extern "C" int pcl_trim_loss_images(const float* cloud, int64_t n, const void* const* panos_host, int nimages, int pano_format, int H, int W,
-                                    const float* trans, int K, const float* rot, int R, const void* groups, int ngroups, const void* order,
-                                    float* loss_tables, float* count_tables, void* workspace, size_t workspace_bytes, void* stream)
+// color_sets: 1 = every image reads the cloud's colours (planes 3..5), nimages = image i reads colour set i (pcl_cloud_pack_sets)
+extern "C" int pcl_trim_loss_images_sets(const float* cloud, int64_t n, int color_sets, const void* const* panos_host, int nimages, int pano_format,
+                                         int H, int W, const float* trans, int K, const float* rot, int R, const void* groups, int ngroups,
+                                         const void* order, float* loss_tables, float* count_tables, void* workspace, size_t workspace_bytes,
+                                         void* stream)
 {
     if (!cloud || !panos_host || !trans || !rot || !groups || !loss_tables || !workspace) return PCL_EINVAL;
     if (nimages <= 0 || nimages > PCL_TRIM_MAX_IMAGES) return PCL_EINVAL;
+    if (color_sets != 1 && (color_sets != nimages || pcl_cloud_sets_bytes(n, color_sets) == 0)) return PCL_EINVAL;
     for (int i = 0; i < nimages; i++)
         if (!panos_host[i]) return PCL_EINVAL;
     if (n <= 0 || n > PCL_MAX_POINTS || K <= 0 || R <= 0 || ngroups <= 0 || ngroups > R || H <= 0 || W <= 0) return PCL_EINVAL;
@@ -717,7 +738,13 @@ extern "C" int pcl_trim_loss_images(const float* cloud, int64_t n, const void* c
     const int64_t nblk = (int64_t)a.nchunks * nslots * nimages;
     if (nblk > 0x7fffffffll) return PCL_EINVAL;
     a.order = (const int*)order;
-    if (pano_format == PCL_PANO_U8P) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_U8P>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
+    if (color_sets > 1) {
+        if (pano_format == PCL_PANO_U8P) hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_U8P>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
+        else if (pano_format == PCL_PANO_U8V) hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_U8V>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
+        else if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_U8>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
+        else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_F16>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
+        else hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_F32>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
+    } else if (pano_format == PCL_PANO_U8P) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_U8P>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
     else if (pano_format == PCL_PANO_U8V) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_U8V>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
     else if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_U8>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
     else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_F16>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
@@ -726,6 +753,14 @@ extern "C" int pcl_trim_loss_images(const float* cloud, int64_t n, const void* c
                        nimages, K, R, hdr, grs, loss_tables, count_tables);
     PCL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int pcl_trim_loss_images(const float* cloud, int64_t n, const void* const* panos_host, int nimages, int pano_format, int H, int W,
+                                    const float* trans, int K, const float* rot, int R, const void* groups, int ngroups, const void* order,
+                                    float* loss_tables, float* count_tables, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return pcl_trim_loss_images_sets(cloud, n, 1, panos_host, nimages, pano_format, H, W, trans, K, rot, R, groups, ngroups, order, loss_tables,
+                                     count_tables, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pcl_trim_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans, int K,

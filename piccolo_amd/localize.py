@@ -292,17 +292,20 @@ def _result_row(t, R, loss, gt_trans, gt_rot, seconds):
 
 
 class _Batcher:
-    """cfg.images_per_launch > 1: query images that share the cloud tensors and the image size are refined in one launch
-    chain (omniloc_batch_images) — at the shipped 6 candidates per image a launch is latency-bound, eight images cost
-    little more than one.  Images whose cloud colours were changed per image (sharpen_color) cannot share a launch and
-    go one by one."""
+    """cfg.images_per_launch > 1: query images that share the cloud's POINTS (the xyz tensor) and the image size are initialised in
+    one set of launches (make_input_images) and refined in one launch chain (omniloc_batch_images) — at the shipped 6 candidates per
+    image a launch is latency-bound, eight images cost little more than one.  Images whose cloud colours were changed per image
+    (sharpen_color: color_mod gives every image its own equalised colours, localize.py:173-179) share the launches too: the group's
+    cloud then holds one colour set per image, and every image's results are those of its own one-image calls, bit for bit.  When
+    every job shares one rgb tensor it is passed as that tensor (the shared-colour path as before).  Grouping by colour sets was
+    measured to beat one image at a time at the shipped and at the cfg-2 shape (tools/color_sets_bench.py)."""
 
     def __init__(self, cfg, size):
         self.cfg, self.size, self.jobs = cfg, size, []
 
     def submit(self, job):
-        if self.jobs and not (job["xyz"] is self.jobs[0]["xyz"] and job["rgb"] is self.jobs[0]["rgb"] and
-                              job["img"].shape == self.jobs[0]["img"].shape and job["img_init"].shape == self.jobs[0]["img_init"].shape):
+        j0 = self.jobs[0] if self.jobs else None
+        if j0 is not None and not (job["xyz"] is j0["xyz"] and job["img"].shape == j0["img"].shape and job["img_init"].shape == j0["img_init"].shape):
             self.flush()
         self.jobs.append(job)
         if len(self.jobs) >= self.size:
@@ -313,9 +316,11 @@ class _Batcher:
         if not jobs:
             return
         cfg = self.cfg
+        # one tensor when the group shares its colours, else one colour set per image
+        rgb = jobs[0]["rgb"] if all(j["rgb"] is jobs[0]["rgb"] for j in jobs) else [j["rgb"] for j in jobs]
         torch.cuda.synchronize()
         t0 = time.time()
-        starts = make_input_images([j["img_init"] for j in jobs], jobs[0]["xyz"], jobs[0]["rgb"], getattr(cfg, "num_input", 6), get_init_dict(cfg),
+        starts = make_input_images([j["img_init"] for j in jobs], jobs[0]["xyz"], rgb, getattr(cfg, "num_input", 6), get_init_dict(cfg),
                                    getattr(cfg, "criterion", "histogram"), getattr(cfg, "num_intermediate", 20))
         for j, (tr, ro) in zip(jobs, starts):
             j["trans"], j["rot"] = tr, ro
@@ -325,7 +330,7 @@ class _Batcher:
             j = jobs[0]
             results = [refine_image(j["img"], j["xyz"], j["rgb"], j["trans"], j["rot"], cfg)]
         else:
-            results = omniloc_batch_images([j["img"] for j in jobs], jobs[0]["xyz"], jobs[0]["rgb"], [j["trans"] for j in jobs],
+            results = omniloc_batch_images([j["img"] for j in jobs], jobs[0]["xyz"], rgb, [j["trans"] for j in jobs],
                                            [j["rot"] for j in jobs], cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
         share = (time.time() - t0) / len(jobs)               # the group's wall time, shared equally (localize.py:208,222-223 per image)
         for j, (t, R, loss) in zip(jobs, results):

@@ -111,6 +111,39 @@ def packed_cloud(xyz, rgb):
     return _cached("cloud", (xyz, rgb), make)
 
 
+def packed_cloud_sets(xyz, rgbs):
+    """ONE packed cloud holding a colour set per entry of `rgbs` (ops.Cloud.with_color_sets): set i is packed_cloud(xyz, rgbs[i])'s colours,
+    in the room's one Morton order (cached per xyz, as for packed_cloud)."""
+    def make():
+        order = _cache.get("order", (None,) + _key(xyz), (xyz,))
+        if order is not None:
+            return ops.Cloud.with_color_sets(xyz, rgbs, order=order)
+        c = ops.Cloud.with_color_sets(xyz, rgbs)
+        if c.order is not None:
+            _cache.put("order", (None,) + _key(xyz), (xyz,), c.order)
+        return c
+    return _cached("cloud", (xyz,) + tuple(rgbs), make)
+
+
+def color_set_groups(n, I, cap=None):
+    """How per-image colour sets split I images of an n-point cloud: group sizes of at most the addressing limit (ops.max_color_sets), the
+    32 images a trim / histogram launch takes and `cap`."""
+    cap = max(1, min(ops.max_color_sets(n), ops.TRIM_MAX_IMAGES, ops.HIST_MAX_IMAGES, cap if cap is not None else I))
+    return [min(cap, I - i0) for i0 in range(0, I, cap)]
+
+
+def shared_rgb(rgb):
+    """`rgb` of the multi-image entry points: one (N, 3) tensor, or a list of one per image.  A list whose entries are all the same tensor
+    is that tensor (the shared-colour path, bit for bit).  -> the tensor, or the list"""
+    if isinstance(rgb, (list, tuple)):
+        if len(rgb) == 0:
+            raise ValueError("rgb: an empty list of colour sets")
+        if all(r is rgb[0] for r in rgb):
+            return rgb[0]
+        return list(rgb)
+    return rgb
+
+
 def packed_pano(img, many_poses=False, n_points=None):
     """Packed panorama of `img`, cached per tensor.  RGBA8 texels (half the footprint of the fp16-level default) when the launch
     evaluates hundreds of candidate poses all over the room (`many_poses`, trim_input_loss: with 1800 poses the fp16 texture
@@ -163,9 +196,10 @@ GRAPH_POINT_POSES = 16_000_000         # use graph replay when points x candidat
 
 def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None):
     """Run the on-device GD for the rows of trans / rot and return the GradientDescent object (read gd.result() / gd.winner()).
-    `panos`: one packed panorama per query image; the B rows split evenly over them, image by image.
+    `panos`: one packed panorama per query image; the B rows split evenly over them, image by image.  `rgb`: one (N, 3) tensor, or a list
+    of one per query image (per-image colour sets: image i's candidates read set i, and the chain runs the single-image plan).
     The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape."""
-    cloud = packed_cloud(xyz, rgb)
+    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb)
     trans, rot = ops._dev(trans).reshape(-1, 3), ops._dev(rot).reshape(-1, 3)
     B = int(trans.shape[0])
     p0 = panos[0]
@@ -191,14 +225,15 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None):
         # One engine (state, workspace, captured graph) per POINT SET and launch shape.  The colours may change with every query
         # image (color_mod / match_color give each image its own rgb): the engine owns a private copy of the packed cloud whose
         # address the captured graph holds, and a cloud with other colours is copied into it (24 bytes per point on the device)
-        # instead of capturing a new graph per image.
+        # instead of capturing a new graph per image.  The same for a cloud of per-image colour sets: one engine per (point set, shape,
+        # number of sets), the new sets copied into its buffer.
         def make_private():
             g = make(ops.Cloud.private_copy(cloud), ops._dev(box).reshape(6).clone())     # (its own box buffer: updated in place below)
             g._cloud_src = weakref.ref(cloud)                # the copy just made IS this cloud: nothing to copy on first use
             g._box_src, g._fresh = box, True
             return g
         # (one or two launches per iteration is frozen into a captured graph: part of the key)
-        gd = _cached("gd", (xyz,), make_private, sub=(B, len(panos), p0.H, p0.W, p0.fmt, fuse) + hyper)
+        gd = _cached("gd", (xyz,), make_private, sub=(B, len(panos), p0.H, p0.W, p0.fmt, fuse, cloud.color_sets) + hyper)
         fresh, gd._fresh = gd._fresh, False                  # (a new engine was initialised with these very poses)
         if gd._cloud_src() is not cloud:                     # weak: the engine must not keep packed clouds of past images alive
             gd.cloud.data.copy_(cloud.data)
@@ -329,10 +364,25 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     its own Adam / scheduler state, so every image gets the result omniloc_batch would give it (bit for bit when the
     cloud is cut into the same chunks, else up to the summation order of the partial sums); at 32 candidates per image,
     8 images per launch are ~25 % faster than 8 separate refinements.  Returns a list of [t, R, loss].
-    batch_mode=False gives every candidate omniloc's SEQUENTIAL semantics instead (what omniloc_all computes per image)."""
+    batch_mode=False gives every candidate omniloc's SEQUENTIAL semantics instead (what omniloc_all computes per image).
+    rgb: one (N, 3) tensor, or a LIST of one per image (per-image colours, e.g. color_mod's): the cloud then holds a colour set per image
+    and the chain runs the single-image plan, so image i's result is omniloc_batch(imgs[i], xyz, rgb[i], ...)'s bit for bit.  Images
+    beyond the colour-set addressing limit go in further groups; with the depth mask (no colour-set kernel) one image per chain."""
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     I = len(imgs)
+    rgb = shared_rgb(rgb)
+    if isinstance(rgb, list):
+        if len(rgb) != I:
+            raise ValueError("omniloc_batch_images: %d colour sets for %d images" % (len(rgb), I))
+        sizes = [1] * I if bool(_cfg(cfg, "depth_mask", False)) else color_set_groups(int(xyz.shape[0]), I)
+        if len(sizes) > 1:
+            out, i0 = [], 0
+            for m in sizes:
+                out += omniloc_batch_images(imgs[i0:i0 + m], xyz, rgb[i0:i0 + m] if m > 1 else rgb[i0], input_trans_list[i0:i0 + m],
+                                            input_rot_list[i0:i0 + m], cfg, scalar_summaries, batch_mode)
+                i0 += m
+            return out
     B = int(input_trans_list[0].shape[0])
     fmt = ops.refine_texels(xyz.shape[0], imgs[0].shape[0], imgs[0].shape[1])
     panos = [packed_pano(im, n_points=xyz.shape[0]) if I <= 8 else ops.Pano(im, fmt=fmt if ops._known_levels(im) else "auto") for im in imgs]

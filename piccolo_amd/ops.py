@@ -67,7 +67,10 @@ def _bytes(nbytes):
 class Cloud:
     """Point cloud packed for the loss kernel: 6 SoA planes, by default in Morton order of xyz.
 
-    `order` maps packed slot -> original point index (None if the original order was kept)."""
+    `order` maps packed slot -> original point index (None if the original order was kept).  `color_sets`: how many colourings of the
+    points the buffer holds (1 here; Cloud.with_color_sets packs several)."""
+
+    color_sets = 1
 
     def __init__(self, xyz, rgb, sort=True, order=None):
         """`order`: a Morton order computed before for the same xyz (Cloud(...).order): skips the sort, e.g. when only
@@ -100,8 +103,56 @@ class Cloud:
         must keep one cloud address while the colours change from image to image."""
         c = cls.__new__(cls)
         c.n, c.order, c.xyz = other.n, other.order, other.xyz
+        c.color_sets = other.color_sets
         c.data = other.data.clone()
         return c
+
+    @classmethod
+    def with_color_sets(cls, xyz, rgbs, order=None, sort=True):
+        """ONE point set with several colourings (pcl_cloud_pack_sets): planes x, y, z, then (-r, -g, -b) per entry of `rgbs` (a list of
+        (N, 3) tensors — e.g. color_mod's per-image colours).  Colour set i is what Cloud(xyz, rgbs[i], order=...) packs, in the same point
+        order.  The kernels that take such a cloud (trim_loss_tables, hist_trim_scores_images, GradientDescent) let query image i read
+        set i.  Raises ValueError past the 32-bit addressing limit (max_color_sets): split the images into groups."""
+        lib = _lib.load()
+        xyz = _dev(xyz)
+        rgbs = [_dev(r) for r in rgbs]
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or not rgbs or any(r.shape != xyz.shape for r in rgbs):
+            raise ValueError("xyz and every rgb must be (N, 3)")
+        c = cls.__new__(cls)
+        c.n = int(xyz.shape[0])
+        if c.n <= 0:
+            raise ValueError("empty point cloud")
+        nbytes = lib.pcl_cloud_sets_bytes(c.n, len(rgbs))
+        if nbytes == 0:
+            raise ValueError("%d colour sets of %d points exceed the cloud's 32-bit addressing (at most %d)" % (len(rgbs), c.n, max_color_sets(c.n)))
+        c.order = None
+        if order is not None:
+            if order.dtype != torch.int64 or order.numel() != c.n or not order.is_cuda:
+                raise ValueError("order must be a CUDA int64 tensor with one entry per point")
+            c.order = order
+        elif sort and c.n > 1:
+            c.order = torch.empty(c.n, dtype=torch.int64, device=xyz.device)
+            nws = lib.pcl_cloud_order_workspace_bytes(c.n)
+            ws = _bytes(nws)
+            _lib.check(lib.pcl_cloud_order(_ptr(xyz), c.n, _ptr(c.order), _ptr(ws), nws, _stream()), "pcl_cloud_order")
+        c.color_sets = len(rgbs)
+        c.data = _bytes(nbytes)
+        arr = (ctypes.c_void_p * len(rgbs))(*[r.data_ptr() for r in rgbs])
+        _lib.check(lib.pcl_cloud_pack_sets(_ptr(xyz), arr, len(rgbs), _ptr(c.order), c.n, _ptr(c.data), _stream()), "pcl_cloud_pack_sets")
+        c.xyz = xyz
+        return c
+
+
+def max_color_sets(n):
+    """The most colour sets a cloud of n points can hold (pcl_cloud_sets_bytes: 3 + 3 k planes below 2^31 bytes); 0 if n is out of range."""
+    lib = _lib.load()
+    if lib.pcl_cloud_sets_bytes(n, 1) == 0:
+        return 0
+    plane = 4 * lib.pcl_cloud_stride(n)
+    k = max(1, ((1 << 31) - 1) // plane // 3 - 1)
+    while k > 1 and lib.pcl_cloud_sets_bytes(n, k) == 0:
+        k -= 1
+    return k
 
 
 class Pano:
@@ -349,13 +400,29 @@ TRIM_MAX_IMAGES = 32       # pcl_trim_loss_images: query images per launch
 
 def trim_loss_tables(cloud, panos, trans, groups, return_count=False, order=None):
     """trim_loss_table for several query images of one room in ONE launch: (I, K, R) float GPU tensor; image i's table has the
-    bits of trim_loss_table(cloud, panos[i], ...) (same chunks of the cloud).  panos: list of Pano of one size / texel format."""
+    bits of trim_loss_table(cloud, panos[i], ...) (same chunks of the cloud).  panos: list of Pano of one size / texel format.
+    A cloud with colour sets (Cloud.with_color_sets, one per image): image i reads set i — its table is trim_loss_table over
+    Cloud(xyz, rgbs[i]), bit for bit."""
     lib = _lib.load()
     trans = _dev(trans).reshape(-1, 3)
     K, I = int(trans.shape[0]), len(panos)
     p0 = panos[0]
     if any((p.H, p.W, p.fmt) != (p0.H, p0.W, p0.fmt) for p in panos):
         raise ValueError("all panoramas of a launch must share size and texel format")
+    if cloud.color_sets > 1:
+        if cloud.color_sets != I:
+            raise ValueError("a cloud of %d colour sets for %d images" % (cloud.color_sets, I))
+        if I > TRIM_MAX_IMAGES:
+            raise ValueError("trim_loss_tables: at most %d images per call with colour sets" % TRIM_MAX_IMAGES)
+        table = torch.empty(I, K, groups.R, dtype=F32, device=trans.device)
+        count = torch.empty(I, K, groups.R, dtype=F32, device=trans.device) if return_count else None
+        nws = lib.pcl_trim_loss_images_workspace_bytes(cloud.n, K, groups.ngroups, I)
+        ws = _bytes(nws)
+        arr = (ctypes.c_void_p * I)(*[p.data.data_ptr() for p in panos])
+        _lib.check(lib.pcl_trim_loss_images_sets(_ptr(cloud.data), cloud.n, I, arr, I, p0.fmt, p0.H, p0.W, _ptr(trans), K, _ptr(groups.rot),
+                                                 groups.R, _ptr(groups.data), groups.ngroups, _ptr(order.data) if order is not None else None,
+                                                 _ptr(table), _ptr(count), _ptr(ws), nws, _stream()), "pcl_trim_loss_images_sets")
+        return (table, count) if return_count else table
     table = torch.empty(I, K, groups.R, dtype=F32, device=trans.device)
     count = torch.empty(I, K, groups.R, dtype=F32, device=trans.device) if return_count else None
     for i0 in range(0, I, TRIM_MAX_IMAGES):
@@ -465,11 +532,15 @@ HIST_MAX_IMAGES = 32       # pcl_hist_trim_scores_images: query images per call
 HIST_BATCH_BYTES = 8e9
 
 
-def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w):
+def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w, splat=False):
     """hist_trim_scores for several query images of one room in ONE set of launches: imgs = list of I (H, W, 3) float GPU images of
     one size, trans / rot (I, K, 3): image i's K candidates.  -> (I, K) scores, row i what hist_trim_scores(imgs[i], ...) returns
     (bit for bit: same keys, same integer counts, one carry-over chain per image).  Images go through in groups that keep the
-    point lists within ~8 GB."""
+    point lists within ~8 GB.  A cloud with colour sets (Cloud.with_color_sets, one per image): image i's candidates are rendered
+    with set i, all images in one call.  splat=True: the z-buffer splat path on purpose (its small workspace selects it, as
+    hist_trim_scores' flag), on either kind of cloud."""
+    if cloud.color_sets > 1:
+        return _hist_trim_scores_sets(imgs, cloud, trans, rot, num_split_h, num_split_w, splat)
     lib = _lib.load()
     imgs = [_dev(im) for im in imgs]
     trans, rot = _dev(trans), _dev(rot)
@@ -483,7 +554,11 @@ def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w):
     nproj = torch.empty(I * K, nblk, dtype=torch.int32, device=dev)
     nimg = torch.empty(I, nblk, dtype=torch.int32, device=dev)
     scores = torch.empty(I, K, dtype=F32, device=dev)
-    per_image = lib.pcl_hist_trim_images_workspace_bytes(cloud.n, 1, K, H, W, num_split_h, num_split_w)
+    if splat:                  # n = 0: the z-buffer splat path's workspace (pcl_hist_trim_images_sets_workspace_bytes)
+        size_of = lambda m: lib.pcl_hist_trim_images_sets_workspace_bytes(0, 1, m, K, H, W, num_split_h, num_split_w)   # noqa: E731
+    else:
+        size_of = lambda m: lib.pcl_hist_trim_images_workspace_bytes(cloud.n, m, K, H, W, num_split_h, num_split_w)      # noqa: E731
+    per_image = size_of(1)
     if per_image == 0:
         raise ValueError("hist_trim_scores_images: need num_split_h >= 3 and blocks of at least one pixel")
     group = max(1, min(HIST_MAX_IMAGES, I, int(HIST_BATCH_BYTES // per_image)))
@@ -491,7 +566,7 @@ def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w):
     i0 = 0
     while i0 < I:
         m = min(group, I - i0)
-        nws = lib.pcl_hist_trim_images_workspace_bytes(cloud.n, m, K, H, W, num_split_h, num_split_w)
+        nws = size_of(m)
         try:
             ws = _bytes(nws)
         except torch.cuda.OutOfMemoryError:
@@ -500,7 +575,7 @@ def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w):
             if group > 1:
                 group = (group + 1) // 2
                 continue
-            scores[i0] = hist_trim_scores(imgs[i0], cloud, trans[i0], rot[i0], num_split_h, num_split_w)
+            scores[i0] = hist_trim_scores(imgs[i0], cloud, trans[i0], rot[i0], num_split_h, num_split_w, splat=splat)
             i0 += 1
             continue
         arr = (ctypes.c_void_p * m)(*[im.data_ptr() for im in imgs[i0:i0 + m]])
@@ -510,6 +585,41 @@ def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w):
         _lib.check(lib.pcl_hist_trim_reduce_images(_ptr(inter[i0 * K:]), _ptr(nproj[i0 * K:]), _ptr(nimg[i0:]), m, K, num_split_h, num_split_w,
                                                    _ptr(scores[i0:]), _stream()), "pcl_hist_trim_reduce_images")
         i0 += m
+    return scores
+
+
+def _hist_trim_scores_sets(imgs, cloud, trans, rot, num_split_h, num_split_w, splat):
+    """hist_trim_scores_images over a cloud of per-image colour sets: one call (pcl_hist_trim_scores_images_sets) for all images."""
+    lib = _lib.load()
+    imgs = [_dev(im) for im in imgs]
+    trans, rot = _dev(trans), _dev(rot)
+    I, K = int(trans.shape[0]), int(trans.shape[1])
+    H, W = int(imgs[0].shape[0]), int(imgs[0].shape[1])
+    if len(imgs) != I or any(tuple(im.shape) != (H, W, 3) or not im.is_contiguous() for im in imgs):
+        raise ValueError("hist_trim_scores_images: one contiguous (H, W, 3) image per row of candidates, all of one size")
+    if cloud.color_sets != I or I > HIST_MAX_IMAGES:
+        raise ValueError("a cloud of %d colour sets for %d images (at most %d per call)" % (cloud.color_sets, I, HIST_MAX_IMAGES))
+    nblk = (num_split_h - 2) * num_split_w
+    dev = imgs[0].device
+    inter = torch.empty(I * K, nblk, dtype=F32, device=dev)
+    nproj = torch.empty(I * K, nblk, dtype=torch.int32, device=dev)
+    nimg = torch.empty(I, nblk, dtype=torch.int32, device=dev)
+    scores = torch.empty(I, K, dtype=F32, device=dev)
+    nws = lib.pcl_hist_trim_images_sets_workspace_bytes(0 if splat else cloud.n, I, I, K, H, W, num_split_h, num_split_w)
+    if nws == 0:
+        raise ValueError("hist_trim_scores_images: need num_split_h >= 3 and blocks of at least one pixel")
+    try:
+        ws = _bytes(nws)
+    except torch.cuda.OutOfMemoryError:                 # the z-buffer splat path's small workspace (same scores)
+        torch.cuda.empty_cache()
+        nws = lib.pcl_hist_trim_images_sets_workspace_bytes(0, I, I, K, H, W, num_split_h, num_split_w)
+        ws = _bytes(nws)
+    t2, r2 = trans.reshape(I * K, 3).contiguous(), rot.reshape(I * K, 3).contiguous()
+    arr = (ctypes.c_void_p * I)(*[im.data_ptr() for im in imgs])
+    _lib.check(lib.pcl_hist_trim_scores_images_sets(_ptr(cloud.data), cloud.n, I, arr, I, K, H, W, _ptr(t2), _ptr(r2), num_split_h, num_split_w,
+                                                    _ptr(inter), _ptr(nproj), _ptr(nimg), _ptr(ws), nws, _stream()), "pcl_hist_trim_scores_images_sets")
+    _lib.check(lib.pcl_hist_trim_reduce_images(_ptr(inter), _ptr(nproj), _ptr(nimg), I, K, num_split_h, num_split_w, _ptr(scores), _stream()),
+               "pcl_hist_trim_reduce_images")
     return scores
 
 
@@ -627,6 +737,11 @@ class GradientDescent:
         dh, dw, tau, st = _depth_args(cloud.n, pano.H, pano.W, depth_res, depth_tau, depth_stride) if depth_mask else (0, 0, 0.0, 0)
         self.hyper = _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL,
                                   1 if depth_mask else 0, float(tau), int(dh), int(dw), int(st), -1 if fuse is False else 0, 0)
+        # a cloud of per-image colour sets (Cloud.with_color_sets): candidates [i * B / k, (i + 1) * B / k) read set i, and the chain runs
+        # the single-image plan (pcl_gd_hyper.color_sets)
+        self.hyper.color_sets = int(cloud.color_sets)
+        if cloud.color_sets > 1 and (self.B % cloud.color_sets or depth_mask):
+            raise ValueError("GradientDescent: %d candidates over %d colour sets%s" % (self.B, cloud.color_sets, " with the depth mask" if depth_mask else ""))
         self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
         self.ws_bytes = lib.pcl_gd_workspace_bytes(cloud.n, self.B, pano.H, pano.W, ctypes.byref(self.hyper))
         if self.ws_bytes == 0:

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .omniloc import packed_cloud, packed_pano
+from .omniloc import color_set_groups, packed_cloud, packed_cloud_sets, packed_pano, shared_rgb
 
 __all__ = ["cloud2idx", "sample_from_img", "warp_from_img", "reshape_img_tensor", "make_pano", "quantile", "out_of_room", "rot_from_ypr", "trim_input_loss",
            "trim_input_hist_secondary", "make_input", "make_input_images", "generate_rot_points", "generate_trans_points", "adaptive_trans_num",
@@ -359,13 +359,32 @@ def make_input_images(imgs, xyz, rgb, num_input, init_dict=None, criterion="hist
     over image x translation x rotation, one selection launch for all images, the second stage for all images' survivors in one set
     of launches, one final selection.
     Returns [(input_trans, input_rot)] per image — the tensors make_input returns for that image, bit for bit (the trim launch
-    cuts the cloud into the single-image launch's chunks; tests/test_hip_harness.py)."""
+    cuts the cloud into the single-image launch's chunks; tests/test_hip_harness.py).
+    rgb: one (N, 3) tensor, or a LIST of one per image (per-image colours, e.g. color_mod's, localize.py:173-179): the cloud is packed once
+    with a colour set per image and image i's trim and histogram launches read set i — still make_input(imgs[i], xyz, rgb[i], ...) bit for
+    bit.  Images beyond the colour-set addressing limit (ops.max_color_sets) go in further groups."""
     from .omniloc import _cached
     if init_dict["sample_rate_for_init"] is not None:
         raise NotImplementedError("sample_rate_for_init: broken in the reference too (utils.py:618-620)")
     if criterion != "loss_histogram":
         raise UnboundLocalError("make_input: only criterion='loss_histogram' is implemented (as in the reference)")
     I = len(imgs)
+    rgb = shared_rgb(rgb)
+    sets = isinstance(rgb, list)
+    if sets:
+        if len(rgb) != I:
+            raise ValueError("make_input_images: %d colour sets for %d images" % (len(rgb), I))
+        # (groups within the addressing limit, and within the histogram stage's list budget: that stage runs all of a group's images in
+        # one call, ops.HIST_BATCH_BYTES)
+        per_image = ops._lib.load().pcl_hist_trim_images_sets_workspace_bytes(int(xyz.shape[0]), 1, 1, int(num_intermediate), int(imgs[0].shape[0]),
+                                                                             int(imgs[0].shape[1]), init_dict["num_split_h"], init_dict["num_split_w"])
+        sizes = color_set_groups(int(xyz.shape[0]), I, int(ops.HIST_BATCH_BYTES // per_image) if per_image else 1)
+        if len(sizes) > 1:
+            out, i0 = [], 0
+            for m in sizes:
+                out += make_input_images(imgs[i0:i0 + m], xyz, rgb[i0:i0 + m] if m > 1 else rgb[i0], num_input, init_dict, criterion, num_intermediate)
+                i0 += m
+            return out
     dev = imgs[0].device
     key = _init_key(init_dict, dev)
     rot = _ROT_GRIDS.get(key)
@@ -375,8 +394,8 @@ def make_input_images(imgs, xyz, rgb, num_input, init_dict=None, criterion="hist
     K, Rn = len(trans), len(rot)
     n_mid = min(num_intermediate, K * Rn)
     if I == 1 or Rn > ops.TRIM_MAX_ROT or n_mid > ops.SELECT_MAX_KEEP:
-        return [make_input(im, xyz, rgb, num_input, init_dict, criterion, num_intermediate) for im in imgs]
-    cloud = packed_cloud(xyz, rgb)
+        return [make_input(im, xyz, c, num_input, init_dict, criterion, num_intermediate) for im, c in zip(imgs, rgb if sets else [rgb] * I)]
+    cloud = packed_cloud_sets(xyz, rgb) if sets else packed_cloud(xyz, rgb)
     panos = [packed_pano(im, many_poses=True, n_points=xyz.shape[0]) for im in imgs]
     if len({p.fmt for p in panos}) > 1:                       # a launch needs one texel format: float4 holds any image
         panos = [ops.Pano(im, fmt="f32") for im in imgs]
