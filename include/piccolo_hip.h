@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define PCL_ABI_VERSION 10 /* 10: per-image colour sets (pcl_cloud_sets_bytes / pcl_cloud_pack_sets, pcl_gd_hyper.color_sets, pcl_trim_loss_images_sets, pcl_hist_trim_*_sets); 9: pcl_gd_hyper.fuse, pcl_loss_depth_workspace_bytes takes the occluder stride, pcl_trim_order + the `order` argument of pcl_trim_loss[_images], the library reads no environment variable; 8: PCL_PANO_U8V / pcl_pano_pack_u8v; 7: depth mask on its own grid (pcl_gd_hyper.depth_h / depth_w, pcl_depth_default, pcl_sampling_loss_depth), refresh rule and pcl_gd_depth_refresh_counts removed, pcl_gd_step_from_grads; 6: pcl_select_poses, pcl_gd_set_pano_groups, pcl_gd_winner; 2: fp16-level texels, colour preprocessing, histograms, dataset text reader; 3: backward of the stand-alone ops; 4: pcl_hist_trim_workspace_bytes_n; 5: pcl_source_hash, pcl_timer_calibrate, pcl_trim_*, pcl_gd_plan */
+#define PCL_ABI_VERSION 11 /* 11: room search — several clouds in one refinement chain (pcl_gd_room, pcl_gd_rooms_workspace_bytes, pcl_gd_plan_rooms, pcl_gd_run_rooms); 10: per-image colour sets (pcl_cloud_sets_bytes / pcl_cloud_pack_sets, pcl_gd_hyper.color_sets, pcl_trim_loss_images_sets, pcl_hist_trim_*_sets); 9: pcl_gd_hyper.fuse, pcl_loss_depth_workspace_bytes takes the occluder stride, pcl_trim_order + the `order` argument of pcl_trim_loss[_images], the library reads no environment variable; 8: PCL_PANO_U8V / pcl_pano_pack_u8v; 7: depth mask on its own grid (pcl_gd_hyper.depth_h / depth_w, pcl_depth_default, pcl_sampling_loss_depth), refresh rule and pcl_gd_depth_refresh_counts removed, pcl_gd_step_from_grads; 6: pcl_select_poses, pcl_gd_set_pano_groups, pcl_gd_winner; 2: fp16-level texels, colour preprocessing, histograms, dataset text reader; 3: backward of the stand-alone ops; 4: pcl_hist_trim_workspace_bytes_n; 5: pcl_source_hash, pcl_timer_calibrate, pcl_trim_*, pcl_gd_plan */
 
 #define PCL_EINVAL (-1)   /* bad size / null pointer / unsupported argument */
 #define PCL_EWORKSPACE (-2) /* workspace too small */
@@ -223,6 +223,33 @@ int pcl_gd_set_pano_groups(void *state, const uint64_t *panos_host, int nimages,
  * that loss, yaw / pitch / roll.  leaf_trans / leaf_rot [B][3] (nullable) receive every candidate's leaf parameters — what the
  * reference leaves in the caller's input_trans / input_rot, whose rows it optimises in place (omniloc.py:216-219). */
 int pcl_gd_winner(const void *state, int nimages, int per_image, float *winners, float *leaf_trans, float *leaf_rot, void *stream);
+
+/* Room search (ABI 11): ONE query panorama against the rooms of a building in ONE launch chain.  Room r's candidates are the contiguous
+ * range [r * per_room, (r + 1) * per_room) of a state of B = nrooms * per_room candidates (pcl_gd_state_bytes / pcl_gd_init /
+ * pcl_gd_result as for pcl_gd_run; pcl_gd_winner(state, nrooms, per_room, ...) gives one winner per room), all sampling `pano`.
+ * Every room keeps its own cloud (packed by pcl_cloud_pack), its own clamp box and its own decomposition: room r's loss blocks run
+ * pcl_gd_plan(n_r, per_room)'s chunks, poses per block and steps per chunk over its own cloud, and its candidates are finished from its
+ * own partial sums in the same order as there.  Contract: each room's results — state, pose records, loss history columns — equal those
+ * of a pcl_gd_run of that room alone (same per_room candidates, same hyper-parameters) BIT FOR BIT, fused or not, eager or replayed.
+ * The room table is written to device memory by one small launch at the start of every pcl_gd_run_rooms call (its values travel as
+ * kernel arguments: no host-to-device copy), so a call stays capturable in a hipGraph.  An iteration is one launch when the blocks of
+ * all rooms together fit the fuse rule of pcl_gd_plan (hyper->fuse < 0: never), else two.
+ * PCL_EINVAL (0 from the sizing function): nrooms outside 1..PCL_GD_MAX_ROOMS, per_room <= 0, a room with a null cloud or box or
+ * n outside 1..PCL_MAX_POINTS, hyper->depth_mask, hyper->color_sets > 1, null arguments.  hyper->images is ignored (one panorama). */
+#define PCL_GD_MAX_ROOMS 32
+typedef struct pcl_gd_room {
+    const float *cloud; /* packed cloud (pcl_cloud_pack) */
+    int64_t n;          /* its points */
+    const float *box;   /* device box[6] of the room (see pcl_gd_run) */
+} pcl_gd_room;
+size_t pcl_gd_rooms_workspace_bytes(const pcl_gd_room *rooms_host, int nrooms, int per_room, const pcl_gd_hyper *hyper_host);
+/* host-only: per room the chunks of its plan (nchunks_host[nrooms], nullable), the poses per block (the same for all rooms), whether
+ * an iteration is one launch */
+int pcl_gd_plan_rooms(const pcl_gd_room *rooms_host, int nrooms, int per_room, const pcl_gd_hyper *hyper_host, int *nchunks_host,
+                      int *poses_per_block_host, int *fused_host);
+int pcl_gd_run_rooms(const pcl_gd_room *rooms_host, int nrooms, const void *pano, int pano_format, int H, int W, void *state, int per_room,
+                     const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace, size_t workspace_bytes, void *timer,
+                     void *stream);
 
 /* ---- kernel timer (measurement aid, HOST object) --------------------------------------------------------------
  * A pool of hipEvent pairs.  When a timer is passed to pcl_gd_run, every launch of the fused loss+gradient kernel is

@@ -11,7 +11,7 @@ from . import build as _build
 _c = ctypes
 _vp, _i64, _int, _sz, _dbl = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_size_t, _c.c_double
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 RESULT_STRIDE = 8
 GD_RESULT_STRIDE = 16
 GD_SEQUENTIAL, GD_BATCH = 0, 1
@@ -22,6 +22,13 @@ class GdHyper(_c.Structure):
     _fields_ = [("lr", _dbl), ("factor", _dbl), ("patience", _c.c_int32), ("mode", _c.c_int32),
                 ("depth_mask", _c.c_int32), ("depth_tau", _c.c_float), ("depth_h", _c.c_int32), ("depth_w", _c.c_int32),
                 ("depth_stride", _c.c_int32), ("fuse", _c.c_int32), ("images", _c.c_int32), ("color_sets", _c.c_int32)]
+
+
+GD_MAX_ROOMS = 32
+
+
+class GdRoom(_c.Structure):
+    _fields_ = [("cloud", _vp), ("n", _i64), ("box", _vp)]
 
 
 # name -> (restype, argtypes); every symbol include/piccolo_hip.h declares
@@ -98,6 +105,9 @@ SIGNATURES = {
     "pcl_gd_set_panos": (_int, [_vp, _vp, _int, _vp]),
     "pcl_gd_set_pano_groups": (_int, [_vp, _c.POINTER(_c.c_uint64), _int, _int, _vp]),
     "pcl_gd_winner": (_int, [_vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "pcl_gd_rooms_workspace_bytes": (_sz, [_c.POINTER(GdRoom), _int, _int, _c.POINTER(GdHyper)]),
+    "pcl_gd_plan_rooms": (_int, [_c.POINTER(GdRoom), _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
+    "pcl_gd_run_rooms": (_int, [_c.POINTER(GdRoom), _int, _vp, _int, _int, _int, _vp, _int, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
     "pcl_select_poses": (_int, [_vp, _int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp]),
     "pcl_cloud2idx": (_int, [_vp, _i64, _vp, _vp]),
     "pcl_sample_from_img": (_int, [_vp, _int, _int, _int, _vp, _i64, _vp, _vp]),

@@ -6,6 +6,7 @@
 // One 256-thread block per candidate pose (four waves gather the partial sums, wave 0 runs the optimiser update in the
 // same precision mix as the reference: fp32 tensors, python-double scalars).
 #include <stdlib.h>
+#include <string.h>
 
 #include "pcl_gd_device.h"
 
@@ -19,6 +20,9 @@ size_t pcl_partials_bytes(int64_t n, int B, int sets = 1);
 int pcl_plan_nchunks(int64_t n, int B, int sets = 1);
 int pcl_plan_nblocks(int64_t n, int B, int sets = 1);
 int pcl_plan_G(int64_t n, int B, int sets = 1);
+void pcl_plan_room(int64_t n, int per_room, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
+int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
+                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse);
 size_t pcl_depth_zbuf_bytes(int B, int Hd, int Wd);
 int pcl_launch_zbuffers(const float* cloud, int64_t n, const PclPoseRec* poses, int B, const PclDepthGrid& g, int zstride, uint32_t* zbuf, bool fill,
                         hipStream_t s);
@@ -477,6 +481,172 @@ extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int p
     }
     if (fused && num_iter > 0) {
         const int last = (num_iter - 1) & 1;                     // the copy the last launch wrote (copy 0 when it was the only one)
+        epilogue(num_iter - 1, num_iter > 1 ? last : 0, partials2[num_iter > 1 ? last : 0]);
+        PCL_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- room search: several clouds in one chain
+
+// The stand-alone epilogue of a multi-room chain: block = pose group of the whole launch; room r owns groups [r ngroups, (r + 1) ngroups)
+// and its group is finished from the room's own partials region over the room's own nchunks and clamped to the room's own box — with
+// pointers shifted to the room's first candidate, so this is pcl_gd_epilogue_kernel of that room alone.
+template <int G>
+__global__ void __launch_bounds__(PCL_GD_THREADS) pcl_gd_epilogue_rooms_kernel(const float* __restrict__ partials, const PclRoomTable* __restrict__ rooms,
+                                                                               int ngroups, const PclGdPose* st_in, const PclPoseRec* recs_in,
+                                                                               PclGdPose* st_out, PclPoseRec* recs_out, double factor, int patience,
+                                                                               int mode, float* loss_out)
+{
+    __shared__ double rows_sh[(PCL_GD_THREADS / 16) * 2 * G][4];
+    __shared__ double sums_sh[G][PCL_NACC];
+    const int r = (int)blockIdx.x / ngroups, grp = (int)blockIdx.x - r * ngroups;
+    const PclRoomRec* rm = rooms->rec + r;
+    const int pose0 = pcl_rfl(rm->group0) * G, nchunks = pcl_rfl(rm->nchunks);
+    const float* part = partials + (long long)pcl_rfl64((unsigned long long)rm->partials);
+    const float* box = (const float*)pcl_rfl64(rm->box);
+    pcl_gd_finish_group<G, false>(part, nchunks, grp, threadIdx.x, st_in + pose0, recs_in + pose0, st_out + pose0, recs_out + pose0, true, box, factor,
+                                  patience, mode, loss_out ? loss_out + pose0 : nullptr, rows_sh, sums_sh, nullptr);
+}
+
+// the room table travels as kernel arguments and is stored with vector stores, one 32-bit word per thread
+__global__ void pcl_gd_rooms_table_kernel(PclRoomTable t, PclRoomTable* dst)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int)(sizeof(PclRoomTable) / 4)) ((int*)dst)[i] = ((const int*)&t)[i];
+}
+
+// the host side of a multi-room chain: every room's plan, partials region and block range, the sizes, the checks
+struct GdRooms {
+    PclRoomTable t;
+    int nrooms, per_room, G, ngroups, nblk;
+    size_t partials_bytes;       // one partials buffer, all rooms (each region 256-byte aligned)
+};
+
+static int gd_rooms_setup(const pcl_gd_room* rooms_host, int nrooms, int per_room, const pcl_gd_hyper* hyper_host, GdRooms* g)
+{
+    if (!rooms_host || !hyper_host || nrooms < 1 || nrooms > PCL_GD_MAX_ROOMS || per_room <= 0) return PCL_EINVAL;
+    if (hyper_host->depth_mask || hyper_host->color_sets > 1 || hyper_host->color_sets < 0) return PCL_EINVAL;
+    if ((int64_t)nrooms * per_room > 0x7fffffff / 2) return PCL_EINVAL;
+    for (int r = 0; r < nrooms; r++)
+        if (!rooms_host[r].cloud || !rooms_host[r].box || rooms_host[r].n <= 0 || rooms_host[r].n > PCL_MAX_POINTS) return PCL_EINVAL;
+    memset(&g->t, 0, sizeof(g->t));
+    g->nrooms = nrooms; g->per_room = per_room;
+    int64_t blocks = 0, floats = 0;
+    for (int r = 0; r < PCL_GD_MAX_ROOMS; r++) g->t.block0[r] = 0x7fffffff;
+    for (int r = 0; r < nrooms; r++) {
+        PclRoomRec& e = g->t.rec[r];
+        int G, ngroups;
+        pcl_plan_room(rooms_host[r].n, per_room, &G, &ngroups, &e.nchunks, &e.seg_len, &e.steps_base, &e.steps_rem);
+        g->G = G; g->ngroups = ngroups;              // (pcl_plan's poses per block depend on per_room alone: the same for every room)
+        e.cloud = (unsigned long long)rooms_host[r].cloud; e.box = (unsigned long long)rooms_host[r].box;
+        e.n = (int)rooms_host[r].n; e.stride = (int)pcl_cloud_stride(rooms_host[r].n);
+        e.block0 = (int)blocks; e.group0 = r * ngroups; e.partials = floats;
+        g->t.block0[r] = (int)blocks;
+        blocks += (int64_t)e.nchunks * ngroups;
+        floats += (int64_t)(gd_align((size_t)e.nchunks * per_room * PCL_NACC * sizeof(float)) / sizeof(float));
+    }
+    if (blocks > 0x7fffffff) return PCL_EINVAL;
+    g->nblk = (int)blocks;
+    g->partials_bytes = (size_t)floats * sizeof(float);
+    return 0;
+}
+
+// table, then two partials buffers (fused iterations read one while they write the other)
+extern "C" size_t pcl_gd_rooms_workspace_bytes(const pcl_gd_room* rooms_host, int nrooms, int per_room, const pcl_gd_hyper* hyper_host)
+{
+    GdRooms g;
+    if (gd_rooms_setup(rooms_host, nrooms, per_room, hyper_host, &g)) return 0;
+    return gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes);
+}
+
+extern "C" int pcl_gd_plan_rooms(const pcl_gd_room* rooms_host, int nrooms, int per_room, const pcl_gd_hyper* hyper_host, int* nchunks_host,
+                                 int* poses_per_block_host, int* fused_host)
+{
+    GdRooms g;
+    const int rc = gd_rooms_setup(rooms_host, nrooms, per_room, hyper_host, &g);
+    if (rc) return rc;
+    if (nchunks_host)
+        for (int r = 0; r < nrooms; r++) nchunks_host[r] = g.t.rec[r].nchunks;
+    if (poses_per_block_host) *poses_per_block_host = g.G;
+    if (fused_host) *fused_host = g.nblk <= gd_fuse_limit(hyper_host) ? 1 : 0;
+    return 0;
+}
+
+// pcl_gd_run for several rooms: the same iteration loop, fused and two-launch forms, with the rooms instances of the loss kernel and
+// the rooms epilogue (flip and timer as there; the XCDs always split the chunks — one panorama)
+extern "C" int pcl_gd_run_rooms(const pcl_gd_room* rooms_host, int nrooms, const void* pano, int pano_format, int H, int W, void* state, int per_room,
+                                const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace, size_t workspace_bytes,
+                                void* timer, void* stream)
+{
+    PclTimer* tm = (PclTimer*)timer;
+    if (!rooms_host || !pano || !state || !hyper_host || !workspace || H <= 0 || W <= 0 || num_iter < 0) return PCL_EINVAL;
+    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
+    GdRooms g;
+    int rc = gd_rooms_setup(rooms_host, nrooms, per_room, hyper_host, &g);
+    if (rc) return rc;
+    if (workspace_bytes < gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes)) return PCL_EWORKSPACE;
+    // one room: pcl_gd_run itself (the same plan and arithmetic — and no room look-up in front of every block: 1.2 us per iteration at the
+    // shipped shape, tools/room_bench.py).  Its workspace, two partials buffers of the same plan, fits in this one.
+    if (nrooms == 1) {
+        pcl_gd_hyper h = *hyper_host;
+        h.images = 0;
+        return pcl_gd_run(rooms_host[0].cloud, rooms_host[0].n, pano, pano_format, H, W, state, per_room, rooms_host[0].box, &h, num_iter, loss_history,
+                          workspace, workspace_bytes, timer, stream);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int B = nrooms * per_room, G = g.G;
+    PclRoomTable* table = (PclRoomTable*)workspace;
+    float* partials2[2] = {(float*)((char*)workspace + gd_align(sizeof(PclRoomTable))),
+                           (float*)((char*)workspace + gd_align(sizeof(PclRoomTable)) + gd_align(g.partials_bytes))};
+    const int words = (int)(sizeof(PclRoomTable) / 4);
+    hipLaunchKernelGGL(pcl_gd_rooms_table_kernel, dim3((words + 255) / 256), dim3(256), 0, s, g.t, table);
+    PCL_LAUNCH_CHECK();
+    static const int flip_env = PCL_KNOB(FLIP, 1);
+    const bool fused = g.nblk <= gd_fuse_limit(hyper_host);
+    auto epilogue = [&](int it, int copy_in, float* partials) {
+        float* lo = loss_history ? loss_history + (int64_t)it * B : nullptr;
+        const double fac = hyper_host->factor;
+        const int pat = (int)hyper_host->patience, mode = (int)hyper_host->mode, ngrp = nrooms * g.ngroups;
+        if (G == 2)
+            hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<2>, dim3(ngrp), dim3(PCL_GD_THREADS), 0, s, partials, table, g.ngroups, gd_poses(state, B, copy_in),
+                               gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), fac, pat, mode, lo);
+        else
+            hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<1>, dim3(ngrp), dim3(PCL_GD_THREADS), 0, s, partials, table, g.ngroups, gd_poses(state, B, copy_in),
+                               gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), fac, pat, mode, lo);
+    };
+    for (int it = 0; it < num_iter; it++) {
+        const bool timed = tm && tm->used < tm->capacity && (it % tm->stride) == 0;
+        if (timed) {
+            hipError_t e = hipEventRecord(tm->start[tm->used], s);
+            if (e != hipSuccess) return (int)e;
+        }
+        const int flip = flip_env ? (it & 1) : 0;
+        if (fused && it > 0) {
+            const int cin = (it - 1) & 1, cout = it & 1;
+            PclFuseArgs f;
+            f.partials_in = partials2[cin]; f.st_in = gd_poses(state, B, cin); f.recs_in = gd_recs(state, B, cin);
+            f.st_out = gd_poses(state, B, cout); f.recs_out = gd_recs(state, B, cout);
+            f.box = nullptr;                                  // (every room's own box: the room table)
+            f.factor = hyper_host->factor; f.patience = (int)hyper_host->patience; f.mode = (int)hyper_host->mode;
+            f.loss_out = loss_history ? loss_history + (int64_t)(it - 1) * B : nullptr;
+            rc = pcl_launch_loss_rooms(table, pano, pano_format, H, W, f.recs_in, B, G, g.ngroups, g.nblk, partials2[cout], s, flip, &f);
+        } else {
+            rc = pcl_launch_loss_rooms(table, pano, pano_format, H, W, gd_recs(state, B), B, G, g.ngroups, g.nblk, partials2[0], s, flip, nullptr);
+        }
+        if (rc) return rc;
+        if (timed) {
+            hipError_t e = hipEventRecord(tm->stop[tm->used], s);
+            if (e != hipSuccess) return (int)e;
+            tm->used++;
+        }
+        if (!fused) {
+            epilogue(it, 0, partials2[0]);
+            PCL_LAUNCH_CHECK();
+        }
+    }
+    if (fused && num_iter > 0) {
+        const int last = (num_iter - 1) & 1;
         epilogue(num_iter - 1, num_iter > 1 ? last : 0, partials2[num_iter > 1 ? last : 0]);
         PCL_LAUNCH_CHECK();
     }

@@ -22,6 +22,30 @@ __device__ __forceinline__ int64_t pcl_partials_row(int nchunks, int G, int grou
     return (((int64_t)group * nchunks + chunk) * G + g) * PCL_NACC;
 }
 
+// The rooms of a multi-room launch chain (pcl_gd_run_rooms): room r's candidates are the contiguous pose records
+// [group0 G, (group0 + ngroups) G), its loss blocks the contiguous grid range [block0, block0 + nchunks ngroups), and those blocks run
+// room r's own single-cloud plan pcl_plan(n, per_room) over its own packed cloud.  Written to device memory once per call
+// (pcl_gd_rooms_table_kernel); every block reads it with scalar loads.  Unused entries of block0 hold INT_MAX.
+struct PclRoomRec {
+    unsigned long long cloud;      // packed cloud of the room (pcl_cloud_pack)
+    unsigned long long box;        // device box[6] of the room
+    long long partials;            // float offset of the room's region in each partials buffer
+    int n, stride;
+    int nchunks, seg_len;
+    int steps_base, steps_rem;
+    int block0, group0;
+};
+struct PclRoomTable {
+    int block0[PCL_GD_MAX_ROOMS];  // first loss block of every room (a multiple of 8: nchunks is): what a block searches
+    PclRoomRec rec[PCL_GD_MAX_ROOMS];
+};
+
+__device__ __forceinline__ int pcl_rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ unsigned long long pcl_rfl64(unsigned long long v)
+{
+    return ((unsigned long long)(unsigned)pcl_rfl((int)(v >> 32)) << 32) | (unsigned long long)(unsigned)pcl_rfl((int)(unsigned)v);
+}
+
 template <int CTRL>
 __device__ __forceinline__ double pcl_dpp_sum_d(double v)
 {

@@ -78,9 +78,48 @@ extern "C" int pcl_debug_stamp(unsigned long long* slot, void* stream)
 // CS: the cloud holds one colour set per query image (pcl_cloud_pack_sets) and the block's G poses read the set their first pose
 // record names (PclPoseRec.cset, one image's poses per group): a scalar plane offset on the same buffer resource — no VGPR, no
 // branch in the load loop.  A template parameter, not a runtime select: the instances without it compile to the loop they always had.
-template <int G, bool GRAD, int VIS, int FMT, bool FUSED, bool CS = false>
-__device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a, const PclFuseArgs& f)
+// RM: one launch covers several ROOMS (pcl_gd_run_rooms): the block finds its room in the room table (pcl_room_select) and runs that
+// room's own single-cloud plan over that room's own cloud, poses, partials region and clamp box, with its block index inside the room's
+// range.  Gradient pass only.  Like CS a template parameter: the instances without it keep their instruction stream.
+template <int G, bool FUSED>
+__device__ __forceinline__ unsigned pcl_room_select(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* __restrict__ tb, PclLossArgs& a,
+                                                    PclFuseArgs& f)
 {
+    // the room: how many rooms start at or before this block (unused entries hold INT_MAX) — 32 independent scalar loads, no search loop
+    int r = -1;
+#pragma unroll
+    for (int q = 0; q < PCL_GD_MAX_ROOMS; q++) r += (int)blockIdx.x >= pcl_rfl(tb->block0[q]) ? 1 : 0;
+    const PclRoomRec* __restrict__ rm = tb->rec + r;
+    const int group0 = pcl_rfl(rm->group0), pose0 = group0 * G;
+    const long long poff = (long long)pcl_rfl64((unsigned long long)rm->partials);
+    a = a_in;
+    a.cloud = (const float*)pcl_rfl64(rm->cloud);
+    a.n = pcl_rfl(rm->n); a.stride = pcl_rfl(rm->stride);
+    a.nchunks = pcl_rfl(rm->nchunks); a.seg_len = pcl_rfl(rm->seg_len);
+    a.steps_base = pcl_rfl(rm->steps_base); a.steps_rem = pcl_rfl(rm->steps_rem);
+    a.poses = a_in.poses + pose0;
+    a.partials = a_in.partials + poff;
+    a.xcd_groups = 0;
+    f = f_in;
+    if constexpr (FUSED) {
+        f.partials_in = f_in.partials_in + poff;
+        f.st_in = f_in.st_in + pose0; f.recs_in = f_in.recs_in + pose0;
+        f.st_out = f_in.st_out + pose0; f.recs_out = f_in.recs_out + pose0;
+        f.box = (const float*)pcl_rfl64(rm->box);
+        f.loss_out = f_in.loss_out ? f_in.loss_out + pose0 : nullptr;
+    }
+    return blockIdx.x - (unsigned)pcl_rfl(rm->block0);           // (block0 is a multiple of 8: the XCD of a block is unchanged)
+}
+
+template <int G, bool GRAD, int VIS, int FMT, bool FUSED, bool CS = false, bool RM = false>
+__device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* rooms = nullptr)
+{
+    PclLossArgs a_rm;
+    PclFuseArgs f_rm;
+    unsigned bid = blockIdx.x;
+    if constexpr (RM) bid = pcl_room_select<G, FUSED>(a_in, f_in, rooms, a_rm, f_rm);
+    const PclLossArgs& a = RM ? a_rm : a_in;
+    const PclFuseArgs& f = RM ? f_rm : f_in;
     // XCD-aware mapping: blocks b and b+8 share an XCD (round-robin dispatch) and each XCD has its own 4 MiB L2.  Within an
     // XCD the pose group varies fastest, so the blocks that are resident together read the same cloud chunk (it stays in
     // that XCD's L2 across the pose groups) and, the candidates being near each other, neighbouring texels.
@@ -97,15 +136,15 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a, const PclFus
         // over ALL chunks.  For launches whose candidates read DIFFERENT panoramas — the images of one room in one chain, image i's
         // candidates a contiguous range of groups — an XCD's L2 then holds ONE image's texture (plus the whole of a small cloud)
         // instead of a slice of the cloud and every texture of the launch.
-        const int gpx = a.ngroups >> 3, j = (int)(blockIdx.x >> 3), cj = j / gpx;
-        group = (int)(blockIdx.x & 7) * gpx + (j - cj * gpx);
+        const int gpx = a.ngroups >> 3, j = (int)(bid >> 3), cj = j / gpx;
+        group = (int)(bid & 7) * gpx + (j - cj * gpx);
         chunk = a.flip ? a.nchunks - 1 - cj : cj;
     } else {
-        const int lq = (int)(blockIdx.x >> 3) / a.ngroups;
-        group = (int)(blockIdx.x >> 3) - lq * a.ngroups;
+        const int lq = (int)(bid >> 3) / a.ngroups;
+        group = (int)(bid >> 3) - lq * a.ngroups;
         const int lc = a.flip ? (a.nchunks >> 3) - 1 - lq : lq;                                         // chunk within the XCD
         const int run = lc / a.seg_len;
-        chunk = (run * 8 + (int)(blockIdx.x & 7)) * a.seg_len + (lc - run * a.seg_len);
+        chunk = (run * 8 + (int)(bid & 7)) * a.seg_len + (lc - run * a.seg_len);
     }
     const int pose0 = group * G;
 
@@ -336,6 +375,20 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_sets_kernel(PclLossA
     pcl_loss_body<G, true, 0, FMT, true, true>(a, f);
 }
 
+// several rooms in one launch (pcl_gd_run_rooms; loss + gradient, no visibility mask, no colour sets): own kernel names as well.  The
+// room table is a kernel argument of its own, after the others: the instances above keep their argument layout.
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_rooms_kernel(PclLossArgs a, const PclRoomTable* rooms)
+{
+    pcl_loss_body<G, true, 0, FMT, false, false, true>(a, PclFuseArgs{}, rooms);
+}
+
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_rooms_kernel(PclLossArgs a, PclFuseArgs f, const PclRoomTable* rooms)
+{
+    pcl_loss_body<G, true, 0, FMT, true, false, true>(a, f, rooms);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launch planning (shared with the GD loop)
 
@@ -411,6 +464,13 @@ static PclPlan pcl_plan_sets(int64_t n, int B, int sets)
     p.ngroups = B / p.G;
     p.seg_len = pcl_xcd_seg_len(p.nchunks, (int64_t)p.nchunks * p.ngroups);
     return p;
+}
+
+// one room of a multi-room chain (pcl_gd_run_rooms): that room's single-cloud plan pcl_plan(n, per_room), XCD runs included
+void pcl_plan_room(int64_t n, int per_room, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem)
+{
+    const PclPlan p = pcl_plan(n, per_room);
+    *G = p.G; *ngroups = p.ngroups; *nchunks = p.nchunks; *seg_len = p.seg_len; *steps_base = p.steps_base; *steps_rem = p.steps_rem;
 }
 
 size_t pcl_partials_bytes(int64_t n, int B, int sets)
@@ -496,6 +556,45 @@ static void pcl_launch_sets(const PclLossArgs& a, const PclFuseArgs* f, int G, i
         else if (G == 2) hipLaunchKernelGGL((pcl_loss_sets_kernel<2, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
         else hipLaunchKernelGGL((pcl_loss_sets_kernel<1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
     }
+}
+
+// The loss pass of a multi-room chain (pcl_gd_run_rooms): nblk blocks, every room's cloud, plan, pose range and partials region from the
+// device room table `rooms`; `poses` / `partials` (and the buffers of `fuse`) are the bases of all rooms.  Gradient pass, no mask.
+int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
+                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse)
+{
+    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;
+    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    PclLossArgs a = PclLossArgs{};
+    a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
+    a.poses = poses; a.B = B; a.partials = partials;
+    a.ngroups = ngroups; a.flip = flip & 1; a.xcd_groups = 0; a.color_sets = 1;
+    const dim3 grid(nblk), blk(PCL_BLOCK);
+    if (fuse) {
+        if (pano_format == PCL_PANO_U8) {
+            if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<2, PCL_PANO_U8>), grid, blk, 0, s, a, *fuse, rooms);
+            else hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<1, PCL_PANO_U8>), grid, blk, 0, s, a, *fuse, rooms);
+        } else if (pano_format == PCL_PANO_F16) {
+            if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<2, PCL_PANO_F16>), grid, blk, 0, s, a, *fuse, rooms);
+            else hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<1, PCL_PANO_F16>), grid, blk, 0, s, a, *fuse, rooms);
+        } else {
+            if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<2, PCL_PANO_F32>), grid, blk, 0, s, a, *fuse, rooms);
+            else hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<1, PCL_PANO_F32>), grid, blk, 0, s, a, *fuse, rooms);
+        }
+    } else {
+        if (pano_format == PCL_PANO_U8) {
+            if (G == 2) hipLaunchKernelGGL((pcl_loss_rooms_kernel<2, PCL_PANO_U8>), grid, blk, 0, s, a, rooms);
+            else hipLaunchKernelGGL((pcl_loss_rooms_kernel<1, PCL_PANO_U8>), grid, blk, 0, s, a, rooms);
+        } else if (pano_format == PCL_PANO_F16) {
+            if (G == 2) hipLaunchKernelGGL((pcl_loss_rooms_kernel<2, PCL_PANO_F16>), grid, blk, 0, s, a, rooms);
+            else hipLaunchKernelGGL((pcl_loss_rooms_kernel<1, PCL_PANO_F16>), grid, blk, 0, s, a, rooms);
+        } else {
+            if (G == 2) hipLaunchKernelGGL((pcl_loss_rooms_kernel<2, PCL_PANO_F32>), grid, blk, 0, s, a, rooms);
+            else hipLaunchKernelGGL((pcl_loss_rooms_kernel<1, PCL_PANO_F32>), grid, blk, 0, s, a, rooms);
+        }
+    }
+    PCL_LAUNCH_CHECK();
+    return 0;
 }
 
 // `fuse` (nullable): finish the previous GD iteration in the prologue of every block (gradient pass without visibility only)

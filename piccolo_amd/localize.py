@@ -18,7 +18,7 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import omniloc_all, omniloc_batch, omniloc_batch_images
+from .omniloc import omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_rooms
 from .utils import make_input, make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
 
@@ -48,6 +48,29 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
         results = omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, summaries)
     best = min(range(len(results)), key=lambda i: float(results[i][2]))
     return results[best][0], results[best][1], results[best][2]
+
+
+def localize_in_rooms(img_init, img_main, rooms, cfg, init_dict):
+    """Room search: which of `rooms` (a list of (xyz, rgb) clouds in one frame, e.g. the rooms of one Stanford area) was the panorama
+    taken in, and where.  Per room the colour preprocessing (preprocess_colors: with sharpen_color every room gets its own equalised
+    colours) and the starting poses (make_input) on the initialisation image, then ONE refinement of the main image against all rooms
+    (omniloc_batch_rooms; cfg.parallel selects omniloc_batch's or omniloc_all's semantics).  The room with the smallest loss wins (ties
+    to the lowest index, as torch.argmin).  -> (room index, t (3,1), R (3,3), loss, every room's loss (R,))
+    (preprocess_colors re-quantises the colour-modulated initialisation image to 8-bit levels and honours match_color, like the OmniScenes
+    loop; the known-room Stanford loop keeps color_mod's image as it is.  So a room search restricted to the ground-truth room does not
+    reproduce a known-room Stanford run bit for bit: its starting poses may differ.)"""
+    trs, ros, prepped = [], [], []
+    for xyz, rgb in rooms:
+        img_r, rgb_r = preprocess_colors(img_init, rgb, cfg)
+        tr, ro = make_input(img_r, xyz, rgb_r, getattr(cfg, "num_input", 6), init_dict, getattr(cfg, "criterion", "histogram"),
+                            getattr(cfg, "num_intermediate", 20))
+        trs.append(tr)
+        ros.append(ro)
+        prepped.append((xyz, rgb_r))
+    res = omniloc_batch_rooms(img_main, prepped, trs, ros, cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
+    losses = torch.stack([r[2].reshape(()) for r in res])
+    k = int(torch.argmin(losses))
+    return k, res[k][0], res[k][1], res[k][2], losses
 
 
 def pose_errors(t, R, gt_trans, gt_rot):
@@ -176,7 +199,7 @@ def omniscenes_success(t_err, r_err):
 LAST_RUN = {}          # rank 0's summary of the latest dataset loop: accuracy, failed / skipped file names (what the reference prints)
 
 
-def write_results(table, gts, filenames, writer, log_dir, csv_name, header, row_prefix, success):
+def write_results(table, gts, filenames, writer, log_dir, csv_name, header, row_prefix, success, row_suffix=None):
     """Rank 0's tail of the dataset loops (localize.py:250-297 / :513-530): the CSV in the reference's columns, the running
     accuracy under the DATASET's own success rule (`success(t_err, r_err)`), failed / skipped rooms.  Pure host code.
     -> {"accuracy", "well_posed", "total", "failed", "skipped"}."""
@@ -209,7 +232,7 @@ def write_results(table, gts, filenames, writer, log_dir, csv_name, header, row_
             scalar_summaries["current_accuracy"] = [accuracy]
             write_summaries(writer, scalar_summaries, k)                     # localize.py:295
             w.writerow(row_prefix(filenames[k]) + [_fmt(gt_t), _fmt(gt_r), 0, _fmt(row[0:3]), _fmt(row[3:12]), t_err, r_err,
-                                                   float(row[15])])
+                                                   float(row[15])] + (row_suffix(k) if row_suffix is not None else []))
     writer.add_scalar("final accuracy", accuracy)
     print("Final Accuracy : {}".format(accuracy))
     print("failed {} rooms : {}\n".format(len(failed), failed))
@@ -217,7 +240,7 @@ def write_results(table, gts, filenames, writer, log_dir, csv_name, header, row_
     return {"accuracy": accuracy, "well_posed": well_posed, "total": total, "failed": failed, "skipped": skipped_list}
 
 
-def _run_dataset(cfg, writer, log_dir, filenames, per_image, csv_name, header, row_prefix, success):
+def _run_dataset(cfg, writer, log_dir, filenames, per_image, csv_name, header, row_prefix, success, row_suffix=None, on_gathered=None):
     """Shared loop of the two dataset harnesses: shard the query images over the ranks, run `per_image(k)` ->
     (RESULT_WIDTH row, gt_trans, gt_rot, skipped), gather, and let rank 0 write the reference's CSV and the accuracy under
     the dataset's own success rule (`success`: stanford_success / omniscenes_success)."""
@@ -244,6 +267,8 @@ def _run_dataset(cfg, writer, log_dir, filenames, per_image, csv_name, header, r
         table = pdist.gather_rows(rows.to(dev), len(filenames), rank, world)
     else:
         table = pdist.localize_sharded(len(filenames), body, dev)
+    if on_gathered is not None:                     # (every rank, after the rows: a collective of the caller's own, e.g. room search's)
+        on_gathered()
     rank, world = pdist.world()
     if world > 1 and rank == 0:                     # ground truths of the other ranks' images, for the CSV
         for k in range(len(filenames)):
@@ -251,7 +276,7 @@ def _run_dataset(cfg, writer, log_dir, filenames, per_image, csv_name, header, r
                 gts[k] = per_image(k, gt_only=True)
     LAST_RUN.clear()
     if rank == 0:
-        LAST_RUN.update(write_results(table.cpu().numpy(), gts, filenames, writer, log_dir, csv_name, header, row_prefix, success))
+        LAST_RUN.update(write_results(table.cpu().numpy(), gts, filenames, writer, log_dir, csv_name, header, row_prefix, success, row_suffix))
     return table
 
 
@@ -337,10 +362,24 @@ class _Batcher:
             j["finish"](t, R, _result_row(t, R, loss, j["gt"][0], j["gt"][1], share))
 
 
+def stanford_area_rooms(root, area, room_search=True):
+    """The rooms a room search of Stanford area `area` considers: the stems of pcd_not_aligned/area_<area>/*.txt, sorted; a list
+    `room_search` keeps those of its names (e.g. ["office_1", "hallway_2"]) in that sorted order."""
+    names = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(root, "pcd_not_aligned/area_{}/*.txt".format(area))))
+    if isinstance(room_search, (list, tuple)):
+        keep = {str(r) for r in room_search}
+        names = [n for n in names if n in keep]
+    return names
+
+
 def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford"):
     """Stanford2D-3D-S loop (localize.py:76-297) over `root`/pano/area_*/ *.png, pcd_not_aligned/area_*/<room>.txt and
-    pose/area_*/ *.json; writes `stanford_results.csv` with the reference's columns and result images under results/."""
+    pose/area_*/ *.json; writes `stanford_results.csv` with the reference's columns and result images under results/.
+    cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms)."""
     _require_gravity_aligned(cfg)
+    room_search = getattr(cfg, "room_search", None)
+    if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
+        raise ValueError("room_search does not combine with images_per_launch > 1: a room search refines one image against many clouds")
     _seed_all()
     dev = ops.device()
     area_num = getattr(cfg, "area", None)
@@ -363,6 +402,8 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     mh, mw = getattr(cfg, "main_downsample_h", 1), getattr(cfg, "main_downsample_w", 1)
     cache = {}
     summaries = {}
+    if room_search:
+        return _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
 
     def per_image(k, gt_only=False, batcher=None, done=None):
         filename = filenames[k]
@@ -407,6 +448,106 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
                         ["area_num", "pano_name", "gt_trans", "gt_rot", "skipped?", "OmniLoc_trans", "OmniLoc_rot", "t_error (m)",
                          "r_error (degrees)", "time (s)"],
                         lambda f: [int(f.split("/")[-2].split("_")[-1]), f.split("/")[-1]], stanford_success)
+
+
+STANFORD_HEADER = ["area_num", "pano_name", "gt_trans", "gt_rot", "skipped?", "OmniLoc_trans", "OmniLoc_rot", "t_error (m)", "r_error (degrees)",
+                   "time (s)"]
+
+
+def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search):
+    """localize_stanford with cfg.room_search: every image is localised among the rooms of its area (stanford_area_rooms) by
+    localize_in_rooms instead of in the room its file name names.  The skip rule stays on the ground-truth room's cloud (the same images
+    are evaluated as in a known-room run); the CSV gets a last column found_room, LAST_RUN a room_accuracy, and the result image is
+    rendered from the found room's cloud.  Each area's clouds are read once.  With several ranks every rank localises its share of the
+    images and the found rooms are gathered with the result rows (as room indices into the area's sorted listing), so that rank 0 writes
+    found_room and room_accuracy for every image."""
+    dev = ops.device()
+    sample_rate = getattr(cfg, "sample_rate", 1)
+    quant = getattr(cfg, "out_of_room_quantile", 0.05)
+    dh, dw = getattr(cfg, "init_downsample_h", 1), getattr(cfg, "init_downsample_w", 1)
+    mh, mw = getattr(cfg, "main_downsample_h", 1), getattr(cfg, "main_downsample_w", 1)
+    init_dict = get_init_dict(cfg)
+    areas, found, found_idx = {}, {}, {}
+
+    def area_of(k):
+        return int(filenames[k].split("/")[-2].split("_")[-1])
+
+    def gt_room_of(k):
+        img_name = filenames[k].split("/")[-1]
+        return "{}_{}".format(img_name.split("_")[2], img_name.split("_")[3])
+
+    def area_rooms(area):
+        if area not in areas:
+            rooms = []
+            for name in stanford_area_rooms(root, area, room_search):
+                xyz_np, rgb_np = data_utils.read_stanford(os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, name)), sample_rate)
+                rooms.append((name, torch.from_numpy(xyz_np).float().to(dev), torch.from_numpy(rgb_np).float().to(dev)))
+            areas.clear()                              # (one area's clouds at a time: the images are sorted by area)
+            areas[area] = rooms
+        return areas[area]
+
+    def per_image(k, gt_only=False):
+        filename = filenames[k]
+        area = int(filename.split("/")[-2].split("_")[-1])
+        img_name = filename.split("/")[-1]
+        gt_room = "{}_{}".format(img_name.split("_")[2], img_name.split("_")[3])
+        gt_trans, gt_rot = data_utils.obtain_gt_stanford(area, img_name, root=os.path.join(root, "pose"))
+        gt_trans, gt_rot = gt_trans.astype(np.float32), gt_rot.astype(np.float32)
+        rooms = area_rooms(area)
+        gt_cloud = next((xyz for name, xyz, _ in rooms if name == gt_room), None)
+        if gt_cloud is None:                           # (a list that leaves the ground-truth room out: its cloud still decides the skip)
+            xyz_np, _ = data_utils.read_stanford(os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, gt_room)), sample_rate)
+            gt_cloud = torch.from_numpy(xyz_np).float().to(dev)
+        skipped = bool(out_of_room(gt_cloud, torch.from_numpy(gt_trans), quant)) and not getattr(cfg, "eval_full", False)
+        if gt_only:
+            return gt_trans, gt_rot, skipped
+        if skipped:
+            print("corrupted file : {}, gt_trans is out of the room\n".format(filename))
+            return _nan_row(), gt_trans, gt_rot, True
+        if not rooms:
+            raise FileNotFoundError("room_search: no room clouds under pcd_not_aligned/area_{}".format(area))
+        orig = read_image(filename)
+        img = _to_img(resize_image(orig, orig.shape[1] // dw, orig.shape[0] // dh), dev)
+        img_main = _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        r, t, R, loss, _ = localize_in_rooms(img, img_main, [(xyz, rgb) for _, xyz, rgb in rooms], cfg, init_dict)
+        row = _result_row(t, R, loss, gt_trans, gt_rot, time.time() - t0)
+        name, xyz, rgb = rooms[r]
+        found_idx[k] = r
+        print("\n{}\nfound room : {}\ntranslation error : {}\nrotation error : {}\n".format(img_name, name, float(row[13]), float(row[14])))
+        if log_dir is not None:
+            _save_result_image(os.path.join(log_dir, "results", "area_{}".format(area), img_name), orig, xyz, rgb, t, R,
+                               (img_main.shape[0] // 2, img_main.shape[1] // 2))
+        return row, gt_trans, gt_rot, False
+
+    def gather_found():
+        # this rank's found-room indices (NaN: skipped, or another rank's image) through the same all_gather as the result rows
+        rank, world = pdist.world()
+        mine = pdist.shard(len(filenames), rank, world)
+        local = torch.full((len(mine), 1), float("nan"), dtype=torch.float32, device=dev)
+        for j, k in enumerate(mine):
+            if k in found_idx:
+                local[j, 0] = float(found_idx[k])
+        every = pdist.gather_rows(local, len(filenames), rank, world).cpu().numpy()[:, 0]
+        found.clear()
+        listings = {}
+        for k, v in enumerate(every):
+            if not np.isnan(v):
+                area = area_of(k)
+                if area not in listings:
+                    listings[area] = stanford_area_rooms(root, area, room_search)
+                found[k] = (listings[area][int(v)], gt_room_of(k))
+
+    table = _run_dataset(cfg, writer, log_dir, filenames, per_image, "stanford_results.csv", STANFORD_HEADER + ["found_room"],
+                         lambda f: [int(f.split("/")[-2].split("_")[-1]), f.split("/")[-1]], stanford_success,
+                         row_suffix=lambda k: [found[k][0] if k in found else ""], on_gathered=gather_found)
+    if LAST_RUN:
+        hits = [name == gt for name, gt in found.values()]
+        LAST_RUN["room_accuracy"] = sum(hits) / len(hits) if hits else 0.0
+        LAST_RUN["found_rooms"] = {filenames[k]: v[0] for k, v in found.items()}
+        print("Room accuracy : {}".format(LAST_RUN["room_accuracy"]))
+    return table
 
 
 def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscenes"):

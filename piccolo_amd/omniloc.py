@@ -37,7 +37,7 @@ strict_reference_asserts = True
 # cloud, quantile box or translation grid (a dataset loop touches 4 cloud-side entries per room and 2 per image).
 # An entry is keyed by the identity of the tensors it was made from (address, shape, in-place version) and holds weak
 # references to them: a hit needs the very same live tensor, and entries whose tensors died are purged.
-_CAPACITY = {"cloud": 2, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "trimgroups": 4}
+_CAPACITY = {"cloud": 2, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "trimgroups": 4}
 
 
 class _PackCache:
@@ -399,6 +399,98 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
             input_trans_list[i].copy_(leaf_t[i * B:(i + 1) * B].to(input_trans_list[i].device))
             input_rot_list[i].copy_(leaf_r[i * B:(i + 1) * B].to(input_rot_list[i].device))
     return [[host[i, 0:3].reshape(3, 1).clone(), host[i, 3:12].reshape(3, 3).clone(), host[i, 12].clone()] for i in range(I)]
+
+
+def _rooms_chain(img, rooms, tr, ro, cfg, batch_mode):
+    """One launch chain over at most PCL_GD_MAX_ROOMS rooms (ops.GradientDescentRooms) -> the engine.  `rooms`: (xyz, rgb) pairs; tr / ro:
+    nrooms * per_room rows, room by room.  One texel format for the chain (the one the largest room's refinement would take: fp16 and RGBA8
+    levels give the same bits).  Graph replay under _refine's rule on the chain's points x candidates; the engine (state, workspace, graph,
+    private copies of the packed clouds and boxes whose addresses the graph holds) is cached per room set and launch shape."""
+    clouds = [packed_cloud(xyz, rgb) for xyz, rgb in rooms]
+    boxes = [quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05)) for xyz, _ in rooms]
+    B = int(tr.shape[0])
+    per_room = B // len(rooms)
+    pano = packed_pano(img, n_points=max(int(xyz.shape[0]) for xyz, _ in rooms))
+    num_iter = _cfg(cfg, "num_iter", 100)
+    hyper = (float(_cfg(cfg, "lr", 0.1)), int(_cfg(cfg, "patience", 5)), float(_cfg(cfg, "factor", 0.9)), bool(batch_mode))
+    fuse = None if _cfg(cfg, "gd_fuse", True) else False
+    use_graph = _cfg(cfg, "gd_graph", None)
+    if use_graph is None and ops.EXPERIMENT.gd_graph is not None:                   # experiments
+        use_graph = bool(ops.EXPERIMENT.gd_graph)
+    if use_graph is None:
+        use_graph = sum(c.n for c in clouds) * per_room <= GRAPH_POINT_POSES
+
+    def make(cs, bs):
+        return ops.GradientDescentRooms(list(zip(cs, bs)), pano, tr, ro, lr=hyper[0], patience=hyper[1], factor=hyper[2], batch_mode=hyper[3],
+                                        fuse=fuse)
+    if not use_graph:
+        gd = make(clouds, boxes)
+        gd.run(num_iter)
+        return gd
+
+    def make_private():
+        g = make([ops.Cloud.private_copy(c) for c in clouds], [ops._dev(b).reshape(6).clone() for b in boxes])
+        g._cloud_src = [weakref.ref(c) for c in clouds]
+        g._box_src, g._fresh = list(boxes), True
+        return g
+    xyzs = tuple(xyz for xyz, _ in rooms)
+    gd = _cached("gd_rooms", xyzs, make_private, sub=(per_room, pano.H, pano.W, pano.fmt, fuse) + hyper)
+    fresh, gd._fresh = gd._fresh, False
+    for r, c in enumerate(clouds):
+        if gd._cloud_src[r]() is not c:                # (the colours may change with every query image)
+            gd.clouds[r].data.copy_(c.data)
+            gd._cloud_src[r] = weakref.ref(c)
+        if gd._box_src[r] is not boxes[r]:
+            gd.boxes[r].copy_(ops._dev(boxes[r]).reshape(6))
+            gd._box_src[r] = boxes[r]
+    if not fresh:
+        gd.reset(tr, ro)
+    ops.GradientDescent.set_pano_groups(gd, [pano])     # the pose records name this image's panorama (the graph holds the first one's)
+    gd.run_graph(num_iter)
+    return gd
+
+
+def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scalar_summaries=None, batch_mode=True):
+    """Room search (not in the reference): omniloc_batch of ONE query image against SEVERAL rooms in one launch chain.
+
+    rooms: list of (xyz, rgb) clouds in one frame; input_trans_list / input_rot_list: per room (B,3) starting poses (the same B for every
+    room).  Returns one [t (3,1), R (3,3), loss ()] per room and writes the leaf rows back into the callers' tensors, as omniloc_batch does;
+    room r's result is omniloc_batch(img, *rooms[r], ...)'s bit for bit (batch_mode=False: omniloc_all's sequential semantics, the winner of
+    each room's candidates).  More than PCL_GD_MAX_ROOMS rooms go in several chains; with the depth mask (no rooms instance of the loss
+    kernel) every room runs on its own."""
+    if strict_reference_asserts and batch_mode:
+        assert cfg.num_input > 1
+    R = len(rooms)
+    if R == 0 or len(input_trans_list) != R or len(input_rot_list) != R:
+        raise ValueError("omniloc_batch_rooms: %d rooms, %d / %d starting-pose sets" % (R, len(input_trans_list), len(input_rot_list)))
+    B = int(input_trans_list[0].shape[0])
+    if any(int(t.shape[0]) != B for t in input_trans_list) or any(int(r.shape[0]) != B for r in input_rot_list):
+        raise ValueError("omniloc_batch_rooms: every room needs the same number of starting poses")
+    if bool(_cfg(cfg, "depth_mask", False)):
+        return [omniloc_batch_images([img], xyz, rgb, [input_trans_list[r]], [input_rot_list[r]], cfg, scalar_summaries, batch_mode)[0]
+                for r, (xyz, rgb) in enumerate(rooms)]
+    if R == 1:                                         # one room: the single-room path itself (no concatenation, no per-room write-back)
+        xyz, rgb = rooms[0]
+        if batch_mode:
+            return [omniloc_batch(img, xyz, rgb, input_trans_list[0], input_rot_list[0], cfg, scalar_summaries)]
+        return omniloc_batch_images([img], xyz, rgb, [input_trans_list[0]], [input_rot_list[0]], cfg, scalar_summaries, batch_mode=False)
+    cap = ops._lib.GD_MAX_ROOMS
+    if R > cap:
+        out = []
+        for r0 in range(0, R, cap):
+            out += omniloc_batch_rooms(img, rooms[r0:r0 + cap], input_trans_list[r0:r0 + cap], input_rot_list[r0:r0 + cap], cfg, scalar_summaries,
+                                       batch_mode)
+        return out
+    tr = torch.cat([ops._dev(t).reshape(B, 3) for t in input_trans_list])
+    ro = torch.cat([ops._dev(r).reshape(B, 3) for r in input_rot_list])
+    gd = _rooms_chain(img, rooms, tr, ro, cfg, batch_mode)
+    leaf_t, leaf_r = torch.empty(R * B, 3, dtype=torch.float32, device=tr.device), torch.empty(R * B, 3, dtype=torch.float32, device=tr.device)
+    host = gd.winner(leaf_t, leaf_r).cpu()
+    with torch.no_grad():
+        for r in range(R):
+            input_trans_list[r].copy_(leaf_t[r * B:(r + 1) * B].reshape(input_trans_list[r].shape).to(input_trans_list[r].device))
+            input_rot_list[r].copy_(leaf_r[r * B:(r + 1) * B].reshape(input_rot_list[r].shape).to(input_rot_list[r].device))
+    return [[host[r, 0:3].reshape(3, 1).clone(), host[r, 3:12].reshape(3, 3).clone(), host[r, 12].clone()] for r in range(R)]
 
 
 def sampling_loss(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, return_list=True):

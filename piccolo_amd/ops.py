@@ -854,6 +854,67 @@ class GradientDescent:
         return out
 
 
+class GradientDescentRooms:
+    """On-device GD refinement of ONE panorama against several rooms in one launch chain (pcl_gd_run_rooms): `rooms` is a list of
+    (Cloud, box) pairs, `trans` / `rot` hold nrooms * per_room rows, room r's candidates the rows [r * per_room, (r + 1) * per_room).
+    Every room's results equal those of a GradientDescent over that room alone, bit for bit.  At most PCL_GD_MAX_ROOMS rooms."""
+
+    def __init__(self, rooms, pano, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None):
+        lib = _lib.load()
+        if not 1 <= len(rooms) <= _lib.GD_MAX_ROOMS:
+            raise ValueError("GradientDescentRooms: %d rooms (1..%d per chain)" % (len(rooms), _lib.GD_MAX_ROOMS))
+        self.pano = pano
+        self.clouds = [c for c, _ in rooms]
+        for c in self.clouds:
+            if c.color_sets > 1:
+                raise ValueError("GradientDescentRooms: a room cloud with colour sets")
+        self.boxes = [_dev(b).reshape(6) for _, b in rooms]
+        trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+        self.nrooms = len(rooms)
+        self.B = int(trans.shape[0])
+        if self.B % self.nrooms or self.B == 0:
+            raise ValueError("GradientDescentRooms: %d candidates do not split into %d rooms" % (self.B, self.nrooms))
+        self.per_room = self.B // self.nrooms
+        self.hyper = _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL,
+                                  0, 0.0, 0, 0, 0, -1 if fuse is False else 0, 0, 0)
+        self._rooms = (_lib.GdRoom * self.nrooms)(*[_lib.GdRoom(c.data.data_ptr(), c.n, b.data_ptr()) for c, b in zip(self.clouds, self.boxes)])
+        self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
+        self.ws_bytes = lib.pcl_gd_rooms_workspace_bytes(self._rooms, self.nrooms, self.per_room, ctypes.byref(self.hyper))
+        if self.ws_bytes == 0:
+            raise _lib.PiccoloHipError("pcl_gd_rooms_workspace_bytes: invalid arguments")
+        self.ws = _bytes(self.ws_bytes)
+        _lib.check(lib.pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
+
+    def plan(self):
+        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms"""
+        nch, G, fused = (ctypes.c_int * self.nrooms)(), ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().pcl_gd_plan_rooms(self._rooms, self.nrooms, self.per_room, ctypes.byref(self.hyper), nch, ctypes.byref(G),
+                                                 ctypes.byref(fused)), "pcl_gd_plan_rooms")
+        return list(nch), G.value, bool(fused.value)
+
+    def run(self, num_iter, history=False, timer=None):
+        lib = _lib.load()
+        hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
+        _lib.check(lib.pcl_gd_run_rooms(self._rooms, self.nrooms, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state),
+                                        self.per_room, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
+                                        timer.handle if timer else None, _stream()), "pcl_gd_run_rooms")
+        return hist
+
+    run_graph = GradientDescent.run_graph          # capture run(num_iter) once per num_iter, replay it
+
+    def reset(self, trans, rot):
+        """New starting poses for the same rooms / panorama / shape (lets one captured graph serve many refinements)."""
+        trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+        assert trans.shape[0] == self.B
+        _lib.check(_lib.load().pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
+
+    def winner(self, leaf_trans=None, leaf_rot=None):
+        """(nrooms, 16): per room the candidate omniloc_batch returns (see GradientDescent.winner)."""
+        return GradientDescent.winner(self, self.nrooms, leaf_trans, leaf_rot)
+
+    result = GradientDescent.result
+
+
 class KernelTimer:
     """HIP-event pairs around every fused loss+gradient launch of GradientDescent.run (measurement aid)."""
 

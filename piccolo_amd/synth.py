@@ -160,3 +160,28 @@ def mark_levels(img):
     device-side exactness flag back — one blocking D2H copy per query image less.  Untagged tensors are checked as before."""
     img._pcl_levels = img._version          # (an in-place change of the tensor afterwards voids the tag)
     return img
+
+
+ROOM_GAP = 1.0        # metres of empty space between neighbouring rooms of `rooms_side_by_side`
+
+
+def room_offset(r):
+    """Centre of room r of `rooms_side_by_side` in the shared frame: the rooms stand in a row along x."""
+    return np.array([r * (ROOM[0] + ROOM_GAP), 0.0, 0.0], np.float32)
+
+
+def rooms_side_by_side(sizes, seed=0):
+    """Room search scenes: len(sizes) box rooms of sizes[r] points in ONE frame, side by side along x without overlapping, each with
+    its own colour field (a per-room phase of the box room's colours), so that no two rooms look alike.  -> list of (xyz, rgb) float32."""
+    out = []
+    for r, n in enumerate(sizes):
+        xyz, _ = box_room(int(n), seed=seed + r)
+        rgb = 0.5 + 0.45 * np.sin(xyz.astype(np.float64) @ _K.T + _PHI + 1.7 * (r + 1) + np.array([0.0, 0.9, 2.1]) * r)
+        out.append(((xyz + room_offset(r)[None, :]).astype(np.float32), rgb.astype(np.float32)))
+    return out
+
+
+def room_gt_pose(r, seed):
+    """Ground-truth (t (3,), ypr (3,)) of a query image taken in room r of `rooms_side_by_side`: gt_pose(seed) moved into that room."""
+    t, ypr = gt_pose(seed)
+    return (t + room_offset(r)).astype(np.float32), ypr

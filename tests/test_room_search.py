@@ -1,0 +1,249 @@
+"""GPU tests of the room search (ABI 11): one panorama refined against several rooms in one launch chain.  Every room's result must be
+the single-room refinement's, bit for bit — state, loss history, winner and the leaf rows written back — whatever the fuse / graph /
+batch-mode choice, across the 32-room chain cap and through the depth-mask fallback; end to end, localize_in_rooms and the Stanford
+harness with room_search must find the room a query was taken in."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import Cfg
+
+pytestmark = pytest.mark.gpu
+
+H, W = 256, 512
+SIZES = (700, 120_000, 166_667)              # the smallest has fewer steps than chunks
+
+
+def _cfg(**kw):
+    base = dict(lr=0.1, num_iter=25, patience=5, factor=0.8, out_of_room_quantile=0.05, num_input=6)
+    base.update(kw)
+    return Cfg(**base)
+
+
+def _rooms(sizes, seed=0):
+    from piccolo_amd import synth
+    return [(torch.from_numpy(x).cuda(), torch.from_numpy(c).cuda()) for x, c in synth.rooms_side_by_side(sizes, seed)]
+
+
+def _query(rooms, r, seed):
+    """the panorama room r shows from room_gt_pose(r, seed) (its own cloud: the walls hide the other rooms)"""
+    from piccolo_amd import ops, synth
+    t, ypr = synth.room_gt_pose(r, seed)
+    xyz, rgb = rooms[r]
+    img = synth.quantise_like_image_file(ops.make_pano(ops.transform_cloud(xyz, torch.from_numpy(t), torch.from_numpy(ypr)), rgb, (H, W)))
+    return img, t, ypr
+
+
+def _starts(nrooms, per_room, seed=3):
+    from piccolo_amd import synth
+    out = []
+    for r in range(nrooms):
+        t, ypr = synth.room_gt_pose(r, seed + r)
+        tr, ro = synth.start_poses(t, ypr, per_room, seed=seed + 7 * r, sigma_t=0.4, sigma_r=0.2)
+        out.append((torch.from_numpy(tr).cuda(), torch.from_numpy(ro).cuda()))
+    return out
+
+
+def _single(img, room, tr, ro, cfg, batch_mode):
+    from piccolo_amd import omniloc as po
+    if batch_mode:
+        return po.omniloc_batch(img, room[0], room[1], tr, ro, cfg, {})
+    return po.omniloc_batch_images([img], room[0], room[1], [tr], [ro], cfg, batch_mode=False)[0]
+
+
+def _compare_rooms(img, rooms, starts, cfg, batch_mode=True):
+    """omniloc_batch_rooms against one single-room call per room: t, R, loss and the leaf rows, bit for bit"""
+    from piccolo_amd import omniloc as po
+    tr_m = [t.clone() for t, _ in starts]
+    ro_m = [r.clone() for _, r in starts]
+    got = po.omniloc_batch_rooms(img, rooms, tr_m, ro_m, cfg, batch_mode=batch_mode)
+    assert len(got) == len(rooms)
+    for r, room in enumerate(rooms):
+        tr, ro = starts[r][0].clone(), starts[r][1].clone()
+        want = _single(img, room, tr, ro, cfg, batch_mode)
+        for k in range(3):
+            assert torch.equal(got[r][k], want[k]), (r, k, got[r][k], want[k])
+        assert torch.equal(tr_m[r], tr) and torch.equal(ro_m[r], ro), r
+    return got
+
+
+@pytest.mark.parametrize("batch_mode", [True, False])
+@pytest.mark.parametrize("fuse", [True, False])
+@pytest.mark.parametrize("graph", [True, False])
+def test_rooms_chain_equals_single_room_calls_bit_for_bit(batch_mode, fuse, graph):
+    rooms = _rooms(SIZES)
+    img, _, _ = _query(rooms, 1, 5)
+    cfg = _cfg(gd_fuse=fuse, gd_graph=graph)
+    _compare_rooms(img, rooms, _starts(len(rooms), 6), cfg, batch_mode)
+    if graph:                                         # a second image through the cached engine (replay, new poses and panorama)
+        img2, _, _ = _query(rooms, 2, 9)
+        _compare_rooms(img2, rooms, _starts(len(rooms), 6, seed=11), cfg, batch_mode)
+
+
+@pytest.mark.parametrize("fuse", [None, False])
+def test_rooms_engine_history_equals_single_room_history(fuse):
+    from piccolo_amd import ops
+    from piccolo_amd import omniloc as po
+    rooms = _rooms(SIZES, seed=4)
+    img, _, _ = _query(rooms, 0, 2)
+    starts = _starts(len(rooms), 6, seed=5)
+    pano = ops.Pano(img, fmt="f16")
+    clouds = [po.packed_cloud(x, c) for x, c in rooms]
+    boxes = [ops.quantile_box(x, 0.05) for x, _ in rooms]
+    tr = torch.cat([t for t, _ in starts])
+    ro = torch.cat([r for _, r in starts])
+    gd = ops.GradientDescentRooms(list(zip(clouds, boxes)), pano, tr, ro, lr=0.1, patience=5, factor=0.8, fuse=fuse)
+    nch, G, fused = gd.plan()
+    assert G == 2 and fused == (fuse is None and sum(c * 3 for c in nch) <= 1024)
+    hist = gd.run(31, history=True)
+    res = gd.result()
+    for r in range(len(rooms)):
+        one = ops.GradientDescent(clouds[r], pano, starts[r][0], starts[r][1], boxes[r], lr=0.1, patience=5, factor=0.8, fuse=fuse)
+        h1 = one.run(31, history=True)
+        assert torch.equal(hist[:, 6 * r:6 * (r + 1)], h1), r
+        assert torch.equal(res[6 * r:6 * (r + 1)], one.result()), r
+
+
+FUSED_SIZES = (700, 20_000, 60_000)          # 24 + 120 + 360 blocks at 6 candidates: the whole chain fits one launch per iteration
+
+
+def test_fused_rooms_chain_equals_single_rooms_and_the_two_launch_form():
+    from piccolo_amd import ops
+    from piccolo_amd import omniloc as po
+    rooms = _rooms(FUSED_SIZES, seed=9)
+    img, _, _ = _query(rooms, 2, 6)
+    starts = _starts(len(rooms), 6, seed=13)
+    pano = ops.Pano(img, fmt="f16")
+    clouds = [po.packed_cloud(x, c) for x, c in rooms]
+    boxes = [ops.quantile_box(x, 0.05) for x, _ in rooms]
+    tr = torch.cat([t for t, _ in starts])
+    ro = torch.cat([r for _, r in starts])
+    out = {}
+    for fuse in (None, False):
+        for n_iter in (1, 2, 31):                                     # (the fused form's first, second and an odd number of launches)
+            gd = ops.GradientDescentRooms(list(zip(clouds, boxes)), pano, tr, ro, lr=0.1, patience=5, factor=0.8, fuse=fuse)
+            assert gd.plan()[2] is (fuse is None), gd.plan()
+            hist = gd.run(n_iter, history=True)
+            res = gd.result()
+            out[fuse, n_iter] = (hist, res)
+            for r in range(len(rooms)):
+                one = ops.GradientDescent(clouds[r], pano, starts[r][0], starts[r][1], boxes[r], lr=0.1, patience=5, factor=0.8, fuse=fuse)
+                h1 = one.run(n_iter, history=True)
+                assert torch.equal(hist[:, 6 * r:6 * (r + 1)], h1), (fuse, n_iter, r)
+                assert torch.equal(res[6 * r:6 * (r + 1)], one.result()), (fuse, n_iter, r)
+        # continuing a state: a second run() call after the first
+        gd = ops.GradientDescentRooms(list(zip(clouds, boxes)), pano, tr, ro, lr=0.1, patience=5, factor=0.8, fuse=fuse)
+        gd.run(20)
+        h2 = gd.run(11, history=True)
+        assert torch.equal(h2, out[fuse, 31][0][20:]) and torch.equal(gd.result(), out[fuse, 31][1]), fuse
+    for n_iter in (1, 2, 31):
+        assert torch.equal(out[None, n_iter][0], out[False, n_iter][0]) and torch.equal(out[None, n_iter][1], out[False, n_iter][1]), n_iter
+    # and through omniloc_batch_rooms, fused by default and with gd_fuse = False, eager and replayed, both batch modes
+    for fuse in (True, False):
+        for graph in (True, False):
+            for batch_mode in (True, False):
+                _compare_rooms(img, rooms, starts, _cfg(gd_fuse=fuse, gd_graph=graph), batch_mode)
+
+
+def test_odd_candidates_and_a_single_room():
+    rooms = _rooms((5_000, 90_000, 166_667), seed=7)
+    img, _, _ = _query(rooms, 2, 4)
+    cfg = _cfg(num_input=5)
+    _compare_rooms(img, rooms, _starts(3, 5, seed=2), cfg)                               # per_room 5: one pose per block (G = 1)
+    _compare_rooms(img, rooms[1:2], _starts(1, 6, seed=8), _cfg())                        # R = 1 is omniloc_batch
+
+
+def test_more_rooms_than_one_chain_takes():
+    sizes = [2_000 + 997 * r for r in range(40)]
+    rooms = _rooms(sizes, seed=1)
+    img, _, _ = _query(rooms, 17, 3)
+    _compare_rooms(img, rooms, _starts(40, 4, seed=6), _cfg(num_input=4, num_iter=12))
+
+
+def test_depth_mask_falls_back_to_one_chain_per_room():
+    rooms = _rooms((30_000, 60_000), seed=2)
+    img, _, _ = _query(rooms, 0, 1)
+    _compare_rooms(img, rooms, _starts(2, 6, seed=4), _cfg(num_iter=10, depth_mask=True))
+
+
+INIT = dict(num_trans=30, xy_only=False, yaw_only=False, num_yaw=4, num_pitch=4, num_roll=4, criterion="loss_histogram", num_intermediate=20,
+            num_input=8, num_split_h=4, num_split_w=4, lr=0.1, num_iter=100, patience=5, factor=0.8, out_of_room_quantile=0.05, sample_rate=1,
+            parallel=True, num_bins=256)
+
+
+def test_localize_in_rooms_finds_the_room_on_synthetic_rooms():
+    from piccolo_amd import localize, synth
+    rooms = _rooms((100_000, 100_000, 100_000), seed=30)
+    cfg = Cfg(dataset="Stanford2D-3D-S", sharpen_color=True, **INIT)
+    init = localize.get_init_dict(cfg)
+    for r in range(3):
+        img, t_gt, ypr_gt = _query(rooms, r, 40 + r)
+        k, t, R, loss, losses = localize.localize_in_rooms(img, img, rooms, cfg, init)
+        assert losses.shape == (3,) and k == int(torch.argmin(losses)) and torch.equal(loss, losses[k])
+        t_err, r_err = localize.pose_errors(t, R, t_gt, synth.rot_from_ypr_np(ypr_gt))
+        assert k == r and localize.stanford_success(t_err, r_err), (r, losses, t_err, r_err)
+
+
+def _write_rooms_tree(root):
+    """a Stanford2D-3D-S tree of three rooms side by side in area 2, one query panorama per room -> [(panorama file, its room)]"""
+    from PIL import Image
+    from piccolo_amd import ops, synth
+    from test_dataset_harness import _euler_for_stanford, _write_cloud
+    names = ["hallway_1", "office_1", "office_2"]
+    scenes = synth.rooms_side_by_side((100_000, 100_000, 100_000), seed=30)
+    os.makedirs(root / "pano/area_2")
+    os.makedirs(root / "pose/area_2")
+    files = []
+    for r, (name, (xyz, rgb)) in enumerate(zip(names, scenes)):
+        rgb8 = np.clip(np.round(rgb * 255), 0, 255).astype(np.uint8)
+        _write_cloud(str(root / "pcd_not_aligned/area_2" / (name + ".txt")), xyz, rgb8)
+        X, C = torch.from_numpy(xyz).cuda(), torch.from_numpy(rgb8.astype(np.float32) / np.float32(255)).cuda()
+        t, ypr = synth.room_gt_pose(r, 40 + r)
+        pano = ops.make_pano(ops.transform_cloud(X, torch.from_numpy(t), torch.from_numpy(ypr)), C, (H, W)).cpu().numpy().astype(np.uint8)
+        stem = "camera_c%03d_%s_frame_equirectangular_domain" % (r, name)
+        Image.fromarray(pano).save(root / "pano/area_2" / (stem + "_rgb.png"))
+        with open(root / "pose/area_2" / (stem + "_pose.json"), "w") as f:
+            json.dump({"camera_location": [float(v) for v in t], "final_camera_rotation": _euler_for_stanford(synth.rot_from_ypr_np(ypr))}, f)
+        files.append((stem + "_rgb.png", name))
+    return files
+
+
+def test_stanford_harness_room_search_finds_every_images_room(tmp_path):
+    import csv
+    from piccolo_amd import localize
+    root = tmp_path / "stanford"
+    files = _write_rooms_tree(root)
+    log = tmp_path / "log"
+    cfg = Cfg(dataset="Stanford2D-3D-S", area=2, sharpen_color=True, room_search=True, **INIT)
+    table = localize.localize_stanford(cfg, None, str(log), root=str(root)).cpu().numpy()
+    assert table.shape[0] == 3 and not np.isnan(table).any()
+    assert localize.LAST_RUN["room_accuracy"] == 1.0 and localize.LAST_RUN["skipped"] == []
+    with open(log / "stanford_results.csv") as f:
+        rows = list(csv.reader(f))
+    assert rows[0][-1] == "found_room" and rows[0][:-1] == localize.STANFORD_HEADER
+    found = {row[1]: row[-1] for row in rows[1:]}
+    for fname, name in files:
+        assert found[fname] == name, (fname, found)
+        assert localize.LAST_RUN["found_rooms"][str(root / "pano/area_2" / fname)] == name
+    assert (log / "results/area_2" / files[0][0]).exists()
+
+
+def test_room_search_on_two_ranks_writes_every_images_found_room(tmp_path):
+    """main.py with room_search under torch.distributed.run with two ranks: every rank localises its share of the images, the found rooms
+    travel with the gathered result rows, and rank 0's CSV equals the single-process one in every column but the wall time — found_room
+    and the room accuracy included."""
+    from test_dataset_harness import _csv_without_time, _run_main
+    files = _write_rooms_tree(tmp_path / "data" / "stanford")
+    ini = tmp_path / "rooms.ini"
+    keys = dict(INIT, dataset="Stanford2D-3D-S", area=2, sharpen_color=True, room_search=True)
+    ini.write_text("[All]\n" + "".join("%s = %s\n" % kv for kv in keys.items()))
+    one = _run_main(["--config", str(ini)], 1, tmp_path / "r1", cwd=tmp_path)
+    two = _run_main(["--config", str(ini)], 2, tmp_path / "r2", cwd=tmp_path)
+    a, b = _csv_without_time(tmp_path / "r1" / "stanford_results.csv"), _csv_without_time(tmp_path / "r2" / "stanford_results.csv")
+    assert len(a) == 4 and a == b, (a, b)
+    assert a[0][-1] == "found_room" and {r[1]: r[-1] for r in a[1:]} == dict(files)
+    for out in (one, two):
+        assert out.count("Room accuracy : 1.0") == 1, out[-2000:]
