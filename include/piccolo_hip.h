@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define PCL_ABI_VERSION 11 /* 11: room search — several clouds in one refinement chain (pcl_gd_room, pcl_gd_rooms_workspace_bytes, pcl_gd_plan_rooms, pcl_gd_run_rooms); 10: per-image colour sets (pcl_cloud_sets_bytes / pcl_cloud_pack_sets, pcl_gd_hyper.color_sets, pcl_trim_loss_images_sets, pcl_hist_trim_*_sets); 9: pcl_gd_hyper.fuse, pcl_loss_depth_workspace_bytes takes the occluder stride, pcl_trim_order + the `order` argument of pcl_trim_loss[_images], the library reads no environment variable; 8: PCL_PANO_U8V / pcl_pano_pack_u8v; 7: depth mask on its own grid (pcl_gd_hyper.depth_h / depth_w, pcl_depth_default, pcl_sampling_loss_depth), refresh rule and pcl_gd_depth_refresh_counts removed, pcl_gd_step_from_grads; 6: pcl_select_poses, pcl_gd_set_pano_groups, pcl_gd_winner; 2: fp16-level texels, colour preprocessing, histograms, dataset text reader; 3: backward of the stand-alone ops; 4: pcl_hist_trim_workspace_bytes_n; 5: pcl_source_hash, pcl_timer_calibrate, pcl_trim_*, pcl_gd_plan */
+#define PCL_ABI_VERSION 12 /* 12: room search over several panoramas — images x rooms in one chain (pcl_gd_rooms_images_workspace_bytes, pcl_gd_plan_rooms_images, pcl_gd_init_rooms_images, pcl_gd_run_rooms_images); 11: room search — several clouds in one refinement chain (pcl_gd_room, pcl_gd_rooms_workspace_bytes, pcl_gd_plan_rooms, pcl_gd_run_rooms); 10: per-image colour sets (pcl_cloud_sets_bytes / pcl_cloud_pack_sets, pcl_gd_hyper.color_sets, pcl_trim_loss_images_sets, pcl_hist_trim_*_sets); 9: pcl_gd_hyper.fuse, pcl_loss_depth_workspace_bytes takes the occluder stride, pcl_trim_order + the `order` argument of pcl_trim_loss[_images], the library reads no environment variable; 8: PCL_PANO_U8V / pcl_pano_pack_u8v; 7: depth mask on its own grid (pcl_gd_hyper.depth_h / depth_w, pcl_depth_default, pcl_sampling_loss_depth), refresh rule and pcl_gd_depth_refresh_counts removed, pcl_gd_step_from_grads; 6: pcl_select_poses, pcl_gd_set_pano_groups, pcl_gd_winner; 2: fp16-level texels, colour preprocessing, histograms, dataset text reader; 3: backward of the stand-alone ops; 4: pcl_hist_trim_workspace_bytes_n; 5: pcl_source_hash, pcl_timer_calibrate, pcl_trim_*, pcl_gd_plan */
 
 #define PCL_EINVAL (-1)   /* bad size / null pointer / unsupported argument */
 #define PCL_EWORKSPACE (-2) /* workspace too small */
@@ -250,6 +250,34 @@ int pcl_gd_plan_rooms(const pcl_gd_room *rooms_host, int nrooms, int per_room, c
 int pcl_gd_run_rooms(const pcl_gd_room *rooms_host, int nrooms, const void *pano, int pano_format, int H, int W, void *state, int per_room,
                      const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace, size_t workspace_bytes, void *timer,
                      void *stream);
+
+/* Room search over several panoramas (ABI 12): nimages query panoramas x nrooms rooms x per_image candidates in ONE launch chain.
+ * Candidate (r, i, j) is record (r * nimages + i) * per_image + j of a state of B = nrooms * nimages * per_image candidates
+ * (pcl_gd_state_bytes / pcl_gd_result as for pcl_gd_run; pcl_gd_winner(state, nrooms * nimages, per_image, ...) gives one winner per
+ * (room, image)).  Image i's panorama travels in its candidates' pose records: pcl_gd_set_pano_groups with the nrooms * nimages
+ * addresses pano[i] repeated room by room; `pano` is the default for records that name none.  hyper->color_sets 0 / 1: the images share
+ * room r's colours (pcl_cloud_pack); hyper->color_sets == nimages: every room's cloud holds one set per image (pcl_cloud_pack_sets with
+ * nimages sets) and candidate (r, i, .) reads set i of room r — pcl_gd_init_rooms_images writes that into the pose records (it is
+ * pcl_gd_init for this layout; pcl_gd_init itself would number the sets through the rooms).
+ * Room r runs the SINGLE-IMAGE plan pcl_gd_plan(n_r, per_image) — chunks, poses per block, steps per chunk — for all nimages * per_image of
+ * its candidates, with shared colours too, and a group of poses never straddles two images.  Contract: for every (r, i) the state, pose
+ * records and loss-history columns equal those of a pcl_gd_run of room r with image i alone (per_image candidates, image i's colours, same
+ * hyper-parameters) BIT FOR BIT — fused or two launches, eager or replayed, both modes, every nrooms >= 1 and nimages >= 1.
+ * An iteration is one launch when the blocks of all rooms and images together fit the fuse rule (hyper->fuse < 0: never), else two; the
+ * room table is written by one small launch from kernel arguments, so a call stays capturable.  nimages == 1 is pcl_gd_run_rooms.
+ * PCL_EINVAL (0 from the sizing function), before any HIP call: null arguments, hyper->depth_mask, nrooms outside 1..PCL_GD_MAX_ROOMS,
+ * nimages < 1, per_image < 1, hyper->color_sets other than 0, 1 or nimages, a room with a null cloud or box or n outside
+ * 1..PCL_MAX_POINTS, a room whose cloud of nimages sets passes 2^31 bytes (pcl_cloud_sets_bytes answers 0: the caller groups its images).
+ * PCL_EWORKSPACE: workspace_bytes below pcl_gd_rooms_images_workspace_bytes. */
+size_t pcl_gd_rooms_images_workspace_bytes(const pcl_gd_room *rooms_host, int nrooms, int nimages, int per_image, const pcl_gd_hyper *hyper_host);
+/* host-only: as pcl_gd_plan_rooms */
+int pcl_gd_plan_rooms_images(const pcl_gd_room *rooms_host, int nrooms, int nimages, int per_image, const pcl_gd_hyper *hyper_host,
+                             int *nchunks_host, int *poses_per_block_host, int *fused_host);
+int pcl_gd_init_rooms_images(void *state, const float *trans, const float *rot, int nrooms, int nimages, int per_image,
+                             const pcl_gd_hyper *hyper_host, void *stream);
+int pcl_gd_run_rooms_images(const pcl_gd_room *rooms_host, int nrooms, int nimages, const void *pano, int pano_format, int H, int W, void *state,
+                            int per_image, const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace,
+                            size_t workspace_bytes, void *timer, void *stream);
 
 /* ---- kernel timer (measurement aid, HOST object) --------------------------------------------------------------
  * A pool of hipEvent pairs.  When a timer is passed to pcl_gd_run, every launch of the fused loss+gradient kernel is

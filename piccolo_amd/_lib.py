@@ -11,7 +11,7 @@ from . import build as _build
 _c = ctypes
 _vp, _i64, _int, _sz, _dbl = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_size_t, _c.c_double
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 RESULT_STRIDE = 8
 GD_RESULT_STRIDE = 16
 GD_SEQUENTIAL, GD_BATCH = 0, 1
@@ -108,6 +108,10 @@ SIGNATURES = {
     "pcl_gd_rooms_workspace_bytes": (_sz, [_c.POINTER(GdRoom), _int, _int, _c.POINTER(GdHyper)]),
     "pcl_gd_plan_rooms": (_int, [_c.POINTER(GdRoom), _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
     "pcl_gd_run_rooms": (_int, [_c.POINTER(GdRoom), _int, _vp, _int, _int, _int, _vp, _int, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
+    "pcl_gd_rooms_images_workspace_bytes": (_sz, [_c.POINTER(GdRoom), _int, _int, _int, _c.POINTER(GdHyper)]),
+    "pcl_gd_plan_rooms_images": (_int, [_c.POINTER(GdRoom), _int, _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
+    "pcl_gd_init_rooms_images": (_int, [_vp, _vp, _vp, _int, _int, _int, _c.POINTER(GdHyper), _vp]),
+    "pcl_gd_run_rooms_images": (_int, [_c.POINTER(GdRoom), _int, _int, _vp, _int, _int, _int, _vp, _int, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
     "pcl_select_poses": (_int, [_vp, _int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp]),
     "pcl_cloud2idx": (_int, [_vp, _i64, _vp, _vp]),
     "pcl_sample_from_img": (_int, [_vp, _int, _int, _int, _vp, _i64, _vp, _vp]),

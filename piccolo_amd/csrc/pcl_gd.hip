@@ -20,9 +20,9 @@ size_t pcl_partials_bytes(int64_t n, int B, int sets = 1);
 int pcl_plan_nchunks(int64_t n, int B, int sets = 1);
 int pcl_plan_nblocks(int64_t n, int B, int sets = 1);
 int pcl_plan_G(int64_t n, int B, int sets = 1);
-void pcl_plan_room(int64_t n, int per_room, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
+void pcl_plan_room_images(int64_t n, int per_image, int nimages, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
 int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
-                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse);
+                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, int color_sets = 1);
 size_t pcl_depth_zbuf_bytes(int B, int Hd, int Wd);
 int pcl_launch_zbuffers(const float* cloud, int64_t n, const PclPoseRec* poses, int B, const PclDepthGrid& g, int zstride, uint32_t* zbuf, bool fill,
                         hipStream_t s);
@@ -519,17 +519,26 @@ __global__ void pcl_gd_rooms_table_kernel(PclRoomTable t, PclRoomTable* dst)
 // the host side of a multi-room chain: every room's plan, partials region and block range, the sizes, the checks
 struct GdRooms {
     PclRoomTable t;
-    int nrooms, per_room, G, ngroups, nblk;
+    int nrooms, per_room, G, ngroups, nblk;   // per_room: candidates of one room (rooms x images chains: of all its images); ngroups likewise
+    int sets;                    // colour sets of every room's cloud (rooms x images chains with per-image colours), else 1
     size_t partials_bytes;       // one partials buffer, all rooms (each region 256-byte aligned)
 };
 
-static int gd_rooms_setup(const pcl_gd_room* rooms_host, int nrooms, int per_room, const pcl_gd_hyper* hyper_host, GdRooms* g)
+// Room r holds nimages * per_image candidates, image by image, and runs the single-image plan pcl_plan(n_r, per_image) for all of them;
+// hyper->color_sets is 0 / 1 (the images share the room's colours) or nimages (every room's cloud holds a set per image).
+// pcl_gd_run_rooms' chain of one panorama is nimages = 1 (per_image its per_room: the room's own plan, and no colour sets above 1).
+static int gd_rooms_setup(const pcl_gd_room* rooms_host, int nrooms, int nimages, int per_image, const pcl_gd_hyper* hyper_host, GdRooms* g)
 {
-    if (!rooms_host || !hyper_host || nrooms < 1 || nrooms > PCL_GD_MAX_ROOMS || per_room <= 0) return PCL_EINVAL;
-    if (hyper_host->depth_mask || hyper_host->color_sets > 1 || hyper_host->color_sets < 0) return PCL_EINVAL;
-    if ((int64_t)nrooms * per_room > 0x7fffffff / 2) return PCL_EINVAL;
-    for (int r = 0; r < nrooms; r++)
+    if (!rooms_host || !hyper_host || nrooms < 1 || nrooms > PCL_GD_MAX_ROOMS || per_image <= 0 || nimages < 1) return PCL_EINVAL;
+    if (hyper_host->depth_mask || hyper_host->color_sets < 0) return PCL_EINVAL;
+    if (hyper_host->color_sets > 1 && hyper_host->color_sets != nimages) return PCL_EINVAL;
+    if ((int64_t)nrooms * per_image * nimages > 0x7fffffff / 2) return PCL_EINVAL;
+    const int per_room = per_image * nimages;
+    g->sets = hyper_host->color_sets > 1 ? hyper_host->color_sets : 1;
+    for (int r = 0; r < nrooms; r++) {
         if (!rooms_host[r].cloud || !rooms_host[r].box || rooms_host[r].n <= 0 || rooms_host[r].n > PCL_MAX_POINTS) return PCL_EINVAL;
+        if (g->sets > 1 && pcl_cloud_sets_bytes(rooms_host[r].n, g->sets) == 0) return PCL_EINVAL;
+    }
     memset(&g->t, 0, sizeof(g->t));
     g->nrooms = nrooms; g->per_room = per_room;
     int64_t blocks = 0, floats = 0;
@@ -537,8 +546,8 @@ static int gd_rooms_setup(const pcl_gd_room* rooms_host, int nrooms, int per_roo
     for (int r = 0; r < nrooms; r++) {
         PclRoomRec& e = g->t.rec[r];
         int G, ngroups;
-        pcl_plan_room(rooms_host[r].n, per_room, &G, &ngroups, &e.nchunks, &e.seg_len, &e.steps_base, &e.steps_rem);
-        g->G = G; g->ngroups = ngroups;              // (pcl_plan's poses per block depend on per_room alone: the same for every room)
+        pcl_plan_room_images(rooms_host[r].n, per_image, nimages, &G, &ngroups, &e.nchunks, &e.seg_len, &e.steps_base, &e.steps_rem);
+        g->G = G; g->ngroups = ngroups;              // (pcl_plan's poses per block depend on per_image alone: the same for every room)
         e.cloud = (unsigned long long)rooms_host[r].cloud; e.box = (unsigned long long)rooms_host[r].box;
         e.n = (int)rooms_host[r].n; e.stride = (int)pcl_cloud_stride(rooms_host[r].n);
         e.block0 = (int)blocks; e.group0 = r * ngroups; e.partials = floats;
@@ -556,7 +565,7 @@ static int gd_rooms_setup(const pcl_gd_room* rooms_host, int nrooms, int per_roo
 extern "C" size_t pcl_gd_rooms_workspace_bytes(const pcl_gd_room* rooms_host, int nrooms, int per_room, const pcl_gd_hyper* hyper_host)
 {
     GdRooms g;
-    if (gd_rooms_setup(rooms_host, nrooms, per_room, hyper_host, &g)) return 0;
+    if (gd_rooms_setup(rooms_host, nrooms, 1, per_room, hyper_host, &g)) return 0;
     return gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes);
 }
 
@@ -564,7 +573,7 @@ extern "C" int pcl_gd_plan_rooms(const pcl_gd_room* rooms_host, int nrooms, int 
                                  int* poses_per_block_host, int* fused_host)
 {
     GdRooms g;
-    const int rc = gd_rooms_setup(rooms_host, nrooms, per_room, hyper_host, &g);
+    const int rc = gd_rooms_setup(rooms_host, nrooms, 1, per_room, hyper_host, &g);
     if (rc) return rc;
     if (nchunks_host)
         for (int r = 0; r < nrooms; r++) nchunks_host[r] = g.t.rec[r].nchunks;
@@ -573,29 +582,13 @@ extern "C" int pcl_gd_plan_rooms(const pcl_gd_room* rooms_host, int nrooms, int 
     return 0;
 }
 
-// pcl_gd_run for several rooms: the same iteration loop, fused and two-launch forms, with the rooms instances of the loss kernel and
-// the rooms epilogue (flip and timer as there; the XCDs always split the chunks — one panorama)
-extern "C" int pcl_gd_run_rooms(const pcl_gd_room* rooms_host, int nrooms, const void* pano, int pano_format, int H, int W, void* state, int per_room,
-                                const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace, size_t workspace_bytes,
-                                void* timer, void* stream)
+// the iteration loop of a multi-room chain whose plan `g` holds (pcl_gd_run_rooms, pcl_gd_run_rooms_images): table launch, then per
+// iteration the rooms loss launch (+ the rooms epilogue in the two-launch form); flip and timer as in pcl_gd_run
+static int gd_rooms_chain(const GdRooms& g, const void* pano, int pano_format, int H, int W, void* state, const pcl_gd_hyper* hyper_host, int num_iter,
+                          float* loss_history, void* workspace, PclTimer* tm, hipStream_t s)
 {
-    PclTimer* tm = (PclTimer*)timer;
-    if (!rooms_host || !pano || !state || !hyper_host || !workspace || H <= 0 || W <= 0 || num_iter < 0) return PCL_EINVAL;
-    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
-    GdRooms g;
-    int rc = gd_rooms_setup(rooms_host, nrooms, per_room, hyper_host, &g);
-    if (rc) return rc;
-    if (workspace_bytes < gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes)) return PCL_EWORKSPACE;
-    // one room: pcl_gd_run itself (the same plan and arithmetic — and no room look-up in front of every block: 1.2 us per iteration at the
-    // shipped shape, tools/room_bench.py).  Its workspace, two partials buffers of the same plan, fits in this one.
-    if (nrooms == 1) {
-        pcl_gd_hyper h = *hyper_host;
-        h.images = 0;
-        return pcl_gd_run(rooms_host[0].cloud, rooms_host[0].n, pano, pano_format, H, W, state, per_room, rooms_host[0].box, &h, num_iter, loss_history,
-                          workspace, workspace_bytes, timer, stream);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int B = nrooms * per_room, G = g.G;
+    const int nrooms = g.nrooms, B = nrooms * g.per_room, G = g.G;
+    int rc;
     PclRoomTable* table = (PclRoomTable*)workspace;
     float* partials2[2] = {(float*)((char*)workspace + gd_align(sizeof(PclRoomTable))),
                            (float*)((char*)workspace + gd_align(sizeof(PclRoomTable)) + gd_align(g.partials_bytes))};
@@ -630,9 +623,9 @@ extern "C" int pcl_gd_run_rooms(const pcl_gd_room* rooms_host, int nrooms, const
             f.box = nullptr;                                  // (every room's own box: the room table)
             f.factor = hyper_host->factor; f.patience = (int)hyper_host->patience; f.mode = (int)hyper_host->mode;
             f.loss_out = loss_history ? loss_history + (int64_t)(it - 1) * B : nullptr;
-            rc = pcl_launch_loss_rooms(table, pano, pano_format, H, W, f.recs_in, B, G, g.ngroups, g.nblk, partials2[cout], s, flip, &f);
+            rc = pcl_launch_loss_rooms(table, pano, pano_format, H, W, f.recs_in, B, G, g.ngroups, g.nblk, partials2[cout], s, flip, &f, g.sets);
         } else {
-            rc = pcl_launch_loss_rooms(table, pano, pano_format, H, W, gd_recs(state, B), B, G, g.ngroups, g.nblk, partials2[0], s, flip, nullptr);
+            rc = pcl_launch_loss_rooms(table, pano, pano_format, H, W, gd_recs(state, B), B, G, g.ngroups, g.nblk, partials2[0], s, flip, nullptr, g.sets);
         }
         if (rc) return rc;
         if (timed) {
@@ -651,6 +644,100 @@ extern "C" int pcl_gd_run_rooms(const pcl_gd_room* rooms_host, int nrooms, const
         PCL_LAUNCH_CHECK();
     }
     return 0;
+}
+
+// pcl_gd_run for several rooms: the same iteration loop, fused and two-launch forms, with the rooms instances of the loss kernel and
+// the rooms epilogue (flip and timer as there; the XCDs always split the chunks — one panorama)
+extern "C" int pcl_gd_run_rooms(const pcl_gd_room* rooms_host, int nrooms, const void* pano, int pano_format, int H, int W, void* state, int per_room,
+                                const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace, size_t workspace_bytes,
+                                void* timer, void* stream)
+{
+    PclTimer* tm = (PclTimer*)timer;
+    if (!rooms_host || !pano || !state || !hyper_host || !workspace || H <= 0 || W <= 0 || num_iter < 0) return PCL_EINVAL;
+    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
+    GdRooms g;
+    int rc = gd_rooms_setup(rooms_host, nrooms, 1, per_room, hyper_host, &g);
+    if (rc) return rc;
+    if (workspace_bytes < gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes)) return PCL_EWORKSPACE;
+    // one room: pcl_gd_run itself (the same plan and arithmetic — and no room look-up in front of every block: 1.2 us per iteration at the
+    // shipped shape, tools/room_bench.py).  Its workspace, two partials buffers of the same plan, fits in this one.
+    if (nrooms == 1) {
+        pcl_gd_hyper h = *hyper_host;
+        h.images = 0;
+        return pcl_gd_run(rooms_host[0].cloud, rooms_host[0].n, pano, pano_format, H, W, state, per_room, rooms_host[0].box, &h, num_iter, loss_history,
+                          workspace, workspace_bytes, timer, stream);
+    }
+    return gd_rooms_chain(g, pano, pano_format, H, W, state, hyper_host, num_iter, loss_history, workspace, tm, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------- room search: several panoramas x several rooms in one chain
+
+extern "C" size_t pcl_gd_rooms_images_workspace_bytes(const pcl_gd_room* rooms_host, int nrooms, int nimages, int per_image, const pcl_gd_hyper* hyper_host)
+{
+    GdRooms g;
+    if (gd_rooms_setup(rooms_host, nrooms, nimages, per_image, hyper_host, &g)) return 0;
+    return gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes);
+}
+
+extern "C" int pcl_gd_plan_rooms_images(const pcl_gd_room* rooms_host, int nrooms, int nimages, int per_image, const pcl_gd_hyper* hyper_host,
+                                        int* nchunks_host, int* poses_per_block_host, int* fused_host)
+{
+    GdRooms g;
+    if (nimages < 1) return PCL_EINVAL;
+    const int rc = gd_rooms_setup(rooms_host, nrooms, nimages, per_image, hyper_host, &g);
+    if (rc) return rc;
+    if (nchunks_host)
+        for (int r = 0; r < nrooms; r++) nchunks_host[r] = g.t.rec[r].nchunks;
+    if (poses_per_block_host) *poses_per_block_host = g.G;
+    if (fused_host) *fused_host = g.nblk <= gd_fuse_limit(hyper_host) ? 1 : 0;
+    return 0;
+}
+
+// candidate b of a rooms x images state belongs to image (b / per_image) % nimages: its colour set
+__global__ void pcl_gd_set_csets_kernel(PclPoseRec* recs, PclPoseRec* recs_shadow, int B, int per_image, int nimages)
+{
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const uint32_t c = (uint32_t)((b / per_image) % nimages);
+    recs[b].cset = c; recs_shadow[b].cset = c;
+}
+
+extern "C" int pcl_gd_init_rooms_images(void* state, const float* trans, const float* rot, int nrooms, int nimages, int per_image,
+                                        const pcl_gd_hyper* hyper_host, void* stream)
+{
+    if (!state || !trans || !rot || !hyper_host || nrooms < 1 || nrooms > PCL_GD_MAX_ROOMS || nimages < 1 || per_image < 1) return PCL_EINVAL;
+    if ((int64_t)nrooms * nimages * per_image > 0x7fffffff / 2) return PCL_EINVAL;
+    if (hyper_host->color_sets < 0 || (hyper_host->color_sets > 1 && hyper_host->color_sets != nimages)) return PCL_EINVAL;
+    const int B = nrooms * nimages * per_image;
+    hipLaunchKernelGGL(pcl_gd_init_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, gd_poses(state), gd_recs(state, B),
+                       gd_recs(state, B, 1), trans, rot, B, hyper_host->lr, 0);
+    PCL_LAUNCH_CHECK();
+    if (hyper_host->color_sets > 1) {
+        hipLaunchKernelGGL(pcl_gd_set_csets_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, gd_recs(state, B), gd_recs(state, B, 1), B,
+                           per_image, nimages);
+        PCL_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int pcl_gd_run_rooms_images(const pcl_gd_room* rooms_host, int nrooms, int nimages, const void* pano, int pano_format, int H, int W,
+                                       void* state, int per_image, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace,
+                                       size_t workspace_bytes, void* timer, void* stream)
+{
+    if (!rooms_host || !pano || !state || !hyper_host || !workspace || H <= 0 || W <= 0 || num_iter < 0 || nimages < 1) return PCL_EINVAL;
+    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
+    GdRooms g;
+    const int rc = gd_rooms_setup(rooms_host, nrooms, nimages, per_image, hyper_host, &g);
+    if (rc) return rc;
+    if (workspace_bytes < gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes)) return PCL_EWORKSPACE;
+    // one image: pcl_gd_run_rooms itself (the same plans, regions and workspace size; one room: no room look-up either)
+    if (nimages == 1) {
+        pcl_gd_hyper h = *hyper_host;
+        h.color_sets = 0;
+        return pcl_gd_run_rooms(rooms_host, nrooms, pano, pano_format, H, W, state, per_image, &h, num_iter, loss_history, workspace, workspace_bytes,
+                                timer, stream);
+    }
+    return gd_rooms_chain(g, pano, pano_format, H, W, state, hyper_host, num_iter, loss_history, workspace, (PclTimer*)timer, (hipStream_t)stream);
 }
 
 extern "C" int pcl_gd_step_from_grads(void* state, int B, const float* loss, const float* grad, const float* box, const pcl_gd_hyper* hyper_host,

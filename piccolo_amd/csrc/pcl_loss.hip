@@ -389,6 +389,21 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_rooms_kernel(PclLoss
     pcl_loss_body<G, true, 0, FMT, true, false, true>(a, f, rooms);
 }
 
+// several rooms x several images with per-image colour sets (pcl_gd_run_rooms_images, hyper->color_sets == nimages): the RM and the CS
+// instance at once.  The block finds its room, then reads the colour set its group's first pose record names: every room's cloud holds
+// the launch's a.color_sets sets (the same count in every room, so it travels in PclLossArgs and the room table keeps its layout).
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_rooms_sets_kernel(PclLossArgs a, const PclRoomTable* rooms)
+{
+    pcl_loss_body<G, true, 0, FMT, false, true, true>(a, PclFuseArgs{}, rooms);
+}
+
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_rooms_sets_kernel(PclLossArgs a, PclFuseArgs f, const PclRoomTable* rooms)
+{
+    pcl_loss_body<G, true, 0, FMT, true, true, true>(a, f, rooms);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launch planning (shared with the GD loop)
 
@@ -466,10 +481,14 @@ static PclPlan pcl_plan_sets(int64_t n, int B, int sets)
     return p;
 }
 
-// one room of a multi-room chain (pcl_gd_run_rooms): that room's single-cloud plan pcl_plan(n, per_room), XCD runs included
-void pcl_plan_room(int64_t n, int per_room, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem)
+// one room of a multi-room chain (pcl_gd_run_rooms: nimages = 1, the room's single-cloud plan; pcl_gd_run_rooms_images): the single-image
+// plan pcl_plan(n, per_image) for all nimages * per_image candidates of the room (pcl_plan_sets' rule, shared colours included); only the
+// XCD runs are chosen for the room's whole block range
+void pcl_plan_room_images(int64_t n, int per_image, int nimages, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem)
 {
-    const PclPlan p = pcl_plan(n, per_room);
+    PclPlan p = pcl_plan(n, per_image);
+    p.ngroups = nimages * (per_image / p.G);
+    p.seg_len = pcl_xcd_seg_len(p.nchunks, (int64_t)p.nchunks * p.ngroups);
     *G = p.G; *ngroups = p.ngroups; *nchunks = p.nchunks; *seg_len = p.seg_len; *steps_base = p.steps_base; *steps_rem = p.steps_rem;
 }
 
@@ -560,16 +579,39 @@ static void pcl_launch_sets(const PclLossArgs& a, const PclFuseArgs* f, int G, i
 
 // The loss pass of a multi-room chain (pcl_gd_run_rooms): nblk blocks, every room's cloud, plan, pose range and partials region from the
 // device room table `rooms`; `poses` / `partials` (and the buffers of `fuse`) are the bases of all rooms.  Gradient pass, no mask.
+// color_sets > 1 (pcl_gd_run_rooms_images): every room's cloud holds that many colour sets and every pose record names its own.
+template <int G, int FMT>
+static void pcl_launch_rooms_sets(const PclLossArgs& a, const PclFuseArgs* f, const PclRoomTable* rooms, int nblk, hipStream_t s)
+{
+    if (f) hipLaunchKernelGGL((pcl_loss_fused_rooms_sets_kernel<G, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, *f, rooms);
+    else hipLaunchKernelGGL((pcl_loss_rooms_sets_kernel<G, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, rooms);
+}
+
 int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
-                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse)
+                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, int color_sets)
 {
     if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;
     if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
     PclLossArgs a = PclLossArgs{};
     a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
     a.poses = poses; a.B = B; a.partials = partials;
-    a.ngroups = ngroups; a.flip = flip & 1; a.xcd_groups = 0; a.color_sets = 1;
+    a.ngroups = ngroups; a.flip = flip & 1; a.xcd_groups = 0; a.color_sets = color_sets > 1 ? color_sets : 1;
     const dim3 grid(nblk), blk(PCL_BLOCK);
+    if (color_sets > 1) {
+        if (G != 1 && G != 2) return PCL_EINVAL;
+        if (pano_format == PCL_PANO_U8) {
+            if (G == 2) pcl_launch_rooms_sets<2, PCL_PANO_U8>(a, fuse, rooms, nblk, s);
+            else pcl_launch_rooms_sets<1, PCL_PANO_U8>(a, fuse, rooms, nblk, s);
+        } else if (pano_format == PCL_PANO_F16) {
+            if (G == 2) pcl_launch_rooms_sets<2, PCL_PANO_F16>(a, fuse, rooms, nblk, s);
+            else pcl_launch_rooms_sets<1, PCL_PANO_F16>(a, fuse, rooms, nblk, s);
+        } else {
+            if (G == 2) pcl_launch_rooms_sets<2, PCL_PANO_F32>(a, fuse, rooms, nblk, s);
+            else pcl_launch_rooms_sets<1, PCL_PANO_F32>(a, fuse, rooms, nblk, s);
+        }
+        PCL_LAUNCH_CHECK();
+        return 0;
+    }
     if (fuse) {
         if (pano_format == PCL_PANO_U8) {
             if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<2, PCL_PANO_U8>), grid, blk, 0, s, a, *fuse, rooms);

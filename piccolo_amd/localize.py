@@ -18,7 +18,7 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_rooms
+from .omniloc import omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_rooms, omniloc_batch_rooms_images
 from .utils import make_input, make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
 
@@ -71,6 +71,34 @@ def localize_in_rooms(img_init, img_main, rooms, cfg, init_dict):
     losses = torch.stack([r[2].reshape(()) for r in res])
     k = int(torch.argmin(losses))
     return k, res[k][0], res[k][1], res[k][2], losses
+
+
+def localize_images_in_rooms(imgs_init, imgs_main, rooms, cfg, init_dict):
+    """localize_in_rooms for SEVERAL panoramas of one size that meet the same rooms: per room the colour preprocessing of every image
+    (preprocess_colors), then ONE make_input_images over the I initialisation images (with a colour list when the colours differ per image:
+    sharpen_color), then ONE refinement of all main images against all rooms (omniloc_batch_rooms_images).
+    -> a list whose entry i equals localize_in_rooms(imgs_init[i], imgs_main[i], rooms, cfg, init_dict) bit for bit: (room index, t, R,
+    loss, every room's loss)."""
+    I = len(imgs_init)
+    if I == 0 or len(imgs_main) != I:
+        raise ValueError("localize_images_in_rooms: %d initialisation images, %d main images" % (I, len(imgs_main)))
+    trs, ros, prepped = [], [], []
+    for xyz, rgb in rooms:
+        pre = [preprocess_colors(im, rgb, cfg) for im in imgs_init]
+        rgbs = [c for _, c in pre]
+        rgb_r = rgb if all(c is rgb for c in rgbs) else rgbs
+        starts = make_input_images([im for im, _ in pre], xyz, rgb_r, getattr(cfg, "num_input", 6), init_dict,
+                                   getattr(cfg, "criterion", "histogram"), getattr(cfg, "num_intermediate", 20))
+        trs.append([tr for tr, _ in starts])
+        ros.append([ro for _, ro in starts])
+        prepped.append((xyz, rgb_r))
+    res = omniloc_batch_rooms_images(imgs_main, prepped, trs, ros, cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
+    out = []
+    for i in range(I):
+        losses = torch.stack([res[r][i][2].reshape(()) for r in range(len(rooms))])
+        k = int(torch.argmin(losses))
+        out.append((k, res[k][i][0], res[k][i][1], res[k][i][2], losses))
+    return out
 
 
 def pose_errors(t, R, gt_trans, gt_rot):
@@ -379,7 +407,7 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     _require_gravity_aligned(cfg)
     room_search = getattr(cfg, "room_search", None)
     if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
-        raise ValueError("room_search does not combine with images_per_launch > 1: a room search refines one image against many clouds")
+        raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")
     _seed_all()
     dev = ops.device()
     area_num = getattr(cfg, "area", None)
@@ -458,7 +486,10 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
     """localize_stanford with cfg.room_search: every image is localised among the rooms of its area (stanford_area_rooms) by
     localize_in_rooms instead of in the room its file name names.  The skip rule stays on the ground-truth room's cloud (the same images
     are evaluated as in a known-room run); the CSV gets a last column found_room, LAST_RUN a room_accuracy, and the result image is
-    rendered from the found room's cloud.  Each area's clouds are read once.  With several ranks every rank localises its share of the
+    rendered from the found room's cloud.  Each area's clouds are read once.  cfg.room_search_images = N > 1: up to N consecutive
+    non-skipped images of this rank that share area and image sizes are localised by ONE localize_images_in_rooms call (the same results,
+    bit for bit); a group ends at an area change and at the end, and its wall time is shared equally over its images, as _Batcher does.
+    With several ranks every rank localises its share of the
     images and the found rooms are gathered with the result rows (as room indices into the area's sorted listing), so that rank 0 writes
     found_room and room_accuracy for every image."""
     dev = ops.device()
@@ -468,6 +499,9 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
     mh, mw = getattr(cfg, "main_downsample_h", 1), getattr(cfg, "main_downsample_w", 1)
     init_dict = get_init_dict(cfg)
     areas, found, found_idx = {}, {}, {}
+    group_size = max(1, int(getattr(cfg, "room_search_images", 1)))
+    ready = {}                                         # room_search_images: image index -> (room, t, R, loss, seconds, images) of its group
+    gts = {}                                           # image index -> (gt_trans, gt_rot, skipped): a group's look-ahead asks before per_image does
 
     def area_of(k):
         return int(filenames[k].split("/")[-2].split("_")[-1])
@@ -486,7 +520,12 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
             areas[area] = rooms
         return areas[area]
 
-    def per_image(k, gt_only=False):
+    def ground_truth(k):
+        if k not in gts:
+            gts[k] = read_ground_truth(k)
+        return gts[k]
+
+    def read_ground_truth(k):
         filename = filenames[k]
         area = int(filename.split("/")[-2].split("_")[-1])
         img_name = filename.split("/")[-1]
@@ -499,6 +538,42 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
             xyz_np, _ = data_utils.read_stanford(os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, gt_room)), sample_rate)
             gt_cloud = torch.from_numpy(xyz_np).float().to(dev)
         skipped = bool(out_of_room(gt_cloud, torch.from_numpy(gt_trans), quant)) and not getattr(cfg, "eval_full", False)
+        return gt_trans, gt_rot, skipped
+
+    def load_images(k):
+        orig = read_image(filenames[k])
+        img = _to_img(resize_image(orig, orig.shape[1] // dw, orig.shape[0] // dh), dev)
+        img_main = _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev)
+        return orig, img, img_main
+
+    def localize_group(k):
+        # image k and the next non-skipped images of this rank in its area with its image sizes, up to group_size, in one call
+        rank, world = pdist.world()
+        rooms = area_rooms(area_of(k))
+        group, images = [k], [load_images(k)]
+        for k2 in range(k + world, len(filenames), world):
+            if len(group) >= group_size or area_of(k2) != area_of(k):
+                break
+            if ground_truth(k2)[2]:
+                continue
+            nxt = load_images(k2)
+            if nxt[1].shape != images[0][1].shape or nxt[2].shape != images[0][2].shape:
+                break
+            group.append(k2)
+            images.append(nxt)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        results = localize_images_in_rooms([im[1] for im in images], [im[2] for im in images], [(xyz, rgb) for _, xyz, rgb in rooms], cfg, init_dict)
+        share = (time.time() - t0) / len(group)        # the group's wall time, shared equally
+        for kk, im, (r, t, R, loss, _) in zip(group, images, results):
+            ready[kk] = (r, t, R, loss, share, im)
+
+    def per_image(k, gt_only=False):
+        filename = filenames[k]
+        area = area_of(k)
+        img_name = filename.split("/")[-1]
+        gt_trans, gt_rot, skipped = ground_truth(k)
+        rooms = area_rooms(area)
         if gt_only:
             return gt_trans, gt_rot, skipped
         if skipped:
@@ -506,13 +581,17 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
             return _nan_row(), gt_trans, gt_rot, True
         if not rooms:
             raise FileNotFoundError("room_search: no room clouds under pcd_not_aligned/area_{}".format(area))
-        orig = read_image(filename)
-        img = _to_img(resize_image(orig, orig.shape[1] // dw, orig.shape[0] // dh), dev)
-        img_main = _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev)
-        torch.cuda.synchronize()
-        t0 = time.time()
-        r, t, R, loss, _ = localize_in_rooms(img, img_main, [(xyz, rgb) for _, xyz, rgb in rooms], cfg, init_dict)
-        row = _result_row(t, R, loss, gt_trans, gt_rot, time.time() - t0)
+        if group_size > 1:
+            if k not in ready:
+                localize_group(k)
+            r, t, R, loss, seconds, (orig, img, img_main) = ready.pop(k)
+            row = _result_row(t, R, loss, gt_trans, gt_rot, seconds)
+        else:
+            orig, img, img_main = load_images(k)
+            torch.cuda.synchronize()
+            t0 = time.time()
+            r, t, R, loss, _ = localize_in_rooms(img, img_main, [(xyz, rgb) for _, xyz, rgb in rooms], cfg, init_dict)
+            row = _result_row(t, R, loss, gt_trans, gt_rot, time.time() - t0)
         name, xyz, rgb = rooms[r]
         found_idx[k] = r
         print("\n{}\nfound room : {}\ntranslation error : {}\nrotation error : {}\n".format(img_name, name, float(row[13]), float(row[14])))

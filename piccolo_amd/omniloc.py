@@ -37,7 +37,7 @@ strict_reference_asserts = True
 # cloud, quantile box or translation grid (a dataset loop touches 4 cloud-side entries per room and 2 per image).
 # An entry is keyed by the identity of the tensors it was made from (address, shape, in-place version) and holds weak
 # references to them: a hit needs the very same live tensor, and entries whose tensors died are purged.
-_CAPACITY = {"cloud": 2, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "trimgroups": 4}
+_CAPACITY = {"cloud": 2, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "gd_rooms_images": 4, "trimgroups": 4}
 
 
 class _PackCache:
@@ -491,6 +491,151 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
             input_trans_list[r].copy_(leaf_t[r * B:(r + 1) * B].reshape(input_trans_list[r].shape).to(input_trans_list[r].device))
             input_rot_list[r].copy_(leaf_r[r * B:(r + 1) * B].reshape(input_rot_list[r].shape).to(input_rot_list[r].device))
     return [[host[r, 0:3].reshape(3, 1).clone(), host[r, 3:12].reshape(3, 3).clone(), host[r, 12].clone()] for r in range(R)]
+
+
+# One chain for several images pays where a one-image chain is bound by launch latency (tools/room_images_bench.py, DESIGN.md §4.6d, ms per
+# image of the chain alone, all images' chain against a chain per image): 4 rooms x 166,667 points x 6 candidates (4M point-poses per
+# image) 2.72 against 3.28 with 8 images, 8 such rooms (8M) 5.21 against 5.46 — and nothing at 4 rooms x 1M points x 32 candidates (128M):
+# 39.22 against 39.08, 0.4 % SLOWER with a spread of 0.1 %.  The cut-off is the size up to which a one-image chain replays a graph.
+ROOMS_IMAGES_POINT_POSES = GRAPH_POINT_POSES
+
+
+def rooms_images_chain_pays(points, per_image):
+    """Do several images share ONE rooms chain (True) or does every image run its own (False)?  `points`: the rooms' points together."""
+    return int(points) * int(per_image) <= ROOMS_IMAGES_POINT_POSES
+
+
+def _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode):
+    """One launch chain over I images x at most PCL_GD_MAX_ROOMS rooms (ops.GradientDescentRoomsImages) -> the engine.  `rooms`: (xyz, rgb)
+    pairs whose rgb is one tensor in every room or a list of I tensors in every room; tr / ro: nrooms * I * per_image rows, room by room and
+    image by image inside a room.  Set up like _rooms_chain: one texel format for the chain (the largest room's; float4 when the images do
+    not agree), graph replay under _refine's rule on the chain's points x candidates, and a cached engine with private copies of the packed
+    clouds and boxes into which the colours of a later group of images are copied."""
+    I = len(imgs)
+    per_image_sets = isinstance(rooms[0][1], list)
+    clouds = [packed_cloud_sets(xyz, rgb) if per_image_sets else packed_cloud(xyz, rgb) for xyz, rgb in rooms]
+    boxes = [quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05)) for xyz, _ in rooms]
+    B = int(tr.shape[0])
+    per_room = B // len(rooms)
+    nmax = max(int(xyz.shape[0]) for xyz, _ in rooms)
+    panos = [packed_pano(im, n_points=nmax) for im in imgs]
+    if len({p.fmt for p in panos}) > 1:          # a launch needs ONE texel format: float4 holds any image
+        panos = [ops.Pano(im, fmt="f32") for im in imgs]
+    num_iter = _cfg(cfg, "num_iter", 100)
+    hyper = (float(_cfg(cfg, "lr", 0.1)), int(_cfg(cfg, "patience", 5)), float(_cfg(cfg, "factor", 0.9)), bool(batch_mode))
+    fuse = None if _cfg(cfg, "gd_fuse", True) else False
+    use_graph = _cfg(cfg, "gd_graph", None)
+    if use_graph is None and ops.EXPERIMENT.gd_graph is not None:                   # experiments
+        use_graph = bool(ops.EXPERIMENT.gd_graph)
+    if use_graph is None:
+        use_graph = sum(c.n for c in clouds) * per_room <= GRAPH_POINT_POSES
+
+    def make(cs, bs):
+        return ops.GradientDescentRoomsImages(list(zip(cs, bs)), panos, tr, ro, lr=hyper[0], patience=hyper[1], factor=hyper[2],
+                                              batch_mode=hyper[3], fuse=fuse)
+    if not use_graph:
+        gd = make(clouds, boxes)
+        gd.run(num_iter)
+        return gd
+
+    def make_private():
+        g = make([ops.Cloud.private_copy(c) for c in clouds], [ops._dev(b).reshape(6).clone() for b in boxes])
+        g._cloud_src = [weakref.ref(c) for c in clouds]
+        g._box_src, g._fresh = list(boxes), True
+        return g
+    xyzs = tuple(xyz for xyz, _ in rooms)
+    p0 = panos[0]
+    gd = _cached("gd_rooms_images", xyzs, make_private, sub=(I, per_room, p0.H, p0.W, p0.fmt, fuse, clouds[0].color_sets) + hyper)
+    fresh, gd._fresh = gd._fresh, False
+    for r, c in enumerate(clouds):
+        if gd._cloud_src[r]() is not c:                # (the colours change with every group of query images)
+            gd.clouds[r].data.copy_(c.data)
+            gd._cloud_src[r] = weakref.ref(c)
+        if gd._box_src[r] is not boxes[r]:
+            gd.boxes[r].copy_(ops._dev(boxes[r]).reshape(6))
+            gd._box_src[r] = boxes[r]
+    if not fresh:
+        gd.reset(tr, ro)
+        gd.set_panos(panos)                            # the pose records name these images' panoramas
+    gd.run_graph(num_iter)
+    return gd
+
+
+def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_summaries=None, batch_mode=True):
+    """Room search for SEVERAL query images (not in the reference): omniloc_batch of every image against every room in one launch chain.
+
+    imgs: list of I (H,W,3) images of one size; rooms: list of R (xyz, rgb) clouds, rgb one (N, 3) tensor (the images share the room's
+    colours) or a list of I tensors (image i's own colours of that room, e.g. color_mod's); input_trans[r][i] / input_rot[r][i]: (B,3)
+    starting poses of image i in room r (the same B everywhere).  Returns out[r][i] = [t (3,1), R (3,3), loss ()] and writes the leaf rows
+    back into the callers' tensors, as omniloc_batch does.  out[r][i] and the leaf rows are omniloc_batch(imgs[i], xyz_r, rgb_r[i], ...)'s
+    bit for bit (batch_mode=False: those of omniloc_batch_images([imgs[i]], ..., batch_mode=False)[0], the sequential semantics) for images
+    whose texels are k/255 levels; for other images against the single call run with the chain's texel format (float4).
+    Fallbacks: more than PCL_GD_MAX_ROOMS rooms go in several chains; with per-image colours, images beyond a room's colour-set limit
+    (color_set_groups of the largest room) go in groups, each a chain of its own; with the depth mask (no rooms instance of the loss
+    kernel) every room runs omniloc_batch_images on its own; one image is omniloc_batch_rooms, and so is every image of a chain too large to
+    gain from sharing (rooms_images_chain_pays: the same results, a chain per image)."""
+    if strict_reference_asserts and batch_mode:
+        assert cfg.num_input > 1
+    R, I = len(rooms), len(imgs)
+    if R == 0 or I == 0 or len(input_trans) != R or len(input_rot) != R:
+        raise ValueError("omniloc_batch_rooms_images: %d rooms, %d images, %d / %d starting-pose sets" % (R, I, len(input_trans), len(input_rot)))
+    if any(len(t) != I for t in input_trans) or any(len(r) != I for r in input_rot):
+        raise ValueError("omniloc_batch_rooms_images: every room needs one starting-pose set per image")
+    B = int(input_trans[0][0].shape[0])
+    if any(int(t.shape[0]) != B for ts in input_trans for t in ts) or any(int(r.shape[0]) != B for rs in input_rot for r in rs):
+        raise ValueError("omniloc_batch_rooms_images: every room and image needs the same number of starting poses")
+    rooms = [(xyz, shared_rgb(rgb)) for xyz, rgb in rooms]
+    for _, rgb in rooms:
+        if isinstance(rgb, list) and len(rgb) != I:
+            raise ValueError("omniloc_batch_rooms_images: %d colour sets for %d images" % (len(rgb), I))
+    if bool(_cfg(cfg, "depth_mask", False)):
+        return [omniloc_batch_images(imgs, xyz, rgb, input_trans[r], input_rot[r], cfg, scalar_summaries, batch_mode)
+                for r, (xyz, rgb) in enumerate(rooms)]
+    if I > 1 and not rooms_images_chain_pays(sum(int(xyz.shape[0]) for xyz, _ in rooms), B):
+        out = [[] for _ in range(R)]
+        for i in range(I):
+            one = omniloc_batch_rooms_images(imgs[i:i + 1], [(xyz, rgb[i] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms],
+                                             [t[i:i + 1] for t in input_trans], [r[i:i + 1] for r in input_rot], cfg, scalar_summaries, batch_mode)
+            for r in range(R):
+                out[r] += one[r]
+        return out
+    if I == 1:
+        one = omniloc_batch_rooms(imgs[0], [(xyz, rgb[0] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms], [t[0] for t in input_trans],
+                                  [r[0] for r in input_rot], cfg, scalar_summaries, batch_mode)
+        return [[o] for o in one]
+    cap = ops._lib.GD_MAX_ROOMS
+    if R > cap:
+        out = []
+        for r0 in range(0, R, cap):
+            out += omniloc_batch_rooms_images(imgs, rooms[r0:r0 + cap], input_trans[r0:r0 + cap], input_rot[r0:r0 + cap], cfg, scalar_summaries,
+                                              batch_mode)
+        return out
+    if any(isinstance(rgb, list) for _, rgb in rooms):
+        # one kind of cloud per chain: a room whose images share its colours holds them I times
+        rooms = [(xyz, rgb if isinstance(rgb, list) else [rgb] * I) for xyz, rgb in rooms]
+        sizes = color_set_groups(max(int(xyz.shape[0]) for xyz, _ in rooms), I)
+        if len(sizes) > 1:
+            out, i0 = [[] for _ in range(R)], 0
+            for m in sizes:
+                part = omniloc_batch_rooms_images(imgs[i0:i0 + m], [(xyz, rgb[i0:i0 + m]) for xyz, rgb in rooms], [t[i0:i0 + m] for t in input_trans],
+                                                  [r[i0:i0 + m] for r in input_rot], cfg, scalar_summaries, batch_mode)
+                for r in range(R):
+                    out[r] += part[r]
+                i0 += m
+            return out
+    tr = torch.cat([ops._dev(t).reshape(B, 3) for ts in input_trans for t in ts])
+    ro = torch.cat([ops._dev(r).reshape(B, 3) for rs in input_rot for r in rs])
+    gd = _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode)
+    leaf_t, leaf_r = torch.empty(R * I * B, 3, dtype=torch.float32, device=tr.device), torch.empty(R * I * B, 3, dtype=torch.float32, device=tr.device)
+    host = gd.winner(leaf_t, leaf_r).cpu()
+    with torch.no_grad():
+        for r in range(R):
+            for i in range(I):
+                k = r * I + i
+                input_trans[r][i].copy_(leaf_t[k * B:(k + 1) * B].reshape(input_trans[r][i].shape).to(input_trans[r][i].device))
+                input_rot[r][i].copy_(leaf_r[k * B:(k + 1) * B].reshape(input_rot[r][i].shape).to(input_rot[r][i].device))
+    return [[[host[r * I + i, 0:3].reshape(3, 1).clone(), host[r * I + i, 3:12].reshape(3, 3).clone(), host[r * I + i, 12].clone()] for i in range(I)]
+            for r in range(R)]
 
 
 def sampling_loss(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, return_list=True):

@@ -915,6 +915,86 @@ class GradientDescentRooms:
     result = GradientDescent.result
 
 
+class GradientDescentRoomsImages:
+    """On-device GD refinement of SEVERAL panoramas against several rooms in one launch chain (pcl_gd_run_rooms_images): `rooms` is a list
+    of (Cloud, box) pairs, `panos` a list of I Pano objects of one size and texel format, `trans` / `rot` hold nrooms * I * per_image rows
+    and candidate (r, i, j) is row (r * I + i) * per_image + j.  Every room cloud holds one colour set (the images share the room's colours)
+    or I of them (Cloud.with_color_sets: image i reads set i of every room).  The results of every (room, image) equal those of a
+    GradientDescent over that room and image alone, bit for bit.  At most PCL_GD_MAX_ROOMS rooms."""
+
+    def __init__(self, rooms, panos, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None):
+        lib = _lib.load()
+        if not 1 <= len(rooms) <= _lib.GD_MAX_ROOMS:
+            raise ValueError("GradientDescentRoomsImages: %d rooms (1..%d per chain)" % (len(rooms), _lib.GD_MAX_ROOMS))
+        if len(panos) < 1:
+            raise ValueError("GradientDescentRoomsImages: no panorama")
+        self.pano = panos[0]
+        self.clouds = [c for c, _ in rooms]
+        self.nrooms, self.nimages = len(rooms), len(panos)
+        sets = {int(c.color_sets) for c in self.clouds}
+        if len(sets) != 1 or sets.pop() not in (1, self.nimages):
+            raise ValueError("GradientDescentRoomsImages: every room cloud needs one colour set, or one per image (%d)" % self.nimages)
+        self.color_sets = int(self.clouds[0].color_sets)
+        self.boxes = [_dev(b).reshape(6) for _, b in rooms]
+        trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+        self.B = int(trans.shape[0])
+        if self.B % (self.nrooms * self.nimages) or self.B == 0:
+            raise ValueError("GradientDescentRoomsImages: %d candidates do not split into %d rooms x %d images" % (self.B, self.nrooms, self.nimages))
+        self.per_image = self.B // (self.nrooms * self.nimages)
+        self.hyper = _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL,
+                                  0, 0.0, 0, 0, 0, -1 if fuse is False else 0, 0, self.color_sets if self.color_sets > 1 else 0)
+        self._rooms = (_lib.GdRoom * self.nrooms)(*[_lib.GdRoom(c.data.data_ptr(), c.n, b.data_ptr()) for c, b in zip(self.clouds, self.boxes)])
+        self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
+        self.ws_bytes = lib.pcl_gd_rooms_images_workspace_bytes(self._rooms, self.nrooms, self.nimages, self.per_image, ctypes.byref(self.hyper))
+        if self.ws_bytes == 0:
+            raise _lib.PiccoloHipError("pcl_gd_rooms_images_workspace_bytes: invalid arguments")
+        self.ws = _bytes(self.ws_bytes)
+        self.reset(trans, rot)
+        self.set_panos(panos)
+
+    def plan(self):
+        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms_images"""
+        nch, G, fused = (ctypes.c_int * self.nrooms)(), ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().pcl_gd_plan_rooms_images(self._rooms, self.nrooms, self.nimages, self.per_image, ctypes.byref(self.hyper), nch,
+                                                        ctypes.byref(G), ctypes.byref(fused)), "pcl_gd_plan_rooms_images")
+        return list(nch), G.value, bool(fused.value)
+
+    def reset(self, trans, rot):
+        """New starting poses for the same rooms / shape (the pose records then name no panorama: call set_panos)."""
+        trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+        assert trans.shape[0] == self.B
+        _lib.check(_lib.load().pcl_gd_init_rooms_images(_ptr(self.state), _ptr(trans), _ptr(rot), self.nrooms, self.nimages, self.per_image,
+                                                        ctypes.byref(self.hyper), _stream()), "pcl_gd_init_rooms_images")
+
+    def set_panos(self, panos):
+        """Image i's candidates in every room sample panos[i] (addresses as kernel arguments: no copy to the device)."""
+        if len(panos) != self.nimages:
+            raise ValueError("GradientDescentRoomsImages: %d panoramas for %d images" % (len(panos), self.nimages))
+        for p in panos:
+            if (p.H, p.W, p.fmt) != (self.pano.H, self.pano.W, self.pano.fmt):
+                raise ValueError("all panoramas of a launch must share size and texel format")
+        self._panos = list(panos)                      # keep them alive
+        n = self.nrooms * self.nimages
+        arr = (ctypes.c_uint64 * n)(*([p.data.data_ptr() for p in panos] * self.nrooms))
+        _lib.check(_lib.load().pcl_gd_set_pano_groups(_ptr(self.state), arr, n, self.per_image, _stream()), "pcl_gd_set_pano_groups")
+
+    def run(self, num_iter, history=False, timer=None):
+        lib = _lib.load()
+        hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
+        _lib.check(lib.pcl_gd_run_rooms_images(self._rooms, self.nrooms, self.nimages, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
+                                               _ptr(self.state), self.per_image, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws),
+                                               self.ws_bytes, timer.handle if timer else None, _stream()), "pcl_gd_run_rooms_images")
+        return hist
+
+    run_graph = GradientDescent.run_graph          # capture run(num_iter) once per num_iter, replay it
+
+    def winner(self, leaf_trans=None, leaf_rot=None):
+        """(nrooms * nimages, 16): per (room, image), room by room, the candidate omniloc_batch returns (see GradientDescent.winner)."""
+        return GradientDescent.winner(self, self.nrooms * self.nimages, leaf_trans, leaf_rot)
+
+    result = GradientDescent.result
+
+
 class KernelTimer:
     """HIP-event pairs around every fused loss+gradient launch of GradientDescent.run (measurement aid)."""
 
