@@ -180,7 +180,8 @@ typedef struct pcl_gd_hyper {
                            /* are k images of B / k (image i's a contiguous range) and image i's candidates read set i.  The chain then runs */
                            /* the SINGLE-IMAGE plan pcl_gd_plan(n, B / k) — its chunks, poses per block and steps per chunk — for all B: */
                            /* every image's results are those of a one-image run with its own colours, bit for bit.  pcl_gd_init writes */
-                           /* the sets into the pose records; B % k != 0 or depth_mask: PCL_EINVAL (sizing functions: 0).                */
+                           /* the sets into the pose records; B % k != 0 or depth_mask: PCL_EINVAL (sizing functions: 0) — colour sets  */
+                           /* under the depth mask run through pcl_gd_run_depth_chain.                                                 */
 } pcl_gd_hyper;
 
 size_t pcl_gd_state_bytes(int B);
@@ -278,6 +279,31 @@ int pcl_gd_init_rooms_images(void *state, const float *trans, const float *rot, 
 int pcl_gd_run_rooms_images(const pcl_gd_room *rooms_host, int nrooms, int nimages, const void *pano, int pano_format, int H, int W, void *state,
                             int per_image, const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace,
                             size_t workspace_bytes, void *timer, void *stream);
+
+/* The depth mask inside a shared chain (additive to ABI 12): the rooms x images chain above with hyper->depth_mask set — which every
+ * entry point above refuses, because this chain's workspace carries z-buffers.  One family for the three shared chains: per-image colour
+ * sets of one room (nrooms = 1, color_sets = nimages), several rooms (nimages = 1), rooms x images.  Layout, state, panoramas and colour
+ * sets as for pcl_gd_run_rooms_images: pcl_gd_state_bytes, pcl_gd_init_rooms_images (nrooms = 1 included; it does not read depth_mask),
+ * pcl_gd_set_pano_groups, pcl_gd_result / pcl_gd_winner.  hyper->depth_mask must be set (else PCL_EINVAL; 0 from the sizing function).
+ * Room r runs the single-image plan pcl_gd_plan(n_r, per_image) for all its candidates (two launches per iteration: a depth-masked run
+ * never fuses) and resolves ITS OWN grid, tolerance and occluder stride from hyper->depth_h / depth_w / depth_tau / depth_stride exactly
+ * as a pcl_gd_run of that room does: pcl_depth_default(n_r, H, W, depth_stride) for a 0 x 0 grid, the given grid for every room otherwise.
+ * Per iteration: one z pass per room (its cloud, its candidates, its region of z-buffer set it & 1), ONE loss launch over all rooms that
+ * looks every point's cell up in its room's z-buffers and resets the other set, ONE epilogue launch.  Contract: for every (r, i) the
+ * state, pose records, loss-history columns and winner equal those of a depth-masked pcl_gd_run of room r with image i alone (image i's
+ * colours, per_image candidates, the same hyper-parameters) BIT FOR BIT, in both modes, also across repeated calls.
+ * workspace: room table, depth table, one partials buffer, two z-buffer sets (per set every room's nimages * per_image z-buffers); pure
+ * scratch, every call fills the set its first iteration reads.  nrooms == 1 with nimages == 1 is pcl_gd_run itself.
+ * PCL_EINVAL, before any HIP call: null arguments, depth_mask == 0, what pcl_gd_run_rooms_images refuses, an invalid grid (a side below
+ * 2, one side 0), a room whose nimages * per_image z-buffers reach 4 GiB.  PCL_EWORKSPACE: workspace_bytes too small.
+ * pcl_gd_plan_depth_chain (host-only; every output nullable): per room the chunks of its plan, grid and occluder stride; poses per block. */
+size_t pcl_gd_depth_chain_workspace_bytes(const pcl_gd_room *rooms_host, int nrooms, int nimages, int per_image, int H, int W,
+                                          const pcl_gd_hyper *hyper_host);
+int pcl_gd_plan_depth_chain(const pcl_gd_room *rooms_host, int nrooms, int nimages, int per_image, int H, int W, const pcl_gd_hyper *hyper_host,
+                            int *nchunks_host, int *poses_per_block_host, int *depth_h_host, int *depth_w_host, int *depth_stride_host);
+int pcl_gd_run_depth_chain(const pcl_gd_room *rooms_host, int nrooms, int nimages, const void *pano, int pano_format, int H, int W, void *state,
+                           int per_image, const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace,
+                           size_t workspace_bytes, void *timer, void *stream);
 
 /* ---- kernel timer (measurement aid, HOST object) --------------------------------------------------------------
  * A pool of hipEvent pairs.  When a timer is passed to pcl_gd_run, every launch of the fused loss+gradient kernel is

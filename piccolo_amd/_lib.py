@@ -112,6 +112,11 @@ SIGNATURES = {
     "pcl_gd_plan_rooms_images": (_int, [_c.POINTER(GdRoom), _int, _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
     "pcl_gd_init_rooms_images": (_int, [_vp, _vp, _vp, _int, _int, _int, _c.POINTER(GdHyper), _vp]),
     "pcl_gd_run_rooms_images": (_int, [_c.POINTER(GdRoom), _int, _int, _vp, _int, _int, _int, _vp, _int, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
+    "pcl_gd_depth_chain_workspace_bytes": (_sz, [_c.POINTER(GdRoom), _int, _int, _int, _int, _int, _c.POINTER(GdHyper)]),
+    "pcl_gd_plan_depth_chain": (_int, [_c.POINTER(GdRoom), _int, _int, _int, _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int),
+                                       _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
+    "pcl_gd_run_depth_chain": (_int, [_c.POINTER(GdRoom), _int, _int, _vp, _int, _int, _int, _vp, _int, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp,
+                                      _vp]),
     "pcl_select_poses": (_int, [_vp, _int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp]),
     "pcl_cloud2idx": (_int, [_vp, _i64, _vp, _vp]),
     "pcl_sample_from_img": (_int, [_vp, _int, _int, _int, _vp, _i64, _vp, _vp]),

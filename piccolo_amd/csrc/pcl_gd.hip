@@ -23,6 +23,9 @@ int pcl_plan_G(int64_t n, int B, int sets = 1);
 void pcl_plan_room_images(int64_t n, int per_image, int nimages, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
 int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
                           int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, int color_sets = 1);
+int pcl_launch_loss_rooms_depth(const PclRoomTable* rooms, const PclDepthTable* dtab, const void* pano, int pano_format, int H, int W,
+                                const PclPoseRec* poses, int B, int G, int ngroups, int nblk, float* partials, hipStream_t s, int flip, int color_sets,
+                                const uint32_t* zbuf, uint32_t* zclear, int64_t zclear_vec4);
 size_t pcl_depth_zbuf_bytes(int B, int Hd, int Wd);
 int pcl_launch_zbuffers(const float* cloud, int64_t n, const PclPoseRec* poses, int B, const PclDepthGrid& g, int zstride, uint32_t* zbuf, bool fill,
                         hipStream_t s);
@@ -225,7 +228,7 @@ __global__ void pcl_gd_result_kernel(const PclGdPose* __restrict__ st, int B, fl
 extern "C" size_t pcl_gd_state_bytes(int B) { return B > 0 ? 2 * gd_copy_bytes(B) : 0; }
 
 // colour sets of a run: 1 (the cloud's one set, or 0 / 1 in the hyper-parameters) or hyper->color_sets; -1 when that does not split B
-// or is combined with the depth mask (whose loss pass has no colour-set instance)
+// or is combined with the depth mask (pcl_gd_run's own loss pass has no colour-set instance with the look-up: pcl_gd_run_depth_chain runs those)
 static int gd_sets(int B, const pcl_gd_hyper* hyper_host)
 {
     if (!hyper_host || hyper_host->color_sets <= 1) return hyper_host && hyper_host->color_sets < 0 ? -1 : 1;
@@ -561,6 +564,21 @@ static int gd_rooms_setup(const pcl_gd_room* rooms_host, int nrooms, int nimages
     return 0;
 }
 
+// the stand-alone epilogue of a multi-room chain: reads copy `copy_in` of the state, writes copy 0
+static void gd_rooms_epilogue(const GdRooms& g, const PclRoomTable* table, void* state, int copy_in, const float* partials, const pcl_gd_hyper* hyper_host,
+                              float* lo, hipStream_t s)
+{
+    const int B = g.nrooms * g.per_room, ngrp = g.nrooms * g.ngroups;
+    const double fac = hyper_host->factor;
+    const int pat = (int)hyper_host->patience, mode = (int)hyper_host->mode;
+    if (g.G == 2)
+        hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<2>, dim3(ngrp), dim3(PCL_GD_THREADS), 0, s, partials, table, g.ngroups, gd_poses(state, B, copy_in),
+                           gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), fac, pat, mode, lo);
+    else
+        hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<1>, dim3(ngrp), dim3(PCL_GD_THREADS), 0, s, partials, table, g.ngroups, gd_poses(state, B, copy_in),
+                           gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), fac, pat, mode, lo);
+}
+
 // table, then two partials buffers (fused iterations read one while they write the other)
 extern "C" size_t pcl_gd_rooms_workspace_bytes(const pcl_gd_room* rooms_host, int nrooms, int per_room, const pcl_gd_hyper* hyper_host)
 {
@@ -598,15 +616,7 @@ static int gd_rooms_chain(const GdRooms& g, const void* pano, int pano_format, i
     static const int flip_env = PCL_KNOB(FLIP, 1);
     const bool fused = g.nblk <= gd_fuse_limit(hyper_host);
     auto epilogue = [&](int it, int copy_in, float* partials) {
-        float* lo = loss_history ? loss_history + (int64_t)it * B : nullptr;
-        const double fac = hyper_host->factor;
-        const int pat = (int)hyper_host->patience, mode = (int)hyper_host->mode, ngrp = nrooms * g.ngroups;
-        if (G == 2)
-            hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<2>, dim3(ngrp), dim3(PCL_GD_THREADS), 0, s, partials, table, g.ngroups, gd_poses(state, B, copy_in),
-                               gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), fac, pat, mode, lo);
-        else
-            hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<1>, dim3(ngrp), dim3(PCL_GD_THREADS), 0, s, partials, table, g.ngroups, gd_poses(state, B, copy_in),
-                               gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), fac, pat, mode, lo);
+        gd_rooms_epilogue(g, table, state, copy_in, partials, hyper_host, loss_history ? loss_history + (int64_t)it * B : nullptr, s);
     };
     for (int it = 0; it < num_iter; it++) {
         const bool timed = tm && tm->used < tm->capacity && (it % tm->stride) == 0;
@@ -738,6 +748,154 @@ extern "C" int pcl_gd_run_rooms_images(const pcl_gd_room* rooms_host, int nrooms
                                 timer, stream);
     }
     return gd_rooms_chain(g, pano, pano_format, H, W, state, hyper_host, num_iter, loss_history, workspace, (PclTimer*)timer, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------- the depth mask inside a shared chain: colour sets, rooms, rooms x images
+
+// both tables of a depth-masked chain in one launch (kernel arguments, vector stores; 3.2 KB of the 4 KB argument block)
+__global__ void pcl_gd_depth_tables_kernel(PclRoomTable t, PclDepthTable d, PclRoomTable* dst_t, PclDepthTable* dst_d)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    constexpr int NT = (int)(sizeof(PclRoomTable) / 4), ND = (int)(sizeof(PclDepthTable) / 4);
+    if (i < NT) ((int*)dst_t)[i] = ((const int*)&t)[i];
+    else if (i < NT + ND) ((int*)dst_d)[i - NT] = ((const int*)&d)[i - NT];
+}
+
+// the host side of a depth-masked chain: the rooms plan of the same hyper-parameters without the mask, plus every room's own grid,
+// tolerance and occluder stride (gd_depth_grid: what a pcl_gd_run of that room resolves) and its region of a z-buffer set
+struct GdDepthChain {
+    GdRooms g;
+    PclDepthTable d;
+    int zstride[PCL_GD_MAX_ROOMS];
+    size_t zset_bytes;           // one z-buffer set: every room's per_room z-buffers, each region a whole number of 16-byte words
+};
+
+static int gd_depth_chain_setup(const pcl_gd_room* rooms_host, int nrooms, int nimages, int per_image, int H, int W, const pcl_gd_hyper* hyper_host,
+                                GdDepthChain* c)
+{
+    if (!rooms_host || !hyper_host || H <= 0 || W <= 0 || !hyper_host->depth_mask) return PCL_EINVAL;
+    pcl_gd_hyper h = *hyper_host;
+    h.depth_mask = 0;
+    int rc = gd_rooms_setup(rooms_host, nrooms, nimages, per_image, &h, &c->g);
+    if (rc) return rc;
+    memset(&c->d, 0, sizeof(c->d));
+    size_t bytes = 0;
+    for (int r = 0; r < nrooms; r++) {
+        PclRoomDepth& e = c->d.rec[r];
+        rc = gd_depth_grid(rooms_host[r].n, H, W, hyper_host->depth_h, hyper_host->depth_w, hyper_host->depth_tau, hyper_host->depth_stride, &e.grid,
+                           &c->zstride[r]);
+        if (rc) return rc;
+        // (one 32-bit buffer descriptor per room in the loss kernel: pcl_depth_check's limit)
+        if ((int64_t)c->g.per_room * e.grid.Hd * e.grid.Wd * 4 >= ((int64_t)1 << 32)) return PCL_EINVAL;
+        e.stride = c->zstride[r];
+        e.zoff = (long long)(bytes / sizeof(uint32_t));
+        bytes += pcl_depth_zbuf_bytes(c->g.per_room, e.grid.Hd, e.grid.Wd);
+    }
+    c->zset_bytes = bytes;
+    return 0;
+}
+
+// room table, depth table, ONE partials buffer (a depth-masked chain never fuses), two z-buffer sets
+static size_t gd_depth_chain_bytes(const GdDepthChain& c)
+{
+    return gd_align(sizeof(PclRoomTable)) + gd_align(sizeof(PclDepthTable)) + gd_align(c.g.partials_bytes) + 2 * gd_align(c.zset_bytes);
+}
+
+// one room and one image: pcl_gd_run itself (hyper without colour sets and without the image hint)
+static pcl_gd_hyper gd_depth_single_hyper(const pcl_gd_hyper* hyper_host)
+{
+    pcl_gd_hyper h = *hyper_host;
+    h.color_sets = 0; h.images = 0;
+    return h;
+}
+
+extern "C" size_t pcl_gd_depth_chain_workspace_bytes(const pcl_gd_room* rooms_host, int nrooms, int nimages, int per_image, int H, int W,
+                                                     const pcl_gd_hyper* hyper_host)
+{
+    GdDepthChain c;
+    if (gd_depth_chain_setup(rooms_host, nrooms, nimages, per_image, H, W, hyper_host, &c)) return 0;
+    size_t bytes = gd_depth_chain_bytes(c);
+    if (nrooms == 1 && nimages == 1) {           // (forwarded to pcl_gd_run: its workspace has to fit as well)
+        const pcl_gd_hyper h = gd_depth_single_hyper(hyper_host);
+        const size_t single = pcl_gd_workspace_bytes(rooms_host[0].n, per_image, H, W, &h);
+        if (single > bytes) bytes = single;
+    }
+    return bytes;
+}
+
+extern "C" int pcl_gd_plan_depth_chain(const pcl_gd_room* rooms_host, int nrooms, int nimages, int per_image, int H, int W,
+                                       const pcl_gd_hyper* hyper_host, int* nchunks_host, int* poses_per_block_host, int* depth_h_host,
+                                       int* depth_w_host, int* depth_stride_host)
+{
+    GdDepthChain c;
+    const int rc = gd_depth_chain_setup(rooms_host, nrooms, nimages, per_image, H, W, hyper_host, &c);
+    if (rc) return rc;
+    for (int r = 0; r < nrooms; r++) {
+        if (nchunks_host) nchunks_host[r] = c.g.t.rec[r].nchunks;
+        if (depth_h_host) depth_h_host[r] = c.d.rec[r].grid.Hd;
+        if (depth_w_host) depth_w_host[r] = c.d.rec[r].grid.Wd;
+        if (depth_stride_host) depth_stride_host[r] = c.zstride[r];
+    }
+    if (poses_per_block_host) *poses_per_block_host = c.g.G;
+    return 0;
+}
+
+// Per iteration: every room's z pass (the existing launch, on the room's cloud, pose range and region of set it & 1), ONE loss launch over
+// all rooms that looks the masks up and resets the other set, ONE rooms epilogue.  Timer and flip as in pcl_gd_run.
+extern "C" int pcl_gd_run_depth_chain(const pcl_gd_room* rooms_host, int nrooms, int nimages, const void* pano, int pano_format, int H, int W,
+                                      void* state, int per_image, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history,
+                                      void* workspace, size_t workspace_bytes, void* timer, void* stream)
+{
+    PclTimer* tm = (PclTimer*)timer;
+    if (!rooms_host || !pano || !state || !hyper_host || !workspace || H <= 0 || W <= 0 || num_iter < 0 || nimages < 1) return PCL_EINVAL;
+    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
+    GdDepthChain c;
+    int rc = gd_depth_chain_setup(rooms_host, nrooms, nimages, per_image, H, W, hyper_host, &c);
+    if (rc) return rc;
+    if (workspace_bytes < pcl_gd_depth_chain_workspace_bytes(rooms_host, nrooms, nimages, per_image, H, W, hyper_host)) return PCL_EWORKSPACE;
+    if (nrooms == 1 && nimages == 1) {
+        const pcl_gd_hyper h = gd_depth_single_hyper(hyper_host);
+        return pcl_gd_run(rooms_host[0].cloud, rooms_host[0].n, pano, pano_format, H, W, state, per_image, rooms_host[0].box, &h, num_iter, loss_history,
+                          workspace, workspace_bytes, timer, stream);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const GdRooms& g = c.g;
+    const int B = nrooms * g.per_room;
+    char* w = (char*)workspace;
+    PclRoomTable* table = (PclRoomTable*)w;                w += gd_align(sizeof(PclRoomTable));
+    PclDepthTable* dtab = (PclDepthTable*)w;               w += gd_align(sizeof(PclDepthTable));
+    float* partials = (float*)w;                           w += gd_align(g.partials_bytes);
+    uint32_t* zset[2] = {(uint32_t*)w, (uint32_t*)(w + gd_align(c.zset_bytes))};
+    const int words = (int)((sizeof(PclRoomTable) + sizeof(PclDepthTable)) / 4);
+    hipLaunchKernelGGL(pcl_gd_depth_tables_kernel, dim3((words + 255) / 256), dim3(256), 0, s, g.t, c.d, table, dtab);
+    PCL_LAUNCH_CHECK();
+    static const int flip_env = PCL_KNOB(FLIP, 1);
+    const int64_t zclear_vec4 = (int64_t)(c.zset_bytes / 16);
+    for (int it = 0; it < num_iter; it++) {
+        const int set = it & 1;
+        // (set 0 is filled by this call before its first iteration; afterwards the previous iteration's loss launch reset the set)
+        for (int r = 0; r < nrooms; r++) {
+            rc = pcl_launch_zbuffers(rooms_host[r].cloud, rooms_host[r].n, gd_recs(state, B) + (size_t)r * g.per_room, g.per_room, c.d.rec[r].grid,
+                                     c.zstride[r], zset[set] + c.d.rec[r].zoff, it == 0, s);
+            if (rc) return rc;
+        }
+        const bool timed = tm && tm->used < tm->capacity && (it % tm->stride) == 0;
+        if (timed) {
+            hipError_t e = hipEventRecord(tm->start[tm->used], s);
+            if (e != hipSuccess) return (int)e;
+        }
+        rc = pcl_launch_loss_rooms_depth(table, dtab, pano, pano_format, H, W, gd_recs(state, B), B, g.G, g.ngroups, g.nblk, partials, s,
+                                         flip_env ? (it & 1) : 0, g.sets, zset[set], zset[set ^ 1], zclear_vec4);
+        if (rc) return rc;
+        if (timed) {
+            hipError_t e = hipEventRecord(tm->stop[tm->used], s);
+            if (e != hipSuccess) return (int)e;
+            tm->used++;
+        }
+        gd_rooms_epilogue(g, table, state, 0, partials, hyper_host, loss_history ? loss_history + (int64_t)it * B : nullptr, s);
+        PCL_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 extern "C" int pcl_gd_step_from_grads(void* state, int B, const float* loss, const float* grad, const float* box, const pcl_gd_hyper* hyper_host,

@@ -40,6 +40,18 @@ struct PclRoomTable {
     PclRoomRec rec[PCL_GD_MAX_ROOMS];
 };
 
+// The depth mask inside a multi-room chain (pcl_gd_run_depth_chain): room r's z-buffer grid and where its per_room z-buffers start inside
+// a z-buffer set (in 32-bit words; every room's region is 16-byte aligned).  A table of its own, written next to the room table by the
+// same launch: PclRoomRec keeps its layout.  `stride` (the room's occluder stride) is host information, kept for the record.
+struct PclRoomDepth {
+    PclDepthGrid grid;
+    int stride, pad;
+    long long zoff;
+};
+struct PclDepthTable {
+    PclRoomDepth rec[PCL_GD_MAX_ROOMS];
+};
+
 __device__ __forceinline__ int pcl_rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ unsigned long long pcl_rfl64(unsigned long long v)
 {

@@ -81,6 +81,9 @@ extern "C" int pcl_debug_stamp(unsigned long long* slot, void* stream)
 // RM: one launch covers several ROOMS (pcl_gd_run_rooms): the block finds its room in the room table (pcl_room_select) and runs that
 // room's own single-cloud plan over that room's own cloud, poses, partials region and clamp box, with its block index inside the room's
 // range.  Gradient pass only.  Like CS a template parameter: the instances without it keep their instruction stream.
+// RM with VIS == 2 (pcl_gd_run_depth_chain): the room also has its own z-buffer grid and its own region of the z-buffer set — the block
+// takes them from the depth table (uniform loads) and counts its poses' z-buffers inside the room; the slice of the OTHER set it resets
+// stays indexed by the launch's block index over the whole set.
 template <int G, bool FUSED>
 __device__ __forceinline__ unsigned pcl_room_select(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* __restrict__ tb, PclLossArgs& a,
                                                     PclFuseArgs& f)
@@ -112,12 +115,26 @@ __device__ __forceinline__ unsigned pcl_room_select(const PclLossArgs& a_in, con
 }
 
 template <int G, bool GRAD, int VIS, int FMT, bool FUSED, bool CS = false, bool RM = false>
-__device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* rooms = nullptr)
+__device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* rooms = nullptr,
+                                              const PclDepthTable* __restrict__ dtab = nullptr)
 {
     PclLossArgs a_rm;
     PclFuseArgs f_rm;
     unsigned bid = blockIdx.x;
     if constexpr (RM) bid = pcl_room_select<G, FUSED>(a_in, f_in, rooms, a_rm, f_rm);
+    if constexpr (RM && VIS == 2) {
+        // (the room again, as pcl_room_select counts it: that function stays as the instances without the mask compile it)
+        int room = -1;
+#pragma unroll
+        for (int q = 0; q < PCL_GD_MAX_ROOMS; q++) room += (int)blockIdx.x >= pcl_rfl(rooms->block0[q]) ? 1 : 0;
+        const PclRoomDepth* __restrict__ dr = dtab->rec + room;
+        a_rm.dgrid.Hd = pcl_rfl(dr->grid.Hd); a_rm.dgrid.Wd = pcl_rfl(dr->grid.Wd); a_rm.dgrid.last = pcl_rfl(dr->grid.last);
+        a_rm.dgrid.wm1 = __builtin_bit_cast(float, pcl_rfl(__builtin_bit_cast(int, dr->grid.wm1)));
+        a_rm.dgrid.hm1 = __builtin_bit_cast(float, pcl_rfl(__builtin_bit_cast(int, dr->grid.hm1)));
+        a_rm.dgrid.tol2 = __builtin_bit_cast(float, pcl_rfl(__builtin_bit_cast(int, dr->grid.tol2)));
+        a_rm.zbuf = a_in.zbuf + (long long)pcl_rfl64((unsigned long long)dr->zoff);
+        a_rm.B = a_in.ngroups * G;                    // the room's candidates: what its z-buffer descriptor covers
+    }
     const PclLossArgs& a = RM ? a_rm : a_in;
     const PclFuseArgs& f = RM ? f_rm : f_in;
     // XCD-aware mapping: blocks b and b+8 share an XCD (round-robin dispatch) and each XCD has its own 4 MiB L2.  Within an
@@ -404,6 +421,20 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_rooms_sets_kernel(Pc
     pcl_loss_body<G, true, 0, FMT, true, true, true>(a, f, rooms);
 }
 
+// the depth mask inside a multi-room chain (pcl_gd_run_depth_chain): RM (+ CS) with VIS = 2, two launches per iteration only.  The depth
+// table is one more kernel argument after the room table.
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_rooms_depth_kernel(PclLossArgs a, const PclRoomTable* rooms, const PclDepthTable* depth)
+{
+    pcl_loss_body<G, true, 2, FMT, false, false, true>(a, PclFuseArgs{}, rooms, depth);
+}
+
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_rooms_sets_depth_kernel(PclLossArgs a, const PclRoomTable* rooms, const PclDepthTable* depth)
+{
+    pcl_loss_body<G, true, 2, FMT, false, true, true>(a, PclFuseArgs{}, rooms, depth);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launch planning (shared with the GD loop)
 
@@ -634,6 +665,44 @@ int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_
             if (G == 2) hipLaunchKernelGGL((pcl_loss_rooms_kernel<2, PCL_PANO_F32>), grid, blk, 0, s, a, rooms);
             else hipLaunchKernelGGL((pcl_loss_rooms_kernel<1, PCL_PANO_F32>), grid, blk, 0, s, a, rooms);
         }
+    }
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
+// The loss pass of a depth-masked multi-room chain (pcl_gd_run_depth_chain): as pcl_launch_loss_rooms without a fused form; every room's
+// grid and z-buffer region come from the device depth table `dtab`, `zbuf` is the base of the z-buffer set this iteration reads and
+// `zclear` the other set (zclear_vec4 16-byte words in all), which the launch resets for the next iteration's z passes.
+template <int G, int FMT>
+static void pcl_launch_rooms_depth(const PclLossArgs& a, const PclRoomTable* rooms, const PclDepthTable* dtab, bool sets, int nblk, hipStream_t s)
+{
+    if (sets) hipLaunchKernelGGL((pcl_loss_rooms_sets_depth_kernel<G, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, rooms, dtab);
+    else hipLaunchKernelGGL((pcl_loss_rooms_depth_kernel<G, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, rooms, dtab);
+}
+
+int pcl_launch_loss_rooms_depth(const PclRoomTable* rooms, const PclDepthTable* dtab, const void* pano, int pano_format, int H, int W,
+                                const PclPoseRec* poses, int B, int G, int ngroups, int nblk, float* partials, hipStream_t s, int flip, int color_sets,
+                                const uint32_t* zbuf, uint32_t* zclear, int64_t zclear_vec4)
+{
+    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;
+    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    if ((G != 1 && G != 2) || !zbuf || !zclear || nblk <= 0) return PCL_EINVAL;
+    PclLossArgs a = PclLossArgs{};
+    a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
+    a.poses = poses; a.B = B; a.partials = partials;
+    a.ngroups = ngroups; a.flip = flip & 1; a.xcd_groups = 0; a.color_sets = color_sets > 1 ? color_sets : 1;
+    a.zbuf = zbuf;
+    a.zclear = (pcl_i4*)zclear; a.zclear_total = zclear_vec4; a.zclear_per_block = (int)((zclear_vec4 + nblk - 1) / nblk);
+    const bool sets = color_sets > 1;
+    if (pano_format == PCL_PANO_U8) {
+        if (G == 2) pcl_launch_rooms_depth<2, PCL_PANO_U8>(a, rooms, dtab, sets, nblk, s);
+        else pcl_launch_rooms_depth<1, PCL_PANO_U8>(a, rooms, dtab, sets, nblk, s);
+    } else if (pano_format == PCL_PANO_F16) {
+        if (G == 2) pcl_launch_rooms_depth<2, PCL_PANO_F16>(a, rooms, dtab, sets, nblk, s);
+        else pcl_launch_rooms_depth<1, PCL_PANO_F16>(a, rooms, dtab, sets, nblk, s);
+    } else {
+        if (G == 2) pcl_launch_rooms_depth<2, PCL_PANO_F32>(a, rooms, dtab, sets, nblk, s);
+        else pcl_launch_rooms_depth<1, PCL_PANO_F32>(a, rooms, dtab, sets, nblk, s);
     }
     PCL_LAUNCH_CHECK();
     return 0;

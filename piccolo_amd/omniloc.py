@@ -367,7 +367,8 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     batch_mode=False gives every candidate omniloc's SEQUENTIAL semantics instead (what omniloc_all computes per image).
     rgb: one (N, 3) tensor, or a LIST of one per image (per-image colours, e.g. color_mod's): the cloud then holds a colour set per image
     and the chain runs the single-image plan, so image i's result is omniloc_batch(imgs[i], xyz, rgb[i], ...)'s bit for bit.  Images
-    beyond the colour-set addressing limit go in further groups; with the depth mask (no colour-set kernel) one image per chain."""
+    beyond the colour-set addressing limit go in further groups.  With the depth mask the colour-set chain is the depth chain
+    (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image."""
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     I = len(imgs)
@@ -375,7 +376,7 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     if isinstance(rgb, list):
         if len(rgb) != I:
             raise ValueError("omniloc_batch_images: %d colour sets for %d images" % (len(rgb), I))
-        sizes = [1] * I if bool(_cfg(cfg, "depth_mask", False)) else color_set_groups(int(xyz.shape[0]), I)
+        sizes = color_set_groups(int(xyz.shape[0]), I)
         if len(sizes) > 1:
             out, i0 = [], 0
             for m in sizes:
@@ -401,11 +402,33 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     return [[host[i, 0:3].reshape(3, 1).clone(), host[i, 3:12].reshape(3, 3).clone(), host[i, 12].clone()] for i in range(I)]
 
 
+def _depth_engine_args(cfg):
+    """the depth-mask arguments of the chain engines (ops.GradientDescentRooms / RoomsImages) from cfg"""
+    d_tau, d_res, d_st = _cfg(cfg, "depth_tau", None), _cfg(cfg, "depth_res", None), _cfg(cfg, "depth_stride", None)
+    return {"depth_mask": bool(_cfg(cfg, "depth_mask", False)), "depth_tau": None if d_tau is None else float(d_tau),
+            "depth_res": None if d_res is None else (int(d_res[0]), int(d_res[1])), "depth_stride": None if d_st is None else int(d_st)}
+
+
+def depth_tau_groups(points, H, W, cfg):
+    """Which rooms may share ONE depth-masked chain: lists of room indices, in order.  A chain has one visibility tolerance, a room run on its
+    own takes the tolerance of ITS grid (cfg.depth_tau, else the rule 3.5 pi / depth_h clipped to [0.02, 0.15]): rooms go together when that
+    value is the same.  One group with an explicit depth_tau or depth_res, and for default grids below 80 rows (clouds below ~150k occluder
+    samples: the rule's upper clip); larger rooms of different sizes split by their grids' tolerances.  Without the mask: one group."""
+    d = _depth_engine_args(cfg)
+    if not d["depth_mask"] or d["depth_tau"] is not None or d["depth_res"] is not None:
+        return [list(range(len(points)))]
+    groups = {}
+    for r, n in enumerate(points):
+        groups.setdefault(ops._depth_args(int(n), H, W, None, None, d["depth_stride"])[2], []).append(r)
+    return list(groups.values())
+
+
 def _rooms_chain(img, rooms, tr, ro, cfg, batch_mode):
     """One launch chain over at most PCL_GD_MAX_ROOMS rooms (ops.GradientDescentRooms) -> the engine.  `rooms`: (xyz, rgb) pairs; tr / ro:
     nrooms * per_room rows, room by room.  One texel format for the chain (the one the largest room's refinement would take: fp16 and RGBA8
     levels give the same bits).  Graph replay under _refine's rule on the chain's points x candidates; the engine (state, workspace, graph,
-    private copies of the packed clouds and boxes whose addresses the graph holds) is cached per room set and launch shape."""
+    private copies of the packed clouds and boxes whose addresses the graph holds) is cached per room set and launch shape.  With
+    cfg.depth_mask the chain is the depth chain (every room on its own grid) and runs eager, as every depth-masked refinement does."""
     clouds = [packed_cloud(xyz, rgb) for xyz, rgb in rooms]
     boxes = [quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05)) for xyz, _ in rooms]
     B = int(tr.shape[0])
@@ -419,10 +442,12 @@ def _rooms_chain(img, rooms, tr, ro, cfg, batch_mode):
         use_graph = bool(ops.EXPERIMENT.gd_graph)
     if use_graph is None:
         use_graph = sum(c.n for c in clouds) * per_room <= GRAPH_POINT_POSES
+    depth = _depth_engine_args(cfg)
+    use_graph = bool(use_graph) and not depth["depth_mask"]
 
     def make(cs, bs):
         return ops.GradientDescentRooms(list(zip(cs, bs)), pano, tr, ro, lr=hyper[0], patience=hyper[1], factor=hyper[2], batch_mode=hyper[3],
-                                        fuse=fuse)
+                                        fuse=fuse, **depth)
     if not use_graph:
         gd = make(clouds, boxes)
         gd.run(num_iter)
@@ -456,8 +481,9 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     rooms: list of (xyz, rgb) clouds in one frame; input_trans_list / input_rot_list: per room (B,3) starting poses (the same B for every
     room).  Returns one [t (3,1), R (3,3), loss ()] per room and writes the leaf rows back into the callers' tensors, as omniloc_batch does;
     room r's result is omniloc_batch(img, *rooms[r], ...)'s bit for bit (batch_mode=False: omniloc_all's sequential semantics, the winner of
-    each room's candidates).  More than PCL_GD_MAX_ROOMS rooms go in several chains; with the depth mask (no rooms instance of the loss
-    kernel) every room runs on its own."""
+    each room's candidates).  More than PCL_GD_MAX_ROOMS rooms go in several chains.  With the depth mask the chain is the depth chain
+    (pcl_gd_run_depth_chain: every room on its own z-buffer grid, the same bits per room); rooms whose tolerances differ (depth_tau_groups)
+    go in a chain per tolerance."""
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R = len(rooms)
@@ -466,9 +492,15 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     B = int(input_trans_list[0].shape[0])
     if any(int(t.shape[0]) != B for t in input_trans_list) or any(int(r.shape[0]) != B for r in input_rot_list):
         raise ValueError("omniloc_batch_rooms: every room needs the same number of starting poses")
-    if bool(_cfg(cfg, "depth_mask", False)):
-        return [omniloc_batch_images([img], xyz, rgb, [input_trans_list[r]], [input_rot_list[r]], cfg, scalar_summaries, batch_mode)[0]
-                for r, (xyz, rgb) in enumerate(rooms)]
+    groups = depth_tau_groups([int(xyz.shape[0]) for xyz, _ in rooms], int(img.shape[0]), int(img.shape[1]), cfg)
+    if len(groups) > 1:
+        out = [None] * R
+        for idx in groups:
+            part = omniloc_batch_rooms(img, [rooms[r] for r in idx], [input_trans_list[r] for r in idx], [input_rot_list[r] for r in idx], cfg,
+                                       scalar_summaries, batch_mode)
+            for r, o in zip(idx, part):
+                out[r] = o
+        return out
     if R == 1:                                         # one room: the single-room path itself (no concatenation, no per-room write-back)
         xyz, rgb = rooms[0]
         if batch_mode:
@@ -505,12 +537,28 @@ def rooms_images_chain_pays(points, per_image):
     return int(points) * int(per_image) <= ROOMS_IMAGES_POINT_POSES
 
 
+# The same question under the depth mask for images that SHARE the rooms' colours (tools/depth_chain_bench.py; rooms of
+# 166,667 points x 6 candidates, ms per (room, image), the shared depth chain against one omniloc_batch_images per room): 2 / 3 / 4 / 5 / 6 /
+# 7 images 1.52 against 1.92, 1.32 / 1.54, 1.20 / 1.36, 1.22 / 1.31, 1.17 / 1.24, 1.14 / 1.19 at 4 rooms (8 rooms alike) — and 8 images 1.11
+# against 0.97, 14 % SLOWER: a room's own chain of all its images cuts the cloud by the plan of 48 candidates and, with 8 images, gives every
+# XCD one image's texture (pcl_gd_run's mapping for several panoramas), which the rooms launch does not have.  Measured wins up to 42
+# candidates per room, the loss at 48; beyond the measured wins every room keeps its own chain.  Per-image colours always share the chain
+# (their other route is one chain per room AND image: 1.12 against 2.51 ms at 8 rooms x 8 images).
+DEPTH_SHARED_ROOM_CANDIDATES = 42
+
+
+def depth_shared_chain_pays(nimages, per_image):
+    """Under the depth mask, do several images that share the rooms' colours go into ONE rooms chain (True), or does every room run
+    omniloc_batch_images over its images (False)?"""
+    return int(nimages) * int(per_image) <= DEPTH_SHARED_ROOM_CANDIDATES
+
+
 def _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode):
     """One launch chain over I images x at most PCL_GD_MAX_ROOMS rooms (ops.GradientDescentRoomsImages) -> the engine.  `rooms`: (xyz, rgb)
     pairs whose rgb is one tensor in every room or a list of I tensors in every room; tr / ro: nrooms * I * per_image rows, room by room and
     image by image inside a room.  Set up like _rooms_chain: one texel format for the chain (the largest room's; float4 when the images do
     not agree), graph replay under _refine's rule on the chain's points x candidates, and a cached engine with private copies of the packed
-    clouds and boxes into which the colours of a later group of images are copied."""
+    clouds and boxes into which the colours of a later group of images are copied.  cfg.depth_mask: the depth chain, eager (_rooms_chain)."""
     I = len(imgs)
     per_image_sets = isinstance(rooms[0][1], list)
     clouds = [packed_cloud_sets(xyz, rgb) if per_image_sets else packed_cloud(xyz, rgb) for xyz, rgb in rooms]
@@ -529,10 +577,12 @@ def _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode):
         use_graph = bool(ops.EXPERIMENT.gd_graph)
     if use_graph is None:
         use_graph = sum(c.n for c in clouds) * per_room <= GRAPH_POINT_POSES
+    depth = _depth_engine_args(cfg)
+    use_graph = bool(use_graph) and not depth["depth_mask"]
 
     def make(cs, bs):
         return ops.GradientDescentRoomsImages(list(zip(cs, bs)), panos, tr, ro, lr=hyper[0], patience=hyper[1], factor=hyper[2],
-                                              batch_mode=hyper[3], fuse=fuse)
+                                              batch_mode=hyper[3], fuse=fuse, **depth)
     if not use_graph:
         gd = make(clouds, boxes)
         gd.run(num_iter)
@@ -571,9 +621,11 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     bit for bit (batch_mode=False: those of omniloc_batch_images([imgs[i]], ..., batch_mode=False)[0], the sequential semantics) for images
     whose texels are k/255 levels; for other images against the single call run with the chain's texel format (float4).
     Fallbacks: more than PCL_GD_MAX_ROOMS rooms go in several chains; with per-image colours, images beyond a room's colour-set limit
-    (color_set_groups of the largest room) go in groups, each a chain of its own; with the depth mask (no rooms instance of the loss
-    kernel) every room runs omniloc_batch_images on its own; one image is omniloc_batch_rooms, and so is every image of a chain too large to
-    gain from sharing (rooms_images_chain_pays: the same results, a chain per image)."""
+    (color_set_groups of the largest room) go in groups, each a chain of its own; one image is omniloc_batch_rooms, and so is every image of
+    a chain too large to gain from sharing (rooms_images_chain_pays: the same results, a chain per image).  With the depth mask the chain is
+    the depth chain (pcl_gd_run_depth_chain) under the same rules; rooms whose tolerances differ (depth_tau_groups) go in a chain per
+    tolerance, and images that share the rooms' colours run omniloc_batch_images per room where that is faster (depth_shared_chain_pays:
+    its plan of all the images' candidates, so equal to the single calls up to the summation order of the partial sums, as there)."""
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R, I = len(rooms), len(imgs)
@@ -588,7 +640,17 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     for _, rgb in rooms:
         if isinstance(rgb, list) and len(rgb) != I:
             raise ValueError("omniloc_batch_rooms_images: %d colour sets for %d images" % (len(rgb), I))
-    if bool(_cfg(cfg, "depth_mask", False)):
+    groups = depth_tau_groups([int(xyz.shape[0]) for xyz, _ in rooms], int(imgs[0].shape[0]), int(imgs[0].shape[1]), cfg)
+    if len(groups) > 1:
+        out = [None] * R
+        for idx in groups:
+            part = omniloc_batch_rooms_images(imgs, [rooms[r] for r in idx], [input_trans[r] for r in idx], [input_rot[r] for r in idx], cfg,
+                                              scalar_summaries, batch_mode)
+            for r, o in zip(idx, part):
+                out[r] = o
+        return out
+    if (bool(_cfg(cfg, "depth_mask", False)) and I > 1 and not any(isinstance(rgb, list) for _, rgb in rooms)
+            and not depth_shared_chain_pays(I, B)):
         return [omniloc_batch_images(imgs, xyz, rgb, input_trans[r], input_rot[r], cfg, scalar_summaries, batch_mode)
                 for r, (xyz, rgb) in enumerate(rooms)]
     if I > 1 and not rooms_images_chain_pays(sum(int(xyz.shape[0]) for xyz, _ in rooms), B):

@@ -306,6 +306,20 @@ def _depth_args(n, H, W, depth_res, depth_tau, depth_stride=None):
     return dh, dw, float(tau), st
 
 
+def _chain_depth_args(ns, H, W, depth_res, depth_tau, depth_stride=None):
+    """(depth_h, depth_w, tau, stride) for the hyper-parameters of ONE depth-masked chain over clouds of `ns` points
+    (pcl_gd_run_depth_chain): without depth_res 0 x 0 and the caller's stride (or 0), so that every room resolves its own default grid
+    and stride as a run of that room alone does.  The chain has ONE tolerance: rooms whose own tolerances (_depth_args) differ — default
+    grids of 80 rows and more without an explicit depth_tau — cannot share it and raise ValueError (omniloc groups its rooms by it)."""
+    per = [_depth_args(n, H, W, depth_res, depth_tau, depth_stride) for n in ns]
+    if len({p[2] for p in per}) > 1:
+        raise ValueError("a depth-masked chain has one tolerance: the rooms' default tolerances differ (%s): pass depth_tau"
+                         % sorted({round(p[2], 4) for p in per}))
+    if depth_res is None:
+        return 0, 0, per[0][2], int(depth_stride or 0)
+    return per[0]
+
+
 def sampling_loss(cloud, pano, trans, rot, with_grad=True, visible=None, depth=None):
     """(B, 8) float tensor on the GPU: loss, count, dL/dt(3), dL/d(yaw, pitch, roll).
     visible: (B, n) uint8 mask in packed point order.  depth: True, or a dict with optional depth_res / depth_tau / depth_stride — the
@@ -740,19 +754,42 @@ class GradientDescent:
         # a cloud of per-image colour sets (Cloud.with_color_sets): candidates [i * B / k, (i + 1) * B / k) read set i, and the chain runs
         # the single-image plan (pcl_gd_hyper.color_sets)
         self.hyper.color_sets = int(cloud.color_sets)
-        if cloud.color_sets > 1 and (self.B % cloud.color_sets or depth_mask):
-            raise ValueError("GradientDescent: %d candidates over %d colour sets%s" % (self.B, cloud.color_sets, " with the depth mask" if depth_mask else ""))
+        if cloud.color_sets > 1 and self.B % cloud.color_sets:
+            raise ValueError("GradientDescent: %d candidates over %d colour sets" % (self.B, cloud.color_sets))
+        # colour sets under the depth mask: the depth-chain family with this cloud as its one room (pcl_gd_run_depth_chain)
+        self._depth_sets = bool(depth_mask) and cloud.color_sets > 1
         self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
-        self.ws_bytes = lib.pcl_gd_workspace_bytes(cloud.n, self.B, pano.H, pano.W, ctypes.byref(self.hyper))
+        if self._depth_sets:
+            self.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(self._one_room(), 1, cloud.color_sets, self.B // cloud.color_sets, pano.H, pano.W,
+                                                                   ctypes.byref(self.hyper))
+        else:
+            self.ws_bytes = lib.pcl_gd_workspace_bytes(cloud.n, self.B, pano.H, pano.W, ctypes.byref(self.hyper))
         if self.ws_bytes == 0:
             raise _lib.PiccoloHipError("pcl_gd_workspace_bytes: invalid arguments (depth grid %dx%d?)" % (dh, dw))
         self.ws = _bytes(self.ws_bytes)
-        _lib.check(lib.pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()),
-                   "pcl_gd_init")
+        self._init(trans, rot)
+
+    def _one_room(self):
+        return (_lib.GdRoom * 1)(_lib.GdRoom(self.cloud.data.data_ptr(), self.cloud.n, self.box.data_ptr()))
+
+    def _init(self, trans, rot):
+        lib = _lib.load()
+        if self._depth_sets:
+            k = self.cloud.color_sets
+            _lib.check(lib.pcl_gd_init_rooms_images(_ptr(self.state), _ptr(trans), _ptr(rot), 1, k, self.B // k, ctypes.byref(self.hyper), _stream()),
+                       "pcl_gd_init_rooms_images")
+        else:
+            _lib.check(lib.pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
 
     def run(self, num_iter, history=False, timer=None):
         lib = _lib.load()
         hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
+        if self._depth_sets:
+            k = self.cloud.color_sets
+            _lib.check(lib.pcl_gd_run_depth_chain(self._one_room(), 1, k, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state),
+                                                  self.B // k, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
+                                                  timer.handle if timer else None, _stream()), "pcl_gd_run_depth_chain")
+            return hist
         _lib.check(lib.pcl_gd_run(_ptr(self.cloud.data), self.cloud.n, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
                                   _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper), int(num_iter),
                                   _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None, _stream()),
@@ -781,11 +818,9 @@ class GradientDescent:
     def reset(self, trans, rot):
         """Re-initialise the optimiser state for new starting poses (same cloud / panorama / B): lets one captured
         graph serve many refinements."""
-        lib = _lib.load()
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         assert trans.shape[0] == self.B
-        _lib.check(lib.pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()),
-                   "pcl_gd_init")
+        self._init(trans, rot)
 
     def set_panos(self, panos):
         """Candidate b samples panos[b] (a list of B Pano objects, all the size / texel format of self.pano): lets the
@@ -854,12 +889,24 @@ class GradientDescent:
         return out
 
 
+def _plan_depth_chain(rooms, nrooms, nimages, per_image, pano, hyper):
+    """-> (nchunks per room, poses per block, False, [(depth_h, depth_w, occluder stride) per room]): pcl_gd_plan_depth_chain"""
+    arr = lambda: (ctypes.c_int * nrooms)()      # noqa: E731
+    nch, dh, dw, st, G = arr(), arr(), arr(), arr(), ctypes.c_int(0)
+    _lib.check(_lib.load().pcl_gd_plan_depth_chain(rooms, nrooms, nimages, per_image, pano.H, pano.W, ctypes.byref(hyper), nch, ctypes.byref(G), dh, dw,
+                                                   st), "pcl_gd_plan_depth_chain")
+    return list(nch), G.value, False, list(zip(dh, dw, st))
+
+
 class GradientDescentRooms:
     """On-device GD refinement of ONE panorama against several rooms in one launch chain (pcl_gd_run_rooms): `rooms` is a list of
     (Cloud, box) pairs, `trans` / `rot` hold nrooms * per_room rows, room r's candidates the rows [r * per_room, (r + 1) * per_room).
     Every room's results equal those of a GradientDescent over that room alone, bit for bit.  At most PCL_GD_MAX_ROOMS rooms."""
 
-    def __init__(self, rooms, pano, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None):
+    def __init__(self, rooms, pano, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None, depth_mask=False, depth_tau=None,
+                 depth_res=None, depth_stride=None):
+        """depth_mask: the scatter-min depth mask in the chain (pcl_gd_run_depth_chain, nimages = 1): every room on its own grid, as
+        GradientDescent(depth_mask=True) of that room resolves it; depth_res applies to every room."""
         lib = _lib.load()
         if not 1 <= len(rooms) <= _lib.GD_MAX_ROOMS:
             raise ValueError("GradientDescentRooms: %d rooms (1..%d per chain)" % (len(rooms), _lib.GD_MAX_ROOMS))
@@ -875,18 +922,27 @@ class GradientDescentRooms:
         if self.B % self.nrooms or self.B == 0:
             raise ValueError("GradientDescentRooms: %d candidates do not split into %d rooms" % (self.B, self.nrooms))
         self.per_room = self.B // self.nrooms
+        self.depth_mask = bool(depth_mask)
+        dh, dw, tau, st = (_chain_depth_args([c.n for c in self.clouds], pano.H, pano.W, depth_res, depth_tau, depth_stride) if depth_mask
+                           else (0, 0, 0.0, 0))
         self.hyper = _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL,
-                                  0, 0.0, 0, 0, 0, -1 if fuse is False else 0, 0, 0)
+                                  1 if depth_mask else 0, float(tau), int(dh), int(dw), int(st), -1 if fuse is False else 0, 0, 0)
         self._rooms = (_lib.GdRoom * self.nrooms)(*[_lib.GdRoom(c.data.data_ptr(), c.n, b.data_ptr()) for c, b in zip(self.clouds, self.boxes)])
         self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
-        self.ws_bytes = lib.pcl_gd_rooms_workspace_bytes(self._rooms, self.nrooms, self.per_room, ctypes.byref(self.hyper))
+        if depth_mask:
+            self.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(self._rooms, self.nrooms, 1, self.per_room, pano.H, pano.W, ctypes.byref(self.hyper))
+        else:
+            self.ws_bytes = lib.pcl_gd_rooms_workspace_bytes(self._rooms, self.nrooms, self.per_room, ctypes.byref(self.hyper))
         if self.ws_bytes == 0:
-            raise _lib.PiccoloHipError("pcl_gd_rooms_workspace_bytes: invalid arguments")
+            raise _lib.PiccoloHipError("pcl_gd_%s_workspace_bytes: invalid arguments" % ("depth_chain" if depth_mask else "rooms"))
         self.ws = _bytes(self.ws_bytes)
-        _lib.check(lib.pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
+        self.reset(trans, rot)
 
     def plan(self):
-        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms"""
+        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms; with the depth mask (never fused) a fourth item, per room
+        (depth_h, depth_w, occluder stride): pcl_gd_plan_depth_chain"""
+        if self.depth_mask:
+            return _plan_depth_chain(self._rooms, self.nrooms, 1, self.per_room, self.pano, self.hyper)
         nch, G, fused = (ctypes.c_int * self.nrooms)(), ctypes.c_int(0), ctypes.c_int(0)
         _lib.check(_lib.load().pcl_gd_plan_rooms(self._rooms, self.nrooms, self.per_room, ctypes.byref(self.hyper), nch, ctypes.byref(G),
                                                  ctypes.byref(fused)), "pcl_gd_plan_rooms")
@@ -895,6 +951,11 @@ class GradientDescentRooms:
     def run(self, num_iter, history=False, timer=None):
         lib = _lib.load()
         hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
+        if self.depth_mask:
+            _lib.check(lib.pcl_gd_run_depth_chain(self._rooms, self.nrooms, 1, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
+                                                  _ptr(self.state), self.per_room, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws),
+                                                  self.ws_bytes, timer.handle if timer else None, _stream()), "pcl_gd_run_depth_chain")
+            return hist
         _lib.check(lib.pcl_gd_run_rooms(self._rooms, self.nrooms, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state),
                                         self.per_room, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
                                         timer.handle if timer else None, _stream()), "pcl_gd_run_rooms")
@@ -922,7 +983,9 @@ class GradientDescentRoomsImages:
     or I of them (Cloud.with_color_sets: image i reads set i of every room).  The results of every (room, image) equal those of a
     GradientDescent over that room and image alone, bit for bit.  At most PCL_GD_MAX_ROOMS rooms."""
 
-    def __init__(self, rooms, panos, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None):
+    def __init__(self, rooms, panos, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None, depth_mask=False, depth_tau=None,
+                 depth_res=None, depth_stride=None):
+        """depth_mask: as for GradientDescentRooms (pcl_gd_run_depth_chain)."""
         lib = _lib.load()
         if not 1 <= len(rooms) <= _lib.GD_MAX_ROOMS:
             raise ValueError("GradientDescentRoomsImages: %d rooms (1..%d per chain)" % (len(rooms), _lib.GD_MAX_ROOMS))
@@ -941,19 +1004,30 @@ class GradientDescentRoomsImages:
         if self.B % (self.nrooms * self.nimages) or self.B == 0:
             raise ValueError("GradientDescentRoomsImages: %d candidates do not split into %d rooms x %d images" % (self.B, self.nrooms, self.nimages))
         self.per_image = self.B // (self.nrooms * self.nimages)
+        self.depth_mask = bool(depth_mask)
+        dh, dw, tau, st = (_chain_depth_args([c.n for c in self.clouds], self.pano.H, self.pano.W, depth_res, depth_tau, depth_stride) if depth_mask
+                           else (0, 0, 0.0, 0))
         self.hyper = _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL,
-                                  0, 0.0, 0, 0, 0, -1 if fuse is False else 0, 0, self.color_sets if self.color_sets > 1 else 0)
+                                  1 if depth_mask else 0, float(tau), int(dh), int(dw), int(st), -1 if fuse is False else 0, 0,
+                                  self.color_sets if self.color_sets > 1 else 0)
         self._rooms = (_lib.GdRoom * self.nrooms)(*[_lib.GdRoom(c.data.data_ptr(), c.n, b.data_ptr()) for c, b in zip(self.clouds, self.boxes)])
         self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
-        self.ws_bytes = lib.pcl_gd_rooms_images_workspace_bytes(self._rooms, self.nrooms, self.nimages, self.per_image, ctypes.byref(self.hyper))
+        if depth_mask:
+            self.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(self._rooms, self.nrooms, self.nimages, self.per_image, self.pano.H, self.pano.W,
+                                                                   ctypes.byref(self.hyper))
+        else:
+            self.ws_bytes = lib.pcl_gd_rooms_images_workspace_bytes(self._rooms, self.nrooms, self.nimages, self.per_image, ctypes.byref(self.hyper))
         if self.ws_bytes == 0:
-            raise _lib.PiccoloHipError("pcl_gd_rooms_images_workspace_bytes: invalid arguments")
+            raise _lib.PiccoloHipError("pcl_gd_%s_workspace_bytes: invalid arguments" % ("depth_chain" if depth_mask else "rooms_images"))
         self.ws = _bytes(self.ws_bytes)
         self.reset(trans, rot)
         self.set_panos(panos)
 
     def plan(self):
-        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms_images"""
+        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms_images; with the depth mask a fourth item, the per-room grids
+        (GradientDescentRooms.plan)"""
+        if self.depth_mask:
+            return _plan_depth_chain(self._rooms, self.nrooms, self.nimages, self.per_image, self.pano, self.hyper)
         nch, G, fused = (ctypes.c_int * self.nrooms)(), ctypes.c_int(0), ctypes.c_int(0)
         _lib.check(_lib.load().pcl_gd_plan_rooms_images(self._rooms, self.nrooms, self.nimages, self.per_image, ctypes.byref(self.hyper), nch,
                                                         ctypes.byref(G), ctypes.byref(fused)), "pcl_gd_plan_rooms_images")
@@ -981,6 +1055,11 @@ class GradientDescentRoomsImages:
     def run(self, num_iter, history=False, timer=None):
         lib = _lib.load()
         hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
+        if self.depth_mask:
+            _lib.check(lib.pcl_gd_run_depth_chain(self._rooms, self.nrooms, self.nimages, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
+                                                  _ptr(self.state), self.per_image, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws),
+                                                  self.ws_bytes, timer.handle if timer else None, _stream()), "pcl_gd_run_depth_chain")
+            return hist
         _lib.check(lib.pcl_gd_run_rooms_images(self._rooms, self.nrooms, self.nimages, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
                                                _ptr(self.state), self.per_image, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws),
                                                self.ws_bytes, timer.handle if timer else None, _stream()), "pcl_gd_run_rooms_images")
