@@ -194,53 +194,71 @@ def _rot_matrix(ypr):
 GRAPH_POINT_POSES = 16_000_000         # use graph replay when points x candidates is at most this (cfg key gd_graph overrides)
 
 
+def _engine_args(cfg, batch_mode=True):
+    """The keyword arguments every GD engine of ops takes, from cfg: the hyper-parameters, one or two launches per iteration (cfg gd_fuse =
+    False: two, bit-identical) and the depth mask's optional tolerance, grid and occluder stride."""
+    d_tau, d_res, d_st = _cfg(cfg, "depth_tau", None), _cfg(cfg, "depth_res", None), _cfg(cfg, "depth_stride", None)
+    return {"lr": float(_cfg(cfg, "lr", 0.1)), "patience": int(_cfg(cfg, "patience", 5)), "factor": float(_cfg(cfg, "factor", 0.9)),
+            "batch_mode": bool(batch_mode), "fuse": None if _cfg(cfg, "gd_fuse", True) else False,
+            "depth_mask": bool(_cfg(cfg, "depth_mask", False)), "depth_tau": None if d_tau is None else float(d_tau),
+            "depth_res": None if d_res is None else (int(d_res[0]), int(d_res[1])), "depth_stride": None if d_st is None else int(d_st)}
+
+
+def _replays_graph(cfg, point_poses, depth_mask):
+    """Does a chain of `point_poses` points x candidates replay a captured graph?  cfg gd_graph decides, else the size; a depth-masked chain
+    always runs eager."""
+    use_graph = _cfg(cfg, "gd_graph", None)
+    if use_graph is None and ops.EXPERIMENT.gd_graph is not None:                   # experiments
+        use_graph = bool(ops.EXPERIMENT.gd_graph)
+    if use_graph is None:
+        use_graph = point_poses <= GRAPH_POINT_POSES
+    return bool(use_graph) and not depth_mask
+
+
+def _cached_engine(kind, xyzs, sub, make, clouds, boxes):
+    """One engine (state, workspace, captured graph) per POINT SETS `xyzs` and launch shape `sub` -> (engine, fresh: it was made just now, with
+    the caller's poses).  The colours may change with every query image (color_mod / match_color give each image its own rgb, or its own
+    colour sets): the engine make(clouds, boxes) builds owns private copies of the packed clouds and boxes, whose addresses its captured graph
+    holds, and clouds with other colours are copied into them (24 bytes per point on the device) instead of capturing a new graph per image."""
+    def make_private():
+        private = [ops.Cloud.private_copy(c) for c in clouds], [ops._dev(b).reshape(6).clone() for b in boxes]
+        g = make(*private)
+        g._private = private
+        g._cloud_src = [weakref.ref(c) for c in clouds]      # the copies just made ARE these clouds: nothing to copy on first use
+        g._box_src, g._fresh = list(boxes), True             # (weak above: the engine must not keep packed clouds of past images alive)
+        return g
+    gd = _cached(kind, xyzs, make_private, sub=sub)
+    fresh, gd._fresh = gd._fresh, False
+    for r, (c, b) in enumerate(zip(clouds, boxes)):
+        if gd._cloud_src[r]() is not c:
+            gd._private[0][r].data.copy_(c.data)
+            gd._cloud_src[r] = weakref.ref(c)
+        if gd._box_src[r] is not b:                          # (the cached box tensor of this cloud: identity is enough)
+            gd._private[1][r].copy_(ops._dev(b).reshape(6))
+            gd._box_src[r] = b
+    return gd, fresh
+
+
 def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None):
     """Run the on-device GD for the rows of trans / rot and return the GradientDescent object (read gd.result() / gd.winner()).
     `panos`: one packed panorama per query image; the B rows split evenly over them, image by image.  `rgb`: one (N, 3) tensor, or a list
     of one per query image (per-image colour sets: image i's candidates read set i, and the chain runs the single-image plan).
-    The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape."""
+    The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape (_cached_engine)."""
     cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb)
     trans, rot = ops._dev(trans).reshape(-1, 3), ops._dev(rot).reshape(-1, 3)
     B = int(trans.shape[0])
     p0 = panos[0]
     num_iter = _cfg(cfg, "num_iter", 100)
-    depth = bool(_cfg(cfg, "depth_mask", False))
-    d_tau, d_res, d_st = _cfg(cfg, "depth_tau", None), _cfg(cfg, "depth_res", None), _cfg(cfg, "depth_stride", None)
-    hyper = (float(_cfg(cfg, "lr", 0.1)), int(_cfg(cfg, "patience", 5)), float(_cfg(cfg, "factor", 0.9)), bool(batch_mode), depth,
-             None if d_tau is None else float(d_tau), None if d_res is None else (int(d_res[0]), int(d_res[1])), None if d_st is None else int(d_st))
-    use_graph = _cfg(cfg, "gd_graph", None)
-    if use_graph is None and ops.EXPERIMENT.gd_graph is not None:                   # experiments
-        use_graph = bool(ops.EXPERIMENT.gd_graph)
-    fuse = None if _cfg(cfg, "gd_fuse", True) else False       # (cfg gd_fuse = False: two launches per iteration, bit-identical)
-    if use_graph is None:
-        use_graph = cloud.n * B <= GRAPH_POINT_POSES
-    use_graph = bool(use_graph) and vis_hook is None and not depth
+    args = _engine_args(cfg, batch_mode)
+    use_graph = _replays_graph(cfg, cloud.n * B, args["depth_mask"]) and vis_hook is None
 
-    def make(c=cloud, bx=box):
-        return ops.GradientDescent(c, p0, trans, rot, bx, lr=hyper[0], patience=hyper[1], factor=hyper[2], batch_mode=hyper[3],
-                                   depth_mask=hyper[4], depth_tau=hyper[5], depth_res=hyper[6], depth_stride=hyper[7], fuse=fuse)
+    def make(cs, bs):
+        return ops.GradientDescent(cs[0], p0, trans, rot, bs[0], **args)
     if not use_graph:
-        gd = make()                                        # (fresh buffers: nothing worth keeping for a long eager chain)
+        gd = make([cloud], [box])                          # (fresh buffers: nothing worth keeping for a long eager chain)
     else:
-        # One engine (state, workspace, captured graph) per POINT SET and launch shape.  The colours may change with every query
-        # image (color_mod / match_color give each image its own rgb): the engine owns a private copy of the packed cloud whose
-        # address the captured graph holds, and a cloud with other colours is copied into it (24 bytes per point on the device)
-        # instead of capturing a new graph per image.  The same for a cloud of per-image colour sets: one engine per (point set, shape,
-        # number of sets), the new sets copied into its buffer.
-        def make_private():
-            g = make(ops.Cloud.private_copy(cloud), ops._dev(box).reshape(6).clone())     # (its own box buffer: updated in place below)
-            g._cloud_src = weakref.ref(cloud)                # the copy just made IS this cloud: nothing to copy on first use
-            g._box_src, g._fresh = box, True
-            return g
-        # (one or two launches per iteration is frozen into a captured graph: part of the key)
-        gd = _cached("gd", (xyz,), make_private, sub=(B, len(panos), p0.H, p0.W, p0.fmt, fuse, cloud.color_sets) + hyper)
-        fresh, gd._fresh = gd._fresh, False                  # (a new engine was initialised with these very poses)
-        if gd._cloud_src() is not cloud:                     # weak: the engine must not keep packed clouds of past images alive
-            gd.cloud.data.copy_(cloud.data)
-            gd._cloud_src = weakref.ref(cloud)
-        if gd._box_src is not box:                           # in place: the captured graph holds this buffer's address
-            gd.box.copy_(ops._dev(box).reshape(6))
-            gd._box_src = box                                # (the cached box tensor of this cloud: identity is enough)
+        # (one or two launches per iteration is frozen into a captured graph: part of the key, with the other arguments)
+        gd, fresh = _cached_engine("gd", (xyz,), (B, len(panos), p0.H, p0.W, p0.fmt, cloud.color_sets) + tuple(args.values()), make, [cloud], [box])
         if not fresh:
             gd.reset(trans, rot)
     if len(panos) > 1 or use_graph:
@@ -252,6 +270,39 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None):
     else:
         gd.run(num_iter)
     return gd
+
+
+def _refine_groups(chain, trans_list, rot_list):
+    """The groups of one chain, start to end: trans_list / rot_list hold one (B, 3) tensor of starting poses per group of candidates (an
+    image, a room, a room's image: the same B everywhere), chain(tr, ro) runs the engine over their concatenation.  -> per group
+    [t (3,1), R (3,3), loss ()] of the candidate with the smallest last loss (omniloc.py:271), after ONE D2H copy, the leaf rows written
+    back into the callers' tensors."""
+    n, B = len(trans_list), int(trans_list[0].shape[0])
+    tr = torch.cat([ops._dev(t).reshape(B, 3) for t in trans_list])
+    ro = torch.cat([ops._dev(r).reshape(B, 3) for r in rot_list])
+    gd = chain(tr, ro)
+    leaf_t, leaf_r = torch.empty(n * B, 3, dtype=torch.float32, device=tr.device), torch.empty(n * B, 3, dtype=torch.float32, device=tr.device)
+    host = gd.winners(n, leaf_t, leaf_r).cpu()
+    with torch.no_grad():
+        for k, (t, r) in enumerate(zip(trans_list, rot_list)):
+            t.copy_(leaf_t[k * B:(k + 1) * B].reshape(t.shape).to(t.device))
+            r.copy_(leaf_r[k * B:(k + 1) * B].reshape(r.shape).to(r.device))
+    return [[host[k, 0:3].reshape(3, 1).clone(), host[k, 3:12].reshape(3, 3).clone(), host[k, 12].clone()] for k in range(n)]
+
+
+def _over_room_groups(groups, part):
+    """part(idx) -> the results of the rooms `idx` (a list of room indices); -> the results of all the rooms of `groups`, in room order"""
+    out = [None] * sum(len(idx) for idx in groups)
+    for idx in groups:
+        for r, o in zip(idx, part(idx)):
+            out[r] = o
+    return out
+
+
+def _room_cap_groups(R):
+    """rooms 0..R-1 in runs of at most PCL_GD_MAX_ROOMS, the rooms of one chain"""
+    cap = ops._lib.GD_MAX_ROOMS
+    return [list(range(r0, min(r0 + cap, R))) for r0 in range(0, R, cap)]
 
 
 def _leaf_buffers(input_trans, input_rot, B):
@@ -384,29 +435,12 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
                                             input_rot_list[i0:i0 + m], cfg, scalar_summaries, batch_mode)
                 i0 += m
             return out
-    B = int(input_trans_list[0].shape[0])
     fmt = ops.refine_texels(xyz.shape[0], imgs[0].shape[0], imgs[0].shape[1])
     panos = [packed_pano(im, n_points=xyz.shape[0]) if I <= 8 else ops.Pano(im, fmt=fmt if ops._known_levels(im) else "auto") for im in imgs]
     if len({p.fmt for p in panos}) > 1:          # a launch needs ONE texel format: float4 holds any image
         panos = [ops.Pano(im, fmt="f32") for im in imgs]
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
-    tr = torch.cat([ops._dev(t).reshape(B, 3) for t in input_trans_list])
-    ro = torch.cat([ops._dev(r).reshape(B, 3) for r in input_rot_list])
-    gd = _refine(xyz, rgb, panos, tr, ro, box, cfg, batch_mode)
-    leaf_t, leaf_r = torch.empty(I * B, 3, dtype=torch.float32, device=tr.device), torch.empty(I * B, 3, dtype=torch.float32, device=tr.device)
-    host = gd.winner(I, leaf_t, leaf_r).cpu()                # per image: the smallest last loss (omniloc.py:271), one D2H copy
-    with torch.no_grad():
-        for i in range(I):
-            input_trans_list[i].copy_(leaf_t[i * B:(i + 1) * B].to(input_trans_list[i].device))
-            input_rot_list[i].copy_(leaf_r[i * B:(i + 1) * B].to(input_rot_list[i].device))
-    return [[host[i, 0:3].reshape(3, 1).clone(), host[i, 3:12].reshape(3, 3).clone(), host[i, 12].clone()] for i in range(I)]
-
-
-def _depth_engine_args(cfg):
-    """the depth-mask arguments of the chain engines (ops.GradientDescentRooms / RoomsImages) from cfg"""
-    d_tau, d_res, d_st = _cfg(cfg, "depth_tau", None), _cfg(cfg, "depth_res", None), _cfg(cfg, "depth_stride", None)
-    return {"depth_mask": bool(_cfg(cfg, "depth_mask", False)), "depth_tau": None if d_tau is None else float(d_tau),
-            "depth_res": None if d_res is None else (int(d_res[0]), int(d_res[1])), "depth_stride": None if d_st is None else int(d_st)}
+    return _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, batch_mode), input_trans_list, input_rot_list)
 
 
 def depth_tau_groups(points, H, W, cfg):
@@ -414,7 +448,7 @@ def depth_tau_groups(points, H, W, cfg):
     own takes the tolerance of ITS grid (cfg.depth_tau, else the rule 3.5 pi / depth_h clipped to [0.02, 0.15]): rooms go together when that
     value is the same.  One group with an explicit depth_tau or depth_res, and for default grids below 80 rows (clouds below ~150k occluder
     samples: the rule's upper clip); larger rooms of different sizes split by their grids' tolerances.  Without the mask: one group."""
-    d = _depth_engine_args(cfg)
+    d = _engine_args(cfg)
     if not d["depth_mask"] or d["depth_tau"] is not None or d["depth_res"] is not None:
         return [list(range(len(points)))]
     groups = {}
@@ -423,56 +457,48 @@ def depth_tau_groups(points, H, W, cfg):
     return list(groups.values())
 
 
-def _rooms_chain(img, rooms, tr, ro, cfg, batch_mode):
-    """One launch chain over at most PCL_GD_MAX_ROOMS rooms (ops.GradientDescentRooms) -> the engine.  `rooms`: (xyz, rgb) pairs; tr / ro:
-    nrooms * per_room rows, room by room.  One texel format for the chain (the one the largest room's refinement would take: fp16 and RGBA8
-    levels give the same bits).  Graph replay under _refine's rule on the chain's points x candidates; the engine (state, workspace, graph,
-    private copies of the packed clouds and boxes whose addresses the graph holds) is cached per room set and launch shape.  With
-    cfg.depth_mask the chain is the depth chain (every room on its own grid) and runs eager, as every depth-masked refinement does."""
-    clouds = [packed_cloud(xyz, rgb) for xyz, rgb in rooms]
+def _chain(kind, imgs, rooms, tr, ro, cfg, batch_mode):
+    """One launch chain over the images `imgs` x at most PCL_GD_MAX_ROOMS rooms -> the engine, run.  kind "gd_rooms": the one image of
+    ops.GradientDescentRooms; "gd_rooms_images": ops.GradientDescentRoomsImages (the two cache kinds).  `rooms`: (xyz, rgb) pairs whose rgb
+    is one tensor in every room or a list of one tensor per image in every room; tr / ro: nrooms * images * per_image rows, room by room and
+    image by image inside a room.  One texel format for the chain (the one the largest room's refinement would take: fp16 and RGBA8 levels
+    give the same bits; float4 when the images do not agree).  Graph replay under _refine's rule on the chain's points x candidates; the
+    engine is cached per room set and launch shape (_cached_engine).  With cfg.depth_mask the chain is the depth chain (every room on its own
+    grid) and runs eager, as every depth-masked refinement does."""
+    one_image = kind == "gd_rooms"
+    per_image_sets = isinstance(rooms[0][1], list)
+    clouds = [packed_cloud_sets(xyz, rgb) if per_image_sets else packed_cloud(xyz, rgb) for xyz, rgb in rooms]
     boxes = [quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05)) for xyz, _ in rooms]
-    B = int(tr.shape[0])
-    per_room = B // len(rooms)
-    pano = packed_pano(img, n_points=max(int(xyz.shape[0]) for xyz, _ in rooms))
+    per_room = int(tr.shape[0]) // len(rooms)
+    nmax = max(int(xyz.shape[0]) for xyz, _ in rooms)
+    panos = [packed_pano(im, n_points=nmax) for im in imgs]
+    if len({p.fmt for p in panos}) > 1:          # a launch needs ONE texel format: float4 holds any image
+        panos = [ops.Pano(im, fmt="f32") for im in imgs]
+    p0 = panos[0]
     num_iter = _cfg(cfg, "num_iter", 100)
-    hyper = (float(_cfg(cfg, "lr", 0.1)), int(_cfg(cfg, "patience", 5)), float(_cfg(cfg, "factor", 0.9)), bool(batch_mode))
-    fuse = None if _cfg(cfg, "gd_fuse", True) else False
-    use_graph = _cfg(cfg, "gd_graph", None)
-    if use_graph is None and ops.EXPERIMENT.gd_graph is not None:                   # experiments
-        use_graph = bool(ops.EXPERIMENT.gd_graph)
-    if use_graph is None:
-        use_graph = sum(c.n for c in clouds) * per_room <= GRAPH_POINT_POSES
-    depth = _depth_engine_args(cfg)
-    use_graph = bool(use_graph) and not depth["depth_mask"]
+    args = _engine_args(cfg, batch_mode)
 
     def make(cs, bs):
-        return ops.GradientDescentRooms(list(zip(cs, bs)), pano, tr, ro, lr=hyper[0], patience=hyper[1], factor=hyper[2], batch_mode=hyper[3],
-                                        fuse=fuse, **depth)
-    if not use_graph:
+        if one_image:
+            return ops.GradientDescentRooms(list(zip(cs, bs)), p0, tr, ro, **args)
+        return ops.GradientDescentRoomsImages(list(zip(cs, bs)), panos, tr, ro, **args)
+    if not _replays_graph(cfg, sum(c.n for c in clouds) * per_room, args["depth_mask"]):
         gd = make(clouds, boxes)
         gd.run(num_iter)
         return gd
-
-    def make_private():
-        g = make([ops.Cloud.private_copy(c) for c in clouds], [ops._dev(b).reshape(6).clone() for b in boxes])
-        g._cloud_src = [weakref.ref(c) for c in clouds]
-        g._box_src, g._fresh = list(boxes), True
-        return g
-    xyzs = tuple(xyz for xyz, _ in rooms)
-    gd = _cached("gd_rooms", xyzs, make_private, sub=(per_room, pano.H, pano.W, pano.fmt, fuse) + hyper)
-    fresh, gd._fresh = gd._fresh, False
-    for r, c in enumerate(clouds):
-        if gd._cloud_src[r]() is not c:                # (the colours may change with every query image)
-            gd.clouds[r].data.copy_(c.data)
-            gd._cloud_src[r] = weakref.ref(c)
-        if gd._box_src[r] is not boxes[r]:
-            gd.boxes[r].copy_(ops._dev(boxes[r]).reshape(6))
-            gd._box_src[r] = boxes[r]
+    gd, fresh = _cached_engine(kind, tuple(xyz for xyz, _ in rooms),
+                               (len(imgs), per_room, p0.H, p0.W, p0.fmt, clouds[0].color_sets) + tuple(args.values()), make, clouds, boxes)
     if not fresh:
         gd.reset(tr, ro)
-    ops.GradientDescent.set_pano_groups(gd, [pano])     # the pose records name this image's panorama (the graph holds the first one's)
+    if not fresh or one_image:                   # (a new several-image engine has named its panoramas itself)
+        gd.set_panos(panos)                      # the pose records name these images' panoramas (the graph holds the first ones')
     gd.run_graph(num_iter)
     return gd
+
+
+def _rooms_chain(img, rooms, tr, ro, cfg, batch_mode):
+    """_chain of ONE image: rgb one tensor per room, tr / ro nrooms * per_room rows"""
+    return _chain("gd_rooms", [img], rooms, tr, ro, cfg, batch_mode)
 
 
 def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scalar_summaries=None, batch_mode=True):
@@ -493,36 +519,20 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     if any(int(t.shape[0]) != B for t in input_trans_list) or any(int(r.shape[0]) != B for r in input_rot_list):
         raise ValueError("omniloc_batch_rooms: every room needs the same number of starting poses")
     groups = depth_tau_groups([int(xyz.shape[0]) for xyz, _ in rooms], int(img.shape[0]), int(img.shape[1]), cfg)
+
+    def part(idx):
+        return omniloc_batch_rooms(img, [rooms[r] for r in idx], [input_trans_list[r] for r in idx], [input_rot_list[r] for r in idx], cfg,
+                                   scalar_summaries, batch_mode)
     if len(groups) > 1:
-        out = [None] * R
-        for idx in groups:
-            part = omniloc_batch_rooms(img, [rooms[r] for r in idx], [input_trans_list[r] for r in idx], [input_rot_list[r] for r in idx], cfg,
-                                       scalar_summaries, batch_mode)
-            for r, o in zip(idx, part):
-                out[r] = o
-        return out
+        return _over_room_groups(groups, part)
     if R == 1:                                         # one room: the single-room path itself (no concatenation, no per-room write-back)
         xyz, rgb = rooms[0]
         if batch_mode:
             return [omniloc_batch(img, xyz, rgb, input_trans_list[0], input_rot_list[0], cfg, scalar_summaries)]
         return omniloc_batch_images([img], xyz, rgb, [input_trans_list[0]], [input_rot_list[0]], cfg, scalar_summaries, batch_mode=False)
-    cap = ops._lib.GD_MAX_ROOMS
-    if R > cap:
-        out = []
-        for r0 in range(0, R, cap):
-            out += omniloc_batch_rooms(img, rooms[r0:r0 + cap], input_trans_list[r0:r0 + cap], input_rot_list[r0:r0 + cap], cfg, scalar_summaries,
-                                       batch_mode)
-        return out
-    tr = torch.cat([ops._dev(t).reshape(B, 3) for t in input_trans_list])
-    ro = torch.cat([ops._dev(r).reshape(B, 3) for r in input_rot_list])
-    gd = _rooms_chain(img, rooms, tr, ro, cfg, batch_mode)
-    leaf_t, leaf_r = torch.empty(R * B, 3, dtype=torch.float32, device=tr.device), torch.empty(R * B, 3, dtype=torch.float32, device=tr.device)
-    host = gd.winner(leaf_t, leaf_r).cpu()
-    with torch.no_grad():
-        for r in range(R):
-            input_trans_list[r].copy_(leaf_t[r * B:(r + 1) * B].reshape(input_trans_list[r].shape).to(input_trans_list[r].device))
-            input_rot_list[r].copy_(leaf_r[r * B:(r + 1) * B].reshape(input_rot_list[r].shape).to(input_rot_list[r].device))
-    return [[host[r, 0:3].reshape(3, 1).clone(), host[r, 3:12].reshape(3, 3).clone(), host[r, 12].clone()] for r in range(R)]
+    if R > ops._lib.GD_MAX_ROOMS:
+        return _over_room_groups(_room_cap_groups(R), part)
+    return _refine_groups(lambda tr, ro: _rooms_chain(img, rooms, tr, ro, cfg, batch_mode), input_trans_list, input_rot_list)
 
 
 # One chain for several images pays where a one-image chain is bound by launch latency (tools/room_images_bench.py, DESIGN.md §4.6d, ms per
@@ -554,61 +564,8 @@ def depth_shared_chain_pays(nimages, per_image):
 
 
 def _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode):
-    """One launch chain over I images x at most PCL_GD_MAX_ROOMS rooms (ops.GradientDescentRoomsImages) -> the engine.  `rooms`: (xyz, rgb)
-    pairs whose rgb is one tensor in every room or a list of I tensors in every room; tr / ro: nrooms * I * per_image rows, room by room and
-    image by image inside a room.  Set up like _rooms_chain: one texel format for the chain (the largest room's; float4 when the images do
-    not agree), graph replay under _refine's rule on the chain's points x candidates, and a cached engine with private copies of the packed
-    clouds and boxes into which the colours of a later group of images are copied.  cfg.depth_mask: the depth chain, eager (_rooms_chain)."""
-    I = len(imgs)
-    per_image_sets = isinstance(rooms[0][1], list)
-    clouds = [packed_cloud_sets(xyz, rgb) if per_image_sets else packed_cloud(xyz, rgb) for xyz, rgb in rooms]
-    boxes = [quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05)) for xyz, _ in rooms]
-    B = int(tr.shape[0])
-    per_room = B // len(rooms)
-    nmax = max(int(xyz.shape[0]) for xyz, _ in rooms)
-    panos = [packed_pano(im, n_points=nmax) for im in imgs]
-    if len({p.fmt for p in panos}) > 1:          # a launch needs ONE texel format: float4 holds any image
-        panos = [ops.Pano(im, fmt="f32") for im in imgs]
-    num_iter = _cfg(cfg, "num_iter", 100)
-    hyper = (float(_cfg(cfg, "lr", 0.1)), int(_cfg(cfg, "patience", 5)), float(_cfg(cfg, "factor", 0.9)), bool(batch_mode))
-    fuse = None if _cfg(cfg, "gd_fuse", True) else False
-    use_graph = _cfg(cfg, "gd_graph", None)
-    if use_graph is None and ops.EXPERIMENT.gd_graph is not None:                   # experiments
-        use_graph = bool(ops.EXPERIMENT.gd_graph)
-    if use_graph is None:
-        use_graph = sum(c.n for c in clouds) * per_room <= GRAPH_POINT_POSES
-    depth = _depth_engine_args(cfg)
-    use_graph = bool(use_graph) and not depth["depth_mask"]
-
-    def make(cs, bs):
-        return ops.GradientDescentRoomsImages(list(zip(cs, bs)), panos, tr, ro, lr=hyper[0], patience=hyper[1], factor=hyper[2],
-                                              batch_mode=hyper[3], fuse=fuse, **depth)
-    if not use_graph:
-        gd = make(clouds, boxes)
-        gd.run(num_iter)
-        return gd
-
-    def make_private():
-        g = make([ops.Cloud.private_copy(c) for c in clouds], [ops._dev(b).reshape(6).clone() for b in boxes])
-        g._cloud_src = [weakref.ref(c) for c in clouds]
-        g._box_src, g._fresh = list(boxes), True
-        return g
-    xyzs = tuple(xyz for xyz, _ in rooms)
-    p0 = panos[0]
-    gd = _cached("gd_rooms_images", xyzs, make_private, sub=(I, per_room, p0.H, p0.W, p0.fmt, fuse, clouds[0].color_sets) + hyper)
-    fresh, gd._fresh = gd._fresh, False
-    for r, c in enumerate(clouds):
-        if gd._cloud_src[r]() is not c:                # (the colours change with every group of query images)
-            gd.clouds[r].data.copy_(c.data)
-            gd._cloud_src[r] = weakref.ref(c)
-        if gd._box_src[r] is not boxes[r]:
-            gd.boxes[r].copy_(ops._dev(boxes[r]).reshape(6))
-            gd._box_src[r] = boxes[r]
-    if not fresh:
-        gd.reset(tr, ro)
-        gd.set_panos(panos)                            # the pose records name these images' panoramas
-    gd.run_graph(num_iter)
-    return gd
+    """_chain of SEVERAL images: rgb one tensor in every room (the images share the room's colours) or a list of one per image in every room"""
+    return _chain("gd_rooms_images", imgs, rooms, tr, ro, cfg, batch_mode)
 
 
 def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_summaries=None, batch_mode=True):
@@ -641,14 +598,12 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
         if isinstance(rgb, list) and len(rgb) != I:
             raise ValueError("omniloc_batch_rooms_images: %d colour sets for %d images" % (len(rgb), I))
     groups = depth_tau_groups([int(xyz.shape[0]) for xyz, _ in rooms], int(imgs[0].shape[0]), int(imgs[0].shape[1]), cfg)
+
+    def part(idx):
+        return omniloc_batch_rooms_images(imgs, [rooms[r] for r in idx], [input_trans[r] for r in idx], [input_rot[r] for r in idx], cfg,
+                                          scalar_summaries, batch_mode)
     if len(groups) > 1:
-        out = [None] * R
-        for idx in groups:
-            part = omniloc_batch_rooms_images(imgs, [rooms[r] for r in idx], [input_trans[r] for r in idx], [input_rot[r] for r in idx], cfg,
-                                              scalar_summaries, batch_mode)
-            for r, o in zip(idx, part):
-                out[r] = o
-        return out
+        return _over_room_groups(groups, part)
     if (bool(_cfg(cfg, "depth_mask", False)) and I > 1 and not any(isinstance(rgb, list) for _, rgb in rooms)
             and not depth_shared_chain_pays(I, B)):
         return [omniloc_batch_images(imgs, xyz, rgb, input_trans[r], input_rot[r], cfg, scalar_summaries, batch_mode)
@@ -665,13 +620,8 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
         one = omniloc_batch_rooms(imgs[0], [(xyz, rgb[0] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms], [t[0] for t in input_trans],
                                   [r[0] for r in input_rot], cfg, scalar_summaries, batch_mode)
         return [[o] for o in one]
-    cap = ops._lib.GD_MAX_ROOMS
-    if R > cap:
-        out = []
-        for r0 in range(0, R, cap):
-            out += omniloc_batch_rooms_images(imgs, rooms[r0:r0 + cap], input_trans[r0:r0 + cap], input_rot[r0:r0 + cap], cfg, scalar_summaries,
-                                              batch_mode)
-        return out
+    if R > ops._lib.GD_MAX_ROOMS:
+        return _over_room_groups(_room_cap_groups(R), part)
     if any(isinstance(rgb, list) for _, rgb in rooms):
         # one kind of cloud per chain: a room whose images share its colours holds them I times
         rooms = [(xyz, rgb if isinstance(rgb, list) else [rgb] * I) for xyz, rgb in rooms]
@@ -679,25 +629,15 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
         if len(sizes) > 1:
             out, i0 = [[] for _ in range(R)], 0
             for m in sizes:
-                part = omniloc_batch_rooms_images(imgs[i0:i0 + m], [(xyz, rgb[i0:i0 + m]) for xyz, rgb in rooms], [t[i0:i0 + m] for t in input_trans],
+                some = omniloc_batch_rooms_images(imgs[i0:i0 + m], [(xyz, rgb[i0:i0 + m]) for xyz, rgb in rooms], [t[i0:i0 + m] for t in input_trans],
                                                   [r[i0:i0 + m] for r in input_rot], cfg, scalar_summaries, batch_mode)
                 for r in range(R):
-                    out[r] += part[r]
+                    out[r] += some[r]
                 i0 += m
             return out
-    tr = torch.cat([ops._dev(t).reshape(B, 3) for ts in input_trans for t in ts])
-    ro = torch.cat([ops._dev(r).reshape(B, 3) for rs in input_rot for r in rs])
-    gd = _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode)
-    leaf_t, leaf_r = torch.empty(R * I * B, 3, dtype=torch.float32, device=tr.device), torch.empty(R * I * B, 3, dtype=torch.float32, device=tr.device)
-    host = gd.winner(leaf_t, leaf_r).cpu()
-    with torch.no_grad():
-        for r in range(R):
-            for i in range(I):
-                k = r * I + i
-                input_trans[r][i].copy_(leaf_t[k * B:(k + 1) * B].reshape(input_trans[r][i].shape).to(input_trans[r][i].device))
-                input_rot[r][i].copy_(leaf_r[k * B:(k + 1) * B].reshape(input_rot[r][i].shape).to(input_rot[r][i].device))
-    return [[[host[r * I + i, 0:3].reshape(3, 1).clone(), host[r * I + i, 3:12].reshape(3, 3).clone(), host[r * I + i, 12].clone()] for i in range(I)]
-            for r in range(R)]
+    flat = _refine_groups(lambda tr, ro: _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode), [t for ts in input_trans for t in ts],
+                          [r for rs in input_rot for r in rs])
+    return [flat[r * I:(r + 1) * I] for r in range(R)]
 
 
 def sampling_loss(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, return_list=True):

@@ -736,65 +736,22 @@ def quantile_box(xyz, q):
     return box
 
 
-class GradientDescent:
-    """On-device GD refinement of B candidates (Adam + ReduceLROnPlateau + clamp), pcl_gd_* of the C ABI."""
+def _checked(name, *args):
+    """call the C entry point `name`, which returns an error code, and raise on failure"""
+    _lib.check(getattr(_lib.load(), name)(*args), name)
 
-    def __init__(self, cloud, pano, trans, rot, box, lr=0.1, patience=5, factor=0.9, batch_mode=True, depth_mask=False,
-                 depth_tau=None, depth_res=None, depth_stride=None, fuse=None):
-        """fuse None: pcl_gd_plan's rule (one launch per iteration for launches whose blocks are all resident); False: always the
-        two-launch form (bit-identical; tests and measurements)."""
-        lib = _lib.load()
-        self.cloud, self.pano = cloud, pano
-        trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-        self.B = int(trans.shape[0])
-        self.box = _dev(box).reshape(6)
-        dh, dw, tau, st = _depth_args(cloud.n, pano.H, pano.W, depth_res, depth_tau, depth_stride) if depth_mask else (0, 0, 0.0, 0)
-        self.hyper = _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL,
-                                  1 if depth_mask else 0, float(tau), int(dh), int(dw), int(st), -1 if fuse is False else 0, 0)
-        # a cloud of per-image colour sets (Cloud.with_color_sets): candidates [i * B / k, (i + 1) * B / k) read set i, and the chain runs
-        # the single-image plan (pcl_gd_hyper.color_sets)
-        self.hyper.color_sets = int(cloud.color_sets)
-        if cloud.color_sets > 1 and self.B % cloud.color_sets:
-            raise ValueError("GradientDescent: %d candidates over %d colour sets" % (self.B, cloud.color_sets))
-        # colour sets under the depth mask: the depth-chain family with this cloud as its one room (pcl_gd_run_depth_chain)
-        self._depth_sets = bool(depth_mask) and cloud.color_sets > 1
-        self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
-        if self._depth_sets:
-            self.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(self._one_room(), 1, cloud.color_sets, self.B // cloud.color_sets, pano.H, pano.W,
-                                                                   ctypes.byref(self.hyper))
-        else:
-            self.ws_bytes = lib.pcl_gd_workspace_bytes(cloud.n, self.B, pano.H, pano.W, ctypes.byref(self.hyper))
-        if self.ws_bytes == 0:
-            raise _lib.PiccoloHipError("pcl_gd_workspace_bytes: invalid arguments (depth grid %dx%d?)" % (dh, dw))
-        self.ws = _bytes(self.ws_bytes)
-        self._init(trans, rot)
 
-    def _one_room(self):
-        return (_lib.GdRoom * 1)(_lib.GdRoom(self.cloud.data.data_ptr(), self.cloud.n, self.box.data_ptr()))
+def _gd_hyper(lr, patience, factor, batch_mode, fuse, depth=None, color_sets=0):
+    """The hyper-parameter struct of every GD engine.  depth: None, or the mask's (depth_h, depth_w, tau, occluder stride); fuse False: always
+    the two-launch form."""
+    dh, dw, tau, st = depth or (0, 0, 0.0, 0)
+    return _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL, 1 if depth else 0, float(tau),
+                        int(dh), int(dw), int(st), -1 if fuse is False else 0, 0, int(color_sets))
 
-    def _init(self, trans, rot):
-        lib = _lib.load()
-        if self._depth_sets:
-            k = self.cloud.color_sets
-            _lib.check(lib.pcl_gd_init_rooms_images(_ptr(self.state), _ptr(trans), _ptr(rot), 1, k, self.B // k, ctypes.byref(self.hyper), _stream()),
-                       "pcl_gd_init_rooms_images")
-        else:
-            _lib.check(lib.pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
 
-    def run(self, num_iter, history=False, timer=None):
-        lib = _lib.load()
-        hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
-        if self._depth_sets:
-            k = self.cloud.color_sets
-            _lib.check(lib.pcl_gd_run_depth_chain(self._one_room(), 1, k, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state),
-                                                  self.B // k, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
-                                                  timer.handle if timer else None, _stream()), "pcl_gd_run_depth_chain")
-            return hist
-        _lib.check(lib.pcl_gd_run(_ptr(self.cloud.data), self.cloud.n, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
-                                  _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper), int(num_iter),
-                                  _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None, _stream()),
-                   "pcl_gd_run")
-        return hist
+class _GdEngine:
+    """What the GD engines share: a state of self.B candidates (self.state), a run(num_iter) that neither allocates nor synchronises, and
+    self.pano, the panorama whose size and texel format every panorama of the chain has."""
 
     def run_graph(self, num_iter):
         """Same as run(num_iter) but the 2 * num_iter launches are captured into one hipGraph and replayed: the host
@@ -815,17 +772,95 @@ class GradientDescent:
             # capture does not execute: fall through to the first replay
         g.replay()
 
+    def _name_panos(self, panos):
+        """The pose records of candidates [i * B / I, (i + 1) * B / I) name panos[i] (I Pano objects of the size / texel format of self.pano):
+        nothing is copied to the device, the addresses are kernel arguments (pcl_gd_set_pano_groups)."""
+        I = len(panos)
+        if I <= 0 or self.B % I:
+            raise ValueError("set_pano_groups: %d candidates do not split into %d images" % (self.B, I))
+        for p in panos:
+            if (p.H, p.W, p.fmt) != (self.pano.H, self.pano.W, self.pano.fmt):
+                raise ValueError("all panoramas of a launch must share size and texel format")
+        self._panos = list(panos)                      # keep them alive
+        arr = (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos])
+        _lib.check(_lib.load().pcl_gd_set_pano_groups(_ptr(self.state), arr, I, self.B // I, _stream()), "pcl_gd_set_pano_groups")
+
+    def winners(self, groups, leaf_trans=None, leaf_rot=None):
+        """(groups, 16) GPU tensor, per group of B / groups candidates the one omniloc_batch returns (omniloc.py:271-277):
+        post-step t (3), R (9), last loss, yaw / pitch / roll.  leaf_trans / leaf_rot: contiguous float32 GPU tensors of B x 3
+        that receive every candidate's leaf parameters (the reference optimises the caller's rows in place)."""
+        if groups <= 0 or self.B % groups:
+            raise ValueError("winner: %d candidates do not split into %d images" % (self.B, groups))
+        out = torch.empty(groups, 16, dtype=F32, device=self.state.device)
+        for t in (leaf_trans, leaf_rot):
+            if t is not None and not (t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == 3 * self.B):
+                raise ValueError("winner: leaf buffers must be contiguous float32 GPU tensors of B x 3")
+        _lib.check(_lib.load().pcl_gd_winner(_ptr(self.state), groups, self.B // groups, _ptr(out), _ptr(leaf_trans), _ptr(leaf_rot), _stream()),
+                   "pcl_gd_winner")
+        return out
+
+    def result(self):
+        """(B, 16): fwd t(3), fwd ypr(3), leaf t(3), leaf ypr(3), last loss, lr, scheduler num_bad_epochs, scheduler best."""
+        out = torch.empty(self.B, _lib.GD_RESULT_STRIDE, dtype=F32, device=self.state.device)
+        _lib.check(_lib.load().pcl_gd_result(_ptr(self.state), self.B, _ptr(out), _stream()), "pcl_gd_result")
+        return out
+
+
+class GradientDescent(_GdEngine):
+    """On-device GD refinement of B candidates (Adam + ReduceLROnPlateau + clamp), pcl_gd_* of the C ABI."""
+
+    def __init__(self, cloud, pano, trans, rot, box, lr=0.1, patience=5, factor=0.9, batch_mode=True, depth_mask=False,
+                 depth_tau=None, depth_res=None, depth_stride=None, fuse=None):
+        """fuse None: pcl_gd_plan's rule (one launch per iteration for launches whose blocks are all resident); False: always the
+        two-launch form (bit-identical; tests and measurements)."""
+        lib = _lib.load()
+        self.cloud, self.pano = cloud, pano
+        trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+        self.B = int(trans.shape[0])
+        self.box = _dev(box).reshape(6)
+        if cloud.color_sets > 1 and self.B % cloud.color_sets:
+            raise ValueError("GradientDescent: %d candidates over %d colour sets" % (self.B, cloud.color_sets))
+        # colour sets under the depth mask: the depth-chain family with this cloud as its one room and a set per image; the engine's state,
+        # workspace and hyper-parameters are this object's (the pose records name no panorama until set_pano_groups)
+        self._chain = None
+        if depth_mask and cloud.color_sets > 1:
+            self._chain = GradientDescentRoomsImages([(cloud, self.box)], [pano] * cloud.color_sets, trans, rot, lr, patience, factor, batch_mode, fuse,
+                                                     True, depth_tau, depth_res, depth_stride, name_panos=False)
+            self.hyper, self.state, self.ws, self.ws_bytes = self._chain.hyper, self._chain.state, self._chain.ws, self._chain.ws_bytes
+            return
+        # a cloud of per-image colour sets (Cloud.with_color_sets): candidates [i * B / k, (i + 1) * B / k) read set i, and the chain runs
+        # the single-image plan (pcl_gd_hyper.color_sets)
+        self.hyper = _gd_hyper(lr, patience, factor, batch_mode, fuse, _depth_args(cloud.n, pano.H, pano.W, depth_res, depth_tau, depth_stride)
+                               if depth_mask else None, cloud.color_sets)
+        self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
+        self.ws_bytes = lib.pcl_gd_workspace_bytes(cloud.n, self.B, pano.H, pano.W, ctypes.byref(self.hyper))
+        if self.ws_bytes == 0:
+            raise _lib.PiccoloHipError("pcl_gd_workspace_bytes: invalid arguments (depth grid %dx%d?)" % (self.hyper.depth_h, self.hyper.depth_w))
+        self.ws = _bytes(self.ws_bytes)
+        self.reset(trans, rot)
+
+    def run(self, num_iter, history=False, timer=None):
+        if self._chain is not None:
+            return self._chain.run(num_iter, history, timer)
+        hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
+        _lib.check(_lib.load().pcl_gd_run(_ptr(self.cloud.data), self.cloud.n, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
+                                          _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper), int(num_iter),
+                                          _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None, _stream()),
+                   "pcl_gd_run")
+        return hist
+
     def reset(self, trans, rot):
         """Re-initialise the optimiser state for new starting poses (same cloud / panorama / B): lets one captured
         graph serve many refinements."""
+        if self._chain is not None:
+            return self._chain.reset(trans, rot)
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         assert trans.shape[0] == self.B
-        self._init(trans, rot)
+        _lib.check(_lib.load().pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
 
     def set_panos(self, panos):
         """Candidate b samples panos[b] (a list of B Pano objects, all the size / texel format of self.pano): lets the
         candidates of several query images share one launch chain.  Call after __init__ / reset()."""
-        lib = _lib.load()
         assert len(panos) == self.B
         for p in panos:
             if (p.H, p.W, p.fmt) != (self.pano.H, self.pano.W, self.pano.fmt):
@@ -846,32 +881,12 @@ class GradientDescent:
     def set_pano_groups(self, panos):
         """Candidates [i * B / I, (i + 1) * B / I) sample panos[i] (I Pano objects of the size / texel format of self.pano, B
         divisible by I).  Unlike set_panos / set_pano_table nothing is copied to the device: the addresses are kernel arguments."""
-        lib = _lib.load()
-        I = len(panos)
-        if I <= 0 or self.B % I:
-            raise ValueError("set_pano_groups: %d candidates do not split into %d images" % (self.B, I))
-        for p in panos:
-            if (p.H, p.W, p.fmt) != (self.pano.H, self.pano.W, self.pano.fmt):
-                raise ValueError("all panoramas of a launch must share size and texel format")
-        self._panos = list(panos)                      # keep them alive
-        self.hyper.images = I                          # (mapping hint for pcl_gd_run: the XCDs split the images)
-        arr = (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos])
-        _lib.check(lib.pcl_gd_set_pano_groups(_ptr(self.state), arr, I, self.B // I, _stream()), "pcl_gd_set_pano_groups")
+        self._name_panos(panos)
+        self.hyper.images = len(panos)                 # (mapping hint for pcl_gd_run: the XCDs split the images)
 
     def winner(self, nimages=1, leaf_trans=None, leaf_rot=None):
-        """(nimages, 16) GPU tensor, per image of B / nimages candidates the one omniloc_batch returns (omniloc.py:271-277):
-        post-step t (3), R (9), last loss, yaw / pitch / roll.  leaf_trans / leaf_rot: contiguous float32 GPU tensors of B x 3
-        that receive every candidate's leaf parameters (the reference optimises the caller's rows in place)."""
-        lib = _lib.load()
-        if nimages <= 0 or self.B % nimages:
-            raise ValueError("winner: %d candidates do not split into %d images" % (self.B, nimages))
-        out = torch.empty(nimages, 16, dtype=F32, device=self.state.device)
-        for t in (leaf_trans, leaf_rot):
-            if t is not None and not (t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == 3 * self.B):
-                raise ValueError("winner: leaf buffers must be contiguous float32 GPU tensors of B x 3")
-        _lib.check(lib.pcl_gd_winner(_ptr(self.state), nimages, self.B // nimages, _ptr(out), _ptr(leaf_trans), _ptr(leaf_rot), _stream()),
-                   "pcl_gd_winner")
-        return out
+        """(nimages, 16) GPU tensor: per image of B / nimages candidates the one omniloc_batch returns (_GdEngine.winners)."""
+        return self.winners(nimages, leaf_trans, leaf_rot)
 
     def step_from_grads(self, loss, grad):
         """Teacher-forcing hook (tests): ONE optimiser step of every candidate from a GIVEN loss (B,) and gradient (B, 6) =
@@ -881,102 +896,8 @@ class GradientDescent:
         _lib.check(_lib.load().pcl_gd_step_from_grads(_ptr(self.state), self.B, _ptr(loss), _ptr(grad), _ptr(self.box), ctypes.byref(self.hyper),
                                                       _ptr(scratch), _stream()), "pcl_gd_step_from_grads")
 
-    def result(self):
-        """(B, 16): fwd t(3), fwd ypr(3), leaf t(3), leaf ypr(3), last loss, lr, scheduler num_bad_epochs, scheduler best."""
-        lib = _lib.load()
-        out = torch.empty(self.B, _lib.GD_RESULT_STRIDE, dtype=F32, device=self.state.device)
-        _lib.check(lib.pcl_gd_result(_ptr(self.state), self.B, _ptr(out), _stream()), "pcl_gd_result")
-        return out
 
-
-def _plan_depth_chain(rooms, nrooms, nimages, per_image, pano, hyper):
-    """-> (nchunks per room, poses per block, False, [(depth_h, depth_w, occluder stride) per room]): pcl_gd_plan_depth_chain"""
-    arr = lambda: (ctypes.c_int * nrooms)()      # noqa: E731
-    nch, dh, dw, st, G = arr(), arr(), arr(), arr(), ctypes.c_int(0)
-    _lib.check(_lib.load().pcl_gd_plan_depth_chain(rooms, nrooms, nimages, per_image, pano.H, pano.W, ctypes.byref(hyper), nch, ctypes.byref(G), dh, dw,
-                                                   st), "pcl_gd_plan_depth_chain")
-    return list(nch), G.value, False, list(zip(dh, dw, st))
-
-
-class GradientDescentRooms:
-    """On-device GD refinement of ONE panorama against several rooms in one launch chain (pcl_gd_run_rooms): `rooms` is a list of
-    (Cloud, box) pairs, `trans` / `rot` hold nrooms * per_room rows, room r's candidates the rows [r * per_room, (r + 1) * per_room).
-    Every room's results equal those of a GradientDescent over that room alone, bit for bit.  At most PCL_GD_MAX_ROOMS rooms."""
-
-    def __init__(self, rooms, pano, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None, depth_mask=False, depth_tau=None,
-                 depth_res=None, depth_stride=None):
-        """depth_mask: the scatter-min depth mask in the chain (pcl_gd_run_depth_chain, nimages = 1): every room on its own grid, as
-        GradientDescent(depth_mask=True) of that room resolves it; depth_res applies to every room."""
-        lib = _lib.load()
-        if not 1 <= len(rooms) <= _lib.GD_MAX_ROOMS:
-            raise ValueError("GradientDescentRooms: %d rooms (1..%d per chain)" % (len(rooms), _lib.GD_MAX_ROOMS))
-        self.pano = pano
-        self.clouds = [c for c, _ in rooms]
-        for c in self.clouds:
-            if c.color_sets > 1:
-                raise ValueError("GradientDescentRooms: a room cloud with colour sets")
-        self.boxes = [_dev(b).reshape(6) for _, b in rooms]
-        trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-        self.nrooms = len(rooms)
-        self.B = int(trans.shape[0])
-        if self.B % self.nrooms or self.B == 0:
-            raise ValueError("GradientDescentRooms: %d candidates do not split into %d rooms" % (self.B, self.nrooms))
-        self.per_room = self.B // self.nrooms
-        self.depth_mask = bool(depth_mask)
-        dh, dw, tau, st = (_chain_depth_args([c.n for c in self.clouds], pano.H, pano.W, depth_res, depth_tau, depth_stride) if depth_mask
-                           else (0, 0, 0.0, 0))
-        self.hyper = _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL,
-                                  1 if depth_mask else 0, float(tau), int(dh), int(dw), int(st), -1 if fuse is False else 0, 0, 0)
-        self._rooms = (_lib.GdRoom * self.nrooms)(*[_lib.GdRoom(c.data.data_ptr(), c.n, b.data_ptr()) for c, b in zip(self.clouds, self.boxes)])
-        self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
-        if depth_mask:
-            self.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(self._rooms, self.nrooms, 1, self.per_room, pano.H, pano.W, ctypes.byref(self.hyper))
-        else:
-            self.ws_bytes = lib.pcl_gd_rooms_workspace_bytes(self._rooms, self.nrooms, self.per_room, ctypes.byref(self.hyper))
-        if self.ws_bytes == 0:
-            raise _lib.PiccoloHipError("pcl_gd_%s_workspace_bytes: invalid arguments" % ("depth_chain" if depth_mask else "rooms"))
-        self.ws = _bytes(self.ws_bytes)
-        self.reset(trans, rot)
-
-    def plan(self):
-        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms; with the depth mask (never fused) a fourth item, per room
-        (depth_h, depth_w, occluder stride): pcl_gd_plan_depth_chain"""
-        if self.depth_mask:
-            return _plan_depth_chain(self._rooms, self.nrooms, 1, self.per_room, self.pano, self.hyper)
-        nch, G, fused = (ctypes.c_int * self.nrooms)(), ctypes.c_int(0), ctypes.c_int(0)
-        _lib.check(_lib.load().pcl_gd_plan_rooms(self._rooms, self.nrooms, self.per_room, ctypes.byref(self.hyper), nch, ctypes.byref(G),
-                                                 ctypes.byref(fused)), "pcl_gd_plan_rooms")
-        return list(nch), G.value, bool(fused.value)
-
-    def run(self, num_iter, history=False, timer=None):
-        lib = _lib.load()
-        hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
-        if self.depth_mask:
-            _lib.check(lib.pcl_gd_run_depth_chain(self._rooms, self.nrooms, 1, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
-                                                  _ptr(self.state), self.per_room, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws),
-                                                  self.ws_bytes, timer.handle if timer else None, _stream()), "pcl_gd_run_depth_chain")
-            return hist
-        _lib.check(lib.pcl_gd_run_rooms(self._rooms, self.nrooms, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state),
-                                        self.per_room, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
-                                        timer.handle if timer else None, _stream()), "pcl_gd_run_rooms")
-        return hist
-
-    run_graph = GradientDescent.run_graph          # capture run(num_iter) once per num_iter, replay it
-
-    def reset(self, trans, rot):
-        """New starting poses for the same rooms / panorama / shape (lets one captured graph serve many refinements)."""
-        trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-        assert trans.shape[0] == self.B
-        _lib.check(_lib.load().pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
-
-    def winner(self, leaf_trans=None, leaf_rot=None):
-        """(nrooms, 16): per room the candidate omniloc_batch returns (see GradientDescent.winner)."""
-        return GradientDescent.winner(self, self.nrooms, leaf_trans, leaf_rot)
-
-    result = GradientDescent.result
-
-
-class GradientDescentRoomsImages:
+class GradientDescentRoomsImages(_GdEngine):
     """On-device GD refinement of SEVERAL panoramas against several rooms in one launch chain (pcl_gd_run_rooms_images): `rooms` is a list
     of (Cloud, box) pairs, `panos` a list of I Pano objects of one size and texel format, `trans` / `rot` hold nrooms * I * per_image rows
     and candidate (r, i, j) is row (r * I + i) * per_image + j.  Every room cloud holds one colour set (the images share the room's colours)
@@ -984,94 +905,96 @@ class GradientDescentRoomsImages:
     GradientDescent over that room and image alone, bit for bit.  At most PCL_GD_MAX_ROOMS rooms."""
 
     def __init__(self, rooms, panos, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None, depth_mask=False, depth_tau=None,
-                 depth_res=None, depth_stride=None):
-        """depth_mask: as for GradientDescentRooms (pcl_gd_run_depth_chain)."""
-        lib = _lib.load()
+                 depth_res=None, depth_stride=None, name_panos=True):
+        """depth_mask: the scatter-min depth mask in the chain (pcl_gd_run_depth_chain): every room on its own grid, as
+        GradientDescent(depth_mask=True) of that room resolves it; depth_res applies to every room.  name_panos False: the pose records name
+        no panorama and every candidate samples panos[0], the kernel argument, until set_panos."""
+        lib, name = _lib.load(), type(self).__name__
         if not 1 <= len(rooms) <= _lib.GD_MAX_ROOMS:
-            raise ValueError("GradientDescentRoomsImages: %d rooms (1..%d per chain)" % (len(rooms), _lib.GD_MAX_ROOMS))
+            raise ValueError("%s: %d rooms (1..%d per chain)" % (name, len(rooms), _lib.GD_MAX_ROOMS))
         if len(panos) < 1:
-            raise ValueError("GradientDescentRoomsImages: no panorama")
+            raise ValueError("%s: no panorama" % name)
         self.pano = panos[0]
         self.clouds = [c for c, _ in rooms]
         self.nrooms, self.nimages = len(rooms), len(panos)
         sets = {int(c.color_sets) for c in self.clouds}
         if len(sets) != 1 or sets.pop() not in (1, self.nimages):
-            raise ValueError("GradientDescentRoomsImages: every room cloud needs one colour set, or one per image (%d)" % self.nimages)
+            raise ValueError("%s: every room cloud needs one colour set, or one per image (%d)" % (name, self.nimages))
         self.color_sets = int(self.clouds[0].color_sets)
         self.boxes = [_dev(b).reshape(6) for _, b in rooms]
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         self.B = int(trans.shape[0])
         if self.B % (self.nrooms * self.nimages) or self.B == 0:
-            raise ValueError("GradientDescentRoomsImages: %d candidates do not split into %d rooms x %d images" % (self.B, self.nrooms, self.nimages))
-        self.per_image = self.B // (self.nrooms * self.nimages)
+            raise ValueError("%s: %d candidates do not split into %d rooms x %d images" % (name, self.B, self.nrooms, self.nimages))
+        self.per_room = self.B // self.nrooms
+        self.per_image = self.per_room // self.nimages
         self.depth_mask = bool(depth_mask)
-        dh, dw, tau, st = (_chain_depth_args([c.n for c in self.clouds], self.pano.H, self.pano.W, depth_res, depth_tau, depth_stride) if depth_mask
-                           else (0, 0, 0.0, 0))
-        self.hyper = _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL,
-                                  1 if depth_mask else 0, float(tau), int(dh), int(dw), int(st), -1 if fuse is False else 0, 0,
-                                  self.color_sets if self.color_sets > 1 else 0)
+        self.hyper = _gd_hyper(lr, patience, factor, batch_mode, fuse,
+                               _chain_depth_args([c.n for c in self.clouds], self.pano.H, self.pano.W, depth_res, depth_tau, depth_stride)
+                               if depth_mask else None, self.color_sets if self.color_sets > 1 else 0)
         self._rooms = (_lib.GdRoom * self.nrooms)(*[_lib.GdRoom(c.data.data_ptr(), c.n, b.data_ptr()) for c, b in zip(self.clouds, self.boxes)])
+        self._shape = (self._rooms, self.nrooms, self.nimages, self.per_image)        # (how every pcl_gd_*rooms_images / *depth_chain call begins)
         self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
         if depth_mask:
-            self.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(self._rooms, self.nrooms, self.nimages, self.per_image, self.pano.H, self.pano.W,
-                                                                   ctypes.byref(self.hyper))
+            self.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(*self._shape, self.pano.H, self.pano.W, ctypes.byref(self.hyper))
         else:
-            self.ws_bytes = lib.pcl_gd_rooms_images_workspace_bytes(self._rooms, self.nrooms, self.nimages, self.per_image, ctypes.byref(self.hyper))
+            self.ws_bytes = lib.pcl_gd_rooms_images_workspace_bytes(*self._shape, ctypes.byref(self.hyper))
         if self.ws_bytes == 0:
             raise _lib.PiccoloHipError("pcl_gd_%s_workspace_bytes: invalid arguments" % ("depth_chain" if depth_mask else "rooms_images"))
         self.ws = _bytes(self.ws_bytes)
         self.reset(trans, rot)
-        self.set_panos(panos)
+        if name_panos:
+            self.set_panos(panos)
 
     def plan(self):
-        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms_images; with the depth mask a fourth item, the per-room grids
-        (GradientDescentRooms.plan)"""
+        """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms_images; with the depth mask (never fused) a fourth item, per room
+        (depth_h, depth_w, occluder stride): pcl_gd_plan_depth_chain"""
+        arr = lambda: (ctypes.c_int * self.nrooms)()      # noqa: E731
+        nch, G = arr(), ctypes.c_int(0)
         if self.depth_mask:
-            return _plan_depth_chain(self._rooms, self.nrooms, self.nimages, self.per_image, self.pano, self.hyper)
-        nch, G, fused = (ctypes.c_int * self.nrooms)(), ctypes.c_int(0), ctypes.c_int(0)
-        _lib.check(_lib.load().pcl_gd_plan_rooms_images(self._rooms, self.nrooms, self.nimages, self.per_image, ctypes.byref(self.hyper), nch,
-                                                        ctypes.byref(G), ctypes.byref(fused)), "pcl_gd_plan_rooms_images")
+            dh, dw, st = arr(), arr(), arr()
+            _checked("pcl_gd_plan_depth_chain", *self._shape, self.pano.H, self.pano.W, ctypes.byref(self.hyper), nch, ctypes.byref(G), dh, dw, st)
+            return list(nch), G.value, False, list(zip(dh, dw, st))
+        fused = ctypes.c_int(0)
+        _checked("pcl_gd_plan_rooms_images", *self._shape, ctypes.byref(self.hyper), nch, ctypes.byref(G), ctypes.byref(fused))
         return list(nch), G.value, bool(fused.value)
 
     def reset(self, trans, rot):
-        """New starting poses for the same rooms / shape (the pose records then name no panorama: call set_panos)."""
+        """New starting poses for the same rooms / shape, which lets one captured graph serve many refinements (the pose records then name no
+        panorama: call set_panos)."""
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         assert trans.shape[0] == self.B
-        _lib.check(_lib.load().pcl_gd_init_rooms_images(_ptr(self.state), _ptr(trans), _ptr(rot), self.nrooms, self.nimages, self.per_image,
-                                                        ctypes.byref(self.hyper), _stream()), "pcl_gd_init_rooms_images")
+        _checked("pcl_gd_init_rooms_images", _ptr(self.state), _ptr(trans), _ptr(rot), self.nrooms, self.nimages, self.per_image,
+                 ctypes.byref(self.hyper), _stream())
 
     def set_panos(self, panos):
         """Image i's candidates in every room sample panos[i] (addresses as kernel arguments: no copy to the device)."""
         if len(panos) != self.nimages:
-            raise ValueError("GradientDescentRoomsImages: %d panoramas for %d images" % (len(panos), self.nimages))
-        for p in panos:
-            if (p.H, p.W, p.fmt) != (self.pano.H, self.pano.W, self.pano.fmt):
-                raise ValueError("all panoramas of a launch must share size and texel format")
-        self._panos = list(panos)                      # keep them alive
-        n = self.nrooms * self.nimages
-        arr = (ctypes.c_uint64 * n)(*([p.data.data_ptr() for p in panos] * self.nrooms))
-        _lib.check(_lib.load().pcl_gd_set_pano_groups(_ptr(self.state), arr, n, self.per_image, _stream()), "pcl_gd_set_pano_groups")
+            raise ValueError("%s: %d panoramas for %d images" % (type(self).__name__, len(panos), self.nimages))
+        self._name_panos(list(panos) * self.nrooms)
 
     def run(self, num_iter, history=False, timer=None):
-        lib = _lib.load()
         hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
-        if self.depth_mask:
-            _lib.check(lib.pcl_gd_run_depth_chain(self._rooms, self.nrooms, self.nimages, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
-                                                  _ptr(self.state), self.per_image, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws),
-                                                  self.ws_bytes, timer.handle if timer else None, _stream()), "pcl_gd_run_depth_chain")
-            return hist
-        _lib.check(lib.pcl_gd_run_rooms_images(self._rooms, self.nrooms, self.nimages, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
-                                               _ptr(self.state), self.per_image, ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws),
-                                               self.ws_bytes, timer.handle if timer else None, _stream()), "pcl_gd_run_rooms_images")
+        _checked("pcl_gd_run_depth_chain" if self.depth_mask else "pcl_gd_run_rooms_images", self._rooms, self.nrooms, self.nimages,
+                 _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state), self.per_image, ctypes.byref(self.hyper), int(num_iter),
+                 _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None, _stream())
         return hist
 
-    run_graph = GradientDescent.run_graph          # capture run(num_iter) once per num_iter, replay it
-
     def winner(self, leaf_trans=None, leaf_rot=None):
-        """(nrooms * nimages, 16): per (room, image), room by room, the candidate omniloc_batch returns (see GradientDescent.winner)."""
-        return GradientDescent.winner(self, self.nrooms * self.nimages, leaf_trans, leaf_rot)
+        """(nrooms * nimages, 16): per (room, image), room by room, the candidate omniloc_batch returns (_GdEngine.winners)."""
+        return self.winners(self.nrooms * self.nimages, leaf_trans, leaf_rot)
 
-    result = GradientDescent.result
+
+class GradientDescentRooms(GradientDescentRoomsImages):
+    """On-device GD refinement of ONE panorama against several rooms in one launch chain: the engine's one-image case (the C side forwards
+    nimages = 1 to pcl_gd_run_rooms).  `rooms` is a list of (Cloud, box) pairs without colour sets, `trans` / `rot` hold nrooms * per_room
+    rows, room r's candidates the rows [r * per_room, (r + 1) * per_room).  Takes the engine's further arguments; the eager chain samples the
+    kernel-argument panorama, so the pose records name none until set_panos."""
+
+    def __init__(self, rooms, pano, trans, rot, *args, **kwargs):
+        if any(c.color_sets > 1 for c, _ in rooms):
+            raise ValueError("GradientDescentRooms: a room cloud with colour sets")
+        super().__init__(rooms, [pano], trans, rot, *args, name_panos=False, **kwargs)
 
 
 class KernelTimer:

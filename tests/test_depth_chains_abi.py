@@ -171,6 +171,27 @@ def test_rooms_share_a_depth_chain_when_their_tolerances_agree(lib):
     assert ops._chain_depth_args(small + large, 1024, 2048, (64, 128), None) == (64, 128, ops.depth_tau_rule(64), 1)
 
 
+def test_engine_arguments_from_cfg(lib):
+    """what omniloc hands every GD engine for a cfg, written out; and the tolerance groups that read the same values"""
+    from conftest import Cfg
+    from piccolo_amd import omniloc as po
+    assert po._engine_args(Cfg(), True) == dict(lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None, depth_mask=False, depth_tau=None,
+                                                depth_res=None, depth_stride=None)
+    assert po._engine_args(Cfg(lr=0.05, patience=3, factor=0.8, gd_fuse=True, depth_mask=True), False) == dict(
+        lr=0.05, patience=3, factor=0.8, batch_mode=False, fuse=None, depth_mask=True, depth_tau=None, depth_res=None, depth_stride=None)
+    got = po._engine_args(Cfg(lr=1, patience=7.0, factor=1, gd_fuse=False, depth_mask=1, depth_tau=1, depth_res=[64.0, 128.0], depth_stride=2.0), 1)
+    want = dict(lr=1.0, patience=7, factor=1.0, batch_mode=True, fuse=False, depth_mask=True, depth_tau=1.0, depth_res=(64, 128), depth_stride=2)
+    assert got == want and [type(v) for v in got.values()] == [type(v) for v in want.values()]
+    assert list(got) == ["lr", "patience", "factor", "batch_mode", "fuse", "depth_mask", "depth_tau", "depth_res", "depth_stride"]
+    # without the mask its optional values still travel (the engines ignore them), with gd_fuse alone nothing else moves
+    assert po._engine_args(Cfg(depth_tau=0.05, depth_res=(32, 64), depth_stride=4, gd_fuse=0)) == dict(
+        lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=False, depth_mask=False, depth_tau=0.05, depth_res=(32, 64), depth_stride=4)
+    points = [2_000, 160_000, 1_000_000]
+    assert po.depth_tau_groups(points, 256, 512, Cfg(depth_mask=True)) == [[0], [1], [2]]          # (every room its own default grid: 3 tolerances)
+    assert po.depth_tau_groups(points, 256, 512, Cfg(depth_mask=True, depth_tau=0.05)) == [[0, 1, 2]]
+    assert po.depth_tau_groups(points, 256, 512, Cfg(depth_tau=0.05)) == [[0, 1, 2]]
+
+
 def test_shared_colour_depth_chain_cut_off_sits_between_the_measured_wins_and_the_measured_loss():
     """with the depth mask and shared colours, one chain won at 2..7 images x 6 candidates per room and lost at 8 x 6"""
     from piccolo_amd import omniloc as po

@@ -28,12 +28,12 @@ def _rooms(sizes, seed=0):
     return [(torch.from_numpy(x).cuda(), torch.from_numpy(c).cuda()) for x, c in synth.rooms_side_by_side(sizes, seed)]
 
 
-def _query(rooms, r, seed):
+def _query(rooms, r, seed, res=(H, W)):
     """the panorama room r shows from room_gt_pose(r, seed) (its own cloud: the walls hide the other rooms)"""
     from piccolo_amd import ops, synth
     t, ypr = synth.room_gt_pose(r, seed)
     xyz, rgb = rooms[r]
-    img = synth.quantise_like_image_file(ops.make_pano(ops.transform_cloud(xyz, torch.from_numpy(t), torch.from_numpy(ypr)), rgb, (H, W)))
+    img = synth.quantise_like_image_file(ops.make_pano(ops.transform_cloud(xyz, torch.from_numpy(t), torch.from_numpy(ypr)), rgb, res))
     return img, t, ypr
 
 
@@ -105,6 +105,51 @@ def test_rooms_engine_history_equals_single_room_history(fuse):
         h1 = one.run(31, history=True)
         assert torch.equal(hist[:, 6 * r:6 * (r + 1)], h1), r
         assert torch.equal(res[6 * r:6 * (r + 1)], one.result()), r
+
+
+ENGINE_SIZES = (700, 5_000, 20_000)          # the smallest has fewer steps than chunks
+
+
+@pytest.mark.parametrize("fuse", [None, False])
+@pytest.mark.parametrize("per_room", [6, 5])
+def test_one_image_engine_is_the_rooms_images_engine_with_one_image(per_room, fuse):
+    """without the mask: GradientDescentRooms and GradientDescentRoomsImages over [pano] plan, size and compute the same, bit for bit; 6
+    candidates are two poses per block, 5 one pose per block (the two plan corners, with the room of fewer steps than chunks)"""
+    from piccolo_amd import ops
+    from piccolo_amd import omniloc as po
+    rooms = _rooms(ENGINE_SIZES, seed=4)
+    pano = ops.Pano(_query(rooms, 1, 2, res=(64, 128))[0], fmt="f16")
+    starts = _starts(len(rooms), per_room, seed=5)
+    pairs = list(zip([po.packed_cloud(x, c) for x, c in rooms], [ops.quantile_box(x, 0.05) for x, _ in rooms]))
+    tr = torch.cat([t for t, _ in starts])
+    ro = torch.cat([r for _, r in starts])
+    one = ops.GradientDescentRooms(pairs, pano, tr, ro, lr=0.1, patience=5, factor=0.8, fuse=fuse)
+    many = ops.GradientDescentRoomsImages(pairs, [pano], tr, ro, lr=0.1, patience=5, factor=0.8, fuse=fuse)
+    assert (one.nrooms, one.per_room) == (3, per_room)
+    assert one.plan() == many.plan() and one.plan()[1] == (2 if per_room == 6 else 1)
+    assert one.ws_bytes == many.ws_bytes
+    assert torch.equal(one.run(12, history=True), many.run(12, history=True))
+    assert torch.equal(one.result(), many.result())
+
+
+def test_cached_rooms_engine_takes_new_colours_on_the_same_points():
+    """the second call through the cached engine brings new rgb tensors on the same xyz (what color_mod gives every query image): they are
+    copied into the engine's private clouds, and the replayed chain equals a fresh eager one"""
+    from piccolo_amd import omniloc as po
+    rooms = _rooms(ENGINE_SIZES, seed=3)
+    img, _, _ = _query(rooms, 1, 5)
+    po._cache.clear()
+    for rs, seed in ((rooms, 3), ([(xyz, (rgb * 0.8 + 0.1).contiguous()) for xyz, rgb in rooms], 11)):
+        starts = _starts(len(rs), 6, seed=seed)
+        out = {}
+        for graph in (True, False):
+            tr, ro = [t.clone() for t, _ in starts], [r.clone() for _, r in starts]
+            out[graph] = (po.omniloc_batch_rooms(img, rs, tr, ro, _cfg(num_iter=10, gd_graph=graph)), tr, ro)
+        for r in range(len(rs)):
+            for k in range(3):
+                assert torch.equal(out[True][0][r][k], out[False][0][r][k]), (seed, r, k)
+            assert torch.equal(out[True][1][r], out[False][1][r]) and torch.equal(out[True][2][r], out[False][2][r]), (seed, r)
+    assert len(po._cache.kinds["gd_rooms"]) == 1           # one engine served both calls
 
 
 FUSED_SIZES = (700, 20_000, 60_000)          # 24 + 120 + 360 blocks at 6 candidates: the whole chain fits one launch per iteration
