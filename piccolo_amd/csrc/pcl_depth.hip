@@ -30,6 +30,7 @@
 //   mark     : only for the stand-alone pcl_depth_mask (a byte mask for callers of pcl_sampling_loss's `visible`).
 #include <stdlib.h>
 
+#include "pcl_host.h"
 #include "pcl_sample_device.h"
 
 struct PclZArgs {

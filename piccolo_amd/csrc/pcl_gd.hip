@@ -9,27 +9,10 @@
 #include <string.h>
 
 #include "pcl_gd_device.h"
+#include "pcl_host.h"
+#include "pcl_timer.h"
 
 #define PCL_GD_MAX_IMAGES 64     // panorama addresses per pcl_gd_set_pano_groups launch (they travel as kernel arguments)
-
-int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses,
-                    int B, bool grad, const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse,
-                    const PclDepthLook* depth, int color_sets = 1);
-// (sets > 1: the single-image plan of B / sets candidates for all B — pcl_plan_sets, pcl_loss.hip)
-size_t pcl_partials_bytes(int64_t n, int B, int sets = 1);
-int pcl_plan_nchunks(int64_t n, int B, int sets = 1);
-int pcl_plan_nblocks(int64_t n, int B, int sets = 1);
-int pcl_plan_G(int64_t n, int B, int sets = 1);
-void pcl_plan_room_images(int64_t n, int per_image, int nimages, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
-int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
-                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, int color_sets = 1);
-int pcl_launch_loss_rooms_depth(const PclRoomTable* rooms, const PclDepthTable* dtab, const void* pano, int pano_format, int H, int W,
-                                const PclPoseRec* poses, int B, int G, int ngroups, int nblk, float* partials, hipStream_t s, int flip, int color_sets,
-                                const uint32_t* zbuf, uint32_t* zclear, int64_t zclear_vec4);
-size_t pcl_depth_zbuf_bytes(int B, int Hd, int Wd);
-int pcl_launch_zbuffers(const float* cloud, int64_t n, const PclPoseRec* poses, int B, const PclDepthGrid& g, int zstride, uint32_t* zbuf, bool fill,
-                        hipStream_t s);
-extern "C" int pcl_depth_default(int64_t n, int H, int W, int stride_in, int* depth_h_host, int* depth_w_host, float* tau_host, int* stride_host);
 
 // ---------------------------------------------------------------- stateless loss: pose setup + finish
 
@@ -68,40 +51,6 @@ __global__ void __launch_bounds__(PCL_GD_THREADS) pcl_finish_kernel(const float*
     }
 }
 
-extern "C" size_t pcl_loss_workspace_bytes(int64_t n, int B)
-{
-    if (n <= 0 || B <= 0) return 0;
-    return (size_t)B * sizeof(PclPoseRec) + pcl_partials_bytes(n, B);
-}
-
-static int pcl_finish_launch(const float* partials, int64_t n, int B, const PclPoseRec* recs, const float* rot, int with_grad, float* result,
-                             hipStream_t s)
-{
-    const int G = pcl_plan_G(n, B), nch = pcl_plan_nchunks(n, B);
-    if (G == 4) hipLaunchKernelGGL(pcl_finish_kernel<4>, dim3(B / 4), dim3(PCL_GD_THREADS), 0, s, partials, nch, B, recs, rot, with_grad, result);
-    else if (G == 2) hipLaunchKernelGGL(pcl_finish_kernel<2>, dim3(B / 2), dim3(PCL_GD_THREADS), 0, s, partials, nch, B, recs, rot, with_grad, result);
-    else hipLaunchKernelGGL(pcl_finish_kernel<1>, dim3(B), dim3(PCL_GD_THREADS), 0, s, partials, nch, B, recs, rot, with_grad, result);
-    PCL_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int pcl_sampling_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
-                                 const float* rot, int B, int with_grad, const uint8_t* visible, float* result,
-                                 void* workspace, size_t workspace_bytes, void* stream)
-{
-    if (!cloud || !pano || !trans || !rot || !result || !workspace || n <= 0 || B <= 0 || H <= 0 || W <= 0) return PCL_EINVAL;
-    if (n > PCL_MAX_POINTS) return PCL_EINVAL;               // (before anything is enqueued)
-    if (workspace_bytes < pcl_loss_workspace_bytes(n, B)) return PCL_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    PclPoseRec* recs = (PclPoseRec*)workspace;
-    float* partials = (float*)((char*)workspace + (size_t)B * sizeof(PclPoseRec));
-    hipLaunchKernelGGL(pcl_pose_setup_kernel, dim3((B + 255) / 256), dim3(256), 0, s, trans, rot, B, recs);
-    PCL_LAUNCH_CHECK();
-    int rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, recs, B, with_grad != 0, visible, partials, s, 0, nullptr, nullptr);
-    if (rc) return rc;
-    return pcl_finish_launch(partials, n, B, recs, rot, with_grad, result, s);
-}
-
 // the grid and occluder stride a depth-masked call uses: the caller's, or pcl_depth_default's for 0 x 0 / stride 0 (a given grid
 // without a stride: every point builds the z-buffer)
 static int gd_depth_grid(int64_t n, int H, int W, int depth_h, int depth_w, float tau, int stride_in, PclDepthGrid* g, int* stride)
@@ -119,43 +68,98 @@ static int gd_depth_grid(int64_t n, int H, int W, int depth_h, int depth_w, floa
     return 0;
 }
 
+// Workspaces are carved in ONE place per family, a layout function that the size query runs without a base and the call with the
+// caller's buffer: raw(bytes) is the next region as it comes (null without a base), take(bytes) one that ends on a 256-byte boundary;
+// `off` is the size so far.
 static size_t gd_align(size_t v) { return (v + 255) & ~(size_t)255; }
+struct GdCarve {
+    char* base;
+    size_t off;
+    void* raw(size_t bytes) { void* p = base ? base + off : nullptr; off += bytes; return p; }
+    void* take(size_t bytes) { return raw(gd_align(bytes)); }
+};
+
+// stateless loss: pose records and partials back to back; with a depth grid the poses' z-buffers from the next 256-byte boundary on
+struct GdLossWs { PclPoseRec* recs; float* partials; uint32_t* zbuf; };
+static size_t gd_loss_layout(void* base, int64_t n, int B, const PclDepthGrid* grid, GdLossWs* w)
+{
+    GdCarve c{(char*)base, 0};
+    w->recs = (PclPoseRec*)c.raw((size_t)B * sizeof(PclPoseRec));
+    w->partials = (float*)c.raw(pcl_partials_bytes(n, B));
+    w->zbuf = nullptr;
+    if (grid) {
+        c.off = gd_align(c.off);
+        w->zbuf = (uint32_t*)c.raw(pcl_depth_zbuf_bytes(B, grid->Hd, grid->Wd));
+    }
+    return c.off;
+}
+
+extern "C" size_t pcl_loss_workspace_bytes(int64_t n, int B)
+{
+    GdLossWs w;
+    return n <= 0 || B <= 0 ? 0 : gd_loss_layout(nullptr, n, B, nullptr, &w);
+}
 
 // (the default grid follows the occluder stride — 1M points: 144 x 288 at the default stride 2, 200 x 400 at stride 1 — so the size query
 //  takes the stride the call will be given: ADVICE r05, a 0 x 0 grid with an explicit stride overflowed a workspace sized without it)
 extern "C" size_t pcl_loss_depth_workspace_bytes(int64_t n, int B, int H, int W, int depth_h, int depth_w, int depth_stride)
 {
     PclDepthGrid g;
+    GdLossWs w;
     if (n <= 0 || B <= 0 || gd_depth_grid(n, H, W, depth_h, depth_w, 0.f, depth_stride, &g, nullptr)) return 0;
-    return gd_align(pcl_loss_workspace_bytes(n, B)) + pcl_depth_zbuf_bytes(B, g.Hd, g.Wd);
+    return gd_loss_layout(nullptr, n, B, &g, &w);
 }
 
-// pcl_sampling_loss with the scatter-min depth mask of the SAME poses multiplied into the mask: pose records, fill + z pass
-// (pcl_depth.hip), loss launch that looks every point's cell up, finish.  Four launches, no byte mask.
+// pose records, (with a grid: fill + z pass, pcl_depth.hip,) loss launch, finish; the workspace is sized from the grid the caller RESOLVED
+static int gd_stateless_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans, const float* rot, int B,
+                             int with_grad, const uint8_t* visible, const PclDepthGrid* grid, int zstride, float* result, void* workspace,
+                             size_t workspace_bytes, hipStream_t s)
+{
+    GdLossWs w;
+    if (workspace_bytes < gd_loss_layout(workspace, n, B, grid, &w)) return PCL_EWORKSPACE;
+    hipLaunchKernelGGL(pcl_pose_setup_kernel, dim3((B + 255) / 256), dim3(256), 0, s, trans, rot, B, w.recs);
+    PCL_LAUNCH_CHECK();
+    PclDepthLook look;
+    if (grid) {
+        look.zbuf = w.zbuf; look.grid = *grid; look.zclear = nullptr; look.zclear_vec4 = 0;
+        int rc = pcl_launch_zbuffers(cloud, n, w.recs, B, *grid, zstride, w.zbuf, true, s);
+        if (rc) return rc;
+    }
+    int rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, w.recs, B, with_grad != 0, visible, w.partials, s, 0, nullptr, grid ? &look : nullptr);
+    if (rc) return rc;
+    const int nch = pcl_plan_nchunks(n, B);
+    pcl_with_G<4>(pcl_plan_G(n, B), [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        hipLaunchKernelGGL(pcl_finish_kernel<G>, dim3(B / G), dim3(PCL_GD_THREADS), 0, s, w.partials, nch, B, w.recs, rot, with_grad, result);
+    });
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pcl_sampling_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
+                                 const float* rot, int B, int with_grad, const uint8_t* visible, float* result,
+                                 void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!cloud || !pano || !trans || !rot || !result || !workspace || n <= 0 || B <= 0 || H <= 0 || W <= 0) return PCL_EINVAL;
+    if (n > PCL_MAX_POINTS) return PCL_EINVAL;               // (before anything is enqueued)
+    return gd_stateless_loss(cloud, n, pano, pano_format, H, W, trans, rot, B, with_grad, visible, nullptr, 1, result, workspace, workspace_bytes,
+                             (hipStream_t)stream);
+}
+
+// pcl_sampling_loss with the scatter-min depth mask of the SAME poses multiplied into the mask: the loss launch looks every point's
+// cell up.  Four launches, no byte mask.
 extern "C" int pcl_sampling_loss_depth(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
                                        const float* rot, int B, int with_grad, int depth_h, int depth_w, float tau, int depth_stride, float* result,
                                        void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!cloud || !pano || !trans || !rot || !result || !workspace || n <= 0 || B <= 0 || H <= 0 || W <= 0) return PCL_EINVAL;
     if (n > PCL_MAX_POINTS) return PCL_EINVAL;
-    PclDepthLook look;
+    PclDepthGrid grid;
     int zstride = 1;
-    int rc = gd_depth_grid(n, H, W, depth_h, depth_w, tau, depth_stride, &look.grid, &zstride);
+    int rc = gd_depth_grid(n, H, W, depth_h, depth_w, tau, depth_stride, &grid, &zstride);
     if (rc) return rc;
-    // sized from the grid this call RESOLVED (not from a second resolution of the arguments)
-    if (workspace_bytes < gd_align(pcl_loss_workspace_bytes(n, B)) + pcl_depth_zbuf_bytes(B, look.grid.Hd, look.grid.Wd)) return PCL_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    PclPoseRec* recs = (PclPoseRec*)workspace;
-    float* partials = (float*)((char*)workspace + (size_t)B * sizeof(PclPoseRec));
-    uint32_t* zbuf = (uint32_t*)((char*)workspace + gd_align(pcl_loss_workspace_bytes(n, B)));
-    look.zbuf = zbuf; look.zclear = nullptr; look.zclear_vec4 = 0;
-    hipLaunchKernelGGL(pcl_pose_setup_kernel, dim3((B + 255) / 256), dim3(256), 0, s, trans, rot, B, recs);
-    PCL_LAUNCH_CHECK();
-    rc = pcl_launch_zbuffers(cloud, n, recs, B, look.grid, zstride, zbuf, true, s);
-    if (rc) return rc;
-    rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, recs, B, with_grad != 0, nullptr, partials, s, 0, nullptr, &look);
-    if (rc) return rc;
-    return pcl_finish_launch(partials, n, B, recs, rot, with_grad, result, s);
+    return gd_stateless_loss(cloud, n, pano, pano_format, H, W, trans, rot, B, with_grad, nullptr, &grid, zstride, result, workspace, workspace_bytes,
+                             (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- GD: state init, epilogue, run, result
@@ -235,21 +239,28 @@ static int gd_sets(int B, const pcl_gd_hyper* hyper_host)
     return B % hyper_host->color_sets || hyper_host->depth_mask ? -1 : hyper_host->color_sets;
 }
 
+// single run: two partials buffers (fused iterations read one while they write the other; with colour sets the single-image plan: more
+// chunks than the plan of B candidates may have, hence larger partials) and, under the depth mask, two sets of z-buffers: iteration k
+// reads set k & 1 and resets the other one for iteration k + 1's z pass (no fill launch between iterations).  Scratch: every pcl_gd_run
+// call fills set 0 itself before its first iteration, nothing persists in them.
+struct GdRunWs { float* partials[2]; uint32_t* zbuf[2]; };
+static size_t gd_run_layout(void* base, int64_t n, int B, int sets, const PclDepthGrid* grid, GdRunWs* w)
+{
+    GdCarve c{(char*)base, 0};
+    for (int k = 0; k < 2; k++) w->partials[k] = (float*)c.take(pcl_partials_bytes(n, B, sets));
+    for (int k = 0; k < 2; k++) w->zbuf[k] = grid ? (uint32_t*)c.take(pcl_depth_zbuf_bytes(B, grid->Hd, grid->Wd)) : nullptr;
+    return c.off;
+}
+
 extern "C" size_t pcl_gd_workspace_bytes(int64_t n, int B, int H, int W, const pcl_gd_hyper* hyper_host)
 {
     if (n <= 0 || B <= 0 || !hyper_host) return 0;
     const int sets = gd_sets(B, hyper_host);
     if (sets < 0) return 0;
-    // (with colour sets the single-image plan: more chunks than the plan of B candidates may have, hence larger partials)
-    size_t bytes = 2 * gd_align(pcl_partials_bytes(n, B, sets));   // (two: fused iterations read one while they write the other)
-    if (hyper_host->depth_mask) {
-        PclDepthGrid g;
-        if (gd_depth_grid(n, H, W, hyper_host->depth_h, hyper_host->depth_w, 0.f, hyper_host->depth_stride, &g, nullptr)) return 0;
-        // two sets: iteration k reads set k & 1 and resets the other one for iteration k + 1's z pass (no fill launch between
-        // iterations).  Scratch: every pcl_gd_run call fills set 0 itself before its first iteration, nothing persists in them.
-        bytes += 2 * gd_align(pcl_depth_zbuf_bytes(B, g.Hd, g.Wd));
-    }
-    return bytes;
+    PclDepthGrid g;
+    GdRunWs w;
+    if (hyper_host->depth_mask && gd_depth_grid(n, H, W, hyper_host->depth_h, hyper_host->depth_w, 0.f, hyper_host->depth_stride, &g, nullptr)) return 0;
+    return gd_run_layout(nullptr, n, B, sets, hyper_host->depth_mask ? &g : nullptr, &w);
 }
 
 extern "C" int pcl_gd_init(void* state, const float* trans, const float* rot, int B, const pcl_gd_hyper* hyper_host, void* stream)
@@ -260,59 +271,6 @@ extern "C" int pcl_gd_init(void* state, const float* trans, const float* rot, in
     hipLaunchKernelGGL(pcl_gd_init_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, gd_poses(state),
                        gd_recs(state, B), gd_recs(state, B, 1), trans, rot, B, hyper_host->lr, sets > 1 ? B / sets : 0);
     PCL_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- kernel timer: host-side pool of event pairs (include/piccolo_hip.h)
-struct PclTimer {
-    int capacity, used, stride;
-    hipEvent_t* start;
-    hipEvent_t* stop;
-};
-
-extern "C" void* pcl_timer_create(int capacity)
-{
-    if (capacity <= 0) return nullptr;
-    PclTimer* t = new PclTimer;
-    t->capacity = capacity; t->used = 0; t->stride = 1;
-    t->start = new hipEvent_t[capacity];
-    t->stop = new hipEvent_t[capacity];
-    for (int i = 0; i < capacity; i++) {
-        if (hipEventCreate(&t->start[i]) != hipSuccess || hipEventCreate(&t->stop[i]) != hipSuccess) {
-            for (int j = 0; j <= i; j++) { (void)hipEventDestroy(t->start[j]); if (j < i) (void)hipEventDestroy(t->stop[j]); }
-            delete[] t->start; delete[] t->stop; delete t;
-            return nullptr;
-        }
-    }
-    return t;
-}
-
-extern "C" void pcl_timer_destroy(void* timer)
-{
-    PclTimer* t = (PclTimer*)timer;
-    if (!t) return;
-    for (int i = 0; i < t->capacity; i++) { (void)hipEventDestroy(t->start[i]); (void)hipEventDestroy(t->stop[i]); }
-    delete[] t->start; delete[] t->stop; delete t;
-}
-
-extern "C" void pcl_timer_reset(void* timer) { if (timer) ((PclTimer*)timer)->used = 0; }
-
-extern "C" void pcl_timer_set_stride(void* timer, int stride) { if (timer && stride > 0) ((PclTimer*)timer)->stride = stride; }
-
-extern "C" int pcl_timer_read(void* timer, double* total_ms_host, int* launches_host)
-{
-    PclTimer* t = (PclTimer*)timer;
-    if (!t || !total_ms_host || !launches_host) return PCL_EINVAL;
-    double total = 0.0;
-    for (int i = 0; i < t->used; i++) {
-        hipError_t e = hipEventSynchronize(t->stop[i]);
-        if (e != hipSuccess) return (int)e;
-        float ms = 0.f;
-        e = hipEventElapsedTime(&ms, t->start[i], t->stop[i]);
-        if (e != hipSuccess) return (int)e;
-        total += (double)ms;
-    }
-    *total_ms_host = total; *launches_host = t->used;
     return 0;
 }
 
@@ -342,152 +300,122 @@ extern "C" int pcl_gd_plan(int64_t n, int B, int* nchunks_host, int* poses_per_b
     return pcl_gd_plan_hyper(n, B, nullptr, nchunks_host, poses_per_block_host, fused_host);
 }
 
-extern "C" int pcl_timer_calibrate(void* timer, int reps, double* pair_ms_host, void* stream)
+// what every run entry point refuses first: a null argument (`what`: its cloud or its rooms), an empty panorama, a negative iteration
+// count, an unknown mode
+static bool gd_run_args_ok(const void* what, const void* pano, const void* state, const pcl_gd_hyper* hyper_host, const void* workspace, int H, int W,
+                           int num_iter)
 {
-    if (!timer || !pair_ms_host || reps <= 0 || reps > 4096) return PCL_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    hipEvent_t a, b;
-    hipError_t e = hipEventCreate(&a);
-    if (e != hipSuccess) return (int)e;
-    e = hipEventCreate(&b);
-    if (e != hipSuccess) { (void)hipEventDestroy(a); return (int)e; }
-    float* ms = new float[reps];
-    int got = 0;
-    for (int i = 0; i < reps && e == hipSuccess; i++) {
-        e = hipEventRecord(a, s);
-        if (e == hipSuccess) e = hipEventRecord(b, s);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms[got], a, b);
-        if (e == hipSuccess) got++;
-    }
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (e == hipSuccess) {
-        for (int i = 1; i < got; i++) {                      // insertion sort: a few dozen values
-            float v = ms[i]; int j = i - 1;
-            while (j >= 0 && ms[j] > v) { ms[j + 1] = ms[j]; j--; }
-            ms[j + 1] = v;
+    return what && pano && state && hyper_host && workspace && H > 0 && W > 0 && num_iter >= 0 &&
+           (hyper_host->mode == PCL_GD_SEQUENTIAL || hyper_host->mode == PCL_GD_BATCH);
+}
+
+// The iteration protocol of every GD chain, once.  Per iteration: before(it) — the z passes of a depth-masked chain —, then the loss
+// launch, bracketed by the timer, then the stand-alone epilogue (two-launch form).  Fused form — ONE launch per iteration for launches
+// whose blocks are all resident at once (the reference's shipped 167k-point / 6-candidate shape, cfg 1): there an iteration is two
+// dependent launches of a few microseconds, and the 5 us the epilogue launch costs are pure dispatch.  The loss launch of iteration
+// k + 1 finishes iteration k in the prologue of every block (PclFuseArgs) — no inter-block synchronisation, the kernel boundary is the
+// only one: iteration `it` reads copy (it - 1) & 1 of state / pose records / partials and writes copy it & 1, and the last iteration is
+// finished by the stand-alone epilogue.  Same arithmetic in the same order: results are bit-identical to the two-launch form.
+//   before(it) -> status
+//   loss(it, recs, partials_out, fuse) -> status      fuse: null, or the previous iteration to finish (`box`: null where a room table
+//                                                      holds every room's own)
+//   epilogue(copy_in, partials, loss_out)              reads copy `copy_in` of the state, writes copy 0; loss_out: its row of the history
+template <class Before, class Loss, class Epilogue>
+static int gd_chain_loop(void* state, int B, bool fused, const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history,
+                         float* const partials2[2], PclTimer* tm, hipStream_t s, Before before, Loss loss, Epilogue epilogue)
+{
+    auto history = [&](int it) { return loss_history ? loss_history + (int64_t)it * B : nullptr; };
+    for (int it = 0; it < num_iter; it++) {
+        int rc = before(it);
+        if (rc) return rc;
+        bool timed;
+        hipError_t e = pcl_timer_begin(tm, it, s, &timed);
+        if (e != hipSuccess) return (int)e;
+        if (fused && it > 0) {
+            const int cin = (it - 1) & 1, cout = it & 1;
+            PclFuseArgs f;
+            f.partials_in = partials2[cin]; f.st_in = gd_poses(state, B, cin); f.recs_in = gd_recs(state, B, cin);
+            f.st_out = gd_poses(state, B, cout); f.recs_out = gd_recs(state, B, cout);
+            f.box = box; f.factor = hyper_host->factor; f.patience = (int)hyper_host->patience; f.mode = (int)hyper_host->mode;
+            f.loss_out = history(it - 1);
+            rc = loss(it, f.recs_in, partials2[cout], &f);
+        } else {
+            rc = loss(it, gd_recs(state, B), partials2[0], nullptr);
         }
-        *pair_ms_host = (double)ms[got / 2];
+        if (rc) return rc;
+        if (timed && (e = pcl_timer_end(tm, s)) != hipSuccess) return (int)e;
+        if (!fused) {
+            epilogue(0, partials2[0], history(it));
+            PCL_LAUNCH_CHECK();
+        }
     }
-    delete[] ms;
-    return (int)e;
+    if (fused && num_iter > 0) {
+        const int last = num_iter > 1 ? (num_iter - 1) & 1 : 0;    // the copy the last launch wrote (copy 0 when it was the only one)
+        epilogue(last, partials2[last], history(num_iter - 1));
+        PCL_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, void* state, int B,
                           const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history,
                           void* workspace, size_t workspace_bytes, void* timer, void* stream)
 {
-    PclTimer* tm = (PclTimer*)timer;
-    if (!cloud || !pano || !state || !box || !hyper_host || !workspace || n <= 0 || B <= 0 || H <= 0 || W <= 0 || num_iter < 0)
-        return PCL_EINVAL;
-    if (n > PCL_MAX_POINTS) return PCL_EINVAL;
-    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
+    if (!gd_run_args_ok(cloud, pano, state, hyper_host, workspace, H, W, num_iter) || !box || n <= 0 || n > PCL_MAX_POINTS || B <= 0) return PCL_EINVAL;
     // colour sets: `cloud` holds hyper->color_sets of them (pcl_cloud_pack_sets) and candidate b reads set b / (B / color_sets), as
     // pcl_gd_init wrote into its pose record; the chain runs the single-image plan of B / color_sets candidates (pcl_plan_sets)
     const int sets = gd_sets(B, hyper_host);
     if (sets < 0 || (sets > 1 && pcl_cloud_sets_bytes(n, sets) == 0)) return PCL_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* partials2[2] = {(float*)workspace, (float*)((char*)workspace + gd_align(pcl_partials_bytes(n, B, sets)))};
+    const bool depth_on = hyper_host->depth_mask != 0;
     PclDepthLook look;
     look.zbuf = nullptr;
     int zstride = 1;
-    if (hyper_host->depth_mask) {
+    if (depth_on) {
         int rcg = gd_depth_grid(n, H, W, hyper_host->depth_h, hyper_host->depth_w, hyper_host->depth_tau, hyper_host->depth_stride, &look.grid, &zstride);
         if (rcg) return rcg;
-    }
-    const size_t need = pcl_gd_workspace_bytes(n, B, H, W, hyper_host);
-    if (need == 0 || workspace_bytes < need) return PCL_EWORKSPACE;
-    uint32_t* zbuf2[2] = {nullptr, nullptr};
-    if (hyper_host->depth_mask) {
-        zbuf2[0] = (uint32_t*)((char*)workspace + 2 * gd_align(pcl_partials_bytes(n, B, sets)));
-        zbuf2[1] = (uint32_t*)((char*)zbuf2[0] + gd_align(pcl_depth_zbuf_bytes(B, look.grid.Hd, look.grid.Wd)));
         look.zclear_vec4 = (int64_t)(pcl_depth_zbuf_bytes(B, look.grid.Hd, look.grid.Wd) / 16);
     }
-    const bool depth_on = zbuf2[0] != nullptr;
+    GdRunWs w;
+    if (workspace_bytes < gd_run_layout(workspace, n, B, sets, depth_on ? &look.grid : nullptr, &w)) return PCL_EWORKSPACE;
     static const int pingpong_env = PCL_KNOB(ZPINGPONG, 1);      // 0: a fill launch per iteration (A/B)
     const int nchunks = pcl_plan_nchunks(n, B, sets);
     // odd iterations walk every XCD's chunks backwards: the first blocks of a launch then read the chunks the previous launch
     // finished with, still in that XCD's L2 (PCL_FLIP=0 turns it off; +0.3 % at cfg 2 in two A/B alternations on one box —
     // the first round of a launch stays 6 us slower than the later ones, so cold L2 is not what makes it slow)
     static const int flip_env = PCL_KNOB(FLIP, 1);
-    // ONE launch per iteration for launches whose blocks are all resident at once (the reference's shipped 167k-point /
-    // 6-candidate shape, cfg 1): there an iteration is two dependent launches of a few microseconds, and the 5 us the epilogue
-    // launch costs are pure dispatch.  The loss launch of iteration k + 1 finishes iteration k in the prologue of every block
-    // (PclFuseArgs) — no inter-block synchronisation, the kernel boundary is the only one; the last iteration is finished by
-    // the stand-alone epilogue.  Same arithmetic in the same order: results are bit-identical to the two-launch form
-    // (pcl_gd_hyper.fuse < 0: never — the form the parity tests compare this one with).
     // several panoramas in the launch AND a cloud small enough to live in every XCD's L2 next to a texture (6 MB: the reference's
     // shipped 167k points): the XCDs split the pose groups — the images — instead of the chunks (pcl_launch_loss).  Large clouds keep
     // the chunk mapping: measured at 1M points, 8 images per launch +0.3 % (3 523 -> 3 533), 5 images per launch (the driver's shape:
     // 10 groups per XCD straddling the images, every XCD walking the whole 24 MB cloud) -1.5 % (3 533 -> 3 479).
     const int xcd_bit = hyper_host->images > 1 && n * 24 <= ((int64_t)6 << 20) ? 2 : 0;
-    const int fuse_blocks = gd_fuse_limit(hyper_host);
-    const bool fused = !depth_on && pcl_plan_nblocks(n, B, sets) <= fuse_blocks;
+    // (the depth-masked loss pass looks a mask up that the fused prologue knows nothing about: two launches there; pcl_gd_hyper.fuse < 0:
+    //  never fused — the form the parity tests compare the fused one with)
+    const bool fused = !depth_on && pcl_plan_nblocks(n, B, sets) <= gd_fuse_limit(hyper_host);
     const int G = pcl_plan_G(n, B, sets);
-    auto epilogue = [&](int it, int copy_in, float* partials) {
-        const PclGdPose* si = gd_poses(state, B, copy_in);
-        const PclPoseRec* ri = gd_recs(state, B, copy_in);
-        PclGdPose* so = gd_poses(state, B, 0);
-        PclPoseRec* ro = gd_recs(state, B, 0);
-        float* lo = loss_history ? loss_history + (int64_t)it * B : nullptr;
-        const double fac = hyper_host->factor;
-        const int pat = (int)hyper_host->patience, mode = (int)hyper_host->mode;
-        if (G == 4) hipLaunchKernelGGL(pcl_gd_epilogue_kernel<4>, dim3(B / 4), dim3(PCL_GD_THREADS), 0, s, partials, nchunks, si, ri, so, ro, box, fac, pat, mode, lo);
-        else if (G == 2) hipLaunchKernelGGL(pcl_gd_epilogue_kernel<2>, dim3(B / 2), dim3(PCL_GD_THREADS), 0, s, partials, nchunks, si, ri, so, ro, box, fac, pat, mode, lo);
-        else hipLaunchKernelGGL(pcl_gd_epilogue_kernel<1>, dim3(B), dim3(PCL_GD_THREADS), 0, s, partials, nchunks, si, ri, so, ro, box, fac, pat, mode, lo);
-    };
-    for (int it = 0; it < num_iter; it++) {
-        const PclDepthLook* depth = nullptr;
-        if (depth_on) {
+    return gd_chain_loop(
+        state, B, fused, box, hyper_host, num_iter, loss_history, w.partials, (PclTimer*)timer, s,
+        [&](int it) {
+            if (!depth_on) return 0;
             // the scatter-min z-buffers of the poses this iteration evaluates: z pass into set it & 1 (filled by this call before its
             // first iteration, reset by the previous iteration's loss launch afterwards); the loss launch looks them up
             const int set = pingpong_env ? (it & 1) : 0;
-            int rcd = pcl_launch_zbuffers(cloud, n, gd_recs(state, B), B, look.grid, zstride, zbuf2[set], it == 0 || !pingpong_env, s);
-            if (rcd) return rcd;
-            look.zbuf = zbuf2[set];
-            look.zclear = pingpong_env ? zbuf2[set ^ 1] : nullptr;
-            depth = &look;
-        }
-        // time every `stride`-th launch only: an event pair costs a few microseconds of GPU timeline, which would
-        // distort short kernels if it bracketed all of them
-        const bool timed = tm && tm->used < tm->capacity && (it % tm->stride) == 0;
-        if (timed) {
-            hipError_t e = hipEventRecord(tm->start[tm->used], s);
-            if (e != hipSuccess) return (int)e;
-        }
-        int rc;
-        if (fused && it > 0) {
-            // iteration `it` reads copy (it - 1) & 1 of state / pose records / partials and writes copy it & 1
-            const int cin = (it - 1) & 1, cout = it & 1;
-            PclFuseArgs f;
-            f.partials_in = partials2[cin]; f.st_in = gd_poses(state, B, cin); f.recs_in = gd_recs(state, B, cin);
-            f.st_out = gd_poses(state, B, cout); f.recs_out = gd_recs(state, B, cout);
-            f.box = box; f.factor = hyper_host->factor; f.patience = (int)hyper_host->patience; f.mode = (int)hyper_host->mode;
-            f.loss_out = loss_history ? loss_history + (int64_t)(it - 1) * B : nullptr;
-            rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, f.recs_in, B, true, nullptr, partials2[cout], s, (flip_env ? (it & 1) : 0) | xcd_bit, &f,
-                                 nullptr, sets);
-        } else {
-            rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, gd_recs(state, B), B, true, nullptr, partials2[0], s, (flip_env ? (it & 1) : 0) | xcd_bit,
-                                 nullptr, depth, sets);
-        }
-        if (rc) return rc;
-        if (timed) {
-            // (only a completed start/stop pair counts as used: pcl_timer_read never sees a half-recorded slot)
-            hipError_t e = hipEventRecord(tm->stop[tm->used], s);
-            if (e != hipSuccess) return (int)e;
-            tm->used++;
-        }
-        if (!fused) {
-            epilogue(it, 0, partials2[0]);
-            PCL_LAUNCH_CHECK();
-        }
-    }
-    if (fused && num_iter > 0) {
-        const int last = (num_iter - 1) & 1;                     // the copy the last launch wrote (copy 0 when it was the only one)
-        epilogue(num_iter - 1, num_iter > 1 ? last : 0, partials2[num_iter > 1 ? last : 0]);
-        PCL_LAUNCH_CHECK();
-    }
-    return 0;
+            look.zbuf = w.zbuf[set];
+            look.zclear = pingpong_env ? w.zbuf[set ^ 1] : nullptr;
+            return pcl_launch_zbuffers(cloud, n, gd_recs(state, B), B, look.grid, zstride, w.zbuf[set], it == 0 || !pingpong_env, s);
+        },
+        [&](int it, const PclPoseRec* recs, float* partials, const PclFuseArgs* fuse) {
+            return pcl_launch_loss(cloud, n, pano, pano_format, H, W, recs, B, true, nullptr, partials, s, (flip_env ? (it & 1) : 0) | xcd_bit, fuse,
+                                   depth_on ? &look : nullptr, sets);
+        },
+        [&](int copy_in, const float* partials, float* loss_out) {
+            pcl_with_G<4>(G, [&](auto g) {
+                constexpr int GG = decltype(g)::value;
+                hipLaunchKernelGGL(pcl_gd_epilogue_kernel<GG>, dim3(B / GG), dim3(PCL_GD_THREADS), 0, s, partials, nchunks, gd_poses(state, B, copy_in),
+                                   gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), box, hyper_host->factor,
+                                   (int)hyper_host->patience, (int)hyper_host->mode, loss_out);
+            });
+        });
 }
 
 // ---------------------------------------------------------------- room search: several clouds in one chain
@@ -568,116 +496,69 @@ static int gd_rooms_setup(const pcl_gd_room* rooms_host, int nrooms, int nimages
 static void gd_rooms_epilogue(const GdRooms& g, const PclRoomTable* table, void* state, int copy_in, const float* partials, const pcl_gd_hyper* hyper_host,
                               float* lo, hipStream_t s)
 {
-    const int B = g.nrooms * g.per_room, ngrp = g.nrooms * g.ngroups;
-    const double fac = hyper_host->factor;
-    const int pat = (int)hyper_host->patience, mode = (int)hyper_host->mode;
-    if (g.G == 2)
-        hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<2>, dim3(ngrp), dim3(PCL_GD_THREADS), 0, s, partials, table, g.ngroups, gd_poses(state, B, copy_in),
-                           gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), fac, pat, mode, lo);
-    else
-        hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<1>, dim3(ngrp), dim3(PCL_GD_THREADS), 0, s, partials, table, g.ngroups, gd_poses(state, B, copy_in),
-                           gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0), fac, pat, mode, lo);
+    const int B = g.nrooms * g.per_room;
+    pcl_with_G<2>(g.G, [&](auto gg) {
+        hipLaunchKernelGGL(pcl_gd_epilogue_rooms_kernel<decltype(gg)::value>, dim3(g.nrooms * g.ngroups), dim3(PCL_GD_THREADS), 0, s, partials, table,
+                           g.ngroups, gd_poses(state, B, copy_in), gd_recs(state, B, copy_in), gd_poses(state, B, 0), gd_recs(state, B, 0),
+                           hyper_host->factor, (int)hyper_host->patience, (int)hyper_host->mode, lo);
+    });
 }
 
-// table, then two partials buffers (fused iterations read one while they write the other)
+// multi-room chain: the room table, then two partials buffers (fused iterations read one while they write the other).  Depth-masked
+// chain (`depth`): room table, depth table, ONE partials buffer — such a chain never fuses, so partials[1] stays null and gd_chain_loop
+// never reads it —, two z-buffer sets of zset_bytes each.
+struct GdRoomsWs { PclRoomTable* table; PclDepthTable* dtab; float* partials[2]; uint32_t* zset[2]; };
+static size_t gd_rooms_layout(void* base, const GdRooms& g, bool depth, size_t zset_bytes, GdRoomsWs* w)
+{
+    GdCarve c{(char*)base, 0};
+    w->table = (PclRoomTable*)c.take(sizeof(PclRoomTable));
+    w->dtab = depth ? (PclDepthTable*)c.take(sizeof(PclDepthTable)) : nullptr;
+    w->partials[0] = (float*)c.take(g.partials_bytes);
+    w->partials[1] = depth ? nullptr : (float*)c.take(g.partials_bytes);
+    for (int k = 0; k < 2; k++) w->zset[k] = depth ? (uint32_t*)c.take(zset_bytes) : nullptr;
+    return c.off;
+}
+
+// the iteration loop of a multi-room chain whose plan `g` holds: table launch, then per iteration the rooms loss launch (+ the rooms
+// epilogue in the two-launch form); flip and timer as in pcl_gd_run, and the XCDs always split the chunks
+static int gd_rooms_chain(const GdRooms& g, const void* pano, int pano_format, int H, int W, void* state, const pcl_gd_hyper* hyper_host, int num_iter,
+                          float* loss_history, void* workspace, PclTimer* tm, hipStream_t s)
+{
+    const int B = g.nrooms * g.per_room;
+    GdRoomsWs w;
+    gd_rooms_layout(workspace, g, false, 0, &w);
+    const int words = (int)(sizeof(PclRoomTable) / 4);
+    hipLaunchKernelGGL(pcl_gd_rooms_table_kernel, dim3((words + 255) / 256), dim3(256), 0, s, g.t, w.table);
+    PCL_LAUNCH_CHECK();
+    static const int flip_env = PCL_KNOB(FLIP, 1);
+    return gd_chain_loop(
+        state, B, g.nblk <= gd_fuse_limit(hyper_host), nullptr, hyper_host, num_iter, loss_history, w.partials, tm, s, [](int) { return 0; },
+        [&](int it, const PclPoseRec* recs, float* partials, const PclFuseArgs* fuse) {
+            return pcl_launch_loss_rooms(w.table, pano, pano_format, H, W, recs, B, g.G, g.ngroups, g.nblk, partials, s, flip_env ? (it & 1) : 0, fuse,
+                                         g.sets);
+        },
+        [&](int copy_in, const float* partials, float* lo) { gd_rooms_epilogue(g, w.table, state, copy_in, partials, hyper_host, lo, s); });
+}
+
+// the one-image entry points: the rooms x images functions with nimages = 1 (which then admit neither colour sets above 1 nor, as ever,
+// the depth mask)
 extern "C" size_t pcl_gd_rooms_workspace_bytes(const pcl_gd_room* rooms_host, int nrooms, int per_room, const pcl_gd_hyper* hyper_host)
 {
-    GdRooms g;
-    if (gd_rooms_setup(rooms_host, nrooms, 1, per_room, hyper_host, &g)) return 0;
-    return gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes);
+    return pcl_gd_rooms_images_workspace_bytes(rooms_host, nrooms, 1, per_room, hyper_host);
 }
 
 extern "C" int pcl_gd_plan_rooms(const pcl_gd_room* rooms_host, int nrooms, int per_room, const pcl_gd_hyper* hyper_host, int* nchunks_host,
                                  int* poses_per_block_host, int* fused_host)
 {
-    GdRooms g;
-    const int rc = gd_rooms_setup(rooms_host, nrooms, 1, per_room, hyper_host, &g);
-    if (rc) return rc;
-    if (nchunks_host)
-        for (int r = 0; r < nrooms; r++) nchunks_host[r] = g.t.rec[r].nchunks;
-    if (poses_per_block_host) *poses_per_block_host = g.G;
-    if (fused_host) *fused_host = g.nblk <= gd_fuse_limit(hyper_host) ? 1 : 0;
-    return 0;
+    return pcl_gd_plan_rooms_images(rooms_host, nrooms, 1, per_room, hyper_host, nchunks_host, poses_per_block_host, fused_host);
 }
 
-// the iteration loop of a multi-room chain whose plan `g` holds (pcl_gd_run_rooms, pcl_gd_run_rooms_images): table launch, then per
-// iteration the rooms loss launch (+ the rooms epilogue in the two-launch form); flip and timer as in pcl_gd_run
-static int gd_rooms_chain(const GdRooms& g, const void* pano, int pano_format, int H, int W, void* state, const pcl_gd_hyper* hyper_host, int num_iter,
-                          float* loss_history, void* workspace, PclTimer* tm, hipStream_t s)
-{
-    const int nrooms = g.nrooms, B = nrooms * g.per_room, G = g.G;
-    int rc;
-    PclRoomTable* table = (PclRoomTable*)workspace;
-    float* partials2[2] = {(float*)((char*)workspace + gd_align(sizeof(PclRoomTable))),
-                           (float*)((char*)workspace + gd_align(sizeof(PclRoomTable)) + gd_align(g.partials_bytes))};
-    const int words = (int)(sizeof(PclRoomTable) / 4);
-    hipLaunchKernelGGL(pcl_gd_rooms_table_kernel, dim3((words + 255) / 256), dim3(256), 0, s, g.t, table);
-    PCL_LAUNCH_CHECK();
-    static const int flip_env = PCL_KNOB(FLIP, 1);
-    const bool fused = g.nblk <= gd_fuse_limit(hyper_host);
-    auto epilogue = [&](int it, int copy_in, float* partials) {
-        gd_rooms_epilogue(g, table, state, copy_in, partials, hyper_host, loss_history ? loss_history + (int64_t)it * B : nullptr, s);
-    };
-    for (int it = 0; it < num_iter; it++) {
-        const bool timed = tm && tm->used < tm->capacity && (it % tm->stride) == 0;
-        if (timed) {
-            hipError_t e = hipEventRecord(tm->start[tm->used], s);
-            if (e != hipSuccess) return (int)e;
-        }
-        const int flip = flip_env ? (it & 1) : 0;
-        if (fused && it > 0) {
-            const int cin = (it - 1) & 1, cout = it & 1;
-            PclFuseArgs f;
-            f.partials_in = partials2[cin]; f.st_in = gd_poses(state, B, cin); f.recs_in = gd_recs(state, B, cin);
-            f.st_out = gd_poses(state, B, cout); f.recs_out = gd_recs(state, B, cout);
-            f.box = nullptr;                                  // (every room's own box: the room table)
-            f.factor = hyper_host->factor; f.patience = (int)hyper_host->patience; f.mode = (int)hyper_host->mode;
-            f.loss_out = loss_history ? loss_history + (int64_t)(it - 1) * B : nullptr;
-            rc = pcl_launch_loss_rooms(table, pano, pano_format, H, W, f.recs_in, B, G, g.ngroups, g.nblk, partials2[cout], s, flip, &f, g.sets);
-        } else {
-            rc = pcl_launch_loss_rooms(table, pano, pano_format, H, W, gd_recs(state, B), B, G, g.ngroups, g.nblk, partials2[0], s, flip, nullptr, g.sets);
-        }
-        if (rc) return rc;
-        if (timed) {
-            hipError_t e = hipEventRecord(tm->stop[tm->used], s);
-            if (e != hipSuccess) return (int)e;
-            tm->used++;
-        }
-        if (!fused) {
-            epilogue(it, 0, partials2[0]);
-            PCL_LAUNCH_CHECK();
-        }
-    }
-    if (fused && num_iter > 0) {
-        const int last = (num_iter - 1) & 1;
-        epilogue(num_iter - 1, num_iter > 1 ? last : 0, partials2[num_iter > 1 ? last : 0]);
-        PCL_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
-// pcl_gd_run for several rooms: the same iteration loop, fused and two-launch forms, with the rooms instances of the loss kernel and
-// the rooms epilogue (flip and timer as there; the XCDs always split the chunks — one panorama)
 extern "C" int pcl_gd_run_rooms(const pcl_gd_room* rooms_host, int nrooms, const void* pano, int pano_format, int H, int W, void* state, int per_room,
                                 const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace, size_t workspace_bytes,
                                 void* timer, void* stream)
 {
-    PclTimer* tm = (PclTimer*)timer;
-    if (!rooms_host || !pano || !state || !hyper_host || !workspace || H <= 0 || W <= 0 || num_iter < 0) return PCL_EINVAL;
-    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
-    GdRooms g;
-    int rc = gd_rooms_setup(rooms_host, nrooms, 1, per_room, hyper_host, &g);
-    if (rc) return rc;
-    if (workspace_bytes < gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes)) return PCL_EWORKSPACE;
-    // one room: pcl_gd_run itself (the same plan and arithmetic — and no room look-up in front of every block: 1.2 us per iteration at the
-    // shipped shape, tools/room_bench.py).  Its workspace, two partials buffers of the same plan, fits in this one.
-    if (nrooms == 1) {
-        pcl_gd_hyper h = *hyper_host;
-        h.images = 0;
-        return pcl_gd_run(rooms_host[0].cloud, rooms_host[0].n, pano, pano_format, H, W, state, per_room, rooms_host[0].box, &h, num_iter, loss_history,
-                          workspace, workspace_bytes, timer, stream);
-    }
-    return gd_rooms_chain(g, pano, pano_format, H, W, state, hyper_host, num_iter, loss_history, workspace, tm, (hipStream_t)stream);
+    return pcl_gd_run_rooms_images(rooms_host, nrooms, 1, pano, pano_format, H, W, state, per_room, hyper_host, num_iter, loss_history, workspace,
+                                   workspace_bytes, timer, stream);
 }
 
 // ---------------------------------------------------------------- room search: several panoramas x several rooms in one chain
@@ -685,15 +566,15 @@ extern "C" int pcl_gd_run_rooms(const pcl_gd_room* rooms_host, int nrooms, const
 extern "C" size_t pcl_gd_rooms_images_workspace_bytes(const pcl_gd_room* rooms_host, int nrooms, int nimages, int per_image, const pcl_gd_hyper* hyper_host)
 {
     GdRooms g;
+    GdRoomsWs w;
     if (gd_rooms_setup(rooms_host, nrooms, nimages, per_image, hyper_host, &g)) return 0;
-    return gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes);
+    return gd_rooms_layout(nullptr, g, false, 0, &w);
 }
 
 extern "C" int pcl_gd_plan_rooms_images(const pcl_gd_room* rooms_host, int nrooms, int nimages, int per_image, const pcl_gd_hyper* hyper_host,
                                         int* nchunks_host, int* poses_per_block_host, int* fused_host)
 {
     GdRooms g;
-    if (nimages < 1) return PCL_EINVAL;
     const int rc = gd_rooms_setup(rooms_host, nrooms, nimages, per_image, hyper_host, &g);
     if (rc) return rc;
     if (nchunks_host)
@@ -730,22 +611,25 @@ extern "C" int pcl_gd_init_rooms_images(void* state, const float* trans, const f
     return 0;
 }
 
+// pcl_gd_run for several rooms and panoramas: the same iteration loop, fused and two-launch forms, with the rooms instances of the loss
+// kernel and the rooms epilogue
 extern "C" int pcl_gd_run_rooms_images(const pcl_gd_room* rooms_host, int nrooms, int nimages, const void* pano, int pano_format, int H, int W,
                                        void* state, int per_image, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace,
                                        size_t workspace_bytes, void* timer, void* stream)
 {
-    if (!rooms_host || !pano || !state || !hyper_host || !workspace || H <= 0 || W <= 0 || num_iter < 0 || nimages < 1) return PCL_EINVAL;
-    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
+    if (!gd_run_args_ok(rooms_host, pano, state, hyper_host, workspace, H, W, num_iter)) return PCL_EINVAL;
     GdRooms g;
+    GdRoomsWs w;
     const int rc = gd_rooms_setup(rooms_host, nrooms, nimages, per_image, hyper_host, &g);
     if (rc) return rc;
-    if (workspace_bytes < gd_align(sizeof(PclRoomTable)) + 2 * gd_align(g.partials_bytes)) return PCL_EWORKSPACE;
-    // one image: pcl_gd_run_rooms itself (the same plans, regions and workspace size; one room: no room look-up either)
-    if (nimages == 1) {
+    if (workspace_bytes < gd_rooms_layout(nullptr, g, false, 0, &w)) return PCL_EWORKSPACE;
+    // one room and one image: pcl_gd_run itself (the same plan and arithmetic — and no room look-up in front of every block: 1.2 us per
+    // iteration at the shipped shape, tools/room_bench.py).  Its workspace, two partials buffers of the same plan, fits in this one.
+    if (nrooms == 1 && nimages == 1) {
         pcl_gd_hyper h = *hyper_host;
-        h.color_sets = 0;
-        return pcl_gd_run_rooms(rooms_host, nrooms, pano, pano_format, H, W, state, per_image, &h, num_iter, loss_history, workspace, workspace_bytes,
-                                timer, stream);
+        h.images = 0; h.color_sets = 0;
+        return pcl_gd_run(rooms_host[0].cloud, rooms_host[0].n, pano, pano_format, H, W, state, per_image, rooms_host[0].box, &h, num_iter, loss_history,
+                          workspace, workspace_bytes, timer, stream);
     }
     return gd_rooms_chain(g, pano, pano_format, H, W, state, hyper_host, num_iter, loss_history, workspace, (PclTimer*)timer, (hipStream_t)stream);
 }
@@ -795,12 +679,6 @@ static int gd_depth_chain_setup(const pcl_gd_room* rooms_host, int nrooms, int n
     return 0;
 }
 
-// room table, depth table, ONE partials buffer (a depth-masked chain never fuses), two z-buffer sets
-static size_t gd_depth_chain_bytes(const GdDepthChain& c)
-{
-    return gd_align(sizeof(PclRoomTable)) + gd_align(sizeof(PclDepthTable)) + gd_align(c.g.partials_bytes) + 2 * gd_align(c.zset_bytes);
-}
-
 // one room and one image: pcl_gd_run itself (hyper without colour sets and without the image hint)
 static pcl_gd_hyper gd_depth_single_hyper(const pcl_gd_hyper* hyper_host)
 {
@@ -813,8 +691,9 @@ extern "C" size_t pcl_gd_depth_chain_workspace_bytes(const pcl_gd_room* rooms_ho
                                                      const pcl_gd_hyper* hyper_host)
 {
     GdDepthChain c;
+    GdRoomsWs w;
     if (gd_depth_chain_setup(rooms_host, nrooms, nimages, per_image, H, W, hyper_host, &c)) return 0;
-    size_t bytes = gd_depth_chain_bytes(c);
+    size_t bytes = gd_rooms_layout(nullptr, c.g, true, c.zset_bytes, &w);
     if (nrooms == 1 && nimages == 1) {           // (forwarded to pcl_gd_run: its workspace has to fit as well)
         const pcl_gd_hyper h = gd_depth_single_hyper(hyper_host);
         const size_t single = pcl_gd_workspace_bytes(rooms_host[0].n, per_image, H, W, &h);
@@ -846,9 +725,7 @@ extern "C" int pcl_gd_run_depth_chain(const pcl_gd_room* rooms_host, int nrooms,
                                       void* state, int per_image, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history,
                                       void* workspace, size_t workspace_bytes, void* timer, void* stream)
 {
-    PclTimer* tm = (PclTimer*)timer;
-    if (!rooms_host || !pano || !state || !hyper_host || !workspace || H <= 0 || W <= 0 || num_iter < 0 || nimages < 1) return PCL_EINVAL;
-    if (hyper_host->mode != PCL_GD_SEQUENTIAL && hyper_host->mode != PCL_GD_BATCH) return PCL_EINVAL;
+    if (!gd_run_args_ok(rooms_host, pano, state, hyper_host, workspace, H, W, num_iter)) return PCL_EINVAL;
     GdDepthChain c;
     int rc = gd_depth_chain_setup(rooms_host, nrooms, nimages, per_image, H, W, hyper_host, &c);
     if (rc) return rc;
@@ -861,41 +738,32 @@ extern "C" int pcl_gd_run_depth_chain(const pcl_gd_room* rooms_host, int nrooms,
     hipStream_t s = (hipStream_t)stream;
     const GdRooms& g = c.g;
     const int B = nrooms * g.per_room;
-    char* w = (char*)workspace;
-    PclRoomTable* table = (PclRoomTable*)w;                w += gd_align(sizeof(PclRoomTable));
-    PclDepthTable* dtab = (PclDepthTable*)w;               w += gd_align(sizeof(PclDepthTable));
-    float* partials = (float*)w;                           w += gd_align(g.partials_bytes);
-    uint32_t* zset[2] = {(uint32_t*)w, (uint32_t*)(w + gd_align(c.zset_bytes))};
+    GdRoomsWs w;
+    gd_rooms_layout(workspace, g, true, c.zset_bytes, &w);
     const int words = (int)((sizeof(PclRoomTable) + sizeof(PclDepthTable)) / 4);
-    hipLaunchKernelGGL(pcl_gd_depth_tables_kernel, dim3((words + 255) / 256), dim3(256), 0, s, g.t, c.d, table, dtab);
+    hipLaunchKernelGGL(pcl_gd_depth_tables_kernel, dim3((words + 255) / 256), dim3(256), 0, s, g.t, c.d, w.table, w.dtab);
     PCL_LAUNCH_CHECK();
     static const int flip_env = PCL_KNOB(FLIP, 1);
-    const int64_t zclear_vec4 = (int64_t)(c.zset_bytes / 16);
-    for (int it = 0; it < num_iter; it++) {
-        const int set = it & 1;
-        // (set 0 is filled by this call before its first iteration; afterwards the previous iteration's loss launch reset the set)
-        for (int r = 0; r < nrooms; r++) {
-            rc = pcl_launch_zbuffers(rooms_host[r].cloud, rooms_host[r].n, gd_recs(state, B) + (size_t)r * g.per_room, g.per_room, c.d.rec[r].grid,
-                                     c.zstride[r], zset[set] + c.d.rec[r].zoff, it == 0, s);
-            if (rc) return rc;
-        }
-        const bool timed = tm && tm->used < tm->capacity && (it % tm->stride) == 0;
-        if (timed) {
-            hipError_t e = hipEventRecord(tm->start[tm->used], s);
-            if (e != hipSuccess) return (int)e;
-        }
-        rc = pcl_launch_loss_rooms_depth(table, dtab, pano, pano_format, H, W, gd_recs(state, B), B, g.G, g.ngroups, g.nblk, partials, s,
-                                         flip_env ? (it & 1) : 0, g.sets, zset[set], zset[set ^ 1], zclear_vec4);
-        if (rc) return rc;
-        if (timed) {
-            hipError_t e = hipEventRecord(tm->stop[tm->used], s);
-            if (e != hipSuccess) return (int)e;
-            tm->used++;
-        }
-        gd_rooms_epilogue(g, table, state, 0, partials, hyper_host, loss_history ? loss_history + (int64_t)it * B : nullptr, s);
-        PCL_LAUNCH_CHECK();
-    }
-    return 0;
+    PclDepthLook look = {};                                   // (every room's grid: the depth table)
+    look.zclear_vec4 = (int64_t)(c.zset_bytes / 16);
+    return gd_chain_loop(
+        state, B, false, nullptr, hyper_host, num_iter, loss_history, w.partials, (PclTimer*)timer, s,
+        [&](int it) {
+            // (set 0 is filled by this call before its first iteration; afterwards the previous iteration's loss launch reset the set)
+            look.zbuf = w.zset[it & 1];
+            look.zclear = w.zset[(it & 1) ^ 1];
+            for (int r = 0; r < nrooms; r++) {
+                const int rcz = pcl_launch_zbuffers(rooms_host[r].cloud, rooms_host[r].n, gd_recs(state, B) + (size_t)r * g.per_room, g.per_room,
+                                                    c.d.rec[r].grid, c.zstride[r], w.zset[it & 1] + c.d.rec[r].zoff, it == 0, s);
+                if (rcz) return rcz;
+            }
+            return 0;
+        },
+        [&](int it, const PclPoseRec* recs, float* partials, const PclFuseArgs* fuse) {
+            return pcl_launch_loss_rooms(w.table, pano, pano_format, H, W, recs, B, g.G, g.ngroups, g.nblk, partials, s, flip_env ? (it & 1) : 0, fuse,
+                                         g.sets, w.dtab, &look);
+        },
+        [&](int copy_in, const float* partials, float* lo) { gd_rooms_epilogue(g, w.table, state, copy_in, partials, hyper_host, lo, s); });
 }
 
 extern "C" int pcl_gd_step_from_grads(void* state, int B, const float* loss, const float* grad, const float* box, const pcl_gd_hyper* hyper_host,

@@ -1,0 +1,42 @@
+// pcl_host.h — host functions that one translation unit of the library defines and another calls (none of them is part of the C ABI),
+// declared once, and the helper that turns a runtime choice of kernel instance into a compile-time one.
+#pragma once
+#include <type_traits>
+
+#include "pcl_device.h"
+
+struct PclFuseArgs;      // pcl_gd_device.h
+struct PclRoomTable;
+struct PclDepthTable;
+
+// ---- pcl_loss.hip: launch plans and the loss launches
+// (sets > 1: the single-image plan of B / sets candidates for all B — pcl_plan_sets)
+size_t pcl_partials_bytes(int64_t n, int B, int sets = 1);
+int pcl_plan_nchunks(int64_t n, int B, int sets = 1);
+int pcl_plan_nblocks(int64_t n, int B, int sets = 1);
+int pcl_plan_G(int64_t n, int B, int sets = 1);
+void pcl_plan_room_images(int64_t n, int per_image, int nimages, int* G, int* ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
+void pcl_plan_for_groups(int64_t n, int ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
+int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, bool grad,
+                    const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, const PclDepthLook* depth,
+                    int color_sets = 1);
+int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
+                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, int color_sets = 1,
+                          const PclDepthTable* dtab = nullptr, const PclDepthLook* depth = nullptr);
+
+// ---- pcl_depth.hip: the z pass
+size_t pcl_depth_zbuf_bytes(int B, int Hd, int Wd);
+int pcl_launch_zbuffers(const float* cloud, int64_t n, const PclPoseRec* poses, int B, const PclDepthGrid& g, int zstride, uint32_t* zbuf, bool fill,
+                        hipStream_t s);
+
+// f(std::integral_constant<int, G>{}) for the runtime G: 4 where MAXG admits it, 2, else 1 — so that a kernel template with instances for
+// G <= MAXG only (the rooms kernels: 1 and 2) gains none
+template <int MAXG, class F>
+static inline void pcl_with_G(int G, F&& f)
+{
+    if constexpr (MAXG >= 4) {
+        if (G == 4) return f(std::integral_constant<int, 4>{});
+    }
+    if (G == 2) return f(std::integral_constant<int, 2>{});
+    f(std::integral_constant<int, 1>{});
+}

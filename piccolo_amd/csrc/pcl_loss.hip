@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "pcl_gd_device.h"
+#include "pcl_host.h"
 #include "pcl_sample_device.h"
 
 struct PclLossArgs {
@@ -563,151 +564,81 @@ void pcl_plan_for_groups(int64_t n, int ngroups, int* nchunks, int* seg_len, int
     *nchunks = p.nchunks; *seg_len = p.seg_len; *steps_base = p.steps_base; *steps_rem = p.steps_rem;
 }
 
-template <int G, int FMT>
-static void pcl_launch_g(const PclLossArgs& a, int nblk, bool grad, int vis, hipStream_t s)
+// ------------------------------------------------------------------------------------------------------------
+// loss launches
+
+// f(G, FMT), both std::integral_constant<int, ...>, for the runtime poses per block and texel format (pcl_with_G's rule for G and MAXG)
+template <int MAXG, class F>
+static inline void pcl_with_G_fmt(int G, int pano_format, F&& f)
 {
-    if (grad) {
-        if (vis == 2) hipLaunchKernelGGL((pcl_loss_kernel<G, true, 2, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-        else if (vis) hipLaunchKernelGGL((pcl_loss_kernel<G, true, 1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((pcl_loss_kernel<G, true, 0, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-    } else {
-        if (vis == 2) hipLaunchKernelGGL((pcl_loss_kernel<G, false, 2, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-        else if (vis) hipLaunchKernelGGL((pcl_loss_kernel<G, false, 1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((pcl_loss_kernel<G, false, 0, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-    }
+    pcl_with_G<MAXG>(G, [&](auto g) {
+        if (pano_format == PCL_PANO_U8) f(g, std::integral_constant<int, PCL_PANO_U8>{});
+        else if (pano_format == PCL_PANO_F16) f(g, std::integral_constant<int, PCL_PANO_F16>{});
+        else f(g, std::integral_constant<int, PCL_PANO_F32>{});
+    });
 }
 
-template <int FMT>
-static void pcl_launch_f(const PclLossArgs& a, int G, int nblk, bool grad, int vis, hipStream_t s)
+// What every loss launch checks and fills first: a known texel format, the padded panorama below 2 GiB (32-bit buffer addressing), then
+// the panorama, the poses, the partials, the walking direction and the colour-set count; everything else zero.
+static int pcl_loss_args(PclLossArgs* a, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, float* partials, int flip,
+                         int color_sets)
 {
-    if (G == 4) pcl_launch_g<4, FMT>(a, nblk, grad, vis, s);
-    else if (G == 2) pcl_launch_g<2, FMT>(a, nblk, grad, vis, s);
-    else pcl_launch_g<1, FMT>(a, nblk, grad, vis, s);
+    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;
+    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    *a = PclLossArgs{};
+    a->pano = pano; a->dims = pcl_make_dims(H, W, pano_format);
+    a->poses = poses; a->B = B; a->partials = partials;
+    a->flip = flip & 1; a->color_sets = color_sets > 1 ? color_sets : 1;
+    return 0;
+}
+
+// the other z-buffer set, which the launch's nblk blocks reset for the next iteration's z passes, a slice per block
+static void pcl_loss_args_zclear(PclLossArgs* a, const PclDepthLook* depth, int64_t nblk)
+{
+    a->zclear = (pcl_i4*)depth->zclear;
+    a->zclear_total = depth->zclear_vec4;
+    a->zclear_per_block = (int)((depth->zclear_vec4 + nblk - 1) / nblk);
+}
+
+// The loss pass of a multi-room chain (pcl_gd_run_rooms_images, pcl_gd_run_depth_chain): nblk blocks, every room's cloud, plan, pose range
+// and partials region from the device room table `rooms`; `poses` / `partials` (and the buffers of `fuse`) are the bases of all rooms.
+// Gradient pass, no byte mask.  color_sets > 1: every room's cloud holds that many colour sets and every pose record names its own.
+// `dtab` (nullable, then no `fuse`: a depth-masked chain keeps two launches per iteration): every room's grid and z-buffer region; of
+// `depth`, zbuf is the base of the z-buffer set this iteration reads and zclear the other set, which the launch resets (its grid is unused).
+int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
+                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, int color_sets,
+                          const PclDepthTable* dtab, const PclDepthLook* depth)
+{
+    PclLossArgs a;
+    int rc = pcl_loss_args(&a, pano, pano_format, H, W, poses, B, partials, flip, color_sets);
+    if (rc) return rc;
+    if ((G != 1 && G != 2) || nblk <= 0) return PCL_EINVAL;           // (the rooms kernels have no G = 4 instance)
+    a.ngroups = ngroups;
+    if (dtab) {
+        if (fuse || !depth || !depth->zbuf || !depth->zclear) return PCL_EINVAL;
+        a.zbuf = depth->zbuf;
+        pcl_loss_args_zclear(&a, depth, nblk);
+    }
+    const bool sets = color_sets > 1;
+    const dim3 grid(nblk), blk(PCL_BLOCK);
+    pcl_with_G_fmt<2>(G, pano_format, [&](auto g, auto fmt) {
+        constexpr int GG = decltype(g)::value, FMT = decltype(fmt)::value;
+        if (dtab) {
+            if (sets) hipLaunchKernelGGL((pcl_loss_rooms_sets_depth_kernel<GG, FMT>), grid, blk, 0, s, a, rooms, dtab);
+            else hipLaunchKernelGGL((pcl_loss_rooms_depth_kernel<GG, FMT>), grid, blk, 0, s, a, rooms, dtab);
+        } else if (sets) {
+            if (fuse) hipLaunchKernelGGL((pcl_loss_fused_rooms_sets_kernel<GG, FMT>), grid, blk, 0, s, a, *fuse, rooms);
+            else hipLaunchKernelGGL((pcl_loss_rooms_sets_kernel<GG, FMT>), grid, blk, 0, s, a, rooms);
+        } else {
+            if (fuse) hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<GG, FMT>), grid, blk, 0, s, a, *fuse, rooms);
+            else hipLaunchKernelGGL((pcl_loss_rooms_kernel<GG, FMT>), grid, blk, 0, s, a, rooms);
+        }
+    });
+    PCL_LAUNCH_CHECK();
+    return 0;
 }
 
 // Enqueue one fused loss(+grad) pass over the cloud for B poses; partials must hold pcl_partials_bytes(n, B).
-template <int FMT>
-static void pcl_launch_fused(const PclLossArgs& a, const PclFuseArgs& f, int G, int nblk, hipStream_t s)
-{
-    if (G == 4) hipLaunchKernelGGL((pcl_loss_fused_kernel<4, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, f);
-    else if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_kernel<2, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, f);
-    else hipLaunchKernelGGL((pcl_loss_fused_kernel<1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, f);
-}
-
-template <int FMT>
-static void pcl_launch_sets(const PclLossArgs& a, const PclFuseArgs* f, int G, int nblk, hipStream_t s)
-{
-    if (f) {
-        if (G == 4) hipLaunchKernelGGL((pcl_loss_fused_sets_kernel<4, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, *f);
-        else if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_sets_kernel<2, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, *f);
-        else hipLaunchKernelGGL((pcl_loss_fused_sets_kernel<1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, *f);
-    } else {
-        if (G == 4) hipLaunchKernelGGL((pcl_loss_sets_kernel<4, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-        else if (G == 2) hipLaunchKernelGGL((pcl_loss_sets_kernel<2, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((pcl_loss_sets_kernel<1, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
-    }
-}
-
-// The loss pass of a multi-room chain (pcl_gd_run_rooms): nblk blocks, every room's cloud, plan, pose range and partials region from the
-// device room table `rooms`; `poses` / `partials` (and the buffers of `fuse`) are the bases of all rooms.  Gradient pass, no mask.
-// color_sets > 1 (pcl_gd_run_rooms_images): every room's cloud holds that many colour sets and every pose record names its own.
-template <int G, int FMT>
-static void pcl_launch_rooms_sets(const PclLossArgs& a, const PclFuseArgs* f, const PclRoomTable* rooms, int nblk, hipStream_t s)
-{
-    if (f) hipLaunchKernelGGL((pcl_loss_fused_rooms_sets_kernel<G, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, *f, rooms);
-    else hipLaunchKernelGGL((pcl_loss_rooms_sets_kernel<G, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, rooms);
-}
-
-int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, int G,
-                          int ngroups, int nblk, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, int color_sets)
-{
-    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;
-    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
-    PclLossArgs a = PclLossArgs{};
-    a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
-    a.poses = poses; a.B = B; a.partials = partials;
-    a.ngroups = ngroups; a.flip = flip & 1; a.xcd_groups = 0; a.color_sets = color_sets > 1 ? color_sets : 1;
-    const dim3 grid(nblk), blk(PCL_BLOCK);
-    if (color_sets > 1) {
-        if (G != 1 && G != 2) return PCL_EINVAL;
-        if (pano_format == PCL_PANO_U8) {
-            if (G == 2) pcl_launch_rooms_sets<2, PCL_PANO_U8>(a, fuse, rooms, nblk, s);
-            else pcl_launch_rooms_sets<1, PCL_PANO_U8>(a, fuse, rooms, nblk, s);
-        } else if (pano_format == PCL_PANO_F16) {
-            if (G == 2) pcl_launch_rooms_sets<2, PCL_PANO_F16>(a, fuse, rooms, nblk, s);
-            else pcl_launch_rooms_sets<1, PCL_PANO_F16>(a, fuse, rooms, nblk, s);
-        } else {
-            if (G == 2) pcl_launch_rooms_sets<2, PCL_PANO_F32>(a, fuse, rooms, nblk, s);
-            else pcl_launch_rooms_sets<1, PCL_PANO_F32>(a, fuse, rooms, nblk, s);
-        }
-        PCL_LAUNCH_CHECK();
-        return 0;
-    }
-    if (fuse) {
-        if (pano_format == PCL_PANO_U8) {
-            if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<2, PCL_PANO_U8>), grid, blk, 0, s, a, *fuse, rooms);
-            else hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<1, PCL_PANO_U8>), grid, blk, 0, s, a, *fuse, rooms);
-        } else if (pano_format == PCL_PANO_F16) {
-            if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<2, PCL_PANO_F16>), grid, blk, 0, s, a, *fuse, rooms);
-            else hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<1, PCL_PANO_F16>), grid, blk, 0, s, a, *fuse, rooms);
-        } else {
-            if (G == 2) hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<2, PCL_PANO_F32>), grid, blk, 0, s, a, *fuse, rooms);
-            else hipLaunchKernelGGL((pcl_loss_fused_rooms_kernel<1, PCL_PANO_F32>), grid, blk, 0, s, a, *fuse, rooms);
-        }
-    } else {
-        if (pano_format == PCL_PANO_U8) {
-            if (G == 2) hipLaunchKernelGGL((pcl_loss_rooms_kernel<2, PCL_PANO_U8>), grid, blk, 0, s, a, rooms);
-            else hipLaunchKernelGGL((pcl_loss_rooms_kernel<1, PCL_PANO_U8>), grid, blk, 0, s, a, rooms);
-        } else if (pano_format == PCL_PANO_F16) {
-            if (G == 2) hipLaunchKernelGGL((pcl_loss_rooms_kernel<2, PCL_PANO_F16>), grid, blk, 0, s, a, rooms);
-            else hipLaunchKernelGGL((pcl_loss_rooms_kernel<1, PCL_PANO_F16>), grid, blk, 0, s, a, rooms);
-        } else {
-            if (G == 2) hipLaunchKernelGGL((pcl_loss_rooms_kernel<2, PCL_PANO_F32>), grid, blk, 0, s, a, rooms);
-            else hipLaunchKernelGGL((pcl_loss_rooms_kernel<1, PCL_PANO_F32>), grid, blk, 0, s, a, rooms);
-        }
-    }
-    PCL_LAUNCH_CHECK();
-    return 0;
-}
-
-// The loss pass of a depth-masked multi-room chain (pcl_gd_run_depth_chain): as pcl_launch_loss_rooms without a fused form; every room's
-// grid and z-buffer region come from the device depth table `dtab`, `zbuf` is the base of the z-buffer set this iteration reads and
-// `zclear` the other set (zclear_vec4 16-byte words in all), which the launch resets for the next iteration's z passes.
-template <int G, int FMT>
-static void pcl_launch_rooms_depth(const PclLossArgs& a, const PclRoomTable* rooms, const PclDepthTable* dtab, bool sets, int nblk, hipStream_t s)
-{
-    if (sets) hipLaunchKernelGGL((pcl_loss_rooms_sets_depth_kernel<G, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, rooms, dtab);
-    else hipLaunchKernelGGL((pcl_loss_rooms_depth_kernel<G, FMT>), dim3(nblk), dim3(PCL_BLOCK), 0, s, a, rooms, dtab);
-}
-
-int pcl_launch_loss_rooms_depth(const PclRoomTable* rooms, const PclDepthTable* dtab, const void* pano, int pano_format, int H, int W,
-                                const PclPoseRec* poses, int B, int G, int ngroups, int nblk, float* partials, hipStream_t s, int flip, int color_sets,
-                                const uint32_t* zbuf, uint32_t* zclear, int64_t zclear_vec4)
-{
-    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;
-    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
-    if ((G != 1 && G != 2) || !zbuf || !zclear || nblk <= 0) return PCL_EINVAL;
-    PclLossArgs a = PclLossArgs{};
-    a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
-    a.poses = poses; a.B = B; a.partials = partials;
-    a.ngroups = ngroups; a.flip = flip & 1; a.xcd_groups = 0; a.color_sets = color_sets > 1 ? color_sets : 1;
-    a.zbuf = zbuf;
-    a.zclear = (pcl_i4*)zclear; a.zclear_total = zclear_vec4; a.zclear_per_block = (int)((zclear_vec4 + nblk - 1) / nblk);
-    const bool sets = color_sets > 1;
-    if (pano_format == PCL_PANO_U8) {
-        if (G == 2) pcl_launch_rooms_depth<2, PCL_PANO_U8>(a, rooms, dtab, sets, nblk, s);
-        else pcl_launch_rooms_depth<1, PCL_PANO_U8>(a, rooms, dtab, sets, nblk, s);
-    } else if (pano_format == PCL_PANO_F16) {
-        if (G == 2) pcl_launch_rooms_depth<2, PCL_PANO_F16>(a, rooms, dtab, sets, nblk, s);
-        else pcl_launch_rooms_depth<1, PCL_PANO_F16>(a, rooms, dtab, sets, nblk, s);
-    } else {
-        if (G == 2) pcl_launch_rooms_depth<2, PCL_PANO_F32>(a, rooms, dtab, sets, nblk, s);
-        else pcl_launch_rooms_depth<1, PCL_PANO_F32>(a, rooms, dtab, sets, nblk, s);
-    }
-    PCL_LAUNCH_CHECK();
-    return 0;
-}
-
 // `fuse` (nullable): finish the previous GD iteration in the prologue of every block (gradient pass without visibility only)
 // `depth` (nullable): the poses' z-buffers and their grid — the scatter-min depth mask looked up inside the kernel (VIS == 2)
 // `color_sets` > 1: the cloud holds that many colour sets (pcl_cloud_pack_sets), the poses are color_sets images of B / color_sets
@@ -716,31 +647,23 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
                     int B, bool grad, const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse,
                     const PclDepthLook* depth, int color_sets)
 {
-    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;
-    // 32-bit buffer addressing: 6 planes x 4 B x n must stay below 4 GiB, the padded panorama below 2 GiB
-    if (n > PCL_MAX_POINTS || (int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    PclLossArgs a;
+    int rc = pcl_loss_args(&a, pano, pano_format, H, W, poses, B, partials, flip, color_sets);
+    if (rc) return rc;
+    if (n > PCL_MAX_POINTS) return PCL_EINVAL;                        // 32-bit buffer addressing: 6 planes x 4 B x n must stay below 4 GiB
     const bool sets = color_sets > 1;
     if (sets && (B % color_sets || !grad || visible || depth || pcl_cloud_sets_bytes(n, color_sets) == 0)) return PCL_EINVAL;
-    PclPlan p = pcl_plan_sets(n, B, color_sets);
-    PclLossArgs a;
+    const PclPlan p = pcl_plan_sets(n, B, color_sets);
+    const int nblk = p.nchunks * p.ngroups;
     a.cloud = cloud; a.n = n; a.stride = pcl_cloud_stride(n);
-    a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
-    a.poses = poses; a.B = B; a.visible = visible; a.partials = partials;
-    a.zbuf = nullptr; a.dgrid = PclDepthGrid{};
-    a.zclear = nullptr; a.zclear_per_block = 0; a.zclear_total = 0;
+    a.visible = visible;
     if (depth) {
         if (visible || !depth->zbuf || depth->grid.Hd <= 0 || depth->grid.Wd <= 0) return PCL_EINVAL;
         if ((int64_t)B * depth->grid.Hd * depth->grid.Wd * 4 >= ((int64_t)1 << 32)) return PCL_EINVAL;     // one 32-bit buffer descriptor
         a.zbuf = depth->zbuf; a.dgrid = depth->grid;
-        if (depth->zclear) {
-            const int64_t nblk64 = (int64_t)p.nchunks * p.ngroups;
-            a.zclear = (pcl_i4*)depth->zclear;
-            a.zclear_total = depth->zclear_vec4;
-            a.zclear_per_block = (int)((depth->zclear_vec4 + nblk64 - 1) / nblk64);
-        }
+        if (depth->zclear) pcl_loss_args_zclear(&a, depth, nblk);
     }
-    a.nchunks = p.nchunks; a.ngroups = p.ngroups; a.seg_len = p.seg_len; a.flip = flip & 1; a.steps_base = p.steps_base; a.steps_rem = p.steps_rem;
-    a.color_sets = sets ? color_sets : 1;
+    a.nchunks = p.nchunks; a.ngroups = p.ngroups; a.seg_len = p.seg_len; a.steps_base = p.steps_base; a.steps_rem = p.steps_rem;
     // bit 1 of `flip`: the poses of this launch read several panoramas (pcl_gd_hyper.images > 1) — the XCDs split the pose groups
     // instead of the chunks when they divide evenly.  Measured per iteration (tools/iter_latency.py, ITER_IMAGES=8): 167k points x 48
     // candidates of 8 images 64.0 -> 49.8 us (poses all over the room) / 51.3 -> 41.7 us (near the ground truth), 1M points x 256
@@ -748,26 +671,25 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
     // PCL_XCD_GROUPS=0 / 1 forces the mapping off / on (A/B).
     static const int xg_env = PCL_KNOB(XCD_GROUPS, -1);
     a.xcd_groups = ((flip & 2) != 0 || xg_env == 1) && xg_env != 0 && p.ngroups % 8 == 0 ? 1 : 0;
-    int nblk = p.nchunks * p.ngroups;
     const int vis = depth ? 2 : visible != nullptr ? 1 : 0;
-    if (sets) {
-        if (pano_format == PCL_PANO_U8) pcl_launch_sets<PCL_PANO_U8>(a, fuse, p.G, nblk, s);
-        else if (pano_format == PCL_PANO_F16) pcl_launch_sets<PCL_PANO_F16>(a, fuse, p.G, nblk, s);
-        else pcl_launch_sets<PCL_PANO_F32>(a, fuse, p.G, nblk, s);
-        PCL_LAUNCH_CHECK();
-        return 0;
-    }
-    if (fuse) {
-        if (!grad || vis) return PCL_EINVAL;
-        if (pano_format == PCL_PANO_U8) pcl_launch_fused<PCL_PANO_U8>(a, *fuse, p.G, nblk, s);
-        else if (pano_format == PCL_PANO_F16) pcl_launch_fused<PCL_PANO_F16>(a, *fuse, p.G, nblk, s);
-        else pcl_launch_fused<PCL_PANO_F32>(a, *fuse, p.G, nblk, s);
-        PCL_LAUNCH_CHECK();
-        return 0;
-    }
-    if (pano_format == PCL_PANO_U8) pcl_launch_f<PCL_PANO_U8>(a, p.G, nblk, grad, vis, s);
-    else if (pano_format == PCL_PANO_F16) pcl_launch_f<PCL_PANO_F16>(a, p.G, nblk, grad, vis, s);
-    else pcl_launch_f<PCL_PANO_F32>(a, p.G, nblk, grad, vis, s);
+    if (fuse && (!grad || vis)) return PCL_EINVAL;
+    const dim3 grid(nblk), blk(PCL_BLOCK);
+    pcl_with_G_fmt<4>(p.G, pano_format, [&](auto g, auto fmt) {
+        constexpr int GG = decltype(g)::value, FMT = decltype(fmt)::value;
+        if (sets) {
+            if (fuse) hipLaunchKernelGGL((pcl_loss_fused_sets_kernel<GG, FMT>), grid, blk, 0, s, a, *fuse);
+            else hipLaunchKernelGGL((pcl_loss_sets_kernel<GG, FMT>), grid, blk, 0, s, a);
+        } else if (fuse) hipLaunchKernelGGL((pcl_loss_fused_kernel<GG, FMT>), grid, blk, 0, s, a, *fuse);
+        else if (grad) {
+            if (vis == 2) hipLaunchKernelGGL((pcl_loss_kernel<GG, true, 2, FMT>), grid, blk, 0, s, a);
+            else if (vis) hipLaunchKernelGGL((pcl_loss_kernel<GG, true, 1, FMT>), grid, blk, 0, s, a);
+            else hipLaunchKernelGGL((pcl_loss_kernel<GG, true, 0, FMT>), grid, blk, 0, s, a);
+        } else {
+            if (vis == 2) hipLaunchKernelGGL((pcl_loss_kernel<GG, false, 2, FMT>), grid, blk, 0, s, a);
+            else if (vis) hipLaunchKernelGGL((pcl_loss_kernel<GG, false, 1, FMT>), grid, blk, 0, s, a);
+            else hipLaunchKernelGGL((pcl_loss_kernel<GG, false, 0, FMT>), grid, blk, 0, s, a);
+        }
+    });
     PCL_LAUNCH_CHECK();
     return 0;
 }

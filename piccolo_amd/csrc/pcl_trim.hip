@@ -25,6 +25,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "pcl_host.h"
 #include "pcl_sample_device.h"
 
 #define PCL_TRIM_Y 4        // yaws evaluated per loaded point pair (partials row = PCL_TRIM_Y x {sum ||d||, count} = PCL_NACC floats)
@@ -48,8 +49,6 @@ struct PclTrimHeader {
     int pad[30];
 };
 static_assert(sizeof(PclTrimHeader) == 128, "trim groups header");
-
-void pcl_plan_for_groups(int64_t n, int ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
 
 // ---------------------------------------------------------------- classes of the rotation table (one block)
 // R = RZ(yaw) RY(pitch) RX(roll) in double from the fp32 angles
