@@ -93,6 +93,20 @@ int pcl_cloud_pack(const float *xyz, const float *rgb, const int64_t *order, int
  * PCL_EINVAL: the caller splits its images into groups. */
 size_t pcl_cloud_sets_bytes(int64_t n, int nsets);
 int pcl_cloud_pack_sets(const float *xyz, const float *const *rgb_host, int nsets, const int64_t *order, int64_t n, float *cloud, void *stream);
+/* Per-point weights (build-defined: the reference has none and treats every point alike).  A cloud may carry ONE weight per point, w_i >= 0
+ * and finite, shared by all poses of a call, in a plane of its own: pcl_cloud_stride(n) floats in the PACKED point order,
+ * plane[s] = w[order ? order[s] : s] with `order` the one given to pcl_cloud_pack, padding slots 0.  pcl_cloud_weights_bytes(n) is its size
+ * (0 for n <= 0 or n > PCL_MAX_POINTS).  pcl_cloud_pack_weights sets *bad (device int, caller zeroes it) if some weight is negative, NaN or
+ * infinite: the plane must then not be used.  The plane's address is the caller's: re-packing into the same buffer changes the weights
+ * that a captured graph of pcl_gd_run_weighted reads.  With weights
+ *   loss_b      = sum_i w_i m_bi ||c_bi - rgb_i|| / sum_i w_i m_bi             (0/0 -> NaN, as for an empty mask)
+ *   grad loss_b = sum_i w_i m_bi grad ||c_bi - rgb_i|| / sum_i w_i m_bi        (m is piecewise constant, as in the reference's autograd)
+ *   result[1] ("count") = sum_i w_i m_bi                                       (a float; the point count when w = 1)
+ * Unit weights give the unweighted results bit for bit, 0/1 weights those of the same byte mask `visible`.
+ * Deliberately left out: weights in the initialisation stage (pcl_trim_*, pcl_hist_trim_*), in the rooms / images / colour-set chains and
+ * under the depth mask, and any built-in source of weights (density, semantics, change detection) — the caller brings them. */
+size_t pcl_cloud_weights_bytes(int64_t n);
+int pcl_cloud_pack_weights(const float *w, const int64_t *order, int64_t n, float *plane, int32_t *bad, void *stream);
 /* The Morton order in one call, entirely on the device: bounding box, 63-bit keys, stable radix sort of (key, index);
  * order[i] = index of the point for packed slot i.  workspace: pcl_cloud_order_workspace_bytes(n). */
 size_t pcl_cloud_order_workspace_bytes(int64_t n);
@@ -133,6 +147,11 @@ int pcl_sampling_loss_depth(const float *cloud, int64_t n, const void *pano, int
 int pcl_sampling_loss(const float *cloud, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans,
                       const float *rot, int B, int with_grad, const uint8_t *visible, float *result, void *workspace,
                       size_t workspace_bytes, void *stream);
+/* pcl_sampling_loss over a cloud with per-point weights (`weights`: the plane of pcl_cloud_pack_weights; definitions above).  The same
+ * launch plan as pcl_sampling_loss plus one plane; workspace: pcl_loss_workspace_bytes(n, B).  No byte mask, no depth mask. */
+int pcl_sampling_loss_weighted(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W,
+                               const float *trans, const float *rot, int B, int with_grad, float *result, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /* ---- gradient-descent refinement ---------------------------------------------------------------------------
  * Replaces the optimisation loops of omniloc (omniloc.py:44-58) and omniloc_batch (omniloc.py:249-269): per
@@ -192,6 +211,13 @@ int pcl_gd_init(void *state, const float *trans, const float *rot, int B, const 
 int pcl_gd_run(const float *cloud, int64_t n, const void *pano, int pano_format, int H, int W, void *state, int B, const float *box,
                const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace,
                size_t workspace_bytes, void *timer, void *stream);
+/* pcl_gd_run over a cloud with per-point weights (`weights`: the plane of pcl_cloud_pack_weights).  State, workspace
+ * (pcl_gd_workspace_bytes), pcl_gd_init / _result / _winner / _set_pano_groups and pcl_gd_plan are pcl_gd_run's: the same chunks, poses
+ * per block and fuse rule (hyper->fuse), one more plane per loss block, capturable alike.  PCL_EINVAL with hyper->depth_mask or
+ * hyper->color_sets > 1. */
+int pcl_gd_run_weighted(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, void *state, int B,
+                        const float *box, const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace,
+                        size_t workspace_bytes, void *timer, void *stream);
 int pcl_gd_result(const void *state, int B, float *result, void *stream);
 /* Teacher-forcing hook (parity tests): ONE optimiser step of every candidate from a GIVEN loss [B] and
  * gradient [B][6] = dL/d(t0, t1, t2, yaw, pitch, roll) — e.g. the reference's recorded loss_list and autograd gradients

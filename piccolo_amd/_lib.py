@@ -42,6 +42,8 @@ SIGNATURES = {
     "pcl_cloud_pack": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "pcl_cloud_sets_bytes": (_sz, [_i64, _int]),
     "pcl_cloud_pack_sets": (_int, [_vp, _c.POINTER(_vp), _int, _vp, _i64, _vp, _vp]),
+    "pcl_cloud_weights_bytes": (_sz, [_i64]),
+    "pcl_cloud_pack_weights": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "pcl_morton_keys": (_int, [_vp, _i64, _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _vp, _vp]),
     "pcl_pano_bytes": (_sz, [_int, _int, _int]),
     "pcl_pano_pack": (_int, [_vp, _int, _int, _vp, _vp]),
@@ -53,6 +55,7 @@ SIGNATURES = {
     "pcl_pano_pack_f16": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "pcl_loss_workspace_bytes": (_sz, [_i64, _int]),
     "pcl_sampling_loss": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "pcl_sampling_loss_weighted": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _sz, _vp]),
     "pcl_loss_depth_workspace_bytes": (_sz, [_i64, _int, _int, _int, _int, _int, _int]),
     "pcl_sampling_loss_depth": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _int, _c.c_float, _int, _vp, _vp, _sz, _vp]),
     "pcl_depth_default": (_int, [_i64, _int, _int, _int, _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_c.c_float), _c.POINTER(_int)]),
@@ -92,6 +95,7 @@ SIGNATURES = {
     "pcl_depth_mask": (_int, [_vp, _i64, _vp, _vp, _int, _int, _int, _c.c_float, _int, _vp, _vp, _sz, _vp]),
     "pcl_gd_init": (_int, [_vp, _vp, _vp, _int, _c.POINTER(GdHyper), _vp]),
     "pcl_gd_run": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _int, _vp, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
+    "pcl_gd_run_weighted": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _int, _vp, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
     "pcl_timer_create": (_vp, [_int]),
     "pcl_timer_destroy": (None, [_vp]),
     "pcl_timer_reset": (None, [_vp]),

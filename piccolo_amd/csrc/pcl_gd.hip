@@ -111,9 +111,10 @@ extern "C" size_t pcl_loss_depth_workspace_bytes(int64_t n, int B, int H, int W,
 }
 
 // pose records, (with a grid: fill + z pass, pcl_depth.hip,) loss launch, finish; the workspace is sized from the grid the caller RESOLVED
+// `weights` (nullable): the cloud's weight plane (pcl_sampling_loss_weighted; neither `visible` nor a grid with it)
 static int gd_stateless_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans, const float* rot, int B,
                              int with_grad, const uint8_t* visible, const PclDepthGrid* grid, int zstride, float* result, void* workspace,
-                             size_t workspace_bytes, hipStream_t s)
+                             size_t workspace_bytes, hipStream_t s, const float* weights = nullptr)
 {
     GdLossWs w;
     if (workspace_bytes < gd_loss_layout(workspace, n, B, grid, &w)) return PCL_EWORKSPACE;
@@ -125,7 +126,8 @@ static int gd_stateless_loss(const float* cloud, int64_t n, const void* pano, in
         int rc = pcl_launch_zbuffers(cloud, n, w.recs, B, *grid, zstride, w.zbuf, true, s);
         if (rc) return rc;
     }
-    int rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, w.recs, B, with_grad != 0, visible, w.partials, s, 0, nullptr, grid ? &look : nullptr);
+    int rc = pcl_launch_loss(cloud, n, pano, pano_format, H, W, w.recs, B, with_grad != 0, visible, w.partials, s, 0, nullptr, grid ? &look : nullptr, 1,
+                             weights);
     if (rc) return rc;
     const int nch = pcl_plan_nchunks(n, B);
     pcl_with_G<4>(pcl_plan_G(n, B), [&](auto g) {
@@ -144,6 +146,17 @@ extern "C" int pcl_sampling_loss(const float* cloud, int64_t n, const void* pano
     if (n > PCL_MAX_POINTS) return PCL_EINVAL;               // (before anything is enqueued)
     return gd_stateless_loss(cloud, n, pano, pano_format, H, W, trans, rot, B, with_grad, visible, nullptr, 1, result, workspace, workspace_bytes,
                              (hipStream_t)stream);
+}
+
+// pcl_sampling_loss over a cloud with per-point weights: loss = sum w m ||d|| / sum w m, the count column sum w m (include/piccolo_hip.h)
+extern "C" int pcl_sampling_loss_weighted(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W,
+                                          const float* trans, const float* rot, int B, int with_grad, float* result, void* workspace,
+                                          size_t workspace_bytes, void* stream)
+{
+    if (!cloud || !weights || !pano || !trans || !rot || !result || !workspace || n <= 0 || B <= 0 || H <= 0 || W <= 0) return PCL_EINVAL;
+    if (!pcl_weighted_plan_ok(n, B)) return PCL_EINVAL;                  // (before anything is enqueued)
+    return gd_stateless_loss(cloud, n, pano, pano_format, H, W, trans, rot, B, with_grad, nullptr, nullptr, 1, result, workspace, workspace_bytes,
+                             (hipStream_t)stream, weights);
 }
 
 // pcl_sampling_loss with the scatter-min depth mask of the SAME poses multiplied into the mask: the loss launch looks every point's
@@ -357,9 +370,10 @@ static int gd_chain_loop(void* state, int B, bool fused, const float* box, const
     return 0;
 }
 
-extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, void* state, int B,
-                          const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history,
-                          void* workspace, size_t workspace_bytes, void* timer, void* stream)
+// pcl_gd_run, and with `weights` (the cloud's weight plane) pcl_gd_run_weighted: the same plan, workspace and chain, the weighted loss launch
+static int gd_run(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, void* state, int B,
+                  const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace, size_t workspace_bytes,
+                  void* timer, void* stream)
 {
     if (!gd_run_args_ok(cloud, pano, state, hyper_host, workspace, H, W, num_iter) || !box || n <= 0 || n > PCL_MAX_POINTS || B <= 0) return PCL_EINVAL;
     // colour sets: `cloud` holds hyper->color_sets of them (pcl_cloud_pack_sets) and candidate b reads set b / (B / color_sets), as
@@ -406,7 +420,7 @@ extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int p
         },
         [&](int it, const PclPoseRec* recs, float* partials, const PclFuseArgs* fuse) {
             return pcl_launch_loss(cloud, n, pano, pano_format, H, W, recs, B, true, nullptr, partials, s, (flip_env ? (it & 1) : 0) | xcd_bit, fuse,
-                                   depth_on ? &look : nullptr, sets);
+                                   depth_on ? &look : nullptr, sets, weights);
         },
         [&](int copy_in, const float* partials, float* loss_out) {
             pcl_with_G<4>(G, [&](auto g) {
@@ -416,6 +430,24 @@ extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int p
                                    (int)hyper_host->patience, (int)hyper_host->mode, loss_out);
             });
         });
+}
+
+extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, void* state, int B,
+                          const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history,
+                          void* workspace, size_t workspace_bytes, void* timer, void* stream)
+{
+    return gd_run(cloud, nullptr, n, pano, pano_format, H, W, state, B, box, hyper_host, num_iter, loss_history, workspace, workspace_bytes, timer, stream);
+}
+
+// pcl_gd_run over a cloud with per-point weights: one more caller of the chain loop, with the weighted loss launch (fused or not by the
+// same rule); neither the depth mask nor colour sets
+extern "C" int pcl_gd_run_weighted(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, void* state,
+                                   int B, const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace,
+                                   size_t workspace_bytes, void* timer, void* stream)
+{
+    if (!weights || !hyper_host || hyper_host->depth_mask || hyper_host->color_sets > 1) return PCL_EINVAL;
+    if (!pcl_weighted_plan_ok(n, B)) return PCL_EINVAL;                  // (before the state is touched)
+    return gd_run(cloud, weights, n, pano, pano_format, H, W, state, B, box, hyper_host, num_iter, loss_history, workspace, workspace_bytes, timer, stream);
 }
 
 // ---------------------------------------------------------------- room search: several clouds in one chain

@@ -85,6 +85,10 @@ extern "C" int pcl_debug_stamp(unsigned long long* slot, void* stream)
 // RM with VIS == 2 (pcl_gd_run_depth_chain): the room also has its own z-buffer grid and its own region of the z-buffer set — the block
 // takes them from the depth table (uniform loads) and counts its poses' z-buffers inside the room; the slice of the OTHER set it resets
 // stays indexed by the launch's block index over the whole set.
+// WT: per-point weights (pcl_sampling_loss_weighted, pcl_gd_run_weighted; build-defined, the reference has none).  The block reads one
+// more plane, pcl_cloud_stride(n) floats in the packed point order (pcl_cloud_pack_weights), through a buffer resource of its own with the
+// lane offsets of the cloud's planes — shared by the block's G poses — and pcl_sample2 folds the weight into 1 / ||d|| and sums the kept
+// weights into the count slot.  VIS = 0, no CS, no RM.  A template parameter once more: the instances without it are unchanged.
 template <int G, bool FUSED>
 __device__ __forceinline__ unsigned pcl_room_select(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* __restrict__ tb, PclLossArgs& a,
                                                     PclFuseArgs& f)
@@ -115,10 +119,11 @@ __device__ __forceinline__ unsigned pcl_room_select(const PclLossArgs& a_in, con
     return blockIdx.x - (unsigned)pcl_rfl(rm->block0);           // (block0 is a multiple of 8: the XCD of a block is unchanged)
 }
 
-template <int G, bool GRAD, int VIS, int FMT, bool FUSED, bool CS = false, bool RM = false>
+template <int G, bool GRAD, int VIS, int FMT, bool FUSED, bool CS = false, bool RM = false, bool WT = false>
 __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* rooms = nullptr,
-                                              const PclDepthTable* __restrict__ dtab = nullptr)
+                                              const PclDepthTable* __restrict__ dtab = nullptr, const float* wts = nullptr)
 {
+    static_assert(!WT || (VIS == 0 && !CS && !RM), "weights: the plain loss only");
     PclLossArgs a_rm;
     PclFuseArgs f_rm;
     unsigned bid = blockIdx.x;
@@ -179,6 +184,9 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const Pcl
     if constexpr (CS) cplane = (int)(3u + 3u * (unsigned)__builtin_amdgcn_readfirstlane((int)(a.poses + pose0)->cset)) * plane;
     __amdgpu_buffer_rsrc_t zb = __amdgpu_buffer_rsrc_t();
     if constexpr (VIS == 2) zb = __builtin_amdgcn_make_buffer_rsrc((void*)a.zbuf, 0, (int)((unsigned)a.B * (unsigned)(a.dgrid.last + 1) * 4u), 0x00020000);
+    __amdgpu_buffer_rsrc_t wrs = __amdgpu_buffer_rsrc_t();
+    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wts, 0, (int)(a.stride * 4), 0x00020000);
+    constexpr int NPL = WT ? 7 : 6;               // values per point: the cloud's six planes (+ its weight)
 
     f2 acc[G][PCL_NACC];
     int count[G];
@@ -210,7 +218,7 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const Pcl
     // two points per lane: i0 = base + tid, i1 = base + 256 + tid.  The loop is unrolled by two with ping-pong register
     // sets: the loads of step k+1 are issued before step k is evaluated (their L2 latency hides under ~450 VALU
     // instructions) and no register copies are needed to rotate the buffers.
-    auto load_step = [&](int base, float (&dst)[2][6]) {
+    auto load_step = [&](int base, float (&dst)[2][NPL]) {
         int j0 = min(base + (int)threadIdx.x, last), j1 = min(base + PCL_BLOCK + (int)threadIdx.x, last);
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -218,8 +226,12 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const Pcl
             dst[0][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j0 * 4, soff, 0));
             dst[1][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(cld, j1 * 4, soff, 0));
         }
+        if constexpr (WT) {
+            dst[0][NPL - 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, j0 * 4, 0, 0));
+            dst[1][NPL - 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, j1 * 4, 0, 0));
+        }
     };
-    auto eval_step = [&](int base, const float (&src)[2][6]) {
+    auto eval_step = [&](int base, const float (&src)[2][NPL]) {
         const int i0 = base + threadIdx.x, i1 = i0 + PCL_BLOCK;
         const bool valid0 = i0 < end, valid1 = i1 < end;
         const unsigned long long vmask0 = __builtin_amdgcn_ballot_w64(valid0), vmask1 = __builtin_amdgcn_ballot_w64(valid1);
@@ -290,10 +302,11 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const Pcl
                 ok0 = ok0 & v0; ok1 = ok1 & v1;
                 m0 = __builtin_amdgcn_ballot_w64(ok0); m1 = __builtin_amdgcn_ballot_w64(ok1);
             }
-            pcl_sample2<GRAD, FMT>(pj, ncr, ncg, ncb, ok0, ok1, m0, m1, tg, a.dims, acc[g], count[g]);
+            if constexpr (WT) pcl_sample2<GRAD, FMT, true>(pj, ncr, ncg, ncb, ok0, ok1, m0, m1, tg, a.dims, acc[g], count[g], (f2){src[0][NPL - 1], src[1][NPL - 1]});
+            else pcl_sample2<GRAD, FMT>(pj, ncr, ncg, ncb, ok0, ok1, m0, m1, tg, a.dims, acc[g], count[g]);
         }
     };
-    float bufA[2][6], bufB[2][6];
+    float bufA[2][NPL], bufB[2][NPL];
     load_step(begin, bufA);                            // (in flight while a fused block finishes the previous iteration)
     if constexpr (FUSED) {
         static_assert(PCL_BLOCK == PCL_GD_THREADS, "the fused prologue reduces with the epilogue kernel's thread layout");
@@ -331,7 +344,7 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const Pcl
     for (int g = 0; g < G; g++)
 #pragma unroll
         for (int k = 0; k < PCL_NACC; k++) {
-            if (k == 1) {
+            if (k == 1 && !WT) {                                                // (WT: slot 1 is a per-lane sum like the others)
                 if (lane == 0) red[wave][g * PCL_NACC + 1] = (float)count[g];   // wave-uniform popcount total
                 continue;
             }
@@ -420,6 +433,20 @@ template <int G, int FMT>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_rooms_sets_kernel(PclLossArgs a, PclFuseArgs f, const PclRoomTable* rooms)
 {
     pcl_loss_body<G, true, 0, FMT, true, true, true>(a, f, rooms);
+}
+
+// per-point weights (pcl_sampling_loss_weighted, pcl_gd_run_weighted): the plain loss with one more plane.  The plane is a kernel argument
+// of its own, after the others, and the kernels have their own names: the instances above keep their argument layout and theirs.
+template <int G, bool GRAD, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_wt_kernel(PclLossArgs a, const float* weights)
+{
+    pcl_loss_body<G, GRAD, 0, FMT, false, false, false, true>(a, PclFuseArgs{}, nullptr, nullptr, weights);
+}
+
+template <int G, int FMT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_wt_kernel(PclLossArgs a, PclFuseArgs f, const float* weights)
+{
+    pcl_loss_body<G, true, 0, FMT, true, false, false, true>(a, f, nullptr, nullptr, weights);
 }
 
 // the depth mask inside a multi-room chain (pcl_gd_run_depth_chain): RM (+ CS) with VIS = 2, two launches per iteration only.  The depth
@@ -643,9 +670,11 @@ int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_
 // `depth` (nullable): the poses' z-buffers and their grid — the scatter-min depth mask looked up inside the kernel (VIS == 2)
 // `color_sets` > 1: the cloud holds that many colour sets (pcl_cloud_pack_sets), the poses are color_sets images of B / color_sets
 // candidates, and each pose record names its set (PclPoseRec.cset): the single-image plan (pcl_plan_sets), gradient pass only
+// `weights` (nullable): the cloud's weight plane (pcl_cloud_pack_weights) — the SAME plan, chunks, poses per block, XCD mapping and flip
+// as without it, one more plane per block; not with `visible`, `depth` or colour sets, and no G = 4 instance (experiments build)
 int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses,
                     int B, bool grad, const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse,
-                    const PclDepthLook* depth, int color_sets)
+                    const PclDepthLook* depth, int color_sets, const float* weights)
 {
     PclLossArgs a;
     int rc = pcl_loss_args(&a, pano, pano_format, H, W, poses, B, partials, flip, color_sets);
@@ -653,6 +682,7 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
     if (n > PCL_MAX_POINTS) return PCL_EINVAL;                        // 32-bit buffer addressing: 6 planes x 4 B x n must stay below 4 GiB
     const bool sets = color_sets > 1;
     if (sets && (B % color_sets || !grad || visible || depth || pcl_cloud_sets_bytes(n, color_sets) == 0)) return PCL_EINVAL;
+    if (weights && (visible || depth || sets || !pcl_weighted_plan_ok(n, B))) return PCL_EINVAL;
     const PclPlan p = pcl_plan_sets(n, B, color_sets);
     const int nblk = p.nchunks * p.ngroups;
     a.cloud = cloud; a.n = n; a.stride = pcl_cloud_stride(n);
@@ -674,6 +704,16 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
     const int vis = depth ? 2 : visible != nullptr ? 1 : 0;
     if (fuse && (!grad || vis)) return PCL_EINVAL;
     const dim3 grid(nblk), blk(PCL_BLOCK);
+    if (weights) {
+        pcl_with_G_fmt<2>(p.G, pano_format, [&](auto g, auto fmt) {
+            constexpr int GG = decltype(g)::value, FMT = decltype(fmt)::value;
+            if (fuse) hipLaunchKernelGGL((pcl_loss_fused_wt_kernel<GG, FMT>), grid, blk, 0, s, a, *fuse, weights);
+            else if (grad) hipLaunchKernelGGL((pcl_loss_wt_kernel<GG, true, FMT>), grid, blk, 0, s, a, weights);
+            else hipLaunchKernelGGL((pcl_loss_wt_kernel<GG, false, FMT>), grid, blk, 0, s, a, weights);
+        });
+        PCL_LAUNCH_CHECK();
+        return 0;
+    }
     pcl_with_G_fmt<4>(p.G, pano_format, [&](auto g, auto fmt) {
         constexpr int GG = decltype(g)::value, FMT = decltype(fmt)::value;
         if (sets) {

@@ -111,6 +111,35 @@ extern "C" int pcl_cloud_pack_sets(const float* xyz, const float* const* rgb_hos
     return 0;
 }
 
+// ---- per-point weights (build-defined: the reference has none): one more plane of pcl_cloud_stride(n) floats in the packed point order,
+// plane[s] = w[order ? order[s] : s], padding slots 0.  A buffer of its own, not a seventh plane of the cloud: the cloud keeps its layout,
+// and re-packing into the same buffer changes the weights a captured graph reads.  *bad (device int, caller zeroes it) is set when a
+// weight is negative, NaN or infinite — pcl_pano_pack_u8's not_exact pattern.
+extern "C" size_t pcl_cloud_weights_bytes(int64_t n) { return n <= 0 || n > PCL_MAX_POINTS ? 0 : (size_t)pcl_cloud_stride(n) * sizeof(float); }
+
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_cloud_pack_weights_kernel(const float* __restrict__ w, const int64_t* __restrict__ order, int64_t n,
+                                                                           int64_t stride, float* __restrict__ plane, int32_t* __restrict__ bad)
+{
+    int64_t i = (int64_t)blockIdx.x * PCL_BLOCK + threadIdx.x;
+    if (i >= stride) return;
+    float v = 0.f;
+    if (i < n) {
+        v = w[order ? order[i] : i];
+        if (!(v >= 0.f && v <= 3.402823466e38f)) *bad = 1;               // negative, NaN or infinite
+    }
+    plane[i] = v;
+}
+
+extern "C" int pcl_cloud_pack_weights(const float* w, const int64_t* order, int64_t n, float* plane, int32_t* bad, void* stream)
+{
+    if (!w || !plane || !bad || n <= 0 || n > PCL_MAX_POINTS) return PCL_EINVAL;
+    const int64_t stride = pcl_cloud_stride(n);
+    hipLaunchKernelGGL(pcl_cloud_pack_weights_kernel, dim3((unsigned)(stride / PCL_BLOCK)), dim3(PCL_BLOCK), 0, (hipStream_t)stream, w, order, n,
+                       stride, plane, bad);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
 __device__ inline uint64_t pcl_spread21(uint32_t v)
 {
     uint64_t x = v & 0x1fffffu;

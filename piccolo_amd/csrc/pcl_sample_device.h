@@ -346,10 +346,13 @@ __device__ __forceinline__ void pcl_project2_rotated(__amdgpu_buffer_rsrc_t tex,
 // Phase B: bilinear colour, mask, residual, gradient, accumulate.
 // acc: 0 sum||d||, 1 unused here (count goes to `count`, wave-uniform), 2-4 sum g, 5-7 sum p x g — each an f2 whose
 // halves are added at the end.
-template <bool GRAD, int FMT>
+// WT (per-point weights, build-defined: the reference has none): `w` holds the two points' weights; 1/||d|| becomes w/||d||, which
+// scales the loss term and every gradient term, and acc[1] takes the sum of the kept points' weights instead of the popcount.
+// A template flag like CS / RM of the loss body: the instances without it keep their instruction stream.
+template <bool GRAD, int FMT, bool WT = false>
 __device__ __forceinline__ void pcl_sample2(const PclProj<FMT>& o, f2 ncr, f2 ncg, f2 ncb, bool valid0, bool valid1,
                                             unsigned long long vmask0, unsigned long long vmask1,
-                                            __amdgpu_buffer_rsrc_t tex, const PclDims& dm, f2* acc, int& count)
+                                            __amdgpu_buffer_rsrc_t tex, const PclDims& dm, f2* acc, int& count, f2 w = F2(1.f))
 {
     const f2 px = o.px, py = o.py, pz = o.pz, fx = o.fx, fy = o.fy;
     f2 c[3], dv[3], dtop[3], dbot[3], dhp[3];
@@ -384,6 +387,7 @@ __device__ __forceinline__ void pcl_sample2(const PclProj<FMT>& o, f2 ncr, f2 nc
     float m1 = fmaxf(fmaxf(fabsf(c[0].y), fabsf(c[1].y)), fabsf(c[2].y));
     bool keep0 = valid0 && m0 > 0.f, keep1 = valid1 && m1 > 0.f;
     // the count is wave-uniform bookkeeping: popcount of the compare's lane mask on the scalar unit (FCMP_OGT = 2)
+    if constexpr (!WT)
     count += __builtin_popcountll(__builtin_amdgcn_fcmpf(m0, 0.f, 2) & vmask0) +
              __builtin_popcountll(__builtin_amdgcn_fcmpf(m1, 0.f, 2) & vmask1);
     // d = c - rgb; the packed cloud stores -rgb (pcl_cloud_pack), so this is one fma / add without a negation
@@ -397,6 +401,10 @@ __device__ __forceinline__ void pcl_sample2(const PclProj<FMT>& o, f2 ncr, f2 nc
     // 1/||d|| for kept points, 0 otherwise (also 0 * huge = 0 at ||d|| = 0: norm backward is 0 there)
     f2 ng = n2 + F2(1e-37f);
     f2 rn = {keep0 ? __builtin_amdgcn_rsqf(ng.x) : 0.f, keep1 ? __builtin_amdgcn_rsqf(ng.y) : 0.f};
+    if constexpr (WT) {
+        acc[1] += (f2){keep0 ? w.x : 0.f, keep1 ? w.y : 0.f};                     // sum of the kept points' weights
+        rn = rn * w;                                                              // w / ||d||: one packed multiply, used wherever 1/||d|| is
+    }
     acc[0] = pcl_fma2(n2, rn, acc[0]);                                            // ||d|| = n2 * rsqrt(n2)
     if (GRAD) {
         // d||d||/dc = d / ||d||: the 1/||d|| is folded into the two angle factors instead of scaling d three times

@@ -37,15 +37,15 @@ def preprocess_colors(img, rgb, cfg):
     return new_img, rgb
 
 
-def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=None):
+def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=None, weights=None):
     """localize.py:215-233: run the refinement the config asks for and pick the min-loss candidate.
-    Returns (t (3,1), R (3,3), loss) as cpu tensors."""
+    Returns (t (3,1), R (3,3), loss) as cpu tensors.  weights (not in the reference): (N,) per-point weights of the refinement's loss."""
     summaries = scalar_summaries if scalar_summaries is not None else {}
     if getattr(cfg, "parallel", False):
-        results = [omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, summaries)]
+        results = [omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)]
     else:
         # the reference loops omniloc() over the starting points (localize.py:219-220); same results, one launch chain
-        results = omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, summaries)
+        results = omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)
     best = min(range(len(results)), key=lambda i: float(results[i][2]))
     return results[best][0], results[best][1], results[best][2]
 

@@ -37,7 +37,7 @@ strict_reference_asserts = True
 # cloud, quantile box or translation grid (a dataset loop touches 4 cloud-side entries per room and 2 per image).
 # An entry is keyed by the identity of the tensors it was made from (address, shape, in-place version) and holds weak
 # references to them: a hit needs the very same live tensor, and entries whose tensors died are purged.
-_CAPACITY = {"cloud": 2, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "gd_rooms_images": 4, "trimgroups": 4}
+_CAPACITY = {"cloud": 2, "cloud_w": 2, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "gd_rooms_images": 4, "trimgroups": 4}
 
 
 class _PackCache:
@@ -97,18 +97,25 @@ def quantile_box_of(xyz, out_quantile):
     return _cached("box", (xyz,), lambda: ops.quantile_box(xyz, out_quantile), sub=float(out_quantile))
 
 
-def packed_cloud(xyz, rgb):
+def packed_cloud(xyz, rgb, weights=None):
     """Packed cloud cached per (xyz, rgb); the Morton order is cached per xyz alone, so a cloud whose colours change with
-    every query image (color_mod, localize.py:175-179) is re-packed without being re-sorted."""
+    every query image (color_mod, localize.py:175-179) is re-packed without being re-sorted.  `weights`: (N,) per-point weights in the
+    order of xyz's rows, part of the cache key and kept in an LRU of their own ('cloud_w'): a weighted and an unweighted pack of the same
+    (xyz, rgb) never alias, and neither takes the other's place."""
     def make():
         order = _cache.get("order", (None,) + _key(xyz), (xyz,))
         if order is not None:
-            return ops.Cloud(xyz, rgb, order=order)
-        c = ops.Cloud(xyz, rgb)
+            return ops.Cloud(xyz, rgb, order=order, weights=weights)
+        c = ops.Cloud(xyz, rgb, weights=weights)
         if c.order is not None:
             _cache.put("order", (None,) + _key(xyz), (xyz,), c.order)
         return c
-    return _cached("cloud", (xyz, rgb), make)
+    if weights is None:
+        return _cached("cloud", (xyz, rgb), make)
+    if not torch.is_tensor(weights):
+        raise ValueError("weights must be an (N,) tensor")
+    # (an LRU of their own: make_input packs the room unweighted and the refinement weighted, and the two must not evict each other)
+    return _cached("cloud_w", (xyz, rgb, weights), make)
 
 
 def packed_cloud_sets(xyz, rgbs):
@@ -232,6 +239,8 @@ def _cached_engine(kind, xyzs, sub, make, clouds, boxes):
     for r, (c, b) in enumerate(zip(clouds, boxes)):
         if gd._cloud_src[r]() is not c:
             gd._private[0][r].data.copy_(c.data)
+            if c.weights is not None:                        # (the engine key tells weighted from unweighted: the private cloud has a plane)
+                gd._private[0][r].weights.copy_(c.weights)
             gd._cloud_src[r] = weakref.ref(c)
         if gd._box_src[r] is not b:                          # (the cached box tensor of this cloud: identity is enough)
             gd._private[1][r].copy_(ops._dev(b).reshape(6))
@@ -239,12 +248,17 @@ def _cached_engine(kind, xyzs, sub, make, clouds, boxes):
     return gd, fresh
 
 
-def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None):
+def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, weights=None):
     """Run the on-device GD for the rows of trans / rot and return the GradientDescent object (read gd.result() / gd.winner()).
     `panos`: one packed panorama per query image; the B rows split evenly over them, image by image.  `rgb`: one (N, 3) tensor, or a list
     of one per query image (per-image colour sets: image i's candidates read set i, and the chain runs the single-image plan).
-    The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape (_cached_engine)."""
-    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb)
+    The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape (_cached_engine).  `weights`: (N,)
+    per-point weights (one colour set, no depth mask)."""
+    if weights is not None and isinstance(rgb, list):
+        raise ValueError("per-point weights do not combine with per-image colour sets")
+    if weights is not None and bool(_cfg(cfg, "depth_mask", False)):
+        raise ValueError("per-point weights do not combine with cfg.depth_mask")
+    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb, weights)
     trans, rot = ops._dev(trans).reshape(-1, 3), ops._dev(rot).reshape(-1, 3)
     B = int(trans.shape[0])
     p0 = panos[0]
@@ -258,7 +272,7 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None):
         gd = make([cloud], [box])                          # (fresh buffers: nothing worth keeping for a long eager chain)
     else:
         # (one or two launches per iteration is frozen into a captured graph: part of the key, with the other arguments)
-        gd, fresh = _cached_engine("gd", (xyz,), (B, len(panos), p0.H, p0.W, p0.fmt, cloud.color_sets) + tuple(args.values()), make, [cloud], [box])
+        gd, fresh = _cached_engine("gd", (xyz,), (B, len(panos), p0.H, p0.W, p0.fmt, cloud.color_sets, cloud.weights is not None) + tuple(args.values()), make, [cloud], [box])
         if not fresh:
             gd.reset(trans, rot)
     if len(panos) > 1 or use_graph:
@@ -322,8 +336,9 @@ def _leaf_buffers(input_trans, input_rot, B):
     return bt, br, after
 
 
-def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_summaries):
+def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_summaries, weights=None):
     """Sequential refinement of ONE starting pose.  Returns [t (3,1), R (3,3), loss ()] (+ frames if cfg.visualize).
+    weights (not in the reference): (N,) per-point weights of the loss in the order of xyz's rows, non-negative and finite.
 
     `loss` is the loss of the last forward, i.e. at the pose before the final update, like the reference
     (omniloc.py:46,102).  Row `starting_point` of input_trans / input_rot ends up holding the final pose, as in the
@@ -337,7 +352,8 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     box = quantile_box_of(xyz, out_quantile)
     frames = []
     hook = (lambda gd, n: frames.extend(_run_with_frames(gd, img, xyz, rgb, n))) if vis else None
-    res = _refine(xyz, rgb, [pano], input_trans[starting_point], input_rot[starting_point], box, cfg, False, vis_hook=hook).result()[0]
+    res = _refine(xyz, rgb, [pano], input_trans[starting_point], input_rot[starting_point], box, cfg, False, vis_hook=hook,
+                  weights=weights).result()[0]
     R = _rot_matrix(res[3:6])
     out = torch.cat([res[0:3], R.reshape(-1), res[12:13]]).cpu()
     with torch.no_grad():
@@ -375,13 +391,13 @@ def _run_with_frames(gd, img, xyz, rgb, num_iter):
     return frames
 
 
-def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=None):
+def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=None, weights=None):
     """Throughput extension: what the reference's non-parallel branch computes with
     `for i in range(num_input): omniloc(..., i, ...)` (localize.py:219-220), for ALL starting points in one launch chain.
     Every starting point keeps omniloc's SEQUENTIAL semantics (its own Adam / scheduler, clamp applied to the parameters
     the next forward reads) and the points never interact, so the list returned equals the K separate calls."""
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
-    res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False).result()
+    res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False, weights=weights).result()
     K = res.shape[0]
     R = ops.rot_from_ypr(res[:, 3:6])
     host = torch.cat([res[:, 0:3], R.reshape(K, 9), res[:, 12:13]], dim=1).cpu()
@@ -391,14 +407,14 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     return [[host[i, 0:3].reshape(3, 1).clone(), host[i, 3:12].reshape(3, 3).clone(), host[i, 12].clone()] for i in range(K)]
 
 
-def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries):
+def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, weights=None):
     """Parallel refinement of all starting poses; returns [t (3,1), R (3,3), loss ()] of the candidate whose LAST
     forward had the smallest loss (omniloc.py:271).  Keeps the reference's clamp lag (omniloc.py:260-269): the
     returned translation is the post-step, pre-clamp value (omniloc.py:272)."""
     if strict_reference_asserts:
         assert cfg.num_input > 1
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
-    gd = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, True)
+    gd = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, True, weights=weights)
     # loss_list.argmin() of the last forward, R of the winner and the write-back of the leaves: one kernel, then the one D2H copy
     # of the whole refinement (64 bytes)
     bt, br, after = _leaf_buffers(input_trans, input_rot, gd.B)
@@ -640,9 +656,11 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     return [flat[r * I:(r + 1) * I] for r in range(R)]
 
 
-def sampling_loss(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, return_list=True):
-    """Forward-only loss of one starting pose — omniloc.py:105-157."""
-    cloud, pano = packed_cloud(xyz, rgb), packed_pano(img)
+def sampling_loss(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, return_list=True, weights=None):
+    """Forward-only loss of one starting pose — omniloc.py:105-157.  weights: (N,) per-point weights (not with cfg.depth_mask)."""
+    if weights is not None and _depth_cfg(cfg):
+        raise ValueError("per-point weights do not combine with cfg.depth_mask")
+    cloud, pano = packed_cloud(xyz, rgb, weights), packed_pano(img)
     t, r = input_trans[starting_point], input_rot[starting_point]
     res = ops.sampling_loss(cloud, pano, t, r, with_grad=False, depth=_depth_cfg(cfg))[0]
     loss = res[0].cpu()
@@ -681,10 +699,12 @@ class _LossFn(torch.autograd.Function):
 class SamplingLoss(nn.Module):
     """omniloc.py:160-202.  forward(translation (3,1), yaw (1,), pitch (1,), roll (1,)) -> scalar loss."""
 
-    def __init__(self, xyz, rgb, img, device, cfg):
+    def __init__(self, xyz, rgb, img, device, cfg, weights=None):
         super().__init__()
         self.xyz, self.rgb, self.img, self.cfg = xyz, rgb, img, cfg
-        self._cloud, self._pano = ops.Cloud(xyz, rgb), ops.Pano(img)
+        if weights is not None and _depth_cfg(cfg):
+            raise ValueError("per-point weights do not combine with cfg.depth_mask")
+        self._cloud, self._pano = ops.Cloud(xyz, rgb, weights=weights), ops.Pano(img)
 
     def forward(self, translation, yaw, pitch, roll):
         trans = translation.reshape(1, 3)
@@ -695,11 +715,13 @@ class SamplingLoss(nn.Module):
 class BatchSamplingLoss(nn.Module):
     """omniloc.py:299-356.  forward(translation (B,3,1), yaw (B,1), pitch (B,1), roll (B,1)) -> (sum, (B,) list)."""
 
-    def __init__(self, xyz, rgb, img, device, cfg):
+    def __init__(self, xyz, rgb, img, device, cfg, weights=None):
         super().__init__()
         self.xyz, self.rgb, self.img, self.cfg = xyz, rgb, img, cfg
         self.num_input = cfg.num_input
-        self._cloud, self._pano = ops.Cloud(xyz, rgb), ops.Pano(img)
+        if weights is not None and _depth_cfg(cfg):
+            raise ValueError("per-point weights do not combine with cfg.depth_mask")
+        self._cloud, self._pano = ops.Cloud(xyz, rgb, weights=weights), ops.Pano(img)
 
     def forward(self, translation, yaw, pitch, roll):
         B = translation.shape[0]

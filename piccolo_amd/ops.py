@@ -68,13 +68,17 @@ class Cloud:
     """Point cloud packed for the loss kernel: 6 SoA planes, by default in Morton order of xyz.
 
     `order` maps packed slot -> original point index (None if the original order was kept).  `color_sets`: how many colourings of the
-    points the buffer holds (1 here; Cloud.with_color_sets packs several)."""
+    points the buffer holds (1 here; Cloud.with_color_sets packs several).  `weights`: None, or the packed plane of per-point weights
+    (build-defined, include/piccolo_hip.h): sampling_loss and GradientDescent then evaluate the weighted loss; everything else refuses
+    such a cloud (ValueError) — weights are never silently dropped."""
 
     color_sets = 1
+    weights = None
 
-    def __init__(self, xyz, rgb, sort=True, order=None):
+    def __init__(self, xyz, rgb, sort=True, order=None, weights=None):
         """`order`: a Morton order computed before for the same xyz (Cloud(...).order): skips the sort, e.g. when only
-        the colours of a cloud changed (color_mod gives every query image its own rgb)."""
+        the colours of a cloud changed (color_mod gives every query image its own rgb).  `weights`: (N,) non-negative finite floats in
+        the order of xyz's rows."""
         lib = _lib.load()
         xyz, rgb = _dev(xyz), _dev(rgb)
         if xyz.dim() != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape:
@@ -96,6 +100,29 @@ class Cloud:
         _lib.check(lib.pcl_cloud_pack(_ptr(xyz), _ptr(rgb), _ptr(self.order), self.n, _ptr(self.data), _stream()),
                    "pcl_cloud_pack")
         self.xyz = xyz          # kept for quantile_box (reads the reference's AoS layout)
+        if weights is not None:
+            self.set_weights(weights)
+
+    def set_weights(self, w):
+        """Pack the (N,) weights `w` (the order of xyz's rows) into this cloud's weight plane — IN PLACE when it has one, so that an engine's
+        captured graph reads the new weights.  Negative, NaN or infinite weights raise ValueError (one 4-byte D2H read), and so does None:
+        a weighted cloud stays weighted."""
+        lib = _lib.load()
+        if self.color_sets > 1:
+            raise ValueError("set_weights: a cloud of colour sets takes no weights")
+        if w is None:
+            raise ValueError("set_weights: None (a weighted cloud stays weighted; pack a new Cloud)")
+        w = _dev(w)
+        if w.dim() != 1 or w.numel() != self.n:
+            raise ValueError("weights must be (N,) with one entry per point")
+        plane = self.weights if self.weights is not None else torch.empty(lib.pcl_cloud_weights_bytes(self.n) // 4, dtype=F32, device=w.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=w.device)
+        _lib.check(lib.pcl_cloud_pack_weights(_ptr(w), _ptr(self.order), self.n, _ptr(plane), _ptr(bad), _stream()), "pcl_cloud_pack_weights")
+        if int(bad.item()) != 0:
+            if self.weights is not None:
+                self.weights.zero_()         # (the plane holds the refused values: no vote rather than a wrong one)
+            raise ValueError("weights must be non-negative and finite")
+        self.weights = plane
 
     @classmethod
     def private_copy(cls, other):
@@ -105,6 +132,7 @@ class Cloud:
         c.n, c.order, c.xyz = other.n, other.order, other.xyz
         c.color_sets = other.color_sets
         c.data = other.data.clone()
+        c.weights = other.weights.clone() if other.weights is not None else None
         return c
 
     @classmethod
@@ -320,8 +348,15 @@ def _chain_depth_args(ns, H, W, depth_res, depth_tau, depth_stride=None):
     return per[0]
 
 
+def _unweighted(cloud, who):
+    """weights are never silently dropped: what takes no weights refuses a weighted cloud"""
+    if getattr(cloud, "weights", None) is not None:
+        raise ValueError("%s: the cloud carries per-point weights, which only sampling_loss and GradientDescent evaluate" % who)
+
+
 def sampling_loss(cloud, pano, trans, rot, with_grad=True, visible=None, depth=None):
     """(B, 8) float tensor on the GPU: loss, count, dL/dt(3), dL/d(yaw, pitch, roll).
+    A cloud with weights (Cloud(weights=...)): the weighted loss, column 1 the sum of the kept points' weights; not with visible / depth.
     visible: (B, n) uint8 mask in packed point order.  depth: True, or a dict with optional depth_res / depth_tau / depth_stride — the
     scatter-min depth mask of the SAME poses is built and looked up inside the launch (pcl_sampling_loss_depth)."""
     lib = _lib.load()
@@ -330,6 +365,15 @@ def sampling_loss(cloud, pano, trans, rot, with_grad=True, visible=None, depth=N
     if rot.shape[0] != B:
         raise ValueError("trans and rot must have the same number of rows")
     out = torch.empty(B, _lib.RESULT_STRIDE, dtype=F32, device=trans.device)
+    if cloud.weights is not None:
+        if visible is not None or depth:
+            raise ValueError("sampling_loss: per-point weights combine with neither a byte mask (visible) nor depth")
+        ws_bytes = lib.pcl_loss_workspace_bytes(cloud.n, B)
+        ws = _bytes(ws_bytes)
+        _lib.check(lib.pcl_sampling_loss_weighted(_ptr(cloud.data), _ptr(cloud.weights), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans),
+                                                  _ptr(rot), B, 1 if with_grad else 0, _ptr(out), _ptr(ws), ws_bytes, _stream()),
+                   "pcl_sampling_loss_weighted")
+        return out
     if depth:
         if visible is not None:
             raise ValueError("sampling_loss: pass either a byte mask (visible) or depth, not both")
@@ -396,6 +440,7 @@ def trim_loss_table(cloud, pano, trans, groups, return_count=False, order=None):
     """utils.py:484-499 for all pairs: (K, R) float GPU tensor loss_table[i, j] = forward-only sampling loss of (trans[i], rot[j]),
     rotations of one (pitch, roll) class sharing the projection (csrc/pcl_trim.hip).  order: a TrimOrder of this cloud / grid."""
     lib = _lib.load()
+    _unweighted(cloud, "trim_loss_table")
     trans = _dev(trans).reshape(-1, 3)
     K = int(trans.shape[0])
     table = torch.empty(K, groups.R, dtype=F32, device=trans.device)
@@ -418,6 +463,7 @@ def trim_loss_tables(cloud, panos, trans, groups, return_count=False, order=None
     A cloud with colour sets (Cloud.with_color_sets, one per image): image i reads set i — its table is trim_loss_table over
     Cloud(xyz, rgbs[i]), bit for bit."""
     lib = _lib.load()
+    _unweighted(cloud, "trim_loss_tables")
     trans = _dev(trans).reshape(-1, 3)
     K, I = int(trans.shape[0]), len(panos)
     p0 = panos[0]
@@ -497,6 +543,7 @@ def hist_trim_scores(img, cloud, trans, rot, num_split_h, num_split_w, batch=64,
     return_parts: (scores, inter, nproj, nimg).  splat=True: the z-buffer splat path on purpose (its small workspace selects it in
     pcl_hist_trim_scores; the tests compare the two renderers bit for bit)."""
     lib = _lib.load()
+    _unweighted(cloud, "hist_trim_scores")
     img = _dev(img)
     trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
     K, (H, W) = int(trans.shape[0]), (int(img.shape[0]), int(img.shape[1]))
@@ -556,6 +603,7 @@ def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w, s
     if cloud.color_sets > 1:
         return _hist_trim_scores_sets(imgs, cloud, trans, rot, num_split_h, num_split_w, splat)
     lib = _lib.load()
+    _unweighted(cloud, "hist_trim_scores_images")
     imgs = [_dev(im) for im in imgs]
     trans, rot = _dev(trans), _dev(rot)
     I, K = int(trans.shape[0]), int(trans.shape[1])
@@ -818,6 +866,8 @@ class GradientDescent(_GdEngine):
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         self.B = int(trans.shape[0])
         self.box = _dev(box).reshape(6)
+        if cloud.weights is not None and depth_mask:
+            raise ValueError("GradientDescent: per-point weights do not combine with the depth mask")
         if cloud.color_sets > 1 and self.B % cloud.color_sets:
             raise ValueError("GradientDescent: %d candidates over %d colour sets" % (self.B, cloud.color_sets))
         # colour sets under the depth mask: the depth-chain family with this cloud as its one room and a set per image; the engine's state,
@@ -843,6 +893,13 @@ class GradientDescent(_GdEngine):
         if self._chain is not None:
             return self._chain.run(num_iter, history, timer)
         hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
+        if self.cloud.weights is not None:
+            # (the plane's address is the cloud's for good — Cloud.set_weights packs in place — so a captured graph reads the current weights)
+            _lib.check(_lib.load().pcl_gd_run_weighted(_ptr(self.cloud.data), _ptr(self.cloud.weights), self.cloud.n, _ptr(self.pano.data), self.pano.fmt,
+                                                       self.pano.H, self.pano.W, _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper),
+                                                       int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None,
+                                                       _stream()), "pcl_gd_run_weighted")
+            return hist
         _lib.check(_lib.load().pcl_gd_run(_ptr(self.cloud.data), self.cloud.n, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
                                           _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper), int(num_iter),
                                           _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None, _stream()),
@@ -916,6 +973,8 @@ class GradientDescentRoomsImages(_GdEngine):
             raise ValueError("%s: no panorama" % name)
         self.pano = panos[0]
         self.clouds = [c for c, _ in rooms]
+        for c in self.clouds:
+            _unweighted(c, name)
         self.nrooms, self.nimages = len(rooms), len(panos)
         sets = {int(c.color_sets) for c in self.clouds}
         if len(sets) != 1 or sets.pop() not in (1, self.nimages):
