@@ -250,6 +250,24 @@ int pcl_gd_set_pano_groups(void *state, const uint64_t *panos_host, int nimages,
  * that loss, yaw / pitch / roll.  leaf_trans / leaf_rot [B][3] (nullable) receive every candidate's leaf parameters — what the
  * reference leaves in the caller's input_trans / input_rot, whose rows it optimises in place (omniloc.py:216-219). */
 int pcl_gd_winner(const void *state, int nimages, int per_image, float *winners, float *leaf_trans, float *leaf_rot, void *stream);
+/* Prune a GD state on the device (additive to ABI 12): per group keep the `keep` best candidates by their last loss and hand their COMPLETE
+ * optimiser state to a smaller state, so that a chain goes on with fewer candidates without a host round trip.  `state_in`: a state of
+ * groups * per_group candidates as pcl_gd_init / any pcl_gd_run* call leaves it (copy 0 is current); group g is the contiguous candidates
+ * [g * per_group, (g + 1) * per_group) — an image of pcl_gd_run, a (room, image) of the rooms chains.  `state_out`: a distinct buffer of
+ * pcl_gd_state_bytes(groups * keep).  Order: pcl_gd_winner's (a NaN is ahead of every number; among equal losses, or among NaNs, the
+ * smaller index is ahead; -0.0 == +0.0); a group keeps the candidates that `keep` successive "take the winner, remove it" steps would take,
+ * so keep = 1 keeps exactly the candidate pcl_gd_winner names.  Survivors keep their ORIGINAL index order: slot g * keep + s holds group
+ * g's s-th survivor and survivors[g * keep + s] its index inside the group (0 .. per_group - 1).  Copied, nothing recomputed: the
+ * survivor's whole optimiser record (Adam moments, lr, scheduler best / bad epochs, step, bias-correction products, sin / cos) and its
+ * pose record of BOTH copies (pose, panorama address, colour set) — bit for bit what pcl_gd_init + pcl_gd_set_panos* + the run would have
+ * left for those candidates alone.  leaf_trans / leaf_rot [groups * per_group][3] (nullable) receive every INPUT candidate's leaf
+ * parameters, as pcl_gd_winner writes them.  keep == per_group is a plain copy.  One launch of one 256-thread block per group, no
+ * workspace, no atomics; capturable.
+ * PCL_EINVAL, before any HIP call: null state_in / state_out / survivors, state_out == state_in, a state that is not 16-byte aligned,
+ * groups <= 0, keep <= 0, keep > per_group, per_group > PCL_GD_PRUNE_MAX, groups * per_group above 2^30. */
+#define PCL_GD_PRUNE_MAX 1024 /* candidates per group */
+int pcl_gd_prune(const void *state_in, int groups, int per_group, int keep, void *state_out, int32_t *survivors, float *leaf_trans,
+                 float *leaf_rot, void *stream);
 
 /* Room search (ABI 11): ONE query panorama against the rooms of a building in ONE launch chain.  Room r's candidates are the contiguous
  * range [r * per_room, (r + 1) * per_room) of a state of B = nrooms * per_room candidates (pcl_gd_state_bytes / pcl_gd_init /

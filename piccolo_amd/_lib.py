@@ -25,6 +25,7 @@ class GdHyper(_c.Structure):
 
 
 GD_MAX_ROOMS = 32
+GD_PRUNE_MAX = 1024       # PCL_GD_PRUNE_MAX: candidates per group of pcl_gd_prune
 
 
 class GdRoom(_c.Structure):
@@ -109,6 +110,7 @@ SIGNATURES = {
     "pcl_gd_set_panos": (_int, [_vp, _vp, _int, _vp]),
     "pcl_gd_set_pano_groups": (_int, [_vp, _c.POINTER(_c.c_uint64), _int, _int, _vp]),
     "pcl_gd_winner": (_int, [_vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "pcl_gd_prune": (_int, [_vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "pcl_gd_rooms_workspace_bytes": (_sz, [_c.POINTER(GdRoom), _int, _int, _c.POINTER(GdHyper)]),
     "pcl_gd_plan_rooms": (_int, [_c.POINTER(GdRoom), _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
     "pcl_gd_run_rooms": (_int, [_c.POINTER(GdRoom), _int, _vp, _int, _int, _int, _vp, _int, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),

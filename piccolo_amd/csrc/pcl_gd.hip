@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "pcl_gd_device.h"
+#include "pcl_gd_state.h"
 #include "pcl_host.h"
 #include "pcl_timer.h"
 
@@ -177,15 +178,7 @@ extern "C" int pcl_sampling_loss_depth(const float* cloud, int64_t n, const void
 
 // ---------------------------------------------------------------- GD: state init, epilogue, run, result
 
-// state blob = { PclGdPose[B], PclPoseRec[B] } x 2: copy 0 is the canonical one (what pcl_gd_init fills and pcl_gd_result reads);
-// fused iterations ping-pong between the two (a block of iteration k + 1 reads iteration k's copy while the block of chunk 0
-// writes iteration k + 1's).  The panorama addresses of the pose records are kept in both copies.
-static inline size_t gd_copy_bytes(int B) { return (size_t)B * (sizeof(PclGdPose) + sizeof(PclPoseRec)); }
-static inline PclGdPose* gd_poses(void* state, int B = 0, int copy = 0) { return (PclGdPose*)((char*)state + (size_t)copy * gd_copy_bytes(B)); }
-static inline PclPoseRec* gd_recs(void* state, int B, int copy = 0)
-{
-    return (PclPoseRec*)((char*)state + (size_t)copy * gd_copy_bytes(B) + (size_t)B * sizeof(PclGdPose));
-}
+// (the state blob's layout — gd_copy_bytes, gd_poses, gd_recs — is pcl_gd_state.h's)
 
 // per_image > 0 (pcl_gd_hyper.color_sets > 1): candidate b reads colour set b / per_image
 __global__ void pcl_gd_init_kernel(PclGdPose* st, PclPoseRec* recs, PclPoseRec* recs_shadow, const float* __restrict__ trans,
@@ -866,31 +859,23 @@ extern "C" int pcl_gd_set_pano_groups(void* state, const uint64_t* panos_host, i
 // translation, R = RZ RY RX of its post-step angles, that loss and the angles: 16 floats per image.  Also hands the leaf
 // parameters of all candidates back (the reference optimises views of the caller's tensors in place, omniloc.py:216-219).
 // One wave per image: lane-strided scan of the candidates' last losses, a wave argmin with torch.argmin's rules (a NaN beats any
-// number, among equals — or among NaNs — the smaller index wins), lane 0 writes the winner's 16 floats, all lanes the leaf rows.
+// number, among equals — or among NaNs — the smaller index wins: pcl_gd_better, which pcl_gd_prune ranks by too), lane 0 writes the winner's 16 floats, all lanes the leaf rows.
 __global__ void __launch_bounds__(PCL_WAVE) pcl_gd_winner_kernel(const PclGdPose* __restrict__ st, int nimages, int per_image, float* __restrict__ out,
                                                                  float* __restrict__ leaf_trans, float* __restrict__ leaf_rot)
 {
     const int i = blockIdx.x, lane = threadIdx.x;
     const PclGdPose* s = st + (int64_t)i * per_image;
     float best = 0.f;
-    int k = 0x7fffffff;                                        // (no candidate yet)
-    auto better = [](float la, int ia, float lb, int ib) {     // is (la, ia) ahead of (lb, ib)?
-        if (ib == 0x7fffffff) return ia != 0x7fffffff;
-        if (ia == 0x7fffffff) return false;
-        const bool na = la != la, nb = lb != lb;
-        if (na != nb) return na;
-        if (na || la == lb) return ia < ib;
-        return la < lb;
-    };
+    int k = PCL_GD_NO_CANDIDATE;                               // (none yet)
     for (int b = lane; b < per_image; b += PCL_WAVE) {
         const float l = s[b].last_loss;
-        if (better(l, b, best, k)) { best = l; k = b; }
+        if (pcl_gd_better(l, b, best, k)) { best = l; k = b; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float lo = __shfl_xor(best, o, 64);
         const int ko = __shfl_xor(k, o, 64);
-        if (better(lo, ko, best, k)) { best = lo; k = ko; }
+        if (pcl_gd_better(lo, ko, best, k)) { best = lo; k = ko; }
     }
     if (lane == 0) {
         float* o = out + (int64_t)i * 16;

@@ -39,7 +39,9 @@ def preprocess_colors(img, rgb, cfg):
 
 def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=None, weights=None):
     """localize.py:215-233: run the refinement the config asks for and pick the min-loss candidate.
-    Returns (t (3,1), R (3,3), loss) as cpu tensors.  weights (not in the reference): (N,) per-point weights of the refinement's loss."""
+    Returns (t (3,1), R (3,3), loss) as cpu tensors.  weights (not in the reference): (N,) per-point weights of the refinement's loss.
+    cfg.prune_iters / cfg.prune_keep (omniloc.prune_schedule) prune the parallel refinement's candidates on the device; the non-parallel
+    branch returns every candidate and refuses the keys (ValueError), as omniloc_all does."""
     summaries = scalar_summaries if scalar_summaries is not None else {}
     if getattr(cfg, "parallel", False):
         results = [omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)]

@@ -17,6 +17,8 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
     (depth_h, depth_w) is the z-buffer's grid (default: by point density, pcl_depth_default — not the panorama's size),
     depth_tau its tolerance (default: the rule's value for the grid), depth_stride = s builds the z-buffer from every s-th
     point of the Morton-ordered cloud (default: pcl_depth_default's choice; every point is still tested against it);
+  * extra, optional cfg keys prune_iters / prune_keep (default absent = reference behaviour): the batch refinements drop all but the best
+    prune_keep candidates of every image after prune_iters iterations, on the device (prune_schedule, csrc/pcl_prune.hip);
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
     per iteration) as 4th element.
@@ -248,8 +250,113 @@ def _cached_engine(kind, xyzs, sub, make, clouds, boxes):
     return gd, fresh
 
 
+# ------------------------------------------------------------------------------------------------ pruned chains
+# cfg prune_iters / prune_keep (not in the reference; absent by default): after prune_iters[j] iterations in all, every image — every
+# (room, image) of a rooms chain — keeps its prune_keep[j] best candidates by the loss of that iteration's forward (history row
+# prune_iters[j] - 1) and the chain goes on with them alone: pcl_gd_prune hands their complete optimiser state to a smaller engine on the
+# device, so nothing is re-initialised and nothing waits for the host.  The reference refines every one of its num_input candidates to
+# the end; which schedule still finds its winner is the user's choice (DESIGN.md §4.6f has the CPU evidence for 16 -> 8 -> 4).
+def _no_prune(cfg, who):
+    """what returns every candidate, or records frames of one, does not prune"""
+    if _cfg(cfg, "prune_iters", None) is not None or _cfg(cfg, "prune_keep", None) is not None:
+        raise ValueError("%s does not take cfg.prune_iters / cfg.prune_keep (the batch refinements do)" % who)
+
+
+def prune_schedule(cfg, per_image):
+    """The segments [(iterations, candidates per image), ...] of a refinement of `per_image` candidates per image under cfg.prune_iters /
+    cfg.prune_keep (an int each, or lists of equal length), or None when the keys are absent.  prune_iters = 20, 40 with prune_keep = 16, 8
+    at num_iter 100 and 32 candidates: [(20, 32), (20, 16), (60, 8)].  ValueError: one key without the other, unequal lengths, iterations
+    not strictly increasing inside (0, num_iter), prune_keep not non-increasing or outside 1 .. min(per_image, PCL_GD_PRUNE_MAX), more than
+    PCL_GD_PRUNE_MAX candidates per image.  Host only."""
+    iters, keep = _cfg(cfg, "prune_iters", None), _cfg(cfg, "prune_keep", None)
+    if iters is None and keep is None:
+        return None
+    if iters is None or keep is None:
+        raise ValueError("cfg.prune_iters and cfg.prune_keep go together")
+
+    def ints(v, name):
+        v = list(v) if isinstance(v, (list, tuple)) else [v]
+        if not v or any(isinstance(x, bool) or not isinstance(x, int) for x in v):
+            raise ValueError("cfg.%s: an int or a list of ints, got %r" % (name, v))
+        return v
+    iters, keep = ints(iters, "prune_iters"), ints(keep, "prune_keep")
+    num_iter, per_image = int(_cfg(cfg, "num_iter", 100)), int(per_image)
+    if len(iters) != len(keep):
+        raise ValueError("cfg.prune_iters has %d entries, cfg.prune_keep %d" % (len(iters), len(keep)))
+    if any(not 0 < k < num_iter for k in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
+        raise ValueError("cfg.prune_iters %r: strictly increasing iteration counts inside (0, %d)" % (iters, num_iter))
+    cap = ops._lib.GD_PRUNE_MAX
+    if per_image > cap:
+        raise ValueError("pruning takes at most %d candidates per image, got %d" % (cap, per_image))
+    if any(not 1 <= k <= per_image for k in keep) or any(b > a for a, b in zip(keep, keep[1:])):
+        raise ValueError("cfg.prune_keep %r: non-increasing counts in 1 .. %d" % (keep, per_image))
+    ends, counts = iters + [num_iter], [per_image] + keep
+    return [(e - b, c) for b, e, c in zip([0] + iters, ends, counts)]
+
+
+class _PrunedChain:
+    """What a pruned refinement hands back in place of its engine: winners() of the LAST segment's engine, and every candidate's leaf row
+    written back to the caller's buffers — a dropped candidate's from the prune call that dropped it (its pose at that time), a
+    survivor's from the last engine, through the survivors' indices composed on the device."""
+
+    def __init__(self, first, groups):
+        self.B, self.groups, self.last = first.B, groups, first
+        self.rows = None                  # row of the caller's tensors each candidate of the current engine came from (None: its own)
+        self.steps = []                   # (rows, leaf_t, leaf_r) of every prune call, in order
+
+    def prune(self, child):
+        gd, dev = self.last, self.last.state.device
+        leaf_t, leaf_r = torch.empty(gd.B, 3, dtype=torch.float32, device=dev), torch.empty(gd.B, 3, dtype=torch.float32, device=dev)
+        survivors = gd.prune_into(child, leaf_t, leaf_r)
+        per, keep = gd.B // self.groups, child.B // self.groups
+        local = survivors.long() + torch.arange(self.groups, device=dev).repeat_interleave(keep) * per
+        self.steps.append((self.rows, leaf_t, leaf_r))
+        self.rows = local if self.rows is None else self.rows[local]
+        self.last = child
+
+    def winners(self, groups, leaf_trans=None, leaf_rot=None):
+        if groups != self.groups:
+            raise ValueError("winners: a chain pruned per %d groups asked for %d" % (self.groups, groups))
+        dev = self.last.state.device
+        leaf_t, leaf_r = torch.empty(self.last.B, 3, dtype=torch.float32, device=dev), torch.empty(self.last.B, 3, dtype=torch.float32, device=dev)
+        out = self.last.winners(groups, leaf_t, leaf_r)
+        for dst, col in ((leaf_trans, 1), (leaf_rot, 2)):
+            if dst is None:
+                continue
+            dst = dst.view(self.B, 3)
+            for step in self.steps + [(self.rows, leaf_t, leaf_r)]:
+                if step[0] is None:
+                    dst.copy_(step[col])
+                else:
+                    dst.index_copy_(0, step[0], step[col])
+        return out
+
+    def winner(self, nimages=1, leaf_trans=None, leaf_rot=None):
+        return self.winners(nimages, leaf_trans, leaf_rot)
+
+
+def _run_segments(sched, groups, gd, point_poses, cfg, depth_mask, cached_child):
+    """Run the segments of prune_schedule one after another, starting with the engine `gd` (initialised, its pose records naming their
+    panoramas): k iterations, prune into the next segment's engine, and so on.  Every segment is a replayed graph or eager by _replays_graph
+    on ITS points x candidates, point_poses(per); a replaying segment's engine comes from cached_child(per) (_cached_engine), an eager one is
+    made for the occasion (`per`: candidates per group).  -> _PrunedChain"""
+    if _cfg(cfg, "visualize", False):
+        raise ValueError("cfg.visualize does not combine with cfg.prune_iters / cfg.prune_keep")
+    chain = _PrunedChain(gd, groups)
+    for s, (iters, per) in enumerate(sched):
+        graph = _replays_graph(cfg, point_poses(per), depth_mask)
+        if s > 0 and groups * per != chain.last.B:           # (keeping every candidate would be a plain copy: the engine goes on as it is)
+            chain.prune(cached_child(per) if graph else chain.last._smaller(per))
+        if graph:
+            chain.last.run_graph(iters)
+        else:
+            chain.last.run(iters)
+    return chain
+
+
 def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, weights=None):
-    """Run the on-device GD for the rows of trans / rot and return the GradientDescent object (read gd.result() / gd.winner()).
+    """Run the on-device GD for the rows of trans / rot and return the GradientDescent object (read gd.result() / gd.winner()); under
+    cfg.prune_iters / cfg.prune_keep the _PrunedChain of its segments (read winner() / winners()).
     `panos`: one packed panorama per query image; the B rows split evenly over them, image by image.  `rgb`: one (N, 3) tensor, or a list
     of one per query image (per-image colour sets: image i's candidates read set i, and the chain runs the single-image plan).
     The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape (_cached_engine).  `weights`: (N,)
@@ -265,18 +372,27 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, we
     num_iter = _cfg(cfg, "num_iter", 100)
     args = _engine_args(cfg, batch_mode)
     use_graph = _replays_graph(cfg, cloud.n * B, args["depth_mask"]) and vis_hook is None
+    sched = prune_schedule(cfg, B // len(panos))
 
-    def make(cs, bs):
-        return ops.GradientDescent(cs[0], p0, trans, rot, bs[0], **args)
-    if not use_graph:
-        gd = make([cloud], [box])                          # (fresh buffers: nothing worth keeping for a long eager chain)
-    else:
+    def cached(Bs):
+        """-> (the cached engine of Bs candidates, fresh): made with the first Bs of the caller's poses"""
+        def make(cs, bs):
+            return ops.GradientDescent(cs[0], p0, trans[:Bs], rot[:Bs], bs[0], **args)
         # (one or two launches per iteration is frozen into a captured graph: part of the key, with the other arguments)
-        gd, fresh = _cached_engine("gd", (xyz,), (B, len(panos), p0.H, p0.W, p0.fmt, cloud.color_sets, cloud.weights is not None) + tuple(args.values()), make, [cloud], [box])
+        return _cached_engine("gd", (xyz,), (Bs, len(panos), p0.H, p0.W, p0.fmt, cloud.color_sets, cloud.weights is not None) + tuple(args.values()), make, [cloud], [box])
+    if not use_graph:
+        gd = ops.GradientDescent(cloud, p0, trans, rot, box, **args)      # (fresh buffers: nothing worth keeping for a long eager chain)
+    else:
+        gd, fresh = cached(B)
         if not fresh:
             gd.reset(trans, rot)
-    if len(panos) > 1 or use_graph:
+    if len(panos) > 1 or use_graph or sched is not None:     # (a later segment may replay a graph that holds another image's panorama)
         gd.set_pano_groups(list(panos))                      # addresses as kernel arguments: no H2D copy, nothing waits
+    if sched is not None:
+        if vis_hook is not None:
+            raise ValueError("cfg.visualize does not combine with cfg.prune_iters / cfg.prune_keep")
+        return _run_segments(sched, len(panos), gd, lambda per: cloud.n * len(panos) * per, cfg, args["depth_mask"],
+                             lambda per: cached(len(panos) * per)[0])
     if vis_hook is not None:
         vis_hook(gd, num_iter)
     elif use_graph:
@@ -344,6 +460,7 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     (omniloc.py:46,102).  Row `starting_point` of input_trans / input_rot ends up holding the final pose, as in the
     reference where the optimised tensors are views of those rows (omniloc.py:15-19).
     """
+    _no_prune(cfg, "omniloc")
     vis = _cfg(cfg, "visualize", False)
     out_quantile = _cfg(cfg, "out_of_room_quantile", 0.05)
 
@@ -396,6 +513,7 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     `for i in range(num_input): omniloc(..., i, ...)` (localize.py:219-220), for ALL starting points in one launch chain.
     Every starting point keeps omniloc's SEQUENTIAL semantics (its own Adam / scheduler, clamp applied to the parameters
     the next forward reads) and the points never interact, so the list returned equals the K separate calls."""
+    _no_prune(cfg, "omniloc_all")
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False, weights=weights).result()
     K = res.shape[0]
@@ -431,6 +549,10 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     its own Adam / scheduler state, so every image gets the result omniloc_batch would give it (bit for bit when the
     cloud is cut into the same chunks, else up to the summation order of the partial sums); at 32 candidates per image,
     8 images per launch are ~25 % faster than 8 separate refinements.  Returns a list of [t, R, loss].
+    The same caveat holds for a PRUNED run (cfg.prune_iters / cfg.prune_keep, prune_schedule; here and in omniloc_batch, omniloc_batch_rooms,
+    omniloc_batch_rooms_images): after a prune the survivors run the plan of the smaller launch, pcl_gd_plan(n, keep), so their trajectories
+    equal the unpruned run's bit for bit only where the two plans cut the cloud into the same chunks, else up to the summation order; the
+    optimiser state itself crosses the prune unchanged.  Every candidate's leaf row still comes back: a dropped one's as it was when dropped.
     batch_mode=False gives every candidate omniloc's SEQUENTIAL semantics instead (what omniloc_all computes per image).
     rgb: one (N, 3) tensor, or a LIST of one per image (per-image colours, e.g. color_mod's): the cloud then holds a colour set per image
     and the chain runs the single-image plan, so image i's result is omniloc_batch(imgs[i], xyz, rgb[i], ...)'s bit for bit.  Images
@@ -494,20 +616,35 @@ def _chain(kind, imgs, rooms, tr, ro, cfg, batch_mode):
     num_iter = _cfg(cfg, "num_iter", 100)
     args = _engine_args(cfg, batch_mode)
 
-    def make(cs, bs):
+    points = sum(c.n for c in clouds)
+    sched = prune_schedule(cfg, per_room // len(imgs))
+
+    def cached(per):
+        """-> (the cached engine of `per` candidates per room, fresh): made with the first rows of the caller's poses"""
+        def make(cs, bs):
+            if one_image:
+                return ops.GradientDescentRooms(list(zip(cs, bs)), p0, tr[:len(rooms) * per], ro[:len(rooms) * per], **args)
+            return ops.GradientDescentRoomsImages(list(zip(cs, bs)), panos, tr[:len(rooms) * per], ro[:len(rooms) * per], **args)
+        return _cached_engine(kind, tuple(xyz for xyz, _ in rooms), (len(imgs), per, p0.H, p0.W, p0.fmt, clouds[0].color_sets) + tuple(args.values()),
+                              make, clouds, boxes)
+    if not _replays_graph(cfg, points * per_room, args["depth_mask"]):
         if one_image:
-            return ops.GradientDescentRooms(list(zip(cs, bs)), p0, tr, ro, **args)
-        return ops.GradientDescentRoomsImages(list(zip(cs, bs)), panos, tr, ro, **args)
-    if not _replays_graph(cfg, sum(c.n for c in clouds) * per_room, args["depth_mask"]):
-        gd = make(clouds, boxes)
-        gd.run(num_iter)
-        return gd
-    gd, fresh = _cached_engine(kind, tuple(xyz for xyz, _ in rooms),
-                               (len(imgs), per_room, p0.H, p0.W, p0.fmt, clouds[0].color_sets) + tuple(args.values()), make, clouds, boxes)
-    if not fresh:
-        gd.reset(tr, ro)
+            gd = ops.GradientDescentRooms(list(zip(clouds, boxes)), p0, tr, ro, **args)
+        else:
+            gd = ops.GradientDescentRoomsImages(list(zip(clouds, boxes)), panos, tr, ro, **args)
+        if sched is None:
+            gd.run(num_iter)
+            return gd
+        fresh = True
+    else:
+        gd, fresh = cached(per_room)
+        if not fresh:
+            gd.reset(tr, ro)
     if not fresh or one_image:                   # (a new several-image engine has named its panoramas itself)
         gd.set_panos(panos)                      # the pose records name these images' panoramas (the graph holds the first ones')
+    if sched is not None:
+        groups = len(rooms) * len(imgs)
+        return _run_segments(sched, groups, gd, lambda per: points * len(imgs) * per, cfg, args["depth_mask"], lambda per: cached(len(imgs) * per)[0])
     gd.run_graph(num_iter)
     return gd
 

@@ -853,6 +853,42 @@ class _GdEngine:
         _lib.check(_lib.load().pcl_gd_result(_ptr(self.state), self.B, _ptr(out), _stream()), "pcl_gd_result")
         return out
 
+    def pruned(self, keep, leaf_trans=None, leaf_rot=None):
+        """-> (engine, survivors): an engine of the same class over the same clouds, panoramas, boxes and hyper-parameters with the `keep`
+        best candidates of every group (an image; a (room, image)) by their last loss, and the survivors' indices inside their groups
+        ((groups * keep,) int32 on the device, original order).  The smaller engine's state is pcl_gd_prune's output — the survivors'
+        complete optimiser state, pose records, panoramas and colour sets — and it has a workspace of its own for the smaller plan; run it
+        to continue the chain.  leaf_trans / leaf_rot: as for winners(), every candidate of THIS engine.  No synchronisation, no D2H."""
+        child = self._smaller(int(keep))
+        return child, self.prune_into(child, leaf_trans, leaf_rot)
+
+    def prune_into(self, child, leaf_trans=None, leaf_rot=None):
+        """pruned() into an engine that exists (the same class, clouds and groups, fewer candidates per group: a cached one whose captured
+        graph is to be replayed): its state is overwritten.  -> survivors"""
+        groups = self._groups()
+        if type(child) is not type(self) or child is self or child.B <= 0 or child.B % groups or child.B > self.B or not self._same_problem(child):
+            raise ValueError("prune: the smaller engine must be one of the same class, clouds and groups with at most as many candidates")
+        for t in (leaf_trans, leaf_rot):
+            if t is not None and not (t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == 3 * self.B):
+                raise ValueError("prune: leaf buffers must be contiguous float32 GPU tensors of B x 3")
+        if self.B // groups > _lib.GD_PRUNE_MAX:
+            raise ValueError("prune: at most %d candidates per group" % _lib.GD_PRUNE_MAX)
+        survivors = torch.empty(child.B, dtype=torch.int32, device=self.state.device)
+        _lib.check(_lib.load().pcl_gd_prune(_ptr(self.state), groups, self.B // groups, child.B // groups, _ptr(child.state), _ptr(survivors),
+                                            _ptr(leaf_trans), _ptr(leaf_rot), _stream()), "pcl_gd_prune")
+        # the survivors' records name the parent's panoramas: keep them alive, and the mapping hint with them
+        child.hyper.images = self.hyper.images
+        for name in ("_panos", "_pano_table"):
+            if name in self.__dict__:
+                setattr(child, name, self.__dict__[name])
+        return survivors
+
+
+def _copy_hyper(h):
+    c = _lib.GdHyper()
+    ctypes.memmove(ctypes.byref(c), ctypes.byref(h), ctypes.sizeof(c))
+    return c
+
 
 class GradientDescent(_GdEngine):
     """On-device GD refinement of B candidates (Adam + ReduceLROnPlateau + clamp), pcl_gd_* of the C ABI."""
@@ -944,6 +980,33 @@ class GradientDescent(_GdEngine):
     def winner(self, nimages=1, leaf_trans=None, leaf_rot=None):
         """(nimages, 16) GPU tensor: per image of B / nimages candidates the one omniloc_batch returns (_GdEngine.winners)."""
         return self.winners(nimages, leaf_trans, leaf_rot)
+
+    def _groups(self):
+        """the images whose candidates share this chain: the cloud's colour sets, else what set_pano_groups / set_panos named, else one"""
+        return max(1, int(self.cloud.color_sets), int(self.hyper.images))
+
+    def _same_problem(self, other):
+        return other.cloud.n == self.cloud.n and other.cloud.color_sets == self.cloud.color_sets and \
+            (other.pano.H, other.pano.W, other.pano.fmt) == (self.pano.H, self.pano.W, self.pano.fmt)
+
+    def _smaller(self, keep):
+        """an engine over the same cloud, panorama, box and hyper-parameters with `keep` candidates per image, its state not yet written"""
+        lib, groups = _lib.load(), self._groups()
+        if self.B % groups or not 1 <= keep <= self.B // groups:
+            raise ValueError("pruned: keep %d of %d candidates per image" % (keep, self.B // max(groups, 1)))
+        g = GradientDescent.__new__(GradientDescent)
+        g.cloud, g.pano, g.box, g.B = self.cloud, self.pano, self.box, groups * keep
+        g._chain = self._chain._smaller(keep) if self._chain is not None else None
+        if g._chain is not None:
+            g.hyper, g.state, g.ws, g.ws_bytes = g._chain.hyper, g._chain.state, g._chain.ws, g._chain.ws_bytes
+            return g
+        g.hyper = _copy_hyper(self.hyper)
+        g.state = _bytes(lib.pcl_gd_state_bytes(g.B))
+        g.ws_bytes = lib.pcl_gd_workspace_bytes(self.cloud.n, g.B, self.pano.H, self.pano.W, ctypes.byref(g.hyper))
+        if g.ws_bytes == 0:
+            raise _lib.PiccoloHipError("pcl_gd_workspace_bytes: invalid arguments for %d candidates" % g.B)
+        g.ws = _bytes(g.ws_bytes)
+        return g
 
     def step_from_grads(self, loss, grad):
         """Teacher-forcing hook (tests): ONE optimiser step of every candidate from a GIVEN loss (B,) and gradient (B, 6) =
@@ -1042,6 +1105,35 @@ class GradientDescentRoomsImages(_GdEngine):
     def winner(self, leaf_trans=None, leaf_rot=None):
         """(nrooms * nimages, 16): per (room, image), room by room, the candidate omniloc_batch returns (_GdEngine.winners)."""
         return self.winners(self.nrooms * self.nimages, leaf_trans, leaf_rot)
+
+    def _groups(self):
+        return self.nrooms * self.nimages
+
+    def _same_problem(self, other):
+        return (other.nrooms, other.nimages, other.color_sets, other.depth_mask) == (self.nrooms, self.nimages, self.color_sets, self.depth_mask) and \
+            [c.n for c in other.clouds] == [c.n for c in self.clouds] and \
+            (other.pano.H, other.pano.W, other.pano.fmt) == (self.pano.H, self.pano.W, self.pano.fmt)
+
+    def _smaller(self, keep):
+        """an engine over the same rooms, panoramas and hyper-parameters with `keep` candidates per (room, image), its state not yet written"""
+        lib = _lib.load()
+        if not 1 <= keep <= self.per_image:
+            raise ValueError("pruned: keep %d of %d candidates per (room, image)" % (keep, self.per_image))
+        g = type(self).__new__(type(self))
+        for name in ("pano", "clouds", "nrooms", "nimages", "color_sets", "boxes", "depth_mask", "_rooms"):
+            setattr(g, name, getattr(self, name))
+        g.per_image, g.per_room, g.B = keep, keep * self.nimages, keep * self.nimages * self.nrooms
+        g.hyper = _copy_hyper(self.hyper)
+        g._shape = (g._rooms, g.nrooms, g.nimages, g.per_image)
+        g.state = _bytes(lib.pcl_gd_state_bytes(g.B))
+        if g.depth_mask:
+            g.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(*g._shape, g.pano.H, g.pano.W, ctypes.byref(g.hyper))
+        else:
+            g.ws_bytes = lib.pcl_gd_rooms_images_workspace_bytes(*g._shape, ctypes.byref(g.hyper))
+        if g.ws_bytes == 0:
+            raise _lib.PiccoloHipError("pcl_gd_%s_workspace_bytes: invalid arguments" % ("depth_chain" if g.depth_mask else "rooms_images"))
+        g.ws = _bytes(g.ws_bytes)
+        return g
 
 
 class GradientDescentRooms(GradientDescentRoomsImages):
