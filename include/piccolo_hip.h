@@ -501,7 +501,9 @@ int pcl_trim_loss_images_sets(const float *cloud, int64_t n, int color_sets, con
  *   zmin[b][cell] = the smallest ||p|| among the OCCLUDER SAMPLES in the cell: every stride-th point of the packed cloud (1: all)
  *   visible[b][i] = 1 iff ||p_i|| <= (1 + tau) x zmin[b][cell of p_i]                  (every point i, packed point order)
  * Feeds the `visible` argument of pcl_sampling_loss; the GD loop and pcl_sampling_loss_depth look the z-buffer up in the loss kernel
- * instead and never build the byte mask.  workspace: pcl_depth_workspace_bytes(B, H, W).
+ * instead and never build the byte mask.  workspace: pcl_depth_workspace_bytes(B, H, W).  Contract: after the call the workspace's last
+ * round_up(B x H x W x 4, 16) bytes — byte offset pcl_depth_workspace_bytes(B, H, W) - round_up(B x H x W x 4, 16) — hold the B z-buffers
+ * [B][H x W] as uint32 words, each the bit pattern of the fp32 value (zmin (1 + tau))^2 of its cell, 0x7f800000 (+inf) for an empty cell.
  * pcl_depth_default (host-only): what is used when a caller does not name them.  Grid: at least 12 occluder samples per cell
  * (depth_w = 2 depth_h, depth_h a multiple of 8, never finer than the H x W panorama); tau = 3.5 pi / depth_h clipped to [0.02, 0.15]
  * (a coarser cell needs a larger tolerance: a surface seen at a grazing angle spans more depth inside it); stride (stride_in = 0): the
