@@ -10,7 +10,7 @@
 //   The template CDF is never materialised: the point colours are sorted once per cloud (rocPRIM radix sort, the one
 //   library call in this file) and a quantile is located by binary search on the count c whose float32 quotient
 //   c / n first exceeds x, exactly as the reference's float32 comparison `x < cumsum(counts) / n` decides it.
-#include "pcl_device.h"
+#include "pcl_host.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -28,8 +28,6 @@ struct PclColorHist {                       // zeroed per call
     unsigned int not_exact;                 // some non-black pixel channel is not k/255
     unsigned int pad[3];
 };
-
-static inline size_t color_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // (img * 255).long() per channel: truncation toward zero
 __device__ __forceinline__ int pcl_level(float v) { return (int)(v * 255.f); }
@@ -55,23 +53,30 @@ static size_t color_sort_temp_bytes(int64_t n)
 
 extern "C" size_t pcl_color_template_bytes(int64_t n) { return n > 0 ? (size_t)n * 3 * sizeof(float) : 0; }
 
-extern "C" size_t pcl_color_template_workspace_bytes(int64_t n)
+// workspace of pcl_color_template_build: the three colour planes, then the sort's temporary storage
+struct ColorTemplateWs { float* planes; void* temp; size_t temp_bytes; };
+static size_t color_template_layout(void* base, int64_t n, ColorTemplateWs* w)
 {
-    return n > 0 ? color_align((size_t)n * 3 * sizeof(float)) + color_align(color_sort_temp_bytes(n)) : 0;
+    if (n <= 0) return 0;
+    PclCarve c{(char*)base, 0};
+    w->planes = (float*)c.take((size_t)n * 3 * sizeof(float));
+    w->temp_bytes = color_sort_temp_bytes(n);
+    w->temp = c.take(w->temp_bytes);
+    return c.off;
 }
+
+extern "C" size_t pcl_color_template_workspace_bytes(int64_t n) { ColorTemplateWs w; return color_template_layout(nullptr, n, &w); }
 
 extern "C" int pcl_color_template_build(const float* rgb, int64_t n, float* tmpl, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!rgb || !tmpl || !workspace || n <= 0 || n > PCL_MAX_POINTS) return PCL_EINVAL;
-    if (workspace_bytes < pcl_color_template_workspace_bytes(n)) return PCL_EWORKSPACE;
+    ColorTemplateWs w;
+    if (workspace_bytes < color_template_layout(workspace, n, &w)) return PCL_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    float* planes = (float*)workspace;
-    void* temp = (char*)workspace + color_align((size_t)n * 3 * sizeof(float));
-    size_t temp_bytes = color_sort_temp_bytes(n);
-    hipLaunchKernelGGL(pcl_color_planes_kernel, dim3((unsigned)((n + PCL_BLOCK - 1) / PCL_BLOCK)), dim3(PCL_BLOCK), 0, s, rgb, n, planes);
+    hipLaunchKernelGGL(pcl_color_planes_kernel, dim3((unsigned)((n + PCL_BLOCK - 1) / PCL_BLOCK)), dim3(PCL_BLOCK), 0, s, rgb, n, w.planes);
     PCL_LAUNCH_CHECK();
     for (int c = 0; c < 3; c++) {
-        hipError_t e = rocprim::radix_sort_keys(temp, temp_bytes, (const float*)(planes + (size_t)c * n), tmpl + (size_t)c * n,
+        hipError_t e = rocprim::radix_sort_keys(w.temp, w.temp_bytes, (const float*)(w.planes + (size_t)c * n), tmpl + (size_t)c * n,
                                                 (size_t)n, 0, 32, s, false);
         if (e != hipSuccess) return (int)e;
     }
@@ -222,26 +227,35 @@ static unsigned color_grid(int64_t items)
     return (unsigned)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);    // 8 blocks per CU, grid-stride beyond
 }
 
-// [PclColorHist][3 x 4096 words: color_match's 3 x 256 table, or color_mod's cumulative table + two luma histograms]
-extern "C" size_t pcl_color_workspace_bytes(void) { return color_align(sizeof(PclColorHist)) + color_align(3 * 4096 * sizeof(float)); }
+// workspace of pcl_color_match and pcl_color_mod: [PclColorHist][3 x 4096 words: color_match's 3 x 256 table, or color_mod's cumulative
+// table + two luma histograms]
+struct ColorWs { PclColorHist* hist; float* table; };
+static size_t color_layout(void* base, ColorWs* w)
+{
+    PclCarve c{(char*)base, 0};
+    w->hist = (PclColorHist*)c.take(sizeof(PclColorHist));
+    w->table = (float*)c.take(3 * 4096 * sizeof(float));
+    return c.off;
+}
+
+extern "C" size_t pcl_color_workspace_bytes(void) { ColorWs w; return color_layout(nullptr, &w); }
 
 extern "C" int pcl_color_match(const float* img, int H, int W, const float* tmpl, int64_t n, float* out, int32_t* not_exact,
                                void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!img || !tmpl || !out || !workspace || H <= 0 || W <= 0 || n <= 0 || n > PCL_MAX_POINTS) return PCL_EINVAL;
-    if (workspace_bytes < pcl_color_workspace_bytes()) return PCL_EWORKSPACE;
+    ColorWs w;
+    if (workspace_bytes < color_layout(workspace, &w)) return PCL_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    PclColorHist* hist = (PclColorHist*)workspace;
-    float* lut = (float*)((char*)workspace + color_align(sizeof(PclColorHist)));
     const int64_t npix = (int64_t)H * W;
-    hipError_t e = hipMemsetAsync(hist, 0, sizeof(PclColorHist), s);
+    hipError_t e = hipMemsetAsync(w.hist, 0, sizeof(PclColorHist), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(pcl_cm_hist_kernel, dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, img, H, W, hist);
-    hipLaunchKernelGGL(pcl_cm_table_kernel, dim3(3), dim3(PCL_CM_LEVELS), 0, s, hist, tmpl, n, lut);
-    hipLaunchKernelGGL(pcl_cm_apply_kernel, dim3(color_grid(npix)), dim3(PCL_BLOCK), 0, s, img, npix, lut, out);
+    hipLaunchKernelGGL(pcl_cm_hist_kernel, dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, img, H, W, w.hist);
+    hipLaunchKernelGGL(pcl_cm_table_kernel, dim3(3), dim3(PCL_CM_LEVELS), 0, s, w.hist, tmpl, n, w.table);
+    hipLaunchKernelGGL(pcl_cm_apply_kernel, dim3(color_grid(npix)), dim3(PCL_BLOCK), 0, s, img, npix, w.table, out);
     PCL_LAUNCH_CHECK();
     if (not_exact) {
-        e = hipMemcpyAsync(not_exact, &hist->not_exact, sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+        e = hipMemcpyAsync(not_exact, &w.hist->not_exact, sizeof(int32_t), hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return (int)e;
     }
     return 0;
@@ -359,10 +373,11 @@ extern "C" int pcl_color_mod(const float* img, int H, int W, const float* rgb, i
 {
     if (!img || !rgb || !out_img || !out_rgb || !workspace || H <= 0 || W <= 0 || n <= 0 || num_bins < 2 || num_bins > PCL_MOD_MAX_BINS)
         return PCL_EINVAL;
-    if (workspace_bytes < pcl_color_workspace_bytes()) return PCL_EWORKSPACE;
+    ColorWs w;
+    if (workspace_bytes < color_layout(workspace, &w)) return PCL_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    // second workspace area: [cdf 4096][hist_img 4096][hist_rgb 4096]
-    float* cdf = (float*)((char*)workspace + color_align(sizeof(PclColorHist)));
+    // the table area: [cdf 4096][hist_img 4096][hist_rgb 4096]
+    float* cdf = w.table;
     unsigned int* hist_img = (unsigned int*)(cdf + PCL_MOD_MAX_BINS);
     unsigned int* hist_rgb = hist_img + PCL_MOD_MAX_BINS;
     const int64_t npix = (int64_t)H * W;
@@ -445,30 +460,36 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_histogram_finish_kernel(const u
     for (int k = threadIdx.x; k < nbins; k += PCL_BLOCK) out[k] = normalize ? __fdiv_rn((float)hist[k], denom) : (float)hist[k];
 }
 
-extern "C" size_t pcl_histogram_workspace_bytes(int c0, int c1, int c2)
+// workspace of pcl_histogram: the image's maximum as a key (16 bytes), then the bins' counters
+struct HistogramWs { unsigned int *maxkey, *counts; };
+static size_t histogram_layout(void* base, int c0, int c1, int c2, HistogramWs* w)
 {
     if (c0 <= 0 || c1 <= 0 || c2 <= 0 || (int64_t)c0 * c1 * c2 > (1 << 24)) return 0;
-    return color_align(16) + color_align((size_t)c0 * c1 * c2 * sizeof(unsigned int));
+    PclCarve c{(char*)base, 0};
+    w->maxkey = (unsigned int*)c.take(16);
+    w->counts = (unsigned int*)c.take((size_t)c0 * c1 * c2 * sizeof(unsigned int));
+    return c.off;
 }
+
+extern "C" size_t pcl_histogram_workspace_bytes(int c0, int c1, int c2) { HistogramWs w; return histogram_layout(nullptr, c0, c1, c2, &w); }
 
 extern "C" int pcl_histogram(const float* img, const uint8_t* mask, int64_t npix, int c0, int c1, int c2, int normalize, float eps,
                              float* hist, void* workspace, size_t workspace_bytes, void* stream)
 {
-    size_t need = pcl_histogram_workspace_bytes(c0, c1, c2);
+    HistogramWs w;
+    const size_t need = histogram_layout(workspace, c0, c1, c2, &w);
     if (!img || !mask || !hist || !workspace || npix <= 0 || need == 0) return PCL_EINVAL;
     if (workspace_bytes < need) return PCL_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int nbins = c0 * c1 * c2;
-    unsigned int* maxkey = (unsigned int*)workspace;
-    unsigned int* counts = (unsigned int*)((char*)workspace + color_align(16));
     hipError_t e = hipMemsetAsync(workspace, 0, need, s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(pcl_img_max_kernel, dim3(color_grid(npix * 3)), dim3(PCL_BLOCK), 0, s, img, npix * 3, maxkey);
+    hipLaunchKernelGGL(pcl_img_max_kernel, dim3(color_grid(npix * 3)), dim3(PCL_BLOCK), 0, s, img, npix * 3, w.maxkey);
     if (nbins <= PCL_HIST_LDS_BINS)
-        hipLaunchKernelGGL((pcl_histogram_kernel<true>), dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, img, mask, npix, c0, c1, c2, maxkey, counts);
+        hipLaunchKernelGGL((pcl_histogram_kernel<true>), dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, img, mask, npix, c0, c1, c2, w.maxkey, w.counts);
     else
-        hipLaunchKernelGGL((pcl_histogram_kernel<false>), dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, img, mask, npix, c0, c1, c2, maxkey, counts);
-    hipLaunchKernelGGL(pcl_histogram_finish_kernel, dim3(1), dim3(PCL_BLOCK), 0, s, counts, nbins, normalize, eps, hist);
+        hipLaunchKernelGGL((pcl_histogram_kernel<false>), dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, img, mask, npix, c0, c1, c2, w.maxkey, w.counts);
+    hipLaunchKernelGGL(pcl_histogram_finish_kernel, dim3(1), dim3(PCL_BLOCK), 0, s, w.counts, nbins, normalize, eps, hist);
     PCL_LAUNCH_CHECK();
     return 0;
 }

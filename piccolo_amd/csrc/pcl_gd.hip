@@ -69,27 +69,17 @@ static int gd_depth_grid(int64_t n, int H, int W, int depth_h, int depth_w, floa
     return 0;
 }
 
-// Workspaces are carved in ONE place per family, a layout function that the size query runs without a base and the call with the
-// caller's buffer: raw(bytes) is the next region as it comes (null without a base), take(bytes) one that ends on a 256-byte boundary;
-// `off` is the size so far.
-static size_t gd_align(size_t v) { return (v + 255) & ~(size_t)255; }
-struct GdCarve {
-    char* base;
-    size_t off;
-    void* raw(size_t bytes) { void* p = base ? base + off : nullptr; off += bytes; return p; }
-    void* take(size_t bytes) { return raw(gd_align(bytes)); }
-};
-
+// (every workspace layout below is one function over a PclCarve, pcl_host.h: the size query runs it without a base)
 // stateless loss: pose records and partials back to back; with a depth grid the poses' z-buffers from the next 256-byte boundary on
 struct GdLossWs { PclPoseRec* recs; float* partials; uint32_t* zbuf; };
 static size_t gd_loss_layout(void* base, int64_t n, int B, const PclDepthGrid* grid, GdLossWs* w)
 {
-    GdCarve c{(char*)base, 0};
+    PclCarve c{(char*)base, 0};
     w->recs = (PclPoseRec*)c.raw((size_t)B * sizeof(PclPoseRec));
     w->partials = (float*)c.raw(pcl_partials_bytes(n, B));
     w->zbuf = nullptr;
     if (grid) {
-        c.off = gd_align(c.off);
+        c.off = pcl_align256(c.off);
         w->zbuf = (uint32_t*)c.raw(pcl_depth_zbuf_bytes(B, grid->Hd, grid->Wd));
     }
     return c.off;
@@ -252,7 +242,7 @@ static int gd_sets(int B, const pcl_gd_hyper* hyper_host)
 struct GdRunWs { float* partials[2]; uint32_t* zbuf[2]; };
 static size_t gd_run_layout(void* base, int64_t n, int B, int sets, const PclDepthGrid* grid, GdRunWs* w)
 {
-    GdCarve c{(char*)base, 0};
+    PclCarve c{(char*)base, 0};
     for (int k = 0; k < 2; k++) w->partials[k] = (float*)c.take(pcl_partials_bytes(n, B, sets));
     for (int k = 0; k < 2; k++) w->zbuf[k] = grid ? (uint32_t*)c.take(pcl_depth_zbuf_bytes(B, grid->Hd, grid->Wd)) : nullptr;
     return c.off;
@@ -509,7 +499,7 @@ static int gd_rooms_setup(const pcl_gd_room* rooms_host, int nrooms, int nimages
         e.block0 = (int)blocks; e.group0 = r * ngroups; e.partials = floats;
         g->t.block0[r] = (int)blocks;
         blocks += (int64_t)e.nchunks * ngroups;
-        floats += (int64_t)(gd_align((size_t)e.nchunks * per_room * PCL_NACC * sizeof(float)) / sizeof(float));
+        floats += (int64_t)(pcl_align256((size_t)e.nchunks * per_room * PCL_NACC * sizeof(float)) / sizeof(float));
     }
     if (blocks > 0x7fffffff) return PCL_EINVAL;
     g->nblk = (int)blocks;
@@ -535,7 +525,7 @@ static void gd_rooms_epilogue(const GdRooms& g, const PclRoomTable* table, void*
 struct GdRoomsWs { PclRoomTable* table; PclDepthTable* dtab; float* partials[2]; uint32_t* zset[2]; };
 static size_t gd_rooms_layout(void* base, const GdRooms& g, bool depth, size_t zset_bytes, GdRoomsWs* w)
 {
-    GdCarve c{(char*)base, 0};
+    PclCarve c{(char*)base, 0};
     w->table = (PclRoomTable*)c.take(sizeof(PclRoomTable));
     w->dtab = depth ? (PclDepthTable*)c.take(sizeof(PclDepthTable)) : nullptr;
     w->partials[0] = (float*)c.take(g.partials_bytes);

@@ -15,8 +15,9 @@
 // dozen tensor ops; the rendered image is never materialised here.
 // Only the middle block rows h = 1 .. num_split_h - 2 are used (utils.py:556); block j <-> (h = 1 + j / nsw, w = j % nsw).
 #include <stdlib.h>
+#include <algorithm>
 
-#include "pcl_device.h"
+#include "pcl_host.h"
 
 #define PCL_HBINS 512   // 8 x 8 x 8
 
@@ -767,8 +768,6 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_hist_codes_sets_kernel(const fl
     }
 }
 
-static size_t hist_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // can the tile-binned render be used at all for this cloud / panorama (16-bit pixel fields, 28-bit slots, <= 4096 tiles)?
 static bool hist_binned_ok(int64_t n, int H, int W)
 {
@@ -776,43 +775,63 @@ static bool hist_binned_ok(int64_t n, int H, int W)
     return nt <= 4096 && H < 65536 && W < 65536 && n < ((int64_t)1 << 28);
 }
 
-// bytes of the render area per candidate: the z-buffer of the splat path, or — when n is given — the larger of that and the
-// tile-binned path's bookkeeping (the run tables: nt n / 256 bytes — 4 % of the lists for a 2048 x 1024 panorama) + point lists (4 n
-// entries of 12 bytes: the exact worst case, nothing can overflow)
+// The render area of the tile-binned path, every table for all candidates back to back: the tiles' launch order heads[ncand][nt] (16 B),
+// their statistics stat[ncand][nt] (8 B), the run tables runs[ncand][nt][nb] (8 B: nt n / 256 bytes per candidate — 4 % of the lists for a
+// 2048 x 1024 panorama) and the point lists lists[ncand][3][cap], cap = 4 n entries of 12 bytes (the exact worst case, nothing can overflow).
+struct HistBinWs { int4* heads; unsigned long long* stat; uint2* runs; uint32_t* lists; };
+static size_t hist_bin_layout(void* base, int64_t n, int ncand, int H, int W, HistBinWs* b)
+{
+    const size_t nt = (size_t)((W + PCL_TS - 1) / PCL_TS) * ((H + PCL_TS - 1) / PCL_TS), nb = (size_t)((n + PCL_BIN_PTS - 1) / PCL_BIN_PTS);
+    PclCarve c{(char*)base, 0};
+    b->heads = (int4*)c.raw((size_t)ncand * nt * sizeof(int4));
+    b->stat = (unsigned long long*)c.raw((size_t)ncand * nt * sizeof(unsigned long long));
+    b->runs = (uint2*)c.raw((size_t)ncand * nt * nb * sizeof(uint2));
+    b->lists = (uint32_t*)c.raw((size_t)ncand * 3 * 4 * n * sizeof(uint32_t));
+    return c.off;
+}
+
+// bytes of the render area per candidate: the z-buffer of the splat path, or — when n is given and the tile-binned path applies (otherwise
+// the launch takes the splat path anyway: no lists to hold) — the larger of that and the tile-binned path's tables
 static size_t hist_render_bytes(int64_t n, int H, int W)
 {
-    size_t zb = (size_t)H * W * 8;
-    if (n <= 0) return zb;
-    const size_t nt = (size_t)((W + PCL_TS - 1) / PCL_TS) * ((H + PCL_TS - 1) / PCL_TS);
-    if (!hist_binned_ok(n, H, W)) return zb;       // the launch would take the splat path anyway: no lists to hold
-    const size_t nb = (size_t)((n + PCL_BIN_PTS - 1) / PCL_BIN_PTS);
-    size_t binned = nt * (16 + 8 + nb * 8) + (size_t)4 * n * 12;      // launch order, tile statistics, run tables + lists
+    const size_t zb = (size_t)H * W * 8;
+    if (n <= 0 || !hist_binned_ok(n, H, W)) return zb;
+    HistBinWs b;
+    const size_t binned = hist_bin_layout(nullptr, n, 1, H, W, &b);
     return binned > zb ? binned : zb;
 }
 
 // words per colour set of the colour codes (per-image colour sets: every set's codes start on a 256-byte boundary)
 static int64_t hist_code_stride(int64_t n) { return (n + 127) & ~(int64_t)127; }
 
-static size_t hist_workspace_bytes(int64_t n, int ncand, int H, int W, int nsh, int nsw, int nimages = 1, int nsets = 1)
+// The workspace of pcl_hist_trim_scores_images_sets, every region ending on a 256-byte boundary: the candidates' pose records, the render
+// area (hist_render_bytes per candidate), the counters — the query images' [nimages][nblk][512], then the candidates' [ncand][nblk][512] —
+// and, with n > 0 (the tile-binned path's workspace), the query masks [nimages][H * W] and the colour codes (one row per colour set).
+// n = 0: the smaller workspace of the z-buffer splat path.  0 for a shape no call accepts.
+struct HistWs { PclPoseRec* recs; void* render; unsigned int* ghist_q; unsigned int* ghist_c; uint8_t* qmask; uint16_t* codes; };
+static size_t hist_layout(void* base, int64_t n, int ncand, int H, int W, int nsh, int nsw, int nimages, int nsets, HistWs* w)
 {
     if (ncand <= 0 || nimages <= 0 || H <= 0 || W <= 0 || nsh < 3 || nsw < 1) return 0;
     const size_t nblk = (size_t)(nsh - 2) * nsw;
-    const size_t code_bytes = nsets > 1 ? (size_t)nsets * hist_code_stride(n) * sizeof(uint16_t) : (size_t)n * sizeof(uint16_t);
-    return hist_align((size_t)ncand * sizeof(PclPoseRec)) + hist_align((size_t)ncand * hist_render_bytes(n, H, W)) +
-           hist_align((size_t)nimages * nblk * PCL_HBINS * sizeof(float)) +
-           hist_align((size_t)(ncand + nimages) * nblk * PCL_HBINS * sizeof(unsigned int)) +
-           (n > 0 ? hist_align((size_t)nimages * H * W) + hist_align(code_bytes) : 0);     // query masks, colour codes (one row per colour set)
+    PclCarve c{(char*)base, 0};
+    w->recs = (PclPoseRec*)c.take((size_t)ncand * sizeof(PclPoseRec));
+    w->render = c.take((size_t)ncand * hist_render_bytes(n, H, W));
+    c.take((size_t)nimages * nblk * PCL_HBINS * sizeof(float));       // reserved: nobody reads it (once the normalised query histograms); sizes stay
+    w->ghist_q = (unsigned int*)c.take((size_t)(ncand + nimages) * nblk * PCL_HBINS * sizeof(unsigned int));
+    w->ghist_c = base ? w->ghist_q + (size_t)nimages * nblk * PCL_HBINS : nullptr;
+    w->qmask = nullptr, w->codes = nullptr;
+    if (n > 0) {                                                      // (the tile-binned path only)
+        w->qmask = (uint8_t*)c.take((size_t)nimages * H * W);
+        w->codes = (uint16_t*)c.take(nsets > 1 ? (size_t)nsets * hist_code_stride(n) * sizeof(uint16_t) : (size_t)n * sizeof(uint16_t));
+    }
+    return c.off;
 }
 
-extern "C" size_t pcl_hist_trim_workspace_bytes_n(int64_t n, int ncand, int H, int W, int nsh, int nsw)
-{
-    return n > 0 ? hist_workspace_bytes(n, ncand, H, W, nsh, nsw) : 0;
-}
+static size_t hist_workspace_bytes(int64_t n, int ncand, int H, int W, int nsh, int nsw, int nimages = 1, int nsets = 1)
+{ HistWs w; return hist_layout(nullptr, n, ncand, H, W, nsh, nsw, nimages, nsets, &w); }
 
-extern "C" size_t pcl_hist_trim_workspace_bytes(int ncand, int H, int W, int nsh, int nsw)
-{
-    return hist_workspace_bytes(0, ncand, H, W, nsh, nsw);
-}
+extern "C" size_t pcl_hist_trim_workspace_bytes_n(int64_t n, int ncand, int H, int W, int nsh, int nsw) { return n > 0 ? hist_workspace_bytes(n, ncand, H, W, nsh, nsw) : 0; }
+extern "C" size_t pcl_hist_trim_workspace_bytes(int ncand, int H, int W, int nsh, int nsw) { return hist_workspace_bytes(0, ncand, H, W, nsh, nsw); }
 
 extern "C" size_t pcl_hist_trim_images_workspace_bytes(int64_t n, int nimages, int cand_per_image, int H, int W, int nsh, int nsw)
 {
@@ -848,55 +867,37 @@ extern "C" int pcl_hist_trim_scores_images_sets(const float* cloud, int64_t n, i
     if (H / nsh <= 0 || W / nsw <= 0) return PCL_EINVAL;
     if (workspace_bytes < hist_workspace_bytes(0, ncand, H, W, nsh, nsw, nimages)) return PCL_EWORKSPACE;
     // a workspace sized with n (pcl_hist_trim_workspace_bytes_n / pcl_hist_trim_images_workspace_bytes) selects the tile-binned
-    // path, the smaller one of pcl_hist_trim_workspace_bytes(...) the z-buffer splat
+    // path, the smaller one of pcl_hist_trim_workspace_bytes(...) the z-buffer splat — how the tests compare the two bit for bit
     const bool roomy = workspace_bytes >= hist_workspace_bytes(n, ncand, H, W, nsh, nsw, nimages, color_sets);
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    PclPoseRec* recs = (PclPoseRec*)ws;
-    ws += hist_align((size_t)ncand * sizeof(PclPoseRec));
-    unsigned long long* zbuf = (unsigned long long*)ws;
-    ws += hist_align((size_t)ncand * hist_render_bytes(roomy ? n : 0, H, W));
+    HistWs w;
+    hist_layout(workspace, roomy ? n : 0, ncand, H, W, nsh, nsw, nimages, color_sets, &w);
     const int nblk = (nsh - 2) * nsw;
-    ws += hist_align((size_t)nimages * nblk * PCL_HBINS * sizeof(float));       // (rounds 1-5: the normalised query histograms; the layout is kept)
-    unsigned int* ghist_q = (unsigned int*)ws;                       // [nimages][nblk][512], then [ncand][nblk][512]
-    unsigned int* ghist_c = ghist_q + (size_t)nimages * nblk * PCL_HBINS;
-    ws += hist_align((size_t)(ncand + nimages) * nblk * PCL_HBINS * sizeof(unsigned int));
-    uint8_t* qmask = roomy ? (uint8_t*)ws : nullptr;                 // [nimages][H * W] (tile-binned path only)
-    uint16_t* codes = roomy ? (uint16_t*)(ws + hist_align((size_t)nimages * H * W)) : nullptr;
     const int64_t stride = pcl_cloud_stride(n);
     const int ntx = (W + PCL_TS - 1) / PCL_TS, nty = (H + PCL_TS - 1) / PCL_TS, nt = ntx * nty;
     const bool binned = roomy && hist_binned_ok(n, H, W);
-    // layout of the tile-binned render area: [ncand] x heads[nt] (16 B), [ncand] x stat[nt] (8 B), [ncand] x runs[nt][nb] (8 B), [ncand] x lists[3][cap]
-    unsigned long long* stat = binned ? (unsigned long long*)((int4*)zbuf + (int64_t)ncand * nt) : nullptr;
+    HistBinWs bin = {};
+    if (binned) hist_bin_layout(w.render, n, ncand, H, W, &bin);
     {
         const int64_t ghist_words = (int64_t)(ncand + nimages) * nblk * PCL_HBINS, stat_words = binned ? (int64_t)ncand * nt : 0;
-        int64_t work = binned ? n : 0;
-        if (work < (ghist_words >> 2)) work = ghist_words >> 2;
-        if (work < stat_words) work = stat_words;
-        if (work < ncand) work = ncand;
+        const int64_t work = std::max({binned ? n : (int64_t)0, ghist_words >> 2, stat_words, (int64_t)ncand});
         const int64_t blocks = (work + PCL_BLOCK - 1) / PCL_BLOCK;
-        hipLaunchKernelGGL(pcl_hist_prepare_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(PCL_BLOCK), 0, s, trans, rot, ncand, recs, ghist_q,
-                           ghist_words, stat, stat_words, cloud, n, stride, binned && !sets ? codes : (uint16_t*)nullptr);
+        hipLaunchKernelGGL(pcl_hist_prepare_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(PCL_BLOCK), 0, s, trans, rot, ncand, w.recs, w.ghist_q,
+                           ghist_words, bin.stat, stat_words, cloud, n, stride, binned && !sets ? w.codes : (uint16_t*)nullptr);
         if (binned && sets) {
             const int64_t cb = (n + PCL_BLOCK - 1) / PCL_BLOCK, per_set = (4096 + color_sets - 1) / color_sets;
             hipLaunchKernelGGL(pcl_hist_codes_sets_kernel, dim3((unsigned)(cb < per_set ? cb : per_set), (unsigned)color_sets), dim3(PCL_BLOCK), 0, s,
-                               cloud, n, stride, codes, hist_code_stride(n));
+                               cloud, n, stride, w.codes, hist_code_stride(n));
         }
     }
     hipLaunchKernelGGL(pcl_hist_accum_kernel<0>, dim3(nblk * PCL_HSUB_QUERY, nimages), dim3(PCL_BLOCK), 0, s, (const unsigned long long*)nullptr,
-                       cloud, stride, imgs, cpi, H, W, nsh, nsw, ghist_q, qmask);
-    // Tile-binned path when the caller sized the workspace for it (pcl_hist_trim_workspace_bytes_n); a caller that passes the smaller
-    // pcl_hist_trim_workspace_bytes gets the z-buffer splat — how the tests compare the two bit for bit.
-    const int64_t cap = 4 * n;
+                       cloud, stride, imgs, cpi, H, W, nsh, nsw, w.ghist_q, w.qmask);
     if (binned) {
         PclBinArgs b;
-        b.cloud = cloud; b.n = n; b.stride = stride; b.poses = recs; b.H = H; b.W = W; b.ntx = ntx; b.nt = nt;
+        b.cloud = cloud; b.n = n; b.stride = stride; b.poses = w.recs; b.H = H; b.W = W; b.ntx = ntx; b.nt = nt;
         b.nb = (int)((n + PCL_BIN_PTS - 1) / PCL_BIN_PTS);
-        b.heads = (int4*)zbuf;
-        b.stat = stat;
-        b.runs = (uint2*)(b.stat + (int64_t)ncand * nt);
-        b.lists = (uint32_t*)(b.runs + (int64_t)ncand * nt * b.nb);
-        b.cap = cap;
+        b.heads = bin.heads; b.stat = bin.stat; b.runs = bin.runs; b.lists = bin.lists;
+        b.cap = 4 * n;
         // margins of the fast projection's certificate: 1.5e-6 x the image size (three times the error budget in the kernel's comment),
         // at least 1e-3 pixel; PCL_BIN_EXACT=1: the reference formula for every point (A/B, and the cross-check of the certificate)
         const bool exact_env = PCL_KNOB(BIN_EXACT, 0) != 0;
@@ -911,19 +912,19 @@ extern "C" int pcl_hist_trim_scores_images_sets(const float* cloud, int64_t n, i
         // per pixel) nothing is dropped and the compares cost 9 us per 50 candidates — hence the density gate.  PCL_BIN_DEDUP=0 / 1 forces.
         const int dedup_env = PCL_KNOB(BIN_DEDUP, -1);
         const bool dedup = dedup_env >= 0 ? dedup_env != 0 : 4 * n >= (int64_t)H * W;
-        if (dedup) hipLaunchKernelGGL((pcl_bin_kernel<true>), pgrid, dim3(PCL_BLOCK), (size_t)2 * nt * sizeof(int), s, b);
-        else hipLaunchKernelGGL((pcl_bin_kernel<false>), pgrid, dim3(PCL_BLOCK), (size_t)2 * nt * sizeof(int), s, b);
+        pcl_with_flag(dedup, [&](auto d) {
+            hipLaunchKernelGGL((pcl_bin_kernel<decltype(d)::value>), pgrid, dim3(PCL_BLOCK), (size_t)2 * nt * sizeof(int), s, b);
+        });
         hipLaunchKernelGGL(pcl_bin_rank_kernel, dim3(ncand, (nt + 63) / 64), dim3(PCL_BLOCK), (size_t)(((nt + 3) & ~3) + PCL_BLOCK) * sizeof(int), s, b);
-        const int rt_env = PCL_KNOB(RESOLVE_THREADS, 0);
-        const int rt = rt_env == 256 ? 256 : 1024;      // measured: 256 threads LOSE at both shapes (0.434 -> 0.489 ms at 167k x 50, 1.35 -> 1.53 at 1M x 64)
-        if (sets) {
-            if (rt == 1024) hipLaunchKernelGGL(pcl_tile_resolve_hist_sets_kernel<1024>, dim3(ncand, nt), dim3(1024), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c,
-                                               hist_code_stride(n));
-            else hipLaunchKernelGGL(pcl_tile_resolve_hist_sets_kernel<256>, dim3(ncand, nt), dim3(256), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c,
-                                    hist_code_stride(n));
-        } else if (rt == 1024) hipLaunchKernelGGL(pcl_tile_resolve_hist_kernel<1024>, dim3(ncand, nt), dim3(1024), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c);
-        else hipLaunchKernelGGL(pcl_tile_resolve_hist_kernel<256>, dim3(ncand, nt), dim3(256), 0, s, b, qmask, codes, cpi, nsh, nsw, ghist_c);
+        // measured: 256 threads LOSE at both shapes (0.434 -> 0.489 ms at 167k x 50, 1.35 -> 1.53 at 1M x 64)
+        pcl_with_flag(PCL_KNOB(RESOLVE_THREADS, 0) == 256, [&](auto narrow) {
+            constexpr int RT = decltype(narrow)::value ? 256 : 1024;
+            if (sets) hipLaunchKernelGGL(pcl_tile_resolve_hist_sets_kernel<RT>, dim3(ncand, nt), dim3(RT), 0, s, b, w.qmask, w.codes, cpi, nsh, nsw, w.ghist_c,
+                                         hist_code_stride(n));
+            else hipLaunchKernelGGL(pcl_tile_resolve_hist_kernel<RT>, dim3(ncand, nt), dim3(RT), 0, s, b, w.qmask, w.codes, cpi, nsh, nsw, w.ghist_c);
+        });
     } else {
+        unsigned long long* zbuf = (unsigned long long*)w.render;
         hipLaunchKernelGGL(pcl_fill_u64b_kernel, dim3(2048), dim3(PCL_BLOCK), 0, s, zbuf, (int64_t)ncand * H * W, ~0ull);
         // 64 x 64-pixel LDS window (32 KB of 64-bit cells) per 256 consecutive (Morton-ordered) points: a compact surface
         // patch whose splats nearly all land inside the window.  Measured at cfg-2 size, 64 candidates (whole trimming
@@ -932,15 +933,11 @@ extern "C" int pcl_hist_trim_scores_images_sets(const float* cloud, int64_t n, i
         // 256-512 points: 64x96 3.8, 48x64 4.5, 48x48 4.0 ms.
         constexpr int TH = 64, TW = 64, PTS = 256;
         hipLaunchKernelGGL((pcl_splat_poses_kernel<TH, TW, PTS>), dim3((unsigned)((n + PTS - 1) / PTS), (unsigned)ncand),
-                           dim3(PCL_BLOCK), 0, s, cloud, n, stride, recs, H, W, zbuf);
-        if (sets)
-            hipLaunchKernelGGL(pcl_hist_accum_sets_kernel, dim3(nblk * PCL_HSUB, ncand), dim3(PCL_BLOCK), 0, s, zbuf, cloud, stride, imgs, cpi, H, W,
-                               nsh, nsw, ghist_c, (uint8_t*)nullptr);
-        else
-            hipLaunchKernelGGL(pcl_hist_accum_kernel<1>, dim3(nblk * PCL_HSUB, ncand), dim3(PCL_BLOCK), 0, s, zbuf, cloud, stride, imgs, cpi, H, W,
-                               nsh, nsw, ghist_c, (uint8_t*)nullptr);
+                           dim3(PCL_BLOCK), 0, s, cloud, n, stride, w.recs, H, W, zbuf);
+        hipLaunchKernelGGL(sets ? pcl_hist_accum_sets_kernel : pcl_hist_accum_kernel<1>, dim3(nblk * PCL_HSUB, ncand), dim3(PCL_BLOCK), 0, s, zbuf, cloud,
+                           stride, imgs, cpi, H, W, nsh, nsw, w.ghist_c, (uint8_t*)nullptr);
     }
-    hipLaunchKernelGGL(pcl_hist_final_kernel, dim3(nblk, ncand), dim3(PCL_BLOCK), 0, s, (const unsigned int*)ghist_c, (const unsigned int*)ghist_q, nimg, inter,
+    hipLaunchKernelGGL(pcl_hist_final_kernel, dim3(nblk, ncand), dim3(PCL_BLOCK), 0, s, (const unsigned int*)w.ghist_c, (const unsigned int*)w.ghist_q, nimg, inter,
                        nproj, cpi);
     PCL_LAUNCH_CHECK();
     return 0;

@@ -1,5 +1,6 @@
 // pcl_host.h — host functions that one translation unit of the library defines and another calls (none of them is part of the C ABI),
-// declared once, and the helper that turns a runtime choice of kernel instance into a compile-time one.
+// declared once, the carve helper behind every workspace layout, and the helpers that turn a runtime choice of kernel instance into a
+// compile-time one.
 #pragma once
 #include <type_traits>
 
@@ -31,6 +32,25 @@ int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_
 size_t pcl_depth_zbuf_bytes(int B, int Hd, int Wd);
 int pcl_launch_zbuffers(const float* cloud, int64_t n, const PclPoseRec* poses, int B, const PclDepthGrid& g, int zstride, uint32_t* zbuf, bool fill,
                         hipStream_t s);
+
+// Workspaces are carved in ONE place per family, a layout function that the size query runs without a base and the call with the
+// caller's buffer: raw(bytes) is the next region as it comes (null without a base), take(bytes) one that ends on a 256-byte boundary;
+// `off` is the size so far.
+static inline size_t pcl_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct PclCarve {
+    char* base;
+    size_t off;
+    void* raw(size_t bytes) { void* p = base ? base + off : nullptr; off += bytes; return p; }
+    void* take(size_t bytes) { return raw(pcl_align256(bytes)); }
+};
+
+// f(std::true_type{}) / f(std::false_type{}) for a runtime flag
+template <class F>
+static inline void pcl_with_flag(bool v, F&& f)
+{
+    if (v) return f(std::true_type{});
+    f(std::false_type{});
+}
 
 // f(std::integral_constant<int, G>{}) for the runtime G: 4 where MAXG admits it, 2, else 1 — so that a kernel template with instances for
 // G <= MAXG only (the rooms kernels: 1 and 2) gains none

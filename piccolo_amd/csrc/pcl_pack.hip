@@ -1,7 +1,7 @@
 // pcl_pack.hip — one-time repacking of the reference's tensors into the layouts the loss kernel streams.
 //   cloud : row-major (N,3) xyz + (N,3) rgb  (localize.py:159-164)  -> 6 SoA planes x,y,z,-r,-g,-b, optionally re-ordered
 //   pano  : (H,W,3) float image              (localize.py:167-170)  -> zero-bordered (H+2, W+2) RGBA float4
-#include "pcl_device.h"
+#include "pcl_host.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -177,7 +177,6 @@ extern "C" int pcl_morton_keys(const float* xyz, int64_t n, const float* lo, con
 }
 
 // ---- Morton order of a cloud, entirely on the device: bounding box -> 63-bit keys -> radix sort of (key, index) pairs.
-// workspace: [box: 6 ordered-uint words][keys n][keys sorted n][iota n][rocPRIM temp]
 __device__ __forceinline__ unsigned int pcl_ordered_key(float v)
 {
     unsigned int b = __float_as_uint(v);
@@ -227,7 +226,6 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_morton_box_kernel(const float* 
     iota[i] = i;
 }
 
-static size_t order_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static size_t order_sort_temp_bytes(int64_t n)
 {
     size_t bytes = 0;
@@ -236,34 +234,40 @@ static size_t order_sort_temp_bytes(int64_t n)
     return bytes;
 }
 
-extern "C" size_t pcl_cloud_order_workspace_bytes(int64_t n)
+// workspace of pcl_cloud_order: the bounding box (6 ordered-uint words in 64 bytes), the keys, the sorted keys, the identity permutation, the sort's temporary storage
+struct OrderWs { unsigned int* box; unsigned long long *keys, *keys_sorted; int64_t* iota; void* temp; size_t temp_bytes; };
+static size_t order_layout(void* base, int64_t n, OrderWs* w)
 {
     if (n <= 0) return 0;
-    return order_align(64) + 3 * order_align((size_t)n * 8) + order_align(order_sort_temp_bytes(n));
+    PclCarve c{(char*)base, 0};
+    w->box = (unsigned int*)c.take(64);
+    w->keys = (unsigned long long*)c.take((size_t)n * 8);
+    w->keys_sorted = (unsigned long long*)c.take((size_t)n * 8);
+    w->iota = (int64_t*)c.take((size_t)n * 8);
+    w->temp_bytes = order_sort_temp_bytes(n);
+    w->temp = c.take(w->temp_bytes);
+    return c.off;
 }
+
+extern "C" size_t pcl_cloud_order_workspace_bytes(int64_t n) { OrderWs w; return order_layout(nullptr, n, &w); }
 
 // order[i] = index of the point that goes to packed slot i (Morton order of xyz inside its bounding box); feed it to
 // pcl_cloud_pack.  Equal keys keep their original relative order (stable LSD radix sort).
 extern "C" int pcl_cloud_order(const float* xyz, int64_t n, int64_t* order, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!xyz || !order || !workspace || n <= 0 || n > PCL_MAX_POINTS) return PCL_EINVAL;
-    if (workspace_bytes < pcl_cloud_order_workspace_bytes(n)) return PCL_EWORKSPACE;
+    OrderWs w;
+    if (workspace_bytes < order_layout(workspace, n, &w)) return PCL_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    unsigned int* box = (unsigned int*)ws; ws += order_align(64);
-    unsigned long long* keys = (unsigned long long*)ws; ws += order_align((size_t)n * 8);
-    unsigned long long* keys_sorted = (unsigned long long*)ws; ws += order_align((size_t)n * 8);
-    int64_t* iota = (int64_t*)ws; ws += order_align((size_t)n * 8);
-    hipError_t e = hipMemsetAsync(box, 0xff, 12, s);                          // lo = max key
-    if (e == hipSuccess) e = hipMemsetAsync(box + 3, 0, 12, s);               // hi = min key
+    hipError_t e = hipMemsetAsync(w.box, 0xff, 12, s);                          // lo = max key
+    if (e == hipSuccess) e = hipMemsetAsync(w.box + 3, 0, 12, s);               // hi = min key
     if (e != hipSuccess) return (int)e;
     int64_t blocks = (n + PCL_BLOCK - 1) / PCL_BLOCK;
-    hipLaunchKernelGGL(pcl_bbox_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(PCL_BLOCK), 0, s, xyz, n, box);
-    hipLaunchKernelGGL(pcl_morton_box_kernel, dim3((unsigned)blocks), dim3(PCL_BLOCK), 0, s, xyz, n, box, keys, iota);
+    hipLaunchKernelGGL(pcl_bbox_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(PCL_BLOCK), 0, s, xyz, n, w.box);
+    hipLaunchKernelGGL(pcl_morton_box_kernel, dim3((unsigned)blocks), dim3(PCL_BLOCK), 0, s, xyz, n, w.box, w.keys, w.iota);
     PCL_LAUNCH_CHECK();
-    size_t temp_bytes = order_sort_temp_bytes(n);
-    e = rocprim::radix_sort_pairs(ws, temp_bytes, (const unsigned long long*)keys, keys_sorted, (const int64_t*)iota, order, (size_t)n, 0, 63,
-                                  s, false);
+    e = rocprim::radix_sort_pairs(w.temp, w.temp_bytes, (const unsigned long long*)w.keys, w.keys_sorted, (const int64_t*)w.iota, order, (size_t)n, 0,
+                                  63, s, false);
     return e == hipSuccess ? 0 : (int)e;
 }
 

@@ -501,8 +501,6 @@ __global__ void __launch_bounds__(256) pcl_trim_finish_kernel(const float* __res
     if (count_table) count_table[o] = (float)s1;
 }
 
-static size_t trim_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // ---------------------------------------------------------------- the row-sorted work list (round 6)
 // Why.  Every (chunk, slot) block streams its own region of the texture: with the blocks in (chunk, slot) order an XCD's L2 sees, for one
 // chunk, the regions of hundreds of views all over the panorama — no line is touched twice before it is evicted, and the launch moved
@@ -594,22 +592,17 @@ static size_t trim_sort_temp_bytes(size_t M)
     return b16 > b32 ? b16 : b32;
 }
 
+// bytes per texel of the trim launch's panorama: the two paired 8-bit layouts, else the loss kernel's formats
+static int trim_texel_bytes(int pano_format) { return pano_format == PCL_PANO_U8P ? 4 : pano_format == PCL_PANO_U8V ? 8 : pcl_texel_bytes(pano_format); }
+
 // bands: a multiple of 8, sized so that one band of the texture is about 2 MB (an XCD's L2 is 4 MB and also holds the cloud chunks)
 static int trim_bands(int pano_format, int H, int W)
 {
-    const int64_t tex = (int64_t)(H + 3) * (W + 2) * (pano_format == PCL_PANO_U8P ? 4 : pano_format == PCL_PANO_U8V ? 8 : pcl_texel_bytes(pano_format));
+    const int64_t tex = (int64_t)(H + 3) * (W + 2) * trim_texel_bytes(pano_format);
     int per_xcd = (int)((tex / 8 + PCL_KNOB(TRIM_BAND_BYTES, 2500000) - 1) / PCL_KNOB(TRIM_BAND_BYTES, 2500000));
     if (per_xcd < 1) per_xcd = 1;
     if (per_xcd > 64) per_xcd = 64;
     return 8 * per_xcd;
-}
-
-static size_t trim_workspace_bytes(int64_t n, int K, int ngroups, int nimages)
-{
-    if (n <= 0 || K <= 0 || ngroups <= 0 || nimages <= 0) return 0;
-    int nchunks, seg_len, sb, sr;
-    pcl_plan_for_groups(n, ngroups * K, &nchunks, &seg_len, &sb, &sr);
-    return trim_align((size_t)ngroups * K * sizeof(PclPoseRec)) + trim_align((size_t)nchunks * nimages * ngroups * K * PCL_NACC * sizeof(float));
 }
 
 static int trim_plan_chunks(int64_t n, int nslots)
@@ -619,19 +612,42 @@ static int trim_plan_chunks(int64_t n, int nslots)
     return nchunks;
 }
 
+// workspace of pcl_trim_loss_images_sets: the slots' pose records, then the launch's partial sums [nchunks][nimages][nslots][PCL_NACC]
+struct TrimWs { PclPoseRec* recs; float* partials; };
+static size_t trim_layout(void* base, int64_t n, int K, int ngroups, int nimages, TrimWs* w)
+{
+    if (n <= 0 || K <= 0 || ngroups <= 0 || nimages <= 0) return 0;
+    PclCarve c{(char*)base, 0};
+    w->recs = (PclPoseRec*)c.take((size_t)ngroups * K * sizeof(PclPoseRec));
+    w->partials = (float*)c.take((size_t)trim_plan_chunks(n, ngroups * K) * nimages * ngroups * K * PCL_NACC * sizeof(float));
+    return c.off;
+}
+
 extern "C" size_t pcl_trim_order_bytes(int64_t n, int K, int ngroups)
 {
     if (n <= 0 || K <= 0 || ngroups <= 0) return 0;
-    return sizeof(PclTrimOrderHdr) + trim_align((size_t)trim_plan_chunks(n, ngroups * K) * ngroups * K * sizeof(int));
+    return sizeof(PclTrimOrderHdr) + pcl_align256((size_t)trim_plan_chunks(n, ngroups * K) * ngroups * K * sizeof(int));
 }
 
-extern "C" size_t pcl_trim_order_workspace_bytes(int64_t n, int K, int ngroups)
+// workspace of pcl_trim_order: the slots' pose records, the chunks' centroids, two key arrays and one value array of M = chunks x slots
+// words, and the sorts' temporary storage
+struct TrimOrderWs { PclPoseRec* recs; float* cent; unsigned int *k0, *k1, *v0; void* temp; size_t temp_bytes; };
+static size_t trim_order_layout(void* base, int64_t n, int K, int ngroups, TrimOrderWs* w)
 {
     if (n <= 0 || K <= 0 || ngroups <= 0) return 0;
     const size_t nchunks = (size_t)trim_plan_chunks(n, ngroups * K), M = nchunks * ngroups * K;
-    return trim_align((size_t)ngroups * K * sizeof(PclPoseRec)) + trim_align(nchunks * 4 * sizeof(float)) + 3 * trim_align(M * sizeof(int)) +
-           trim_align(trim_sort_temp_bytes(M));
+    PclCarve c{(char*)base, 0};
+    w->recs = (PclPoseRec*)c.take((size_t)ngroups * K * sizeof(PclPoseRec));
+    w->cent = (float*)c.take(nchunks * 4 * sizeof(float));
+    w->k0 = (unsigned int*)c.take(M * sizeof(int));
+    w->k1 = (unsigned int*)c.take(M * sizeof(int));
+    w->v0 = (unsigned int*)c.take(M * sizeof(int));
+    w->temp_bytes = trim_sort_temp_bytes(M);
+    w->temp = c.take(w->temp_bytes);
+    return c.off;
 }
+
+extern "C" size_t pcl_trim_order_workspace_bytes(int64_t n, int K, int ngroups) { TrimOrderWs w; return trim_order_layout(nullptr, n, K, ngroups, &w); }
 
 extern "C" int pcl_trim_order(const float* cloud, int64_t n, int pano_format, int H, int W, const float* trans, int K, const float* rot, int R,
                               const void* groups, int ngroups, void* order, void* workspace, size_t workspace_bytes, void* stream)
@@ -641,7 +657,8 @@ extern "C" int pcl_trim_order(const float* cloud, int64_t n, int pano_format, in
     if (pano_format < PCL_PANO_F32 || pano_format > PCL_PANO_U8V) return PCL_EINVAL;
     const int nslots = ngroups * K;
     if ((int64_t)nslots > (1 << 24)) return PCL_EINVAL;
-    if (workspace_bytes < pcl_trim_order_workspace_bytes(n, K, ngroups)) return PCL_EWORKSPACE;
+    TrimOrderWs w;
+    if (workspace_bytes < trim_order_layout(workspace, n, K, ngroups, &w)) return PCL_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const PclTrimHeader* hdr = (const PclTrimHeader*)groups;
     const PclTrimGroup* grs = (const PclTrimGroup*)(hdr + 1);
@@ -653,41 +670,52 @@ extern "C" int pcl_trim_order(const float* cloud, int64_t n, int pano_format, in
     const size_t M = (size_t)M64;
     so.cloud = cloud; so.n = n; so.stride = pcl_cloud_stride(n); so.nslots = nslots;
     so.bands = trim_bands(pano_format, H, W);
-    char* w = (char*)workspace;
-    PclPoseRec* recs = (PclPoseRec*)w; w += trim_align((size_t)nslots * sizeof(PclPoseRec));
-    so.poses = recs;
-    so.cent = (float*)w; w += trim_align((size_t)so.nchunks * 4 * sizeof(float));
-    unsigned int* k0 = (unsigned int*)w; w += trim_align(M * sizeof(int));
-    unsigned int* k1 = (unsigned int*)w; w += trim_align(M * sizeof(int));
-    unsigned int* v0 = (unsigned int*)w; w += trim_align(M * sizeof(int));
-    void* temp = w;
-    size_t temp_bytes = trim_sort_temp_bytes(M);
+    so.poses = w.recs; so.cent = w.cent;
     PclTrimOrderHdr* oh = (PclTrimOrderHdr*)order;
     unsigned int* list = (unsigned int*)(oh + 1);
     hipLaunchKernelGGL(pcl_trim_order_hdr_kernel, dim3(1), dim3(64), 0, s, oh, 0, 0, 0, 0);
-    hipLaunchKernelGGL(pcl_trim_pose_setup_kernel, dim3((nslots + 255) / 256), dim3(256), 0, s, trans, rot, K, hdr, grs, ngroups, recs);
+    hipLaunchKernelGGL(pcl_trim_pose_setup_kernel, dim3((nslots + 255) / 256), dim3(256), 0, s, trans, rot, K, hdr, grs, ngroups, w.recs);
     hipLaunchKernelGGL(pcl_trim_centroid_kernel, dim3(so.nchunks), dim3(PCL_BLOCK), 0, s, so);
     const unsigned nb = (unsigned)((M + PCL_BLOCK - 1) / PCL_BLOCK);
-    hipLaunchKernelGGL(pcl_trim_rowkey_kernel, dim3(nb), dim3(PCL_BLOCK), 0, s, so, k0, v0);
+    hipLaunchKernelGGL(pcl_trim_rowkey_kernel, dim3(nb), dim3(PCL_BLOCK), 0, s, so, w.k0, w.v0);
     PCL_LAUNCH_CHECK();
     // rank by row (16-bit keys, stable): v0 -> list
-    hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, (const unsigned int*)k0, k1, (const unsigned int*)v0, list, M, 0, 16, s, false);
+    hipError_t e = rocprim::radix_sort_pairs(w.temp, w.temp_bytes, (const unsigned int*)w.k0, w.k1, (const unsigned int*)w.v0, list, M, 0, 16, s, false);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(pcl_trim_bandkey_kernel, dim3(nb), dim3(PCL_BLOCK), 0, s, so, (const unsigned int*)list, k0);
-    e = hipMemcpyAsync(v0, list, M * sizeof(int), hipMemcpyDeviceToDevice, s);
+    hipLaunchKernelGGL(pcl_trim_bandkey_kernel, dim3(nb), dim3(PCL_BLOCK), 0, s, so, (const unsigned int*)list, w.k0);
+    e = hipMemcpyAsync(w.v0, list, M * sizeof(int), hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return (int)e;
     // (band, chunk)-major, stable: inside a cell the row ranking survives
-    e = rocprim::radix_sort_pairs(temp, temp_bytes, (const unsigned int*)k0, k1, (const unsigned int*)v0, list, M, 0, 32, s, false);
+    e = rocprim::radix_sort_pairs(w.temp, w.temp_bytes, (const unsigned int*)w.k0, w.k1, (const unsigned int*)w.v0, list, M, 0, 32, s, false);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(pcl_trim_order_hdr_kernel, dim3(1), dim3(64), 0, s, oh, PCL_TRIM_ORDER_MAGIC, so.nchunks, nslots, so.bands);
     PCL_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" size_t pcl_trim_loss_workspace_bytes(int64_t n, int K, int ngroups) { return trim_workspace_bytes(n, K, ngroups, 1); }
 extern "C" size_t pcl_trim_loss_images_workspace_bytes(int64_t n, int K, int ngroups, int nimages)
 {
-    return nimages <= PCL_TRIM_MAX_IMAGES ? trim_workspace_bytes(n, K, ngroups, nimages) : 0;
+    TrimWs w;
+    return nimages <= PCL_TRIM_MAX_IMAGES ? trim_layout(nullptr, n, K, ngroups, nimages, &w) : 0;
+}
+extern "C" size_t pcl_trim_loss_workspace_bytes(int64_t n, int K, int ngroups) { return pcl_trim_loss_images_workspace_bytes(n, K, ngroups, 1); }
+
+// the trim launch of a runtime texel format (one the caller validated): pcl_trim_sets_kernel<FMT> for per-image colour sets, else pcl_trim_kernel<FMT>
+template <int FMT, bool SETS>
+static void trim_launch(const PclTrimArgs& a, unsigned nblk, hipStream_t s)
+{
+    hipLaunchKernelGGL(SETS ? pcl_trim_sets_kernel<FMT> : pcl_trim_kernel<FMT>, dim3(nblk), dim3(PCL_BLOCK), 0, s, a);
+}
+template <bool SETS>
+static void trim_launch_fmt(int pano_format, const PclTrimArgs& a, unsigned nblk, hipStream_t s)
+{
+    switch (pano_format) {
+    case PCL_PANO_U8P: return trim_launch<PCL_PANO_U8P, SETS>(a, nblk, s);
+    case PCL_PANO_U8V: return trim_launch<PCL_PANO_U8V, SETS>(a, nblk, s);
+    case PCL_PANO_U8: return trim_launch<PCL_PANO_U8, SETS>(a, nblk, s);
+    case PCL_PANO_F16: return trim_launch<PCL_PANO_F16, SETS>(a, nblk, s);
+    default: return trim_launch<PCL_PANO_F32, SETS>(a, nblk, s);
+    }
 }
 
 // color_sets: 1 = every image reads the cloud's colours (planes 3..5), nimages = image i reads colour set i (pcl_cloud_pack_sets)
@@ -705,22 +733,21 @@ extern "C" int pcl_trim_loss_images_sets(const float* cloud, int64_t n, int colo
     if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16 && pano_format != PCL_PANO_U8P &&
         pano_format != PCL_PANO_U8V)
         return PCL_EINVAL;
-    if ((int64_t)(H + 3) * (W + 2) * (pano_format == PCL_PANO_U8P ? 4 : pano_format == PCL_PANO_U8V ? 8 : pcl_texel_bytes(pano_format)) >= ((int64_t)1 << 31))
+    if ((int64_t)(H + 3) * (W + 2) * trim_texel_bytes(pano_format) >= ((int64_t)1 << 31))
         return PCL_EINVAL;
     if ((int64_t)ngroups * K * nimages > (1 << 24)) return PCL_EINVAL;
-    if (workspace_bytes < trim_workspace_bytes(n, K, ngroups, nimages)) return PCL_EWORKSPACE;
+    TrimWs w;
+    if (workspace_bytes < trim_layout(workspace, n, K, ngroups, nimages, &w)) return PCL_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const PclTrimHeader* hdr = (const PclTrimHeader*)groups;
     const PclTrimGroup* grs = (const PclTrimGroup*)(hdr + 1);
     const int nslots = ngroups * K;
-    PclPoseRec* recs = (PclPoseRec*)workspace;
-    float* partials = (float*)((char*)workspace + trim_align((size_t)nslots * sizeof(PclPoseRec)));
     // every entry starts as NaN (0xFFFFFFFF): what the finish kernel does not write — `ngroups` below the table's group count,
     // a blob built from another table — ranks last in the caller's selection instead of as whatever the buffer held
     hipError_t me = hipMemsetAsync(loss_tables, 0xFF, (size_t)nimages * K * R * sizeof(float), s);
     if (me == hipSuccess && count_tables) me = hipMemsetAsync(count_tables, 0, (size_t)nimages * K * R * sizeof(float), s);
     if (me != hipSuccess) return (int)me;
-    hipLaunchKernelGGL(pcl_trim_pose_setup_kernel, dim3((nslots + 255) / 256), dim3(256), 0, s, trans, rot, K, hdr, grs, ngroups, recs);
+    hipLaunchKernelGGL(pcl_trim_pose_setup_kernel, dim3((nslots + 255) / 256), dim3(256), 0, s, trans, rot, K, hdr, grs, ngroups, w.recs);
     PclTrimArgs a;
     a.cloud = cloud; a.n = n; a.stride = pcl_cloud_stride(n);
     for (int i = 0; i < PCL_TRIM_MAX_IMAGES; i++) a.pano[i] = i < nimages ? panos_host[i] : nullptr;
@@ -731,24 +758,15 @@ extern "C" int pcl_trim_loss_images_sets(const float* cloud, int64_t n, int colo
         a.xcd_images = nimages % 8 == 0 && PCL_KNOB(TRIM_XCD_IMAGES, 1) != 0 ? 1 : 0;
     }
     a.dims = pcl_make_dims(H, W, pano_format == PCL_PANO_U8P || pano_format == PCL_PANO_U8V ? PCL_PANO_U8 : pano_format);       // (the same levels, the same constants)
-    a.poses = recs; a.hdr = hdr; a.groups = grs; a.K = K; a.nslots = nslots; a.partials = partials;
+    a.poses = w.recs; a.hdr = hdr; a.groups = grs; a.K = K; a.nslots = nslots; a.partials = w.partials;
     // the chunks of the SINGLE-image launch, whatever the number of images: per-image tables keep that launch's bits
     pcl_plan_for_groups(n, nslots, &a.nchunks, &a.seg_len, &a.steps_base, &a.steps_rem);
     const int64_t nblk = (int64_t)a.nchunks * nslots * nimages;
     if (nblk > 0x7fffffffll) return PCL_EINVAL;
     a.order = (const int*)order;
-    if (color_sets > 1) {
-        if (pano_format == PCL_PANO_U8P) hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_U8P>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-        else if (pano_format == PCL_PANO_U8V) hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_U8V>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-        else if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_U8>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-        else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_F16>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL(pcl_trim_sets_kernel<PCL_PANO_F32>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-    } else if (pano_format == PCL_PANO_U8P) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_U8P>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-    else if (pano_format == PCL_PANO_U8V) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_U8V>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-    else if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_U8>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-    else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_F16>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL(pcl_trim_kernel<PCL_PANO_F32>, dim3((unsigned)nblk), dim3(PCL_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(pcl_trim_finish_kernel, dim3((nimages * nslots * PCL_TRIM_Y + 255) / 256), dim3(256), 0, s, partials, a.nchunks, nslots,
+    if (color_sets > 1) trim_launch_fmt<true>(pano_format, a, (unsigned)nblk, s);
+    else trim_launch_fmt<false>(pano_format, a, (unsigned)nblk, s);
+    hipLaunchKernelGGL(pcl_trim_finish_kernel, dim3((nimages * nslots * PCL_TRIM_Y + 255) / 256), dim3(256), 0, s, w.partials, a.nchunks, nslots,
                        nimages, K, R, hdr, grs, loss_tables, count_tables);
     PCL_LAUNCH_CHECK();
     return 0;

@@ -436,53 +436,14 @@ class TrimOrder:
                                       _ptr(groups.data), groups.ngroups, _ptr(self.data), _ptr(ws), nws, _stream()), "pcl_trim_order")
 
 
-def trim_loss_table(cloud, pano, trans, groups, return_count=False, order=None):
-    """utils.py:484-499 for all pairs: (K, R) float GPU tensor loss_table[i, j] = forward-only sampling loss of (trans[i], rot[j]),
-    rotations of one (pitch, roll) class sharing the projection (csrc/pcl_trim.hip).  order: a TrimOrder of this cloud / grid."""
+TRIM_MAX_IMAGES = 32       # pcl_trim_loss_images_sets: query images per launch
+
+
+def _trim_tables(cloud, panos, trans, groups, return_count, order, sets=False):
+    """(I, K, R) loss tables (and counts) of the panoramas, TRIM_MAX_IMAGES per launch; sets: image i reads colour set i (one launch)"""
     lib = _lib.load()
-    _unweighted(cloud, "trim_loss_table")
     trans = _dev(trans).reshape(-1, 3)
-    K = int(trans.shape[0])
-    table = torch.empty(K, groups.R, dtype=F32, device=trans.device)
-    count = torch.empty(K, groups.R, dtype=F32, device=trans.device) if return_count else None
-    nws = lib.pcl_trim_loss_workspace_bytes(cloud.n, K, groups.ngroups)
-    ws = _bytes(nws)
-    _lib.check(lib.pcl_trim_loss(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans), K, _ptr(groups.rot),
-                                 groups.R, _ptr(groups.data), groups.ngroups, _ptr(order.data) if order is not None else None, _ptr(table), _ptr(count),
-                                 _ptr(ws), nws, _stream()),
-               "pcl_trim_loss")
-    return (table, count) if return_count else table
-
-
-TRIM_MAX_IMAGES = 32       # pcl_trim_loss_images: query images per launch
-
-
-def trim_loss_tables(cloud, panos, trans, groups, return_count=False, order=None):
-    """trim_loss_table for several query images of one room in ONE launch: (I, K, R) float GPU tensor; image i's table has the
-    bits of trim_loss_table(cloud, panos[i], ...) (same chunks of the cloud).  panos: list of Pano of one size / texel format.
-    A cloud with colour sets (Cloud.with_color_sets, one per image): image i reads set i — its table is trim_loss_table over
-    Cloud(xyz, rgbs[i]), bit for bit."""
-    lib = _lib.load()
-    _unweighted(cloud, "trim_loss_tables")
-    trans = _dev(trans).reshape(-1, 3)
-    K, I = int(trans.shape[0]), len(panos)
-    p0 = panos[0]
-    if any((p.H, p.W, p.fmt) != (p0.H, p0.W, p0.fmt) for p in panos):
-        raise ValueError("all panoramas of a launch must share size and texel format")
-    if cloud.color_sets > 1:
-        if cloud.color_sets != I:
-            raise ValueError("a cloud of %d colour sets for %d images" % (cloud.color_sets, I))
-        if I > TRIM_MAX_IMAGES:
-            raise ValueError("trim_loss_tables: at most %d images per call with colour sets" % TRIM_MAX_IMAGES)
-        table = torch.empty(I, K, groups.R, dtype=F32, device=trans.device)
-        count = torch.empty(I, K, groups.R, dtype=F32, device=trans.device) if return_count else None
-        nws = lib.pcl_trim_loss_images_workspace_bytes(cloud.n, K, groups.ngroups, I)
-        ws = _bytes(nws)
-        arr = (ctypes.c_void_p * I)(*[p.data.data_ptr() for p in panos])
-        _lib.check(lib.pcl_trim_loss_images_sets(_ptr(cloud.data), cloud.n, I, arr, I, p0.fmt, p0.H, p0.W, _ptr(trans), K, _ptr(groups.rot),
-                                                 groups.R, _ptr(groups.data), groups.ngroups, _ptr(order.data) if order is not None else None,
-                                                 _ptr(table), _ptr(count), _ptr(ws), nws, _stream()), "pcl_trim_loss_images_sets")
-        return (table, count) if return_count else table
+    K, I, p0 = int(trans.shape[0]), len(panos), panos[0]
     table = torch.empty(I, K, groups.R, dtype=F32, device=trans.device)
     count = torch.empty(I, K, groups.R, dtype=F32, device=trans.device) if return_count else None
     for i0 in range(0, I, TRIM_MAX_IMAGES):
@@ -490,9 +451,36 @@ def trim_loss_tables(cloud, panos, trans, groups, return_count=False, order=None
         nws = lib.pcl_trim_loss_images_workspace_bytes(cloud.n, K, groups.ngroups, len(part))
         ws = _bytes(nws)
         arr = (ctypes.c_void_p * len(part))(*[p.data.data_ptr() for p in part])
-        _lib.check(lib.pcl_trim_loss_images(_ptr(cloud.data), cloud.n, arr, len(part), p0.fmt, p0.H, p0.W, _ptr(trans), K, _ptr(groups.rot),
-                                            groups.R, _ptr(groups.data), groups.ngroups, _ptr(order.data) if order is not None else None, _ptr(table[i0:]),
-                                            _ptr(count[i0:]) if return_count else None, _ptr(ws), nws, _stream()), "pcl_trim_loss_images")
+        _lib.check(lib.pcl_trim_loss_images_sets(_ptr(cloud.data), cloud.n, len(part) if sets else 1, arr, len(part), p0.fmt, p0.H, p0.W, _ptr(trans), K,
+                                                 _ptr(groups.rot), groups.R, _ptr(groups.data), groups.ngroups, _ptr(order.data) if order is not None else None,
+                                                 _ptr(table[i0:]), _ptr(count[i0:]) if return_count else None, _ptr(ws), nws, _stream()),
+                   "pcl_trim_loss_images_sets")
+    return table, count
+
+
+def trim_loss_table(cloud, pano, trans, groups, return_count=False, order=None):
+    """utils.py:484-499 for all pairs: (K, R) float GPU tensor loss_table[i, j] = forward-only sampling loss of (trans[i], rot[j]),
+    rotations of one (pitch, roll) class sharing the projection (csrc/pcl_trim.hip).  order: a TrimOrder of this cloud / grid."""
+    _unweighted(cloud, "trim_loss_table")
+    table, count = _trim_tables(cloud, [pano], trans, groups, return_count, order)
+    return (table[0], count[0]) if return_count else table[0]
+
+
+def trim_loss_tables(cloud, panos, trans, groups, return_count=False, order=None):
+    """trim_loss_table for several query images of one room in ONE launch: (I, K, R) float GPU tensor; image i's table has the
+    bits of trim_loss_table(cloud, panos[i], ...) (same chunks of the cloud).  panos: list of Pano of one size / texel format.
+    A cloud with colour sets (Cloud.with_color_sets, one per image): image i reads set i — its table is trim_loss_table over
+    Cloud(xyz, rgbs[i]), bit for bit."""
+    _unweighted(cloud, "trim_loss_tables")
+    I, p0 = len(panos), panos[0]
+    if any((p.H, p.W, p.fmt) != (p0.H, p0.W, p0.fmt) for p in panos):
+        raise ValueError("all panoramas of a launch must share size and texel format")
+    if cloud.color_sets > 1:
+        if cloud.color_sets != I:
+            raise ValueError("a cloud of %d colour sets for %d images" % (cloud.color_sets, I))
+        if I > TRIM_MAX_IMAGES:
+            raise ValueError("trim_loss_tables: at most %d images per call with colour sets" % TRIM_MAX_IMAGES)
+    table, count = _trim_tables(cloud, panos, trans, groups, return_count, order, sets=cloud.color_sets > 1)
     return (table, count) if return_count else table
 
 
@@ -533,6 +521,100 @@ def select_poses(values, n_keep, trans, rot, largest=False, rot_per_trans=0, ret
 SELECT_MAX_KEEP = 1024      # pcl_select_poses: winners per problem (include/piccolo_hip.h)
 
 
+HIST_MAX_IMAGES = 32       # pcl_hist_trim_scores_images_sets: query images per call
+# bytes of point lists one histogram-trim call may hold
+HIST_BATCH_BYTES = 8e9
+
+
+def _hist_workspace(size_of, count, most, halve, last):
+    """The histogram stage's one allocation ladder: a workspace of size_of(min(count, most)) bytes; while the allocation fails `count` is
+    halved (where the caller can split its work), and the last resort is a workspace of last() bytes — the z-buffer splat's small one.
+    -> (workspace, its bytes, count); workspace None where there is no `last` (the caller has another path)."""
+    while True:
+        nws = size_of(min(count, most))
+        try:
+            return _bytes(nws), nws, count
+        except torch.cuda.OutOfMemoryError:
+            torch.cuda.empty_cache()
+            if halve and count > 1:
+                count = (count + 1) // 2
+                continue
+            nws = last() if last else 0
+            return (_bytes(nws) if last else None), nws, count
+
+
+def hist_workspace_bytes(n, images, cand_per_image, H, W, num_split_h, num_split_w, color_sets=False):
+    """bytes of the histogram stage's workspace for `images` query images of cand_per_image candidates each (0: a shape the stage
+    refuses).  n = the cloud's points: the tile-binned render's workspace (the z-buffer's size where that render does not apply);
+    n = 0: the z-buffer splat's smaller one, which selects that path.  color_sets: a colour set per image."""
+    return _lib.load().pcl_hist_trim_images_sets_workspace_bytes(int(n), images if color_sets else 1, images, int(cand_per_image), int(H), int(W),
+                                                                 num_split_h, num_split_w)
+
+
+def _hist_scores(who, imgs, cloud, trans, rot, num_split_h, num_split_w, splat, batch=None):
+    """The one driver of the histogram stage (pcl_hist_trim_scores_images_sets, pcl_hist_trim_reduce_images): imgs = I images, trans / rot
+    (I, K, 3) -> (scores (I, K), inter, nproj, nimg).  batch (one image): its candidates `batch` at a time over one workspace, then one
+    reduce over all K (the carry-over chain runs through the batches).  Otherwise images in groups, each with its reduce — or, with a
+    colour set per image, all images in one call."""
+    lib = _lib.load()
+    I, K = int(trans.shape[0]), int(trans.shape[1])
+    H, W = int(imgs[0].shape[0]), int(imgs[0].shape[1])
+    sets = cloud.color_sets > 1
+    nblk = (num_split_h - 2) * num_split_w
+    dev = imgs[0].device
+    inter = torch.empty(I * K, nblk, dtype=F32, device=dev)
+    nproj = torch.empty(I * K, nblk, dtype=torch.int32, device=dev)
+    nimg = torch.empty(I, nblk, dtype=torch.int32, device=dev)
+    scores = torch.empty(I, K, dtype=F32, device=dev)
+    t2, r2 = trans.reshape(I * K, 3).contiguous(), rot.reshape(I * K, 3).contiguous()
+    n_ws = 0 if splat else cloud.n               # n = 0: the z-buffer splat path's workspace, which selects it
+
+    def size_of(n, m, cpi):
+        return hist_workspace_bytes(n, m, cpi, H, W, num_split_h, num_split_w, sets)
+
+    def run(i0, m, k0, cpi, ws, nws):            # images [i0, i0 + m), candidates [k0, k0 + cpi) of each (k0 > 0: one image in batches)
+        arr = (ctypes.c_void_p * m)(*[im.data_ptr() for im in imgs[i0:i0 + m]])
+        c0 = i0 * K + k0
+        _lib.check(lib.pcl_hist_trim_scores_images_sets(_ptr(cloud.data), cloud.n, m if sets else 1, arr, m, cpi, H, W, _ptr(t2[c0:]), _ptr(r2[c0:]),
+                                                        num_split_h, num_split_w, _ptr(inter[c0:]), _ptr(nproj[c0:]), _ptr(nimg[i0:]), _ptr(ws), nws,
+                                                        _stream()), "pcl_hist_trim_scores_images_sets")
+
+    def reduce(i0, m):                           # a block with no pixels ends its block row (the reference `break`s there, utils.py:568-571)
+        _lib.check(lib.pcl_hist_trim_reduce_images(_ptr(inter[i0 * K:]), _ptr(nproj[i0 * K:]), _ptr(nimg[i0:]), m, K, num_split_h, num_split_w,
+                                                   _ptr(scores[i0:]), _stream()), "pcl_hist_trim_reduce_images")
+
+    if batch:
+        # one batch for the 64 survivors of the loss trim at 1M points (four batches of 16: 2.0 instead of 1.7 ms; 0.8 instead of
+        # 0.5 ms at 167k points); a batch is kept within ~8 GB (10M points: 16 candidates at a time).
+        batch = max(1, min(batch, K, int(HIST_BATCH_BYTES // max(size_of(n_ws, 1, 1), 1))))
+    unit = size_of(n_ws, I if sets else 1, batch or K)                # one batch / one image / all the images
+    if unit == 0:
+        raise ValueError("%s: need num_split_h >= 3 and blocks of at least one pixel" % who)
+    if batch:
+        ws, nws, batch = _hist_workspace(lambda b: size_of(n_ws, 1, b), batch, K, True, lambda: size_of(0, 1, 1))
+        for k0 in range(0, K, batch):
+            run(0, 1, k0, min(batch, K - k0), ws, nws)
+        reduce(0, 1)
+    elif sets:
+        ws, nws, _ = _hist_workspace(lambda m: size_of(n_ws, m, K), I, I, False, lambda: size_of(0, I, K))
+        run(0, I, 0, K, ws, nws)
+        reduce(0, I)
+    else:
+        group, i0 = max(1, min(HIST_MAX_IMAGES, I, int(HIST_BATCH_BYTES // unit))), 0
+        while i0 < I:
+            # like one image's batches: fewer images at a time, and in the end the per-image path with its own fallbacks
+            ws, nws, group = _hist_workspace(lambda m: size_of(n_ws, m, K), group, I - i0, True, None)
+            m = min(group, I - i0)
+            if ws is None:
+                scores[i0] = hist_trim_scores(imgs[i0], cloud, trans[i0], rot[i0], num_split_h, num_split_w, splat=splat)
+                m = 1
+            else:
+                run(i0, m, 0, K, ws, nws)
+                reduce(i0, m)
+            i0 += m
+    return scores, inter, nproj, nimg
+
+
 def hist_trim_scores(img, cloud, trans, rot, num_split_h, num_split_w, batch=64, return_parts=False, splat=False):
     """Histogram-intersection score of every candidate pose (utils.py:510-588): (K,) GPU tensor, higher is better.
     `cloud` is a packed Cloud.  Candidates are processed `batch` at a time.  Workspace per candidate: the point lists of the
@@ -541,56 +623,11 @@ def hist_trim_scores(img, cloud, trans, rot, num_split_h, num_split_w, batch=64,
     or, where that path does not apply (more than 4096 image tiles, ...) or does not fit, H * W * 8 bytes for the z-buffer of the
     splat path.  If the allocation fails the batch is halved, and the last resort is the splat path's small workspace.
     return_parts: (scores, inter, nproj, nimg).  splat=True: the z-buffer splat path on purpose (its small workspace selects it in
-    pcl_hist_trim_scores; the tests compare the two renderers bit for bit)."""
-    lib = _lib.load()
+    pcl_hist_trim_scores_images_sets; the tests compare the two renderers bit for bit)."""
     _unweighted(cloud, "hist_trim_scores")
-    img = _dev(img)
-    trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-    K, (H, W) = int(trans.shape[0]), (int(img.shape[0]), int(img.shape[1]))
-    if splat:
-        size_of = lambda b: lib.pcl_hist_trim_workspace_bytes(b, H, W, num_split_h, num_split_w)          # noqa: E731
-    else:
-        size_of = lambda b: lib.pcl_hist_trim_workspace_bytes_n(cloud.n, b, H, W, num_split_h, num_split_w)  # noqa: E731
-    nblk = (num_split_h - 2) * num_split_w
-    inter = torch.empty(K, nblk, dtype=F32, device=img.device)
-    nproj = torch.empty(K, nblk, dtype=torch.int32, device=img.device)
-    nimg = torch.empty(nblk, dtype=torch.int32, device=img.device)
-    # one batch for the 64 survivors of the loss trim at 1M points (four batches of 16: 2.0 instead of 1.7 ms; 0.8 instead of
-    # 0.5 ms at 167k points); a batch is kept within ~8 GB (10M points: 16 candidates at a time).
-    # pcl_hist_trim_workspace_bytes_n is the binned path's size where that path will be taken, the splat path's otherwise.
-    per_cand = max(size_of(1), 1)
-    batch = max(1, min(batch, K, int(HIST_BATCH_BYTES // per_cand)))
-    if size_of(batch) == 0:
-        raise ValueError("hist_trim_scores: need num_split_h >= 3 and blocks of at least one pixel")
-    ws = None
-    while ws is None:
-        nws = size_of(batch)
-        try:
-            ws = _bytes(nws)
-        except torch.cuda.OutOfMemoryError:
-            torch.cuda.empty_cache()
-            if batch > 1:
-                batch = (batch + 1) // 2
-                continue
-            nws = lib.pcl_hist_trim_workspace_bytes(1, H, W, num_split_h, num_split_w)      # the z-buffer splat path
-            ws = _bytes(nws)
-    for k0 in range(0, K, batch):
-        k1 = min(k0 + batch, K)
-        _lib.check(lib.pcl_hist_trim_scores(_ptr(cloud.data), cloud.n, _ptr(img), H, W, _ptr(trans[k0:k1]),
-                                            _ptr(rot[k0:k1]), k1 - k0, num_split_h, num_split_w, _ptr(inter[k0:k1]),
-                                            _ptr(nproj[k0:k1]), _ptr(nimg), _ptr(ws), nws, _stream()), "pcl_hist_trim_scores")
-    # a block with no pixels ends its block row (the reference `break`s there, utils.py:568-571)
-    scores = torch.empty(K, dtype=F32, device=img.device)
-    _lib.check(lib.pcl_hist_trim_reduce(_ptr(inter), _ptr(nproj), _ptr(nimg), K, num_split_h, num_split_w, _ptr(scores), _stream()),
-               "pcl_hist_trim_reduce")
-    if return_parts:
-        return scores, inter, nproj, nimg
-    return scores
-
-
-HIST_MAX_IMAGES = 32       # pcl_hist_trim_scores_images: query images per call
-# bytes of point lists one histogram-trim call may hold
-HIST_BATCH_BYTES = 8e9
+    trans, rot = _dev(trans).reshape(1, -1, 3), _dev(rot).reshape(1, -1, 3)
+    scores, inter, nproj, nimg = _hist_scores("hist_trim_scores", [_dev(img)], cloud, trans, rot, num_split_h, num_split_w, splat, batch=max(1, batch))
+    return (scores[0], inter, nproj, nimg[0]) if return_parts else scores[0]
 
 
 def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w, splat=False):
@@ -600,89 +637,15 @@ def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w, s
     point lists within ~8 GB.  A cloud with colour sets (Cloud.with_color_sets, one per image): image i's candidates are rendered
     with set i, all images in one call.  splat=True: the z-buffer splat path on purpose (its small workspace selects it, as
     hist_trim_scores' flag), on either kind of cloud."""
-    if cloud.color_sets > 1:
-        return _hist_trim_scores_sets(imgs, cloud, trans, rot, num_split_h, num_split_w, splat)
-    lib = _lib.load()
     _unweighted(cloud, "hist_trim_scores_images")
     imgs = [_dev(im) for im in imgs]
     trans, rot = _dev(trans), _dev(rot)
-    I, K = int(trans.shape[0]), int(trans.shape[1])
-    H, W = int(imgs[0].shape[0]), int(imgs[0].shape[1])
+    I, (H, W) = int(trans.shape[0]), (int(imgs[0].shape[0]), int(imgs[0].shape[1]))
     if len(imgs) != I or any(tuple(im.shape) != (H, W, 3) or not im.is_contiguous() for im in imgs):
         raise ValueError("hist_trim_scores_images: one contiguous (H, W, 3) image per row of candidates, all of one size")
-    nblk = (num_split_h - 2) * num_split_w
-    dev = imgs[0].device
-    inter = torch.empty(I * K, nblk, dtype=F32, device=dev)
-    nproj = torch.empty(I * K, nblk, dtype=torch.int32, device=dev)
-    nimg = torch.empty(I, nblk, dtype=torch.int32, device=dev)
-    scores = torch.empty(I, K, dtype=F32, device=dev)
-    if splat:                  # n = 0: the z-buffer splat path's workspace (pcl_hist_trim_images_sets_workspace_bytes)
-        size_of = lambda m: lib.pcl_hist_trim_images_sets_workspace_bytes(0, 1, m, K, H, W, num_split_h, num_split_w)   # noqa: E731
-    else:
-        size_of = lambda m: lib.pcl_hist_trim_images_workspace_bytes(cloud.n, m, K, H, W, num_split_h, num_split_w)      # noqa: E731
-    per_image = size_of(1)
-    if per_image == 0:
-        raise ValueError("hist_trim_scores_images: need num_split_h >= 3 and blocks of at least one pixel")
-    group = max(1, min(HIST_MAX_IMAGES, I, int(HIST_BATCH_BYTES // per_image)))
-    t2, r2 = trans.reshape(I * K, 3).contiguous(), rot.reshape(I * K, 3).contiguous()
-    i0 = 0
-    while i0 < I:
-        m = min(group, I - i0)
-        nws = size_of(m)
-        try:
-            ws = _bytes(nws)
-        except torch.cuda.OutOfMemoryError:
-            # like hist_trim_scores: fewer images at a time, and in the end the per-image path with its own fallbacks
-            torch.cuda.empty_cache()
-            if group > 1:
-                group = (group + 1) // 2
-                continue
-            scores[i0] = hist_trim_scores(imgs[i0], cloud, trans[i0], rot[i0], num_split_h, num_split_w, splat=splat)
-            i0 += 1
-            continue
-        arr = (ctypes.c_void_p * m)(*[im.data_ptr() for im in imgs[i0:i0 + m]])
-        _lib.check(lib.pcl_hist_trim_scores_images(_ptr(cloud.data), cloud.n, arr, m, K, H, W, _ptr(t2[i0 * K:]), _ptr(r2[i0 * K:]), num_split_h,
-                                                   num_split_w, _ptr(inter[i0 * K:]), _ptr(nproj[i0 * K:]), _ptr(nimg[i0:]), _ptr(ws), nws, _stream()),
-                   "pcl_hist_trim_scores_images")
-        _lib.check(lib.pcl_hist_trim_reduce_images(_ptr(inter[i0 * K:]), _ptr(nproj[i0 * K:]), _ptr(nimg[i0:]), m, K, num_split_h, num_split_w,
-                                                   _ptr(scores[i0:]), _stream()), "pcl_hist_trim_reduce_images")
-        i0 += m
-    return scores
-
-
-def _hist_trim_scores_sets(imgs, cloud, trans, rot, num_split_h, num_split_w, splat):
-    """hist_trim_scores_images over a cloud of per-image colour sets: one call (pcl_hist_trim_scores_images_sets) for all images."""
-    lib = _lib.load()
-    imgs = [_dev(im) for im in imgs]
-    trans, rot = _dev(trans), _dev(rot)
-    I, K = int(trans.shape[0]), int(trans.shape[1])
-    H, W = int(imgs[0].shape[0]), int(imgs[0].shape[1])
-    if len(imgs) != I or any(tuple(im.shape) != (H, W, 3) or not im.is_contiguous() for im in imgs):
-        raise ValueError("hist_trim_scores_images: one contiguous (H, W, 3) image per row of candidates, all of one size")
-    if cloud.color_sets != I or I > HIST_MAX_IMAGES:
+    if cloud.color_sets > 1 and (cloud.color_sets != I or I > HIST_MAX_IMAGES):
         raise ValueError("a cloud of %d colour sets for %d images (at most %d per call)" % (cloud.color_sets, I, HIST_MAX_IMAGES))
-    nblk = (num_split_h - 2) * num_split_w
-    dev = imgs[0].device
-    inter = torch.empty(I * K, nblk, dtype=F32, device=dev)
-    nproj = torch.empty(I * K, nblk, dtype=torch.int32, device=dev)
-    nimg = torch.empty(I, nblk, dtype=torch.int32, device=dev)
-    scores = torch.empty(I, K, dtype=F32, device=dev)
-    nws = lib.pcl_hist_trim_images_sets_workspace_bytes(0 if splat else cloud.n, I, I, K, H, W, num_split_h, num_split_w)
-    if nws == 0:
-        raise ValueError("hist_trim_scores_images: need num_split_h >= 3 and blocks of at least one pixel")
-    try:
-        ws = _bytes(nws)
-    except torch.cuda.OutOfMemoryError:                 # the z-buffer splat path's small workspace (same scores)
-        torch.cuda.empty_cache()
-        nws = lib.pcl_hist_trim_images_sets_workspace_bytes(0, I, I, K, H, W, num_split_h, num_split_w)
-        ws = _bytes(nws)
-    t2, r2 = trans.reshape(I * K, 3).contiguous(), rot.reshape(I * K, 3).contiguous()
-    arr = (ctypes.c_void_p * I)(*[im.data_ptr() for im in imgs])
-    _lib.check(lib.pcl_hist_trim_scores_images_sets(_ptr(cloud.data), cloud.n, I, arr, I, K, H, W, _ptr(t2), _ptr(r2), num_split_h, num_split_w,
-                                                    _ptr(inter), _ptr(nproj), _ptr(nimg), _ptr(ws), nws, _stream()), "pcl_hist_trim_scores_images_sets")
-    _lib.check(lib.pcl_hist_trim_reduce_images(_ptr(inter), _ptr(nproj), _ptr(nimg), I, K, num_split_h, num_split_w, _ptr(scores), _stream()),
-               "pcl_hist_trim_reduce_images")
-    return scores
+    return _hist_scores("hist_trim_scores_images", imgs, cloud, trans, rot, num_split_h, num_split_w, splat)[0]
 
 
 def depth_mask(cloud, trans, rot, resolution, tau=None, stride=1):

@@ -376,8 +376,8 @@ def make_input_images(imgs, xyz, rgb, num_input, init_dict=None, criterion="hist
             raise ValueError("make_input_images: %d colour sets for %d images" % (len(rgb), I))
         # (groups within the addressing limit, and within the histogram stage's list budget: that stage runs all of a group's images in
         # one call, ops.HIST_BATCH_BYTES)
-        per_image = ops._lib.load().pcl_hist_trim_images_sets_workspace_bytes(int(xyz.shape[0]), 1, 1, int(num_intermediate), int(imgs[0].shape[0]),
-                                                                             int(imgs[0].shape[1]), init_dict["num_split_h"], init_dict["num_split_w"])
+        per_image = ops.hist_workspace_bytes(xyz.shape[0], 1, num_intermediate, imgs[0].shape[0], imgs[0].shape[1], init_dict["num_split_h"],
+                                             init_dict["num_split_w"])
         sizes = color_set_groups(int(xyz.shape[0]), I, int(ops.HIST_BATCH_BYTES // per_image) if per_image else 1)
         if len(sizes) > 1:
             out, i0 = [], 0

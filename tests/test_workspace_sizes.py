@@ -1,6 +1,7 @@
-"""CPU checks of the workspace layouts behind the loss and GD entry points: every size query answers the byte count it has always
-answered (a table of literals, recorded from the library before the layouts were gathered into one carve per family), the plan
-queries likewise, and every run entry point refuses a workspace one byte below its query — before anything touches a device."""
+"""CPU checks of the workspace layouts behind the loss, GD and initialisation-stage entry points: every size query answers the byte
+count it has always answered (a table of literals, recorded from the library before the layouts were gathered into one carve per
+family), the plan queries likewise, and every run entry point refuses a workspace one byte below its query — before anything
+touches a device."""
 import ctypes
 
 import pytest
@@ -107,6 +108,92 @@ PINNED = {
 }
 
 
+# the initialisation stage (histogram trim, loss trim, work list) and the colour / packing workspaces: (points, candidates, H, W); every
+# histogram shape on 4 x 4 blocks.  The last panorama has 65 x 65 = 4225 tiles of 64 px: the tile-binned render is refused and the
+# render area of the n-sized workspace falls back to the z-buffer's size.
+INIT_SHAPES = [(1025, 4, 64, 128), (166_667, 50, 1024, 2048), (1_000_000, 64, 1024, 2048), (166_667, 4, 4160, 4160)]
+INIT_IMAGES = 4                                                            # images (and colour sets) of the several-image queries
+TRIM_SHAPES = [(1025, 4, 2), (166_667, 50, 6), (1_000_000, 64, 6)]        # (points, translations, rotation groups)
+
+
+def _measure_init(lib):
+    out = {}
+    for n, K, h, w in INIT_SHAPES:
+        key = "%dx%d %dx%d" % (n, K, h, w)
+        out["hist " + key] = lib.pcl_hist_trim_workspace_bytes(K, h, w, 4, 4)
+        out["hist_n " + key] = lib.pcl_hist_trim_workspace_bytes_n(n, K, h, w, 4, 4)
+        out["hist_images %d x " % INIT_IMAGES + key] = lib.pcl_hist_trim_images_workspace_bytes(n, INIT_IMAGES, K, h, w, 4, 4)
+        for npts, sets in ((0, 1), (n, 1), (n, INIT_IMAGES)):
+            out["hist_images_sets n %d sets %d: %d x %s" % (npts, sets, INIT_IMAGES, key)] = lib.pcl_hist_trim_images_sets_workspace_bytes(
+                npts, sets, INIT_IMAGES, K, h, w, 4, 4)
+    for n, K, g in TRIM_SHAPES:
+        key = "%dx%dx%d" % (n, K, g)
+        out["trim " + key] = lib.pcl_trim_loss_workspace_bytes(n, K, g)
+        for images in (8, 32):
+            out["trim_images %d x " % images + key] = lib.pcl_trim_loss_images_workspace_bytes(n, K, g, images)
+        out["trim_order " + key] = lib.pcl_trim_order_bytes(n, K, g)
+    # (pcl_trim_order_workspace_bytes, pcl_cloud_order_workspace_bytes and pcl_color_template_workspace_bytes end in rocprim's temporary
+    #  storage, whose size query depends on the device it finds — none without one: not figures a table of literals can hold)
+    out["color_ws"] = lib.pcl_color_workspace_bytes()
+    for c in (8, 256):
+        out["histogram_ws %d^3" % c] = lib.pcl_histogram_workspace_bytes(c, c, c)
+    return out
+
+
+PINNED_INIT = {
+    'hist 1025x4 64x128': 360704,
+    'hist_n 1025x4 64x128': 371200,
+    'hist_images 4 x 1025x4 64x128': 1477888,
+    'hist_images_sets n 0 sets 1: 4 x 1025x4 64x128': 1442816,
+    'hist_images_sets n 1025 sets 1: 4 x 1025x4 64x128': 1477888,
+    'hist_images_sets n 1025 sets 4: 4 x 1025x4 64x128': 1484800,
+    'hist 166667x50 1024x2048': 839716096,
+    'hist_n 166667x50 1024x2048': 842146816,
+    'hist_images 4 x 166667x50 1024x2048': 3367586048,
+    'hist_images_sets n 0 sets 1: 4 x 166667x50 1024x2048': 3358863872,
+    'hist_images_sets n 166667 sets 1: 4 x 166667x50 1024x2048': 3367586048,
+    'hist_images_sets n 166667 sets 4: 4 x 166667x50 1024x2048': 3368586752,
+    'hist 1000000x64 1024x2048': 1074827264,
+    'hist_n 1000000x64 1024x2048': 3206157568,
+    'hist_images 4 x 1000000x64 1024x2048': 12818629888,
+    'hist_images_sets n 0 sets 1: 4 x 1000000x64 1024x2048': 4299309056,
+    'hist_images_sets n 1000000 sets 1: 4 x 1000000x64 1024x2048': 12818629888,
+    'hist_images_sets n 1000000 sets 4: 4 x 1000000x64 1024x2048': 12824630272,
+    'hist 166667x4 4160x4160': 553877760,
+    'hist_n 166667x4 4160x4160': 571516928,
+    'hist_images 4 x 166667x4 4160x4160': 2285067008,
+    'hist_images_sets n 0 sets 1: 4 x 166667x4 4160x4160': 2215511040,
+    'hist_images_sets n 166667 sets 1: 4 x 166667x4 4160x4160': 2285067008,
+    'hist_images_sets n 166667 sets 4: 4 x 166667x4 4160x4160': 2286067712,
+    'trim 1025x4x2': 2560,
+    'trim_images 8 x 1025x4x2': 16896,
+    'trim_images 32 x 1025x4x2': 66048,
+    'trim_order 1025x4x2': 512,
+    'trim 166667x50x6': 633600,
+    'trim_images 8 x 166667x50x6': 4934400,
+    'trim_images 32 x 166667x50x6': 19680000,
+    'trim_order 166667x50x6': 77056,
+    'trim 1000000x64x6': 1597440,
+    'trim_images 8 x 1000000x64x6': 12607488,
+    'trim_images 32 x 1000000x64x6': 50356224,
+    'trim_order 1000000x64x6': 196864,
+    'color_ws': 58624,
+    'histogram_ws 8^3': 2304,
+    'histogram_ws 256^3': 67109120,
+}
+
+
+def test_initialisation_stage_queries_answer_the_pinned_figures(lib):
+    got = _measure_init(lib)
+    assert sorted(got) == sorted(PINNED_INIT)
+    wrong = {k: (v, PINNED_INIT[k]) for k, v in got.items() if v != PINNED_INIT[k]}
+    assert not wrong, wrong
+    assert all(v for v in got.values())
+    n, K, h, w = INIT_SHAPES[-1]                                          # no tile-binned render: the n-sized query adds the masks and codes only
+    key = "%dx%d %dx%d" % (n, K, h, w)
+    assert got["hist_n " + key] - got["hist " + key] == ((h * w + 255) // 256 + (2 * n + 255) // 256) * 256
+
+
 def test_size_and_plan_queries_answer_the_pinned_figures(lib):
     got = _measure(lib)
     assert sorted(got) == sorted(PINNED)
@@ -149,3 +236,21 @@ def test_every_run_refuses_a_workspace_one_byte_below_its_query(lib):
     h, one = _hyper(depth_mask=1), _rooms((166_667,))
     need = lib.pcl_gd_depth_chain_workspace_bytes(one, 1, 1, 6, H, W, ctypes.byref(h))
     assert need > 0 and lib.pcl_gd_run_depth_chain(one, 1, 1, d, fmt, H, W, d, 6, ctypes.byref(h), 3, None, d, need - 1, None, None) == -2
+
+
+def test_initialisation_stage_runs_refuse_a_workspace_one_byte_below_their_query(lib):
+    """The histogram entry refuses below its SMALL (n = 0) query — anything between that and the n-sized one selects the z-buffer splat."""
+    from piccolo_amd import _lib
+    d, fmt = VP(DUMMY), _lib.PANO_U8
+    ptrs = (VP * INIT_IMAGES)(*([DUMMY] * INIT_IMAGES))
+    for n, K, h, w in INIT_SHAPES:
+        for sets in (1, INIT_IMAGES):
+            need = lib.pcl_hist_trim_images_sets_workspace_bytes(0, sets, INIT_IMAGES, K, h, w, 4, 4)
+            assert need > 0 and lib.pcl_hist_trim_scores_images_sets(d, n, sets, ptrs, INIT_IMAGES, K, h, w, d, d, 4, 4, d, d, d, d, need - 1, None) == -2
+    for n, K, g in TRIM_SHAPES:
+        for sets in (1, INIT_IMAGES):
+            need = lib.pcl_trim_loss_images_workspace_bytes(n, K, g, INIT_IMAGES)
+            assert need > 0 and lib.pcl_trim_loss_images_sets(d, n, sets, ptrs, INIT_IMAGES, fmt, H, W, d, K, d, 4 * g, d, g, None, d, None, d, need - 1,
+                                                              None) == -2
+        need = lib.pcl_trim_order_workspace_bytes(n, K, g)
+        assert need > 0 and lib.pcl_trim_order(d, n, fmt, H, W, d, K, d, 4 * g, d, g, d, d, need - 1, None) == -2
