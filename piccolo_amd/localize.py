@@ -4,8 +4,14 @@ the two dataset loops `localize_stanford` / `localize_omniscenes` over the refer
 The reference's own localize.py also runs unchanged on top of piccolo_amd's modules; the loops here
 exist so that `main.py` works without OpenCV / TensorBoard (images through PIL, an optional writer) and shards the query
 images over the ranks of a process group.
+Every dataset loop (Stanford known room, Stanford room search, OmniScenes) is a `_Dataset` — ground_truth / load / report per image,
+localize_group per call — run by ONE driver, `_run_dataset`, under ONE grouping rule, `_groups`: consecutive non-skipped images of this
+rank whose jobs have equal group keys go into one call, up to cfg.images_per_launch (known room) or cfg.room_search_images (room search)
+of them.  A size of 1 is the same path with groups of one.
 """
+import collections
 import csv
+import dataclasses
 import glob
 import os
 import random
@@ -18,8 +24,8 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_rooms, omniloc_batch_rooms_images
-from .utils import make_input, make_input_images, make_pano, out_of_room, resize_image, write_summaries
+from .omniloc import omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_rooms_images
+from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
 
 def preprocess_colors(img, rgb, cfg):
@@ -52,6 +58,36 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
     return results[best][0], results[best][1], results[best][2]
 
 
+def _make_input_args(cfg, init_dict=None):
+    """What make_input / make_input_images take after the cloud, from cfg: (num_input, init_dict, criterion, num_intermediate)."""
+    return (getattr(cfg, "num_input", 6), init_dict if init_dict is not None else get_init_dict(cfg), getattr(cfg, "criterion", "histogram"),
+            getattr(cfg, "num_intermediate", 20))
+
+
+def _images_in_rooms(imgs_init, imgs_main, rooms, cfg, init_dict):
+    """The body of localize_in_rooms (I = 1) and localize_images_in_rooms.  One image issues exactly make_input per room and one
+    omniloc_batch_rooms, by the entry points' own forwarding: shared_rgb turns a one-entry colour list into its tensor; make_input_images
+    returns [make_input(...)] for I == 1, after looking up the same cached grids; omniloc_batch_rooms_images returns
+    omniloc_batch_rooms(imgs[0], ...) on the callers' pose tensors for I == 1 — its depth_tau_groups split is omniloc_batch_rooms' own,
+    and its other fallbacks ask for I > 1."""
+    trs, ros, prepped = [], [], []
+    for xyz, rgb in rooms:
+        pre = [preprocess_colors(im, rgb, cfg) for im in imgs_init]
+        rgbs = [c for _, c in pre]
+        rgb_r = rgb if all(c is rgb for c in rgbs) else rgbs
+        starts = make_input_images([im for im, _ in pre], xyz, rgb_r, *_make_input_args(cfg, init_dict))
+        trs.append([tr for tr, _ in starts])
+        ros.append([ro for _, ro in starts])
+        prepped.append((xyz, rgb_r))
+    res = omniloc_batch_rooms_images(imgs_main, prepped, trs, ros, cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
+    out = []
+    for i in range(len(imgs_init)):
+        losses = torch.stack([res[r][i][2].reshape(()) for r in range(len(rooms))])
+        k = int(torch.argmin(losses))
+        out.append((k, res[k][i][0], res[k][i][1], res[k][i][2], losses))
+    return out
+
+
 def localize_in_rooms(img_init, img_main, rooms, cfg, init_dict):
     """Room search: which of `rooms` (a list of (xyz, rgb) clouds in one frame, e.g. the rooms of one Stanford area) was the panorama
     taken in, and where.  Per room the colour preprocessing (preprocess_colors: with sharpen_color every room gets its own equalised
@@ -61,18 +97,7 @@ def localize_in_rooms(img_init, img_main, rooms, cfg, init_dict):
     (preprocess_colors re-quantises the colour-modulated initialisation image to 8-bit levels and honours match_color, like the OmniScenes
     loop; the known-room Stanford loop keeps color_mod's image as it is.  So a room search restricted to the ground-truth room does not
     reproduce a known-room Stanford run bit for bit: its starting poses may differ.)"""
-    trs, ros, prepped = [], [], []
-    for xyz, rgb in rooms:
-        img_r, rgb_r = preprocess_colors(img_init, rgb, cfg)
-        tr, ro = make_input(img_r, xyz, rgb_r, getattr(cfg, "num_input", 6), init_dict, getattr(cfg, "criterion", "histogram"),
-                            getattr(cfg, "num_intermediate", 20))
-        trs.append(tr)
-        ros.append(ro)
-        prepped.append((xyz, rgb_r))
-    res = omniloc_batch_rooms(img_main, prepped, trs, ros, cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
-    losses = torch.stack([r[2].reshape(()) for r in res])
-    k = int(torch.argmin(losses))
-    return k, res[k][0], res[k][1], res[k][2], losses
+    return _images_in_rooms([img_init], [img_main], rooms, cfg, init_dict)[0]
 
 
 def localize_images_in_rooms(imgs_init, imgs_main, rooms, cfg, init_dict):
@@ -81,26 +106,9 @@ def localize_images_in_rooms(imgs_init, imgs_main, rooms, cfg, init_dict):
     sharpen_color), then ONE refinement of all main images against all rooms (omniloc_batch_rooms_images).
     -> a list whose entry i equals localize_in_rooms(imgs_init[i], imgs_main[i], rooms, cfg, init_dict) bit for bit: (room index, t, R,
     loss, every room's loss)."""
-    I = len(imgs_init)
-    if I == 0 or len(imgs_main) != I:
-        raise ValueError("localize_images_in_rooms: %d initialisation images, %d main images" % (I, len(imgs_main)))
-    trs, ros, prepped = [], [], []
-    for xyz, rgb in rooms:
-        pre = [preprocess_colors(im, rgb, cfg) for im in imgs_init]
-        rgbs = [c for _, c in pre]
-        rgb_r = rgb if all(c is rgb for c in rgbs) else rgbs
-        starts = make_input_images([im for im, _ in pre], xyz, rgb_r, getattr(cfg, "num_input", 6), init_dict,
-                                   getattr(cfg, "criterion", "histogram"), getattr(cfg, "num_intermediate", 20))
-        trs.append([tr for tr, _ in starts])
-        ros.append([ro for _, ro in starts])
-        prepped.append((xyz, rgb_r))
-    res = omniloc_batch_rooms_images(imgs_main, prepped, trs, ros, cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
-    out = []
-    for i in range(I):
-        losses = torch.stack([res[r][i][2].reshape(()) for r in range(len(rooms))])
-        k = int(torch.argmin(losses))
-        out.append((k, res[k][i][0], res[k][i][1], res[k][i][2], losses))
-    return out
+    if len(imgs_init) == 0 or len(imgs_main) != len(imgs_init):
+        raise ValueError("localize_images_in_rooms: %d initialisation images, %d main images" % (len(imgs_init), len(imgs_main)))
+    return _images_in_rooms(imgs_init, imgs_main, rooms, cfg, init_dict)
 
 
 def pose_errors(t, R, gt_trans, gt_rot):
@@ -174,6 +182,36 @@ def _to_img(img8, dev):
     if img8.dtype != np.uint8:                    # the tag below promises levels k/255: only a decoded 8-bit image keeps it
         raise TypeError("_to_img: expected a uint8 image, got %s" % img8.dtype)
     return synth.mark_levels((torch.from_numpy(img8).float() / 255.).to(dev))
+
+
+def _downsample(cfg):
+    """cfg's down-sample factors of the query image: (init_h, init_w, main_h, main_w)."""
+    return tuple(getattr(cfg, k, 1) for k in ("init_downsample_h", "init_downsample_w", "main_downsample_h", "main_downsample_w"))
+
+
+def _query_images(orig, factors, dev):
+    """The decoded uint8 image at the initialisation and at the main resolution (localize.py:168-169, :211-213), on the device."""
+    dh, dw, mh, mw = factors
+    return (_to_img(resize_image(orig, orig.shape[1] // dw, orig.shape[0] // dh), dev),
+            _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev))
+
+
+def _read_cloud(read, path, sample_rate, dev):
+    xyz_np, rgb_np = read(path, sample_rate)
+    return torch.from_numpy(xyz_np).float().to(dev), torch.from_numpy(rgb_np).float().to(dev)
+
+
+def _cloud_cache(read, sample_rate, dev):
+    """path -> (xyz, rgb) on the device through a one-entry cache: consecutive images of one room get the SAME tensors (what their group
+    key compares), and one room's cloud is held at a time."""
+    cache = {}
+
+    def cloud(path):
+        if path not in cache:
+            cache.clear()
+            cache[path] = _read_cloud(read, path, sample_rate, dev)
+        return cache[path]
+    return cloud
 
 
 def _fmt(a):
@@ -270,44 +308,125 @@ def write_results(table, gts, filenames, writer, log_dir, csv_name, header, row_
     return {"accuracy": accuracy, "well_posed": well_posed, "total": total, "failed": failed, "skipped": skipped_list}
 
 
-def _run_dataset(cfg, writer, log_dir, filenames, per_image, csv_name, header, row_prefix, success, row_suffix=None, on_gathered=None):
-    """Shared loop of the two dataset harnesses: shard the query images over the ranks, run `per_image(k)` ->
-    (RESULT_WIDTH row, gt_trans, gt_rot, skipped), gather, and let rank 0 write the reference's CSV and the accuracy under
-    the dataset's own success rule (`success`: stanford_success / omniscenes_success)."""
-    dev = ops.device()
-    gts = {}
+@dataclasses.dataclass(eq=False)
+class _Job:
+    """One loaded query image of a dataset loop: what localize_group and report need of it."""
+    img_init: torch.Tensor             # the image at the initialisation and at the main resolution, on the device
+    img_main: torch.Tensor
+    orig: np.ndarray                   # the uint8 image the result images show
+    xyz: torch.Tensor = None           # known room: its cloud with THIS image's colours (color_mod / preprocess_colors) ...
+    rgb: torch.Tensor = None
+    show_rgb: torch.Tensor = None      # ... and the colours its result image is rendered with
+    area: int = None                   # room search: the area and its [(room name, xyz, rgb)]
+    rooms: list = None
+    on_start: object = None            # on_start(input_trans, input_rot), called once the starting poses exist (save_starting_point)
 
-    def body(k):
-        row, gt_t, gt_r, skipped = per_image(k)
-        gts[k] = (gt_t, gt_r, skipped)
-        return row
+    @property
+    def group_key(self):
+        """Jobs go into one call only if these are equal: the cloud's POINTS (known room: the xyz tensor itself; room search: the area)
+        and the two image sizes."""
+        return (id(self.xyz) if self.rooms is None else self.area, self.img_init.shape, self.img_main.shape)
 
-    per_launch = int(getattr(cfg, "images_per_launch", 1))
-    if per_launch > 1:
-        rank, world = pdist.world()
-        mine = pdist.shard(len(filenames), rank, world)
-        rows = torch.full((len(mine), pdist.RESULT_WIDTH), float("nan"), dtype=torch.float32)
-        batcher = _Batcher(cfg, per_launch)
-        for j, k in enumerate(mine):
-            def store(row, j=j):
-                rows[j] = row
-            _, gt_t, gt_r, skipped = per_image(k, batcher=batcher, done=store)
-            gts[k] = (gt_t, gt_r, skipped)
-        batcher.flush()
-        table = pdist.gather_rows(rows.to(dev), len(filenames), rank, world)
-    else:
-        table = pdist.localize_sharded(len(filenames), body, dev)
+
+# A dataset loop in plain steps.  ground_truth(k) -> (gt_trans, gt_rot, skipped): host work plus the cloud the skip rule needs (rank 0
+# calls it for the other ranks' images too).  load(k) -> the image's job (anything with a group_key).  localize_group(jobs) -> one
+# (t, R, loss, ...) per job, from ONE call.  report(k, job, result, row): the prints and the result image of a localised image.
+_Dataset = collections.namedtuple("_Dataset", "ground_truth load localize_group report")
+
+
+def _groups(indices, skipped, key, size):
+    """THE grouping rule of the dataset loops, pure host code: walk `indices` in order; a skipped index neither joins nor ends a group;
+    any other index joins the open group if its key equals the group's, else the open group ends and the index opens the next; a group
+    of `size` ends at once.  Yields each group (a list of indices) when it ends — a full one before the next index is looked at — and
+    calls skipped(k), then key(k), once per index."""
+    group, group_key = [], None
+    for k in indices:
+        if skipped(k):
+            continue
+        k_key = key(k)
+        if group and k_key != group_key:
+            yield group
+            group = []
+        group, group_key = group + [k], k_key
+        if len(group) >= size:
+            yield group
+            group = []
+    if group:
+        yield group
+
+
+def _result_row(t, R, loss, gt_trans, gt_rot, seconds):
+    t_err, r_err = pose_errors(t, R, gt_trans, gt_rot)
+    return torch.cat([t.reshape(3), R.reshape(9), loss.reshape(1), torch.tensor([t_err, r_err, seconds], dtype=torch.float32)])
+
+
+def _run_dataset(writer, log_dir, filenames, dataset, group_size, csv_name, header, row_prefix, success, row_suffix=None, on_gathered=None):
+    """The one loop of the dataset harnesses: this rank's images (pdist.shard) in groups (_groups; every image is loaded once), one
+    clock around a group's localize_group with the wall time shared equally (localize.py:208,222-223 per image), then a RESULT_WIDTH
+    row and a report per image; a skipped image keeps its NaN row.  The rows are gathered, and rank 0 writes the reference's CSV and the
+    accuracy under the dataset's own success rule (`success`: stanford_success / omniscenes_success)."""
+    rank, world = pdist.world()
+    mine = pdist.shard(len(filenames), rank, world)
+    rows = torch.full((len(mine), pdist.RESULT_WIDTH), float("nan"), dtype=torch.float32)
+    cuda = torch.cuda.is_available()                # (the loop itself is host code: the CPU tests drive it with a canned dataset)
+    gts, jobs = {}, {}
+
+    def ground_truth(k):
+        if k not in gts:
+            gts[k] = dataset.ground_truth(k)
+        return gts[k]
+
+    def skipped(k):
+        skip = ground_truth(k)[2]
+        if skip:
+            print("corrupted file : {}, gt_trans is out of the room\n".format(filenames[k]))
+        return skip
+
+    def key(k):
+        jobs[k] = dataset.load(k)
+        return jobs[k].group_key
+
+    for group in _groups(mine, skipped, key, group_size):
+        batch = [jobs.pop(k) for k in group]
+        if cuda:
+            torch.cuda.synchronize()
+        t0 = time.time()
+        results = dataset.localize_group(batch)
+        share = (time.time() - t0) / len(group)     # the group's wall time, shared equally
+        for k, job, result in zip(group, batch, results):
+            row = rows[(k - rank) // world] = _result_row(*result[:3], *ground_truth(k)[:2], share)
+            dataset.report(k, job, result, row)
+    table = pdist.gather_rows(rows.to(ops.device()) if cuda else rows, len(filenames), rank, world)
     if on_gathered is not None:                     # (every rank, after the rows: a collective of the caller's own, e.g. room search's)
         on_gathered()
-    rank, world = pdist.world()
     if world > 1 and rank == 0:                     # ground truths of the other ranks' images, for the CSV
         for k in range(len(filenames)):
-            if k not in gts:
-                gts[k] = per_image(k, gt_only=True)
+            ground_truth(k)
     LAST_RUN.clear()
     if rank == 0:
         LAST_RUN.update(write_results(table.cpu().numpy(), gts, filenames, writer, log_dir, csv_name, header, row_prefix, success, row_suffix))
     return table
+
+
+def _localize_known_room(cfg, jobs):
+    """localize_group of the known-room loops (localize.py:199-233): images that share the cloud's POINTS and the image sizes are
+    initialised in one set of launches (make_input_images) and refined in one launch chain (omniloc_batch_images) — at the shipped 6
+    candidates per image a launch is latency-bound, eight images cost little more than one.  Images whose cloud colours were changed per
+    image (sharpen_color: color_mod gives every image its own equalised colours, localize.py:173-179) share the launches too: the
+    group's cloud then holds one colour set per image, and every image's results are those of its own one-image calls, bit for bit.  When
+    every job shares one rgb tensor it is passed as that tensor (the shared-colour path).  Grouping by colour sets was measured to beat
+    one image at a time at the shipped and at the cfg-2 shape (tools/color_sets_bench.py).  One job: make_input_images is
+    make_input, and the refinement is refine_image."""
+    xyz = jobs[0].xyz
+    rgb = jobs[0].rgb if all(j.rgb is jobs[0].rgb for j in jobs) else [j.rgb for j in jobs]
+    starts = make_input_images([j.img_init for j in jobs], xyz, rgb, *_make_input_args(cfg))
+    for j, (tr, ro) in zip(jobs, starts):
+        if j.on_start is not None:
+            j.on_start(tr, ro)
+    if len(jobs) == 1:
+        return [refine_image(jobs[0].img_main, xyz, rgb, *starts[0], cfg)]
+    return omniloc_batch_images([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg,
+                                batch_mode=bool(getattr(cfg, "parallel", False)))
 
 
 def _seed_all():
@@ -318,78 +437,31 @@ def _seed_all():
     random.seed(2)
 
 
-def _nan_row():
-    return torch.full((pdist.RESULT_WIDTH,), float("nan"))
+def _f32(gt_trans, gt_rot):
+    return gt_trans.astype(np.float32), gt_rot.astype(np.float32)
 
 
-def _refine_and_score(img_init, img_main, xyz, rgb, cfg, gt_trans, gt_rot, summaries, batcher=None, finish=None, on_start=None):
-    """localize.py:199-247: make_input on the initialisation image, refinement on the main image, errors.  With a
-    `batcher` BOTH stages are deferred: images of one cloud are initialised together (make_input_images) and refined together
-    (omniloc_batch_images); `finish(t, R, row)` is called then."""
-    if batcher is not None:
-        batcher.submit(dict(img_init=img_init, img=img_main, xyz=xyz, rgb=rgb, gt=(gt_trans, gt_rot), finish=finish, on_start=on_start))
-        return None
-    init_dict = get_init_dict(cfg)
-    torch.cuda.synchronize()
-    t0 = time.time()
-    input_trans, input_rot = make_input(img_init, xyz, rgb, getattr(cfg, "num_input", 6), init_dict,
-                                        getattr(cfg, "criterion", "histogram"), getattr(cfg, "num_intermediate", 20))
-    if on_start is not None:
-        on_start(input_trans, input_rot)
-    t, R, loss = refine_image(img_main, xyz, rgb, input_trans, input_rot, cfg, summaries)
-    dt = time.time() - t0
-    return (t, R) + (_result_row(t, R, loss, gt_trans, gt_rot, dt),)
+STANFORD_HEADER = ["area_num", "pano_name", "gt_trans", "gt_rot", "skipped?", "OmniLoc_trans", "OmniLoc_rot", "t_error (m)", "r_error (degrees)",
+                   "time (s)"]
+OMNISCENES_HEADER = STANFORD_HEADER[1:]             # (the same columns without the area)
 
 
-def _result_row(t, R, loss, gt_trans, gt_rot, seconds):
-    t_err, r_err = pose_errors(t, R, gt_trans, gt_rot)
-    return torch.cat([t.reshape(3), R.reshape(9), loss.reshape(1), torch.tensor([t_err, r_err, seconds], dtype=torch.float32)])
+def _stanford_parts(filename):
+    """.../area_<area>/camera_<id>_<room type>_<room number>_... -> (area, image name, "<room type>_<room number>")"""
+    img_name = filename.split("/")[-1]
+    return int(filename.split("/")[-2].split("_")[-1]), img_name, "{}_{}".format(img_name.split("_")[2], img_name.split("_")[3])
 
 
-class _Batcher:
-    """cfg.images_per_launch > 1: query images that share the cloud's POINTS (the xyz tensor) and the image size are initialised in
-    one set of launches (make_input_images) and refined in one launch chain (omniloc_batch_images) — at the shipped 6 candidates per
-    image a launch is latency-bound, eight images cost little more than one.  Images whose cloud colours were changed per image
-    (sharpen_color: color_mod gives every image its own equalised colours, localize.py:173-179) share the launches too: the group's
-    cloud then holds one colour set per image, and every image's results are those of its own one-image calls, bit for bit.  When
-    every job shares one rgb tensor it is passed as that tensor (the shared-colour path as before).  Grouping by colour sets was
-    measured to beat one image at a time at the shipped and at the cfg-2 shape (tools/color_sets_bench.py)."""
+def _stanford_row_prefix(filename):
+    return list(_stanford_parts(filename)[:2])
 
-    def __init__(self, cfg, size):
-        self.cfg, self.size, self.jobs = cfg, size, []
 
-    def submit(self, job):
-        j0 = self.jobs[0] if self.jobs else None
-        if j0 is not None and not (job["xyz"] is j0["xyz"] and job["img"].shape == j0["img"].shape and job["img_init"].shape == j0["img_init"].shape):
-            self.flush()
-        self.jobs.append(job)
-        if len(self.jobs) >= self.size:
-            self.flush()
-
-    def flush(self):
-        jobs, self.jobs = self.jobs, []
-        if not jobs:
-            return
-        cfg = self.cfg
-        # one tensor when the group shares its colours, else one colour set per image
-        rgb = jobs[0]["rgb"] if all(j["rgb"] is jobs[0]["rgb"] for j in jobs) else [j["rgb"] for j in jobs]
-        torch.cuda.synchronize()
-        t0 = time.time()
-        starts = make_input_images([j["img_init"] for j in jobs], jobs[0]["xyz"], rgb, getattr(cfg, "num_input", 6), get_init_dict(cfg),
-                                   getattr(cfg, "criterion", "histogram"), getattr(cfg, "num_intermediate", 20))
-        for j, (tr, ro) in zip(jobs, starts):
-            j["trans"], j["rot"] = tr, ro
-            if j["on_start"] is not None:
-                j["on_start"](tr, ro)
-        if len(jobs) == 1:
-            j = jobs[0]
-            results = [refine_image(j["img"], j["xyz"], j["rgb"], j["trans"], j["rot"], cfg)]
-        else:
-            results = omniloc_batch_images([j["img"] for j in jobs], jobs[0]["xyz"], rgb, [j["trans"] for j in jobs],
-                                           [j["rot"] for j in jobs], cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
-        share = (time.time() - t0) / len(jobs)               # the group's wall time, shared equally (localize.py:208,222-223 per image)
-        for j, (t, R, loss) in zip(jobs, results):
-            j["finish"](t, R, _result_row(t, R, loss, j["gt"][0], j["gt"][1], share))
+def _stanford_report(filename, log_dir, job, xyz, rgb, result, row, found=""):
+    area, img_name, _ = _stanford_parts(filename)
+    print("\n{}\n{}translation error : {}\nrotation error : {}\n".format(img_name, found, float(row[13]), float(row[14])))
+    if log_dir is not None:
+        _save_result_image(os.path.join(log_dir, "results", "area_{}".format(area), img_name), job.orig, xyz, rgb, result[0], result[1],
+                           (job.img_main.shape[0] // 2, job.img_main.shape[1] // 2))
 
 
 def stanford_area_rooms(root, area, room_search=True):
@@ -405,6 +477,7 @@ def stanford_area_rooms(root, area, room_search=True):
 def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford"):
     """Stanford2D-3D-S loop (localize.py:76-297) over `root`/pano/area_*/ *.png, pcd_not_aligned/area_*/<room>.txt and
     pose/area_*/ *.json; writes `stanford_results.csv` with the reference's columns and result images under results/.
+    cfg.images_per_launch is the group size of _run_dataset (_localize_known_room).
     cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms)."""
     _require_gravity_aligned(cfg)
     room_search = getattr(cfg, "room_search", None)
@@ -426,181 +499,91 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     room_name = getattr(cfg, "room_name", None)
     if room_name is not None:
         filenames = [f for f in filenames if room_name in f]
-    sample_rate = getattr(cfg, "sample_rate", 1)
-    quant = getattr(cfg, "out_of_room_quantile", 0.05)
-    dh, dw = getattr(cfg, "init_downsample_h", 1), getattr(cfg, "init_downsample_w", 1)
-    mh, mw = getattr(cfg, "main_downsample_h", 1), getattr(cfg, "main_downsample_w", 1)
-    cache = {}
-    summaries = {}
     if room_search:
         return _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
+    quant = getattr(cfg, "out_of_room_quantile", 0.05)
+    read_cloud = _cloud_cache(data_utils.read_stanford, getattr(cfg, "sample_rate", 1), dev)
 
-    def per_image(k, gt_only=False, batcher=None, done=None):
-        filename = filenames[k]
-        area = int(filename.split("/")[-2].split("_")[-1])
-        img_name = filename.split("/")[-1]
-        room_type, room_no = img_name.split("_")[2], img_name.split("_")[3]
-        gt_trans, gt_rot = data_utils.obtain_gt_stanford(area, img_name, root=os.path.join(root, "pose"))
-        gt_trans, gt_rot = gt_trans.astype(np.float32), gt_rot.astype(np.float32)
-        pcd_name = os.path.join(root, "pcd_not_aligned/area_{}/{}_{}.txt".format(area, room_type, room_no))
-        if cache.get("name") != pcd_name:
-            xyz_np, rgb_np = data_utils.read_stanford(pcd_name, sample_rate)
-            cache.update(name=pcd_name, xyz=torch.from_numpy(xyz_np).float().to(dev), rgb=torch.from_numpy(rgb_np).float().to(dev))
-        xyz, rgb = cache["xyz"], cache["rgb"]
-        skipped = bool(out_of_room(xyz, torch.from_numpy(gt_trans), quant)) and not getattr(cfg, "eval_full", False)
-        if gt_only:
-            return gt_trans, gt_rot, skipped
-        if skipped:
-            print("corrupted file : {}, gt_trans is out of the room\n".format(filename))
-            return _nan_row(), gt_trans, gt_rot, True
-        orig = read_image(filename)
-        img = _to_img(resize_image(orig, orig.shape[1] // dw, orig.shape[0] // dh), dev)
+    def cloud(k):
+        area, _, room = _stanford_parts(filenames[k])
+        return read_cloud(os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, room)))
+
+    def ground_truth(k):
+        area, img_name, _ = _stanford_parts(filenames[k])
+        gt_trans, gt_rot = _f32(*data_utils.obtain_gt_stanford(area, img_name, root=os.path.join(root, "pose")))
+        skipped = bool(out_of_room(cloud(k)[0], torch.from_numpy(gt_trans), quant)) and not getattr(cfg, "eval_full", False)
+        return gt_trans, gt_rot, skipped
+
+    def load(k):
+        xyz, rgb = cloud(k)
+        orig = read_image(filenames[k])
+        img, img_main = _query_images(orig, _downsample(cfg), dev)
         rgb_k = rgb
         if getattr(cfg, "sharpen_color", False):        # localize.py:175-179: only the INITIALISATION image is equalised
             img, rgb_k = color_mod(img, rgb, int(getattr(cfg, "num_bins", 256)))
-        img_main = _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev)      # localize.py:211-213
-        def report(t, R, row):
-            print("\n{}\ntranslation error : {}\nrotation error : {}\n".format(img_name, float(row[13]), float(row[14])))
-            if log_dir is not None:
-                _save_result_image(os.path.join(log_dir, "results", "area_{}".format(area), img_name), orig, xyz, rgb, t, R,
-                                   (img_main.shape[0] // 2, img_main.shape[1] // 2))
-            if done is not None:
-                done(row)
+        return _Job(img, img_main, orig, xyz, rgb_k, show_rgb=rgb)
 
-        if batcher is not None:
-            _refine_and_score(img, img_main, xyz, rgb_k, cfg, gt_trans, gt_rot, summaries, batcher=batcher, finish=report)
-            return None, gt_trans, gt_rot, False
-        t, R, row = _refine_and_score(img, img_main, xyz, rgb_k, cfg, gt_trans, gt_rot, summaries)
-        report(t, R, row)
-        return row, gt_trans, gt_rot, False
+    def report(k, job, result, row):
+        _stanford_report(filenames[k], log_dir, job, job.xyz, job.show_rgb, result, row)
 
-    return _run_dataset(cfg, writer, log_dir, filenames, per_image, "stanford_results.csv",
-                        ["area_num", "pano_name", "gt_trans", "gt_rot", "skipped?", "OmniLoc_trans", "OmniLoc_rot", "t_error (m)",
-                         "r_error (degrees)", "time (s)"],
-                        lambda f: [int(f.split("/")[-2].split("_")[-1]), f.split("/")[-1]], stanford_success)
-
-
-STANFORD_HEADER = ["area_num", "pano_name", "gt_trans", "gt_rot", "skipped?", "OmniLoc_trans", "OmniLoc_rot", "t_error (m)", "r_error (degrees)",
-                   "time (s)"]
+    return _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
+                        int(getattr(cfg, "images_per_launch", 1)), "stanford_results.csv", STANFORD_HEADER, _stanford_row_prefix, stanford_success)
 
 
 def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search):
     """localize_stanford with cfg.room_search: every image is localised among the rooms of its area (stanford_area_rooms) by
     localize_in_rooms instead of in the room its file name names.  The skip rule stays on the ground-truth room's cloud (the same images
     are evaluated as in a known-room run); the CSV gets a last column found_room, LAST_RUN a room_accuracy, and the result image is
-    rendered from the found room's cloud.  Each area's clouds are read once.  cfg.room_search_images = N > 1: up to N consecutive
-    non-skipped images of this rank that share area and image sizes are localised by ONE localize_images_in_rooms call (the same results,
-    bit for bit); a group ends at an area change and at the end, and its wall time is shared equally over its images, as _Batcher does.
+    rendered from the found room's cloud.  Each area's clouds are read once.  cfg.room_search_images = N is the group size of
+    _run_dataset: up to N consecutive non-skipped images of this rank that share area and image sizes are localised by ONE
+    localize_images_in_rooms call (the same results, bit for bit); a group of one goes through localize_in_rooms.
     With several ranks every rank localises its share of the
     images and the found rooms are gathered with the result rows (as room indices into the area's sorted listing), so that rank 0 writes
     found_room and room_accuracy for every image."""
     dev = ops.device()
     sample_rate = getattr(cfg, "sample_rate", 1)
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
-    dh, dw = getattr(cfg, "init_downsample_h", 1), getattr(cfg, "init_downsample_w", 1)
-    mh, mw = getattr(cfg, "main_downsample_h", 1), getattr(cfg, "main_downsample_w", 1)
     init_dict = get_init_dict(cfg)
     areas, found, found_idx = {}, {}, {}
-    group_size = max(1, int(getattr(cfg, "room_search_images", 1)))
-    ready = {}                                         # room_search_images: image index -> (room, t, R, loss, seconds, images) of its group
-    gts = {}                                           # image index -> (gt_trans, gt_rot, skipped): a group's look-ahead asks before per_image does
 
-    def area_of(k):
-        return int(filenames[k].split("/")[-2].split("_")[-1])
-
-    def gt_room_of(k):
-        img_name = filenames[k].split("/")[-1]
-        return "{}_{}".format(img_name.split("_")[2], img_name.split("_")[3])
+    def read_cloud(area, room):
+        return _read_cloud(data_utils.read_stanford, os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, room)), sample_rate, dev)
 
     def area_rooms(area):
         if area not in areas:
-            rooms = []
-            for name in stanford_area_rooms(root, area, room_search):
-                xyz_np, rgb_np = data_utils.read_stanford(os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, name)), sample_rate)
-                rooms.append((name, torch.from_numpy(xyz_np).float().to(dev), torch.from_numpy(rgb_np).float().to(dev)))
+            rooms = [(name,) + read_cloud(area, name) for name in stanford_area_rooms(root, area, room_search)]
             areas.clear()                              # (one area's clouds at a time: the images are sorted by area)
             areas[area] = rooms
         return areas[area]
 
     def ground_truth(k):
-        if k not in gts:
-            gts[k] = read_ground_truth(k)
-        return gts[k]
-
-    def read_ground_truth(k):
-        filename = filenames[k]
-        area = int(filename.split("/")[-2].split("_")[-1])
-        img_name = filename.split("/")[-1]
-        gt_room = "{}_{}".format(img_name.split("_")[2], img_name.split("_")[3])
-        gt_trans, gt_rot = data_utils.obtain_gt_stanford(area, img_name, root=os.path.join(root, "pose"))
-        gt_trans, gt_rot = gt_trans.astype(np.float32), gt_rot.astype(np.float32)
-        rooms = area_rooms(area)
-        gt_cloud = next((xyz for name, xyz, _ in rooms if name == gt_room), None)
+        area, img_name, gt_room = _stanford_parts(filenames[k])
+        gt_trans, gt_rot = _f32(*data_utils.obtain_gt_stanford(area, img_name, root=os.path.join(root, "pose")))
+        gt_cloud = next((xyz for name, xyz, _ in area_rooms(area) if name == gt_room), None)
         if gt_cloud is None:                           # (a list that leaves the ground-truth room out: its cloud still decides the skip)
-            xyz_np, _ = data_utils.read_stanford(os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, gt_room)), sample_rate)
-            gt_cloud = torch.from_numpy(xyz_np).float().to(dev)
+            gt_cloud = read_cloud(area, gt_room)[0]
         skipped = bool(out_of_room(gt_cloud, torch.from_numpy(gt_trans), quant)) and not getattr(cfg, "eval_full", False)
         return gt_trans, gt_rot, skipped
 
-    def load_images(k):
-        orig = read_image(filenames[k])
-        img = _to_img(resize_image(orig, orig.shape[1] // dw, orig.shape[0] // dh), dev)
-        img_main = _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev)
-        return orig, img, img_main
-
-    def localize_group(k):
-        # image k and the next non-skipped images of this rank in its area with its image sizes, up to group_size, in one call
-        rank, world = pdist.world()
-        rooms = area_rooms(area_of(k))
-        group, images = [k], [load_images(k)]
-        for k2 in range(k + world, len(filenames), world):
-            if len(group) >= group_size or area_of(k2) != area_of(k):
-                break
-            if ground_truth(k2)[2]:
-                continue
-            nxt = load_images(k2)
-            if nxt[1].shape != images[0][1].shape or nxt[2].shape != images[0][2].shape:
-                break
-            group.append(k2)
-            images.append(nxt)
-        torch.cuda.synchronize()
-        t0 = time.time()
-        results = localize_images_in_rooms([im[1] for im in images], [im[2] for im in images], [(xyz, rgb) for _, xyz, rgb in rooms], cfg, init_dict)
-        share = (time.time() - t0) / len(group)        # the group's wall time, shared equally
-        for kk, im, (r, t, R, loss, _) in zip(group, images, results):
-            ready[kk] = (r, t, R, loss, share, im)
-
-    def per_image(k, gt_only=False):
-        filename = filenames[k]
-        area = area_of(k)
-        img_name = filename.split("/")[-1]
-        gt_trans, gt_rot, skipped = ground_truth(k)
-        rooms = area_rooms(area)
-        if gt_only:
-            return gt_trans, gt_rot, skipped
-        if skipped:
-            print("corrupted file : {}, gt_trans is out of the room\n".format(filename))
-            return _nan_row(), gt_trans, gt_rot, True
-        if not rooms:
+    def load(k):
+        area = _stanford_parts(filenames[k])[0]
+        if not area_rooms(area):
             raise FileNotFoundError("room_search: no room clouds under pcd_not_aligned/area_{}".format(area))
-        if group_size > 1:
-            if k not in ready:
-                localize_group(k)
-            r, t, R, loss, seconds, (orig, img, img_main) = ready.pop(k)
-            row = _result_row(t, R, loss, gt_trans, gt_rot, seconds)
+        orig = read_image(filenames[k])
+        return _Job(*_query_images(orig, _downsample(cfg), dev), orig, area=area, rooms=area_rooms(area))
+
+    def localize_group(jobs):
+        rooms = [(xyz, rgb) for _, xyz, rgb in jobs[0].rooms]
+        if len(jobs) == 1:
+            res = [localize_in_rooms(jobs[0].img_init, jobs[0].img_main, rooms, cfg, init_dict)]
         else:
-            orig, img, img_main = load_images(k)
-            torch.cuda.synchronize()
-            t0 = time.time()
-            r, t, R, loss, _ = localize_in_rooms(img, img_main, [(xyz, rgb) for _, xyz, rgb in rooms], cfg, init_dict)
-            row = _result_row(t, R, loss, gt_trans, gt_rot, time.time() - t0)
-        name, xyz, rgb = rooms[r]
-        found_idx[k] = r
-        print("\n{}\nfound room : {}\ntranslation error : {}\nrotation error : {}\n".format(img_name, name, float(row[13]), float(row[14])))
-        if log_dir is not None:
-            _save_result_image(os.path.join(log_dir, "results", "area_{}".format(area), img_name), orig, xyz, rgb, t, R,
-                               (img_main.shape[0] // 2, img_main.shape[1] // 2))
-        return row, gt_trans, gt_rot, False
+            res = localize_images_in_rooms([j.img_init for j in jobs], [j.img_main for j in jobs], rooms, cfg, init_dict)
+        return [(t, R, loss, r) for r, t, R, loss, _ in res]
+
+    def report(k, job, result, row):
+        name, xyz, rgb = job.rooms[result[3]]
+        found_idx[k] = result[3]
+        _stanford_report(filenames[k], log_dir, job, xyz, rgb, result, row, "found room : {}\n".format(name))
 
     def gather_found():
         # this rank's found-room indices (NaN: skipped, or another rank's image) through the same all_gather as the result rows
@@ -615,14 +598,14 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
         listings = {}
         for k, v in enumerate(every):
             if not np.isnan(v):
-                area = area_of(k)
+                area, _, gt_room = _stanford_parts(filenames[k])
                 if area not in listings:
                     listings[area] = stanford_area_rooms(root, area, room_search)
-                found[k] = (listings[area][int(v)], gt_room_of(k))
+                found[k] = (listings[area][int(v)], gt_room)
 
-    table = _run_dataset(cfg, writer, log_dir, filenames, per_image, "stanford_results.csv", STANFORD_HEADER + ["found_room"],
-                         lambda f: [int(f.split("/")[-2].split("_")[-1]), f.split("/")[-1]], stanford_success,
-                         row_suffix=lambda k: [found[k][0] if k in found else ""], on_gathered=gather_found)
+    table = _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, localize_group, report),
+                         int(getattr(cfg, "room_search_images", 1)), "stanford_results.csv", STANFORD_HEADER + ["found_room"], _stanford_row_prefix,
+                         stanford_success, row_suffix=lambda k: [found[k][0] if k in found else ""], on_gathered=gather_found)
     if LAST_RUN:
         hits = [name == gt for name, gt in found.values()]
         LAST_RUN["room_accuracy"] = sum(hits) / len(hits) if hits else 0.0
@@ -634,7 +617,8 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
 def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscenes"):
     """OmniScenes loop (localize.py:300-530) over `root`/<split>_pano/<video>/<frame>, pcd/<room>.txt and <split>_pose;
     writes `omniscenes_results.csv`.  Includes the synthetic illumination changes (synth_const / synth_gamma / synth_wb)
-    and the colour preprocessing of the whole image (match_color / sharpen_color)."""
+    and the colour preprocessing of the whole image (match_color / sharpen_color).  cfg.images_per_launch is the group size of
+    _run_dataset (_localize_known_room)."""
     _require_gravity_aligned(cfg)
     _seed_all()
     dev = ops.device()
@@ -647,32 +631,27 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
         filenames = [f for f in filenames if any(rm in f for rm in room_name)]
     if scene is not None:
         filenames = [f for f in filenames if "scene_{}".format(scene) in f]
-    sample_rate = getattr(cfg, "sample_rate", 1)
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
-    dh = max(getattr(cfg, "init_downsample_h", 1) // 2, 1)         # "match resolution with stanford" (localize.py:349-350)
-    dw = max(getattr(cfg, "init_downsample_w", 1) // 2, 1)
-    mh, mw = getattr(cfg, "main_downsample_h", 1), getattr(cfg, "main_downsample_w", 1)
-    cache = {}
-    summaries = {}
+    dh, dw, mh, mw = _downsample(cfg)
+    factors = (max(dh // 2, 1), max(dw // 2, 1), mh, mw)           # "match resolution with stanford" (localize.py:349-350)
+    read_cloud = _cloud_cache(data_utils.read_omniscenes, getattr(cfg, "sample_rate", 1), dev)
 
-    def per_image(k, gt_only=False, batcher=None, done=None):
-        filename = filenames[k]
-        video = filename.split("/")[-2]
-        room_type, room_no = video.split("_")[1], video.split("_")[2]
-        gt_trans, gt_rot = data_utils.obtain_gt_omniscenes(filename)
-        gt_trans, gt_rot = gt_trans.astype(np.float32), gt_rot.astype(np.float32)
-        pcd_name = os.path.join(root, "pcd/{}_{}.txt".format(room_type, room_no))
-        if cache.get("name") != pcd_name:
-            xyz_np, rgb_np = data_utils.read_omniscenes(pcd_name, sample_rate)
-            cache.update(name=pcd_name, xyz=torch.from_numpy(xyz_np).float().to(dev), rgb=torch.from_numpy(rgb_np).float().to(dev))
-        xyz, rgb = cache["xyz"], cache["rgb"]
-        skipped = bool(out_of_room(xyz, torch.from_numpy(gt_trans), quant))
-        if gt_only:
-            return gt_trans, gt_rot, skipped
-        if skipped:
-            print("corrupted file : {}, gt_trans is out of the room\n".format(filename))
-            return _nan_row(), gt_trans, gt_rot, True
-        orig = resize_image(read_image(filename), 2048, 1024)       # localize.py:372
+    def names(k):
+        video, frame = filenames[k].split("/")[-2:]
+        return video, frame, os.path.splitext(frame)[0]
+
+    def cloud(k):
+        video = names(k)[0]
+        return read_cloud(os.path.join(root, "pcd/{}_{}.txt".format(video.split("_")[1], video.split("_")[2])))
+
+    def ground_truth(k):
+        gt_trans, gt_rot = _f32(*data_utils.obtain_gt_omniscenes(filenames[k]))
+        return gt_trans, gt_rot, bool(out_of_room(cloud(k)[0], torch.from_numpy(gt_trans), quant))
+
+    def load(k):
+        xyz, rgb = cloud(k)
+        video, _, stem = names(k)
+        orig = resize_image(read_image(filenames[k]), 2048, 1024)   # localize.py:372
         if getattr(cfg, "synth_const", None) is not None:           # synthetic illumination changes, localize.py:375-385
             orig = orig // cfg.synth_const
         if getattr(cfg, "synth_gamma", None) is not None:
@@ -682,30 +661,19 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
                 orig[..., c] = (((orig[..., c] / 255.) * gain) * 255).astype(np.uint8)
         new_img, rgb_k = preprocess_colors(_to_img(orig, dev), rgb, cfg)
         orig = (255 * new_img.cpu().numpy()).astype(np.uint8)
-        img = _to_img(resize_image(orig, orig.shape[1] // dw, orig.shape[0] // dh), dev)
-        img_main = _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev)
-        def report(t, R, row):
-            print("\n{}/{}\ntranslation error : {}\nrotation error : {}\n".format(video, filename.split("/")[-1], float(row[13]), float(row[14])))
-            if log_dir is not None:
-                _save_result_image(os.path.join(log_dir, "results", video, os.path.splitext(filename.split("/")[-1])[0] + ".png"), orig, xyz,
-                                   rgb_k, t, R, (img_main.shape[0] // 2, img_main.shape[1] // 2))
-            if done is not None:
-                done(row)
-
         on_start = None
         if getattr(cfg, "save_starting_point", False) and log_dir is not None:
             def on_start(input_trans, input_rot):
-                _save_starting_points(os.path.join(log_dir, "starting_points", video), os.path.splitext(filename.split("/")[-1])[0],
-                                      orig, xyz, rgb_k, input_trans, input_rot)
-        if batcher is not None:
-            _refine_and_score(img, img_main, xyz, rgb_k, cfg, gt_trans, gt_rot, summaries, batcher=batcher, finish=report,
-                              on_start=on_start)
-            return None, gt_trans, gt_rot, False
-        t, R, row = _refine_and_score(img, img_main, xyz, rgb_k, cfg, gt_trans, gt_rot, summaries, on_start=on_start)
-        report(t, R, row)
-        return row, gt_trans, gt_rot, False
+                _save_starting_points(os.path.join(log_dir, "starting_points", video), stem, orig, xyz, rgb_k, input_trans, input_rot)
+        return _Job(*_query_images(orig, factors, dev), orig, xyz, rgb_k, show_rgb=rgb_k, on_start=on_start)
 
-    return _run_dataset(cfg, writer, log_dir, filenames, per_image, "omniscenes_results.csv",
-                        ["pano_name", "gt_trans", "gt_rot", "skipped?", "OmniLoc_trans", "OmniLoc_rot", "t_error (m)", "r_error (degrees)",
-                         "time (s)"],
-                        lambda f: ["{}/{}".format(f.split("/")[-2], f.split("/")[-1])], omniscenes_success)
+    def report(k, job, result, row):
+        video, frame, stem = names(k)
+        print("\n{}/{}\ntranslation error : {}\nrotation error : {}\n".format(video, frame, float(row[13]), float(row[14])))
+        if log_dir is not None:
+            _save_result_image(os.path.join(log_dir, "results", video, stem + ".png"), job.orig, job.xyz, job.show_rgb, result[0], result[1],
+                               (job.img_main.shape[0] // 2, job.img_main.shape[1] // 2))
+
+    return _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
+                        int(getattr(cfg, "images_per_launch", 1)), "omniscenes_results.csv", OMNISCENES_HEADER,
+                        lambda f: ["{}/{}".format(*f.split("/")[-2:])], omniscenes_success)

@@ -112,8 +112,8 @@ def test_localize_stanford_layout(tmp_path):
     assert np.abs(est - POSES[0][0]).max() < 0.15
     img = Image.open(log / "results/area_3" / names[0])
     assert img.size == (W // 2, 2 * (H // 2))                               # GT panorama over the render, half resolution
-    # images_per_launch with sharpen_color: every image has its own equalised cloud colours, so the batcher falls back to
-    # one image per launch — same table as above
+    # images_per_launch with sharpen_color: every image has its own equalised cloud colours, and the group's cloud holds one
+    # colour set per image — same table as above
     again = localize.localize_stanford(Cfg(**{**cfg.__dict__, "images_per_launch": 4}), None, None, root=str(root)).cpu().numpy()
     again = again[:3]
     assert np.array_equal(np.isnan(again), np.isnan(table)) and np.allclose(again[:2, :13], table[:2, :13], atol=0, rtol=0)
