@@ -104,9 +104,39 @@ int pcl_cloud_pack_sets(const float *xyz, const float *const *rgb_host, int nset
  *   result[1] ("count") = sum_i w_i m_bi                                       (a float; the point count when w = 1)
  * Unit weights give the unweighted results bit for bit, 0/1 weights those of the same byte mask `visible`.
  * Deliberately left out: weights in the initialisation stage (pcl_trim_*, pcl_hist_trim_*), in the rooms / images / colour-set chains and
- * under the depth mask, and any built-in source of weights (density, semantics, change detection) — the caller brings them. */
+ * under the depth mask, and any built-in source of weights (density, semantics) — the caller brings them, or makes them
+ * from the residuals of a pose with pcl_point_residuals / pcl_robust_weights below. */
 size_t pcl_cloud_weights_bytes(int64_t n);
 int pcl_cloud_pack_weights(const float *w, const int64_t *order, int64_t n, float *plane, int32_t *bad, void *stream);
+/* Per-point residuals (additive to ABI 12; build-defined, one cloud with one colour set, no depth mask — the scope of the weights they feed):
+ * what the loss kernel sums, before it is summed.  For pose b = (trans + b * pose_stride, rot + b * pose_stride: yaw, pitch, roll)
+ *   residual[b][i] = ||c_bi - rgb_i||   where pcl_sampling_loss's mask keeps point i (the n2 * rsq(n2 + 1e-37) the loss kernel adds),
+ *                  = -1.0f exactly      where the sampled colour is exactly (0, 0, 0) and the point is masked;
+ * a pose that holds a NaN or an infinity sees nothing: its whole row is NaN (neither kept nor masked).  At a finite pose (row >= 0).sum() is pcl_sampling_loss's count, bit for bit, and the sum
+ * of the kept entries its loss numerator up to the summation order.  pose_stride = 3 reads plain [B][3] arrays; pose_stride = 16 with
+ * trans = winners, rot = winners + 13 reads the rows pcl_gd_winner wrote, on the device.  order == NULL: packed slot order,
+ * residual[b][s]; order = the order given to pcl_cloud_pack: the caller's point order, residual[b][order[s]].  Rows are n floats apart.
+ * One launch (256-thread blocks, two points per lane, chunks x poses), forward only, no workspace, no atomics; capturable.
+ * PCL_EINVAL, before any HIP call: a null cloud / pano / trans / rot / residual, n outside 1..PCL_MAX_POINTS, B <= 0 or more blocks than a
+ * grid holds, H or W <= 0, a packed panorama of 2 GiB, the trim-only texel formats PCL_PANO_U8P / PCL_PANO_U8V, pose_stride < 3. */
+int pcl_point_residuals(const float *cloud, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans, const float *rot,
+                        int pose_stride, int B, const int64_t *order, float *residual, void *stream);
+/* Robust weights from ONE residual row in packed order (residual_packed[n]; M = the number of entries that are not -1):
+ *   s = the lower median of those entries, the element of 0-based rank (M - 1) / 2 in ascending order — exact, by an MSB radix select over
+ *       the bit patterns with integer atomics only, so it does not depend on scheduling (every NaN ranks as one value behind +inf);
+ *   c = k * s (one fp32 multiply);
+ *   plane[slot] = 1 where the entry is -1 (masked at this pose: no evidence either way),
+ *                 PCL_ROBUST_TRUNC: l <= c ? 1 : 0,    PCL_ROBUST_HUBER: l <= c ? 1 : c / l (IEEE division; 0 when c is NaN),
+ *                 0 for a NaN or infinite entry under both kinds;  M == 0: every weight 1 and s = 0.
+ * `plane` is the packed plane pcl_gd_run_weighted reads: pcl_cloud_stride(n) floats, padding 0; it may be written in place of an older
+ * one.  scale_out (nullable, device float[2]) receives s and M (as a float: exact up to 2^24).  Six launches, capturable.
+ * PCL_EINVAL, before any HIP call: a null residual / plane / workspace, n outside 1..PCL_MAX_POINTS, an unknown kind, k <= 0 or not
+ * finite, workspace_bytes below pcl_robust_weights_workspace_bytes(n) (0 for n out of range). */
+#define PCL_ROBUST_TRUNC 0
+#define PCL_ROBUST_HUBER 1
+size_t pcl_robust_weights_workspace_bytes(int64_t n);
+int pcl_robust_weights(const float *residual_packed, int64_t n, int kind, float k, float *plane, float *scale_out, void *workspace,
+                       size_t workspace_bytes, void *stream);
 /* The Morton order in one call, entirely on the device: bounding box, 63-bit keys, stable radix sort of (key, index);
  * order[i] = index of the point for packed slot i.  workspace: pcl_cloud_order_workspace_bytes(n). */
 size_t pcl_cloud_order_workspace_bytes(int64_t n);

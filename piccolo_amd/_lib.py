@@ -25,6 +25,7 @@ class GdHyper(_c.Structure):
 
 
 GD_MAX_ROOMS = 32
+ROBUST_TRUNC, ROBUST_HUBER = 0, 1
 GD_PRUNE_MAX = 1024       # PCL_GD_PRUNE_MAX: candidates per group of pcl_gd_prune
 
 
@@ -45,6 +46,9 @@ SIGNATURES = {
     "pcl_cloud_pack_sets": (_int, [_vp, _c.POINTER(_vp), _int, _vp, _i64, _vp, _vp]),
     "pcl_cloud_weights_bytes": (_sz, [_i64]),
     "pcl_cloud_pack_weights": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "pcl_point_residuals": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "pcl_robust_weights_workspace_bytes": (_sz, [_i64]),
+    "pcl_robust_weights": (_int, [_vp, _i64, _int, _c.c_float, _vp, _vp, _vp, _sz, _vp]),
     "pcl_morton_keys": (_int, [_vp, _i64, _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _vp, _vp]),
     "pcl_pano_bytes": (_sz, [_int, _int, _int]),
     "pcl_pano_pack": (_int, [_vp, _int, _int, _vp, _vp]),

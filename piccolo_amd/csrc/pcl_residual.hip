@@ -1,0 +1,265 @@
+// pcl_residual.hip — what the loss kernel sums, per point, and a robust weight plane made from it on the device (additive to ABI 12).
+//
+//   pcl_point_residuals   residual[b][i] = ||c_bi - rgb_i|| where the loss kernel's mask keeps point i at pose b, exactly -1 where the sampled
+//                         colour is exactly (0, 0, 0), NaN at a pose that is not finite — one forward-only launch beside the loss kernel,
+//                         whose instances are left as they are
+//   pcl_robust_weights    s = lower median of one residual row's unmasked entries (exact MSB radix select over the bit patterns, integer
+//                         atomics only), c = k s, and the truncated / Huber weight of every point into a packed weight plane
+//
+// The residual kernel is built from the device functions the loss kernel is built from (pcl_sample_device.h): pcl_rotate2, pcl_angles2,
+// the tap fetch and the three bilinear forms inside pcl_project2 / pcl_sample2 — the weighted forward-only instance of pcl_sample2 with
+// unit weights and fresh accumulators, so a lane ends with exactly the two numbers the loss kernel would have added for its two points:
+// acc[0] = n2 * rsq(n2 + 1e-37) under the mask and acc[1] = the mask bit.  Same instructions on the same inputs: the kept set is the loss
+// kernel's count, bit for bit, and the kept values differ from its sum by the summation order only.
+// Mapping: 256-thread blocks, a lane carries the two ADJACENT packed slots 2 t, 2 t + 1 of a 512-slot step (the loss kernel pairs slot t
+// with t + 256: the packed halves never interact, so the pairing changes no value), which makes the cloud six 8-byte loads per lane and the
+// packed-order output one 8-byte store.  The pose's R and t sit in SGPRs (computed by the block from yaw / pitch / roll with
+// pcl_rot_from_ypr, what pcl_sampling_loss's pose records hold), cloud and texels go through buffer resources.  No LDS, no atomics, no
+// scratch; no allocation and no synchronisation on the host side (capturable).  The grid is chunks x poses with the pose varying fastest
+// (blocks resident together read the same chunk); it need not be pcl_plan's, because nothing is summed.
+#include "pcl_host.h"
+#include "pcl_sample_device.h"
+
+#define PCL_RES_STEP (2 * PCL_BLOCK)       // packed slots per block iteration: two per lane
+#define PCL_RES_MAX_CHUNKS 1024
+
+struct PclResArgs {
+    const float* cloud;      // 6 planes of `stride` floats: x, y, z, -r, -g, -b
+    int64_t n, stride;
+    const void* pano;
+    PclDims dims;
+    const float* trans;      // pose b: trans + b * pose_stride, rot + b * pose_stride (yaw, pitch, roll)
+    const float* rot;
+    int pose_stride, B;
+    const int64_t* order;    // ORDERED: packed slot -> the caller's point index
+    float* residual;         // [B][n]
+    int steps_base, steps_rem;   // the cloud's ceil(n / PCL_RES_STEP) steps dealt out evenly: chunk c has steps_base + (c < steps_rem)
+};
+
+typedef float pcl_f2u __attribute__((ext_vector_type(2), aligned(4)));      // a row of n floats starts on a 4-byte boundary only
+
+__device__ __forceinline__ float pcl_res_value(float sum, float kept, bool pose_ok)
+{
+    // kept: ||d||.  Not kept: -1.  A pose that holds a NaN or an infinity projects every point to NaN; the clip of the angles (v_med3) then
+    // turns the NaN into a number and the point samples a corner of the panorama as if it had been seen there: such a point is neither
+    // kept nor masked here, it is NaN — nobody takes a pose that sees nothing for one whose points agree or are masked
+    if (!pose_ok || sum != sum) return __builtin_nanf("");
+    return kept != 0.f ? sum : -1.f;
+}
+
+template <int FMT, bool ORDERED>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_point_residuals_kernel(PclResArgs a)
+{
+    const unsigned b = blockIdx.x % (unsigned)a.B, chunk = blockIdx.x / (unsigned)a.B;
+    // the pose as six SGPR pairs (R0,R1)(R2,R3)(R4,R5)(R6,R7)(R8,t0)(t1,t2): every lane computes the same R, the first one's is read
+    const float* __restrict__ tp = a.trans + (int64_t)b * a.pose_stride;
+    const float* __restrict__ rp = a.rot + (int64_t)b * a.pose_stride;
+    float v[12];
+    pcl_rot_from_ypr(rp[0], rp[1], rp[2], v);
+    v[9] = tp[0]; v[10] = tp[1]; v[11] = tp[2];
+#pragma unroll
+    for (int k = 0; k < 12; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v[k])));
+    bool pose_ok = true;                                      // wave-uniform: R and t finite
+#pragma unroll
+    for (int k = 0; k < 12; k++) pose_ok = pose_ok && fabsf(v[k]) <= 3.402823466e38f;
+    const PclPose6 P{(f2){v[0], v[1]}, (f2){v[2], v[3]}, (f2){v[4], v[5]}, (f2){v[6], v[7]}, (f2){v[8], v[9]}, (f2){v[10], v[11]}};
+
+    __amdgpu_buffer_rsrc_t tex = pcl_tex_rsrc(a.pano, a.dims.H, a.dims.W, pcl_texel_bytes(FMT));
+    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, (int)(a.stride * 6 * 4), 0x00020000);
+    const int plane = (int)a.stride * 4;
+    float* __restrict__ row = a.residual + (int64_t)b * a.n;
+
+    const int first = (int)chunk * a.steps_base + min((int)chunk, a.steps_rem);
+    const int nsteps = a.steps_base + ((int)chunk < a.steps_rem ? 1 : 0);
+    const int n = (int)a.n, last_pair = (int)a.stride - 2;
+    for (int s = first; s < first + nsteps; s++) {
+        const int i0 = s * PCL_RES_STEP + 2 * (int)threadIdx.x, i1 = i0 + 1;
+        const bool valid0 = i0 < n, valid1 = i1 < n;
+        const int j = min(i0, last_pair);                     // (the planes are padded to a multiple of 256 slots: a pair never leaves its plane)
+        f2 p[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) p[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(cld, j * 4, k * plane, 0));
+        PclProj<FMT> pj;
+        pcl_project2<FMT>(p[0], p[1], p[2], P, tex, a.dims, pj);
+        f2 acc[PCL_NACC];
+#pragma unroll
+        for (int k = 0; k < PCL_NACC; k++) acc[k] = F2(0.f);
+        int count = 0;
+        pcl_sample2<false, FMT, true>(pj, p[3], p[4], p[5], valid0, valid1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
+        const float r0 = pcl_res_value(acc[0].x, acc[1].x, pose_ok), r1 = pcl_res_value(acc[0].y, acc[1].y, pose_ok);
+        if constexpr (ORDERED) {
+            if (valid0) {
+                const int64_t o = a.order[i0];
+                if ((uint64_t)o < (uint64_t)a.n) row[o] = r0;
+            }
+            if (valid1) {
+                const int64_t o = a.order[i1];
+                if ((uint64_t)o < (uint64_t)a.n) row[o] = r1;
+            }
+        } else {
+            if (valid1) *reinterpret_cast<pcl_f2u*>(row + i0) = (pcl_f2u){r0, r1};
+            else if (valid0) row[i0] = r0;
+        }
+    }
+}
+
+extern "C" int pcl_point_residuals(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans, const float* rot,
+                                   int pose_stride, int B, const int64_t* order, float* residual, void* stream)
+{
+    if (!cloud || !pano || !trans || !rot || !residual) return PCL_EINVAL;
+    if (n <= 0 || n > PCL_MAX_POINTS || B <= 0 || H <= 0 || W <= 0 || pose_stride < 3) return PCL_EINVAL;
+    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;      // (U8P / U8V: trim only)
+    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    const int64_t steps = (n + PCL_RES_STEP - 1) / PCL_RES_STEP;
+    const int64_t nchunks = steps < PCL_RES_MAX_CHUNKS ? steps : PCL_RES_MAX_CHUNKS;
+    if (nchunks * B > 0x7fffffffll) return PCL_EINVAL;
+    PclResArgs a;
+    a.cloud = cloud; a.n = n; a.stride = pcl_cloud_stride(n);
+    a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
+    a.trans = trans; a.rot = rot; a.pose_stride = pose_stride; a.B = B;
+    a.order = order; a.residual = residual;
+    a.steps_base = (int)(steps / nchunks); a.steps_rem = (int)(steps % nchunks);
+    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    pcl_with_flag(order != nullptr, [&](auto ord) {
+        constexpr bool ORD = decltype(ord)::value;
+        if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL((pcl_point_residuals_kernel<PCL_PANO_U8, ORD>), grid, blk, 0, s, a);
+        else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL((pcl_point_residuals_kernel<PCL_PANO_F16, ORD>), grid, blk, 0, s, a);
+        else hipLaunchKernelGGL((pcl_point_residuals_kernel<PCL_PANO_F32, ORD>), grid, blk, 0, s, a);
+    });
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// robust weights: the scale of one residual row and the weight plane, pcl_quantile_box's way — an exact order statistic by a 4-pass MSB
+// radix select over order-preserving uint32 keys, integer atomics only, so the result does not depend on scheduling.  The rank is not
+// known beforehand (M, the number of entries that are not -1, is pass 0's total), and there is no scan launch: every block of a later
+// pass resolves the earlier passes' histograms itself (256 counts each), and so does the weight kernel.  Six launches in all.
+
+struct PclRobustState { uint32_t hist[4][256]; };                  // (n <= 2^27: a count fits 32 bits)
+struct PclRobustWs { PclRobustState* st; };
+static size_t robust_layout(void* base, PclRobustWs* w)
+{
+    PclCarve c{(char*)base, 0};
+    w->st = (PclRobustState*)c.take(sizeof(PclRobustState));
+    return c.off;
+}
+
+extern "C" size_t pcl_robust_weights_workspace_bytes(int64_t n)
+{
+    PclRobustWs w;
+    return n <= 0 || n > PCL_MAX_POINTS ? 0 : robust_layout(nullptr, &w);
+}
+
+// ascending floats -> ascending keys; every NaN is ONE key behind +inf (a NaN residual comes from a NaN pose, with either sign bit)
+__device__ __forceinline__ uint32_t pcl_rw_key(float l)
+{
+    uint32_t u = l != l ? 0x7fc00000u : __float_as_uint(l);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float pcl_rw_key2f(uint32_t k)
+{
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// What the first `npass` histograms say, computed by all 256 threads of a block: M, the known high bytes of the wanted key and the wanted
+// rank among the entries that share them.  The wanted rank is (M - 1) / 2, the lower median.
+__device__ __forceinline__ void pcl_rw_resolve(const PclRobustState* st, int npass, uint32_t& prefix, uint32_t& rank, uint32_t& M)
+{
+    __shared__ uint32_t wave_tot[PCL_BLOCK / PCL_WAVE], sel[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    prefix = 0u; rank = 0u; M = 0u;
+    for (int p = 0; p < npass; p++) {
+        const uint32_t h = st->hist[p][tid];
+        uint32_t incl = h;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) wave_tot[wave] = incl;
+        if (tid == 0) { sel[0] = 0u; sel[1] = 0u; }
+        __syncthreads();
+        uint32_t before = 0u, total = 0u;
+        for (int w = 0; w < PCL_BLOCK / PCL_WAVE; w++) {
+            if (w < wave) before += wave_tot[w];
+            total += wave_tot[w];
+        }
+        incl += before;
+        const uint32_t excl = incl - h;
+        if (p == 0) { M = total; rank = M ? (M - 1u) / 2u : 0u; }
+        if (excl <= rank && rank < incl) { sel[0] = (uint32_t)tid; sel[1] = excl; }       // exactly one bin (none when M == 0)
+        __syncthreads();
+        prefix |= sel[0] << (24 - 8 * p);
+        rank -= sel[1];
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_init_kernel(PclRobustState* st)
+{
+    (&st->hist[0][0])[blockIdx.x * PCL_BLOCK + threadIdx.x] = 0u;
+}
+
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_hist_kernel(const float* __restrict__ res, int64_t n, PclRobustState* st, int pass)
+{
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0u;
+    uint32_t prefix, rank, M;
+    pcl_rw_resolve(st, pass, prefix, rank, M);
+    __syncthreads();
+    const int shift = 24 - 8 * pass;
+    const uint32_t known = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+    for (int64_t i = (int64_t)blockIdx.x * PCL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * PCL_BLOCK) {
+        const float l = res[i];
+        if (l == -1.0f) continue;                                  // masked at this pose: no evidence
+        const uint32_t k = pcl_rw_key(l);
+        if ((k & known) == prefix) atomicAdd(&h[(k >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const uint32_t c = h[threadIdx.x];
+    if (c) atomicAdd(&st->hist[pass][threadIdx.x], c);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_plane_kernel(const float* __restrict__ res, int64_t n, int64_t stride, const PclRobustState* st, float k,
+                                                                 float* __restrict__ plane, float* __restrict__ scale_out)
+{
+    uint32_t prefix, rank, M;
+    pcl_rw_resolve(st, 4, prefix, rank, M);
+    const float s = M ? pcl_rw_key2f(prefix) : 0.f;
+    const float c = __fmul_rn(k, s);
+    if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) { scale_out[0] = s; scale_out[1] = (float)M; }
+    for (int64_t i = (int64_t)blockIdx.x * PCL_BLOCK + threadIdx.x; i < stride; i += (int64_t)gridDim.x * PCL_BLOCK) {
+        float w = 0.f;                                             // padding
+        if (i < n) {
+            const float l = res[i];
+            if (l == -1.0f || M == 0u) w = 1.f;
+            else if (!(fabsf(l) <= 3.402823466e38f)) w = 0.f;      // NaN or infinite
+            else if (l <= c) w = 1.f;
+            else if (KIND == PCL_ROBUST_HUBER && c == c) w = __fdiv_rn(c, l);      // (a NaN scale — most of the row NaN — votes 0)
+        }
+        plane[i] = w;
+    }
+}
+
+extern "C" int pcl_robust_weights(const float* residual_packed, int64_t n, int kind, float k, float* plane, float* scale_out, void* workspace,
+                                  size_t workspace_bytes, void* stream)
+{
+    if (!residual_packed || !plane || !workspace || n <= 0 || n > PCL_MAX_POINTS) return PCL_EINVAL;
+    if ((kind != PCL_ROBUST_TRUNC && kind != PCL_ROBUST_HUBER) || !(k > 0.f && k <= 3.402823466e38f)) return PCL_EINVAL;
+    PclRobustWs w;
+    if (workspace_bytes < robust_layout(workspace, &w)) return PCL_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t stride = pcl_cloud_stride(n), want = stride / PCL_BLOCK;
+    const unsigned nblk = (unsigned)(want < 1024 ? want : 1024);
+    hipLaunchKernelGGL(pcl_rw_init_kernel, dim3(4), dim3(PCL_BLOCK), 0, s, w.st);
+    for (int pass = 0; pass < 4; pass++) hipLaunchKernelGGL(pcl_rw_hist_kernel, dim3(nblk), dim3(PCL_BLOCK), 0, s, residual_packed, n, w.st, pass);
+    if (kind == PCL_ROBUST_HUBER)
+        hipLaunchKernelGGL(pcl_rw_plane_kernel<PCL_ROBUST_HUBER>, dim3(nblk), dim3(PCL_BLOCK), 0, s, residual_packed, n, stride, w.st, k, plane, scale_out);
+    else
+        hipLaunchKernelGGL(pcl_rw_plane_kernel<PCL_ROBUST_TRUNC>, dim3(nblk), dim3(PCL_BLOCK), 0, s, residual_packed, n, stride, w.st, k, plane, scale_out);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}

@@ -24,7 +24,7 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_rooms_images
+from .omniloc import ROBUST_KEYS, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_rooms_images, robust_schedule
 from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
 
@@ -47,7 +47,8 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
     """localize.py:215-233: run the refinement the config asks for and pick the min-loss candidate.
     Returns (t (3,1), R (3,3), loss) as cpu tensors.  weights (not in the reference): (N,) per-point weights of the refinement's loss.
     cfg.prune_iters / cfg.prune_keep (omniloc.prune_schedule) prune the parallel refinement's candidates on the device; the non-parallel
-    branch returns every candidate and refuses the keys (ValueError), as omniloc_all does."""
+    branch returns every candidate and refuses the keys (ValueError), as omniloc_all does.  cfg.robust_iters / robust_kind / robust_k
+    (omniloc.robust_schedule): the parallel branch runs omniloc_batch's robust chain; the non-parallel branch refuses them as well."""
     summaries = scalar_summaries if scalar_summaries is not None else {}
     if getattr(cfg, "parallel", False):
         results = [omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)]
@@ -56,6 +57,21 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
         results = omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)
     best = min(range(len(results)), key=lambda i: float(results[i][2]))
     return results[best][0], results[best][1], results[best][2]
+
+
+def _check_robust_cfg(cfg):
+    """Configuration-time refusal of the robust keys where the harness would refine through an entry point that does not take them: several
+    images per launch chain and the room searches (omniloc._no_robust is what those entry points would raise, after the first cloud is read)."""
+    for key in ROBUST_KEYS:
+        if getattr(cfg, key, None) is None:
+            continue
+        if int(getattr(cfg, "images_per_launch", 1)) > 1:
+            raise ValueError("cfg.%s does not combine with images_per_launch > 1 (one image per refinement)" % key)
+        for other in ("room_search", "room_search_images"):
+            if getattr(cfg, other, None):
+                raise ValueError("cfg.%s does not combine with cfg.%s" % (key, other))
+        robust_schedule(cfg)                          # (its own ValueErrors, before any file is read)
+        return
 
 
 def _make_input_args(cfg, init_dict=None):
@@ -480,6 +496,7 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     cfg.images_per_launch is the group size of _run_dataset (_localize_known_room).
     cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms)."""
     _require_gravity_aligned(cfg)
+    _check_robust_cfg(cfg)
     room_search = getattr(cfg, "room_search", None)
     if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
         raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")
@@ -620,6 +637,7 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
     and the colour preprocessing of the whole image (match_color / sharpen_color).  cfg.images_per_launch is the group size of
     _run_dataset (_localize_known_room)."""
     _require_gravity_aligned(cfg)
+    _check_robust_cfg(cfg)
     _seed_all()
     dev = ops.device()
     split = getattr(cfg, "split_name", "extreme")

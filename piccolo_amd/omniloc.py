@@ -19,6 +19,10 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
     point of the Morton-ordered cloud (default: pcl_depth_default's choice; every point is still tested against it);
   * extra, optional cfg keys prune_iters / prune_keep (default absent = reference behaviour): the batch refinements drop all but the best
     prune_keep candidates of every image after prune_iters iterations, on the device (prune_schedule, csrc/pcl_prune.hip);
+  * extra, optional cfg keys robust_iters / robust_kind / robust_k (default absent = reference behaviour): omniloc_batch re-weights the
+    cloud's points from the residuals of its current best candidate after robust_iters iterations, on the device, and the same optimiser
+    state goes on under the weighted loss (robust_schedule, csrc/pcl_residual.hip); point_residuals / robust_weights give the same per-point
+    quantities to a caller;
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
     per iteration) as 4th element.
@@ -294,6 +298,69 @@ def prune_schedule(cfg, per_image):
     return [(e - b, c) for b, e, c in zip([0] + iters, ends, counts)]
 
 
+# ------------------------------------------------------------------------------------------------ robust chains
+# cfg robust_iters / robust_kind / robust_k (not in the reference; absent by default): a built-in source of per-point weights for a scene
+# that changed since the cloud was scanned.  After robust_iters[j] iterations in all the chain takes the candidate pcl_gd_winner names, the
+# per-point residuals at its pose (pcl_point_residuals), their lower median s, and weighs every point l <= k s ? 1 : 0 ("trunc") or
+# l <= k s ? 1 : k s / l ("huber"); the SAME optimiser state goes on under pcl_gd_run_weighted.  Nothing waits for the host.  The returned
+# loss is the WEIGHTED loss of the last forward; Adam's moments and the plateau scheduler carry on across the switch, so the scheduler's
+# `best` then compares weighted with unweighted losses — it is not reset.  One cloud, one colour set, one image, no depth mask.
+ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
+
+
+def _no_robust(cfg, who):
+    """what does not run the robust chain refuses its keys, naming the first one it finds"""
+    for key in ROBUST_KEYS:
+        if _cfg(cfg, key, None) is not None:
+            raise ValueError("%s does not take cfg.%s (omniloc_batch and localize.refine_image's parallel branch do)" % (who, key))
+
+
+def robust_schedule(cfg):
+    """(robust_iters as a list, kind, k) of a refinement under cfg.robust_iters (an int, or a strictly increasing list inside (0, num_iter)),
+    cfg.robust_kind ("trunc", the default, or "huber") and cfg.robust_k (default 2.5), or None when the keys are absent.  The chain's
+    segments end at robust_iters + [num_iter]: robust_iters = [4, 8] at num_iter 12 runs 4 unweighted, 4 and 4 weighted iterations.
+    ValueError: robust_kind / robust_k without robust_iters, entries that are not ints, iterations not strictly increasing inside
+    (0, num_iter), an unknown kind, k not a positive finite number; the depth mask or the prune keys next to them.  Host only."""
+    iters, kind, k = (_cfg(cfg, key, None) for key in ROBUST_KEYS)
+    if iters is None and kind is None and k is None:
+        return None
+    if iters is None:
+        raise ValueError("cfg.%s goes with cfg.robust_iters" % ("robust_kind" if kind is not None else "robust_k"))
+    iters = list(iters) if isinstance(iters, (list, tuple)) else [iters]
+    if not iters or any(isinstance(x, bool) or not isinstance(x, int) for x in iters):
+        raise ValueError("cfg.robust_iters: an int or a list of ints, got %r" % (iters,))
+    num_iter = int(_cfg(cfg, "num_iter", 100))
+    if any(not 0 < i < num_iter for i in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
+        raise ValueError("cfg.robust_iters %r: strictly increasing iteration counts inside (0, %d)" % (iters, num_iter))
+    kind = "trunc" if kind is None else kind
+    if kind not in ops.ROBUST_KINDS:
+        raise ValueError("cfg.robust_kind %r: one of %s" % (kind, sorted(ops.ROBUST_KINDS)))
+    k = 2.5 if k is None else k
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or not (0.0 < float(k) < float("inf")):
+        raise ValueError("cfg.robust_k %r: a positive finite number" % (k,))
+    if bool(_cfg(cfg, "depth_mask", False)):
+        raise ValueError("cfg.robust_iters does not combine with cfg.depth_mask")
+    if _cfg(cfg, "prune_iters", None) is not None or _cfg(cfg, "prune_keep", None) is not None:
+        raise ValueError("cfg.robust_iters does not combine with cfg.prune_iters / cfg.prune_keep")
+    return iters, kind, float(k)
+
+
+def point_residuals(img, xyz, rgb, trans, rot):
+    """(B, N) GPU tensor, in the order of xyz's rows: per point the ||c - rgb|| the sampling loss sums at the poses trans / rot ((B, 3)
+    tensors: translation; yaw, pitch, roll) where its mask keeps the point, exactly -1 where the point samples exact black
+    (ops.point_residuals over the cached packed cloud and panorama)."""
+    return ops.point_residuals(packed_cloud(xyz, rgb), packed_pano(img, n_points=xyz.shape[0]), trans, rot)
+
+
+def robust_weights(residuals_row, kind="trunc", k=2.5):
+    """(N,) GPU weights in the caller's point order from ONE row of point_residuals, usable as `weights=` wherever weights are taken: with s
+    the lower median of the entries that are not -1, "trunc": l <= k s ? 1 : 0, "huber": l <= k s ? 1 : k s / l; masked points (-1) weigh 1,
+    NaN or infinite residuals 0 (pcl_robust_weights — the weights do not depend on the order of the points)."""
+    row = ops._dev(residuals_row).reshape(-1)
+    n = int(row.numel())
+    return ops.robust_plane(n, row, kind, k)[0][:n].clone()
+
+
 class _PrunedChain:
     """What a pruned refinement hands back in place of its engine: winners() of the LAST segment's engine, and every candidate's leaf row
     written back to the caller's buffers — a dropped candidate's from the prune call that dropped it (its pose at that time), a
@@ -361,6 +428,12 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, we
     of one per query image (per-image colour sets: image i's candidates read set i, and the chain runs the single-image plan).
     The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape (_cached_engine).  `weights`: (N,)
     per-point weights (one colour set, no depth mask)."""
+    robust = robust_schedule(cfg)
+    if robust is not None:
+        if weights is not None:
+            raise ValueError("cfg.robust_iters does not combine with weights= (the chain makes its own)")
+        if isinstance(rgb, list) or len(panos) != 1 or not batch_mode or vis_hook is not None:
+            raise ValueError("cfg.robust_iters: the parallel refinement of one image over one colour set only")
     if weights is not None and isinstance(rgb, list):
         raise ValueError("per-point weights do not combine with per-image colour sets")
     if weights is not None and bool(_cfg(cfg, "depth_mask", False)):
@@ -379,7 +452,9 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, we
         def make(cs, bs):
             return ops.GradientDescent(cs[0], p0, trans[:Bs], rot[:Bs], bs[0], **args)
         # (one or two launches per iteration is frozen into a captured graph: part of the key, with the other arguments)
-        return _cached_engine("gd", (xyz,), (Bs, len(panos), p0.H, p0.W, p0.fmt, cloud.color_sets, cloud.weights is not None) + tuple(args.values()), make, [cloud], [box])
+        # (a robust chain has engines of its own: a plain call never meets an engine whose plane is switched on)
+        return _cached_engine("gd", (xyz,), (Bs, len(panos), p0.H, p0.W, p0.fmt, cloud.color_sets, cloud.weights is not None) + tuple(args.values())
+                              + (("robust",) if robust is not None else ()), make, [cloud], [box])
     if not use_graph:
         gd = ops.GradientDescent(cloud, p0, trans, rot, box, **args)      # (fresh buffers: nothing worth keeping for a long eager chain)
     else:
@@ -393,7 +468,9 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, we
             raise ValueError("cfg.visualize does not combine with cfg.prune_iters / cfg.prune_keep")
         return _run_segments(sched, len(panos), gd, lambda per: cloud.n * len(panos) * per, cfg, args["depth_mask"],
                              lambda per: cached(len(panos) * per)[0])
-    if vis_hook is not None:
+    if robust is not None:
+        gd.run_robust(num_iter, robust[0], robust[1], robust[2], graph=use_graph)
+    elif vis_hook is not None:
         vis_hook(gd, num_iter)
     elif use_graph:
         gd.run_graph(num_iter)
@@ -461,6 +538,7 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     reference where the optimised tensors are views of those rows (omniloc.py:15-19).
     """
     _no_prune(cfg, "omniloc")
+    _no_robust(cfg, "omniloc")
     vis = _cfg(cfg, "visualize", False)
     out_quantile = _cfg(cfg, "out_of_room_quantile", 0.05)
 
@@ -514,6 +592,7 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     Every starting point keeps omniloc's SEQUENTIAL semantics (its own Adam / scheduler, clamp applied to the parameters
     the next forward reads) and the points never interact, so the list returned equals the K separate calls."""
     _no_prune(cfg, "omniloc_all")
+    _no_robust(cfg, "omniloc_all")
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False, weights=weights).result()
     K = res.shape[0]
@@ -528,7 +607,11 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
 def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, weights=None):
     """Parallel refinement of all starting poses; returns [t (3,1), R (3,3), loss ()] of the candidate whose LAST
     forward had the smallest loss (omniloc.py:271).  Keeps the reference's clamp lag (omniloc.py:260-269): the
-    returned translation is the post-step, pre-clamp value (omniloc.py:272)."""
+    returned translation is the post-step, pre-clamp value (omniloc.py:272).
+    cfg.robust_iters / robust_kind / robust_k (robust_schedule; not in the reference): the robust chain — the returned loss is then the
+    WEIGHTED loss of the last forward, the return shapes are unchanged.  Not with weights=, cfg.depth_mask or the prune keys (ValueError)."""
+    if robust_schedule(cfg) is not None and weights is not None:          # (and the schedule's own refusals, before a device is touched)
+        raise ValueError("cfg.robust_iters does not combine with weights= (the chain makes its own)")
     if strict_reference_asserts:
         assert cfg.num_input > 1
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
@@ -558,6 +641,7 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     and the chain runs the single-image plan, so image i's result is omniloc_batch(imgs[i], xyz, rgb[i], ...)'s bit for bit.  Images
     beyond the colour-set addressing limit go in further groups.  With the depth mask the colour-set chain is the depth chain
     (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image."""
+    _no_robust(cfg, "omniloc_batch_images")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     I = len(imgs)
@@ -663,6 +747,7 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     each room's candidates).  More than PCL_GD_MAX_ROOMS rooms go in several chains.  With the depth mask the chain is the depth chain
     (pcl_gd_run_depth_chain: every room on its own z-buffer grid, the same bits per room); rooms whose tolerances differ (depth_tau_groups)
     go in a chain per tolerance."""
+    _no_robust(cfg, "omniloc_batch_rooms")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R = len(rooms)
@@ -736,6 +821,7 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     the depth chain (pcl_gd_run_depth_chain) under the same rules; rooms whose tolerances differ (depth_tau_groups) go in a chain per
     tolerance, and images that share the rooms' colours run omniloc_batch_images per room where that is faster (depth_shared_chain_pays:
     its plan of all the images' candidates, so equal to the single calls up to the summation order of the partial sums, as there)."""
+    _no_robust(cfg, "omniloc_batch_rooms_images")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R, I = len(rooms), len(imgs)

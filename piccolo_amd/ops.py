@@ -124,6 +124,20 @@ class Cloud:
             raise ValueError("weights must be non-negative and finite")
         self.weights = plane
 
+    def weighted_view(self, plane):
+        """A Cloud that SHARES this one's packed buffer, order and xyz and carries `plane` as its weight plane (the packed plane of
+        pcl_cloud_pack_weights / robust_weights: pcl_cloud_stride(n) float32 on the GPU, used as it is — not copied, not checked).  This
+        cloud itself stays as it is: a cached unweighted pack never becomes weighted through a view."""
+        if self.color_sets > 1:
+            raise ValueError("weighted_view: a cloud of colour sets takes no weights")
+        if not (torch.is_tensor(plane) and plane.is_cuda and plane.dtype == F32 and plane.is_contiguous()
+                and plane.numel() == _lib.load().pcl_cloud_stride(self.n)):
+            raise ValueError("weighted_view: the plane must be a contiguous float32 GPU tensor of pcl_cloud_stride(n) entries")
+        c = Cloud.__new__(Cloud)
+        c.n, c.order, c.xyz, c.data = self.n, self.order, self.xyz, self.data
+        c.weights = plane
+        return c
+
     @classmethod
     def private_copy(cls, other):
         """A Cloud with its own packed buffer holding `other`'s contents (same point order): for an engine whose captured graph
@@ -396,6 +410,85 @@ def sampling_loss(cloud, pano, trans, rot, with_grad=True, visible=None, depth=N
                                      1 if with_grad else 0, _ptr(vis), _ptr(out), _ptr(ws), ws_bytes, _stream()),
                "pcl_sampling_loss")
     return out
+
+
+def _residual_cloud(cloud, pano, who):
+    if cloud.color_sets > 1:
+        raise ValueError("%s: a cloud of colour sets (one colour set only)" % who)
+    if pano.fmt not in (_lib.PANO_F32, _lib.PANO_U8, _lib.PANO_F16):
+        raise ValueError("%s: the trim launch's texel layouts (u8p, u8v) are not sampled here" % who)
+
+
+def point_residuals(cloud, pano, trans, rot, packed=False):
+    """(B, N) float GPU tensor: row b holds, per point, the ||c - rgb|| the loss kernel sums at pose (trans[b], rot[b]) where its mask keeps
+    the point and exactly -1 where the sampled colour is exactly black (pcl_point_residuals) — in the order of the cloud's xyz rows, or with
+    packed=True in the packed slot order (what robust_weights reads).  A cloud's weights play no part.  ValueError: a cloud of colour sets,
+    a panorama in one of the trim launch's texel layouts."""
+    lib = _lib.load()
+    _residual_cloud(cloud, pano, "point_residuals")
+    trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+    B = int(trans.shape[0])
+    if rot.shape[0] != B or B == 0:
+        raise ValueError("trans and rot must have the same, positive number of rows")
+    out = torch.empty(B, cloud.n, dtype=F32, device=trans.device)
+    _lib.check(lib.pcl_point_residuals(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans), _ptr(rot), 3, B,
+                                       None if packed else _ptr(cloud.order), _ptr(out), _stream()), "pcl_point_residuals")
+    return out
+
+
+def point_residuals_at_winners(cloud, pano, winners, packed=False, out=None):
+    """point_residuals at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (pose stride 16: translation in
+    columns 0-2, yaw / pitch / roll in 13-15) — no host round trip between a chain and the residuals of its winner.  out: a (G, N) tensor to
+    write into."""
+    lib = _lib.load()
+    _residual_cloud(cloud, pano, "point_residuals_at_winners")
+    if not (torch.is_tensor(winners) and winners.is_cuda and winners.dtype == F32 and winners.is_contiguous() and winners.dim() == 2
+            and winners.shape[1] == 16 and winners.shape[0] > 0):
+        raise ValueError("point_residuals_at_winners: winners must be a contiguous (G, 16) float32 GPU tensor")
+    G = int(winners.shape[0])
+    if out is None:
+        out = torch.empty(G, cloud.n, dtype=F32, device=winners.device)
+    elif not (out.is_cuda and out.dtype == F32 and out.is_contiguous() and out.numel() == G * cloud.n):
+        raise ValueError("point_residuals_at_winners: out must be a contiguous (G, N) float32 GPU tensor")
+    rot = ctypes.c_void_p(winners.data_ptr() + 13 * 4)
+    _lib.check(lib.pcl_point_residuals(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(winners), rot, 16, G,
+                                       None if packed else _ptr(cloud.order), _ptr(out), _stream()), "pcl_point_residuals")
+    return out
+
+
+ROBUST_KINDS = {"trunc": _lib.ROBUST_TRUNC, "huber": _lib.ROBUST_HUBER}
+
+
+def robust_weights(cloud, residual_row_packed, kind="trunc", k=2.5, plane=None, scale=None):
+    """(plane, scale) from ONE row of point_residuals(..., packed=True): scale = (s, M) on the GPU, s the lower median of the row's M
+    entries that are not -1, and plane the packed weight plane (pcl_cloud_stride(n) floats, what Cloud.weighted_view takes) of
+    kind "trunc": l <= k s ? 1 : 0 or "huber": l <= k s ? 1 : k s / l; a masked point (-1) weighs 1, a NaN or infinite residual 0, and with
+    M = 0 every point weighs 1 (pcl_robust_weights).  plane / scale: tensors to write into (a plane a captured graph reads, in place)."""
+    return robust_plane(cloud.n, residual_row_packed, kind, k, plane, scale)
+
+
+def robust_plane(n, row, kind="trunc", k=2.5, plane=None, scale=None):
+    """robust_weights for a row of n residuals in any one point order: the plane's first n entries are in that order"""
+    lib = _lib.load()
+    if kind not in ROBUST_KINDS:
+        raise ValueError("robust_weights: kind %r (one of %s)" % (kind, sorted(ROBUST_KINDS)))
+    k = float(k)
+    if not (k > 0.0 and k < float("inf")):
+        raise ValueError("robust_weights: k must be positive and finite, got %r" % (k,))
+    row = _dev(row)
+    if row.dim() != 1 or row.numel() != n or n <= 0:
+        raise ValueError("robust_weights: one residual per point, (N,)")
+    stride = lib.pcl_cloud_stride(n)
+    if plane is None:
+        plane = torch.empty(stride, dtype=F32, device=row.device)
+    elif not (plane.is_cuda and plane.dtype == F32 and plane.is_contiguous() and plane.numel() == stride):
+        raise ValueError("robust_weights: plane must be a contiguous float32 GPU tensor of pcl_cloud_stride(n) entries")
+    if scale is None:
+        scale = torch.empty(2, dtype=F32, device=row.device)
+    nws = lib.pcl_robust_weights_workspace_bytes(n)
+    ws = _bytes(nws)
+    _lib.check(lib.pcl_robust_weights(_ptr(row), n, ROBUST_KINDS[kind], k, _ptr(plane), _ptr(scale), _ptr(ws), nws, _stream()), "pcl_robust_weights")
+    return plane, scale
 
 
 TRIM_MAX_ROT = 1024        # pcl_trim_groups: rotations per table (include/piccolo_hip.h)
@@ -767,10 +860,12 @@ class _GdEngine:
     def run_graph(self, num_iter):
         """Same as run(num_iter) but the 2 * num_iter launches are captured into one hipGraph and replayed: the host
         enqueues one graph instead of 200 kernels per refinement (pcl_gd_run neither allocates nor synchronises, so it
-        is capture-safe).  The instantiated graph is cached per num_iter; replaying it continues from the current
-        state, exactly like calling run() again."""
+        is capture-safe).  The instantiated graph is cached per num_iter and _graph_key() — what else the captured launches
+        depend on: a graph captured for an unweighted segment is never replayed for a weighted one; replaying it continues
+        from the current state, exactly like calling run() again."""
         cache = self.__dict__.setdefault("_graphs", {})
-        g = cache.get(num_iter)
+        key = (num_iter,) + tuple(self._graph_key())
+        g = cache.get(key)
         if g is None:
             g = torch.cuda.CUDAGraph()
             side = torch.cuda.Stream(device=self.state.device)
@@ -779,9 +874,13 @@ class _GdEngine:
                 with torch.cuda.graph(g, stream=side):
                     self.run(num_iter)
             torch.cuda.current_stream().wait_stream(side)
-            cache[num_iter] = g
+            cache[key] = g
             # capture does not execute: fall through to the first replay
         g.replay()
+
+    def _graph_key(self):
+        """what, besides num_iter, a captured run() depends on (GradientDescent: the weight plane it reads)"""
+        return ()
 
     def _name_panos(self, panos):
         """The pose records of candidates [i * B / I, (i + 1) * B / I) name panos[i] (I Pano objects of the size / texel format of self.pano):
@@ -892,9 +991,10 @@ class GradientDescent(_GdEngine):
         if self._chain is not None:
             return self._chain.run(num_iter, history, timer)
         hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
-        if self.cloud.weights is not None:
+        weights = self._run_weights()
+        if weights is not None:
             # (the plane's address is the cloud's for good — Cloud.set_weights packs in place — so a captured graph reads the current weights)
-            _lib.check(_lib.load().pcl_gd_run_weighted(_ptr(self.cloud.data), _ptr(self.cloud.weights), self.cloud.n, _ptr(self.pano.data), self.pano.fmt,
+            _lib.check(_lib.load().pcl_gd_run_weighted(_ptr(self.cloud.data), _ptr(weights), self.cloud.n, _ptr(self.pano.data), self.pano.fmt,
                                                        self.pano.H, self.pano.W, _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper),
                                                        int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None,
                                                        _stream()), "pcl_gd_run_weighted")
@@ -904,6 +1004,69 @@ class GradientDescent(_GdEngine):
                                           _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None, _stream()),
                    "pcl_gd_run")
         return hist
+
+    def _run_weights(self):
+        """the weight plane run() evaluates: the engine's own robust plane once robust_reweight has filled it, else the cloud's, else None"""
+        robust = self.__dict__.get("_robust")
+        return robust["plane"] if robust is not None and robust["on"] else self.cloud.weights
+
+    def _graph_key(self):
+        w = self._run_weights() if self._chain is None else None
+        return (0 if w is None else w.data_ptr(),)
+
+    # ---- robust re-weighting (cfg.robust_iters of omniloc_batch): the SAME state goes on under weights made from its own winner's residuals.
+    def robust_clear(self):
+        """back to the cloud's own weights (none, for a robust chain): what a new refinement on a cached engine starts with"""
+        if self.__dict__.get("_robust") is not None:
+            self._robust["on"] = False
+
+    def robust_reweight(self, kind="trunc", k=2.5):
+        """pcl_gd_winner -> pcl_point_residuals at the pose that call reports (stride 16, packed, on the device) -> pcl_robust_weights into the
+        engine's OWN plane, in place at a stable address; from here on run() evaluates the weighted loss (pcl_gd_run_weighted) with the state
+        as it is.  Eight launches, nothing waits for the host.  One image, one colour set, no depth mask, a cloud without weights of its own.
+        -> (plane, scale): the plane and the device (s, M) of this re-weighting."""
+        if self._chain is not None or self.hyper.depth_mask or self.cloud.color_sets > 1:
+            raise ValueError("robust_reweight: one colour set and no depth mask")
+        if self.cloud.weights is not None:
+            raise ValueError("robust_reweight: the cloud carries per-point weights of its own")
+        panos = {id(p): p for p in self.__dict__.get("_panos", [])}
+        if len(panos) > 1:
+            raise ValueError("robust_reweight: the candidates of one image only")
+        pano = next(iter(panos.values())) if panos else self.pano
+        lib, r = _lib.load(), self.__dict__.get("_robust")
+        if r is None:
+            dev = self.state.device
+            r = self._robust = {"on": False, "plane": torch.empty(lib.pcl_cloud_stride(self.cloud.n), dtype=F32, device=dev),
+                                "row": torch.empty(1, self.cloud.n, dtype=F32, device=dev), "scale": torch.empty(2, dtype=F32, device=dev),
+                                "ws": _bytes(lib.pcl_robust_weights_workspace_bytes(self.cloud.n))}
+        if kind not in ROBUST_KINDS:
+            raise ValueError("robust_reweight: kind %r (one of %s)" % (kind, sorted(ROBUST_KINDS)))
+        win = self.winners(1)
+        point_residuals_at_winners(self.cloud, pano, win, packed=True, out=r["row"])
+        _lib.check(lib.pcl_robust_weights(_ptr(r["row"]), self.cloud.n, ROBUST_KINDS[kind], float(k), _ptr(r["plane"]), _ptr(r["scale"]), _ptr(r["ws"]),
+                                          r["ws"].numel(), _stream()), "pcl_robust_weights")
+        r["on"] = True
+        return r["plane"], r["scale"]
+
+    def run_robust(self, num_iter, robust_iters, kind="trunc", k=2.5, history=False, graph=False):
+        """The robust chain: unweighted up to robust_iters[0]; at every entry of robust_iters robust_reweight(kind, k), and the same state
+        goes on weighted.  graph: every segment replays its captured graph (no history then).  The loss a segment reports is ITS loss: weighted
+        after the first entry — also the last forward's that winners() / result() hand back.  Adam's moments and the plateau scheduler carry
+        on across a switch; the scheduler's `best` then compares weighted with unweighted losses (it is not reset).  -> history or None"""
+        iters = [int(i) for i in robust_iters]
+        if not iters or any(not 0 < i < num_iter for i in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
+            raise ValueError("run_robust: robust_iters %r: strictly increasing iteration counts inside (0, %d)" % (iters, num_iter))
+        self.robust_clear()
+        hists, done = [], 0
+        for end in iters + [int(num_iter)]:
+            if done:
+                self.robust_reweight(kind, k)
+            if graph:
+                self.run_graph(end - done)
+            else:
+                hists.append(self.run(end - done, history))
+            done = end
+        return torch.cat(hists) if history and not graph else None
 
     def reset(self, trans, rot):
         """Re-initialise the optimiser state for new starting poses (same cloud / panorama / B): lets one captured
