@@ -103,8 +103,9 @@ int pcl_cloud_pack_sets(const float *xyz, const float *const *rgb_host, int nset
  *   grad loss_b = sum_i w_i m_bi grad ||c_bi - rgb_i|| / sum_i w_i m_bi        (m is piecewise constant, as in the reference's autograd)
  *   result[1] ("count") = sum_i w_i m_bi                                       (a float; the point count when w = 1)
  * Unit weights give the unweighted results bit for bit, 0/1 weights those of the same byte mask `visible`.
- * Deliberately left out: weights in the initialisation stage (pcl_trim_*, pcl_hist_trim_*), in the rooms / images / colour-set chains and
- * under the depth mask, and any built-in source of weights (density, semantics) — the caller brings them, or makes them
+ * Deliberately left out: weights in the initialisation stage (pcl_trim_*, pcl_hist_trim_*), in the rooms and rooms x images chains and
+ * under the depth mask, caller-brought weights in the images / colour-set chains (one plane per query image exists for the robust chain:
+ * pcl_gd_run_weight_sets below), and any built-in source of weights (density, semantics) — the caller brings them, or makes them
  * from the residuals of a pose with pcl_point_residuals / pcl_robust_weights below. */
 size_t pcl_cloud_weights_bytes(int64_t n);
 int pcl_cloud_pack_weights(const float *w, const int64_t *order, int64_t n, float *plane, int32_t *bad, void *stream);
@@ -121,6 +122,16 @@ int pcl_cloud_pack_weights(const float *w, const int64_t *order, int64_t n, floa
  * grid holds, H or W <= 0, a packed panorama of 2 GiB, the trim-only texel formats PCL_PANO_U8P / PCL_PANO_U8V, pose_stride < 3. */
 int pcl_point_residuals(const float *cloud, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans, const float *rot,
                         int pose_stride, int B, const int64_t *order, float *residual, void *stream);
+/* The same for nimages poses, each against ITS OWN panorama (additive to ABI 12): row i is the residual row of pose i (trans + i * pose_stride, rot
+ * + i * pose_stride) against panos_host[i] (HOST array of nimages device addresses of packed panoramas of one H, W and texel format) and, when
+ * color_sets == nimages, colour set i of a cloud of pcl_cloud_pack_sets (color_sets 0 / 1: the cloud's one set).  Row i equals what
+ * pcl_point_residuals returns for that pose, panorama and colour set alone, bit for bit: the same kernel body.  The addresses travel as kernel
+ * arguments (one launch per 64 images): nothing is copied, nothing waits for the host, capturable.  pose_stride = 16 with trans = winners,
+ * rot = winners + 13 reads pcl_gd_winner's [nimages][16] rows on the device.
+ * PCL_EINVAL, before any HIP call: what pcl_point_residuals refuses (B = nimages), a null panos_host or a null entry, color_sets < 0 or
+ * > 1 and not nimages, a cloud of color_sets sets past the addressing limit (pcl_cloud_sets_bytes answers 0). */
+int pcl_point_residuals_images(const float *cloud, int64_t n, int color_sets, const uint64_t *panos_host, int nimages, int pano_format, int H, int W,
+                               const float *trans, const float *rot, int pose_stride, const int64_t *order, float *residual, void *stream);
 /* Robust weights from ONE residual row in packed order (residual_packed[n]; M = the number of entries that are not -1):
  *   s = the lower median of those entries, the element of 0-based rank (M - 1) / 2 in ascending order — exact, by an MSB radix select over
  *       the bit patterns with integer atomics only, so it does not depend on scheduling (every NaN ranks as one value behind +inf);
@@ -137,6 +148,14 @@ int pcl_point_residuals(const float *cloud, int64_t n, const void *pano, int pan
 size_t pcl_robust_weights_workspace_bytes(int64_t n);
 int pcl_robust_weights(const float *residual_packed, int64_t n, int kind, float k, float *plane, float *scale_out, void *workspace,
                        size_t workspace_bytes, void *stream);
+/* pcl_robust_weights for nrows rows in the SAME six launches (additive to ABI 12; the row is the grid's second dimension, so the launch count
+ * does not grow with the rows): residual_packed [nrows][n] (rows n floats apart), planes [nrows][pcl_cloud_stride(n)], scale_out (nullable)
+ * [nrows][2].  Every row has its own histograms in the workspace, pcl_robust_weights_rows_workspace_bytes(n, nrows) (0 for n out of range or
+ * nrows outside 1..65535).  Plane i and scale_out[i] equal pcl_robust_weights of row i alone, bit for bit (integer atomics only; a row
+ * with M = 0 or NaN entries behaves as there).  PCL_EINVAL, before any HIP call: as pcl_robust_weights, nrows outside 1..65535. */
+size_t pcl_robust_weights_rows_workspace_bytes(int64_t n, int nrows);
+int pcl_robust_weights_rows(const float *residual_packed, int64_t n, int nrows, int kind, float k, float *planes, float *scale_out, void *workspace,
+                            size_t workspace_bytes, void *stream);
 /* The Morton order in one call, entirely on the device: bounding box, 63-bit keys, stable radix sort of (key, index);
  * order[i] = index of the point for packed slot i.  workspace: pcl_cloud_order_workspace_bytes(n). */
 size_t pcl_cloud_order_workspace_bytes(int64_t n);
@@ -248,6 +267,26 @@ int pcl_gd_run(const float *cloud, int64_t n, const void *pano, int pano_format,
 int pcl_gd_run_weighted(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, void *state, int B,
                         const float *box, const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace,
                         size_t workspace_bytes, void *timer, void *stream);
+/* One weight plane per query image (additive to ABI 12): pcl_gd_run_weighted for a chain whose B candidates are nsets images of B / nsets
+ * (image i's a contiguous range, its panorama named by pcl_gd_set_pano_groups), image i's candidates reading plane i of `weights`: nsets
+ * planes of pcl_cloud_stride(n) floats, plane i behind plane i - 1.  weights == NULL: the unweighted loss.  Either way the chain runs the
+ * SINGLE-IMAGE plan pcl_gd_plan(n, B / nsets) — its chunks, poses per block and steps per chunk — for all B candidates, with shared colours
+ * (hyper->color_sets 0 / 1) as with per-image colour sets (hyper->color_sets == nsets, pcl_cloud_pack_sets), so image i's state, pose records
+ * and loss-history columns equal those of pcl_gd_run / pcl_gd_run_weighted of that image alone with plane i, BIT FOR BIT, fused or two
+ * launches (hyper->fuse: the same rule over all blocks), eager or replayed.  A block finds its plane through `cset` of its group's first
+ * pose record: pcl_gd_init_weight_sets (pcl_gd_init for this layout) writes cset = b / (B / nsets) into both copies of the records, with
+ * shared colours too.  State, pcl_gd_result / _winner / _set_pano_groups as for pcl_gd_run; workspace pcl_gd_weight_sets_workspace_bytes;
+ * pcl_gd_plan_weight_sets is pcl_gd_plan for this chain (host-only, outputs nullable).  The robust chain over several images: run
+ * unweighted, pcl_gd_winner -> pcl_point_residuals_images -> pcl_robust_weights_rows into the planes, run on with them.
+ * PCL_EINVAL (0 from the size query), before any HIP call: nsets < 1, B % nsets != 0, hyper->color_sets > 1 that is not nsets,
+ * hyper->depth_mask, a candidate count per image that the plan's poses per block do not divide, n outside 1..PCL_MAX_POINTS, and what
+ * pcl_gd_run refuses.  PCL_EWORKSPACE: workspace_bytes too small. */
+size_t pcl_gd_weight_sets_workspace_bytes(int64_t n, int B, int nsets, const pcl_gd_hyper *hyper_host);
+int pcl_gd_plan_weight_sets(int64_t n, int B, int nsets, const pcl_gd_hyper *hyper_host, int *nchunks_host, int *poses_per_block_host, int *fused_host);
+int pcl_gd_init_weight_sets(void *state, const float *trans, const float *rot, int B, int nsets, const pcl_gd_hyper *hyper_host, void *stream);
+int pcl_gd_run_weight_sets(const float *cloud, const float *weights, int nsets, int64_t n, const void *pano, int pano_format, int H, int W, void *state,
+                           int B, const float *box, const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace,
+                           size_t workspace_bytes, void *timer, void *stream);
 int pcl_gd_result(const void *state, int B, float *result, void *stream);
 /* Teacher-forcing hook (parity tests): ONE optimiser step of every candidate from a GIVEN loss [B] and
  * gradient [B][6] = dL/d(t0, t1, t2, yaw, pitch, roll) — e.g. the reference's recorded loss_list and autograd gradients

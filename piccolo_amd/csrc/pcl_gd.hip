@@ -353,8 +353,10 @@ static int gd_chain_loop(void* state, int B, bool fused, const float* box, const
     return 0;
 }
 
-// pcl_gd_run, and with `weights` (the cloud's weight plane) pcl_gd_run_weighted: the same plan, workspace and chain, the weighted loss launch
-static int gd_run(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, void* state, int B,
+// pcl_gd_run, and with `weights` (the cloud's weight plane) pcl_gd_run_weighted: the same plan, workspace and chain, the weighted loss launch.
+// wsets >= 1 (pcl_gd_run_weight_sets): the B candidates are wsets images of B / wsets and the chain runs the single-image plan for all of
+// them — its chunks, poses per block and partials — with `weights` null (the plain or colour-set loss launch under that plan) or wsets planes.
+static int gd_run(const float* cloud, const float* weights, int wsets, int64_t n, const void* pano, int pano_format, int H, int W, void* state, int B,
                   const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history, void* workspace, size_t workspace_bytes,
                   void* timer, void* stream)
 {
@@ -363,6 +365,7 @@ static int gd_run(const float* cloud, const float* weights, int64_t n, const voi
     // pcl_gd_init wrote into its pose record; the chain runs the single-image plan of B / color_sets candidates (pcl_plan_sets)
     const int sets = gd_sets(B, hyper_host);
     if (sets < 0 || (sets > 1 && pcl_cloud_sets_bytes(n, sets) == 0)) return PCL_EINVAL;
+    const int psets = wsets > 0 ? wsets : sets;                  // the images whose single-image plan the chain runs
     hipStream_t s = (hipStream_t)stream;
     const bool depth_on = hyper_host->depth_mask != 0;
     PclDepthLook look;
@@ -374,9 +377,9 @@ static int gd_run(const float* cloud, const float* weights, int64_t n, const voi
         look.zclear_vec4 = (int64_t)(pcl_depth_zbuf_bytes(B, look.grid.Hd, look.grid.Wd) / 16);
     }
     GdRunWs w;
-    if (workspace_bytes < gd_run_layout(workspace, n, B, sets, depth_on ? &look.grid : nullptr, &w)) return PCL_EWORKSPACE;
+    if (workspace_bytes < gd_run_layout(workspace, n, B, psets, depth_on ? &look.grid : nullptr, &w)) return PCL_EWORKSPACE;
     static const int pingpong_env = PCL_KNOB(ZPINGPONG, 1);      // 0: a fill launch per iteration (A/B)
-    const int nchunks = pcl_plan_nchunks(n, B, sets);
+    const int nchunks = pcl_plan_nchunks(n, B, psets);
     // odd iterations walk every XCD's chunks backwards: the first blocks of a launch then read the chunks the previous launch
     // finished with, still in that XCD's L2 (PCL_FLIP=0 turns it off; +0.3 % at cfg 2 in two A/B alternations on one box —
     // the first round of a launch stays 6 us slower than the later ones, so cold L2 is not what makes it slow)
@@ -388,8 +391,8 @@ static int gd_run(const float* cloud, const float* weights, int64_t n, const voi
     const int xcd_bit = hyper_host->images > 1 && n * 24 <= ((int64_t)6 << 20) ? 2 : 0;
     // (the depth-masked loss pass looks a mask up that the fused prologue knows nothing about: two launches there; pcl_gd_hyper.fuse < 0:
     //  never fused — the form the parity tests compare the fused one with)
-    const bool fused = !depth_on && pcl_plan_nblocks(n, B, sets) <= gd_fuse_limit(hyper_host);
-    const int G = pcl_plan_G(n, B, sets);
+    const bool fused = !depth_on && pcl_plan_nblocks(n, B, psets) <= gd_fuse_limit(hyper_host);
+    const int G = pcl_plan_G(n, B, psets);
     return gd_chain_loop(
         state, B, fused, box, hyper_host, num_iter, loss_history, w.partials, (PclTimer*)timer, s,
         [&](int it) {
@@ -403,7 +406,7 @@ static int gd_run(const float* cloud, const float* weights, int64_t n, const voi
         },
         [&](int it, const PclPoseRec* recs, float* partials, const PclFuseArgs* fuse) {
             return pcl_launch_loss(cloud, n, pano, pano_format, H, W, recs, B, true, nullptr, partials, s, (flip_env ? (it & 1) : 0) | xcd_bit, fuse,
-                                   depth_on ? &look : nullptr, sets, weights);
+                                   depth_on ? &look : nullptr, sets, weights, wsets);
         },
         [&](int copy_in, const float* partials, float* loss_out) {
             pcl_with_G<4>(G, [&](auto g) {
@@ -419,7 +422,7 @@ extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int p
                           const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history,
                           void* workspace, size_t workspace_bytes, void* timer, void* stream)
 {
-    return gd_run(cloud, nullptr, n, pano, pano_format, H, W, state, B, box, hyper_host, num_iter, loss_history, workspace, workspace_bytes, timer, stream);
+    return gd_run(cloud, nullptr, 0, n, pano, pano_format, H, W, state, B, box, hyper_host, num_iter, loss_history, workspace, workspace_bytes, timer, stream);
 }
 
 // pcl_gd_run over a cloud with per-point weights: one more caller of the chain loop, with the weighted loss launch (fused or not by the
@@ -430,7 +433,58 @@ extern "C" int pcl_gd_run_weighted(const float* cloud, const float* weights, int
 {
     if (!weights || !hyper_host || hyper_host->depth_mask || hyper_host->color_sets > 1) return PCL_EINVAL;
     if (!pcl_weighted_plan_ok(n, B)) return PCL_EINVAL;                  // (before the state is touched)
-    return gd_run(cloud, weights, n, pano, pano_format, H, W, state, B, box, hyper_host, num_iter, loss_history, workspace, workspace_bytes, timer, stream);
+    return gd_run(cloud, weights, 0, n, pano, pano_format, H, W, state, B, box, hyper_host, num_iter, loss_history, workspace, workspace_bytes, timer, stream);
+}
+
+// ---------------------------------------------------------------- one weight plane per query image (robust chains over several images)
+
+// what the weight-set entry points refuse: a set count that does not split B, colour sets that are not the weight sets, the depth mask, a
+// cloud of that many colour sets past the addressing limit, a plan whose poses per block do not divide an image's candidates or have no
+// weighted instance
+static bool gd_weight_sets_ok(int64_t n, int B, int nsets, const pcl_gd_hyper* hyper_host)
+{
+    if (!hyper_host || n <= 0 || n > PCL_MAX_POINTS || B <= 0 || nsets < 1 || B % nsets) return false;
+    if (hyper_host->depth_mask || hyper_host->color_sets < 0 || (hyper_host->color_sets > 1 && hyper_host->color_sets != nsets)) return false;
+    if (hyper_host->color_sets > 1 && pcl_cloud_sets_bytes(n, nsets) == 0) return false;
+    const int G = pcl_plan_G(n, B, nsets);
+    return G <= 2 && (B / nsets) % G == 0;
+}
+
+extern "C" size_t pcl_gd_weight_sets_workspace_bytes(int64_t n, int B, int nsets, const pcl_gd_hyper* hyper_host)
+{
+    GdRunWs w;
+    return gd_weight_sets_ok(n, B, nsets, hyper_host) ? gd_run_layout(nullptr, n, B, nsets, nullptr, &w) : 0;
+}
+
+extern "C" int pcl_gd_plan_weight_sets(int64_t n, int B, int nsets, const pcl_gd_hyper* hyper_host, int* nchunks_host, int* poses_per_block_host,
+                                       int* fused_host)
+{
+    if (!gd_weight_sets_ok(n, B, nsets, hyper_host)) return PCL_EINVAL;
+    if (nchunks_host) *nchunks_host = pcl_plan_nchunks(n, B, nsets);
+    if (poses_per_block_host) *poses_per_block_host = pcl_plan_G(n, B, nsets);
+    if (fused_host) *fused_host = pcl_plan_nblocks(n, B, nsets) <= gd_fuse_limit(hyper_host) ? 1 : 0;
+    return 0;
+}
+
+// pcl_gd_init for a chain of nsets images: candidate b's pose records (both copies) name image b / (B / nsets) in `cset`, with shared
+// colours too — what the weight-set instances of the loss kernel select their plane by (the instances without colour sets never read it)
+extern "C" int pcl_gd_init_weight_sets(void* state, const float* trans, const float* rot, int B, int nsets, const pcl_gd_hyper* hyper_host, void* stream)
+{
+    if (!state || !trans || !rot || !hyper_host || B <= 0 || nsets < 1 || B % nsets) return PCL_EINVAL;
+    if (hyper_host->depth_mask || hyper_host->color_sets < 0 || (hyper_host->color_sets > 1 && hyper_host->color_sets != nsets)) return PCL_EINVAL;
+    hipLaunchKernelGGL(pcl_gd_init_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, gd_poses(state), gd_recs(state, B),
+                       gd_recs(state, B, 1), trans, rot, B, hyper_host->lr, B / nsets);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pcl_gd_run_weight_sets(const float* cloud, const float* weights, int nsets, int64_t n, const void* pano, int pano_format, int H, int W,
+                                      void* state, int B, const float* box, const pcl_gd_hyper* hyper_host, int num_iter, float* loss_history,
+                                      void* workspace, size_t workspace_bytes, void* timer, void* stream)
+{
+    if (!gd_weight_sets_ok(n, B, nsets, hyper_host)) return PCL_EINVAL;                  // (before the state is touched)
+    return gd_run(cloud, weights, nsets, n, pano, pano_format, H, W, state, B, box, hyper_host, num_iter, loss_history, workspace, workspace_bytes, timer,
+                  stream);
 }
 
 // ---------------------------------------------------------------- room search: several clouds in one chain

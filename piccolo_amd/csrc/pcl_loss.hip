@@ -89,6 +89,10 @@ extern "C" int pcl_debug_stamp(unsigned long long* slot, void* stream)
 // more plane, pcl_cloud_stride(n) floats in the packed point order (pcl_cloud_pack_weights), through a buffer resource of its own with the
 // lane offsets of the cloud's planes — shared by the block's G poses — and pcl_sample2 folds the weight into 1 / ||d|| and sums the kept
 // weights into the count slot.  VIS = 0, no CS, no RM.  A template parameter once more: the instances without it are unchanged.
+// WS (with WT): one weight plane per query image (pcl_gd_run_weight_sets), `nsets` planes of `stride` floats back to back.  The block reads
+// the plane its group's first pose record names in `cset` (one image's poses per group), made wave-uniform like the colour set's plane
+// and applied to the BASE of the weight resource, which still covers exactly one plane: padding and bounds as with one plane, no VGPR and no
+// descriptor per pose.  WS admits CS (per-image colours and per-image weights: the same index).
 template <int G, bool FUSED>
 __device__ __forceinline__ unsigned pcl_room_select(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* __restrict__ tb, PclLossArgs& a,
                                                     PclFuseArgs& f)
@@ -119,11 +123,12 @@ __device__ __forceinline__ unsigned pcl_room_select(const PclLossArgs& a_in, con
     return blockIdx.x - (unsigned)pcl_rfl(rm->block0);           // (block0 is a multiple of 8: the XCD of a block is unchanged)
 }
 
-template <int G, bool GRAD, int VIS, int FMT, bool FUSED, bool CS = false, bool RM = false, bool WT = false>
+template <int G, bool GRAD, int VIS, int FMT, bool FUSED, bool CS = false, bool RM = false, bool WT = false, bool WS = false>
 __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const PclFuseArgs& f_in, const PclRoomTable* rooms = nullptr,
                                               const PclDepthTable* __restrict__ dtab = nullptr, const float* wts = nullptr)
 {
-    static_assert(!WT || (VIS == 0 && !CS && !RM), "weights: the plain loss only");
+    static_assert(!WT || (VIS == 0 && !RM && (!CS || WS)), "weights: the plain loss only (weight sets: with colour sets too)");
+    static_assert(!WS || (WT && GRAD), "weight sets: the weighted gradient pass");
     PclLossArgs a_rm;
     PclFuseArgs f_rm;
     unsigned bid = blockIdx.x;
@@ -185,7 +190,11 @@ __device__ __forceinline__ void pcl_loss_body(const PclLossArgs& a_in, const Pcl
     __amdgpu_buffer_rsrc_t zb = __amdgpu_buffer_rsrc_t();
     if constexpr (VIS == 2) zb = __builtin_amdgcn_make_buffer_rsrc((void*)a.zbuf, 0, (int)((unsigned)a.B * (unsigned)(a.dgrid.last + 1) * 4u), 0x00020000);
     __amdgpu_buffer_rsrc_t wrs = __amdgpu_buffer_rsrc_t();
-    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wts, 0, (int)(a.stride * 4), 0x00020000);
+    if constexpr (WS) {
+        // this block's plane: a uniform 64-bit base, the resource covers that one plane
+        const unsigned long long wset = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(a.poses + pose0)->cset);
+        wrs = __builtin_amdgcn_make_buffer_rsrc((void*)(wts + wset * (unsigned long long)a.stride), 0, (int)(a.stride * 4), 0x00020000);
+    } else if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wts, 0, (int)(a.stride * 4), 0x00020000);
     constexpr int NPL = WT ? 7 : 6;               // values per point: the cloud's six planes (+ its weight)
 
     f2 acc[G][PCL_NACC];
@@ -449,6 +458,20 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_wt_kernel(PclLossArg
     pcl_loss_body<G, true, 0, FMT, true, false, false, true>(a, f, nullptr, nullptr, weights);
 }
 
+// one weight plane per query image (pcl_gd_run_weight_sets): the weighted gradient pass whose blocks read the plane their pose records
+// name, over shared colours or (CS) per-image colour sets.  Own names and the planes as an argument of their own once more.
+template <int G, int FMT, bool CS>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_wsets_kernel(PclLossArgs a, const float* weights)
+{
+    pcl_loss_body<G, true, 0, FMT, false, CS, false, true, true>(a, PclFuseArgs{}, nullptr, nullptr, weights);
+}
+
+template <int G, int FMT, bool CS>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_loss_fused_wsets_kernel(PclLossArgs a, PclFuseArgs f, const float* weights)
+{
+    pcl_loss_body<G, true, 0, FMT, true, CS, false, true, true>(a, f, nullptr, nullptr, weights);
+}
+
 // the depth mask inside a multi-room chain (pcl_gd_run_depth_chain): RM (+ CS) with VIS = 2, two launches per iteration only.  The depth
 // table is one more kernel argument after the room table.
 template <int G, int FMT>
@@ -672,9 +695,12 @@ int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_
 // candidates, and each pose record names its set (PclPoseRec.cset): the single-image plan (pcl_plan_sets), gradient pass only
 // `weights` (nullable): the cloud's weight plane (pcl_cloud_pack_weights) — the SAME plan, chunks, poses per block, XCD mapping and flip
 // as without it, one more plane per block; not with `visible`, `depth` or colour sets, and no G = 4 instance (experiments build)
+// `wsets` >= 1 (pcl_gd_run_weight_sets): the poses are wsets images of B / wsets candidates whose records name their image in `cset`, and
+// the launch runs the single-image plan (pcl_plan_sets over wsets) whatever it evaluates: with `weights` = wsets planes the weight-set
+// instances (colour sets admitted, color_sets == wsets), without them the plain or colour-set instances under that plan.  Gradient pass only.
 int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses,
                     int B, bool grad, const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse,
-                    const PclDepthLook* depth, int color_sets, const float* weights)
+                    const PclDepthLook* depth, int color_sets, const float* weights, int wsets)
 {
     PclLossArgs a;
     int rc = pcl_loss_args(&a, pano, pano_format, H, W, poses, B, partials, flip, color_sets);
@@ -682,8 +708,9 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
     if (n > PCL_MAX_POINTS) return PCL_EINVAL;                        // 32-bit buffer addressing: 6 planes x 4 B x n must stay below 4 GiB
     const bool sets = color_sets > 1;
     if (sets && (B % color_sets || !grad || visible || depth || pcl_cloud_sets_bytes(n, color_sets) == 0)) return PCL_EINVAL;
-    if (weights && (visible || depth || sets || !pcl_weighted_plan_ok(n, B))) return PCL_EINVAL;
-    const PclPlan p = pcl_plan_sets(n, B, color_sets);
+    if (wsets > 0 && (B % wsets || !grad || visible || depth || (sets && color_sets != wsets))) return PCL_EINVAL;
+    if (weights && (visible || depth || (wsets > 0 ? pcl_plan_G(n, B, wsets) > 2 : sets || !pcl_weighted_plan_ok(n, B)))) return PCL_EINVAL;
+    const PclPlan p = pcl_plan_sets(n, B, wsets > 0 ? wsets : color_sets);
     const int nblk = p.nchunks * p.ngroups;
     a.cloud = cloud; a.n = n; a.stride = pcl_cloud_stride(n);
     a.visible = visible;
@@ -704,6 +731,18 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
     const int vis = depth ? 2 : visible != nullptr ? 1 : 0;
     if (fuse && (!grad || vis)) return PCL_EINVAL;
     const dim3 grid(nblk), blk(PCL_BLOCK);
+    if (weights && wsets > 0) {
+        pcl_with_G_fmt<2>(p.G, pano_format, [&](auto g, auto fmt) {
+            constexpr int GG = decltype(g)::value, FMT = decltype(fmt)::value;
+            pcl_with_flag(sets, [&](auto cs) {
+                constexpr bool CSS = decltype(cs)::value;
+                if (fuse) hipLaunchKernelGGL((pcl_loss_fused_wsets_kernel<GG, FMT, CSS>), grid, blk, 0, s, a, *fuse, weights);
+                else hipLaunchKernelGGL((pcl_loss_wsets_kernel<GG, FMT, CSS>), grid, blk, 0, s, a, weights);
+            });
+        });
+        PCL_LAUNCH_CHECK();
+        return 0;
+    }
     if (weights) {
         pcl_with_G_fmt<2>(p.G, pano_format, [&](auto g, auto fmt) {
             constexpr int GG = decltype(g)::value, FMT = decltype(fmt)::value;

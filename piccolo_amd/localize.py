@@ -24,7 +24,8 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import ROBUST_KEYS, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_rooms_images, robust_schedule
+from .omniloc import (ROBUST_KEYS, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_robust, omniloc_batch_rooms_images,
+                      robust_schedule)
 from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
 
@@ -61,17 +62,35 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
 
 def _check_robust_cfg(cfg):
     """Configuration-time refusal of the robust keys where the harness would refine through an entry point that does not take them: several
-    images per launch chain and the room searches (omniloc._no_robust is what those entry points would raise, after the first cloud is read)."""
+    images per launch chain and the room searches (omniloc._no_robust is what those entry points would raise, after the first cloud is read).
+    A robust run groups its images with its own key, cfg.robust_images_per_launch (omniloc_batch_images_robust): an int >= 1 that needs
+    cfg.robust_iters and cfg.parallel."""
+    rpl = getattr(cfg, "robust_images_per_launch", None)
+    if rpl is not None:
+        if isinstance(rpl, bool) or not isinstance(rpl, int) or rpl < 1:
+            raise ValueError("cfg.robust_images_per_launch %r: an int >= 1" % (rpl,))
+        if getattr(cfg, "robust_iters", None) is None:
+            raise ValueError("cfg.robust_images_per_launch goes with cfg.robust_iters (images_per_launch groups a plain run)")
+        if not getattr(cfg, "parallel", False):
+            raise ValueError("cfg.robust_images_per_launch needs cfg.parallel (the robust chain has parallel semantics only)")
     for key in ROBUST_KEYS:
         if getattr(cfg, key, None) is None:
             continue
         if int(getattr(cfg, "images_per_launch", 1)) > 1:
-            raise ValueError("cfg.%s does not combine with images_per_launch > 1 (one image per refinement)" % key)
+            raise ValueError("cfg.%s does not combine with images_per_launch > 1 (a robust run groups its images with "
+                             "robust_images_per_launch)" % key)
         for other in ("room_search", "room_search_images"):
             if getattr(cfg, other, None):
                 raise ValueError("cfg.%s does not combine with cfg.%s" % (key, other))
         robust_schedule(cfg)                          # (its own ValueErrors, before any file is read)
         return
+
+
+def _group_size(cfg):
+    """images per group of the known-room loops: cfg.images_per_launch, or under the robust keys cfg.robust_images_per_launch (default 1)"""
+    if getattr(cfg, "robust_iters", None) is not None:
+        return int(getattr(cfg, "robust_images_per_launch", None) or 1)
+    return int(getattr(cfg, "images_per_launch", 1))
 
 
 def _make_input_args(cfg, init_dict=None):
@@ -441,6 +460,8 @@ def _localize_known_room(cfg, jobs):
             j.on_start(tr, ro)
     if len(jobs) == 1:
         return [refine_image(jobs[0].img_main, xyz, rgb, *starts[0], cfg)]
+    if getattr(cfg, "robust_iters", None) is not None:       # (a group under the robust keys: cfg.robust_images_per_launch, parallel only)
+        return omniloc_batch_images_robust([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg)
     return omniloc_batch_images([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg,
                                 batch_mode=bool(getattr(cfg, "parallel", False)))
 
@@ -493,7 +514,7 @@ def stanford_area_rooms(root, area, room_search=True):
 def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford"):
     """Stanford2D-3D-S loop (localize.py:76-297) over `root`/pano/area_*/ *.png, pcd_not_aligned/area_*/<room>.txt and
     pose/area_*/ *.json; writes `stanford_results.csv` with the reference's columns and result images under results/.
-    cfg.images_per_launch is the group size of _run_dataset (_localize_known_room).
+    cfg.images_per_launch is the group size of _run_dataset (_localize_known_room); under cfg.robust_iters it is cfg.robust_images_per_launch.
     cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms)."""
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
@@ -544,7 +565,7 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
         _stanford_report(filenames[k], log_dir, job, job.xyz, job.show_rgb, result, row)
 
     return _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
-                        int(getattr(cfg, "images_per_launch", 1)), "stanford_results.csv", STANFORD_HEADER, _stanford_row_prefix, stanford_success)
+                        _group_size(cfg), "stanford_results.csv", STANFORD_HEADER, _stanford_row_prefix, stanford_success)
 
 
 def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search):
@@ -693,5 +714,5 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
                                (job.img_main.shape[0] // 2, job.img_main.shape[1] // 2))
 
     return _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
-                        int(getattr(cfg, "images_per_launch", 1)), "omniscenes_results.csv", OMNISCENES_HEADER,
+                        _group_size(cfg), "omniscenes_results.csv", OMNISCENES_HEADER,
                         lambda f: ["{}/{}".format(*f.split("/")[-2:])], omniscenes_success)

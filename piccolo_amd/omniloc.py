@@ -22,7 +22,8 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
   * extra, optional cfg keys robust_iters / robust_kind / robust_k (default absent = reference behaviour): omniloc_batch re-weights the
     cloud's points from the residuals of its current best candidate after robust_iters iterations, on the device, and the same optimiser
     state goes on under the weighted loss (robust_schedule, csrc/pcl_residual.hip); point_residuals / robust_weights give the same per-point
-    quantities to a caller;
+    quantities to a caller; omniloc_batch_images_robust runs that chain for several query images of one cloud at once, a weight plane per
+    image;
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
     per iteration) as 4th element.
@@ -305,6 +306,8 @@ def prune_schedule(cfg, per_image):
 # l <= k s ? 1 : k s / l ("huber"); the SAME optimiser state goes on under pcl_gd_run_weighted.  Nothing waits for the host.  The returned
 # loss is the WEIGHTED loss of the last forward; Adam's moments and the plateau scheduler carry on across the switch, so the scheduler's
 # `best` then compares weighted with unweighted losses — it is not reset.  One cloud, one colour set, one image, no depth mask.
+# Several images of one cloud: omniloc_batch_images_robust — one chain, one weight plane per image, every image its own winner, residuals and
+# scale; shared colours or per-image colour sets; image i's result is its own robust omniloc_batch call's, bit for bit.
 ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
 
 
@@ -312,7 +315,8 @@ def _no_robust(cfg, who):
     """what does not run the robust chain refuses its keys, naming the first one it finds"""
     for key in ROBUST_KEYS:
         if _cfg(cfg, key, None) is not None:
-            raise ValueError("%s does not take cfg.%s (omniloc_batch and localize.refine_image's parallel branch do)" % (who, key))
+            raise ValueError("%s does not take cfg.%s (omniloc_batch, omniloc_batch_images_robust and localize.refine_image's parallel branch do)"
+                             % (who, key))
 
 
 def robust_schedule(cfg):
@@ -663,6 +667,71 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
         panos = [ops.Pano(im, fmt="f32") for im in imgs]
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     return _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, batch_mode), input_trans_list, input_rot_list)
+
+
+def _refine_robust_images(xyz, rgb, panos, trans, rot, box, cfg, robust):
+    """The robust chain over the images `panos` of one cloud: a weight-set engine (ops.GradientDescent(weight_sets=I): the single-image plan,
+    one weight plane per image), cached like _refine's engines under a key of its own, run through run_robust -> the engine."""
+    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb)
+    trans, rot = ops._dev(trans).reshape(-1, 3), ops._dev(rot).reshape(-1, 3)
+    B, I, p0 = int(trans.shape[0]), len(panos), panos[0]
+    args = _engine_args(cfg, True)
+    use_graph = _replays_graph(cfg, cloud.n * B, False)
+    if not use_graph:
+        gd = ops.GradientDescent(cloud, p0, trans, rot, box, weight_sets=I, **args)
+    else:
+        def make(cs, bs):
+            return ops.GradientDescent(cs[0], p0, trans, rot, bs[0], weight_sets=I, **args)
+        # (engines of their own: a plain omniloc_batch_images never meets an engine of the single-image plan or one whose planes are on)
+        gd, fresh = _cached_engine("gd", (xyz,), (B, I, p0.H, p0.W, p0.fmt, cloud.color_sets, False) + tuple(args.values()) + ("robust_images",),
+                                   make, [cloud], [box])
+        if not fresh:
+            gd.reset(trans, rot)
+    gd.set_pano_groups(list(panos))
+    gd.run_robust(_cfg(cfg, "num_iter", 100), robust[0], robust[1], robust[2], graph=use_graph)
+    return gd
+
+
+def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries=None):
+    """Throughput extension (not in the reference): the ROBUST omniloc_batch (cfg.robust_iters / robust_kind / robust_k, robust_schedule) for
+    several query images of the same cloud in one launch chain.  Arguments, return value and write-back as omniloc_batch_images; rgb: one
+    (N, 3) tensor or a list of one per image (per-image colour sets, grouped by color_set_groups).  Every image keeps a weight plane of its
+    own: at every entry of robust_iters the chain takes every image's current best candidate, the residuals at its pose against that image's
+    panorama (and colours), their lower median, and re-weights that image's plane — eight launches for all the images, nothing waits for the
+    host.  The chain runs the single-image plan, with shared colours too, so entry i equals omniloc_batch(imgs[i], xyz, rgb_i, ...) under the
+    same cfg bit for bit; every loss is the WEIGHTED loss of the last forward.  Parallel semantics only.  ValueError: cfg without
+    robust_iters (and robust_schedule's refusals: the depth mask, the prune keys), cfg.visualize, lists of different lengths.  One image is
+    omniloc_batch."""
+    robust = robust_schedule(cfg)
+    if robust is None:
+        raise ValueError("omniloc_batch_images_robust needs cfg.robust_iters (omniloc_batch_images runs the plain chain)")
+    if _cfg(cfg, "visualize", False):
+        raise ValueError("omniloc_batch_images_robust does not take cfg.visualize")
+    I = len(imgs)
+    if I < 1 or len(input_trans_list) != I or len(input_rot_list) != I:
+        raise ValueError("omniloc_batch_images_robust: %d images, %d / %d lists of starting poses" % (I, len(input_trans_list), len(input_rot_list)))
+    rgb = shared_rgb(rgb)
+    if isinstance(rgb, list) and len(rgb) != I:
+        raise ValueError("omniloc_batch_images_robust: %d colour sets for %d images" % (len(rgb), I))
+    if strict_reference_asserts:
+        assert cfg.num_input > 1
+    if I == 1:
+        return [omniloc_batch(imgs[0], xyz, rgb[0] if isinstance(rgb, list) else rgb, input_trans_list[0], input_rot_list[0], cfg, scalar_summaries)]
+    if isinstance(rgb, list):
+        sizes = color_set_groups(int(xyz.shape[0]), I)
+        if len(sizes) > 1:
+            out, i0 = [], 0
+            for m in sizes:
+                out += omniloc_batch_images_robust(imgs[i0:i0 + m], xyz, rgb[i0:i0 + m], input_trans_list[i0:i0 + m], input_rot_list[i0:i0 + m],
+                                                   cfg, scalar_summaries)
+                i0 += m
+            return out
+    # (the texel format every image's own omniloc_batch call takes: packed_pano's; float4 for all when the images do not agree)
+    panos = [packed_pano(im, n_points=xyz.shape[0]) for im in imgs]
+    if len({p.fmt for p in panos}) > 1:
+        panos = [ops.Pano(im, fmt="f32") for im in imgs]
+    box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
+    return _refine_groups(lambda tr, ro: _refine_robust_images(xyz, rgb, panos, tr, ro, box, cfg, robust), input_trans_list, input_rot_list)
 
 
 def depth_tau_groups(points, H, W, cfg):

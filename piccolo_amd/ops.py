@@ -456,6 +456,59 @@ def point_residuals_at_winners(cloud, pano, winners, packed=False, out=None):
     return out
 
 
+def _residual_images(cloud, panos, who):
+    """the checks of the several-image residual calls -> (the panoramas' addresses as a ctypes array, the colour-set count to pass)"""
+    I = len(panos)
+    if I < 1:
+        raise ValueError("%s: no panorama" % who)
+    if cloud.color_sets > 1 and cloud.color_sets != I:
+        raise ValueError("%s: %d colour sets for %d images" % (who, cloud.color_sets, I))
+    p0 = panos[0]
+    if p0.fmt not in (_lib.PANO_F32, _lib.PANO_U8, _lib.PANO_F16):
+        raise ValueError("%s: the trim launch's texel layouts (u8p, u8v) are not sampled here" % who)
+    for p in panos:
+        if (p.H, p.W, p.fmt) != (p0.H, p0.W, p0.fmt):
+            raise ValueError("%s: all panoramas must share size and texel format" % who)
+    return (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos]), int(cloud.color_sets)
+
+
+def point_residuals_images(cloud, panos, trans, rot, packed=False):
+    """(I, N) float GPU tensor: row i is point_residuals of pose (trans[i], rot[i]) against panos[i] — and, for a cloud of I colour sets
+    (Cloud.with_color_sets), colour set i — in ONE launch (pcl_point_residuals_images; the panorama addresses are kernel arguments).  Row i
+    equals the single call's row bit for bit.  packed: as point_residuals."""
+    lib = _lib.load()
+    arr, sets = _residual_images(cloud, panos, "point_residuals_images")
+    trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+    I = len(panos)
+    if trans.shape[0] != I or rot.shape[0] != I:
+        raise ValueError("point_residuals_images: one pose per panorama")
+    out = torch.empty(I, cloud.n, dtype=F32, device=trans.device)
+    p0 = panos[0]
+    _lib.check(lib.pcl_point_residuals_images(_ptr(cloud.data), cloud.n, sets, arr, I, p0.fmt, p0.H, p0.W, _ptr(trans), _ptr(rot), 3,
+                                              None if packed else _ptr(cloud.order), _ptr(out), _stream()), "pcl_point_residuals_images")
+    return out
+
+
+def point_residuals_images_at_winners(cloud, panos, winners, packed=False, out=None):
+    """point_residuals_images at the poses of an (I, 16) tensor as _GdEngine.winners(I) returns it, read on the device (pose stride 16): row i
+    is winner i against panos[i] (and colour set i).  out: an (I, N) tensor to write into."""
+    lib = _lib.load()
+    arr, sets = _residual_images(cloud, panos, "point_residuals_images_at_winners")
+    I = len(panos)
+    if not (torch.is_tensor(winners) and winners.is_cuda and winners.dtype == F32 and winners.is_contiguous() and winners.dim() == 2
+            and winners.shape[1] == 16 and winners.shape[0] == I):
+        raise ValueError("point_residuals_images_at_winners: winners must be a contiguous (I, 16) float32 GPU tensor, one row per panorama")
+    if out is None:
+        out = torch.empty(I, cloud.n, dtype=F32, device=winners.device)
+    elif not (out.is_cuda and out.dtype == F32 and out.is_contiguous() and out.numel() == I * cloud.n):
+        raise ValueError("point_residuals_images_at_winners: out must be a contiguous (I, N) float32 GPU tensor")
+    p0 = panos[0]
+    rot = ctypes.c_void_p(winners.data_ptr() + 13 * 4)
+    _lib.check(lib.pcl_point_residuals_images(_ptr(cloud.data), cloud.n, sets, arr, I, p0.fmt, p0.H, p0.W, _ptr(winners), rot, 16,
+                                              None if packed else _ptr(cloud.order), _ptr(out), _stream()), "pcl_point_residuals_images")
+    return out
+
+
 ROBUST_KINDS = {"trunc": _lib.ROBUST_TRUNC, "huber": _lib.ROBUST_HUBER}
 
 
@@ -489,6 +542,38 @@ def robust_plane(n, row, kind="trunc", k=2.5, plane=None, scale=None):
     ws = _bytes(nws)
     _lib.check(lib.pcl_robust_weights(_ptr(row), n, ROBUST_KINDS[kind], k, _ptr(plane), _ptr(scale), _ptr(ws), nws, _stream()), "pcl_robust_weights")
     return plane, scale
+
+
+def robust_planes(n, rows, kind="trunc", k=2.5, planes=None, scales=None, ws=None):
+    """robust_plane for the R rows of an (R, n) tensor in the same six launches (pcl_robust_weights_rows): -> (planes (R, pcl_cloud_stride(n)),
+    scales (R, 2)); plane i and scale i equal robust_plane(n, rows[i], kind, k) bit for bit.  planes / scales / ws: tensors to write into
+    (ws: a byte workspace of pcl_robust_weights_rows_workspace_bytes(n, R))."""
+    lib = _lib.load()
+    if kind not in ROBUST_KINDS:
+        raise ValueError("robust_weights: kind %r (one of %s)" % (kind, sorted(ROBUST_KINDS)))
+    k = float(k)
+    if not (k > 0.0 and k < float("inf")):
+        raise ValueError("robust_weights: k must be positive and finite, got %r" % (k,))
+    rows = _dev(rows)
+    if rows.dim() != 2 or rows.shape[1] != n or n <= 0 or rows.shape[0] < 1:
+        raise ValueError("robust_weights: rows of one residual per point, (R, N)")
+    R, stride = int(rows.shape[0]), lib.pcl_cloud_stride(n)
+    if planes is None:
+        planes = torch.empty(R, stride, dtype=F32, device=rows.device)
+    elif not (planes.is_cuda and planes.dtype == F32 and planes.is_contiguous() and planes.numel() == R * stride):
+        raise ValueError("robust_weights: planes must be a contiguous float32 GPU tensor of R x pcl_cloud_stride(n) entries")
+    if scales is None:
+        scales = torch.empty(R, 2, dtype=F32, device=rows.device)
+    elif not (scales.is_cuda and scales.dtype == F32 and scales.is_contiguous() and scales.numel() == 2 * R):
+        raise ValueError("robust_weights: scales must be a contiguous float32 GPU tensor of R x 2 entries")
+    nws = lib.pcl_robust_weights_rows_workspace_bytes(n, R)
+    if nws == 0:
+        raise ValueError("robust_weights: %d rows of %d points" % (R, n))
+    if ws is None:
+        ws = _bytes(nws)
+    _lib.check(lib.pcl_robust_weights_rows(_ptr(rows), n, R, ROBUST_KINDS[kind], k, _ptr(planes), _ptr(scales), _ptr(ws), ws.numel(), _stream()),
+               "pcl_robust_weights_rows")
+    return planes, scales
 
 
 TRIM_MAX_ROT = 1024        # pcl_trim_groups: rotations per table (include/piccolo_hip.h)
@@ -956,14 +1041,24 @@ class GradientDescent(_GdEngine):
     """On-device GD refinement of B candidates (Adam + ReduceLROnPlateau + clamp), pcl_gd_* of the C ABI."""
 
     def __init__(self, cloud, pano, trans, rot, box, lr=0.1, patience=5, factor=0.9, batch_mode=True, depth_mask=False,
-                 depth_tau=None, depth_res=None, depth_stride=None, fuse=None):
+                 depth_tau=None, depth_res=None, depth_stride=None, fuse=None, weight_sets=0):
         """fuse None: pcl_gd_plan's rule (one launch per iteration for launches whose blocks are all resident); False: always the
-        two-launch form (bit-identical; tests and measurements)."""
+        two-launch form (bit-identical; tests and measurements).
+        weight_sets I >= 1: the candidates are I images of B / I (set_pano_groups names their panoramas) and the engine is the weight-set
+        chain (pcl_gd_run_weight_sets): the single-image plan for all B candidates with shared colours too, pose records that name their
+        image, and I weight planes of its own (self.weight_planes(), unused until robust_reweight or weight_planes_on) — image i's results are
+        those of a GradientDescent over image i alone, bit for bit.  One colour set or I of them, no depth mask, a cloud without weights."""
         lib = _lib.load()
         self.cloud, self.pano = cloud, pano
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         self.B = int(trans.shape[0])
         self.box = _dev(box).reshape(6)
+        self.weight_sets = int(weight_sets)
+        if self.weight_sets:
+            if self.weight_sets < 1 or self.B % self.weight_sets or depth_mask or cloud.weights is not None or \
+                    cloud.color_sets not in (1, self.weight_sets):
+                raise ValueError("GradientDescent: weight_sets=%d needs B (%d) candidates that split into that many images, one colour set or one "
+                                 "per image, no depth mask and a cloud without weights" % (self.weight_sets, self.B))
         if cloud.weights is not None and depth_mask:
             raise ValueError("GradientDescent: per-point weights do not combine with the depth mask")
         if cloud.color_sets > 1 and self.B % cloud.color_sets:
@@ -981,17 +1076,30 @@ class GradientDescent(_GdEngine):
         self.hyper = _gd_hyper(lr, patience, factor, batch_mode, fuse, _depth_args(cloud.n, pano.H, pano.W, depth_res, depth_tau, depth_stride)
                                if depth_mask else None, cloud.color_sets)
         self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
-        self.ws_bytes = lib.pcl_gd_workspace_bytes(cloud.n, self.B, pano.H, pano.W, ctypes.byref(self.hyper))
+        if self.weight_sets:
+            self.ws_bytes = lib.pcl_gd_weight_sets_workspace_bytes(cloud.n, self.B, self.weight_sets, ctypes.byref(self.hyper))
+        else:
+            self.ws_bytes = lib.pcl_gd_workspace_bytes(cloud.n, self.B, pano.H, pano.W, ctypes.byref(self.hyper))
         if self.ws_bytes == 0:
             raise _lib.PiccoloHipError("pcl_gd_workspace_bytes: invalid arguments (depth grid %dx%d?)" % (self.hyper.depth_h, self.hyper.depth_w))
         self.ws = _bytes(self.ws_bytes)
         self.reset(trans, rot)
+
+    def _wsets(self):
+        return int(self.__dict__.get("weight_sets", 0))
 
     def run(self, num_iter, history=False, timer=None):
         if self._chain is not None:
             return self._chain.run(num_iter, history, timer)
         hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
         weights = self._run_weights()
+        if self._wsets():
+            # (planes at a stable address, like the one plane below; None: the unweighted loss under the same single-image plan)
+            _lib.check(_lib.load().pcl_gd_run_weight_sets(_ptr(self.cloud.data), _ptr(weights), self._wsets(), self.cloud.n, _ptr(self.pano.data),
+                                                          self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state), self.B, _ptr(self.box),
+                                                          ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
+                                                          timer.handle if timer else None, _stream()), "pcl_gd_run_weight_sets")
+            return hist
         if weights is not None:
             # (the plane's address is the cloud's for good — Cloud.set_weights packs in place — so a captured graph reads the current weights)
             _lib.check(_lib.load().pcl_gd_run_weighted(_ptr(self.cloud.data), _ptr(weights), self.cloud.n, _ptr(self.pano.data), self.pano.fmt,
@@ -1012,7 +1120,30 @@ class GradientDescent(_GdEngine):
 
     def _graph_key(self):
         w = self._run_weights() if self._chain is None else None
-        return (0 if w is None else w.data_ptr(),)
+        return (0 if w is None else w.data_ptr(), self._wsets())
+
+    def _robust_buffers(self):
+        """the engine's own plane(s), residual row(s), scale(s) and select workspace, at stable addresses: one per image of a weight-set engine"""
+        r = self.__dict__.get("_robust")
+        if r is None:
+            lib, dev, I = _lib.load(), self.state.device, max(1, self._wsets())
+            nws = lib.pcl_robust_weights_rows_workspace_bytes(self.cloud.n, I) if self._wsets() else lib.pcl_robust_weights_workspace_bytes(self.cloud.n)
+            r = self._robust = {"on": False, "plane": torch.empty(I * lib.pcl_cloud_stride(self.cloud.n), dtype=F32, device=dev),
+                                "row": torch.empty(I, self.cloud.n, dtype=F32, device=dev),
+                                "scale": torch.empty(2 * I if self._wsets() else 2, dtype=F32, device=dev), "ws": _bytes(nws)}
+        return r
+
+    def weight_planes(self):
+        """(I, pcl_cloud_stride(n)) view of a weight-set engine's planes, packed point order (what robust_reweight fills in place)"""
+        if not self._wsets():
+            raise ValueError("weight_planes: an engine made with weight_sets")
+        return self._robust_buffers()["plane"].view(self._wsets(), -1)
+
+    def weight_planes_on(self, on=True):
+        """run() evaluates the weighted loss with weight_planes() as they are (on) or the unweighted one (off): for planes a caller filled"""
+        if not self._wsets():
+            raise ValueError("weight_planes_on: an engine made with weight_sets")
+        self._robust_buffers()["on"] = bool(on)
 
     # ---- robust re-weighting (cfg.robust_iters of omniloc_batch): the SAME state goes on under weights made from its own winner's residuals.
     def robust_clear(self):
@@ -1025,20 +1156,17 @@ class GradientDescent(_GdEngine):
         engine's OWN plane, in place at a stable address; from here on run() evaluates the weighted loss (pcl_gd_run_weighted) with the state
         as it is.  Eight launches, nothing waits for the host.  One image, one colour set, no depth mask, a cloud without weights of its own.
         -> (plane, scale): the plane and the device (s, M) of this re-weighting."""
+        if self._wsets():
+            return self._robust_reweight_sets(kind, k)
         if self._chain is not None or self.hyper.depth_mask or self.cloud.color_sets > 1:
             raise ValueError("robust_reweight: one colour set and no depth mask")
         if self.cloud.weights is not None:
             raise ValueError("robust_reweight: the cloud carries per-point weights of its own")
         panos = {id(p): p for p in self.__dict__.get("_panos", [])}
         if len(panos) > 1:
-            raise ValueError("robust_reweight: the candidates of one image only")
+            raise ValueError("robust_reweight: the candidates of one image only (several: an engine made with weight_sets)")
         pano = next(iter(panos.values())) if panos else self.pano
-        lib, r = _lib.load(), self.__dict__.get("_robust")
-        if r is None:
-            dev = self.state.device
-            r = self._robust = {"on": False, "plane": torch.empty(lib.pcl_cloud_stride(self.cloud.n), dtype=F32, device=dev),
-                                "row": torch.empty(1, self.cloud.n, dtype=F32, device=dev), "scale": torch.empty(2, dtype=F32, device=dev),
-                                "ws": _bytes(lib.pcl_robust_weights_workspace_bytes(self.cloud.n))}
+        lib, r = _lib.load(), self._robust_buffers()
         if kind not in ROBUST_KINDS:
             raise ValueError("robust_reweight: kind %r (one of %s)" % (kind, sorted(ROBUST_KINDS)))
         win = self.winners(1)
@@ -1048,11 +1176,27 @@ class GradientDescent(_GdEngine):
         r["on"] = True
         return r["plane"], r["scale"]
 
+    def _robust_reweight_sets(self, kind, k):
+        """robust_reweight of a weight-set engine of I images: pcl_gd_winner over the I groups -> pcl_point_residuals_images at those I winners
+        (image i's panorama and colour set) -> pcl_robust_weights_rows into the I planes, in place: the same eight launches as for one image.
+        -> (planes (I, stride), scales (I, 2))"""
+        I = self._wsets()
+        panos = self.__dict__.get("_panos") or [self.pano] * I
+        if len(panos) != I:
+            raise ValueError("robust_reweight: %d panoramas named for %d images (set_pano_groups)" % (len(panos), I))
+        r = self._robust_buffers()
+        win = self.winners(I)
+        point_residuals_images_at_winners(self.cloud, panos, win, packed=True, out=r["row"])
+        planes, scales = robust_planes(self.cloud.n, r["row"], kind, k, r["plane"].view(I, -1), r["scale"].view(I, 2), r["ws"])
+        r["on"] = True
+        return planes, scales
+
     def run_robust(self, num_iter, robust_iters, kind="trunc", k=2.5, history=False, graph=False):
         """The robust chain: unweighted up to robust_iters[0]; at every entry of robust_iters robust_reweight(kind, k), and the same state
         goes on weighted.  graph: every segment replays its captured graph (no history then).  The loss a segment reports is ITS loss: weighted
         after the first entry — also the last forward's that winners() / result() hand back.  Adam's moments and the plateau scheduler carry
-        on across a switch; the scheduler's `best` then compares weighted with unweighted losses (it is not reset).  -> history or None"""
+        on across a switch; the scheduler's `best` then compares weighted with unweighted losses (it is not reset).  An engine made with
+        weight_sets=I runs it for its I image groups at once: every image its own winner, residual row, scale and plane.  -> history or None"""
         iters = [int(i) for i in robust_iters]
         if not iters or any(not 0 < i < num_iter for i in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
             raise ValueError("run_robust: robust_iters %r: strictly increasing iteration counts inside (0, %d)" % (iters, num_iter))
@@ -1075,6 +1219,10 @@ class GradientDescent(_GdEngine):
             return self._chain.reset(trans, rot)
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         assert trans.shape[0] == self.B
+        if self._wsets():
+            _lib.check(_lib.load().pcl_gd_init_weight_sets(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, self._wsets(), ctypes.byref(self.hyper),
+                                                           _stream()), "pcl_gd_init_weight_sets")
+            return
         _lib.check(_lib.load().pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
 
     def set_panos(self, panos):
@@ -1118,6 +1266,8 @@ class GradientDescent(_GdEngine):
     def _smaller(self, keep):
         """an engine over the same cloud, panorama, box and hyper-parameters with `keep` candidates per image, its state not yet written"""
         lib, groups = _lib.load(), self._groups()
+        if self._wsets():
+            raise ValueError("pruned: a weight-set engine is not pruned")
         if self.B % groups or not 1 <= keep <= self.B // groups:
             raise ValueError("pruned: keep %d of %d candidates per image" % (keep, self.B // max(groups, 1)))
         g = GradientDescent.__new__(GradientDescent)
