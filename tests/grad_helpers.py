@@ -1,0 +1,381 @@
+"""The loss kernel's gradient, point by point (not a test module; tests/test_point_gradients.py).
+
+model(): the per-point term [l, kept, grad_t, grad_ypr] of one (point, pose) pair, composed in numpy from the oracle's stand-alone
+pieces — rot_from_ypr, cloud2idx, sample_from_img, sample_from_img_backward, cloud2idx_backward — in float64 or float32.  The 8
+accumulators of the loss kernel are linear in the points, so a launch that isolates one point per pose row (a one-hot `visible` row, or a
+cloud of one point) returns exactly this term.
+
+decisive(): which pairs can be compared at all.  The gradient of a clipped, piecewise-bilinear, masked sample is discontinuous at texel
+boundaries, at the +-0.99 clip and where the exact-zero mask flips; a pair within delta of one of these is a BORDER pair and is left out.
+delta is 3 x the model's own fp32-vs-fp64 gap of the pixel coordinates, per case, taken over the points outside a cone of CONE (sine of
+the angle) around the camera's vertical axis, where the azimuth is ill-conditioned; a pair inside the cone gets 3 x its own gap if that
+is larger.  (A clipped coordinate near an integer is NOT a border: its own derivative is not used, and the other coordinate's derivative is
+continuous in it.)
+
+three_stats(): e_i = ||out_i - ref64_i||inf / max(||ref64_i||inf, s), s the case's median of ||ref64_i||inf, over the six gradient
+components; median, 99th percentile and worst.  The yardstick is the same statistic of the float32 model; the device is asserted at
+FACTOR x the yardstick, each of the three.
+
+VARIANTS: planted mistakes of the model, to show that the comparison would notice them."""
+import numpy as np
+
+LIM = 0.99
+CONE = 0.05          # sine of the half-angle of the cone around the vertical axis
+FACTOR = 3.0         # device <= FACTOR x the fp32 model's statistic (the 2-3 x margin over the reference's own fp32 gap)
+BORDER_CAP = 0.01    # at most this share of a case's (point, pose) pairs may be border pairs
+EPS = 1e-6
+
+VARIANTS = {
+    "clip_passes": "(a) the clip passes the gradient outside +-0.99",
+    "no_eps": "(b) the + 1e-6 is dropped from the denominators of d phi and d theta",
+    "edge_clamp": "(c) border taps clamp to the edge instead of reading zero",
+    "align_corners": "(d) align_corners=True scaling of the pixel derivative",
+    "pitch_roll": "(e) the pitch and roll axes are swapped in the torque",
+    "skip_black": "(f) a black tap is skipped in the derivative of a footprint that is kept",
+    "d0_nan": "(g) d = 0 yields a non-zero term (d / ||d|| unguarded: NaN)",
+}
+
+
+# ---------------------------------------------------------------------------------------------------------------- the model
+def rotations(oracle, rot, dtype):
+    """R (k,3,3) from the oracle and the three angle derivatives (k,3,3,3: yaw, pitch, roll) of R = RZ RY RX, in `dtype`"""
+    rot = np.asarray(rot).reshape(-1, 3)
+    R = np.stack([oracle.rot_from_ypr(r, dtype) for r in rot]).astype(dtype)
+    a = rot.astype(dtype)
+    cy, sy, cp, sp, cr, sr = np.cos(a[:, 0]), np.sin(a[:, 0]), np.cos(a[:, 1]), np.sin(a[:, 1]), np.cos(a[:, 2]), np.sin(a[:, 2])
+    one, zero = np.ones_like(cy), np.zeros_like(cy)
+
+    def mat(*e):
+        return np.stack(e, -1).reshape(-1, 3, 3)
+    RX, dRX = mat(one, zero, zero, zero, cr, -sr, zero, sr, cr), mat(zero, zero, zero, zero, -sr, -cr, zero, cr, -sr)
+    RY, dRY = mat(cp, zero, sp, zero, one, zero, -sp, zero, cp), mat(-sp, zero, cp, zero, zero, zero, -cp, zero, -sp)
+    RZ, dRZ = mat(cy, -sy, zero, sy, cy, zero, zero, zero, one), mat(-sy, -cy, zero, cy, -sy, zero, zero, zero, zero)
+    dR = np.stack([dRZ @ RY @ RX, RZ @ dRY @ RX, RZ @ RY @ dRX], 1)
+    return R, dR.astype(dtype)
+
+
+def _apply(M, v):
+    """rows M_i v_i for M (k,3,3), k in {1, m}, and v (m,3); the products are added left to right as the oracle's C adds them, so that
+    the float64 model lands on the oracle's own pixel coordinates bit for bit"""
+    return np.stack([(M[:, i, 0] * v[:, 0] + M[:, i, 1] * v[:, 1]) + M[:, i, 2] * v[:, 2] for i in range(3)], 1)
+
+
+def taps(img, coord, mode=None):
+    """numpy restatement of the bilinear sample and its pixel derivatives (clip, unnormalise, four taps, zero border), for the planted
+    variants only: mode "edge_clamp" reads the nearest texel for a tap outside the image, "skip_black" drops a tap difference of the
+    derivative when one of its two taps is black.  -> c, dc/dix, dc/diy (m,3 each)"""
+    H, W, _ = img.shape
+    lim = img.dtype.type(LIM)
+    g = np.clip(coord, -lim, lim)
+    ix, iy = ((g[:, 0] + 1) * W - 1) / 2, ((g[:, 1] + 1) * H - 1) / 2
+    fx0, fy0 = np.floor(ix), np.floor(iy)
+    x0, y0 = fx0.astype(np.int64), fy0.astype(np.int64)
+    wx1, wx0, wy1, wy0 = (ix - fx0)[:, None], ((fx0 + 1) - ix)[:, None], (iy - fy0)[:, None], ((fy0 + 1) - iy)[:, None]
+
+    def tap(y, x):
+        v = img[np.clip(y, 0, H - 1), np.clip(x, 0, W - 1)]
+        if mode == "edge_clamp":
+            return v
+        return np.where(((x >= 0) & (x < W) & (y >= 0) & (y < H))[:, None], v, 0).astype(img.dtype)
+    v00, v01, v10, v11 = tap(y0, x0), tap(y0, x0 + 1), tap(y0 + 1, x0), tap(y0 + 1, x0 + 1)
+    c = v00 * (wx0 * wy0) + v01 * (wx1 * wy0) + v10 * (wx0 * wy1) + v11 * (wx1 * wy1)
+
+    def diff(a, b):
+        d = a - b
+        if mode == "skip_black":
+            d = np.where(((a == 0).all(1) | (b == 0).all(1))[:, None], 0, d).astype(img.dtype)
+        return d
+    dcdx = diff(v01, v00) * wy0 + diff(v11, v10) * wy1
+    dcdy = diff(v10, v00) * wx0 + diff(v11, v01) * wx1
+    return c, dcdx, dcdy
+
+
+def _c2i_backward_no_eps(p, gc):
+    """cloud2idx_backward with the + 1e-6 kept in the numerators and dropped from the two sums of squares (variant b)"""
+    dt = p.dtype.type
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    a, b, rho = x + dt(EPS), z + dt(EPS), np.sqrt(x * x + y * y)
+    s1, s2 = x * x + y * y, rho * rho + z * z
+    dphi, dth = -gc[:, 0] / dt(np.pi), 2 * gc[:, 1] / dt(np.pi)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        drho = dth * b / s2
+        rx, ry = np.where(rho > 0, x / rho, 0), np.where(rho > 0, y / rho, 0)
+        return np.stack([dphi * (-y / s1) + drho * rx, dphi * (a / s1) + drho * ry, dth * (-rho / s2)], 1).astype(p.dtype)
+
+
+def model(oracle, xyz, rgb, img, trans, rot, dtype, variant=None):
+    """The per-pair terms for points xyz (m,3) / rgb (m,3) under poses trans / rot: one pose (3,) for all points, or one per point (m,3)
+    (a single point (1,3) is repeated for every pose).  Everything per pair is computed in `dtype`.
+    -> dict: loss (m,), kept (m,), grad (m,6) = [grad_t, grad_ypr] (NaN where masked, as the loss kernel's 0/0), ix, iy (the pixel
+    coordinates of the UNCLIPPED g, so that they say how far a pair is from the clip), gx, gy, in_x, in_y, p (camera frame), g (dl/dp),
+    gc (dl/d(gx, gy)), tau = p x g."""
+    assert variant is None or variant in VARIANTS, variant
+    dt = np.dtype(dtype).type
+    t, r = np.asarray(trans, dtype).reshape(-1, 3), np.asarray(rot).reshape(-1, 3)
+    x, c0 = np.asarray(xyz, dtype).reshape(-1, 3), np.asarray(rgb, dtype).reshape(-1, 3)
+    m = max(len(x), len(t))
+    if len(x) == 1 and m > 1:
+        x, c0 = np.repeat(x, m, 0), np.repeat(c0, m, 0)
+    im = np.asarray(img, dtype)
+    H, W, _ = im.shape
+    R, dR = rotations(oracle, r, dtype)
+    q = x - t
+    p = _apply(R, q).astype(dtype)
+    coord = oracle.cloud2idx(p, dtype)
+    gx, gy = coord[:, 0], coord[:, 1]
+    lim = dt(LIM)
+    in_x, in_y = (gx >= -lim) & (gx <= lim), (gy >= -lim) & (gy <= lim)
+    c = oracle.sample_from_img(im, coord, dtype)
+    if variant in ("edge_clamp", "skip_black"):
+        cv, dcdx, dcdy = taps(im, coord, variant)
+        if variant == "edge_clamp":
+            c = cv
+    kept = (c != 0).any(1)
+    d = c - c0
+    nrm = np.sqrt((d * d).sum(1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = d / nrm[:, None]
+    if variant != "d0_nan":
+        u = np.where((nrm > 0)[:, None], u, 0)
+    u = u.astype(dtype)
+    if variant in ("edge_clamp", "skip_black"):
+        gc = np.stack([np.where(in_x, (u * dcdx).sum(1) * (dt(W) / 2), 0), np.where(in_y, (u * dcdy).sum(1) * (dt(H) / 2), 0)], 1).astype(dtype)
+    elif variant == "clip_passes":
+        gc = oracle.sample_from_img_backward(im, np.clip(coord, -lim, lim), u, dtype, want_img=False)[0]
+    else:
+        gc = oracle.sample_from_img_backward(im, coord, u, dtype, want_img=False)[0]
+    if variant == "align_corners":
+        gc = (gc * np.array([dt(W - 1) / dt(W), dt(H - 1) / dt(H)], dtype)).astype(dtype)
+    g = _c2i_backward_no_eps(p, gc) if variant == "no_eps" else oracle.cloud2idx_backward(p, gc, dtype)
+    grad_t = -_apply(np.swapaxes(R, 1, 2), g)
+    ang = [(g * _apply(dR[:, k], q)).sum(1) for k in range(3)]
+    if variant == "pitch_roll":
+        ang = [ang[0], ang[2], ang[1]]
+    grad = np.concatenate([grad_t, np.stack(ang, 1)], 1).astype(dtype)
+    grad[~kept] = np.nan
+    loss = np.where(kept, nrm, np.nan).astype(dtype)
+    return dict(loss=loss, kept=kept, grad=grad, ix=((gx + 1) * W - 1) / 2, iy=((gy + 1) * H - 1) / 2, gx=gx, gy=gy, in_x=in_x, in_y=in_y,
+                p=p, g=g, gc=gc, tau=np.cross(p, g), H=H, W=W)
+
+
+def oracle_rows(oracle, xyz, rgb, img, t, ypr, dtype=np.float64):
+    """every point's own [loss, count, grad_t, grad_ypr] from the oracle's loss itself: B = n copies of the pose, identity mask"""
+    n = len(xyz)
+    o = oracle.sampling_loss(xyz, rgb, img, np.repeat(np.asarray(t).reshape(1, 3), n, 0), np.repeat(np.asarray(ypr).reshape(1, 3), n, 0), dtype=dtype,
+                             visible=np.eye(n, dtype=np.uint8))
+    return o["loss"], o["count"], np.concatenate([o["grad_t"], o["grad_ypr"]], 1)
+
+
+# --------------------------------------------------------------------------------------------------------- the decisive pairs
+def decisive(m64, m32):
+    """-> (ok (m,) bool: the pair is decisive, delta in px, gap in px).  See the module docstring for the rule."""
+    H, W = m64["H"], m64["W"]
+    p = m64["p"]
+    rho, r = np.hypot(p[:, 0], p[:, 1]), np.sqrt((p * p).sum(1))
+    outside = rho >= CONE * r
+    own = np.maximum(np.abs(m32["ix"].astype(np.float64) - m64["ix"]), np.abs(m32["iy"].astype(np.float64) - m64["iy"]))
+    gap = float(own[outside].max()) if outside.any() else 0.0
+    delta = 3 * gap
+    di = np.where(outside, delta, np.maximum(delta, 3 * own))
+    ix, iy = m64["ix"], m64["iy"]
+    border = (m64["in_x"] & (np.abs(ix - np.round(ix)) < di)) | (m64["in_y"] & (np.abs(iy - np.round(iy)) < di))
+    border |= (np.abs(np.abs(m64["gx"]) - LIM) * W / 2 < di) | (np.abs(np.abs(m64["gy"]) - LIM) * H / 2 < di)
+    border |= m64["kept"] != m32["kept"]
+    return ~border, delta, gap
+
+
+def point_errors(out, ref, sel):
+    """e_i over the rows `sel` of out / ref (m,6); a NaN or infinity in `out` counts as an infinite error"""
+    out, ref = np.asarray(out, np.float64)[sel], np.asarray(ref, np.float64)[sel]
+    if len(ref) == 0:
+        return np.zeros(0)
+    rn = np.abs(ref).max(1)
+    s = max(float(np.median(rn)), 1e-300)
+    with np.errstate(invalid="ignore"):
+        e = np.abs(out - ref).max(1) / np.maximum(rn, s)
+    return np.where(np.isfinite(e), e, np.inf)
+
+
+def three_stats(e):
+    """(median, 99th percentile, worst)"""
+    if len(e) == 0:
+        return 0.0, 0.0, 0.0
+    e = np.sort(e)
+    return float(e[(len(e) - 1) // 2]), float(e[int(np.ceil(0.99 * len(e))) - 1]), float(e[-1])
+
+
+def exceeds(stats, yard):
+    """does a (median, p99, worst) triple break the device bound FACTOR x yardstick somewhere?"""
+    return any(not (a <= FACTOR * y) for a, y in zip(stats, yard))
+
+
+# -------------------------------------------------------------------------------------------------- one-hot cases (section 2)
+# name: (n, H, W, panorama): "render" = the oracle's rendered panorama of the cloud (masked points exist), "levels" = random levels
+# 1..255 with a few black rectangles (a render of 2048 points on 1024 x 2048 is nearly all black)
+CASES = {
+    "G2": (2048, 64, 128, "render"),       # B = 2048: two poses per block
+    "odd": (2049, 64, 128, "render"),      # B = 2049: one pose per block, five steps, a ragged last one
+    "tiny": (513, 7, 9, "render"),         # zero-border taps in both directions
+    "tall": (1025, 300, 100, "render"),    # W = 100: the clipped column sits on the last texel's centre
+    "fine": (2048, 1024, 2048, "levels"),  # pixel coordinates with an ulp of 1.2e-4 px
+}
+SEED = 7
+N_POSES = 2
+_SCENES, _MODELS = {}, {}
+
+
+def scene(oracle, name):
+    """(xyz, rgb, img k/255, img float (not k/255), trans (2,3), rot (2,3)) of a case, computed once"""
+    if name not in _SCENES:
+        from piccolo_amd import synth
+        n, H, W, kind = CASES[name]
+        xyz, rgb = synth.box_room(n, seed=SEED)
+        t_gt, ypr_gt = synth.gt_pose(SEED)
+        if kind == "render":
+            img = oracle.make_pano_u8(synth.transform_cloud(xyz, t_gt, ypr_gt), rgb, (H, W)).astype(np.float32) / 255
+        else:
+            rng = np.random.default_rng(n)
+            lev = rng.integers(1, 256, size=(H, W, 3))
+            for _ in range(6):
+                y, x = int(rng.integers(0, H - 200)), int(rng.integers(0, W - 300))
+                lev[y:y + int(rng.integers(40, 200)), x:x + int(rng.integers(40, 300))] = 0
+            img = lev.astype(np.float32) / 255
+        trans, rot = synth.start_poses(t_gt, ypr_gt, N_POSES, seed=SEED)
+        _SCENES[name] = (xyz, rgb, img, (img * np.float32(0.9173)).astype(np.float32), trans, rot)
+    return _SCENES[name]
+
+
+def case_model(oracle, name, b, flt=False, dtype=np.float64, variant=None):
+    """the model of pose b of a case on its k/255 image (flt: on its float image), computed once"""
+    key = (name, b, flt, np.dtype(dtype).name, variant)
+    if key not in _MODELS:
+        xyz, rgb, img, imgf, trans, rot = scene(oracle, name)
+        _MODELS[key] = model(oracle, xyz, rgb, imgf if flt else img, trans[b], rot[b], dtype, variant)
+    return _MODELS[key]
+
+
+def case_rule(oracle, name, b, flt=False):
+    m64, m32 = case_model(oracle, name, b, flt), case_model(oracle, name, b, flt, np.float32)
+    return (m64, m32) + decisive(m64, m32)
+
+
+# ----------------------------------------------------------------------------------------------------- probe poses (section 3)
+ROTS = np.array([[0, 0, 0], [0.7, 0.3, -0.4], [2.5, -0.6, 0.9], [-1.9, 1.2, 2.8]], np.float32)   # identity and three general rotations
+POINT = np.array([0.4, -0.3, 0.2], np.float32)
+COLOUR = np.array([77, 153, 230], np.float32) / np.float32(255)
+
+
+def g_of(i, size):
+    """normalised coordinate of pixel coordinate i (align_corners=False)"""
+    return (2 * np.asarray(i, np.float64) + 1) / size - 1
+
+
+def aim(gx, gy, rho):
+    """camera-frame point that cloud2idx sends to (gx, gy), at distance ~rho: the inverse of the oracle's formulas, 1e-6 included"""
+    psi, th = -np.pi * gx, np.pi * (gy + 1) / 2
+    px, py = rho * np.sin(th) * np.cos(psi) - EPS, rho * np.sin(th) * np.sin(psi)
+    return np.stack([px, py, np.hypot(px, py) / np.tan(th) - EPS], -1)
+
+
+def probe_poses(x, targets):
+    """every target (gx, gy, rho) under every rotation of ROTS: t = x - R^T p, in float32 as the device gets it"""
+    from piccolo_amd import synth
+    tg = np.asarray(targets, np.float64).reshape(-1, 3)
+    p = aim(tg[:, 0], tg[:, 1], tg[:, 2])
+    trans, rot = [], []
+    for ypr in ROTS:
+        R = synth.rot_from_ypr_np(ypr)
+        trans.append(np.asarray(x, np.float64)[None, :] - p @ R)
+        rot.append(np.repeat(ypr[None, :], len(p), 0))
+    return np.concatenate(trans).astype(np.float32), np.concatenate(rot).astype(np.float32)
+
+
+def _levels(H, W, seed):
+    return np.random.default_rng(seed).integers(1, 256, size=(H, W, 3))
+
+
+def _grid(gxs, gys, rhos):
+    return [(a, b, r) for a in gxs for b in gys for r in rhos]
+
+
+def probe_class(name):
+    """-> dict(x (3,), rgb (3,), img (H,W,3) k/255, trans (B,3), rot (B,3)); B is odd for every class (the tests also run B - 1)"""
+    H, W = 64, 128
+    x, rgb, lev = POINT, np.array([0.3, 0.6, 0.9], np.float32), None
+    edge = [0.97, 0.988, 0.992, 0.9985]                      # inside, just inside, just outside, well outside the +-0.99 clip
+    if name == "seam":                                       # azimuth at the clip and on both sides of the seam
+        gxs = [s * v for s in (1, -1) for v in edge + [0.99995]]
+        tg = _grid(gxs, g_of([10.3, 31.5, 50.7], H), [1.0, 3.0])
+    elif name == "poles":                                    # elevation at the clip, towards both poles (H = 64: a zero-border row)
+        tg = _grid(g_of([20.3, 64.5, 100.7], W), [s * v for s in (1, -1) for v in edge], [1.0, 3.0])
+    elif name == "border16":                                 # 16 x 32: footprints with one axis (two taps) and both axes (three) in the zero border
+        H, W = 16, 32
+        xs, ys = g_of([-0.25, 31.25], W), g_of([-0.3, 15.3], H)
+        tg = _grid(xs, g_of([4.4, 9.6], H), [0.5, 1.0, 3.0]) + _grid(g_of([8.4, 20.6], W), ys, [0.5, 1.0, 3.0]) + _grid(xs, ys, [0.5, 1.0, 3.0])
+    elif name == "border300":                                # 300 x 100: the clipped column is pixel coordinate 99.0 / 0.0 exactly
+        H, W = 300, 100
+        tg = _grid(list(g_of([98.5, 0.5, 50.3], W)) + [0.995, -0.995], list(g_of([1.5, 150.3, 297.5], H)) + [0.995, -0.995], [1.0, 3.0])
+    elif name == "fractions":                                # 0.05 / 0.5 / 0.95 inside a texel
+        tg = [(g_of(x0 + fx, W), g_of(y0 + fy, H), r) for (y0, x0) in ((12, 40), (33, 77), (50, 101)) for fx in (0.05, 0.5, 0.95)
+              for fy in (0.05, 0.5, 0.95) for r in (1.0, 3.0)]
+    elif name == "black":                                    # footprints with one, two, three black taps (kept) and four (masked)
+        lev = _levels(H, W, 11)
+        sites = {(10, 20): [(0, 0)], (12, 100): [(1, 1)], (20, 40): [(0, 0), (1, 1)], (22, 90): [(0, 1), (1, 1)],
+                 (30, 60): [(0, 0), (0, 1), (1, 0)], (32, 30): [(0, 1), (1, 0), (1, 1)], (40, 80): [(0, 0), (0, 1), (1, 0), (1, 1)],
+                 (44, 110): [(0, 0), (0, 1), (1, 0), (1, 1)]}
+        for (y0, x0), blk in sites.items():
+            for dy, dx in blk:
+                lev[y0 + dy, x0 + dx] = 0
+        tg = [(g_of(x0 + fx, W), g_of(y0 + fy, H), r) for (y0, x0) in sites for fx, fy in ((0.3, 0.6), (0.7, 0.2), (0.5, 0.5)) for r in (1.0, 3.0)]
+    elif name == "const":                                    # a constant patch of the point's own colour: l = 0, gradient 0
+        rgb = COLOUR
+        lev = _levels(H, W, 12)
+        lev[20:28, 50:58] = [77, 153, 230]
+        tg = _grid(g_of([51.3, 53.5, 55.7], W), g_of([21.2, 24.5, 25.8], H), [1.0, 3.0])
+    elif name == "rho":                                      # distance 1e-3 .. 1e3 (the point at the origin, so that the pose carries the distance)
+        x = np.zeros(3, np.float32)
+        tg = _grid(g_of([30.3], W), g_of([20.6], H), np.logspace(-3, 3, 13)) + _grid(g_of([90.7], W), g_of([44.4], H), np.logspace(-3, 3, 13))
+    elif name == "axis":                                     # 1e-3 .. 1e-1 rad from the vertical axis, up and down
+        th = np.array([1e-3, 3e-3, 1e-2, 3e-2, 1e-1])
+        tg = _grid(g_of([10.3, 45.4, 80.6, 115.7], W), list(2 * th / np.pi - 1) + list(1 - 2 * th / np.pi), [1.0, 3.0])
+    else:
+        raise KeyError(name)
+    if lev is None:
+        lev = _levels(H, W, 10)
+    trans, rot = probe_poses(x, tg)
+    if len(trans) % 2 == 0:
+        trans, rot = trans[:-1], rot[:-1]
+    return dict(x=x, rgb=rgb, img=lev.astype(np.float32) / 255, trans=trans, rot=rot)
+
+
+PROBES = ("seam", "poles", "border16", "border300", "fractions", "black", "const", "rho", "axis")
+_PROBES = {}
+
+
+def probe(oracle, name):
+    """a probe class with its fp64 / fp32 models and its decisive pairs, computed once"""
+    if name not in _PROBES:
+        k = probe_class(name)
+        k["m64"] = model(oracle, k["x"][None, :], k["rgb"][None, :], k["img"], k["trans"], k["rot"], np.float64)
+        k["m32"] = model(oracle, k["x"][None, :], k["rgb"][None, :], k["img"], k["trans"], k["rot"], np.float32)
+        k["ok"], k["delta"], k["gap"] = decisive(k["m64"], k["m32"])
+        _PROBES[name] = k
+    return _PROBES[name]
+
+
+def angle_parts(m64, g):
+    """g (m,3) = alpha grad(phi) + beta grad(theta) at the model's camera-frame points, least squares -> the two parts' sizes
+    (|alpha| ||grad phi||, |beta| ||grad theta||): the part that belongs to a clipped coordinate must vanish"""
+    p = m64["p"].astype(np.float64)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    a, b, rho = x + EPS, z + EPS, np.hypot(x, y)
+    s1, s2 = a * a + y * y, rho * rho + b * b
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rx, ry = np.where(rho > 0, x / rho, 0), np.where(rho > 0, y / rho, 0)
+    vp = np.stack([-y / s1, a / s1, np.zeros_like(x)], 1)
+    vt = np.stack([b / s2 * rx, b / s2 * ry, -rho / s2], 1)
+    App, Apt, Att = (vp * vp).sum(1), (vp * vt).sum(1), (vt * vt).sum(1)
+    bp, bt = (vp * g).sum(1), (vt * g).sum(1)
+    det = App * Att - Apt * Apt
+    alpha, beta = (Att * bp - Apt * bt) / det, (App * bt - Apt * bp) / det
+    return np.abs(alpha) * np.sqrt(App), np.abs(beta) * np.sqrt(Att)
