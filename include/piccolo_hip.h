@@ -156,6 +156,31 @@ int pcl_robust_weights(const float *residual_packed, int64_t n, int kind, float 
 size_t pcl_robust_weights_rows_workspace_bytes(int64_t n, int nrows);
 int pcl_robust_weights_rows(const float *residual_packed, int64_t n, int nrows, int kind, float k, float *planes, float *scale_out, void *workspace,
                             size_t workspace_bytes, void *stream);
+/* Pose information matrix and covariance (additive to ABI 12; BUILD-DEFINED: the reference returns a pose and a loss and says nothing about
+ * how well the panorama constrains the pose).  One cloud with one colour set, no depth mask, as the residuals above.  For pose b =
+ * (trans + b * pose_stride, rot + b * pose_stride: yaw, pitch, roll), theta = (t0, t1, t2, yaw, pitch, roll), and per point i the loss
+ * kernel's mask bit m_i (sampled colour not exactly black), its weight w_i (1 when weights == NULL; otherwise the packed plane of
+ * pcl_cloud_pack_weights / pcl_robust_weights), its residual l_i = ||c_i - rgb_i|| and j_i = d l_i / d theta (6), the per-point term
+ * [grad_t, grad_ypr] that pcl_sampling_loss sums: j = C a, a = [g; tau], g = d l / d p in the camera frame, tau = p x g, and
+ *   grad_t = -R^T g;  yaw = tau_z;  pitch = -sin(yaw) tau_x + cos(yaw) tau_y;  roll = cy cp tau_x + sy cp tau_y - sp tau_z:
+ *   M = sum w m     S1 = sum w m l     S2 = sum w m l^2     H = sum w m j j^T (6 x 6, symmetric)     b = sum w m l j (6)
+ *   sigma^2 = S2 / M          cov = sigma^2 H^-1 (6 x 6, symmetric bit for bit; theta's units: metres for t, radians for the angles)
+ * w enters linearly (one factor per term, never squared).  info[b] is 48 floats: H row-major (36), b (6), M, S1, S2, sigma^2, status, 0.
+ * cov (nullable) is [B][36].  status: 0 fine; 1: M = 0, or a pose or a sum that is not finite — H and b are reported as summed, cov is
+ * all NaN; 2: H is not positive definite in double (a Cholesky pivot <= 6 * 2^-52 * the largest diagonal entry) — cov is all NaN.
+ * Nothing aborts.  Two launches: 256-thread blocks over chunks x poses accumulate the 30 sums in fp32 per lane and reduce them in a
+ * fixed order into one partial row per (chunk, pose) in the workspace, then one block per pose adds the rows, applies C, factorises and
+ * inverts in double and rounds every output once.  No atomics, no allocation, no synchronisation: capturable; the same inputs give the
+ * same bits.  pose_stride as for pcl_point_residuals (16 with trans = winners, rot = winners + 13 reads pcl_gd_winner's rows in place).
+ * Weights scaled by a power of two scale H, b, M, S1, S2 by it and cov by its inverse and change no other bit.
+ * pcl_pose_information_workspace_bytes(n, B): 0 for n outside 1..PCL_MAX_POINTS, B <= 0 or more blocks than a grid holds.
+ * PCL_EINVAL, before any HIP call: what pcl_point_residuals refuses (null cloud / pano / trans / rot, n, B, H, W, a 2 GiB panorama, the
+ * trim-only texel formats PCL_PANO_U8P / PCL_PANO_U8V, pose_stride < 3), a null info or workspace, workspace_bytes below the query's.
+ * Deliberately left out: colour sets, the images / rooms / depth chains, a Gauss-Newton step on H and b, and any claim that cov is
+ * calibrated on real data (sigma^2 is the mean squared colour residual of the kept points, nothing more). */
+size_t pcl_pose_information_workspace_bytes(int64_t n, int B);
+int pcl_pose_information(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans,
+                         const float *rot, int pose_stride, int B, float *info, float *cov, void *workspace, size_t workspace_bytes, void *stream);
 /* The Morton order in one call, entirely on the device: bounding box, 63-bit keys, stable radix sort of (key, index);
  * order[i] = index of the point for packed slot i.  workspace: pcl_cloud_order_workspace_bytes(n). */
 size_t pcl_cloud_order_workspace_bytes(int64_t n);

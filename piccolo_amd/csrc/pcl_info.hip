@@ -1,0 +1,302 @@
+// pcl_info.hip — how well the panorama constrains a pose: the Gauss-Newton information matrix of the sampling loss at given poses and
+// the covariance that follows from it (additive to ABI 12).  BUILD-DEFINED: the reference returns a pose and a loss and nothing else.
+//
+//   theta = (t0, t1, t2, yaw, pitch, roll); per point i: mask bit m_i (the loss kernel's), weight w_i (1 without a weight plane),
+//   residual l_i = ||c_i - rgb_i||, j_i = d l_i / d theta = C a_i with a_i = [g_i; tau_i], g = d l / d p in the camera frame,
+//   tau = p x g, and C the 6 x 6 map of pcl_chain_rule (restated in the finish kernel below).
+//   M = sum w m    S1 = sum w m l    S2 = sum w m l^2    H = sum w m j j^T    b = sum w m l j    sigma^2 = S2 / M    cov = sigma^2 H^-1
+//
+// pcl_pose_info_kernel is built as pcl_point_residuals_kernel is (pcl_residual.hip): 256 threads, a lane carries the two ADJACENT packed
+// slots 2 t, 2 t + 1 of a 512-slot step, R and t in SGPRs from pcl_rot_from_ypr, cloud / weights / texels through buffer resources,
+// pcl_project2 followed by the weighted gradient instance of pcl_sample2 with UNIT weight and fresh accumulators — so that after a step
+// acc[0], acc[1], acc[2..7] are that pair of points' own l, mask, g, tau: the very numbers the loss kernel would have added (a masked or
+// invalid point has l = 0 and a = 0 through its 1/||d|| = 0).  The weight enters ONCE, here: a lane forms w a_k (exact for w = 1) and
+// adds (w a_k) a_l, (w a_k) l, (w l) l, w l, w m with one fma each into 30 packed-fp32 accumulators, every one of them named at compile
+// time (fully unrolled loops: a runtime-indexed register array would live in scratch).  Squaring a weighted gradient would give w^2.
+// The block then adds the two packed halves, the 64 lanes of a wave (DPP) and the four waves (LDS) in a fixed order and stores one
+// partial row of 32 floats per (chunk, pose).  No atomics, no scratch; the grid is chunks x poses with the pose varying fastest.
+// pcl_pose_info_finish_kernel: one block per pose adds the chunks' rows in double in a fixed order, forms H = C A C^T and b = C v in
+// double, factorises (Cholesky), inverts, and rounds every output once to fp32.  Same inputs, same bits.
+#include <math.h>
+
+#include "pcl_host.h"
+#include "pcl_sample_device.h"
+
+#define PCL_INFO_STEP (2 * PCL_BLOCK)      // packed slots per block iteration: two per lane
+#define PCL_INFO_MIN_STEPS 2               // a chunk walks at least two steps where the cloud has them (a one-off call: fewer, longer blocks)
+#define PCL_INFO_MAX_CHUNKS 1024
+#define PCL_INFO_ROW 32                    // floats per partial row: A (21, k <= l row-major), sum w l a (6), S2, S1, M, 0, 0
+#define PCL_INFO_NSUM 30
+#define PCL_INFO_REC 48                    // floats per info record (include/piccolo_hip.h)
+
+struct PclInfoArgs {
+    const float* cloud;      // 6 planes of `stride` floats: x, y, z, -r, -g, -b
+    const float* weights;    // WT: one more plane of `stride` floats, packed order
+    int64_t n, stride;
+    const void* pano;
+    PclDims dims;
+    const float* trans;      // pose b: trans + b * pose_stride, rot + b * pose_stride (yaw, pitch, roll)
+    const float* rot;
+    int pose_stride, B;
+    float* partials;         // [nchunks][B][PCL_INFO_ROW]
+    int steps_base, steps_rem;   // the cloud's ceil(n / PCL_INFO_STEP) steps dealt out evenly: chunk c has steps_base + (c < steps_rem)
+};
+
+template <int FMT, bool WT>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_kernel(PclInfoArgs a)
+{
+    const unsigned b = blockIdx.x % (unsigned)a.B, chunk = blockIdx.x / (unsigned)a.B;
+    // the pose as six SGPR pairs (R0,R1)(R2,R3)(R4,R5)(R6,R7)(R8,t0)(t1,t2): every lane computes the same R, the first one's is read
+    const float* __restrict__ tp = a.trans + (int64_t)b * a.pose_stride;
+    const float* __restrict__ rp = a.rot + (int64_t)b * a.pose_stride;
+    float v[12];
+    pcl_rot_from_ypr(rp[0], rp[1], rp[2], v);
+    v[9] = tp[0]; v[10] = tp[1]; v[11] = tp[2];
+#pragma unroll
+    for (int k = 0; k < 12; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v[k])));
+    const PclPose6 P{(f2){v[0], v[1]}, (f2){v[2], v[3]}, (f2){v[4], v[5]}, (f2){v[6], v[7]}, (f2){v[8], v[9]}, (f2){v[10], v[11]}};
+
+    __amdgpu_buffer_rsrc_t tex = pcl_tex_rsrc(a.pano, a.dims.H, a.dims.W, pcl_texel_bytes(FMT));
+    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, (int)(a.stride * 6 * 4), 0x00020000);
+    __amdgpu_buffer_rsrc_t wrs = cld;
+    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(a.stride * 4), 0x00020000);
+    const int plane = (int)a.stride * 4;
+
+    f2 hh[21], bb[6], s2 = F2(0.f), s1 = F2(0.f), mm = F2(0.f);
+#pragma unroll
+    for (int k = 0; k < 21; k++) hh[k] = F2(0.f);
+#pragma unroll
+    for (int k = 0; k < 6; k++) bb[k] = F2(0.f);
+
+    const int first = (int)chunk * a.steps_base + min((int)chunk, a.steps_rem);
+    const int nsteps = a.steps_base + ((int)chunk < a.steps_rem ? 1 : 0);
+    const int n = (int)a.n, last_pair = (int)a.stride - 2;
+    for (int s = first; s < first + nsteps; s++) {
+        const int i0 = s * PCL_INFO_STEP + 2 * (int)threadIdx.x, i1 = i0 + 1;
+        const bool valid0 = i0 < n, valid1 = i1 < n;
+        const int j = min(i0, last_pair);                     // (the planes are padded to a multiple of 256 slots: a pair never leaves its plane)
+        f2 p[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) p[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(cld, j * 4, k * plane, 0));
+        f2 w = F2(1.f);
+        if constexpr (WT) w = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(wrs, j * 4, 0, 0));
+        PclProj<FMT> pj;
+        pcl_project2<FMT>(p[0], p[1], p[2], P, tex, a.dims, pj);
+        f2 acc[PCL_NACC];
+#pragma unroll
+        for (int k = 0; k < PCL_NACC; k++) acc[k] = F2(0.f);
+        int count = 0;
+        pcl_sample2<true, FMT, true>(pj, p[3], p[4], p[5], valid0, valid1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
+        // acc: 0 l, 1 m, 2-4 g, 5-7 tau of this pair of points alone.  One factor w (a slot past n never counts, whatever its plane holds)
+        f2 wl = acc[0], wm = acc[1], wa[6];
+        if constexpr (WT) {
+            w = (f2){valid0 ? w.x : 0.f, valid1 ? w.y : 0.f};
+            wl = w * acc[0]; wm = w * acc[1];
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) wa[k] = WT ? w * acc[2 + k] : acc[2 + k];
+        int q = 0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+#pragma unroll
+            for (int l = k; l < 6; l++, q++) hh[q] = pcl_fma2(wa[k], acc[2 + l], hh[q]);
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) bb[k] = pcl_fma2(wa[k], acc[0], bb[k]);
+        s2 = pcl_fma2(wl, acc[0], s2);
+        s1 += wl;
+        mm += wm;
+    }
+
+    // the block's sums in a fixed order: packed halves, the lanes of a wave (DPP), the four waves (LDS)
+    __shared__ float red[PCL_BLOCK / PCL_WAVE][PCL_INFO_ROW];
+    const int lane = threadIdx.x & (PCL_WAVE - 1), wave = threadIdx.x / PCL_WAVE;
+    auto put = [&](int k, f2 t) {
+        const float r = pcl_wave_sum(t.x + t.y);
+        if (lane == 0) red[wave][k] = r;
+    };
+#pragma unroll
+    for (int k = 0; k < 21; k++) put(k, hh[k]);
+#pragma unroll
+    for (int k = 0; k < 6; k++) put(21 + k, bb[k]);
+    put(27, s2); put(28, s1); put(29, mm);
+    if (lane == 0) { red[wave][30] = 0.f; red[wave][31] = 0.f; }
+    __syncthreads();
+    if (threadIdx.x < PCL_INFO_ROW) {
+        const int k = threadIdx.x;
+        a.partials[(int64_t)blockIdx.x * PCL_INFO_ROW + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+}
+
+// One 256-thread block per pose.  Thread (part, k), part = tid / 32, adds entry k of its eighth of the chunks' rows in double, lowest chunk
+// first; the eight parts are then added pairwise in a fixed order (a 1M-point cloud has ~1000 rows per pose: one lane walking them all
+// is most of the call's time at B = 1).  Thread 0 then does the 6 x 6 algebra in double on matrices kept in LDS (runtime indices there
+// cost nothing; in registers they would cost scratch) and rounds every output once.
+//   j = C a:  grad_t = -R^T g;  yaw = tau_z;  pitch = -sy tau_x + cy tau_y;  roll = cy cp tau_x + sy cp tau_y - sp tau_z
+// with R the fp32 matrix of pcl_rot_from_ypr and the sines / cosines of the fp32 angles in double, as pcl_finish_kernel takes them.
+// The factorisation runs on H scaled by an exact power of two (largest diagonal entry into [1/2, 1)), so that weights scaled by a power
+// of two scale cov by the inverse power and change no other bit.  status 2: a pivot <= 6 * 2^-52 * (the largest diagonal entry).
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_finish_kernel(const float* __restrict__ partials, int nchunks, int B,
+                                                                        const float* __restrict__ trans, const float* __restrict__ rot,
+                                                                        int pose_stride, float* __restrict__ info, float* __restrict__ cov)
+{
+    __shared__ double s[PCL_INFO_ROW];
+    __shared__ double A[6][6], C[6][6], T[6][6], Hm[6][6], L[6][6], Li[6][6], bv[6];
+    __shared__ float R[9];
+    __shared__ double parts[PCL_BLOCK / PCL_INFO_ROW][PCL_INFO_ROW];
+    const int b = blockIdx.x, k = threadIdx.x % PCL_INFO_ROW, part = threadIdx.x / PCL_INFO_ROW;
+    {
+        const int per = (nchunks + PCL_BLOCK / PCL_INFO_ROW - 1) / (PCL_BLOCK / PCL_INFO_ROW);
+        const int c0 = part * per, c1 = min(nchunks, c0 + per);
+        double t = 0.0;
+        for (int c = c0; c < c1; c++) t += (double)partials[((int64_t)c * B + b) * PCL_INFO_ROW + k];
+        parts[part][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < PCL_INFO_ROW)
+        s[k] = ((parts[0][k] + parts[1][k]) + (parts[2][k] + parts[3][k])) + ((parts[4][k] + parts[5][k]) + (parts[6][k] + parts[7][k]));
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const float* tp = trans + (int64_t)b * pose_stride;
+    const float* rp = rot + (int64_t)b * pose_stride;
+    double sy, cy, sp, cp;
+    sincos((double)rp[0], &sy, &cy);
+    sincos((double)rp[1], &sp, &cp);
+    pcl_rot_from_ypr(rp[0], rp[1], rp[2], R);
+    bool finite = true;
+    for (int i = 0; i < 3; i++) finite = finite && fabsf(tp[i]) <= 3.402823466e38f && fabsf(rp[i]) <= 3.402823466e38f;
+    for (int i = 0; i < 6; i++)
+        for (int m = 0; m < 6; m++) C[i][m] = 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int m = 0; m < 3; m++) C[i][m] = -(double)R[3 * m + i];
+    C[3][5] = 1.0;
+    C[4][3] = -sy; C[4][4] = cy;
+    C[5][3] = cy * cp; C[5][4] = sy * cp; C[5][5] = -sp;
+    int q = 0;
+    for (int i = 0; i < 6; i++)
+        for (int m = i; m < 6; m++, q++) { A[i][m] = s[q]; A[m][i] = s[q]; }
+    for (int i = 0; i < 6; i++)
+        for (int m = 0; m < 6; m++) {
+            double t = 0.0;
+            for (int r = 0; r < 6; r++) t += C[i][r] * A[r][m];
+            T[i][m] = t;
+        }
+    for (int i = 0; i < 6; i++) {
+        for (int m = i; m < 6; m++) {
+            double t = 0.0;
+            for (int r = 0; r < 6; r++) t += T[i][r] * C[m][r];
+            Hm[i][m] = t; Hm[m][i] = t;
+        }
+        double t = 0.0;
+        for (int r = 0; r < 6; r++) t += C[i][r] * s[21 + r];
+        bv[i] = t;
+    }
+    const double S2 = s[27], S1 = s[28], M = s[29], sigma2 = S2 / M;
+    for (int i = 0; i < PCL_INFO_NSUM; i++) finite = finite && fabs(s[i]) <= 1.7976931348623157e308;
+    for (int i = 0; i < 6; i++) {
+        finite = finite && fabs(bv[i]) <= 1.7976931348623157e308;
+        for (int m = 0; m < 6; m++) finite = finite && fabs(Hm[i][m]) <= 1.7976931348623157e308;
+    }
+    int status = (finite && M > 0.0) ? 0 : 1;
+    int e = 0;
+    if (status == 0) {
+        double maxd = 0.0;
+        for (int i = 0; i < 6; i++) maxd = fmax(maxd, Hm[i][i]);
+        if (!(maxd > 0.0)) status = 2;
+        else {
+            const double ms = frexp(maxd, &e), tol = 6.0 * 2.220446049250313e-16 * ms;
+            for (int i = 0; i < 6 && status == 0; i++) {
+                double d = ldexp(Hm[i][i], -e);
+                for (int r = 0; r < i; r++) d -= L[i][r] * L[i][r];
+                if (!(d > tol)) { status = 2; break; }
+                const double piv = sqrt(d);
+                L[i][i] = piv;
+                for (int m = i + 1; m < 6; m++) {
+                    double t = ldexp(Hm[m][i], -e);
+                    for (int r = 0; r < i; r++) t -= L[m][r] * L[i][r];
+                    L[m][i] = t / piv;
+                }
+            }
+        }
+    }
+    float* o = info + (int64_t)b * PCL_INFO_REC;
+    for (int i = 0; i < 6; i++)
+        for (int m = 0; m < 6; m++) o[6 * i + m] = (float)Hm[i][m];
+    for (int i = 0; i < 6; i++) o[36 + i] = (float)bv[i];
+    o[42] = (float)M; o[43] = (float)S1; o[44] = (float)S2; o[45] = (float)sigma2; o[46] = (float)status; o[47] = 0.f;
+    if (!cov) return;
+    float* cv = cov + (int64_t)b * 36;
+    if (status != 0) {
+        for (int i = 0; i < 36; i++) cv[i] = __builtin_nanf("");
+        return;
+    }
+    // Li = L^-1 (lower triangular), (H / 2^e)^-1 = Li^T Li
+    for (int m = 0; m < 6; m++) {
+        Li[m][m] = 1.0 / L[m][m];
+        for (int i = m + 1; i < 6; i++) {
+            double t = 0.0;
+            for (int r = m; r < i; r++) t += L[i][r] * Li[r][m];
+            Li[i][m] = -t / L[i][i];
+        }
+    }
+    for (int i = 0; i < 6; i++)
+        for (int m = i; m < 6; m++) {
+            double t = 0.0;
+            for (int r = m; r < 6; r++) t += Li[r][i] * Li[r][m];
+            const float c = (float)ldexp(sigma2 * t, -e);
+            cv[6 * i + m] = c; cv[6 * m + i] = c;
+        }
+}
+
+// what the size query and the call agree on: the chunks of an n-point cloud (0: n out of range)
+static int64_t info_chunks(int64_t n, int64_t* steps_out)
+{
+    if (n <= 0 || n > PCL_MAX_POINTS) return 0;
+    const int64_t steps = (n + PCL_INFO_STEP - 1) / PCL_INFO_STEP;
+    int64_t nchunks = (steps + PCL_INFO_MIN_STEPS - 1) / PCL_INFO_MIN_STEPS;
+    if (nchunks > PCL_INFO_MAX_CHUNKS) nchunks = PCL_INFO_MAX_CHUNKS;
+    if (steps_out) *steps_out = steps;
+    return nchunks;
+}
+
+extern "C" size_t pcl_pose_information_workspace_bytes(int64_t n, int B)
+{
+    const int64_t nchunks = info_chunks(n, nullptr);
+    if (nchunks == 0 || B <= 0 || nchunks * B > 0x7fffffffll) return 0;
+    PclCarve c{nullptr, 0};
+    c.take((size_t)nchunks * (size_t)B * PCL_INFO_ROW * sizeof(float));
+    return c.off;
+}
+
+extern "C" int pcl_pose_information(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W,
+                                    const float* trans, const float* rot, int pose_stride, int B, float* info, float* cov, void* workspace,
+                                    size_t workspace_bytes, void* stream)
+{
+    if (!cloud || !pano || !trans || !rot || !info || !workspace) return PCL_EINVAL;
+    if (n <= 0 || n > PCL_MAX_POINTS || B <= 0 || H <= 0 || W <= 0 || pose_stride < 3) return PCL_EINVAL;
+    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;      // (U8P / U8V: trim only)
+    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    const size_t need = pcl_pose_information_workspace_bytes(n, B);
+    if (need == 0 || workspace_bytes < need) return PCL_EINVAL;
+    int64_t steps;
+    const int64_t nchunks = info_chunks(n, &steps);
+    PclInfoArgs a;
+    a.cloud = cloud; a.weights = weights; a.n = n; a.stride = pcl_cloud_stride(n);
+    a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
+    a.trans = trans; a.rot = rot; a.pose_stride = pose_stride; a.B = B;
+    a.partials = (float*)workspace;
+    a.steps_base = (int)(steps / nchunks); a.steps_rem = (int)(steps % nchunks);
+    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    pcl_with_flag(weights != nullptr, [&](auto wt) {
+        constexpr bool WT = decltype(wt)::value;
+        if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL((pcl_pose_info_kernel<PCL_PANO_U8, WT>), grid, blk, 0, s, a);
+        else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL((pcl_pose_info_kernel<PCL_PANO_F16, WT>), grid, blk, 0, s, a);
+        else hipLaunchKernelGGL((pcl_pose_info_kernel<PCL_PANO_F32, WT>), grid, blk, 0, s, a);
+    });
+    PCL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, B, trans, rot,
+                       pose_stride, info, cov);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}

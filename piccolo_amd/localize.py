@@ -24,8 +24,8 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import (ROBUST_KEYS, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_robust, omniloc_batch_rooms_images,
-                      robust_schedule)
+from .omniloc import (ROBUST_KEYS, _no_pose_covariance, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_robust,
+                      omniloc_batch_rooms_images, robust_schedule)
 from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
 
@@ -49,7 +49,9 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
     Returns (t (3,1), R (3,3), loss) as cpu tensors.  weights (not in the reference): (N,) per-point weights of the refinement's loss.
     cfg.prune_iters / cfg.prune_keep (omniloc.prune_schedule) prune the parallel refinement's candidates on the device; the non-parallel
     branch returns every candidate and refuses the keys (ValueError), as omniloc_all does.  cfg.robust_iters / robust_kind / robust_k
-    (omniloc.robust_schedule): the parallel branch runs omniloc_batch's robust chain; the non-parallel branch refuses them as well."""
+    (omniloc.robust_schedule): the parallel branch runs omniloc_batch's robust chain; the non-parallel branch refuses them as well.
+    cfg.pose_covariance (omniloc.pose_covariance_flag): the parallel branch returns (t, R, loss, cov), cov the (6, 6) covariance of
+    (t, yaw, pitch, roll) at the returned pose; the non-parallel branch refuses the key."""
     summaries = scalar_summaries if scalar_summaries is not None else {}
     if getattr(cfg, "parallel", False):
         results = [omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)]
@@ -57,7 +59,7 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
         # the reference loops omniloc() over the starting points (localize.py:219-220); same results, one launch chain
         results = omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)
     best = min(range(len(results)), key=lambda i: float(results[i][2]))
-    return results[best][0], results[best][1], results[best][2]
+    return tuple(results[best][:4]) if getattr(cfg, "pose_covariance", None) else (results[best][0], results[best][1], results[best][2])
 
 
 def _check_robust_cfg(cfg):
@@ -156,6 +158,7 @@ def localize_synthetic(cfg, writer=None, log_dir=None):
 
     Query images are sharded over the ranks of an initialised process group (one process per GPU); every rank
     returns the full (num_images, 16) result table [t(3), R(9), loss, t_err, r_err, seconds]."""
+    _no_pose_covariance(cfg, "localize_synthetic")
     dev = ops.device()
     n = int(getattr(cfg, "num_points", 100_000))
     H, W = int(getattr(cfg, "pano_height", 256)), int(getattr(cfg, "pano_width", 512))
@@ -518,6 +521,7 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms)."""
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
+    _no_pose_covariance(cfg, "localize_stanford")
     room_search = getattr(cfg, "room_search", None)
     if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
         raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")
@@ -659,6 +663,7 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
     _run_dataset (_localize_known_room)."""
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
+    _no_pose_covariance(cfg, "localize_omniscenes")
     _seed_all()
     dev = ops.device()
     split = getattr(cfg, "split_name", "extreme")

@@ -24,6 +24,9 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
     state goes on under the weighted loss (robust_schedule, csrc/pcl_residual.hip); point_residuals / robust_weights give the same per-point
     quantities to a caller; omniloc_batch_images_robust runs that chain for several query images of one cloud at once, a weight plane per
     image;
+  * extra, optional cfg key pose_covariance (a bool, default absent = reference behaviour): omniloc_batch appends the 6 x 6 covariance of
+    (t, yaw, pitch, roll) at the pose it returns (pose_covariance_flag, csrc/pcl_info.hip); pose_information / pose_covariance give the
+    information matrix and the covariance at any poses to a caller;
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
     per iteration) as 4th element.
@@ -365,6 +368,54 @@ def robust_weights(residuals_row, kind="trunc", k=2.5):
     return ops.robust_plane(n, row, kind, k)[0][:n].clone()
 
 
+# ------------------------------------------------------------------------------------------------ pose information / covariance
+# (not in the reference; build-defined, include/piccolo_hip.h): how well the panorama constrains a pose — the Gauss-Newton information
+# matrix H = sum w m j j^T of theta = (t, yaw, pitch, roll) and cov = sigma^2 H^-1 with sigma^2 = sum w m l^2 / sum w m.  cfg
+# pose_covariance (a bool, absent by default): omniloc_batch returns [t, R, loss, cov], cov (6, 6) on the CPU, taken at the pose it returns
+# under the weights its last forward ran with (the caller's weights=, the robust chain's last plane, else none).  One cloud, one colour
+# set, one image, no depth mask; nothing is claimed about its calibration on real data.
+def pose_covariance_flag(cfg):
+    """cfg.pose_covariance as a bool (absent or None: False).  ValueError: a value that is not a bool, cfg.depth_mask next to it.  Host only."""
+    v = _cfg(cfg, "pose_covariance", None)
+    if v is None:
+        return False
+    if not isinstance(v, bool):
+        raise ValueError("cfg.pose_covariance %r: a bool" % (v,))
+    if v and bool(_cfg(cfg, "depth_mask", False)):
+        raise ValueError("cfg.pose_covariance does not combine with cfg.depth_mask")
+    return v
+
+
+def _no_pose_covariance(cfg, who):
+    """what does not return a covariance refuses the key"""
+    if _cfg(cfg, "pose_covariance", None) is not None:
+        raise ValueError("%s does not take cfg.pose_covariance (omniloc_batch and localize.refine_image's parallel branch do)" % who)
+
+
+def pose_information(img, xyz, rgb, trans, rot, weights=None):
+    """(H (B,6,6), b (B,6), stats (B,5) = M, S1, S2, sigma^2, status, cov (B,6,6)) on the GPU at the poses trans / rot ((B, 3) tensors:
+    translation; yaw, pitch, roll), over the cached packed cloud and panorama (ops.pose_information).  weights: (N,) per-point weights in
+    the order of xyz's rows."""
+    return ops.pose_information(packed_cloud(xyz, rgb, weights), packed_pano(img, n_points=xyz.shape[0]), trans, rot)
+
+
+def pose_covariance(img, xyz, rgb, trans, rot, weights=None):
+    """(cov (B,6,6), sigma^2 (B,), status (B,)) of pose_information: cov = sigma^2 H^-1 in theta's units (metres, radians), all NaN where
+    status is not 0 (1: nothing kept or something not finite; 2: H not positive definite)."""
+    _, _, stats, cov = pose_information(img, xyz, rgb, trans, rot, weights)
+    return cov, stats[:, 3], stats[:, 4]
+
+
+def _winner_covariance(gd, cloud, pano, win):
+    """cov (1,6,6) on the GPU at the pose of the (1, 16) winners row `win` of the chain `gd` (an engine or a _PrunedChain), under the weight
+    plane its last forward ran with"""
+    engine = gd.last if isinstance(gd, _PrunedChain) else gd
+    plane = engine._run_weights()
+    if plane is not None and plane is not cloud.weights:
+        cloud = cloud.weighted_view(plane)
+    return ops.pose_information_at_winners(cloud, pano, win)[3]
+
+
 class _PrunedChain:
     """What a pruned refinement hands back in place of its engine: winners() of the LAST segment's engine, and every candidate's leaf row
     written back to the caller's buffers — a dropped candidate's from the prune call that dropped it (its pose at that time), a
@@ -543,6 +594,7 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     """
     _no_prune(cfg, "omniloc")
     _no_robust(cfg, "omniloc")
+    _no_pose_covariance(cfg, "omniloc")
     vis = _cfg(cfg, "visualize", False)
     out_quantile = _cfg(cfg, "out_of_room_quantile", 0.05)
 
@@ -597,6 +649,7 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     the next forward reads) and the points never interact, so the list returned equals the K separate calls."""
     _no_prune(cfg, "omniloc_all")
     _no_robust(cfg, "omniloc_all")
+    _no_pose_covariance(cfg, "omniloc_all")
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False, weights=weights).result()
     K = res.shape[0]
@@ -613,19 +666,32 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     forward had the smallest loss (omniloc.py:271).  Keeps the reference's clamp lag (omniloc.py:260-269): the
     returned translation is the post-step, pre-clamp value (omniloc.py:272).
     cfg.robust_iters / robust_kind / robust_k (robust_schedule; not in the reference): the robust chain — the returned loss is then the
-    WEIGHTED loss of the last forward, the return shapes are unchanged.  Not with weights=, cfg.depth_mask or the prune keys (ValueError)."""
+    WEIGHTED loss of the last forward, the return shapes are unchanged.  Not with weights=, cfg.depth_mask or the prune keys (ValueError).
+    cfg.pose_covariance (a bool; not in the reference): a fourth entry, cov (6, 6) on the CPU — sigma^2 H^-1 of (t, yaw, pitch, roll) at the
+    returned pose (pose_information), under weights= or the robust chain's last plane; the first three entries are those of the run
+    without the key, bit for bit.  With the prune keys too; not with cfg.depth_mask or a list of colour sets (ValueError)."""
     if robust_schedule(cfg) is not None and weights is not None:          # (and the schedule's own refusals, before a device is touched)
         raise ValueError("cfg.robust_iters does not combine with weights= (the chain makes its own)")
+    want_cov = pose_covariance_flag(cfg)
+    if want_cov and isinstance(rgb, (list, tuple)):
+        raise ValueError("cfg.pose_covariance: one colour set only")
     if strict_reference_asserts:
         assert cfg.num_input > 1
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
-    gd = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, True, weights=weights)
+    pano = packed_pano(img, n_points=xyz.shape[0])
+    gd = _refine(xyz, rgb, [pano], input_trans, input_rot, box, cfg, True, weights=weights)
     # loss_list.argmin() of the last forward, R of the winner and the write-back of the leaves: one kernel, then the one D2H copy
     # of the whole refinement (64 bytes)
     bt, br, after = _leaf_buffers(input_trans, input_rot, gd.B)
-    out = gd.winner(1, bt, br)[0].cpu()
+    win = gd.winner(1, bt, br)
+    # (the covariance reads the winners row on the device and changes nothing the first three entries are made from)
+    cov = _winner_covariance(gd, packed_cloud(xyz, rgb, weights), pano, win) if want_cov else None
+    out = win[0].cpu()
     after()
-    return [out[0:3].reshape(3, 1).clone(), out[3:12].reshape(3, 3).clone(), out[12].clone()]
+    ret = [out[0:3].reshape(3, 1).clone(), out[3:12].reshape(3, 3).clone(), out[12].clone()]
+    if want_cov:
+        ret.append(cov[0].cpu())
+    return ret
 
 
 def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries=None, batch_mode=True):
@@ -646,6 +712,7 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     beyond the colour-set addressing limit go in further groups.  With the depth mask the colour-set chain is the depth chain
     (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image."""
     _no_robust(cfg, "omniloc_batch_images")
+    _no_pose_covariance(cfg, "omniloc_batch_images")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     I = len(imgs)
@@ -702,6 +769,7 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
     same cfg bit for bit; every loss is the WEIGHTED loss of the last forward.  Parallel semantics only.  ValueError: cfg without
     robust_iters (and robust_schedule's refusals: the depth mask, the prune keys), cfg.visualize, lists of different lengths.  One image is
     omniloc_batch."""
+    _no_pose_covariance(cfg, "omniloc_batch_images_robust")
     robust = robust_schedule(cfg)
     if robust is None:
         raise ValueError("omniloc_batch_images_robust needs cfg.robust_iters (omniloc_batch_images runs the plain chain)")
@@ -817,6 +885,7 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     (pcl_gd_run_depth_chain: every room on its own z-buffer grid, the same bits per room); rooms whose tolerances differ (depth_tau_groups)
     go in a chain per tolerance."""
     _no_robust(cfg, "omniloc_batch_rooms")
+    _no_pose_covariance(cfg, "omniloc_batch_rooms")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R = len(rooms)
@@ -891,6 +960,7 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     tolerance, and images that share the rooms' colours run omniloc_batch_images per room where that is faster (depth_shared_chain_pays:
     its plan of all the images' candidates, so equal to the single calls up to the summation order of the partial sums, as there)."""
     _no_robust(cfg, "omniloc_batch_rooms_images")
+    _no_pose_covariance(cfg, "omniloc_batch_rooms_images")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R, I = len(rooms), len(imgs)

@@ -456,6 +456,44 @@ def point_residuals_at_winners(cloud, pano, winners, packed=False, out=None):
     return out
 
 
+def _pose_information(cloud, pano, trans_ptr, rot_ptr, stride, B, dev):
+    lib = _lib.load()
+    info = torch.empty(B, 48, dtype=F32, device=dev)
+    cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
+    nws = lib.pcl_pose_information_workspace_bytes(cloud.n, B)
+    if nws == 0:
+        raise ValueError("pose_information: %d points x %d poses are out of range" % (cloud.n, B))
+    ws = _bytes(nws)
+    _lib.check(lib.pcl_pose_information(_ptr(cloud.data), _ptr(cloud.weights), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr,
+                                        stride, B, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), "pcl_pose_information")
+    return info[:, :36].reshape(B, 6, 6), info[:, 36:42], info[:, 42:47], cov
+
+
+def pose_information(cloud, pano, trans, rot):
+    """(H (B,6,6), b (B,6), stats (B,5) = M, S1, S2, sigma^2, status, cov (B,6,6)), float32 on the GPU: the Gauss-Newton information matrix
+    H = sum w m j j^T of the pose theta = (t, yaw, pitch, roll) at every pose (trans[b], rot[b]), b = sum w m l j, and cov = sigma^2 H^-1
+    with sigma^2 = S2 / M (pcl_pose_information; build-defined, include/piccolo_hip.h; metres and radians).  A weighted cloud contributes
+    its weights, one factor per term.  status 0: fine; 1: nothing kept or something not finite (cov NaN); 2: H not positive definite
+    (cov NaN).  ValueError: a cloud of colour sets, a panorama in one of the trim launch's texel layouts."""
+    _residual_cloud(cloud, pano, "pose_information")
+    trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+    B = int(trans.shape[0])
+    if rot.shape[0] != B or B == 0:
+        raise ValueError("trans and rot must have the same, positive number of rows")
+    return _pose_information(cloud, pano, _ptr(trans), _ptr(rot), 3, B, trans.device)
+
+
+def pose_information_at_winners(cloud, pano, winners):
+    """pose_information at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (pose stride 16: translation in
+    columns 0-2, yaw / pitch / roll in 13-15) — no host round trip between a chain and the covariance of its winner."""
+    _residual_cloud(cloud, pano, "pose_information_at_winners")
+    if not (torch.is_tensor(winners) and winners.is_cuda and winners.dtype == F32 and winners.is_contiguous() and winners.dim() == 2
+            and winners.shape[1] == 16 and winners.shape[0] > 0):
+        raise ValueError("pose_information_at_winners: winners must be a contiguous (G, 16) float32 GPU tensor")
+    rot = ctypes.c_void_p(winners.data_ptr() + 13 * 4)
+    return _pose_information(cloud, pano, _ptr(winners), rot, 16, int(winners.shape[0]), winners.device)
+
+
 def _residual_images(cloud, panos, who):
     """the checks of the several-image residual calls -> (the panoramas' addresses as a ctypes array, the colour-set count to pass)"""
     I = len(panos)
