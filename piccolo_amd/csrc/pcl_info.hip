@@ -6,61 +6,39 @@
 //   tau = p x g, and C the 6 x 6 map of pcl_chain_rule (restated in the finish kernel below).
 //   M = sum w m    S1 = sum w m l    S2 = sum w m l^2    H = sum w m j j^T    b = sum w m l j    sigma^2 = S2 / M    cov = sigma^2 H^-1
 //
-// pcl_pose_info_kernel is built as pcl_point_residuals_kernel is (pcl_residual.hip): 256 threads, a lane carries the two ADJACENT packed
-// slots 2 t, 2 t + 1 of a 512-slot step, R and t in SGPRs from pcl_rot_from_ypr, cloud / weights / texels through buffer resources,
-// pcl_project2 followed by the weighted gradient instance of pcl_sample2 with UNIT weight and fresh accumulators — so that after a step
-// acc[0], acc[1], acc[2..7] are that pair of points' own l, mask, g, tau: the very numbers the loss kernel would have added (a masked or
-// invalid point has l = 0 and a = 0 through its 1/||d|| = 0).  The weight enters ONCE, here: a lane forms w a_k (exact for w = 1) and
-// adds (w a_k) a_l, (w a_k) l, (w l) l, w l, w m with one fma each into 30 packed-fp32 accumulators, every one of them named at compile
-// time (fully unrolled loops: a runtime-indexed register array would live in scratch).  Squaring a weighted gradient would give w^2.
+// pcl_pose_info_kernel is the per-point pass of pcl_point_pass.h, the one pcl_point_residuals_kernel is (256 threads, a lane carries the two
+// ADJACENT packed slots 2 t, 2 t + 1 of a 512-slot step, R and t in SGPRs, cloud / weights / texels through buffer resources), with the
+// weighted gradient instance of pcl_sample2 under UNIT weight and fresh accumulators — so that after a step acc[0], acc[1], acc[2..7]
+// are that pair of points' own l, mask, g, tau: the very numbers the loss kernel would have added (a masked or invalid point has l = 0
+// and a = 0 through its 1/||d|| = 0).  What this kernel adds is what becomes of a pair.  The weight enters ONCE, here: a lane forms w a_k
+// (exact for w = 1) and adds (w a_k) a_l, (w a_k) l, (w l) l, w l, w m with one fma each into 30 packed-fp32 accumulators, every one of
+// them named at compile time (fully unrolled loops: a runtime-indexed register array would live in scratch).  Squaring a weighted
+// gradient would give w^2.
 // The block then adds the two packed halves, the 64 lanes of a wave (DPP) and the four waves (LDS) in a fixed order and stores one
 // partial row of 32 floats per (chunk, pose).  No atomics, no scratch; the grid is chunks x poses with the pose varying fastest.
 // pcl_pose_info_finish_kernel: one block per pose adds the chunks' rows in double in a fixed order, forms H = C A C^T and b = C v in
 // double, factorises (Cholesky), inverts, and rounds every output once to fp32.  Same inputs, same bits.
 #include <math.h>
 
-#include "pcl_host.h"
+#include "pcl_point_pass.h"
 #include "pcl_sample_device.h"
 
-#define PCL_INFO_STEP (2 * PCL_BLOCK)      // packed slots per block iteration: two per lane
 #define PCL_INFO_MIN_STEPS 2               // a chunk walks at least two steps where the cloud has them (a one-off call: fewer, longer blocks)
-#define PCL_INFO_MAX_CHUNKS 1024
 #define PCL_INFO_ROW 32                    // floats per partial row: A (21, k <= l row-major), sum w l a (6), S2, S1, M, 0, 0
 #define PCL_INFO_NSUM 30
 #define PCL_INFO_REC 48                    // floats per info record (include/piccolo_hip.h)
 
 struct PclInfoArgs {
-    const float* cloud;      // 6 planes of `stride` floats: x, y, z, -r, -g, -b
+    PclPassArgs pass;
     const float* weights;    // WT: one more plane of `stride` floats, packed order
-    int64_t n, stride;
-    const void* pano;
-    PclDims dims;
-    const float* trans;      // pose b: trans + b * pose_stride, rot + b * pose_stride (yaw, pitch, roll)
-    const float* rot;
-    int pose_stride, B;
     float* partials;         // [nchunks][B][PCL_INFO_ROW]
-    int steps_base, steps_rem;   // the cloud's ceil(n / PCL_INFO_STEP) steps dealt out evenly: chunk c has steps_base + (c < steps_rem)
 };
 
 template <int FMT, bool WT>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_kernel(PclInfoArgs a)
 {
-    const unsigned b = blockIdx.x % (unsigned)a.B, chunk = blockIdx.x / (unsigned)a.B;
-    // the pose as six SGPR pairs (R0,R1)(R2,R3)(R4,R5)(R6,R7)(R8,t0)(t1,t2): every lane computes the same R, the first one's is read
-    const float* __restrict__ tp = a.trans + (int64_t)b * a.pose_stride;
-    const float* __restrict__ rp = a.rot + (int64_t)b * a.pose_stride;
-    float v[12];
-    pcl_rot_from_ypr(rp[0], rp[1], rp[2], v);
-    v[9] = tp[0]; v[10] = tp[1]; v[11] = tp[2];
-#pragma unroll
-    for (int k = 0; k < 12; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v[k])));
-    const PclPose6 P{(f2){v[0], v[1]}, (f2){v[2], v[3]}, (f2){v[4], v[5]}, (f2){v[6], v[7]}, (f2){v[8], v[9]}, (f2){v[10], v[11]}};
-
-    __amdgpu_buffer_rsrc_t tex = pcl_tex_rsrc(a.pano, a.dims.H, a.dims.W, pcl_texel_bytes(FMT));
-    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, (int)(a.stride * 6 * 4), 0x00020000);
-    __amdgpu_buffer_rsrc_t wrs = cld;
-    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(a.stride * 4), 0x00020000);
-    const int plane = (int)a.stride * 4;
+    __amdgpu_buffer_rsrc_t wrs;
+    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(a.pass.stride * 4), 0x00020000);
 
     f2 hh[21], bb[6], s2 = F2(0.f), s1 = F2(0.f), mm = F2(0.f);
 #pragma unroll
@@ -68,28 +46,11 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_kernel(PclInfoArgs a)
 #pragma unroll
     for (int k = 0; k < 6; k++) bb[k] = F2(0.f);
 
-    const int first = (int)chunk * a.steps_base + min((int)chunk, a.steps_rem);
-    const int nsteps = a.steps_base + ((int)chunk < a.steps_rem ? 1 : 0);
-    const int n = (int)a.n, last_pair = (int)a.stride - 2;
-    for (int s = first; s < first + nsteps; s++) {
-        const int i0 = s * PCL_INFO_STEP + 2 * (int)threadIdx.x, i1 = i0 + 1;
-        const bool valid0 = i0 < n, valid1 = i1 < n;
-        const int j = min(i0, last_pair);                     // (the planes are padded to a multiple of 256 slots: a pair never leaves its plane)
-        f2 p[6];
-#pragma unroll
-        for (int k = 0; k < 6; k++) p[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(cld, j * 4, k * plane, 0));
-        f2 w = F2(1.f);
-        if constexpr (WT) w = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(wrs, j * 4, 0, 0));
-        PclProj<FMT> pj;
-        pcl_project2<FMT>(p[0], p[1], p[2], P, tex, a.dims, pj);
-        f2 acc[PCL_NACC];
-#pragma unroll
-        for (int k = 0; k < PCL_NACC; k++) acc[k] = F2(0.f);
-        int count = 0;
-        pcl_sample2<true, FMT, true>(pj, p[3], p[4], p[5], valid0, valid1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
+    pcl_point_pass<FMT, true, false>(a.pass, a.pass.pano, 1, 0, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool) {
         // acc: 0 l, 1 m, 2-4 g, 5-7 tau of this pair of points alone.  One factor w (a slot past n never counts, whatever its plane holds)
-        f2 wl = acc[0], wm = acc[1], wa[6];
+        f2 w = F2(1.f), wl = acc[0], wm = acc[1], wa[6];
         if constexpr (WT) {
+            w = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(wrs, j * 4, 0, 0));
             w = (f2){valid0 ? w.x : 0.f, valid1 ? w.y : 0.f};
             wl = w * acc[0]; wm = w * acc[1];
         }
@@ -106,7 +67,7 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_kernel(PclInfoArgs a)
         s2 = pcl_fma2(wl, acc[0], s2);
         s1 += wl;
         mm += wm;
-    }
+    });
 
     // the block's sums in a fixed order: packed halves, the lanes of a wave (DPP), the four waves (LDS)
     __shared__ float red[PCL_BLOCK / PCL_WAVE][PCL_INFO_ROW];
@@ -248,20 +209,9 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_finish_kernel(const f
         }
 }
 
-// what the size query and the call agree on: the chunks of an n-point cloud (0: n out of range)
-static int64_t info_chunks(int64_t n, int64_t* steps_out)
-{
-    if (n <= 0 || n > PCL_MAX_POINTS) return 0;
-    const int64_t steps = (n + PCL_INFO_STEP - 1) / PCL_INFO_STEP;
-    int64_t nchunks = (steps + PCL_INFO_MIN_STEPS - 1) / PCL_INFO_MIN_STEPS;
-    if (nchunks > PCL_INFO_MAX_CHUNKS) nchunks = PCL_INFO_MAX_CHUNKS;
-    if (steps_out) *steps_out = steps;
-    return nchunks;
-}
-
 extern "C" size_t pcl_pose_information_workspace_bytes(int64_t n, int B)
 {
-    const int64_t nchunks = info_chunks(n, nullptr);
+    const int64_t nchunks = pcl_pass_chunks(n, PCL_INFO_MIN_STEPS, nullptr);
     if (nchunks == 0 || B <= 0 || nchunks * B > 0x7fffffffll) return 0;
     PclCarve c{nullptr, 0};
     c.take((size_t)nchunks * (size_t)B * PCL_INFO_ROW * sizeof(float));
@@ -272,27 +222,19 @@ extern "C" int pcl_pose_information(const float* cloud, const float* weights, in
                                     const float* trans, const float* rot, int pose_stride, int B, float* info, float* cov, void* workspace,
                                     size_t workspace_bytes, void* stream)
 {
-    if (!cloud || !pano || !trans || !rot || !info || !workspace) return PCL_EINVAL;
-    if (n <= 0 || n > PCL_MAX_POINTS || B <= 0 || H <= 0 || W <= 0 || pose_stride < 3) return PCL_EINVAL;
-    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;      // (U8P / U8V: trim only)
-    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
-    const size_t need = pcl_pose_information_workspace_bytes(n, B);
-    if (need == 0 || workspace_bytes < need) return PCL_EINVAL;
-    int64_t steps;
-    const int64_t nchunks = info_chunks(n, &steps);
+    if (!info || !workspace) return PCL_EINVAL;
     PclInfoArgs a;
-    a.cloud = cloud; a.weights = weights; a.n = n; a.stride = pcl_cloud_stride(n);
-    a.pano = pano; a.dims = pcl_make_dims(H, W, pano_format);
-    a.trans = trans; a.rot = rot; a.pose_stride = pose_stride; a.B = B;
-    a.partials = (float*)workspace;
-    a.steps_base = (int)(steps / nchunks); a.steps_rem = (int)(steps % nchunks);
+    int64_t nchunks;
+    const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
+    if (rc) return rc;
+    if (workspace_bytes < pcl_pose_information_workspace_bytes(n, B)) return PCL_EINVAL;
+    a.weights = weights; a.partials = (float*)workspace;
     const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
     hipStream_t s = (hipStream_t)stream;
     pcl_with_flag(weights != nullptr, [&](auto wt) {
-        constexpr bool WT = decltype(wt)::value;
-        if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL((pcl_pose_info_kernel<PCL_PANO_U8, WT>), grid, blk, 0, s, a);
-        else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL((pcl_pose_info_kernel<PCL_PANO_F16, WT>), grid, blk, 0, s, a);
-        else hipLaunchKernelGGL((pcl_pose_info_kernel<PCL_PANO_F32, WT>), grid, blk, 0, s, a);
+        pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+            hipLaunchKernelGGL((pcl_pose_info_kernel<decltype(fmt)::value, decltype(wt)::value>), grid, blk, 0, s, a);
+        });
     });
     PCL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, B, trans, rot,

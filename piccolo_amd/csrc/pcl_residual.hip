@@ -8,34 +8,24 @@
 //   pcl_point_residuals_images / pcl_robust_weights_rows   the same for the I winners of a chain of I query images in the same launches: row i
 //                         against panorama i (and colour set i), plane i from row i — what pcl_gd_run_weight_sets' planes are made from
 //
-// The residual kernel is built from the device functions the loss kernel is built from (pcl_sample_device.h): pcl_rotate2, pcl_angles2,
-// the tap fetch and the three bilinear forms inside pcl_project2 / pcl_sample2 — the weighted forward-only instance of pcl_sample2 with
-// unit weights and fresh accumulators, so a lane ends with exactly the two numbers the loss kernel would have added for its two points:
-// acc[0] = n2 * rsq(n2 + 1e-37) under the mask and acc[1] = the mask bit.  Same instructions on the same inputs: the kept set is the loss
-// kernel's count, bit for bit, and the kept values differ from its sum by the summation order only.
+// Both residual kernels are the per-point pass of pcl_point_pass.h (built from the device functions the loss kernel is built from: the
+// weighted forward-only instance of pcl_sample2 with unit weights and fresh accumulators) with ONE body for what becomes of a pair: a lane
+// ends with exactly the two numbers the loss kernel would have added for its two points, acc[0] = n2 * rsq(n2 + 1e-37) under the mask and
+// acc[1] = the mask bit, and stores them.  Same instructions on the same inputs: the kept set is the loss kernel's count, bit for bit, and
+// the kept values differ from its sum by the summation order only.
 // Mapping: 256-thread blocks, a lane carries the two ADJACENT packed slots 2 t, 2 t + 1 of a 512-slot step (the loss kernel pairs slot t
 // with t + 256: the packed halves never interact, so the pairing changes no value), which makes the cloud six 8-byte loads per lane and the
-// packed-order output one 8-byte store.  The pose's R and t sit in SGPRs (computed by the block from yaw / pitch / roll with
-// pcl_rot_from_ypr, what pcl_sampling_loss's pose records hold), cloud and texels go through buffer resources.  No LDS, no atomics, no
-// scratch; no allocation and no synchronisation on the host side (capturable).  The grid is chunks x poses with the pose varying fastest
-// (blocks resident together read the same chunk); it need not be pcl_plan's, because nothing is summed.
-#include "pcl_host.h"
-#include "pcl_sample_device.h"
-
-#define PCL_RES_STEP (2 * PCL_BLOCK)       // packed slots per block iteration: two per lane
-#define PCL_RES_MAX_CHUNKS 1024
+// packed-order output one 8-byte store.  No LDS, no atomics, no scratch; no allocation and no synchronisation on the host side
+// (capturable).  The grid is chunks x poses with the pose varying fastest (blocks resident together read the same chunk); it need not be
+// pcl_plan's, because nothing is summed.  The two entry points differ in their launch shape only: any B poses on one panorama in one
+// launch, against up to PCL_RES_MAX_IMAGES panorama addresses as kernel arguments.
+// The robust weights have ONE rows path: the row is blockIdx.y, and a single row is the rows form with one row.
+#include "pcl_point_pass.h"
 
 struct PclResArgs {
-    const float* cloud;      // 6 planes of `stride` floats: x, y, z, -r, -g, -b
-    int64_t n, stride;
-    const void* pano;
-    PclDims dims;
-    const float* trans;      // pose b: trans + b * pose_stride, rot + b * pose_stride (yaw, pitch, roll)
-    const float* rot;
-    int pose_stride, B;
+    PclPassArgs pass;
     const int64_t* order;    // ORDERED: packed slot -> the caller's point index
     float* residual;         // [B][n]
-    int steps_base, steps_rem;   // the cloud's ceil(n / PCL_RES_STEP) steps dealt out evenly: chunk c has steps_base + (c < steps_rem)
 };
 
 typedef float pcl_f2u __attribute__((ext_vector_type(2), aligned(4)));      // a row of n floats starts on a 4-byte boundary only
@@ -49,155 +39,55 @@ __device__ __forceinline__ float pcl_res_value(float sum, float kept, bool pose_
     return kept != 0.f ? sum : -1.f;
 }
 
+// row b of the residuals from pose b against `pano_b` (and, with CS, colour set `set` of `sets`)
+template <int FMT, bool ORDERED, bool CS>
+__device__ __forceinline__ void pcl_res_body(const PclResArgs& a, const void* pano_b, int sets, unsigned set)
+{
+    const int64_t n = a.pass.n;
+    float* __restrict__ row = a.residual + (int64_t)(blockIdx.x % (unsigned)a.pass.B) * n;
+    pcl_point_pass<FMT, false, CS>(a.pass, pano_b, sets, set, [&](int i0, int, bool valid0, bool valid1, const f2* acc, bool pose_ok) {
+        const float r0 = pcl_res_value(acc[0].x, acc[1].x, pose_ok), r1 = pcl_res_value(acc[0].y, acc[1].y, pose_ok);
+        if constexpr (ORDERED) {
+            if (valid0) {
+                const int64_t o = a.order[i0];
+                if ((uint64_t)o < (uint64_t)n) row[o] = r0;
+            }
+            if (valid1) {
+                const int64_t o = a.order[i0 + 1];
+                if ((uint64_t)o < (uint64_t)n) row[o] = r1;
+            }
+        } else {
+            if (valid1) *reinterpret_cast<pcl_f2u*>(row + i0) = (pcl_f2u){r0, r1};
+            else if (valid0) row[i0] = r0;
+        }
+    });
+}
+
 template <int FMT, bool ORDERED>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_point_residuals_kernel(PclResArgs a)
 {
-    const unsigned b = blockIdx.x % (unsigned)a.B, chunk = blockIdx.x / (unsigned)a.B;
-    // the pose as six SGPR pairs (R0,R1)(R2,R3)(R4,R5)(R6,R7)(R8,t0)(t1,t2): every lane computes the same R, the first one's is read
-    const float* __restrict__ tp = a.trans + (int64_t)b * a.pose_stride;
-    const float* __restrict__ rp = a.rot + (int64_t)b * a.pose_stride;
-    float v[12];
-    pcl_rot_from_ypr(rp[0], rp[1], rp[2], v);
-    v[9] = tp[0]; v[10] = tp[1]; v[11] = tp[2];
-#pragma unroll
-    for (int k = 0; k < 12; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v[k])));
-    bool pose_ok = true;                                      // wave-uniform: R and t finite
-#pragma unroll
-    for (int k = 0; k < 12; k++) pose_ok = pose_ok && fabsf(v[k]) <= 3.402823466e38f;
-    const PclPose6 P{(f2){v[0], v[1]}, (f2){v[2], v[3]}, (f2){v[4], v[5]}, (f2){v[6], v[7]}, (f2){v[8], v[9]}, (f2){v[10], v[11]}};
-
-    __amdgpu_buffer_rsrc_t tex = pcl_tex_rsrc(a.pano, a.dims.H, a.dims.W, pcl_texel_bytes(FMT));
-    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, (int)(a.stride * 6 * 4), 0x00020000);
-    const int plane = (int)a.stride * 4;
-    float* __restrict__ row = a.residual + (int64_t)b * a.n;
-
-    const int first = (int)chunk * a.steps_base + min((int)chunk, a.steps_rem);
-    const int nsteps = a.steps_base + ((int)chunk < a.steps_rem ? 1 : 0);
-    const int n = (int)a.n, last_pair = (int)a.stride - 2;
-    for (int s = first; s < first + nsteps; s++) {
-        const int i0 = s * PCL_RES_STEP + 2 * (int)threadIdx.x, i1 = i0 + 1;
-        const bool valid0 = i0 < n, valid1 = i1 < n;
-        const int j = min(i0, last_pair);                     // (the planes are padded to a multiple of 256 slots: a pair never leaves its plane)
-        f2 p[6];
-#pragma unroll
-        for (int k = 0; k < 6; k++) p[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(cld, j * 4, k * plane, 0));
-        PclProj<FMT> pj;
-        pcl_project2<FMT>(p[0], p[1], p[2], P, tex, a.dims, pj);
-        f2 acc[PCL_NACC];
-#pragma unroll
-        for (int k = 0; k < PCL_NACC; k++) acc[k] = F2(0.f);
-        int count = 0;
-        pcl_sample2<false, FMT, true>(pj, p[3], p[4], p[5], valid0, valid1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
-        const float r0 = pcl_res_value(acc[0].x, acc[1].x, pose_ok), r1 = pcl_res_value(acc[0].y, acc[1].y, pose_ok);
-        if constexpr (ORDERED) {
-            if (valid0) {
-                const int64_t o = a.order[i0];
-                if ((uint64_t)o < (uint64_t)a.n) row[o] = r0;
-            }
-            if (valid1) {
-                const int64_t o = a.order[i1];
-                if ((uint64_t)o < (uint64_t)a.n) row[o] = r1;
-            }
-        } else {
-            if (valid1) *reinterpret_cast<pcl_f2u*>(row + i0) = (pcl_f2u){r0, r1};
-            else if (valid0) row[i0] = r0;
-        }
-    }
-}
-
-// pcl_point_residuals_images: the kernel above, statement for statement, where pose b samples its own panorama `pano_b` (a uniform address
-// out of the kernel arguments) and, with CS, colour set `set` of a cloud of `sets` colour sets — a scalar plane offset on the one cloud
-// resource, as in the loss kernel.  A body of its own and not a shared one: wrapped into a shared inline function the kernel above no longer
-// compiles to the instruction stream it had (another register assignment), and it is pinned to that.
-template <int FMT, bool ORDERED, bool CS>
-__device__ __forceinline__ void pcl_res_images_body(const PclResArgs& a, const void* pano_b, int sets, unsigned set)
-{
-    const unsigned b = blockIdx.x % (unsigned)a.B, chunk = blockIdx.x / (unsigned)a.B;
-    // the pose as six SGPR pairs (R0,R1)(R2,R3)(R4,R5)(R6,R7)(R8,t0)(t1,t2): every lane computes the same R, the first one's is read
-    const float* __restrict__ tp = a.trans + (int64_t)b * a.pose_stride;
-    const float* __restrict__ rp = a.rot + (int64_t)b * a.pose_stride;
-    float v[12];
-    pcl_rot_from_ypr(rp[0], rp[1], rp[2], v);
-    v[9] = tp[0]; v[10] = tp[1]; v[11] = tp[2];
-#pragma unroll
-    for (int k = 0; k < 12; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v[k])));
-    bool pose_ok = true;                                      // wave-uniform: R and t finite
-#pragma unroll
-    for (int k = 0; k < 12; k++) pose_ok = pose_ok && fabsf(v[k]) <= 3.402823466e38f;
-    const PclPose6 P{(f2){v[0], v[1]}, (f2){v[2], v[3]}, (f2){v[4], v[5]}, (f2){v[6], v[7]}, (f2){v[8], v[9]}, (f2){v[10], v[11]}};
-
-    __amdgpu_buffer_rsrc_t tex = pcl_tex_rsrc(pano_b, a.dims.H, a.dims.W, pcl_texel_bytes(FMT));
-    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, CS ? (int)(a.stride * (3 + 3 * sets) * 4) : (int)(a.stride * 6 * 4),
-                                                                   0x00020000);
-    const int plane = (int)a.stride * 4;
-    const int cplane = CS ? (int)(3u + 3u * set) * plane : 3 * plane;      // byte offset of the first colour plane this pose reads (uniform)
-    float* __restrict__ row = a.residual + (int64_t)b * a.n;
-
-    const int first = (int)chunk * a.steps_base + min((int)chunk, a.steps_rem);
-    const int nsteps = a.steps_base + ((int)chunk < a.steps_rem ? 1 : 0);
-    const int n = (int)a.n, last_pair = (int)a.stride - 2;
-    for (int s = first; s < first + nsteps; s++) {
-        const int i0 = s * PCL_RES_STEP + 2 * (int)threadIdx.x, i1 = i0 + 1;
-        const bool valid0 = i0 < n, valid1 = i1 < n;
-        const int j = min(i0, last_pair);                     // (the planes are padded to a multiple of 256 slots: a pair never leaves its plane)
-        f2 p[6];
-#pragma unroll
-        for (int k = 0; k < 6; k++)
-            p[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(cld, j * 4, (CS && k >= 3) ? cplane + (k - 3) * plane : k * plane, 0));
-        PclProj<FMT> pj;
-        pcl_project2<FMT>(p[0], p[1], p[2], P, tex, a.dims, pj);
-        f2 acc[PCL_NACC];
-#pragma unroll
-        for (int k = 0; k < PCL_NACC; k++) acc[k] = F2(0.f);
-        int count = 0;
-        pcl_sample2<false, FMT, true>(pj, p[3], p[4], p[5], valid0, valid1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
-        const float r0 = pcl_res_value(acc[0].x, acc[1].x, pose_ok), r1 = pcl_res_value(acc[0].y, acc[1].y, pose_ok);
-        if constexpr (ORDERED) {
-            if (valid0) {
-                const int64_t o = a.order[i0];
-                if ((uint64_t)o < (uint64_t)a.n) row[o] = r0;
-            }
-            if (valid1) {
-                const int64_t o = a.order[i1];
-                if ((uint64_t)o < (uint64_t)a.n) row[o] = r1;
-            }
-        } else {
-            if (valid1) *reinterpret_cast<pcl_f2u*>(row + i0) = (pcl_f2u){r0, r1};
-            else if (valid0) row[i0] = r0;
-        }
-    }
+    pcl_res_body<FMT, ORDERED, false>(a, a.pass.pano, 1, 0);
 }
 
 // Row i = pose i against panorama i (and colour set i): the panorama addresses travel as kernel arguments, up to PCL_RES_MAX_IMAGES per
-// launch; `img0` is the first image of this launch (the colour set counts from the call's first image, a.B is this launch's pose count)
+// launch; `img0` is the first image of this launch (the colour set counts from the call's first image, a.pass.B is this launch's pose count)
 #define PCL_RES_MAX_IMAGES 64
 struct PclResPanos { unsigned long long p[PCL_RES_MAX_IMAGES]; };
 
 template <int FMT, bool ORDERED, bool CS>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_point_residuals_images_kernel(PclResArgs a, PclResPanos panos, int sets, int img0)
 {
-    const unsigned b = blockIdx.x % (unsigned)a.B;
-    pcl_res_images_body<FMT, ORDERED, CS>(a, (const void*)panos.p[b], sets, b + (unsigned)img0);           // (b: from the block index, uniform)
+    const unsigned b = blockIdx.x % (unsigned)a.pass.B;
+    pcl_res_body<FMT, ORDERED, CS>(a, (const void*)panos.p[b], sets, b + (unsigned)img0);                  // (b: from the block index, uniform)
 }
 
 // what both entry points check and fill; the grid is nchunks x B
 static int res_args(PclResArgs* a, const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans, const float* rot,
                     int pose_stride, int B, const int64_t* order, float* residual, int64_t* nchunks_out)
 {
-    if (!cloud || !pano || !trans || !rot || !residual) return PCL_EINVAL;
-    if (n <= 0 || n > PCL_MAX_POINTS || B <= 0 || H <= 0 || W <= 0 || pose_stride < 3) return PCL_EINVAL;
-    if (pano_format != PCL_PANO_F32 && pano_format != PCL_PANO_U8 && pano_format != PCL_PANO_F16) return PCL_EINVAL;      // (U8P / U8V: trim only)
-    if ((int64_t)(H + 2) * (W + 2) * pcl_texel_bytes(pano_format) >= ((int64_t)1 << 31)) return PCL_EINVAL;
-    const int64_t steps = (n + PCL_RES_STEP - 1) / PCL_RES_STEP;
-    const int64_t nchunks = steps < PCL_RES_MAX_CHUNKS ? steps : PCL_RES_MAX_CHUNKS;
-    if (nchunks * B > 0x7fffffffll) return PCL_EINVAL;
-    a->cloud = cloud; a->n = n; a->stride = pcl_cloud_stride(n);
-    a->pano = pano; a->dims = pcl_make_dims(H, W, pano_format);
-    a->trans = trans; a->rot = rot; a->pose_stride = pose_stride; a->B = B;
+    if (!residual) return PCL_EINVAL;
     a->order = order; a->residual = residual;
-    a->steps_base = (int)(steps / nchunks); a->steps_rem = (int)(steps % nchunks);
-    *nchunks_out = nchunks;
-    return 0;
+    return pcl_pass_args(&a->pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, 1, nchunks_out);
 }
 
 extern "C" int pcl_point_residuals(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans, const float* rot,
@@ -210,10 +100,9 @@ extern "C" int pcl_point_residuals(const float* cloud, int64_t n, const void* pa
     const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
     hipStream_t s = (hipStream_t)stream;
     pcl_with_flag(order != nullptr, [&](auto ord) {
-        constexpr bool ORD = decltype(ord)::value;
-        if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL((pcl_point_residuals_kernel<PCL_PANO_U8, ORD>), grid, blk, 0, s, a);
-        else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL((pcl_point_residuals_kernel<PCL_PANO_F16, ORD>), grid, blk, 0, s, a);
-        else hipLaunchKernelGGL((pcl_point_residuals_kernel<PCL_PANO_F32, ORD>), grid, blk, 0, s, a);
+        pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+            hipLaunchKernelGGL((pcl_point_residuals_kernel<decltype(fmt)::value, decltype(ord)::value>), grid, blk, 0, s, a);
+        });
     });
     PCL_LAUNCH_CHECK();
     return 0;
@@ -240,15 +129,15 @@ extern "C" int pcl_point_residuals_images(const float* cloud, int64_t n, int col
         PclResPanos list;
         for (int i = 0; i < PCL_RES_MAX_IMAGES; i++) list.p[i] = i < m ? (unsigned long long)panos_host[i0 + i] : 0ull;
         PclResArgs al = a;
-        al.trans = trans + (int64_t)i0 * pose_stride; al.rot = rot + (int64_t)i0 * pose_stride;
-        al.residual = residual + (int64_t)i0 * n; al.B = m;
+        al.pass.trans = trans + (int64_t)i0 * pose_stride; al.pass.rot = rot + (int64_t)i0 * pose_stride;
+        al.residual = residual + (int64_t)i0 * n; al.pass.B = m;
         const dim3 grid((unsigned)(nchunks * m)), blk(PCL_BLOCK);
         pcl_with_flag(order != nullptr, [&](auto ord) {
             pcl_with_flag(sets, [&](auto cs) {
-                constexpr bool ORD = decltype(ord)::value, CSS = decltype(cs)::value;
-                if (pano_format == PCL_PANO_U8) hipLaunchKernelGGL((pcl_point_residuals_images_kernel<PCL_PANO_U8, ORD, CSS>), grid, blk, 0, s, al, list, color_sets, i0);
-                else if (pano_format == PCL_PANO_F16) hipLaunchKernelGGL((pcl_point_residuals_images_kernel<PCL_PANO_F16, ORD, CSS>), grid, blk, 0, s, al, list, color_sets, i0);
-                else hipLaunchKernelGGL((pcl_point_residuals_images_kernel<PCL_PANO_F32, ORD, CSS>), grid, blk, 0, s, al, list, color_sets, i0);
+                pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+                    hipLaunchKernelGGL((pcl_point_residuals_images_kernel<decltype(fmt)::value, decltype(ord)::value, decltype(cs)::value>), grid, blk, 0,
+                                       s, al, list, color_sets, i0);
+                });
             });
         });
         PCL_LAUNCH_CHECK();
@@ -257,10 +146,12 @@ extern "C" int pcl_point_residuals_images(const float* cloud, int64_t n, int col
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// robust weights: the scale of one residual row and the weight plane, pcl_quantile_box's way — an exact order statistic by a 4-pass MSB
+// robust weights: the scale of every residual row and its weight plane, pcl_quantile_box's way — an exact order statistic by a 4-pass MSB
 // radix select over order-preserving uint32 keys, integer atomics only, so the result does not depend on scheduling.  The rank is not
 // known beforehand (M, the number of entries that are not -1, is pass 0's total), and there is no scan launch: every block of a later
-// pass resolves the earlier passes' histograms itself (256 counts each), and so does the weight kernel.  Six launches in all.
+// pass resolves the earlier passes' histograms itself (256 counts each), and so does the weight kernel.  Six launches in all, for any
+// number of rows: the row is blockIdx.y — its residuals n floats, its histograms one PclRobustState, its plane `stride` floats and its
+// (s, M) two floats behind the previous row's.  The counts are integers, so a row's plane and scale do not depend on the rows beside it.
 
 struct PclRobustState { uint32_t hist[4][256]; };                  // (n <= 2^27: a count fits 32 bits)
 struct PclRobustWs { PclRobustState* st; };                        // one state per row, back to back
@@ -331,11 +222,12 @@ __device__ __forceinline__ void pcl_rw_resolve(const PclRobustState* st, int npa
 
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_init_kernel(PclRobustState* st)
 {
-    (&st->hist[0][0])[blockIdx.x * PCL_BLOCK + threadIdx.x] = 0u;
+    (&st[blockIdx.y].hist[0][0])[blockIdx.x * PCL_BLOCK + threadIdx.x] = 0u;
 }
 
-__device__ __forceinline__ void pcl_rw_hist_body(const float* __restrict__ res, int64_t n, PclRobustState* st, int pass)
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_hist_kernel(const float* __restrict__ res, int64_t n, PclRobustState* st, int pass)
 {
+    res += (int64_t)blockIdx.y * n; st += blockIdx.y;
     __shared__ uint32_t h[256];
     h[threadIdx.x] = 0u;
     uint32_t prefix, rank, M;
@@ -354,20 +246,16 @@ __device__ __forceinline__ void pcl_rw_hist_body(const float* __restrict__ res, 
     if (c) atomicAdd(&st->hist[pass][threadIdx.x], c);
 }
 
-__global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_hist_kernel(const float* __restrict__ res, int64_t n, PclRobustState* st, int pass)
-{
-    pcl_rw_hist_body(res, n, st, pass);
-}
-
 template <int KIND>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_plane_kernel(const float* __restrict__ res, int64_t n, int64_t stride, const PclRobustState* st, float k,
                                                                  float* __restrict__ plane, float* __restrict__ scale_out)
 {
+    res += (int64_t)blockIdx.y * n; st += blockIdx.y; plane += (int64_t)blockIdx.y * stride;
     uint32_t prefix, rank, M;
     pcl_rw_resolve(st, 4, prefix, rank, M);
     const float s = M ? pcl_rw_key2f(prefix) : 0.f;
     const float c = __fmul_rn(k, s);
-    if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) { scale_out[0] = s; scale_out[1] = (float)M; }
+    if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) { scale_out[2 * blockIdx.y] = s; scale_out[2 * blockIdx.y + 1] = (float)M; }
     for (int64_t i = (int64_t)blockIdx.x * PCL_BLOCK + threadIdx.x; i < stride; i += (int64_t)gridDim.x * PCL_BLOCK) {
         float w = 0.f;                                             // padding
         if (i < n) {
@@ -381,73 +269,9 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_plane_kernel(const float* __
     }
 }
 
-// (pcl_rw_plane_kernel's statements for a row of the rows kernel below: a shared inline body changes that kernel's instruction stream)
-template <int KIND>
-__device__ __forceinline__ void pcl_rw_plane_body(const float* __restrict__ res, int64_t n, int64_t stride, const PclRobustState* st, float k,
-                                                  float* __restrict__ plane, float* __restrict__ scale_out)
-{
-    uint32_t prefix, rank, M;
-    pcl_rw_resolve(st, 4, prefix, rank, M);
-    const float s = M ? pcl_rw_key2f(prefix) : 0.f;
-    const float c = __fmul_rn(k, s);
-    if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) { scale_out[0] = s; scale_out[1] = (float)M; }
-    for (int64_t i = (int64_t)blockIdx.x * PCL_BLOCK + threadIdx.x; i < stride; i += (int64_t)gridDim.x * PCL_BLOCK) {
-        float w = 0.f;                                             // padding
-        if (i < n) {
-            const float l = res[i];
-            if (l == -1.0f || M == 0u) w = 1.f;
-            else if (!(fabsf(l) <= 3.402823466e38f)) w = 0.f;      // NaN or infinite
-            else if (l <= c) w = 1.f;
-            else if (KIND == PCL_ROBUST_HUBER && c == c) w = __fdiv_rn(c, l);      // (a NaN scale — most of the row NaN — votes 0)
-        }
-        plane[i] = w;
-    }
-}
-
-
-// The same for several rows in the same launches: the row is blockIdx.y — its residuals n floats, its histograms one PclRobustState, its plane
-// `stride` floats and its (s, M) two floats behind the previous row's.  The bodies are the single-row kernels'; the counts are integers, so
-// every row's plane and scale are those of pcl_robust_weights on that row alone.
-__global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_init_rows_kernel(PclRobustState* st)
-{
-    (&st[blockIdx.y].hist[0][0])[blockIdx.x * PCL_BLOCK + threadIdx.x] = 0u;
-}
-
-__global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_hist_rows_kernel(const float* __restrict__ res, int64_t n, PclRobustState* st, int pass)
-{
-    pcl_rw_hist_body(res + (int64_t)blockIdx.y * n, n, st + blockIdx.y, pass);
-}
-
-template <int KIND>
-__global__ void __launch_bounds__(PCL_BLOCK) pcl_rw_plane_rows_kernel(const float* __restrict__ res, int64_t n, int64_t stride, const PclRobustState* st,
-                                                                      float k, float* __restrict__ planes, float* __restrict__ scale_out)
-{
-    pcl_rw_plane_body<KIND>(res + (int64_t)blockIdx.y * n, n, stride, st + blockIdx.y, k, planes + (int64_t)blockIdx.y * stride,
-                            scale_out ? scale_out + 2 * blockIdx.y : nullptr);
-}
-
-extern "C" int pcl_robust_weights(const float* residual_packed, int64_t n, int kind, float k, float* plane, float* scale_out, void* workspace,
-                                  size_t workspace_bytes, void* stream)
-{
-    if (!residual_packed || !plane || !workspace || n <= 0 || n > PCL_MAX_POINTS) return PCL_EINVAL;
-    if ((kind != PCL_ROBUST_TRUNC && kind != PCL_ROBUST_HUBER) || !(k > 0.f && k <= 3.402823466e38f)) return PCL_EINVAL;
-    PclRobustWs w;
-    if (workspace_bytes < robust_layout(workspace, 1, &w)) return PCL_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t stride = pcl_cloud_stride(n), want = stride / PCL_BLOCK;
-    const unsigned nblk = (unsigned)(want < 1024 ? want : 1024);
-    hipLaunchKernelGGL(pcl_rw_init_kernel, dim3(4), dim3(PCL_BLOCK), 0, s, w.st);
-    for (int pass = 0; pass < 4; pass++) hipLaunchKernelGGL(pcl_rw_hist_kernel, dim3(nblk), dim3(PCL_BLOCK), 0, s, residual_packed, n, w.st, pass);
-    if (kind == PCL_ROBUST_HUBER)
-        hipLaunchKernelGGL(pcl_rw_plane_kernel<PCL_ROBUST_HUBER>, dim3(nblk), dim3(PCL_BLOCK), 0, s, residual_packed, n, stride, w.st, k, plane, scale_out);
-    else
-        hipLaunchKernelGGL(pcl_rw_plane_kernel<PCL_ROBUST_TRUNC>, dim3(nblk), dim3(PCL_BLOCK), 0, s, residual_packed, n, stride, w.st, k, plane, scale_out);
-    PCL_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int pcl_robust_weights_rows(const float* residual_packed, int64_t n, int nrows, int kind, float k, float* planes, float* scale_out,
-                                       void* workspace, size_t workspace_bytes, void* stream)
+// the checks and the six launches of both entry points
+static int robust_rows(const float* residual_packed, int64_t n, int nrows, int kind, float k, float* planes, float* scale_out, void* workspace,
+                       size_t workspace_bytes, void* stream)
 {
     if (!residual_packed || !planes || !workspace || n <= 0 || n > PCL_MAX_POINTS || nrows < 1 || nrows > PCL_ROBUST_MAX_ROWS) return PCL_EINVAL;
     if ((kind != PCL_ROBUST_TRUNC && kind != PCL_ROBUST_HUBER) || !(k > 0.f && k <= 3.402823466e38f)) return PCL_EINVAL;
@@ -457,12 +281,24 @@ extern "C" int pcl_robust_weights_rows(const float* residual_packed, int64_t n, 
     const int64_t stride = pcl_cloud_stride(n), want = stride / PCL_BLOCK;
     const unsigned nblk = (unsigned)(want < 1024 ? want : 1024);
     const dim3 grid(nblk, (unsigned)nrows), blk(PCL_BLOCK);
-    hipLaunchKernelGGL(pcl_rw_init_rows_kernel, dim3(4, (unsigned)nrows), blk, 0, s, w.st);
-    for (int pass = 0; pass < 4; pass++) hipLaunchKernelGGL(pcl_rw_hist_rows_kernel, grid, blk, 0, s, residual_packed, n, w.st, pass);
+    hipLaunchKernelGGL(pcl_rw_init_kernel, dim3(4, (unsigned)nrows), blk, 0, s, w.st);
+    for (int pass = 0; pass < 4; pass++) hipLaunchKernelGGL(pcl_rw_hist_kernel, grid, blk, 0, s, residual_packed, n, w.st, pass);
     if (kind == PCL_ROBUST_HUBER)
-        hipLaunchKernelGGL(pcl_rw_plane_rows_kernel<PCL_ROBUST_HUBER>, grid, blk, 0, s, residual_packed, n, stride, w.st, k, planes, scale_out);
+        hipLaunchKernelGGL(pcl_rw_plane_kernel<PCL_ROBUST_HUBER>, grid, blk, 0, s, residual_packed, n, stride, w.st, k, planes, scale_out);
     else
-        hipLaunchKernelGGL(pcl_rw_plane_rows_kernel<PCL_ROBUST_TRUNC>, grid, blk, 0, s, residual_packed, n, stride, w.st, k, planes, scale_out);
+        hipLaunchKernelGGL(pcl_rw_plane_kernel<PCL_ROBUST_TRUNC>, grid, blk, 0, s, residual_packed, n, stride, w.st, k, planes, scale_out);
     PCL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int pcl_robust_weights(const float* residual_packed, int64_t n, int kind, float k, float* plane, float* scale_out, void* workspace,
+                                  size_t workspace_bytes, void* stream)
+{
+    return robust_rows(residual_packed, n, 1, kind, k, plane, scale_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pcl_robust_weights_rows(const float* residual_packed, int64_t n, int nrows, int kind, float k, float* planes, float* scale_out,
+                                       void* workspace, size_t workspace_bytes, void* stream)
+{
+    return robust_rows(residual_packed, n, nrows, kind, k, planes, scale_out, workspace, workspace_bytes, stream);
 }

@@ -412,11 +412,62 @@ def sampling_loss(cloud, pano, trans, rot, with_grad=True, visible=None, depth=N
     return out
 
 
-def _residual_cloud(cloud, pano, who):
-    if cloud.color_sets > 1:
-        raise ValueError("%s: a cloud of colour sets (one colour set only)" % who)
+def _residual_cloud(cloud, pano, who, images=None):
+    """images: how many panoramas the call takes, one per colour set (None: one panorama, one colour set only)"""
+    if cloud.color_sets > 1 and cloud.color_sets != images:
+        raise ValueError("%s: a cloud of colour sets (one colour set only)" % who if images is None else
+                         "%s: %d colour sets for %d images" % (who, cloud.color_sets, images))
     if pano.fmt not in (_lib.PANO_F32, _lib.PANO_U8, _lib.PANO_F16):
         raise ValueError("%s: the trim launch's texel layouts (u8p, u8v) are not sampled here" % who)
+
+
+def _winner_poses(winners, who, rows=None):
+    """a (G, 16) tensor as _GdEngine.winners returns it, read on the device -> (trans_ptr, rot_ptr, 16, G): pose stride 16, translation in
+    columns 0-2, yaw / pitch / roll in 13-15 — no host round trip between a chain and what is evaluated at its winners.  rows: the row
+    count it must have (one per panorama)"""
+    ok = torch.is_tensor(winners) and winners.is_cuda and winners.dtype == F32 and winners.is_contiguous() and winners.dim() == 2 \
+        and winners.shape[1] == 16 and (winners.shape[0] > 0 if rows is None else winners.shape[0] == rows)
+    if not ok:
+        raise ValueError("%s: winners must be a contiguous %s float32 GPU tensor" % (who, "(G, 16)" if rows is None else "(I, 16)")
+                         + ("" if rows is None else ", one row per panorama"))
+    return _ptr(winners), ctypes.c_void_p(winners.data_ptr() + 13 * 4), 16, int(winners.shape[0])
+
+
+def _point_residuals(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, packed, out=None):
+    """What the four residual functions do: `rows` poses (pointers and pose stride) against ONE Pano — pcl_point_residuals, any number of
+    poses in one launch — or row i against panos[i] and colour set i of a list of Panos — pcl_point_residuals_images -> (rows, N)"""
+    lib = _lib.load()
+    several = not isinstance(panos, Pano)
+    if several and len(panos) < 1:
+        raise ValueError("%s: no panorama" % who)
+    p0 = panos[0] if several else panos
+    _residual_cloud(cloud, p0, who, len(panos) if several else None)
+    if several:
+        for p in panos:
+            if (p.H, p.W, p.fmt) != (p0.H, p0.W, p0.fmt):
+                raise ValueError("%s: all panoramas must share size and texel format" % who)
+        if rows != len(panos):
+            raise ValueError("%s: one pose per panorama" % who)
+    if out is None:
+        out = torch.empty(rows, cloud.n, dtype=F32, device=dev)
+    elif not (out.is_cuda and out.dtype == F32 and out.is_contiguous() and out.numel() == rows * cloud.n):
+        raise ValueError("%s: out must be a contiguous (%s, N) float32 GPU tensor" % (who, "I" if several else "G"))
+    order = None if packed else _ptr(cloud.order)
+    if several:
+        arr = (ctypes.c_uint64 * rows)(*[p.data.data_ptr() for p in panos])
+        _lib.check(lib.pcl_point_residuals_images(_ptr(cloud.data), cloud.n, int(cloud.color_sets), arr, rows, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr,
+                                                  stride, order, _ptr(out), _stream()), "pcl_point_residuals_images")
+    else:
+        _lib.check(lib.pcl_point_residuals(_ptr(cloud.data), cloud.n, _ptr(p0.data), p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride, rows,
+                                           order, _ptr(out), _stream()), "pcl_point_residuals")
+    return out
+
+
+def _pose_rows(trans, rot):
+    trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+    if rot.shape[0] != trans.shape[0] or trans.shape[0] == 0:
+        raise ValueError("trans and rot must have the same, positive number of rows")
+    return trans, rot
 
 
 def point_residuals(cloud, pano, trans, rot, packed=False):
@@ -424,36 +475,14 @@ def point_residuals(cloud, pano, trans, rot, packed=False):
     the point and exactly -1 where the sampled colour is exactly black (pcl_point_residuals) — in the order of the cloud's xyz rows, or with
     packed=True in the packed slot order (what robust_weights reads).  A cloud's weights play no part.  ValueError: a cloud of colour sets,
     a panorama in one of the trim launch's texel layouts."""
-    lib = _lib.load()
-    _residual_cloud(cloud, pano, "point_residuals")
-    trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-    B = int(trans.shape[0])
-    if rot.shape[0] != B or B == 0:
-        raise ValueError("trans and rot must have the same, positive number of rows")
-    out = torch.empty(B, cloud.n, dtype=F32, device=trans.device)
-    _lib.check(lib.pcl_point_residuals(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans), _ptr(rot), 3, B,
-                                       None if packed else _ptr(cloud.order), _ptr(out), _stream()), "pcl_point_residuals")
-    return out
+    trans, rot = _pose_rows(trans, rot)
+    return _point_residuals("point_residuals", cloud, pano, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, packed)
 
 
 def point_residuals_at_winners(cloud, pano, winners, packed=False, out=None):
-    """point_residuals at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (pose stride 16: translation in
-    columns 0-2, yaw / pitch / roll in 13-15) — no host round trip between a chain and the residuals of its winner.  out: a (G, N) tensor to
-    write into."""
-    lib = _lib.load()
-    _residual_cloud(cloud, pano, "point_residuals_at_winners")
-    if not (torch.is_tensor(winners) and winners.is_cuda and winners.dtype == F32 and winners.is_contiguous() and winners.dim() == 2
-            and winners.shape[1] == 16 and winners.shape[0] > 0):
-        raise ValueError("point_residuals_at_winners: winners must be a contiguous (G, 16) float32 GPU tensor")
-    G = int(winners.shape[0])
-    if out is None:
-        out = torch.empty(G, cloud.n, dtype=F32, device=winners.device)
-    elif not (out.is_cuda and out.dtype == F32 and out.is_contiguous() and out.numel() == G * cloud.n):
-        raise ValueError("point_residuals_at_winners: out must be a contiguous (G, N) float32 GPU tensor")
-    rot = ctypes.c_void_p(winners.data_ptr() + 13 * 4)
-    _lib.check(lib.pcl_point_residuals(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(winners), rot, 16, G,
-                                       None if packed else _ptr(cloud.order), _ptr(out), _stream()), "pcl_point_residuals")
-    return out
+    """point_residuals at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses).  out: a (G, N)
+    tensor to write into."""
+    return _point_residuals("point_residuals_at_winners", cloud, pano, *_winner_poses(winners, "point_residuals_at_winners"), winners.device, packed, out)
 
 
 def _pose_information(cloud, pano, trans_ptr, rot_ptr, stride, B, dev):
@@ -476,75 +505,31 @@ def pose_information(cloud, pano, trans, rot):
     its weights, one factor per term.  status 0: fine; 1: nothing kept or something not finite (cov NaN); 2: H not positive definite
     (cov NaN).  ValueError: a cloud of colour sets, a panorama in one of the trim launch's texel layouts."""
     _residual_cloud(cloud, pano, "pose_information")
-    trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-    B = int(trans.shape[0])
-    if rot.shape[0] != B or B == 0:
-        raise ValueError("trans and rot must have the same, positive number of rows")
-    return _pose_information(cloud, pano, _ptr(trans), _ptr(rot), 3, B, trans.device)
+    trans, rot = _pose_rows(trans, rot)
+    return _pose_information(cloud, pano, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
 
 
 def pose_information_at_winners(cloud, pano, winners):
-    """pose_information at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (pose stride 16: translation in
-    columns 0-2, yaw / pitch / roll in 13-15) — no host round trip between a chain and the covariance of its winner."""
+    """pose_information at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses)."""
     _residual_cloud(cloud, pano, "pose_information_at_winners")
-    if not (torch.is_tensor(winners) and winners.is_cuda and winners.dtype == F32 and winners.is_contiguous() and winners.dim() == 2
-            and winners.shape[1] == 16 and winners.shape[0] > 0):
-        raise ValueError("pose_information_at_winners: winners must be a contiguous (G, 16) float32 GPU tensor")
-    rot = ctypes.c_void_p(winners.data_ptr() + 13 * 4)
-    return _pose_information(cloud, pano, _ptr(winners), rot, 16, int(winners.shape[0]), winners.device)
-
-
-def _residual_images(cloud, panos, who):
-    """the checks of the several-image residual calls -> (the panoramas' addresses as a ctypes array, the colour-set count to pass)"""
-    I = len(panos)
-    if I < 1:
-        raise ValueError("%s: no panorama" % who)
-    if cloud.color_sets > 1 and cloud.color_sets != I:
-        raise ValueError("%s: %d colour sets for %d images" % (who, cloud.color_sets, I))
-    p0 = panos[0]
-    if p0.fmt not in (_lib.PANO_F32, _lib.PANO_U8, _lib.PANO_F16):
-        raise ValueError("%s: the trim launch's texel layouts (u8p, u8v) are not sampled here" % who)
-    for p in panos:
-        if (p.H, p.W, p.fmt) != (p0.H, p0.W, p0.fmt):
-            raise ValueError("%s: all panoramas must share size and texel format" % who)
-    return (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos]), int(cloud.color_sets)
+    return _pose_information(cloud, pano, *_winner_poses(winners, "pose_information_at_winners"), winners.device)
 
 
 def point_residuals_images(cloud, panos, trans, rot, packed=False):
     """(I, N) float GPU tensor: row i is point_residuals of pose (trans[i], rot[i]) against panos[i] — and, for a cloud of I colour sets
     (Cloud.with_color_sets), colour set i — in ONE launch (pcl_point_residuals_images; the panorama addresses are kernel arguments).  Row i
     equals the single call's row bit for bit.  packed: as point_residuals."""
-    lib = _lib.load()
-    arr, sets = _residual_images(cloud, panos, "point_residuals_images")
     trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-    I = len(panos)
-    if trans.shape[0] != I or rot.shape[0] != I:
+    if rot.shape[0] != trans.shape[0]:
         raise ValueError("point_residuals_images: one pose per panorama")
-    out = torch.empty(I, cloud.n, dtype=F32, device=trans.device)
-    p0 = panos[0]
-    _lib.check(lib.pcl_point_residuals_images(_ptr(cloud.data), cloud.n, sets, arr, I, p0.fmt, p0.H, p0.W, _ptr(trans), _ptr(rot), 3,
-                                              None if packed else _ptr(cloud.order), _ptr(out), _stream()), "pcl_point_residuals_images")
-    return out
+    return _point_residuals("point_residuals_images", cloud, list(panos), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, packed)
 
 
 def point_residuals_images_at_winners(cloud, panos, winners, packed=False, out=None):
     """point_residuals_images at the poses of an (I, 16) tensor as _GdEngine.winners(I) returns it, read on the device (pose stride 16): row i
     is winner i against panos[i] (and colour set i).  out: an (I, N) tensor to write into."""
-    lib = _lib.load()
-    arr, sets = _residual_images(cloud, panos, "point_residuals_images_at_winners")
-    I = len(panos)
-    if not (torch.is_tensor(winners) and winners.is_cuda and winners.dtype == F32 and winners.is_contiguous() and winners.dim() == 2
-            and winners.shape[1] == 16 and winners.shape[0] == I):
-        raise ValueError("point_residuals_images_at_winners: winners must be a contiguous (I, 16) float32 GPU tensor, one row per panorama")
-    if out is None:
-        out = torch.empty(I, cloud.n, dtype=F32, device=winners.device)
-    elif not (out.is_cuda and out.dtype == F32 and out.is_contiguous() and out.numel() == I * cloud.n):
-        raise ValueError("point_residuals_images_at_winners: out must be a contiguous (I, N) float32 GPU tensor")
-    p0 = panos[0]
-    rot = ctypes.c_void_p(winners.data_ptr() + 13 * 4)
-    _lib.check(lib.pcl_point_residuals_images(_ptr(cloud.data), cloud.n, sets, arr, I, p0.fmt, p0.H, p0.W, _ptr(winners), rot, 16,
-                                              None if packed else _ptr(cloud.order), _ptr(out), _stream()), "pcl_point_residuals_images")
-    return out
+    who = "point_residuals_images_at_winners"
+    return _point_residuals(who, cloud, list(panos), *_winner_poses(winners, who, len(panos)), winners.device, packed, out)
 
 
 ROBUST_KINDS = {"trunc": _lib.ROBUST_TRUNC, "huber": _lib.ROBUST_HUBER}
@@ -559,31 +544,19 @@ def robust_weights(cloud, residual_row_packed, kind="trunc", k=2.5, plane=None, 
 
 
 def robust_plane(n, row, kind="trunc", k=2.5, plane=None, scale=None):
-    """robust_weights for a row of n residuals in any one point order: the plane's first n entries are in that order"""
-    lib = _lib.load()
-    if kind not in ROBUST_KINDS:
-        raise ValueError("robust_weights: kind %r (one of %s)" % (kind, sorted(ROBUST_KINDS)))
-    k = float(k)
-    if not (k > 0.0 and k < float("inf")):
-        raise ValueError("robust_weights: k must be positive and finite, got %r" % (k,))
+    """robust_weights for a row of n residuals in any one point order: the plane's first n entries are in that order.  robust_planes on a
+    one-row view"""
     row = _dev(row)
     if row.dim() != 1 or row.numel() != n or n <= 0:
         raise ValueError("robust_weights: one residual per point, (N,)")
-    stride = lib.pcl_cloud_stride(n)
-    if plane is None:
-        plane = torch.empty(stride, dtype=F32, device=row.device)
-    elif not (plane.is_cuda and plane.dtype == F32 and plane.is_contiguous() and plane.numel() == stride):
+    if plane is not None and not (plane.is_cuda and plane.dtype == F32 and plane.is_contiguous() and plane.numel() == _lib.load().pcl_cloud_stride(n)):
         raise ValueError("robust_weights: plane must be a contiguous float32 GPU tensor of pcl_cloud_stride(n) entries")
-    if scale is None:
-        scale = torch.empty(2, dtype=F32, device=row.device)
-    nws = lib.pcl_robust_weights_workspace_bytes(n)
-    ws = _bytes(nws)
-    _lib.check(lib.pcl_robust_weights(_ptr(row), n, ROBUST_KINDS[kind], k, _ptr(plane), _ptr(scale), _ptr(ws), nws, _stream()), "pcl_robust_weights")
-    return plane, scale
+    planes, scales = robust_planes(n, row.view(1, n), kind, k, None if plane is None else plane.view(1, -1), None if scale is None else scale.view(1, 2))
+    return planes[0] if plane is None else plane, scales[0] if scale is None else scale
 
 
 def robust_planes(n, rows, kind="trunc", k=2.5, planes=None, scales=None, ws=None):
-    """robust_plane for the R rows of an (R, n) tensor in the same six launches (pcl_robust_weights_rows): -> (planes (R, pcl_cloud_stride(n)),
+    """The robust weights of the R rows of an (R, n) tensor in six launches (pcl_robust_weights_rows): -> (planes (R, pcl_cloud_stride(n)),
     scales (R, 2)); plane i and scale i equal robust_plane(n, rows[i], kind, k) bit for bit.  planes / scales / ws: tensors to write into
     (ws: a byte workspace of pcl_robust_weights_rows_workspace_bytes(n, R))."""
     lib = _lib.load()
@@ -1091,7 +1064,7 @@ class GradientDescent(_GdEngine):
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         self.B = int(trans.shape[0])
         self.box = _dev(box).reshape(6)
-        self.weight_sets = int(weight_sets)
+        self.weight_sets, self._robust = int(weight_sets), None       # (_robust: _robust_buffers, once a re-weighting or a plane asks for them)
         if self.weight_sets:
             if self.weight_sets < 1 or self.B % self.weight_sets or depth_mask or cloud.weights is not None or \
                     cloud.color_sets not in (1, self.weight_sets):
@@ -1123,17 +1096,14 @@ class GradientDescent(_GdEngine):
         self.ws = _bytes(self.ws_bytes)
         self.reset(trans, rot)
 
-    def _wsets(self):
-        return int(self.__dict__.get("weight_sets", 0))
-
     def run(self, num_iter, history=False, timer=None):
         if self._chain is not None:
             return self._chain.run(num_iter, history, timer)
         hist = torch.empty(num_iter, self.B, dtype=F32, device=self.state.device) if history else None
         weights = self._run_weights()
-        if self._wsets():
+        if self.weight_sets:
             # (planes at a stable address, like the one plane below; None: the unweighted loss under the same single-image plan)
-            _lib.check(_lib.load().pcl_gd_run_weight_sets(_ptr(self.cloud.data), _ptr(weights), self._wsets(), self.cloud.n, _ptr(self.pano.data),
+            _lib.check(_lib.load().pcl_gd_run_weight_sets(_ptr(self.cloud.data), _ptr(weights), self.weight_sets, self.cloud.n, _ptr(self.pano.data),
                                                           self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state), self.B, _ptr(self.box),
                                                           ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
                                                           timer.handle if timer else None, _stream()), "pcl_gd_run_weight_sets")
@@ -1153,81 +1123,67 @@ class GradientDescent(_GdEngine):
 
     def _run_weights(self):
         """the weight plane run() evaluates: the engine's own robust plane once robust_reweight has filled it, else the cloud's, else None"""
-        robust = self.__dict__.get("_robust")
-        return robust["plane"] if robust is not None and robust["on"] else self.cloud.weights
+        return self._robust["plane"] if self._robust is not None and self._robust["on"] else self.cloud.weights
 
     def _graph_key(self):
         w = self._run_weights() if self._chain is None else None
-        return (0 if w is None else w.data_ptr(), self._wsets())
+        return (0 if w is None else w.data_ptr(), self.weight_sets)
 
     def _robust_buffers(self):
         """the engine's own plane(s), residual row(s), scale(s) and select workspace, at stable addresses: one per image of a weight-set engine"""
-        r = self.__dict__.get("_robust")
-        if r is None:
-            lib, dev, I = _lib.load(), self.state.device, max(1, self._wsets())
-            nws = lib.pcl_robust_weights_rows_workspace_bytes(self.cloud.n, I) if self._wsets() else lib.pcl_robust_weights_workspace_bytes(self.cloud.n)
-            r = self._robust = {"on": False, "plane": torch.empty(I * lib.pcl_cloud_stride(self.cloud.n), dtype=F32, device=dev),
-                                "row": torch.empty(I, self.cloud.n, dtype=F32, device=dev),
-                                "scale": torch.empty(2 * I if self._wsets() else 2, dtype=F32, device=dev), "ws": _bytes(nws)}
-        return r
+        if self._robust is None:
+            lib, dev, I = _lib.load(), self.state.device, max(1, self.weight_sets)
+            self._robust = {"on": False, "plane": torch.empty(I * lib.pcl_cloud_stride(self.cloud.n), dtype=F32, device=dev),
+                            "row": torch.empty(I, self.cloud.n, dtype=F32, device=dev), "scale": torch.empty(2 * I, dtype=F32, device=dev),
+                            "ws": _bytes(lib.pcl_robust_weights_rows_workspace_bytes(self.cloud.n, I))}
+        return self._robust
 
     def weight_planes(self):
         """(I, pcl_cloud_stride(n)) view of a weight-set engine's planes, packed point order (what robust_reweight fills in place)"""
-        if not self._wsets():
+        if not self.weight_sets:
             raise ValueError("weight_planes: an engine made with weight_sets")
-        return self._robust_buffers()["plane"].view(self._wsets(), -1)
+        return self._robust_buffers()["plane"].view(self.weight_sets, -1)
 
     def weight_planes_on(self, on=True):
         """run() evaluates the weighted loss with weight_planes() as they are (on) or the unweighted one (off): for planes a caller filled"""
-        if not self._wsets():
+        if not self.weight_sets:
             raise ValueError("weight_planes_on: an engine made with weight_sets")
         self._robust_buffers()["on"] = bool(on)
 
     # ---- robust re-weighting (cfg.robust_iters of omniloc_batch): the SAME state goes on under weights made from its own winner's residuals.
     def robust_clear(self):
         """back to the cloud's own weights (none, for a robust chain): what a new refinement on a cached engine starts with"""
-        if self.__dict__.get("_robust") is not None:
+        if self._robust is not None:
             self._robust["on"] = False
 
     def robust_reweight(self, kind="trunc", k=2.5):
-        """pcl_gd_winner -> pcl_point_residuals at the pose that call reports (stride 16, packed, on the device) -> pcl_robust_weights into the
-        engine's OWN plane, in place at a stable address; from here on run() evaluates the weighted loss (pcl_gd_run_weighted) with the state
-        as it is.  Eight launches, nothing waits for the host.  One image, one colour set, no depth mask, a cloud without weights of its own.
-        -> (plane, scale): the plane and the device (s, M) of this re-weighting."""
-        if self._wsets():
-            return self._robust_reweight_sets(kind, k)
-        if self._chain is not None or self.hyper.depth_mask or self.cloud.color_sets > 1:
-            raise ValueError("robust_reweight: one colour set and no depth mask")
-        if self.cloud.weights is not None:
-            raise ValueError("robust_reweight: the cloud carries per-point weights of its own")
-        panos = {id(p): p for p in self.__dict__.get("_panos", [])}
-        if len(panos) > 1:
-            raise ValueError("robust_reweight: the candidates of one image only (several: an engine made with weight_sets)")
-        pano = next(iter(panos.values())) if panos else self.pano
-        lib, r = _lib.load(), self._robust_buffers()
-        if kind not in ROBUST_KINDS:
-            raise ValueError("robust_reweight: kind %r (one of %s)" % (kind, sorted(ROBUST_KINDS)))
-        win = self.winners(1)
-        point_residuals_at_winners(self.cloud, pano, win, packed=True, out=r["row"])
-        _lib.check(lib.pcl_robust_weights(_ptr(r["row"]), self.cloud.n, ROBUST_KINDS[kind], float(k), _ptr(r["plane"]), _ptr(r["scale"]), _ptr(r["ws"]),
-                                          r["ws"].numel(), _stream()), "pcl_robust_weights")
-        r["on"] = True
-        return r["plane"], r["scale"]
-
-    def _robust_reweight_sets(self, kind, k):
-        """robust_reweight of a weight-set engine of I images: pcl_gd_winner over the I groups -> pcl_point_residuals_images at those I winners
-        (image i's panorama and colour set) -> pcl_robust_weights_rows into the I planes, in place: the same eight launches as for one image.
-        -> (planes (I, stride), scales (I, 2))"""
-        I = self._wsets()
+        """pcl_gd_winner over the I = max(1, weight_sets) image groups -> the residuals at the poses that call reports (stride 16, packed, on
+        the device; image i's panorama and colour set) -> pcl_robust_weights_rows into the engine's OWN I planes, in place at stable
+        addresses; from here on run() evaluates the weighted loss with the state as it is.  Eight launches, nothing waits for the host.
+        An engine made without weight_sets: one image, one colour set, no depth mask, a cloud without weights of its own.
+        -> (plane, scale) of this re-weighting: `stride` floats and the device (s, M); a weight-set engine: (I, stride) and (I, 2)."""
+        I = max(1, self.weight_sets)
         panos = self.__dict__.get("_panos") or [self.pano] * I
-        if len(panos) != I:
-            raise ValueError("robust_reweight: %d panoramas named for %d images (set_pano_groups)" % (len(panos), I))
+        if self.weight_sets:
+            if len(panos) != I:
+                raise ValueError("robust_reweight: %d panoramas named for %d images (set_pano_groups)" % (len(panos), I))
+        else:
+            if self._chain is not None or self.hyper.depth_mask or self.cloud.color_sets > 1:
+                raise ValueError("robust_reweight: one colour set and no depth mask")
+            if self.cloud.weights is not None:
+                raise ValueError("robust_reweight: the cloud carries per-point weights of its own")
+            if len({id(p) for p in panos}) > 1:
+                raise ValueError("robust_reweight: the candidates of one image only (several: an engine made with weight_sets)")
+            if kind not in ROBUST_KINDS:
+                raise ValueError("robust_reweight: kind %r (one of %s)" % (kind, sorted(ROBUST_KINDS)))
+            panos = panos[0]                           # (one Pano: pcl_point_residuals, as for any number of poses on one panorama)
         r = self._robust_buffers()
+        who = "point_residuals_images_at_winners" if self.weight_sets else "point_residuals_at_winners"
         win = self.winners(I)
-        point_residuals_images_at_winners(self.cloud, panos, win, packed=True, out=r["row"])
+        _point_residuals(who, self.cloud, panos, *_winner_poses(win, who, I), win.device, True, r["row"])
         planes, scales = robust_planes(self.cloud.n, r["row"], kind, k, r["plane"].view(I, -1), r["scale"].view(I, 2), r["ws"])
         r["on"] = True
-        return planes, scales
+        return (planes, scales) if self.weight_sets else (r["plane"], r["scale"])
 
     def run_robust(self, num_iter, robust_iters, kind="trunc", k=2.5, history=False, graph=False):
         """The robust chain: unweighted up to robust_iters[0]; at every entry of robust_iters robust_reweight(kind, k), and the same state
@@ -1257,8 +1213,8 @@ class GradientDescent(_GdEngine):
             return self._chain.reset(trans, rot)
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         assert trans.shape[0] == self.B
-        if self._wsets():
-            _lib.check(_lib.load().pcl_gd_init_weight_sets(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, self._wsets(), ctypes.byref(self.hyper),
+        if self.weight_sets:
+            _lib.check(_lib.load().pcl_gd_init_weight_sets(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, self.weight_sets, ctypes.byref(self.hyper),
                                                            _stream()), "pcl_gd_init_weight_sets")
             return
         _lib.check(_lib.load().pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
@@ -1304,12 +1260,13 @@ class GradientDescent(_GdEngine):
     def _smaller(self, keep):
         """an engine over the same cloud, panorama, box and hyper-parameters with `keep` candidates per image, its state not yet written"""
         lib, groups = _lib.load(), self._groups()
-        if self._wsets():
+        if self.weight_sets:
             raise ValueError("pruned: a weight-set engine is not pruned")
         if self.B % groups or not 1 <= keep <= self.B // groups:
             raise ValueError("pruned: keep %d of %d candidates per image" % (keep, self.B // max(groups, 1)))
         g = GradientDescent.__new__(GradientDescent)
         g.cloud, g.pano, g.box, g.B = self.cloud, self.pano, self.box, groups * keep
+        g.weight_sets, g._robust = 0, None
         g._chain = self._chain._smaller(keep) if self._chain is not None else None
         if g._chain is not None:
             g.hyper, g.state, g.ws, g.ws_bytes = g._chain.hyper, g._chain.state, g._chain.ws, g._chain.ws_bytes

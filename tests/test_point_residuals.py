@@ -141,6 +141,45 @@ def test_same_values_across_orders_strides_and_formats(ops, oracle, name, B):
     assert same_bits(rows["u8"], rows["f16"])
 
 
+def head_case(ops, oracle, n, B):
+    """the first n points of S1 against S1's u8 panorama under B of its start poses"""
+    xyz, rgb, img = scene(oracle, "S1")[:3]
+    trans, rot = poses(oracle, "S1", B)
+    return ops.Cloud(T(xyz[:n]), T(rgb[:n])), ops.Pano(T(img), fmt="u8"), T(trans), T(rot)
+
+
+@pytest.mark.parametrize("packed", [True, False])
+def test_more_poses_on_one_panorama_than_an_address_list_holds(ops, oracle, packed):
+    """B = 65 poses on ONE panorama, n = 513 (two steps, the second one point): one call == the 65 one-pose calls stacked, bit for bit.  The
+    several-image form carries 64 panorama addresses per launch; the single form takes any B in one launch and must not go through that list."""
+    cloud, pano, trans, rot = head_case(ops, oracle, 513, 65)
+    got = ops.point_residuals(cloud, pano, trans, rot, packed=packed)
+    assert got.shape == (65, 513)
+    alone = torch.cat([ops.point_residuals(cloud, pano, trans[b:b + 1], rot[b:b + 1], packed=packed) for b in range(65)])
+    assert same_bits(got, alone)
+    assert (got >= 0).any() and (got == -1).any()             # (neither all kept nor all masked)
+
+
+@pytest.mark.parametrize("n", [1, 511, 512, 513, 1025])
+def test_the_residual_walk_is_the_information_walk(ops, oracle, n):
+    """n where a pair, a step or a chunk is partial (the information kernel deals at least two steps to a chunk, the residual kernel one): per
+    pose, the kept entries of point_residuals are counted by pose_information's M exactly, and their float64 sum is its S1.
+
+    The bound is info_helpers.bounds' BS1 = n e + ADDS u S1 with e = 0: both kernels hold the SAME fp32 l_i per point (one body, the same
+    instructions on the same inputs; the cloud has no weights), so what is left is the information kernel's ADDS fp32 roundings per sum."""
+    import info_helpers as ih
+    cloud, pano, trans, rot = head_case(ops, oracle, n, 3)
+    res = ops.point_residuals(cloud, pano, trans, rot)
+    stats = ops.pose_information(cloud, pano, trans, rot)[2].cpu().numpy().astype(np.float64)
+    kept = res >= 0
+    assert ((res == -1) | kept).all()
+    assert np.array_equal(kept.sum(1).cpu().numpy().astype(np.float64), stats[:, 0]), (n, kept.sum(1), stats[:, 0])
+    s1 = torch.where(kept, res, torch.zeros_like(res)).double().sum(1).cpu().numpy()
+    bound = ih.ADDS * ih.U * s1
+    print("n=%d: M %s; |S1 - sum| %s of bound %s" % (n, stats[:, 0], np.abs(stats[:, 1] - s1), bound))
+    assert (np.abs(stats[:, 1] - s1) <= bound).all(), (n, stats[:, 1], s1)
+
+
 @pytest.mark.parametrize("fmt", FMTS)
 @pytest.mark.parametrize("name,B", CASES)
 def test_per_point_against_the_reference_formulas(ops, oracle, parity, name, B, fmt):

@@ -54,8 +54,8 @@ def test_symbols_are_declared_bound_and_exported(lib):
         assert _lib.SIGNATURES[name][0] in (ctypes.c_int, ctypes.c_size_t)
     assert lib.pcl_abi_version() == 12 and _lib.ABI_VERSION == 12
     blob = open(_lib.so_path(), "rb").read()
-    for kernel in (b"pcl_loss_wsets_kernel", b"pcl_loss_fused_wsets_kernel", b"pcl_point_residuals_images_kernel", b"pcl_rw_hist_rows_kernel",
-                   b"pcl_rw_plane_rows_kernel"):
+    for kernel in (b"pcl_loss_wsets_kernel", b"pcl_loss_fused_wsets_kernel", b"pcl_point_residuals_images_kernel", b"pcl_rw_init_kernel",
+                   b"pcl_rw_hist_kernel", b"pcl_rw_plane_kernel"):
         assert kernel in blob, kernel
     left_out = re.search(r"Deliberately left out: weights in the initialisation stage.*?\*/", open(HEADER).read(), flags=re.S).group(0)
     assert "pcl_gd_run_weight_sets" in left_out
