@@ -181,6 +181,43 @@ int pcl_robust_weights_rows(const float *residual_packed, int64_t n, int nrows, 
 size_t pcl_pose_information_workspace_bytes(int64_t n, int B);
 int pcl_pose_information(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans,
                          const float *rot, int pose_stride, int B, float *info, float *cov, void *workspace, size_t workspace_bytes, void *stream);
+/* Levenberg-Marquardt pose polish on H and b (additive to ABI 12; BUILD-DEFINED: the reference refines with Adam and has nothing like it).
+ * What is minimised is the MEAN SQUARED residual sigma^2(theta) = sum w m l^2 / sum w m over theta = (t0, t1, t2, yaw, pitch, roll), with m, w,
+ * l, H and b those of pcl_pose_information above.  It is NOT the sampling loss sum w m l / sum w m that the pcl_gd_* chains minimise: the two
+ * share their per-point terms, mask and weights and are different objectives.  Units: metres for t, radians for the angles; step_cap and
+ * tol bound both alike.  The whole chain runs on the device: one call enqueues an init launch and, for every evaluation k = 0 .. iters, a
+ * per-point pass launch at the trial pose (pcl_pose_information's pass, same arithmetic and partial rows, with the poses read from the
+ * state; the blocks of a frozen pose return before their point loop) and a step launch (one block per pose):
+ *   F = (float)(S2 / M) from the rows added in double in pcl_pose_information's order.  The trial is ACCEPTED iff the sums are finite,
+ *   M > 0 and F < F_acc compared in fp32 (F_acc = +inf at the start; evaluation 0 is accepted iff the sums are finite and M > 0, else the pose
+ *   freezes with status 1 and the caller's pose is returned).  On acceptance theta_acc, F_acc, H, b and the stats become the trial's and,
+ *   except at k = 0, lambda = fmaxf(lambda * lam_down, lam_min); on rejection lambda = fminf(lambda * lam_up, lam_max).
+ *   Step (none after evaluation `iters`): (H + lambda diag H) delta = -b in double on the ACCEPTED H and b, by pcl_pose_information's Cholesky
+ *   with its power-of-two scaling (a failed pivot freezes the pose with status 2); if max |delta_i| > step_cap the whole delta is scaled by
+ *   step_cap / max |delta_i|; theta_try = (float)((double)theta_acc + delta).  The pose freezes converged, status 3, when max |delta_i| <= tol
+ *   or theta_try equals theta_acc in all six floats.  A frozen pose takes no further part.
+ * out[b] is 16 floats: theta_acc (6), F at the start, F_acc, the final lambda, accepted, rejected, evaluations, status, 0, 0, 0.
+ * status: 0 all evaluations ran; 1 the first evaluation had M = 0 or something not finite; 2 the damped matrix was not positive
+ * definite; 3 converged.  info[b] (48 floats) and cov[b] (nullable, 36) are pcl_pose_information's record and covariance at theta_acc, formed
+ * from the accepted sums by the same code: the same bits as that call at that pose.  trace (nullable) is [iters + 1][B][16]: per
+ * evaluation theta_try (6), F, accepted 0/1, lambda after the decision, M, 0 x 6; rows a frozen pose never reached are 0.
+ * pcl_gn_hyper is read on the host when the call is enqueued (a captured graph keeps its values).  Defaults of the package: lam0 1e-3,
+ * lam_up 10, lam_down 0.1, lam_min 1e-9, lam_max 1e9, step_cap 0.1, tol 0 (never converged by size).
+ * state: pcl_gn_state_bytes(B) bytes the caller owns (0 for B <= 0), written by the init launch; workspace: pcl_gn_workspace_bytes(n, B)
+ * (0 for a bad n or B).  No atomics, no allocation, no synchronisation: capturable; the same inputs give the same bits, and pose b of a
+ * batch has the bits of its own call.  Weights scaled by a power of two change no pose, no lambda, no flag and no F.
+ * PCL_EINVAL, before any HIP call: everything pcl_pose_information refuses; iters < 0 or > 1000; a null hyper_host, state, out or info; a
+ * hyper-parameter that is not finite; lam0 <= 0, lam_up <= 1, lam_down <= 0 or > 1, lam_min > lam_max, step_cap <= 0, tol < 0.
+ * Deliberately left out: an IRLS form that minimises the sampling loss itself, re-weighting inside the chain, the box clamp of the
+ * reference's refinement, colour sets, the images / rooms / depth chains, and any claim about real data. */
+typedef struct pcl_gn_hyper {
+    float lam0, lam_up, lam_down, lam_min, lam_max, step_cap, tol;
+} pcl_gn_hyper;
+size_t pcl_gn_state_bytes(int B);
+size_t pcl_gn_workspace_bytes(int64_t n, int B);
+int pcl_gn_refine(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans,
+                  const float *rot, int pose_stride, int B, const pcl_gn_hyper *hyper_host, int iters, void *state, float *out, float *info,
+                  float *cov, float *trace, void *workspace, size_t workspace_bytes, void *stream);
 /* The Morton order in one call, entirely on the device: bounding box, 63-bit keys, stable radix sort of (key, index);
  * order[i] = index of the point for packed slot i.  workspace: pcl_cloud_order_workspace_bytes(n). */
 size_t pcl_cloud_order_workspace_bytes(int64_t n);

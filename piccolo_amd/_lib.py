@@ -24,6 +24,11 @@ class GdHyper(_c.Structure):
                 ("depth_stride", _c.c_int32), ("fuse", _c.c_int32), ("images", _c.c_int32), ("color_sets", _c.c_int32)]
 
 
+class GnHyper(_c.Structure):
+    _fields_ = [("lam0", _c.c_float), ("lam_up", _c.c_float), ("lam_down", _c.c_float), ("lam_min", _c.c_float), ("lam_max", _c.c_float),
+                ("step_cap", _c.c_float), ("tol", _c.c_float)]
+
+
 GD_MAX_ROOMS = 32
 ROBUST_TRUNC, ROBUST_HUBER = 0, 1
 GD_PRUNE_MAX = 1024       # PCL_GD_PRUNE_MAX: candidates per group of pcl_gd_prune
@@ -54,6 +59,10 @@ SIGNATURES = {
     "pcl_robust_weights_rows": (_int, [_vp, _i64, _int, _int, _c.c_float, _vp, _vp, _vp, _sz, _vp]),
     "pcl_pose_information_workspace_bytes": (_sz, [_i64, _int]),
     "pcl_pose_information": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "pcl_gn_state_bytes": (_sz, [_int]),
+    "pcl_gn_workspace_bytes": (_sz, [_i64, _int]),
+    "pcl_gn_refine": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _c.POINTER(GnHyper), _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                             _vp]),
     "pcl_gd_weight_sets_workspace_bytes": (_sz, [_i64, _int, _int, _c.POINTER(GdHyper)]),
     "pcl_gd_plan_weight_sets": (_int, [_i64, _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
     "pcl_gd_init_weight_sets": (_int, [_vp, _vp, _vp, _int, _int, _c.POINTER(GdHyper), _vp]),

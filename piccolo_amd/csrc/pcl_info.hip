@@ -20,75 +20,19 @@
 // double, factorises (Cholesky), inverts, and rounds every output once to fp32.  Same inputs, same bits.
 #include <math.h>
 
+#include "pcl_info_device.h"
 #include "pcl_point_pass.h"
 #include "pcl_sample_device.h"
 
-#define PCL_INFO_MIN_STEPS 2               // a chunk walks at least two steps where the cloud has them (a one-off call: fewer, longer blocks)
-#define PCL_INFO_ROW 32                    // floats per partial row: A (21, k <= l row-major), sum w l a (6), S2, S1, M, 0, 0
-#define PCL_INFO_NSUM 30
-#define PCL_INFO_REC 48                    // floats per info record (include/piccolo_hip.h)
-
-struct PclInfoArgs {
-    PclPassArgs pass;
-    const float* weights;    // WT: one more plane of `stride` floats, packed order
-    float* partials;         // [nchunks][B][PCL_INFO_ROW]
-};
-
+// (the pass is pcl_info_pass of pcl_info_device.h, which pcl_gn.hip runs as well, gated)
 template <int FMT, bool WT>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_kernel(PclInfoArgs a)
 {
-    __amdgpu_buffer_rsrc_t wrs;
-    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(a.pass.stride * 4), 0x00020000);
-
-    f2 hh[21], bb[6], s2 = F2(0.f), s1 = F2(0.f), mm = F2(0.f);
-#pragma unroll
-    for (int k = 0; k < 21; k++) hh[k] = F2(0.f);
-#pragma unroll
-    for (int k = 0; k < 6; k++) bb[k] = F2(0.f);
-
-    pcl_point_pass<FMT, true, false>(a.pass, a.pass.pano, 1, 0, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool) {
-        // acc: 0 l, 1 m, 2-4 g, 5-7 tau of this pair of points alone.  One factor w (a slot past n never counts, whatever its plane holds)
-        f2 w = F2(1.f), wl = acc[0], wm = acc[1], wa[6];
-        if constexpr (WT) {
-            w = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(wrs, j * 4, 0, 0));
-            w = (f2){valid0 ? w.x : 0.f, valid1 ? w.y : 0.f};
-            wl = w * acc[0]; wm = w * acc[1];
-        }
-#pragma unroll
-        for (int k = 0; k < 6; k++) wa[k] = WT ? w * acc[2 + k] : acc[2 + k];
-        int q = 0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-#pragma unroll
-            for (int l = k; l < 6; l++, q++) hh[q] = pcl_fma2(wa[k], acc[2 + l], hh[q]);
-        }
-#pragma unroll
-        for (int k = 0; k < 6; k++) bb[k] = pcl_fma2(wa[k], acc[0], bb[k]);
-        s2 = pcl_fma2(wl, acc[0], s2);
-        s1 += wl;
-        mm += wm;
-    });
-
-    // the block's sums in a fixed order: packed halves, the lanes of a wave (DPP), the four waves (LDS)
-    __shared__ float red[PCL_BLOCK / PCL_WAVE][PCL_INFO_ROW];
-    const int lane = threadIdx.x & (PCL_WAVE - 1), wave = threadIdx.x / PCL_WAVE;
-    auto put = [&](int k, f2 t) {
-        const float r = pcl_wave_sum(t.x + t.y);
-        if (lane == 0) red[wave][k] = r;
-    };
-#pragma unroll
-    for (int k = 0; k < 21; k++) put(k, hh[k]);
-#pragma unroll
-    for (int k = 0; k < 6; k++) put(21 + k, bb[k]);
-    put(27, s2); put(28, s1); put(29, mm);
-    if (lane == 0) { red[wave][30] = 0.f; red[wave][31] = 0.f; }
-    __syncthreads();
-    if (threadIdx.x < PCL_INFO_ROW) {
-        const int k = threadIdx.x;
-        a.partials[(int64_t)blockIdx.x * PCL_INFO_ROW + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-    }
+    pcl_info_pass<FMT, WT>(a);
 }
 
+// (pcl_info_device.h restates the row sum, the chain rule, the factorisation and the record below as device functions for pcl_gn_step_kernel;
+// this kernel keeps its own text: built from those functions it computes the same and compiles to another instruction stream.)
 // One 256-thread block per pose.  Thread (part, k), part = tid / 32, adds entry k of its eighth of the chunks' rows in double, lowest chunk
 // first; the eight parts are then added pairwise in a fixed order (a 1M-point cloud has ~1000 rows per pose: one lane walking them all
 // is most of the call's time at B = 1).  Thread 0 then does the 6 x 6 algebra in double on matrices kept in LDS (runtime indices there

@@ -1,0 +1,203 @@
+// pcl_info_device.h — what pcl_info.hip (the information matrix at given poses) and pcl_gn.hip (the Levenberg-Marquardt chain on it) share:
+// the per-point pass that accumulates the 30 sums into one partial row per (chunk, pose), the fixed-order sum of a pose's rows in
+// double, the chain rule H = C A C^T, b = C v, the Cholesky factorisation on a power-of-two scaling and the info record / covariance.
+// Every function is inlined into its kernel: a kernel built from them has the arithmetic, and the bits, of every other.
+// Outside the loss-kernel hash: the four files it covers are included, never edited.
+#pragma once
+#include <math.h>
+
+#include "pcl_point_pass.h"
+#include "pcl_sample_device.h"
+
+#define PCL_INFO_MIN_STEPS 2               // a chunk walks at least two steps where the cloud has them (a one-off call: fewer, longer blocks)
+#define PCL_INFO_ROW 32                    // floats per partial row: A (21, k <= l row-major), sum w l a (6), S2, S1, M, 0, 0
+#define PCL_INFO_NSUM 30
+#define PCL_INFO_REC 48                    // floats per info record (include/piccolo_hip.h)
+
+struct PclInfoArgs {
+    PclPassArgs pass;
+    const float* weights;    // WT: one more plane of `stride` floats, packed order
+    float* partials;         // [nchunks][B][PCL_INFO_ROW]
+};
+
+// The whole per-point pass of a block: the pass of pcl_point_pass.h with the weighted gradient instance of pcl_sample2 under UNIT weight,
+// the 30 packed-fp32 accumulators, and the block's sums in a fixed order into partial row blockIdx.x.
+template <int FMT, bool WT>
+__device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a)
+{
+    __amdgpu_buffer_rsrc_t wrs;
+    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(a.pass.stride * 4), 0x00020000);
+
+    f2 hh[21], bb[6], s2 = F2(0.f), s1 = F2(0.f), mm = F2(0.f);
+#pragma unroll
+    for (int k = 0; k < 21; k++) hh[k] = F2(0.f);
+#pragma unroll
+    for (int k = 0; k < 6; k++) bb[k] = F2(0.f);
+
+    pcl_point_pass<FMT, true, false>(a.pass, a.pass.pano, 1, 0, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool) {
+        // acc: 0 l, 1 m, 2-4 g, 5-7 tau of this pair of points alone.  One factor w (a slot past n never counts, whatever its plane holds)
+        f2 w = F2(1.f), wl = acc[0], wm = acc[1], wa[6];
+        if constexpr (WT) {
+            w = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(wrs, j * 4, 0, 0));
+            w = (f2){valid0 ? w.x : 0.f, valid1 ? w.y : 0.f};
+            wl = w * acc[0]; wm = w * acc[1];
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) wa[k] = WT ? w * acc[2 + k] : acc[2 + k];
+        int q = 0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+#pragma unroll
+            for (int l = k; l < 6; l++, q++) hh[q] = pcl_fma2(wa[k], acc[2 + l], hh[q]);
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) bb[k] = pcl_fma2(wa[k], acc[0], bb[k]);
+        s2 = pcl_fma2(wl, acc[0], s2);
+        s1 += wl;
+        mm += wm;
+    });
+
+    // the block's sums in a fixed order: packed halves, the lanes of a wave (DPP), the four waves (LDS)
+    __shared__ float red[PCL_BLOCK / PCL_WAVE][PCL_INFO_ROW];
+    const int lane = threadIdx.x & (PCL_WAVE - 1), wave = threadIdx.x / PCL_WAVE;
+    auto put = [&](int k, f2 t) {
+        const float r = pcl_wave_sum(t.x + t.y);
+        if (lane == 0) red[wave][k] = r;
+    };
+#pragma unroll
+    for (int k = 0; k < 21; k++) put(k, hh[k]);
+#pragma unroll
+    for (int k = 0; k < 6; k++) put(21 + k, bb[k]);
+    put(27, s2); put(28, s1); put(29, mm);
+    if (lane == 0) { red[wave][30] = 0.f; red[wave][31] = 0.f; }
+    __syncthreads();
+    if (threadIdx.x < PCL_INFO_ROW) {
+        const int k = threadIdx.x;
+        a.partials[(int64_t)blockIdx.x * PCL_INFO_ROW + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+}
+
+// All 256 threads of a block.  Thread (part, k), part = tid / 32, adds entry k of its eighth of pose b's chunk rows in double, lowest chunk
+// first; the eight parts are then added pairwise in a fixed order into s[k] (a 1M-point cloud has ~1000 rows per pose: one lane walking
+// them all is most of a call's time at B = 1).  s is complete after the second barrier.
+__device__ __forceinline__ void pcl_info_row_sum(const float* __restrict__ partials, int nchunks, int B, int b, double (*parts)[PCL_INFO_ROW], double* s)
+{
+    const int k = threadIdx.x % PCL_INFO_ROW, part = threadIdx.x / PCL_INFO_ROW;
+    {
+        const int per = (nchunks + PCL_BLOCK / PCL_INFO_ROW - 1) / (PCL_BLOCK / PCL_INFO_ROW);
+        const int c0 = part * per, c1 = min(nchunks, c0 + per);
+        double t = 0.0;
+        for (int c = c0; c < c1; c++) t += (double)partials[((int64_t)c * B + b) * PCL_INFO_ROW + k];
+        parts[part][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < PCL_INFO_ROW)
+        s[k] = ((parts[0][k] + parts[1][k]) + (parts[2][k] + parts[3][k])) + ((parts[4][k] + parts[5][k]) + (parts[6][k] + parts[7][k]));
+    __syncthreads();
+}
+
+// One thread, matrices in LDS (runtime indices there cost nothing; in registers they would cost scratch).  H = C A C^T and b = C v in
+// double from the sums s at the pose (tp, rp):
+//   j = C a:  grad_t = -R^T g;  yaw = tau_z;  pitch = -sy tau_x + cy tau_y;  roll = cy cp tau_x + sy cp tau_y - sp tau_z
+// with R the fp32 matrix of pcl_rot_from_ypr and the sines / cosines of the fp32 angles in double, as pcl_finish_kernel takes them.
+// -> whether the pose, the 30 sums, H and b are all finite; S2, S1, M and sigma^2 = S2 / M
+__device__ __forceinline__ bool pcl_info_chain(const double* s, const float* tp, const float* rp, double (*A)[6], double (*C)[6], double (*T)[6],
+                                               double (*Hm)[6], double* bv, float* R, double& S2, double& S1, double& M, double& sigma2)
+{
+    double sy, cy, sp, cp;
+    sincos((double)rp[0], &sy, &cy);
+    sincos((double)rp[1], &sp, &cp);
+    pcl_rot_from_ypr(rp[0], rp[1], rp[2], R);
+    bool finite = true;
+    for (int i = 0; i < 3; i++) finite = finite && fabsf(tp[i]) <= 3.402823466e38f && fabsf(rp[i]) <= 3.402823466e38f;
+    for (int i = 0; i < 6; i++)
+        for (int m = 0; m < 6; m++) C[i][m] = 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int m = 0; m < 3; m++) C[i][m] = -(double)R[3 * m + i];
+    C[3][5] = 1.0;
+    C[4][3] = -sy; C[4][4] = cy;
+    C[5][3] = cy * cp; C[5][4] = sy * cp; C[5][5] = -sp;
+    int q = 0;
+    for (int i = 0; i < 6; i++)
+        for (int m = i; m < 6; m++, q++) { A[i][m] = s[q]; A[m][i] = s[q]; }
+    for (int i = 0; i < 6; i++)
+        for (int m = 0; m < 6; m++) {
+            double t = 0.0;
+            for (int r = 0; r < 6; r++) t += C[i][r] * A[r][m];
+            T[i][m] = t;
+        }
+    for (int i = 0; i < 6; i++) {
+        for (int m = i; m < 6; m++) {
+            double t = 0.0;
+            for (int r = 0; r < 6; r++) t += T[i][r] * C[m][r];
+            Hm[i][m] = t; Hm[m][i] = t;
+        }
+        double t = 0.0;
+        for (int r = 0; r < 6; r++) t += C[i][r] * s[21 + r];
+        bv[i] = t;
+    }
+    S2 = s[27]; S1 = s[28]; M = s[29]; sigma2 = S2 / M;
+    for (int i = 0; i < PCL_INFO_NSUM; i++) finite = finite && fabs(s[i]) <= 1.7976931348623157e308;
+    for (int i = 0; i < 6; i++) {
+        finite = finite && fabs(bv[i]) <= 1.7976931348623157e308;
+        for (int m = 0; m < 6; m++) finite = finite && fabs(Hm[i][m]) <= 1.7976931348623157e308;
+    }
+    return finite;
+}
+
+// Cholesky factor L of Hm scaled by an exact power of two, 2^-e (largest diagonal entry into [1/2, 1)), so that a matrix scaled by a power
+// of two has the same L bit for bit.  -> 0, or 2: a pivot <= 6 * 2^-52 * (the largest diagonal entry)
+__device__ __forceinline__ int pcl_info_factor(const double (*Hm)[6], double (*L)[6], int& e)
+{
+    int status = 0;
+    double maxd = 0.0;
+    for (int i = 0; i < 6; i++) maxd = fmax(maxd, Hm[i][i]);
+    if (!(maxd > 0.0)) status = 2;
+    else {
+        const double ms = frexp(maxd, &e), tol = 6.0 * 2.220446049250313e-16 * ms;
+        for (int i = 0; i < 6 && status == 0; i++) {
+            double d = ldexp(Hm[i][i], -e);
+            for (int r = 0; r < i; r++) d -= L[i][r] * L[i][r];
+            if (!(d > tol)) { status = 2; break; }
+            const double piv = sqrt(d);
+            L[i][i] = piv;
+            for (int m = i + 1; m < 6; m++) {
+                double t = ldexp(Hm[m][i], -e);
+                for (int r = 0; r < i; r++) t -= L[m][r] * L[i][r];
+                L[m][i] = t / piv;
+            }
+        }
+    }
+    return status;
+}
+
+// The 48-float info record o and (cv != nullptr) the covariance sigma^2 H^-1 from the factor L of H / 2^e, every output rounded once
+__device__ __forceinline__ void pcl_info_emit(const double (*Hm)[6], const double* bv, double M, double S1, double S2, double sigma2, int status, int e,
+                                              const double (*L)[6], double (*Li)[6], float* o, float* cv)
+{
+    for (int i = 0; i < 6; i++)
+        for (int m = 0; m < 6; m++) o[6 * i + m] = (float)Hm[i][m];
+    for (int i = 0; i < 6; i++) o[36 + i] = (float)bv[i];
+    o[42] = (float)M; o[43] = (float)S1; o[44] = (float)S2; o[45] = (float)sigma2; o[46] = (float)status; o[47] = 0.f;
+    if (!cv) return;
+    if (status != 0) {
+        for (int i = 0; i < 36; i++) cv[i] = __builtin_nanf("");
+        return;
+    }
+    // Li = L^-1 (lower triangular), (H / 2^e)^-1 = Li^T Li
+    for (int m = 0; m < 6; m++) {
+        Li[m][m] = 1.0 / L[m][m];
+        for (int i = m + 1; i < 6; i++) {
+            double t = 0.0;
+            for (int r = m; r < i; r++) t += L[i][r] * Li[r][m];
+            Li[i][m] = -t / L[i][i];
+        }
+    }
+    for (int i = 0; i < 6; i++)
+        for (int m = i; m < 6; m++) {
+            double t = 0.0;
+            for (int r = m; r < 6; r++) t += Li[r][i] * Li[r][m];
+            const float c = (float)ldexp(sigma2 * t, -e);
+            cv[6 * i + m] = c; cv[6 * m + i] = c;
+        }
+}

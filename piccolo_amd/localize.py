@@ -24,7 +24,7 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import (ROBUST_KEYS, _no_pose_covariance, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_robust,
+from .omniloc import (ROBUST_KEYS, _no_gn, _no_pose_covariance, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_robust,
                       omniloc_batch_rooms_images, robust_schedule)
 from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
@@ -51,7 +51,9 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
     branch returns every candidate and refuses the keys (ValueError), as omniloc_all does.  cfg.robust_iters / robust_kind / robust_k
     (omniloc.robust_schedule): the parallel branch runs omniloc_batch's robust chain; the non-parallel branch refuses them as well.
     cfg.pose_covariance (omniloc.pose_covariance_flag): the parallel branch returns (t, R, loss, cov), cov the (6, 6) covariance of
-    (t, yaw, pitch, roll) at the returned pose; the non-parallel branch refuses the key."""
+    (t, yaw, pitch, roll) at the returned pose; the non-parallel branch refuses the key.  cfg.gn_iters / gn_step_cap / gn_lambda
+    (omniloc.gn_schedule): the parallel branch passes them on to omniloc_batch, which polishes its winner; the non-parallel branch refuses
+    them."""
     summaries = scalar_summaries if scalar_summaries is not None else {}
     if getattr(cfg, "parallel", False):
         results = [omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)]
@@ -159,6 +161,7 @@ def localize_synthetic(cfg, writer=None, log_dir=None):
     Query images are sharded over the ranks of an initialised process group (one process per GPU); every rank
     returns the full (num_images, 16) result table [t(3), R(9), loss, t_err, r_err, seconds]."""
     _no_pose_covariance(cfg, "localize_synthetic")
+    _no_gn(cfg, "localize_synthetic")
     dev = ops.device()
     n = int(getattr(cfg, "num_points", 100_000))
     H, W = int(getattr(cfg, "pano_height", 256)), int(getattr(cfg, "pano_width", 512))
@@ -522,6 +525,7 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
     _no_pose_covariance(cfg, "localize_stanford")
+    _no_gn(cfg, "localize_stanford")
     room_search = getattr(cfg, "room_search", None)
     if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
         raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")
@@ -664,6 +668,7 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
     _no_pose_covariance(cfg, "localize_omniscenes")
+    _no_gn(cfg, "localize_omniscenes")
     _seed_all()
     dev = ops.device()
     split = getattr(cfg, "split_name", "extreme")

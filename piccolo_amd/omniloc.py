@@ -392,6 +392,57 @@ def _no_pose_covariance(cfg, who):
         raise ValueError("%s does not take cfg.pose_covariance (omniloc_batch and localize.refine_image's parallel branch do)" % who)
 
 
+# ------------------------------------------------------------------------------------------------ Levenberg-Marquardt polish
+# (not in the reference; build-defined, include/piccolo_hip.h): a damped Gauss-Newton chain on H and b, wholly on
+# the device.  It minimises the MEAN SQUARED residual sigma^2 = sum w m l^2 / sum w m — not the sampling loss sum w m l / sum w m the GD
+# chains minimise: same per-point terms, mask and weights, another objective.  cfg gn_iters (an int >= 1, absent by default), gn_step_cap
+# and gn_lambda (optional: the step cap in metres / radians and the starting damping): omniloc_batch polishes its winner.  One cloud, one
+# colour set, one image, no depth mask; nothing is claimed about real data.
+GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda")
+
+
+def gn_schedule(cfg):
+    """(iters, hyper dict for ops.gauss_newton_refine) under cfg.gn_iters / gn_step_cap / gn_lambda, or None when the keys are absent.
+    ValueError: gn_step_cap / gn_lambda without gn_iters, gn_iters not an int in 1 .. 1000, a cap or damping that is not a positive finite
+    number, cfg.depth_mask next to them.  Host only."""
+    iters, cap, lam = (_cfg(cfg, key, None) for key in GN_KEYS)
+    if iters is None and cap is None and lam is None:
+        return None
+    if iters is None:
+        raise ValueError("cfg.%s goes with cfg.gn_iters" % ("gn_step_cap" if cap is not None else "gn_lambda"))
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= ops.GN_MAX_ITERS:
+        raise ValueError("cfg.gn_iters %r: an int in 1 .. %d" % (iters, ops.GN_MAX_ITERS))
+    hyper = {}
+    for key, name, v in (("gn_step_cap", "step_cap", cap), ("gn_lambda", "lam0", lam)):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 < float(v) < float("inf")):
+            raise ValueError("cfg.%s %r: a positive finite number" % (key, v))
+        hyper[name] = float(v)
+    try:
+        ops.gn_hyper("cfg.gn_step_cap / cfg.gn_lambda", **hyper)          # (what float32 makes of them)
+    except ValueError as e:
+        raise ValueError("cfg.gn_step_cap / cfg.gn_lambda: %s" % e) from None
+    if bool(_cfg(cfg, "depth_mask", False)):
+        raise ValueError("cfg.gn_iters does not combine with cfg.depth_mask")
+    return iters, hyper
+
+
+def _no_gn(cfg, who):
+    """what does not polish its result refuses the keys, naming the first one it finds"""
+    for key in GN_KEYS:
+        if _cfg(cfg, key, None) is not None:
+            raise ValueError("%s does not take cfg.%s (omniloc_batch and localize.refine_image's parallel branch do)" % (who, key))
+
+
+def gauss_newton_refine(img, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, **hyper):
+    """ops.gauss_newton_refine from the poses trans / rot ((B, 3) tensors: translation; yaw, pitch, roll) over the cached packed cloud and
+    panorama: a dict of GPU tensors (trans, rot, sigma2_start, sigma2, lam, accepted, rejected, evaluations, status, H, b, stats, cov, and
+    trace when asked).  weights: (N,) per-point weights in the order of xyz's rows."""
+    return ops.gauss_newton_refine(packed_cloud(xyz, rgb, weights), packed_pano(img, n_points=xyz.shape[0]), trans, rot, iters=iters, trace=trace,
+                                   **hyper)
+
+
 def pose_information(img, xyz, rgb, trans, rot, weights=None):
     """(H (B,6,6), b (B,6), stats (B,5) = M, S1, S2, sigma^2, status, cov (B,6,6)) on the GPU at the poses trans / rot ((B, 3) tensors:
     translation; yaw, pitch, roll), over the cached packed cloud and panorama (ops.pose_information).  weights: (N,) per-point weights in
@@ -406,14 +457,31 @@ def pose_covariance(img, xyz, rgb, trans, rot, weights=None):
     return cov, stats[:, 3], stats[:, 4]
 
 
-def _winner_covariance(gd, cloud, pano, win):
-    """cov (1,6,6) on the GPU at the pose of the (1, 16) winners row `win` of the chain `gd` (an engine or a _PrunedChain), under the weight
-    plane its last forward ran with"""
+def _winner_cloud(gd, cloud):
+    """`cloud` under the weight plane the last forward of the chain `gd` (an engine or a _PrunedChain) ran with"""
     engine = gd.last if isinstance(gd, _PrunedChain) else gd
     plane = engine._run_weights()
     if plane is not None and plane is not cloud.weights:
         cloud = cloud.weighted_view(plane)
-    return ops.pose_information_at_winners(cloud, pano, win)[3]
+    return cloud
+
+
+def _winner_covariance(gd, cloud, pano, win):
+    """cov (1,6,6) on the GPU at the pose of the (1, 16) winners row `win` of the chain `gd` (an engine or a _PrunedChain), under the weight
+    plane its last forward ran with"""
+    return ops.pose_information_at_winners(_winner_cloud(gd, cloud), pano, win)[3]
+
+
+def _winner_polish(gd, cloud, pano, win, gn):
+    """The (1, 16) winners row `win` polished on the device under the chain's weights -> (row (13,) GPU: t, R, loss where the polish took a
+    step — accepted > 1 and status 0 or 3; R is rot_from_ypr of the polished angles, loss the sampling loss re-evaluated there by one
+    forward-only launch — else the chain's own three entries bit for bit; cov (1,6,6) GPU: the polish's own, at the returned pose)"""
+    cloud = _winner_cloud(gd, cloud)
+    res = ops.gauss_newton_refine_at_winners(cloud, pano, win, iters=gn[0], **gn[1])
+    R = ops.rot_from_ypr(res["rot"]).reshape(1, 9)
+    loss = ops.sampling_loss(cloud, pano, res["trans"], res["rot"], with_grad=False)[:, 0:1]
+    took = (res["accepted"] > 1) & ((res["status"] == 0) | (res["status"] == 3))
+    return torch.where(took.reshape(1, 1), torch.cat([res["trans"], R, loss], dim=1), win[:, 0:13])[0], res["cov"]
 
 
 class _PrunedChain:
@@ -595,6 +663,7 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     _no_prune(cfg, "omniloc")
     _no_robust(cfg, "omniloc")
     _no_pose_covariance(cfg, "omniloc")
+    _no_gn(cfg, "omniloc")
     vis = _cfg(cfg, "visualize", False)
     out_quantile = _cfg(cfg, "out_of_room_quantile", 0.05)
 
@@ -650,6 +719,7 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     _no_prune(cfg, "omniloc_all")
     _no_robust(cfg, "omniloc_all")
     _no_pose_covariance(cfg, "omniloc_all")
+    _no_gn(cfg, "omniloc_all")
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False, weights=weights).result()
     K = res.shape[0]
@@ -669,12 +739,21 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     WEIGHTED loss of the last forward, the return shapes are unchanged.  Not with weights=, cfg.depth_mask or the prune keys (ValueError).
     cfg.pose_covariance (a bool; not in the reference): a fourth entry, cov (6, 6) on the CPU — sigma^2 H^-1 of (t, yaw, pitch, roll) at the
     returned pose (pose_information), under weights= or the robust chain's last plane; the first three entries are those of the run
-    without the key, bit for bit.  With the prune keys too; not with cfg.depth_mask or a list of colour sets (ValueError)."""
+    without the key, bit for bit.  With the prune keys too; not with cfg.depth_mask or a list of colour sets (ValueError).
+    cfg.gn_iters / gn_step_cap / gn_lambda (gn_schedule; not in the reference): after the chain its winner is polished on the device by
+    gn_iters Levenberg-Marquardt iterations on the MEAN SQUARED residual (gauss_newton_refine: not the sampling loss), under weights= or the
+    robust chain's last plane.  Where the polish accepted a step (accepted > 1, status 0 or 3) t is the polished translation, R
+    rot_from_ypr of the polished angles and loss the sampling loss re-evaluated at that pose; otherwise the three entries are the
+    chain's own, bit for bit.  With cfg.pose_covariance the fourth entry is the polish's own cov at its returned pose.  The written-back
+    leaves stay the chain's.  With the prune keys too; not with cfg.depth_mask or a list of colour sets (ValueError)."""
     if robust_schedule(cfg) is not None and weights is not None:          # (and the schedule's own refusals, before a device is touched)
         raise ValueError("cfg.robust_iters does not combine with weights= (the chain makes its own)")
     want_cov = pose_covariance_flag(cfg)
     if want_cov and isinstance(rgb, (list, tuple)):
         raise ValueError("cfg.pose_covariance: one colour set only")
+    gn = gn_schedule(cfg)
+    if gn is not None and isinstance(rgb, (list, tuple)):
+        raise ValueError("cfg.gn_iters: one colour set only")
     if strict_reference_asserts:
         assert cfg.num_input > 1
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
@@ -685,8 +764,13 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     bt, br, after = _leaf_buffers(input_trans, input_rot, gd.B)
     win = gd.winner(1, bt, br)
     # (the covariance reads the winners row on the device and changes nothing the first three entries are made from)
-    cov = _winner_covariance(gd, packed_cloud(xyz, rgb, weights), pano, win) if want_cov else None
-    out = win[0].cpu()
+    if gn is not None:
+        # (the polish starts from the winners row on the device; its 13 floats travel with the one D2H copy's worth of the row)
+        row, cov = _winner_polish(gd, packed_cloud(xyz, rgb, weights), pano, win, gn)
+        out = row.cpu()
+    else:
+        cov = _winner_covariance(gd, packed_cloud(xyz, rgb, weights), pano, win) if want_cov else None
+        out = win[0].cpu()
     after()
     ret = [out[0:3].reshape(3, 1).clone(), out[3:12].reshape(3, 3).clone(), out[12].clone()]
     if want_cov:
@@ -713,6 +797,7 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image."""
     _no_robust(cfg, "omniloc_batch_images")
     _no_pose_covariance(cfg, "omniloc_batch_images")
+    _no_gn(cfg, "omniloc_batch_images")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     I = len(imgs)
@@ -770,6 +855,7 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
     robust_iters (and robust_schedule's refusals: the depth mask, the prune keys), cfg.visualize, lists of different lengths.  One image is
     omniloc_batch."""
     _no_pose_covariance(cfg, "omniloc_batch_images_robust")
+    _no_gn(cfg, "omniloc_batch_images_robust")
     robust = robust_schedule(cfg)
     if robust is None:
         raise ValueError("omniloc_batch_images_robust needs cfg.robust_iters (omniloc_batch_images runs the plain chain)")
@@ -886,6 +972,7 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     go in a chain per tolerance."""
     _no_robust(cfg, "omniloc_batch_rooms")
     _no_pose_covariance(cfg, "omniloc_batch_rooms")
+    _no_gn(cfg, "omniloc_batch_rooms")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R = len(rooms)
@@ -961,6 +1048,7 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     its plan of all the images' candidates, so equal to the single calls up to the summation order of the partial sums, as there)."""
     _no_robust(cfg, "omniloc_batch_rooms_images")
     _no_pose_covariance(cfg, "omniloc_batch_rooms_images")
+    _no_gn(cfg, "omniloc_batch_rooms_images")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R, I = len(rooms), len(imgs)

@@ -515,6 +515,74 @@ def pose_information_at_winners(cloud, pano, winners):
     return _pose_information(cloud, pano, *_winner_poses(winners, "pose_information_at_winners"), winners.device)
 
 
+GN_HYPER = dict(lam0=1e-3, lam_up=10.0, lam_down=0.1, lam_min=1e-9, lam_max=1e9, step_cap=0.1, tol=0.0)
+GN_MAX_ITERS = 1000
+
+
+def gn_hyper(who="gauss_newton_refine", **hyper):
+    """_lib.GnHyper of the defaults GN_HYPER with the given values in their place.  ValueError: an unknown name, what pcl_gn_refine
+    refuses (a value that is not finite, lam0 <= 0, lam_up <= 1, lam_down outside (0, 1], lam_min > lam_max, step_cap <= 0, tol < 0)."""
+    import math
+    h = dict(GN_HYPER)
+    for key, v in hyper.items():
+        if key not in h:
+            raise ValueError("%s: unknown hyper-parameter %r (one of %s)" % (who, key, sorted(h)))
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError("%s: %s = %r is not a finite number" % (who, key, v))
+        h[key] = float(v)
+    g = _lib.GnHyper(**h)
+    if not (g.lam0 > 0 and g.lam_up > 1 and 0 < g.lam_down <= 1 and g.lam_min <= g.lam_max and g.step_cap > 0 and g.tol >= 0
+            and all(math.isfinite(getattr(g, key)) for key in h)):
+        raise ValueError("%s: hyper-parameters out of range: %r (lam0 > 0, lam_up > 1, 0 < lam_down <= 1, lam_min <= lam_max, step_cap > 0, "
+                         "tol >= 0, all finite in float32)" % (who, h))
+    return g
+
+
+def _gauss_newton(who, cloud, pano, trans_ptr, rot_ptr, stride, B, dev, iters, trace, hyper):
+    lib = _lib.load()
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= GN_MAX_ITERS:
+        raise ValueError("%s: iters %r: an int in 0 .. %d" % (who, iters, GN_MAX_ITERS))
+    hp = gn_hyper(who, **hyper)
+    nws, nst = lib.pcl_gn_workspace_bytes(cloud.n, B), lib.pcl_gn_state_bytes(B)
+    if nws == 0 or nst == 0:
+        raise ValueError("%s: %d points x %d poses are out of range" % (who, cloud.n, B))
+    out = torch.empty(B, 16, dtype=F32, device=dev)
+    info = torch.empty(B, 48, dtype=F32, device=dev)
+    cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
+    tr = torch.empty(iters + 1, B, 16, dtype=F32, device=dev) if trace else None
+    ws, st = _bytes(nws), _bytes(nst)
+    _lib.check(lib.pcl_gn_refine(_ptr(cloud.data), _ptr(cloud.weights), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr, stride, B,
+                                 ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()), "pcl_gn_refine")
+    ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
+               evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(B, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
+    if trace:
+        ret["trace"] = tr
+    return ret
+
+
+def gauss_newton_refine(cloud, pano, trans, rot, iters=10, trace=False, **hyper):
+    """A Levenberg-Marquardt polish of the poses (trans[b], rot[b]) on the device (pcl_gn_refine; build-defined, include/piccolo_hip.h): it
+    minimises the MEAN SQUARED residual sigma^2 = sum w m l^2 / sum w m over theta = (t, yaw, pitch, roll; metres, radians) with the H and b
+    of pose_information — NOT the sampling loss sum w m l / sum w m; the two share their per-point terms, mask and weights and are
+    different objectives.  -> dict of float32 GPU tensors: trans (B,3), rot (B,3) the best accepted pose; sigma2_start, sigma2 (B,): F at the
+    caller's pose and at the returned one; lam the final damping; accepted, rejected, evaluations, status (B,) (0 all iters + 1
+    evaluations ran, 1 the first had nothing kept or something not finite — the caller's pose comes back —, 2 the damped matrix was
+    not positive definite, 3 converged); H, b, stats, cov: pose_information at the returned pose, bit for bit; with trace=True `trace`
+    (iters + 1, B, 16): per evaluation theta_try (6), F, accepted, lambda after the decision, M.  hyper: lam0, lam_up, lam_down, lam_min,
+    lam_max, step_cap, tol (GN_HYPER).  A weighted cloud contributes its weights.  ValueError: a cloud of colour sets, a panorama in one of
+    the trim launch's texel layouts, iters outside 0 .. 1000, hyper-parameters out of range."""
+    _residual_cloud(cloud, pano, "gauss_newton_refine")
+    trans, rot = _pose_rows(trans, rot)
+    return _gauss_newton("gauss_newton_refine", cloud, pano, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace, hyper)
+
+
+def gauss_newton_refine_at_winners(cloud, pano, winners, iters=10, trace=False, **hyper):
+    """gauss_newton_refine from the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses)."""
+    _residual_cloud(cloud, pano, "gauss_newton_refine_at_winners")
+    return _gauss_newton("gauss_newton_refine_at_winners", cloud, pano, *_winner_poses(winners, "gauss_newton_refine_at_winners"), winners.device,
+                         iters, trace, hyper)
+
+
 def point_residuals_images(cloud, panos, trans, rot, packed=False):
     """(I, N) float GPU tensor: row i is point_residuals of pose (trans[i], rot[i]) against panos[i] — and, for a cloud of I colour sets
     (Cloud.with_color_sets), colour set i — in ONE launch (pcl_point_residuals_images; the panorama addresses are kernel arguments).  Row i
