@@ -302,6 +302,14 @@ typedef struct pcl_gd_hyper {
                         /* against them).  0: pcl_depth_default's choice with a default grid, 1 with a given grid.                           */
     int32_t fuse;          /* 0: pcl_gd_plan's rule (ONE launch per iteration when every block of the launch is resident at once).     */
                            /* < 0: never — always loss launch + epilogue launch.  Same bits either way (tests compare the two forms).  */
+                           /* A chain of two launches per iteration without the depth mask, enqueued on a stream that is not capturing, */
+                           /* runs as TWO half-chains over the two halves of its pose groups — the caller's stream and a side stream of */
+                           /* the library, forked and joined by events inside the call: no host synchronisation, and whatever follows   */
+                           /* on the caller's stream sees the finished state — when each half has at least 896 loss blocks (7/8 of what */
+                           /* the GPU holds at once).  Every group runs under the whole chain's plan: same bits, split or not.  0 and   */
+                           /* -1: that rule;                                                                                            */
+                           /* -2: -1 and never split; -3: -1 and split whenever there are two pose groups (tests reach the path at      */
+                           /* small sizes).  (pcl_gd_run, _run_weighted, _run_weight_sets; the rooms and depth chains never split.)     */
     int32_t images;        /* number of query images whose candidates share this launch chain (pcl_gd_set_panos / _set_pano_groups;   */
                            /* image i's candidates a contiguous range).  0 / 1: one image.  A hint for the block -> XCD mapping only    */
                            /* (with several panoramas every XCD takes a range of pose groups, i.e. of images, over the whole cloud      */

@@ -8,6 +8,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
+
 #include "pcl_gd_device.h"
 #include "pcl_gd_state.h"
 #include "pcl_host.h"
@@ -353,6 +355,65 @@ static int gd_chain_loop(void* state, int B, bool fused, const float* box, const
     return 0;
 }
 
+// ---- two half-chains on two streams
+// The candidates of a chain are independent until the caller's argmin, so a chain of two launches per iteration may run as TWO chains
+// over the pose groups [0, gA) and [gA, ngroups), each under the plan of the whole chain (pcl_launch_loss's group range: the same chunks,
+// the same partials rows, the same bits), half A on the caller's stream and half B on a side stream, B half a launch behind A: each
+// half's tail, epilogue, kernel boundaries and ramp then run under the other half's bulk.  No launch waits for another inside the loop.
+// The side stream (non-blocking: a caller on the legacy default stream is not serialised with it) and the three events exist once per
+// device, created on first use by a caller whose stream is not capturing, under a relaxed capture mode so that a capture another
+// thread has open is not invalidated.  `mu` is held for the whole enqueue of a split chain: two host threads take turns, so an event
+// recorded by one is never re-recorded by the other between its record and its wait.
+#define PCL_GD_MAX_DEVICES 64
+struct GdSide {
+    std::mutex mu;
+    bool ready = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t fork = nullptr, stagger = nullptr, join = nullptr;
+};
+static GdSide gd_sides[PCL_GD_MAX_DEVICES];
+
+// the current device's side stream with `mu` LOCKED, or null (then nothing is locked): the caller's stream is capturing or cannot be
+// asked, the device is out of range, or the stream and events cannot be created — the chain then runs on the caller's stream alone
+static GdSide* gd_side_acquire(hipStream_t s)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusActive;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PCL_GD_MAX_DEVICES) return nullptr;
+    GdSide* sd = &gd_sides[dev];
+    sd->mu.lock();
+    if (!sd->ready) {
+        hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+        bool ok = hipThreadExchangeStreamCaptureMode(&mode) == hipSuccess;
+        if (ok) {
+            ok = hipStreamCreateWithFlags(&sd->stream, hipStreamNonBlocking) == hipSuccess &&
+                 hipEventCreateWithFlags(&sd->fork, hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&sd->stagger, hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&sd->join, hipEventDisableTiming) == hipSuccess;
+            (void)hipThreadExchangeStreamCaptureMode(&mode);
+        }
+        if (!ok) {
+            (void)hipGetLastError();
+            if (sd->fork) (void)hipEventDestroy(sd->fork);
+            if (sd->stagger) (void)hipEventDestroy(sd->stagger);
+            if (sd->join) (void)hipEventDestroy(sd->join);
+            if (sd->stream) (void)hipStreamDestroy(sd->stream);
+            sd->stream = nullptr; sd->fork = sd->stagger = sd->join = nullptr;
+            sd->mu.unlock();
+            return nullptr;
+        }
+        sd->ready = true;
+    }
+    return sd;
+}
+
+// smallest half (in loss blocks) that is split by default.  Measured, eager chains of 100 iterations, one stream against two:
+// halves of 528 blocks -5.6 %, 656 +8.8 %, 672 +0.0 %, 896 +16.5 %, 1312 +25.9 %, 1344 +21.1 %, 2048 +4 to +12 % — below about two thirds of
+// a residency (256 CUs x 4 resident 256-thread blocks = 1024) the two halves of an iteration fit the GPU together, there is no tail to hide
+// and the second stream's launches only cost; 896 is the smallest half measured that clearly gains.
+static int gd_split_min_blocks() { return PCL_KNOB(GD_SPLIT_BLOCKS, 896); }
+
 // pcl_gd_run, and with `weights` (the cloud's weight plane) pcl_gd_run_weighted: the same plan, workspace and chain, the weighted loss launch.
 // wsets >= 1 (pcl_gd_run_weight_sets): the B candidates are wsets images of B / wsets and the chain runs the single-image plan for all of
 // them — its chunks, poses per block and partials — with `weights` null (the plain or colour-set loss launch under that plan) or wsets planes.
@@ -393,7 +454,34 @@ static int gd_run(const float* cloud, const float* weights, int wsets, int64_t n
     //  never fused — the form the parity tests compare the fused one with)
     const bool fused = !depth_on && pcl_plan_nblocks(n, B, psets) <= gd_fuse_limit(hyper_host);
     const int G = pcl_plan_G(n, B, psets);
-    return gd_chain_loop(
+    const int ngroups = B / G;
+    // two half-chains (above): pose groups [0, gA) on the caller's stream, [gA, ngroups) on the side stream.  pcl_gd_hyper.fuse -2: never;
+    // -3: whenever there are two groups; else when the smaller half has gd_split_min_blocks() loss blocks.  A capturing caller keeps the one-stream chain.
+    const int gA = ngroups / 2;
+    GdSide* side = nullptr;
+    if (!fused && !depth_on && num_iter > 0 && ngroups >= 2 && hyper_host->fuse != -2 &&
+        (hyper_host->fuse == -3 || (int64_t)gA * nchunks >= gd_split_min_blocks()))
+        side = gd_side_acquire(s);
+    if (side) {
+        // fork: the side stream starts behind everything the caller has enqueued
+        hipError_t e = hipEventRecord(side->fork, s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(side->stream, side->fork, 0);
+        if (e != hipSuccess) { side->mu.unlock(); return (int)e; }
+    }
+    auto loss_range = [&](int it, const PclPoseRec* recs, float* partials, hipStream_t st, int g0, int g1) {
+        return pcl_launch_loss(cloud, n, pano, pano_format, H, W, recs, B, true, nullptr, partials, st, (flip_env ? (it & 1) : 0) | xcd_bit, nullptr, nullptr,
+                               sets, weights, wsets, g0, g1);
+    };
+    auto epilogue_range = [&](const float* partials, float* loss_out, hipStream_t st, int g0, int g1) {
+        pcl_with_G<4>(G, [&](auto g) {
+            constexpr int GG = decltype(g)::value;
+            const int64_t p0 = (int64_t)g0 * GG;
+            hipLaunchKernelGGL(pcl_gd_epilogue_kernel<GG>, dim3(g1 - g0), dim3(PCL_GD_THREADS), 0, st, partials + (int64_t)g0 * nchunks * GG * PCL_NACC, nchunks,
+                               gd_poses(state, B, 0) + p0, gd_recs(state, B, 0) + p0, gd_poses(state, B, 0) + p0, gd_recs(state, B, 0) + p0, box,
+                               hyper_host->factor, (int)hyper_host->patience, (int)hyper_host->mode, loss_out ? loss_out + p0 : nullptr);
+        });
+    };
+    int rc = gd_chain_loop(
         state, B, fused, box, hyper_host, num_iter, loss_history, w.partials, (PclTimer*)timer, s,
         [&](int it) {
             if (!depth_on) return 0;
@@ -405,10 +493,27 @@ static int gd_run(const float* cloud, const float* weights, int wsets, int64_t n
             return pcl_launch_zbuffers(cloud, n, gd_recs(state, B), B, look.grid, zstride, w.zbuf[set], it == 0 || !pingpong_env, s);
         },
         [&](int it, const PclPoseRec* recs, float* partials, const PclFuseArgs* fuse) {
-            return pcl_launch_loss(cloud, n, pano, pano_format, H, W, recs, B, true, nullptr, partials, s, (flip_env ? (it & 1) : 0) | xcd_bit, fuse,
-                                   depth_on ? &look : nullptr, sets, weights, wsets);
+            if (!side)
+                return pcl_launch_loss(cloud, n, pano, pano_format, H, W, recs, B, true, nullptr, partials, s, (flip_env ? (it & 1) : 0) | xcd_bit, fuse,
+                                       depth_on ? &look : nullptr, sets, weights, wsets);
+            // half A (what the timer brackets), then half B.  The stagger: A's first launch goes out as two, and B's first launch waits for
+            // the first of them — B runs half a launch behind A from there on
+            int rcl;
+            if (it == 0 && gA >= 2) {
+                if ((rcl = loss_range(it, recs, partials, s, 0, gA / 2))) return rcl;
+                hipError_t e = hipEventRecord(side->stagger, s);
+                if (e == hipSuccess) e = hipStreamWaitEvent(side->stream, side->stagger, 0);
+                if (e != hipSuccess) return (int)e;
+                if ((rcl = loss_range(it, recs, partials, s, gA / 2, gA))) return rcl;
+            } else if ((rcl = loss_range(it, recs, partials, s, 0, gA))) return rcl;
+            return loss_range(it, recs, partials, side->stream, gA, ngroups);
         },
         [&](int copy_in, const float* partials, float* loss_out) {
+            if (side) {
+                epilogue_range(partials, loss_out, s, 0, gA);
+                epilogue_range(partials, loss_out, side->stream, gA, ngroups);
+                return;
+            }
             pcl_with_G<4>(G, [&](auto g) {
                 constexpr int GG = decltype(g)::value;
                 hipLaunchKernelGGL(pcl_gd_epilogue_kernel<GG>, dim3(B / GG), dim3(PCL_GD_THREADS), 0, s, partials, nchunks, gd_poses(state, B, copy_in),
@@ -416,6 +521,14 @@ static int gd_run(const float* cloud, const float* weights, int wsets, int64_t n
                                    (int)hyper_host->patience, (int)hyper_host->mode, loss_out);
             });
         });
+    if (side) {
+        // join (after an error too: the side stream's work stays ordered before whatever the caller enqueues next)
+        hipError_t e = hipEventRecord(side->join, side->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, side->join, 0);
+        side->mu.unlock();
+        if (!rc && e != hipSuccess) rc = (int)e;
+    }
+    return rc;
 }
 
 extern "C" int pcl_gd_run(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, void* state, int B,

@@ -20,7 +20,7 @@ void pcl_plan_room_images(int64_t n, int per_image, int nimages, int* G, int* ng
 void pcl_plan_for_groups(int64_t n, int ngroups, int* nchunks, int* seg_len, int* steps_base, int* steps_rem);
 int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses, int B, bool grad,
                     const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse, const PclDepthLook* depth,
-                    int color_sets = 1, const float* weights = nullptr, int wsets = 0);
+                    int color_sets = 1, const float* weights = nullptr, int wsets = 0, int g0 = 0, int g1 = -1);
 // a weighted launch runs the plan of (n, B) unchanged and has instances for one and two poses per block only (four exist through the
 // experiments build's PCL_G): asked by the weighted entry points before they enqueue anything, and by pcl_launch_loss itself
 static inline bool pcl_weighted_plan_ok(int64_t n, int B) { return n > 0 && n <= PCL_MAX_POINTS && B > 0 && pcl_plan_G(n, B) <= 2; }

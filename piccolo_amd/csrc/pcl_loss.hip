@@ -698,9 +698,13 @@ int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_
 // `wsets` >= 1 (pcl_gd_run_weight_sets): the poses are wsets images of B / wsets candidates whose records name their image in `cset`, and
 // the launch runs the single-image plan (pcl_plan_sets over wsets) whatever it evaluates: with `weights` = wsets planes the weight-set
 // instances (colour sets admitted, color_sets == wsets), without them the plain or colour-set instances under that plan.  Gradient pass only.
+// `g0`, `g1` (g1 >= 0; pcl_gd_run's half-chains): the launch covers the pose groups [g0, g1) of the B poses only, under the plan of all B —
+// its chunks, poses per block and steps per chunk — with `poses` and `partials` still the bases of all B: the blocks write exactly the
+// partials rows (group-major, pcl_partials_row) the whole launch would write, with the same bits.  Only the XCD runs are chosen for the
+// sub-launch (scheduling).  Gradient pass without `fuse`, `visible` or `depth`.
 int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W, const PclPoseRec* poses,
                     int B, bool grad, const uint8_t* visible, float* partials, hipStream_t s, int flip, const PclFuseArgs* fuse,
-                    const PclDepthLook* depth, int color_sets, const float* weights, int wsets)
+                    const PclDepthLook* depth, int color_sets, const float* weights, int wsets, int g0, int g1)
 {
     PclLossArgs a;
     int rc = pcl_loss_args(&a, pano, pano_format, H, W, poses, B, partials, flip, color_sets);
@@ -710,7 +714,15 @@ int pcl_launch_loss(const float* cloud, int64_t n, const void* pano, int pano_fo
     if (sets && (B % color_sets || !grad || visible || depth || pcl_cloud_sets_bytes(n, color_sets) == 0)) return PCL_EINVAL;
     if (wsets > 0 && (B % wsets || !grad || visible || depth || (sets && color_sets != wsets))) return PCL_EINVAL;
     if (weights && (visible || depth || (wsets > 0 ? pcl_plan_G(n, B, wsets) > 2 : sets || !pcl_weighted_plan_ok(n, B)))) return PCL_EINVAL;
-    const PclPlan p = pcl_plan_sets(n, B, wsets > 0 ? wsets : color_sets);
+    PclPlan p = pcl_plan_sets(n, B, wsets > 0 ? wsets : color_sets);
+    if (g1 >= 0) {
+        if (g0 < 0 || g1 <= g0 || g1 > p.ngroups || !grad || fuse || visible || depth) return PCL_EINVAL;
+        a.poses = poses + (int64_t)g0 * p.G;
+        a.partials = partials + (int64_t)g0 * p.nchunks * p.G * PCL_NACC;          // pcl_partials_row(nchunks, G, g0, 0, 0)
+        a.B = (g1 - g0) * p.G;
+        p.ngroups = g1 - g0;
+        p.seg_len = pcl_xcd_seg_len(p.nchunks, (int64_t)p.nchunks * p.ngroups);
+    }
     const int nblk = p.nchunks * p.ngroups;
     a.cloud = cloud; a.n = n; a.stride = pcl_cloud_stride(n);
     a.visible = visible;

@@ -1011,10 +1011,19 @@ def _checked(name, *args):
 
 def _gd_hyper(lr, patience, factor, batch_mode, fuse, depth=None, color_sets=0):
     """The hyper-parameter struct of every GD engine.  depth: None, or the mask's (depth_h, depth_w, tau, occluder stride); fuse False: always
-    the two-launch form."""
+    the two-launch form; a negative int: pcl_gd_hyper.fuse as it is (-2: two launches on the caller's stream alone, -3: two half-chains
+    on two streams whenever there are two pose groups — what the tests of the split compare)."""
     dh, dw, tau, st = depth or (0, 0, 0.0, 0)
+    if fuse is None or fuse is True:
+        fz = 0
+    elif fuse is False:
+        fz = -1
+    elif isinstance(fuse, int) and -3 <= fuse <= 0:
+        fz = int(fuse)
+    else:
+        raise ValueError("fuse: None, True, False or pcl_gd_hyper.fuse's 0, -1, -2, -3, not %r" % (fuse,))
     return _lib.GdHyper(float(lr), float(factor), int(patience), _lib.GD_BATCH if batch_mode else _lib.GD_SEQUENTIAL, 1 if depth else 0, float(tau),
-                        int(dh), int(dw), int(st), -1 if fuse is False else 0, 0, int(color_sets))
+                        int(dh), int(dw), int(st), fz, 0, int(color_sets))
 
 
 class _GdEngine:
