@@ -24,7 +24,7 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import (ROBUST_KEYS, _no_gn, _no_pose_covariance, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_robust,
+from .omniloc import (ROBUST_KEYS, _is_int, _refuse, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_robust,
                       omniloc_batch_rooms_images, robust_schedule)
 from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
@@ -66,12 +66,12 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
 
 def _check_robust_cfg(cfg):
     """Configuration-time refusal of the robust keys where the harness would refine through an entry point that does not take them: several
-    images per launch chain and the room searches (omniloc._no_robust is what those entry points would raise, after the first cloud is read).
+    images per launch chain and the room searches (omniloc._refuse is what those entry points would raise, after the first cloud is read).
     A robust run groups its images with its own key, cfg.robust_images_per_launch (omniloc_batch_images_robust): an int >= 1 that needs
     cfg.robust_iters and cfg.parallel."""
     rpl = getattr(cfg, "robust_images_per_launch", None)
     if rpl is not None:
-        if isinstance(rpl, bool) or not isinstance(rpl, int) or rpl < 1:
+        if not _is_int(rpl) or rpl < 1:
             raise ValueError("cfg.robust_images_per_launch %r: an int >= 1" % (rpl,))
         if getattr(cfg, "robust_iters", None) is None:
             raise ValueError("cfg.robust_images_per_launch goes with cfg.robust_iters (images_per_launch groups a plain run)")
@@ -160,8 +160,7 @@ def localize_synthetic(cfg, writer=None, log_dir=None):
 
     Query images are sharded over the ranks of an initialised process group (one process per GPU); every rank
     returns the full (num_images, 16) result table [t(3), R(9), loss, t_err, r_err, seconds]."""
-    _no_pose_covariance(cfg, "localize_synthetic")
-    _no_gn(cfg, "localize_synthetic")
+    _refuse(cfg, "localize_synthetic", "pose_covariance", "gn")
     dev = ops.device()
     n = int(getattr(cfg, "num_points", 100_000))
     H, W = int(getattr(cfg, "pano_height", 256)), int(getattr(cfg, "pano_width", 512))
@@ -524,8 +523,7 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms)."""
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
-    _no_pose_covariance(cfg, "localize_stanford")
-    _no_gn(cfg, "localize_stanford")
+    _refuse(cfg, "localize_stanford", "pose_covariance", "gn")
     room_search = getattr(cfg, "room_search", None)
     if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
         raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")
@@ -667,8 +665,7 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
     _run_dataset (_localize_known_room)."""
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
-    _no_pose_covariance(cfg, "localize_omniscenes")
-    _no_gn(cfg, "localize_omniscenes")
+    _refuse(cfg, "localize_omniscenes", "pose_covariance", "gn")
     _seed_all()
     dev = ops.device()
     split = getattr(cfg, "split_name", "extreme")

@@ -33,6 +33,7 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
 """
 import weakref
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -190,8 +191,85 @@ def packed_pano(img, many_poses=False, n_points=None):
     return _cached("pano_" + fmt, (img,), make)
 
 
+def _chain_panos(imgs, n_points, direct=False):
+    """The packed panoramas of the images of ONE chain, in one texel format: the one packed_pano gives a refinement of n_points points, float4
+    for all when the images do not agree (a launch needs ONE format, and float4 holds any image).  direct: packed past the cache, at
+    refine_texels' format for images tagged as k/255 levels (omniloc_batch_images beyond eight images: more than the cache is meant to hold)."""
+    if direct:
+        fmt = ops.refine_texels(n_points, imgs[0].shape[0], imgs[0].shape[1])
+        panos = [ops.Pano(im, fmt=fmt if ops._known_levels(im) else "auto") for im in imgs]
+    else:
+        panos = [packed_pano(im, n_points=n_points) for im in imgs]
+    if len({p.fmt for p in panos}) > 1:
+        panos = [ops.Pano(im, fmt="f32") for im in imgs]
+    return panos
+
+
+def _over_color_sets(n, I, part, rooms=None):
+    """I images with per-image colour sets of an n-point cloud (the largest room's) in color_set_groups' groups: None when one group holds them
+    all, else part(i0, i1) of every group [i0, i1) concatenated, image after image — per room when part returns `rooms` lists"""
+    sizes = color_set_groups(n, I)
+    if len(sizes) == 1:
+        return None
+    out, i0 = [] if rooms is None else [[] for _ in range(rooms)], 0
+    for m in sizes:
+        some = part(i0, i0 + m)
+        if rooms is None:
+            out += some
+        else:
+            for r in range(rooms):
+                out[r] += some[r]
+        i0 += m
+    return out
+
+
 def _cfg(cfg, key, default):
     return getattr(cfg, key, default)
+
+
+# The cfg keys that are not the reference's, by family: (its keys, how a refusal names them — None: the first key it finds, what does take
+# them).  An entry point refuses the families it does not take with one _refuse call; the schedules below validate the ones it does.
+ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
+GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda")
+_EXTENSIONS = {
+    "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
+    "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust and localize.refine_image's parallel branch do"),
+    "pose_covariance": (("pose_covariance",), None, "omniloc_batch and localize.refine_image's parallel branch do"),
+    "gn": (GN_KEYS, None, "omniloc_batch and localize.refine_image's parallel branch do"),
+}
+
+
+def _refuse(cfg, who, *families):
+    """`who` returns every candidate, records frames, or runs a chain without the robust plane, the covariance or the polish: it refuses the
+    keys of those `families`, in the order given"""
+    for keys, named, takers in map(_EXTENSIONS.get, families):
+        for key in keys:
+            if _cfg(cfg, key, None) is not None:
+                raise ValueError("%s does not take cfg.%s (%s)" % (who, named or key, takers))
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _int_list(cfg, name):
+    """cfg.`name`, an int or a list of ints, as a list"""
+    v = _cfg(cfg, name, None)
+    v = list(v) if isinstance(v, (list, tuple)) else [v]
+    if not v or not all(_is_int(x) for x in v):
+        raise ValueError("cfg.%s: an int or a list of ints, got %r" % (name, v))
+    return v
+
+
+def _inside_num_iter(iters, name, num_iter):
+    if any(not 0 < i < num_iter for i in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
+        raise ValueError("cfg.%s %r: strictly increasing iteration counts inside (0, %d)" % (name, iters, num_iter))
+
+
+def _positive(v, name):
+    if not isinstance(v, (int, float)) or isinstance(v, bool) or not (0.0 < float(v) < float("inf")):
+        raise ValueError("cfg.%s %r: a positive finite number" % (name, v))
+    return float(v)
 
 
 def _rot_matrix(ypr):
@@ -264,12 +342,6 @@ def _cached_engine(kind, xyzs, sub, make, clouds, boxes):
 # prune_iters[j] - 1) and the chain goes on with them alone: pcl_gd_prune hands their complete optimiser state to a smaller engine on the
 # device, so nothing is re-initialised and nothing waits for the host.  The reference refines every one of its num_input candidates to
 # the end; which schedule still finds its winner is the user's choice (DESIGN.md §4.6f has the CPU evidence for 16 -> 8 -> 4).
-def _no_prune(cfg, who):
-    """what returns every candidate, or records frames of one, does not prune"""
-    if _cfg(cfg, "prune_iters", None) is not None or _cfg(cfg, "prune_keep", None) is not None:
-        raise ValueError("%s does not take cfg.prune_iters / cfg.prune_keep (the batch refinements do)" % who)
-
-
 def prune_schedule(cfg, per_image):
     """The segments [(iterations, candidates per image), ...] of a refinement of `per_image` candidates per image under cfg.prune_iters /
     cfg.prune_keep (an int each, or lists of equal length), or None when the keys are absent.  prune_iters = 20, 40 with prune_keep = 16, 8
@@ -281,18 +353,11 @@ def prune_schedule(cfg, per_image):
         return None
     if iters is None or keep is None:
         raise ValueError("cfg.prune_iters and cfg.prune_keep go together")
-
-    def ints(v, name):
-        v = list(v) if isinstance(v, (list, tuple)) else [v]
-        if not v or any(isinstance(x, bool) or not isinstance(x, int) for x in v):
-            raise ValueError("cfg.%s: an int or a list of ints, got %r" % (name, v))
-        return v
-    iters, keep = ints(iters, "prune_iters"), ints(keep, "prune_keep")
+    iters, keep = _int_list(cfg, "prune_iters"), _int_list(cfg, "prune_keep")
     num_iter, per_image = int(_cfg(cfg, "num_iter", 100)), int(per_image)
     if len(iters) != len(keep):
         raise ValueError("cfg.prune_iters has %d entries, cfg.prune_keep %d" % (len(iters), len(keep)))
-    if any(not 0 < k < num_iter for k in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
-        raise ValueError("cfg.prune_iters %r: strictly increasing iteration counts inside (0, %d)" % (iters, num_iter))
+    _inside_num_iter(iters, "prune_iters", num_iter)
     cap = ops._lib.GD_PRUNE_MAX
     if per_image > cap:
         raise ValueError("pruning takes at most %d candidates per image, got %d" % (cap, per_image))
@@ -311,17 +376,6 @@ def prune_schedule(cfg, per_image):
 # `best` then compares weighted with unweighted losses — it is not reset.  One cloud, one colour set, one image, no depth mask.
 # Several images of one cloud: omniloc_batch_images_robust — one chain, one weight plane per image, every image its own winner, residuals and
 # scale; shared colours or per-image colour sets; image i's result is its own robust omniloc_batch call's, bit for bit.
-ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
-
-
-def _no_robust(cfg, who):
-    """what does not run the robust chain refuses its keys, naming the first one it finds"""
-    for key in ROBUST_KEYS:
-        if _cfg(cfg, key, None) is not None:
-            raise ValueError("%s does not take cfg.%s (omniloc_batch, omniloc_batch_images_robust and localize.refine_image's parallel branch do)"
-                             % (who, key))
-
-
 def robust_schedule(cfg):
     """(robust_iters as a list, kind, k) of a refinement under cfg.robust_iters (an int, or a strictly increasing list inside (0, num_iter)),
     cfg.robust_kind ("trunc", the default, or "huber") and cfg.robust_k (default 2.5), or None when the keys are absent.  The chain's
@@ -333,23 +387,17 @@ def robust_schedule(cfg):
         return None
     if iters is None:
         raise ValueError("cfg.%s goes with cfg.robust_iters" % ("robust_kind" if kind is not None else "robust_k"))
-    iters = list(iters) if isinstance(iters, (list, tuple)) else [iters]
-    if not iters or any(isinstance(x, bool) or not isinstance(x, int) for x in iters):
-        raise ValueError("cfg.robust_iters: an int or a list of ints, got %r" % (iters,))
-    num_iter = int(_cfg(cfg, "num_iter", 100))
-    if any(not 0 < i < num_iter for i in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
-        raise ValueError("cfg.robust_iters %r: strictly increasing iteration counts inside (0, %d)" % (iters, num_iter))
+    iters = _int_list(cfg, "robust_iters")
+    _inside_num_iter(iters, "robust_iters", int(_cfg(cfg, "num_iter", 100)))
     kind = "trunc" if kind is None else kind
     if kind not in ops.ROBUST_KINDS:
         raise ValueError("cfg.robust_kind %r: one of %s" % (kind, sorted(ops.ROBUST_KINDS)))
-    k = 2.5 if k is None else k
-    if isinstance(k, bool) or not isinstance(k, (int, float)) or not (0.0 < float(k) < float("inf")):
-        raise ValueError("cfg.robust_k %r: a positive finite number" % (k,))
+    k = _positive(2.5 if k is None else k, "robust_k")
     if bool(_cfg(cfg, "depth_mask", False)):
         raise ValueError("cfg.robust_iters does not combine with cfg.depth_mask")
     if _cfg(cfg, "prune_iters", None) is not None or _cfg(cfg, "prune_keep", None) is not None:
         raise ValueError("cfg.robust_iters does not combine with cfg.prune_iters / cfg.prune_keep")
-    return iters, kind, float(k)
+    return iters, kind, k
 
 
 def point_residuals(img, xyz, rgb, trans, rot):
@@ -386,21 +434,12 @@ def pose_covariance_flag(cfg):
     return v
 
 
-def _no_pose_covariance(cfg, who):
-    """what does not return a covariance refuses the key"""
-    if _cfg(cfg, "pose_covariance", None) is not None:
-        raise ValueError("%s does not take cfg.pose_covariance (omniloc_batch and localize.refine_image's parallel branch do)" % who)
-
-
 # ------------------------------------------------------------------------------------------------ Levenberg-Marquardt polish
 # (not in the reference; build-defined, include/piccolo_hip.h, DESIGN.md section 4.1f): a damped Gauss-Newton chain on H and b, wholly on
 # the device.  It minimises the MEAN SQUARED residual sigma^2 = sum w m l^2 / sum w m — not the sampling loss sum w m l / sum w m the GD
 # chains minimise: same per-point terms, mask and weights, another objective.  cfg gn_iters (an int >= 1, absent by default), gn_step_cap
 # and gn_lambda (optional: the step cap in metres / radians and the starting damping): omniloc_batch polishes its winner.  One cloud, one
 # colour set, one image, no depth mask; nothing is claimed about real data.
-GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda")
-
-
 def gn_schedule(cfg):
     """(iters, hyper dict for ops.gauss_newton_refine) under cfg.gn_iters / gn_step_cap / gn_lambda, or None when the keys are absent.
     ValueError: gn_step_cap / gn_lambda without gn_iters, gn_iters not an int in 1 .. 1000, a cap or damping that is not a positive finite
@@ -410,15 +449,12 @@ def gn_schedule(cfg):
         return None
     if iters is None:
         raise ValueError("cfg.%s goes with cfg.gn_iters" % ("gn_step_cap" if cap is not None else "gn_lambda"))
-    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= ops.GN_MAX_ITERS:
+    if not _is_int(iters) or not 1 <= iters <= ops.GN_MAX_ITERS:
         raise ValueError("cfg.gn_iters %r: an int in 1 .. %d" % (iters, ops.GN_MAX_ITERS))
     hyper = {}
     for key, name, v in (("gn_step_cap", "step_cap", cap), ("gn_lambda", "lam0", lam)):
-        if v is None:
-            continue
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 < float(v) < float("inf")):
-            raise ValueError("cfg.%s %r: a positive finite number" % (key, v))
-        hyper[name] = float(v)
+        if v is not None:
+            hyper[name] = _positive(v, key)
     try:
         ops.gn_hyper("cfg.gn_step_cap / cfg.gn_lambda", **hyper)          # (what float32 makes of them)
     except ValueError as e:
@@ -426,13 +462,6 @@ def gn_schedule(cfg):
     if bool(_cfg(cfg, "depth_mask", False)):
         raise ValueError("cfg.gn_iters does not combine with cfg.depth_mask")
     return iters, hyper
-
-
-def _no_gn(cfg, who):
-    """what does not polish its result refuses the keys, naming the first one it finds"""
-    for key in GN_KEYS:
-        if _cfg(cfg, key, None) is not None:
-            raise ValueError("%s does not take cfg.%s (omniloc_batch and localize.refine_image's parallel branch do)" % (who, key))
 
 
 def gauss_newton_refine(img, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, **hyper):
@@ -544,15 +573,50 @@ def _run_segments(sched, groups, gd, point_poses, cfg, depth_mask, cached_child)
     return chain
 
 
-def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, weights=None):
+# What _drive needs to know of a chain.  kind, key(per), xyzs: the engine cache's LRU, the launch shape of `per` candidates per group, the point
+# sets (_cached_engine); clouds, boxes: the caller's packs; make(clouds, boxes, trans, rot) -> a new engine; name(gd, graph, fresh): name the
+# panoramas where this kind of chain does; groups: the candidate groups (images; rooms x images); point_poses(per): the size _replays_graph
+# judges; run(gd, graph): the iterations of a chain without a schedule; sched: prune_schedule's segments or None; replay False: never a graph.
+# (A plain namespace filled by keyword: a namedtuple built by keyword costs the host three times as much per refinement.)
+_Chain = SimpleNamespace
+
+
+def _drive(c, tr, ro, cfg):
+    """THE chain driver: decide graph replay; eager: a new engine on the caller's packs, replay: the cached engine, reset unless it was made
+    just now with these poses; name the panoramas; run the prune segments, or the chain's own run form.  -> the engine, or the _PrunedChain"""
+    B = int(tr.shape[0])
+    per = B // c.groups
+    if per * c.groups != B:
+        raise ValueError("%d candidates do not split into %d groups" % (B, c.groups))
+    graph = c.replay and _replays_graph(cfg, c.point_poses(per), c.depth_mask)
+
+    def cached(per):
+        """-> (the cached engine of `per` candidates per group, fresh): made with the first rows of the caller's poses"""
+        rows = c.groups * per
+        return _cached_engine(c.kind, c.xyzs, c.key(per), lambda cs, bs: c.make(cs, bs, tr[:rows], ro[:rows]), c.clouds, c.boxes)
+    if not graph:
+        gd, fresh = c.make(c.clouds, c.boxes, tr, ro), True      # (fresh buffers: nothing worth keeping for a long eager chain)
+    else:
+        gd, fresh = cached(per)
+        if not fresh:
+            gd.reset(tr, ro)
+    c.name(gd, graph, fresh)
+    if c.sched is not None:
+        return _run_segments(c.sched, c.groups, gd, c.point_poses, cfg, c.depth_mask, lambda per: cached(per)[0])
+    c.run(gd, graph)
+    return gd
+
+
+def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, weights=None, weight_sets=0):
     """Run the on-device GD for the rows of trans / rot and return the GradientDescent object (read gd.result() / gd.winner()); under
     cfg.prune_iters / cfg.prune_keep the _PrunedChain of its segments (read winner() / winners()).
     `panos`: one packed panorama per query image; the B rows split evenly over them, image by image.  `rgb`: one (N, 3) tensor, or a list
     of one per query image (per-image colour sets: image i's candidates read set i, and the chain runs the single-image plan).
     The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape (_cached_engine).  `weights`: (N,)
-    per-point weights (one colour set, no depth mask)."""
+    per-point weights (one colour set, no depth mask).  weight_sets = len(panos): the robust chain over several images (a weight-set engine,
+    ops.GradientDescent(weight_sets=I): the single-image plan, one weight plane per image; omniloc_batch_images_robust)."""
     robust = robust_schedule(cfg)
-    if robust is not None:
+    if robust is not None and not weight_sets:
         if weights is not None:
             raise ValueError("cfg.robust_iters does not combine with weights= (the chain makes its own)")
         if isinstance(rgb, list) or len(panos) != 1 or not batch_mode or vis_hook is not None:
@@ -563,43 +627,34 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, we
         raise ValueError("per-point weights do not combine with cfg.depth_mask")
     cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb, weights)
     trans, rot = ops._dev(trans).reshape(-1, 3), ops._dev(rot).reshape(-1, 3)
-    B = int(trans.shape[0])
-    p0 = panos[0]
-    num_iter = _cfg(cfg, "num_iter", 100)
+    I, p0, num_iter = len(panos), panos[0], _cfg(cfg, "num_iter", 100)
     args = _engine_args(cfg, batch_mode)
-    use_graph = _replays_graph(cfg, cloud.n * B, args["depth_mask"]) and vis_hook is None
-    sched = prune_schedule(cfg, B // len(panos))
+    sched = prune_schedule(cfg, int(trans.shape[0]) // I)
+    if sched is not None and vis_hook is not None:
+        raise ValueError("cfg.visualize does not combine with cfg.prune_iters / cfg.prune_keep")
+    extra = {"weight_sets": weight_sets} if weight_sets else {}
+    # (one or two launches per iteration is frozen into a captured graph: part of the key, with the other arguments)
+    # (the robust chains have engines of their own: a plain call never meets an engine whose plane is switched on, or one of the
+    # single-image plan)
+    tail = tuple(args.values()) + (("robust_images",) if weight_sets else ("robust",) if robust is not None else ())
 
-    def cached(Bs):
-        """-> (the cached engine of Bs candidates, fresh): made with the first Bs of the caller's poses"""
-        def make(cs, bs):
-            return ops.GradientDescent(cs[0], p0, trans[:Bs], rot[:Bs], bs[0], **args)
-        # (one or two launches per iteration is frozen into a captured graph: part of the key, with the other arguments)
-        # (a robust chain has engines of its own: a plain call never meets an engine whose plane is switched on)
-        return _cached_engine("gd", (xyz,), (Bs, len(panos), p0.H, p0.W, p0.fmt, cloud.color_sets, cloud.weights is not None) + tuple(args.values())
-                              + (("robust",) if robust is not None else ()), make, [cloud], [box])
-    if not use_graph:
-        gd = ops.GradientDescent(cloud, p0, trans, rot, box, **args)      # (fresh buffers: nothing worth keeping for a long eager chain)
-    else:
-        gd, fresh = cached(B)
-        if not fresh:
-            gd.reset(trans, rot)
-    if len(panos) > 1 or use_graph or sched is not None:     # (a later segment may replay a graph that holds another image's panorama)
-        gd.set_pano_groups(list(panos))                      # addresses as kernel arguments: no H2D copy, nothing waits
-    if sched is not None:
-        if vis_hook is not None:
-            raise ValueError("cfg.visualize does not combine with cfg.prune_iters / cfg.prune_keep")
-        return _run_segments(sched, len(panos), gd, lambda per: cloud.n * len(panos) * per, cfg, args["depth_mask"],
-                             lambda per: cached(len(panos) * per)[0])
-    if robust is not None:
-        gd.run_robust(num_iter, robust[0], robust[1], robust[2], graph=use_graph)
-    elif vis_hook is not None:
-        vis_hook(gd, num_iter)
-    elif use_graph:
-        gd.run_graph(num_iter)
-    else:
-        gd.run(num_iter)
-    return gd
+    def name(gd, graph, fresh):
+        if weight_sets or I > 1 or graph or sched is not None:   # (a later segment may replay a graph that holds another image's panorama)
+            gd.set_pano_groups(list(panos))                      # addresses as kernel arguments: no H2D copy, nothing waits
+
+    def run(gd, graph):
+        if robust is not None:
+            gd.run_robust(num_iter, robust[0], robust[1], robust[2], graph=graph)
+        elif vis_hook is not None:
+            vis_hook(gd, num_iter)
+        elif graph:
+            gd.run_graph(num_iter)
+        else:
+            gd.run(num_iter)
+    return _drive(_Chain(kind="gd", key=lambda per: (I * per, I, p0.H, p0.W, p0.fmt, cloud.color_sets, cloud.weights is not None) + tail,
+                         xyzs=(xyz,), clouds=[cloud], boxes=[box], make=lambda cs, bs, t, r: ops.GradientDescent(cs[0], p0, t, r, bs[0], **args, **extra),
+                         name=name, groups=I, point_poses=lambda per: cloud.n * I * per, run=run, sched=sched, depth_mask=args["depth_mask"],
+                         replay=vis_hook is None), trans, rot, cfg)
 
 
 def _refine_groups(chain, trans_list, rot_list):
@@ -660,10 +715,7 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     (omniloc.py:46,102).  Row `starting_point` of input_trans / input_rot ends up holding the final pose, as in the
     reference where the optimised tensors are views of those rows (omniloc.py:15-19).
     """
-    _no_prune(cfg, "omniloc")
-    _no_robust(cfg, "omniloc")
-    _no_pose_covariance(cfg, "omniloc")
-    _no_gn(cfg, "omniloc")
+    _refuse(cfg, "omniloc", "prune", "robust", "pose_covariance", "gn")
     vis = _cfg(cfg, "visualize", False)
     out_quantile = _cfg(cfg, "out_of_room_quantile", 0.05)
 
@@ -716,10 +768,7 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     `for i in range(num_input): omniloc(..., i, ...)` (localize.py:219-220), for ALL starting points in one launch chain.
     Every starting point keeps omniloc's SEQUENTIAL semantics (its own Adam / scheduler, clamp applied to the parameters
     the next forward reads) and the points never interact, so the list returned equals the K separate calls."""
-    _no_prune(cfg, "omniloc_all")
-    _no_robust(cfg, "omniloc_all")
-    _no_pose_covariance(cfg, "omniloc_all")
-    _no_gn(cfg, "omniloc_all")
+    _refuse(cfg, "omniloc_all", "prune", "robust", "pose_covariance", "gn")
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False, weights=weights).result()
     K = res.shape[0]
@@ -795,9 +844,7 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     and the chain runs the single-image plan, so image i's result is omniloc_batch(imgs[i], xyz, rgb[i], ...)'s bit for bit.  Images
     beyond the colour-set addressing limit go in further groups.  With the depth mask the colour-set chain is the depth chain
     (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image."""
-    _no_robust(cfg, "omniloc_batch_images")
-    _no_pose_covariance(cfg, "omniloc_batch_images")
-    _no_gn(cfg, "omniloc_batch_images")
+    _refuse(cfg, "omniloc_batch_images", "robust", "pose_covariance", "gn")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     I = len(imgs)
@@ -805,43 +852,13 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     if isinstance(rgb, list):
         if len(rgb) != I:
             raise ValueError("omniloc_batch_images: %d colour sets for %d images" % (len(rgb), I))
-        sizes = color_set_groups(int(xyz.shape[0]), I)
-        if len(sizes) > 1:
-            out, i0 = [], 0
-            for m in sizes:
-                out += omniloc_batch_images(imgs[i0:i0 + m], xyz, rgb[i0:i0 + m] if m > 1 else rgb[i0], input_trans_list[i0:i0 + m],
-                                            input_rot_list[i0:i0 + m], cfg, scalar_summaries, batch_mode)
-                i0 += m
+        out = _over_color_sets(int(xyz.shape[0]), I, lambda i0, i1: omniloc_batch_images(
+            imgs[i0:i1], xyz, rgb[i0:i1] if i1 - i0 > 1 else rgb[i0], input_trans_list[i0:i1], input_rot_list[i0:i1], cfg, scalar_summaries, batch_mode))
+        if out is not None:
             return out
-    fmt = ops.refine_texels(xyz.shape[0], imgs[0].shape[0], imgs[0].shape[1])
-    panos = [packed_pano(im, n_points=xyz.shape[0]) if I <= 8 else ops.Pano(im, fmt=fmt if ops._known_levels(im) else "auto") for im in imgs]
-    if len({p.fmt for p in panos}) > 1:          # a launch needs ONE texel format: float4 holds any image
-        panos = [ops.Pano(im, fmt="f32") for im in imgs]
+    panos = _chain_panos(imgs, xyz.shape[0], direct=I > 8)
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     return _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, batch_mode), input_trans_list, input_rot_list)
-
-
-def _refine_robust_images(xyz, rgb, panos, trans, rot, box, cfg, robust):
-    """The robust chain over the images `panos` of one cloud: a weight-set engine (ops.GradientDescent(weight_sets=I): the single-image plan,
-    one weight plane per image), cached like _refine's engines under a key of its own, run through run_robust -> the engine."""
-    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb)
-    trans, rot = ops._dev(trans).reshape(-1, 3), ops._dev(rot).reshape(-1, 3)
-    B, I, p0 = int(trans.shape[0]), len(panos), panos[0]
-    args = _engine_args(cfg, True)
-    use_graph = _replays_graph(cfg, cloud.n * B, False)
-    if not use_graph:
-        gd = ops.GradientDescent(cloud, p0, trans, rot, box, weight_sets=I, **args)
-    else:
-        def make(cs, bs):
-            return ops.GradientDescent(cs[0], p0, trans, rot, bs[0], weight_sets=I, **args)
-        # (engines of their own: a plain omniloc_batch_images never meets an engine of the single-image plan or one whose planes are on)
-        gd, fresh = _cached_engine("gd", (xyz,), (B, I, p0.H, p0.W, p0.fmt, cloud.color_sets, False) + tuple(args.values()) + ("robust_images",),
-                                   make, [cloud], [box])
-        if not fresh:
-            gd.reset(trans, rot)
-    gd.set_pano_groups(list(panos))
-    gd.run_robust(_cfg(cfg, "num_iter", 100), robust[0], robust[1], robust[2], graph=use_graph)
-    return gd
 
 
 def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries=None):
@@ -854,8 +871,7 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
     same cfg bit for bit; every loss is the WEIGHTED loss of the last forward.  Parallel semantics only.  ValueError: cfg without
     robust_iters (and robust_schedule's refusals: the depth mask, the prune keys), cfg.visualize, lists of different lengths.  One image is
     omniloc_batch."""
-    _no_pose_covariance(cfg, "omniloc_batch_images_robust")
-    _no_gn(cfg, "omniloc_batch_images_robust")
+    _refuse(cfg, "omniloc_batch_images_robust", "pose_covariance", "gn")
     robust = robust_schedule(cfg)
     if robust is None:
         raise ValueError("omniloc_batch_images_robust needs cfg.robust_iters (omniloc_batch_images runs the plain chain)")
@@ -872,20 +888,13 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
     if I == 1:
         return [omniloc_batch(imgs[0], xyz, rgb[0] if isinstance(rgb, list) else rgb, input_trans_list[0], input_rot_list[0], cfg, scalar_summaries)]
     if isinstance(rgb, list):
-        sizes = color_set_groups(int(xyz.shape[0]), I)
-        if len(sizes) > 1:
-            out, i0 = [], 0
-            for m in sizes:
-                out += omniloc_batch_images_robust(imgs[i0:i0 + m], xyz, rgb[i0:i0 + m], input_trans_list[i0:i0 + m], input_rot_list[i0:i0 + m],
-                                                   cfg, scalar_summaries)
-                i0 += m
+        out = _over_color_sets(int(xyz.shape[0]), I, lambda i0, i1: omniloc_batch_images_robust(
+            imgs[i0:i1], xyz, rgb[i0:i1], input_trans_list[i0:i1], input_rot_list[i0:i1], cfg, scalar_summaries))
+        if out is not None:
             return out
-    # (the texel format every image's own omniloc_batch call takes: packed_pano's; float4 for all when the images do not agree)
-    panos = [packed_pano(im, n_points=xyz.shape[0]) for im in imgs]
-    if len({p.fmt for p in panos}) > 1:
-        panos = [ops.Pano(im, fmt="f32") for im in imgs]
+    panos = _chain_panos(imgs, xyz.shape[0])      # (the texel format every image's own omniloc_batch call takes)
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
-    return _refine_groups(lambda tr, ro: _refine_robust_images(xyz, rgb, panos, tr, ro, box, cfg, robust), input_trans_list, input_rot_list)
+    return _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, True, weight_sets=I), input_trans_list, input_rot_list)
 
 
 def depth_tau_groups(points, H, W, cfg):
@@ -916,44 +925,25 @@ def _chain(kind, imgs, rooms, tr, ro, cfg, batch_mode):
     boxes = [quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05)) for xyz, _ in rooms]
     per_room = int(tr.shape[0]) // len(rooms)
     nmax = max(int(xyz.shape[0]) for xyz, _ in rooms)
-    panos = [packed_pano(im, n_points=nmax) for im in imgs]
-    if len({p.fmt for p in panos}) > 1:          # a launch needs ONE texel format: float4 holds any image
-        panos = [ops.Pano(im, fmt="f32") for im in imgs]
-    p0 = panos[0]
-    num_iter = _cfg(cfg, "num_iter", 100)
+    panos = _chain_panos(imgs, nmax)
+    I, p0, num_iter = len(imgs), panos[0], _cfg(cfg, "num_iter", 100)
     args = _engine_args(cfg, batch_mode)
-
     points = sum(c.n for c in clouds)
-    sched = prune_schedule(cfg, per_room // len(imgs))
+    sched = prune_schedule(cfg, per_room // I)
 
-    def cached(per):
-        """-> (the cached engine of `per` candidates per room, fresh): made with the first rows of the caller's poses"""
-        def make(cs, bs):
-            if one_image:
-                return ops.GradientDescentRooms(list(zip(cs, bs)), p0, tr[:len(rooms) * per], ro[:len(rooms) * per], **args)
-            return ops.GradientDescentRoomsImages(list(zip(cs, bs)), panos, tr[:len(rooms) * per], ro[:len(rooms) * per], **args)
-        return _cached_engine(kind, tuple(xyz for xyz, _ in rooms), (len(imgs), per, p0.H, p0.W, p0.fmt, clouds[0].color_sets) + tuple(args.values()),
-                              make, clouds, boxes)
-    if not _replays_graph(cfg, points * per_room, args["depth_mask"]):
+    def make(cs, bs, t, r):
         if one_image:
-            gd = ops.GradientDescentRooms(list(zip(clouds, boxes)), p0, tr, ro, **args)
-        else:
-            gd = ops.GradientDescentRoomsImages(list(zip(clouds, boxes)), panos, tr, ro, **args)
-        if sched is None:
-            gd.run(num_iter)
-            return gd
-        fresh = True
-    else:
-        gd, fresh = cached(per_room)
-        if not fresh:
-            gd.reset(tr, ro)
-    if not fresh or one_image:                   # (a new several-image engine has named its panoramas itself)
-        gd.set_panos(panos)                      # the pose records name these images' panoramas (the graph holds the first ones')
-    if sched is not None:
-        groups = len(rooms) * len(imgs)
-        return _run_segments(sched, groups, gd, lambda per: points * len(imgs) * per, cfg, args["depth_mask"], lambda per: cached(len(imgs) * per)[0])
-    gd.run_graph(num_iter)
-    return gd
+            return ops.GradientDescentRooms(list(zip(cs, bs)), p0, t, r, **args)
+        return ops.GradientDescentRoomsImages(list(zip(cs, bs)), panos, t, r, **args)
+
+    def name(gd, graph, fresh):
+        # never on the eager path without a schedule; a new several-image engine has named its panoramas itself (as found)
+        if (graph or sched is not None) and (not fresh or one_image):
+            gd.set_panos(panos)                  # the pose records name these images' panoramas (the graph holds the first ones')
+    return _drive(_Chain(kind=kind, key=lambda per: (I, I * per, p0.H, p0.W, p0.fmt, clouds[0].color_sets) + tuple(args.values()),
+                         xyzs=tuple(xyz for xyz, _ in rooms), clouds=clouds, boxes=boxes, make=make, name=name, groups=len(rooms) * I,
+                         point_poses=lambda per: points * I * per, run=lambda gd, graph: gd.run_graph(num_iter) if graph else gd.run(num_iter),
+                         sched=sched, depth_mask=args["depth_mask"], replay=True), tr, ro, cfg)
 
 
 def _rooms_chain(img, rooms, tr, ro, cfg, batch_mode):
@@ -970,9 +960,7 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     each room's candidates).  More than PCL_GD_MAX_ROOMS rooms go in several chains.  With the depth mask the chain is the depth chain
     (pcl_gd_run_depth_chain: every room on its own z-buffer grid, the same bits per room); rooms whose tolerances differ (depth_tau_groups)
     go in a chain per tolerance."""
-    _no_robust(cfg, "omniloc_batch_rooms")
-    _no_pose_covariance(cfg, "omniloc_batch_rooms")
-    _no_gn(cfg, "omniloc_batch_rooms")
+    _refuse(cfg, "omniloc_batch_rooms", "robust", "pose_covariance", "gn")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R = len(rooms)
@@ -1046,9 +1034,7 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     the depth chain (pcl_gd_run_depth_chain) under the same rules; rooms whose tolerances differ (depth_tau_groups) go in a chain per
     tolerance, and images that share the rooms' colours run omniloc_batch_images per room where that is faster (depth_shared_chain_pays:
     its plan of all the images' candidates, so equal to the single calls up to the summation order of the partial sums, as there)."""
-    _no_robust(cfg, "omniloc_batch_rooms_images")
-    _no_pose_covariance(cfg, "omniloc_batch_rooms_images")
-    _no_gn(cfg, "omniloc_batch_rooms_images")
+    _refuse(cfg, "omniloc_batch_rooms_images", "robust", "pose_covariance", "gn")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R, I = len(rooms), len(imgs)
@@ -1091,15 +1077,10 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     if any(isinstance(rgb, list) for _, rgb in rooms):
         # one kind of cloud per chain: a room whose images share its colours holds them I times
         rooms = [(xyz, rgb if isinstance(rgb, list) else [rgb] * I) for xyz, rgb in rooms]
-        sizes = color_set_groups(max(int(xyz.shape[0]) for xyz, _ in rooms), I)
-        if len(sizes) > 1:
-            out, i0 = [[] for _ in range(R)], 0
-            for m in sizes:
-                some = omniloc_batch_rooms_images(imgs[i0:i0 + m], [(xyz, rgb[i0:i0 + m]) for xyz, rgb in rooms], [t[i0:i0 + m] for t in input_trans],
-                                                  [r[i0:i0 + m] for r in input_rot], cfg, scalar_summaries, batch_mode)
-                for r in range(R):
-                    out[r] += some[r]
-                i0 += m
+        out = _over_color_sets(max(int(xyz.shape[0]) for xyz, _ in rooms), I, lambda i0, i1: omniloc_batch_rooms_images(
+            imgs[i0:i1], [(xyz, rgb[i0:i1]) for xyz, rgb in rooms], [t[i0:i1] for t in input_trans], [r[i0:i1] for r in input_rot], cfg,
+            scalar_summaries, batch_mode), rooms=R)
+        if out is not None:
             return out
     flat = _refine_groups(lambda tr, ro: _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode), [t for ts in input_trans for t in ts],
                           [r for rs in input_rot for r in rs])

@@ -64,6 +64,22 @@ def _bytes(nbytes):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device())
 
 
+def _order_and_buffer(xyz, n, order, sort, nbytes):
+    """-> (order, a packed buffer of nbytes) of an n-point cloud.  order maps packed slot -> point index: `order` as computed before for the
+    same xyz (checked), else sorted here (pcl_cloud_order), else None (sort False, or a single point: the original order).  The buffer is
+    allocated while the sort's workspace is alive: in that block the cloud makes the trim launch 10 % slower."""
+    ws = None
+    if order is not None:
+        if order.dtype != torch.int64 or order.numel() != n or not order.is_cuda:
+            raise ValueError("order must be a CUDA int64 tensor with one entry per point")
+    elif sort and n > 1:
+        order = torch.empty(n, dtype=torch.int64, device=xyz.device)
+        nws = _lib.load().pcl_cloud_order_workspace_bytes(n)
+        ws = _bytes(nws)
+        _lib.check(_lib.load().pcl_cloud_order(_ptr(xyz), n, _ptr(order), _ptr(ws), nws, _stream()), "pcl_cloud_order")
+    return order, _bytes(nbytes)
+
+
 class Cloud:
     """Point cloud packed for the loss kernel: 6 SoA planes, by default in Morton order of xyz.
 
@@ -86,17 +102,7 @@ class Cloud:
         self.n = int(xyz.shape[0])
         if self.n <= 0:
             raise ValueError("empty point cloud")
-        self.order = None
-        if order is not None:
-            if order.dtype != torch.int64 or order.numel() != self.n or not order.is_cuda:
-                raise ValueError("order must be a CUDA int64 tensor with one entry per point")
-            self.order = order
-        elif sort and self.n > 1:
-            self.order = torch.empty(self.n, dtype=torch.int64, device=xyz.device)
-            nws = lib.pcl_cloud_order_workspace_bytes(self.n)
-            ws = _bytes(nws)
-            _lib.check(lib.pcl_cloud_order(_ptr(xyz), self.n, _ptr(self.order), _ptr(ws), nws, _stream()), "pcl_cloud_order")
-        self.data = _bytes(lib.pcl_cloud_bytes(self.n))
+        self.order, self.data = _order_and_buffer(xyz, self.n, order, sort, lib.pcl_cloud_bytes(self.n))
         _lib.check(lib.pcl_cloud_pack(_ptr(xyz), _ptr(rgb), _ptr(self.order), self.n, _ptr(self.data), _stream()),
                    "pcl_cloud_pack")
         self.xyz = xyz          # kept for quantile_box (reads the reference's AoS layout)
@@ -167,18 +173,8 @@ class Cloud:
         nbytes = lib.pcl_cloud_sets_bytes(c.n, len(rgbs))
         if nbytes == 0:
             raise ValueError("%d colour sets of %d points exceed the cloud's 32-bit addressing (at most %d)" % (len(rgbs), c.n, max_color_sets(c.n)))
-        c.order = None
-        if order is not None:
-            if order.dtype != torch.int64 or order.numel() != c.n or not order.is_cuda:
-                raise ValueError("order must be a CUDA int64 tensor with one entry per point")
-            c.order = order
-        elif sort and c.n > 1:
-            c.order = torch.empty(c.n, dtype=torch.int64, device=xyz.device)
-            nws = lib.pcl_cloud_order_workspace_bytes(c.n)
-            ws = _bytes(nws)
-            _lib.check(lib.pcl_cloud_order(_ptr(xyz), c.n, _ptr(c.order), _ptr(ws), nws, _stream()), "pcl_cloud_order")
+        c.order, c.data = _order_and_buffer(xyz, c.n, order, sort, nbytes)
         c.color_sets = len(rgbs)
-        c.data = _bytes(nbytes)
         arr = (ctypes.c_void_p * len(rgbs))(*[r.data_ptr() for r in rgbs])
         _lib.check(lib.pcl_cloud_pack_sets(_ptr(xyz), arr, len(rgbs), _ptr(c.order), c.n, _ptr(c.data), _stream()), "pcl_cloud_pack_sets")
         c.xyz = xyz
@@ -208,6 +204,7 @@ class Pano:
     _PACK = {"f16": ("pcl_pano_pack_f16", _lib.PANO_F16), "u8": ("pcl_pano_pack_u8", _lib.PANO_U8),
              "u8p": ("pcl_pano_pack_u8p", _lib.PANO_U8P),         # u8p: rows interleaved in pairs, u8v: vertical pairs — trim launch only
              "u8v": ("pcl_pano_pack_u8v", _lib.PANO_U8V)}
+    texels = property(lambda self: (self.H, self.W, self.fmt))      # what the panoramas of one launch share
 
     def __init__(self, img, fmt="auto"):
         lib = _lib.load()
@@ -244,6 +241,12 @@ class Pano:
 
 
 _SCRATCH_FLAGS = {}
+
+
+def _same_texels(panos, p0, complaint="all panoramas of a launch must share size and texel format"):
+    """every panorama of a launch has p0's size and texel format"""
+    if any(p.texels != p0.texels for p in panos):
+        raise ValueError(complaint)
 
 
 def _scratch_flag(dev):
@@ -443,9 +446,7 @@ def _point_residuals(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, p
     p0 = panos[0] if several else panos
     _residual_cloud(cloud, p0, who, len(panos) if several else None)
     if several:
-        for p in panos:
-            if (p.H, p.W, p.fmt) != (p0.H, p0.W, p0.fmt):
-                raise ValueError("%s: all panoramas must share size and texel format" % who)
+        _same_texels(panos, p0, "%s: all panoramas must share size and texel format" % who)
         if rows != len(panos):
             raise ValueError("%s: one pose per panorama" % who)
     if out is None:
@@ -730,8 +731,7 @@ def trim_loss_tables(cloud, panos, trans, groups, return_count=False, order=None
     Cloud(xyz, rgbs[i]), bit for bit."""
     _unweighted(cloud, "trim_loss_tables")
     I, p0 = len(panos), panos[0]
-    if any((p.H, p.W, p.fmt) != (p0.H, p0.W, p0.fmt) for p in panos):
-        raise ValueError("all panoramas of a launch must share size and texel format")
+    _same_texels(panos, p0)
     if cloud.color_sets > 1:
         if cloud.color_sets != I:
             raise ValueError("a cloud of %d colour sets for %d images" % (cloud.color_sets, I))
@@ -1028,7 +1028,47 @@ def _gd_hyper(lr, patience, factor, batch_mode, fuse, depth=None, color_sets=0):
 
 class _GdEngine:
     """What the GD engines share: a state of self.B candidates (self.state), a run(num_iter) that neither allocates nor synchronises, and
-    self.pano, the panorama whose size and texel format every panorama of the chain has."""
+    self.pano, the panorama whose size and texel format every panorama of the chain has.  A class says how its candidates split into groups
+    (_groups, _GROUP), what a smaller engine takes over as it is (_INHERITED) and how large a workspace it needs (_workspace_bytes)."""
+
+    _chain = None                   # an inner engine whose hyper-parameters, state and workspace are this object's (GradientDescent's)
+
+    def _size(self, B):
+        self.B = B
+
+    def _allocate(self, smaller=False):
+        """the state and the workspace of self.B candidates under self.hyper; the class says how large (_workspace_bytes) and what 0 means"""
+        self.state = _bytes(_lib.load().pcl_gd_state_bytes(self.B))
+        self.ws_bytes = self._workspace_bytes()
+        if self.ws_bytes == 0:
+            raise _lib.PiccoloHipError(self._refusal(smaller))
+        self.ws = _bytes(self.ws_bytes)
+
+    def _share(self, inner):
+        self._chain, self.hyper, self.state, self.ws, self.ws_bytes = inner, inner.hyper, inner.state, inner.ws, inner.ws_bytes
+
+    def _smaller(self, keep):
+        """An engine of the same class, clouds, panorama, boxes and hyper-parameters with `keep` candidates per group, its state not yet
+        written: the attributes _INHERITED names, a copy of the hyper-parameters, buffers of its own.  Nothing tied to THIS engine's buffers
+        goes along — captured graphs, robust planes, a cached engine's private clouds; prune_into hands over the named panoramas."""
+        groups = self._groups()
+        if self.B % groups or not 1 <= keep <= self.B // groups:
+            raise ValueError("pruned: keep %d of %d candidates per %s" % (keep, self.B // groups, self._GROUP))
+        g = type(self).__new__(type(self))
+        for name in self._INHERITED:
+            setattr(g, name, getattr(self, name))
+        g._size(groups * keep)
+        if self._chain is not None:
+            g._share(self._chain._smaller(keep))
+        else:
+            g.hyper = _copy_hyper(self.hyper)
+            g._allocate(smaller=True)
+        return g
+
+    def _leaf_check(self, who, *leaves):
+        for t in leaves:
+            if t is not None and not (t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == 3 * self.B):
+                raise ValueError("%s: leaf buffers must be contiguous float32 GPU tensors of B x 3" % who)
 
     def run_graph(self, num_iter):
         """Same as run(num_iter) but the 2 * num_iter launches are captured into one hipGraph and replayed: the host
@@ -1061,9 +1101,7 @@ class _GdEngine:
         I = len(panos)
         if I <= 0 or self.B % I:
             raise ValueError("set_pano_groups: %d candidates do not split into %d images" % (self.B, I))
-        for p in panos:
-            if (p.H, p.W, p.fmt) != (self.pano.H, self.pano.W, self.pano.fmt):
-                raise ValueError("all panoramas of a launch must share size and texel format")
+        _same_texels(panos, self.pano)
         self._panos = list(panos)                      # keep them alive
         arr = (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos])
         _lib.check(_lib.load().pcl_gd_set_pano_groups(_ptr(self.state), arr, I, self.B // I, _stream()), "pcl_gd_set_pano_groups")
@@ -1075,9 +1113,7 @@ class _GdEngine:
         if groups <= 0 or self.B % groups:
             raise ValueError("winner: %d candidates do not split into %d images" % (self.B, groups))
         out = torch.empty(groups, 16, dtype=F32, device=self.state.device)
-        for t in (leaf_trans, leaf_rot):
-            if t is not None and not (t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == 3 * self.B):
-                raise ValueError("winner: leaf buffers must be contiguous float32 GPU tensors of B x 3")
+        self._leaf_check("winner", leaf_trans, leaf_rot)
         _lib.check(_lib.load().pcl_gd_winner(_ptr(self.state), groups, self.B // groups, _ptr(out), _ptr(leaf_trans), _ptr(leaf_rot), _stream()),
                    "pcl_gd_winner")
         return out
@@ -1103,9 +1139,7 @@ class _GdEngine:
         groups = self._groups()
         if type(child) is not type(self) or child is self or child.B <= 0 or child.B % groups or child.B > self.B or not self._same_problem(child):
             raise ValueError("prune: the smaller engine must be one of the same class, clouds and groups with at most as many candidates")
-        for t in (leaf_trans, leaf_rot):
-            if t is not None and not (t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == 3 * self.B):
-                raise ValueError("prune: leaf buffers must be contiguous float32 GPU tensors of B x 3")
+        self._leaf_check("prune", leaf_trans, leaf_rot)
         if self.B // groups > _lib.GD_PRUNE_MAX:
             raise ValueError("prune: at most %d candidates per group" % _lib.GD_PRUNE_MAX)
         survivors = torch.empty(child.B, dtype=torch.int32, device=self.state.device)
@@ -1128,6 +1162,9 @@ def _copy_hyper(h):
 class GradientDescent(_GdEngine):
     """On-device GD refinement of B candidates (Adam + ReduceLROnPlateau + clamp), pcl_gd_* of the C ABI."""
 
+    _INHERITED, _GROUP = ("cloud", "pano", "box"), "image"
+    weight_sets, _robust = 0, None  # (a smaller engine's: no weight sets, no plane of its own)
+
     def __init__(self, cloud, pano, trans, rot, box, lr=0.1, patience=5, factor=0.9, batch_mode=True, depth_mask=False,
                  depth_tau=None, depth_res=None, depth_stride=None, fuse=None, weight_sets=0):
         """fuse None: pcl_gd_plan's rule (one launch per iteration for launches whose blocks are all resident); False: always the
@@ -1136,10 +1173,9 @@ class GradientDescent(_GdEngine):
         chain (pcl_gd_run_weight_sets): the single-image plan for all B candidates with shared colours too, pose records that name their
         image, and I weight planes of its own (self.weight_planes(), unused until robust_reweight or weight_planes_on) — image i's results are
         those of a GradientDescent over image i alone, bit for bit.  One colour set or I of them, no depth mask, a cloud without weights."""
-        lib = _lib.load()
         self.cloud, self.pano = cloud, pano
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-        self.B = int(trans.shape[0])
+        self._size(int(trans.shape[0]))
         self.box = _dev(box).reshape(6)
         self.weight_sets, self._robust = int(weight_sets), None       # (_robust: _robust_buffers, once a re-weighting or a plane asks for them)
         if self.weight_sets:
@@ -1153,25 +1189,25 @@ class GradientDescent(_GdEngine):
             raise ValueError("GradientDescent: %d candidates over %d colour sets" % (self.B, cloud.color_sets))
         # colour sets under the depth mask: the depth-chain family with this cloud as its one room and a set per image; the engine's state,
         # workspace and hyper-parameters are this object's (the pose records name no panorama until set_pano_groups)
-        self._chain = None
         if depth_mask and cloud.color_sets > 1:
-            self._chain = GradientDescentRoomsImages([(cloud, self.box)], [pano] * cloud.color_sets, trans, rot, lr, patience, factor, batch_mode, fuse,
-                                                     True, depth_tau, depth_res, depth_stride, name_panos=False)
-            self.hyper, self.state, self.ws, self.ws_bytes = self._chain.hyper, self._chain.state, self._chain.ws, self._chain.ws_bytes
+            self._share(GradientDescentRoomsImages([(cloud, self.box)], [pano] * cloud.color_sets, trans, rot, lr, patience, factor, batch_mode, fuse,
+                                                   True, depth_tau, depth_res, depth_stride, name_panos=False))
             return
         # a cloud of per-image colour sets (Cloud.with_color_sets): candidates [i * B / k, (i + 1) * B / k) read set i, and the chain runs
         # the single-image plan (pcl_gd_hyper.color_sets)
         self.hyper = _gd_hyper(lr, patience, factor, batch_mode, fuse, _depth_args(cloud.n, pano.H, pano.W, depth_res, depth_tau, depth_stride)
                                if depth_mask else None, cloud.color_sets)
-        self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
-        if self.weight_sets:
-            self.ws_bytes = lib.pcl_gd_weight_sets_workspace_bytes(cloud.n, self.B, self.weight_sets, ctypes.byref(self.hyper))
-        else:
-            self.ws_bytes = lib.pcl_gd_workspace_bytes(cloud.n, self.B, pano.H, pano.W, ctypes.byref(self.hyper))
-        if self.ws_bytes == 0:
-            raise _lib.PiccoloHipError("pcl_gd_workspace_bytes: invalid arguments (depth grid %dx%d?)" % (self.hyper.depth_h, self.hyper.depth_w))
-        self.ws = _bytes(self.ws_bytes)
+        self._allocate()
         self.reset(trans, rot)
+
+    def _workspace_bytes(self):
+        if self.weight_sets:
+            return _lib.load().pcl_gd_weight_sets_workspace_bytes(self.cloud.n, self.B, self.weight_sets, ctypes.byref(self.hyper))
+        return _lib.load().pcl_gd_workspace_bytes(self.cloud.n, self.B, self.pano.H, self.pano.W, ctypes.byref(self.hyper))
+
+    def _refusal(self, smaller):
+        h = self.hyper
+        return "pcl_gd_workspace_bytes: invalid arguments " + ("for %d candidates" % self.B if smaller else "(depth grid %dx%d?)" % (h.depth_h, h.depth_w))
 
     def run(self, num_iter, history=False, timer=None):
         if self._chain is not None:
@@ -1300,9 +1336,7 @@ class GradientDescent(_GdEngine):
         """Candidate b samples panos[b] (a list of B Pano objects, all the size / texel format of self.pano): lets the
         candidates of several query images share one launch chain.  Call after __init__ / reset()."""
         assert len(panos) == self.B
-        for p in panos:
-            if (p.H, p.W, p.fmt) != (self.pano.H, self.pano.W, self.pano.fmt):
-                raise ValueError("all panoramas of a launch must share size and texel format")
+        _same_texels(panos, self.pano)
         self._panos = list(panos)                      # keep them alive
         self.set_pano_table(torch.tensor([p.data.data_ptr() for p in panos], dtype=torch.int64, device=self.state.device),
                             images=len({id(p) for p in panos}))
@@ -1331,30 +1365,12 @@ class GradientDescent(_GdEngine):
         return max(1, int(self.cloud.color_sets), int(self.hyper.images))
 
     def _same_problem(self, other):
-        return other.cloud.n == self.cloud.n and other.cloud.color_sets == self.cloud.color_sets and \
-            (other.pano.H, other.pano.W, other.pano.fmt) == (self.pano.H, self.pano.W, self.pano.fmt)
+        return other.cloud.n == self.cloud.n and other.cloud.color_sets == self.cloud.color_sets and other.pano.texels == self.pano.texels
 
     def _smaller(self, keep):
-        """an engine over the same cloud, panorama, box and hyper-parameters with `keep` candidates per image, its state not yet written"""
-        lib, groups = _lib.load(), self._groups()
         if self.weight_sets:
             raise ValueError("pruned: a weight-set engine is not pruned")
-        if self.B % groups or not 1 <= keep <= self.B // groups:
-            raise ValueError("pruned: keep %d of %d candidates per image" % (keep, self.B // max(groups, 1)))
-        g = GradientDescent.__new__(GradientDescent)
-        g.cloud, g.pano, g.box, g.B = self.cloud, self.pano, self.box, groups * keep
-        g.weight_sets, g._robust = 0, None
-        g._chain = self._chain._smaller(keep) if self._chain is not None else None
-        if g._chain is not None:
-            g.hyper, g.state, g.ws, g.ws_bytes = g._chain.hyper, g._chain.state, g._chain.ws, g._chain.ws_bytes
-            return g
-        g.hyper = _copy_hyper(self.hyper)
-        g.state = _bytes(lib.pcl_gd_state_bytes(g.B))
-        g.ws_bytes = lib.pcl_gd_workspace_bytes(self.cloud.n, g.B, self.pano.H, self.pano.W, ctypes.byref(g.hyper))
-        if g.ws_bytes == 0:
-            raise _lib.PiccoloHipError("pcl_gd_workspace_bytes: invalid arguments for %d candidates" % g.B)
-        g.ws = _bytes(g.ws_bytes)
-        return g
+        return super()._smaller(keep)
 
     def step_from_grads(self, loss, grad):
         """Teacher-forcing hook (tests): ONE optimiser step of every candidate from a GIVEN loss (B,) and gradient (B, 6) =
@@ -1372,12 +1388,14 @@ class GradientDescentRoomsImages(_GdEngine):
     or I of them (Cloud.with_color_sets: image i reads set i of every room).  The results of every (room, image) equal those of a
     GradientDescent over that room and image alone, bit for bit.  At most PCL_GD_MAX_ROOMS rooms."""
 
+    _INHERITED, _GROUP = ("pano", "clouds", "nrooms", "nimages", "color_sets", "boxes", "depth_mask", "_rooms"), "(room, image)"
+
     def __init__(self, rooms, panos, trans, rot, lr=0.1, patience=5, factor=0.9, batch_mode=True, fuse=None, depth_mask=False, depth_tau=None,
                  depth_res=None, depth_stride=None, name_panos=True):
         """depth_mask: the scatter-min depth mask in the chain (pcl_gd_run_depth_chain): every room on its own grid, as
         GradientDescent(depth_mask=True) of that room resolves it; depth_res applies to every room.  name_panos False: the pose records name
         no panorama and every candidate samples panos[0], the kernel argument, until set_panos."""
-        lib, name = _lib.load(), type(self).__name__
+        name = type(self).__name__
         if not 1 <= len(rooms) <= _lib.GD_MAX_ROOMS:
             raise ValueError("%s: %d rooms (1..%d per chain)" % (name, len(rooms), _lib.GD_MAX_ROOMS))
         if len(panos) < 1:
@@ -1393,28 +1411,31 @@ class GradientDescentRoomsImages(_GdEngine):
         self.color_sets = int(self.clouds[0].color_sets)
         self.boxes = [_dev(b).reshape(6) for _, b in rooms]
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
-        self.B = int(trans.shape[0])
-        if self.B % (self.nrooms * self.nimages) or self.B == 0:
-            raise ValueError("%s: %d candidates do not split into %d rooms x %d images" % (name, self.B, self.nrooms, self.nimages))
-        self.per_room = self.B // self.nrooms
-        self.per_image = self.per_room // self.nimages
+        B = int(trans.shape[0])
+        if B % (self.nrooms * self.nimages) or B == 0:
+            raise ValueError("%s: %d candidates do not split into %d rooms x %d images" % (name, B, self.nrooms, self.nimages))
         self.depth_mask = bool(depth_mask)
         self.hyper = _gd_hyper(lr, patience, factor, batch_mode, fuse,
                                _chain_depth_args([c.n for c in self.clouds], self.pano.H, self.pano.W, depth_res, depth_tau, depth_stride)
                                if depth_mask else None, self.color_sets if self.color_sets > 1 else 0)
         self._rooms = (_lib.GdRoom * self.nrooms)(*[_lib.GdRoom(c.data.data_ptr(), c.n, b.data_ptr()) for c, b in zip(self.clouds, self.boxes)])
-        self._shape = (self._rooms, self.nrooms, self.nimages, self.per_image)        # (how every pcl_gd_*rooms_images / *depth_chain call begins)
-        self.state = _bytes(lib.pcl_gd_state_bytes(self.B))
-        if depth_mask:
-            self.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(*self._shape, self.pano.H, self.pano.W, ctypes.byref(self.hyper))
-        else:
-            self.ws_bytes = lib.pcl_gd_rooms_images_workspace_bytes(*self._shape, ctypes.byref(self.hyper))
-        if self.ws_bytes == 0:
-            raise _lib.PiccoloHipError("pcl_gd_%s_workspace_bytes: invalid arguments" % ("depth_chain" if depth_mask else "rooms_images"))
-        self.ws = _bytes(self.ws_bytes)
+        self._size(B)
+        self._allocate()
         self.reset(trans, rot)
         if name_panos:
             self.set_panos(panos)
+
+    def _size(self, B):
+        self.B, self.per_room, self.per_image = B, B // self.nrooms, B // self.nrooms // self.nimages
+        self._shape = (self._rooms, self.nrooms, self.nimages, self.per_image)        # (how every pcl_gd_*rooms_images / *depth_chain call begins)
+
+    def _workspace_bytes(self):
+        if self.depth_mask:
+            return _lib.load().pcl_gd_depth_chain_workspace_bytes(*self._shape, self.pano.H, self.pano.W, ctypes.byref(self.hyper))
+        return _lib.load().pcl_gd_rooms_images_workspace_bytes(*self._shape, ctypes.byref(self.hyper))
+
+    def _refusal(self, smaller):
+        return "pcl_gd_%s_workspace_bytes: invalid arguments" % ("depth_chain" if self.depth_mask else "rooms_images")
 
     def plan(self):
         """-> (nchunks per room, poses per block, fused): pcl_gd_plan_rooms_images; with the depth mask (never fused) a fourth item, per room
@@ -1459,29 +1480,7 @@ class GradientDescentRoomsImages(_GdEngine):
 
     def _same_problem(self, other):
         return (other.nrooms, other.nimages, other.color_sets, other.depth_mask) == (self.nrooms, self.nimages, self.color_sets, self.depth_mask) and \
-            [c.n for c in other.clouds] == [c.n for c in self.clouds] and \
-            (other.pano.H, other.pano.W, other.pano.fmt) == (self.pano.H, self.pano.W, self.pano.fmt)
-
-    def _smaller(self, keep):
-        """an engine over the same rooms, panoramas and hyper-parameters with `keep` candidates per (room, image), its state not yet written"""
-        lib = _lib.load()
-        if not 1 <= keep <= self.per_image:
-            raise ValueError("pruned: keep %d of %d candidates per (room, image)" % (keep, self.per_image))
-        g = type(self).__new__(type(self))
-        for name in ("pano", "clouds", "nrooms", "nimages", "color_sets", "boxes", "depth_mask", "_rooms"):
-            setattr(g, name, getattr(self, name))
-        g.per_image, g.per_room, g.B = keep, keep * self.nimages, keep * self.nimages * self.nrooms
-        g.hyper = _copy_hyper(self.hyper)
-        g._shape = (g._rooms, g.nrooms, g.nimages, g.per_image)
-        g.state = _bytes(lib.pcl_gd_state_bytes(g.B))
-        if g.depth_mask:
-            g.ws_bytes = lib.pcl_gd_depth_chain_workspace_bytes(*g._shape, g.pano.H, g.pano.W, ctypes.byref(g.hyper))
-        else:
-            g.ws_bytes = lib.pcl_gd_rooms_images_workspace_bytes(*g._shape, ctypes.byref(g.hyper))
-        if g.ws_bytes == 0:
-            raise _lib.PiccoloHipError("pcl_gd_%s_workspace_bytes: invalid arguments" % ("depth_chain" if g.depth_mask else "rooms_images"))
-        g.ws = _bytes(g.ws_bytes)
-        return g
+            [c.n for c in other.clouds] == [c.n for c in self.clouds] and other.pano.texels == self.pano.texels
 
 
 class GradientDescentRooms(GradientDescentRoomsImages):

@@ -8,37 +8,10 @@ import pytest
 import torch
 
 from conftest import Cfg
+from room_helpers import image_starts as _starts, per_image_colours as _per_image_colours
 from test_room_search import FUSED_SIZES, H, INIT, SIZES, W, _cfg, _query, _rooms, _single, _write_rooms_tree  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def _starts(nrooms, nimages, per_image, seed=3):
-    """starts[r][i] = (trans, rot) of image i in room r: around room r's ground-truth pose, another draw per image"""
-    from piccolo_amd import synth
-    out = []
-    for r in range(nrooms):
-        t, ypr = synth.room_gt_pose(r, seed + r)
-        row = []
-        for i in range(nimages):
-            tr, ro = synth.start_poses(t, ypr, per_image, seed=seed + 7 * r + 101 * i, sigma_t=0.4, sigma_r=0.2)
-            row.append((torch.from_numpy(tr).cuda(), torch.from_numpy(ro).cuda()))
-        out.append(row)
-    return out
-
-
-def _per_image_colours(rooms, nimages, seed=0):
-    """rooms whose rgb is a list: image i's own colours of every room (a per-image perturbation of the room's rgb, as color_mod gives)"""
-    out = []
-    for r, (xyz, rgb) in enumerate(rooms):
-        g = torch.Generator(device="cpu").manual_seed(seed + 13 * r)
-        cols = []
-        for i in range(nimages):
-            gain = 0.8 + 0.05 * i
-            noise = (torch.rand(rgb.shape, generator=g) * 0.1).to(rgb.device)
-            cols.append((rgb * gain + noise).clamp(0, 1).contiguous())
-        out.append((xyz, cols))
-    return out
 
 
 def _queries(rooms, nimages, seed):

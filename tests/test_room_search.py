@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import Cfg
+from room_helpers import query as _query, rooms as _rooms  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,20 +22,6 @@ def _cfg(**kw):
     base = dict(lr=0.1, num_iter=25, patience=5, factor=0.8, out_of_room_quantile=0.05, num_input=6)
     base.update(kw)
     return Cfg(**base)
-
-
-def _rooms(sizes, seed=0):
-    from piccolo_amd import synth
-    return [(torch.from_numpy(x).cuda(), torch.from_numpy(c).cuda()) for x, c in synth.rooms_side_by_side(sizes, seed)]
-
-
-def _query(rooms, r, seed, res=(H, W)):
-    """the panorama room r shows from room_gt_pose(r, seed) (its own cloud: the walls hide the other rooms)"""
-    from piccolo_amd import ops, synth
-    t, ypr = synth.room_gt_pose(r, seed)
-    xyz, rgb = rooms[r]
-    img = synth.quantise_like_image_file(ops.make_pano(ops.transform_cloud(xyz, torch.from_numpy(t), torch.from_numpy(ypr)), rgb, res))
-    return img, t, ypr
 
 
 def _starts(nrooms, per_room, seed=3):
