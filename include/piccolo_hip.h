@@ -218,6 +218,34 @@ size_t pcl_gn_workspace_bytes(int64_t n, int B);
 int pcl_gn_refine(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans,
                   const float *rot, int pose_stride, int B, const pcl_gn_hyper *hyper_host, int iters, void *state, float *out, float *info,
                   float *cov, float *trace, void *workspace, size_t workspace_bytes, void *stream);
+/* pcl_pose_information and pcl_gn_refine for the nimages winners of a chain over several query images of one cloud, in ONE set of launches
+ * (additive to ABI 12; BUILD-DEFINED): pose i = (trans + i * pose_stride, rot + i * pose_stride) is evaluated against panos_host[i] (HOST
+ * array of nimages device addresses of packed panoramas of one H, W and texel format; they travel as kernel arguments, 64 per pass launch:
+ * nothing is copied, nothing waits for the host, capturable), against colour set i of a cloud of pcl_cloud_pack_sets when color_sets ==
+ * nimages (color_sets 0 / 1: the cloud's one set, pcl_point_residuals_images' rule), and under
+ *   weights == NULL, weight_sets == 0         no weights;
+ *   weight_sets == 1                          the one packed plane `weights` for every image;
+ *   weight_sets == nimages                    plane i at weights + i * pcl_cloud_stride(n) (pcl_robust_weights_rows' layout; the planes of
+ *                                             pcl_gd_run_weight_sets).
+ * Record i (info, cov; for pcl_gn_refine_images also out, the state and the trace rows [iters + 1][nimages][16]) equals what
+ * pcl_pose_information / pcl_gn_refine returns for that pose, panorama, colour set and plane alone, bit for bit: the same per-point pass
+ * over chunks that depend on n only, the same partial rows, and the per-pose finish / init / step kernels themselves.  Poses never
+ * interact; the blocks of a frozen pose return before their point loop, per pose.  More than 64 images run in groups of 64 inside the
+ * call (one pass launch per group and evaluation; colour set and plane are counted from the call's first image).  Sizes:
+ * pcl_pose_information_workspace_bytes(n, nimages), pcl_gn_state_bytes(nimages), pcl_gn_workspace_bytes(n, nimages).  No atomics, no
+ * allocation, no synchronisation.
+ * PCL_EINVAL, before any launch: what pcl_pose_information / pcl_gn_refine refuse (B = nimages); a null panos_host or a zero entry;
+ * weights == NULL with weight_sets != 0, weights with a weight_sets that is neither 1 nor nimages; color_sets < 0, or > 1 and not nimages;
+ * weight planes or colour sets of 2^31 bytes or more together (one buffer resource each).
+ * Deliberately left out: the rooms and depth chains, a forward-only loss launch for a colour set or a per-image plane (the weighted
+ * sampling loss at a returned pose is S1 / M of its info record), and any claim that cov is calibrated on real data. */
+int pcl_pose_information_images(const float *cloud, const float *weights, int weight_sets, int64_t n, int color_sets, const uint64_t *panos_host,
+                                int nimages, int pano_format, int H, int W, const float *trans, const float *rot, int pose_stride, float *info,
+                                float *cov, void *workspace, size_t workspace_bytes, void *stream);
+int pcl_gn_refine_images(const float *cloud, const float *weights, int weight_sets, int64_t n, int color_sets, const uint64_t *panos_host, int nimages,
+                         int pano_format, int H, int W, const float *trans, const float *rot, int pose_stride, const pcl_gn_hyper *hyper_host,
+                         int iters, void *state, float *out, float *info, float *cov, float *trace, void *workspace, size_t workspace_bytes,
+                         void *stream);
 /* The Morton order in one call, entirely on the device: bounding box, 63-bit keys, stable radix sort of (key, index);
  * order[i] = index of the point for packed slot i.  workspace: pcl_cloud_order_workspace_bytes(n). */
 size_t pcl_cloud_order_workspace_bytes(int64_t n);

@@ -22,6 +22,8 @@
 //                             pcl_pose_information forms them with.
 // No atomics, no scratch, no host synchronisation, no allocation: capturable (the hyper-parameters are kernel arguments, read from the host
 // struct when the call is enqueued).  Poses never interact: pose b of a batch has the bits of its own call.
+// pcl_gn_refine_images is the same chain for poses that each have their own panorama, colour set and weight plane (the winners of a chain
+// over several query images): pcl_gn_pass_images_kernel in place of the pass, the init and step kernels as they are.
 #include <math.h>
 
 #include "pcl_info_device.h"
@@ -66,7 +68,19 @@ template <int FMT, bool WT>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_pass_kernel(PclInfoArgs a, const PclGnState* __restrict__ state)
 {
     if (state[blockIdx.x % (unsigned)a.pass.B].frozen) return;      // (a scalar load: the address depends on the block alone)
-    pcl_info_pass<FMT, WT>(a);
+    pcl_info_pass<FMT, WT>(a, a.pass.pano, 1, 0, 1, 0, blockIdx.x);
+}
+
+// The gated pass of pcl_gn_refine_images: pcl_pose_info_images_kernel's block (pose b against panorama b, colour set and weight plane
+// b + img0, partial row chunk * btot + img0 + b) behind the same gate, per pose: `state` is the launch's first image's.
+template <int FMT, bool WT, bool CS>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_pass_images_kernel(PclInfoArgs a, PclInfoImages im, const PclGnState* __restrict__ state)
+{
+    const unsigned b = blockIdx.x % (unsigned)a.pass.B, chunk = blockIdx.x / (unsigned)a.pass.B;      // (from the block index: uniform)
+    if (state[b].frozen) return;
+    const unsigned g = b + (unsigned)im.img0;
+    pcl_info_pass<FMT, WT, CS>(a, (const void*)im.panos.p[b], im.sets, g, im.wsets, im.wsets > 1 ? (int)g * ((int)a.pass.stride * 4) : 0,
+                               chunk * (unsigned)im.btot + g);
 }
 
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_step_kernel(const float* __restrict__ partials, int nchunks, int B, PclGnState* __restrict__ state,
@@ -222,6 +236,50 @@ extern "C" int pcl_gn_refine(const float* cloud, const float* weights, int64_t n
         });
         PCL_LAUNCH_CHECK();
         hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)B), blk, 0, s, (const float*)a.partials, (int)nchunks, B, st, hp, k, iters, out, info, cov, trace);
+        PCL_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// pcl_gn_refine for nimages poses, each against ITS OWN panorama, colour set and weight plane, in one chain: the init and step launches run
+// over all the images (they are per pose and do not care which image a pose belongs to), the gated pass runs once per
+// PCL_RES_MAX_IMAGES images into the call's [nchunks][nimages] partial rows.  1 + (groups + 1) (iters + 1) launches.
+extern "C" int pcl_gn_refine_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets, const uint64_t* panos_host,
+                                    int nimages, int pano_format, int H, int W, const float* trans, const float* rot, int pose_stride,
+                                    const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info, float* cov, float* trace,
+                                    void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!hyper_host || !state || !out || !info || !workspace) return PCL_EINVAL;
+    if (iters < 0 || iters > PCL_GN_MAX_ITERS || !gn_hyper_ok(hyper_host)) return PCL_EINVAL;
+    PclInfoArgs a;
+    PclInfoImages im;
+    int64_t nchunks;
+    const int rc = pcl_info_images_args(&a, &im, cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot,
+                                        pose_stride, &nchunks);
+    if (rc) return rc;
+    if (workspace_bytes < pcl_gn_workspace_bytes(n, nimages)) return PCL_EINVAL;
+    PclGnState* st = (PclGnState*)state;
+    a.partials = (float*)workspace;
+    a.pass.trans = st->tri; a.pass.rot = st->tri + 3; a.pass.pose_stride = (int)(sizeof(PclGnState) / sizeof(float));
+    const pcl_gn_hyper hp = *hyper_host;
+    const dim3 blk(PCL_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(pcl_gn_init_kernel, dim3((unsigned)nimages), blk, 0, s, st, trans, rot, pose_stride, hp.lam0, trace, nimages, iters);
+    PCL_LAUNCH_CHECK();
+    for (int k = 0; k <= iters; k++) {
+        pcl_info_images_launches(a, im, panos_host, nchunks, [&](const PclInfoArgs& al, const PclInfoImages& il, int i0, dim3 grid) {
+            pcl_with_flag(weights != nullptr, [&](auto wt) {
+                pcl_with_flag(color_sets > 1, [&](auto cs) {
+                    pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+                        hipLaunchKernelGGL((pcl_gn_pass_images_kernel<decltype(fmt)::value, decltype(wt)::value, decltype(cs)::value>), grid, blk, 0, s,
+                                           al, il, (const PclGnState*)(st + i0));
+                    });
+                });
+            });
+        });
+        PCL_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)nimages), blk, 0, s, (const float*)a.partials, (int)nchunks, nimages, st, hp, k, iters, out,
+                           info, cov, trace);
         PCL_LAUNCH_CHECK();
     }
     return 0;

@@ -28,7 +28,19 @@
 template <int FMT, bool WT>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_kernel(PclInfoArgs a)
 {
-    pcl_info_pass<FMT, WT>(a);
+    pcl_info_pass<FMT, WT>(a, a.pass.pano, 1, 0, 1, 0, blockIdx.x);
+}
+
+// Pose b against panorama b (pcl_pose_information_images): block chunk * a.pass.B + b of a launch of a.pass.B images evaluates pose b
+// against im.panos.p[b], with CS colour set b + img0 and with per-image planes (im.wsets > 1) weight plane b + img0, into partial row
+// chunk * btot + img0 + b.  The same pass: row b has the bits of pcl_pose_info_kernel's row for that pose, panorama, set and plane alone.
+template <int FMT, bool WT, bool CS>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_images_kernel(PclInfoArgs a, PclInfoImages im)
+{
+    const unsigned b = blockIdx.x % (unsigned)a.pass.B, chunk = blockIdx.x / (unsigned)a.pass.B;      // (from the block index: uniform)
+    const unsigned g = b + (unsigned)im.img0;
+    pcl_info_pass<FMT, WT, CS>(a, (const void*)im.panos.p[b], im.sets, g, im.wsets, im.wsets > 1 ? (int)g * ((int)a.pass.stride * 4) : 0,
+                               chunk * (unsigned)im.btot + g);
 }
 
 // (pcl_info_device.h restates the row sum, the chain rule, the factorisation and the record below as device functions for pcl_gn_step_kernel;
@@ -183,6 +195,39 @@ extern "C" int pcl_pose_information(const float* cloud, const float* weights, in
     PCL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, B, trans, rot,
                        pose_stride, info, cov);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
+// Record i = pcl_pose_information of pose i against panos_host[i], colour set i and weight plane i: one pass launch per PCL_RES_MAX_IMAGES
+// images into the call's [nchunks][nimages] partial rows (the chunking depends on n alone), then pcl_pose_info_finish_kernel over all of them.
+extern "C" int pcl_pose_information_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets,
+                                           const uint64_t* panos_host, int nimages, int pano_format, int H, int W, const float* trans, const float* rot,
+                                           int pose_stride, float* info, float* cov, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!info || !workspace) return PCL_EINVAL;
+    PclInfoArgs a;
+    PclInfoImages im;
+    int64_t nchunks;
+    const int rc = pcl_info_images_args(&a, &im, cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot,
+                                        pose_stride, &nchunks);
+    if (rc) return rc;
+    if (workspace_bytes < pcl_pose_information_workspace_bytes(n, nimages)) return PCL_EINVAL;
+    a.partials = (float*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    pcl_info_images_launches(a, im, panos_host, nchunks, [&](const PclInfoArgs& al, const PclInfoImages& il, int, dim3 grid) {
+        pcl_with_flag(weights != nullptr, [&](auto wt) {
+            pcl_with_flag(color_sets > 1, [&](auto cs) {
+                pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+                    hipLaunchKernelGGL((pcl_pose_info_images_kernel<decltype(fmt)::value, decltype(wt)::value, decltype(cs)::value>), grid,
+                                       dim3(PCL_BLOCK), 0, s, al, il);
+                });
+            });
+        });
+    });
+    PCL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)nimages), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, nimages,
+                       trans, rot, pose_stride, info, cov);
     PCL_LAUNCH_CHECK();
     return 0;
 }

@@ -16,17 +16,29 @@
 
 struct PclInfoArgs {
     PclPassArgs pass;
-    const float* weights;    // WT: one more plane of `stride` floats, packed order
-    float* partials;         // [nchunks][B][PCL_INFO_ROW]
+    const float* weights;    // WT: one more plane of `stride` floats, packed order (the images instances: one per image, back to back)
+    float* partials;         // [nchunks][B][PCL_INFO_ROW] (the images instances: B = the call's image count)
+};
+
+// What the images instances (pose b against panorama b) take beside PclInfoArgs: this launch's panorama addresses, and where the launch
+// sits in its call — a.pass.B is the LAUNCH's pose count, `img0` its first image, `btot` the call's image count (the partial rows are
+// [nchunks][btot]), `sets` the cloud's colour sets and `wsets` the weight resource's planes (1: one plane for every image).
+struct PclInfoImages {
+    PclResPanos panos;
+    int sets, img0, btot, wsets;
 };
 
 // The whole per-point pass of a block: the pass of pcl_point_pass.h with the weighted gradient instance of pcl_sample2 under UNIT weight,
-// the 30 packed-fp32 accumulators, and the block's sums in a fixed order into partial row blockIdx.x.
-template <int FMT, bool WT>
-__device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a)
+// the 30 packed-fp32 accumulators, and the block's sums in a fixed order into partial row `row`.  The block's panorama is `pano_b`; with
+// CS it reads colour set `set` of `sets`; with WT the weight resource covers `wsets` planes of `stride` floats and the block reads the
+// one at byte offset `wplane`, which goes through the load's scalar offset (wave-uniform), as the loss kernel's wsets instances do it.
+// The single-image kernels pass a.pass.pano, one set, one plane at offset 0 and row blockIdx.x as literals: their instruction streams
+// are those of the pass before it took these arguments.
+template <int FMT, bool WT, bool CS = false>
+__device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a, const void* pano_b, int sets, unsigned set, int wsets, int wplane, unsigned row)
 {
     __amdgpu_buffer_rsrc_t wrs;
-    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(a.pass.stride * 4), 0x00020000);
+    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(a.pass.stride * 4) * wsets, 0x00020000);
 
     f2 hh[21], bb[6], s2 = F2(0.f), s1 = F2(0.f), mm = F2(0.f);
 #pragma unroll
@@ -34,11 +46,11 @@ __device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a)
 #pragma unroll
     for (int k = 0; k < 6; k++) bb[k] = F2(0.f);
 
-    pcl_point_pass<FMT, true, false>(a.pass, a.pass.pano, 1, 0, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool) {
+    pcl_point_pass<FMT, true, CS>(a.pass, pano_b, sets, set, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool) {
         // acc: 0 l, 1 m, 2-4 g, 5-7 tau of this pair of points alone.  One factor w (a slot past n never counts, whatever its plane holds)
         f2 w = F2(1.f), wl = acc[0], wm = acc[1], wa[6];
         if constexpr (WT) {
-            w = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(wrs, j * 4, 0, 0));
+            w = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(wrs, j * 4, wplane, 0));
             w = (f2){valid0 ? w.x : 0.f, valid1 ? w.y : 0.f};
             wl = w * acc[0]; wm = w * acc[1];
         }
@@ -73,7 +85,7 @@ __device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a)
     __syncthreads();
     if (threadIdx.x < PCL_INFO_ROW) {
         const int k = threadIdx.x;
-        a.partials[(int64_t)blockIdx.x * PCL_INFO_ROW + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+        a.partials[(int64_t)row * PCL_INFO_ROW + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
     }
 }
 
@@ -200,4 +212,46 @@ __device__ __forceinline__ void pcl_info_emit(const double (*Hm)[6], const doubl
             const float c = (float)ldexp(sigma2 * t, -e);
             cv[6 * i + m] = c; cv[6 * m + i] = c;
         }
+}
+
+// ---- host side of the images entry points (pcl_pose_information_images, pcl_gn_refine_images): every check, before any launch
+// weights == NULL with weight_sets 0; else weight_sets 1 (one plane for every image) or nimages (plane i at weights + i * stride);
+// color_sets 0 / 1 (the cloud's one set) or nimages (pcl_point_residuals_images' rule).  Fills a (a.pass.B = nimages, a.pass.pano = the
+// first panorama) and what the launches of one call share of im; a launch sets im->panos, im->img0 and its own pose count.
+static inline int pcl_info_images_args(PclInfoArgs* a, PclInfoImages* im, const float* cloud, const float* weights, int weight_sets, int64_t n,
+                                       int color_sets, const uint64_t* panos_host, int nimages, int pano_format, int H, int W, const float* trans,
+                                       const float* rot, int pose_stride, int64_t* nchunks_out)
+{
+    if (!panos_host || nimages <= 0) return PCL_EINVAL;
+    for (int i = 0; i < nimages; i++)
+        if (!panos_host[i]) return PCL_EINVAL;
+    if (weights ? (weight_sets != 1 && weight_sets != nimages) : weight_sets != 0) return PCL_EINVAL;
+    if (color_sets < 0 || (color_sets > 1 && color_sets != nimages)) return PCL_EINVAL;
+    const int rc = pcl_pass_args(&a->pass, cloud, n, (const void*)panos_host[0], pano_format, H, W, trans, rot, pose_stride, nimages, PCL_INFO_MIN_STEPS,
+                                 nchunks_out);
+    if (rc) return rc;
+    // one buffer resource each: the weight planes and the colour sets stay below 2^31 bytes
+    if (weights && a->pass.stride * 4 * (int64_t)weight_sets >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    if (color_sets > 1 ? pcl_cloud_sets_bytes(n, color_sets) == 0 : a->pass.stride * 6 * 4 >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    a->weights = weights;
+    im->sets = color_sets > 1 ? color_sets : 1; im->img0 = 0; im->btot = nimages; im->wsets = weights ? weight_sets : 1;
+    return 0;
+}
+
+// The launches of one evaluation of all the images: launch(al, il, grid) for every run of at most PCL_RES_MAX_IMAGES images, with the
+// poses sliced (pose_stride floats per pose from a.pass.trans / rot) and the colour set, weight plane and partial row counted from the
+// call's first image
+template <class F>
+static inline void pcl_info_images_launches(const PclInfoArgs& a, const PclInfoImages& im, const uint64_t* panos_host, int64_t nchunks, F&& launch)
+{
+    for (int i0 = 0; i0 < im.btot; i0 += PCL_RES_MAX_IMAGES) {
+        const int m = im.btot - i0 < PCL_RES_MAX_IMAGES ? im.btot - i0 : PCL_RES_MAX_IMAGES;
+        PclInfoImages il = im;
+        for (int i = 0; i < PCL_RES_MAX_IMAGES; i++) il.panos.p[i] = i < m ? (unsigned long long)panos_host[i0 + i] : 0ull;
+        il.img0 = i0;
+        PclInfoArgs al = a;
+        al.pass.trans = a.pass.trans + (int64_t)i0 * a.pass.pose_stride; al.pass.rot = a.pass.rot + (int64_t)i0 * a.pass.pose_stride;
+        al.pass.B = m;
+        launch(al, il, i0, dim3((unsigned)(nchunks * m)));
+    }
 }

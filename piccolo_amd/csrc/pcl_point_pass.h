@@ -21,6 +21,11 @@ struct PclPassArgs {
     int steps_base, steps_rem;   // the cloud's ceil(n / PCL_PASS_STEP) steps dealt out evenly: chunk c has steps_base + (c < steps_rem)
 };
 
+// Row i = pose i against panorama i: the panorama addresses of the kernels that take one image per pose travel as kernel arguments, up to
+// PCL_RES_MAX_IMAGES per launch (pcl_residual.hip's residual rows, pcl_info.hip's and pcl_gn.hip's images instances)
+#define PCL_RES_MAX_IMAGES 64
+struct PclResPanos { unsigned long long p[PCL_RES_MAX_IMAGES]; };
+
 // The pose as six SGPR pairs (R0,R1)(R2,R3)(R4,R5)(R6,R7)(R8,t0)(t1,t2): every lane computes the same R from yaw / pitch / roll
 // (pcl_rot_from_ypr, what pcl_sampling_loss's pose records hold), the first one's is read.  pose_ok (wave-uniform): R and t finite.
 __device__ __forceinline__ PclPose6 pcl_pass_pose(const PclPassArgs& a, unsigned b, bool& pose_ok)

@@ -70,10 +70,8 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_point_residuals_kernel(PclResAr
 }
 
 // Row i = pose i against panorama i (and colour set i): the panorama addresses travel as kernel arguments, up to PCL_RES_MAX_IMAGES per
-// launch; `img0` is the first image of this launch (the colour set counts from the call's first image, a.pass.B is this launch's pose count)
-#define PCL_RES_MAX_IMAGES 64
-struct PclResPanos { unsigned long long p[PCL_RES_MAX_IMAGES]; };
-
+// launch (PclResPanos, pcl_point_pass.h); `img0` is the first image of this launch (the colour set counts from the call's first image,
+// a.pass.B is this launch's pose count)
 template <int FMT, bool ORDERED, bool CS>
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_point_residuals_images_kernel(PclResArgs a, PclResPanos panos, int sets, int img0)
 {

@@ -24,8 +24,8 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import (ROBUST_KEYS, _is_int, _refuse, omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_robust,
-                      omniloc_batch_rooms_images, robust_schedule)
+from .omniloc import (GN_KEYS, ROBUST_KEYS, _is_int, _refuse, gn_schedule, omniloc_all, omniloc_batch, omniloc_batch_images,
+                      omniloc_batch_images_polished, omniloc_batch_images_robust, omniloc_batch_rooms_images, pose_covariance_flag, robust_schedule)
 from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
 
@@ -90,8 +90,37 @@ def _check_robust_cfg(cfg):
         return
 
 
+def _check_polish_cfg(cfg, who):
+    """Configuration-time rules of the polish keys (cfg.gn_iters / gn_step_cap / gn_lambda) and cfg.pose_covariance in a dataset loop, before
+    any file is read.  Without cfg.polish_images_per_launch the loop `who` refuses them, as it always did.  With it — an int >= 1, the group
+    size of a known-room run routed through omniloc_batch_images_polished (a group of one: refine_image) — the run needs cfg.parallel and at
+    least one of those keys, and does not combine with room_search, room_search_images, images_per_launch > 1 or robust_images_per_launch
+    (a robust polished run groups by polish_images_per_launch).  -> the group size, or None without the key"""
+    ppl = getattr(cfg, "polish_images_per_launch", None)
+    if ppl is None:
+        _refuse(cfg, who, "pose_covariance", "gn")
+        return None
+    if not _is_int(ppl) or ppl < 1:
+        raise ValueError("cfg.polish_images_per_launch %r: an int >= 1" % (ppl,))
+    if not getattr(cfg, "parallel", False):
+        raise ValueError("cfg.polish_images_per_launch needs cfg.parallel (the polished chain has parallel semantics only)")
+    if all(getattr(cfg, key, None) is None for key in GN_KEYS) and not getattr(cfg, "pose_covariance", None):
+        raise ValueError("cfg.polish_images_per_launch goes with cfg.gn_iters and / or cfg.pose_covariance (images_per_launch groups a plain run)")
+    for other in ("room_search", "room_search_images", "robust_images_per_launch"):
+        if getattr(cfg, other, None):
+            raise ValueError("cfg.polish_images_per_launch does not combine with cfg.%s" % other)
+    if int(getattr(cfg, "images_per_launch", 1)) > 1:
+        raise ValueError("cfg.polish_images_per_launch does not combine with images_per_launch > 1 (it is the polished run's group size)")
+    gn_schedule(cfg)                                  # (their own ValueErrors, before any file is read)
+    pose_covariance_flag(cfg)
+    return int(ppl)
+
+
 def _group_size(cfg):
-    """images per group of the known-room loops: cfg.images_per_launch, or under the robust keys cfg.robust_images_per_launch (default 1)"""
+    """images per group of the known-room loops: cfg.images_per_launch; under the robust keys cfg.robust_images_per_launch (default 1); with
+    cfg.polish_images_per_launch that (a robust polished run too)"""
+    if getattr(cfg, "polish_images_per_launch", None) is not None:
+        return int(cfg.polish_images_per_launch)
     if getattr(cfg, "robust_iters", None) is not None:
         return int(getattr(cfg, "robust_images_per_launch", None) or 1)
     return int(getattr(cfg, "images_per_launch", 1))
@@ -456,7 +485,8 @@ def _localize_known_room(cfg, jobs):
     group's cloud then holds one colour set per image, and every image's results are those of its own one-image calls, bit for bit.  When
     every job shares one rgb tensor it is passed as that tensor (the shared-colour path).  Grouping by colour sets was measured to beat
     one image at a time at the shipped and at the cfg-2 shape (tools/color_sets_bench.py).  One job: make_input_images is
-    make_input, and the refinement is refine_image."""
+    make_input, and the refinement is refine_image.  Under cfg.polish_images_per_launch (the gn keys and / or pose_covariance) a group goes
+    through omniloc_batch_images_polished — the plain, robust or pruned chain, then the polish and / or covariance of all winners at once."""
     xyz = jobs[0].xyz
     rgb = jobs[0].rgb if all(j.rgb is jobs[0].rgb for j in jobs) else [j.rgb for j in jobs]
     starts = make_input_images([j.img_init for j in jobs], xyz, rgb, *_make_input_args(cfg))
@@ -465,10 +495,54 @@ def _localize_known_room(cfg, jobs):
             j.on_start(tr, ro)
     if len(jobs) == 1:
         return [refine_image(jobs[0].img_main, xyz, rgb, *starts[0], cfg)]
+    if getattr(cfg, "polish_images_per_launch", None) is not None:      # (the gn keys and / or pose_covariance: the chain, then all winners at once)
+        return [tuple(r) for r in omniloc_batch_images_polished([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts],
+                                                                [ro for _, ro in starts], cfg)]
     if getattr(cfg, "robust_iters", None) is not None:       # (a group under the robust keys: cfg.robust_images_per_launch, parallel only)
         return omniloc_batch_images_robust([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg)
     return omniloc_batch_images([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg,
                                 batch_mode=bool(getattr(cfg, "parallel", False)))
+
+
+SIGMA_HEADER = ["sigma_t (m)", "sigma_r (degrees)"]
+
+
+def pose_sigmas(cov):
+    """(sigma_t in metres, sigma_r in degrees) of a (6, 6) pose covariance of (t, yaw, pitch, roll): sqrt(trace(cov[:3, :3])) and
+    degrees(sqrt(trace(cov[3:, 3:]))); NaN where cov is"""
+    cov = np.asarray(cov, dtype=np.float64).reshape(6, 6)
+    return float(np.sqrt(np.trace(cov[:3, :3]))), float(np.degrees(np.sqrt(np.trace(cov[3:, 3:]))))
+
+
+def _run_known_room(cfg, writer, log_dir, filenames, dataset, csv_name, header, row_prefix, success):
+    """_run_dataset of a known-room loop.  With cfg.pose_covariance (a polished run: every result carries cov as its fourth entry) the CSV
+    gains two last columns, sigma_t (m) and sigma_r (degrees) (pose_sigmas; empty where cov is NaN), gathered across the ranks the way the
+    room search's found_room is: every rank notes its own images' values when it reports them, and they travel through the all_gather of
+    the result rows.  Without the key the header and the rows are unchanged."""
+    if not getattr(cfg, "pose_covariance", None):
+        return _run_dataset(writer, log_dir, filenames, dataset, _group_size(cfg), csv_name, header, row_prefix, success)
+    local, every = {}, {}
+
+    def report(k, job, result, row):
+        local[k] = pose_sigmas(result[3])
+        dataset.report(k, job, result, row)
+
+    def gather():
+        rank, world = pdist.world()
+        mine = pdist.shard(len(filenames), rank, world)
+        rows = torch.full((len(mine), 2), float("nan"), dtype=torch.float32)
+        for j, k in enumerate(mine):
+            if k in local:
+                rows[j] = torch.tensor(local[k], dtype=torch.float32)
+        table = pdist.gather_rows(rows.to(ops.device()) if torch.cuda.is_available() else rows, len(filenames), rank, world).cpu().numpy()
+        every.clear()
+        every.update({k: table[k] for k in range(len(filenames))})
+
+    def suffix(k):
+        return ["" if np.isnan(v) else float(v) for v in every.get(k, (np.nan, np.nan))]
+
+    return _run_dataset(writer, log_dir, filenames, dataset._replace(report=report), _group_size(cfg), csv_name, header + SIGMA_HEADER, row_prefix,
+                        success, row_suffix=suffix, on_gathered=gather)
 
 
 def _seed_all():
@@ -520,10 +594,12 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     """Stanford2D-3D-S loop (localize.py:76-297) over `root`/pano/area_*/ *.png, pcd_not_aligned/area_*/<room>.txt and
     pose/area_*/ *.json; writes `stanford_results.csv` with the reference's columns and result images under results/.
     cfg.images_per_launch is the group size of _run_dataset (_localize_known_room); under cfg.robust_iters it is cfg.robust_images_per_launch.
+    cfg.polish_images_per_launch (_check_polish_cfg): the group size of a run that carries the gn keys and / or cfg.pose_covariance, routed
+    through omniloc_batch_images_polished; with cfg.pose_covariance the CSV gains sigma_t (m) and sigma_r (degrees) (_run_known_room).
     cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms)."""
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
-    _refuse(cfg, "localize_stanford", "pose_covariance", "gn")
+    _check_polish_cfg(cfg, "localize_stanford")
     room_search = getattr(cfg, "room_search", None)
     if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
         raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")
@@ -570,8 +646,8 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     def report(k, job, result, row):
         _stanford_report(filenames[k], log_dir, job, job.xyz, job.show_rgb, result, row)
 
-    return _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
-                        _group_size(cfg), "stanford_results.csv", STANFORD_HEADER, _stanford_row_prefix, stanford_success)
+    return _run_known_room(cfg, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
+                           "stanford_results.csv", STANFORD_HEADER, _stanford_row_prefix, stanford_success)
 
 
 def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search):
@@ -662,10 +738,10 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
     """OmniScenes loop (localize.py:300-530) over `root`/<split>_pano/<video>/<frame>, pcd/<room>.txt and <split>_pose;
     writes `omniscenes_results.csv`.  Includes the synthetic illumination changes (synth_const / synth_gamma / synth_wb)
     and the colour preprocessing of the whole image (match_color / sharpen_color).  cfg.images_per_launch is the group size of
-    _run_dataset (_localize_known_room)."""
+    _run_dataset (_localize_known_room); cfg.polish_images_per_launch and the CSV's sigma columns as in localize_stanford."""
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
-    _refuse(cfg, "localize_omniscenes", "pose_covariance", "gn")
+    _check_polish_cfg(cfg, "localize_omniscenes")
     _seed_all()
     dev = ops.device()
     split = getattr(cfg, "split_name", "extreme")
@@ -720,6 +796,5 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
             _save_result_image(os.path.join(log_dir, "results", video, stem + ".png"), job.orig, job.xyz, job.show_rgb, result[0], result[1],
                                (job.img_main.shape[0] // 2, job.img_main.shape[1] // 2))
 
-    return _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
-                        _group_size(cfg), "omniscenes_results.csv", OMNISCENES_HEADER,
-                        lambda f: ["{}/{}".format(*f.split("/")[-2:])], omniscenes_success)
+    return _run_known_room(cfg, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
+                           "omniscenes_results.csv", OMNISCENES_HEADER, lambda f: ["{}/{}".format(*f.split("/")[-2:])], omniscenes_success)

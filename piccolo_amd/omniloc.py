@@ -27,6 +27,10 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
   * extra, optional cfg key pose_covariance (a bool, default absent = reference behaviour): omniloc_batch appends the 6 x 6 covariance of
     (t, yaw, pitch, roll) at the pose it returns (pose_covariance_flag, csrc/pcl_info.hip); pose_information / pose_covariance give the
     information matrix and the covariance at any poses to a caller;
+  * extra, optional cfg keys gn_iters / gn_step_cap / gn_lambda (default absent = reference behaviour): omniloc_batch polishes its winner
+    by a Levenberg-Marquardt chain on the device (gn_schedule, csrc/pcl_gn.hip); omniloc_batch_images_polished does that, and / or the
+    covariance, for all query images of a shared chain at once (pose_information_images / gauss_newton_refine_images give the several-image
+    calls to a caller);
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
     per iteration) as 4th element.
@@ -233,9 +237,12 @@ ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
 GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda")
 _EXTENSIONS = {
     "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
-    "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust and localize.refine_image's parallel branch do"),
-    "pose_covariance": (("pose_covariance",), None, "omniloc_batch and localize.refine_image's parallel branch do"),
-    "gn": (GN_KEYS, None, "omniloc_batch and localize.refine_image's parallel branch do"),
+    "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust, omniloc_batch_images_polished and localize.refine_image's parallel "
+                                  "branch do"),
+    "pose_covariance": (("pose_covariance",), None, "omniloc_batch, omniloc_batch_images_polished and localize.refine_image's parallel branch do; the "
+                                                    "dataset loops with cfg.polish_images_per_launch"),
+    "gn": (GN_KEYS, None, "omniloc_batch, omniloc_batch_images_polished and localize.refine_image's parallel branch do; the dataset loops with "
+                          "cfg.polish_images_per_launch"),
 }
 
 
@@ -486,6 +493,62 @@ def pose_covariance(img, xyz, rgb, trans, rot, weights=None):
     return cov, stats[:, 3], stats[:, 4]
 
 
+def _images_cloud(who, imgs, xyz, rgb, weights):
+    """The packed cloud and panoramas of the several-image forms below: rgb one (N, 3) tensor (with optional (N,) weights) or a list of one
+    per image (one colour set per image; no weights)"""
+    rgb = shared_rgb(rgb)
+    if isinstance(rgb, list):
+        if len(rgb) != len(imgs):
+            raise ValueError("%s: %d colour sets for %d images" % (who, len(rgb), len(imgs)))
+        if weights is not None:
+            raise ValueError("%s: per-point weights do not combine with per-image colour sets" % who)
+        if len(rgb) == 1:
+            rgb = rgb[0]
+    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb, weights)
+    return cloud, _chain_panos(list(imgs), xyz.shape[0])
+
+
+def pose_information_images(imgs, xyz, rgb, trans, rot, weights=None):
+    """pose_information for several query images of one cloud in one set of launches (ops.pose_information_images): row i of (H, b, stats,
+    cov) is pose (trans[i], rot[i]) against imgs[i] — and rgb[i], when rgb is a list of one colour tensor per image.  weights: (N,) per-point
+    weights in the order of xyz's rows, shared by the images (one colour tensor only)."""
+    cloud, panos = _images_cloud("pose_information_images", imgs, xyz, rgb, weights)
+    return ops.pose_information_images(cloud, panos, trans, rot)
+
+
+def gauss_newton_refine_images(imgs, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, **hyper):
+    """gauss_newton_refine for several query images of one cloud in ONE chain (ops.gauss_newton_refine_images): pose i is polished against
+    imgs[i] — and rgb[i], when rgb is a list of one colour tensor per image.  Row i of every entry equals the single-image call's."""
+    cloud, panos = _images_cloud("gauss_newton_refine_images", imgs, xyz, rgb, weights)
+    return ops.gauss_newton_refine_images(cloud, panos, trans, rot, iters=iters, trace=trace, **hyper)
+
+
+POLISHED_ROW = 52      # floats per image a polished chain copies to the host: t (3), R (9), loss, took, S1, M, cov (36)
+
+
+def _winners_polished(gd, cloud, panos, wins, gn, want_cov):
+    """What omniloc_batch does for its one winner, for the (I, 16) winners rows `wins` of the chain `gd` (an engine or a _PrunedChain) at
+    once -> (I, POLISHED_ROW) on the GPU.  With gn: one gauss_newton_refine_images_at_winners under the weight planes the chain's last
+    forward ran with; where the polish took a step (accepted > 1, status 0 or 3) t and R are the polished pose's, `took` is 1 and S1, M are
+    those of the polish's info record at that pose (the caller forms the loss S1 / M), else the chain's own t, R, loss.  cov: the polish's
+    own, or pose_information_images_at_winners' when there is no polish (zeros when not wanted)."""
+    I = int(wins.shape[0])
+    engine = gd.last if isinstance(gd, _PrunedChain) else gd
+    planes = engine._run_weights()
+    if planes is not None:
+        planes = planes.view(I, -1) if engine.weight_sets else None          # (a plain chain's cloud plane is the cloud's own)
+    zero = torch.zeros(I, 3, dtype=torch.float32, device=wins.device)
+    if gn is None:
+        cov = ops.pose_information_images_at_winners(cloud, panos, wins, planes=planes)[3]
+        return torch.cat([wins[:, 0:13], zero, cov.reshape(I, 36)], dim=1)
+    res = ops.gauss_newton_refine_images_at_winners(cloud, panos, wins, iters=gn[0], planes=planes, **gn[1])
+    R = ops.rot_from_ypr(res["rot"]).reshape(I, 9)
+    took = ((res["accepted"] > 1) & ((res["status"] == 0) | (res["status"] == 3))).reshape(I, 1)
+    rows = torch.where(took, torch.cat([res["trans"], R, zero[:, 0:1]], dim=1), wins[:, 0:13])
+    cov = res["cov"].reshape(I, 36) if want_cov else torch.zeros(I, 36, dtype=torch.float32, device=wins.device)
+    return torch.cat([rows, took.to(torch.float32), res["stats"][:, 1:2], res["stats"][:, 0:1], cov], dim=1)
+
+
 def _winner_cloud(gd, cloud):
     """`cloud` under the weight plane the last forward of the chain `gd` (an engine or a _PrunedChain) ran with"""
     engine = gd.last if isinstance(gd, _PrunedChain) else gd
@@ -657,21 +720,25 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, we
                          replay=vis_hook is None), trans, rot, cfg)
 
 
-def _refine_groups(chain, trans_list, rot_list):
+def _refine_groups(chain, trans_list, rot_list, polish=None):
     """The groups of one chain, start to end: trans_list / rot_list hold one (B, 3) tensor of starting poses per group of candidates (an
     image, a room, a room's image: the same B everywhere), chain(tr, ro) runs the engine over their concatenation.  -> per group
     [t (3,1), R (3,3), loss ()] of the candidate with the smallest last loss (omniloc.py:271), after ONE D2H copy, the leaf rows written
-    back into the callers' tensors."""
+    back into the callers' tensors.  polish(gd, winners) -> a GPU tensor of one row per group, made from the winners rows on the device:
+    it is what the one D2H copy brings, and it is returned as it is (omniloc_batch_images_polished)."""
     n, B = len(trans_list), int(trans_list[0].shape[0])
     tr = torch.cat([ops._dev(t).reshape(B, 3) for t in trans_list])
     ro = torch.cat([ops._dev(r).reshape(B, 3) for r in rot_list])
     gd = chain(tr, ro)
     leaf_t, leaf_r = torch.empty(n * B, 3, dtype=torch.float32, device=tr.device), torch.empty(n * B, 3, dtype=torch.float32, device=tr.device)
-    host = gd.winners(n, leaf_t, leaf_r).cpu()
+    wins = gd.winners(n, leaf_t, leaf_r)
+    host = (wins if polish is None else polish(gd, wins)).cpu()
     with torch.no_grad():
         for k, (t, r) in enumerate(zip(trans_list, rot_list)):
             t.copy_(leaf_t[k * B:(k + 1) * B].reshape(t.shape).to(t.device))
             r.copy_(leaf_r[k * B:(k + 1) * B].reshape(r.shape).to(r.device))
+    if polish is not None:
+        return host
     return [[host[k, 0:3].reshape(3, 1).clone(), host[k, 3:12].reshape(3, 3).clone(), host[k, 12].clone()] for k in range(n)]
 
 
@@ -895,6 +962,62 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
     panos = _chain_panos(imgs, xyz.shape[0])      # (the texel format every image's own omniloc_batch call takes)
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     return _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, True, weight_sets=I), input_trans_list, input_rot_list)
+
+
+def omniloc_batch_images_polished(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries=None):
+    """Throughput extension (not in the reference): what omniloc_batch does AFTER its chain — the Levenberg-Marquardt polish of the winner
+    (cfg.gn_iters / gn_step_cap / gn_lambda, gn_schedule) and / or the covariance at the returned pose (cfg.pose_covariance) — for several
+    query images of one cloud at once.  Arguments, return value and write-back as omniloc_batch_images; rgb: one (N, 3) tensor or a list of
+    one per image.  The chain is omniloc_batch_images'; with the robust keys omniloc_batch_images_robust's; with the prune keys a pruned
+    plain chain.  Then, on the device, from the winners rows: with the gn keys ONE gauss_newton_refine_images_at_winners for all the
+    images, under the robust chain's per-image weight planes where there are some; with cfg.pose_covariance a fourth entry per image, cov
+    (6, 6) on the CPU — the polish's own, or pose_information_images_at_winners' when there is no polish.  One D2H copy per call; the
+    written-back leaves stay the chain's.
+    Entry i against omniloc_batch(imgs[i], xyz, rgb_i, ...) under the same cfg: t, R and cov are equal bit for bit (for a plain chain of
+    shared colours under omniloc_batch_images' own caveat: where its plan cuts the cloud as the single call's does).  Where the polish took
+    no step (it needs accepted > 1 and status 0 or 3) all three entries are the chain's own, bit for bit.  Where it took one, `loss` is
+    float32(S1) / float32(M) of the polish's info record at the returned pose: the weighted sampling loss sum w m l / sum w m from the
+    pass's own sums — NOT the separate forward-only launch omniloc_batch re-evaluates it with (there is none for a colour set or a
+    per-image plane), so that one number differs from omniloc_batch's by the summation order.
+    Parallel semantics only.  ValueError, before a device is touched: a cfg with neither the gn keys nor pose_covariance (omniloc_batch_images
+    / omniloc_batch_images_robust run the chains alone), cfg.depth_mask (gn_schedule / pose_covariance_flag), cfg.visualize, lists of
+    different lengths, a colour-set count that is not the image count.  One image is omniloc_batch; images beyond the colour-set addressing
+    limit go in further groups."""
+    who = "omniloc_batch_images_polished"
+    gn, want_cov = gn_schedule(cfg), pose_covariance_flag(cfg)
+    if gn is None and not want_cov:
+        raise ValueError("%s needs cfg.gn_iters or cfg.pose_covariance (omniloc_batch_images / omniloc_batch_images_robust run the chain alone)" % who)
+    if _cfg(cfg, "visualize", False):
+        raise ValueError("%s does not take cfg.visualize" % who)
+    robust = robust_schedule(cfg)
+    I = len(imgs)
+    if I < 1 or len(input_trans_list) != I or len(input_rot_list) != I:
+        raise ValueError("%s: %d images, %d / %d lists of starting poses" % (who, I, len(input_trans_list), len(input_rot_list)))
+    rgb = shared_rgb(rgb)
+    if isinstance(rgb, list) and len(rgb) != I:
+        raise ValueError("%s: %d colour sets for %d images" % (who, len(rgb), I))
+    prune_schedule(cfg, int(input_trans_list[0].shape[0]))       # (its own refusals, before a device is touched)
+    if strict_reference_asserts:
+        assert cfg.num_input > 1
+    if I == 1:
+        return [omniloc_batch(imgs[0], xyz, rgb[0] if isinstance(rgb, list) else rgb, input_trans_list[0], input_rot_list[0], cfg, scalar_summaries)]
+    if isinstance(rgb, list):
+        out = _over_color_sets(int(xyz.shape[0]), I, lambda i0, i1: omniloc_batch_images_polished(
+            imgs[i0:i1], xyz, rgb[i0:i1], input_trans_list[i0:i1], input_rot_list[i0:i1], cfg, scalar_summaries))
+        if out is not None:
+            return out
+    panos = _chain_panos(imgs, xyz.shape[0])      # (the texel format every image's own omniloc_batch call takes)
+    box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
+    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb)
+    host = _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, True, weight_sets=I if robust is not None else 0),
+                          input_trans_list, input_rot_list, polish=lambda gd, wins: _winners_polished(gd, cloud, panos, wins, gn, want_cov))
+    out = []
+    for row in host:
+        loss = row[14] / row[15] if float(row[13]) != 0.0 else row[12]       # (float32 on the host: one correctly rounded division)
+        out.append([row[0:3].reshape(3, 1).clone(), row[3:12].reshape(3, 3).clone(), loss.clone()])
+        if want_cov:
+            out[-1].append(row[16:POLISHED_ROW].reshape(6, 6).clone())
+    return out
 
 
 def depth_tau_groups(points, H, W, cfg):

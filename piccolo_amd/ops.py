@@ -584,6 +584,104 @@ def gauss_newton_refine_at_winners(cloud, pano, winners, iters=10, trace=False, 
                          iters, trace, hyper)
 
 
+def _images_call(who, cloud, panos, rows, planes):
+    """What the images forms of pose_information / gauss_newton_refine check and pass on: one pose per panorama, panoramas of one size and
+    texel format, a cloud of one colour set or of one per image (_residual_cloud), and the weights — planes None: the cloud's own plane for
+    every image, where it has one; else an (I, pcl_cloud_stride(n)) float32 GPU tensor, plane i for image i (what
+    GradientDescent.weight_planes() of a weight-set chain returns).  -> (panos, the host array of their addresses, weights, weight_sets)"""
+    panos = list(panos)
+    if len(panos) < 1:
+        raise ValueError("%s: no panorama" % who)
+    I = len(panos)
+    _residual_cloud(cloud, panos[0], who, I)
+    _same_texels(panos, panos[0], "%s: all panoramas must share size and texel format" % who)
+    if rows != I:
+        raise ValueError("%s: one pose per panorama" % who)
+    if planes is None:
+        weights, sets = cloud.weights, 0 if cloud.weights is None else 1
+    else:
+        if not (torch.is_tensor(planes) and planes.is_cuda and planes.dtype == F32 and planes.is_contiguous()
+                and tuple(planes.shape) == (I, _lib.load().pcl_cloud_stride(cloud.n))):
+            raise ValueError("%s: planes must be a contiguous (I, pcl_cloud_stride(n)) float32 GPU tensor, one plane per panorama" % who)
+        weights, sets = planes, I
+    return panos, (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos]), weights, sets
+
+
+def _pose_information_images(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, planes):
+    lib = _lib.load()
+    panos, arr, weights, sets = _images_call(who, cloud, panos, rows, planes)
+    p0, I = panos[0], len(panos)
+    nws = lib.pcl_pose_information_workspace_bytes(cloud.n, I)
+    if nws == 0:
+        raise ValueError("%s: %d points x %d poses are out of range" % (who, cloud.n, I))
+    info = torch.empty(I, 48, dtype=F32, device=dev)
+    cov = torch.empty(I, 6, 6, dtype=F32, device=dev)
+    ws = _bytes(nws)
+    _lib.check(lib.pcl_pose_information_images(_ptr(cloud.data), _ptr(weights), sets, cloud.n, int(cloud.color_sets), arr, I, p0.fmt, p0.H, p0.W,
+                                               trans_ptr, rot_ptr, stride, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()),
+               "pcl_pose_information_images")
+    return info[:, :36].reshape(I, 6, 6), info[:, 36:42], info[:, 42:47], cov
+
+
+def pose_information_images(cloud, panos, trans, rot, planes=None):
+    """pose_information for I poses, each against ITS OWN panorama, in one set of launches (pcl_pose_information_images): row i of
+    (H, b, stats, cov) is pose (trans[i], rot[i]) against panos[i] — and, for a cloud of I colour sets (Cloud.with_color_sets), colour
+    set i — under the cloud's own weight plane where it has one (planes=None) or under planes[i] of an (I, pcl_cloud_stride(n)) float32 GPU
+    tensor (GradientDescent.weight_planes() of a weight-set chain).  Row i equals pose_information of that pose, panorama, colour set and
+    plane alone, bit for bit.  ValueError: as pose_information; a colour-set count that is not the image count; panoramas of different
+    sizes or texel formats; planes of another shape."""
+    trans, rot = _pose_rows(trans, rot)
+    return _pose_information_images("pose_information_images", cloud, panos, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, planes)
+
+
+def pose_information_images_at_winners(cloud, panos, winners, planes=None):
+    """pose_information_images at the poses of an (I, 16) tensor as _GdEngine.winners(I) returns it, read on the device (_winner_poses): row
+    i is winner i against panos[i] (colour set i, plane i)."""
+    who = "pose_information_images_at_winners"
+    return _pose_information_images(who, cloud, panos, *_winner_poses(winners, who), winners.device, planes)
+
+
+def _gauss_newton_images(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, iters, trace, planes, hyper):
+    lib = _lib.load()
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= GN_MAX_ITERS:
+        raise ValueError("%s: iters %r: an int in 0 .. %d" % (who, iters, GN_MAX_ITERS))
+    hp = gn_hyper(who, **hyper)
+    panos, arr, weights, sets = _images_call(who, cloud, panos, rows, planes)
+    p0, I = panos[0], len(panos)
+    nws, nst = lib.pcl_gn_workspace_bytes(cloud.n, I), lib.pcl_gn_state_bytes(I)
+    if nws == 0 or nst == 0:
+        raise ValueError("%s: %d points x %d poses are out of range" % (who, cloud.n, I))
+    out = torch.empty(I, 16, dtype=F32, device=dev)
+    info = torch.empty(I, 48, dtype=F32, device=dev)
+    cov = torch.empty(I, 6, 6, dtype=F32, device=dev)
+    tr = torch.empty(iters + 1, I, 16, dtype=F32, device=dev) if trace else None
+    ws, st = _bytes(nws), _bytes(nst)
+    _lib.check(lib.pcl_gn_refine_images(_ptr(cloud.data), _ptr(weights), sets, cloud.n, int(cloud.color_sets), arr, I, p0.fmt, p0.H, p0.W, trans_ptr,
+                                        rot_ptr, stride, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws,
+                                        _stream()), "pcl_gn_refine_images")
+    ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
+               evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(I, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
+    if trace:
+        ret["trace"] = tr
+    return ret
+
+
+def gauss_newton_refine_images(cloud, panos, trans, rot, iters=10, trace=False, planes=None, **hyper):
+    """gauss_newton_refine for I poses, each against ITS OWN panorama, in ONE chain (pcl_gn_refine_images): pose i = (trans[i], rot[i]) is
+    polished against panos[i] — colour set i of a cloud of I colour sets, the cloud's own weight plane (planes=None) or planes[i] as for
+    pose_information_images.  -> gauss_newton_refine's dict with one row per image (trace: (iters + 1, I, 16)); row i equals the single
+    call's for that pose, panorama, colour set and plane, bit for bit — a pose that freezes moves no other pose's bits."""
+    trans, rot = _pose_rows(trans, rot)
+    return _gauss_newton_images("gauss_newton_refine_images", cloud, panos, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace,
+                                planes, hyper)
+
+
+def gauss_newton_refine_images_at_winners(cloud, panos, winners, iters=10, trace=False, planes=None, **hyper):
+    """gauss_newton_refine_images from the poses of an (I, 16) tensor as _GdEngine.winners(I) returns it, read on the device (_winner_poses)."""
+    who = "gauss_newton_refine_images_at_winners"
+    return _gauss_newton_images(who, cloud, panos, *_winner_poses(winners, who), winners.device, iters, trace, planes, hyper)
+
+
 def point_residuals_images(cloud, panos, trans, rot, packed=False):
     """(I, N) float GPU tensor: row i is point_residuals of pose (trans[i], rot[i]) against panos[i] — and, for a cloud of I colour sets
     (Cloud.with_color_sets), colour set i — in ONE launch (pcl_point_residuals_images; the panorama addresses are kernel arguments).  Row i
