@@ -176,8 +176,8 @@ int pcl_robust_weights_rows(const float *residual_packed, int64_t n, int nrows, 
  * pcl_pose_information_workspace_bytes(n, B): 0 for n outside 1..PCL_MAX_POINTS, B <= 0 or more blocks than a grid holds.
  * PCL_EINVAL, before any HIP call: what pcl_point_residuals refuses (null cloud / pano / trans / rot, n, B, H, W, a 2 GiB panorama, the
  * trim-only texel formats PCL_PANO_U8P / PCL_PANO_U8V, pose_stride < 3), a null info or workspace, workspace_bytes below the query's.
- * Deliberately left out: colour sets, the images / rooms / depth chains, a Gauss-Newton step on H and b, and any claim that cov is
- * calibrated on real data (sigma^2 is the mean squared colour residual of the kept points, nothing more). */
+ * Deliberately left out: colour sets, the images / depth chains (the rooms chains: pcl_pose_information_rooms), a Gauss-Newton step on H
+ * and b, and any claim that cov is calibrated on real data (sigma^2 is the mean squared colour residual of the kept points, nothing more). */
 size_t pcl_pose_information_workspace_bytes(int64_t n, int B);
 int pcl_pose_information(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans,
                          const float *rot, int pose_stride, int B, float *info, float *cov, void *workspace, size_t workspace_bytes, void *stream);
@@ -209,7 +209,7 @@ int pcl_pose_information(const float *cloud, const float *weights, int64_t n, co
  * PCL_EINVAL, before any HIP call: everything pcl_pose_information refuses; iters < 0 or > 1000; a null hyper_host, state, out or info; a
  * hyper-parameter that is not finite; lam0 <= 0, lam_up <= 1, lam_down <= 0 or > 1, lam_min > lam_max, step_cap <= 0, tol < 0.
  * Deliberately left out: an IRLS form that minimises the sampling loss itself, re-weighting inside the chain, the box clamp of the
- * reference's refinement, colour sets, the images / rooms / depth chains, and any claim about real data. */
+ * reference's refinement, colour sets, the images / depth chains (the rooms chains: pcl_gn_refine_rooms), and any claim about real data. */
 typedef struct pcl_gn_hyper {
     float lam0, lam_up, lam_down, lam_min, lam_max, step_cap, tol;
 } pcl_gn_hyper;
@@ -237,8 +237,9 @@ int pcl_gn_refine(const float *cloud, const float *weights, int64_t n, const voi
  * PCL_EINVAL, before any launch: what pcl_pose_information / pcl_gn_refine refuse (B = nimages); a null panos_host or a zero entry;
  * weights == NULL with weight_sets != 0, weights with a weight_sets that is neither 1 nor nimages; color_sets < 0, or > 1 and not nimages;
  * weight planes or colour sets of 2^31 bytes or more together (one buffer resource each).
- * Deliberately left out: the rooms and depth chains, a forward-only loss launch for a colour set or a per-image plane (the weighted
- * sampling loss at a returned pose is S1 / M of its info record), and any claim that cov is calibrated on real data. */
+ * Deliberately left out: of the rooms and depth chains the depth chains (the rooms chains have pcl_pose_information_rooms /
+ * pcl_gn_refine_rooms, declared next to pcl_gd_run_rooms_images), a forward-only loss launch for a colour set or a per-image plane (the
+ * weighted sampling loss at a returned pose is S1 / M of its info record), and any claim that cov is calibrated on real data. */
 int pcl_pose_information_images(const float *cloud, const float *weights, int weight_sets, int64_t n, int color_sets, const uint64_t *panos_host,
                                 int nimages, int pano_format, int H, int W, const float *trans, const float *rot, int pose_stride, float *info,
                                 float *cov, void *workspace, size_t workspace_bytes, void *stream);
@@ -490,6 +491,35 @@ int pcl_gd_init_rooms_images(void *state, const float *trans, const float *rot, 
 int pcl_gd_run_rooms_images(const pcl_gd_room *rooms_host, int nrooms, int nimages, const void *pano, int pano_format, int H, int W, void *state,
                             int per_image, const pcl_gd_hyper *hyper_host, int num_iter, float *loss_history, void *workspace,
                             size_t workspace_bytes, void *timer, void *stream);
+/* pcl_pose_information and pcl_gn_refine for the nrooms * nimages winners of a rooms x images chain, in ONE set of launches (additive to
+ * ABI 12; BUILD-DEFINED).  Pose (r, i) is row r * nimages + i of trans / rot — the layout of pcl_gd_winner(state, nrooms * nimages,
+ * per_image, ...), so pose_stride 16 with trans = winners, rot = winners + 13 reads the winners in place — and is evaluated against room
+ * r's packed cloud rooms_host[r].cloud of rooms_host[r].n points (pcl_gd_room.box is ignored and may be null), against panos_host[i] (HOST
+ * array of nimages device addresses of packed panoramas of one H, W and texel format, as for pcl_pose_information_images) and against
+ * colour set i of room r when color_sets == nimages (every room's cloud is then one of pcl_cloud_pack_sets with nimages sets; color_sets
+ * 0 / 1: the room's one set).  No weights: the rooms chains take none.
+ * Record (r, i) — info, cov; for pcl_gn_refine_rooms also out, the state (pcl_gn_state_bytes(nrooms * nimages)) and the trace rows
+ * [iters + 1][nrooms * nimages][16] — equals what pcl_pose_information / pcl_gn_refine returns for that pose against room r's cloud, that
+ * colour set and panos_host[i] alone, in the same texel format, BIT FOR BIT, for every nrooms >= 1 and nimages >= 1: room r walks its own
+ * chunking (that of the single call: it depends on n_r alone) into its own region of partial rows, and a pose is finished over its room's
+ * rows by the code of the single call.  A frozen pose stops only its own blocks.  The room records (cloud address, n, stride, chunks,
+ * steps, first block, row offset) and the panorama addresses travel as kernel arguments: nothing is copied, nothing waits for the host,
+ * capturable.  Per evaluation one pass launch per 64 images (all rooms in each; colour set and row are counted from the call's first
+ * image) and one step launch over all poses; pcl_pose_information_rooms: the pass launches and one finish launch.  No atomics, no
+ * allocation, no synchronisation.  workspace: the sum over the rooms of pcl_pose_information_workspace_bytes(n_r, nimages).
+ * PCL_EINVAL (0 from the sizing functions, for what they are told), before any HIP call: everything pcl_pose_information_images /
+ * pcl_gn_refine_images refuse (B = nimages; no weights); nrooms outside 1..PCL_GD_MAX_ROOMS; a room with a null cloud or n outside
+ * 1..PCL_MAX_POINTS; a room whose colour sets pass 2^31 bytes (one buffer resource per room); more blocks than a grid holds; a workspace
+ * below the query.
+ * Deliberately left out: the depth chains, weights (the rooms chains have none), and any claim that cov is calibrated on real data. */
+size_t pcl_pose_information_rooms_workspace_bytes(const pcl_gd_room *rooms_host, int nrooms, int nimages);
+int pcl_pose_information_rooms(const pcl_gd_room *rooms_host, int nrooms, int color_sets, const uint64_t *panos_host, int nimages, int pano_format,
+                               int H, int W, const float *trans, const float *rot, int pose_stride, float *info, float *cov, void *workspace,
+                               size_t workspace_bytes, void *stream);
+size_t pcl_gn_rooms_workspace_bytes(const pcl_gd_room *rooms_host, int nrooms, int nimages);
+int pcl_gn_refine_rooms(const pcl_gd_room *rooms_host, int nrooms, int color_sets, const uint64_t *panos_host, int nimages, int pano_format, int H,
+                        int W, const float *trans, const float *rot, int pose_stride, const pcl_gn_hyper *hyper_host, int iters, void *state,
+                        float *out, float *info, float *cov, float *trace, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The depth mask inside a shared chain (additive to ABI 12): the rooms x images chain above with hyper->depth_mask set — which every
  * entry point above refuses, because this chain's workspace carries z-buffers.  One family for the three shared chains: per-image colour

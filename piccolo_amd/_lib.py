@@ -144,6 +144,12 @@ SIGNATURES = {
     "pcl_gd_plan_rooms_images": (_int, [_c.POINTER(GdRoom), _int, _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
     "pcl_gd_init_rooms_images": (_int, [_vp, _vp, _vp, _int, _int, _int, _c.POINTER(GdHyper), _vp]),
     "pcl_gd_run_rooms_images": (_int, [_c.POINTER(GdRoom), _int, _int, _vp, _int, _int, _int, _vp, _int, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
+    "pcl_pose_information_rooms_workspace_bytes": (_sz, [_c.POINTER(GdRoom), _int, _int]),
+    "pcl_pose_information_rooms": (_int, [_c.POINTER(GdRoom), _int, _int, _c.POINTER(_c.c_uint64), _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp,
+                                          _sz, _vp]),
+    "pcl_gn_rooms_workspace_bytes": (_sz, [_c.POINTER(GdRoom), _int, _int]),
+    "pcl_gn_refine_rooms": (_int, [_c.POINTER(GdRoom), _int, _int, _c.POINTER(_c.c_uint64), _int, _int, _int, _int, _vp, _vp, _int, _c.POINTER(GnHyper),
+                                   _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcl_gd_depth_chain_workspace_bytes": (_sz, [_c.POINTER(GdRoom), _int, _int, _int, _int, _int, _c.POINTER(GdHyper)]),
     "pcl_gd_plan_depth_chain": (_int, [_c.POINTER(GdRoom), _int, _int, _int, _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int),
                                        _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),

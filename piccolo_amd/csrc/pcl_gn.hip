@@ -26,20 +26,8 @@
 // over several query images): pcl_gn_pass_images_kernel in place of the pass, the init and step kernels as they are.
 #include <math.h>
 
+#include "pcl_gn_device.h"
 #include "pcl_info_device.h"
-
-#define PCL_GN_OUT 16                      // floats per out / trace row (include/piccolo_hip.h)
-#define PCL_GN_MAX_ITERS 1000
-
-// Per pose, in the caller's state buffer.  The pass reads theta_try in place: trans = &tri[0], rot = &tri[3], pose stride sizeof / 4.
-struct PclGnState {
-    double H[6][6], b[6], M, S1, S2;       // the accepted evaluation's sums (k = 0 refused: the refused ones)
-    float acc[6];                          // theta_acc: t, yaw, pitch, roll
-    float tri[6];                          // theta_try
-    float F_acc, F_start, lam;
-    int accepted, rejected, evaluations, status, frozen, sums_ok, pad;
-};
-static_assert(sizeof(PclGnState) % 8 == 0, "state rows keep their doubles aligned");
 
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_init_kernel(PclGnState* __restrict__ state, const float* __restrict__ trans,
                                                                const float* __restrict__ rot, int pose_stride, float lam0, float* __restrict__ trace,
@@ -83,6 +71,7 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_pass_images_kernel(PclInfoAr
                                chunk * (unsigned)im.btot + g);
 }
 
+// (pcl_gn_step_rooms_kernel of pcl_gn_rooms.hip repeats this text over a room's region of rows.)
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_step_kernel(const float* __restrict__ partials, int nchunks, int B, PclGnState* __restrict__ state,
                                                                pcl_gn_hyper hp, int k, int iters, float* __restrict__ out, float* __restrict__ info,
                                                                float* __restrict__ cov, float* __restrict__ trace)
@@ -186,6 +175,13 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_step_kernel(const float* __r
     pcl_info_emit(Hm, bv, M, S1, S2, sigma2, status, e, L, Li, info + (int64_t)b * PCL_INFO_REC, cov ? cov + (int64_t)b * 36 : nullptr);
 }
 
+int pcl_gn_launch_init(PclGnState* state, const float* trans, const float* rot, int pose_stride, float lam0, float* trace, int B, int iters, hipStream_t s)
+{
+    hipLaunchKernelGGL(pcl_gn_init_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, state, trans, rot, pose_stride, lam0, trace, B, iters);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" size_t pcl_gn_state_bytes(int B)
 {
     if (B <= 0) return 0;
@@ -201,20 +197,12 @@ extern "C" size_t pcl_gn_workspace_bytes(int64_t n, int B)
     return c.off;
 }
 
-static bool gn_hyper_ok(const pcl_gn_hyper* h)
-{
-    const float v[7] = {h->lam0, h->lam_up, h->lam_down, h->lam_min, h->lam_max, h->step_cap, h->tol};
-    for (int i = 0; i < 7; i++)
-        if (!(fabsf(v[i]) <= 3.402823466e38f)) return false;
-    return h->lam0 > 0.f && h->lam_up > 1.f && h->lam_down > 0.f && h->lam_down <= 1.f && h->lam_min <= h->lam_max && h->step_cap > 0.f && h->tol >= 0.f;
-}
-
 extern "C" int pcl_gn_refine(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
                              const float* rot, int pose_stride, int B, const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info,
                              float* cov, float* trace, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!hyper_host || !state || !out || !info || !workspace) return PCL_EINVAL;
-    if (iters < 0 || iters > PCL_GN_MAX_ITERS || !gn_hyper_ok(hyper_host)) return PCL_EINVAL;
+    if (iters < 0 || iters > PCL_GN_MAX_ITERS || !pcl_gn_hyper_ok(hyper_host)) return PCL_EINVAL;
     PclInfoArgs a;
     int64_t nchunks;
     const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
@@ -250,7 +238,7 @@ extern "C" int pcl_gn_refine_images(const float* cloud, const float* weights, in
                                     void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!hyper_host || !state || !out || !info || !workspace) return PCL_EINVAL;
-    if (iters < 0 || iters > PCL_GN_MAX_ITERS || !gn_hyper_ok(hyper_host)) return PCL_EINVAL;
+    if (iters < 0 || iters > PCL_GN_MAX_ITERS || !pcl_gn_hyper_ok(hyper_host)) return PCL_EINVAL;
     PclInfoArgs a;
     PclInfoImages im;
     int64_t nchunks;
@@ -284,3 +272,4 @@ extern "C" int pcl_gn_refine_images(const float* cloud, const float* weights, in
     }
     return 0;
 }
+

@@ -1,0 +1,31 @@
+// pcl_gn_device.h — what pcl_gn.hip and pcl_gn_rooms.hip share of the Levenberg-Marquardt chain: the per-pose state, the hyper-parameter
+// check and the init launch.  The rooms chain is a translation unit of its own: a second step kernel beside pcl_gn_step_kernel changes how
+// the compiler inlines the double-precision library calls of both, and pcl_gn_step_kernel keeps the instruction stream it had.
+#pragma once
+#include <math.h>
+
+#include "pcl_info_device.h"
+
+#define PCL_GN_OUT 16                      // floats per out / trace row (include/piccolo_hip.h)
+#define PCL_GN_MAX_ITERS 1000
+
+// Per pose, in the caller's state buffer.  The pass reads theta_try in place: trans = &tri[0], rot = &tri[3], pose stride sizeof / 4.
+struct PclGnState {
+    double H[6][6], b[6], M, S1, S2;       // the accepted evaluation's sums (k = 0 refused: the refused ones)
+    float acc[6];                          // theta_acc: t, yaw, pitch, roll
+    float tri[6];                          // theta_try
+    float F_acc, F_start, lam;
+    int accepted, rejected, evaluations, status, frozen, sums_ok, pad;
+};
+static_assert(sizeof(PclGnState) % 8 == 0, "state rows keep their doubles aligned");
+
+static inline bool pcl_gn_hyper_ok(const pcl_gn_hyper* h)
+{
+    const float v[7] = {h->lam0, h->lam_up, h->lam_down, h->lam_min, h->lam_max, h->step_cap, h->tol};
+    for (int i = 0; i < 7; i++)
+        if (!(fabsf(v[i]) <= 3.402823466e38f)) return false;
+    return h->lam0 > 0.f && h->lam_up > 1.f && h->lam_down > 0.f && h->lam_down <= 1.f && h->lam_min <= h->lam_max && h->step_cap > 0.f && h->tol >= 0.f;
+}
+
+// pcl_gn_init_kernel over B poses (pcl_gn.hip): the launch of the chains of the other translation unit
+int pcl_gn_launch_init(PclGnState* state, const float* trans, const float* rot, int pose_stride, float lam0, float* trace, int B, int iters, hipStream_t s);

@@ -5,6 +5,7 @@
 // Outside the loss-kernel hash: the four files it covers are included, never edited.
 #pragma once
 #include <math.h>
+#include <string.h>
 
 #include "pcl_point_pass.h"
 #include "pcl_sample_device.h"
@@ -34,11 +35,14 @@ struct PclInfoImages {
 // one at byte offset `wplane`, which goes through the load's scalar offset (wave-uniform), as the loss kernel's wsets instances do it.
 // The single-image kernels pass a.pass.pano, one set, one plane at offset 0 and row blockIdx.x as literals: their instruction streams
 // are those of the pass before it took these arguments.
+// pcl_info_pass_at is that pass for block (chunk, pose b) over the cloud `c` into row `row` of `partials`: what a block of a rooms launch
+// passes from its room's record, and what pcl_info_pass passes from the call's own struct and block index.
 template <int FMT, bool WT, bool CS = false>
-__device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a, const void* pano_b, int sets, unsigned set, int wsets, int wplane, unsigned row)
+__device__ __forceinline__ void pcl_info_pass_at(const PclInfoArgs& a, const PclPassCloud& c, unsigned b, unsigned chunk, const void* pano_b, int sets,
+                                                 unsigned set, int wsets, int wplane, float* partials, unsigned row)
 {
     __amdgpu_buffer_rsrc_t wrs;
-    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(a.pass.stride * 4) * wsets, 0x00020000);
+    if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(c.stride * 4) * wsets, 0x00020000);
 
     f2 hh[21], bb[6], s2 = F2(0.f), s1 = F2(0.f), mm = F2(0.f);
 #pragma unroll
@@ -46,7 +50,7 @@ __device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a, const void* 
 #pragma unroll
     for (int k = 0; k < 6; k++) bb[k] = F2(0.f);
 
-    pcl_point_pass<FMT, true, CS>(a.pass, pano_b, sets, set, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool) {
+    pcl_point_pass_at<FMT, true, CS>(a.pass, c, b, chunk, pano_b, sets, set, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool) {
         // acc: 0 l, 1 m, 2-4 g, 5-7 tau of this pair of points alone.  One factor w (a slot past n never counts, whatever its plane holds)
         f2 w = F2(1.f), wl = acc[0], wm = acc[1], wa[6];
         if constexpr (WT) {
@@ -85,8 +89,72 @@ __device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a, const void* 
     __syncthreads();
     if (threadIdx.x < PCL_INFO_ROW) {
         const int k = threadIdx.x;
-        a.partials[(int64_t)row * PCL_INFO_ROW + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+        partials[(int64_t)row * PCL_INFO_ROW + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
     }
+}
+
+template <int FMT, bool WT, bool CS = false>
+__device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a, const void* pano_b, int sets, unsigned set, int wsets, int wplane, unsigned row)
+{
+    pcl_info_pass_at<FMT, WT, CS>(a, PclPassCloud{a.pass.cloud, a.pass.n, a.pass.stride, a.pass.steps_base, a.pass.steps_rem},
+                                  blockIdx.x % (unsigned)a.pass.B, blockIdx.x / (unsigned)a.pass.B, pano_b, sets, set, wsets, wplane, a.partials, row);
+}
+
+// ---- the rooms instances (pcl_pose_information_rooms, pcl_gn_refine_rooms): pose (r, i) = row r * btot + i against room r's cloud,
+// panorama i and, with CS, colour set i of room r's cloud.  Room r owns the contiguous blocks [block0_r, block0_r + nchunks_r * m) of a
+// launch of m images, the image varying fastest, walks its own chunking pcl_pass_chunks(n_r, PCL_INFO_MIN_STEPS), and keeps its partial
+// rows [nchunks_r][btot][PCL_INFO_ROW] in a region of its own, `rows` floats into the call's partials.  The table travels as kernel
+// arguments: a block counts the rooms that start at or before it (unused entries of block0 hold INT_MAX) and reads its record with
+// scalar loads at an index that depends on the block index alone — everything below is wave-uniform and lives in SGPRs, the cloud's
+// buffer resource included.
+struct PclInfoRoom {
+    unsigned long long cloud;      // packed cloud of the room (pcl_cloud_pack / pcl_cloud_pack_sets)
+    long long rows;                // float offset of the room's partial rows
+    int n, stride;
+    int nchunks, block0;           // block0: of this LAUNCH (it depends on the launch's image count)
+    int steps_base, steps_rem;
+};
+struct PclInfoRooms {
+    int block0[PCL_GD_MAX_ROOMS];
+    PclInfoRoom rec[PCL_GD_MAX_ROOMS];
+};
+
+__device__ __forceinline__ int pcl_info_sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ unsigned long long pcl_info_sgpr64(unsigned long long v)
+{
+    return ((unsigned long long)(unsigned)pcl_info_sgpr((int)(v >> 32)) << 32) | (unsigned long long)(unsigned)pcl_info_sgpr((int)(unsigned)v);
+}
+
+// Where block blockIdx.x of a rooms launch of `m` images works: its room, the room's cloud and chunking, its chunk and its image
+struct PclInfoRoomAt {
+    PclPassCloud c;
+    unsigned room, chunk, image;
+    long long rows;
+};
+__device__ __forceinline__ PclInfoRoomAt pcl_info_room_select(const PclInfoRooms& rm, unsigned m)
+{
+    int r = -1;
+#pragma unroll
+    for (int q = 0; q < PCL_GD_MAX_ROOMS; q++) r += (int)blockIdx.x >= rm.block0[q] ? 1 : 0;
+    r = pcl_info_sgpr(r);
+    const PclInfoRoom& e = rm.rec[r];
+    const unsigned local = blockIdx.x - (unsigned)pcl_info_sgpr(e.block0);
+    PclInfoRoomAt at;
+    at.c = PclPassCloud{(const float*)pcl_info_sgpr64(e.cloud), (int64_t)pcl_info_sgpr(e.n), (int64_t)pcl_info_sgpr(e.stride), pcl_info_sgpr(e.steps_base),
+                        pcl_info_sgpr(e.steps_rem)};
+    at.room = (unsigned)r; at.chunk = local / m; at.image = local - at.chunk * m;
+    at.rows = (long long)pcl_info_sgpr64((unsigned long long)e.rows);
+    return at;
+}
+
+// The block of the rooms pass launches: pose at.room * btot + at.image of the launch's sliced poses against panorama at.image of the launch,
+// colour set img0 + at.image, into row chunk * btot + img0 + at.image of the room's region.  No weights: the rooms chains take none.
+template <int FMT, bool CS>
+__device__ __forceinline__ void pcl_info_pass_rooms(const PclInfoArgs& a, const PclInfoImages& im, const PclInfoRoomAt& at)
+{
+    const unsigned g = at.image + (unsigned)im.img0;
+    pcl_info_pass_at<FMT, false, CS>(a, at.c, at.room * (unsigned)im.btot + at.image, at.chunk, (const void*)im.panos.p[at.image], im.sets, g, 1, 0,
+                                     a.partials + at.rows, at.chunk * (unsigned)im.btot + g);
 }
 
 // All 256 threads of a block.  Thread (part, k), part = tid / 32, adds entry k of its eighth of pose b's chunk rows in double, lowest chunk
@@ -253,5 +321,87 @@ static inline void pcl_info_images_launches(const PclInfoArgs& a, const PclInfoI
         al.pass.trans = a.pass.trans + (int64_t)i0 * a.pass.pose_stride; al.pass.rot = a.pass.rot + (int64_t)i0 * a.pass.pose_stride;
         al.pass.B = m;
         launch(al, il, i0, dim3((unsigned)(nchunks * m)));
+    }
+}
+
+// ---- host side of the rooms entry points (pcl_pose_information_rooms, pcl_gn_refine_rooms): every check, before any launch
+struct PclInfoRoomsPlan {
+    PclInfoRooms t;              // block0 is filled per launch (pcl_info_rooms_launches)
+    int nrooms;
+    size_t bytes;                // every room's region [nchunks_r][nimages][PCL_INFO_ROW], each 256-byte aligned: the workspace
+};
+
+// The rooms' chunkings and regions (they depend on n_r and nimages alone); PCL_EINVAL: nrooms outside 1..PCL_GD_MAX_ROOMS, nimages < 1, a
+// room with a null cloud or n outside 1..PCL_MAX_POINTS, more blocks than a grid holds.  pcl_gd_room.box is not read.
+static inline int pcl_info_rooms_plan(const pcl_gd_room* rooms_host, int nrooms, int nimages, PclInfoRoomsPlan* g)
+{
+    if (!rooms_host || nrooms < 1 || nrooms > PCL_GD_MAX_ROOMS || nimages < 1) return PCL_EINVAL;
+    memset(&g->t, 0, sizeof(g->t));
+    for (int r = 0; r < PCL_GD_MAX_ROOMS; r++) g->t.block0[r] = 0x7fffffff;
+    g->nrooms = nrooms;
+    PclCarve c{nullptr, 0};
+    int64_t chunks = 0;
+    for (int r = 0; r < nrooms; r++) {
+        const int64_t n = rooms_host[r].n;
+        if (!rooms_host[r].cloud || n <= 0 || n > PCL_MAX_POINTS) return PCL_EINVAL;
+        int64_t steps;
+        const int64_t nchunks = pcl_pass_chunks(n, PCL_INFO_MIN_STEPS, &steps);
+        PclInfoRoom& e = g->t.rec[r];
+        e.cloud = (unsigned long long)rooms_host[r].cloud;
+        e.n = (int)n; e.stride = (int)pcl_cloud_stride(n);
+        e.nchunks = (int)nchunks; e.steps_base = (int)(steps / nchunks); e.steps_rem = (int)(steps % nchunks);
+        e.rows = (long long)(c.off / sizeof(float));
+        c.take((size_t)nchunks * (size_t)nimages * PCL_INFO_ROW * sizeof(float));
+        chunks += nchunks;
+    }
+    if (chunks * nimages > 0x7fffffffll) return PCL_EINVAL;
+    g->bytes = c.off;
+    return 0;
+}
+
+// Everything the rooms entry points check beside their own outputs, and what their launches share: a (a.pass.B = nimages; the cloud
+// fields are room 0's and no kernel reads them), im, the plan.  color_sets 0 / 1, or nimages: every room's cloud has that many sets.
+static inline int pcl_info_rooms_args(PclInfoArgs* a, PclInfoImages* im, PclInfoRoomsPlan* g, const pcl_gd_room* rooms_host, int nrooms, int color_sets,
+                                      const uint64_t* panos_host, int nimages, int pano_format, int H, int W, const float* trans, const float* rot,
+                                      int pose_stride)
+{
+    if (!panos_host || nimages <= 0) return PCL_EINVAL;
+    for (int i = 0; i < nimages; i++)
+        if (!panos_host[i]) return PCL_EINVAL;
+    if (color_sets < 0 || (color_sets > 1 && color_sets != nimages)) return PCL_EINVAL;
+    int rc = pcl_info_rooms_plan(rooms_host, nrooms, nimages, g);
+    if (rc) return rc;
+    int64_t nchunks0;
+    rc = pcl_pass_args(&a->pass, (const float*)rooms_host[0].cloud, rooms_host[0].n, (const void*)panos_host[0], pano_format, H, W, trans, rot, pose_stride,
+                       nimages, PCL_INFO_MIN_STEPS, &nchunks0);
+    if (rc) return rc;
+    // one buffer resource per room: its colour sets stay below 2^31 bytes
+    for (int r = 0; r < nrooms; r++)
+        if (color_sets > 1 ? pcl_cloud_sets_bytes(rooms_host[r].n, color_sets) == 0 : (int64_t)g->t.rec[r].stride * 6 * 4 >= ((int64_t)1 << 31)) return PCL_EINVAL;
+    a->weights = nullptr;
+    im->sets = color_sets > 1 ? color_sets : 1; im->img0 = 0; im->btot = nimages; im->wsets = 1;
+    return 0;
+}
+
+// The launches of one evaluation of all rooms x images: launch(al, il, tl, i0, grid) for every run of at most PCL_RES_MAX_IMAGES images, all
+// rooms in each — the poses sliced by the run's first image, the rooms' block ranges laid out for the run's image count
+template <class F>
+static inline void pcl_info_rooms_launches(const PclInfoArgs& a, const PclInfoImages& im, const PclInfoRoomsPlan& g, const uint64_t* panos_host, F&& launch)
+{
+    for (int i0 = 0; i0 < im.btot; i0 += PCL_RES_MAX_IMAGES) {
+        const int m = im.btot - i0 < PCL_RES_MAX_IMAGES ? im.btot - i0 : PCL_RES_MAX_IMAGES;
+        PclInfoImages il = im;
+        for (int i = 0; i < PCL_RES_MAX_IMAGES; i++) il.panos.p[i] = i < m ? (unsigned long long)panos_host[i0 + i] : 0ull;
+        il.img0 = i0;
+        PclInfoArgs al = a;
+        al.pass.trans = a.pass.trans + (int64_t)i0 * a.pass.pose_stride; al.pass.rot = a.pass.rot + (int64_t)i0 * a.pass.pose_stride;
+        al.pass.B = m;
+        PclInfoRooms tl = g.t;
+        int64_t blocks = 0;
+        for (int r = 0; r < g.nrooms; r++) {
+            tl.rec[r].block0 = tl.block0[r] = (int)blocks;
+            blocks += (int64_t)tl.rec[r].nchunks * m;
+        }
+        launch(al, il, tl, i0, dim3((unsigned)blocks));
     }
 }

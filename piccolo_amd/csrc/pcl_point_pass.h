@@ -43,26 +43,35 @@ __device__ __forceinline__ PclPose6 pcl_pass_pose(const PclPassArgs& a, unsigned
     return PclPose6{(f2){v[0], v[1]}, (f2){v[2], v[3]}, (f2){v[4], v[5]}, (f2){v[6], v[7]}, (f2){v[8], v[9]}, (f2){v[10], v[11]}};
 }
 
-// Block blockIdx.x = chunk * a.B + b walks its chunk's steps at pose b against `pano_b` and, with CS, colour set `set` of a cloud of `sets`
+// The cloud a block walks and how its steps are dealt to chunks: what PclPassArgs holds for the one cloud of a call, and what a block of a
+// rooms launch takes from its room's record instead (wave-uniform: the record is selected by the block index alone)
+struct PclPassCloud {
+    const float* cloud;
+    int64_t n, stride;
+    int steps_base, steps_rem;
+};
+
+// Block (chunk, pose b) walks its chunk's steps of cloud `c` at pose b against `pano_b` and, with CS, colour set `set` of a cloud of `sets`
 // colour sets (a uniform plane offset on the one cloud resource, as in the loss kernel).  For every pair of slots i0, i0 + 1:
 //   per_pair(i0, j, valid0, valid1, acc, pose_ok)      j: the slot the pair was loaded from (a pair never leaves its padded plane)
 // with acc the forward (GRAD: and gradient) sums of pcl_sample2 for that pair alone: 0 l, 1 mask bit, GRAD: 2-4 g, 5-7 tau.
+// pcl_point_pass below is block blockIdx.x = chunk * a.B + b over the call's one cloud, a's own.
 template <int FMT, bool GRAD, bool CS, class F>
-__device__ __forceinline__ void pcl_point_pass(const PclPassArgs& a, const void* pano_b, int sets, unsigned set, F&& per_pair)
+__device__ __forceinline__ void pcl_point_pass_at(const PclPassArgs& a, const PclPassCloud& c, unsigned b, unsigned chunk, const void* pano_b, int sets,
+                                                  unsigned set, F&& per_pair)
 {
-    const unsigned b = blockIdx.x % (unsigned)a.B, chunk = blockIdx.x / (unsigned)a.B;
     bool pose_ok;
     const PclPose6 P = pcl_pass_pose(a, b, pose_ok);
 
     __amdgpu_buffer_rsrc_t tex = pcl_tex_rsrc(pano_b, a.dims.H, a.dims.W, pcl_texel_bytes(FMT));
-    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)a.cloud, 0, CS ? (int)(a.stride * (3 + 3 * sets) * 4) : (int)(a.stride * 6 * 4),
+    __amdgpu_buffer_rsrc_t cld = __builtin_amdgcn_make_buffer_rsrc((void*)c.cloud, 0, CS ? (int)(c.stride * (3 + 3 * sets) * 4) : (int)(c.stride * 6 * 4),
                                                                    0x00020000);
-    const int plane = (int)a.stride * 4;
+    const int plane = (int)c.stride * 4;
     const int cplane = CS ? (int)(3u + 3u * set) * plane : 3 * plane;      // byte offset of the first colour plane this pose reads (uniform)
 
-    const int first = (int)chunk * a.steps_base + min((int)chunk, a.steps_rem);
-    const int nsteps = a.steps_base + ((int)chunk < a.steps_rem ? 1 : 0);
-    const int n = (int)a.n, last_pair = (int)a.stride - 2;
+    const int first = (int)chunk * c.steps_base + min((int)chunk, c.steps_rem);
+    const int nsteps = c.steps_base + ((int)chunk < c.steps_rem ? 1 : 0);
+    const int n = (int)c.n, last_pair = (int)c.stride - 2;
     for (int s = first; s < first + nsteps; s++) {
         const int i0 = s * PCL_PASS_STEP + 2 * (int)threadIdx.x, i1 = i0 + 1;
         const bool valid0 = i0 < n, valid1 = i1 < n;
@@ -80,6 +89,13 @@ __device__ __forceinline__ void pcl_point_pass(const PclPassArgs& a, const void*
         pcl_sample2<GRAD, FMT, true>(pj, p[3], p[4], p[5], valid0, valid1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
         per_pair(i0, j, valid0, valid1, acc, pose_ok);
     }
+}
+
+template <int FMT, bool GRAD, bool CS, class F>
+__device__ __forceinline__ void pcl_point_pass(const PclPassArgs& a, const void* pano_b, int sets, unsigned set, F&& per_pair)
+{
+    pcl_point_pass_at<FMT, GRAD, CS>(a, PclPassCloud{a.cloud, a.n, a.stride, a.steps_base, a.steps_rem}, blockIdx.x % (unsigned)a.B,
+                                     blockIdx.x / (unsigned)a.B, pano_b, sets, set, per_pair);
 }
 
 // ---- host side

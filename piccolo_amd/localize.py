@@ -25,7 +25,8 @@ from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
 from .omniloc import (GN_KEYS, ROBUST_KEYS, _is_int, _refuse, gn_schedule, omniloc_all, omniloc_batch, omniloc_batch_images,
-                      omniloc_batch_images_polished, omniloc_batch_images_robust, omniloc_batch_rooms_images, pose_covariance_flag, robust_schedule)
+                      omniloc_batch_images_polished, omniloc_batch_images_robust, omniloc_batch_rooms_images,
+                      omniloc_batch_rooms_images_polished, pose_covariance_flag, robust_schedule)
 from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
 
 
@@ -116,6 +117,30 @@ def _check_polish_cfg(cfg, who):
     return int(ppl)
 
 
+def _check_room_polish_cfg(cfg):
+    """Configuration-time rules of cfg.room_search_polish, before any file is read: True lets a room search (cfg.room_search, with or without
+    cfg.room_search_images) carry the polish keys (cfg.gn_iters / gn_step_cap / gn_lambda) and / or cfg.pose_covariance — every group then goes
+    through omniloc_batch_rooms_images_polished.  It needs cfg.room_search, cfg.parallel (the polished chain has parallel semantics only) and
+    at least one of those keys, and does not combine with cfg.polish_images_per_launch (the known-room loops' key); the schedules' own
+    refusals (a bad gn_iters, cfg.depth_mask) come here too.  -> whether the key is set (without it the loops refuse the keys as before)"""
+    rsp = getattr(cfg, "room_search_polish", None)
+    if rsp is None or rsp is False:
+        return False
+    if rsp is not True:
+        raise ValueError("cfg.room_search_polish %r: a bool" % (rsp,))
+    if not getattr(cfg, "room_search", None):
+        raise ValueError("cfg.room_search_polish goes with cfg.room_search (polish_images_per_launch polishes a known-room run)")
+    if getattr(cfg, "polish_images_per_launch", None) is not None:
+        raise ValueError("cfg.polish_images_per_launch does not combine with cfg.room_search")
+    if not getattr(cfg, "parallel", False):
+        raise ValueError("cfg.room_search_polish needs cfg.parallel (the polished chain has parallel semantics only)")
+    if all(getattr(cfg, key, None) is None for key in GN_KEYS) and not getattr(cfg, "pose_covariance", None):
+        raise ValueError("cfg.room_search_polish goes with cfg.gn_iters and / or cfg.pose_covariance (room_search alone runs the plain search)")
+    gn_schedule(cfg)                                  # (their own ValueErrors, before any file is read)
+    pose_covariance_flag(cfg)
+    return True
+
+
 def _group_size(cfg):
     """images per group of the known-room loops: cfg.images_per_launch; under the robust keys cfg.robust_images_per_launch (default 1); with
     cfg.polish_images_per_launch that (a robust polished run too)"""
@@ -147,6 +172,15 @@ def _images_in_rooms(imgs_init, imgs_main, rooms, cfg, init_dict):
         trs.append([tr for tr, _ in starts])
         ros.append([ro for _, ro in starts])
         prepped.append((xyz, rgb_r))
+    if getattr(cfg, "room_search_polish", None):
+        # the room is decided by the CHAIN's losses — the plain search's, bit for bit —; pose, loss and cov are the found room's polished entry
+        res, chain_loss = omniloc_batch_rooms_images_polished(imgs_main, prepped, trs, ros, cfg)
+        out = []
+        for i in range(len(imgs_init)):
+            losses = chain_loss[:, i].clone()
+            k = int(torch.argmin(losses))
+            out.append((k,) + tuple(res[k][i][:3]) + (losses,) + tuple(res[k][i][3:4]))
+        return out
     res = omniloc_batch_rooms_images(imgs_main, prepped, trs, ros, cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
     out = []
     for i in range(len(imgs_init)):
@@ -162,6 +196,9 @@ def localize_in_rooms(img_init, img_main, rooms, cfg, init_dict):
     colours) and the starting poses (make_input) on the initialisation image, then ONE refinement of the main image against all rooms
     (omniloc_batch_rooms; cfg.parallel selects omniloc_batch's or omniloc_all's semantics).  The room with the smallest loss wins (ties
     to the lowest index, as torch.argmin).  -> (room index, t (3,1), R (3,3), loss, every room's loss (R,))
+    With cfg.room_search_polish (and the gn keys and / or cfg.pose_covariance; parallel only) the refinement is
+    omniloc_batch_rooms_images_polished: the room and every room's loss are still the chain's — those of the plain search, bit for bit —,
+    t, R and loss are the found room's polished entry, and with cfg.pose_covariance the tuple ends with that entry's cov (6, 6).
     (preprocess_colors re-quantises the colour-modulated initialisation image to 8-bit levels and honours match_color, like the OmniScenes
     loop; the known-room Stanford loop keeps color_mod's image as it is.  So a room search restricted to the ground-truth room does not
     reproduce a known-room Stanford run bit for bit: its starting poses may differ.)"""
@@ -596,10 +633,12 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     cfg.images_per_launch is the group size of _run_dataset (_localize_known_room); under cfg.robust_iters it is cfg.robust_images_per_launch.
     cfg.polish_images_per_launch (_check_polish_cfg): the group size of a run that carries the gn keys and / or cfg.pose_covariance, routed
     through omniloc_batch_images_polished; with cfg.pose_covariance the CSV gains sigma_t (m) and sigma_r (degrees) (_run_known_room).
-    cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms)."""
+    cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms); with
+    cfg.room_search_polish = True such a run takes the gn keys and / or cfg.pose_covariance (_check_room_polish_cfg)."""
     _require_gravity_aligned(cfg)
     _check_robust_cfg(cfg)
-    _check_polish_cfg(cfg, "localize_stanford")
+    if not _check_room_polish_cfg(cfg):
+        _check_polish_cfg(cfg, "localize_stanford")
     room_search = getattr(cfg, "room_search", None)
     if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
         raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")
@@ -659,12 +698,16 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
     localize_images_in_rooms call (the same results, bit for bit); a group of one goes through localize_in_rooms.
     With several ranks every rank localises its share of the
     images and the found rooms are gathered with the result rows (as room indices into the area's sorted listing), so that rank 0 writes
-    found_room and room_accuracy for every image."""
+    found_room and room_accuracy for every image.  With cfg.room_search_polish (_check_room_polish_cfg) every group goes through
+    omniloc_batch_rooms_images_polished (localize_in_rooms); found_room and room_accuracy stay those of the plain search, and with
+    cfg.pose_covariance the CSV ends found_room, sigma_t (m), sigma_r (degrees), gathered across the ranks with the found rooms."""
     dev = ops.device()
     sample_rate = getattr(cfg, "sample_rate", 1)
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
     init_dict = get_init_dict(cfg)
     areas, found, found_idx = {}, {}, {}
+    want_sigmas = bool(getattr(cfg, "room_search_polish", None)) and bool(getattr(cfg, "pose_covariance", None))
+    sigmas, every_sigma = {}, {}                      # (this rank's (sigma_t, sigma_r) per image; every rank's after the gather, as _run_known_room's)
 
     def read_cloud(area, room):
         return _read_cloud(data_utils.read_stanford, os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, room)), sample_rate, dev)
@@ -698,23 +741,30 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
             res = [localize_in_rooms(jobs[0].img_init, jobs[0].img_main, rooms, cfg, init_dict)]
         else:
             res = localize_images_in_rooms([j.img_init for j in jobs], [j.img_main for j in jobs], rooms, cfg, init_dict)
-        return [(t, R, loss, r) for r, t, R, loss, _ in res]
+        return [(one[1], one[2], one[3], one[0]) + tuple(one[5:6]) for one in res]      # (t, R, loss, room[, cov])
 
     def report(k, job, result, row):
         name, xyz, rgb = job.rooms[result[3]]
         found_idx[k] = result[3]
+        if want_sigmas:
+            sigmas[k] = pose_sigmas(result[4])
         _stanford_report(filenames[k], log_dir, job, xyz, rgb, result, row, "found room : {}\n".format(name))
 
     def gather_found():
         # this rank's found-room indices (NaN: skipped, or another rank's image) through the same all_gather as the result rows
         rank, world = pdist.world()
         mine = pdist.shard(len(filenames), rank, world)
-        local = torch.full((len(mine), 1), float("nan"), dtype=torch.float32, device=dev)
+        local = torch.full((len(mine), 3), float("nan"), dtype=torch.float32, device=dev)
         for j, k in enumerate(mine):
             if k in found_idx:
                 local[j, 0] = float(found_idx[k])
-        every = pdist.gather_rows(local, len(filenames), rank, world).cpu().numpy()[:, 0]
+            if k in sigmas:
+                local[j, 1:3] = torch.tensor(sigmas[k], dtype=torch.float32)
+        gathered = pdist.gather_rows(local, len(filenames), rank, world).cpu().numpy()
+        every = gathered[:, 0]
         found.clear()
+        every_sigma.clear()
+        every_sigma.update({k: gathered[k, 1:3] for k in range(len(filenames))})
         listings = {}
         for k, v in enumerate(every):
             if not np.isnan(v):
@@ -723,9 +773,16 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
                     listings[area] = stanford_area_rooms(root, area, room_search)
                 found[k] = (listings[area][int(v)], gt_room)
 
+    def suffix(k):
+        room = [found[k][0] if k in found else ""]
+        if not want_sigmas:
+            return room
+        return room + ["" if np.isnan(v) else float(v) for v in every_sigma.get(k, (np.nan, np.nan))]
+
     table = _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, localize_group, report),
-                         int(getattr(cfg, "room_search_images", 1)), "stanford_results.csv", STANFORD_HEADER + ["found_room"], _stanford_row_prefix,
-                         stanford_success, row_suffix=lambda k: [found[k][0] if k in found else ""], on_gathered=gather_found)
+                         int(getattr(cfg, "room_search_images", 1)), "stanford_results.csv",
+                         STANFORD_HEADER + ["found_room"] + (SIGMA_HEADER if want_sigmas else []), _stanford_row_prefix, stanford_success,
+                         row_suffix=suffix, on_gathered=gather_found)
     if LAST_RUN:
         hits = [name == gt for name, gt in found.values()]
         LAST_RUN["room_accuracy"] = sum(hits) / len(hits) if hits else 0.0

@@ -239,10 +239,11 @@ _EXTENSIONS = {
     "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
     "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust, omniloc_batch_images_polished and localize.refine_image's parallel "
                                   "branch do"),
-    "pose_covariance": (("pose_covariance",), None, "omniloc_batch, omniloc_batch_images_polished and localize.refine_image's parallel branch do; the "
-                                                    "dataset loops with cfg.polish_images_per_launch"),
-    "gn": (GN_KEYS, None, "omniloc_batch, omniloc_batch_images_polished and localize.refine_image's parallel branch do; the dataset loops with "
-                          "cfg.polish_images_per_launch"),
+    "pose_covariance": (("pose_covariance",), None, "omniloc_batch, omniloc_batch_images_polished, omniloc_batch_rooms_images_polished and "
+                                                    "localize.refine_image's parallel branch do; the dataset loops with "
+                                                    "cfg.polish_images_per_launch, a room search with cfg.room_search_polish"),
+    "gn": (GN_KEYS, None, "omniloc_batch, omniloc_batch_images_polished, omniloc_batch_rooms_images_polished and localize.refine_image's parallel "
+                          "branch do; the dataset loops with cfg.polish_images_per_launch, a room search with cfg.room_search_polish"),
 }
 
 
@@ -537,11 +538,18 @@ def _winners_polished(gd, cloud, panos, wins, gn, want_cov):
     planes = engine._run_weights()
     if planes is not None:
         planes = planes.view(I, -1) if engine.weight_sets else None          # (a plain chain's cloud plane is the cloud's own)
+    return _polished_rows(wins, gn, want_cov, lambda: ops.pose_information_images_at_winners(cloud, panos, wins, planes=planes),
+                          lambda: ops.gauss_newton_refine_images_at_winners(cloud, panos, wins, iters=gn[0], planes=planes, **gn[1]))
+
+
+def _polished_rows(wins, gn, want_cov, information, polish):
+    """The (I, POLISHED_ROW) rows of _winners_polished from information() (gn None) or polish(): the images or the rooms form at `wins`"""
+    I = int(wins.shape[0])
     zero = torch.zeros(I, 3, dtype=torch.float32, device=wins.device)
     if gn is None:
-        cov = ops.pose_information_images_at_winners(cloud, panos, wins, planes=planes)[3]
+        cov = information()[3]
         return torch.cat([wins[:, 0:13], zero, cov.reshape(I, 36)], dim=1)
-    res = ops.gauss_newton_refine_images_at_winners(cloud, panos, wins, iters=gn[0], planes=planes, **gn[1])
+    res = polish()
     R = ops.rot_from_ypr(res["rot"]).reshape(I, 9)
     took = ((res["accepted"] > 1) & ((res["status"] == 0) | (res["status"] == 3))).reshape(I, 1)
     rows = torch.where(took, torch.cat([res["trans"], R, zero[:, 0:1]], dim=1), wins[:, 0:13])
@@ -1208,6 +1216,87 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     flat = _refine_groups(lambda tr, ro: _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode), [t for ts in input_trans for t in ts],
                           [r for rs in input_rot for r in rs])
     return [flat[r * I:(r + 1) * I] for r in range(R)]
+
+
+ROOMS_POLISHED_ROW = POLISHED_ROW + 1      # _winners_polished's row and the chain's own winner loss (a polished row's column 12 is the polish's)
+
+
+def omniloc_batch_rooms_images_polished(imgs, rooms, input_trans, input_rot, cfg, scalar_summaries=None):
+    """Room search with omniloc_batch's polish and covariance (not in the reference): omniloc_batch_rooms_images' chain — pruned under the
+    prune keys —, then, on the device from its winners rows, ONE gauss_newton_refine_rooms_at_winners (cfg.gn_iters / gn_step_cap /
+    gn_lambda, gn_schedule) and / or pose_information_rooms_at_winners (cfg.pose_covariance) over all (room, image) winners, and one D2H
+    copy per chain.  Arguments and write-back as omniloc_batch_rooms_images (the written-back leaves stay the chain's); parallel semantics
+    only.  -> (out, chain_loss): out[r][i] = [t (3,1), R (3,3), loss ()] plus cov (6,6) with cfg.pose_covariance, and chain_loss an (R, I)
+    CPU tensor of the chain's own winner losses — omniloc_batch_rooms_images' losses bit for bit: what a room search decides the room by.
+    out[r][i] against omniloc_batch(imgs[i], xyz_r, rgb_r[i], ...) under the same cfg: t, R and cov bit for bit (under
+    omniloc_batch_rooms_images' caveat: images of k/255 levels); loss is float32(S1) / float32(M) of the polish's info record where it took
+    a step (accepted > 1, status 0 or 3), else the chain's — omniloc_batch_images_polished's rule.
+    omniloc_batch_rooms_images' fallbacks apply: more than PCL_GD_MAX_ROOMS rooms, images beyond the colour-set limit and chains too large
+    to gain from sharing go in several chains, each polished by itself; one image runs the one-image rooms chain.
+    ValueError, before a device is touched: a cfg with neither the gn keys nor pose_covariance, cfg.depth_mask, the robust keys,
+    cfg.visualize, ragged lists."""
+    who = "omniloc_batch_rooms_images_polished"
+    gn, want_cov = gn_schedule(cfg), pose_covariance_flag(cfg)
+    if gn is None and not want_cov:
+        raise ValueError("%s needs cfg.gn_iters or cfg.pose_covariance (omniloc_batch_rooms_images runs the chain alone)" % who)
+    if bool(_cfg(cfg, "depth_mask", False)):
+        raise ValueError("%s does not combine with cfg.depth_mask" % who)
+    _refuse(cfg, who, "robust")
+    if _cfg(cfg, "visualize", False):
+        raise ValueError("%s does not take cfg.visualize" % who)
+    R, I = len(rooms), len(imgs)
+    if R == 0 or I == 0 or len(input_trans) != R or len(input_rot) != R:
+        raise ValueError("%s: %d rooms, %d images, %d / %d starting-pose sets" % (who, R, I, len(input_trans), len(input_rot)))
+    if any(len(t) != I for t in input_trans) or any(len(r) != I for r in input_rot):
+        raise ValueError("%s: every room needs one starting-pose set per image" % who)
+    B = int(input_trans[0][0].shape[0])
+    if any(int(t.shape[0]) != B for ts in input_trans for t in ts) or any(int(r.shape[0]) != B for rs in input_rot for r in rs):
+        raise ValueError("%s: every room and image needs the same number of starting poses" % who)
+    rooms = [(xyz, shared_rgb(rgb)) for xyz, rgb in rooms]
+    for _, rgb in rooms:
+        if isinstance(rgb, list) and len(rgb) != I:
+            raise ValueError("%s: %d colour sets for %d images" % (who, len(rgb), I))
+    prune_schedule(cfg, B)                                   # (its own refusals, before a device is touched)
+    if strict_reference_asserts:
+        assert cfg.num_input > 1
+
+    def images(i0, i1):
+        return omniloc_batch_rooms_images_polished(imgs[i0:i1], [(xyz, rgb[i0:i1] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms],
+                                                   [t[i0:i1] for t in input_trans], [r[i0:i1] for r in input_rot], cfg, scalar_summaries)
+
+    def side_by_side(parts):
+        """(out, chain_loss) of runs of images -> of all the images"""
+        return [sum((o[r] for o, _ in parts), []) for r in range(R)], torch.cat([c for _, c in parts], dim=1)
+    if I > 1 and not rooms_images_chain_pays(sum(int(xyz.shape[0]) for xyz, _ in rooms), B):
+        return side_by_side([images(i, i + 1) for i in range(I)])
+    if R > ops._lib.GD_MAX_ROOMS:
+        parts = [(idx, omniloc_batch_rooms_images_polished(imgs, [rooms[r] for r in idx], [input_trans[r] for r in idx], [input_rot[r] for r in idx],
+                                                           cfg, scalar_summaries)) for idx in _room_cap_groups(R)]
+        return sum((o for _, (o, _) in parts), []), torch.cat([c for _, (_, c) in parts], dim=0)
+    if I > 1 and any(isinstance(rgb, list) for _, rgb in rooms):
+        # one kind of cloud per chain: a room whose images share its colours holds them I times
+        rooms = [(xyz, rgb if isinstance(rgb, list) else [rgb] * I) for xyz, rgb in rooms]
+        sizes = color_set_groups(max(int(xyz.shape[0]) for xyz, _ in rooms), I)
+        if len(sizes) > 1:
+            starts = [sum(sizes[:k]) for k in range(len(sizes))]
+            return side_by_side([images(i0, i0 + m) for i0, m in zip(starts, sizes)])
+    if I == 1:
+        rooms = [(xyz, rgb[0] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms]
+    clouds = [packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb) for xyz, rgb in rooms]      # (the chain's own: cached)
+    panos = _chain_panos(imgs, max(int(xyz.shape[0]) for xyz, _ in rooms))
+    host = _refine_groups(lambda tr, ro: _chain("gd_rooms" if I == 1 else "gd_rooms_images", imgs, rooms, tr, ro, cfg, True),
+                          [t for ts in input_trans for t in ts], [r for rs in input_rot for r in rs],
+                          polish=lambda gd, wins: torch.cat([_polished_rows(
+                              wins, gn, want_cov, lambda: ops.pose_information_rooms_at_winners(clouds, panos, wins),
+                              lambda: ops.gauss_newton_refine_rooms_at_winners(clouds, panos, wins, iters=gn[0], **gn[1])), wins[:, 12:13]], dim=1))
+    out = [[] for _ in range(R)]
+    for k, row in enumerate(host):
+        loss = row[14] / row[15] if float(row[13]) != 0.0 else row[12]       # (float32 on the host: one correctly rounded division)
+        entry = [row[0:3].reshape(3, 1).clone(), row[3:12].reshape(3, 3).clone(), loss.clone()]
+        if want_cov:
+            entry.append(row[16:POLISHED_ROW].reshape(6, 6).clone())
+        out[k // I].append(entry)
+    return out, host[:, POLISHED_ROW].reshape(R, I).clone()
 
 
 def sampling_loss(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, return_list=True, weights=None):

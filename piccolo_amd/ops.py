@@ -682,6 +682,103 @@ def gauss_newton_refine_images_at_winners(cloud, panos, winners, iters=10, trace
     return _gauss_newton_images(who, cloud, panos, *_winner_poses(winners, who), winners.device, iters, trace, planes, hyper)
 
 
+def _rooms_call(who, clouds, panos, rows):
+    """What the rooms forms of pose_information / gauss_newton_refine check and pass on: 1..PCL_GD_MAX_ROOMS unweighted room clouds that all
+    hold one colour set or all one per image, panoramas of one size and texel format, one pose per (room, image), room by room.
+    -> (clouds, panos, the GdRoom array (no boxes), the host array of the panorama addresses, color_sets)"""
+    clouds, panos = list(clouds), list(panos)
+    if not 1 <= len(clouds) <= _lib.GD_MAX_ROOMS:
+        raise ValueError("%s: %d rooms (1..%d per call)" % (who, len(clouds), _lib.GD_MAX_ROOMS))
+    if len(panos) < 1:
+        raise ValueError("%s: no panorama" % who)
+    I = len(panos)
+    for c in clouds:
+        if c.weights is not None:
+            raise ValueError("%s: a weighted room cloud (the rooms chains take no weights)" % who)
+        _residual_cloud(c, panos[0], who, I)
+    if len({int(c.color_sets) for c in clouds}) != 1:
+        raise ValueError("%s: every room cloud needs one colour set, or one per image (%d)" % (who, I))
+    _same_texels(panos, panos[0], "%s: all panoramas must share size and texel format" % who)
+    if rows != len(clouds) * I:
+        raise ValueError("%s: one pose per (room, panorama): %d poses for %d rooms x %d panoramas" % (who, rows, len(clouds), I))
+    rooms = (_lib.GdRoom * len(clouds))(*[_lib.GdRoom(c.data.data_ptr(), c.n, None) for c in clouds])
+    return clouds, panos, rooms, (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos]), int(clouds[0].color_sets)
+
+
+def _pose_information_rooms(who, clouds, panos, trans_ptr, rot_ptr, stride, rows, dev):
+    lib = _lib.load()
+    clouds, panos, rooms, arr, sets = _rooms_call(who, clouds, panos, rows)
+    p0, R, I = panos[0], len(clouds), len(panos)
+    nws = lib.pcl_pose_information_rooms_workspace_bytes(rooms, R, I)
+    if nws == 0:
+        raise ValueError("%s: %d rooms x %d poses are out of range" % (who, R, I))
+    info = torch.empty(R * I, 48, dtype=F32, device=dev)
+    cov = torch.empty(R * I, 6, 6, dtype=F32, device=dev)
+    ws = _bytes(nws)
+    _lib.check(lib.pcl_pose_information_rooms(rooms, R, sets, arr, I, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride, _ptr(info), _ptr(cov), _ptr(ws), nws,
+                                              _stream()), "pcl_pose_information_rooms")
+    return info[:, :36].reshape(R * I, 6, 6), info[:, 36:42], info[:, 42:47], cov
+
+
+def pose_information_rooms(clouds, panos, trans, rot):
+    """pose_information for R x I poses in one set of launches (pcl_pose_information_rooms): row r * I + i of (H, b, stats, cov) is pose
+    (trans[r * I + i], rot[r * I + i]) against room cloud clouds[r] and panos[i] — and, where every room cloud holds I colour sets
+    (Cloud.with_color_sets), colour set i of room r.  That row equals pose_information of that pose, room, colour set and panorama alone,
+    bit for bit.  ValueError: as pose_information; more than PCL_GD_MAX_ROOMS rooms; a weighted room cloud; room clouds whose colour-set
+    counts differ or are neither 1 nor I; panoramas of different sizes or texel formats; a pose count that is not R * I."""
+    trans, rot = _pose_rows(trans, rot)
+    return _pose_information_rooms("pose_information_rooms", clouds, panos, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
+
+
+def pose_information_rooms_at_winners(clouds, panos, winners):
+    """pose_information_rooms at the poses of an (R * I, 16) tensor as GradientDescentRoomsImages.winner() returns it, read on the device
+    (_winner_poses): row r * I + i is the winner of (room r, image i)."""
+    who = "pose_information_rooms_at_winners"
+    return _pose_information_rooms(who, clouds, panos, *_winner_poses(winners, who), winners.device)
+
+
+def _gauss_newton_rooms(who, clouds, panos, trans_ptr, rot_ptr, stride, rows, dev, iters, trace, hyper):
+    lib = _lib.load()
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= GN_MAX_ITERS:
+        raise ValueError("%s: iters %r: an int in 0 .. %d" % (who, iters, GN_MAX_ITERS))
+    hp = gn_hyper(who, **hyper)
+    clouds, panos, rooms, arr, sets = _rooms_call(who, clouds, panos, rows)
+    p0, R, I = panos[0], len(clouds), len(panos)
+    B = R * I
+    nws, nst = lib.pcl_gn_rooms_workspace_bytes(rooms, R, I), lib.pcl_gn_state_bytes(B)
+    if nws == 0 or nst == 0:
+        raise ValueError("%s: %d rooms x %d poses are out of range" % (who, R, I))
+    out = torch.empty(B, 16, dtype=F32, device=dev)
+    info = torch.empty(B, 48, dtype=F32, device=dev)
+    cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
+    tr = torch.empty(iters + 1, B, 16, dtype=F32, device=dev) if trace else None
+    ws, st = _bytes(nws), _bytes(nst)
+    _lib.check(lib.pcl_gn_refine_rooms(rooms, R, sets, arr, I, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride, ctypes.byref(hp), iters, _ptr(st), _ptr(out),
+                                       _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()), "pcl_gn_refine_rooms")
+    ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
+               evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(B, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
+    if trace:
+        ret["trace"] = tr
+    return ret
+
+
+def gauss_newton_refine_rooms(clouds, panos, trans, rot, iters=10, trace=False, **hyper):
+    """gauss_newton_refine for R x I poses in ONE chain (pcl_gn_refine_rooms): pose r * I + i is polished against room cloud clouds[r] and
+    panos[i] — colour set i of room r where the room clouds hold I sets.  -> gauss_newton_refine's dict with one row per (room, image),
+    room by room (trace: (iters + 1, R * I, 16)); every row equals the single call's for that pose, room, colour set and panorama, bit for
+    bit — a pose that freezes moves no other pose's bits.  ValueError: as pose_information_rooms and gauss_newton_refine."""
+    trans, rot = _pose_rows(trans, rot)
+    return _gauss_newton_rooms("gauss_newton_refine_rooms", clouds, panos, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace,
+                               hyper)
+
+
+def gauss_newton_refine_rooms_at_winners(clouds, panos, winners, iters=10, trace=False, **hyper):
+    """gauss_newton_refine_rooms from the poses of an (R * I, 16) tensor as GradientDescentRoomsImages.winner() returns it, read on the device
+    (_winner_poses)."""
+    who = "gauss_newton_refine_rooms_at_winners"
+    return _gauss_newton_rooms(who, clouds, panos, *_winner_poses(winners, who), winners.device, iters, trace, hyper)
+
+
 def point_residuals_images(cloud, panos, trans, rot, packed=False):
     """(I, N) float GPU tensor: row i is point_residuals of pose (trans[i], rot[i]) against panos[i] — and, for a cloud of I colour sets
     (Cloud.with_color_sets), colour set i — in ONE launch (pcl_point_residuals_images; the panorama addresses are kernel arguments).  Row i
