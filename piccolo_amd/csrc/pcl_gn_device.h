@@ -1,6 +1,7 @@
-// pcl_gn_device.h — what pcl_gn.hip and pcl_gn_rooms.hip share of the Levenberg-Marquardt chain: the per-pose state, the hyper-parameter
-// check and the init launch.  The rooms chain is a translation unit of its own: a second step kernel beside pcl_gn_step_kernel changes how
-// the compiler inlines the double-precision library calls of both, and pcl_gn_step_kernel keeps the instruction stream it had.
+// pcl_gn_device.h — what pcl_gn.hip and pcl_gn_rooms.hip share of the Levenberg-Marquardt chain: the per-pose state, the entry check of
+// the three pcl_gn_refine* calls, the init launch and the chain driver.  The step kernels' body, the other thing they share, is the text
+// pcl_gn_step_body.h.  The rooms chain is a translation unit of its own: a second step kernel beside pcl_gn_step_kernel changes how the
+// compiler inlines the double-precision library calls of both, and pcl_gn_step_kernel keeps the instruction stream it had.
 #pragma once
 #include <math.h>
 
@@ -27,5 +28,34 @@ static inline bool pcl_gn_hyper_ok(const pcl_gn_hyper* h)
     return h->lam0 > 0.f && h->lam_up > 1.f && h->lam_down > 0.f && h->lam_down <= 1.f && h->lam_min <= h->lam_max && h->step_cap > 0.f && h->tol >= 0.f;
 }
 
-// pcl_gn_init_kernel over B poses (pcl_gn.hip): the launch of the chains of the other translation unit
+// What every pcl_gn_refine* entry point checks first, before its form's own arguments: the buffers it cannot do without, iters, the hyper
+static inline bool pcl_gn_entry_ok(const pcl_gn_hyper* hyper_host, int iters, const void* state, const float* out, const float* info, const void* workspace)
+{
+    if (!hyper_host || !state || !out || !info || !workspace) return false;
+    return iters >= 0 && iters <= PCL_GN_MAX_ITERS && pcl_gn_hyper_ok(hyper_host);
+}
+
+// pcl_gn_init_kernel over B poses (pcl_gn.hip)
 int pcl_gn_launch_init(PclGnState* state, const float* trans, const float* rot, int pose_stride, float lam0, float* trace, int B, int iters, hipStream_t s);
+
+// The chain of all three forms over B poses: `a` comes from the form's argument check with the caller's poses in a.pass.  The init launch
+// reads them; from then on the state is the pose source (theta_try in place) and the workspace holds the partial rows.  Evaluation
+// k = 0 .. iters is pass(a, st), whatever launches the form's gated pass takes, and step(a.partials, st, hp, k), its one step launch.
+template <class Pass, class Step>
+static inline int pcl_gn_chain(PclInfoArgs& a, int B, const pcl_gn_hyper* hyper_host, int iters, void* state, float* trace, void* workspace, hipStream_t s,
+                               Pass&& pass, Step&& step)
+{
+    PclGnState* st = (PclGnState*)state;
+    const pcl_gn_hyper hp = *hyper_host;
+    const int rc = pcl_gn_launch_init(st, a.pass.trans, a.pass.rot, a.pass.pose_stride, hp.lam0, trace, B, iters, s);
+    if (rc) return rc;
+    a.partials = (float*)workspace;
+    a.pass.trans = st->tri; a.pass.rot = st->tri + 3; a.pass.pose_stride = (int)(sizeof(PclGnState) / sizeof(float));
+    for (int k = 0; k <= iters; k++) {
+        pass(a, (const PclGnState*)st);
+        PCL_LAUNCH_CHECK();
+        step((const float*)a.partials, st, hp, k);
+        PCL_LAUNCH_CHECK();
+    }
+    return 0;
+}

@@ -3,7 +3,7 @@
 //
 //   theta = (t0, t1, t2, yaw, pitch, roll); per point i: mask bit m_i (the loss kernel's), weight w_i (1 without a weight plane),
 //   residual l_i = ||c_i - rgb_i||, j_i = d l_i / d theta = C a_i with a_i = [g_i; tau_i], g = d l / d p in the camera frame,
-//   tau = p x g, and C the 6 x 6 map of pcl_chain_rule (restated in the finish kernel below).
+//   tau = p x g, and C the 6 x 6 map of pcl_chain_rule (restated in the finish text, pcl_info_finish_body.h).
 //   M = sum w m    S1 = sum w m l    S2 = sum w m l^2    H = sum w m j j^T    b = sum w m l j    sigma^2 = S2 / M    cov = sigma^2 H^-1
 //
 // pcl_pose_info_kernel is the per-point pass of pcl_point_pass.h, the one pcl_point_residuals_kernel is (256 threads, a lane carries the two
@@ -51,258 +51,32 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_rooms_kernel(PclInfoA
     pcl_info_pass_rooms<FMT, CS>(a, im, pcl_info_room_select(rm, (unsigned)a.pass.B));
 }
 
-// (pcl_info_device.h restates the row sum, the chain rule, the factorisation and the record below as device functions for pcl_gn_step_kernel;
-// this kernel keeps its own text: built from those functions it computes the same and compiles to another instruction stream.)
-// One 256-thread block per pose.  Thread (part, k), part = tid / 32, adds entry k of its eighth of the chunks' rows in double, lowest chunk
-// first; the eight parts are then added pairwise in a fixed order (a 1M-point cloud has ~1000 rows per pose: one lane walking them all
-// is most of the call's time at B = 1).  Thread 0 then does the 6 x 6 algebra in double on matrices kept in LDS (runtime indices there
-// cost nothing; in registers they would cost scratch) and rounds every output once.
-//   j = C a:  grad_t = -R^T g;  yaw = tau_z;  pitch = -sy tau_x + cy tau_y;  roll = cy cp tau_x + sy cp tau_y - sp tau_z
-// with R the fp32 matrix of pcl_rot_from_ypr and the sines / cosines of the fp32 angles in double, as pcl_finish_kernel takes them.
-// The factorisation runs on H scaled by an exact power of two (largest diagonal entry into [1/2, 1)), so that weights scaled by a power
-// of two scale cov by the inverse power and change no other bit.  status 2: a pivot <= 6 * 2^-52 * (the largest diagonal entry).
+// The finish: one 256-thread block per pose adds the pose's chunk rows in double in a fixed order, forms H = C A C^T and b = C v, factorises
+// and writes the record and the covariance.  Its body is ONE text, pcl_info_finish_body.h, included by both kernels below after a
+// prologue that names the pose's rows, pose and outputs (that file says why it is a text, not a function).
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_finish_kernel(const float* __restrict__ partials, int nchunks, int B,
                                                                         const float* __restrict__ trans, const float* __restrict__ rot,
                                                                         int pose_stride, float* __restrict__ info, float* __restrict__ cov)
 {
-    __shared__ double s[PCL_INFO_ROW];
-    __shared__ double A[6][6], C[6][6], T[6][6], Hm[6][6], L[6][6], Li[6][6], bv[6];
-    __shared__ float R[9];
-    __shared__ double parts[PCL_BLOCK / PCL_INFO_ROW][PCL_INFO_ROW];
-    const int b = blockIdx.x, k = threadIdx.x % PCL_INFO_ROW, part = threadIdx.x / PCL_INFO_ROW;
-    {
-        const int per = (nchunks + PCL_BLOCK / PCL_INFO_ROW - 1) / (PCL_BLOCK / PCL_INFO_ROW);
-        const int c0 = part * per, c1 = min(nchunks, c0 + per);
-        double t = 0.0;
-        for (int c = c0; c < c1; c++) t += (double)partials[((int64_t)c * B + b) * PCL_INFO_ROW + k];
-        parts[part][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < PCL_INFO_ROW)
-        s[k] = ((parts[0][k] + parts[1][k]) + (parts[2][k] + parts[3][k])) + ((parts[4][k] + parts[5][k]) + (parts[6][k] + parts[7][k]));
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const float* tp = trans + (int64_t)b * pose_stride;
-    const float* rp = rot + (int64_t)b * pose_stride;
-    double sy, cy, sp, cp;
-    sincos((double)rp[0], &sy, &cy);
-    sincos((double)rp[1], &sp, &cp);
-    pcl_rot_from_ypr(rp[0], rp[1], rp[2], R);
-    bool finite = true;
-    for (int i = 0; i < 3; i++) finite = finite && fabsf(tp[i]) <= 3.402823466e38f && fabsf(rp[i]) <= 3.402823466e38f;
-    for (int i = 0; i < 6; i++)
-        for (int m = 0; m < 6; m++) C[i][m] = 0.0;
-    for (int i = 0; i < 3; i++)
-        for (int m = 0; m < 3; m++) C[i][m] = -(double)R[3 * m + i];
-    C[3][5] = 1.0;
-    C[4][3] = -sy; C[4][4] = cy;
-    C[5][3] = cy * cp; C[5][4] = sy * cp; C[5][5] = -sp;
-    int q = 0;
-    for (int i = 0; i < 6; i++)
-        for (int m = i; m < 6; m++, q++) { A[i][m] = s[q]; A[m][i] = s[q]; }
-    for (int i = 0; i < 6; i++)
-        for (int m = 0; m < 6; m++) {
-            double t = 0.0;
-            for (int r = 0; r < 6; r++) t += C[i][r] * A[r][m];
-            T[i][m] = t;
-        }
-    for (int i = 0; i < 6; i++) {
-        for (int m = i; m < 6; m++) {
-            double t = 0.0;
-            for (int r = 0; r < 6; r++) t += T[i][r] * C[m][r];
-            Hm[i][m] = t; Hm[m][i] = t;
-        }
-        double t = 0.0;
-        for (int r = 0; r < 6; r++) t += C[i][r] * s[21 + r];
-        bv[i] = t;
-    }
-    const double S2 = s[27], S1 = s[28], M = s[29], sigma2 = S2 / M;
-    for (int i = 0; i < PCL_INFO_NSUM; i++) finite = finite && fabs(s[i]) <= 1.7976931348623157e308;
-    for (int i = 0; i < 6; i++) {
-        finite = finite && fabs(bv[i]) <= 1.7976931348623157e308;
-        for (int m = 0; m < 6; m++) finite = finite && fabs(Hm[i][m]) <= 1.7976931348623157e308;
-    }
-    int status = (finite && M > 0.0) ? 0 : 1;
-    int e = 0;
-    if (status == 0) {
-        double maxd = 0.0;
-        for (int i = 0; i < 6; i++) maxd = fmax(maxd, Hm[i][i]);
-        if (!(maxd > 0.0)) status = 2;
-        else {
-            const double ms = frexp(maxd, &e), tol = 6.0 * 2.220446049250313e-16 * ms;
-            for (int i = 0; i < 6 && status == 0; i++) {
-                double d = ldexp(Hm[i][i], -e);
-                for (int r = 0; r < i; r++) d -= L[i][r] * L[i][r];
-                if (!(d > tol)) { status = 2; break; }
-                const double piv = sqrt(d);
-                L[i][i] = piv;
-                for (int m = i + 1; m < 6; m++) {
-                    double t = ldexp(Hm[m][i], -e);
-                    for (int r = 0; r < i; r++) t -= L[m][r] * L[i][r];
-                    L[m][i] = t / piv;
-                }
-            }
-        }
-    }
-    float* o = info + (int64_t)b * PCL_INFO_REC;
-    for (int i = 0; i < 6; i++)
-        for (int m = 0; m < 6; m++) o[6 * i + m] = (float)Hm[i][m];
-    for (int i = 0; i < 6; i++) o[36 + i] = (float)bv[i];
-    o[42] = (float)M; o[43] = (float)S1; o[44] = (float)S2; o[45] = (float)sigma2; o[46] = (float)status; o[47] = 0.f;
-    if (!cov) return;
-    float* cv = cov + (int64_t)b * 36;
-    if (status != 0) {
-        for (int i = 0; i < 36; i++) cv[i] = __builtin_nanf("");
-        return;
-    }
-    // Li = L^-1 (lower triangular), (H / 2^e)^-1 = Li^T Li
-    for (int m = 0; m < 6; m++) {
-        Li[m][m] = 1.0 / L[m][m];
-        for (int i = m + 1; i < 6; i++) {
-            double t = 0.0;
-            for (int r = m; r < i; r++) t += L[i][r] * Li[r][m];
-            Li[i][m] = -t / L[i][i];
-        }
-    }
-    for (int i = 0; i < 6; i++)
-        for (int m = i; m < 6; m++) {
-            double t = 0.0;
-            for (int r = m; r < 6; r++) t += Li[r][i] * Li[r][m];
-            const float c = (float)ldexp(sigma2 * t, -e);
-            cv[6 * i + m] = c; cv[6 * m + i] = c;
-        }
+    const int b = blockIdx.x;
+#include "pcl_info_finish_body.h"
 }
 
 // The finish of pcl_pose_information_rooms: one block per pose (r, i) = blockIdx.x, over room r's own chunk count and region of rows.
-// pcl_pose_info_finish_kernel's text, statement for statement (a pose that is not finite reports NaNs whose SIGN BITS depend on how the
-// compiler orders and negates the operands of the products below: the same statements give the same bits, the device functions of
-// pcl_info_device.h give the bits of pcl_gn_step_kernel instead).
 __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_finish_rooms_kernel(const float* __restrict__ partials_all, PclInfoRooms rm, int nimages,
                                                                               const float* __restrict__ trans_all, const float* __restrict__ rot_all,
                                                                               int pose_stride, float* __restrict__ info_all, float* __restrict__ cov_all)
 {
-    __shared__ double s[PCL_INFO_ROW];
-    __shared__ double A[6][6], C[6][6], T[6][6], Hm[6][6], L[6][6], Li[6][6], bv[6];
-    __shared__ float R[9];
-    __shared__ double parts[PCL_BLOCK / PCL_INFO_ROW][PCL_INFO_ROW];
     const int pose = blockIdx.x, room = pose / nimages, b = pose - room * nimages, B = nimages, nchunks = rm.rec[room].nchunks;
     const float* __restrict__ partials = partials_all + rm.rec[room].rows;
     const float* __restrict__ trans = trans_all + (int64_t)room * nimages * pose_stride;
     const float* __restrict__ rot = rot_all + (int64_t)room * nimages * pose_stride;
     float* __restrict__ info = info_all + (int64_t)room * nimages * PCL_INFO_REC;
     float* __restrict__ cov = cov_all ? cov_all + (int64_t)room * nimages * 36 : nullptr;
-    const int k = threadIdx.x % PCL_INFO_ROW, part = threadIdx.x / PCL_INFO_ROW;
-    {
-        const int per = (nchunks + PCL_BLOCK / PCL_INFO_ROW - 1) / (PCL_BLOCK / PCL_INFO_ROW);
-        const int c0 = part * per, c1 = min(nchunks, c0 + per);
-        double t = 0.0;
-        for (int c = c0; c < c1; c++) t += (double)partials[((int64_t)c * B + b) * PCL_INFO_ROW + k];
-        parts[part][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < PCL_INFO_ROW)
-        s[k] = ((parts[0][k] + parts[1][k]) + (parts[2][k] + parts[3][k])) + ((parts[4][k] + parts[5][k]) + (parts[6][k] + parts[7][k]));
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const float* tp = trans + (int64_t)b * pose_stride;
-    const float* rp = rot + (int64_t)b * pose_stride;
-    double sy, cy, sp, cp;
-    sincos((double)rp[0], &sy, &cy);
-    sincos((double)rp[1], &sp, &cp);
-    pcl_rot_from_ypr(rp[0], rp[1], rp[2], R);
-    bool finite = true;
-    for (int i = 0; i < 3; i++) finite = finite && fabsf(tp[i]) <= 3.402823466e38f && fabsf(rp[i]) <= 3.402823466e38f;
-    for (int i = 0; i < 6; i++)
-        for (int m = 0; m < 6; m++) C[i][m] = 0.0;
-    for (int i = 0; i < 3; i++)
-        for (int m = 0; m < 3; m++) C[i][m] = -(double)R[3 * m + i];
-    C[3][5] = 1.0;
-    C[4][3] = -sy; C[4][4] = cy;
-    C[5][3] = cy * cp; C[5][4] = sy * cp; C[5][5] = -sp;
-    int q = 0;
-    for (int i = 0; i < 6; i++)
-        for (int m = i; m < 6; m++, q++) { A[i][m] = s[q]; A[m][i] = s[q]; }
-    for (int i = 0; i < 6; i++)
-        for (int m = 0; m < 6; m++) {
-            double t = 0.0;
-            for (int r = 0; r < 6; r++) t += C[i][r] * A[r][m];
-            T[i][m] = t;
-        }
-    for (int i = 0; i < 6; i++) {
-        for (int m = i; m < 6; m++) {
-            double t = 0.0;
-            for (int r = 0; r < 6; r++) t += T[i][r] * C[m][r];
-            Hm[i][m] = t; Hm[m][i] = t;
-        }
-        double t = 0.0;
-        for (int r = 0; r < 6; r++) t += C[i][r] * s[21 + r];
-        bv[i] = t;
-    }
-    const double S2 = s[27], S1 = s[28], M = s[29], sigma2 = S2 / M;
-    for (int i = 0; i < PCL_INFO_NSUM; i++) finite = finite && fabs(s[i]) <= 1.7976931348623157e308;
-    for (int i = 0; i < 6; i++) {
-        finite = finite && fabs(bv[i]) <= 1.7976931348623157e308;
-        for (int m = 0; m < 6; m++) finite = finite && fabs(Hm[i][m]) <= 1.7976931348623157e308;
-    }
-    int status = (finite && M > 0.0) ? 0 : 1;
-    int e = 0;
-    if (status == 0) {
-        double maxd = 0.0;
-        for (int i = 0; i < 6; i++) maxd = fmax(maxd, Hm[i][i]);
-        if (!(maxd > 0.0)) status = 2;
-        else {
-            const double ms = frexp(maxd, &e), tol = 6.0 * 2.220446049250313e-16 * ms;
-            for (int i = 0; i < 6 && status == 0; i++) {
-                double d = ldexp(Hm[i][i], -e);
-                for (int r = 0; r < i; r++) d -= L[i][r] * L[i][r];
-                if (!(d > tol)) { status = 2; break; }
-                const double piv = sqrt(d);
-                L[i][i] = piv;
-                for (int m = i + 1; m < 6; m++) {
-                    double t = ldexp(Hm[m][i], -e);
-                    for (int r = 0; r < i; r++) t -= L[m][r] * L[i][r];
-                    L[m][i] = t / piv;
-                }
-            }
-        }
-    }
-    float* o = info + (int64_t)b * PCL_INFO_REC;
-    for (int i = 0; i < 6; i++)
-        for (int m = 0; m < 6; m++) o[6 * i + m] = (float)Hm[i][m];
-    for (int i = 0; i < 6; i++) o[36 + i] = (float)bv[i];
-    o[42] = (float)M; o[43] = (float)S1; o[44] = (float)S2; o[45] = (float)sigma2; o[46] = (float)status; o[47] = 0.f;
-    if (!cov) return;
-    float* cv = cov + (int64_t)b * 36;
-    if (status != 0) {
-        for (int i = 0; i < 36; i++) cv[i] = __builtin_nanf("");
-        return;
-    }
-    // Li = L^-1 (lower triangular), (H / 2^e)^-1 = Li^T Li
-    for (int m = 0; m < 6; m++) {
-        Li[m][m] = 1.0 / L[m][m];
-        for (int i = m + 1; i < 6; i++) {
-            double t = 0.0;
-            for (int r = m; r < i; r++) t += L[i][r] * Li[r][m];
-            Li[i][m] = -t / L[i][i];
-        }
-    }
-    for (int i = 0; i < 6; i++)
-        for (int m = i; m < 6; m++) {
-            double t = 0.0;
-            for (int r = m; r < 6; r++) t += Li[r][i] * Li[r][m];
-            const float c = (float)ldexp(sigma2 * t, -e);
-            cv[6 * i + m] = c; cv[6 * m + i] = c;
-        }
+#include "pcl_info_finish_body.h"
 }
 
-extern "C" size_t pcl_pose_information_workspace_bytes(int64_t n, int B)
-{
-    const int64_t nchunks = pcl_pass_chunks(n, PCL_INFO_MIN_STEPS, nullptr);
-    if (nchunks == 0 || B <= 0 || nchunks * B > 0x7fffffffll) return 0;
-    PclCarve c{nullptr, 0};
-    c.take((size_t)nchunks * (size_t)B * PCL_INFO_ROW * sizeof(float));
-    return c.off;
-}
+extern "C" size_t pcl_pose_information_workspace_bytes(int64_t n, int B) { return pcl_info_workspace_bytes(n, B); }
 
 extern "C" int pcl_pose_information(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W,
                                     const float* trans, const float* rot, int pose_stride, int B, float* info, float* cov, void* workspace,
@@ -313,7 +87,7 @@ extern "C" int pcl_pose_information(const float* cloud, const float* weights, in
     int64_t nchunks;
     const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
     if (rc) return rc;
-    if (workspace_bytes < pcl_pose_information_workspace_bytes(n, B)) return PCL_EINVAL;
+    if (workspace_bytes < pcl_info_workspace_bytes(n, B)) return PCL_EINVAL;
     a.weights = weights; a.partials = (float*)workspace;
     const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
     hipStream_t s = (hipStream_t)stream;
@@ -342,7 +116,7 @@ extern "C" int pcl_pose_information_images(const float* cloud, const float* weig
     const int rc = pcl_info_images_args(&a, &im, cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot,
                                         pose_stride, &nchunks);
     if (rc) return rc;
-    if (workspace_bytes < pcl_pose_information_workspace_bytes(n, nimages)) return PCL_EINVAL;
+    if (workspace_bytes < pcl_info_workspace_bytes(n, nimages)) return PCL_EINVAL;
     a.partials = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
     pcl_info_images_launches(a, im, panos_host, nchunks, [&](const PclInfoArgs& al, const PclInfoImages& il, int, dim3 grid) {

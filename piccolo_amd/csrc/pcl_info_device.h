@@ -1,7 +1,10 @@
 // pcl_info_device.h — what pcl_info.hip (the information matrix at given poses) and pcl_gn.hip (the Levenberg-Marquardt chain on it) share:
 // the per-point pass that accumulates the 30 sums into one partial row per (chunk, pose), the fixed-order sum of a pose's rows in
 // double, the chain rule H = C A C^T, b = C v, the Cholesky factorisation on a power-of-two scaling and the info record / covariance.
-// Every function is inlined into its kernel: a kernel built from them has the arithmetic, and the bits, of every other.
+// Every function is inlined into its kernel: a kernel built from them has the arithmetic, and the bits, of every other.  The step text
+// (pcl_gn_step_body.h) is built from the row sum, chain rule, factorisation and record below; the finish text (pcl_info_finish_body.h)
+// spells the same algebra out on its own, because built from these functions it compiles to another instruction stream.  An edit to
+// the algebra is made in those two places, here and there, and the tests assert on the device that they agree bit for bit.
 // Outside the loss-kernel hash: the four files it covers are included, never edited.
 #pragma once
 #include <math.h>
@@ -282,6 +285,18 @@ __device__ __forceinline__ void pcl_info_emit(const double (*Hm)[6], const doubl
         }
 }
 
+// ---- host side: the partial rows [nchunks][B][PCL_INFO_ROW] of a call over one cloud, which are the whole workspace of
+// pcl_pose_information, pcl_pose_information_images, pcl_gn_refine and pcl_gn_refine_images (0: n or B out of range, or more blocks than
+// a grid holds)
+static inline size_t pcl_info_workspace_bytes(int64_t n, int B)
+{
+    const int64_t nchunks = pcl_pass_chunks(n, PCL_INFO_MIN_STEPS, nullptr);
+    if (nchunks == 0 || B <= 0 || nchunks * B > 0x7fffffffll) return 0;
+    PclCarve c{nullptr, 0};
+    c.take((size_t)nchunks * (size_t)B * PCL_INFO_ROW * sizeof(float));
+    return c.off;
+}
+
 // ---- host side of the images entry points (pcl_pose_information_images, pcl_gn_refine_images): every check, before any launch
 // weights == NULL with weight_sets 0; else weight_sets 1 (one plane for every image) or nimages (plane i at weights + i * stride);
 // color_sets 0 / 1 (the cloud's one set) or nimages (pcl_point_residuals_images' rule).  Fills a (a.pass.B = nimages, a.pass.pano = the
@@ -306,20 +321,29 @@ static inline int pcl_info_images_args(PclInfoArgs* a, PclInfoImages* im, const 
     return 0;
 }
 
-// The launches of one evaluation of all the images: launch(al, il, grid) for every run of at most PCL_RES_MAX_IMAGES images, with the
-// poses sliced (pose_stride floats per pose from a.pass.trans / rot) and the colour set, weight plane and partial row counted from the
-// call's first image
+// One launch's slice of a call: the run of at most PCL_RES_MAX_IMAGES images from image i0 on.  *al, *il are the call's a, im with the run's
+// panorama table, img0 = i0, the poses sliced (pose_stride floats per pose from a.pass.trans / rot) and the launch's pose count.  -> that count
+static inline int pcl_info_slice(const PclInfoArgs& a, const PclInfoImages& im, const uint64_t* panos_host, int i0, PclInfoArgs* al, PclInfoImages* il)
+{
+    const int m = im.btot - i0 < PCL_RES_MAX_IMAGES ? im.btot - i0 : PCL_RES_MAX_IMAGES;
+    *il = im;
+    for (int i = 0; i < PCL_RES_MAX_IMAGES; i++) il->panos.p[i] = i < m ? (unsigned long long)panos_host[i0 + i] : 0ull;
+    il->img0 = i0;
+    *al = a;
+    al->pass.trans = a.pass.trans + (int64_t)i0 * a.pass.pose_stride; al->pass.rot = a.pass.rot + (int64_t)i0 * a.pass.pose_stride;
+    al->pass.B = m;
+    return m;
+}
+
+// The launches of one evaluation of all the images: launch(al, il, i0, grid) for every such run, the colour set, weight plane and partial
+// row counted from the call's first image
 template <class F>
 static inline void pcl_info_images_launches(const PclInfoArgs& a, const PclInfoImages& im, const uint64_t* panos_host, int64_t nchunks, F&& launch)
 {
     for (int i0 = 0; i0 < im.btot; i0 += PCL_RES_MAX_IMAGES) {
-        const int m = im.btot - i0 < PCL_RES_MAX_IMAGES ? im.btot - i0 : PCL_RES_MAX_IMAGES;
-        PclInfoImages il = im;
-        for (int i = 0; i < PCL_RES_MAX_IMAGES; i++) il.panos.p[i] = i < m ? (unsigned long long)panos_host[i0 + i] : 0ull;
-        il.img0 = i0;
-        PclInfoArgs al = a;
-        al.pass.trans = a.pass.trans + (int64_t)i0 * a.pass.pose_stride; al.pass.rot = a.pass.rot + (int64_t)i0 * a.pass.pose_stride;
-        al.pass.B = m;
+        PclInfoArgs al;
+        PclInfoImages il;
+        const int m = pcl_info_slice(a, im, panos_host, i0, &al, &il);
         launch(al, il, i0, dim3((unsigned)(nchunks * m)));
     }
 }
@@ -383,19 +407,15 @@ static inline int pcl_info_rooms_args(PclInfoArgs* a, PclInfoImages* im, PclInfo
     return 0;
 }
 
-// The launches of one evaluation of all rooms x images: launch(al, il, tl, i0, grid) for every run of at most PCL_RES_MAX_IMAGES images, all
-// rooms in each — the poses sliced by the run's first image, the rooms' block ranges laid out for the run's image count
+// The launches of one evaluation of all rooms x images: launch(al, il, tl, i0, grid) for every run of pcl_info_slice, all rooms in each,
+// the rooms' block ranges laid out for the run's image count
 template <class F>
 static inline void pcl_info_rooms_launches(const PclInfoArgs& a, const PclInfoImages& im, const PclInfoRoomsPlan& g, const uint64_t* panos_host, F&& launch)
 {
     for (int i0 = 0; i0 < im.btot; i0 += PCL_RES_MAX_IMAGES) {
-        const int m = im.btot - i0 < PCL_RES_MAX_IMAGES ? im.btot - i0 : PCL_RES_MAX_IMAGES;
-        PclInfoImages il = im;
-        for (int i = 0; i < PCL_RES_MAX_IMAGES; i++) il.panos.p[i] = i < m ? (unsigned long long)panos_host[i0 + i] : 0ull;
-        il.img0 = i0;
-        PclInfoArgs al = a;
-        al.pass.trans = a.pass.trans + (int64_t)i0 * a.pass.pose_stride; al.pass.rot = a.pass.rot + (int64_t)i0 * a.pass.pose_stride;
-        al.pass.B = m;
+        PclInfoArgs al;
+        PclInfoImages il;
+        const int m = pcl_info_slice(a, im, panos_host, i0, &al, &il);
         PclInfoRooms tl = g.t;
         int64_t blocks = 0;
         for (int r = 0; r < g.nrooms; r++) {

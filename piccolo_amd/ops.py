@@ -486,16 +486,38 @@ def point_residuals_at_winners(cloud, pano, winners, packed=False, out=None):
     return _point_residuals("point_residuals_at_winners", cloud, pano, *_winner_poses(winners, "point_residuals_at_winners"), winners.device, packed, out)
 
 
-def _pose_information(cloud, pano, trans_ptr, rot_ptr, stride, B, dev):
+# The three forms of pose_information / gauss_newton_refine: one cloud and one panorama, one cloud and a panorama per pose, rooms x panoramas.
+# -> (pose information: library call, workspace query; polish: library call, workspace query)
+_POSE_FORMS = {
+    "single": ("pcl_pose_information", "pcl_pose_information_workspace_bytes", "pcl_gn_refine", "pcl_gn_workspace_bytes"),
+    "images": ("pcl_pose_information_images", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_images", "pcl_gn_workspace_bytes"),
+    "rooms": ("pcl_pose_information_rooms", "pcl_pose_information_rooms_workspace_bytes", "pcl_gn_refine_rooms", "pcl_gn_rooms_workspace_bytes"),
+}
+
+
+def _single_form(cloud, pano):
+    """A form is what _pose_information and _gauss_newton take as the form-specific part of a call: form(who, trans_ptr, rot_ptr, stride, rows)
+    runs the form's own argument checks and -> (key of _POSE_FORMS, the workspace queries' arguments, the pose count B, the arguments the
+    two library calls of the form begin with, up to the poses, and what the queries found out of range when they answer 0).  This one:
+    `rows` poses against one cloud and one panorama (the public functions have run _residual_cloud)."""
+    def form(who, trans_ptr, rot_ptr, stride, rows):
+        head = (_ptr(cloud.data), _ptr(cloud.weights), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr, stride, rows)
+        return "single", (cloud.n, rows), rows, head, "%d points x %d poses" % (cloud.n, rows)
+    return form
+
+
+def _pose_information(who, form, trans_ptr, rot_ptr, stride, rows, dev):
+    """What the six pose_information functions do behind their form's checks -> (H, b, stats, cov)"""
     lib = _lib.load()
+    key, size_args, B, head, what = form(who, trans_ptr, rot_ptr, stride, rows)
+    name, size_name = _POSE_FORMS[key][:2]
+    nws = getattr(lib, size_name)(*size_args)
+    if nws == 0:
+        raise ValueError("%s: %s are out of range" % (who, what))
     info = torch.empty(B, 48, dtype=F32, device=dev)
     cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
-    nws = lib.pcl_pose_information_workspace_bytes(cloud.n, B)
-    if nws == 0:
-        raise ValueError("pose_information: %d points x %d poses are out of range" % (cloud.n, B))
     ws = _bytes(nws)
-    _lib.check(lib.pcl_pose_information(_ptr(cloud.data), _ptr(cloud.weights), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr,
-                                        stride, B, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), "pcl_pose_information")
+    _lib.check(getattr(lib, name)(*head, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), name)
     return info[:, :36].reshape(B, 6, 6), info[:, 36:42], info[:, 42:47], cov
 
 
@@ -507,13 +529,13 @@ def pose_information(cloud, pano, trans, rot):
     (cov NaN).  ValueError: a cloud of colour sets, a panorama in one of the trim launch's texel layouts."""
     _residual_cloud(cloud, pano, "pose_information")
     trans, rot = _pose_rows(trans, rot)
-    return _pose_information(cloud, pano, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
+    return _pose_information("pose_information", _single_form(cloud, pano), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
 
 
 def pose_information_at_winners(cloud, pano, winners):
     """pose_information at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses)."""
     _residual_cloud(cloud, pano, "pose_information_at_winners")
-    return _pose_information(cloud, pano, *_winner_poses(winners, "pose_information_at_winners"), winners.device)
+    return _pose_information("pose_information", _single_form(cloud, pano), *_winner_poses(winners, "pose_information_at_winners"), winners.device)
 
 
 GN_HYPER = dict(lam0=1e-3, lam_up=10.0, lam_down=0.1, lam_min=1e-9, lam_max=1e9, step_cap=0.1, tol=0.0)
@@ -539,21 +561,23 @@ def gn_hyper(who="gauss_newton_refine", **hyper):
     return g
 
 
-def _gauss_newton(who, cloud, pano, trans_ptr, rot_ptr, stride, B, dev, iters, trace, hyper):
+def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace, hyper):
+    """What the six gauss_newton_refine functions do: iters, the hyper-parameters, the form's checks, the sizes, the call -> the result dict"""
     lib = _lib.load()
     if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= GN_MAX_ITERS:
         raise ValueError("%s: iters %r: an int in 0 .. %d" % (who, iters, GN_MAX_ITERS))
     hp = gn_hyper(who, **hyper)
-    nws, nst = lib.pcl_gn_workspace_bytes(cloud.n, B), lib.pcl_gn_state_bytes(B)
+    key, size_args, B, head, what = form(who, trans_ptr, rot_ptr, stride, rows)
+    name, size_name = _POSE_FORMS[key][2:]
+    nws, nst = getattr(lib, size_name)(*size_args), lib.pcl_gn_state_bytes(B)
     if nws == 0 or nst == 0:
-        raise ValueError("%s: %d points x %d poses are out of range" % (who, cloud.n, B))
+        raise ValueError("%s: %s are out of range" % (who, what))
     out = torch.empty(B, 16, dtype=F32, device=dev)
     info = torch.empty(B, 48, dtype=F32, device=dev)
     cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
     tr = torch.empty(iters + 1, B, 16, dtype=F32, device=dev) if trace else None
     ws, st = _bytes(nws), _bytes(nst)
-    _lib.check(lib.pcl_gn_refine(_ptr(cloud.data), _ptr(cloud.weights), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr, stride, B,
-                                 ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()), "pcl_gn_refine")
+    _lib.check(getattr(lib, name)(*head, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()), name)
     ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
                evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(B, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
     if trace:
@@ -574,14 +598,15 @@ def gauss_newton_refine(cloud, pano, trans, rot, iters=10, trace=False, **hyper)
     the trim launch's texel layouts, iters outside 0 .. 1000, hyper-parameters out of range."""
     _residual_cloud(cloud, pano, "gauss_newton_refine")
     trans, rot = _pose_rows(trans, rot)
-    return _gauss_newton("gauss_newton_refine", cloud, pano, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace, hyper)
+    return _gauss_newton("gauss_newton_refine", _single_form(cloud, pano), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace,
+                         hyper)
 
 
 def gauss_newton_refine_at_winners(cloud, pano, winners, iters=10, trace=False, **hyper):
     """gauss_newton_refine from the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses)."""
     _residual_cloud(cloud, pano, "gauss_newton_refine_at_winners")
-    return _gauss_newton("gauss_newton_refine_at_winners", cloud, pano, *_winner_poses(winners, "gauss_newton_refine_at_winners"), winners.device,
-                         iters, trace, hyper)
+    who = "gauss_newton_refine_at_winners"
+    return _gauss_newton(who, _single_form(cloud, pano), *_winner_poses(winners, who), winners.device, iters, trace, hyper)
 
 
 def _images_call(who, cloud, panos, rows, planes):
@@ -607,20 +632,14 @@ def _images_call(who, cloud, panos, rows, planes):
     return panos, (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos]), weights, sets
 
 
-def _pose_information_images(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, planes):
-    lib = _lib.load()
-    panos, arr, weights, sets = _images_call(who, cloud, panos, rows, planes)
-    p0, I = panos[0], len(panos)
-    nws = lib.pcl_pose_information_workspace_bytes(cloud.n, I)
-    if nws == 0:
-        raise ValueError("%s: %d points x %d poses are out of range" % (who, cloud.n, I))
-    info = torch.empty(I, 48, dtype=F32, device=dev)
-    cov = torch.empty(I, 6, 6, dtype=F32, device=dev)
-    ws = _bytes(nws)
-    _lib.check(lib.pcl_pose_information_images(_ptr(cloud.data), _ptr(weights), sets, cloud.n, int(cloud.color_sets), arr, I, p0.fmt, p0.H, p0.W,
-                                               trans_ptr, rot_ptr, stride, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()),
-               "pcl_pose_information_images")
-    return info[:, :36].reshape(I, 6, 6), info[:, 36:42], info[:, 42:47], cov
+def _images_form(cloud, panos, planes):
+    """The form (_single_form) of row i against panos[i]: _images_call's checks"""
+    def form(who, trans_ptr, rot_ptr, stride, rows):
+        ps, arr, weights, sets = _images_call(who, cloud, panos, rows, planes)
+        p0, I = ps[0], len(ps)
+        head = (_ptr(cloud.data), _ptr(weights), sets, cloud.n, int(cloud.color_sets), arr, I, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride)
+        return "images", (cloud.n, I), I, head, "%d points x %d poses" % (cloud.n, I)
+    return form
 
 
 def pose_information_images(cloud, panos, trans, rot, planes=None):
@@ -631,39 +650,14 @@ def pose_information_images(cloud, panos, trans, rot, planes=None):
     plane alone, bit for bit.  ValueError: as pose_information; a colour-set count that is not the image count; panoramas of different
     sizes or texel formats; planes of another shape."""
     trans, rot = _pose_rows(trans, rot)
-    return _pose_information_images("pose_information_images", cloud, panos, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, planes)
+    return _pose_information("pose_information_images", _images_form(cloud, panos, planes), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
 
 
 def pose_information_images_at_winners(cloud, panos, winners, planes=None):
     """pose_information_images at the poses of an (I, 16) tensor as _GdEngine.winners(I) returns it, read on the device (_winner_poses): row
     i is winner i against panos[i] (colour set i, plane i)."""
     who = "pose_information_images_at_winners"
-    return _pose_information_images(who, cloud, panos, *_winner_poses(winners, who), winners.device, planes)
-
-
-def _gauss_newton_images(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, iters, trace, planes, hyper):
-    lib = _lib.load()
-    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= GN_MAX_ITERS:
-        raise ValueError("%s: iters %r: an int in 0 .. %d" % (who, iters, GN_MAX_ITERS))
-    hp = gn_hyper(who, **hyper)
-    panos, arr, weights, sets = _images_call(who, cloud, panos, rows, planes)
-    p0, I = panos[0], len(panos)
-    nws, nst = lib.pcl_gn_workspace_bytes(cloud.n, I), lib.pcl_gn_state_bytes(I)
-    if nws == 0 or nst == 0:
-        raise ValueError("%s: %d points x %d poses are out of range" % (who, cloud.n, I))
-    out = torch.empty(I, 16, dtype=F32, device=dev)
-    info = torch.empty(I, 48, dtype=F32, device=dev)
-    cov = torch.empty(I, 6, 6, dtype=F32, device=dev)
-    tr = torch.empty(iters + 1, I, 16, dtype=F32, device=dev) if trace else None
-    ws, st = _bytes(nws), _bytes(nst)
-    _lib.check(lib.pcl_gn_refine_images(_ptr(cloud.data), _ptr(weights), sets, cloud.n, int(cloud.color_sets), arr, I, p0.fmt, p0.H, p0.W, trans_ptr,
-                                        rot_ptr, stride, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws,
-                                        _stream()), "pcl_gn_refine_images")
-    ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
-               evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(I, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
-    if trace:
-        ret["trace"] = tr
-    return ret
+    return _pose_information(who, _images_form(cloud, panos, planes), *_winner_poses(winners, who), winners.device)
 
 
 def gauss_newton_refine_images(cloud, panos, trans, rot, iters=10, trace=False, planes=None, **hyper):
@@ -672,14 +666,14 @@ def gauss_newton_refine_images(cloud, panos, trans, rot, iters=10, trace=False, 
     pose_information_images.  -> gauss_newton_refine's dict with one row per image (trace: (iters + 1, I, 16)); row i equals the single
     call's for that pose, panorama, colour set and plane, bit for bit — a pose that freezes moves no other pose's bits."""
     trans, rot = _pose_rows(trans, rot)
-    return _gauss_newton_images("gauss_newton_refine_images", cloud, panos, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace,
-                                planes, hyper)
+    return _gauss_newton("gauss_newton_refine_images", _images_form(cloud, panos, planes), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device,
+                         iters, trace, hyper)
 
 
 def gauss_newton_refine_images_at_winners(cloud, panos, winners, iters=10, trace=False, planes=None, **hyper):
     """gauss_newton_refine_images from the poses of an (I, 16) tensor as _GdEngine.winners(I) returns it, read on the device (_winner_poses)."""
     who = "gauss_newton_refine_images_at_winners"
-    return _gauss_newton_images(who, cloud, panos, *_winner_poses(winners, who), winners.device, iters, trace, planes, hyper)
+    return _gauss_newton(who, _images_form(cloud, panos, planes), *_winner_poses(winners, who), winners.device, iters, trace, hyper)
 
 
 def _rooms_call(who, clouds, panos, rows):
@@ -705,19 +699,14 @@ def _rooms_call(who, clouds, panos, rows):
     return clouds, panos, rooms, (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos]), int(clouds[0].color_sets)
 
 
-def _pose_information_rooms(who, clouds, panos, trans_ptr, rot_ptr, stride, rows, dev):
-    lib = _lib.load()
-    clouds, panos, rooms, arr, sets = _rooms_call(who, clouds, panos, rows)
-    p0, R, I = panos[0], len(clouds), len(panos)
-    nws = lib.pcl_pose_information_rooms_workspace_bytes(rooms, R, I)
-    if nws == 0:
-        raise ValueError("%s: %d rooms x %d poses are out of range" % (who, R, I))
-    info = torch.empty(R * I, 48, dtype=F32, device=dev)
-    cov = torch.empty(R * I, 6, 6, dtype=F32, device=dev)
-    ws = _bytes(nws)
-    _lib.check(lib.pcl_pose_information_rooms(rooms, R, sets, arr, I, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride, _ptr(info), _ptr(cov), _ptr(ws), nws,
-                                              _stream()), "pcl_pose_information_rooms")
-    return info[:, :36].reshape(R * I, 6, 6), info[:, 36:42], info[:, 42:47], cov
+def _rooms_form(clouds, panos):
+    """The form (_single_form) of row r * I + i against clouds[r] and panos[i]: _rooms_call's checks"""
+    def form(who, trans_ptr, rot_ptr, stride, rows):
+        cs, ps, rooms, arr, sets = _rooms_call(who, clouds, panos, rows)
+        p0, R, I = ps[0], len(cs), len(ps)
+        head = (rooms, R, sets, arr, I, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride)
+        return "rooms", (rooms, R, I), R * I, head, "%d rooms x %d poses" % (R, I)
+    return form
 
 
 def pose_information_rooms(clouds, panos, trans, rot):
@@ -727,39 +716,14 @@ def pose_information_rooms(clouds, panos, trans, rot):
     bit for bit.  ValueError: as pose_information; more than PCL_GD_MAX_ROOMS rooms; a weighted room cloud; room clouds whose colour-set
     counts differ or are neither 1 nor I; panoramas of different sizes or texel formats; a pose count that is not R * I."""
     trans, rot = _pose_rows(trans, rot)
-    return _pose_information_rooms("pose_information_rooms", clouds, panos, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
+    return _pose_information("pose_information_rooms", _rooms_form(clouds, panos), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
 
 
 def pose_information_rooms_at_winners(clouds, panos, winners):
     """pose_information_rooms at the poses of an (R * I, 16) tensor as GradientDescentRoomsImages.winner() returns it, read on the device
     (_winner_poses): row r * I + i is the winner of (room r, image i)."""
     who = "pose_information_rooms_at_winners"
-    return _pose_information_rooms(who, clouds, panos, *_winner_poses(winners, who), winners.device)
-
-
-def _gauss_newton_rooms(who, clouds, panos, trans_ptr, rot_ptr, stride, rows, dev, iters, trace, hyper):
-    lib = _lib.load()
-    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= GN_MAX_ITERS:
-        raise ValueError("%s: iters %r: an int in 0 .. %d" % (who, iters, GN_MAX_ITERS))
-    hp = gn_hyper(who, **hyper)
-    clouds, panos, rooms, arr, sets = _rooms_call(who, clouds, panos, rows)
-    p0, R, I = panos[0], len(clouds), len(panos)
-    B = R * I
-    nws, nst = lib.pcl_gn_rooms_workspace_bytes(rooms, R, I), lib.pcl_gn_state_bytes(B)
-    if nws == 0 or nst == 0:
-        raise ValueError("%s: %d rooms x %d poses are out of range" % (who, R, I))
-    out = torch.empty(B, 16, dtype=F32, device=dev)
-    info = torch.empty(B, 48, dtype=F32, device=dev)
-    cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
-    tr = torch.empty(iters + 1, B, 16, dtype=F32, device=dev) if trace else None
-    ws, st = _bytes(nws), _bytes(nst)
-    _lib.check(lib.pcl_gn_refine_rooms(rooms, R, sets, arr, I, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride, ctypes.byref(hp), iters, _ptr(st), _ptr(out),
-                                       _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()), "pcl_gn_refine_rooms")
-    ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
-               evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(B, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
-    if trace:
-        ret["trace"] = tr
-    return ret
+    return _pose_information(who, _rooms_form(clouds, panos), *_winner_poses(winners, who), winners.device)
 
 
 def gauss_newton_refine_rooms(clouds, panos, trans, rot, iters=10, trace=False, **hyper):
@@ -768,15 +732,15 @@ def gauss_newton_refine_rooms(clouds, panos, trans, rot, iters=10, trace=False, 
     room by room (trace: (iters + 1, R * I, 16)); every row equals the single call's for that pose, room, colour set and panorama, bit for
     bit — a pose that freezes moves no other pose's bits.  ValueError: as pose_information_rooms and gauss_newton_refine."""
     trans, rot = _pose_rows(trans, rot)
-    return _gauss_newton_rooms("gauss_newton_refine_rooms", clouds, panos, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace,
-                               hyper)
+    return _gauss_newton("gauss_newton_refine_rooms", _rooms_form(clouds, panos), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters,
+                         trace, hyper)
 
 
 def gauss_newton_refine_rooms_at_winners(clouds, panos, winners, iters=10, trace=False, **hyper):
     """gauss_newton_refine_rooms from the poses of an (R * I, 16) tensor as GradientDescentRoomsImages.winner() returns it, read on the device
     (_winner_poses)."""
     who = "gauss_newton_refine_rooms_at_winners"
-    return _gauss_newton_rooms(who, clouds, panos, *_winner_poses(winners, who), winners.device, iters, trace, hyper)
+    return _gauss_newton(who, _rooms_form(clouds, panos), *_winner_poses(winners, who), winners.device, iters, trace, hyper)
 
 
 def point_residuals_images(cloud, panos, trans, rot, packed=False):
