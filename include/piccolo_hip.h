@@ -247,6 +247,34 @@ int pcl_gn_refine_images(const float *cloud, const float *weights, int weight_se
                          int pano_format, int H, int W, const float *trans, const float *rot, int pose_stride, const pcl_gn_hyper *hyper_host,
                          int iters, void *state, float *out, float *info, float *cov, float *trace, void *workspace, size_t workspace_bytes,
                          void *stream);
+/* The Huber-L1 forms of the four calls above (additive to ABI 12; BUILD-DEFINED): a polish that minimises, for
+ * delta -> 0, the sampling loss itself.  Per kept point with residual l >= 0 and delta > 0
+ *   phi(l) = min(1 / l, 1 / delta)                              the IRLS weight (l = 0: 1 / delta)
+ *   rho(l) = l >= delta ? l - delta / 2 : l^2 / (2 delta)       Huber's function divided by delta: C^1, rho' = phi l, -> l as delta -> 0
+ *   F_rho = sum w m rho / sum w m     H_rho = sum w m phi j j^T     b_rho = sum w m phi l j
+ * The parameters are the twin's without `cov`, plus `float delta` before the stream.  The 48-float record holds H_rho (0..35), b_rho
+ * (36..41), M (42) and S1 (43) — both PLAIN, no phi: S1 / M is the weighted sampling loss at the pose —, sum w m rho (44), F_rho (45) and
+ * the status (46).  In pcl_gn_refine_l1 / pcl_gn_refine_images_l1 the chain decides on F_rho and solves (H_rho + lambda diag H_rho) d =
+ * -b_rho; the `out` and trace columns that hold sigma^2 in the twin hold F_rho.  For delta >= max l the record's H, b are the twin's
+ * divided by delta and slot 44 is S2 / (2 delta).  No covariance is offered: F_rho H_rho^-1 is not the twin's.  Only the per-point pass
+ * differs from the twin (an instance of the same kernel text); the init, step and finish kernels, the state, the sizes
+ * (pcl_pose_information_workspace_bytes, pcl_gn_workspace_bytes, pcl_gn_state_bytes), the launch counts, the gate on frozen poses and the
+ * bit-for-bit independence of poses and images are the twin's.  No atomics, no allocation, no synchronisation: capturable.
+ * PCL_EINVAL, before any launch: what the twin refuses; a delta that is not finite or lies outside [2^-20, 4] as a float (residuals
+ * never exceed sqrt(3)).  Deliberately left out: a rooms form, the depth mask, any claim about real data. */
+int pcl_pose_information_l1(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans,
+                            const float *rot, int pose_stride, int B, float *info, void *workspace, size_t workspace_bytes, float delta,
+                            void *stream);
+int pcl_pose_information_images_l1(const float *cloud, const float *weights, int weight_sets, int64_t n, int color_sets, const uint64_t *panos_host,
+                                   int nimages, int pano_format, int H, int W, const float *trans, const float *rot, int pose_stride, float *info,
+                                   void *workspace, size_t workspace_bytes, float delta, void *stream);
+int pcl_gn_refine_l1(const float *cloud, const float *weights, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans,
+                     const float *rot, int pose_stride, int B, const pcl_gn_hyper *hyper_host, int iters, void *state, float *out, float *info,
+                     float *trace, void *workspace, size_t workspace_bytes, float delta, void *stream);
+int pcl_gn_refine_images_l1(const float *cloud, const float *weights, int weight_sets, int64_t n, int color_sets, const uint64_t *panos_host,
+                            int nimages, int pano_format, int H, int W, const float *trans, const float *rot, int pose_stride,
+                            const pcl_gn_hyper *hyper_host, int iters, void *state, float *out, float *info, float *trace, void *workspace,
+                            size_t workspace_bytes, float delta, void *stream);
 /* The Morton order in one call, entirely on the device: bounding box, 63-bit keys, stable radix sort of (key, index);
  * order[i] = index of the point for packed slot i.  workspace: pcl_cloud_order_workspace_bytes(n). */
 size_t pcl_cloud_order_workspace_bytes(int64_t n);

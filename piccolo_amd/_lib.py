@@ -67,6 +67,13 @@ SIGNATURES = {
                                            _sz, _vp]),
     "pcl_gn_refine_images": (_int, [_vp, _vp, _int, _i64, _int, _c.POINTER(_c.c_uint64), _int, _int, _int, _int, _vp, _vp, _int, _c.POINTER(GnHyper),
                                     _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pcl_pose_information_l1": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _sz, _c.c_float, _vp]),
+    "pcl_pose_information_images_l1": (_int, [_vp, _vp, _int, _i64, _int, _c.POINTER(_c.c_uint64), _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _sz,
+                                              _c.c_float, _vp]),
+    "pcl_gn_refine_l1": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _c.POINTER(GnHyper), _int, _vp, _vp, _vp, _vp, _vp, _sz,
+                                _c.c_float, _vp]),
+    "pcl_gn_refine_images_l1": (_int, [_vp, _vp, _int, _i64, _int, _c.POINTER(_c.c_uint64), _int, _int, _int, _int, _vp, _vp, _int, _c.POINTER(GnHyper),
+                                       _int, _vp, _vp, _vp, _vp, _vp, _sz, _c.c_float, _vp]),
     "pcl_gd_weight_sets_workspace_bytes": (_sz, [_i64, _int, _int, _c.POINTER(GdHyper)]),
     "pcl_gd_plan_weight_sets": (_int, [_i64, _int, _int, _c.POINTER(GdHyper), _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)]),
     "pcl_gd_init_weight_sets": (_int, [_vp, _vp, _vp, _int, _int, _c.POINTER(GdHyper), _vp]),

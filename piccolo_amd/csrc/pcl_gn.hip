@@ -4,7 +4,8 @@
 // What is minimised: the MEAN SQUARED residual sigma^2(theta) = sum w m l^2 / sum w m over theta = (t0, t1, t2, yaw, pitch, roll), with the
 // Gauss-Newton model H = sum w m j j^T, b = sum w m l j of pcl_info.hip.  This is NOT the sampling loss sum w m l / sum w m that the GD chains
 // minimise: the two share their per-point terms, mask and weights and are different objectives.  The mask m is treated as constant
-// inside a step (it is re-evaluated at every trial pose).  Nothing is claimed about real data.
+// inside a step (it is re-evaluated at every trial pose).  Nothing is claimed about real data.  The Huber-L1 form at the end of this file
+// (pcl_gn_refine_l1, pcl_gn_refine_images_l1) runs the same chain on an objective that tends to the sampling loss itself.
 //
 // One call enqueues 1 + 2 (iters + 1) launches and nothing else; every decision is taken on the device:
 //   pcl_gn_init_kernel        theta_try = theta_acc = the caller's pose, F_acc = +inf, lambda = lam0, counters 0; the trace is zeroed
@@ -71,6 +72,27 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_pass_images_kernel(PclInfoAr
     const unsigned g = b + (unsigned)im.img0;
     pcl_info_pass<FMT, WT, CS>(a, (const void*)im.panos.p[b], im.sets, g, im.wsets, im.wsets > 1 ? (int)g * ((int)a.pass.stride * 4) : 0,
                                chunk * (unsigned)im.btot + g);
+}
+
+// The Huber-L1 instances of the two gated passes (pcl_gn_refine_l1, pcl_gn_refine_images_l1): the same gate, blocks and rows, with the pass's L1
+// flag and its two floats by value in the kernel arguments.  Templates of their own beside their twins, as in pcl_info.hip.
+template <int FMT, bool WT, bool L1>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_pass_kernel(PclInfoArgs a, const PclGnState* __restrict__ state, PclInfoL1 l1)
+{
+    static_assert(L1, "the plain instance is pcl_gn_pass_kernel<FMT, WT>");
+    if (state[blockIdx.x % (unsigned)a.pass.B].frozen) return;      // (a scalar load: the address depends on the block alone)
+    pcl_info_pass<FMT, WT, false, L1>(a, a.pass.pano, 1, 0, 1, 0, blockIdx.x, l1.inv_delta, l1.half_delta);
+}
+
+template <int FMT, bool WT, bool CS, bool L1>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_gn_pass_images_kernel(PclInfoArgs a, PclInfoImages im, const PclGnState* __restrict__ state, PclInfoL1 l1)
+{
+    static_assert(L1, "the plain instance is pcl_gn_pass_images_kernel<FMT, WT, CS>");
+    const unsigned b = blockIdx.x % (unsigned)a.pass.B, chunk = blockIdx.x / (unsigned)a.pass.B;      // (from the block index: uniform)
+    if (state[b].frozen) return;
+    const unsigned g = b + (unsigned)im.img0;
+    pcl_info_pass<FMT, WT, CS, L1>(a, (const void*)im.panos.p[b], im.sets, g, im.wsets, im.wsets > 1 ? (int)g * ((int)a.pass.stride * 4) : 0,
+                                   chunk * (unsigned)im.btot + g, l1.inv_delta, l1.half_delta);
 }
 
 // The step's body is ONE text, pcl_gn_step_body.h, which pcl_gn_step_rooms_kernel of pcl_gn_rooms.hip includes as well, over a room's
@@ -160,5 +182,76 @@ extern "C" int pcl_gn_refine_images(const float* cloud, const float* weights, in
         [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
             hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)nimages), blk, 0, s, partials, (int)nchunks, nimages, st, hp, k, iters, out, info, cov,
                                trace);
+        });
+}
+
+// ---- the Huber-L1 form: the same chain on F_rho = sum w m rho(l) / sum w m, rho Huber's function divided by delta,
+// with H_rho = sum w m phi j j^T and b_rho = sum w m phi l j, phi = min(1 / l, 1 / delta).  For delta -> 0 F_rho tends to the sampling loss
+// and b_rho / M to its gradient; for delta >= max l it is the chain above up to the factor 1 / delta.  Only the pass differs: its L1
+// instance puts sum w m rho where S2 goes, and the init, step and finish kernels, the state and pcl_gn_chain run as they are — the step
+// accepts on (float)(s[27] / M), which is F_rho, and solves on the accepted H_rho, b_rho.  M and S1 of the record stay plain.  The `out`
+// and trace columns that hold sigma^2 hold F_rho.  No covariance: the step kernel gets a null cov.  Sizes and launch counts are the twins'.
+extern "C" int pcl_gn_refine_l1(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
+                                const float* rot, int pose_stride, int B, const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info,
+                                float* trace, void* workspace, size_t workspace_bytes, float delta, void* stream)
+{
+    PclInfoL1 l1;
+    if (!pcl_gn_entry_ok(hyper_host, iters, state, out, info, workspace) || !pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
+    PclInfoArgs a;
+    int64_t nchunks;
+    const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
+    if (rc) return rc;
+    if (workspace_bytes < pcl_info_workspace_bytes(n, B)) return PCL_EINVAL;
+    a.weights = weights;
+    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    return pcl_gn_chain(
+        a, B, hyper_host, iters, state, trace, workspace, s,
+        [&](const PclInfoArgs& ak, const PclGnState* st) {
+            pcl_with_flag(weights != nullptr, [&](auto wt) {
+                pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+                    hipLaunchKernelGGL((pcl_gn_pass_kernel<decltype(fmt)::value, decltype(wt)::value, true>), grid, blk, 0, s, ak, st, l1);
+                });
+            });
+        },
+        [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
+            hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)B), blk, 0, s, partials, (int)nchunks, B, st, hp, k, iters, out, info, (float*)nullptr,
+                               trace);
+        });
+}
+
+extern "C" int pcl_gn_refine_images_l1(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets, const uint64_t* panos_host,
+                                       int nimages, int pano_format, int H, int W, const float* trans, const float* rot, int pose_stride,
+                                       const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info, float* trace, void* workspace,
+                                       size_t workspace_bytes, float delta, void* stream)
+{
+    PclInfoL1 l1;
+    if (!pcl_gn_entry_ok(hyper_host, iters, state, out, info, workspace) || !pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
+    PclInfoArgs a;
+    PclInfoImages im;
+    int64_t nchunks;
+    const int rc = pcl_info_images_args(&a, &im, cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot,
+                                        pose_stride, &nchunks);
+    if (rc) return rc;
+    if (workspace_bytes < pcl_info_workspace_bytes(n, nimages)) return PCL_EINVAL;
+    const dim3 blk(PCL_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    return pcl_gn_chain(
+        a, nimages, hyper_host, iters, state, trace, workspace, s,
+        [&](const PclInfoArgs& ak, const PclGnState* st) {
+            pcl_info_images_launches(ak, im, panos_host, nchunks, [&](const PclInfoArgs& al, const PclInfoImages& il, int i0, dim3 grid) {
+                pcl_with_flag(weights != nullptr, [&](auto wt) {
+                    pcl_with_flag(color_sets > 1, [&](auto cs) {
+                        pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+                            hipLaunchKernelGGL((pcl_gn_pass_images_kernel<decltype(fmt)::value, decltype(wt)::value, decltype(cs)::value, true>), grid,
+                                               blk, 0, s, al, il, st + i0, l1);
+                        });
+                    });
+                });
+            });
+        },
+        [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
+            hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)nimages), blk, 0, s, partials, (int)nchunks, nimages, st, hp, k, iters, out, info,
+                               (float*)nullptr, trace);
         });
 }

@@ -18,6 +18,8 @@
 // partial row of 32 floats per (chunk, pose).  No atomics, no scratch; the grid is chunks x poses with the pose varying fastest.
 // pcl_pose_info_finish_kernel: one block per pose adds the chunks' rows in double in a fixed order, forms H = C A C^T and b = C v in
 // double, factorises (Cholesky), inverts, and rounds every output once to fp32.  Same inputs, same bits.
+// The L1 instances of the pass (pcl_pose_information_l1, pcl_pose_information_images_l1) put the IRLS weight
+// phi = min(1 / l, 1 / delta) on the 21 + 6 moment sums and sum w m rho(l) where S2 goes; M and S1 stay plain and the finish is unchanged.
 #include <math.h>
 
 #include "pcl_info_device.h"
@@ -41,6 +43,26 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_images_kernel(PclInfo
     const unsigned g = b + (unsigned)im.img0;
     pcl_info_pass<FMT, WT, CS>(a, (const void*)im.panos.p[b], im.sets, g, im.wsets, im.wsets > 1 ? (int)g * ((int)a.pass.stride * 4) : 0,
                                chunk * (unsigned)im.btot + g);
+}
+
+// The Huber-L1 instances of the two kernels above (pcl_pose_information_l1, pcl_pose_information_images_l1): the same blocks, chunking, partial
+// rows and reduction order, with the pass's L1 flag (pcl_info_device.h) and its two wave-uniform floats by value in the kernel arguments.
+// They are templates of their own beside their twins, so that every instance that existed before them keeps its name and its text.
+template <int FMT, bool WT, bool L1>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_kernel(PclInfoArgs a, PclInfoL1 l1)
+{
+    static_assert(L1, "the plain instance is pcl_pose_info_kernel<FMT, WT>");
+    pcl_info_pass<FMT, WT, false, L1>(a, a.pass.pano, 1, 0, 1, 0, blockIdx.x, l1.inv_delta, l1.half_delta);
+}
+
+template <int FMT, bool WT, bool CS, bool L1>
+__global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_images_kernel(PclInfoArgs a, PclInfoImages im, PclInfoL1 l1)
+{
+    static_assert(L1, "the plain instance is pcl_pose_info_images_kernel<FMT, WT, CS>");
+    const unsigned b = blockIdx.x % (unsigned)a.pass.B, chunk = blockIdx.x / (unsigned)a.pass.B;      // (from the block index: uniform)
+    const unsigned g = b + (unsigned)im.img0;
+    pcl_info_pass<FMT, WT, CS, L1>(a, (const void*)im.panos.p[b], im.sets, g, im.wsets, im.wsets > 1 ? (int)g * ((int)a.pass.stride * 4) : 0,
+                                   chunk * (unsigned)im.btot + g, l1.inv_delta, l1.half_delta);
 }
 
 // Pose (r, i) against room r's cloud and panorama i (pcl_pose_information_rooms): the block finds its room, chunk and image from its index
@@ -103,6 +125,34 @@ extern "C" int pcl_pose_information(const float* cloud, const float* weights, in
     return 0;
 }
 
+// pcl_pose_information under the Huber-L1 objective of pcl_gn_refine_l1: the record holds H_rho, b_rho, M, S1 (both plain), sum w m rho and
+// F_rho = sum w m rho / M in the slots of H, b, M, S1, S2 and sigma^2.  No covariance: F_rho H_rho^-1 is not one.
+extern "C" int pcl_pose_information_l1(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W,
+                                       const float* trans, const float* rot, int pose_stride, int B, float* info, void* workspace,
+                                       size_t workspace_bytes, float delta, void* stream)
+{
+    PclInfoL1 l1;
+    if (!info || !workspace || !pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
+    PclInfoArgs a;
+    int64_t nchunks;
+    const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
+    if (rc) return rc;
+    if (workspace_bytes < pcl_info_workspace_bytes(n, B)) return PCL_EINVAL;
+    a.weights = weights; a.partials = (float*)workspace;
+    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    pcl_with_flag(weights != nullptr, [&](auto wt) {
+        pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+            hipLaunchKernelGGL((pcl_pose_info_kernel<decltype(fmt)::value, decltype(wt)::value, true>), grid, blk, 0, s, a, l1);
+        });
+    });
+    PCL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, B, trans, rot,
+                       pose_stride, info, (float*)nullptr);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
 // Record i = pcl_pose_information of pose i against panos_host[i], colour set i and weight plane i: one pass launch per PCL_RES_MAX_IMAGES
 // images into the call's [nchunks][nimages] partial rows (the chunking depends on n alone), then pcl_pose_info_finish_kernel over all of them.
 extern "C" int pcl_pose_information_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets,
@@ -132,6 +182,39 @@ extern "C" int pcl_pose_information_images(const float* cloud, const float* weig
     PCL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)nimages), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, nimages,
                        trans, rot, pose_stride, info, cov);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pcl_pose_information_images_l1(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets,
+                                              const uint64_t* panos_host, int nimages, int pano_format, int H, int W, const float* trans,
+                                              const float* rot, int pose_stride, float* info, void* workspace, size_t workspace_bytes, float delta,
+                                              void* stream)
+{
+    PclInfoL1 l1;
+    if (!info || !workspace || !pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
+    PclInfoArgs a;
+    PclInfoImages im;
+    int64_t nchunks;
+    const int rc = pcl_info_images_args(&a, &im, cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot,
+                                        pose_stride, &nchunks);
+    if (rc) return rc;
+    if (workspace_bytes < pcl_info_workspace_bytes(n, nimages)) return PCL_EINVAL;
+    a.partials = (float*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    pcl_info_images_launches(a, im, panos_host, nchunks, [&](const PclInfoArgs& al, const PclInfoImages& il, int, dim3 grid) {
+        pcl_with_flag(weights != nullptr, [&](auto wt) {
+            pcl_with_flag(color_sets > 1, [&](auto cs) {
+                pcl_with_pass_fmt(pano_format, [&](auto fmt) {
+                    hipLaunchKernelGGL((pcl_pose_info_images_kernel<decltype(fmt)::value, decltype(wt)::value, decltype(cs)::value, true>), grid,
+                                       dim3(PCL_BLOCK), 0, s, al, il, l1);
+                });
+            });
+        });
+    });
+    PCL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)nimages), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, nimages,
+                       trans, rot, pose_stride, info, (float*)nullptr);
     PCL_LAUNCH_CHECK();
     return 0;
 }

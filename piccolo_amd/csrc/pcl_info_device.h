@@ -40,9 +40,15 @@ struct PclInfoImages {
 // are those of the pass before it took these arguments.
 // pcl_info_pass_at is that pass for block (chunk, pose b) over the cloud `c` into row `row` of `partials`: what a block of a rooms launch
 // passes from its room's record, and what pcl_info_pass passes from the call's own struct and block index.
-template <int FMT, bool WT, bool CS = false>
+// With L1 (the Huber-L1 form of the polish, pcl_gn.hip) a pair's factor on the 21 + 6 moment sums is w phi(l), phi = min(1 / l, 1 / delta)
+// (v_rcp_f32; l = 0: 1 / delta, and a masked point's a = 0 anyway), slot 27 takes sum w rho(l), rho = l >= delta ? l - delta / 2 :
+// l^2 / (2 delta), in place of S2, and S1 and M keep the plain w.  inv_delta = 1 / delta and half_delta = delta / 2 are formed on the host
+// and travel by value in the kernel arguments (wave-uniform: SGPRs); delta itself is half_delta + half_delta, exactly.  Without L1 the two
+// are not read and the instruction stream is the one it was before the flag.
+template <int FMT, bool WT, bool CS = false, bool L1 = false>
 __device__ __forceinline__ void pcl_info_pass_at(const PclInfoArgs& a, const PclPassCloud& c, unsigned b, unsigned chunk, const void* pano_b, int sets,
-                                                 unsigned set, int wsets, int wplane, float* partials, unsigned row)
+                                                 unsigned set, int wsets, int wplane, float* partials, unsigned row, float inv_delta = 0.f,
+                                                 float half_delta = 0.f)
 {
     __amdgpu_buffer_rsrc_t wrs;
     if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(c.stride * 4) * wsets, 0x00020000);
@@ -61,8 +67,16 @@ __device__ __forceinline__ void pcl_info_pass_at(const PclInfoArgs& a, const Pcl
             w = (f2){valid0 ? w.x : 0.f, valid1 ? w.y : 0.f};
             wl = w * acc[0]; wm = w * acc[1];
         }
+        if constexpr (L1) {
+            // the IRLS weight of the pair: the saturated branch is the host's 1 / delta itself
+            const f2 phi = (f2){fminf(__builtin_amdgcn_rcpf(acc[0].x), inv_delta), fminf(__builtin_amdgcn_rcpf(acc[0].y), inv_delta)};
+            const f2 wp = WT ? w * phi : phi;
 #pragma unroll
-        for (int k = 0; k < 6; k++) wa[k] = WT ? w * acc[2 + k] : acc[2 + k];
+            for (int k = 0; k < 6; k++) wa[k] = wp * acc[2 + k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 6; k++) wa[k] = WT ? w * acc[2 + k] : acc[2 + k];
+        }
         int q = 0;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -71,7 +85,15 @@ __device__ __forceinline__ void pcl_info_pass_at(const PclInfoArgs& a, const Pcl
         }
 #pragma unroll
         for (int k = 0; k < 6; k++) bb[k] = pcl_fma2(wa[k], acc[0], bb[k]);
-        s2 = pcl_fma2(wl, acc[0], s2);
+        if constexpr (L1) {
+            const float delta = half_delta + half_delta, hi = 0.5f * inv_delta;
+            const f2 l = acc[0];
+            const f2 rho = (f2){l.x >= delta ? l.x - half_delta : l.x * l.x * hi, l.y >= delta ? l.y - half_delta : l.y * l.y * hi};
+            if constexpr (WT) s2 = pcl_fma2(w, rho, s2);
+            else s2 += rho;
+        } else {
+            s2 = pcl_fma2(wl, acc[0], s2);
+        }
         s1 += wl;
         mm += wm;
     });
@@ -96,11 +118,25 @@ __device__ __forceinline__ void pcl_info_pass_at(const PclInfoArgs& a, const Pcl
     }
 }
 
-template <int FMT, bool WT, bool CS = false>
-__device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a, const void* pano_b, int sets, unsigned set, int wsets, int wplane, unsigned row)
+template <int FMT, bool WT, bool CS = false, bool L1 = false>
+__device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a, const void* pano_b, int sets, unsigned set, int wsets, int wplane, unsigned row,
+                                              float inv_delta = 0.f, float half_delta = 0.f)
 {
-    pcl_info_pass_at<FMT, WT, CS>(a, PclPassCloud{a.pass.cloud, a.pass.n, a.pass.stride, a.pass.steps_base, a.pass.steps_rem},
-                                  blockIdx.x % (unsigned)a.pass.B, blockIdx.x / (unsigned)a.pass.B, pano_b, sets, set, wsets, wplane, a.partials, row);
+    pcl_info_pass_at<FMT, WT, CS, L1>(a, PclPassCloud{a.pass.cloud, a.pass.n, a.pass.stride, a.pass.steps_base, a.pass.steps_rem},
+                                      blockIdx.x % (unsigned)a.pass.B, blockIdx.x / (unsigned)a.pass.B, pano_b, sets, set, wsets, wplane, a.partials, row,
+                                      inv_delta, half_delta);
+}
+
+// ---- host side of the L1 entry points: delta is refused unless it is finite and inside [2^-20, 4] as a float (residuals never exceed
+// sqrt(3); the range keeps 1 / delta and what it scales well inside fp32)
+struct PclInfoL1 {
+    float inv_delta, half_delta;
+};
+static inline bool pcl_info_l1_args(float delta, PclInfoL1* l1)
+{
+    if (!(delta >= 9.5367431640625e-07f && delta <= 4.f)) return false;      // (a NaN fails both)
+    l1->inv_delta = 1.f / delta; l1->half_delta = 0.5f * delta;
+    return true;
 }
 
 // ---- the rooms instances (pcl_pose_information_rooms, pcl_gn_refine_rooms): pose (r, i) = row r * btot + i against room r's cloud,

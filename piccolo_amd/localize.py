@@ -24,7 +24,7 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import (GN_KEYS, ROBUST_KEYS, _is_int, _refuse, gn_schedule, omniloc_all, omniloc_batch, omniloc_batch_images,
+from .omniloc import (GN_KEYS, ROBUST_KEYS, _is_int, _refuse, _refuse_l1, gn_schedule, omniloc_all, omniloc_batch, omniloc_batch_images,
                       omniloc_batch_images_polished, omniloc_batch_images_robust, omniloc_batch_rooms_images,
                       omniloc_batch_rooms_images_polished, pose_covariance_flag, robust_schedule)
 from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
@@ -52,8 +52,8 @@ def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=No
     branch returns every candidate and refuses the keys (ValueError), as omniloc_all does.  cfg.robust_iters / robust_kind / robust_k
     (omniloc.robust_schedule): the parallel branch runs omniloc_batch's robust chain; the non-parallel branch refuses them as well.
     cfg.pose_covariance (omniloc.pose_covariance_flag): the parallel branch returns (t, R, loss, cov), cov the (6, 6) covariance of
-    (t, yaw, pitch, roll) at the returned pose; the non-parallel branch refuses the key.  cfg.gn_iters / gn_step_cap / gn_lambda
-    (omniloc.gn_schedule): the parallel branch passes them on to omniloc_batch, which polishes its winner; the non-parallel branch refuses
+    (t, yaw, pitch, roll) at the returned pose; the non-parallel branch refuses the key.  cfg.gn_iters / gn_step_cap / gn_lambda /
+    gn_objective / gn_delta (omniloc.gn_schedule): the parallel branch passes them on to omniloc_batch, which polishes its winner; the non-parallel branch refuses
     them."""
     summaries = scalar_summaries if scalar_summaries is not None else {}
     if getattr(cfg, "parallel", False):
@@ -136,7 +136,7 @@ def _check_room_polish_cfg(cfg):
         raise ValueError("cfg.room_search_polish needs cfg.parallel (the polished chain has parallel semantics only)")
     if all(getattr(cfg, key, None) is None for key in GN_KEYS) and not getattr(cfg, "pose_covariance", None):
         raise ValueError("cfg.room_search_polish goes with cfg.gn_iters and / or cfg.pose_covariance (room_search alone runs the plain search)")
-    gn_schedule(cfg)                                  # (their own ValueErrors, before any file is read)
+    _refuse_l1(gn_schedule(cfg), "cfg.room_search_polish")      # (the schedule's own ValueErrors, before any file is read)
     pose_covariance_flag(cfg)
     return True
 

@@ -30,7 +30,8 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
   * extra, optional cfg keys gn_iters / gn_step_cap / gn_lambda (default absent = reference behaviour): omniloc_batch polishes its winner
     by a Levenberg-Marquardt chain on the device (gn_schedule, csrc/pcl_gn.hip); omniloc_batch_images_polished does that, and / or the
     covariance, for all query images of a shared chain at once (pose_information_images / gauss_newton_refine_images give the several-image
-    calls to a caller);
+    calls to a caller); cfg gn_objective = "l1" (with gn_delta; default "l2") polishes on the Huber-L1 objective instead, which tends to
+    the sampling loss itself as delta -> 0 (the rooms forms refuse it);
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
     per iteration) as 4th element.
@@ -234,7 +235,7 @@ def _cfg(cfg, key, default):
 # The cfg keys that are not the reference's, by family: (its keys, how a refusal names them — None: the first key it finds, what does take
 # them).  An entry point refuses the families it does not take with one _refuse call; the schedules below validate the ones it does.
 ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
-GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda")
+GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda", "gn_objective", "gn_delta")
 _EXTENSIONS = {
     "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
     "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust, omniloc_batch_images_polished and localize.refine_image's parallel "
@@ -448,15 +449,31 @@ def pose_covariance_flag(cfg):
 # chains minimise: same per-point terms, mask and weights, another objective.  cfg gn_iters (an int >= 1, absent by default), gn_step_cap
 # and gn_lambda (optional: the step cap in metres / radians and the starting damping): omniloc_batch polishes its winner.  One cloud, one
 # colour set, one image, no depth mask; nothing is claimed about real data.
+# cfg gn_objective ("l2", the default, or "l1") and gn_delta (with "l1" only; ops.GN_L1_DELTA = 1 / 64 when absent): "l1" polishes on the
+# Huber-L1 objective sum w m rho(l) / sum w m, which tends to the sampling loss itself as delta -> 0, re-weighting
+# inside the chain.  Off by default.  The rooms forms refuse "l1".
 def gn_schedule(cfg):
-    """(iters, hyper dict for ops.gauss_newton_refine) under cfg.gn_iters / gn_step_cap / gn_lambda, or None when the keys are absent.
-    ValueError: gn_step_cap / gn_lambda without gn_iters, gn_iters not an int in 1 .. 1000, a cap or damping that is not a positive finite
-    number, cfg.depth_mask next to them.  Host only."""
-    iters, cap, lam = (_cfg(cfg, key, None) for key in GN_KEYS)
-    if iters is None and cap is None and lam is None:
+    """(iters, keyword dict for ops.gauss_newton_refine) under cfg.gn_iters / gn_step_cap / gn_lambda / gn_objective / gn_delta, or None when
+    the keys are absent.  Without gn_objective, or with "l2", the dict holds hyper-parameters alone, as before the key; with "l1" it gains
+    objective="l1" (and delta= when cfg.gn_delta is given).
+    ValueError: gn_step_cap / gn_lambda / gn_objective / gn_delta without gn_iters, gn_iters not an int in 1 .. 1000, a cap or damping that
+    is not a positive finite number, a gn_objective that is neither "l2" nor "l1", gn_delta without gn_objective = "l1", a gn_delta that is
+    not a positive finite number inside [2^-20, 4], cfg.depth_mask next to them.  Host only."""
+    iters, cap, lam, objective, delta = (_cfg(cfg, key, None) for key in GN_KEYS)
+    if iters is None and cap is None and lam is None and objective is None and delta is None:
         return None
+    if objective is not None and (not isinstance(objective, str) or objective not in ops.GN_OBJECTIVES):
+        raise ValueError("cfg.gn_objective %r: one of %s" % (objective, list(ops.GN_OBJECTIVES)))
     if iters is None:
-        raise ValueError("cfg.%s goes with cfg.gn_iters" % ("gn_step_cap" if cap is not None else "gn_lambda"))
+        raise ValueError("cfg.%s goes with cfg.gn_iters" % next(key for key, v in zip(GN_KEYS[1:], (cap, lam, objective, delta)) if v is not None))
+    if delta is not None:
+        if objective != "l1":
+            raise ValueError('cfg.gn_delta goes with cfg.gn_objective = "l1"')
+        delta = _positive(delta, "gn_delta")
+        try:
+            ops.gn_objective("cfg.gn_delta", "l1", delta)
+        except ValueError as e:
+            raise ValueError("cfg.gn_delta: %s" % e) from None
     if not _is_int(iters) or not 1 <= iters <= ops.GN_MAX_ITERS:
         raise ValueError("cfg.gn_iters %r: an int in 1 .. %d" % (iters, ops.GN_MAX_ITERS))
     hyper = {}
@@ -469,22 +486,39 @@ def gn_schedule(cfg):
         raise ValueError("cfg.gn_step_cap / cfg.gn_lambda: %s" % e) from None
     if bool(_cfg(cfg, "depth_mask", False)):
         raise ValueError("cfg.gn_iters does not combine with cfg.depth_mask")
+    if objective == "l1":
+        hyper["objective"] = "l1"
+        if delta is not None:
+            hyper["delta"] = delta
     return iters, hyper
 
 
-def gauss_newton_refine(img, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, **hyper):
+def _gn_is_l1(gn):
+    return gn is not None and gn[1].get("objective") == "l1"
+
+
+def _refuse_l1(gn, who):
+    """the rooms forms have no L1 twin"""
+    if _gn_is_l1(gn):
+        raise ValueError('%s does not take cfg.gn_objective = "l1" (the rooms polish has no L1 form; omniloc_batch and '
+                         'omniloc_batch_images_polished do)' % who)
+
+
+def gauss_newton_refine(img, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, objective="l2", delta=None, **hyper):
     """ops.gauss_newton_refine from the poses trans / rot ((B, 3) tensors: translation; yaw, pitch, roll) over the cached packed cloud and
     panorama: a dict of GPU tensors (trans, rot, sigma2_start, sigma2, lam, accepted, rejected, evaluations, status, H, b, stats, cov, and
-    trace when asked).  weights: (N,) per-point weights in the order of xyz's rows."""
+    trace when asked).  weights: (N,) per-point weights in the order of xyz's rows.  objective="l1" / delta: the Huber-L1 objective
+    (ops.gauss_newton_refine: sigma2* hold F_rho, stats = (M, S1, sum w m rho, F_rho, status), cov None)."""
     return ops.gauss_newton_refine(packed_cloud(xyz, rgb, weights), packed_pano(img, n_points=xyz.shape[0]), trans, rot, iters=iters, trace=trace,
-                                   **hyper)
+                                   objective=objective, delta=delta, **hyper)
 
 
-def pose_information(img, xyz, rgb, trans, rot, weights=None):
+def pose_information(img, xyz, rgb, trans, rot, weights=None, objective="l2", delta=None):
     """(H (B,6,6), b (B,6), stats (B,5) = M, S1, S2, sigma^2, status, cov (B,6,6)) on the GPU at the poses trans / rot ((B, 3) tensors:
     translation; yaw, pitch, roll), over the cached packed cloud and panorama (ops.pose_information).  weights: (N,) per-point weights in
-    the order of xyz's rows."""
-    return ops.pose_information(packed_cloud(xyz, rgb, weights), packed_pano(img, n_points=xyz.shape[0]), trans, rot)
+    the order of xyz's rows.  objective="l1" / delta: the Huber-L1 record (ops.pose_information: H_rho, b_rho, stats = (M, S1, sum w m rho,
+    F_rho, status), cov None)."""
+    return ops.pose_information(packed_cloud(xyz, rgb, weights), packed_pano(img, n_points=xyz.shape[0]), trans, rot, objective=objective, delta=delta)
 
 
 def pose_covariance(img, xyz, rgb, trans, rot, weights=None):
@@ -509,19 +543,20 @@ def _images_cloud(who, imgs, xyz, rgb, weights):
     return cloud, _chain_panos(list(imgs), xyz.shape[0])
 
 
-def pose_information_images(imgs, xyz, rgb, trans, rot, weights=None):
+def pose_information_images(imgs, xyz, rgb, trans, rot, weights=None, objective="l2", delta=None):
     """pose_information for several query images of one cloud in one set of launches (ops.pose_information_images): row i of (H, b, stats,
     cov) is pose (trans[i], rot[i]) against imgs[i] — and rgb[i], when rgb is a list of one colour tensor per image.  weights: (N,) per-point
-    weights in the order of xyz's rows, shared by the images (one colour tensor only)."""
+    weights in the order of xyz's rows, shared by the images (one colour tensor only).  objective / delta: as pose_information."""
     cloud, panos = _images_cloud("pose_information_images", imgs, xyz, rgb, weights)
-    return ops.pose_information_images(cloud, panos, trans, rot)
+    return ops.pose_information_images(cloud, panos, trans, rot, objective=objective, delta=delta)
 
 
-def gauss_newton_refine_images(imgs, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, **hyper):
+def gauss_newton_refine_images(imgs, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, objective="l2", delta=None, **hyper):
     """gauss_newton_refine for several query images of one cloud in ONE chain (ops.gauss_newton_refine_images): pose i is polished against
-    imgs[i] — and rgb[i], when rgb is a list of one colour tensor per image.  Row i of every entry equals the single-image call's."""
+    imgs[i] — and rgb[i], when rgb is a list of one colour tensor per image.  Row i of every entry equals the single-image call's.
+    objective / delta: as gauss_newton_refine."""
     cloud, panos = _images_cloud("gauss_newton_refine_images", imgs, xyz, rgb, weights)
-    return ops.gauss_newton_refine_images(cloud, panos, trans, rot, iters=iters, trace=trace, **hyper)
+    return ops.gauss_newton_refine_images(cloud, panos, trans, rot, iters=iters, trace=trace, objective=objective, delta=delta, **hyper)
 
 
 POLISHED_ROW = 52      # floats per image a polished chain copies to the host: t (3), R (9), loss, took, S1, M, cov (36)
@@ -539,11 +574,13 @@ def _winners_polished(gd, cloud, panos, wins, gn, want_cov):
     if planes is not None:
         planes = planes.view(I, -1) if engine.weight_sets else None          # (a plain chain's cloud plane is the cloud's own)
     return _polished_rows(wins, gn, want_cov, lambda: ops.pose_information_images_at_winners(cloud, panos, wins, planes=planes),
-                          lambda: ops.gauss_newton_refine_images_at_winners(cloud, panos, wins, iters=gn[0], planes=planes, **gn[1]))
+                          lambda: ops.gauss_newton_refine_images_at_winners(cloud, panos, wins, iters=gn[0], planes=planes, **gn[1]),
+                          lambda trans, rot: ops.pose_information_images(cloud, panos, trans, rot, planes=planes))
 
 
-def _polished_rows(wins, gn, want_cov, information, polish):
-    """The (I, POLISHED_ROW) rows of _winners_polished from information() (gn None) or polish(): the images or the rooms form at `wins`"""
+def _polished_rows(wins, gn, want_cov, information, polish, information_at=None):
+    """The (I, POLISHED_ROW) rows of _winners_polished from information() (gn None) or polish(): the images or the rooms form at `wins`.
+    An L1 polish has no cov of its own: information_at(trans, rot), one plain pass at the RETURNED poses, gives it."""
     I = int(wins.shape[0])
     zero = torch.zeros(I, 3, dtype=torch.float32, device=wins.device)
     if gn is None:
@@ -553,7 +590,10 @@ def _polished_rows(wins, gn, want_cov, information, polish):
     R = ops.rot_from_ypr(res["rot"]).reshape(I, 9)
     took = ((res["accepted"] > 1) & ((res["status"] == 0) | (res["status"] == 3))).reshape(I, 1)
     rows = torch.where(took, torch.cat([res["trans"], R, zero[:, 0:1]], dim=1), wins[:, 0:13])
-    cov = res["cov"].reshape(I, 36) if want_cov else torch.zeros(I, 36, dtype=torch.float32, device=wins.device)
+    if want_cov and res["cov"] is None:
+        cov = information_at(torch.where(took, res["trans"], wins[:, 0:3]), torch.where(took, res["rot"], wins[:, 13:16]))[3].reshape(I, 36)
+    else:
+        cov = res["cov"].reshape(I, 36) if want_cov else torch.zeros(I, 36, dtype=torch.float32, device=wins.device)
     return torch.cat([rows, took.to(torch.float32), res["stats"][:, 1:2], res["stats"][:, 0:1], cov], dim=1)
 
 
@@ -572,16 +612,20 @@ def _winner_covariance(gd, cloud, pano, win):
     return ops.pose_information_at_winners(_winner_cloud(gd, cloud), pano, win)[3]
 
 
-def _winner_polish(gd, cloud, pano, win, gn):
+def _winner_polish(gd, cloud, pano, win, gn, want_cov=False):
     """The (1, 16) winners row `win` polished on the device under the chain's weights -> (row (13,) GPU: t, R, loss where the polish took a
     step — accepted > 1 and status 0 or 3; R is rot_from_ypr of the polished angles, loss the sampling loss re-evaluated there by one
-    forward-only launch — else the chain's own three entries bit for bit; cov (1,6,6) GPU: the polish's own, at the returned pose)"""
+    forward-only launch — else the chain's own three entries bit for bit; cov (1,6,6) GPU: the polish's own, at the returned pose — an
+    L1 polish has none: with want_cov one plain pose_information pass at the returned pose gives it, else None)"""
     cloud = _winner_cloud(gd, cloud)
     res = ops.gauss_newton_refine_at_winners(cloud, pano, win, iters=gn[0], **gn[1])
     R = ops.rot_from_ypr(res["rot"]).reshape(1, 9)
     loss = ops.sampling_loss(cloud, pano, res["trans"], res["rot"], with_grad=False)[:, 0:1]
-    took = (res["accepted"] > 1) & ((res["status"] == 0) | (res["status"] == 3))
-    return torch.where(took.reshape(1, 1), torch.cat([res["trans"], R, loss], dim=1), win[:, 0:13])[0], res["cov"]
+    took = ((res["accepted"] > 1) & ((res["status"] == 0) | (res["status"] == 3))).reshape(1, 1)
+    cov = res["cov"]
+    if cov is None and want_cov:
+        cov = ops.pose_information(cloud, pano, torch.where(took, res["trans"], win[:, 0:3]), torch.where(took, res["rot"], win[:, 13:16]))[3]
+    return torch.where(took, torch.cat([res["trans"], R, loss], dim=1), win[:, 0:13])[0], cov
 
 
 class _PrunedChain:
@@ -869,7 +913,10 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     robust chain's last plane.  Where the polish accepted a step (accepted > 1, status 0 or 3) t is the polished translation, R
     rot_from_ypr of the polished angles and loss the sampling loss re-evaluated at that pose; otherwise the three entries are the
     chain's own, bit for bit.  With cfg.pose_covariance the fourth entry is the polish's own cov at its returned pose.  The written-back
-    leaves stay the chain's.  With the prune keys too; not with cfg.depth_mask or a list of colour sets (ValueError)."""
+    leaves stay the chain's.  With the prune keys too; not with cfg.depth_mask or a list of colour sets (ValueError).
+    cfg.gn_objective = "l1" (and cfg.gn_delta; gn_schedule): the polish minimises the Huber-L1 objective sum w m rho(l) / sum w m instead —
+    for small delta the sampling loss itself —, with the same rules for the three entries; the fourth entry is then pose_information's
+    cov at the RETURNED pose, from one plain pass after the polish (omniloc.pose_covariance's bits there)."""
     if robust_schedule(cfg) is not None and weights is not None:          # (and the schedule's own refusals, before a device is touched)
         raise ValueError("cfg.robust_iters does not combine with weights= (the chain makes its own)")
     want_cov = pose_covariance_flag(cfg)
@@ -890,7 +937,7 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     # (the covariance reads the winners row on the device and changes nothing the first three entries are made from)
     if gn is not None:
         # (the polish starts from the winners row on the device; its 13 floats travel with the one D2H copy's worth of the row)
-        row, cov = _winner_polish(gd, packed_cloud(xyz, rgb, weights), pano, win, gn)
+        row, cov = _winner_polish(gd, packed_cloud(xyz, rgb, weights), pano, win, gn, want_cov)
         out = row.cpu()
     else:
         cov = _winner_covariance(gd, packed_cloud(xyz, rgb, weights), pano, win) if want_cov else None
@@ -990,7 +1037,10 @@ def omniloc_batch_images_polished(imgs, xyz, rgb, input_trans_list, input_rot_li
     Parallel semantics only.  ValueError, before a device is touched: a cfg with neither the gn keys nor pose_covariance (omniloc_batch_images
     / omniloc_batch_images_robust run the chains alone), cfg.depth_mask (gn_schedule / pose_covariance_flag), cfg.visualize, lists of
     different lengths, a colour-set count that is not the image count.  One image is omniloc_batch; images beyond the colour-set addressing
-    limit go in further groups."""
+    limit go in further groups.
+    cfg.gn_objective = "l1" (and cfg.gn_delta): ONE L1 chain over all winners (gauss_newton_refine_images_at_winners(objective="l1")); a
+    polished entry's loss stays float32(S1) / float32(M) of the polish's record — S1 and M are plain there, and the sampling loss is now
+    what the polish works on —, and cov comes from one plain pose_information_images call at the returned poses."""
     who = "omniloc_batch_images_polished"
     gn, want_cov = gn_schedule(cfg), pose_covariance_flag(cfg)
     if gn is None and not want_cov:
@@ -1237,6 +1287,7 @@ def omniloc_batch_rooms_images_polished(imgs, rooms, input_trans, input_rot, cfg
     cfg.visualize, ragged lists."""
     who = "omniloc_batch_rooms_images_polished"
     gn, want_cov = gn_schedule(cfg), pose_covariance_flag(cfg)
+    _refuse_l1(gn, who)
     if gn is None and not want_cov:
         raise ValueError("%s needs cfg.gn_iters or cfg.pose_covariance (omniloc_batch_rooms_images runs the chain alone)" % who)
     if bool(_cfg(cfg, "depth_mask", False)):

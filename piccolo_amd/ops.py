@@ -495,6 +495,38 @@ _POSE_FORMS = {
 }
 
 
+# The L1 twins of the single and images forms (pcl_pose_information_l1 ...: no cov, a float delta before the stream; the twin's sizes)
+_POSE_FORMS_L1 = {
+    "single": ("pcl_pose_information_l1", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_l1", "pcl_gn_workspace_bytes"),
+    "images": ("pcl_pose_information_images_l1", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_images_l1", "pcl_gn_workspace_bytes"),
+}
+GN_OBJECTIVES = ("l2", "l1")
+GN_L1_DELTA = 1.0 / 64         # the default delta of objective="l1": about four grey levels, exact in fp32.  A choice, not a derived value.
+GN_L1_DELTA_RANGE = (2.0 ** -20, 4.0)
+
+
+def gn_objective(who, objective="l2", delta=None):
+    """None for objective "l2" (or None), else the float delta of objective "l1" (GN_L1_DELTA when not given).  ValueError: an objective
+    that is neither string, a delta without "l1", a delta that is not a finite number inside GN_L1_DELTA_RANGE as a float32.  Host only."""
+    import math
+    if objective is None:
+        objective = "l2"
+    if not isinstance(objective, str) or objective not in GN_OBJECTIVES:
+        raise ValueError("%s: objective %r: one of %s" % (who, objective, list(GN_OBJECTIVES)))
+    if objective == "l2":
+        if delta is not None:
+            raise ValueError('%s: delta goes with objective="l1"' % who)
+        return None
+    if delta is None:
+        return GN_L1_DELTA
+    if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not math.isfinite(delta):
+        raise ValueError("%s: delta %r is not a finite number" % (who, delta))
+    d = ctypes.c_float(delta).value
+    if not GN_L1_DELTA_RANGE[0] <= d <= GN_L1_DELTA_RANGE[1]:
+        raise ValueError("%s: delta %r outside [2^-20, 4] as a float32" % (who, delta))
+    return float(delta)
+
+
 def _single_form(cloud, pano):
     """A form is what _pose_information and _gauss_newton take as the form-specific part of a call: form(who, trans_ptr, rot_ptr, stride, rows)
     runs the form's own argument checks and -> (key of _POSE_FORMS, the workspace queries' arguments, the pose count B, the arguments the
@@ -506,36 +538,48 @@ def _single_form(cloud, pano):
     return form
 
 
-def _pose_information(who, form, trans_ptr, rot_ptr, stride, rows, dev):
-    """What the six pose_information functions do behind their form's checks -> (H, b, stats, cov)"""
+def _pose_information(who, form, trans_ptr, rot_ptr, stride, rows, dev, objective="l2", delta=None):
+    """What the six pose_information functions do behind their form's checks -> (H, b, stats, cov); objective "l1": the form's L1 twin,
+    cov None"""
     lib = _lib.load()
+    delta = gn_objective(who, objective, delta)
     key, size_args, B, head, what = form(who, trans_ptr, rot_ptr, stride, rows)
-    name, size_name = _POSE_FORMS[key][:2]
+    name, size_name = (_POSE_FORMS if delta is None else _POSE_FORMS_L1)[key][:2]
     nws = getattr(lib, size_name)(*size_args)
     if nws == 0:
         raise ValueError("%s: %s are out of range" % (who, what))
     info = torch.empty(B, 48, dtype=F32, device=dev)
-    cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
     ws = _bytes(nws)
-    _lib.check(getattr(lib, name)(*head, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), name)
+    if delta is None:
+        cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
+        _lib.check(getattr(lib, name)(*head, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), name)
+    else:
+        cov = None
+        _lib.check(getattr(lib, name)(*head, _ptr(info), _ptr(ws), nws, delta, _stream()), name)
     return info[:, :36].reshape(B, 6, 6), info[:, 36:42], info[:, 42:47], cov
 
 
-def pose_information(cloud, pano, trans, rot):
+def pose_information(cloud, pano, trans, rot, objective="l2", delta=None):
     """(H (B,6,6), b (B,6), stats (B,5) = M, S1, S2, sigma^2, status, cov (B,6,6)), float32 on the GPU: the Gauss-Newton information matrix
     H = sum w m j j^T of the pose theta = (t, yaw, pitch, roll) at every pose (trans[b], rot[b]), b = sum w m l j, and cov = sigma^2 H^-1
     with sigma^2 = S2 / M (pcl_pose_information; build-defined, include/piccolo_hip.h; metres and radians).  A weighted cloud contributes
     its weights, one factor per term.  status 0: fine; 1: nothing kept or something not finite (cov NaN); 2: H not positive definite
-    (cov NaN).  ValueError: a cloud of colour sets, a panorama in one of the trim launch's texel layouts."""
+    (cov NaN).  ValueError: a cloud of colour sets, a panorama in one of the trim launch's texel layouts.
+    objective="l1" (pcl_pose_information_l1; delta: GN_L1_DELTA unless given, inside [2^-20, 4]): the Huber-L1 form the L1 polish works on —
+    the tuple keeps its layout, H = sum w m phi j j^T and b = sum w m phi l j with phi = min(1 / l, 1 / delta), stats = (M, S1, sum w m rho,
+    F_rho, status) with M and S1 PLAIN (S1 / M is the weighted sampling loss at the pose), and cov is None.  objective="l2" (or absent):
+    the call above, bit for bit.  ValueError: an objective that is neither, delta without "l1" or outside its range."""
     _residual_cloud(cloud, pano, "pose_information")
     trans, rot = _pose_rows(trans, rot)
-    return _pose_information("pose_information", _single_form(cloud, pano), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
+    return _pose_information("pose_information", _single_form(cloud, pano), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, objective,
+                             delta)
 
 
-def pose_information_at_winners(cloud, pano, winners):
+def pose_information_at_winners(cloud, pano, winners, objective="l2", delta=None):
     """pose_information at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses)."""
     _residual_cloud(cloud, pano, "pose_information_at_winners")
-    return _pose_information("pose_information", _single_form(cloud, pano), *_winner_poses(winners, "pose_information_at_winners"), winners.device)
+    return _pose_information("pose_information", _single_form(cloud, pano), *_winner_poses(winners, "pose_information_at_winners"), winners.device,
+                             objective, delta)
 
 
 GN_HYPER = dict(lam0=1e-3, lam_up=10.0, lam_down=0.1, lam_min=1e-9, lam_max=1e9, step_cap=0.1, tol=0.0)
@@ -561,23 +605,31 @@ def gn_hyper(who="gauss_newton_refine", **hyper):
     return g
 
 
-def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace, hyper):
-    """What the six gauss_newton_refine functions do: iters, the hyper-parameters, the form's checks, the sizes, the call -> the result dict"""
+def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace, hyper, objective="l2", delta=None):
+    """What the six gauss_newton_refine functions do: iters, the hyper-parameters, the form's checks, the sizes, the call -> the result dict;
+    objective "l1": the form's L1 twin, cov None (objective and delta are not hyper-parameters: gn_hyper refuses them)"""
     lib = _lib.load()
     if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= GN_MAX_ITERS:
         raise ValueError("%s: iters %r: an int in 0 .. %d" % (who, iters, GN_MAX_ITERS))
     hp = gn_hyper(who, **hyper)
+    delta = gn_objective(who, objective, delta)
     key, size_args, B, head, what = form(who, trans_ptr, rot_ptr, stride, rows)
-    name, size_name = _POSE_FORMS[key][2:]
+    if delta is not None and key not in _POSE_FORMS_L1:
+        raise ValueError('%s: objective="l1" has no rooms form' % who)
+    name, size_name = (_POSE_FORMS if delta is None else _POSE_FORMS_L1)[key][2:]
     nws, nst = getattr(lib, size_name)(*size_args), lib.pcl_gn_state_bytes(B)
     if nws == 0 or nst == 0:
         raise ValueError("%s: %s are out of range" % (who, what))
     out = torch.empty(B, 16, dtype=F32, device=dev)
     info = torch.empty(B, 48, dtype=F32, device=dev)
-    cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
+    cov = torch.empty(B, 6, 6, dtype=F32, device=dev) if delta is None else None
     tr = torch.empty(iters + 1, B, 16, dtype=F32, device=dev) if trace else None
     ws, st = _bytes(nws), _bytes(nst)
-    _lib.check(getattr(lib, name)(*head, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()), name)
+    if delta is None:
+        _lib.check(getattr(lib, name)(*head, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()),
+                   name)
+    else:
+        _lib.check(getattr(lib, name)(*head, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(tr), _ptr(ws), nws, delta, _stream()), name)
     ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
                evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(B, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
     if trace:
@@ -585,7 +637,7 @@ def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace
     return ret
 
 
-def gauss_newton_refine(cloud, pano, trans, rot, iters=10, trace=False, **hyper):
+def gauss_newton_refine(cloud, pano, trans, rot, iters=10, trace=False, objective="l2", delta=None, **hyper):
     """A Levenberg-Marquardt polish of the poses (trans[b], rot[b]) on the device (pcl_gn_refine; build-defined, include/piccolo_hip.h): it
     minimises the MEAN SQUARED residual sigma^2 = sum w m l^2 / sum w m over theta = (t, yaw, pitch, roll; metres, radians) with the H and b
     of pose_information — NOT the sampling loss sum w m l / sum w m; the two share their per-point terms, mask and weights and are
@@ -595,18 +647,23 @@ def gauss_newton_refine(cloud, pano, trans, rot, iters=10, trace=False, **hyper)
     not positive definite, 3 converged); H, b, stats, cov: pose_information at the returned pose, bit for bit; with trace=True `trace`
     (iters + 1, B, 16): per evaluation theta_try (6), F, accepted, lambda after the decision, M.  hyper: lam0, lam_up, lam_down, lam_min,
     lam_max, step_cap, tol (GN_HYPER).  A weighted cloud contributes its weights.  ValueError: a cloud of colour sets, a panorama in one of
-    the trim launch's texel layouts, iters outside 0 .. 1000, hyper-parameters out of range."""
+    the trim launch's texel layouts, iters outside 0 .. 1000, hyper-parameters out of range.
+    objective="l1" (pcl_gn_refine_l1; delta: GN_L1_DELTA unless given, inside [2^-20, 4]): the same chain on the Huber-L1 objective
+    F_rho = sum w m rho(l) / sum w m, rho = l - delta / 2 (l >= delta), l^2 / (2 delta) (l < delta) — for delta -> 0 the sampling loss
+    itself —, re-weighted at every evaluation: H, b are pose_information(objective="l1")'s.  The dict keeps its layout: sigma2_start, sigma2
+    and the trace's F column hold F_rho, stats is (M, S1, sum w m rho, F_rho, status) with M and S1 plain, cov is None.  objective="l2" (or
+    absent): the chain above, bit for bit.  objective and delta are no hyper-parameters (gn_hyper refuses them)."""
     _residual_cloud(cloud, pano, "gauss_newton_refine")
     trans, rot = _pose_rows(trans, rot)
     return _gauss_newton("gauss_newton_refine", _single_form(cloud, pano), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace,
-                         hyper)
+                         hyper, objective, delta)
 
 
-def gauss_newton_refine_at_winners(cloud, pano, winners, iters=10, trace=False, **hyper):
+def gauss_newton_refine_at_winners(cloud, pano, winners, iters=10, trace=False, objective="l2", delta=None, **hyper):
     """gauss_newton_refine from the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses)."""
     _residual_cloud(cloud, pano, "gauss_newton_refine_at_winners")
     who = "gauss_newton_refine_at_winners"
-    return _gauss_newton(who, _single_form(cloud, pano), *_winner_poses(winners, who), winners.device, iters, trace, hyper)
+    return _gauss_newton(who, _single_form(cloud, pano), *_winner_poses(winners, who), winners.device, iters, trace, hyper, objective, delta)
 
 
 def _images_call(who, cloud, panos, rows, planes):
@@ -642,38 +699,42 @@ def _images_form(cloud, panos, planes):
     return form
 
 
-def pose_information_images(cloud, panos, trans, rot, planes=None):
+def pose_information_images(cloud, panos, trans, rot, planes=None, objective="l2", delta=None):
     """pose_information for I poses, each against ITS OWN panorama, in one set of launches (pcl_pose_information_images): row i of
     (H, b, stats, cov) is pose (trans[i], rot[i]) against panos[i] — and, for a cloud of I colour sets (Cloud.with_color_sets), colour
     set i — under the cloud's own weight plane where it has one (planes=None) or under planes[i] of an (I, pcl_cloud_stride(n)) float32 GPU
     tensor (GradientDescent.weight_planes() of a weight-set chain).  Row i equals pose_information of that pose, panorama, colour set and
     plane alone, bit for bit.  ValueError: as pose_information; a colour-set count that is not the image count; panoramas of different
-    sizes or texel formats; planes of another shape."""
+    sizes or texel formats; planes of another shape.  objective / delta: as pose_information ("l1": pcl_pose_information_images_l1, cov
+    None, stats = (M, S1, sum w m rho, F_rho, status)); row i still equals the single call's with the same objective, bit for bit."""
     trans, rot = _pose_rows(trans, rot)
-    return _pose_information("pose_information_images", _images_form(cloud, panos, planes), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device)
+    return _pose_information("pose_information_images", _images_form(cloud, panos, planes), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device,
+                             objective, delta)
 
 
-def pose_information_images_at_winners(cloud, panos, winners, planes=None):
+def pose_information_images_at_winners(cloud, panos, winners, planes=None, objective="l2", delta=None):
     """pose_information_images at the poses of an (I, 16) tensor as _GdEngine.winners(I) returns it, read on the device (_winner_poses): row
     i is winner i against panos[i] (colour set i, plane i)."""
     who = "pose_information_images_at_winners"
-    return _pose_information(who, _images_form(cloud, panos, planes), *_winner_poses(winners, who), winners.device)
+    return _pose_information(who, _images_form(cloud, panos, planes), *_winner_poses(winners, who), winners.device, objective, delta)
 
 
-def gauss_newton_refine_images(cloud, panos, trans, rot, iters=10, trace=False, planes=None, **hyper):
+def gauss_newton_refine_images(cloud, panos, trans, rot, iters=10, trace=False, planes=None, objective="l2", delta=None, **hyper):
     """gauss_newton_refine for I poses, each against ITS OWN panorama, in ONE chain (pcl_gn_refine_images): pose i = (trans[i], rot[i]) is
     polished against panos[i] — colour set i of a cloud of I colour sets, the cloud's own weight plane (planes=None) or planes[i] as for
     pose_information_images.  -> gauss_newton_refine's dict with one row per image (trace: (iters + 1, I, 16)); row i equals the single
-    call's for that pose, panorama, colour set and plane, bit for bit — a pose that freezes moves no other pose's bits."""
+    call's for that pose, panorama, colour set and plane, bit for bit — a pose that freezes moves no other pose's bits.  objective / delta:
+    as gauss_newton_refine ("l1": pcl_gn_refine_images_l1; sigma2_start, sigma2 and the trace's F hold F_rho, stats = (M, S1, sum w m rho,
+    F_rho, status), cov None)."""
     trans, rot = _pose_rows(trans, rot)
     return _gauss_newton("gauss_newton_refine_images", _images_form(cloud, panos, planes), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device,
-                         iters, trace, hyper)
+                         iters, trace, hyper, objective, delta)
 
 
-def gauss_newton_refine_images_at_winners(cloud, panos, winners, iters=10, trace=False, planes=None, **hyper):
+def gauss_newton_refine_images_at_winners(cloud, panos, winners, iters=10, trace=False, planes=None, objective="l2", delta=None, **hyper):
     """gauss_newton_refine_images from the poses of an (I, 16) tensor as _GdEngine.winners(I) returns it, read on the device (_winner_poses)."""
     who = "gauss_newton_refine_images_at_winners"
-    return _gauss_newton(who, _images_form(cloud, panos, planes), *_winner_poses(winners, who), winners.device, iters, trace, hyper)
+    return _gauss_newton(who, _images_form(cloud, panos, planes), *_winner_poses(winners, who), winners.device, iters, trace, hyper, objective, delta)
 
 
 def _rooms_call(who, clouds, panos, rows):
