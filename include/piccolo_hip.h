@@ -156,6 +156,37 @@ int pcl_robust_weights(const float *residual_packed, int64_t n, int kind, float 
 size_t pcl_robust_weights_rows_workspace_bytes(int64_t n, int nrows);
 int pcl_robust_weights_rows(const float *residual_packed, int64_t n, int nrows, int kind, float k, float *planes, float *scale_out, void *workspace,
                             size_t workspace_bytes, void *stream);
+/* Score maps (additive to ABI 12; BUILD-DEFINED: the reference reduces the histogram stage's evidence to one number per pose).  Inputs: a
+ * packed cloud of pcl_cloud_pack (one colour set, no weights), K poses trans[K][3] / rot[K][3], the panorama size H x W, a split nsh x nsw
+ * (bh = H / nsh, bw = W / nsw, nblk = (nsh - 2) nsw) and pcl_hist_trim_scores' inter[K][nblk], nproj[K][nblk], nimg[nblk] for exactly these
+ * poses and this split.  valid(k, j) = nproj[k][j] > 0 && nimg[j] > 0 (the slot carry-over of pcl_hist_trim_reduce plays no part).
+ *   score2d[j], count2d[j]   the fp32 sum of inter[k][j] over the valid k in ascending order / their number (one IEEE division; exactly -1
+ *                            where the count is 0);
+ *   score3d[p], count3d[p]   the same over the poses k for which point p's centre pixel — the render's: R (x - t), truncate, clamp, no
+ *                            wrap — lies in a scored block j (h = row / bh in 1 .. nsh - 2, w = col / bw < nsw) with valid(k, j).  A pose
+ *                            that is not finite casts no vote.  No occlusion test: a hidden point votes with the patch in front of it.
+ * order null: score3d / count3d in packed order; otherwise order[slot] is the caller's index of the packed point (pcl_cloud_pack's order)
+ * and the outputs are in the caller's order.  Either pair of outputs may be null, not both.  Two launches, no atomics: the result does not
+ * depend on scheduling; nothing is allocated, nothing waits for the host (capturable).
+ * PCL_EINVAL, before any HIP call: a null input or workspace, both output pairs null or half a pair, n outside 1..PCL_MAX_POINTS, K outside
+ * 1..65535, nsh < 3, nsw < 1, H or W outside 1..65535, a block of zero pixels, workspace_bytes below pcl_score_maps_workspace_bytes(n, K,
+ * nsh, nsw) (0 for a shape no call accepts). */
+size_t pcl_score_maps_workspace_bytes(int64_t n, int K, int nsh, int nsw);
+int pcl_score_maps(const float *cloud, int64_t n, const float *trans, const float *rot, int K, int H, int W, int nsh, int nsw, const float *inter,
+                   const int32_t *nproj, const int32_t *nimg, const int64_t *order, float *score3d, int32_t *count3d, float *score2d,
+                   int32_t *count2d, void *workspace, size_t workspace_bytes, void *stream);
+/* A weight plane from a 3D score map given in any one point order (score_packed[n], count_packed[n]; scores >= 0 wherever the count is at
+ * least min_count).  lo / hi = the smallest / largest score over the points with count >= min_count (`voted` of them), by integer atomic
+ * min / max on the bit patterns: the result does not depend on scheduling.
+ *   plane[i] = clamp(fma(1 - floor, (s - lo) / (hi - lo), floor), 0, 1) for such a point, every operation rounded once, in this order;
+ *              1 for a point with fewer votes (no evidence), and for every point when voted == 0 or hi == lo.
+ * `plane` is the packed plane pcl_gd_run_weighted reads: pcl_cloud_stride(n) floats, padding 0.  range_out (nullable, device float[3])
+ * receives lo, hi (0, 0 when nothing voted) and voted (as a float).  Three launches, capturable.
+ * PCL_EINVAL, before any HIP call: a null score / count / plane / workspace, n outside 1..PCL_MAX_POINTS, min_count < 1, floor outside
+ * [0, 1), workspace_bytes below pcl_score_weights_workspace_bytes(n) (0 for n out of range). */
+size_t pcl_score_weights_workspace_bytes(int64_t n);
+int pcl_score_weights(const float *score_packed, const int32_t *count_packed, int64_t n, int min_count, float floor, float *plane, float *range_out,
+                      void *workspace, size_t workspace_bytes, void *stream);
 /* Pose information matrix and covariance (additive to ABI 12; BUILD-DEFINED: the reference returns a pose and a loss and says nothing about
  * how well the panorama constrains the pose).  One cloud with one colour set, no depth mask, as the residuals above.  For pose b =
  * (trans + b * pose_stride, rot + b * pose_stride: yaw, pitch, roll), theta = (t0, t1, t2, yaw, pitch, roll), and per point i the loss

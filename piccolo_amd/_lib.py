@@ -57,6 +57,10 @@ SIGNATURES = {
     "pcl_point_residuals_images": (_int, [_vp, _i64, _int, _c.POINTER(_c.c_uint64), _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp]),
     "pcl_robust_weights_rows_workspace_bytes": (_sz, [_i64, _int]),
     "pcl_robust_weights_rows": (_int, [_vp, _i64, _int, _int, _c.c_float, _vp, _vp, _vp, _sz, _vp]),
+    "pcl_score_maps_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
+    "pcl_score_maps": (_int, [_vp, _i64, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pcl_score_weights_workspace_bytes": (_sz, [_i64]),
+    "pcl_score_weights": (_int, [_vp, _vp, _i64, _int, _c.c_float, _vp, _vp, _vp, _sz, _vp]),
     "pcl_pose_information_workspace_bytes": (_sz, [_i64, _int]),
     "pcl_pose_information": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "pcl_gn_state_bytes": (_sz, [_int]),

@@ -24,10 +24,10 @@ from . import data_utils
 from . import dist as pdist
 from . import ops, synth
 from .color_utils import color_match, color_mod
-from .omniloc import (GN_KEYS, ROBUST_KEYS, _is_int, _refuse, _refuse_l1, gn_schedule, omniloc_all, omniloc_batch, omniloc_batch_images,
+from .omniloc import (GN_KEYS, ROBUST_KEYS, SCORE_KEYS, _is_int, _refuse, _refuse_l1, gn_schedule, omniloc_all, omniloc_batch, omniloc_batch_images,
                       omniloc_batch_images_polished, omniloc_batch_images_robust, omniloc_batch_rooms_images,
-                      omniloc_batch_rooms_images_polished, pose_covariance_flag, robust_schedule)
-from .utils import make_input_images, make_pano, out_of_room, resize_image, write_summaries
+                      omniloc_batch_rooms_images_polished, pose_covariance_flag, robust_schedule, score_weights)
+from .utils import make_input_images, make_input_scored, make_pano, out_of_room, resize_image, write_summaries
 
 
 def preprocess_colors(img, rgb, cfg):
@@ -89,6 +89,40 @@ def _check_robust_cfg(cfg):
                 raise ValueError("cfg.%s does not combine with cfg.%s" % (key, other))
         robust_schedule(cfg)                          # (its own ValueErrors, before any file is read)
         return
+
+
+def _check_score_cfg(cfg):
+    """Configuration-time rules of the score-weight keys of a known-room dataset loop, before any file is read: cfg.score_weights = True
+    initialises every image with make_input_scored and refines it under omniloc.score_weights of its maps, one image per launch chain;
+    cfg.score_split ([num_split_h >= 3, num_split_w >= 1]: the maps' own split, default the initialisation's), cfg.score_floor (a number
+    in [0, 1), default 0) and cfg.score_min_count (an int >= 1, default 1) go with it.  Not next to images_per_launch > 1, the robust keys,
+    robust_images_per_launch, polish_images_per_launch, room_search, room_search_images or depth_mask.
+    -> None without the keys, else (score_split or None, floor, min_count)"""
+    on = getattr(cfg, "score_weights", None)
+    others = [key for key in SCORE_KEYS[1:] if getattr(cfg, key, None) is not None]
+    if on is None or on is False:
+        if others:
+            raise ValueError("cfg.%s goes with cfg.score_weights = True" % others[0])
+        return None
+    if on is not True:
+        raise ValueError("cfg.score_weights %r: a bool" % (on,))
+    split = getattr(cfg, "score_split", None)
+    if split is not None:
+        if not isinstance(split, (list, tuple)) or len(split) != 2 or not all(_is_int(v) for v in split) or split[0] < 3 or split[1] < 1:
+            raise ValueError("cfg.score_split %r: [num_split_h >= 3, num_split_w >= 1]" % (split,))
+        split = (int(split[0]), int(split[1]))
+    floor = getattr(cfg, "score_floor", None)
+    if floor is not None and (not isinstance(floor, (int, float)) or isinstance(floor, bool) or not 0.0 <= float(floor) < 1.0):
+        raise ValueError("cfg.score_floor %r: a number in [0, 1)" % (floor,))
+    min_count = getattr(cfg, "score_min_count", None)
+    if min_count is not None and (not _is_int(min_count) or min_count < 1):
+        raise ValueError("cfg.score_min_count %r: an int >= 1" % (min_count,))
+    if int(getattr(cfg, "images_per_launch", 1)) > 1:
+        raise ValueError("cfg.score_weights does not combine with images_per_launch > 1 (one image per launch chain)")
+    for other in ROBUST_KEYS + ("robust_images_per_launch", "polish_images_per_launch", "room_search", "room_search_images", "depth_mask"):
+        if getattr(cfg, other, None):
+            raise ValueError("cfg.score_weights does not combine with cfg.%s" % other)
+    return split, 0.0 if floor is None else float(floor), 1 if min_count is None else int(min_count)
 
 
 def _check_polish_cfg(cfg, who):
@@ -226,7 +260,7 @@ def localize_synthetic(cfg, writer=None, log_dir=None):
 
     Query images are sharded over the ranks of an initialised process group (one process per GPU); every rank
     returns the full (num_images, 16) result table [t(3), R(9), loss, t_err, r_err, seconds]."""
-    _refuse(cfg, "localize_synthetic", "pose_covariance", "gn")
+    _refuse(cfg, "localize_synthetic", "pose_covariance", "gn", "score")
     dev = ops.device()
     n = int(getattr(cfg, "num_points", 100_000))
     H, W = int(getattr(cfg, "pano_height", 256)), int(getattr(cfg, "pano_width", 512))
@@ -526,6 +560,13 @@ def _localize_known_room(cfg, jobs):
     through omniloc_batch_images_polished — the plain, robust or pruned chain, then the polish and / or covariance of all winners at once."""
     xyz = jobs[0].xyz
     rgb = jobs[0].rgb if all(j.rgb is jobs[0].rgb for j in jobs) else [j.rgb for j in jobs]
+    score = _check_score_cfg(cfg)
+    if score is not None:                                    # (one image per group: _check_score_cfg refused every other group size)
+        (job,), (split, floor, min_count) = jobs, score
+        tr, ro, maps = make_input_scored(job.img_init, xyz, rgb, *_make_input_args(cfg), score_split=split)
+        if job.on_start is not None:
+            job.on_start(tr, ro)
+        return [refine_image(job.img_main, xyz, rgb, tr, ro, cfg, weights=score_weights(maps, floor, min_count))]
     starts = make_input_images([j.img_init for j in jobs], xyz, rgb, *_make_input_args(cfg))
     for j, (tr, ro) in zip(jobs, starts):
         if j.on_start is not None:
@@ -633,9 +674,12 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     cfg.images_per_launch is the group size of _run_dataset (_localize_known_room); under cfg.robust_iters it is cfg.robust_images_per_launch.
     cfg.polish_images_per_launch (_check_polish_cfg): the group size of a run that carries the gn keys and / or cfg.pose_covariance, routed
     through omniloc_batch_images_polished; with cfg.pose_covariance the CSV gains sigma_t (m) and sigma_r (degrees) (_run_known_room).
+    cfg.score_weights = True (_check_score_cfg; with cfg.score_split / score_floor / score_min_count): every image is initialised with
+    make_input_scored and refined under the score weights of its maps, one image per launch chain.
     cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms); with
     cfg.room_search_polish = True such a run takes the gn keys and / or cfg.pose_covariance (_check_room_polish_cfg)."""
     _require_gravity_aligned(cfg)
+    _check_score_cfg(cfg)
     _check_robust_cfg(cfg)
     if not _check_room_polish_cfg(cfg):
         _check_polish_cfg(cfg, "localize_stanford")
@@ -795,8 +839,9 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
     """OmniScenes loop (localize.py:300-530) over `root`/<split>_pano/<video>/<frame>, pcd/<room>.txt and <split>_pose;
     writes `omniscenes_results.csv`.  Includes the synthetic illumination changes (synth_const / synth_gamma / synth_wb)
     and the colour preprocessing of the whole image (match_color / sharpen_color).  cfg.images_per_launch is the group size of
-    _run_dataset (_localize_known_room); cfg.polish_images_per_launch and the CSV's sigma columns as in localize_stanford."""
+    _run_dataset (_localize_known_room); cfg.polish_images_per_launch, the CSV's sigma columns and cfg.score_weights as in localize_stanford."""
     _require_gravity_aligned(cfg)
+    _check_score_cfg(cfg)
     _check_robust_cfg(cfg)
     _check_polish_cfg(cfg, "localize_omniscenes")
     _seed_all()

@@ -32,6 +32,9 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
     covariance, for all query images of a shared chain at once (pose_information_images / gauss_newton_refine_images give the several-image
     calls to a caller); cfg gn_objective = "l1" (with gn_delta; default "l2") polishes on the Huber-L1 objective instead, which tends to
     the sampling loss itself as delta -> 0 (the rooms forms refuse it);
+  * score_maps / score_weights (not in the reference): per-point weights from the histogram stage's patch intersections averaged over
+    candidate poses (csrc/pcl_score.hip), usable as weights=; the cfg keys score_weights / score_split / score_floor / score_min_count
+    belong to the known-room dataset loops (localize._check_score_cfg) — the several-image and rooms entry points here refuse them;
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
     per iteration) as 4th element.
@@ -236,6 +239,7 @@ def _cfg(cfg, key, default):
 # them).  An entry point refuses the families it does not take with one _refuse call; the schedules below validate the ones it does.
 ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
 GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda", "gn_objective", "gn_delta")
+SCORE_KEYS = ("score_weights", "score_split", "score_floor", "score_min_count")
 _EXTENSIONS = {
     "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
     "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust, omniloc_batch_images_polished and localize.refine_image's parallel "
@@ -245,6 +249,7 @@ _EXTENSIONS = {
                                                     "cfg.polish_images_per_launch, a room search with cfg.room_search_polish"),
     "gn": (GN_KEYS, None, "omniloc_batch, omniloc_batch_images_polished, omniloc_batch_rooms_images_polished and localize.refine_image's parallel "
                           "branch do; the dataset loops with cfg.polish_images_per_launch, a room search with cfg.room_search_polish"),
+    "score": (SCORE_KEYS, None, "the known-room dataset loops do, one image per launch chain; elsewhere pass weights=score_weights(score_maps(...))"),
 }
 
 
@@ -423,6 +428,37 @@ def robust_weights(residuals_row, kind="trunc", k=2.5):
     row = ops._dev(residuals_row).reshape(-1)
     n = int(row.numel())
     return ops.robust_plane(n, row, kind, k)[0][:n].clone()
+
+
+# ------------------------------------------------------------------------------------------------ score maps
+# (not in the reference; build-defined, include/piccolo_hip.h) a source of per-point weights that needs no current pose: the histogram
+# stage's table of patch intersections, averaged over the candidate poses per image patch (2D map) and per point (3D map: the patch each
+# point projects into).  A region of the cloud that no longer looks like the query image collects low intersections from every pose that
+# sees it.  No occlusion test: a hidden point votes with the patch in front of it.  One cloud, one colour set, one image.
+def score_maps(img, xyz, rgb, trans, rot, num_split_h, num_split_w, parts=None):
+    """Namespace(score3d (N,), count3d (N,) int32 — in the order of xyz's rows; score2d, count2d (num_split_h - 2, num_split_w); inter, nproj
+    (K, nblk), nimg (nblk,), scores (K,): the histogram stage's parts; num_split_h, num_split_w) of the K poses trans / rot against img:
+    ops.hist_trim_scores(..., return_parts=True), then ops.score_maps.  parts: (scores, inter, nproj, nimg) of that very call made before
+    (utils.make_input_scored keeps its histogram stage's)."""
+    cloud = packed_cloud(xyz, rgb)
+    trans, rot = ops._dev(trans).reshape(-1, 3), ops._dev(rot).reshape(-1, 3)
+    H, W = int(img.shape[0]), int(img.shape[1])
+    if parts is None:
+        parts = ops.hist_trim_scores(img, cloud, trans, rot, num_split_h, num_split_w, return_parts=True)
+    scores, inter, nproj, nimg = parts
+    s3, c3, s2, c2 = ops.score_maps(cloud, trans, rot, H, W, num_split_h, num_split_w, inter, nproj, nimg)
+    shape = (num_split_h - 2, num_split_w)
+    return SimpleNamespace(score3d=s3, count3d=c3, score2d=s2.view(shape), count2d=c2.view(shape), inter=inter, nproj=nproj, nimg=nimg,
+                                 scores=scores, num_split_h=num_split_h, num_split_w=num_split_w)
+
+
+def score_weights(maps, floor=0.0, min_count=1):
+    """(N,) GPU weights in the caller's point order from score_maps' 3D map, usable as `weights=` wherever weights are taken: the scores of
+    the points with at least min_count votes stretched from [lowest, highest] to [floor, 1]; a point with fewer votes weighs 1, and so does
+    every point when nothing voted or all voted scores are equal (pcl_score_weights — the weights do not depend on the order of the
+    points)."""
+    n = int(maps.score3d.numel())
+    return ops.score_weight_plane(n, maps.score3d, maps.count3d, floor, min_count)[0][:n].clone()
 
 
 # ------------------------------------------------------------------------------------------------ pose information / covariance
@@ -966,7 +1002,7 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     and the chain runs the single-image plan, so image i's result is omniloc_batch(imgs[i], xyz, rgb[i], ...)'s bit for bit.  Images
     beyond the colour-set addressing limit go in further groups.  With the depth mask the colour-set chain is the depth chain
     (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image."""
-    _refuse(cfg, "omniloc_batch_images", "robust", "pose_covariance", "gn")
+    _refuse(cfg, "omniloc_batch_images", "robust", "pose_covariance", "gn", "score")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     I = len(imgs)
@@ -993,7 +1029,7 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
     same cfg bit for bit; every loss is the WEIGHTED loss of the last forward.  Parallel semantics only.  ValueError: cfg without
     robust_iters (and robust_schedule's refusals: the depth mask, the prune keys), cfg.visualize, lists of different lengths.  One image is
     omniloc_batch."""
-    _refuse(cfg, "omniloc_batch_images_robust", "pose_covariance", "gn")
+    _refuse(cfg, "omniloc_batch_images_robust", "pose_covariance", "gn", "score")
     robust = robust_schedule(cfg)
     if robust is None:
         raise ValueError("omniloc_batch_images_robust needs cfg.robust_iters (omniloc_batch_images runs the plain chain)")
@@ -1047,6 +1083,7 @@ def omniloc_batch_images_polished(imgs, xyz, rgb, input_trans_list, input_rot_li
         raise ValueError("%s needs cfg.gn_iters or cfg.pose_covariance (omniloc_batch_images / omniloc_batch_images_robust run the chain alone)" % who)
     if _cfg(cfg, "visualize", False):
         raise ValueError("%s does not take cfg.visualize" % who)
+    _refuse(cfg, who, "score")
     robust = robust_schedule(cfg)
     I = len(imgs)
     if I < 1 or len(input_trans_list) != I or len(input_rot_list) != I:
@@ -1141,7 +1178,7 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     each room's candidates).  More than PCL_GD_MAX_ROOMS rooms go in several chains.  With the depth mask the chain is the depth chain
     (pcl_gd_run_depth_chain: every room on its own z-buffer grid, the same bits per room); rooms whose tolerances differ (depth_tau_groups)
     go in a chain per tolerance."""
-    _refuse(cfg, "omniloc_batch_rooms", "robust", "pose_covariance", "gn")
+    _refuse(cfg, "omniloc_batch_rooms", "robust", "pose_covariance", "gn", "score")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R = len(rooms)
@@ -1215,7 +1252,7 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     the depth chain (pcl_gd_run_depth_chain) under the same rules; rooms whose tolerances differ (depth_tau_groups) go in a chain per
     tolerance, and images that share the rooms' colours run omniloc_batch_images per room where that is faster (depth_shared_chain_pays:
     its plan of all the images' candidates, so equal to the single calls up to the summation order of the partial sums, as there)."""
-    _refuse(cfg, "omniloc_batch_rooms_images", "robust", "pose_covariance", "gn")
+    _refuse(cfg, "omniloc_batch_rooms_images", "robust", "pose_covariance", "gn", "score")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R, I = len(rooms), len(imgs)
@@ -1292,7 +1329,7 @@ def omniloc_batch_rooms_images_polished(imgs, rooms, input_trans, input_rot, cfg
         raise ValueError("%s needs cfg.gn_iters or cfg.pose_covariance (omniloc_batch_rooms_images runs the chain alone)" % who)
     if bool(_cfg(cfg, "depth_mask", False)):
         raise ValueError("%s does not combine with cfg.depth_mask" % who)
-    _refuse(cfg, who, "robust")
+    _refuse(cfg, who, "robust", "score")
     if _cfg(cfg, "visualize", False):
         raise ValueError("%s does not take cfg.visualize" % who)
     R, I = len(rooms), len(imgs)

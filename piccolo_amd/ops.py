@@ -1125,6 +1125,65 @@ def hist_trim_scores_images(imgs, cloud, trans, rot, num_split_h, num_split_w, s
     return _hist_scores("hist_trim_scores_images", imgs, cloud, trans, rot, num_split_h, num_split_w, splat)[0]
 
 
+def _score_cloud(cloud, who):
+    _unweighted(cloud, who)
+    if cloud.color_sets > 1:
+        raise ValueError("%s: a cloud of colour sets is not taken (one colour set, as the histogram parts it reads)" % who)
+
+
+def score_maps(cloud, trans, rot, H, W, num_split_h, num_split_w, inter, nproj, nimg, packed=False):
+    """(score3d (N,), count3d (N,) int32, score2d (nblk,), count2d (nblk,) int32) from the parts of hist_trim_scores(..., return_parts=True)
+    for exactly these K poses and this split (pcl_score_maps, include/piccolo_hip.h): per scored image block the mean of `inter` over the
+    poses whose block is valid (nproj > 0 and nimg > 0), per point the mean over the poses of the intersection of the block its centre
+    pixel falls into; -1 and count 0 where nothing voted.  The 3D map is in the order of the cloud's xyz rows, packed=True: in packed
+    order.  Two launches, no host synchronisation."""
+    lib = _lib.load()
+    _score_cloud(cloud, "score_maps")
+    trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
+    K, nblk = int(trans.shape[0]), (int(num_split_h) - 2) * int(num_split_w)
+    inter, nproj, nimg = _dev(inter), _dev(nproj, torch.int32), _dev(nimg, torch.int32)
+    nws = lib.pcl_score_maps_workspace_bytes(cloud.n, K, int(num_split_h), int(num_split_w))
+    if nws == 0 or rot.shape[0] != K or int(H) // int(num_split_h) <= 0 or int(W) // int(num_split_w) <= 0:
+        raise ValueError("score_maps: K >= 1 poses, num_split_h >= 3, num_split_w >= 1 and blocks of at least one pixel")
+    if inter.numel() != K * nblk or nproj.numel() != K * nblk or nimg.numel() != nblk:
+        raise ValueError("score_maps: inter / nproj must be (K, nblk) and nimg (nblk,) for these poses and this split")
+    dev = cloud.data.device
+    score3d, count3d = torch.empty(cloud.n, dtype=F32, device=dev), torch.empty(cloud.n, dtype=torch.int32, device=dev)
+    score2d, count2d = torch.empty(nblk, dtype=F32, device=dev), torch.empty(nblk, dtype=torch.int32, device=dev)
+    ws = _bytes(nws)
+    _lib.check(lib.pcl_score_maps(_ptr(cloud.data), cloud.n, _ptr(trans), _ptr(rot), K, int(H), int(W), int(num_split_h), int(num_split_w), _ptr(inter),
+                                  _ptr(nproj), _ptr(nimg), None if packed else _ptr(cloud.order), _ptr(score3d), _ptr(count3d), _ptr(score2d),
+                                  _ptr(count2d), _ptr(ws), nws, _stream()), "pcl_score_maps")
+    return score3d, count3d, score2d, count2d
+
+
+def score_weight_plane(n, score_packed, count_packed, floor=0.0, min_count=1, plane=None):
+    """(plane, range) from a 3D score map of n points in any one point order (pcl_score_weights): range = (lo, hi, voted) on the GPU, the
+    smallest and largest score over the `voted` points with at least min_count votes; plane (pcl_cloud_stride(n) floats, what
+    Cloud.weighted_view takes for a map in packed order) = floor + (1 - floor) (s - lo) / (hi - lo) for such a point, 1 for a point with
+    fewer votes and for every point when nothing voted or hi == lo; padding 0.  plane: a tensor to write into."""
+    lib = _lib.load()
+    floor, min_count = float(floor), int(min_count)
+    if not (0.0 <= floor < 1.0):
+        raise ValueError("score_weight_plane: floor must be in [0, 1), got %r" % (floor,))
+    if min_count < 1:
+        raise ValueError("score_weight_plane: min_count must be at least 1, got %r" % (min_count,))
+    score, count = _dev(score_packed), _dev(count_packed, torch.int32)
+    nws = lib.pcl_score_weights_workspace_bytes(int(n))
+    if nws == 0 or score.dim() != 1 or score.numel() != n or count.dim() != 1 or count.numel() != n:
+        raise ValueError("score_weight_plane: one score and one count per point, (N,)")
+    stride = lib.pcl_cloud_stride(n)
+    if plane is None:
+        plane = torch.empty(stride, dtype=F32, device=score.device)
+    elif not (plane.is_cuda and plane.dtype == F32 and plane.is_contiguous() and plane.numel() == stride):
+        raise ValueError("score_weight_plane: plane must be a contiguous float32 GPU tensor of pcl_cloud_stride(n) entries")
+    rng = torch.empty(3, dtype=F32, device=score.device)
+    ws = _bytes(nws)
+    _lib.check(lib.pcl_score_weights(_ptr(score), _ptr(count), int(n), min_count, floor, _ptr(plane), _ptr(rng), _ptr(ws), nws, _stream()),
+               "pcl_score_weights")
+    return plane, rng
+
+
 def depth_mask(cloud, trans, rot, resolution, tau=None, stride=1):
     """(B, n) uint8 GPU tensor in PACKED point order: scatter-min visibility of every point for every pose on a z-buffer grid of
     `resolution` = (depth_h, depth_w) cells (the DEPTH grid — see default_depth — not the panorama's size) built from every

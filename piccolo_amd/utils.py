@@ -212,7 +212,11 @@ def trim_input_hist_secondary(img, xyz, rgb, trans, rot, num_input, num_split_h,
     """Second trimming stage (utils.py:510-588): render a panorama per candidate and rank candidates by the mean
     block-wise colour-histogram intersection with the query image.  All candidates go through three fused kernels
     (csrc/pcl_hist.hip): batched z-buffer splat, query histograms, per-(candidate, block) LDS histogram + intersection."""
-    scores = ops.hist_trim_scores(img, packed_cloud(xyz, rgb), trans, rot, num_split_h, num_split_w)
+    return _best_by_hist_score(ops.hist_trim_scores(img, packed_cloud(xyz, rgb), trans, rot, num_split_h, num_split_w), trans, rot, num_input)
+
+
+def _best_by_hist_score(scores, trans, rot, num_input):
+    """the num_input candidates with the highest scores, best first (utils.py:583-586)"""
     n = min(num_input, scores.numel())
     if n <= ops.SELECT_MAX_KEEP:                    # flip(argsort()[-n:]) and the two gathers (utils.py:583-586) in one launch
         tt, tr = ops.select_poses(scores, n, trans, rot, largest=True)
@@ -351,6 +355,35 @@ def make_input(img, xyz, rgb, num_input, init_dict=None, criterion="histogram", 
         raise UnboundLocalError("make_input: only criterion='loss_histogram' is implemented (as in the reference)")
     t1, r1 = trim_input_loss(img, xyz, rgb, trans, rot, num_intermediate)
     return trim_input_hist_secondary(img, xyz, rgb, t1, r1, num_input, init_dict["num_split_h"], init_dict["num_split_w"])
+
+
+def candidate_grids(img, xyz, init_dict):
+    """(trans, rot): the candidate grids of make_input for this cloud and config, from the same caches"""
+    from .omniloc import _cached
+    key = _init_key(init_dict, img.device)
+    rot = _ROT_GRIDS.get(key)
+    if rot is None:
+        rot = _ROT_GRIDS[key] = generate_rot_points(init_dict, device=img.device)
+    return _cached("grid", (xyz,), lambda: generate_trans_points(xyz, init_dict, device=img.device), sub=key), rot
+
+
+def make_input_scored(img, xyz, rgb, num_input, init_dict, criterion, num_intermediate, score_split=None):
+    """make_input with the histogram stage's parts kept (not in the reference): -> (input_trans, input_rot, maps).  The first two are
+    make_input's, bit for bit; maps = omniloc.score_maps over the num_intermediate survivors of the loss trim.  score_split None: at the
+    initialisation's own split, from the parts of the ONE histogram stage that ranked the survivors; (num_split_h, num_split_w): a second
+    histogram stage at that split over the same poses."""
+    from .omniloc import score_maps
+    if init_dict["sample_rate_for_init"] is not None:
+        raise NotImplementedError("sample_rate_for_init: broken in the reference too (utils.py:618-620)")
+    if criterion != "loss_histogram":
+        raise UnboundLocalError("make_input: only criterion='loss_histogram' is implemented (as in the reference)")
+    trans, rot = candidate_grids(img, xyz, init_dict)
+    t1, r1 = trim_input_loss(img, xyz, rgb, trans, rot, num_intermediate)
+    nsh, nsw = init_dict["num_split_h"], init_dict["num_split_w"]
+    parts = ops.hist_trim_scores(img, packed_cloud(xyz, rgb), t1, r1, nsh, nsw, return_parts=True)
+    tt, tr = _best_by_hist_score(parts[0], t1, r1, num_input)
+    maps = score_maps(img, xyz, rgb, t1, r1, nsh, nsw, parts=parts) if score_split is None else score_maps(img, xyz, rgb, t1, r1, *score_split)
+    return tt, tr, maps
 
 
 def make_input_images(imgs, xyz, rgb, num_input, init_dict=None, criterion="histogram", num_intermediate=None):
