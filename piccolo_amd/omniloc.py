@@ -215,10 +215,13 @@ def _chain_panos(imgs, n_points, direct=False):
 
 def _over_color_sets(n, I, part, rooms=None):
     """I images with per-image colour sets of an n-point cloud (the largest room's) in color_set_groups' groups: None when one group holds them
-    all, else part(i0, i1) of every group [i0, i1) concatenated, image after image — per room when part returns `rooms` lists"""
+    all, else _side_by_side of the groups"""
     sizes = color_set_groups(n, I)
-    if len(sizes) == 1:
-        return None
+    return None if len(sizes) == 1 else _side_by_side(sizes, part, rooms)
+
+
+def _side_by_side(sizes, part, rooms=None):
+    """part(i0, i1) of every run [i0, i1) of `sizes` images concatenated, image after image — per room when part returns `rooms` lists"""
     out, i0 = [] if rooms is None else [[] for _ in range(rooms)], 0
     for m in sizes:
         some = part(i0, i0 + m)
@@ -598,6 +601,26 @@ def gauss_newton_refine_images(imgs, xyz, rgb, trans, rot, iters=10, weights=Non
 POLISHED_ROW = 52      # floats per image a polished chain copies to the host: t (3), R (9), loss, took, S1, M, cov (36)
 
 
+def _entry(row, want_cov=False, loss=None):
+    """A host row -> [t (3,1), R (3,3), loss ()] from its columns 0:3, 3:12 and 12 (or the `loss` given), and cov (6,6) from a POLISHED_ROW's
+    last 36 when wanted: with _polished_entry the only places where what an entry point returns is cut from what the D2H copy brought"""
+    out = [row[0:3].reshape(3, 1).clone(), row[3:12].reshape(3, 3).clone(), row[12].clone() if loss is None else loss]
+    if want_cov:
+        out.append(row[16:POLISHED_ROW].reshape(6, 6).clone())
+    return out
+
+
+def _polished_entry(row, want_cov):
+    """_entry of a _polished_rows row: where the polish took a step (column 13) the loss is S1 / M of its info record (columns 14, 15)"""
+    # (float32 on the host: one correctly rounded division)
+    return _entry(row, want_cov, row[14] / row[15] if float(row[13]) != 0.0 else None)
+
+
+def _last_engine(gd):
+    """the engine whose forward ran last in the chain `gd` (an engine or a _PrunedChain)"""
+    return gd.last if isinstance(gd, _PrunedChain) else gd
+
+
 def _winners_polished(gd, cloud, panos, wins, gn, want_cov):
     """What omniloc_batch does for its one winner, for the (I, 16) winners rows `wins` of the chain `gd` (an engine or a _PrunedChain) at
     once -> (I, POLISHED_ROW) on the GPU.  With gn: one gauss_newton_refine_images_at_winners under the weight planes the chain's last
@@ -605,7 +628,7 @@ def _winners_polished(gd, cloud, panos, wins, gn, want_cov):
     those of the polish's info record at that pose (the caller forms the loss S1 / M), else the chain's own t, R, loss.  cov: the polish's
     own, or pose_information_images_at_winners' when there is no polish (zeros when not wanted)."""
     I = int(wins.shape[0])
-    engine = gd.last if isinstance(gd, _PrunedChain) else gd
+    engine = _last_engine(gd)
     planes = engine._run_weights()
     if planes is not None:
         planes = planes.view(I, -1) if engine.weight_sets else None          # (a plain chain's cloud plane is the cloud's own)
@@ -635,8 +658,7 @@ def _polished_rows(wins, gn, want_cov, information, polish, information_at=None)
 
 def _winner_cloud(gd, cloud):
     """`cloud` under the weight plane the last forward of the chain `gd` (an engine or a _PrunedChain) ran with"""
-    engine = gd.last if isinstance(gd, _PrunedChain) else gd
-    plane = engine._run_weights()
+    plane = _last_engine(gd)._run_weights()
     if plane is not None and plane is not cloud.weights:
         cloud = cloud.weighted_view(plane)
     return cloud
@@ -827,7 +849,7 @@ def _refine_groups(chain, trans_list, rot_list, polish=None):
             r.copy_(leaf_r[k * B:(k + 1) * B].reshape(r.shape).to(r.device))
     if polish is not None:
         return host
-    return [[host[k, 0:3].reshape(3, 1).clone(), host[k, 3:12].reshape(3, 3).clone(), host[k, 12].clone()] for k in range(n)]
+    return [_entry(row) for row in host]
 
 
 def _over_room_groups(groups, part):
@@ -886,7 +908,7 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     with torch.no_grad():
         input_trans[starting_point] = res[6:9].to(input_trans.device)
         input_rot[starting_point] = res[9:12].to(input_rot.device)
-    ret = [out[0:3].reshape(3, 1).clone(), out[3:12].reshape(3, 3).clone(), out[12].clone()]
+    ret = _entry(out)
     if vis:
         ret.append(frames)
     return ret
@@ -932,7 +954,7 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     with torch.no_grad():
         input_trans.copy_(res[:, 6:9].to(input_trans.device))
         input_rot.copy_(res[:, 9:12].to(input_rot.device))
-    return [[host[i, 0:3].reshape(3, 1).clone(), host[i, 3:12].reshape(3, 3).clone(), host[i, 12].clone()] for i in range(K)]
+    return [_entry(row) for row in host]
 
 
 def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, weights=None):
@@ -979,10 +1001,63 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
         cov = _winner_covariance(gd, packed_cloud(xyz, rgb, weights), pano, win) if want_cov else None
         out = win[0].cpu()
     after()
-    ret = [out[0:3].reshape(3, 1).clone(), out[3:12].reshape(3, 3).clone(), out[12].clone()]
+    ret = _entry(out)
     if want_cov:
         ret.append(cov[0].cpu())
     return ret
+
+
+def _check_images(who, imgs, trans_list, rot_list, rgb):
+    """The list lengths of a several-image entry point `who`, before a device is touched -> (the image count, shared_rgb(rgb))"""
+    I = len(imgs)
+    if I < 1 or len(trans_list) != I or len(rot_list) != I:
+        raise ValueError("%s: %d images, %d / %d lists of starting poses" % (who, I, len(trans_list), len(rot_list)))
+    rgb = shared_rgb(rgb)
+    if isinstance(rgb, list) and len(rgb) != I:
+        raise ValueError("%s: %d colour sets for %d images" % (who, len(rgb), I))
+    return I, rgb
+
+
+def _images_ladder(who, imgs, xyz, rgb, trans_list, rot_list, cfg, scalar_summaries, batch_mode=True, forward_one=False, direct=False,
+                   weight_sets=False, polish=None):
+    """How the images of ONE cloud are cut into chains, for omniloc_batch_images, _robust and _polished (each has refused the cfg keys it does
+    not take): check the lists; one image may be omniloc_batch itself; per-image colour sets beyond color_set_groups' limit go group by group
+    through this ladder again; else one chain (_chain_panos, the box, _refine_groups).  What the three forms differ in, as found:
+
+        parameter      omniloc_batch_images         _robust      _polished
+        batch_mode     the caller's                 True         True
+        forward_one    False: one image runs the    True         True
+                       chain (batch_mode=False
+                       has no omniloc_batch)
+        direct         True: more than 8 images     False        False
+                       are packed past the cache
+        weight_sets    False                        True         with the robust keys (a weight plane per image)
+        polish         None                         None         (gn_schedule, want_cov): _winners_polished after the chain, and
+                                                                 prune_schedule's refusals before a device is touched"""
+    I, rgb = _check_images(who, imgs, trans_list, rot_list, rgb)
+    if polish is not None:
+        prune_schedule(cfg, int(trans_list[0].shape[0]))         # (its own refusals, before a device is touched)
+    if strict_reference_asserts and batch_mode:
+        assert cfg.num_input > 1
+    if forward_one and I == 1:
+        return [omniloc_batch(imgs[0], xyz, rgb, trans_list[0], rot_list[0], cfg, scalar_summaries)]
+    if isinstance(rgb, list):
+        out = _over_color_sets(int(xyz.shape[0]), I, lambda i0, i1: _images_ladder(
+            who, imgs[i0:i1], xyz, rgb[i0:i1], trans_list[i0:i1], rot_list[i0:i1], cfg, scalar_summaries, batch_mode, forward_one, direct,
+            weight_sets, polish))
+        if out is not None:
+            return out
+    panos = _chain_panos(imgs, xyz.shape[0], direct=direct and I > 8)      # (else the texel format every image's own omniloc_batch call takes)
+    box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
+
+    def chain(tr, ro):
+        return _refine(xyz, rgb, panos, tr, ro, box, cfg, batch_mode, weight_sets=I if weight_sets else 0)
+    if polish is None:
+        return _refine_groups(chain, trans_list, rot_list)
+    gn, want_cov = polish
+    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb)
+    host = _refine_groups(chain, trans_list, rot_list, polish=lambda gd, wins: _winners_polished(gd, cloud, panos, wins, gn, want_cov))
+    return [_polished_entry(row, want_cov) for row in host]
 
 
 def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries=None, batch_mode=True):
@@ -1001,22 +1076,10 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     rgb: one (N, 3) tensor, or a LIST of one per image (per-image colours, e.g. color_mod's): the cloud then holds a colour set per image
     and the chain runs the single-image plan, so image i's result is omniloc_batch(imgs[i], xyz, rgb[i], ...)'s bit for bit.  Images
     beyond the colour-set addressing limit go in further groups.  With the depth mask the colour-set chain is the depth chain
-    (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image."""
+    (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image.
+    ValueError, before a device is touched: lists of different lengths, a colour-set count that is not the image count."""
     _refuse(cfg, "omniloc_batch_images", "robust", "pose_covariance", "gn", "score")
-    if strict_reference_asserts and batch_mode:
-        assert cfg.num_input > 1
-    I = len(imgs)
-    rgb = shared_rgb(rgb)
-    if isinstance(rgb, list):
-        if len(rgb) != I:
-            raise ValueError("omniloc_batch_images: %d colour sets for %d images" % (len(rgb), I))
-        out = _over_color_sets(int(xyz.shape[0]), I, lambda i0, i1: omniloc_batch_images(
-            imgs[i0:i1], xyz, rgb[i0:i1] if i1 - i0 > 1 else rgb[i0], input_trans_list[i0:i1], input_rot_list[i0:i1], cfg, scalar_summaries, batch_mode))
-        if out is not None:
-            return out
-    panos = _chain_panos(imgs, xyz.shape[0], direct=I > 8)
-    box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
-    return _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, batch_mode), input_trans_list, input_rot_list)
+    return _images_ladder("omniloc_batch_images", imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries, batch_mode, direct=True)
 
 
 def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries=None):
@@ -1035,24 +1098,8 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
         raise ValueError("omniloc_batch_images_robust needs cfg.robust_iters (omniloc_batch_images runs the plain chain)")
     if _cfg(cfg, "visualize", False):
         raise ValueError("omniloc_batch_images_robust does not take cfg.visualize")
-    I = len(imgs)
-    if I < 1 or len(input_trans_list) != I or len(input_rot_list) != I:
-        raise ValueError("omniloc_batch_images_robust: %d images, %d / %d lists of starting poses" % (I, len(input_trans_list), len(input_rot_list)))
-    rgb = shared_rgb(rgb)
-    if isinstance(rgb, list) and len(rgb) != I:
-        raise ValueError("omniloc_batch_images_robust: %d colour sets for %d images" % (len(rgb), I))
-    if strict_reference_asserts:
-        assert cfg.num_input > 1
-    if I == 1:
-        return [omniloc_batch(imgs[0], xyz, rgb[0] if isinstance(rgb, list) else rgb, input_trans_list[0], input_rot_list[0], cfg, scalar_summaries)]
-    if isinstance(rgb, list):
-        out = _over_color_sets(int(xyz.shape[0]), I, lambda i0, i1: omniloc_batch_images_robust(
-            imgs[i0:i1], xyz, rgb[i0:i1], input_trans_list[i0:i1], input_rot_list[i0:i1], cfg, scalar_summaries))
-        if out is not None:
-            return out
-    panos = _chain_panos(imgs, xyz.shape[0])      # (the texel format every image's own omniloc_batch call takes)
-    box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
-    return _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, True, weight_sets=I), input_trans_list, input_rot_list)
+    return _images_ladder("omniloc_batch_images_robust", imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries, forward_one=True,
+                          weight_sets=True)
 
 
 def omniloc_batch_images_polished(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries=None):
@@ -1084,35 +1131,8 @@ def omniloc_batch_images_polished(imgs, xyz, rgb, input_trans_list, input_rot_li
     if _cfg(cfg, "visualize", False):
         raise ValueError("%s does not take cfg.visualize" % who)
     _refuse(cfg, who, "score")
-    robust = robust_schedule(cfg)
-    I = len(imgs)
-    if I < 1 or len(input_trans_list) != I or len(input_rot_list) != I:
-        raise ValueError("%s: %d images, %d / %d lists of starting poses" % (who, I, len(input_trans_list), len(input_rot_list)))
-    rgb = shared_rgb(rgb)
-    if isinstance(rgb, list) and len(rgb) != I:
-        raise ValueError("%s: %d colour sets for %d images" % (who, len(rgb), I))
-    prune_schedule(cfg, int(input_trans_list[0].shape[0]))       # (its own refusals, before a device is touched)
-    if strict_reference_asserts:
-        assert cfg.num_input > 1
-    if I == 1:
-        return [omniloc_batch(imgs[0], xyz, rgb[0] if isinstance(rgb, list) else rgb, input_trans_list[0], input_rot_list[0], cfg, scalar_summaries)]
-    if isinstance(rgb, list):
-        out = _over_color_sets(int(xyz.shape[0]), I, lambda i0, i1: omniloc_batch_images_polished(
-            imgs[i0:i1], xyz, rgb[i0:i1], input_trans_list[i0:i1], input_rot_list[i0:i1], cfg, scalar_summaries))
-        if out is not None:
-            return out
-    panos = _chain_panos(imgs, xyz.shape[0])      # (the texel format every image's own omniloc_batch call takes)
-    box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
-    cloud = packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb)
-    host = _refine_groups(lambda tr, ro: _refine(xyz, rgb, panos, tr, ro, box, cfg, True, weight_sets=I if robust is not None else 0),
-                          input_trans_list, input_rot_list, polish=lambda gd, wins: _winners_polished(gd, cloud, panos, wins, gn, want_cov))
-    out = []
-    for row in host:
-        loss = row[14] / row[15] if float(row[13]) != 0.0 else row[12]       # (float32 on the host: one correctly rounded division)
-        out.append([row[0:3].reshape(3, 1).clone(), row[3:12].reshape(3, 3).clone(), loss.clone()])
-        if want_cov:
-            out[-1].append(row[16:POLISHED_ROW].reshape(6, 6).clone())
-    return out
+    return _images_ladder(who, imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries, forward_one=True,
+                          weight_sets=robust_schedule(cfg) is not None, polish=(gn, want_cov))
 
 
 def depth_tau_groups(points, H, W, cfg):
@@ -1187,21 +1207,10 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     B = int(input_trans_list[0].shape[0])
     if any(int(t.shape[0]) != B for t in input_trans_list) or any(int(r.shape[0]) != B for r in input_rot_list):
         raise ValueError("omniloc_batch_rooms: every room needs the same number of starting poses")
-    groups = depth_tau_groups([int(xyz.shape[0]) for xyz, _ in rooms], int(img.shape[0]), int(img.shape[1]), cfg)
-
-    def part(idx):
-        return omniloc_batch_rooms(img, [rooms[r] for r in idx], [input_trans_list[r] for r in idx], [input_rot_list[r] for r in idx], cfg,
-                                   scalar_summaries, batch_mode)
-    if len(groups) > 1:
-        return _over_room_groups(groups, part)
-    if R == 1:                                         # one room: the single-room path itself (no concatenation, no per-room write-back)
-        xyz, rgb = rooms[0]
-        if batch_mode:
-            return [omniloc_batch(img, xyz, rgb, input_trans_list[0], input_rot_list[0], cfg, scalar_summaries)]
-        return omniloc_batch_images([img], xyz, rgb, [input_trans_list[0]], [input_rot_list[0]], cfg, scalar_summaries, batch_mode=False)
-    if R > ops._lib.GD_MAX_ROOMS:
-        return _over_room_groups(_room_cap_groups(R), part)
-    return _refine_groups(lambda tr, ro: _rooms_chain(img, rooms, tr, ro, cfg, batch_mode), input_trans_list, input_rot_list)
+    # (the rooms ladder's one-image case)
+    out = _rooms_ladder([img], rooms, [[t] for t in input_trans_list], [[r] for r in input_rot_list], cfg,
+                        lambda *piece: _plain_leaf(*piece, cfg, scalar_summaries, batch_mode), scalar_summaries, batch_mode)
+    return [o[0] for o in out]
 
 
 # One chain for several images pays where a one-image chain is bound by launch latency (tools/room_images_bench.py, DESIGN.md §4.6d, ms per
@@ -1237,6 +1246,100 @@ def _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode):
     return _chain("gd_rooms_images", imgs, rooms, tr, ro, cfg, batch_mode)
 
 
+def _check_rooms(who, imgs, rooms, input_trans, input_rot):
+    """The shapes of a rooms x images entry point `who`, before a device is touched -> (R, I, B, the rooms with shared_rgb colours)"""
+    R, I = len(rooms), len(imgs)
+    if R == 0 or I == 0 or len(input_trans) != R or len(input_rot) != R:
+        raise ValueError("%s: %d rooms, %d images, %d / %d starting-pose sets" % (who, R, I, len(input_trans), len(input_rot)))
+    if any(len(t) != I for t in input_trans) or any(len(r) != I for r in input_rot):
+        raise ValueError("%s: every room needs one starting-pose set per image" % who)
+    B = int(input_trans[0][0].shape[0])
+    if any(int(t.shape[0]) != B for ts in input_trans for t in ts) or any(int(r.shape[0]) != B for rs in input_rot for r in rs):
+        raise ValueError("%s: every room and image needs the same number of starting poses" % who)
+    rooms = [(xyz, shared_rgb(rgb)) for xyz, rgb in rooms]
+    for _, rgb in rooms:
+        if isinstance(rgb, list) and len(rgb) != I:
+            raise ValueError("%s: %d colour sets for %d images" % (who, len(rgb), I))
+    return R, I, B, rooms
+
+
+def _rooms_ladder(imgs, rooms, trans, rot, cfg, leaf, scalar_summaries=None, batch_mode=True):
+    """How images x rooms are cut into chains, for omniloc_batch_rooms (one image), omniloc_batch_rooms_images and its polished form, on
+    checked arguments (rgb: shared_rgb's; trans[r][i] / rot[r][i]) -> out[r][i].  A step that cuts sends every piece down this ladder again:
+      1. rooms whose depth tolerances differ go group by group (depth_tau_groups);
+      2. under the depth mask, images that share the rooms' colours run omniloc_batch_images per room where that is faster
+         (depth_shared_chain_pays);
+      3. every image runs by itself where one chain for all is too large to gain (rooms_images_chain_pays);
+      4. more than PCL_GD_MAX_ROOMS rooms go in runs of that many;
+      5. per-image colour sets beyond the largest room's limit go in color_set_groups' groups;
+      6. leaf(imgs, rooms, trans, rot) runs the chain of what is left.  One image or one room is the leaf's business.
+    Why the order is safe for every caller: the polished form refuses the depth mask, so steps 1 and 2 never cut for it;
+    rooms_images_chain_pays is monotone in the points (points x candidates <= a constant), so step 3, decided on all the rooms, comes out the
+    same for every run of rooms step 4 cuts — deciding it before the room cap equals deciding it after —, and once every image runs by
+    itself (or there is one image only) steps 2, 3 and 5 are inert."""
+    R, I, B = len(rooms), len(imgs), int(trans[0][0].shape[0])
+    points = [int(xyz.shape[0]) for xyz, _ in rooms]
+
+    def of_rooms(idx):
+        return _rooms_ladder(imgs, [rooms[r] for r in idx], [trans[r] for r in idx], [rot[r] for r in idx], cfg, leaf, scalar_summaries, batch_mode)
+
+    def of_images(i0, i1):
+        return _rooms_ladder(imgs[i0:i1], [(xyz, shared_rgb(rgb[i0:i1]) if isinstance(rgb, list) else rgb) for xyz, rgb in rooms],
+                             [t[i0:i1] for t in trans], [r[i0:i1] for r in rot], cfg, leaf, scalar_summaries, batch_mode)
+    groups = depth_tau_groups(points, int(imgs[0].shape[0]), int(imgs[0].shape[1]), cfg)
+    if len(groups) > 1:
+        return _over_room_groups(groups, of_rooms)
+    sets = any(isinstance(rgb, list) for _, rgb in rooms)
+    if I > 1 and not sets and bool(_cfg(cfg, "depth_mask", False)) and not depth_shared_chain_pays(I, B):
+        return [omniloc_batch_images(imgs, xyz, rgb, trans[r], rot[r], cfg, scalar_summaries, batch_mode) for r, (xyz, rgb) in enumerate(rooms)]
+    if I > 1 and not rooms_images_chain_pays(sum(points), B):
+        return _side_by_side([1] * I, of_images, R)
+    if R > ops._lib.GD_MAX_ROOMS:
+        return _over_room_groups(_room_cap_groups(R), of_rooms)
+    if sets:
+        # one kind of cloud per chain: a room whose images share its colours holds them I times
+        rooms = [(xyz, rgb if isinstance(rgb, list) else [rgb] * I) for xyz, rgb in rooms]
+        out = _over_color_sets(max(points), I, of_images, R)
+        if out is not None:
+            return out
+    return leaf(imgs, rooms, trans, rot)
+
+
+def _leaf_chain(imgs, rooms, cfg, batch_mode):
+    """chain(tr, ro) of one leaf of the rooms ladder: the one-image rooms chain, or the rooms x images chain"""
+    if len(imgs) == 1:
+        return lambda tr, ro: _rooms_chain(imgs[0], rooms, tr, ro, cfg, batch_mode)
+    return lambda tr, ro: _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode)
+
+
+def _plain_leaf(imgs, rooms, trans, rot, cfg, scalar_summaries, batch_mode):
+    """The plain leaf of _rooms_ladder -> out[r][i] = [t, R, loss].  One image in one room is the single-room path itself (no concatenation,
+    no per-room write-back)."""
+    I, flat_t, flat_r = len(imgs), [t for ts in trans for t in ts], [r for rs in rot for r in rs]
+    if len(flat_t) > 1:
+        flat = _refine_groups(_leaf_chain(imgs, rooms, cfg, batch_mode), flat_t, flat_r)
+    elif batch_mode:
+        flat = [omniloc_batch(imgs[0], *rooms[0], flat_t[0], flat_r[0], cfg, scalar_summaries)]
+    else:
+        flat = omniloc_batch_images(imgs, *rooms[0], flat_t, flat_r, cfg, scalar_summaries, batch_mode=False)
+    return [flat[r * I:(r + 1) * I] for r in range(len(rooms))]
+
+
+def _polished_leaf(imgs, rooms, trans, rot, cfg, gn, want_cov):
+    """The polished leaf of _rooms_ladder: the chain, then on the device from its winners rows ONE polish and / or information pass over all
+    (room, image) winners -> out[r][i] = _polished_entry + [the chain's own winner loss] (a polished row's column 12 is the polish's)"""
+    I = len(imgs)
+    clouds = [packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb) for xyz, rgb in rooms]      # (the chain's own: cached)
+    panos = _chain_panos(imgs, max(int(xyz.shape[0]) for xyz, _ in rooms))
+    host = _refine_groups(_leaf_chain(imgs, rooms, cfg, True), [t for ts in trans for t in ts], [r for rs in rot for r in rs],
+                          polish=lambda gd, wins: torch.cat([_polished_rows(
+                              wins, gn, want_cov, lambda: ops.pose_information_rooms_at_winners(clouds, panos, wins),
+                              lambda: ops.gauss_newton_refine_rooms_at_winners(clouds, panos, wins, iters=gn[0], **gn[1])), wins[:, 12:13]], dim=1))
+    # (the chain's losses ride as Python floats — float32 values, exact — so that carrying them costs the host one tolist per chain)
+    flat = [_polished_entry(row, want_cov) + [loss] for row, loss in zip(host, host[:, POLISHED_ROW].tolist())]
+    return [flat[r * I:(r + 1) * I] for r in range(len(rooms))]
+
+
 def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_summaries=None, batch_mode=True):
     """Room search for SEVERAL query images (not in the reference): omniloc_batch of every image against every room in one launch chain.
 
@@ -1255,54 +1358,9 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     _refuse(cfg, "omniloc_batch_rooms_images", "robust", "pose_covariance", "gn", "score")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
-    R, I = len(rooms), len(imgs)
-    if R == 0 or I == 0 or len(input_trans) != R or len(input_rot) != R:
-        raise ValueError("omniloc_batch_rooms_images: %d rooms, %d images, %d / %d starting-pose sets" % (R, I, len(input_trans), len(input_rot)))
-    if any(len(t) != I for t in input_trans) or any(len(r) != I for r in input_rot):
-        raise ValueError("omniloc_batch_rooms_images: every room needs one starting-pose set per image")
-    B = int(input_trans[0][0].shape[0])
-    if any(int(t.shape[0]) != B for ts in input_trans for t in ts) or any(int(r.shape[0]) != B for rs in input_rot for r in rs):
-        raise ValueError("omniloc_batch_rooms_images: every room and image needs the same number of starting poses")
-    rooms = [(xyz, shared_rgb(rgb)) for xyz, rgb in rooms]
-    for _, rgb in rooms:
-        if isinstance(rgb, list) and len(rgb) != I:
-            raise ValueError("omniloc_batch_rooms_images: %d colour sets for %d images" % (len(rgb), I))
-    groups = depth_tau_groups([int(xyz.shape[0]) for xyz, _ in rooms], int(imgs[0].shape[0]), int(imgs[0].shape[1]), cfg)
-
-    def part(idx):
-        return omniloc_batch_rooms_images(imgs, [rooms[r] for r in idx], [input_trans[r] for r in idx], [input_rot[r] for r in idx], cfg,
-                                          scalar_summaries, batch_mode)
-    if len(groups) > 1:
-        return _over_room_groups(groups, part)
-    if (bool(_cfg(cfg, "depth_mask", False)) and I > 1 and not any(isinstance(rgb, list) for _, rgb in rooms)
-            and not depth_shared_chain_pays(I, B)):
-        return [omniloc_batch_images(imgs, xyz, rgb, input_trans[r], input_rot[r], cfg, scalar_summaries, batch_mode)
-                for r, (xyz, rgb) in enumerate(rooms)]
-    if I > 1 and not rooms_images_chain_pays(sum(int(xyz.shape[0]) for xyz, _ in rooms), B):
-        out = [[] for _ in range(R)]
-        for i in range(I):
-            one = omniloc_batch_rooms_images(imgs[i:i + 1], [(xyz, rgb[i] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms],
-                                             [t[i:i + 1] for t in input_trans], [r[i:i + 1] for r in input_rot], cfg, scalar_summaries, batch_mode)
-            for r in range(R):
-                out[r] += one[r]
-        return out
-    if I == 1:
-        one = omniloc_batch_rooms(imgs[0], [(xyz, rgb[0] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms], [t[0] for t in input_trans],
-                                  [r[0] for r in input_rot], cfg, scalar_summaries, batch_mode)
-        return [[o] for o in one]
-    if R > ops._lib.GD_MAX_ROOMS:
-        return _over_room_groups(_room_cap_groups(R), part)
-    if any(isinstance(rgb, list) for _, rgb in rooms):
-        # one kind of cloud per chain: a room whose images share its colours holds them I times
-        rooms = [(xyz, rgb if isinstance(rgb, list) else [rgb] * I) for xyz, rgb in rooms]
-        out = _over_color_sets(max(int(xyz.shape[0]) for xyz, _ in rooms), I, lambda i0, i1: omniloc_batch_rooms_images(
-            imgs[i0:i1], [(xyz, rgb[i0:i1]) for xyz, rgb in rooms], [t[i0:i1] for t in input_trans], [r[i0:i1] for r in input_rot], cfg,
-            scalar_summaries, batch_mode), rooms=R)
-        if out is not None:
-            return out
-    flat = _refine_groups(lambda tr, ro: _rooms_images_chain(imgs, rooms, tr, ro, cfg, batch_mode), [t for ts in input_trans for t in ts],
-                          [r for rs in input_rot for r in rs])
-    return [flat[r * I:(r + 1) * I] for r in range(R)]
+    rooms = _check_rooms("omniloc_batch_rooms_images", imgs, rooms, input_trans, input_rot)[3]
+    return _rooms_ladder(imgs, rooms, input_trans, input_rot, cfg, lambda *piece: _plain_leaf(*piece, cfg, scalar_summaries, batch_mode),
+                         scalar_summaries, batch_mode)
 
 
 ROOMS_POLISHED_ROW = POLISHED_ROW + 1      # _winners_polished's row and the chain's own winner loss (a polished row's column 12 is the polish's)
@@ -1332,59 +1390,14 @@ def omniloc_batch_rooms_images_polished(imgs, rooms, input_trans, input_rot, cfg
     _refuse(cfg, who, "robust", "score")
     if _cfg(cfg, "visualize", False):
         raise ValueError("%s does not take cfg.visualize" % who)
-    R, I = len(rooms), len(imgs)
-    if R == 0 or I == 0 or len(input_trans) != R or len(input_rot) != R:
-        raise ValueError("%s: %d rooms, %d images, %d / %d starting-pose sets" % (who, R, I, len(input_trans), len(input_rot)))
-    if any(len(t) != I for t in input_trans) or any(len(r) != I for r in input_rot):
-        raise ValueError("%s: every room needs one starting-pose set per image" % who)
-    B = int(input_trans[0][0].shape[0])
-    if any(int(t.shape[0]) != B for ts in input_trans for t in ts) or any(int(r.shape[0]) != B for rs in input_rot for r in rs):
-        raise ValueError("%s: every room and image needs the same number of starting poses" % who)
-    rooms = [(xyz, shared_rgb(rgb)) for xyz, rgb in rooms]
-    for _, rgb in rooms:
-        if isinstance(rgb, list) and len(rgb) != I:
-            raise ValueError("%s: %d colour sets for %d images" % (who, len(rgb), I))
+    _, _, B, rooms = _check_rooms(who, imgs, rooms, input_trans, input_rot)
     prune_schedule(cfg, B)                                   # (its own refusals, before a device is touched)
     if strict_reference_asserts:
         assert cfg.num_input > 1
-
-    def images(i0, i1):
-        return omniloc_batch_rooms_images_polished(imgs[i0:i1], [(xyz, rgb[i0:i1] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms],
-                                                   [t[i0:i1] for t in input_trans], [r[i0:i1] for r in input_rot], cfg, scalar_summaries)
-
-    def side_by_side(parts):
-        """(out, chain_loss) of runs of images -> of all the images"""
-        return [sum((o[r] for o, _ in parts), []) for r in range(R)], torch.cat([c for _, c in parts], dim=1)
-    if I > 1 and not rooms_images_chain_pays(sum(int(xyz.shape[0]) for xyz, _ in rooms), B):
-        return side_by_side([images(i, i + 1) for i in range(I)])
-    if R > ops._lib.GD_MAX_ROOMS:
-        parts = [(idx, omniloc_batch_rooms_images_polished(imgs, [rooms[r] for r in idx], [input_trans[r] for r in idx], [input_rot[r] for r in idx],
-                                                           cfg, scalar_summaries)) for idx in _room_cap_groups(R)]
-        return sum((o for _, (o, _) in parts), []), torch.cat([c for _, (_, c) in parts], dim=0)
-    if I > 1 and any(isinstance(rgb, list) for _, rgb in rooms):
-        # one kind of cloud per chain: a room whose images share its colours holds them I times
-        rooms = [(xyz, rgb if isinstance(rgb, list) else [rgb] * I) for xyz, rgb in rooms]
-        sizes = color_set_groups(max(int(xyz.shape[0]) for xyz, _ in rooms), I)
-        if len(sizes) > 1:
-            starts = [sum(sizes[:k]) for k in range(len(sizes))]
-            return side_by_side([images(i0, i0 + m) for i0, m in zip(starts, sizes)])
-    if I == 1:
-        rooms = [(xyz, rgb[0] if isinstance(rgb, list) else rgb) for xyz, rgb in rooms]
-    clouds = [packed_cloud_sets(xyz, rgb) if isinstance(rgb, list) else packed_cloud(xyz, rgb) for xyz, rgb in rooms]      # (the chain's own: cached)
-    panos = _chain_panos(imgs, max(int(xyz.shape[0]) for xyz, _ in rooms))
-    host = _refine_groups(lambda tr, ro: _chain("gd_rooms" if I == 1 else "gd_rooms_images", imgs, rooms, tr, ro, cfg, True),
-                          [t for ts in input_trans for t in ts], [r for rs in input_rot for r in rs],
-                          polish=lambda gd, wins: torch.cat([_polished_rows(
-                              wins, gn, want_cov, lambda: ops.pose_information_rooms_at_winners(clouds, panos, wins),
-                              lambda: ops.gauss_newton_refine_rooms_at_winners(clouds, panos, wins, iters=gn[0], **gn[1])), wins[:, 12:13]], dim=1))
-    out = [[] for _ in range(R)]
-    for k, row in enumerate(host):
-        loss = row[14] / row[15] if float(row[13]) != 0.0 else row[12]       # (float32 on the host: one correctly rounded division)
-        entry = [row[0:3].reshape(3, 1).clone(), row[3:12].reshape(3, 3).clone(), loss.clone()]
-        if want_cov:
-            entry.append(row[16:POLISHED_ROW].reshape(6, 6).clone())
-        out[k // I].append(entry)
-    return out, host[:, POLISHED_ROW].reshape(R, I).clone()
+    out = _rooms_ladder(imgs, rooms, input_trans, input_rot, cfg, lambda *piece: _polished_leaf(*piece, cfg, gn, want_cov))
+    # (every entry carries the chain's own winner loss last: taken apart here, after the ladder has stitched the pieces)
+    chain_loss = torch.tensor([[entry.pop() for entry in row] for row in out], dtype=torch.float32)
+    return out, chain_loss
 
 
 def sampling_loss(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, return_list=True, weights=None):

@@ -61,6 +61,23 @@ def test_the_entry_point_refuses_before_it_touches_a_device():
         _polished(_cfg(gn_iters=3, prune_iters=10, prune_keep=5))                      # more than the 4 candidates per image
 
 
+def test_the_plain_chain_refuses_ragged_lists_before_it_touches_a_device():
+    """omniloc_batch_images checks its lists as the robust and polished forms do, with their messages"""
+    from piccolo_amd import omniloc as po
+    for batch_mode in (True, False):
+        with pytest.raises(ValueError, match="omniloc_batch_images: 2 images, 3 / 2 lists of starting poses"):
+            po.omniloc_batch_images([IMG, IMG], Z, Z, [Z.clone() for _ in range(3)], [Z.clone(), Z.clone()], _cfg(), batch_mode=batch_mode)
+        with pytest.raises(ValueError, match="omniloc_batch_images: 2 images, 2 / 1 lists of starting poses"):
+            po.omniloc_batch_images([IMG, IMG], Z, Z, [Z.clone(), Z.clone()], [Z.clone()], _cfg(), batch_mode=batch_mode)
+        with pytest.raises(ValueError, match="omniloc_batch_images: 0 images"):
+            po.omniloc_batch_images([], Z, Z, [], [], _cfg(), batch_mode=batch_mode)
+        with pytest.raises(ValueError, match="omniloc_batch_images: 3 colour sets for 2 images"):
+            po.omniloc_batch_images([IMG, IMG], Z, [Z, Z.clone(), Z.clone()], [Z.clone(), Z.clone()], [Z.clone(), Z.clone()], _cfg(),
+                                    batch_mode=batch_mode)
+    with pytest.raises(ValueError, match="omniloc_batch_images_robust: 2 images, 3 / 2 lists of starting poses"):
+        po.omniloc_batch_images_robust([IMG, IMG], Z, Z, [Z.clone() for _ in range(3)], [Z.clone(), Z.clone()], _cfg(robust_iters=20))
+
+
 def test_the_chains_alone_go_on_refusing_the_keys():
     from piccolo_amd import omniloc as po
     two = ([IMG, IMG], Z, Z, [Z.clone(), Z.clone()], [Z.clone(), Z.clone()])
