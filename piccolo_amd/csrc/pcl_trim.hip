@@ -7,8 +7,11 @@
 // p_x^2 + p_y^2 = q'_x^2 + q'_y^2, so
 //     theta = atan2(rho, p_z + eps)                    does not depend on delta at all (panorama row and its fraction shared),
 //     phi   = atan2(p_y, p_x + eps) = phi0 + delta - eps p_y / rho^2 + O(eps^2 / rho^2),   phi0 = atan2(q'_y, q'_x)
-// (first-order carry of the reference's `x + 1e-6`, utils.py:48-51; eps / rho < 1e-2 for every point farther than 0.1 mm from the
-// camera's vertical axis — waves that hold a nearer point evaluate phi exactly, see `tiny` below).  A block therefore rotates,
+// (first-order carry of the reference's `x + 1e-6`, utils.py:48-51.  The term it drops is (eps / rho)^2 / 2 rad = (eps / rho)^2 / 4 pi
+// turns; it stays below half an ulp of the fp32 column coordinate in turns, 2^-25, for rho^2 >= eps^2 2^25 / 4 pi = 2.7e-6, i.e. from
+// 1.64 mm off the camera's vertical axis — waves that hold a nearer point evaluate phi exactly for those lanes, see `tiny` below.
+// Before, the exact branch ended at 0.1 mm, where the dropped term is 80 x fp32's own error: 1.5e-2 px on a 2048-wide panorama,
+// measured pair by pair in tests/test_trim_points.py)  A block therefore rotates,
 // normalises and takes BOTH atan2s once per point for up to PCL_TRIM_Y yaws of one class and per yaw only computes p_y, shifts
 // the column, gathers and accumulates: 51.5 VALU instructions per point-pose on the reference's grids against 78.5 of the generic
 // forward kernel (profiles/r03/t_trim_bench_*; DESIGN.md §4.6 — with that the kernel is bound by the texture path).
@@ -19,8 +22,13 @@
 // (0, pi, pi) = RZ(pi) (0, 0, 0).  Classes are found ON THE DEVICE from the (R, 3) rotation table (third rows, computed in double,
 // equal to 4e-7 — the table's quarter turns are fp32 roundings of pi/2, pi, ...: as matrices the grid's "equal" rotations differ by
 // 1e-7, which is also how far the fp32 rotation matrix the reference multiplies with is from the ideal one), the class's first rotation
-// supplies the matrix, every member its yaw relative to it (double).  The entry point takes the reference's arguments as they
-// are; pairs come back as the reference's row-major loss_table[i, j] (utils.py:497).
+// supplies the matrix, every member its yaw relative to it (double).  A member whose third row is NOT the first rotation's — a class
+// merged inside the tolerance — is off by a rotation of ~1e-7 rad about a horizontal axis: nothing for the row, but the azimuth of a point
+// at the angle theta from the camera's vertical axis moves by 1e-7 / sin theta, 2e-3 px of a 128-wide panorama at 1e-3 rad.  Such a
+// member carries the first-order correction of its own p_x, p_y: d p = (R_member R_first^T)[0..1][2] q'_z (the other two columns only
+// add the 1e-7 rad that fp32 has anyway), folded into the column like the eps carry for the lanes within 0.1 rad of the axis (a
+// wave-uniform branch); classes of exactly equal (pitch, roll) carry none and keep their instruction stream.  The entry point takes
+// the reference's arguments as they are; pairs come back as the reference's row-major loss_table[i, j] (utils.py:497).
 #include <stdlib.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -39,9 +47,12 @@ struct PclTrimGroup {
     int ny;
     int leader;                           // row of the class's first rotation (its matrix is the slot's pose record)
     float row1[PCL_TRIM_Y][3];            // second row of the member's OWN fp32 rotation matrix (exact sign of p_y at the seam)
-    int pad[2];
+    int corr;                             // 1: a member's third row differs from the first rotation's (merged inside the tolerance)
+    int pad;
+    float cx[PCL_TRIM_Y], cy[PCL_TRIM_Y]; // (R_member R_first^T)[0][2], [1][2]: d p_x = cx q'_z, d p_y = cy q'_z
+    float ca[PCL_TRIM_Y], cb[PCL_TRIM_Y]; // p_x cy - p_y cx = ca q'_x + cb q'_y
 };
-static_assert(sizeof(PclTrimGroup) == 128, "trim group record");
+static_assert(sizeof(PclTrimGroup) == 192, "trim group record");
 
 // blob handed back to the caller: header + PclTrimGroup[R]
 struct PclTrimHeader {
@@ -118,7 +129,7 @@ __global__ void __launch_bounds__(256) pcl_trim_groups_kernel(const float* __res
         const int g = base[l] + pos[r] / PCL_TRIM_Y, y = pos[r] % PCL_TRIM_Y;
         PclTrimGroup* gr = groups + g;
         // the member's yaw relative to the class's first rotation: RZ(delta) = R_member R_leader^T (double)
-        double sd = 0.0, cd = 1.0, t = 0.0;
+        double sd = 0.0, cd = 1.0, t = 0.0, ex = 0.0, ey = 0.0;
         if (l != r) {
             double A[9], B[9];
             pcl_trim_rot_d(rot + 3 * r, A);
@@ -129,9 +140,15 @@ __global__ void __launch_bounds__(256) pcl_trim_groups_kernel(const float* __res
             const double two_pi = 6.283185307179586476925287;
             t = delta / two_pi;
             t -= floor(t);
+            // (equal (pitch, roll): zero up to the rounding of the products, 1e-16)
+            ex = A[0] * B[6] + A[1] * B[7] + A[2] * B[8];
+            ey = A[3] * B[6] + A[4] * B[7] + A[5] * B[8];
+            if (fabs(ex) < 1e-12 && fabs(ey) < 1e-12) ex = ey = 0.0;
         }
         // (what the kernel adds is 0.5 - turns: its column coordinate runs against phi; and it wants -sin, -cos: see there)
         gr->ns[y] = (float)-sd; gr->nc[y] = (float)-cd; gr->turn[y] = (float)(0.5 - t); gr->rot_idx[y] = r;
+        // p_x = cd q'_x - sd q'_y, p_y = sd q'_x + cd q'_y:  p_x ey - p_y ex = (cd ey - sd ex) q'_x - (sd ey + cd ex) q'_y
+        gr->cx[y] = (float)ex; gr->cy[y] = (float)ey; gr->ca[y] = (float)(cd * ey - sd * ex); gr->cb[y] = (float)-(sd * ey + cd * ex);
         {
             float Rm[9];
             pcl_rot_from_ypr(rot[3 * r], rot[3 * r + 1], rot[3 * r + 2], Rm);       // the matrix the generic kernel multiplies with
@@ -144,8 +161,19 @@ __global__ void __launch_bounds__(256) pcl_trim_groups_kernel(const float* __res
             for (int k = gr->ny; k < PCL_TRIM_Y; k++) {
                 gr->ns[k] = 0.f; gr->nc[k] = -1.f; gr->turn[k] = 0.5f; gr->rot_idx[k] = -1;
                 gr->row1[k][0] = 0.f; gr->row1[k][1] = 1.f; gr->row1[k][2] = 0.f;
+                gr->cx[k] = gr->cy[k] = gr->ca[k] = gr->cb[k] = 0.f;
             }
+            gr->pad = 0;
         }
+    }
+    __syncthreads();
+    // corr of a sub-group: does one of its members carry a correction?  (its first member's thread, after all members wrote theirs)
+    for (int r = threadIdx.x; r < R; r += blockDim.x) {
+        if (pos[r] % PCL_TRIM_Y != 0) continue;
+        PclTrimGroup* gr = groups + base[leader[r]] + pos[r] / PCL_TRIM_Y;
+        int any = 0;
+        for (int k = 0; k < PCL_TRIM_Y; k++) any |= gr->cx[k] != 0.f || gr->cy[k] != 0.f;
+        gr->corr = any;
     }
     if (threadIdx.x == 0) {
         hdr->R = R;
@@ -205,6 +233,7 @@ struct PclTrimArgs {
 };
 
 #define PCL_STEP (2 * PCL_BLOCK)
+#define PCL_TRIM_NEAR 1.4707963f    // pi / 2 - 0.1: elevations beyond it are within 0.1 rad of the camera's vertical axis
 
 // PCL_PANO_U8P (include/piccolo_hip.h): RGBA8 with the rows interleaved in pairs.  Round 4: the launch is bound by the texture unit's
 // line rate (one L1 line lookup per cycle per CU, TA busy 0.80 at 167k points, profiles/r04/t_trim_167k_*), and with row-major
@@ -314,6 +343,7 @@ __device__ __forceinline__ void pcl_trim_body(const PclTrimArgs& a)
         return;
     }
     const int ny = gr->ny;
+    const bool corr = gr->corr != 0;
     const PclPoseRec* __restrict__ pose = a.poses + slot;
 
     __amdgpu_buffer_rsrc_t tex = FMT == PCL_PANO_U8P
@@ -373,9 +403,15 @@ __device__ __forceinline__ void pcl_trim_body(const PclTrimArgs& a)
         // -phi0 / 2 pi, and the first-order carry of the reference's p_x + 1e-6:  d phi = -eps p_y / rho^2
         f2 u0 = pcl_atan2_2(qy, qx) * F2(-inv_two_pi);
         f2 nkk = (rinv * rinv) * F2(-1e-6f * inv_two_pi);
-        // a point within 0.1 mm of the camera's vertical axis: the expansion in eps / rho no longer holds — the wave takes
-        // the exact atan2(p_y, p_x + eps) for its lanes that need it (wave-uniform branch, practically never taken)
-        const bool tiny0 = rho2.x < 1e-8f, tiny1 = rho2.y < 1e-8f;
+        // a group with a member of a merged class: d phi = (p_x d p_y - p_y d p_x) / rho^2 with d p = (cx, cy) q'_z, for the lanes within
+        // 0.1 rad of the axis (PCL_TRIM_NEAR; outside, the 1e-7 rad of the grid's quarter turns move the azimuth by at most
+        // 1e-7 / tan 0.1 = 1e-6 rad) — a wave-uniform branch that only tests in the hot path: the lane masks are taken again inside
+        bool any_near = false;
+        if (corr) any_near = __builtin_amdgcn_ballot_w64(fabsf(elev.x) > PCL_TRIM_NEAR || fabsf(elev.y) > PCL_TRIM_NEAR) != 0ull;
+        // a point within 1.64 mm of the camera's vertical axis (rho^2 < 2.7e-6: see the head of this file): the first-order carry is no
+        // longer exact to half an ulp of the column — the wave takes the exact atan2(p_y, p_x + eps) for its lanes that need it
+        // (wave-uniform branch; lanes outside keep the bits of the carry)
+        const bool tiny0 = rho2.x < 2.7e-6f, tiny1 = rho2.y < 2.7e-6f;
         const bool any_tiny = __builtin_amdgcn_ballot_w64(tiny0 || tiny1) != 0ull;
         // phase A for every yaw of the group: column, fractions, gathers issued — phase B samples them.  (All the group's
         // gathers are in flight together: with four panorama regions per block the kernel waits on texels, not on VALU issue —
@@ -387,10 +423,16 @@ __device__ __forceinline__ void pcl_trim_body(const PclTrimArgs& a)
             const float ns = gr->ns[yy], nc = gr->nc[yy], turn = gr->turn[yy];
             f2 npy = pcl_fma2(F2(ns), qx, F2(nc) * qy);                     // -p_y
             f2 u = pcl_fma2(nkk, npy, u0) + F2(turn);                       // 0.5 - phi / 2 pi, before wrapping into [0, 1)
+            if (any_near) {
+                const f2 kz = (rinv * rinv) * qz * F2(-inv_two_pi);
+                f2 uc = pcl_fma2(kz, pcl_fma2(F2(gr->ca[yy]), qx, F2(gr->cb[yy]) * qy), u);
+                u = (f2){fabsf(elev.x) > PCL_TRIM_NEAR ? uc.x : u.x, fabsf(elev.y) > PCL_TRIM_NEAR ? uc.y : u.y};
+            }
             f2 gg = (f2){__builtin_amdgcn_fractf(u.x), __builtin_amdgcn_fractf(u.y)} - F2(0.5f);
             if (any_tiny) {
-                f2 px = pcl_fma2(F2(-nc), qx, F2(ns) * qy);
-                f2 ge = pcl_atan2_2(-npy, px + F2(1e-6f)) * F2(-inv_two_pi);
+                f2 px = pcl_fma2(F2(-nc), qx, F2(ns) * qy), py = -npy;
+                if (corr) { px = pcl_fma2(F2(gr->cx[yy]), qz, px); py = pcl_fma2(F2(gr->cy[yy]), qz, py); }
+                f2 ge = pcl_atan2_2(py, px + F2(1e-6f)) * F2(-inv_two_pi);
                 gg = (f2){tiny0 ? ge.x : gg.x, tiny1 ? ge.y : gg.y};
             }
             // Which END of the panorama a point at phi = +-pi belongs to is decided by the sign of p_y, like atan2 decides it

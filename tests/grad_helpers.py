@@ -298,8 +298,8 @@ def _grid(gxs, gys, rhos):
     return [(a, b, r) for a in gxs for b in gys for r in rhos]
 
 
-def probe_class(name):
-    """-> dict(x (3,), rgb (3,), img (H,W,3) k/255, trans (B,3), rot (B,3)); B is odd for every class (the tests also run B - 1)"""
+def probe_targets(name):
+    """-> dict(x (3,), rgb (3,), img (H,W,3) k/255, targets [(gx, gy, rho)]): where a probe class aims, before any rotation is chosen"""
     H, W = 64, 128
     x, rgb, lev = POINT, np.array([0.3, 0.6, 0.9], np.float32), None
     edge = [0.97, 0.988, 0.992, 0.9985]                      # inside, just inside, just outside, well outside the +-0.99 clip
@@ -342,10 +342,16 @@ def probe_class(name):
         raise KeyError(name)
     if lev is None:
         lev = _levels(H, W, 10)
-    trans, rot = probe_poses(x, tg)
+    return dict(x=x, rgb=rgb, img=lev.astype(np.float32) / 255, targets=tg)
+
+
+def probe_class(name):
+    """-> dict(x (3,), rgb (3,), img (H,W,3) k/255, trans (B,3), rot (B,3)); B is odd for every class (the tests also run B - 1)"""
+    k = probe_targets(name)
+    trans, rot = probe_poses(k["x"], k.pop("targets"))
     if len(trans) % 2 == 0:
         trans, rot = trans[:-1], rot[:-1]
-    return dict(x=x, rgb=rgb, img=lev.astype(np.float32) / 255, trans=trans, rot=rot)
+    return dict(k, trans=trans, rot=rot)
 
 
 PROBES = ("seam", "poles", "border16", "border300", "fractions", "black", "const", "rho", "axis")
