@@ -22,11 +22,12 @@ import torch
 
 from . import data_utils
 from . import dist as pdist
-from . import ops, synth
+from . import cfg_rules, ops, synth
+from .cfg_rules import (dataset_plan, group_size as _group_size, polish_rules as _check_polish_cfg,  # noqa: F401  (the rules' old names here)
+                        robust_rules as _check_robust_cfg, room_polish_rules as _check_room_polish_cfg, score_rules as _check_score_cfg)
 from .color_utils import color_match, color_mod
-from .omniloc import (GN_KEYS, ROBUST_KEYS, SCORE_KEYS, _is_int, _refuse, _refuse_l1, gn_schedule, omniloc_all, omniloc_batch, omniloc_batch_images,
-                      omniloc_batch_images_polished, omniloc_batch_images_robust, omniloc_batch_rooms_images,
-                      omniloc_batch_rooms_images_polished, pose_covariance_flag, robust_schedule, score_weights)
+from .omniloc import (omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_polished, omniloc_batch_images_robust,
+                      omniloc_batch_rooms_images, omniloc_batch_rooms_images_polished, score_weights)
 from .utils import make_input_images, make_input_scored, make_pano, out_of_room, resize_image, write_summaries
 
 
@@ -48,141 +49,16 @@ def preprocess_colors(img, rgb, cfg):
 def refine_image(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=None, weights=None):
     """localize.py:215-233: run the refinement the config asks for and pick the min-loss candidate.
     Returns (t (3,1), R (3,3), loss) as cpu tensors.  weights (not in the reference): (N,) per-point weights of the refinement's loss.
-    cfg.prune_iters / cfg.prune_keep (omniloc.prune_schedule) prune the parallel refinement's candidates on the device; the non-parallel
-    branch returns every candidate and refuses the keys (ValueError), as omniloc_all does.  cfg.robust_iters / robust_kind / robust_k
-    (omniloc.robust_schedule): the parallel branch runs omniloc_batch's robust chain; the non-parallel branch refuses them as well.
-    cfg.pose_covariance (omniloc.pose_covariance_flag): the parallel branch returns (t, R, loss, cov), cov the (6, 6) covariance of
-    (t, yaw, pitch, roll) at the returned pose; the non-parallel branch refuses the key.  cfg.gn_iters / gn_step_cap / gn_lambda /
-    gn_objective / gn_delta (omniloc.gn_schedule): the parallel branch passes them on to omniloc_batch, which polishes its winner; the non-parallel branch refuses
-    them."""
+    The extension keys (cfg_rules' table): the parallel branch is omniloc_batch and takes what it takes — with cfg.pose_covariance the
+    return is (t, R, loss, cov); the non-parallel branch returns every candidate and refuses them all (ValueError), as omniloc_all does."""
     summaries = scalar_summaries if scalar_summaries is not None else {}
-    if getattr(cfg, "parallel", False):
+    if cfg_rules.on(cfg, "parallel"):
         results = [omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)]
     else:
         # the reference loops omniloc() over the starting points (localize.py:219-220); same results, one launch chain
         results = omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, summaries, weights=weights)
     best = min(range(len(results)), key=lambda i: float(results[i][2]))
-    return tuple(results[best][:4]) if getattr(cfg, "pose_covariance", None) else (results[best][0], results[best][1], results[best][2])
-
-
-def _check_robust_cfg(cfg):
-    """Configuration-time refusal of the robust keys where the harness would refine through an entry point that does not take them: several
-    images per launch chain and the room searches (omniloc._refuse is what those entry points would raise, after the first cloud is read).
-    A robust run groups its images with its own key, cfg.robust_images_per_launch (omniloc_batch_images_robust): an int >= 1 that needs
-    cfg.robust_iters and cfg.parallel."""
-    rpl = getattr(cfg, "robust_images_per_launch", None)
-    if rpl is not None:
-        if not _is_int(rpl) or rpl < 1:
-            raise ValueError("cfg.robust_images_per_launch %r: an int >= 1" % (rpl,))
-        if getattr(cfg, "robust_iters", None) is None:
-            raise ValueError("cfg.robust_images_per_launch goes with cfg.robust_iters (images_per_launch groups a plain run)")
-        if not getattr(cfg, "parallel", False):
-            raise ValueError("cfg.robust_images_per_launch needs cfg.parallel (the robust chain has parallel semantics only)")
-    for key in ROBUST_KEYS:
-        if getattr(cfg, key, None) is None:
-            continue
-        if int(getattr(cfg, "images_per_launch", 1)) > 1:
-            raise ValueError("cfg.%s does not combine with images_per_launch > 1 (a robust run groups its images with "
-                             "robust_images_per_launch)" % key)
-        for other in ("room_search", "room_search_images"):
-            if getattr(cfg, other, None):
-                raise ValueError("cfg.%s does not combine with cfg.%s" % (key, other))
-        robust_schedule(cfg)                          # (its own ValueErrors, before any file is read)
-        return
-
-
-def _check_score_cfg(cfg):
-    """Configuration-time rules of the score-weight keys of a known-room dataset loop, before any file is read: cfg.score_weights = True
-    initialises every image with make_input_scored and refines it under omniloc.score_weights of its maps, one image per launch chain;
-    cfg.score_split ([num_split_h >= 3, num_split_w >= 1]: the maps' own split, default the initialisation's), cfg.score_floor (a number
-    in [0, 1), default 0) and cfg.score_min_count (an int >= 1, default 1) go with it.  Not next to images_per_launch > 1, the robust keys,
-    robust_images_per_launch, polish_images_per_launch, room_search, room_search_images or depth_mask.
-    -> None without the keys, else (score_split or None, floor, min_count)"""
-    on = getattr(cfg, "score_weights", None)
-    others = [key for key in SCORE_KEYS[1:] if getattr(cfg, key, None) is not None]
-    if on is None or on is False:
-        if others:
-            raise ValueError("cfg.%s goes with cfg.score_weights = True" % others[0])
-        return None
-    if on is not True:
-        raise ValueError("cfg.score_weights %r: a bool" % (on,))
-    split = getattr(cfg, "score_split", None)
-    if split is not None:
-        if not isinstance(split, (list, tuple)) or len(split) != 2 or not all(_is_int(v) for v in split) or split[0] < 3 or split[1] < 1:
-            raise ValueError("cfg.score_split %r: [num_split_h >= 3, num_split_w >= 1]" % (split,))
-        split = (int(split[0]), int(split[1]))
-    floor = getattr(cfg, "score_floor", None)
-    if floor is not None and (not isinstance(floor, (int, float)) or isinstance(floor, bool) or not 0.0 <= float(floor) < 1.0):
-        raise ValueError("cfg.score_floor %r: a number in [0, 1)" % (floor,))
-    min_count = getattr(cfg, "score_min_count", None)
-    if min_count is not None and (not _is_int(min_count) or min_count < 1):
-        raise ValueError("cfg.score_min_count %r: an int >= 1" % (min_count,))
-    if int(getattr(cfg, "images_per_launch", 1)) > 1:
-        raise ValueError("cfg.score_weights does not combine with images_per_launch > 1 (one image per launch chain)")
-    for other in ROBUST_KEYS + ("robust_images_per_launch", "polish_images_per_launch", "room_search", "room_search_images", "depth_mask"):
-        if getattr(cfg, other, None):
-            raise ValueError("cfg.score_weights does not combine with cfg.%s" % other)
-    return split, 0.0 if floor is None else float(floor), 1 if min_count is None else int(min_count)
-
-
-def _check_polish_cfg(cfg, who):
-    """Configuration-time rules of the polish keys (cfg.gn_iters / gn_step_cap / gn_lambda) and cfg.pose_covariance in a dataset loop, before
-    any file is read.  Without cfg.polish_images_per_launch the loop `who` refuses them, as it always did.  With it — an int >= 1, the group
-    size of a known-room run routed through omniloc_batch_images_polished (a group of one: refine_image) — the run needs cfg.parallel and at
-    least one of those keys, and does not combine with room_search, room_search_images, images_per_launch > 1 or robust_images_per_launch
-    (a robust polished run groups by polish_images_per_launch).  -> the group size, or None without the key"""
-    ppl = getattr(cfg, "polish_images_per_launch", None)
-    if ppl is None:
-        _refuse(cfg, who, "pose_covariance", "gn")
-        return None
-    if not _is_int(ppl) or ppl < 1:
-        raise ValueError("cfg.polish_images_per_launch %r: an int >= 1" % (ppl,))
-    if not getattr(cfg, "parallel", False):
-        raise ValueError("cfg.polish_images_per_launch needs cfg.parallel (the polished chain has parallel semantics only)")
-    if all(getattr(cfg, key, None) is None for key in GN_KEYS) and not getattr(cfg, "pose_covariance", None):
-        raise ValueError("cfg.polish_images_per_launch goes with cfg.gn_iters and / or cfg.pose_covariance (images_per_launch groups a plain run)")
-    for other in ("room_search", "room_search_images", "robust_images_per_launch"):
-        if getattr(cfg, other, None):
-            raise ValueError("cfg.polish_images_per_launch does not combine with cfg.%s" % other)
-    if int(getattr(cfg, "images_per_launch", 1)) > 1:
-        raise ValueError("cfg.polish_images_per_launch does not combine with images_per_launch > 1 (it is the polished run's group size)")
-    gn_schedule(cfg)                                  # (their own ValueErrors, before any file is read)
-    pose_covariance_flag(cfg)
-    return int(ppl)
-
-
-def _check_room_polish_cfg(cfg):
-    """Configuration-time rules of cfg.room_search_polish, before any file is read: True lets a room search (cfg.room_search, with or without
-    cfg.room_search_images) carry the polish keys (cfg.gn_iters / gn_step_cap / gn_lambda) and / or cfg.pose_covariance — every group then goes
-    through omniloc_batch_rooms_images_polished.  It needs cfg.room_search, cfg.parallel (the polished chain has parallel semantics only) and
-    at least one of those keys, and does not combine with cfg.polish_images_per_launch (the known-room loops' key); the schedules' own
-    refusals (a bad gn_iters, cfg.depth_mask) come here too.  -> whether the key is set (without it the loops refuse the keys as before)"""
-    rsp = getattr(cfg, "room_search_polish", None)
-    if rsp is None or rsp is False:
-        return False
-    if rsp is not True:
-        raise ValueError("cfg.room_search_polish %r: a bool" % (rsp,))
-    if not getattr(cfg, "room_search", None):
-        raise ValueError("cfg.room_search_polish goes with cfg.room_search (polish_images_per_launch polishes a known-room run)")
-    if getattr(cfg, "polish_images_per_launch", None) is not None:
-        raise ValueError("cfg.polish_images_per_launch does not combine with cfg.room_search")
-    if not getattr(cfg, "parallel", False):
-        raise ValueError("cfg.room_search_polish needs cfg.parallel (the polished chain has parallel semantics only)")
-    if all(getattr(cfg, key, None) is None for key in GN_KEYS) and not getattr(cfg, "pose_covariance", None):
-        raise ValueError("cfg.room_search_polish goes with cfg.gn_iters and / or cfg.pose_covariance (room_search alone runs the plain search)")
-    _refuse_l1(gn_schedule(cfg), "cfg.room_search_polish")      # (the schedule's own ValueErrors, before any file is read)
-    pose_covariance_flag(cfg)
-    return True
-
-
-def _group_size(cfg):
-    """images per group of the known-room loops: cfg.images_per_launch; under the robust keys cfg.robust_images_per_launch (default 1); with
-    cfg.polish_images_per_launch that (a robust polished run too)"""
-    if getattr(cfg, "polish_images_per_launch", None) is not None:
-        return int(cfg.polish_images_per_launch)
-    if getattr(cfg, "robust_iters", None) is not None:
-        return int(getattr(cfg, "robust_images_per_launch", None) or 1)
-    return int(getattr(cfg, "images_per_launch", 1))
+    return tuple(results[best][:4]) if cfg_rules.on(cfg, "pose_covariance") else (results[best][0], results[best][1], results[best][2])
 
 
 def _make_input_args(cfg, init_dict=None):
@@ -206,21 +82,17 @@ def _images_in_rooms(imgs_init, imgs_main, rooms, cfg, init_dict):
         trs.append([tr for tr, _ in starts])
         ros.append([ro for _, ro in starts])
         prepped.append((xyz, rgb_r))
-    if getattr(cfg, "room_search_polish", None):
+    polished = cfg_rules.on(cfg, "room_search_polish")
+    if polished:
         # the room is decided by the CHAIN's losses — the plain search's, bit for bit —; pose, loss and cov are the found room's polished entry
         res, chain_loss = omniloc_batch_rooms_images_polished(imgs_main, prepped, trs, ros, cfg)
-        out = []
-        for i in range(len(imgs_init)):
-            losses = chain_loss[:, i].clone()
-            k = int(torch.argmin(losses))
-            out.append((k,) + tuple(res[k][i][:3]) + (losses,) + tuple(res[k][i][3:4]))
-        return out
-    res = omniloc_batch_rooms_images(imgs_main, prepped, trs, ros, cfg, batch_mode=bool(getattr(cfg, "parallel", False)))
+    else:
+        res = omniloc_batch_rooms_images(imgs_main, prepped, trs, ros, cfg, batch_mode=cfg_rules.on(cfg, "parallel"))
     out = []
     for i in range(len(imgs_init)):
-        losses = torch.stack([res[r][i][2].reshape(()) for r in range(len(rooms))])
+        losses = chain_loss[:, i].clone() if polished else torch.stack([res[r][i][2].reshape(()) for r in range(len(rooms))])
         k = int(torch.argmin(losses))
-        out.append((k, res[k][i][0], res[k][i][1], res[k][i][2], losses))
+        out.append((k,) + tuple(res[k][i][:3]) + (losses,) + tuple(res[k][i][3:4]))          # (room, t, R, loss, every room's loss[, cov])
     return out
 
 
@@ -260,7 +132,7 @@ def localize_synthetic(cfg, writer=None, log_dir=None):
 
     Query images are sharded over the ranks of an initialised process group (one process per GPU); every rank
     returns the full (num_images, 16) result table [t(3), R(9), loss, t_err, r_err, seconds]."""
-    _refuse(cfg, "localize_synthetic", "pose_covariance", "gn", "score")
+    cfg_rules._refuse(cfg, "localize_synthetic")
     dev = ops.device()
     n = int(getattr(cfg, "num_points", 100_000))
     H, W = int(getattr(cfg, "pano_height", 256)), int(getattr(cfg, "pano_width", 512))
@@ -548,7 +420,7 @@ def _run_dataset(writer, log_dir, filenames, dataset, group_size, csv_name, head
     return table
 
 
-def _localize_known_room(cfg, jobs):
+def _localize_known_room(cfg, plan, jobs):
     """localize_group of the known-room loops (localize.py:199-233): images that share the cloud's POINTS and the image sizes are
     initialised in one set of launches (make_input_images) and refined in one launch chain (omniloc_batch_images) — at the shipped 6
     candidates per image a launch is latency-bound, eight images cost little more than one.  Images whose cloud colours were changed per
@@ -556,13 +428,13 @@ def _localize_known_room(cfg, jobs):
     group's cloud then holds one colour set per image, and every image's results are those of its own one-image calls, bit for bit.  When
     every job shares one rgb tensor it is passed as that tensor (the shared-colour path).  Grouping by colour sets was measured to beat
     one image at a time at the shipped and at the cfg-2 shape (tools/color_sets_bench.py).  One job: make_input_images is
-    make_input, and the refinement is refine_image.  Under cfg.polish_images_per_launch (the gn keys and / or pose_covariance) a group goes
-    through omniloc_batch_images_polished — the plain, robust or pruned chain, then the polish and / or covariance of all winners at once."""
+    make_input, and the refinement is refine_image.  plan.route names a larger group's entry point: "polished" omniloc_batch_images_polished
+    (the plain, robust or pruned chain, then the polish and / or covariance of all winners at once), "robust" omniloc_batch_images_robust;
+    "scored" has groups of one, initialised with make_input_scored and refined under the score weights of their maps."""
     xyz = jobs[0].xyz
     rgb = jobs[0].rgb if all(j.rgb is jobs[0].rgb for j in jobs) else [j.rgb for j in jobs]
-    score = _check_score_cfg(cfg)
-    if score is not None:                                    # (one image per group: _check_score_cfg refused every other group size)
-        (job,), (split, floor, min_count) = jobs, score
+    if plan.route == "scored":                               # (one image per group: the rules refused every other group size)
+        (job,), (split, floor, min_count) = jobs, plan.score
         tr, ro, maps = make_input_scored(job.img_init, xyz, rgb, *_make_input_args(cfg), score_split=split)
         if job.on_start is not None:
             job.on_start(tr, ro)
@@ -573,13 +445,12 @@ def _localize_known_room(cfg, jobs):
             j.on_start(tr, ro)
     if len(jobs) == 1:
         return [refine_image(jobs[0].img_main, xyz, rgb, *starts[0], cfg)]
-    if getattr(cfg, "polish_images_per_launch", None) is not None:      # (the gn keys and / or pose_covariance: the chain, then all winners at once)
-        return [tuple(r) for r in omniloc_batch_images_polished([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts],
-                                                                [ro for _, ro in starts], cfg)]
-    if getattr(cfg, "robust_iters", None) is not None:       # (a group under the robust keys: cfg.robust_images_per_launch, parallel only)
-        return omniloc_batch_images_robust([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg)
-    return omniloc_batch_images([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg,
-                                batch_mode=bool(getattr(cfg, "parallel", False)))
+    chain = ([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg)
+    if plan.route == "polished":                             # (the gn keys and / or pose_covariance: the chain, then all winners at once)
+        return [tuple(r) for r in omniloc_batch_images_polished(*chain)]
+    if plan.route == "robust":                               # (groups of cfg.robust_images_per_launch, parallel only)
+        return omniloc_batch_images_robust(*chain)
+    return omniloc_batch_images(*chain, batch_mode=plan.parallel)
 
 
 SIGMA_HEADER = ["sigma_t (m)", "sigma_r (degrees)"]
@@ -592,35 +463,44 @@ def pose_sigmas(cov):
     return float(np.sqrt(np.trace(cov[:3, :3]))), float(np.degrees(np.sqrt(np.trace(cov[3:, 3:]))))
 
 
-def _run_known_room(cfg, writer, log_dir, filenames, dataset, csv_name, header, row_prefix, success):
-    """_run_dataset of a known-room loop.  With cfg.pose_covariance (a polished run: every result carries cov as its fourth entry) the CSV
-    gains two last columns, sigma_t (m) and sigma_r (degrees) (pose_sigmas; empty where cov is NaN), gathered across the ranks the way the
-    room search's found_room is: every rank notes its own images' values when it reports them, and they travel through the all_gather of
-    the result rows.  Without the key the header and the rows are unchanged."""
-    if not getattr(cfg, "pose_covariance", None):
-        return _run_dataset(writer, log_dir, filenames, dataset, _group_size(cfg), csv_name, header, row_prefix, success)
-    local, every = {}, {}
+class _Columns:
+    """`width` extra float columns per image of a dataset loop, next to its result row: a rank notes an image's values when it reports it,
+    on_gathered sends them through the ranks' all_gather the way the result rows went, and every[k] / cells(k) read image k's out on every
+    rank — NaN (an empty CSV cell) where nothing was noted: a skipped image, or a value that is NaN itself."""
+
+    def __init__(self, width, count):
+        self.width, self.count, self.local = width, count, {}
+        self.every = np.full((count, width), np.nan, dtype=np.float32)
+
+    def note(self, k, values):
+        self.local[k] = values
+
+    def on_gathered(self):
+        rank, world = pdist.world()
+        mine = pdist.shard(self.count, rank, world)
+        rows = torch.full((len(mine), self.width), float("nan"), dtype=torch.float32)
+        for j, k in enumerate(mine):
+            if k in self.local:
+                rows[j] = torch.tensor(self.local[k], dtype=torch.float32)
+        self.every = pdist.gather_rows(rows.to(ops.device()) if torch.cuda.is_available() else rows, self.count, rank, world).cpu().numpy()
+
+    def cells(self, k, first=0):
+        return ["" if np.isnan(v) else float(v) for v in self.every[k][first:]]
+
+
+def _run_known_room(plan, writer, log_dir, filenames, dataset, csv_name, header, row_prefix, success):
+    """_run_dataset of a known-room loop.  With plan.sigmas (cfg.pose_covariance in a polished run: every result carries cov as its fourth
+    entry) the CSV gains two last columns, sigma_t (m) and sigma_r (degrees) (pose_sigmas; empty where cov is NaN), through _Columns."""
+    if not plan.sigmas:
+        return _run_dataset(writer, log_dir, filenames, dataset, plan.group_size, csv_name, header, row_prefix, success)
+    sigmas = _Columns(2, len(filenames))
 
     def report(k, job, result, row):
-        local[k] = pose_sigmas(result[3])
+        sigmas.note(k, pose_sigmas(result[3]))
         dataset.report(k, job, result, row)
 
-    def gather():
-        rank, world = pdist.world()
-        mine = pdist.shard(len(filenames), rank, world)
-        rows = torch.full((len(mine), 2), float("nan"), dtype=torch.float32)
-        for j, k in enumerate(mine):
-            if k in local:
-                rows[j] = torch.tensor(local[k], dtype=torch.float32)
-        table = pdist.gather_rows(rows.to(ops.device()) if torch.cuda.is_available() else rows, len(filenames), rank, world).cpu().numpy()
-        every.clear()
-        every.update({k: table[k] for k in range(len(filenames))})
-
-    def suffix(k):
-        return ["" if np.isnan(v) else float(v) for v in every.get(k, (np.nan, np.nan))]
-
-    return _run_dataset(writer, log_dir, filenames, dataset._replace(report=report), _group_size(cfg), csv_name, header + SIGMA_HEADER, row_prefix,
-                        success, row_suffix=suffix, on_gathered=gather)
+    return _run_dataset(writer, log_dir, filenames, dataset._replace(report=report), plan.group_size, csv_name, header + SIGMA_HEADER, row_prefix,
+                        success, row_suffix=sigmas.cells, on_gathered=sigmas.on_gathered)
 
 
 def _seed_all():
@@ -671,21 +551,12 @@ def stanford_area_rooms(root, area, room_search=True):
 def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford"):
     """Stanford2D-3D-S loop (localize.py:76-297) over `root`/pano/area_*/ *.png, pcd_not_aligned/area_*/<room>.txt and
     pose/area_*/ *.json; writes `stanford_results.csv` with the reference's columns and result images under results/.
-    cfg.images_per_launch is the group size of _run_dataset (_localize_known_room); under cfg.robust_iters it is cfg.robust_images_per_launch.
-    cfg.polish_images_per_launch (_check_polish_cfg): the group size of a run that carries the gn keys and / or cfg.pose_covariance, routed
-    through omniloc_batch_images_polished; with cfg.pose_covariance the CSV gains sigma_t (m) and sigma_r (degrees) (_run_known_room).
-    cfg.score_weights = True (_check_score_cfg; with cfg.score_split / score_floor / score_min_count): every image is initialised with
-    make_input_scored and refined under the score weights of its maps, one image per launch chain.
-    cfg.room_search (True, or a list of room names): localise every image among the rooms of its area (_localize_stanford_rooms); with
-    cfg.room_search_polish = True such a run takes the gn keys and / or cfg.pose_covariance (_check_room_polish_cfg)."""
+    The extension keys — cfg.images_per_launch and its robust_ / polish_ forms, the robust, gn, pose_covariance and score keys, room_search
+    with room_search_images and room_search_polish — are resolved once, before any file is read, into cfg_rules.dataset_plan's route,
+    group size and CSV columns (the rules: cfg_rules' table): a known-room route goes through _run_known_room and _localize_known_room,
+    a room search (cfg.room_search True, or a list of room names) through _localize_stanford_rooms."""
     _require_gravity_aligned(cfg)
-    _check_score_cfg(cfg)
-    _check_robust_cfg(cfg)
-    if not _check_room_polish_cfg(cfg):
-        _check_polish_cfg(cfg, "localize_stanford")
-    room_search = getattr(cfg, "room_search", None)
-    if room_search and int(getattr(cfg, "images_per_launch", 1)) > 1:
-        raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")
+    plan = dataset_plan(cfg, "localize_stanford")
     _seed_all()
     dev = ops.device()
     area_num = getattr(cfg, "area", None)
@@ -702,8 +573,8 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     room_name = getattr(cfg, "room_name", None)
     if room_name is not None:
         filenames = [f for f in filenames if room_name in f]
-    if room_search:
-        return _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
+    if plan.room_search:
+        return _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames)
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
     read_cloud = _cloud_cache(data_utils.read_stanford, getattr(cfg, "sample_rate", 1), dev)
 
@@ -729,29 +600,27 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     def report(k, job, result, row):
         _stanford_report(filenames[k], log_dir, job, job.xyz, job.show_rgb, result, row)
 
-    return _run_known_room(cfg, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
+    return _run_known_room(plan, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, plan, jobs), report),
                            "stanford_results.csv", STANFORD_HEADER, _stanford_row_prefix, stanford_success)
 
 
-def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search):
-    """localize_stanford with cfg.room_search: every image is localised among the rooms of its area (stanford_area_rooms) by
-    localize_in_rooms instead of in the room its file name names.  The skip rule stays on the ground-truth room's cloud (the same images
-    are evaluated as in a known-room run); the CSV gets a last column found_room, LAST_RUN a room_accuracy, and the result image is
-    rendered from the found room's cloud.  Each area's clouds are read once.  cfg.room_search_images = N is the group size of
-    _run_dataset: up to N consecutive non-skipped images of this rank that share area and image sizes are localised by ONE
-    localize_images_in_rooms call (the same results, bit for bit); a group of one goes through localize_in_rooms.
-    With several ranks every rank localises its share of the
-    images and the found rooms are gathered with the result rows (as room indices into the area's sorted listing), so that rank 0 writes
-    found_room and room_accuracy for every image.  With cfg.room_search_polish (_check_room_polish_cfg) every group goes through
-    omniloc_batch_rooms_images_polished (localize_in_rooms); found_room and room_accuracy stay those of the plain search, and with
-    cfg.pose_covariance the CSV ends found_room, sigma_t (m), sigma_r (degrees), gathered across the ranks with the found rooms."""
+def _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames):
+    """localize_stanford on the routes "rooms" / "rooms-polished" (cfg.room_search): every image is localised among the rooms of its area
+    (stanford_area_rooms) by localize_in_rooms instead of in the room its file name names.  The skip rule stays on the ground-truth room's
+    cloud (the same images are evaluated as in a known-room run); the CSV gets a last column found_room, LAST_RUN a room_accuracy, and
+    the result image is rendered from the found room's cloud.  Each area's clouds are read once.  plan.group_size (cfg.room_search_images)
+    = N: up to N consecutive non-skipped images of this rank that share area and image sizes are localised by ONE localize_images_in_rooms
+    call (the same results, bit for bit); a group of one goes through localize_in_rooms.  Every rank localises its share of the images; the
+    found rooms (as indices into the area's sorted listing) and, with plan.sigmas, sigma_t (m) and sigma_r (degrees) — the CSV's last
+    columns after found_room — are gathered with the result rows (_Columns), so that rank 0 writes them and room_accuracy for every image.
+    On "rooms-polished" (cfg.room_search_polish) localize_in_rooms goes through omniloc_batch_rooms_images_polished; found_room and
+    room_accuracy stay those of the plain search."""
     dev = ops.device()
     sample_rate = getattr(cfg, "sample_rate", 1)
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
     init_dict = get_init_dict(cfg)
-    areas, found, found_idx = {}, {}, {}
-    want_sigmas = bool(getattr(cfg, "room_search_polish", None)) and bool(getattr(cfg, "pose_covariance", None))
-    sigmas, every_sigma = {}, {}                      # (this rank's (sigma_t, sigma_r) per image; every rank's after the gather, as _run_known_room's)
+    room_search, areas, found = plan.room_search, {}, {}
+    extra = _Columns(3 if plan.sigmas else 1, len(filenames))      # (the found room's index in the area's sorted listing[, sigma_t, sigma_r])
 
     def read_cloud(area, room):
         return _read_cloud(data_utils.read_stanford, os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, room)), sample_rate, dev)
@@ -789,28 +658,14 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
 
     def report(k, job, result, row):
         name, xyz, rgb = job.rooms[result[3]]
-        found_idx[k] = result[3]
-        if want_sigmas:
-            sigmas[k] = pose_sigmas(result[4])
+        extra.note(k, (float(result[3]),) + (pose_sigmas(result[4]) if plan.sigmas else ()))
         _stanford_report(filenames[k], log_dir, job, xyz, rgb, result, row, "found room : {}\n".format(name))
 
     def gather_found():
-        # this rank's found-room indices (NaN: skipped, or another rank's image) through the same all_gather as the result rows
-        rank, world = pdist.world()
-        mine = pdist.shard(len(filenames), rank, world)
-        local = torch.full((len(mine), 3), float("nan"), dtype=torch.float32, device=dev)
-        for j, k in enumerate(mine):
-            if k in found_idx:
-                local[j, 0] = float(found_idx[k])
-            if k in sigmas:
-                local[j, 1:3] = torch.tensor(sigmas[k], dtype=torch.float32)
-        gathered = pdist.gather_rows(local, len(filenames), rank, world).cpu().numpy()
-        every = gathered[:, 0]
+        extra.on_gathered()
         found.clear()
-        every_sigma.clear()
-        every_sigma.update({k: gathered[k, 1:3] for k in range(len(filenames))})
         listings = {}
-        for k, v in enumerate(every):
+        for k, v in enumerate(extra.every[:, 0]):
             if not np.isnan(v):
                 area, _, gt_room = _stanford_parts(filenames[k])
                 if area not in listings:
@@ -818,14 +673,11 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
                 found[k] = (listings[area][int(v)], gt_room)
 
     def suffix(k):
-        room = [found[k][0] if k in found else ""]
-        if not want_sigmas:
-            return room
-        return room + ["" if np.isnan(v) else float(v) for v in every_sigma.get(k, (np.nan, np.nan))]
+        return [found[k][0] if k in found else ""] + extra.cells(k, 1)
 
     table = _run_dataset(writer, log_dir, filenames, _Dataset(ground_truth, load, localize_group, report),
-                         int(getattr(cfg, "room_search_images", 1)), "stanford_results.csv",
-                         STANFORD_HEADER + ["found_room"] + (SIGMA_HEADER if want_sigmas else []), _stanford_row_prefix, stanford_success,
+                         plan.group_size, "stanford_results.csv",
+                         STANFORD_HEADER + ["found_room"] + (SIGMA_HEADER if plan.sigmas else []), _stanford_row_prefix, stanford_success,
                          row_suffix=suffix, on_gathered=gather_found)
     if LAST_RUN:
         hits = [name == gt for name, gt in found.values()]
@@ -838,12 +690,10 @@ def _localize_stanford_rooms(cfg, writer, log_dir, root, filenames, room_search)
 def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscenes"):
     """OmniScenes loop (localize.py:300-530) over `root`/<split>_pano/<video>/<frame>, pcd/<room>.txt and <split>_pose;
     writes `omniscenes_results.csv`.  Includes the synthetic illumination changes (synth_const / synth_gamma / synth_wb)
-    and the colour preprocessing of the whole image (match_color / sharpen_color).  cfg.images_per_launch is the group size of
-    _run_dataset (_localize_known_room); cfg.polish_images_per_launch, the CSV's sigma columns and cfg.score_weights as in localize_stanford."""
+    and the colour preprocessing of the whole image (match_color / sharpen_color).  The extension keys as in localize_stanford's
+    known-room routes (cfg_rules.dataset_plan; the room-search keys are ignored here)."""
     _require_gravity_aligned(cfg)
-    _check_score_cfg(cfg)
-    _check_robust_cfg(cfg)
-    _check_polish_cfg(cfg, "localize_omniscenes")
+    plan = dataset_plan(cfg, "localize_omniscenes")
     _seed_all()
     dev = ops.device()
     split = getattr(cfg, "split_name", "extreme")
@@ -898,5 +748,5 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
             _save_result_image(os.path.join(log_dir, "results", video, stem + ".png"), job.orig, job.xyz, job.show_rgb, result[0], result[1],
                                (job.img_main.shape[0] // 2, job.img_main.shape[1] // 2))
 
-    return _run_known_room(cfg, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, jobs), report),
+    return _run_known_room(plan, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, plan, jobs), report),
                            "omniscenes_results.csv", OMNISCENES_HEADER, lambda f: ["{}/{}".format(*f.split("/")[-2:])], omniscenes_success)

@@ -17,24 +17,10 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
     (depth_h, depth_w) is the z-buffer's grid (default: by point density, pcl_depth_default — not the panorama's size),
     depth_tau its tolerance (default: the rule's value for the grid), depth_stride = s builds the z-buffer from every s-th
     point of the Morton-ordered cloud (default: pcl_depth_default's choice; every point is still tested against it);
-  * extra, optional cfg keys prune_iters / prune_keep (default absent = reference behaviour): the batch refinements drop all but the best
-    prune_keep candidates of every image after prune_iters iterations, on the device (prune_schedule, csrc/pcl_prune.hip);
-  * extra, optional cfg keys robust_iters / robust_kind / robust_k (default absent = reference behaviour): omniloc_batch re-weights the
-    cloud's points from the residuals of its current best candidate after robust_iters iterations, on the device, and the same optimiser
-    state goes on under the weighted loss (robust_schedule, csrc/pcl_residual.hip); point_residuals / robust_weights give the same per-point
-    quantities to a caller; omniloc_batch_images_robust runs that chain for several query images of one cloud at once, a weight plane per
-    image;
-  * extra, optional cfg key pose_covariance (a bool, default absent = reference behaviour): omniloc_batch appends the 6 x 6 covariance of
-    (t, yaw, pitch, roll) at the pose it returns (pose_covariance_flag, csrc/pcl_info.hip); pose_information / pose_covariance give the
-    information matrix and the covariance at any poses to a caller;
-  * extra, optional cfg keys gn_iters / gn_step_cap / gn_lambda (default absent = reference behaviour): omniloc_batch polishes its winner
-    by a Levenberg-Marquardt chain on the device (gn_schedule, csrc/pcl_gn.hip); omniloc_batch_images_polished does that, and / or the
-    covariance, for all query images of a shared chain at once (pose_information_images / gauss_newton_refine_images give the several-image
-    calls to a caller); cfg gn_objective = "l1" (with gn_delta; default "l2") polishes on the Huber-L1 objective instead, which tends to
-    the sampling loss itself as delta -> 0 (the rooms forms refuse it);
-  * score_maps / score_weights (not in the reference): per-point weights from the histogram stage's patch intersections averaged over
-    candidate poses (csrc/pcl_score.hip), usable as weights=; the cfg keys score_weights / score_split / score_floor / score_min_count
-    belong to the known-room dataset loops (localize._check_score_cfg) — the several-image and rooms entry points here refuse them;
+  * extra, optional cfg keys, all absent by default = reference behaviour, ruled by cfg_rules (its table: what goes with what, which entry
+    point takes which family) and described at their sections below: prune_iters / prune_keep, robust_iters / robust_kind / robust_k,
+    pose_covariance, gn_iters / gn_step_cap / gn_lambda / gn_objective / gn_delta; the score keys belong to the known-room dataset loops —
+    here score_maps / score_weights give a caller the weights for weights=;
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
     per iteration) as 4th element.
@@ -47,6 +33,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .cfg_rules import (GN_KEYS, ROBUST_KEYS, SCORE_KEYS, _EXTENSIONS, _cfg, _refuse, _refuse_l1,  # noqa: F401  (re-exported)
+                        gn_schedule, pose_covariance_flag, prune_schedule, robust_schedule)
 
 strict_reference_asserts = True
 
@@ -234,61 +222,6 @@ def _side_by_side(sizes, part, rooms=None):
     return out
 
 
-def _cfg(cfg, key, default):
-    return getattr(cfg, key, default)
-
-
-# The cfg keys that are not the reference's, by family: (its keys, how a refusal names them — None: the first key it finds, what does take
-# them).  An entry point refuses the families it does not take with one _refuse call; the schedules below validate the ones it does.
-ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
-GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda", "gn_objective", "gn_delta")
-SCORE_KEYS = ("score_weights", "score_split", "score_floor", "score_min_count")
-_EXTENSIONS = {
-    "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
-    "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust, omniloc_batch_images_polished and localize.refine_image's parallel "
-                                  "branch do"),
-    "pose_covariance": (("pose_covariance",), None, "omniloc_batch, omniloc_batch_images_polished, omniloc_batch_rooms_images_polished and "
-                                                    "localize.refine_image's parallel branch do; the dataset loops with "
-                                                    "cfg.polish_images_per_launch, a room search with cfg.room_search_polish"),
-    "gn": (GN_KEYS, None, "omniloc_batch, omniloc_batch_images_polished, omniloc_batch_rooms_images_polished and localize.refine_image's parallel "
-                          "branch do; the dataset loops with cfg.polish_images_per_launch, a room search with cfg.room_search_polish"),
-    "score": (SCORE_KEYS, None, "the known-room dataset loops do, one image per launch chain; elsewhere pass weights=score_weights(score_maps(...))"),
-}
-
-
-def _refuse(cfg, who, *families):
-    """`who` returns every candidate, records frames, or runs a chain without the robust plane, the covariance or the polish: it refuses the
-    keys of those `families`, in the order given"""
-    for keys, named, takers in map(_EXTENSIONS.get, families):
-        for key in keys:
-            if _cfg(cfg, key, None) is not None:
-                raise ValueError("%s does not take cfg.%s (%s)" % (who, named or key, takers))
-
-
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
-def _int_list(cfg, name):
-    """cfg.`name`, an int or a list of ints, as a list"""
-    v = _cfg(cfg, name, None)
-    v = list(v) if isinstance(v, (list, tuple)) else [v]
-    if not v or not all(_is_int(x) for x in v):
-        raise ValueError("cfg.%s: an int or a list of ints, got %r" % (name, v))
-    return v
-
-
-def _inside_num_iter(iters, name, num_iter):
-    if any(not 0 < i < num_iter for i in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
-        raise ValueError("cfg.%s %r: strictly increasing iteration counts inside (0, %d)" % (name, iters, num_iter))
-
-
-def _positive(v, name):
-    if not isinstance(v, (int, float)) or isinstance(v, bool) or not (0.0 < float(v) < float("inf")):
-        raise ValueError("cfg.%s %r: a positive finite number" % (name, v))
-    return float(v)
-
-
 def _rot_matrix(ypr):
     return ops.rot_from_ypr(ypr.reshape(1, 3))[0]
 
@@ -353,70 +286,13 @@ def _cached_engine(kind, xyzs, sub, make, clouds, boxes):
     return gd, fresh
 
 
-# ------------------------------------------------------------------------------------------------ pruned chains
-# cfg prune_iters / prune_keep (not in the reference; absent by default): after prune_iters[j] iterations in all, every image — every
-# (room, image) of a rooms chain — keeps its prune_keep[j] best candidates by the loss of that iteration's forward (history row
-# prune_iters[j] - 1) and the chain goes on with them alone: pcl_gd_prune hands their complete optimiser state to a smaller engine on the
-# device, so nothing is re-initialised and nothing waits for the host.  The reference refines every one of its num_input candidates to
-# the end; which schedule still finds its winner is the user's choice (DESIGN.md §4.6f has the CPU evidence for 16 -> 8 -> 4).
-def prune_schedule(cfg, per_image):
-    """The segments [(iterations, candidates per image), ...] of a refinement of `per_image` candidates per image under cfg.prune_iters /
-    cfg.prune_keep (an int each, or lists of equal length), or None when the keys are absent.  prune_iters = 20, 40 with prune_keep = 16, 8
-    at num_iter 100 and 32 candidates: [(20, 32), (20, 16), (60, 8)].  ValueError: one key without the other, unequal lengths, iterations
-    not strictly increasing inside (0, num_iter), prune_keep not non-increasing or outside 1 .. min(per_image, PCL_GD_PRUNE_MAX), more than
-    PCL_GD_PRUNE_MAX candidates per image.  Host only."""
-    iters, keep = _cfg(cfg, "prune_iters", None), _cfg(cfg, "prune_keep", None)
-    if iters is None and keep is None:
-        return None
-    if iters is None or keep is None:
-        raise ValueError("cfg.prune_iters and cfg.prune_keep go together")
-    iters, keep = _int_list(cfg, "prune_iters"), _int_list(cfg, "prune_keep")
-    num_iter, per_image = int(_cfg(cfg, "num_iter", 100)), int(per_image)
-    if len(iters) != len(keep):
-        raise ValueError("cfg.prune_iters has %d entries, cfg.prune_keep %d" % (len(iters), len(keep)))
-    _inside_num_iter(iters, "prune_iters", num_iter)
-    cap = ops._lib.GD_PRUNE_MAX
-    if per_image > cap:
-        raise ValueError("pruning takes at most %d candidates per image, got %d" % (cap, per_image))
-    if any(not 1 <= k <= per_image for k in keep) or any(b > a for a, b in zip(keep, keep[1:])):
-        raise ValueError("cfg.prune_keep %r: non-increasing counts in 1 .. %d" % (keep, per_image))
-    ends, counts = iters + [num_iter], [per_image] + keep
-    return [(e - b, c) for b, e, c in zip([0] + iters, ends, counts)]
-
-
 # ------------------------------------------------------------------------------------------------ robust chains
 # cfg robust_iters / robust_kind / robust_k (not in the reference; absent by default): a built-in source of per-point weights for a scene
 # that changed since the cloud was scanned.  After robust_iters[j] iterations in all the chain takes the candidate pcl_gd_winner names, the
 # per-point residuals at its pose (pcl_point_residuals), their lower median s, and weighs every point l <= k s ? 1 : 0 ("trunc") or
 # l <= k s ? 1 : k s / l ("huber"); the SAME optimiser state goes on under pcl_gd_run_weighted.  Nothing waits for the host.  The returned
 # loss is the WEIGHTED loss of the last forward; Adam's moments and the plateau scheduler carry on across the switch, so the scheduler's
-# `best` then compares weighted with unweighted losses — it is not reset.  One cloud, one colour set, one image, no depth mask.
-# Several images of one cloud: omniloc_batch_images_robust — one chain, one weight plane per image, every image its own winner, residuals and
-# scale; shared colours or per-image colour sets; image i's result is its own robust omniloc_batch call's, bit for bit.
-def robust_schedule(cfg):
-    """(robust_iters as a list, kind, k) of a refinement under cfg.robust_iters (an int, or a strictly increasing list inside (0, num_iter)),
-    cfg.robust_kind ("trunc", the default, or "huber") and cfg.robust_k (default 2.5), or None when the keys are absent.  The chain's
-    segments end at robust_iters + [num_iter]: robust_iters = [4, 8] at num_iter 12 runs 4 unweighted, 4 and 4 weighted iterations.
-    ValueError: robust_kind / robust_k without robust_iters, entries that are not ints, iterations not strictly increasing inside
-    (0, num_iter), an unknown kind, k not a positive finite number; the depth mask or the prune keys next to them.  Host only."""
-    iters, kind, k = (_cfg(cfg, key, None) for key in ROBUST_KEYS)
-    if iters is None and kind is None and k is None:
-        return None
-    if iters is None:
-        raise ValueError("cfg.%s goes with cfg.robust_iters" % ("robust_kind" if kind is not None else "robust_k"))
-    iters = _int_list(cfg, "robust_iters")
-    _inside_num_iter(iters, "robust_iters", int(_cfg(cfg, "num_iter", 100)))
-    kind = "trunc" if kind is None else kind
-    if kind not in ops.ROBUST_KINDS:
-        raise ValueError("cfg.robust_kind %r: one of %s" % (kind, sorted(ops.ROBUST_KINDS)))
-    k = _positive(2.5 if k is None else k, "robust_k")
-    if bool(_cfg(cfg, "depth_mask", False)):
-        raise ValueError("cfg.robust_iters does not combine with cfg.depth_mask")
-    if _cfg(cfg, "prune_iters", None) is not None or _cfg(cfg, "prune_keep", None) is not None:
-        raise ValueError("cfg.robust_iters does not combine with cfg.prune_iters / cfg.prune_keep")
-    return iters, kind, k
-
-
+# `best` then compares weighted with unweighted losses — it is not reset.  Several images of one cloud: omniloc_batch_images_robust.
 def point_residuals(img, xyz, rgb, trans, rot):
     """(B, N) GPU tensor, in the order of xyz's rows: per point the ||c - rgb|| the sampling loss sums at the poses trans / rot ((B, 3)
     tensors: translation; yaw, pitch, roll) where its mask keeps the point, exactly -1 where the point samples exact black
@@ -467,82 +343,17 @@ def score_weights(maps, floor=0.0, min_count=1):
 # ------------------------------------------------------------------------------------------------ pose information / covariance
 # (not in the reference; build-defined, include/piccolo_hip.h): how well the panorama constrains a pose — the Gauss-Newton information
 # matrix H = sum w m j j^T of theta = (t, yaw, pitch, roll) and cov = sigma^2 H^-1 with sigma^2 = sum w m l^2 / sum w m.  cfg
-# pose_covariance (a bool, absent by default): omniloc_batch returns [t, R, loss, cov], cov (6, 6) on the CPU, taken at the pose it returns
-# under the weights its last forward ran with (the caller's weights=, the robust chain's last plane, else none).  One cloud, one colour
-# set, one image, no depth mask; nothing is claimed about its calibration on real data.
-def pose_covariance_flag(cfg):
-    """cfg.pose_covariance as a bool (absent or None: False).  ValueError: a value that is not a bool, cfg.depth_mask next to it.  Host only."""
-    v = _cfg(cfg, "pose_covariance", None)
-    if v is None:
-        return False
-    if not isinstance(v, bool):
-        raise ValueError("cfg.pose_covariance %r: a bool" % (v,))
-    if v and bool(_cfg(cfg, "depth_mask", False)):
-        raise ValueError("cfg.pose_covariance does not combine with cfg.depth_mask")
-    return v
-
+# pose_covariance (a bool, absent by default): omniloc_batch returns [t, R, loss, cov] under the weights its last forward ran with.  One
+# cloud, one colour set, one image, no depth mask; nothing is claimed about its calibration on real data.
 
 # ------------------------------------------------------------------------------------------------ Levenberg-Marquardt polish
 # (not in the reference; build-defined, include/piccolo_hip.h, DESIGN.md section 4.1f): a damped Gauss-Newton chain on H and b, wholly on
 # the device.  It minimises the MEAN SQUARED residual sigma^2 = sum w m l^2 / sum w m — not the sampling loss sum w m l / sum w m the GD
 # chains minimise: same per-point terms, mask and weights, another objective.  cfg gn_iters (an int >= 1, absent by default), gn_step_cap
 # and gn_lambda (optional: the step cap in metres / radians and the starting damping): omniloc_batch polishes its winner.  One cloud, one
-# colour set, one image, no depth mask; nothing is claimed about real data.
-# cfg gn_objective ("l2", the default, or "l1") and gn_delta (with "l1" only; ops.GN_L1_DELTA = 1 / 64 when absent): "l1" polishes on the
-# Huber-L1 objective sum w m rho(l) / sum w m, which tends to the sampling loss itself as delta -> 0 (DESIGN.md section 4.1i), re-weighting
-# inside the chain.  Off by default.  The rooms forms refuse "l1".
-def gn_schedule(cfg):
-    """(iters, keyword dict for ops.gauss_newton_refine) under cfg.gn_iters / gn_step_cap / gn_lambda / gn_objective / gn_delta, or None when
-    the keys are absent.  Without gn_objective, or with "l2", the dict holds hyper-parameters alone, as before the key; with "l1" it gains
-    objective="l1" (and delta= when cfg.gn_delta is given).
-    ValueError: gn_step_cap / gn_lambda / gn_objective / gn_delta without gn_iters, gn_iters not an int in 1 .. 1000, a cap or damping that
-    is not a positive finite number, a gn_objective that is neither "l2" nor "l1", gn_delta without gn_objective = "l1", a gn_delta that is
-    not a positive finite number inside [2^-20, 4], cfg.depth_mask next to them.  Host only."""
-    iters, cap, lam, objective, delta = (_cfg(cfg, key, None) for key in GN_KEYS)
-    if iters is None and cap is None and lam is None and objective is None and delta is None:
-        return None
-    if objective is not None and (not isinstance(objective, str) or objective not in ops.GN_OBJECTIVES):
-        raise ValueError("cfg.gn_objective %r: one of %s" % (objective, list(ops.GN_OBJECTIVES)))
-    if iters is None:
-        raise ValueError("cfg.%s goes with cfg.gn_iters" % next(key for key, v in zip(GN_KEYS[1:], (cap, lam, objective, delta)) if v is not None))
-    if delta is not None:
-        if objective != "l1":
-            raise ValueError('cfg.gn_delta goes with cfg.gn_objective = "l1"')
-        delta = _positive(delta, "gn_delta")
-        try:
-            ops.gn_objective("cfg.gn_delta", "l1", delta)
-        except ValueError as e:
-            raise ValueError("cfg.gn_delta: %s" % e) from None
-    if not _is_int(iters) or not 1 <= iters <= ops.GN_MAX_ITERS:
-        raise ValueError("cfg.gn_iters %r: an int in 1 .. %d" % (iters, ops.GN_MAX_ITERS))
-    hyper = {}
-    for key, name, v in (("gn_step_cap", "step_cap", cap), ("gn_lambda", "lam0", lam)):
-        if v is not None:
-            hyper[name] = _positive(v, key)
-    try:
-        ops.gn_hyper("cfg.gn_step_cap / cfg.gn_lambda", **hyper)          # (what float32 makes of them)
-    except ValueError as e:
-        raise ValueError("cfg.gn_step_cap / cfg.gn_lambda: %s" % e) from None
-    if bool(_cfg(cfg, "depth_mask", False)):
-        raise ValueError("cfg.gn_iters does not combine with cfg.depth_mask")
-    if objective == "l1":
-        hyper["objective"] = "l1"
-        if delta is not None:
-            hyper["delta"] = delta
-    return iters, hyper
-
-
-def _gn_is_l1(gn):
-    return gn is not None and gn[1].get("objective") == "l1"
-
-
-def _refuse_l1(gn, who):
-    """the rooms forms have no L1 twin"""
-    if _gn_is_l1(gn):
-        raise ValueError('%s does not take cfg.gn_objective = "l1" (the rooms polish has no L1 form; omniloc_batch and '
-                         'omniloc_batch_images_polished do)' % who)
-
-
+# colour set, one image, no depth mask; nothing is claimed about real data.  cfg gn_objective = "l1" (gn_delta: ops.GN_L1_DELTA = 1 / 64 when
+# absent) polishes on the Huber-L1 objective sum w m rho(l) / sum w m instead, which tends to the sampling loss itself as delta -> 0
+# (DESIGN.md section 4.1i), re-weighting inside the chain.  The rooms forms refuse it.
 def gauss_newton_refine(img, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, objective="l2", delta=None, **hyper):
     """ops.gauss_newton_refine from the poses trans / rot ((B, 3) tensors: translation; yaw, pitch, roll) over the cached packed cloud and
     panorama: a dict of GPU tensors (trans, rot, sigma2_start, sigma2, lam, accepted, rejected, evaluations, status, H, b, stats, cov, and
@@ -686,6 +497,12 @@ def _winner_polish(gd, cloud, pano, win, gn, want_cov=False):
     return torch.where(took, torch.cat([res["trans"], R, loss], dim=1), win[:, 0:13])[0], cov
 
 
+# ------------------------------------------------------------------------------------------------ pruned chains
+# cfg prune_iters / prune_keep (not in the reference; absent by default): after prune_iters[j] iterations in all, every image — every
+# (room, image) of a rooms chain — keeps its prune_keep[j] best candidates by the loss of that iteration's forward (history row
+# prune_iters[j] - 1) and the chain goes on with them alone: pcl_gd_prune hands their complete optimiser state to a smaller engine on the
+# device, so nothing is re-initialised and nothing waits for the host.  The reference refines every one of its num_input candidates to
+# the end; which schedule still finds its winner is the user's choice (DESIGN.md §4.6f has the CPU evidence for 16 -> 8 -> 4).
 class _PrunedChain:
     """What a pruned refinement hands back in place of its engine: winners() of the LAST segment's engine, and every candidate's leaf row
     written back to the caller's buffers — a dropped candidate's from the prune call that dropped it (its pose at that time), a
@@ -892,7 +709,7 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     (omniloc.py:46,102).  Row `starting_point` of input_trans / input_rot ends up holding the final pose, as in the
     reference where the optimised tensors are views of those rows (omniloc.py:15-19).
     """
-    _refuse(cfg, "omniloc", "prune", "robust", "pose_covariance", "gn")
+    _refuse(cfg, "omniloc")
     vis = _cfg(cfg, "visualize", False)
     out_quantile = _cfg(cfg, "out_of_room_quantile", 0.05)
 
@@ -945,7 +762,7 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     `for i in range(num_input): omniloc(..., i, ...)` (localize.py:219-220), for ALL starting points in one launch chain.
     Every starting point keeps omniloc's SEQUENTIAL semantics (its own Adam / scheduler, clamp applied to the parameters
     the next forward reads) and the points never interact, so the list returned equals the K separate calls."""
-    _refuse(cfg, "omniloc_all", "prune", "robust", "pose_covariance", "gn")
+    _refuse(cfg, "omniloc_all")
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False, weights=weights).result()
     K = res.shape[0]
@@ -961,17 +778,16 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     """Parallel refinement of all starting poses; returns [t (3,1), R (3,3), loss ()] of the candidate whose LAST
     forward had the smallest loss (omniloc.py:271).  Keeps the reference's clamp lag (omniloc.py:260-269): the
     returned translation is the post-step, pre-clamp value (omniloc.py:272).
-    cfg.robust_iters / robust_kind / robust_k (robust_schedule; not in the reference): the robust chain — the returned loss is then the
-    WEIGHTED loss of the last forward, the return shapes are unchanged.  Not with weights=, cfg.depth_mask or the prune keys (ValueError).
-    cfg.pose_covariance (a bool; not in the reference): a fourth entry, cov (6, 6) on the CPU — sigma^2 H^-1 of (t, yaw, pitch, roll) at the
-    returned pose (pose_information), under weights= or the robust chain's last plane; the first three entries are those of the run
-    without the key, bit for bit.  With the prune keys too; not with cfg.depth_mask or a list of colour sets (ValueError).
-    cfg.gn_iters / gn_step_cap / gn_lambda (gn_schedule; not in the reference): after the chain its winner is polished on the device by
-    gn_iters Levenberg-Marquardt iterations on the MEAN SQUARED residual (gauss_newton_refine: not the sampling loss), under weights= or the
-    robust chain's last plane.  Where the polish accepted a step (accepted > 1, status 0 or 3) t is the polished translation, R
-    rot_from_ypr of the polished angles and loss the sampling loss re-evaluated at that pose; otherwise the three entries are the
-    chain's own, bit for bit.  With cfg.pose_covariance the fourth entry is the polish's own cov at its returned pose.  The written-back
-    leaves stay the chain's.  With the prune keys too; not with cfg.depth_mask or a list of colour sets (ValueError).
+    The keys that are not the reference's (what each stands next to: cfg_rules' table; neither of the last two takes a list of colour sets):
+    cfg.robust_iters / robust_kind / robust_k (robust_schedule): the robust chain — the returned loss is then the WEIGHTED loss of the last
+    forward, the return shapes are unchanged.
+    cfg.pose_covariance (a bool): a fourth entry, cov (6, 6) on the CPU — sigma^2 H^-1 of (t, yaw, pitch, roll) at the returned pose
+    (pose_information), under weights= or the robust chain's last plane; the first three entries are the run's without the key, bit for bit.
+    cfg.gn_iters / gn_step_cap / gn_lambda (gn_schedule): after the chain its winner is polished on the device by gn_iters Levenberg-
+    Marquardt iterations on the MEAN SQUARED residual (gauss_newton_refine: not the sampling loss), under weights= or the robust chain's
+    last plane.  Where the polish accepted a step (accepted > 1, status 0 or 3) t is the polished translation, R rot_from_ypr of the
+    polished angles and loss the sampling loss re-evaluated at that pose; otherwise the three entries are the chain's own, bit for bit.
+    With cfg.pose_covariance the fourth entry is the polish's own cov at its returned pose.  The written-back leaves stay the chain's.
     cfg.gn_objective = "l1" (and cfg.gn_delta; gn_schedule): the polish minimises the Huber-L1 objective sum w m rho(l) / sum w m instead —
     for small delta the sampling loss itself —, with the same rules for the three entries; the fourth entry is then pose_information's
     cov at the RETURNED pose, from one plain pass after the polish (omniloc.pose_covariance's bits there)."""
@@ -1078,7 +894,7 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     beyond the colour-set addressing limit go in further groups.  With the depth mask the colour-set chain is the depth chain
     (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image.
     ValueError, before a device is touched: lists of different lengths, a colour-set count that is not the image count."""
-    _refuse(cfg, "omniloc_batch_images", "robust", "pose_covariance", "gn", "score")
+    _refuse(cfg, "omniloc_batch_images")
     return _images_ladder("omniloc_batch_images", imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries, batch_mode, direct=True)
 
 
@@ -1090,9 +906,8 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
     panorama (and colours), their lower median, and re-weights that image's plane — eight launches for all the images, nothing waits for the
     host.  The chain runs the single-image plan, with shared colours too, so entry i equals omniloc_batch(imgs[i], xyz, rgb_i, ...) under the
     same cfg bit for bit; every loss is the WEIGHTED loss of the last forward.  Parallel semantics only.  ValueError: cfg without
-    robust_iters (and robust_schedule's refusals: the depth mask, the prune keys), cfg.visualize, lists of different lengths.  One image is
-    omniloc_batch."""
-    _refuse(cfg, "omniloc_batch_images_robust", "pose_covariance", "gn", "score")
+    robust_iters (and cfg_rules' refusals), cfg.visualize, lists of different lengths.  One image is omniloc_batch."""
+    _refuse(cfg, "omniloc_batch_images_robust")
     robust = robust_schedule(cfg)
     if robust is None:
         raise ValueError("omniloc_batch_images_robust needs cfg.robust_iters (omniloc_batch_images runs the plain chain)")
@@ -1117,10 +932,9 @@ def omniloc_batch_images_polished(imgs, xyz, rgb, input_trans_list, input_rot_li
     float32(S1) / float32(M) of the polish's info record at the returned pose: the weighted sampling loss sum w m l / sum w m from the
     pass's own sums — NOT the separate forward-only launch omniloc_batch re-evaluates it with (there is none for a colour set or a
     per-image plane), so that one number differs from omniloc_batch's by the summation order.
-    Parallel semantics only.  ValueError, before a device is touched: a cfg with neither the gn keys nor pose_covariance (omniloc_batch_images
-    / omniloc_batch_images_robust run the chains alone), cfg.depth_mask (gn_schedule / pose_covariance_flag), cfg.visualize, lists of
-    different lengths, a colour-set count that is not the image count.  One image is omniloc_batch; images beyond the colour-set addressing
-    limit go in further groups.
+    Parallel semantics only.  ValueError, before a device is touched: a cfg with neither the gn keys nor pose_covariance (and cfg_rules'
+    refusals), cfg.visualize, lists of different lengths, a colour-set count that is not the image count.  One image is omniloc_batch;
+    images beyond the colour-set addressing limit go in further groups.
     cfg.gn_objective = "l1" (and cfg.gn_delta): ONE L1 chain over all winners (gauss_newton_refine_images_at_winners(objective="l1")); a
     polished entry's loss stays float32(S1) / float32(M) of the polish's record — S1 and M are plain there, and the sampling loss is now
     what the polish works on —, and cov comes from one plain pose_information_images call at the returned poses."""
@@ -1130,7 +944,7 @@ def omniloc_batch_images_polished(imgs, xyz, rgb, input_trans_list, input_rot_li
         raise ValueError("%s needs cfg.gn_iters or cfg.pose_covariance (omniloc_batch_images / omniloc_batch_images_robust run the chain alone)" % who)
     if _cfg(cfg, "visualize", False):
         raise ValueError("%s does not take cfg.visualize" % who)
-    _refuse(cfg, who, "score")
+    _refuse(cfg, who)
     return _images_ladder(who, imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries, forward_one=True,
                           weight_sets=robust_schedule(cfg) is not None, polish=(gn, want_cov))
 
@@ -1198,7 +1012,7 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     each room's candidates).  More than PCL_GD_MAX_ROOMS rooms go in several chains.  With the depth mask the chain is the depth chain
     (pcl_gd_run_depth_chain: every room on its own z-buffer grid, the same bits per room); rooms whose tolerances differ (depth_tau_groups)
     go in a chain per tolerance."""
-    _refuse(cfg, "omniloc_batch_rooms", "robust", "pose_covariance", "gn", "score")
+    _refuse(cfg, "omniloc_batch_rooms")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R = len(rooms)
@@ -1355,7 +1169,7 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     the depth chain (pcl_gd_run_depth_chain) under the same rules; rooms whose tolerances differ (depth_tau_groups) go in a chain per
     tolerance, and images that share the rooms' colours run omniloc_batch_images per room where that is faster (depth_shared_chain_pays:
     its plan of all the images' candidates, so equal to the single calls up to the summation order of the partial sums, as there)."""
-    _refuse(cfg, "omniloc_batch_rooms_images", "robust", "pose_covariance", "gn", "score")
+    _refuse(cfg, "omniloc_batch_rooms_images")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     rooms = _check_rooms("omniloc_batch_rooms_images", imgs, rooms, input_trans, input_rot)[3]
@@ -1378,8 +1192,7 @@ def omniloc_batch_rooms_images_polished(imgs, rooms, input_trans, input_rot, cfg
     a step (accepted > 1, status 0 or 3), else the chain's — omniloc_batch_images_polished's rule.
     omniloc_batch_rooms_images' fallbacks apply: more than PCL_GD_MAX_ROOMS rooms, images beyond the colour-set limit and chains too large
     to gain from sharing go in several chains, each polished by itself; one image runs the one-image rooms chain.
-    ValueError, before a device is touched: a cfg with neither the gn keys nor pose_covariance, cfg.depth_mask, the robust keys,
-    cfg.visualize, ragged lists."""
+    ValueError, before a device is touched: a cfg with neither the gn keys nor pose_covariance (and cfg_rules' refusals), ragged lists."""
     who = "omniloc_batch_rooms_images_polished"
     gn, want_cov = gn_schedule(cfg), pose_covariance_flag(cfg)
     _refuse_l1(gn, who)
@@ -1387,7 +1200,7 @@ def omniloc_batch_rooms_images_polished(imgs, rooms, input_trans, input_rot, cfg
         raise ValueError("%s needs cfg.gn_iters or cfg.pose_covariance (omniloc_batch_rooms_images runs the chain alone)" % who)
     if bool(_cfg(cfg, "depth_mask", False)):
         raise ValueError("%s does not combine with cfg.depth_mask" % who)
-    _refuse(cfg, who, "robust", "score")
+    _refuse(cfg, who)
     if _cfg(cfg, "visualize", False):
         raise ValueError("%s does not take cfg.visualize" % who)
     _, _, B, rooms = _check_rooms(who, imgs, rooms, input_trans, input_rot)

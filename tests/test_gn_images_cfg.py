@@ -189,7 +189,9 @@ def test_the_csv_header_with_and_without_pose_covariance(tmp_path, want_cov):
     dataset = localize._Dataset(lambda k: (np.full(3, k, np.float32), np.eye(3, dtype=np.float32), k == 1), lambda k: _FakeJob(k), localize_group,
                                 lambda k, job, result, row: reported.append(k))
     cfg = _cfg(gn_iters=3, polish_images_per_launch=2, **HARNESS, **({"pose_covariance": True} if want_cov else {}))
-    table = localize._run_known_room(cfg, None, str(tmp_path), files, dataset, "fake.csv", header, lambda f: [f], localize.stanford_success)
+    plan = localize.dataset_plan(cfg, "localize_stanford")
+    assert plan.route == "polished" and plan.group_size == 2 and plan.sigmas is want_cov
+    table = localize._run_known_room(plan, None, str(tmp_path), files, dataset, "fake.csv", header, lambda f: [f], localize.stanford_success)
     assert groups == [[0, 2], [3, 4]] and reported == [0, 2, 3, 4] and tuple(table.shape) == (n, 16)
     with open(tmp_path / "fake.csv") as f:
         rows = list(csv.reader(f))
