@@ -770,6 +770,43 @@ int pcl_depth_default(int64_t n, int H, int W, int stride_in, int *depth_h_host,
 size_t pcl_depth_workspace_bytes(int B, int H, int W);
 int pcl_depth_mask(const float *cloud, int64_t n, const float *trans, const float *rot, int B, int H, int W, float tau, int stride,
                    uint8_t *visible, void *workspace, size_t workspace_bytes, void *stream);
+/* Residuals, pose information and LM polish under the depth mask (additive to ABI 12; BUILD-DEFINED: the reference has no occlusion test
+ * and none of the three).  pcl_point_residuals, pcl_pose_information (objective 0) / pcl_pose_information_l1 (objective 1) and pcl_gn_refine /
+ * pcl_gn_refine_l1 for an UNWEIGHTED cloud with one colour set, with the scatter-min depth mask OF THE EVALUATED POSES multiplied into the
+ * loss kernel's mask: before the per-point pass the call writes pose records from the pose rows, fills and builds the z-buffers of all B
+ * poses on the depth_h x depth_w grid from every stride-th packed point (pcl_depth_mask's z pass), and the pass looks each point's cell up
+ * while its texels are in flight: point i counts at pose b iff ||p_i||^2 <= (zmin (1 + tau))^2 of its cell — pcl_sampling_loss_depth's test.
+ * pcl_point_residuals_depth: residual[b][i] is pcl_point_residuals' value where the point is visible (the same instructions on the same
+ *   inputs), exactly -1 where it is hidden or samples exact black (pcl_robust_weights reads the row unchanged), NaN at a pose that is not
+ *   finite.  visible (nullable) is [B][n] bytes in the row's order (order as for pcl_point_residuals): the in-kernel depth decision alone,
+ *   1 visible / 0 hidden, which tells "hidden" from "black".
+ * pcl_pose_information_depth: the record layout of pcl_pose_information (objective 0; cov nullable) or pcl_pose_information_l1 (objective 1,
+ *   delta by that call's rule; cov is not written) with m the product of both masks; the finish kernel is pcl_pose_information's.
+ * pcl_gn_refine_depth: pcl_gn_refine's chain (objective 1: pcl_gn_refine_l1's; cov not written) with the objective REBUILT at every trial
+ *   pose: evaluation k = 0 .. iters is pose records from the state's trial poses, fill + z pass for all B poses there, the pass gated on
+ *   finished poses, the unchanged step kernel — 1 + 5 (iters + 1) launches.  out, info, cov, trace and state as for pcl_gn_refine; the final
+ *   record and covariance are those of the returned pose under the mask at that pose.
+ * With a tolerance so large that nothing is hidden every output equals the plain call's bit for bit.  pose_stride as for pcl_point_residuals.
+ * Workspaces (pose records, z-buffers, partial rows, in that order, nothing read before it is written): the three size queries, 0 for a
+ * B, n or grid no call accepts.  No allocation, no host synchronisation.  Eager launches: nothing is claimed about graph capture.
+ * PCL_EINVAL, before any launch: what the plain call refuses; depth_h or depth_w below 2 or B z-buffers of 4 GiB or more (pcl_depth_mask's
+ * rule); tau < 0 or not finite; stride outside 1..64; an objective that is neither 0 nor 1; with objective 1 a delta outside [2^-20, 4].
+ * PCL_EWORKSPACE: workspace_bytes below the query's.
+ * Deliberately left out: weights and robust re-weighting under the mask, colour sets, the images and rooms forms, graph capture, any
+ * claim about real data. */
+size_t pcl_point_residuals_depth_workspace_bytes(int B, int depth_h, int depth_w);
+int pcl_point_residuals_depth(const float *cloud, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans, const float *rot,
+                              int pose_stride, int B, int depth_h, int depth_w, float tau, int stride, const int64_t *order, float *residual,
+                              uint8_t *visible, void *workspace, size_t workspace_bytes, void *stream);
+size_t pcl_pose_information_depth_workspace_bytes(int64_t n, int B, int depth_h, int depth_w);
+int pcl_pose_information_depth(const float *cloud, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans, const float *rot,
+                               int pose_stride, int B, int depth_h, int depth_w, float tau, int stride, int objective, float delta, float *info,
+                               float *cov, void *workspace, size_t workspace_bytes, void *stream);
+size_t pcl_gn_depth_workspace_bytes(int64_t n, int B, int depth_h, int depth_w);
+int pcl_gn_refine_depth(const float *cloud, int64_t n, const void *pano, int pano_format, int H, int W, const float *trans, const float *rot,
+                        int pose_stride, int B, int depth_h, int depth_w, float tau, int stride, int objective, float delta,
+                        const pcl_gn_hyper *hyper_host, int iters, void *state, float *out, float *info, float *cov, float *trace, void *workspace,
+                        size_t workspace_bytes, void *stream);
 /* ---- colour preprocessing of the query panorama (color_utils.py; called at localize.py:173-179, :395-409) ----
  *
  * pcl_color_template_build: the point colours rgb [n][3] sorted per channel, tmpl [3][n] — once per cloud.

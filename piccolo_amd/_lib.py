@@ -131,6 +131,15 @@ SIGNATURES = {
     "pcl_trim_loss_images_sets": (_int, [_vp, _i64, _int, _c.POINTER(_vp), _int, _int, _int, _int, _vp, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcl_depth_workspace_bytes": (_sz, [_int, _int, _int]),
     "pcl_depth_mask": (_int, [_vp, _i64, _vp, _vp, _int, _int, _int, _c.c_float, _int, _vp, _vp, _sz, _vp]),
+    "pcl_point_residuals_depth_workspace_bytes": (_sz, [_int, _int, _int]),
+    "pcl_point_residuals_depth": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _int, _c.c_float, _int, _vp, _vp, _vp, _vp, _sz,
+                                         _vp]),
+    "pcl_pose_information_depth_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
+    "pcl_pose_information_depth": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _int, _c.c_float, _int, _int, _c.c_float, _vp,
+                                          _vp, _vp, _sz, _vp]),
+    "pcl_gn_depth_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
+    "pcl_gn_refine_depth": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _int, _c.c_float, _int, _int, _c.c_float,
+                                   _c.POINTER(GnHyper), _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcl_gd_init": (_int, [_vp, _vp, _vp, _int, _c.POINTER(GdHyper), _vp]),
     "pcl_gd_run": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _int, _vp, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
     "pcl_gd_run_weighted": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _int, _vp, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),

@@ -11,6 +11,8 @@ next to, and which chain a dataset loop routes a run through.  Host only — no 
                                                                                               (parallel); omniloc_batch and the *_polished entry points
     score            score_weights = True       every grouping key, robust, room_search,      "scored", one image per launch chain; no entry point (weights=)
                                                 depth_mask
+    depth_polish     depth_mask, and gn_iters   robust, score, weights=; lifts "depth_mask"   none: both loops refuse it; omniloc_batch alone (and through it
+                     and / or pose_covariance   from the gn and pose_covariance rows          localize.refine_image's parallel branch)
 
 An entry point refuses the families it does not take with one _refuse(cfg, its name) (REFUSES) and validates the ones it does with their
 schedules; a dataset loop resolves its cfg once, with dataset_plan, and dispatches on the plan."""
@@ -37,22 +39,23 @@ _EXTENSIONS = {
     "gn": (GN_KEYS, None, "omniloc_batch, omniloc_batch_images_polished, omniloc_batch_rooms_images_polished and localize.refine_image's parallel "
                           "branch do; the dataset loops with cfg.polish_images_per_launch, a room search with cfg.room_search_polish"),
     "score": (SCORE_KEYS, None, "the known-room dataset loops do, one image per launch chain; elsewhere pass weights=score_weights(score_maps(...))"),
+    "depth_polish": (("depth_polish",), None, "omniloc_batch and localize.refine_image's parallel branch do"),
 }
 # The families an entry point refuses, in the order it looks for them: it returns every candidate, records frames, or runs a chain without the
 # robust plane, the covariance or the polish.  omniloc_batch must go on accepting the score keys: refine_image hands it the scored loops' cfg.
 REFUSES = {
-    "omniloc": ("prune", "robust", "pose_covariance", "gn"),
-    "omniloc_all": ("prune", "robust", "pose_covariance", "gn"),
+    "omniloc": ("prune", "robust", "pose_covariance", "gn", "depth_polish"),
+    "omniloc_all": ("prune", "robust", "pose_covariance", "gn", "depth_polish"),
     "omniloc_batch": (),
-    "omniloc_batch_images": ("robust", "pose_covariance", "gn", "score"),
-    "omniloc_batch_images_robust": ("pose_covariance", "gn", "score"),
-    "omniloc_batch_images_polished": ("score",),
-    "omniloc_batch_rooms": ("robust", "pose_covariance", "gn", "score"),
-    "omniloc_batch_rooms_images": ("robust", "pose_covariance", "gn", "score"),
-    "omniloc_batch_rooms_images_polished": ("robust", "score"),
-    "localize_synthetic": ("pose_covariance", "gn", "score"),
-    "localize_stanford": ("pose_covariance", "gn"),
-    "localize_omniscenes": ("pose_covariance", "gn"),
+    "omniloc_batch_images": ("robust", "pose_covariance", "gn", "score", "depth_polish"),
+    "omniloc_batch_images_robust": ("pose_covariance", "gn", "score", "depth_polish"),
+    "omniloc_batch_images_polished": ("score", "depth_polish"),
+    "omniloc_batch_rooms": ("robust", "pose_covariance", "gn", "score", "depth_polish"),
+    "omniloc_batch_rooms_images": ("robust", "pose_covariance", "gn", "score", "depth_polish"),
+    "omniloc_batch_rooms_images_polished": ("robust", "score", "depth_polish"),
+    "localize_synthetic": ("pose_covariance", "gn", "score", "depth_polish"),
+    "localize_stanford": ("pose_covariance", "gn", "depth_polish"),
+    "localize_omniscenes": ("pose_covariance", "gn", "depth_polish"),
 }
 
 
@@ -103,8 +106,9 @@ def _switch(cfg, key):
 
 
 # ------------------------------------------------------------------------------------------------ combinations, each stated once
-def _no_depth_mask(cfg, key):
-    if bool(_cfg(cfg, "depth_mask", False)):
+def _no_depth_mask(cfg, key, polish=False):
+    """polish: `key` belongs to a family that cfg.depth_polish = True takes under the mask (depth_polish_flag holds the rest of that rule)"""
+    if bool(_cfg(cfg, "depth_mask", False)) and not (polish and _cfg(cfg, "depth_polish", None) is True):
         raise ValueError("cfg.%s does not combine with cfg.depth_mask" % key)
 
 
@@ -178,7 +182,7 @@ def pose_covariance_flag(cfg):
     """cfg.pose_covariance as a bool (absent or None: False).  ValueError: a value that is not a bool, cfg.depth_mask next to it.  Host only."""
     v = _switch(cfg, "pose_covariance")
     if v:
-        _no_depth_mask(cfg, "pose_covariance")
+        _no_depth_mask(cfg, "pose_covariance", polish=True)
     return v
 
 
@@ -211,12 +215,27 @@ def gn_schedule(cfg):
         ops.gn_hyper("cfg.gn_step_cap / cfg.gn_lambda", **hyper)          # (what float32 makes of them)
     except ValueError as e:
         raise ValueError("cfg.gn_step_cap / cfg.gn_lambda: %s" % e) from None
-    _no_depth_mask(cfg, "gn_iters")
+    _no_depth_mask(cfg, "gn_iters", polish=True)
     if objective == "l1":
         hyper["objective"] = "l1"
         if delta is not None:
             hyper["delta"] = delta
     return iters, hyper
+
+
+def depth_polish_flag(cfg):
+    """cfg.depth_polish as a bool (absent or None: False): with cfg.depth_mask the winner of omniloc_batch's depth-masked chain is polished
+    (the gn keys) and / or gets its covariance (cfg.pose_covariance) UNDER THE MASK, rebuilt at every trial pose.  ValueError: a value
+    that is not a bool; set without cfg.depth_mask, without any of the gn keys or cfg.pose_covariance, next to the robust or score keys.
+    (weights= is an argument, not a key: omniloc_batch refuses it beside the switch.)  Host only."""
+    if not _switch(cfg, "depth_polish"):
+        return False
+    if not bool(_cfg(cfg, "depth_mask", False)):
+        raise ValueError("cfg.depth_polish goes with cfg.depth_mask (without the mask the gn keys and cfg.pose_covariance need no switch)")
+    if all(_cfg(cfg, k, None) is None for k in GN_KEYS) and not _cfg(cfg, "pose_covariance", None):
+        raise ValueError("cfg.depth_polish goes with cfg.gn_iters and / or cfg.pose_covariance (cfg.depth_mask alone runs the plain depth chain)")
+    _excludes(cfg, "depth_polish", ROBUST_KEYS + SCORE_KEYS)
+    return True
 
 
 def _refuse_l1(gn, who):
@@ -321,6 +340,7 @@ def dataset_plan(cfg, loop):
     score (score_rules' triple or None), room_search (cfg's, where the loop searches: localize_omniscenes ignores the room-search keys) and
     sigmas (every result carries a covariance, the CSV its two sigma columns)."""
     stanford = {"localize_stanford": True, "localize_omniscenes": False}[loop]
+    _refuse(cfg, loop, "depth_polish")
     score = score_rules(cfg)
     robust_rules(cfg)
     rooms_polished = stanford and room_polish_rules(cfg)

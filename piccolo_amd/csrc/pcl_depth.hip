@@ -385,6 +385,8 @@ static int pcl_depth_check(int64_t n, int B, const PclDepthGrid& g)
     return 0;
 }
 
+int pcl_depth_grid_check(int64_t n, int B, const PclDepthGrid& g) { return pcl_depth_check(n, B, g); }
+
 // (fill +) z pass for the B poses of `poses`: zbuf [B][Hd * Wd] afterwards holds every cell's smallest squared depth (+inf: empty).
 // fill = false: the caller guarantees the buffers hold +inf already (the GD loop: the previous iteration's loss launch reset them).
 // zstride: the z-buffers are built from every zstride-th point of the packed cloud (1 = all of them).

@@ -112,6 +112,14 @@ int pcl_gn_launch_init(PclGnState* state, const float* trans, const float* rot, 
     return 0;
 }
 
+int pcl_gn_launch_step(const float* partials, int nchunks, int B, PclGnState* state, const pcl_gn_hyper& hp, int k, int iters, float* out, float* info,
+                       float* cov, float* trace, hipStream_t s)
+{
+    hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, partials, nchunks, B, state, hp, k, iters, out, info, cov, trace);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" size_t pcl_gn_state_bytes(int B)
 {
     if (B <= 0) return 0;

@@ -37,6 +37,9 @@ static inline bool pcl_gn_entry_ok(const pcl_gn_hyper* hyper_host, int iters, co
 
 // pcl_gn_init_kernel over B poses (pcl_gn.hip)
 int pcl_gn_launch_init(PclGnState* state, const float* trans, const float* rot, int pose_stride, float lam0, float* trace, int B, int iters, hipStream_t s);
+// pcl_gn_step_kernel over B poses (pcl_gn.hip), for a chain of another translation unit (pcl_depth_info.hip)
+int pcl_gn_launch_step(const float* partials, int nchunks, int B, PclGnState* state, const pcl_gn_hyper& hp, int k, int iters, float* out, float* info,
+                       float* cov, float* trace, hipStream_t s);
 
 // The chain of all three forms over B poses: `a` comes from the form's argument check with the caller's poses in a.pass.  The init launch
 // reads them; from then on the state is the pose source (theta_try in place) and the workspace holds the partial rows.  Evaluation

@@ -30,6 +30,7 @@ int pcl_launch_loss_rooms(const PclRoomTable* rooms, const void* pano, int pano_
 
 // ---- pcl_depth.hip: the z pass
 size_t pcl_depth_zbuf_bytes(int B, int Hd, int Wd);
+int pcl_depth_grid_check(int64_t n, int B, const PclDepthGrid& g);      // pcl_depth_check, for the entry points of pcl_depth_info.hip
 int pcl_launch_zbuffers(const float* cloud, int64_t n, const PclPoseRec* poses, int B, const PclDepthGrid& g, int zstride, uint32_t* zbuf, bool fill,
                         hipStream_t s);
 

@@ -98,6 +98,14 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_pose_info_finish_rooms_kernel(c
 #include "pcl_info_finish_body.h"
 }
 
+int pcl_info_launch_finish(const float* partials, int nchunks, int B, const float* trans, const float* rot, int pose_stride, float* info, float* cov,
+                           hipStream_t s)
+{
+    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, partials, nchunks, B, trans, rot, pose_stride, info, cov);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" size_t pcl_pose_information_workspace_bytes(int64_t n, int B) { return pcl_info_workspace_bytes(n, B); }
 
 extern "C" int pcl_pose_information(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W,

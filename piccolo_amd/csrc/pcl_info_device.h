@@ -45,10 +45,12 @@ struct PclInfoImages {
 // l^2 / (2 delta), in place of S2, and S1 and M keep the plain w.  inv_delta = 1 / delta and half_delta = delta / 2 are formed on the host
 // and travel by value in the kernel arguments (wave-uniform: SGPRs); delta itself is half_delta + half_delta, exactly.  Without L1 the two
 // are not read and the instruction stream is the one it was before the flag.
-template <int FMT, bool WT, bool CS = false, bool L1 = false>
+// With DEPTH (pcl_depth_info.hip) the pass is pcl_point_pass_at's depth form over the z-buffers `dz`: a hidden point arrives with l = 0,
+// m = 0 and a = 0 like a masked one and adds nothing to any sum; the two visibility bits are not needed here.  Without it: as before.
+template <int FMT, bool WT, bool CS = false, bool L1 = false, bool DEPTH = false>
 __device__ __forceinline__ void pcl_info_pass_at(const PclInfoArgs& a, const PclPassCloud& c, unsigned b, unsigned chunk, const void* pano_b, int sets,
                                                  unsigned set, int wsets, int wplane, float* partials, unsigned row, float inv_delta = 0.f,
-                                                 float half_delta = 0.f)
+                                                 float half_delta = 0.f, const PclPassDepth* dz = nullptr)
 {
     __amdgpu_buffer_rsrc_t wrs;
     if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.weights, 0, (int)(c.stride * 4) * wsets, 0x00020000);
@@ -59,7 +61,8 @@ __device__ __forceinline__ void pcl_info_pass_at(const PclInfoArgs& a, const Pcl
 #pragma unroll
     for (int k = 0; k < 6; k++) bb[k] = F2(0.f);
 
-    pcl_point_pass_at<FMT, true, CS>(a.pass, c, b, chunk, pano_b, sets, set, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool) {
+    // (auto...: the depth form's two visibility bits, not read)
+    pcl_point_pass_at<FMT, true, CS, DEPTH>(a.pass, c, b, chunk, pano_b, sets, set, [&](int, int j, bool valid0, bool valid1, const f2* acc, bool, auto...) {
         // acc: 0 l, 1 m, 2-4 g, 5-7 tau of this pair of points alone.  One factor w (a slot past n never counts, whatever its plane holds)
         f2 w = F2(1.f), wl = acc[0], wm = acc[1], wa[6];
         if constexpr (WT) {
@@ -96,7 +99,7 @@ __device__ __forceinline__ void pcl_info_pass_at(const PclInfoArgs& a, const Pcl
         }
         s1 += wl;
         mm += wm;
-    });
+    }, dz);
 
     // the block's sums in a fixed order: packed halves, the lanes of a wave (DPP), the four waves (LDS)
     __shared__ float red[PCL_BLOCK / PCL_WAVE][PCL_INFO_ROW];
@@ -332,6 +335,10 @@ static inline size_t pcl_info_workspace_bytes(int64_t n, int B)
     c.take((size_t)nchunks * (size_t)B * PCL_INFO_ROW * sizeof(float));
     return c.off;
 }
+
+// pcl_pose_info_finish_kernel over B poses (pcl_info.hip), for an entry point of another translation unit (pcl_depth_info.hip)
+int pcl_info_launch_finish(const float* partials, int nchunks, int B, const float* trans, const float* rot, int pose_stride, float* info, float* cov,
+                           hipStream_t s);
 
 // ---- host side of the images entry points (pcl_pose_information_images, pcl_gn_refine_images): every check, before any launch
 // weights == NULL with weight_sets 0; else weight_sets 1 (one plane for every image) or nimages (plane i at weights + i * stride);

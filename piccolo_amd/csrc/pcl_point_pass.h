@@ -56,9 +56,20 @@ struct PclPassCloud {
 //   per_pair(i0, j, valid0, valid1, acc, pose_ok)      j: the slot the pair was loaded from (a pair never leaves its padded plane)
 // with acc the forward (GRAD: and gradient) sums of pcl_sample2 for that pair alone: 0 l, 1 mask bit, GRAD: 2-4 g, 5-7 tau.
 // pcl_point_pass below is block blockIdx.x = chunk * a.B + b over the call's one cloud, a's own.
-template <int FMT, bool GRAD, bool CS, class F>
+// DEPTH (the depth mask): the block also takes the call's z-buffers `dz` ([a.B][Hd * Wd] words behind one buffer
+// resource, pose b's at a wave-uniform scalar offset) and their grid; pcl_project2<FMT, true> issues the two cells' look-ups with the
+// texels, the pair is sampled with its valid bits cleared where d2 = pz^2 + rho2 > Z[cell] — the loss kernel's own test (pcl_loss.hip,
+// VIS == 2) — so a hidden point's acc is that of a masked one, and per_pair takes the two visibility bits behind its other arguments:
+//   per_pair(i0, j, valid0, valid1, acc, pose_ok, vis0, vis1)      valid0 / valid1 still say "a point of the cloud"
+// Without the flag nothing of this is compiled and an instance keeps the instruction stream it had.
+struct PclPassDepth {
+    const uint32_t* zbuf;    // [B][Hd * Wd], built by pcl_launch_zbuffers at the poses the pass evaluates
+    PclDepthGrid grid;
+};
+
+template <int FMT, bool GRAD, bool CS, bool DEPTH = false, class F>
 __device__ __forceinline__ void pcl_point_pass_at(const PclPassArgs& a, const PclPassCloud& c, unsigned b, unsigned chunk, const void* pano_b, int sets,
-                                                  unsigned set, F&& per_pair)
+                                                  unsigned set, F&& per_pair, const PclPassDepth* dz = nullptr)
 {
     bool pose_ok;
     const PclPose6 P = pcl_pass_pose(a, b, pose_ok);
@@ -72,6 +83,13 @@ __device__ __forceinline__ void pcl_point_pass_at(const PclPassArgs& a, const Pc
     const int first = (int)chunk * c.steps_base + min((int)chunk, c.steps_rem);
     const int nsteps = c.steps_base + ((int)chunk < c.steps_rem ? 1 : 0);
     const int n = (int)c.n, last_pair = (int)c.stride - 2;
+    __amdgpu_buffer_rsrc_t zb = __amdgpu_buffer_rsrc_t();
+    int zoff = 0;
+    if constexpr (DEPTH) {
+        // (32 unsigned bits: the B z-buffers together stay below 4 GiB, pcl_depth_check)
+        zb = __builtin_amdgcn_make_buffer_rsrc((void*)dz->zbuf, 0, (int)((unsigned)a.B * (unsigned)(dz->grid.last + 1) * 4u), 0x00020000);
+        zoff = (int)(b * (unsigned)(dz->grid.last + 1) * 4u);
+    }
     for (int s = first; s < first + nsteps; s++) {
         const int i0 = s * PCL_PASS_STEP + 2 * (int)threadIdx.x, i1 = i0 + 1;
         const bool valid0 = i0 < n, valid1 = i1 < n;
@@ -81,21 +99,31 @@ __device__ __forceinline__ void pcl_point_pass_at(const PclPassArgs& a, const Pc
         for (int k = 0; k < 6; k++)
             p[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(cld, j * 4, (CS && k >= 3) ? cplane + (k - 3) * plane : k * plane, 0));
         PclProj<FMT> pj;
-        pcl_project2<FMT>(p[0], p[1], p[2], P, tex, a.dims, pj);
+        if constexpr (DEPTH) pcl_project2<FMT, true>(p[0], p[1], p[2], P, tex, a.dims, pj, zb, zoff, &dz->grid);
+        else pcl_project2<FMT>(p[0], p[1], p[2], P, tex, a.dims, pj);
         f2 acc[PCL_NACC];
 #pragma unroll
         for (int k = 0; k < PCL_NACC; k++) acc[k] = F2(0.f);
         int count = 0;
-        pcl_sample2<GRAD, FMT, true>(pj, p[3], p[4], p[5], valid0, valid1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
-        per_pair(i0, j, valid0, valid1, acc, pose_ok);
+        if constexpr (DEPTH) {
+            // visible iff d^2 <= (zmin (1 + tau))^2 = the cell; an empty cell holds +inf (no short-circuit, as in the loss kernel)
+            const f2 d2 = pcl_fma2(pj.pz, pj.pz, pj.rho2);
+            const bool vis0 = d2.x <= __uint_as_float(pj.zq0), vis1 = d2.y <= __uint_as_float(pj.zq1);
+            pcl_sample2<GRAD, FMT, true>(pj, p[3], p[4], p[5], valid0 & vis0, valid1 & vis1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
+            per_pair(i0, j, valid0, valid1, acc, pose_ok, vis0, vis1);
+        } else {
+            pcl_sample2<GRAD, FMT, true>(pj, p[3], p[4], p[5], valid0, valid1, 0ull, 0ull, tex, a.dims, acc, count, F2(1.f));
+            per_pair(i0, j, valid0, valid1, acc, pose_ok);
+        }
     }
 }
 
-template <int FMT, bool GRAD, bool CS, class F>
-__device__ __forceinline__ void pcl_point_pass(const PclPassArgs& a, const void* pano_b, int sets, unsigned set, F&& per_pair)
+template <int FMT, bool GRAD, bool CS, bool DEPTH = false, class F>
+__device__ __forceinline__ void pcl_point_pass(const PclPassArgs& a, const void* pano_b, int sets, unsigned set, F&& per_pair,
+                                               const PclPassDepth* dz = nullptr)
 {
-    pcl_point_pass_at<FMT, GRAD, CS>(a, PclPassCloud{a.cloud, a.n, a.stride, a.steps_base, a.steps_rem}, blockIdx.x % (unsigned)a.B,
-                                     blockIdx.x / (unsigned)a.B, pano_b, sets, set, per_pair);
+    pcl_point_pass_at<FMT, GRAD, CS, DEPTH>(a, PclPassCloud{a.cloud, a.n, a.stride, a.steps_base, a.steps_rem}, blockIdx.x % (unsigned)a.B,
+                                            blockIdx.x / (unsigned)a.B, pano_b, sets, set, per_pair, dz);
 }
 
 // ---- host side

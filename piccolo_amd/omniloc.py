@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from . import ops
 from .cfg_rules import (GN_KEYS, ROBUST_KEYS, SCORE_KEYS, _EXTENSIONS, _cfg, _refuse, _refuse_l1,  # noqa: F401  (re-exported)
-                        gn_schedule, pose_covariance_flag, prune_schedule, robust_schedule)
+                        depth_polish_flag, gn_schedule, pose_covariance_flag, prune_schedule, robust_schedule)
 
 strict_reference_asserts = True
 
@@ -293,11 +293,13 @@ def _cached_engine(kind, xyzs, sub, make, clouds, boxes):
 # l <= k s ? 1 : k s / l ("huber"); the SAME optimiser state goes on under pcl_gd_run_weighted.  Nothing waits for the host.  The returned
 # loss is the WEIGHTED loss of the last forward; Adam's moments and the plateau scheduler carry on across the switch, so the scheduler's
 # `best` then compares weighted with unweighted losses — it is not reset.  Several images of one cloud: omniloc_batch_images_robust.
-def point_residuals(img, xyz, rgb, trans, rot):
+def point_residuals(img, xyz, rgb, trans, rot, depth=None, return_visible=False):
     """(B, N) GPU tensor, in the order of xyz's rows: per point the ||c - rgb|| the sampling loss sums at the poses trans / rot ((B, 3)
     tensors: translation; yaw, pitch, roll) where its mask keeps the point, exactly -1 where the point samples exact black
-    (ops.point_residuals over the cached packed cloud and panorama)."""
-    return ops.point_residuals(packed_cloud(xyz, rgb), packed_pano(img, n_points=xyz.shape[0]), trans, rot)
+    (ops.point_residuals over the cached packed cloud and panorama).  depth / return_visible: ops.point_residuals' (the depth mask of the
+    same poses; -1 where hidden; with return_visible (rows, visible))."""
+    return ops.point_residuals(packed_cloud(xyz, rgb), packed_pano(img, n_points=xyz.shape[0]), trans, rot, depth=depth,
+                               return_visible=return_visible)
 
 
 def robust_weights(residuals_row, kind="trunc", k=2.5):
@@ -354,27 +356,32 @@ def score_weights(maps, floor=0.0, min_count=1):
 # colour set, one image, no depth mask; nothing is claimed about real data.  cfg gn_objective = "l1" (gn_delta: ops.GN_L1_DELTA = 1 / 64 when
 # absent) polishes on the Huber-L1 objective sum w m rho(l) / sum w m instead, which tends to the sampling loss itself as delta -> 0
 # (DESIGN.md section 4.1i), re-weighting inside the chain.  The rooms forms refuse it.
-def gauss_newton_refine(img, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, objective="l2", delta=None, **hyper):
+# Under the depth mask: depth= of the functions below evaluates residuals, information and polish under the mask of
+# the poses they evaluate, rebuilt at every trial pose; cfg depth_polish = True next to depth_mask lets omniloc_batch take the gn keys and
+# pose_covariance (cfg_rules.depth_polish_flag).  Unweighted, one colour set, one image.
+def gauss_newton_refine(img, xyz, rgb, trans, rot, iters=10, weights=None, trace=False, objective="l2", delta=None, depth=None, **hyper):
     """ops.gauss_newton_refine from the poses trans / rot ((B, 3) tensors: translation; yaw, pitch, roll) over the cached packed cloud and
     panorama: a dict of GPU tensors (trans, rot, sigma2_start, sigma2, lam, accepted, rejected, evaluations, status, H, b, stats, cov, and
     trace when asked).  weights: (N,) per-point weights in the order of xyz's rows.  objective="l1" / delta: the Huber-L1 objective
-    (ops.gauss_newton_refine: sigma2* hold F_rho, stats = (M, S1, sum w m rho, F_rho, status), cov None)."""
+    (ops.gauss_newton_refine: sigma2* hold F_rho, stats = (M, S1, sum w m rho, F_rho, status), cov None).  depth: the chain under the depth
+    mask, rebuilt at every trial pose (ops.gauss_newton_refine; not with weights)."""
     return ops.gauss_newton_refine(packed_cloud(xyz, rgb, weights), packed_pano(img, n_points=xyz.shape[0]), trans, rot, iters=iters, trace=trace,
-                                   objective=objective, delta=delta, **hyper)
+                                   objective=objective, delta=delta, depth=depth, **hyper)
 
 
-def pose_information(img, xyz, rgb, trans, rot, weights=None, objective="l2", delta=None):
+def pose_information(img, xyz, rgb, trans, rot, weights=None, objective="l2", delta=None, depth=None):
     """(H (B,6,6), b (B,6), stats (B,5) = M, S1, S2, sigma^2, status, cov (B,6,6)) on the GPU at the poses trans / rot ((B, 3) tensors:
     translation; yaw, pitch, roll), over the cached packed cloud and panorama (ops.pose_information).  weights: (N,) per-point weights in
     the order of xyz's rows.  objective="l1" / delta: the Huber-L1 record (ops.pose_information: H_rho, b_rho, stats = (M, S1, sum w m rho,
-    F_rho, status), cov None)."""
-    return ops.pose_information(packed_cloud(xyz, rgb, weights), packed_pano(img, n_points=xyz.shape[0]), trans, rot, objective=objective, delta=delta)
+    F_rho, status), cov None).  depth: the sums under the depth mask of the same poses (ops.pose_information; not with weights)."""
+    return ops.pose_information(packed_cloud(xyz, rgb, weights), packed_pano(img, n_points=xyz.shape[0]), trans, rot, objective=objective, delta=delta,
+                                depth=depth)
 
 
-def pose_covariance(img, xyz, rgb, trans, rot, weights=None):
+def pose_covariance(img, xyz, rgb, trans, rot, weights=None, depth=None):
     """(cov (B,6,6), sigma^2 (B,), status (B,)) of pose_information: cov = sigma^2 H^-1 in theta's units (metres, radians), all NaN where
-    status is not 0 (1: nothing kept or something not finite; 2: H not positive definite)."""
-    _, _, stats, cov = pose_information(img, xyz, rgb, trans, rot, weights)
+    status is not 0 (1: nothing kept or something not finite; 2: H not positive definite).  depth: under the depth mask of the poses."""
+    _, _, stats, cov = pose_information(img, xyz, rgb, trans, rot, weights, depth=depth)
     return cov, stats[:, 3], stats[:, 4]
 
 
@@ -475,25 +482,27 @@ def _winner_cloud(gd, cloud):
     return cloud
 
 
-def _winner_covariance(gd, cloud, pano, win):
+def _winner_covariance(gd, cloud, pano, win, depth=None):
     """cov (1,6,6) on the GPU at the pose of the (1, 16) winners row `win` of the chain `gd` (an engine or a _PrunedChain), under the weight
-    plane its last forward ran with"""
-    return ops.pose_information_at_winners(_winner_cloud(gd, cloud), pano, win)[3]
+    plane its last forward ran with (depth: under the chain's depth mask at that pose — cfg.depth_polish; such a chain has no weights)"""
+    return ops.pose_information_at_winners(_winner_cloud(gd, cloud), pano, win, depth=depth)[3]
 
 
-def _winner_polish(gd, cloud, pano, win, gn, want_cov=False):
+def _winner_polish(gd, cloud, pano, win, gn, want_cov=False, depth=None):
     """The (1, 16) winners row `win` polished on the device under the chain's weights -> (row (13,) GPU: t, R, loss where the polish took a
     step — accepted > 1 and status 0 or 3; R is rot_from_ypr of the polished angles, loss the sampling loss re-evaluated there by one
     forward-only launch — else the chain's own three entries bit for bit; cov (1,6,6) GPU: the polish's own, at the returned pose — an
-    L1 polish has none: with want_cov one plain pose_information pass at the returned pose gives it, else None)"""
+    L1 polish has none: with want_cov one plain pose_information pass at the returned pose gives it, else None).  depth (cfg.depth_polish):
+    the polish, the re-evaluated loss and that pass all run under the chain's depth mask, rebuilt at the pose each of them evaluates."""
     cloud = _winner_cloud(gd, cloud)
-    res = ops.gauss_newton_refine_at_winners(cloud, pano, win, iters=gn[0], **gn[1])
+    res = ops.gauss_newton_refine_at_winners(cloud, pano, win, iters=gn[0], depth=depth, **gn[1])
     R = ops.rot_from_ypr(res["rot"]).reshape(1, 9)
-    loss = ops.sampling_loss(cloud, pano, res["trans"], res["rot"], with_grad=False)[:, 0:1]
+    loss = ops.sampling_loss(cloud, pano, res["trans"], res["rot"], with_grad=False, depth=depth)[:, 0:1]
     took = ((res["accepted"] > 1) & ((res["status"] == 0) | (res["status"] == 3))).reshape(1, 1)
     cov = res["cov"]
     if cov is None and want_cov:
-        cov = ops.pose_information(cloud, pano, torch.where(took, res["trans"], win[:, 0:3]), torch.where(took, res["rot"], win[:, 13:16]))[3]
+        cov = ops.pose_information(cloud, pano, torch.where(took, res["trans"], win[:, 0:3]), torch.where(took, res["rot"], win[:, 13:16]),
+                                   depth=depth)[3]
     return torch.where(took, torch.cat([res["trans"], R, loss], dim=1), win[:, 0:13])[0], cov
 
 
@@ -790,7 +799,14 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     With cfg.pose_covariance the fourth entry is the polish's own cov at its returned pose.  The written-back leaves stay the chain's.
     cfg.gn_objective = "l1" (and cfg.gn_delta; gn_schedule): the polish minimises the Huber-L1 objective sum w m rho(l) / sum w m instead —
     for small delta the sampling loss itself —, with the same rules for the three entries; the fourth entry is then pose_information's
-    cov at the RETURNED pose, from one plain pass after the polish (omniloc.pose_covariance's bits there)."""
+    cov at the RETURNED pose, from one plain pass after the polish (omniloc.pose_covariance's bits there).
+    cfg.depth_polish = True next to cfg.depth_mask (depth_polish_flag): the gn keys and cfg.pose_covariance are taken under the mask.  The
+    depth-masked chain runs as without the key; its winner is polished from the winners row on the device by gauss_newton_refine(depth=...)
+    under the chain's own grid, tolerance and stride, the mask rebuilt at every trial pose; the returned loss is ops.sampling_loss(depth=...)
+    at the polished pose; the covariance is the one under the mask at the returned pose.  Not with weights=, the robust or the score keys."""
+    depth = _depth_cfg(cfg) if depth_polish_flag(cfg) else None          # (its own refusals first: without the key nothing changes)
+    if depth is not None and weights is not None:
+        raise ValueError("cfg.depth_polish does not combine with weights=")
     if robust_schedule(cfg) is not None and weights is not None:          # (and the schedule's own refusals, before a device is touched)
         raise ValueError("cfg.robust_iters does not combine with weights= (the chain makes its own)")
     want_cov = pose_covariance_flag(cfg)
@@ -811,10 +827,10 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     # (the covariance reads the winners row on the device and changes nothing the first three entries are made from)
     if gn is not None:
         # (the polish starts from the winners row on the device; its 13 floats travel with the one D2H copy's worth of the row)
-        row, cov = _winner_polish(gd, packed_cloud(xyz, rgb, weights), pano, win, gn, want_cov)
+        row, cov = _winner_polish(gd, packed_cloud(xyz, rgb, weights), pano, win, gn, want_cov, depth)
         out = row.cpu()
     else:
-        cov = _winner_covariance(gd, packed_cloud(xyz, rgb, weights), pano, win) if want_cov else None
+        cov = _winner_covariance(gd, packed_cloud(xyz, rgb, weights), pano, win, depth) if want_cov else None
         out = win[0].cpu()
     after()
     ret = _entry(out)

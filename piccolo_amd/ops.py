@@ -436,6 +436,43 @@ def _winner_poses(winners, who, rows=None):
     return _ptr(winners), ctypes.c_void_p(winners.data_ptr() + 13 * 4), 16, int(winners.shape[0])
 
 
+def _depth_form(who, cloud, pano, depth, return_visible=False):
+    """The depth= keyword of the single-cloud residual / information / polish functions, sampling_loss's convention (True, or a dict with
+    optional depth_res / depth_tau / depth_stride, resolved by _depth_args) -> None without it, else (depth_h, depth_w, tau, stride).
+    ValueError: return_visible without depth; with depth a weighted cloud or a cloud of colour sets.  Host only."""
+    if not depth:
+        if return_visible:
+            raise ValueError("%s: return_visible goes with depth" % who)
+        return None
+    if getattr(cloud, "weights", None) is not None:
+        raise ValueError("%s: per-point weights do not combine with depth" % who)
+    if cloud.color_sets > 1:
+        raise ValueError("%s: a cloud of colour sets does not combine with depth" % who)
+    d = depth if isinstance(depth, dict) else {}
+    return _depth_args(cloud.n, pano.H, pano.W, d.get("depth_res"), d.get("depth_tau"), d.get("depth_stride"))
+
+
+def _point_residuals_depth(who, cloud, pano, trans_ptr, rot_ptr, stride, rows, dev, packed, out, dz, return_visible):
+    """_point_residuals of ONE Pano under the depth mask of the same poses (pcl_point_residuals_depth) -> rows, or (rows, visible)"""
+    lib = _lib.load()
+    _residual_cloud(cloud, pano, who)
+    dh, dw, tau, st = dz
+    if out is None:
+        out = torch.empty(rows, cloud.n, dtype=F32, device=dev)
+    elif not (out.is_cuda and out.dtype == F32 and out.is_contiguous() and out.numel() == rows * cloud.n):
+        raise ValueError("%s: out must be a contiguous (G, N) float32 GPU tensor" % who)
+    vis = torch.empty(rows, cloud.n, dtype=torch.uint8, device=dev) if return_visible else None
+    nws = lib.pcl_point_residuals_depth_workspace_bytes(rows, dh, dw)
+    if nws == 0:
+        raise ValueError("%s: %d poses on a %dx%d depth grid are out of range" % (who, rows, dh, dw))
+    # (a typed torch.empty like the outputs: the memory-contract harness guards and poisons it alike, tests/test_depth_info.py)
+    ws = torch.empty(max(int(nws), 16), dtype=torch.uint8, device=dev)
+    order = None if packed else _ptr(cloud.order)
+    _lib.check(lib.pcl_point_residuals_depth(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr, stride, rows,
+                                             dh, dw, tau, st, order, _ptr(out), _ptr(vis), _ptr(ws), nws, _stream()), "pcl_point_residuals_depth")
+    return (out, vis) if return_visible else out
+
+
 def _point_residuals(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, packed, out=None):
     """What the four residual functions do: `rows` poses (pointers and pose stride) against ONE Pano — pcl_point_residuals, any number of
     poses in one launch — or row i against panos[i] and colour set i of a list of Panos — pcl_point_residuals_images -> (rows, N)"""
@@ -471,18 +508,30 @@ def _pose_rows(trans, rot):
     return trans, rot
 
 
-def point_residuals(cloud, pano, trans, rot, packed=False):
+def point_residuals(cloud, pano, trans, rot, packed=False, depth=None, return_visible=False):
     """(B, N) float GPU tensor: row b holds, per point, the ||c - rgb|| the loss kernel sums at pose (trans[b], rot[b]) where its mask keeps
     the point and exactly -1 where the sampled colour is exactly black (pcl_point_residuals) — in the order of the cloud's xyz rows, or with
     packed=True in the packed slot order (what robust_weights reads).  A cloud's weights play no part.  ValueError: a cloud of colour sets,
-    a panorama in one of the trim launch's texel layouts."""
+    a panorama in one of the trim launch's texel layouts.
+    depth (sampling_loss's convention: True, or a dict with optional depth_res / depth_tau / depth_stride): the scatter-min depth mask of the
+    SAME poses is built and looked up inside the launch (pcl_point_residuals_depth) — a visible point keeps its value bit for bit, a hidden
+    one reads exactly -1; with return_visible=True -> (rows, visible), visible (B, N) uint8 in the rows' order: the depth decision alone,
+    which tells "hidden" from "black".  ValueError: depth with a weighted cloud, return_visible without depth.  depth=None: the call above."""
+    dz = _depth_form("point_residuals", cloud, pano, depth, return_visible)
     trans, rot = _pose_rows(trans, rot)
+    if dz is not None:
+        return _point_residuals_depth("point_residuals", cloud, pano, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, packed, None, dz,
+                                      return_visible)
     return _point_residuals("point_residuals", cloud, pano, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, packed)
 
 
-def point_residuals_at_winners(cloud, pano, winners, packed=False, out=None):
+def point_residuals_at_winners(cloud, pano, winners, packed=False, out=None, depth=None, return_visible=False):
     """point_residuals at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses).  out: a (G, N)
-    tensor to write into."""
+    tensor to write into.  depth / return_visible: as for point_residuals."""
+    who = "point_residuals_at_winners"
+    dz = _depth_form(who, cloud, pano, depth, return_visible)
+    if dz is not None:
+        return _point_residuals_depth(who, cloud, pano, *_winner_poses(winners, who), winners.device, packed, out, dz, return_visible)
     return _point_residuals("point_residuals_at_winners", cloud, pano, *_winner_poses(winners, "point_residuals_at_winners"), winners.device, packed, out)
 
 
@@ -538,19 +587,36 @@ def _single_form(cloud, pano):
     return form
 
 
+def _depth_single_form(cloud, pano, dz):
+    """_single_form under the depth mask (dz of _depth_form): one entry point for both objectives, which travel as (objective, delta) behind
+    the grid — the callers append them (_DEPTH_FORM)"""
+    dh, dw, tau, st = dz
+
+    def form(who, trans_ptr, rot_ptr, stride, rows):
+        head = (_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr, stride, rows, dh, dw, tau, st)
+        return "depth", (cloud.n, rows, dh, dw), rows, head, "%d points x %d poses on a %dx%d depth grid" % (cloud.n, rows, dh, dw)
+    return form
+
+
+_DEPTH_FORM = ("pcl_pose_information_depth", "pcl_pose_information_depth_workspace_bytes", "pcl_gn_refine_depth", "pcl_gn_depth_workspace_bytes")
+
+
 def _pose_information(who, form, trans_ptr, rot_ptr, stride, rows, dev, objective="l2", delta=None):
     """What the six pose_information functions do behind their form's checks -> (H, b, stats, cov); objective "l1": the form's L1 twin,
     cov None"""
     lib = _lib.load()
     delta = gn_objective(who, objective, delta)
     key, size_args, B, head, what = form(who, trans_ptr, rot_ptr, stride, rows)
-    name, size_name = (_POSE_FORMS if delta is None else _POSE_FORMS_L1)[key][:2]
+    name, size_name = _DEPTH_FORM[:2] if key == "depth" else (_POSE_FORMS if delta is None else _POSE_FORMS_L1)[key][:2]
     nws = getattr(lib, size_name)(*size_args)
     if nws == 0:
         raise ValueError("%s: %s are out of range" % (who, what))
     info = torch.empty(B, 48, dtype=F32, device=dev)
     ws = _bytes(nws)
-    if delta is None:
+    if key == "depth":
+        cov = torch.empty(B, 6, 6, dtype=F32, device=dev) if delta is None else None
+        _lib.check(getattr(lib, name)(*head, 0 if delta is None else 1, delta or 0.0, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), name)
+    elif delta is None:
         cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
         _lib.check(getattr(lib, name)(*head, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), name)
     else:
@@ -559,7 +625,7 @@ def _pose_information(who, form, trans_ptr, rot_ptr, stride, rows, dev, objectiv
     return info[:, :36].reshape(B, 6, 6), info[:, 36:42], info[:, 42:47], cov
 
 
-def pose_information(cloud, pano, trans, rot, objective="l2", delta=None):
+def pose_information(cloud, pano, trans, rot, objective="l2", delta=None, depth=None):
     """(H (B,6,6), b (B,6), stats (B,5) = M, S1, S2, sigma^2, status, cov (B,6,6)), float32 on the GPU: the Gauss-Newton information matrix
     H = sum w m j j^T of the pose theta = (t, yaw, pitch, roll) at every pose (trans[b], rot[b]), b = sum w m l j, and cov = sigma^2 H^-1
     with sigma^2 = S2 / M (pcl_pose_information; build-defined, include/piccolo_hip.h; metres and radians).  A weighted cloud contributes
@@ -568,18 +634,23 @@ def pose_information(cloud, pano, trans, rot, objective="l2", delta=None):
     objective="l1" (pcl_pose_information_l1; delta: GN_L1_DELTA unless given, inside [2^-20, 4]): the Huber-L1 form the L1 polish works on —
     the tuple keeps its layout, H = sum w m phi j j^T and b = sum w m phi l j with phi = min(1 / l, 1 / delta), stats = (M, S1, sum w m rho,
     F_rho, status) with M and S1 PLAIN (S1 / M is the weighted sampling loss at the pose), and cov is None.  objective="l2" (or absent):
-    the call above, bit for bit.  ValueError: an objective that is neither, delta without "l1" or outside its range."""
+    the call above, bit for bit.  ValueError: an objective that is neither, delta without "l1" or outside its range.
+    depth (sampling_loss's convention): every sum runs over the points the depth mask of the SAME poses keeps as well
+    (pcl_pose_information_depth: the z-buffers are built at the poses, the pass looks them up); both objectives.  ValueError: depth with a
+    weighted cloud.  depth=None: the calls above."""
     _residual_cloud(cloud, pano, "pose_information")
+    dz = _depth_form("pose_information", cloud, pano, depth)
     trans, rot = _pose_rows(trans, rot)
-    return _pose_information("pose_information", _single_form(cloud, pano), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, objective,
-                             delta)
+    form = _single_form(cloud, pano) if dz is None else _depth_single_form(cloud, pano, dz)
+    return _pose_information("pose_information", form, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, objective, delta)
 
 
-def pose_information_at_winners(cloud, pano, winners, objective="l2", delta=None):
+def pose_information_at_winners(cloud, pano, winners, objective="l2", delta=None, depth=None):
     """pose_information at the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses)."""
     _residual_cloud(cloud, pano, "pose_information_at_winners")
-    return _pose_information("pose_information", _single_form(cloud, pano), *_winner_poses(winners, "pose_information_at_winners"), winners.device,
-                             objective, delta)
+    dz = _depth_form("pose_information_at_winners", cloud, pano, depth)
+    form = _single_form(cloud, pano) if dz is None else _depth_single_form(cloud, pano, dz)
+    return _pose_information("pose_information", form, *_winner_poses(winners, "pose_information_at_winners"), winners.device, objective, delta)
 
 
 GN_HYPER = dict(lam0=1e-3, lam_up=10.0, lam_down=0.1, lam_min=1e-9, lam_max=1e9, step_cap=0.1, tol=0.0)
@@ -614,9 +685,9 @@ def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace
     hp = gn_hyper(who, **hyper)
     delta = gn_objective(who, objective, delta)
     key, size_args, B, head, what = form(who, trans_ptr, rot_ptr, stride, rows)
-    if delta is not None and key not in _POSE_FORMS_L1:
+    if delta is not None and key != "depth" and key not in _POSE_FORMS_L1:
         raise ValueError('%s: objective="l1" has no rooms form' % who)
-    name, size_name = (_POSE_FORMS if delta is None else _POSE_FORMS_L1)[key][2:]
+    name, size_name = _DEPTH_FORM[2:] if key == "depth" else (_POSE_FORMS if delta is None else _POSE_FORMS_L1)[key][2:]
     nws, nst = getattr(lib, size_name)(*size_args), lib.pcl_gn_state_bytes(B)
     if nws == 0 or nst == 0:
         raise ValueError("%s: %s are out of range" % (who, what))
@@ -625,7 +696,10 @@ def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace
     cov = torch.empty(B, 6, 6, dtype=F32, device=dev) if delta is None else None
     tr = torch.empty(iters + 1, B, 16, dtype=F32, device=dev) if trace else None
     ws, st = _bytes(nws), _bytes(nst)
-    if delta is None:
+    if key == "depth":
+        _lib.check(getattr(lib, name)(*head, 0 if delta is None else 1, delta or 0.0, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info),
+                                      _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()), name)
+    elif delta is None:
         _lib.check(getattr(lib, name)(*head, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()),
                    name)
     else:
@@ -637,7 +711,7 @@ def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace
     return ret
 
 
-def gauss_newton_refine(cloud, pano, trans, rot, iters=10, trace=False, objective="l2", delta=None, **hyper):
+def gauss_newton_refine(cloud, pano, trans, rot, iters=10, trace=False, objective="l2", delta=None, depth=None, **hyper):
     """A Levenberg-Marquardt polish of the poses (trans[b], rot[b]) on the device (pcl_gn_refine; build-defined, include/piccolo_hip.h): it
     minimises the MEAN SQUARED residual sigma^2 = sum w m l^2 / sum w m over theta = (t, yaw, pitch, roll; metres, radians) with the H and b
     of pose_information — NOT the sampling loss sum w m l / sum w m; the two share their per-point terms, mask and weights and are
@@ -652,18 +726,26 @@ def gauss_newton_refine(cloud, pano, trans, rot, iters=10, trace=False, objectiv
     F_rho = sum w m rho(l) / sum w m, rho = l - delta / 2 (l >= delta), l^2 / (2 delta) (l < delta) — for delta -> 0 the sampling loss
     itself —, re-weighted at every evaluation: H, b are pose_information(objective="l1")'s.  The dict keeps its layout: sigma2_start, sigma2
     and the trace's F column hold F_rho, stats is (M, S1, sum w m rho, F_rho, status) with M and S1 plain, cov is None.  objective="l2" (or
-    absent): the chain above, bit for bit.  objective and delta are no hyper-parameters (gn_hyper refuses them)."""
+    absent): the chain above, bit for bit.  objective and delta are no hyper-parameters (gn_hyper refuses them).
+    depth (sampling_loss's convention; pcl_gn_refine_depth): the same chain under the depth mask, REBUILT at every trial pose — the z-buffers
+    of all poses are built at the trial poses in front of every evaluation, so a point that the step uncovers counts at once; H, b, stats
+    and cov are pose_information(depth=...) at the returned pose, bit for bit.  Both objectives.  ValueError: depth with a weighted cloud.
+    depth=None: the chains above.  Nothing is claimed about real data."""
     _residual_cloud(cloud, pano, "gauss_newton_refine")
+    dz = _depth_form("gauss_newton_refine", cloud, pano, depth)
     trans, rot = _pose_rows(trans, rot)
-    return _gauss_newton("gauss_newton_refine", _single_form(cloud, pano), _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace,
-                         hyper, objective, delta)
+    form = _single_form(cloud, pano) if dz is None else _depth_single_form(cloud, pano, dz)
+    return _gauss_newton("gauss_newton_refine", form, _ptr(trans), _ptr(rot), 3, int(trans.shape[0]), trans.device, iters, trace, hyper, objective,
+                         delta)
 
 
-def gauss_newton_refine_at_winners(cloud, pano, winners, iters=10, trace=False, objective="l2", delta=None, **hyper):
+def gauss_newton_refine_at_winners(cloud, pano, winners, iters=10, trace=False, objective="l2", delta=None, depth=None, **hyper):
     """gauss_newton_refine from the poses of a (G, 16) tensor as _GdEngine.winners returns it, read on the device (_winner_poses)."""
     _residual_cloud(cloud, pano, "gauss_newton_refine_at_winners")
     who = "gauss_newton_refine_at_winners"
-    return _gauss_newton(who, _single_form(cloud, pano), *_winner_poses(winners, who), winners.device, iters, trace, hyper, objective, delta)
+    dz = _depth_form(who, cloud, pano, depth)
+    form = _single_form(cloud, pano) if dz is None else _depth_single_form(cloud, pano, dz)
+    return _gauss_newton(who, form, *_winner_poses(winners, who), winners.device, iters, trace, hyper, objective, delta)
 
 
 def _images_call(who, cloud, panos, rows, planes):
