@@ -9,6 +9,9 @@
 // refused under the mask everywhere upstream.  The kernels are instances of the texts the plain kernels are instances of; they live in a
 // translation unit of their own so that no existing code object function changes.  No atomics (the z pass has its own), no scratch, no
 // LDS beyond the pass's reduction rows, no allocation, no host synchronisation.
+// Host side: the three entry points share one setup (depth_call_setup: every check that is not an entry point's own, the workspace layout)
+// and one z-buffer step (depth_zbuffers_at); the two that take an objective take it as (objective, delta).  The polish is pcl_gn_chain
+// with a pass callback that builds the z-buffers first: a launch that fails there or in the step ends the chain at once.
 // Outside the loss-kernel hash: the four files it covers are included, never edited.
 #include <math.h>
 
@@ -37,13 +40,6 @@ struct PclResDepthArgs {
     uint8_t* visible;        // nullable, [B][n], the row's order: the depth decision alone
 };
 
-// pcl_res_value of pcl_residual.hip, restated: that file's kernels keep their translation unit to themselves
-__device__ __forceinline__ float pcl_res_depth_value(float sum, float kept, bool pose_ok)
-{
-    if (!pose_ok || sum != sum) return __builtin_nanf("");
-    return kept != 0.f ? sum : -1.f;
-}
-
 // Row b of the residuals under pose b's z-buffer: a visible point's value is pcl_point_residuals' (the same instructions on the same
 // inputs), a hidden one's acc is (0, 0) and reads -1 like a black sample; `visible` tells the two apart.
 template <int FMT, bool ORDERED>
@@ -56,7 +52,7 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_point_residuals_depth_kernel(Pc
     pcl_point_pass<FMT, false, false, true>(
         a.pass, a.pass.pano, 1, 0,
         [&](int i0, int, bool valid0, bool valid1, const f2* acc, bool pose_ok, bool vis0, bool vis1) {
-            const float r0 = pcl_res_depth_value(acc[0].x, acc[1].x, pose_ok), r1 = pcl_res_depth_value(acc[0].y, acc[1].y, pose_ok);
+            const float r0 = pcl_res_value(acc[0].x, acc[1].x, pose_ok), r1 = pcl_res_value(acc[0].y, acc[1].y, pose_ok);
             if (valid0) {
                 int64_t o = i0;
                 if constexpr (ORDERED) o = a.order[i0];
@@ -130,14 +126,38 @@ static size_t depth_ws_bytes(int64_t n, int B, int depth_h, int depth_w, bool ro
     return depth_info_layout(nullptr, B, depth_h, depth_w, rows_bytes, &w);
 }
 
-// records and z-buffers of the B poses (trans + b * pose_stride, rot + b * pose_stride)
-static int depth_zbuffers_at(const PclPassArgs& p, const float* trans, const float* rot, int pose_stride, const PclDepthGrid& g, int stride,
-                             const PclDepthInfoWs& w, hipStream_t s)
+// What the three entry points have in hand once their arguments are checked, beside the PclPassArgs of their kernel arguments
+struct PclDepthCall {
+    PclPassDepth dz;         // the grid, and the z-buffers of the workspace
+    PclDepthInfoWs w;
+    int64_t nchunks;
+    int zstride;
+    hipStream_t s;
+};
+
+// Every check the entry points share, in the order the codes are promised in: the pass's arguments with the form's min_steps, the grid,
+// tolerance and stride, the partial rows of (n, B) where the form has them (`rows`) — PCL_EINVAL — and the workspace: PCL_EWORKSPACE
+static int depth_call_setup(PclDepthCall* c, PclPassArgs* pass, const float* cloud, int64_t n, const void* pano, int pano_format, int H, int W,
+                            const float* trans, const float* rot, int pose_stride, int B, int min_steps, int depth_h, int depth_w, float tau, int stride,
+                            bool rows, void* workspace, size_t workspace_bytes, void* stream)
 {
-    hipLaunchKernelGGL(pcl_depth_pose_rows_kernel, dim3((unsigned)((p.B + PCL_BLOCK - 1) / PCL_BLOCK)), dim3(PCL_BLOCK), 0, s, trans, rot, pose_stride, p.B,
-                       w.recs);
+    const int rc = pcl_pass_args(pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, min_steps, &c->nchunks);
+    if (rc) return rc;
+    if (!depth_args_ok(n, B, depth_h, depth_w, tau, stride, &c->dz.grid)) return PCL_EINVAL;
+    const size_t rows_bytes = rows ? pcl_info_workspace_bytes(n, B) : 0;
+    if (rows && rows_bytes == 0) return PCL_EINVAL;
+    if (workspace_bytes < depth_info_layout(workspace, B, depth_h, depth_w, rows_bytes, &c->w)) return PCL_EWORKSPACE;
+    c->dz.zbuf = c->w.zbuf; c->zstride = stride; c->s = (hipStream_t)stream;
+    return 0;
+}
+
+// records and z-buffers of the B poses (trans + b * pose_stride, rot + b * pose_stride)
+static int depth_zbuffers_at(const PclPassArgs& p, const float* trans, const float* rot, int pose_stride, const PclDepthCall& c)
+{
+    hipLaunchKernelGGL(pcl_depth_pose_rows_kernel, dim3((unsigned)((p.B + PCL_BLOCK - 1) / PCL_BLOCK)), dim3(PCL_BLOCK), 0, c.s, trans, rot, pose_stride,
+                       p.B, c.w.recs);
     PCL_LAUNCH_CHECK();
-    return pcl_launch_zbuffers(p.cloud, p.n, w.recs, p.B, g, stride, w.zbuf, true, s);
+    return pcl_launch_zbuffers(p.cloud, p.n, c.w.recs, p.B, c.dz.grid, c.zstride, c.w.zbuf, true, c.s);
 }
 
 extern "C" size_t pcl_point_residuals_depth_workspace_bytes(int B, int depth_h, int depth_w) { return depth_ws_bytes(1, B, depth_h, depth_w, false); }
@@ -148,20 +168,17 @@ extern "C" int pcl_point_residuals_depth(const float* cloud, int64_t n, const vo
 {
     if (!residual || !workspace) return PCL_EINVAL;
     PclResDepthArgs a;
-    int64_t nchunks;
-    const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, 1, &nchunks);
+    PclDepthCall c;
+    int rc = depth_call_setup(&c, &a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, 1, depth_h, depth_w, tau, stride, false, workspace,
+                              workspace_bytes, stream);
     if (rc) return rc;
-    if (!depth_args_ok(n, B, depth_h, depth_w, tau, stride, &a.dz.grid)) return PCL_EINVAL;
-    PclDepthInfoWs w;
-    if (workspace_bytes < depth_info_layout(workspace, B, depth_h, depth_w, 0, &w)) return PCL_EWORKSPACE;
-    a.dz.zbuf = w.zbuf; a.order = order; a.residual = residual; a.visible = visible;
-    hipStream_t s = (hipStream_t)stream;
-    const int zrc = depth_zbuffers_at(a.pass, trans, rot, pose_stride, a.dz.grid, stride, w, s);
-    if (zrc) return zrc;
-    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
+    a.dz = c.dz; a.order = order; a.residual = residual; a.visible = visible;
+    rc = depth_zbuffers_at(a.pass, trans, rot, pose_stride, c);
+    if (rc) return rc;
+    const dim3 grid((unsigned)(c.nchunks * B)), blk(PCL_BLOCK);
     pcl_with_flag(order != nullptr, [&](auto ord) {
         pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-            hipLaunchKernelGGL((pcl_point_residuals_depth_kernel<decltype(fmt)::value, decltype(ord)::value>), grid, blk, 0, s, a);
+            hipLaunchKernelGGL((pcl_point_residuals_depth_kernel<decltype(fmt)::value, decltype(ord)::value>), grid, blk, 0, c.s, a);
         });
     });
     PCL_LAUNCH_CHECK();
@@ -194,26 +211,20 @@ extern "C" int pcl_pose_information_depth(const float* cloud, int64_t n, const v
     PclInfoL1 l1;
     if (!info || !workspace || !depth_objective_ok(objective, delta, &l1)) return PCL_EINVAL;
     PclInfoArgs a;
-    PclPassDepth dz;
-    int64_t nchunks;
-    const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
+    PclDepthCall c;
+    int rc = depth_call_setup(&c, &a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, depth_h, depth_w, tau, stride,
+                              true, workspace, workspace_bytes, stream);
     if (rc) return rc;
-    if (!depth_args_ok(n, B, depth_h, depth_w, tau, stride, &dz.grid)) return PCL_EINVAL;
-    const size_t rows_bytes = pcl_info_workspace_bytes(n, B);
-    if (rows_bytes == 0) return PCL_EINVAL;
-    PclDepthInfoWs w;
-    if (workspace_bytes < depth_info_layout(workspace, B, depth_h, depth_w, rows_bytes, &w)) return PCL_EWORKSPACE;
-    dz.zbuf = w.zbuf; a.weights = nullptr; a.partials = w.partials;
-    hipStream_t s = (hipStream_t)stream;
-    const int zrc = depth_zbuffers_at(a.pass, trans, rot, pose_stride, dz.grid, stride, w, s);
-    if (zrc) return zrc;
-    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
+    a.weights = nullptr; a.partials = c.w.partials;
+    rc = depth_zbuffers_at(a.pass, trans, rot, pose_stride, c);
+    if (rc) return rc;
+    const dim3 grid((unsigned)(c.nchunks * B)), blk(PCL_BLOCK);
     with_fmt_l1(pano_format, objective == 1, [&](auto fmt, auto l) {
-        hipLaunchKernelGGL((pcl_pose_info_depth_kernel<decltype(fmt)::value, decltype(l)::value>), grid, blk, 0, s, a, dz, l1);
+        hipLaunchKernelGGL((pcl_pose_info_depth_kernel<decltype(fmt)::value, decltype(l)::value>), grid, blk, 0, c.s, a, c.dz, l1);
     });
     PCL_LAUNCH_CHECK();
     // (no covariance under the L1 objective, as in pcl_pose_information_l1)
-    return pcl_info_launch_finish((const float*)a.partials, (int)nchunks, B, trans, rot, pose_stride, info, objective == 1 ? nullptr : cov, s);
+    return pcl_info_launch_finish((const float*)a.partials, (int)c.nchunks, B, trans, rot, pose_stride, info, objective == 1 ? nullptr : cov, c.s);
 }
 
 extern "C" size_t pcl_gn_depth_workspace_bytes(int64_t n, int B, int depth_h, int depth_w) { return depth_ws_bytes(n, B, depth_h, depth_w, true); }
@@ -229,33 +240,24 @@ extern "C" int pcl_gn_refine_depth(const float* cloud, int64_t n, const void* pa
     PclInfoL1 l1;
     if (!pcl_gn_entry_ok(hyper_host, iters, state, out, info, workspace) || !depth_objective_ok(objective, delta, &l1)) return PCL_EINVAL;
     PclInfoArgs a;
-    PclPassDepth dz;
-    int64_t nchunks;
-    const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
+    PclDepthCall c;
+    const int rc = depth_call_setup(&c, &a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, depth_h, depth_w, tau,
+                                    stride, true, workspace, workspace_bytes, stream);
     if (rc) return rc;
-    if (!depth_args_ok(n, B, depth_h, depth_w, tau, stride, &dz.grid)) return PCL_EINVAL;
-    const size_t rows_bytes = pcl_info_workspace_bytes(n, B);
-    if (rows_bytes == 0) return PCL_EINVAL;
-    PclDepthInfoWs w;
-    if (workspace_bytes < depth_info_layout(workspace, B, depth_h, depth_w, rows_bytes, &w)) return PCL_EWORKSPACE;
-    dz.zbuf = w.zbuf; a.weights = nullptr;
-    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    float* const cov_out = objective == 1 ? nullptr : cov;
-    int chain_rc = 0;
-    const int rc2 = pcl_gn_chain(
-        a, B, hyper_host, iters, state, trace, w.partials, s,
+    a.weights = nullptr;
+    const dim3 grid((unsigned)(c.nchunks * B)), blk(PCL_BLOCK);
+    return pcl_gn_chain(
+        a, B, hyper_host, iters, state, trace, c.w.partials, c.s,
         [&](const PclInfoArgs& ak, const PclGnState* st) {
             // (ak.pass.trans / rot / pose_stride: the state's trial poses in place)
-            const int zrc = depth_zbuffers_at(ak.pass, ak.pass.trans, ak.pass.rot, ak.pass.pose_stride, dz.grid, stride, w, s);
-            if (zrc) { chain_rc = chain_rc ? chain_rc : zrc; return; }
+            const int zrc = depth_zbuffers_at(ak.pass, ak.pass.trans, ak.pass.rot, ak.pass.pose_stride, c);
+            if (zrc) return zrc;
             with_fmt_l1(pano_format, objective == 1, [&](auto fmt, auto l) {
-                hipLaunchKernelGGL((pcl_gn_pass_depth_kernel<decltype(fmt)::value, decltype(l)::value>), grid, blk, 0, s, ak, dz, l1, st);
+                hipLaunchKernelGGL((pcl_gn_pass_depth_kernel<decltype(fmt)::value, decltype(l)::value>), grid, blk, 0, c.s, ak, c.dz, l1, st);
             });
+            return 0;
         },
         [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
-            const int src = pcl_gn_launch_step(partials, (int)nchunks, B, st, hp, k, iters, out, info, cov_out, trace, s);
-            if (src) chain_rc = chain_rc ? chain_rc : src;
+            return pcl_gn_launch_step(partials, (int)c.nchunks, B, st, hp, k, iters, out, info, objective == 1 ? nullptr : cov, trace, c.s);
         });
-    return rc2 ? rc2 : chain_rc;
 }

@@ -25,8 +25,11 @@
 // struct when the call is enqueued).  Poses never interact: pose b of a batch has the bits of its own call.
 // pcl_gn_refine_images is the same chain for poses that each have their own panorama, colour set and weight plane (the winners of a chain
 // over several query images): pcl_gn_pass_images_kernel in place of the pass, the init and step kernels as they are.
-// The chain itself — state as pose source, init launch, the k loop — is pcl_gn_chain of pcl_gn_device.h for every entry point, that of
-// pcl_gn_rooms.hip included; an entry point says how its pass and its step are launched.
+// The chain itself — state as pose source, init launch, the k loop — is pcl_gn_chain of pcl_gn_device.h for every entry point, those of
+// pcl_gn_rooms.hip and pcl_depth_info.hip included; a form says how its pass and its step are launched.  Host side here: one body per
+// form, a template over the objective (pcl_gn_single<L1>, pcl_gn_images<L1>) with the form's checks and the one place that picks the gated
+// pass instance; the step kernel is launched from pcl_gn_launch_step and nowhere else.  An extern "C" function checks what is its own
+// and calls its instance of the body.
 #include <math.h>
 
 #include "pcl_gn_device.h"
@@ -128,9 +131,12 @@ extern "C" size_t pcl_gn_state_bytes(int B)
 
 extern "C" size_t pcl_gn_workspace_bytes(int64_t n, int B) { return pcl_info_workspace_bytes(n, B); }
 
-extern "C" int pcl_gn_refine(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
-                             const float* rot, int pose_stride, int B, const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info,
-                             float* cov, float* trace, void* workspace, size_t workspace_bytes, void* stream)
+// The host body of the single form under either objective (pcl_info_device.h: `l1` is read under L1 only): the checks, then the chain
+// with the one place that picks the gated pass instance and the step launch.  Under L1 the step kernel gets a null cov.
+template <bool L1>
+static int pcl_gn_single(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
+                         const float* rot, int pose_stride, int B, const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info,
+                         float* cov, float* trace, PclInfoL1 l1, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!pcl_gn_entry_ok(hyper_host, iters, state, out, info, workspace)) return PCL_EINVAL;
     PclInfoArgs a;
@@ -146,22 +152,27 @@ extern "C" int pcl_gn_refine(const float* cloud, const float* weights, int64_t n
         [&](const PclInfoArgs& ak, const PclGnState* st) {
             pcl_with_flag(weights != nullptr, [&](auto wt) {
                 pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-                    hipLaunchKernelGGL((pcl_gn_pass_kernel<decltype(fmt)::value, decltype(wt)::value>), grid, blk, 0, s, ak, st);
+                    constexpr int FMT = decltype(fmt)::value;
+                    constexpr bool WT = decltype(wt)::value;
+                    if constexpr (L1) hipLaunchKernelGGL((pcl_gn_pass_kernel<FMT, WT, true>), grid, blk, 0, s, ak, st, l1);
+                    else hipLaunchKernelGGL((pcl_gn_pass_kernel<FMT, WT>), grid, blk, 0, s, ak, st);
                 });
             });
+            return 0;
         },
         [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
-            hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)B), blk, 0, s, partials, (int)nchunks, B, st, hp, k, iters, out, info, cov, trace);
+            return pcl_gn_launch_step(partials, (int)nchunks, B, st, hp, k, iters, out, info, L1 ? nullptr : cov, trace, s);
         });
 }
 
-// pcl_gn_refine for nimages poses, each against ITS OWN panorama, colour set and weight plane, in one chain: the init and step launches run
-// over all the images (they are per pose and do not care which image a pose belongs to), the gated pass runs once per
-// PCL_RES_MAX_IMAGES images into the call's [nchunks][nimages] partial rows.  1 + (groups + 1) (iters + 1) launches.
-extern "C" int pcl_gn_refine_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets, const uint64_t* panos_host,
-                                    int nimages, int pano_format, int H, int W, const float* trans, const float* rot, int pose_stride,
-                                    const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info, float* cov, float* trace,
-                                    void* workspace, size_t workspace_bytes, void* stream)
+// The host body of the images form: pcl_gn_refine for nimages poses, each against ITS OWN panorama, colour set and weight plane, in one
+// chain: the init and step launches run over all the images (they are per pose and do not care which image a pose belongs to), the
+// gated pass runs once per PCL_RES_MAX_IMAGES images into the call's [nchunks][nimages] partial rows.  1 + (groups + 1) (iters + 1) launches.
+template <bool L1>
+static int pcl_gn_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets, const uint64_t* panos_host, int nimages,
+                         int pano_format, int H, int W, const float* trans, const float* rot, int pose_stride, const pcl_gn_hyper* hyper_host, int iters,
+                         void* state, float* out, float* info, float* cov, float* trace, PclInfoL1 l1, void* workspace, size_t workspace_bytes,
+                         void* stream)
 {
     if (!pcl_gn_entry_ok(hyper_host, iters, state, out, info, workspace)) return PCL_EINVAL;
     PclInfoArgs a;
@@ -180,17 +191,36 @@ extern "C" int pcl_gn_refine_images(const float* cloud, const float* weights, in
                 pcl_with_flag(weights != nullptr, [&](auto wt) {
                     pcl_with_flag(color_sets > 1, [&](auto cs) {
                         pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-                            hipLaunchKernelGGL((pcl_gn_pass_images_kernel<decltype(fmt)::value, decltype(wt)::value, decltype(cs)::value>), grid, blk, 0,
-                                               s, al, il, st + i0);
+                            constexpr int FMT = decltype(fmt)::value;
+                            constexpr bool WT = decltype(wt)::value, CS = decltype(cs)::value;
+                            if constexpr (L1) hipLaunchKernelGGL((pcl_gn_pass_images_kernel<FMT, WT, CS, true>), grid, blk, 0, s, al, il, st + i0, l1);
+                            else hipLaunchKernelGGL((pcl_gn_pass_images_kernel<FMT, WT, CS>), grid, blk, 0, s, al, il, st + i0);
                         });
                     });
                 });
             });
+            return 0;
         },
         [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
-            hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)nimages), blk, 0, s, partials, (int)nchunks, nimages, st, hp, k, iters, out, info, cov,
-                               trace);
+            return pcl_gn_launch_step(partials, (int)nchunks, nimages, st, hp, k, iters, out, info, L1 ? nullptr : cov, trace, s);
         });
+}
+
+extern "C" int pcl_gn_refine(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
+                             const float* rot, int pose_stride, int B, const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info,
+                             float* cov, float* trace, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return pcl_gn_single<false>(cloud, weights, n, pano, pano_format, H, W, trans, rot, pose_stride, B, hyper_host, iters, state, out, info, cov, trace,
+                                PclInfoL1{}, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pcl_gn_refine_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets, const uint64_t* panos_host,
+                                    int nimages, int pano_format, int H, int W, const float* trans, const float* rot, int pose_stride,
+                                    const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info, float* cov, float* trace,
+                                    void* workspace, size_t workspace_bytes, void* stream)
+{
+    return pcl_gn_images<false>(cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot, pose_stride, hyper_host,
+                                iters, state, out, info, cov, trace, PclInfoL1{}, workspace, workspace_bytes, stream);
 }
 
 // ---- the Huber-L1 form: the same chain on F_rho = sum w m rho(l) / sum w m, rho Huber's function divided by delta,
@@ -198,34 +228,15 @@ extern "C" int pcl_gn_refine_images(const float* cloud, const float* weights, in
 // and b_rho / M to its gradient; for delta >= max l it is the chain above up to the factor 1 / delta.  Only the pass differs: its L1
 // instance puts sum w m rho where S2 goes, and the init, step and finish kernels, the state and pcl_gn_chain run as they are — the step
 // accepts on (float)(s[27] / M), which is F_rho, and solves on the accepted H_rho, b_rho.  M and S1 of the record stay plain.  The `out`
-// and trace columns that hold sigma^2 hold F_rho.  No covariance: the step kernel gets a null cov.  Sizes and launch counts are the twins'.
+// and trace columns that hold sigma^2 hold F_rho.  No covariance.  Sizes and launch counts are the L2 entry points'.
 extern "C" int pcl_gn_refine_l1(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
                                 const float* rot, int pose_stride, int B, const pcl_gn_hyper* hyper_host, int iters, void* state, float* out, float* info,
                                 float* trace, void* workspace, size_t workspace_bytes, float delta, void* stream)
 {
     PclInfoL1 l1;
-    if (!pcl_gn_entry_ok(hyper_host, iters, state, out, info, workspace) || !pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
-    PclInfoArgs a;
-    int64_t nchunks;
-    const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
-    if (rc) return rc;
-    if (workspace_bytes < pcl_info_workspace_bytes(n, B)) return PCL_EINVAL;
-    a.weights = weights;
-    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    return pcl_gn_chain(
-        a, B, hyper_host, iters, state, trace, workspace, s,
-        [&](const PclInfoArgs& ak, const PclGnState* st) {
-            pcl_with_flag(weights != nullptr, [&](auto wt) {
-                pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-                    hipLaunchKernelGGL((pcl_gn_pass_kernel<decltype(fmt)::value, decltype(wt)::value, true>), grid, blk, 0, s, ak, st, l1);
-                });
-            });
-        },
-        [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
-            hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)B), blk, 0, s, partials, (int)nchunks, B, st, hp, k, iters, out, info, (float*)nullptr,
-                               trace);
-        });
+    if (!pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
+    return pcl_gn_single<true>(cloud, weights, n, pano, pano_format, H, W, trans, rot, pose_stride, B, hyper_host, iters, state, out, info, nullptr, trace,
+                               l1, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pcl_gn_refine_images_l1(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets, const uint64_t* panos_host,
@@ -234,32 +245,7 @@ extern "C" int pcl_gn_refine_images_l1(const float* cloud, const float* weights,
                                        size_t workspace_bytes, float delta, void* stream)
 {
     PclInfoL1 l1;
-    if (!pcl_gn_entry_ok(hyper_host, iters, state, out, info, workspace) || !pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
-    PclInfoArgs a;
-    PclInfoImages im;
-    int64_t nchunks;
-    const int rc = pcl_info_images_args(&a, &im, cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot,
-                                        pose_stride, &nchunks);
-    if (rc) return rc;
-    if (workspace_bytes < pcl_info_workspace_bytes(n, nimages)) return PCL_EINVAL;
-    const dim3 blk(PCL_BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    return pcl_gn_chain(
-        a, nimages, hyper_host, iters, state, trace, workspace, s,
-        [&](const PclInfoArgs& ak, const PclGnState* st) {
-            pcl_info_images_launches(ak, im, panos_host, nchunks, [&](const PclInfoArgs& al, const PclInfoImages& il, int i0, dim3 grid) {
-                pcl_with_flag(weights != nullptr, [&](auto wt) {
-                    pcl_with_flag(color_sets > 1, [&](auto cs) {
-                        pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-                            hipLaunchKernelGGL((pcl_gn_pass_images_kernel<decltype(fmt)::value, decltype(wt)::value, decltype(cs)::value, true>), grid,
-                                               blk, 0, s, al, il, st + i0, l1);
-                        });
-                    });
-                });
-            });
-        },
-        [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
-            hipLaunchKernelGGL(pcl_gn_step_kernel, dim3((unsigned)nimages), blk, 0, s, partials, (int)nchunks, nimages, st, hp, k, iters, out, info,
-                               (float*)nullptr, trace);
-        });
+    if (!pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
+    return pcl_gn_images<true>(cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot, pose_stride, hyper_host,
+                               iters, state, out, info, nullptr, trace, l1, workspace, workspace_bytes, stream);
 }

@@ -1,5 +1,6 @@
-// pcl_gn_device.h — what pcl_gn.hip and pcl_gn_rooms.hip share of the Levenberg-Marquardt chain: the per-pose state, the entry check of
-// the three pcl_gn_refine* calls, the init launch and the chain driver.  The step kernels' body, the other thing they share, is the text
+// pcl_gn_device.h — what pcl_gn.hip, pcl_gn_rooms.hip and pcl_depth_info.hip share of the Levenberg-Marquardt chain: the per-pose state, the
+// entry check of every pcl_gn_refine* call, the init and step launches and the chain driver, whose pass and step callbacks return an
+// error code that ends the chain.  The step kernels' body, the other thing they share, is the text
 // pcl_gn_step_body.h.  The rooms chain is a translation unit of its own: a second step kernel beside pcl_gn_step_kernel changes how the
 // compiler inlines the double-precision library calls of both, and pcl_gn_step_kernel keeps the instruction stream it had.
 #pragma once
@@ -37,28 +38,30 @@ static inline bool pcl_gn_entry_ok(const pcl_gn_hyper* hyper_host, int iters, co
 
 // pcl_gn_init_kernel over B poses (pcl_gn.hip)
 int pcl_gn_launch_init(PclGnState* state, const float* trans, const float* rot, int pose_stride, float lam0, float* trace, int B, int iters, hipStream_t s);
-// pcl_gn_step_kernel over B poses (pcl_gn.hip), for a chain of another translation unit (pcl_depth_info.hip)
+// pcl_gn_step_kernel over B poses (pcl_gn.hip): the one place that launches it, for the chains of pcl_gn.hip and of pcl_depth_info.hip
 int pcl_gn_launch_step(const float* partials, int nchunks, int B, PclGnState* state, const pcl_gn_hyper& hp, int k, int iters, float* out, float* info,
                        float* cov, float* trace, hipStream_t s);
 
 // The chain of all three forms over B poses: `a` comes from the form's argument check with the caller's poses in a.pass.  The init launch
 // reads them; from then on the state is the pose source (theta_try in place) and the workspace holds the partial rows.  Evaluation
 // k = 0 .. iters is pass(a, st), whatever launches the form's gated pass takes, and step(a.partials, st, hp, k), its one step launch.
+// Both return 0 or an error code; the chain returns the first one that is not 0, or a launch error, at once and enqueues nothing after it.
 template <class Pass, class Step>
 static inline int pcl_gn_chain(PclInfoArgs& a, int B, const pcl_gn_hyper* hyper_host, int iters, void* state, float* trace, void* workspace, hipStream_t s,
                                Pass&& pass, Step&& step)
 {
     PclGnState* st = (PclGnState*)state;
     const pcl_gn_hyper hp = *hyper_host;
-    const int rc = pcl_gn_launch_init(st, a.pass.trans, a.pass.rot, a.pass.pose_stride, hp.lam0, trace, B, iters, s);
+    int rc = pcl_gn_launch_init(st, a.pass.trans, a.pass.rot, a.pass.pose_stride, hp.lam0, trace, B, iters, s);
     if (rc) return rc;
     a.partials = (float*)workspace;
     a.pass.trans = st->tri; a.pass.rot = st->tri + 3; a.pass.pose_stride = (int)(sizeof(PclGnState) / sizeof(float));
     for (int k = 0; k <= iters; k++) {
-        pass(a, (const PclGnState*)st);
+        rc = pass(a, (const PclGnState*)st);
+        if (rc) return rc;
         PCL_LAUNCH_CHECK();
-        step((const float*)a.partials, st, hp, k);
-        PCL_LAUNCH_CHECK();
+        rc = step((const float*)a.partials, st, hp, k);
+        if (rc) return rc;
     }
     return 0;
 }

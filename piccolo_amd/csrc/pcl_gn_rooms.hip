@@ -63,8 +63,11 @@ extern "C" int pcl_gn_refine_rooms(const pcl_gd_room* rooms_host, int nrooms, in
                     });
                 });
             });
+            return 0;
         },
         [&](const float* partials, PclGnState* st, const pcl_gn_hyper& hp, int k) {
             hipLaunchKernelGGL(pcl_gn_step_rooms_kernel, dim3((unsigned)B), blk, 0, s, partials, g.t, nimages, B, st, hp, k, iters, out, info, cov, trace);
+            PCL_LAUNCH_CHECK();
+            return 0;
         });
 }

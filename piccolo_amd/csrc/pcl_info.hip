@@ -20,6 +20,9 @@
 // double, factorises (Cholesky), inverts, and rounds every output once to fp32.  Same inputs, same bits.
 // The L1 instances of the pass (pcl_pose_information_l1, pcl_pose_information_images_l1) put the IRLS weight
 // phi = min(1 / l, 1 / delta) on the 21 + 6 moment sums and sum w m rho(l) where S2 goes; M and S1 stay plain and the finish is unchanged.
+// Host side: one body per form, a template over the objective (pcl_info_single<L1>, pcl_info_images<L1>; the rooms form has L2 alone and is
+// its own entry point).  A body holds the form's checks and the one place that picks the pass instance; the finish kernel is launched
+// from pcl_info_launch_finish and nowhere else.  An extern "C" function checks what is its own and calls its instance of the body.
 #include <math.h>
 
 #include "pcl_info_device.h"
@@ -108,9 +111,13 @@ int pcl_info_launch_finish(const float* partials, int nchunks, int B, const floa
 
 extern "C" size_t pcl_pose_information_workspace_bytes(int64_t n, int B) { return pcl_info_workspace_bytes(n, B); }
 
-extern "C" int pcl_pose_information(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W,
-                                    const float* trans, const float* rot, int pose_stride, int B, float* info, float* cov, void* workspace,
-                                    size_t workspace_bytes, void* stream)
+// The host body of the single form under either objective (pcl_info_device.h: `l1` is read under L1 only): the checks, the one place
+// that picks the pass instance, the finish.  Under L1 the record holds H_rho, b_rho, M, S1 (both plain), sum w m rho and F_rho = sum w m rho / M
+// in the slots of H, b, M, S1, S2 and sigma^2, and there is no covariance: F_rho H_rho^-1 is not one.
+template <bool L1>
+static int pcl_info_single(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W, const float* trans,
+                           const float* rot, int pose_stride, int B, float* info, float* cov, PclInfoL1 l1, void* workspace, size_t workspace_bytes,
+                           void* stream)
 {
     if (!info || !workspace) return PCL_EINVAL;
     PclInfoArgs a;
@@ -123,49 +130,41 @@ extern "C" int pcl_pose_information(const float* cloud, const float* weights, in
     hipStream_t s = (hipStream_t)stream;
     pcl_with_flag(weights != nullptr, [&](auto wt) {
         pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-            hipLaunchKernelGGL((pcl_pose_info_kernel<decltype(fmt)::value, decltype(wt)::value>), grid, blk, 0, s, a);
+            constexpr int FMT = decltype(fmt)::value;
+            constexpr bool WT = decltype(wt)::value;
+            if constexpr (L1) hipLaunchKernelGGL((pcl_pose_info_kernel<FMT, WT, true>), grid, blk, 0, s, a, l1);
+            else hipLaunchKernelGGL((pcl_pose_info_kernel<FMT, WT>), grid, blk, 0, s, a);
         });
     });
     PCL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, B, trans, rot,
-                       pose_stride, info, cov);
-    PCL_LAUNCH_CHECK();
-    return 0;
+    return pcl_info_launch_finish((const float*)a.partials, (int)nchunks, B, trans, rot, pose_stride, info, L1 ? nullptr : cov, s);
 }
 
-// pcl_pose_information under the Huber-L1 objective of pcl_gn_refine_l1: the record holds H_rho, b_rho, M, S1 (both plain), sum w m rho and
-// F_rho = sum w m rho / M in the slots of H, b, M, S1, S2 and sigma^2.  No covariance: F_rho H_rho^-1 is not one.
+extern "C" int pcl_pose_information(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W,
+                                    const float* trans, const float* rot, int pose_stride, int B, float* info, float* cov, void* workspace,
+                                    size_t workspace_bytes, void* stream)
+{
+    return pcl_info_single<false>(cloud, weights, n, pano, pano_format, H, W, trans, rot, pose_stride, B, info, cov, PclInfoL1{}, workspace,
+                                  workspace_bytes, stream);
+}
+
 extern "C" int pcl_pose_information_l1(const float* cloud, const float* weights, int64_t n, const void* pano, int pano_format, int H, int W,
                                        const float* trans, const float* rot, int pose_stride, int B, float* info, void* workspace,
                                        size_t workspace_bytes, float delta, void* stream)
 {
     PclInfoL1 l1;
-    if (!info || !workspace || !pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
-    PclInfoArgs a;
-    int64_t nchunks;
-    const int rc = pcl_pass_args(&a.pass, cloud, n, pano, pano_format, H, W, trans, rot, pose_stride, B, PCL_INFO_MIN_STEPS, &nchunks);
-    if (rc) return rc;
-    if (workspace_bytes < pcl_info_workspace_bytes(n, B)) return PCL_EINVAL;
-    a.weights = weights; a.partials = (float*)workspace;
-    const dim3 grid((unsigned)(nchunks * B)), blk(PCL_BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    pcl_with_flag(weights != nullptr, [&](auto wt) {
-        pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-            hipLaunchKernelGGL((pcl_pose_info_kernel<decltype(fmt)::value, decltype(wt)::value, true>), grid, blk, 0, s, a, l1);
-        });
-    });
-    PCL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)B), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, B, trans, rot,
-                       pose_stride, info, (float*)nullptr);
-    PCL_LAUNCH_CHECK();
-    return 0;
+    if (!pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
+    return pcl_info_single<true>(cloud, weights, n, pano, pano_format, H, W, trans, rot, pose_stride, B, info, nullptr, l1, workspace, workspace_bytes,
+                                 stream);
 }
 
-// Record i = pcl_pose_information of pose i against panos_host[i], colour set i and weight plane i: one pass launch per PCL_RES_MAX_IMAGES
-// images into the call's [nchunks][nimages] partial rows (the chunking depends on n alone), then pcl_pose_info_finish_kernel over all of them.
-extern "C" int pcl_pose_information_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets,
-                                           const uint64_t* panos_host, int nimages, int pano_format, int H, int W, const float* trans, const float* rot,
-                                           int pose_stride, float* info, float* cov, void* workspace, size_t workspace_bytes, void* stream)
+// The host body of the images form.  Record i = the single form's of pose i against panos_host[i], colour set i and weight plane i: one
+// pass launch per PCL_RES_MAX_IMAGES images into the call's [nchunks][nimages] partial rows (the chunking depends on n alone), then the
+// finish over all of them.
+template <bool L1>
+static int pcl_info_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets, const uint64_t* panos_host, int nimages,
+                           int pano_format, int H, int W, const float* trans, const float* rot, int pose_stride, float* info, float* cov, PclInfoL1 l1,
+                           void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!info || !workspace) return PCL_EINVAL;
     PclInfoArgs a;
@@ -176,22 +175,30 @@ extern "C" int pcl_pose_information_images(const float* cloud, const float* weig
     if (rc) return rc;
     if (workspace_bytes < pcl_info_workspace_bytes(n, nimages)) return PCL_EINVAL;
     a.partials = (float*)workspace;
+    const dim3 blk(PCL_BLOCK);
     hipStream_t s = (hipStream_t)stream;
     pcl_info_images_launches(a, im, panos_host, nchunks, [&](const PclInfoArgs& al, const PclInfoImages& il, int, dim3 grid) {
         pcl_with_flag(weights != nullptr, [&](auto wt) {
             pcl_with_flag(color_sets > 1, [&](auto cs) {
                 pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-                    hipLaunchKernelGGL((pcl_pose_info_images_kernel<decltype(fmt)::value, decltype(wt)::value, decltype(cs)::value>), grid,
-                                       dim3(PCL_BLOCK), 0, s, al, il);
+                    constexpr int FMT = decltype(fmt)::value;
+                    constexpr bool WT = decltype(wt)::value, CS = decltype(cs)::value;
+                    if constexpr (L1) hipLaunchKernelGGL((pcl_pose_info_images_kernel<FMT, WT, CS, true>), grid, blk, 0, s, al, il, l1);
+                    else hipLaunchKernelGGL((pcl_pose_info_images_kernel<FMT, WT, CS>), grid, blk, 0, s, al, il);
                 });
             });
         });
     });
     PCL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)nimages), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, nimages,
-                       trans, rot, pose_stride, info, cov);
-    PCL_LAUNCH_CHECK();
-    return 0;
+    return pcl_info_launch_finish((const float*)a.partials, (int)nchunks, nimages, trans, rot, pose_stride, info, L1 ? nullptr : cov, s);
+}
+
+extern "C" int pcl_pose_information_images(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets,
+                                           const uint64_t* panos_host, int nimages, int pano_format, int H, int W, const float* trans, const float* rot,
+                                           int pose_stride, float* info, float* cov, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return pcl_info_images<false>(cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot, pose_stride, info, cov,
+                                  PclInfoL1{}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pcl_pose_information_images_l1(const float* cloud, const float* weights, int weight_sets, int64_t n, int color_sets,
@@ -200,31 +207,9 @@ extern "C" int pcl_pose_information_images_l1(const float* cloud, const float* w
                                               void* stream)
 {
     PclInfoL1 l1;
-    if (!info || !workspace || !pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
-    PclInfoArgs a;
-    PclInfoImages im;
-    int64_t nchunks;
-    const int rc = pcl_info_images_args(&a, &im, cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot,
-                                        pose_stride, &nchunks);
-    if (rc) return rc;
-    if (workspace_bytes < pcl_info_workspace_bytes(n, nimages)) return PCL_EINVAL;
-    a.partials = (float*)workspace;
-    hipStream_t s = (hipStream_t)stream;
-    pcl_info_images_launches(a, im, panos_host, nchunks, [&](const PclInfoArgs& al, const PclInfoImages& il, int, dim3 grid) {
-        pcl_with_flag(weights != nullptr, [&](auto wt) {
-            pcl_with_flag(color_sets > 1, [&](auto cs) {
-                pcl_with_pass_fmt(pano_format, [&](auto fmt) {
-                    hipLaunchKernelGGL((pcl_pose_info_images_kernel<decltype(fmt)::value, decltype(wt)::value, decltype(cs)::value, true>), grid,
-                                       dim3(PCL_BLOCK), 0, s, al, il, l1);
-                });
-            });
-        });
-    });
-    PCL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pcl_pose_info_finish_kernel, dim3((unsigned)nimages), dim3(PCL_BLOCK), 0, s, (const float*)a.partials, (int)nchunks, nimages,
-                       trans, rot, pose_stride, info, (float*)nullptr);
-    PCL_LAUNCH_CHECK();
-    return 0;
+    if (!pcl_info_l1_args(delta, &l1)) return PCL_EINVAL;
+    return pcl_info_images<true>(cloud, weights, weight_sets, n, color_sets, panos_host, nimages, pano_format, H, W, trans, rot, pose_stride, info, nullptr,
+                                 l1, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t pcl_pose_information_rooms_workspace_bytes(const pcl_gd_room* rooms_host, int nrooms, int nimages)

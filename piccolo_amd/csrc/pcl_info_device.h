@@ -130,8 +130,11 @@ __device__ __forceinline__ void pcl_info_pass(const PclInfoArgs& a, const void* 
                                       inv_delta, half_delta);
 }
 
-// ---- host side of the L1 entry points: delta is refused unless it is finite and inside [2^-20, 4] as a float (residuals never exceed
-// sqrt(3); the range keeps 1 / delta and what it scales well inside fp32)
+// ---- host side of the objective.  The host body of a form in pcl_info.hip and pcl_gn.hip is a template over `bool L1` that takes a PclInfoL1
+// by value and reads it under L1 only; the L2 and the L1 entry point of the form are its two instances.  (A template and not a runtime
+// flag: the instances are made in the order of the entry points, and a translation unit emits its kernels in the order it always did.)
+// delta is refused unless it is finite and inside [2^-20, 4] as a float (residuals never exceed sqrt(3); the range keeps 1 / delta and
+// what it scales well inside fp32)
 struct PclInfoL1 {
     float inv_delta, half_delta;
 };
@@ -336,7 +339,8 @@ static inline size_t pcl_info_workspace_bytes(int64_t n, int B)
     return c.off;
 }
 
-// pcl_pose_info_finish_kernel over B poses (pcl_info.hip), for an entry point of another translation unit (pcl_depth_info.hip)
+// pcl_pose_info_finish_kernel over B poses (pcl_info.hip): the one place that launches it, for the bodies of pcl_info.hip and the entry
+// point of pcl_depth_info.hip
 int pcl_info_launch_finish(const float* partials, int nchunks, int B, const float* trans, const float* rot, int pose_stride, float* info, float* cov,
                            hipStream_t s);
 

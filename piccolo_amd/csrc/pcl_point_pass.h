@@ -126,6 +126,16 @@ __device__ __forceinline__ void pcl_point_pass(const PclPassArgs& a, const void*
                                             blockIdx.x / (unsigned)a.B, pano_b, sets, set, per_pair, dz);
 }
 
+// What a residual row holds for a point from the pass's forward sums acc[0] = sum, acc[1] = kept (pcl_residual.hip, pcl_depth_info.hip)
+__device__ __forceinline__ float pcl_res_value(float sum, float kept, bool pose_ok)
+{
+    // kept: ||d||.  Not kept: -1.  A pose that holds a NaN or an infinity projects every point to NaN; the clip of the angles (v_med3) then
+    // turns the NaN into a number and the point samples a corner of the panorama as if it had been seen there: such a point is neither
+    // kept nor masked here, it is NaN — nobody takes a pose that sees nothing for one whose points agree or are masked
+    if (!pose_ok || sum != sum) return __builtin_nanf("");
+    return kept != 0.f ? sum : -1.f;
+}
+
 // ---- host side
 
 // The chunks of an n-point cloud whose chunks walk at least `min_steps` steps where the cloud has them (0: n out of range), and its steps

@@ -30,15 +30,6 @@ struct PclResArgs {
 
 typedef float pcl_f2u __attribute__((ext_vector_type(2), aligned(4)));      // a row of n floats starts on a 4-byte boundary only
 
-__device__ __forceinline__ float pcl_res_value(float sum, float kept, bool pose_ok)
-{
-    // kept: ||d||.  Not kept: -1.  A pose that holds a NaN or an infinity projects every point to NaN; the clip of the angles (v_med3) then
-    // turns the NaN into a number and the point samples a corner of the panorama as if it had been seen there: such a point is neither
-    // kept nor masked here, it is NaN — nobody takes a pose that sees nothing for one whose points agree or are masked
-    if (!pose_ok || sum != sum) return __builtin_nanf("");
-    return kept != 0.f ? sum : -1.f;
-}
-
 // row b of the residuals from pose b against `pano_b` (and, with CS, colour set `set` of `sets`)
 template <int FMT, bool ORDERED, bool CS>
 __device__ __forceinline__ void pcl_res_body(const PclResArgs& a, const void* pano_b, int sets, unsigned set)

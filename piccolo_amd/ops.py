@@ -535,20 +535,40 @@ def point_residuals_at_winners(cloud, pano, winners, packed=False, out=None, dep
     return _point_residuals("point_residuals_at_winners", cloud, pano, *_winner_poses(winners, "point_residuals_at_winners"), winners.device, packed, out)
 
 
-# The three forms of pose_information / gauss_newton_refine: one cloud and one panorama, one cloud and a panorama per pose, rooms x panoramas.
-# -> (pose information: library call, workspace query; polish: library call, workspace query)
+# The forms of pose_information / gauss_newton_refine — one cloud and one panorama, one cloud and a panorama per pose, rooms x panoramas, one
+# cloud and one panorama under the depth mask — by objective; a form that has no row for an objective does not exist.
+# -> (pose information: library call, workspace query; polish: library call, workspace query; the calls' argument convention, _pose_args)
 _POSE_FORMS = {
-    "single": ("pcl_pose_information", "pcl_pose_information_workspace_bytes", "pcl_gn_refine", "pcl_gn_workspace_bytes"),
-    "images": ("pcl_pose_information_images", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_images", "pcl_gn_workspace_bytes"),
-    "rooms": ("pcl_pose_information_rooms", "pcl_pose_information_rooms_workspace_bytes", "pcl_gn_refine_rooms", "pcl_gn_rooms_workspace_bytes"),
+    ("single", "l2"): ("pcl_pose_information", "pcl_pose_information_workspace_bytes", "pcl_gn_refine", "pcl_gn_workspace_bytes", "cov"),
+    ("images", "l2"): ("pcl_pose_information_images", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_images", "pcl_gn_workspace_bytes", "cov"),
+    ("rooms", "l2"): ("pcl_pose_information_rooms", "pcl_pose_information_rooms_workspace_bytes", "pcl_gn_refine_rooms", "pcl_gn_rooms_workspace_bytes",
+                      "cov"),
+    ("single", "l1"): ("pcl_pose_information_l1", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_l1", "pcl_gn_workspace_bytes", "delta"),
+    ("images", "l1"): ("pcl_pose_information_images_l1", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_images_l1", "pcl_gn_workspace_bytes",
+                       "delta"),
+    ("depth", "l2"): ("pcl_pose_information_depth", "pcl_pose_information_depth_workspace_bytes", "pcl_gn_refine_depth", "pcl_gn_depth_workspace_bytes",
+                      "objective"),
+    ("depth", "l1"): ("pcl_pose_information_depth", "pcl_pose_information_depth_workspace_bytes", "pcl_gn_refine_depth", "pcl_gn_depth_workspace_bytes",
+                      "objective"),
 }
 
 
-# The L1 twins of the single and images forms (pcl_pose_information_l1 ...: no cov, a float delta before the stream; the twin's sizes)
-_POSE_FORMS_L1 = {
-    "single": ("pcl_pose_information_l1", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_l1", "pcl_gn_workspace_bytes"),
-    "images": ("pcl_pose_information_images_l1", "pcl_pose_information_workspace_bytes", "pcl_gn_refine_images_l1", "pcl_gn_workspace_bytes"),
-}
+def _pose_form(who, key, delta):
+    """The row of _POSE_FORMS for form `key`; delta: what gn_objective returned (None: "l2").  ValueError: the form has no such row."""
+    row = _POSE_FORMS.get((key, "l2" if delta is None else "l1"))
+    if row is None:
+        raise ValueError('%s: objective="l1" has no %s form' % (who, key))
+    return row
+
+
+def _pose_args(convention, head, delta, before_cov, cov, after_cov, ws, nws):
+    """The arguments of a library call of a row of _POSE_FORMS: the form's `head`, the call's own pointers around cov, workspace and stream.
+    "cov": just that; "delta": no cov, and the float delta before the stream; "objective": (objective, delta) behind the head."""
+    args = tuple(head) + ((0 if delta is None else 1, delta or 0.0) if convention == "objective" else ()) + tuple(before_cov)
+    args += (() if convention == "delta" else (_ptr(cov),)) + tuple(after_cov) + (_ptr(ws), nws)
+    return args + ((delta,) if convention == "delta" else ()) + (_stream(),)
+
+
 GN_OBJECTIVES = ("l2", "l1")
 GN_L1_DELTA = 1.0 / 64         # the default delta of objective="l1": about four grey levels, exact in fp32.  A choice, not a derived value.
 GN_L1_DELTA_RANGE = (2.0 ** -20, 4.0)
@@ -578,7 +598,7 @@ def gn_objective(who, objective="l2", delta=None):
 
 def _single_form(cloud, pano):
     """A form is what _pose_information and _gauss_newton take as the form-specific part of a call: form(who, trans_ptr, rot_ptr, stride, rows)
-    runs the form's own argument checks and -> (key of _POSE_FORMS, the workspace queries' arguments, the pose count B, the arguments the
+    runs the form's own argument checks and -> (the form's key in _POSE_FORMS, the workspace queries' arguments, the pose count B, the arguments the
     two library calls of the form begin with, up to the poses, and what the queries found out of range when they answer 0).  This one:
     `rows` poses against one cloud and one panorama (the public functions have run _residual_cloud)."""
     def form(who, trans_ptr, rot_ptr, stride, rows):
@@ -589,7 +609,7 @@ def _single_form(cloud, pano):
 
 def _depth_single_form(cloud, pano, dz):
     """_single_form under the depth mask (dz of _depth_form): one entry point for both objectives, which travel as (objective, delta) behind
-    the grid — the callers append them (_DEPTH_FORM)"""
+    the grid (_pose_args' "objective" convention)"""
     dh, dw, tau, st = dz
 
     def form(who, trans_ptr, rot_ptr, stride, rows):
@@ -598,30 +618,20 @@ def _depth_single_form(cloud, pano, dz):
     return form
 
 
-_DEPTH_FORM = ("pcl_pose_information_depth", "pcl_pose_information_depth_workspace_bytes", "pcl_gn_refine_depth", "pcl_gn_depth_workspace_bytes")
-
-
 def _pose_information(who, form, trans_ptr, rot_ptr, stride, rows, dev, objective="l2", delta=None):
-    """What the six pose_information functions do behind their form's checks -> (H, b, stats, cov); objective "l1": the form's L1 twin,
+    """What the six pose_information functions do behind their form's checks -> (H, b, stats, cov); objective "l1": the form's L1 row,
     cov None"""
     lib = _lib.load()
     delta = gn_objective(who, objective, delta)
     key, size_args, B, head, what = form(who, trans_ptr, rot_ptr, stride, rows)
-    name, size_name = _DEPTH_FORM[:2] if key == "depth" else (_POSE_FORMS if delta is None else _POSE_FORMS_L1)[key][:2]
+    name, size_name, _, _, convention = _pose_form(who, key, delta)
     nws = getattr(lib, size_name)(*size_args)
     if nws == 0:
         raise ValueError("%s: %s are out of range" % (who, what))
     info = torch.empty(B, 48, dtype=F32, device=dev)
     ws = _bytes(nws)
-    if key == "depth":
-        cov = torch.empty(B, 6, 6, dtype=F32, device=dev) if delta is None else None
-        _lib.check(getattr(lib, name)(*head, 0 if delta is None else 1, delta or 0.0, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), name)
-    elif delta is None:
-        cov = torch.empty(B, 6, 6, dtype=F32, device=dev)
-        _lib.check(getattr(lib, name)(*head, _ptr(info), _ptr(cov), _ptr(ws), nws, _stream()), name)
-    else:
-        cov = None
-        _lib.check(getattr(lib, name)(*head, _ptr(info), _ptr(ws), nws, delta, _stream()), name)
+    cov = torch.empty(B, 6, 6, dtype=F32, device=dev) if delta is None else None
+    _lib.check(getattr(lib, name)(*_pose_args(convention, head, delta, (_ptr(info),), cov, (), ws, nws)), name)
     return info[:, :36].reshape(B, 6, 6), info[:, 36:42], info[:, 42:47], cov
 
 
@@ -685,9 +695,7 @@ def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace
     hp = gn_hyper(who, **hyper)
     delta = gn_objective(who, objective, delta)
     key, size_args, B, head, what = form(who, trans_ptr, rot_ptr, stride, rows)
-    if delta is not None and key != "depth" and key not in _POSE_FORMS_L1:
-        raise ValueError('%s: objective="l1" has no rooms form' % who)
-    name, size_name = _DEPTH_FORM[2:] if key == "depth" else (_POSE_FORMS if delta is None else _POSE_FORMS_L1)[key][2:]
+    _, _, name, size_name, convention = _pose_form(who, key, delta)
     nws, nst = getattr(lib, size_name)(*size_args), lib.pcl_gn_state_bytes(B)
     if nws == 0 or nst == 0:
         raise ValueError("%s: %s are out of range" % (who, what))
@@ -696,14 +704,8 @@ def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace
     cov = torch.empty(B, 6, 6, dtype=F32, device=dev) if delta is None else None
     tr = torch.empty(iters + 1, B, 16, dtype=F32, device=dev) if trace else None
     ws, st = _bytes(nws), _bytes(nst)
-    if key == "depth":
-        _lib.check(getattr(lib, name)(*head, 0 if delta is None else 1, delta or 0.0, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info),
-                                      _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()), name)
-    elif delta is None:
-        _lib.check(getattr(lib, name)(*head, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(cov), _ptr(tr), _ptr(ws), nws, _stream()),
-                   name)
-    else:
-        _lib.check(getattr(lib, name)(*head, ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info), _ptr(tr), _ptr(ws), nws, delta, _stream()), name)
+    before_cov = (ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info))
+    _lib.check(getattr(lib, name)(*_pose_args(convention, head, delta, before_cov, cov, (_ptr(tr),), ws, nws)), name)
     ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
                evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(B, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
     if trace:

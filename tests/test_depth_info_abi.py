@@ -158,6 +158,7 @@ def test_pose_information_depth_refusals_before_any_device_call(lib):
     for delta in (0.0, -1.0, 2.0 ** -21, 4.5, float("nan"), float("inf")):            # pcl_info_l1_args' rule, under objective 1 only
         assert call(objective=1, delta=delta) == EINVAL, delta
     assert call(objective=1, delta=1.0 / 64, nbytes=need - 1) == EWORKSPACE           # (a good delta gets as far as the workspace check)
+    assert call(cov=None, nbytes=need - 1) == EWORKSPACE                              # (and so does a null cov under L2: it is nullable)
     assert call(n=1 << 27, B=1 << 22, dh=2, dw=2, nbytes=1 << 60) == EINVAL
 
 
@@ -183,6 +184,7 @@ def test_gn_refine_depth_refusals_before_any_device_call(lib):
     for delta in (0.0, 2.0 ** -21, 4.5, float("nan")):
         assert call(objective=1, delta=delta) == EINVAL, delta
     assert call(objective=1, delta=1.0 / 64, nbytes=need - 1) == EWORKSPACE
+    assert call(cov=None, nbytes=need - 1) == EWORKSPACE and call(cov=None, trace=None, nbytes=need - 1) == EWORKSPACE      # both nullable
 
 
 def test_python_surface_refuses_before_a_device(lib):

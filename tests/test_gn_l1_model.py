@@ -246,7 +246,10 @@ def test_the_rooms_paths_refuse_l1(tmp_path):
     cfg = _cfg(num_input=6, parallel=True, gn_iters=3, gn_objective="l1", dataset="stanford", room_search=True, room_search_polish=True)
     with pytest.raises(ValueError, match="gn_objective"):
         localize.localize_stanford(cfg, None, None, str(tmp_path / "nowhere"))
-    assert "rooms" not in ops._POSE_FORMS_L1 and set(ops._POSE_FORMS_L1) == {"single", "images"}      # (and gn_hyper refuses objective=)
+    l1_forms = {form for form, objective in ops._POSE_FORMS if objective == "l1"}
+    assert ("rooms", "l2") in ops._POSE_FORMS and l1_forms == {"single", "images", "depth"}      # (and gn_hyper refuses objective=)
+    with pytest.raises(ValueError, match='objective="l1" has no rooms form'):
+        ops._pose_form("gauss_newton_refine_rooms", "rooms", 1.0 / 64)
     # "l2" passes the refusal (and fails later, on what the call lacks)
     po._refuse_l1(po.gn_schedule(_cfg(gn_iters=3, gn_objective="l2")), "x")
 

@@ -308,6 +308,29 @@ def test_copies_of_a_point_sum_to_the_point(ops, oracle, name, n):
 
 
 @gpu
+def test_a_null_cov_changes_no_bit_of_the_record(ops, oracle):
+    """pcl_pose_information with cov = NULL (the header: nullable) on the one-point probe cloud, one pose: the 48-float record of the call
+    with a covariance buffer, bit for bit"""
+    import torch
+    from parity_helpers import T
+    k = gh.probe(oracle, "fractions")
+    b = int(np.nonzero(k["m64"]["kept"][:len(k["trans"]) - 1])[0][0])
+    cloud, pano = ops.Cloud(T(k["x"][None, :]), T(k["rgb"][None, :])), ops.Pano(T(k["img"]), fmt="f16")
+    trans, rot = T(k["trans"][b:b + 1]).float().contiguous(), T(k["rot"][b:b + 1]).float().contiguous()
+    lib = ops._lib.load()
+    nws = lib.pcl_pose_information_workspace_bytes(cloud.n, 1)
+    records = []
+    for cov in (torch.empty(1, 6, 6, device="cuda"), None):
+        info, ws = torch.full((1, 48), float("nan"), device="cuda"), torch.empty(nws, dtype=torch.uint8, device="cuda")
+        ops._lib.check(lib.pcl_pose_information(ops._ptr(cloud.data), None, cloud.n, ops._ptr(pano.data), pano.fmt, pano.H, pano.W, ops._ptr(trans),
+                                                ops._ptr(rot), 3, 1, ops._ptr(info), ops._ptr(cov), ops._ptr(ws), nws, ops._stream()),
+                       "pcl_pose_information")
+        records.append(info)
+    assert same_bits(records[0], records[1])
+    assert float(records[0][0, 42]) == 1.0 and bool(torch.isfinite(records[0]).all())      # M = 1: the point is kept; every slot was written
+
+
+@gpu
 def test_weights_enter_linearly_and_layout_changes_nothing(ops, oracle):
     """on `odd` (2049 points: five steps in three chunks, a ragged last one), f16 texels, both poses in one call:
     weights all 2.0 give exactly twice the unit-weight H, b, S1, S2, M, bit for bit, the same sigma^2, and cov = sigma^2 H^-1 exactly halved
