@@ -105,8 +105,9 @@ int pcl_cloud_pack_sets(const float *xyz, const float *const *rgb_host, int nset
  * Unit weights give the unweighted results bit for bit, 0/1 weights those of the same byte mask `visible`.
  * Deliberately left out: weights in the initialisation stage (pcl_trim_*, pcl_hist_trim_*), in the rooms and rooms x images chains and
  * under the depth mask, caller-brought weights in the images / colour-set chains (one plane per query image exists for the robust chain:
- * pcl_gd_run_weight_sets below), and any built-in source of weights (density, semantics) — the caller brings them, or makes them
- * from the residuals of a pose with pcl_point_residuals / pcl_robust_weights below. */
+ * pcl_gd_run_weight_sets below), and a semantic source of weights — the caller brings them, or makes them
+ * from the residuals of a pose with pcl_point_residuals / pcl_robust_weights below, from a score map (pcl_score_weights), or from the
+ * sampling density (pcl_voxel_grid / pcl_density_weights). */
 size_t pcl_cloud_weights_bytes(int64_t n);
 int pcl_cloud_pack_weights(const float *w, const int64_t *order, int64_t n, float *plane, int32_t *bad, void *stream);
 /* Per-point residuals (additive to ABI 12; build-defined, one cloud with one colour set, no depth mask — the scope of the weights they feed):
@@ -312,6 +313,27 @@ size_t pcl_cloud_order_workspace_bytes(int64_t n);
 int pcl_cloud_order(const float *xyz, int64_t n, int64_t *order, void *workspace, size_t workspace_bytes, void *stream);
 /* 63-bit Morton keys of xyz quantised to 21 bits per axis inside [lo, hi] (host arrays of 3); sort them to get `order`. */
 int pcl_morton_keys(const float *xyz, int64_t n, const float *lo_host, const float *hi_host, int64_t *keys, void *stream);
+/* A voxel grid over a cloud in the reference's (N,3) layout (additive to ABI 12; build-defined: the reference has nothing of the kind).
+ *   cell       per axis floor((double)x / voxel), the origin fixed at 0; a cell must lie in [-2^20, 2^20)
+ *   voxel ids  in first-occurrence order: first[v], voxel v's lowest point index, increases strictly with v
+ *   centroid   (xyz and rgb alike) q = llrint((double)a * 65536) (half to even), S[v] = sum of q as exact int64,
+ *              (float)((double)S / ((double)count * 65536.0)): integer sums, so the bits do not depend on the order of summation
+ *   weight     w_i = 1 where count[cell_i] <= cap, else (float)((double)cap / (double)count[cell_i])
+ * pcl_voxel_grid writes cell[n] (the voxel id of every point, in the caller's point order), count[v] and first[v] for v < *nvoxels (the
+ * entries at and beyond *nvoxels of the n-entry buffers are not written) and *nvoxels (device int).  pcl_voxel_centroids writes
+ * xyz_out / rgb_out, (nvoxels, 3) each, in voxel-id order; pcl_density_weights w[n].  A point whose cell[] lies outside [0, nvoxels) adds
+ * nothing to a centroid and weighs 0.  *bad (device int, set by the call: 0 when all is well) is a bit set — 1: a value that is NaN or
+ * infinite, 2: a cell outside +-2^20, 4: a magnitude >= 32768 (the grid looks at xyz, the centroids at xyz and rgb); with a bit set the
+ * outputs hold valid indices but must not be used.  One workspace size serves both calls, pcl_voxel_workspace_bytes(n) (0 for n outside
+ * 1..PCL_MAX_POINTS); the library initialises what it needs: results do not depend on what the workspace or the outputs held before.
+ * PCL_EINVAL, before any HIP call: a null pointer, n outside 1..PCL_MAX_POINTS, voxel not positive and finite, nvoxels outside 1..n,
+ * cap < 1.  PCL_EWORKSPACE: workspace_bytes below the query. */
+size_t pcl_voxel_workspace_bytes(int64_t n);
+int pcl_voxel_grid(const float *xyz, int64_t n, double voxel, int32_t *cell, int32_t *count, int64_t *first, int32_t *nvoxels, int32_t *bad,
+                   void *workspace, size_t workspace_bytes, void *stream);
+int pcl_voxel_centroids(const float *xyz, const float *rgb, int64_t n, const int32_t *cell, const int32_t *count, int64_t nvoxels, float *xyz_out,
+                        float *rgb_out, int32_t *bad, void *workspace, size_t workspace_bytes, void *stream);
+int pcl_density_weights(const int32_t *cell, const int32_t *count, int64_t n, int64_t nvoxels, int64_t cap, float *w, void *stream);
 
 size_t pcl_pano_bytes(int H, int W, int pano_format);
 int pcl_pano_pack(const float *img_hwc, int H, int W, float *pano, void *stream);

@@ -83,6 +83,10 @@ SIGNATURES = {
     "pcl_gd_init_weight_sets": (_int, [_vp, _vp, _vp, _int, _int, _c.POINTER(GdHyper), _vp]),
     "pcl_gd_run_weight_sets": (_int, [_vp, _vp, _int, _i64, _vp, _int, _int, _int, _vp, _int, _vp, _c.POINTER(GdHyper), _int, _vp, _vp, _sz, _vp, _vp]),
     "pcl_morton_keys": (_int, [_vp, _i64, _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _vp, _vp]),
+    "pcl_voxel_workspace_bytes": (_sz, [_i64]),
+    "pcl_voxel_grid": (_int, [_vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pcl_voxel_centroids": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pcl_density_weights": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "pcl_pano_bytes": (_sz, [_int, _int, _int]),
     "pcl_pano_pack": (_int, [_vp, _int, _int, _vp, _vp]),
     "pcl_cloud_order_workspace_bytes": (_sz, [_i64]),

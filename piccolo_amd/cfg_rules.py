@@ -13,6 +13,10 @@ next to, and which chain a dataset loop routes a run through.  Host only — no 
                                                 depth_mask
     depth_polish     depth_mask, and gn_iters   robust, score, weights=; lifts "depth_mask"   none: both loops refuse it; omniloc_batch alone (and through it
                      and / or pose_covariance   from the gn and pose_covariance rows          localize.refine_image's parallel branch)
+    density          density_weights = True     what score excludes, and score                "plain", one image per launch chain, refined under
+                     and density_voxel                                                        omniloc.density_weights_of; no entry point (weights=)
+    voxel            voxel_size                 nothing: the down-sampled cloud is a cloud    any: localize._read_cloud applies it once per room; the
+                                                                                              synthetic driver refuses it (utils.voxel_downsample)
 
 An entry point refuses the families it does not take with one _refuse(cfg, its name) (REFUSES) and validates the ones it does with their
 schedules; a dataset loop resolves its cfg once, with dataset_plan, and dispatches on the plan."""
@@ -29,6 +33,9 @@ def _cfg(cfg, key, default):
 ROBUST_KEYS = ("robust_iters", "robust_kind", "robust_k")
 GN_KEYS = ("gn_iters", "gn_step_cap", "gn_lambda", "gn_objective", "gn_delta")
 SCORE_KEYS = ("score_weights", "score_split", "score_floor", "score_min_count")
+DENSITY_KEYS = ("density_weights", "density_voxel", "density_cap")
+VOXEL_KEYS = ("voxel_size", "voxel_how")
+VOXEL_HOW = ("centroid", "first")
 _EXTENSIONS = {
     "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
     "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust, omniloc_batch_images_polished and localize.refine_image's parallel "
@@ -39,21 +46,27 @@ _EXTENSIONS = {
     "gn": (GN_KEYS, None, "omniloc_batch, omniloc_batch_images_polished, omniloc_batch_rooms_images_polished and localize.refine_image's parallel "
                           "branch do; the dataset loops with cfg.polish_images_per_launch, a room search with cfg.room_search_polish"),
     "score": (SCORE_KEYS, None, "the known-room dataset loops do, one image per launch chain; elsewhere pass weights=score_weights(score_maps(...))"),
+    "density": (DENSITY_KEYS, None, "the known-room dataset loops do, one image per launch chain; elsewhere pass "
+                                    "weights=density_weights(xyz, voxel, cap)"),
+    "voxel": (VOXEL_KEYS, None, "the dataset loops do, once per room as its cloud is read; elsewhere down-sample the cloud with "
+                                "utils.voxel_downsample"),
     "depth_polish": (("depth_polish",), None, "omniloc_batch and localize.refine_image's parallel branch do"),
 }
 # The families an entry point refuses, in the order it looks for them: it returns every candidate, records frames, or runs a chain without the
-# robust plane, the covariance or the polish.  omniloc_batch must go on accepting the score keys: refine_image hands it the scored loops' cfg.
+# robust plane, the covariance or the polish.  omniloc_batch must go on accepting the score and density keys: refine_image hands it the
+# scored and the density-weighted loops' cfg.  The voxel keys travel with every loop's cfg: only the synthetic driver, which reads no cloud,
+# refuses them.
 REFUSES = {
     "omniloc": ("prune", "robust", "pose_covariance", "gn", "depth_polish"),
     "omniloc_all": ("prune", "robust", "pose_covariance", "gn", "depth_polish"),
     "omniloc_batch": (),
-    "omniloc_batch_images": ("robust", "pose_covariance", "gn", "score", "depth_polish"),
-    "omniloc_batch_images_robust": ("pose_covariance", "gn", "score", "depth_polish"),
-    "omniloc_batch_images_polished": ("score", "depth_polish"),
-    "omniloc_batch_rooms": ("robust", "pose_covariance", "gn", "score", "depth_polish"),
-    "omniloc_batch_rooms_images": ("robust", "pose_covariance", "gn", "score", "depth_polish"),
-    "omniloc_batch_rooms_images_polished": ("robust", "score", "depth_polish"),
-    "localize_synthetic": ("pose_covariance", "gn", "score", "depth_polish"),
+    "omniloc_batch_images": ("robust", "pose_covariance", "gn", "score", "density", "depth_polish"),
+    "omniloc_batch_images_robust": ("pose_covariance", "gn", "score", "density", "depth_polish"),
+    "omniloc_batch_images_polished": ("score", "density", "depth_polish"),
+    "omniloc_batch_rooms": ("robust", "pose_covariance", "gn", "score", "density", "depth_polish"),
+    "omniloc_batch_rooms_images": ("robust", "pose_covariance", "gn", "score", "density", "depth_polish"),
+    "omniloc_batch_rooms_images_polished": ("robust", "score", "density", "depth_polish"),
+    "localize_synthetic": ("pose_covariance", "gn", "score", "density", "voxel", "depth_polish"),
     "localize_stanford": ("pose_covariance", "gn", "depth_polish"),
     "localize_omniscenes": ("pose_covariance", "gn", "depth_polish"),
 }
@@ -270,6 +283,42 @@ def score_rules(cfg):
     return split, 0.0 if floor is None else float(floor), min_count
 
 
+def density_rules(cfg):
+    """cfg.density_weights = True (a known-room loop refines every image under omniloc.density_weights_of(xyz, density_voxel, density_cap):
+    every occupied voxel of cfg.density_voxel metres votes once, or at most density_cap times) with cfg.density_voxel (required: a positive
+    finite number) and cfg.density_cap (an int >= 1, default 1) -> None without the keys, else (voxel, cap).  It excludes what the score
+    keys exclude, and the score keys."""
+    others = [key for key in DENSITY_KEYS[1:] if _cfg(cfg, key, None) is not None]
+    if not _switch(cfg, "density_weights"):
+        if others:
+            raise ValueError("cfg.%s goes with cfg.density_weights = True" % others[0])
+        return None
+    if "density_voxel" not in others:
+        raise ValueError("cfg.density_weights goes with cfg.density_voxel (the voxel's edge in metres)")
+    voxel = _positive(_cfg(cfg, "density_voxel", None), "density_voxel")
+    cap = 1 if "density_cap" not in others else _count(cfg, "density_cap")
+    _one_image_per_launch(cfg, "density_weights", "one image per launch chain")
+    _excludes(cfg, "density_weights", SCORE_KEYS + ROBUST_KEYS + ("robust_images_per_launch", "polish_images_per_launch", "room_search",
+                                                                   "room_search_images", "depth_mask"))
+    return voxel, cap
+
+
+def voxel_rules(cfg):
+    """cfg.voxel_size (a positive finite number: the cloud of every room is replaced by its voxel grid's points as it is read, after
+    sample_rate and before everything else) with cfg.voxel_how ("centroid", the default, or "first") -> None without the keys, else
+    (voxel, how)"""
+    size, how = _cfg(cfg, "voxel_size", None), _cfg(cfg, "voxel_how", None)
+    if size is None:
+        if how is not None:
+            raise ValueError("cfg.voxel_how goes with cfg.voxel_size")
+        return None
+    size = _positive(size, "voxel_size")
+    how = VOXEL_HOW[0] if how is None else how
+    if not isinstance(how, str) or how not in VOXEL_HOW:
+        raise ValueError("cfg.voxel_how %r: one of %s" % (how, list(VOXEL_HOW)))
+    return size, how
+
+
 def robust_rules(cfg):
     """The robust keys in a dataset loop; cfg.robust_images_per_launch (an int >= 1) is such a run's group size."""
     if _cfg(cfg, "robust_images_per_launch", None) is not None:
@@ -335,13 +384,16 @@ DatasetPlan = collections.namedtuple("DatasetPlan", "route group_size parallel s
 
 def dataset_plan(cfg, loop):
     """What `loop` ("localize_stanford" / "localize_omniscenes") does with cfg, decided once, before any file is read: the rules above in
-    the loop's order — score, robust, the room search's polish (Stanford) else the known-room polish, room_search x images_per_launch —, then
-    route (plain | robust | polished | scored, or Stanford's rooms | rooms-polished), group_size (images per localize_group call), parallel,
+    the loop's order — score, density, voxel, robust, the room search's polish (Stanford) else the known-room polish, room_search x
+    images_per_launch —, then route (plain | robust | polished | scored, or Stanford's rooms | rooms-polished), group_size (images per
+    localize_group call), parallel,
     score (score_rules' triple or None), room_search (cfg's, where the loop searches: localize_omniscenes ignores the room-search keys) and
     sigmas (every result carries a covariance, the CSV its two sigma columns)."""
     stanford = {"localize_stanford": True, "localize_omniscenes": False}[loop]
     _refuse(cfg, loop, "depth_polish")
     score = score_rules(cfg)
+    density_rules(cfg)
+    voxel_rules(cfg)
     robust_rules(cfg)
     rooms_polished = stanford and room_polish_rules(cfg)
     polished = None if rooms_polished else polish_rules(cfg, loop)

@@ -27,8 +27,8 @@ from .cfg_rules import (dataset_plan, group_size as _group_size, polish_rules as
                         robust_rules as _check_robust_cfg, room_polish_rules as _check_room_polish_cfg, score_rules as _check_score_cfg)
 from .color_utils import color_match, color_mod
 from .omniloc import (omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_polished, omniloc_batch_images_robust,
-                      omniloc_batch_rooms_images, omniloc_batch_rooms_images_polished, score_weights)
-from .utils import make_input_images, make_input_scored, make_pano, out_of_room, resize_image, write_summaries
+                      omniloc_batch_rooms_images, omniloc_batch_rooms_images_polished, density_weights_of, score_weights)
+from .utils import make_input_images, make_input_scored, make_pano, out_of_room, resize_image, voxel_downsample, write_summaries
 
 
 def preprocess_colors(img, rgb, cfg):
@@ -208,20 +208,25 @@ def _query_images(orig, factors, dev):
             _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev))
 
 
-def _read_cloud(read, path, sample_rate, dev):
+def _read_cloud(read, path, sample_rate, dev, voxel=None):
+    """(xyz, rgb) of a room on the device.  voxel: cfg_rules.voxel_rules' (size, how) under cfg.voxel_size — the cloud is then replaced, once,
+    after sample_rate and before everything else, by its voxel grid's points (utils.voxel_downsample): every route sees a plain cloud."""
     xyz_np, rgb_np = read(path, sample_rate)
-    return torch.from_numpy(xyz_np).float().to(dev), torch.from_numpy(rgb_np).float().to(dev)
+    xyz, rgb = torch.from_numpy(xyz_np).float().to(dev), torch.from_numpy(rgb_np).float().to(dev)
+    if voxel is not None:
+        xyz, rgb = voxel_downsample(xyz, rgb, voxel[0], how=voxel[1])[:2]
+    return xyz, rgb
 
 
-def _cloud_cache(read, sample_rate, dev):
+def _cloud_cache(read, sample_rate, dev, voxel=None):
     """path -> (xyz, rgb) on the device through a one-entry cache: consecutive images of one room get the SAME tensors (what their group
-    key compares), and one room's cloud is held at a time."""
+    key compares), and one room's cloud is held at a time.  voxel: _read_cloud's."""
     cache = {}
 
     def cloud(path):
         if path not in cache:
             cache.clear()
-            cache[path] = _read_cloud(read, path, sample_rate, dev)
+            cache[path] = _read_cloud(read, path, sample_rate, dev, voxel)
         return cache[path]
     return cloud
 
@@ -430,7 +435,9 @@ def _localize_known_room(cfg, plan, jobs):
     one image at a time at the shipped and at the cfg-2 shape (tools/color_sets_bench.py).  One job: make_input_images is
     make_input, and the refinement is refine_image.  plan.route names a larger group's entry point: "polished" omniloc_batch_images_polished
     (the plain, robust or pruned chain, then the polish and / or covariance of all winners at once), "robust" omniloc_batch_images_robust;
-    "scored" has groups of one, initialised with make_input_scored and refined under the score weights of their maps."""
+    "scored" has groups of one, initialised with make_input_scored and refined under the score weights of their maps.  Under the density
+    keys (cfg_rules.density_rules; route "plain", groups of one) the refinement runs under omniloc.density_weights_of the room's points: one
+    weights tensor per room, hence one weighted pack for all of its images."""
     xyz = jobs[0].xyz
     rgb = jobs[0].rgb if all(j.rgb is jobs[0].rgb for j in jobs) else [j.rgb for j in jobs]
     if plan.route == "scored":                               # (one image per group: the rules refused every other group size)
@@ -444,7 +451,9 @@ def _localize_known_room(cfg, plan, jobs):
         if j.on_start is not None:
             j.on_start(tr, ro)
     if len(jobs) == 1:
-        return [refine_image(jobs[0].img_main, xyz, rgb, *starts[0], cfg)]
+        density = cfg_rules.density_rules(cfg)               # (one image per group under the density keys: the rules refused every other size)
+        weights = density_weights_of(xyz, *density) if density is not None else None
+        return [refine_image(jobs[0].img_main, xyz, rgb, *starts[0], cfg, weights=weights)]
     chain = ([j.img_main for j in jobs], xyz, rgb, [tr for tr, _ in starts], [ro for _, ro in starts], cfg)
     if plan.route == "polished":                             # (the gn keys and / or pose_covariance: the chain, then all winners at once)
         return [tuple(r) for r in omniloc_batch_images_polished(*chain)]
@@ -576,7 +585,7 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     if plan.room_search:
         return _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames)
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
-    read_cloud = _cloud_cache(data_utils.read_stanford, getattr(cfg, "sample_rate", 1), dev)
+    read_cloud = _cloud_cache(data_utils.read_stanford, getattr(cfg, "sample_rate", 1), dev, cfg_rules.voxel_rules(cfg))
 
     def cloud(k):
         area, _, room = _stanford_parts(filenames[k])
@@ -619,11 +628,12 @@ def _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames):
     sample_rate = getattr(cfg, "sample_rate", 1)
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
     init_dict = get_init_dict(cfg)
-    room_search, areas, found = plan.room_search, {}, {}
+    room_search, areas, found, voxel = plan.room_search, {}, {}, cfg_rules.voxel_rules(cfg)
     extra = _Columns(3 if plan.sigmas else 1, len(filenames))      # (the found room's index in the area's sorted listing[, sigma_t, sigma_r])
 
     def read_cloud(area, room):
-        return _read_cloud(data_utils.read_stanford, os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, room)), sample_rate, dev)
+        return _read_cloud(data_utils.read_stanford, os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, room)), sample_rate, dev,
+                           voxel)
 
     def area_rooms(area):
         if area not in areas:
@@ -708,7 +718,7 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
     dh, dw, mh, mw = _downsample(cfg)
     factors = (max(dh // 2, 1), max(dw // 2, 1), mh, mw)           # "match resolution with stanford" (localize.py:349-350)
-    read_cloud = _cloud_cache(data_utils.read_omniscenes, getattr(cfg, "sample_rate", 1), dev)
+    read_cloud = _cloud_cache(data_utils.read_omniscenes, getattr(cfg, "sample_rate", 1), dev, cfg_rules.voxel_rules(cfg))
 
     def names(k):
         video, frame = filenames[k].split("/")[-2:]

@@ -44,7 +44,7 @@ strict_reference_asserts = True
 # cloud, quantile box or translation grid (a dataset loop touches 4 cloud-side entries per room and 2 per image).
 # An entry is keyed by the identity of the tensors it was made from (address, shape, in-place version) and holds weak
 # references to them: a hit needs the very same live tensor, and entries whose tensors died are purged.
-_CAPACITY = {"cloud": 2, "cloud_w": 2, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "gd_rooms_images": 4, "trimgroups": 4}
+_CAPACITY = {"cloud": 2, "cloud_w": 2, "density": 4, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "gd_rooms_images": 4, "trimgroups": 4}
 
 
 class _PackCache:
@@ -340,6 +340,17 @@ def score_weights(maps, floor=0.0, min_count=1):
     points)."""
     n = int(maps.score3d.numel())
     return ops.score_weight_plane(n, maps.score3d, maps.count3d, floor, min_count)[0][:n].clone()
+
+
+# ------------------------------------------------------------------------------------------------ density weights
+# (not in the reference; build-defined, include/piccolo_hip.h, DESIGN.md section 2c) a source of per-point weights that needs neither a pose
+# nor the query image: a surface the scanner sampled fifty times as densely as another one otherwise gets fifty times the vote.
+def density_weights_of(xyz, voxel, cap=1):
+    """ops.VoxelGrid(xyz, voxel).weights(cap), cached per live xyz tensor and (voxel, cap): the SAME (N,) tensor object for every query image
+    of a room — packed_cloud keys its weighted pack on the identity of the weights tensor, so one tensor means one pack.  Eager (the grid
+    reads its voxel count back): the first image of a room pays for it."""
+    voxel, cap = ops.voxel_size(voxel), ops.density_cap(cap)
+    return _cached("density", (xyz,), lambda: ops.VoxelGrid(xyz, voxel).weights(cap), sub=(voxel, cap))
 
 
 # ------------------------------------------------------------------------------------------------ pose information / covariance

@@ -1268,6 +1268,116 @@ def score_weight_plane(n, score_packed, count_packed, floor=0.0, min_count=1, pl
     return plane, rng
 
 
+_VOXEL_BAD = ((1, "a NaN or infinite value"), (2, "a cell outside [-2^20, 2^20): the voxel is too small for the cloud's extent"),
+              (4, "a magnitude of 32768 or more"))
+
+
+def _voxel_bad(what, word):
+    """ValueError naming every bit of a voxel call's bad set"""
+    word = int(word)
+    if word:
+        raise ValueError("%s: %s" % (what, "; ".join(text for bit, text in _VOXEL_BAD if word & bit)))
+
+
+def voxel_size(voxel, what="voxel"):
+    """`voxel` as a float; ValueError unless it is a positive finite number.  Host only."""
+    if isinstance(voxel, bool) or not isinstance(voxel, (int, float)) or not (0.0 < float(voxel) < float("inf")):
+        raise ValueError("%s %r: a positive finite number" % (what, voxel))
+    return float(voxel)
+
+
+def density_cap(cap, what="cap"):
+    """`cap` as an int; ValueError unless it is an int >= 1.  Host only."""
+    if isinstance(cap, bool) or not isinstance(cap, int) or cap < 1:
+        raise ValueError("%s %r: an int >= 1" % (what, cap))
+    return int(cap)
+
+
+class VoxelGrid:
+    """The voxel grid of a cloud (pcl_voxel_grid; the rules: include/piccolo_hip.h): per axis
+    cell = floor((double)x / voxel), the origin at 0, voxels numbered in the order in which xyz's rows first reach them.
+      n, nvoxels     points, occupied voxels
+      cell           (N,) int32: the voxel of every point, in the order of xyz's rows (never the packed cloud's Morton order)
+      count, first   (V,) int32 / int64: a voxel's points and its lowest point index (strictly increasing with the voxel id)
+    The call runs EAGERLY and ends with one 8-byte D2H read (the voxel count, which sizes the outputs, and the bad set): it does not belong
+    inside a captured graph.  ValueError: an empty cloud, a voxel that is not a positive finite number, a NaN or infinite coordinate, a
+    cell outside [-2^20, 2^20), a coordinate of magnitude 32768 or more.
+    ws / buffers: a workspace of at least pcl_voxel_workspace_bytes(n) bytes and (count, first) buffers of N entries to use instead of fresh
+    ones (count and first are then views of them; entries at and beyond nvoxels are left as they were)."""
+
+    def __init__(self, xyz, voxel, ws=None, buffers=None):
+        lib = _lib.load()
+        self.voxel = voxel_size(voxel)
+        if not torch.is_tensor(xyz):
+            xyz = torch.as_tensor(xyz)
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError("xyz must be (N, 3)")
+        self.n = int(xyz.shape[0])
+        if self.n <= 0:
+            raise ValueError("empty point cloud")
+        xyz = _dev(xyz)
+        nws = lib.pcl_voxel_workspace_bytes(self.n)
+        if nws == 0:
+            raise ValueError("VoxelGrid: %d points are more than a cloud holds" % self.n)
+        ws = _voxel_ws(ws, nws)
+        dev = xyz.device
+        if buffers is None:
+            count, first = torch.empty(self.n, dtype=torch.int32, device=dev), torch.empty(self.n, dtype=torch.int64, device=dev)
+        else:
+            count, first = buffers
+            if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == self.n and first.is_cuda
+                    and first.dtype == torch.int64 and first.is_contiguous() and first.numel() == self.n):
+                raise ValueError("VoxelGrid: buffers must be contiguous GPU tensors (int32 count, int64 first) of N entries")
+        self.cell = torch.empty(self.n, dtype=torch.int32, device=dev)
+        words = torch.empty(2, dtype=torch.int32, device=dev)                     # (nvoxels, bad)
+        _lib.check(lib.pcl_voxel_grid(_ptr(xyz), self.n, self.voxel, _ptr(self.cell), _ptr(count), _ptr(first), _ptr(words),
+                                      ctypes.c_void_p(words.data_ptr() + 4), _ptr(ws), nws, _stream()), "pcl_voxel_grid")
+        nvoxels, bad = (int(v) for v in words.tolist())
+        _voxel_bad("VoxelGrid: xyz holds", bad)
+        self.nvoxels = nvoxels
+        self.count, self.first = count[:nvoxels], first[:nvoxels]
+        if buffers is None:                                                       # (keep V entries, not N)
+            self.count, self.first = self.count.clone(), self.first.clone()
+        self.xyz = xyz
+
+    def centroids(self, rgb, ws=None):
+        """(xyz', rgb'), (V, 3) float32 each in voxel-id order: per voxel the mean of its points' coordinates and colours over exact int64
+        sums of llrint(a * 65536) — the same bits whatever the launch shape (pcl_voxel_centroids).  Eager, one 4-byte D2H read (the bad
+        set).  ValueError: rgb that is not (N, 3), a NaN or infinite colour, a colour of magnitude 32768 or more."""
+        lib = _lib.load()
+        if not torch.is_tensor(rgb) or rgb.dim() != 2 or tuple(rgb.shape) != (self.n, 3):
+            raise ValueError("rgb must be one (N, 3) tensor")
+        rgb = _dev(rgb)
+        nws = lib.pcl_voxel_workspace_bytes(self.n)
+        ws = _voxel_ws(ws, nws)
+        dev = self.xyz.device
+        xyz_out, rgb_out = torch.empty(self.nvoxels, 3, dtype=F32, device=dev), torch.empty(self.nvoxels, 3, dtype=F32, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.pcl_voxel_centroids(_ptr(self.xyz), _ptr(rgb), self.n, _ptr(self.cell), _ptr(self.count), self.nvoxels, _ptr(xyz_out),
+                                           _ptr(rgb_out), _ptr(bad), _ptr(ws), nws, _stream()), "pcl_voxel_centroids")
+        _voxel_bad("VoxelGrid.centroids: the cloud holds", bad.item())
+        return xyz_out, rgb_out
+
+    def weights(self, cap=1):
+        """(N,) float32 density weights in the order of xyz's rows: 1 where the point's voxel holds at most `cap` points, else
+        (float)((double)cap / count) (pcl_density_weights) — with cap = 1 every occupied voxel has total weight 1."""
+        cap = density_cap(cap)
+        w = torch.empty(self.n, dtype=F32, device=self.cell.device)
+        _lib.check(_lib.load().pcl_density_weights(_ptr(self.cell), _ptr(self.count), self.n, self.nvoxels, cap, _ptr(w), _stream()),
+                   "pcl_density_weights")
+        return w
+
+
+def _voxel_ws(ws, nws):
+    """the caller's workspace, checked, or a fresh one (DESIGN.md section 2b's contract for it — results independent of its contents, no
+    write outside the queried bytes — is pinned by tests/test_voxel.py with the same three fill words, on a workspace the test brings)"""
+    if ws is None:
+        return torch.empty(max(int(nws), 16), dtype=torch.uint8, device=device())
+    if not (torch.is_tensor(ws) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nws):
+        raise ValueError("ws must be a contiguous uint8 GPU tensor of at least pcl_voxel_workspace_bytes(n) = %d bytes" % nws)
+    return ws
+
+
 def depth_mask(cloud, trans, rot, resolution, tau=None, stride=1):
     """(B, n) uint8 GPU tensor in PACKED point order: scatter-min visibility of every point for every pose on a z-buffer grid of
     `resolution` = (depth_h, depth_w) cells (the DEPTH grid — see default_depth — not the panorama's size) built from every

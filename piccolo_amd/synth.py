@@ -50,6 +50,43 @@ def box_room(n_points, seed=0):
     return xyz.astype(np.float32), rgb.astype(np.float32)
 
 
+SCANNER = (-2.0, 1.0, -0.3)        # scanned_room's default scanner position: off centre, 1.2 m above the floor
+
+
+def scanned_room(n_points, seed=0, scanner=SCANNER):
+    """(xyz, rgb) float32 (N,3): the box room as ONE scanner position inside it sees it — the density of the points on a surface is
+    proportional to cos(incidence) / r^2, the solid angle a patch subtends, obtained by rejection from box_room's uniform-by-area draw
+    (a draw is kept with probability (d / r^3) / (1 / d_min^2): d its face's distance from the scanner, r its own, d_min the nearest
+    face's).  The floor under the scanner is sampled tens of times as densely as the far wall, the way a real scan is.  Same colour
+    field as box_room; deterministic per (n_points, seed, scanner)."""
+    s = np.asarray(scanner, np.float64).reshape(3)
+    if not np.all(np.abs(s) < ROOM / 2):
+        raise ValueError("scanned_room: the scanner %r must stand inside the room" % (tuple(scanner),))
+    rng = np.random.default_rng(seed)
+    areas = np.array([ROOM[1] * ROOM[2]] * 2 + [ROOM[0] * ROOM[2]] * 2 + [ROOM[0] * ROOM[1]] * 2)
+    top = 1.0 / float(np.min(np.concatenate([ROOM / 2 - s, ROOM / 2 + s]))) ** 2
+    kept, have = [], 0
+    while have < n_points:
+        m = max(4 * int(n_points), 1024)
+        face, u, v, coin = rng.choice(6, size=m, p=areas / areas.sum()), rng.random(m), rng.random(m), rng.random(m)
+        axis, sign = face // 2, np.where(face % 2 == 0, -1.0, 1.0)
+        xyz = np.empty((m, 3), dtype=np.float64)
+        for k in range(3):
+            a, b = [c for c in range(3) if c != k]
+            on = axis == k
+            xyz[on, k] = sign[on] * ROOM[k] / 2
+            xyz[on, a] = (u[on] - 0.5) * ROOM[a]
+            xyz[on, b] = (v[on] - 0.5) * ROOM[b]
+        d = np.abs(xyz[np.arange(m), axis] - s[axis])
+        r = np.linalg.norm(xyz - s[None, :], axis=1)
+        keep = coin * top < d / r ** 3
+        kept.append(xyz[keep])
+        have += int(keep.sum())
+    xyz = np.concatenate(kept)[:n_points]
+    rgb = 0.5 + 0.45 * np.sin(xyz @ _K.T + _PHI)
+    return xyz.astype(np.float32), rgb.astype(np.float32)
+
+
 # interior boxes of `furnished_room`: (centre, size) in metres — a pillar, a cabinet against a wall, a table-high block
 _FURNITURE = (((1.2, 0.6, 0.0), (0.5, 0.5, 3.0)), ((-2.6, -1.8, -0.5), (1.2, 0.6, 2.0)), ((0.3, -1.4, -1.0), (1.6, 0.9, 1.0)))
 

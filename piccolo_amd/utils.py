@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .cfg_rules import VOXEL_HOW  # noqa: F401  (the one list of the accepted `how` values of voxel_downsample)
 from .omniloc import color_set_groups, packed_cloud, packed_cloud_sets, packed_pano, shared_rgb
 
 __all__ = ["cloud2idx", "sample_from_img", "warp_from_img", "reshape_img_tensor", "make_pano", "quantile", "out_of_room", "rot_from_ypr", "trim_input_loss",
@@ -163,6 +164,41 @@ def make_pano(xyz, rgb, resolution=(200, 400), return_torch=False):
     if return_torch:
         return _like(img, xyz)
     return img.cpu().numpy().astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ voxel grid
+# (not in the reference; build-defined, include/piccolo_hip.h)
+
+
+def voxel_downsample(xyz, rgb, voxel, how="centroid"):
+    """(xyz', rgb', count, first) of the voxel grid of `voxel` metres over the cloud (ops.VoxelGrid), GPU tensors in voxel-id order — the
+    order in which xyz's rows first reach the voxels: one point per occupied voxel, its centroid in position and colour
+    (how="centroid", ops.VoxelGrid.centroids: exact integer sums, the same bits on every run) or its lowest-index point, copied bit for
+    bit (how="first"); count (V,) int32 the voxel's points, first (V,) int64 its lowest point index.  The result is just a cloud: every
+    route takes it, at no weighted-kernel cost.  rgb is ONE (N, 3) tensor: down-sample before the colour preprocessing, which works on
+    whatever cloud it is given.  Eager (the voxel count is read back).  ValueError: what ops.VoxelGrid refuses, a list of colour sets, an
+    unknown `how`."""
+    if how not in VOXEL_HOW:
+        raise ValueError("voxel_downsample: how %r: one of %s" % (how, list(VOXEL_HOW)))
+    if isinstance(rgb, (list, tuple)):
+        raise ValueError("voxel_downsample takes one (N, 3) rgb tensor, not a list of colour sets (down-sample before the colour preprocessing)")
+    if not torch.is_tensor(xyz):
+        xyz = torch.as_tensor(xyz)
+    if not torch.is_tensor(rgb):
+        rgb = torch.as_tensor(rgb)
+    if rgb.dim() != 2 or rgb.shape != xyz.shape:
+        raise ValueError("xyz and rgb must both be (N, 3)")
+    grid = ops.VoxelGrid(xyz, voxel)
+    if how == "first":
+        return grid.xyz[grid.first], ops._dev(rgb)[grid.first], grid.count, grid.first
+    return grid.centroids(rgb) + (grid.count, grid.first)
+
+
+def density_weights(xyz, voxel, cap=1):
+    """(N,) GPU weights in the order of xyz's rows, usable as `weights=` wherever weights are taken: 1 where the point's voxel (of `voxel`
+    metres, ops.VoxelGrid) holds at most `cap` points, else cap / count — with cap = 1 every occupied voxel votes once, a larger cap leaves
+    sparse regions alone and trims only the dense ones.  Eager.  omniloc.density_weights_of caches the tensor per room."""
+    return ops.VoxelGrid(xyz, voxel).weights(cap)
 
 
 # ------------------------------------------------------------------------------------------------ initialisation
