@@ -334,6 +334,55 @@ int pcl_voxel_grid(const float *xyz, int64_t n, double voxel, int32_t *cell, int
 int pcl_voxel_centroids(const float *xyz, const float *rgb, int64_t n, const int32_t *cell, const int32_t *count, int64_t nvoxels, float *xyz_out,
                         float *rgb_out, int32_t *bad, void *workspace, size_t workspace_bytes, void *stream);
 int pcl_density_weights(const int32_t *cell, const int32_t *count, int64_t n, int64_t nvoxels, int64_t cap, float *w, void *stream);
+/* From the voxel grid to the cloud's up direction (additive to ABI 12; build-defined: the reference calls data_utils.obtain_align_matrix
+ * and never defines it).  DESIGN.md section 2d.
+ *   moments    (nvoxels, 9) int64, zeroed by the call.  q(a) = llrint((double)a * 65536), d_i = q(x_i) - q(x_first[v]) per axis;
+ *              S1 = sum d (3), S2 = sum d_a d_b in the order xx xy xz yy yz zz: exact integers, the same bits for any launch shape.
+ *              The sums are about the voxel's FIRST point, which the point order chooses: another order gives other moments and
+ *              the same scatter matrix count S2 - S1 S1^T, exactly, hence the same normals.
+ *              Range: points of one cell lie less than a voxel apart, |d| <= voxel 65536 + 1; at voxel <= 2 m d^2 < 2^34.0001 and
+ *              PCL_MAX_POINTS = 2^27 of them stay below 2^63; a voxel above 2 m is refused.  `voxel` is the grid's.  A point with a bad
+ *              coordinate (*bad as pcl_voxel_centroids sets it: 1 NaN or infinite, 4 magnitude >= 32768), one whose cell[] lies outside
+ *              [0, nvoxels), and one whose voxel's first[] lies outside [0, n) or names a bad point, adds nothing.
+ *   normals    A = count S2 - S1 S1^T exactly (128-bit integers), every entry rounded once to double and divided by
+ *              ((double)count * (double)count * 2^32): the covariance in m^2.  Eigenvalues l0 <= l1 <= l2 by cyclic Jacobi in double
+ *              (8 sweeps, contraction off).  normal (nvoxels, 3): the unit eigenvector of l0, its component of largest magnitude (the
+ *              first of equals) positive; planarity = (l1 - l0) / l2; eig (nvoxels, 3) = (l0, l1, l2), or a null pointer.  A voxel with
+ *              count < min_count or l2 <= 0 gets zeros.
+ *   vote       w_v = count_v * llrint(planarity_v * 4096) (a voxel with planarity outside (0, 1], count <= 0 or a normal that is not a
+ *              unit vector does not vote).  Up: the normals folded into z >= 0 and within max_tilt degrees of +z fill 64 x 64 int64 bins
+ *              over (n_x / n_z, n_y / n_z) in [-tan max_tilt, tan max_tilt]^2; the heaviest bin (the lowest index of equals) starts the
+ *              estimate; three rounds of e <- normalise(sum w_v llrint(n 2^20)) over the folded normals with n . e >= cos 5 degrees.
+ *              Walls (params->yaw): the normals within 10 degrees of the horizontal plane after the up rotation; their azimuth modulo 90
+ *              degrees fills 360 bins; within 3 degrees of the heaviest bin's centre sum w_v llrint(cos 4 psi 2^20), sum w_v llrint(sin 4 psi 2^20)
+ *              name 4 phi, phi in (-45, 45] degrees.  rot = Rz(-phi) * (the minimal rotation taking up to +z): x_aligned = rot x.
+ *              status 0; 1: no voxel inside the tilt cone, rot is the identity; 2: no wall normals, phi = 0.  weight[]: what the up bins, the
+ *              last cone round, the wall bins and the wall mean kept.  All accumulation is in integers: one set of bits for any launch
+ *              shape.  pcl_align_workspace_bytes(nvoxels) is one size for every count (0 outside 1..PCL_MAX_POINTS); the call initialises it.
+ *   transform  out = R (x - a) in fp32, d = x - a, out_r = (R_r0 d_0 + R_r1 d_1) + R_r2 d_2, contraction off; rot (9) and trans (3)
+ *              are device floats.  (pcl_transform_cloud below is the pose form: yaw / pitch / roll, the reference's operation order.)
+ * PCL_EINVAL, before any HIP call: a null pointer (eig may be null), n outside 1..PCL_MAX_POINTS, nvoxels outside 1..n (moments) or
+ * 1..PCL_MAX_POINTS, voxel not in (0, 2], min_count < 3, max_tilt not in (0, 45].  PCL_EWORKSPACE: workspace_bytes below the query. */
+typedef struct pcl_align_params {
+    double max_tilt;  /* degrees, in (0, 45] */
+    int32_t yaw;      /* != 0: the wall direction too */
+    int32_t reserved;
+} PclAlignParams;
+typedef struct pcl_align_out {
+    double up[3];
+    double rot[9];    /* row-major */
+    double cos_tilt, sin_tilt, cos_yaw, sin_yaw;
+    int64_t weight[4];
+    int64_t status;
+} PclAlignOut;
+int pcl_voxel_moments(const float *xyz, int64_t n, double voxel, const int32_t *cell, const int64_t *first, int64_t nvoxels, int64_t *moments,
+                      int32_t *bad, void *stream);
+int pcl_voxel_normals(const int64_t *moments, const int32_t *count, int64_t nvoxels, int64_t min_count, float *normal, float *planarity,
+                      float *eig, void *stream);
+size_t pcl_align_workspace_bytes(int64_t nvoxels);
+int pcl_align_vote(const float *normal, const float *planarity, const int32_t *count, int64_t nvoxels, const PclAlignParams *params,
+                   PclAlignOut *out, void *workspace, size_t workspace_bytes, void *stream);
+int pcl_align_transform_cloud(const float *xyz, int64_t n, const float *rot, const float *trans, float *out, void *stream);
 
 size_t pcl_pano_bytes(int H, int W, int pano_format);
 int pcl_pano_pack(const float *img_hwc, int H, int W, float *pano, void *stream);

@@ -38,6 +38,13 @@ class GdRoom(_c.Structure):
     _fields_ = [("cloud", _vp), ("n", _i64), ("box", _vp)]
 
 
+class AlignParams(_c.Structure):
+    _fields_ = [("max_tilt", _dbl), ("yaw", _c.c_int32), ("reserved", _c.c_int32)]
+
+
+ALIGN_OUT_WORDS = 21      # PclAlignOut: 16 doubles (up, rot, cos / sin of tilt and yaw), then 5 int64 (four weights, status)
+
+
 # name -> (restype, argtypes); every symbol include/piccolo_hip.h declares
 SIGNATURES = {
     "pcl_abi_version": (_int, []),
@@ -87,6 +94,11 @@ SIGNATURES = {
     "pcl_voxel_grid": (_int, [_vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcl_voxel_centroids": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcl_density_weights": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "pcl_voxel_moments": (_int, [_vp, _i64, _dbl, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "pcl_voxel_normals": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "pcl_align_workspace_bytes": (_sz, [_i64]),
+    "pcl_align_vote": (_int, [_vp, _vp, _vp, _i64, _c.POINTER(AlignParams), _vp, _vp, _sz, _vp]),
+    "pcl_align_transform_cloud": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "pcl_pano_bytes": (_sz, [_int, _int, _int]),
     "pcl_pano_pack": (_int, [_vp, _int, _int, _vp, _vp]),
     "pcl_cloud_order_workspace_bytes": (_sz, [_i64]),

@@ -17,6 +17,9 @@ next to, and which chain a dataset loop routes a run through.  Host only — no 
                      and density_voxel                                                        omniloc.density_weights_of; no entry point (weights=)
     voxel            voxel_size                 nothing: the down-sampled cloud is a cloud    any: localize._read_cloud applies it once per room; the
                                                                                               synthetic driver refuses it (utils.voxel_downsample)
+    align            align_cloud = True and     nothing: the aligned cloud is a cloud         any: localize._read_cloud aligns every room once, before the
+                     gravity_aligned = False                                                  voxel keys; results are mapped back to the cloud's own frame;
+                                                                                              the synthetic driver refuses it (utils.align_cloud)
 
 An entry point refuses the families it does not take with one _refuse(cfg, its name) (REFUSES) and validates the ones it does with their
 schedules; a dataset loop resolves its cfg once, with dataset_plan, and dispatches on the plan."""
@@ -36,6 +39,7 @@ SCORE_KEYS = ("score_weights", "score_split", "score_floor", "score_min_count")
 DENSITY_KEYS = ("density_weights", "density_voxel", "density_cap")
 VOXEL_KEYS = ("voxel_size", "voxel_how")
 VOXEL_HOW = ("centroid", "first")
+ALIGN_KEYS = ("align_cloud", "align_voxel", "align_max_tilt", "align_yaw", "align_min_count")
 _EXTENSIONS = {
     "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
     "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust, omniloc_batch_images_polished and localize.refine_image's parallel "
@@ -51,6 +55,7 @@ _EXTENSIONS = {
     "voxel": (VOXEL_KEYS, None, "the dataset loops do, once per room as its cloud is read; elsewhere down-sample the cloud with "
                                 "utils.voxel_downsample"),
     "depth_polish": (("depth_polish",), None, "omniloc_batch and localize.refine_image's parallel branch do"),
+    "align": (ALIGN_KEYS, None, "the dataset loops do, once per room as its cloud is read; elsewhere align the cloud with utils.align_cloud"),
 }
 # The families an entry point refuses, in the order it looks for them: it returns every candidate, records frames, or runs a chain without the
 # robust plane, the covariance or the polish.  omniloc_batch must go on accepting the score and density keys: refine_image hands it the
@@ -66,7 +71,7 @@ REFUSES = {
     "omniloc_batch_rooms": ("robust", "pose_covariance", "gn", "score", "density", "depth_polish"),
     "omniloc_batch_rooms_images": ("robust", "pose_covariance", "gn", "score", "density", "depth_polish"),
     "omniloc_batch_rooms_images_polished": ("robust", "score", "density", "depth_polish"),
-    "localize_synthetic": ("pose_covariance", "gn", "score", "density", "voxel", "depth_polish"),
+    "localize_synthetic": ("pose_covariance", "gn", "score", "density", "voxel", "align", "depth_polish"),
     "localize_stanford": ("pose_covariance", "gn", "depth_polish"),
     "localize_omniscenes": ("pose_covariance", "gn", "depth_polish"),
 }
@@ -319,6 +324,35 @@ def voxel_rules(cfg):
     return size, how
 
 
+AlignRules = collections.namedtuple("AlignRules", "voxel max_tilt yaw min_count")
+
+
+def align_rules(cfg):
+    """cfg.align_cloud = True (the cloud of every room is turned, as it is read — after sample_rate and before voxel_size —, so that its up
+    direction is +z: utils.align_cloud; every result is mapped back to the cloud's own frame) with cfg.align_voxel (a positive number, at
+    most 2, default 0.1), align_max_tilt (degrees in (0, 45], default 40), align_yaw (a bool: the walls along the axes too, default off) and
+    align_min_count (an int >= 3, default 8) -> None without the keys, else AlignRules(voxel, max_tilt, yaw, min_count).  It needs
+    cfg.gravity_aligned = False beside it: on a cloud that is declared aligned there is nothing to align.  (gravity_aligned = False
+    WITHOUT the switch stays the NotImplementedError of localize._require_gravity_aligned.)"""
+    others = [key for key in ALIGN_KEYS[1:] if _cfg(cfg, key, None) is not None]
+    if not _switch(cfg, "align_cloud"):
+        if others:
+            raise ValueError("cfg.%s goes with cfg.align_cloud = True" % others[0])
+        return None
+    if _cfg(cfg, "gravity_aligned", True):
+        raise ValueError("cfg.align_cloud goes with cfg.gravity_aligned = False (a cloud declared gravity-aligned has nothing to align)")
+    voxel = 0.1 if "align_voxel" not in others else _positive(_cfg(cfg, "align_voxel", None), "align_voxel")
+    if voxel > ops.ALIGN_MAX_VOXEL:
+        raise ValueError("cfg.align_voxel %r: at most %g (metres)" % (voxel, ops.ALIGN_MAX_VOXEL))
+    tilt = _cfg(cfg, "align_max_tilt", None)
+    if tilt is not None and (not isinstance(tilt, (int, float)) or isinstance(tilt, bool) or not 0.0 < float(tilt) <= 45.0):
+        raise ValueError("cfg.align_max_tilt %r: degrees in (0, 45]" % (tilt,))
+    min_count = _cfg(cfg, "align_min_count", None)
+    if min_count is not None and (not _is_int(min_count) or min_count < 3):
+        raise ValueError("cfg.align_min_count %r: an int >= 3" % (min_count,))
+    return AlignRules(voxel, 40.0 if tilt is None else float(tilt), _switch(cfg, "align_yaw"), 8 if min_count is None else int(min_count))
+
+
 def robust_rules(cfg):
     """The robust keys in a dataset loop; cfg.robust_images_per_launch (an int >= 1) is such a run's group size."""
     if _cfg(cfg, "robust_images_per_launch", None) is not None:
@@ -379,16 +413,32 @@ def on(cfg, key):
     return bool(_cfg(cfg, key, None))
 
 
-DatasetPlan = collections.namedtuple("DatasetPlan", "route group_size parallel score room_search sigmas")
+class DatasetPlan(collections.namedtuple("DatasetPlan", "route group_size parallel score room_search sigmas")):
+    """dataset_plan's answer; .align is align_rules' answer, None without the align keys.  It is an attribute, not a field — the tuple keeps
+    its six, which older tests pin —, so `==`, iteration and a plain tuple(plan) do not see it; with_align and _replace carry it."""
+    align = None
+
+    def with_align(self, align):
+        plan = DatasetPlan(*self)
+        plan.align = align
+        return plan
+
+    def _replace(self, **fields):
+        return DatasetPlan(*super()._replace(**fields)).with_align(self.align)
 
 
 def dataset_plan(cfg, loop):
     """What `loop` ("localize_stanford" / "localize_omniscenes") does with cfg, decided once, before any file is read: the rules above in
-    the loop's order — score, density, voxel, robust, the room search's polish (Stanford) else the known-room polish, room_search x
+    the loop's order — align, score, density, voxel, robust, the room search's polish (Stanford) else the known-room polish, room_search x
     images_per_launch —, then route (plain | robust | polished | scored, or Stanford's rooms | rooms-polished), group_size (images per
     localize_group call), parallel,
     score (score_rules' triple or None), room_search (cfg's, where the loop searches: localize_omniscenes ignores the room-search keys) and
-    sigmas (every result carries a covariance, the CSV its two sigma columns)."""
+    sigmas (every result carries a covariance, the CSV its two sigma columns); the plan's attribute .align is align_rules' answer."""
+    align = align_rules(cfg)
+    return _dataset_plan(cfg, loop).with_align(align)
+
+
+def _dataset_plan(cfg, loop):
     stanford = {"localize_stanford": True, "localize_omniscenes": False}[loop]
     _refuse(cfg, loop, "depth_polish")
     score = score_rules(cfg)

@@ -83,6 +83,17 @@ def load_cloud(filepath, sample_rate=1, cache=True):
             torch.from_numpy(np.ascontiguousarray(rgb)).float().to(dev))
 
 
+def obtain_align_matrix(xyz_np, **options):
+    """(align_trans (3, 1), align_rot (3, 3)) as float64 numpy: what the reference calls at localize.py:156 / :371 under
+    gravity_aligned = False and never defines — `xyz = (align_rot @ (xyz.T - align_trans)).T` has its up direction on +z.  The answer is
+    utils.align_cloud's (voxel plane normals and an integer vote, on the GPU); options are its keywords (voxel, max_tilt, yaw, min_count).
+    align_trans is zeros: the rotation is about the origin."""
+    import torch
+    from . import utils
+    _, align_rot, align_trans, _ = utils.align_cloud(torch.from_numpy(np.ascontiguousarray(xyz_np, dtype=np.float32)), **options)
+    return align_trans, align_rot
+
+
 def _euler_xyz_matrix(angles):
     """scipy Rotation.from_euler('xyz', angles).as_matrix(): extrinsic rotations about x, then y, then z,
     R = Rz(c) Ry(b) Rx(a) (data_utils.py:78-79)."""

@@ -28,7 +28,7 @@ from .cfg_rules import (dataset_plan, group_size as _group_size, polish_rules as
 from .color_utils import color_match, color_mod
 from .omniloc import (omniloc_all, omniloc_batch, omniloc_batch_images, omniloc_batch_images_polished, omniloc_batch_images_robust,
                       omniloc_batch_rooms_images, omniloc_batch_rooms_images_polished, density_weights_of, score_weights)
-from .utils import make_input_images, make_input_scored, make_pano, out_of_room, resize_image, voxel_downsample, write_summaries
+from .utils import align_cloud, make_input_images, make_input_scored, make_pano, out_of_room, resize_image, voxel_downsample, write_summaries
 
 
 def preprocess_colors(img, rgb, cfg):
@@ -208,27 +208,87 @@ def _query_images(orig, factors, dev):
             _to_img(resize_image(orig, orig.shape[1] // mw, orig.shape[0] // mh), dev))
 
 
-def _read_cloud(read, path, sample_rate, dev, voxel=None):
-    """(xyz, rgb) of a room on the device.  voxel: cfg_rules.voxel_rules' (size, how) under cfg.voxel_size — the cloud is then replaced, once,
-    after sample_rate and before everything else, by its voxel grid's points (utils.voxel_downsample): every route sees a plain cloud."""
+def pose_to_cloud_frame(t, R, align_rot, align_trans):
+    """A pose (t (3, 1), R (3, 3)) found on the ALIGNED cloud x' = align_rot (x - align_trans), as a pose of the cloud's own frame: from
+    R (R_a (x - a) - t) = (R R_a) (x - (a + R_a^T t)), t0 = a + R_a^T t and R0 = R R_a.  Computed in float64 -> float32 numpy."""
+    Ra, a = np.asarray(align_rot, np.float64).reshape(3, 3), np.asarray(align_trans, np.float64).reshape(3, 1)
+    t, R = np.asarray(t, np.float64).reshape(3, 1), np.asarray(R, np.float64).reshape(3, 3)
+    return (a + Ra.T @ t).astype(np.float32), (R @ Ra).astype(np.float32)
+
+
+def pose_from_cloud_frame(t0, R0, align_rot, align_trans):
+    """pose_to_cloud_frame's inverse (what the reference does to the ground truth, localize.py:185-186): t = R_a (t0 - a), R = R0 R_a^T."""
+    Ra, a = np.asarray(align_rot, np.float64).reshape(3, 3), np.asarray(align_trans, np.float64).reshape(3, 1)
+    t0, R0 = np.asarray(t0, np.float64).reshape(3, 1), np.asarray(R0, np.float64).reshape(3, 3)
+    return (Ra @ (t0 - a)).astype(np.float32), (R0 @ Ra.T).astype(np.float32)
+
+
+# A room's alignment (cfg.align_cloud): utils.align_cloud's rot, trans and info, and xyz — the points of the cloud the routes see, in the
+# room's OWN frame (what the result images show under the mapped pose)
+_Alignment = collections.namedtuple("_Alignment", "rot trans info xyz")
+
+
+class _Cloud(tuple):
+    """(xyz, rgb) of a room on the device; .align: its _Alignment under cfg.align_cloud, else None"""
+    align = None
+
+
+def _read_cloud(read, path, sample_rate, dev, voxel=None, align=None):
+    """(xyz, rgb) of a room on the device, a _Cloud.  align: cfg_rules.align_rules' answer under cfg.align_cloud — the cloud is turned once,
+    after sample_rate and before the voxel keys (cells depend on the frame), so that its up direction is +z (utils.align_cloud).  voxel:
+    cfg_rules.voxel_rules' (size, how) under cfg.voxel_size — the cloud is then replaced, once, before everything else, by its voxel grid's
+    points (utils.voxel_downsample).  Every route sees a plain cloud."""
     xyz_np, rgb_np = read(path, sample_rate)
     xyz, rgb = torch.from_numpy(xyz_np).float().to(dev), torch.from_numpy(rgb_np).float().to(dev)
+    own = xyz
+    if align is not None:
+        xyz, rot, trans, info = align_cloud(own, *align)
     if voxel is not None:
         xyz, rgb = voxel_downsample(xyz, rgb, voxel[0], how=voxel[1])[:2]
-    return xyz, rgb
+    cloud = _Cloud((xyz, rgb))
+    if align is not None:
+        if voxel is not None:                          # (the down-sampled points, back in the room's frame: R_a^T x + a)
+            own = ops.align_transform_cloud(xyz, torch.from_numpy(rot.T.copy()), torch.from_numpy(-(rot @ trans)))
+        cloud.align = _Alignment(rot, trans, info, own)
+    return cloud
 
 
-def _cloud_cache(read, sample_rate, dev, voxel=None):
+def _cloud_cache(read, sample_rate, dev, voxel=None, align=None, log=None):
     """path -> (xyz, rgb) on the device through a one-entry cache: consecutive images of one room get the SAME tensors (what their group
-    key compares), and one room's cloud is held at a time.  voxel: _read_cloud's."""
+    key compares), and one room's cloud is held at a time.  voxel, align: _read_cloud's; log: a dict that gets every aligned room's
+    tilt, yaw (degrees) and status under the cloud file's stem."""
     cache = {}
 
     def cloud(path):
         if path not in cache:
             cache.clear()
-            cache[path] = _read_cloud(read, path, sample_rate, dev, voxel)
+            cache[path] = _read_cloud(read, path, sample_rate, dev, voxel, align)
+            _log_alignment(log, path, cache[path].align)
         return cache[path]
     return cloud
+
+
+def _log_alignment(log, path, align):
+    if log is not None and align is not None:
+        log[os.path.splitext(os.path.basename(path))[0]] = {"tilt": float(np.degrees(align.info["tilt"])), "yaw": float(np.degrees(align.info["yaw"])),
+                                                            "status": int(align.info["status"])}
+
+
+def _gt_for_skip(align, gt_trans, gt_rot):
+    """the ground-truth translation the skip rule tests against the cloud the routes see: mapped into the aligned frame under an alignment"""
+    return gt_trans if align is None else pose_from_cloud_frame(gt_trans, gt_rot, align.rot, align.trans)[0]
+
+
+def _results_to_cloud_frame(aligns, results):
+    """every (t, R, ...) found on an aligned cloud as a pose of the room's own frame (pose_to_cloud_frame); the rest of a result — loss,
+    covariance (the aligned frame's), found room — stays"""
+    out = []
+    for align, result in zip(aligns, results):
+        if align is not None:
+            t0, R0 = pose_to_cloud_frame(result[0], result[1], align.rot, align.trans)
+            result = (torch.from_numpy(t0), torch.from_numpy(R0)) + tuple(result[2:])
+        out.append(result)
+    return out
 
 
 def _fmt(a):
@@ -253,20 +313,24 @@ def _save_result_image(path, gt_img8, xyz, rgb, t, R, resolution):
     Image.fromarray(np.concatenate([gt, np.asarray(render, np.uint8)], axis=0)).save(path)
 
 
-def _save_starting_points(dirname, stem, gt_img8, xyz, rgb, input_trans, input_rot):
+def _save_starting_points(dirname, stem, gt_img8, xyz, rgb, input_trans, input_rot, align=None):
     """cfg.save_starting_point (localize.py:457-471): for every starting pose of the refinement, the query panorama stacked over
-    the cloud rendered from that pose at half the panorama's resolution, as <dirname>/<stem>_<idx>.png."""
+    the cloud rendered from that pose at half the panorama's resolution, as <dirname>/<stem>_<idx>.png.  align: the room's _Alignment —
+    the poses are then mapped to the room's own frame and rendered over its own points."""
     from .utils import rot_from_ypr
     for idx in range(int(input_trans.shape[0])):
-        R = rot_from_ypr(input_rot[idx].detach().cpu()).float()
-        _save_result_image(os.path.join(dirname, "{}_{}.png".format(stem, idx)), gt_img8, xyz, rgb,
-                           input_trans[idx].detach().cpu().float(), R, (gt_img8.shape[0] // 2, gt_img8.shape[1] // 2))
+        t, R = input_trans[idx].detach().cpu().float(), rot_from_ypr(input_rot[idx].detach().cpu()).float()
+        if align is not None:
+            t, R = (torch.from_numpy(v) for v in pose_to_cloud_frame(t, R, align.rot, align.trans))
+            xyz = align.xyz
+        _save_result_image(os.path.join(dirname, "{}_{}.png".format(stem, idx)), gt_img8, xyz, rgb, t, R,
+                           (gt_img8.shape[0] // 2, gt_img8.shape[1] // 2))
 
 
 def _require_gravity_aligned(cfg):
     """localize.py:141,155-157 / :355,370-372: with gravity_aligned = False the reference calls data_utils.obtain_align_matrix,
     which its data_utils.py does not define (AttributeError on the first room); refused here before anything is loaded."""
-    if not getattr(cfg, "gravity_aligned", True):
+    if not getattr(cfg, "gravity_aligned", True) and not cfg_rules.on(cfg, "align_cloud"):       # (with the switch: cfg_rules.align_rules)
         raise NotImplementedError("gravity_aligned = False: the reference's own path stops at the undefined "
                                   "data_utils.obtain_align_matrix (localize.py:155); align the cloud beforehand")
 
@@ -337,6 +401,12 @@ class _Job:
     area: int = None                   # room search: the area and its [(room name, xyz, rgb)]
     rooms: list = None
     on_start: object = None            # on_start(input_trans, input_rot), called once the starting poses exist (save_starting_point)
+    align: object = None               # known room under cfg.align_cloud: the room's _Alignment (xyz is then the aligned cloud)
+
+    @property
+    def show_xyz(self):
+        """the points a result image shows under the reported pose: the room's own frame"""
+        return self.xyz if self.align is None else self.align.xyz
 
     @property
     def group_key(self):
@@ -462,6 +532,19 @@ def _localize_known_room(cfg, plan, jobs):
     return omniloc_batch_images(*chain, batch_mode=plan.parallel)
 
 
+def _localize_aligned(cfg, plan, jobs):
+    """_localize_known_room, its poses mapped back to the room's own frame where the jobs' cloud was aligned (cfg.align_cloud): errors, CSV
+    rows, LAST_RUN and the result images are all made from the mapped poses.  A covariance stays the aligned frame's."""
+    return _results_to_cloud_frame([j.align for j in jobs], _localize_known_room(cfg, plan, jobs))
+
+
+def _note_alignments(plan, aligned):
+    """LAST_RUN["align"] (rank 0, which reads every room for the ground truths): per room the tilt and yaw found, in degrees, and the vote's
+    status — 1 (no voxel inside the tilt cone: the cloud was left as it is) is reported here, not raised"""
+    if LAST_RUN and plan.align is not None:
+        LAST_RUN["align"] = dict(aligned)
+
+
 SIGMA_HEADER = ["sigma_t (m)", "sigma_r (degrees)"]
 
 
@@ -585,7 +668,8 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     if plan.room_search:
         return _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames)
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
-    read_cloud = _cloud_cache(data_utils.read_stanford, getattr(cfg, "sample_rate", 1), dev, cfg_rules.voxel_rules(cfg))
+    aligned = {}
+    read_cloud = _cloud_cache(data_utils.read_stanford, getattr(cfg, "sample_rate", 1), dev, cfg_rules.voxel_rules(cfg), plan.align, aligned)
 
     def cloud(k):
         area, _, room = _stanford_parts(filenames[k])
@@ -594,23 +678,28 @@ def localize_stanford(cfg, writer=None, log_dir="./log", root="./data/stanford")
     def ground_truth(k):
         area, img_name, _ = _stanford_parts(filenames[k])
         gt_trans, gt_rot = _f32(*data_utils.obtain_gt_stanford(area, img_name, root=os.path.join(root, "pose")))
-        skipped = bool(out_of_room(cloud(k)[0], torch.from_numpy(gt_trans), quant)) and not getattr(cfg, "eval_full", False)
+        room = cloud(k)
+        skipped = (bool(out_of_room(room[0], torch.from_numpy(_gt_for_skip(room.align, gt_trans, gt_rot)), quant))
+                   and not getattr(cfg, "eval_full", False))
         return gt_trans, gt_rot, skipped
 
     def load(k):
-        xyz, rgb = cloud(k)
+        room = cloud(k)
+        xyz, rgb = room
         orig = read_image(filenames[k])
         img, img_main = _query_images(orig, _downsample(cfg), dev)
         rgb_k = rgb
         if getattr(cfg, "sharpen_color", False):        # localize.py:175-179: only the INITIALISATION image is equalised
             img, rgb_k = color_mod(img, rgb, int(getattr(cfg, "num_bins", 256)))
-        return _Job(img, img_main, orig, xyz, rgb_k, show_rgb=rgb)
+        return _Job(img, img_main, orig, xyz, rgb_k, show_rgb=rgb, align=room.align)
 
     def report(k, job, result, row):
-        _stanford_report(filenames[k], log_dir, job, job.xyz, job.show_rgb, result, row)
+        _stanford_report(filenames[k], log_dir, job, job.show_xyz, job.show_rgb, result, row)
 
-    return _run_known_room(plan, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, plan, jobs), report),
-                           "stanford_results.csv", STANFORD_HEADER, _stanford_row_prefix, stanford_success)
+    table = _run_known_room(plan, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_aligned(cfg, plan, jobs), report),
+                            "stanford_results.csv", STANFORD_HEADER, _stanford_row_prefix, stanford_success)
+    _note_alignments(plan, aligned)
+    return table
 
 
 def _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames):
@@ -630,10 +719,14 @@ def _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames):
     init_dict = get_init_dict(cfg)
     room_search, areas, found, voxel = plan.room_search, {}, {}, cfg_rules.voxel_rules(cfg)
     extra = _Columns(3 if plan.sigmas else 1, len(filenames))      # (the found room's index in the area's sorted listing[, sigma_t, sigma_r])
+    frames, aligned = {}, {}                                       # cfg.align_cloud: (area, room) -> its _Alignment; LAST_RUN's log
 
     def read_cloud(area, room):
-        return _read_cloud(data_utils.read_stanford, os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, room)), sample_rate, dev,
-                           voxel)
+        path = os.path.join(root, "pcd_not_aligned/area_{}/{}.txt".format(area, room))
+        cloud = _read_cloud(data_utils.read_stanford, path, sample_rate, dev, voxel, plan.align)
+        frames[(area, room)] = cloud.align                         # (every room its own alignment)
+        _log_alignment(aligned, path, cloud.align)
+        return tuple(cloud)
 
     def area_rooms(area):
         if area not in areas:
@@ -648,7 +741,8 @@ def _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames):
         gt_cloud = next((xyz for name, xyz, _ in area_rooms(area) if name == gt_room), None)
         if gt_cloud is None:                           # (a list that leaves the ground-truth room out: its cloud still decides the skip)
             gt_cloud = read_cloud(area, gt_room)[0]
-        skipped = bool(out_of_room(gt_cloud, torch.from_numpy(gt_trans), quant)) and not getattr(cfg, "eval_full", False)
+        skipped = (bool(out_of_room(gt_cloud, torch.from_numpy(_gt_for_skip(frames.get((area, gt_room)), gt_trans, gt_rot)), quant))
+                   and not getattr(cfg, "eval_full", False))
         return gt_trans, gt_rot, skipped
 
     def load(k):
@@ -664,10 +758,13 @@ def _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames):
             res = [localize_in_rooms(jobs[0].img_init, jobs[0].img_main, rooms, cfg, init_dict)]
         else:
             res = localize_images_in_rooms([j.img_init for j in jobs], [j.img_main for j in jobs], rooms, cfg, init_dict)
-        return [(one[1], one[2], one[3], one[0]) + tuple(one[5:6]) for one in res]      # (t, R, loss, room[, cov])
+        res = [(one[1], one[2], one[3], one[0]) + tuple(one[5:6]) for one in res]       # (t, R, loss, room[, cov])
+        return _results_to_cloud_frame([frames.get((j.area, j.rooms[one[3]][0])) for j, one in zip(jobs, res)], res)
 
     def report(k, job, result, row):
         name, xyz, rgb = job.rooms[result[3]]
+        if frames.get((job.area, name)) is not None:
+            xyz = frames[(job.area, name)].xyz
         extra.note(k, (float(result[3]),) + (pose_sigmas(result[4]) if plan.sigmas else ()))
         _stanford_report(filenames[k], log_dir, job, xyz, rgb, result, row, "found room : {}\n".format(name))
 
@@ -694,6 +791,7 @@ def _localize_stanford_rooms(cfg, plan, writer, log_dir, root, filenames):
         LAST_RUN["room_accuracy"] = sum(hits) / len(hits) if hits else 0.0
         LAST_RUN["found_rooms"] = {filenames[k]: v[0] for k, v in found.items()}
         print("Room accuracy : {}".format(LAST_RUN["room_accuracy"]))
+    _note_alignments(plan, aligned)
     return table
 
 
@@ -718,7 +816,8 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
     quant = getattr(cfg, "out_of_room_quantile", 0.05)
     dh, dw, mh, mw = _downsample(cfg)
     factors = (max(dh // 2, 1), max(dw // 2, 1), mh, mw)           # "match resolution with stanford" (localize.py:349-350)
-    read_cloud = _cloud_cache(data_utils.read_omniscenes, getattr(cfg, "sample_rate", 1), dev, cfg_rules.voxel_rules(cfg))
+    aligned = {}
+    read_cloud = _cloud_cache(data_utils.read_omniscenes, getattr(cfg, "sample_rate", 1), dev, cfg_rules.voxel_rules(cfg), plan.align, aligned)
 
     def names(k):
         video, frame = filenames[k].split("/")[-2:]
@@ -730,10 +829,12 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
 
     def ground_truth(k):
         gt_trans, gt_rot = _f32(*data_utils.obtain_gt_omniscenes(filenames[k]))
-        return gt_trans, gt_rot, bool(out_of_room(cloud(k)[0], torch.from_numpy(gt_trans), quant))
+        room = cloud(k)
+        return gt_trans, gt_rot, bool(out_of_room(room[0], torch.from_numpy(_gt_for_skip(room.align, gt_trans, gt_rot)), quant))
 
     def load(k):
-        xyz, rgb = cloud(k)
+        room = cloud(k)
+        xyz, rgb = room
         video, _, stem = names(k)
         orig = resize_image(read_image(filenames[k]), 2048, 1024)   # localize.py:372
         if getattr(cfg, "synth_const", None) is not None:           # synthetic illumination changes, localize.py:375-385
@@ -748,15 +849,17 @@ def localize_omniscenes(cfg, writer=None, log_dir="./log", root="./data/omniscen
         on_start = None
         if getattr(cfg, "save_starting_point", False) and log_dir is not None:
             def on_start(input_trans, input_rot):
-                _save_starting_points(os.path.join(log_dir, "starting_points", video), stem, orig, xyz, rgb_k, input_trans, input_rot)
-        return _Job(*_query_images(orig, factors, dev), orig, xyz, rgb_k, show_rgb=rgb_k, on_start=on_start)
+                _save_starting_points(os.path.join(log_dir, "starting_points", video), stem, orig, xyz, rgb_k, input_trans, input_rot, room.align)
+        return _Job(*_query_images(orig, factors, dev), orig, xyz, rgb_k, show_rgb=rgb_k, on_start=on_start, align=room.align)
 
     def report(k, job, result, row):
         video, frame, stem = names(k)
         print("\n{}/{}\ntranslation error : {}\nrotation error : {}\n".format(video, frame, float(row[13]), float(row[14])))
         if log_dir is not None:
-            _save_result_image(os.path.join(log_dir, "results", video, stem + ".png"), job.orig, job.xyz, job.show_rgb, result[0], result[1],
+            _save_result_image(os.path.join(log_dir, "results", video, stem + ".png"), job.orig, job.show_xyz, job.show_rgb, result[0], result[1],
                                (job.img_main.shape[0] // 2, job.img_main.shape[1] // 2))
 
-    return _run_known_room(plan, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_known_room(cfg, plan, jobs), report),
-                           "omniscenes_results.csv", OMNISCENES_HEADER, lambda f: ["{}/{}".format(*f.split("/")[-2:])], omniscenes_success)
+    table = _run_known_room(plan, writer, log_dir, filenames, _Dataset(ground_truth, load, lambda jobs: _localize_aligned(cfg, plan, jobs), report),
+                            "omniscenes_results.csv", OMNISCENES_HEADER, lambda f: ["{}/{}".format(*f.split("/")[-2:])], omniscenes_success)
+    _note_alignments(plan, aligned)
+    return table

@@ -1367,6 +1367,124 @@ class VoxelGrid:
                    "pcl_density_weights")
         return w
 
+    def moments(self, out=None):
+        """(V, 9) int64 in voxel-id order: per voxel the exact sums S1 = sum d (3) and S2 = sum d_a d_b (xx, xy, xz, yy, yz, zz) of
+        d = llrint(x * 65536) - llrint(x_first * 65536), the offsets from the voxel's first point (pcl_voxel_moments): integers, the same
+        bits for any launch shape.  (Which point is a voxel's first depends on the order of xyz's rows: another order gives other moments
+        and, exactly, the same scatter matrix count S2 - S1 S1^T, so the same normals.)  Eager, one 4-byte D2H read (the bad set).  ValueError: a voxel above 2 m (the sums' range rule,
+        include/piccolo_hip.h).  out: a contiguous (V, 9) int64 GPU tensor to write into."""
+        if self.voxel > ALIGN_MAX_VOXEL:
+            raise ValueError("VoxelGrid.moments: voxel %r: at most %g m (the exact sums' range)" % (self.voxel, ALIGN_MAX_VOXEL))
+        dev = self.xyz.device
+        if out is None:
+            out = torch.empty(self.nvoxels, 9, dtype=torch.int64, device=dev)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (self.nvoxels, 9)):
+            raise ValueError("VoxelGrid.moments: out must be a contiguous (V, 9) int64 GPU tensor")
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().pcl_voxel_moments(_ptr(self.xyz), self.n, self.voxel, _ptr(self.cell), _ptr(self.first), self.nvoxels, _ptr(out),
+                                                 _ptr(bad), _stream()), "pcl_voxel_moments")
+        _voxel_bad("VoxelGrid.moments: xyz holds", bad.item())
+        return out
+
+    def normals(self, min_count=8, return_eig=False):
+        """(normal (V, 3), planarity (V,)[, eig (V, 3)]) float32 in voxel-id order, from moments(): the plane fit of every voxel with at
+        least min_count points (pcl_voxel_normals) — the unit eigenvector of the covariance's smallest eigenvalue, signed so that its
+        component of largest magnitude is positive; planarity = (l1 - l0) / l2; eig = (l0, l1, l2) in m^2.  A voxel with fewer points, or
+        all of whose points coincide, gets zeros.  ValueError: min_count that is not an int >= 3."""
+        return voxel_normals_of(self.moments(), self.count, min_count, return_eig)
+
+
+ALIGN_MAX_VOXEL = 2.0
+
+
+def align_min_count(min_count, what="min_count"):
+    """`min_count` as an int; ValueError unless it is an int >= 3 (a plane needs three points).  Host only."""
+    if isinstance(min_count, bool) or not isinstance(min_count, int) or min_count < 3:
+        raise ValueError("%s %r: an int >= 3" % (what, min_count))
+    return int(min_count)
+
+
+def align_max_tilt(max_tilt, what="max_tilt"):
+    """`max_tilt` in degrees as a float; ValueError unless it is a number in (0, 45].  Host only."""
+    if isinstance(max_tilt, bool) or not isinstance(max_tilt, (int, float)) or not (0.0 < float(max_tilt) <= 45.0):
+        raise ValueError("%s %r: degrees in (0, 45]" % (what, max_tilt))
+    return float(max_tilt)
+
+
+def voxel_normals_of(moments, count, min_count=8, return_eig=False):
+    """VoxelGrid.normals on moments and counts the caller holds: (V, 9) int64 and (V,) int32 GPU tensors."""
+    min_count = align_min_count(min_count)
+    if not (torch.is_tensor(moments) and moments.is_cuda and moments.dtype == torch.int64 and moments.is_contiguous() and moments.dim() == 2
+            and moments.shape[1] == 9 and moments.shape[0] > 0):
+        raise ValueError("moments must be a contiguous (V, 9) int64 GPU tensor")
+    V = int(moments.shape[0])
+    count = _dev(count, torch.int32)
+    if tuple(count.shape) != (V,):
+        raise ValueError("count must be (V,), one entry per row of moments")
+    dev = moments.device
+    normal, planarity = torch.empty(V, 3, dtype=F32, device=dev), torch.empty(V, dtype=F32, device=dev)
+    eig = torch.empty(V, 3, dtype=F32, device=dev) if return_eig else None
+    _lib.check(_lib.load().pcl_voxel_normals(_ptr(moments), _ptr(count), V, min_count, _ptr(normal), _ptr(planarity), _ptr(eig), _stream()),
+               "pcl_voxel_normals")
+    return (normal, planarity, eig) if return_eig else (normal, planarity)
+
+
+def align_vote(normal, planarity, count, max_tilt=40.0, yaw=False, ws=None):
+    """The up direction (and with yaw the wall direction) of a cloud from its voxels' normals (V, 3), planarities (V,) and counts (V,)
+    (pcl_align_vote; the recipe: include/piccolo_hip.h).  Eager, one D2H copy of the 168-byte record.  -> a dict:
+      up (3,), rot (3, 3)   float64 numpy: the up vector in the cloud's frame, and align_rot — x_aligned = rot @ x
+      tilt, yaw             radians: atan2 of the record's (sin, cos) pairs, taken here on the host; yaw in (-pi/4, pi/4]
+      cos_tilt, sin_tilt, cos_yaw, sin_yaw    the pairs themselves
+      weights               (up bins, last cone round, wall bins, wall mean): the integer weight each stage kept
+      status                0; 1: no voxel inside the tilt cone (rot is the identity); 2: no wall normals (yaw 0)
+    ws: a contiguous uint8 GPU workspace of at least pcl_align_workspace_bytes(V) bytes to use instead of a fresh one (DESIGN.md section 2b's
+    contract for it — the same bits whatever it held, no write outside the queried bytes — is pinned by tests/test_align.py).
+    ValueError: max_tilt outside (0, 45] degrees, yaw that is not a bool, shapes that do not agree, a workspace that is too small."""
+    import math
+    max_tilt = align_max_tilt(max_tilt)
+    if not isinstance(yaw, bool):
+        raise ValueError("yaw %r: a bool" % (yaw,))
+    if not torch.is_tensor(normal) or normal.dim() != 2 or normal.shape[1] != 3 or normal.shape[0] <= 0:
+        raise ValueError("normal must be (V, 3)")
+    V = int(normal.shape[0])
+    normal, planarity, count = _dev(normal), _dev(planarity), _dev(count, torch.int32)
+    if tuple(planarity.shape) != (V,) or tuple(count.shape) != (V,):
+        raise ValueError("planarity and count must be (V,), one entry per normal")
+    lib = _lib.load()
+    nws = lib.pcl_align_workspace_bytes(V)
+    if ws is None:
+        ws = torch.empty(int(nws), dtype=torch.uint8, device=normal.device)
+    elif not (torch.is_tensor(ws) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nws):
+        raise ValueError("ws must be a contiguous uint8 GPU tensor of at least pcl_align_workspace_bytes(V) = %d bytes" % nws)
+    out = torch.empty(_lib.ALIGN_OUT_WORDS, dtype=torch.float64, device=normal.device)
+    params = _lib.AlignParams(max_tilt, int(yaw), 0)
+    _lib.check(lib.pcl_align_vote(_ptr(normal), _ptr(planarity), _ptr(count), V, ctypes.byref(params), _ptr(out), _ptr(ws), nws, _stream()),
+               "pcl_align_vote")
+    rec = out.cpu()
+    d, w = rec[:16].numpy(), rec[16:].view(torch.int64).tolist()
+    return {"up": d[0:3].copy(), "rot": d[3:12].reshape(3, 3).copy(), "cos_tilt": float(d[12]), "sin_tilt": float(d[13]), "cos_yaw": float(d[14]),
+            "sin_yaw": float(d[15]), "tilt": math.atan2(float(d[13]), float(d[12])), "yaw": math.atan2(float(d[15]), float(d[14])),
+            "weights": tuple(w[:4]), "status": int(w[4])}
+
+
+def align_transform_cloud(xyz, rot, trans):
+    """(N, 3) float32: rot (x - trans) per point, rot a (3, 3) matrix and trans 3 values (pcl_align_transform_cloud: fp32, d = x - trans,
+    out_r = (R_r0 d_0 + R_r1 d_1) + R_r2 d_2, no contraction).  The reference's `np.matmul(align_rot, xyz.T - align_trans).T`
+    (localize.py:157) with stated bits.  (transform_cloud is the POSE form: a translation and yaw / pitch / roll.)"""
+    if not torch.is_tensor(xyz):
+        xyz = torch.as_tensor(xyz)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] <= 0:
+        raise ValueError("xyz must be (N, 3) with at least one point")
+    x = _dev(xyz)
+    r, t = _dev(torch.as_tensor(rot)), _dev(torch.as_tensor(trans))
+    if r.numel() != 9 or (r.dim() == 2 and tuple(r.shape) != (3, 3)):
+        raise ValueError("rot must be a (3, 3) matrix")
+    if t.numel() != 3:
+        raise ValueError("trans must hold 3 values")
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().pcl_align_transform_cloud(_ptr(x), int(x.shape[0]), _ptr(r), _ptr(t), _ptr(out), _stream()), "pcl_align_transform_cloud")
+    return out
+
 
 def _voxel_ws(ws, nws):
     """the caller's workspace, checked, or a fresh one (DESIGN.md section 2b's contract for it — results independent of its contents, no

@@ -201,6 +201,47 @@ def density_weights(xyz, voxel, cap=1):
     return ops.VoxelGrid(xyz, voxel).weights(cap)
 
 
+# ------------------------------------------------------------------------------------------------ plane normals and gravity alignment
+# (not in the reference, which calls an undefined data_utils.obtain_align_matrix; build-defined)
+def voxel_normals(xyz, voxel, min_count=8):
+    """(normal (V, 3), planarity (V,), grid): the plane fit of every voxel of `voxel` metres (at most 2) with at least min_count points, in
+    voxel-id order (ops.VoxelGrid.normals), and the grid itself.  A voxel with fewer points has normal 0 and planarity 0.  Eager."""
+    ops.align_min_count(min_count)
+    grid = ops.VoxelGrid(xyz, voxel)
+    return grid.normals(min_count) + (grid,)
+
+
+def point_normals(xyz, voxel, min_count=8):
+    """(normal (N, 3), planarity (N,)): every point gets its voxel's normal and planarity (voxel_normals through grid.cell), in the order of
+    xyz's rows."""
+    normal, planarity, grid = voxel_normals(xyz, voxel, min_count)
+    cell = grid.cell.long()
+    return normal[cell], planarity[cell]
+
+
+def align_cloud(xyz, voxel=0.1, max_tilt=40.0, yaw=False, min_count=8):
+    """(xyz_aligned, align_rot, align_trans, info): the cloud turned so that its up direction is +z (and with yaw=True its walls run along
+    the axes): voxel_normals, ops.align_vote, then xyz_aligned = align_rot (x - align_trans) on the device (ops.align_transform_cloud).
+    align_rot is (3, 3) float64 numpy; align_trans is zeros of shape (3, 1): the rotation is about the origin — the reference's form
+    (localize.py:157) keeps a translation slot and it is filled with 0.  info: ops.align_vote's dict (tilt and yaw in radians, status, the
+    weights each stage kept).  With status 1 (no voxel inside the tilt cone) the cloud is returned as it is, with the identity.
+    ValueError before any launch: what ops.VoxelGrid refuses, a voxel above 2 m, min_count below 3, max_tilt outside (0, 45], yaw that is
+    not a bool."""
+    voxel = ops.voxel_size(voxel)
+    if voxel > ops.ALIGN_MAX_VOXEL:
+        raise ValueError("align_cloud: voxel %r: at most %g m" % (voxel, ops.ALIGN_MAX_VOXEL))
+    ops.align_min_count(min_count)
+    ops.align_max_tilt(max_tilt)
+    if not isinstance(yaw, bool):
+        raise ValueError("yaw %r: a bool" % (yaw,))
+    normal, planarity, grid = voxel_normals(xyz, voxel, min_count)
+    info = ops.align_vote(normal, planarity, grid.count, max_tilt=max_tilt, yaw=yaw)
+    align_trans = np.zeros((3, 1), dtype=np.float64)
+    if info["status"] == 1:
+        return grid.xyz, info["rot"], align_trans, info
+    return ops.align_transform_cloud(grid.xyz, torch.from_numpy(info["rot"]), torch.zeros(3)), info["rot"], align_trans, info
+
+
 # ------------------------------------------------------------------------------------------------ initialisation
 def _trim_order(xyz, cloud, pano, trans, rot, groups):
     """The trim launch's work list (ops.TrimOrder), cached per (cloud points, candidate grid, panorama size / texel layout): it does not
