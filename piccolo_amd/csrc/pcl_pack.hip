@@ -398,7 +398,7 @@ __global__ void __launch_bounds__(PCL_BLOCK) pcl_pano_pack_f16_kernel(const floa
         for (int c = 0; c < 3; c++) {
             float f = s[c], k = rintf(f * 255.f);
             bad = bad || !(k >= 0.f && k <= 255.f) || __fdiv_rn(k, 255.f) != f;
-            lv[c] = k;
+            lv[c] = k + 0.f;                                   // -0.0 is level 0: the +0 half, as the integer formats store it
         }
         if (bad) *not_exact = 1;
     }
