@@ -391,6 +391,29 @@ int pcl_pano_pack_u8p(const float *img_hwc, int H, int W, uint32_t *pano, int *n
 int pcl_pano_pack_u8v(const float *img_hwc, int H, int W, uint32_t *pano, int *not_exact, void *stream);
 int pcl_pano_pack_f16(const float *img_hwc, int H, int W, void *pano, int *not_exact, void *stream);
 
+/* ---- panorama pyramid (build-defined, additive to ABI 12: the reference resizes its query on the host to two fixed sizes and has no
+ * pyramid).  Level 0 is the query image, every value exactly k/255.  Level l is made from level l - 1 — cascaded, never from level 0
+ * directly — by ALIGNED 2 x 2 blocks in integer arithmetic on the levels k (aligned blocks: nothing wraps in azimuth; a plain box
+ * pyramid: NO latitude weighting):
+ *   - a pixel is BLACK when its three channels are 0: the loss's "no data" marker (mask = not (c == 0 on all three channels));
+ *   - cnt = the non-black pixels of the block; cnt == 0: the output is black;
+ *   - otherwise, per channel, k_out = (sum of k over the non-black pixels + cnt / 2) / cnt in integer division (round to nearest, ties up);
+ *   - if that rounds every channel to 0, every channel whose sum equals the largest channel sum gets level 1 (the only reachable case:
+ *     cnt == 3, sums 1, 1, 1) — so a coarse pixel is black iff there is no data under it;
+ *   - a level's float value is the correctly rounded fp32 quotient k / 255 (as the pack kernels test it): every level is an exact-level
+ *     image again and takes the F16 / U8 texel formats.
+ * pcl_pano_pyramid_bytes: the bytes of the packed texels of levels 1..levels, level l in format formats[l - 1] (PCL_PANO_F16, _U8 or
+ * _F32) at a 256-byte aligned offset, its region pcl_pano_bytes(H >> l, W >> l, format) rounded up to 256 bytes; 0 for anything refused:
+ * levels outside 1..4, H or W not a multiple of 2^levels, another format, NULL.
+ * pcl_pano_pyramid: ONE launch for all levels.  Writes every byte of `texels` (pcl_pano_pyramid_bytes of them) once: per level the
+ * zero-bordered texels, byte for byte what the pack kernel of that format writes for the level's float image, and zeros up to the next
+ * 256-byte boundary.  images (nullable): the float (H >> l, W >> l, 3) level images, level 1 first, one behind the other.  *not_exact
+ * (device int, caller zeroes it) is set when a source value is not exactly k/255 — pcl_pano_pack_u8's pattern; the outputs are then
+ * meaningless.  img_hwc must be 8-byte aligned (PCL_EINVAL otherwise). */
+size_t pcl_pano_pyramid_bytes(int H, int W, int levels, const int *formats);
+int pcl_pano_pyramid(const float *img_hwc, int H, int W, int levels, const int *formats, void *texels, float *images, int *not_exact,
+                     void *stream);
+
 /* ---- sampling loss (+ gradient) ----------------------------------------------------------------------------
  * Replaces SamplingLoss.forward (omniloc.py:171-202), BatchSamplingLoss.forward (omniloc.py:311-356), the forward
  * in trim_input_loss (utils.py:484-499) and sampling_loss (omniloc.py:105-157), plus — with with_grad != 0 — the
@@ -542,6 +565,10 @@ int pcl_gd_set_panos(void *state, const uint64_t *panos, int B, void *stream);
  * packed panoramas; B = nimages * per_image).  The addresses travel as kernel arguments — nothing is copied to the device, so
  * nothing waits for the work the stream already holds (one launch per 64 images). */
 int pcl_gd_set_pano_groups(void *state, const uint64_t *panos_host, int nimages, int per_image, void *stream);
+/* The plateau scheduler starts over (additive to ABI 12; one small launch): in both copies of the state, `best` and `num_bad` of every
+ * candidate become what pcl_gd_init writes (+inf, 0).  Every other byte stays: lr, Adam's moments, the step count, the pose records.
+ * For a chain that goes on against another panorama level (pcl_pano_pyramid), whose losses do not compare with the last level's. */
+int pcl_gd_plateau_reset(void *state, int B, void *stream);
 /* The end of omniloc_batch, omniloc.py:271-277, for nimages x per_image candidates (B = nimages * per_image): per image the
  * candidate whose LAST forward had the smallest loss (torch.argmin semantics: first of equal minima, a NaN loss wins), as
  * winners [nimages][16] = post-step translation (3), R = RZ(yaw) RY(pitch) RX(roll) of the post-step angles (9, row-major),

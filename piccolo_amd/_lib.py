@@ -107,6 +107,9 @@ SIGNATURES = {
     "pcl_pano_pack_u8p": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "pcl_pano_pack_u8v": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "pcl_pano_pack_f16": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
+    "pcl_pano_pyramid_bytes": (_sz, [_int, _int, _int, _c.POINTER(_int)]),
+    "pcl_pano_pyramid": (_int, [_vp, _int, _int, _int, _c.POINTER(_int), _vp, _vp, _vp, _vp]),
+    "pcl_gd_plateau_reset": (_int, [_vp, _int, _vp]),
     "pcl_loss_workspace_bytes": (_sz, [_i64, _int]),
     "pcl_sampling_loss": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "pcl_sampling_loss_weighted": (_int, [_vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _sz, _vp]),

@@ -20,6 +20,9 @@ next to, and which chain a dataset loop routes a run through.  Host only — no 
     align            align_cloud = True and     nothing: the aligned cloud is a cloud         any: localize._read_cloud aligns every room once, before the
                      gravity_aligned = False                                                  voxel keys; results are mapped back to the cloud's own frame;
                                                                                               the synthetic driver refuses it (utils.align_cloud)
+    pyramid          pyramid_iters (an int or   depth_mask, weights=, the robust, score,      "plain" (parallel), any images_per_launch; omniloc_batch (next to
+                     a list: 1 .. 4 switches)   density and prune keys, room_search           the gn keys and pose_covariance, which run at level 0),
+                                                                                              omniloc_batch_images and localize.refine_image's parallel branch
 
 An entry point refuses the families it does not take with one _refuse(cfg, its name) (REFUSES) and validates the ones it does with their
 schedules; a dataset loop resolves its cfg once, with dataset_plan, and dispatches on the plan."""
@@ -40,6 +43,7 @@ DENSITY_KEYS = ("density_weights", "density_voxel", "density_cap")
 VOXEL_KEYS = ("voxel_size", "voxel_how")
 VOXEL_HOW = ("centroid", "first")
 ALIGN_KEYS = ("align_cloud", "align_voxel", "align_max_tilt", "align_yaw", "align_min_count")
+PYRAMID_KEYS = ("pyramid_iters", "pyramid_reset")
 _EXTENSIONS = {
     "prune": (("prune_iters", "prune_keep"), "prune_iters / cfg.prune_keep", "the batch refinements do"),
     "robust": (ROBUST_KEYS, None, "omniloc_batch, omniloc_batch_images_robust, omniloc_batch_images_polished and localize.refine_image's parallel "
@@ -56,6 +60,8 @@ _EXTENSIONS = {
                                 "utils.voxel_downsample"),
     "depth_polish": (("depth_polish",), None, "omniloc_batch and localize.refine_image's parallel branch do"),
     "align": (ALIGN_KEYS, None, "the dataset loops do, once per room as its cloud is read; elsewhere align the cloud with utils.align_cloud"),
+    "pyramid": (PYRAMID_KEYS, None, "omniloc_batch, omniloc_batch_images and localize.refine_image's parallel branch do; the known-room dataset "
+                                    "loops on their plain route"),
 }
 # The families an entry point refuses, in the order it looks for them: it returns every candidate, records frames, or runs a chain without the
 # robust plane, the covariance or the polish.  omniloc_batch must go on accepting the score and density keys: refine_image hands it the
@@ -194,6 +200,30 @@ def robust_schedule(cfg):
     if _cfg(cfg, "prune_iters", None) is not None or _cfg(cfg, "prune_keep", None) is not None:
         raise ValueError("cfg.robust_iters does not combine with cfg.prune_iters / cfg.prune_keep")
     return iters, kind, k
+
+
+def pyramid_schedule(cfg, shape=None):
+    """(pyramid_iters as a list, pyramid_reset) of a coarse-to-fine refinement under cfg.pyramid_iters (an int, or a strictly increasing
+    list inside (0, num_iter): one entry per coarse level, at most ops.PYRAMID_MAX_LEVELS) and cfg.pyramid_reset (a bool, default False:
+    the plateau scheduler carries on across the levels), or None when the keys are absent.  [10, 30] at num_iter 100 runs 10 iterations
+    on level 2, 20 on level 1 and 70 on the image itself.  shape: the query image's (H, W), where it is known — both must be multiples
+    of 2^len(pyramid_iters).  The keys exclude cfg.depth_mask and the robust, score, density and prune keys (weights= is an argument:
+    the entry points refuse it beside the keys).  Host only."""
+    iters, reset = (_cfg(cfg, key, None) for key in PYRAMID_KEYS)
+    if iters is None:
+        if reset is not None:
+            raise ValueError("cfg.pyramid_reset goes with cfg.pyramid_iters")
+        return None
+    iters = _int_list(cfg, "pyramid_iters")
+    _inside_num_iter(iters, "pyramid_iters", int(_cfg(cfg, "num_iter", 100)))
+    if len(iters) > ops.PYRAMID_MAX_LEVELS:
+        raise ValueError("cfg.pyramid_iters %r: at most %d coarse levels" % (iters, ops.PYRAMID_MAX_LEVELS))
+    reset = _switch(cfg, "pyramid_reset")
+    _no_depth_mask(cfg, "pyramid_iters")
+    _excludes(cfg, "pyramid_iters", ROBUST_KEYS + SCORE_KEYS + DENSITY_KEYS + ("prune_iters", "prune_keep"))
+    if shape is not None:
+        ops.pyramid_shape(int(shape[0]), int(shape[1]), len(iters), "cfg.pyramid_iters %r" % (iters,))
+    return iters, reset
 
 
 def pose_covariance_flag(cfg):
@@ -448,6 +478,11 @@ def _dataset_plan(cfg, loop):
     rooms_polished = stanford and room_polish_rules(cfg)
     polished = None if rooms_polished else polish_rules(cfg, loop)
     room_search = (_cfg(cfg, "room_search", None) or None) if stanford else None
+    if pyramid_schedule(cfg) is not None:
+        # (the plain route alone: the room searches, the robust and the polished images forms have no coarse-to-fine chain)
+        if room_search or polished is not None:
+            _refuse(cfg, "a room search" if room_search else "a polished run (cfg.polish_images_per_launch)", "pyramid")
+        _needs_parallel(cfg, "pyramid_iters", "coarse-to-fine")
     if room_search:
         if int(_cfg(cfg, "images_per_launch", 1)) > 1:
             raise ValueError("room_search does not combine with images_per_launch > 1: a room search groups its images with room_search_images")

@@ -19,7 +19,7 @@ device (csrc/pcl_gd.hip) without a host round trip per iteration.  Differences a
     point of the Morton-ordered cloud (default: pcl_depth_default's choice; every point is still tested against it);
   * extra, optional cfg keys, all absent by default = reference behaviour, ruled by cfg_rules (its table: what goes with what, which entry
     point takes which family) and described at their sections below: prune_iters / prune_keep, robust_iters / robust_kind / robust_k,
-    pose_covariance, gn_iters / gn_step_cap / gn_lambda / gn_objective / gn_delta; the score keys belong to the known-room dataset loops —
+    pose_covariance, gn_iters / gn_step_cap / gn_lambda / gn_objective / gn_delta, pyramid_iters / pyramid_reset; the score keys belong to the known-room dataset loops —
     here score_maps / score_weights give a caller the weights for weights=;
   * cfg.visualize: the reference's frame capture is broken (`new_xyz` undefined, omniloc.py:61 -> NameError); here
     omniloc returns the frame list that code means to build (query image over the cloud rendered at the current pose,
@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from . import ops
 from .cfg_rules import (GN_KEYS, ROBUST_KEYS, SCORE_KEYS, _EXTENSIONS, _cfg, _refuse, _refuse_l1,  # noqa: F401  (re-exported)
-                        depth_polish_flag, gn_schedule, pose_covariance_flag, prune_schedule, robust_schedule)
+                        depth_polish_flag, gn_schedule, pose_covariance_flag, prune_schedule, pyramid_schedule, robust_schedule)
 
 strict_reference_asserts = True
 
@@ -44,7 +44,7 @@ strict_reference_asserts = True
 # cloud, quantile box or translation grid (a dataset loop touches 4 cloud-side entries per room and 2 per image).
 # An entry is keyed by the identity of the tensors it was made from (address, shape, in-place version) and holds weak
 # references to them: a hit needs the very same live tensor, and entries whose tensors died are purged.
-_CAPACITY = {"cloud": 2, "cloud_w": 2, "density": 4, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "gd_rooms_images": 4, "trimgroups": 4}
+_CAPACITY = {"cloud": 2, "cloud_w": 2, "density": 4, "order": 2, "box": 8, "grid": 4, "pano": 16, "pano_u8": 16, "pano_u8p": 16, "pano_u8v": 16, "gd": 6, "gd_rooms": 4, "gd_rooms_images": 4, "trimgroups": 4, "pyramid": 16}
 
 
 class _PackCache:
@@ -617,14 +617,28 @@ def _drive(c, tr, ro, cfg):
     return gd
 
 
-def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, weights=None, weight_sets=0):
+def packed_pyramid(img, levels, pano0, n_points):
+    """The PanoPyramid of `img` with `levels` coarse levels over the packed level-0 panorama `pano0`, cached per tensor; the coarse levels'
+    texel formats are ops.refine_texels' for n_points points at each level's size."""
+    return _cached("pyramid", (img,), lambda: ops.PanoPyramid(img, levels, n=n_points, pano0=pano0), sub=(levels, int(n_points), pano0.fmt))
+
+
+def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, weights=None, weight_sets=0, imgs=None):
     """Run the on-device GD for the rows of trans / rot and return the GradientDescent object (read gd.result() / gd.winner()); under
     cfg.prune_iters / cfg.prune_keep the _PrunedChain of its segments (read winner() / winners()).
     `panos`: one packed panorama per query image; the B rows split evenly over them, image by image.  `rgb`: one (N, 3) tensor, or a list
     of one per query image (per-image colour sets: image i's candidates read set i, and the chain runs the single-image plan).
     The GradientDescent object (state, workspace, captured graph) is cached per cloud and launch shape (_cached_engine).  `weights`: (N,)
     per-point weights (one colour set, no depth mask).  weight_sets = len(panos): the robust chain over several images (a weight-set engine,
-    ops.GradientDescent(weight_sets=I): the single-image plan, one weight plane per image; omniloc_batch_images_robust)."""
+    ops.GradientDescent(weight_sets=I): the single-image plan, one weight plane per image; omniloc_batch_images_robust).
+    `imgs`: the query images `panos` were packed from, where the caller takes cfg.pyramid_iters / cfg.pyramid_reset (pyramid_schedule): the
+    chain then runs coarse-to-fine over every image's PanoPyramid (ops.GradientDescent.run_pyramid), on an engine of its own."""
+    pyramid = pyramid_schedule(cfg, (panos[0].H, panos[0].W))
+    if pyramid is not None:
+        if imgs is None or weight_sets or vis_hook is not None:
+            raise ValueError("cfg.pyramid_iters: the plain refinement of omniloc_batch / omniloc_batch_images only")
+        if weights is not None:
+            raise ValueError("cfg.pyramid_iters does not combine with weights=")
     robust = robust_schedule(cfg)
     if robust is not None and not weight_sets:
         if weights is not None:
@@ -646,7 +660,10 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, we
     # (one or two launches per iteration is frozen into a captured graph: part of the key, with the other arguments)
     # (the robust chains have engines of their own: a plain call never meets an engine whose plane is switched on, or one of the
     # single-image plan)
+    # (and so has a coarse-to-fine chain: its graphs are the levels', and a plain call never meets them)
     tail = tuple(args.values()) + (("robust_images",) if weight_sets else ("robust",) if robust is not None else ())
+    if pyramid is not None:
+        tail += ("pyramid", tuple(pyramid[0]), pyramid[1])
 
     def name(gd, graph, fresh):
         if weight_sets or I > 1 or graph or sched is not None:   # (a later segment may replay a graph that holds another image's panorama)
@@ -655,6 +672,9 @@ def _refine(xyz, rgb, panos, trans, rot, box, cfg, batch_mode, vis_hook=None, we
     def run(gd, graph):
         if robust is not None:
             gd.run_robust(num_iter, robust[0], robust[1], robust[2], graph=graph)
+        elif pyramid is not None:
+            pyramids = [packed_pyramid(im, len(pyramid[0]), p, cloud.n) for im, p in zip(imgs, panos)]
+            gd.run_pyramid(pyramids, num_iter, pyramid[0], reset_plateau=pyramid[1], graph=graph)
         elif vis_hook is not None:
             vis_hook(gd, num_iter)
         elif graph:
@@ -730,6 +750,7 @@ def omniloc(img, xyz, rgb, input_trans, input_rot, starting_point, cfg, scalar_s
     reference where the optimised tensors are views of those rows (omniloc.py:15-19).
     """
     _refuse(cfg, "omniloc")
+    _refuse(cfg, "omniloc", "pyramid")
     vis = _cfg(cfg, "visualize", False)
     out_quantile = _cfg(cfg, "out_of_room_quantile", 0.05)
 
@@ -783,6 +804,7 @@ def omniloc_all(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries=Non
     Every starting point keeps omniloc's SEQUENTIAL semantics (its own Adam / scheduler, clamp applied to the parameters
     the next forward reads) and the points never interact, so the list returned equals the K separate calls."""
     _refuse(cfg, "omniloc_all")
+    _refuse(cfg, "omniloc_all", "pyramid")
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     res = _refine(xyz, rgb, [packed_pano(img, n_points=xyz.shape[0])], input_trans, input_rot, box, cfg, False, weights=weights).result()
     K = res.shape[0]
@@ -814,12 +836,20 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
     cfg.depth_polish = True next to cfg.depth_mask (depth_polish_flag): the gn keys and cfg.pose_covariance are taken under the mask.  The
     depth-masked chain runs as without the key; its winner is polished from the winners row on the device by gauss_newton_refine(depth=...)
     under the chain's own grid, tolerance and stride, the mask rebuilt at every trial pose; the returned loss is ops.sampling_loss(depth=...)
-    at the polished pose; the covariance is the one under the mask at the returned pose.  Not with weights=, the robust or the score keys."""
+    at the polished pose; the covariance is the one under the mask at the returned pose.  Not with weights=, the robust or the score keys.
+    cfg.pyramid_iters / pyramid_reset (pyramid_schedule): the chain runs coarse to fine over the image's PanoPyramid — the first
+    pyramid_iters[0] iterations against the coarsest level, the last num_iter - pyramid_iters[-1] against the image itself, ONE optimiser
+    state throughout (ops.GradientDescent.run_pyramid; with pyramid_reset the plateau scheduler starts over at every switch).  The returned
+    loss is the plain sampling loss at full resolution; the gn keys and cfg.pose_covariance start from that chain's winners row and run at
+    level 0, unchanged.  Not with weights=, cfg.depth_mask, the robust, score, density or prune keys; the image must be exactly k/255 and
+    its sides multiples of 2^len(pyramid_iters)."""
     depth = _depth_cfg(cfg) if depth_polish_flag(cfg) else None          # (its own refusals first: without the key nothing changes)
     if depth is not None and weights is not None:
         raise ValueError("cfg.depth_polish does not combine with weights=")
     if robust_schedule(cfg) is not None and weights is not None:          # (and the schedule's own refusals, before a device is touched)
         raise ValueError("cfg.robust_iters does not combine with weights= (the chain makes its own)")
+    if pyramid_schedule(cfg, getattr(img, "shape", None)) is not None and weights is not None:         # (likewise)
+        raise ValueError("cfg.pyramid_iters does not combine with weights=")
     want_cov = pose_covariance_flag(cfg)
     if want_cov and isinstance(rgb, (list, tuple)):
         raise ValueError("cfg.pose_covariance: one colour set only")
@@ -830,7 +860,7 @@ def omniloc_batch(img, xyz, rgb, input_trans, input_rot, cfg, scalar_summaries, 
         assert cfg.num_input > 1
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
     pano = packed_pano(img, n_points=xyz.shape[0])
-    gd = _refine(xyz, rgb, [pano], input_trans, input_rot, box, cfg, True, weights=weights)
+    gd = _refine(xyz, rgb, [pano], input_trans, input_rot, box, cfg, True, weights=weights, imgs=[img])
     # loss_list.argmin() of the last forward, R of the winner and the write-back of the leaves: one kernel, then the one D2H copy
     # of the whole refinement (64 bytes)
     bt, br, after = _leaf_buffers(input_trans, input_rot, gd.B)
@@ -894,7 +924,7 @@ def _images_ladder(who, imgs, xyz, rgb, trans_list, rot_list, cfg, scalar_summar
     box = quantile_box_of(xyz, _cfg(cfg, "out_of_room_quantile", 0.05))
 
     def chain(tr, ro):
-        return _refine(xyz, rgb, panos, tr, ro, box, cfg, batch_mode, weight_sets=I if weight_sets else 0)
+        return _refine(xyz, rgb, panos, tr, ro, box, cfg, batch_mode, weight_sets=I if weight_sets else 0, imgs=imgs)
     if polish is None:
         return _refine_groups(chain, trans_list, rot_list)
     gn, want_cov = polish
@@ -920,8 +950,12 @@ def omniloc_batch_images(imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, 
     and the chain runs the single-image plan, so image i's result is omniloc_batch(imgs[i], xyz, rgb[i], ...)'s bit for bit.  Images
     beyond the colour-set addressing limit go in further groups.  With the depth mask the colour-set chain is the depth chain
     (pcl_gd_run_depth_chain) with this cloud as its one room: the same grouping, the same bits per image.
+    cfg.pyramid_iters / pyramid_reset (pyramid_schedule; omniloc_batch describes them): every image's candidates descend that image's own
+    pyramid in the one chain, with shared colours or a colour set per image; image i's result is its own omniloc_batch run under the keys,
+    under the plain chain's caveat above.
     ValueError, before a device is touched: lists of different lengths, a colour-set count that is not the image count."""
     _refuse(cfg, "omniloc_batch_images")
+    pyramid_schedule(cfg, getattr(imgs[0], "shape", None) if imgs else None)       # (its own refusals, before a device is touched)
     return _images_ladder("omniloc_batch_images", imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries, batch_mode, direct=True)
 
 
@@ -935,6 +969,7 @@ def omniloc_batch_images_robust(imgs, xyz, rgb, input_trans_list, input_rot_list
     same cfg bit for bit; every loss is the WEIGHTED loss of the last forward.  Parallel semantics only.  ValueError: cfg without
     robust_iters (and cfg_rules' refusals), cfg.visualize, lists of different lengths.  One image is omniloc_batch."""
     _refuse(cfg, "omniloc_batch_images_robust")
+    _refuse(cfg, "omniloc_batch_images_robust", "pyramid")
     robust = robust_schedule(cfg)
     if robust is None:
         raise ValueError("omniloc_batch_images_robust needs cfg.robust_iters (omniloc_batch_images runs the plain chain)")
@@ -972,6 +1007,7 @@ def omniloc_batch_images_polished(imgs, xyz, rgb, input_trans_list, input_rot_li
     if _cfg(cfg, "visualize", False):
         raise ValueError("%s does not take cfg.visualize" % who)
     _refuse(cfg, who)
+    _refuse(cfg, who, "pyramid")
     return _images_ladder(who, imgs, xyz, rgb, input_trans_list, input_rot_list, cfg, scalar_summaries, forward_one=True,
                           weight_sets=robust_schedule(cfg) is not None, polish=(gn, want_cov))
 
@@ -1040,6 +1076,7 @@ def omniloc_batch_rooms(img, rooms, input_trans_list, input_rot_list, cfg, scala
     (pcl_gd_run_depth_chain: every room on its own z-buffer grid, the same bits per room); rooms whose tolerances differ (depth_tau_groups)
     go in a chain per tolerance."""
     _refuse(cfg, "omniloc_batch_rooms")
+    _refuse(cfg, "omniloc_batch_rooms", "pyramid")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     R = len(rooms)
@@ -1197,6 +1234,7 @@ def omniloc_batch_rooms_images(imgs, rooms, input_trans, input_rot, cfg, scalar_
     tolerance, and images that share the rooms' colours run omniloc_batch_images per room where that is faster (depth_shared_chain_pays:
     its plan of all the images' candidates, so equal to the single calls up to the summation order of the partial sums, as there)."""
     _refuse(cfg, "omniloc_batch_rooms_images")
+    _refuse(cfg, "omniloc_batch_rooms_images", "pyramid")
     if strict_reference_asserts and batch_mode:
         assert cfg.num_input > 1
     rooms = _check_rooms("omniloc_batch_rooms_images", imgs, rooms, input_trans, input_rot)[3]
@@ -1228,6 +1266,7 @@ def omniloc_batch_rooms_images_polished(imgs, rooms, input_trans, input_rot, cfg
     if bool(_cfg(cfg, "depth_mask", False)):
         raise ValueError("%s does not combine with cfg.depth_mask" % who)
     _refuse(cfg, who)
+    _refuse(cfg, who, "pyramid")
     if _cfg(cfg, "visualize", False):
         raise ValueError("%s does not take cfg.visualize" % who)
     _, _, B, rooms = _check_rooms(who, imgs, rooms, input_trans, input_rot)

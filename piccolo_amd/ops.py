@@ -240,6 +240,89 @@ class Pano:
             _lib.check(lib.pcl_pano_pack(_ptr(img), self.H, self.W, _ptr(self.data), _stream()), "pcl_pano_pack")
 
 
+PYRAMID_MAX_LEVELS = 4      # PCL_PYR_MAX_LEVELS: coarse levels of one pcl_pano_pyramid call
+_PYRAMID_FMTS = {"f16": _lib.PANO_F16, "u8": _lib.PANO_U8, "f32": _lib.PANO_F32}
+
+
+def pyramid_shape(H, W, levels, who="PanoPyramid"):
+    """ValueError unless `levels` is an int in 1 .. PYRAMID_MAX_LEVELS and H and W are multiples of 2^levels (pcl_pano_pyramid's refusals,
+    on the host: no library, no device) -> levels"""
+    if not isinstance(levels, int) or isinstance(levels, bool) or not 1 <= levels <= PYRAMID_MAX_LEVELS:
+        raise ValueError("%s: levels %r: an int in 1 .. %d" % (who, levels, PYRAMID_MAX_LEVELS))
+    if int(H) <= 0 or int(W) <= 0 or int(H) % (1 << levels) or int(W) % (1 << levels):
+        raise ValueError("%s: a %d x %d image has no %d coarse levels (H and W must be multiples of %d)" % (who, H, W, levels, 1 << levels))
+    return levels
+
+
+class _PanoLevel:
+    """One coarse level of a PanoPyramid: what the engines read of a Pano (H, W, fmt, data, texels); `data` is a view of the pyramid's
+    one buffer, which it keeps alive."""
+    texels = property(lambda self: (self.H, self.W, self.fmt))
+
+    def __init__(self, H, W, fmt, data):
+        self.H, self.W, self.fmt, self.data = H, W, fmt, data
+
+
+class PanoPyramid:
+    """The query panorama and its coarse levels, packed for the loss kernel (pcl_pano_pyramid, ONE launch for all coarse levels; the rule:
+    include/piccolo_hip.h — aligned 2 x 2 blocks of the level below, black pixels are "no data" and leave the mean, a block with data
+    never comes out black; a plain box pyramid, no latitude weighting).  The image must be exactly k/255 (ValueError otherwise; an image
+    tagged by synth.mark_levels is not waited for, as in Pano).
+
+    .panos[0] is Pano(img) — or `pano0`, the level-0 Pano a caller has packed already —, .panos[l] level l over this object's buffer, in
+    the texel format fmts[l - 1] ("f16" | "u8" | "f32"; one string: every level's); default: refine_texels(n, h, w) of the level's size
+    when the point count `n` is given, else "f16".  "f16" and "u8" give the same loss bits, so that choice affects speed only.
+    images=True: .images holds the float (h, w, 3) level images as well (level 1 first)."""
+
+    def __init__(self, img, levels, fmts=None, n=None, pano0=None, images=False):
+        lib = _lib.load()
+        src = img
+        if not torch.is_tensor(img):
+            img = torch.as_tensor(img)
+        if img.dim() != 3 or img.shape[2] != 3:
+            raise ValueError("img must be (H, W, 3)")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        self.levels = pyramid_shape(H, W, levels)
+        if fmts is None or isinstance(fmts, str):
+            fmts = [fmts or (refine_texels(n, H >> l, W >> l) if n is not None else "f16") for l in range(1, levels + 1)]
+        fmts = list(fmts)
+        if len(fmts) != levels or any(f not in _PYRAMID_FMTS for f in fmts):
+            raise ValueError("PanoPyramid: fmts %r: one of %s per coarse level" % (fmts, sorted(_PYRAMID_FMTS)))
+        if pano0 is not None and pano0 is not False and (pano0.H, pano0.W) != (H, W):
+            raise ValueError("PanoPyramid: pano0 is not this image's size")
+        img = _dev(img)
+        if img.data_ptr() % 8:                                # (the kernel reads pixel pairs as 8-byte words)
+            img = img.clone()
+        codes = (ctypes.c_int * levels)(*[_PYRAMID_FMTS[f] for f in fmts])
+        nbytes = lib.pcl_pano_pyramid_bytes(H, W, levels, codes)
+        if nbytes == 0:
+            raise ValueError("PanoPyramid: pcl_pano_pyramid_bytes refuses %d x %d with %d levels" % (H, W, levels))
+        # (an OUTPUT, of which the call writes every byte — tests/test_pyramid.py runs it into poisoned buffers —, not a workspace)
+        self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        sizes = [(H >> l, W >> l) for l in range(1, levels + 1)]
+        flat = torch.empty(sum(3 * h * w for h, w in sizes), dtype=F32, device=img.device) if images else None
+        known = _known_levels(src)
+        flag = _scratch_flag(img.device) if known else torch.zeros(1, dtype=torch.int32, device=img.device)
+        _lib.check(lib.pcl_pano_pyramid(_ptr(img), H, W, levels, codes, _ptr(self.buffer), _ptr(flat), _ptr(flag), _stream()), "pcl_pano_pyramid")
+        if not known and int(flag.item()) != 0:
+            raise ValueError("image is not exactly k/255: no pyramid (the rule works on the levels k)")
+        # (pano0=False: no level 0 at all — pano_pyramid wants the level images alone)
+        self.panos, self.images, off, at = [Pano(src) if pano0 is None else (pano0 or None)], None if flat is None else [], 0, 0
+        for (h, w), f in zip(sizes, fmts):
+            size = lib.pcl_pano_bytes(h, w, _PYRAMID_FMTS[f])
+            self.panos.append(_PanoLevel(h, w, _PYRAMID_FMTS[f], self.buffer[off:off + size]))
+            off += (size + 255) // 256 * 256
+            if flat is not None:
+                self.images.append(flat[at:at + 3 * h * w].view(h, w, 3))
+                at += 3 * h * w
+
+
+def pano_pyramid(img, levels):
+    """[level 1, ..., level `levels`] of the (H, W, 3) image of exact levels k/255: float (H >> l, W >> l, 3) GPU tensors, every value
+    again exactly k/255 (PanoPyramid's rule and refusals)."""
+    return PanoPyramid(img, levels, fmts="u8", pano0=False, images=True).images
+
+
 _SCRATCH_FLAGS = {}
 
 
@@ -1831,7 +1914,8 @@ class GradientDescent(_GdEngine):
 
     def _graph_key(self):
         w = self._run_weights() if self._chain is None else None
-        return (0 if w is None else w.data_ptr(), self.weight_sets)
+        # (the panorama's size and texel format: run_pyramid's segments run one engine against several)
+        return (0 if w is None else w.data_ptr(), self.weight_sets) + tuple(self.pano.texels)
 
     def _robust_buffers(self):
         """the engine's own plane(s), residual row(s), scale(s) and select workspace, at stable addresses: one per image of a weight-set engine"""
@@ -1903,6 +1987,50 @@ class GradientDescent(_GdEngine):
         for end in iters + [int(num_iter)]:
             if done:
                 self.robust_reweight(kind, k)
+            if graph:
+                self.run_graph(end - done)
+            else:
+                hists.append(self.run(end - done, history))
+            done = end
+        return torch.cat(hists) if history and not graph else None
+
+    # ---- coarse-to-fine (cfg.pyramid_iters of omniloc_batch): the SAME state goes on against the next finer level of a panorama pyramid.
+    def run_pyramid(self, pyramids, num_iter, iters, reset_plateau=False, history=False, graph=False):
+        """The coarse-to-fine chain over `pyramids`, one PanoPyramid per image of the engine (1, or the I of set_pano_groups: candidates
+        [i * B / I, (i + 1) * B / I) sample image i's levels).  iters = [i_1 < ... < i_L] strictly inside (0, num_iter), L the coarse levels
+        used: iterations [0, i_1) run on level L, [i_1, i_2) on level L - 1, ..., [i_L, num_iter) on level 0.  At a switch the engine takes
+        the next level's size and texel format for its launches and names that level's panoramas in the pose records; nothing else
+        changes: Adam's moments, every candidate's lr and the step count ALWAYS carry on.  Without reset_plateau the plateau scheduler's
+        `best` and its bad-epoch count carry on too — `best` then compares the losses of one level with those of another, as run_robust's
+        compares weighted with unweighted ones (it is not reset); with reset_plateau pcl_gd_plateau_reset starts the scheduler over at
+        every switch (best = +inf, no bad epochs; lr stays).  graph: every segment replays its own captured graph (no history then); the
+        naming and reset launches sit between the replays.  The loss the chain reports — the last history rows, result(), winners() — is
+        the last segment's: the plain sampling loss at full resolution.  ValueError: a depth mask, weight_sets, a weighted cloud (or a
+        robust plane switched on), pyramids of differing sizes, fewer levels than len(iters).  -> history or None"""
+        iters, pyramids = [int(i) for i in iters], list(pyramids)
+        if not iters or any(not 0 < i < num_iter for i in iters) or any(b <= a for a, b in zip(iters, iters[1:])):
+            raise ValueError("run_pyramid: iters %r: strictly increasing iteration counts inside (0, %d)" % (iters, num_iter))
+        if self._chain is not None or self.hyper.depth_mask:
+            raise ValueError("run_pyramid: no depth mask (the z-buffer's grid belongs to one panorama size)")
+        if self.weight_sets or self._run_weights() is not None:
+            raise ValueError("run_pyramid: an engine without weight_sets over a cloud without weights")
+        I, L = len(pyramids), len(iters)
+        if I < 1 or self.B % I or (self.cloud.color_sets > 1 and I != self.cloud.color_sets):
+            raise ValueError("run_pyramid: %d pyramids for %d candidates over %d colour sets" % (I, self.B, self.cloud.color_sets))
+        if any(p.levels < L for p in pyramids):
+            raise ValueError("run_pyramid: %d switches need pyramids of at least %d coarse levels" % (L, L))
+        for l in range(L + 1):
+            _same_texels([p.panos[l] for p in pyramids], pyramids[0].panos[l], "run_pyramid: the pyramids must share sizes and texel formats, level by level")
+        # one stand-in panorama per size and format for good: it is the launches' default (a captured graph holds its address), every
+        # candidate reads the panorama its pose record names
+        kept = self.__dict__.setdefault("_level_panos", {})
+        hists, done = [], 0
+        for s, end in enumerate(iters + [int(num_iter)]):
+            level = [p.panos[L - s] for p in pyramids]
+            self.pano = kept.setdefault(level[0].texels, level[0])
+            self.set_pano_groups(level)
+            if s and reset_plateau:
+                _lib.check(_lib.load().pcl_gd_plateau_reset(_ptr(self.state), self.B, _stream()), "pcl_gd_plateau_reset")
             if graph:
                 self.run_graph(end - done)
             else:

@@ -201,6 +201,17 @@ def density_weights(xyz, voxel, cap=1):
     return ops.VoxelGrid(xyz, voxel).weights(cap)
 
 
+# ------------------------------------------------------------------------------------------------ panorama pyramid
+# (not in the reference, which resizes its query on the host to two fixed sizes; build-defined, DESIGN.md section 4.6h)
+def pano_pyramid(img, levels):
+    """[level 1, ..., level `levels`] of the (H, W, 3) query image, every value exactly k/255: float (H >> l, W >> l, 3) GPU tensors made
+    by ONE launch (ops.pano_pyramid; the rule: include/piccolo_hip.h).  Level l is level l - 1 in aligned 2 x 2 blocks: the mean of the
+    block's non-black pixels, rounded to the nearest level with ties up; black (all three channels 0) is the loss's "no data" marker, and
+    a coarse pixel is black iff there is no data under it.  A plain box pyramid: no latitude weighting, nothing wraps in azimuth.
+    ValueError: levels outside 1 .. 4, H or W not a multiple of 2^levels, an image that is not exactly k/255.  Eager."""
+    return ops.pano_pyramid(img, levels)
+
+
 # ------------------------------------------------------------------------------------------------ plane normals and gravity alignment
 # (not in the reference, which calls an undefined data_utils.obtain_align_matrix; build-defined, DESIGN.md section 2d)
 def voxel_normals(xyz, voxel, min_count=8):
