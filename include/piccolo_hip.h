@@ -913,6 +913,8 @@ int pcl_gn_refine_depth(const float *cloud, int64_t n, const void *pano, int pan
  *   wrapped interpolation (period 360) and its rank-indexed lookup.  out [H][W][3]; black pixels are copied.
  *   *not_exact (device int32, nullable) = 1 when some non-black pixel channel is not exactly k/255: the output is then
  *   not the reference's (its lookup is by distinct float value) and the Python layer raises.
+ *   DEVIATION: without a non-black pixel, or when every non-black pixel lies in row 0 (weight sin(0) = 0: any image of one row),
+ *   the reference raises an IndexError (0 / 0 quantiles); here out = img and nothing is flagged.
  * pcl_color_mod (color_utils.py:7-65): joint luma equalisation.  Panorama (non-black pixels) and point colours go to
  *   8-bit YCrCb (OpenCV's fixed-point cvtColor, restated), the two Y histograms with num_bins levels are added, Y becomes
  *   the joint cumulative distribution at its level, back to RGB.  out_img [H][W][3], out_rgb [n][3].
@@ -932,6 +934,12 @@ int pcl_color_mod(const float *img_hwc, int H, int W, const float *rgb, int64_t 
 size_t pcl_histogram_workspace_bytes(int c0, int c1, int c2);
 int pcl_histogram(const float *img, const uint8_t *mask, int64_t npix, int c0, int c1, int c2, int normalize, float eps,
                   float *hist, void *workspace, size_t workspace_bytes, void *stream);
+/* color_utils.py:103-117, the batched form: img [batch][npix][3], mask [batch][npix] -> hist [batch][c0*c1*c2].  The reference asks
+ * `max(img) <= 1` of the whole batch (:88), so ONE maximum over all images decides the scale of every image (a black image in a
+ * 0..255 batch is not scaled); each image is then counted as pcl_histogram counts it. */
+size_t pcl_histogram_batch_workspace_bytes(int batch, int c0, int c1, int c2);
+int pcl_histogram_batch(const float *img, const uint8_t *mask, int batch, int64_t npix, int c0, int c1, int c2, int normalize, float eps,
+                        float *hist, void *workspace, size_t workspace_bytes, void *stream);
 int pcl_histogram_intersection(const float *a, const float *b, int batch, int nbins, float *out, void *stream);
 /* p = R (x - t) for one pose: xyz [n][3] -> out [n][3] (feeds make_pano / scatter-min; localize.py:266-267). */
 int pcl_transform_cloud(const float *xyz, int64_t n, const float *trans, const float *rot, float *out, void *stream);

@@ -129,6 +129,8 @@ SIGNATURES = {
     "pcl_color_mod": (_int, [_vp, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _sz, _vp]),
     "pcl_histogram_workspace_bytes": (_sz, [_int, _int, _int]),
     "pcl_histogram": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _c.c_float, _vp, _vp, _sz, _vp]),
+    "pcl_histogram_batch_workspace_bytes": (_sz, [_int, _int, _int, _int]),
+    "pcl_histogram_batch": (_int, [_vp, _vp, _int, _i64, _int, _int, _int, _int, _c.c_float, _vp, _vp, _sz, _vp]),
     "pcl_histogram_intersection": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "pcl_cloud_txt_rows": (_i64, [_c.c_char_p]),
     "pcl_cloud_txt_read": (_i64, [_c.c_char_p, _i64, _int, _vp, _int]),

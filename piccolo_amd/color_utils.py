@@ -9,8 +9,6 @@ Results come back on the device of `img` (CPU tensors in -> CPU tensors out, lik
 """
 import weakref
 
-import torch
-
 from . import ops
 
 _templates = {}
@@ -46,11 +44,11 @@ def color_mod(img, rgb, num_bins):
 
 def histogram(img, mask, channels=[32, 32, 32], normalize=True):
     """Colour histogram of the masked pixels (color_utils.py:68-118): (H,W,3)/(H,W) -> (*channels);
-    batched (B,H,W,3)/(B,H,W) -> (B,*channels) with the batched form's eps in the normalisation."""
+    batched (B,H,W,3)/(B,H,W) -> (B,*channels) with the batched form's eps in the normalisation.  Whether the colours are
+    scaled by 255 is decided by the maximum of the whole input (color_utils.py:88): once for a batch, not per image."""
     if img.dim() == 3:
         return ops.histogram(img, mask, channels, normalize, 0.0).reshape(*channels).to(img.device)
-    hists = [ops.histogram(img[b], mask[b], channels, normalize, 1e-6) for b in range(img.shape[0])]
-    return torch.stack(hists).reshape(img.shape[0], *channels).to(img.device)
+    return ops.histogram(img, mask, channels, normalize, 1e-6).reshape(img.shape[0], *channels).to(img.device)
 
 
 def histogram_intersection(hist_1, hist_2):

@@ -170,7 +170,10 @@ __global__ void __launch_bounds__(PCL_CM_LEVELS) pcl_cm_table_kernel(const PclCo
         maxbin = mb;
     }
     __syncthreads();
-    if (maxbin < 0) { lut[c * PCL_CM_LEVELS + b] = 0.f; return; }            // no non-black pixel at all
+    // DEVIATION from the reference: without a non-black pixel, or with a total weight of 0 (every non-black pixel in row 0, whose
+    // weight is sin(0): any image of one row), the quantiles are 0 / 0 and the reference raises an IndexError (no sample point lies
+    // above NaN).  The table is the identity here: the image comes back unchanged, and no NaN is written.
+    if (maxbin < 0 || !(cum[maxbin] > 0.0)) { lut[c * PCL_CM_LEVELS + b] = __fdiv_rn((float)b, 255.f); return; }
     const float nf = (float)n;
     // x = src_quantiles[b] = cumsum[b] / cumsum[-1] in float32 (color_utils.py:195-196)
     const float x = __fdiv_rn((float)cum[b], (float)cum[maxbin]);
@@ -393,7 +396,8 @@ extern "C" int pcl_color_mod(const float* img, int H, int W, const float* rgb, i
 }
 
 // ------------------------------------------------------------------- histogram / histogram_intersection
-// color_utils.py:68-118 (unbatched form; the batched form is the same per image with eps in the normalisation) and
+// color_utils.py:68-118 (unbatched form; the batched form is the same per image with eps in the normalisation and the scale decided by
+// the maximum of the whole batch: pcl_histogram_batch) and
 // :122-144.  The fused trimming stage (pcl_hist.hip) does not call these; they back the stand-alone functions.
 
 // order-preserving key of a float, for atomicMax
@@ -490,6 +494,50 @@ extern "C" int pcl_histogram(const float* img, const uint8_t* mask, int64_t npix
     else
         hipLaunchKernelGGL((pcl_histogram_kernel<false>), dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, img, mask, npix, c0, c1, c2, w.maxkey, w.counts);
     hipLaunchKernelGGL(pcl_histogram_finish_kernel, dim3(1), dim3(PCL_BLOCK), 0, s, w.counts, nbins, normalize, eps, hist);
+    PCL_LAUNCH_CHECK();
+    return 0;
+}
+
+// workspace of pcl_histogram_batch: the batch's maximum as a key (16 bytes), then the bins' counters of every image
+static size_t histogram_batch_layout(void* base, int batch, int c0, int c1, int c2, HistogramWs* w)
+{
+    if (batch <= 0 || c0 <= 0 || c1 <= 0 || c2 <= 0 || (int64_t)c0 * c1 * c2 > (1 << 24) || (int64_t)batch * c0 * c1 * c2 > ((int64_t)1 << 28)) return 0;
+    PclCarve c{(char*)base, 0};
+    w->maxkey = (unsigned int*)c.take(16);
+    w->counts = (unsigned int*)c.take((size_t)batch * c0 * c1 * c2 * sizeof(unsigned int));
+    return c.off;
+}
+
+extern "C" size_t pcl_histogram_batch_workspace_bytes(int batch, int c0, int c1, int c2)
+{
+    HistogramWs w;
+    return histogram_batch_layout(nullptr, batch, c0, c1, c2, &w);
+}
+
+// The batched form (color_utils.py:103-117): `tgt_img.max() <= 1` (:88) is asked ONCE, of the whole batch, so one maximum over all
+// images decides the scale of every image; then each image is counted and finished like a single one.
+extern "C" int pcl_histogram_batch(const float* img, const uint8_t* mask, int batch, int64_t npix, int c0, int c1, int c2, int normalize,
+                                   float eps, float* hist, void* workspace, size_t workspace_bytes, void* stream)
+{
+    HistogramWs w;
+    const size_t need = histogram_batch_layout(workspace, batch, c0, c1, c2, &w);
+    if (!img || !mask || !hist || !workspace || npix <= 0 || need == 0) return PCL_EINVAL;
+    if (workspace_bytes < need) return PCL_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int nbins = c0 * c1 * c2;
+    hipError_t e = hipMemsetAsync(workspace, 0, need, s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pcl_img_max_kernel, dim3(color_grid(batch * npix * 3)), dim3(PCL_BLOCK), 0, s, img, batch * npix * 3, w.maxkey);
+    for (int i = 0; i < batch; i++) {
+        const float* im = img + (size_t)i * npix * 3;
+        const uint8_t* mk = mask + (size_t)i * npix;
+        unsigned int* counts = w.counts + (size_t)i * nbins;
+        if (nbins <= PCL_HIST_LDS_BINS)
+            hipLaunchKernelGGL((pcl_histogram_kernel<true>), dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, im, mk, npix, c0, c1, c2, w.maxkey, counts);
+        else
+            hipLaunchKernelGGL((pcl_histogram_kernel<false>), dim3(color_hgrid(npix)), dim3(PCL_HBLOCK), 0, s, im, mk, npix, c0, c1, c2, w.maxkey, counts);
+        hipLaunchKernelGGL(pcl_histogram_finish_kernel, dim3(1), dim3(PCL_BLOCK), 0, s, counts, nbins, normalize, eps, hist + (size_t)i * nbins);
+    }
     PCL_LAUNCH_CHECK();
     return 0;
 }

@@ -1643,16 +1643,23 @@ def color_mod(img, rgb, num_bins=256):
 
 
 def histogram(img, mask, channels, normalize=True, eps=0.0):
-    """color_utils.histogram of one image (color_utils.py:68-103): flat float histogram of c0*c1*c2 bins on the GPU."""
+    """color_utils.histogram on the GPU.  One image (color_utils.py:68-103), (H,W,3) / (H,W): flat float histogram of c0*c1*c2 bins.
+    A batch (color_utils.py:103-117), (B,H,W,3) / (B,H,W) -> (B, c0*c1*c2): the maximum of the whole batch decides whether the colours
+    are scaled by 255, as the reference's one `tgt_img.max() <= 1` does (the caller passes the batched form's eps)."""
     lib = _lib.load()
+    B = int(img.shape[0]) if len(img.shape) == 4 else 0             # 0: the unbatched form
     img = _dev(img).reshape(-1, 3)
     mask = _dev(mask != 0, torch.uint8).reshape(-1)
     c0, c1, c2 = (int(c) for c in channels)
-    nws = lib.pcl_histogram_workspace_bytes(c0, c1, c2)
+    nws = lib.pcl_histogram_batch_workspace_bytes(B, c0, c1, c2) if B else lib.pcl_histogram_workspace_bytes(c0, c1, c2)
     if nws == 0:
-        raise ValueError("histogram: bad bin counts %r" % (channels,))
+        raise ValueError("histogram: bad bin counts %r (or batch size %d)" % (channels, B))
     ws = _bytes(nws)
-    hist = torch.empty(c0 * c1 * c2, dtype=F32, device=img.device)
+    hist = torch.empty(max(B, 1) * c0 * c1 * c2, dtype=F32, device=img.device)
+    if B:
+        _lib.check(lib.pcl_histogram_batch(_ptr(img), _ptr(mask), B, int(img.shape[0]) // B, c0, c1, c2, int(bool(normalize)), float(eps),
+                                           _ptr(hist), _ptr(ws), nws, _stream()), "pcl_histogram_batch")
+        return hist.reshape(B, -1)
     _lib.check(lib.pcl_histogram(_ptr(img), _ptr(mask), int(img.shape[0]), c0, c1, c2, int(bool(normalize)), float(eps),
                                  _ptr(hist), _ptr(ws), nws, _stream()), "pcl_histogram")
     return hist

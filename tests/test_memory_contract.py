@@ -422,6 +422,7 @@ def colour(oracle):
             out[name + ".hist.raw.%d" % ch[0]] = ops.histogram(I, mask, ch, normalize=False)
             h2 = ops.histogram(I.flip(1).contiguous(), torch.ones_like(mask), ch, eps=1e-6)
             out[name + ".inter.%d" % ch[0]] = ops.histogram_intersection(torch.stack([h, h2, h]), torch.stack([h2, h2, h]))
+            out[name + ".hist.batch.%d" % ch[0]] = ops.histogram(torch.stack([I, I.flip(1)]), torch.stack([mask, torch.ones_like(mask)]), ch, eps=1e-6)
     return ws.flat(out)
 
 
