@@ -60,6 +60,11 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _checked(name, *args):
+    """call the C entry point `name`, which returns an error code, and raise on failure"""
+    _lib.check(getattr(_lib.load(), name)(*args), name)
+
+
 def _bytes(nbytes):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device())
 
@@ -76,7 +81,7 @@ def _order_and_buffer(xyz, n, order, sort, nbytes):
         order = torch.empty(n, dtype=torch.int64, device=xyz.device)
         nws = _lib.load().pcl_cloud_order_workspace_bytes(n)
         ws = _bytes(nws)
-        _lib.check(_lib.load().pcl_cloud_order(_ptr(xyz), n, _ptr(order), _ptr(ws), nws, _stream()), "pcl_cloud_order")
+        _checked("pcl_cloud_order", _ptr(xyz), n, _ptr(order), _ptr(ws), nws, _stream())
     return order, _bytes(nbytes)
 
 
@@ -103,8 +108,7 @@ class Cloud:
         if self.n <= 0:
             raise ValueError("empty point cloud")
         self.order, self.data = _order_and_buffer(xyz, self.n, order, sort, lib.pcl_cloud_bytes(self.n))
-        _lib.check(lib.pcl_cloud_pack(_ptr(xyz), _ptr(rgb), _ptr(self.order), self.n, _ptr(self.data), _stream()),
-                   "pcl_cloud_pack")
+        _checked("pcl_cloud_pack", _ptr(xyz), _ptr(rgb), _ptr(self.order), self.n, _ptr(self.data), _stream())
         self.xyz = xyz          # kept for quantile_box (reads the reference's AoS layout)
         if weights is not None:
             self.set_weights(weights)
@@ -123,7 +127,7 @@ class Cloud:
             raise ValueError("weights must be (N,) with one entry per point")
         plane = self.weights if self.weights is not None else torch.empty(lib.pcl_cloud_weights_bytes(self.n) // 4, dtype=F32, device=w.device)
         bad = torch.zeros(1, dtype=torch.int32, device=w.device)
-        _lib.check(lib.pcl_cloud_pack_weights(_ptr(w), _ptr(self.order), self.n, _ptr(plane), _ptr(bad), _stream()), "pcl_cloud_pack_weights")
+        _checked("pcl_cloud_pack_weights", _ptr(w), _ptr(self.order), self.n, _ptr(plane), _ptr(bad), _stream())
         if int(bad.item()) != 0:
             if self.weights is not None:
                 self.weights.zero_()         # (the plane holds the refused values: no vote rather than a wrong one)
@@ -176,7 +180,7 @@ class Cloud:
         c.order, c.data = _order_and_buffer(xyz, c.n, order, sort, nbytes)
         c.color_sets = len(rgbs)
         arr = (ctypes.c_void_p * len(rgbs))(*[r.data_ptr() for r in rgbs])
-        _lib.check(lib.pcl_cloud_pack_sets(_ptr(xyz), arr, len(rgbs), _ptr(c.order), c.n, _ptr(c.data), _stream()), "pcl_cloud_pack_sets")
+        _checked("pcl_cloud_pack_sets", _ptr(xyz), arr, len(rgbs), _ptr(c.order), c.n, _ptr(c.data), _stream())
         c.xyz = xyz
         return c
 
@@ -229,7 +233,7 @@ class Pano:
             # need not be zeroed first (a scratch word per device instead of a fill launch per image)
             known = _known_levels(src)
             flag = _scratch_flag(img.device) if known else torch.zeros(1, dtype=torch.int32, device=img.device)
-            _lib.check(getattr(lib, fn)(_ptr(img), self.H, self.W, _ptr(data), _ptr(flag), _stream()), fn)
+            _checked(fn, _ptr(img), self.H, self.W, _ptr(data), _ptr(flag), _stream())
             if known or int(flag.item()) == 0:
                 self.fmt, self.data = code, data
             elif fmt != "auto":
@@ -237,7 +241,7 @@ class Pano:
         if self.fmt is None:
             self.fmt = _lib.PANO_F32
             self.data = _bytes(lib.pcl_pano_bytes(self.H, self.W, _lib.PANO_F32))
-            _lib.check(lib.pcl_pano_pack(_ptr(img), self.H, self.W, _ptr(self.data), _stream()), "pcl_pano_pack")
+            _checked("pcl_pano_pack", _ptr(img), self.H, self.W, _ptr(self.data), _stream())
 
 
 PYRAMID_MAX_LEVELS = 4      # PCL_PYR_MAX_LEVELS: coarse levels of one pcl_pano_pyramid call
@@ -303,7 +307,7 @@ class PanoPyramid:
         flat = torch.empty(sum(3 * h * w for h, w in sizes), dtype=F32, device=img.device) if images else None
         known = _known_levels(src)
         flag = _scratch_flag(img.device) if known else torch.zeros(1, dtype=torch.int32, device=img.device)
-        _lib.check(lib.pcl_pano_pyramid(_ptr(img), H, W, levels, codes, _ptr(self.buffer), _ptr(flat), _ptr(flag), _stream()), "pcl_pano_pyramid")
+        _checked("pcl_pano_pyramid", _ptr(img), H, W, levels, codes, _ptr(self.buffer), _ptr(flat), _ptr(flag), _stream())
         if not known and int(flag.item()) != 0:
             raise ValueError("image is not exactly k/255: no pyramid (the rule works on the levels k)")
         # (pano0=False: no level 0 at all — pano_pyramid wants the level images alone)
@@ -407,8 +411,7 @@ def default_depth(n, H, W, stride=0):
     n-point cloud seen in an H x W panorama (>= 12 occluder samples per cell, never finer than the panorama; tau = 3.5 pi / depth_h
     in [0.02, 0.15]; stride 0: the largest of 1, 2, 4 that keeps depth_h >= 128)."""
     dh, dw, tau, st = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_float(0), ctypes.c_int(0)
-    _lib.check(_lib.load().pcl_depth_default(int(n), int(H), int(W), int(stride), ctypes.byref(dh), ctypes.byref(dw), ctypes.byref(tau),
-                                             ctypes.byref(st)), "pcl_depth_default")
+    _checked("pcl_depth_default", int(n), int(H), int(W), int(stride), ctypes.byref(dh), ctypes.byref(dw), ctypes.byref(tau), ctypes.byref(st))
     return dh.value, dw.value, tau.value, st.value
 
 
@@ -470,9 +473,8 @@ def sampling_loss(cloud, pano, trans, rot, with_grad=True, visible=None, depth=N
             raise ValueError("sampling_loss: per-point weights combine with neither a byte mask (visible) nor depth")
         ws_bytes = lib.pcl_loss_workspace_bytes(cloud.n, B)
         ws = _bytes(ws_bytes)
-        _lib.check(lib.pcl_sampling_loss_weighted(_ptr(cloud.data), _ptr(cloud.weights), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans),
-                                                  _ptr(rot), B, 1 if with_grad else 0, _ptr(out), _ptr(ws), ws_bytes, _stream()),
-                   "pcl_sampling_loss_weighted")
+        _checked("pcl_sampling_loss_weighted", _ptr(cloud.data), _ptr(cloud.weights), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans),
+                 _ptr(rot), B, 1 if with_grad else 0, _ptr(out), _ptr(ws), ws_bytes, _stream())
         return out
     if depth:
         if visible is not None:
@@ -483,18 +485,16 @@ def sampling_loss(cloud, pano, trans, rot, with_grad=True, visible=None, depth=N
         if ws_bytes == 0:
             raise _lib.PiccoloHipError("pcl_loss_depth_workspace_bytes: invalid depth grid %dx%d" % (dh, dw))
         ws = _bytes(ws_bytes)
-        _lib.check(lib.pcl_sampling_loss_depth(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans), _ptr(rot), B,
-                                               1 if with_grad else 0, dh, dw, tau, st, _ptr(out), _ptr(ws), ws_bytes, _stream()),
-                   "pcl_sampling_loss_depth")
+        _checked("pcl_sampling_loss_depth", _ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans), _ptr(rot), B,
+                 1 if with_grad else 0, dh, dw, tau, st, _ptr(out), _ptr(ws), ws_bytes, _stream())
         return out
     ws_bytes = lib.pcl_loss_workspace_bytes(cloud.n, B)
     ws = _bytes(ws_bytes)
     vis = None
     if visible is not None:
         vis = _dev(visible, torch.uint8).reshape(B, cloud.n)
-    _lib.check(lib.pcl_sampling_loss(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans), _ptr(rot), B,
-                                     1 if with_grad else 0, _ptr(vis), _ptr(out), _ptr(ws), ws_bytes, _stream()),
-               "pcl_sampling_loss")
+    _checked("pcl_sampling_loss", _ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(trans), _ptr(rot), B, 1 if with_grad else 0,
+             _ptr(vis), _ptr(out), _ptr(ws), ws_bytes, _stream())
     return out
 
 
@@ -551,15 +551,14 @@ def _point_residuals_depth(who, cloud, pano, trans_ptr, rot_ptr, stride, rows, d
     # (a typed torch.empty like the outputs: the memory-contract harness guards and poisons it alike, tests/test_depth_info.py)
     ws = torch.empty(max(int(nws), 16), dtype=torch.uint8, device=dev)
     order = None if packed else _ptr(cloud.order)
-    _lib.check(lib.pcl_point_residuals_depth(_ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr, stride, rows,
-                                             dh, dw, tau, st, order, _ptr(out), _ptr(vis), _ptr(ws), nws, _stream()), "pcl_point_residuals_depth")
+    _checked("pcl_point_residuals_depth", _ptr(cloud.data), cloud.n, _ptr(pano.data), pano.fmt, pano.H, pano.W, trans_ptr, rot_ptr, stride, rows, dh, dw, tau,
+             st, order, _ptr(out), _ptr(vis), _ptr(ws), nws, _stream())
     return (out, vis) if return_visible else out
 
 
 def _point_residuals(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, packed, out=None):
     """What the four residual functions do: `rows` poses (pointers and pose stride) against ONE Pano — pcl_point_residuals, any number of
     poses in one launch — or row i against panos[i] and colour set i of a list of Panos — pcl_point_residuals_images -> (rows, N)"""
-    lib = _lib.load()
     several = not isinstance(panos, Pano)
     if several and len(panos) < 1:
         raise ValueError("%s: no panorama" % who)
@@ -576,11 +575,11 @@ def _point_residuals(who, cloud, panos, trans_ptr, rot_ptr, stride, rows, dev, p
     order = None if packed else _ptr(cloud.order)
     if several:
         arr = (ctypes.c_uint64 * rows)(*[p.data.data_ptr() for p in panos])
-        _lib.check(lib.pcl_point_residuals_images(_ptr(cloud.data), cloud.n, int(cloud.color_sets), arr, rows, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr,
-                                                  stride, order, _ptr(out), _stream()), "pcl_point_residuals_images")
+        _checked("pcl_point_residuals_images", _ptr(cloud.data), cloud.n, int(cloud.color_sets), arr, rows, p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride,
+                 order, _ptr(out), _stream())
     else:
-        _lib.check(lib.pcl_point_residuals(_ptr(cloud.data), cloud.n, _ptr(p0.data), p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride, rows,
-                                           order, _ptr(out), _stream()), "pcl_point_residuals")
+        _checked("pcl_point_residuals", _ptr(cloud.data), cloud.n, _ptr(p0.data), p0.fmt, p0.H, p0.W, trans_ptr, rot_ptr, stride, rows, order, _ptr(out),
+                 _stream())
     return out
 
 
@@ -714,7 +713,7 @@ def _pose_information(who, form, trans_ptr, rot_ptr, stride, rows, dev, objectiv
     info = torch.empty(B, 48, dtype=F32, device=dev)
     ws = _bytes(nws)
     cov = torch.empty(B, 6, 6, dtype=F32, device=dev) if delta is None else None
-    _lib.check(getattr(lib, name)(*_pose_args(convention, head, delta, (_ptr(info),), cov, (), ws, nws)), name)
+    _checked(name, *_pose_args(convention, head, delta, (_ptr(info),), cov, (), ws, nws))
     return info[:, :36].reshape(B, 6, 6), info[:, 36:42], info[:, 42:47], cov
 
 
@@ -788,7 +787,7 @@ def _gauss_newton(who, form, trans_ptr, rot_ptr, stride, rows, dev, iters, trace
     tr = torch.empty(iters + 1, B, 16, dtype=F32, device=dev) if trace else None
     ws, st = _bytes(nws), _bytes(nst)
     before_cov = (ctypes.byref(hp), iters, _ptr(st), _ptr(out), _ptr(info))
-    _lib.check(getattr(lib, name)(*_pose_args(convention, head, delta, before_cov, cov, (_ptr(tr),), ws, nws)), name)
+    _checked(name, *_pose_args(convention, head, delta, before_cov, cov, (_ptr(tr),), ws, nws))
     ret = dict(trans=out[:, 0:3], rot=out[:, 3:6], sigma2_start=out[:, 6], sigma2=out[:, 7], lam=out[:, 8], accepted=out[:, 9], rejected=out[:, 10],
                evaluations=out[:, 11], status=out[:, 12], H=info[:, :36].reshape(B, 6, 6), b=info[:, 36:42], stats=info[:, 42:47], cov=cov)
     if trace:
@@ -1038,8 +1037,7 @@ def robust_planes(n, rows, kind="trunc", k=2.5, planes=None, scales=None, ws=Non
         raise ValueError("robust_weights: %d rows of %d points" % (R, n))
     if ws is None:
         ws = _bytes(nws)
-    _lib.check(lib.pcl_robust_weights_rows(_ptr(rows), n, R, ROBUST_KINDS[kind], k, _ptr(planes), _ptr(scales), _ptr(ws), ws.numel(), _stream()),
-               "pcl_robust_weights_rows")
+    _checked("pcl_robust_weights_rows", _ptr(rows), n, R, ROBUST_KINDS[kind], k, _ptr(planes), _ptr(scales), _ptr(ws), ws.numel(), _stream())
     return planes, scales
 
 
@@ -1058,7 +1056,7 @@ class TrimGroups:
         if self.R <= 0:
             raise ValueError("empty rotation table")
         self.data = _bytes(lib.pcl_trim_groups_bytes(self.R))
-        _lib.check(lib.pcl_trim_groups(_ptr(self.rot), self.R, _ptr(self.data), _stream()), "pcl_trim_groups")
+        _checked("pcl_trim_groups", _ptr(self.rot), self.R, _ptr(self.data), _stream())
         self.ngroups = int(self.data[:4].view(torch.int32).item())
 
 
@@ -1077,8 +1075,8 @@ class TrimOrder:
         self.data = _bytes(lib.pcl_trim_order_bytes(cloud.n, self.key[1], groups.ngroups))
         nws = lib.pcl_trim_order_workspace_bytes(cloud.n, self.key[1], groups.ngroups)
         ws = _bytes(nws)
-        _lib.check(lib.pcl_trim_order(_ptr(cloud.data), cloud.n, int(fmt), int(H), int(W), _ptr(trans), self.key[1], _ptr(groups.rot), groups.R,
-                                      _ptr(groups.data), groups.ngroups, _ptr(self.data), _ptr(ws), nws, _stream()), "pcl_trim_order")
+        _checked("pcl_trim_order", _ptr(cloud.data), cloud.n, int(fmt), int(H), int(W), _ptr(trans), self.key[1], _ptr(groups.rot), groups.R, _ptr(groups.data),
+                 groups.ngroups, _ptr(self.data), _ptr(ws), nws, _stream())
 
 
 TRIM_MAX_IMAGES = 32       # pcl_trim_loss_images_sets: query images per launch
@@ -1096,10 +1094,9 @@ def _trim_tables(cloud, panos, trans, groups, return_count, order, sets=False):
         nws = lib.pcl_trim_loss_images_workspace_bytes(cloud.n, K, groups.ngroups, len(part))
         ws = _bytes(nws)
         arr = (ctypes.c_void_p * len(part))(*[p.data.data_ptr() for p in part])
-        _lib.check(lib.pcl_trim_loss_images_sets(_ptr(cloud.data), cloud.n, len(part) if sets else 1, arr, len(part), p0.fmt, p0.H, p0.W, _ptr(trans), K,
-                                                 _ptr(groups.rot), groups.R, _ptr(groups.data), groups.ngroups, _ptr(order.data) if order is not None else None,
-                                                 _ptr(table[i0:]), _ptr(count[i0:]) if return_count else None, _ptr(ws), nws, _stream()),
-                   "pcl_trim_loss_images_sets")
+        _checked("pcl_trim_loss_images_sets", _ptr(cloud.data), cloud.n, len(part) if sets else 1, arr, len(part), p0.fmt, p0.H, p0.W, _ptr(trans), K,
+                 _ptr(groups.rot), groups.R, _ptr(groups.data), groups.ngroups, _ptr(order.data) if order is not None else None, _ptr(table[i0:]),
+                 _ptr(count[i0:]) if return_count else None, _ptr(ws), nws, _stream())
     return table, count
 
 
@@ -1133,7 +1130,6 @@ def select_poses(values, n_keep, trans, rot, largest=False, rot_per_trans=0, ret
     n_keep best rows (trans[idx // rot_per_trans], rot[idx % rot_per_trans]) — or (trans[idx], rot[idx]) when rot_per_trans is 0
     — in rank order, as ((P,) n_keep, 3) tensors.  Stable order; NaN ranks last.  With (P, M) values, trans / rot are either shared
     2-D tables or (P, rows, 3) stacks."""
-    lib = _lib.load()
     values = _dev(values)
     single = values.dim() == 1
     v = values.reshape(1, -1) if single else values.reshape(values.shape[0], -1)
@@ -1155,8 +1151,8 @@ def select_poses(values, n_keep, trans, rot, largest=False, rot_per_trans=0, ret
     ot = torch.empty(P, n_keep, 3, dtype=F32, device=v.device)
     orr = torch.empty(P, n_keep, 3, dtype=F32, device=v.device)
     oi = torch.empty(P, n_keep, dtype=torch.int32, device=v.device) if return_idx else None
-    _lib.check(lib.pcl_select_poses(_ptr(v), P, M, n_keep, 1 if largest else 0, _ptr(trans), _ptr(rot), int(rot_per_trans), stride,
-                                    _ptr(ot), _ptr(orr), _ptr(oi), _stream()), "pcl_select_poses")
+    _checked("pcl_select_poses", _ptr(v), P, M, n_keep, 1 if largest else 0, _ptr(trans), _ptr(rot), int(rot_per_trans), stride, _ptr(ot), _ptr(orr), _ptr(oi),
+             _stream())
     if single:
         ot, orr, oi = ot[0], orr[0], (oi[0] if oi is not None else None)
     return (ot, orr, oi) if return_idx else (ot, orr)
@@ -1200,7 +1196,6 @@ def _hist_scores(who, imgs, cloud, trans, rot, num_split_h, num_split_w, splat, 
     (I, K, 3) -> (scores (I, K), inter, nproj, nimg).  batch (one image): its candidates `batch` at a time over one workspace, then one
     reduce over all K (the carry-over chain runs through the batches).  Otherwise images in groups, each with its reduce — or, with a
     colour set per image, all images in one call."""
-    lib = _lib.load()
     I, K = int(trans.shape[0]), int(trans.shape[1])
     H, W = int(imgs[0].shape[0]), int(imgs[0].shape[1])
     sets = cloud.color_sets > 1
@@ -1219,13 +1214,12 @@ def _hist_scores(who, imgs, cloud, trans, rot, num_split_h, num_split_w, splat, 
     def run(i0, m, k0, cpi, ws, nws):            # images [i0, i0 + m), candidates [k0, k0 + cpi) of each (k0 > 0: one image in batches)
         arr = (ctypes.c_void_p * m)(*[im.data_ptr() for im in imgs[i0:i0 + m]])
         c0 = i0 * K + k0
-        _lib.check(lib.pcl_hist_trim_scores_images_sets(_ptr(cloud.data), cloud.n, m if sets else 1, arr, m, cpi, H, W, _ptr(t2[c0:]), _ptr(r2[c0:]),
-                                                        num_split_h, num_split_w, _ptr(inter[c0:]), _ptr(nproj[c0:]), _ptr(nimg[i0:]), _ptr(ws), nws,
-                                                        _stream()), "pcl_hist_trim_scores_images_sets")
+        _checked("pcl_hist_trim_scores_images_sets", _ptr(cloud.data), cloud.n, m if sets else 1, arr, m, cpi, H, W, _ptr(t2[c0:]), _ptr(r2[c0:]), num_split_h,
+                 num_split_w, _ptr(inter[c0:]), _ptr(nproj[c0:]), _ptr(nimg[i0:]), _ptr(ws), nws, _stream())
 
     def reduce(i0, m):                           # a block with no pixels ends its block row (the reference `break`s there, utils.py:568-571)
-        _lib.check(lib.pcl_hist_trim_reduce_images(_ptr(inter[i0 * K:]), _ptr(nproj[i0 * K:]), _ptr(nimg[i0:]), m, K, num_split_h, num_split_w,
-                                                   _ptr(scores[i0:]), _stream()), "pcl_hist_trim_reduce_images")
+        _checked("pcl_hist_trim_reduce_images", _ptr(inter[i0 * K:]), _ptr(nproj[i0 * K:]), _ptr(nimg[i0:]), m, K, num_split_h, num_split_w, _ptr(scores[i0:]),
+                 _stream())
 
     if batch:
         # one batch for the 64 survivors of the loss trim at 1M points (four batches of 16: 2.0 instead of 1.7 ms; 0.8 instead of
@@ -1318,9 +1312,9 @@ def score_maps(cloud, trans, rot, H, W, num_split_h, num_split_w, inter, nproj, 
     score3d, count3d = torch.empty(cloud.n, dtype=F32, device=dev), torch.empty(cloud.n, dtype=torch.int32, device=dev)
     score2d, count2d = torch.empty(nblk, dtype=F32, device=dev), torch.empty(nblk, dtype=torch.int32, device=dev)
     ws = _bytes(nws)
-    _lib.check(lib.pcl_score_maps(_ptr(cloud.data), cloud.n, _ptr(trans), _ptr(rot), K, int(H), int(W), int(num_split_h), int(num_split_w), _ptr(inter),
-                                  _ptr(nproj), _ptr(nimg), None if packed else _ptr(cloud.order), _ptr(score3d), _ptr(count3d), _ptr(score2d),
-                                  _ptr(count2d), _ptr(ws), nws, _stream()), "pcl_score_maps")
+    _checked("pcl_score_maps", _ptr(cloud.data), cloud.n, _ptr(trans), _ptr(rot), K, int(H), int(W), int(num_split_h), int(num_split_w), _ptr(inter),
+             _ptr(nproj), _ptr(nimg), None if packed else _ptr(cloud.order), _ptr(score3d), _ptr(count3d), _ptr(score2d), _ptr(count2d), _ptr(ws), nws,
+             _stream())
     return score3d, count3d, score2d, count2d
 
 
@@ -1346,8 +1340,7 @@ def score_weight_plane(n, score_packed, count_packed, floor=0.0, min_count=1, pl
         raise ValueError("score_weight_plane: plane must be a contiguous float32 GPU tensor of pcl_cloud_stride(n) entries")
     rng = torch.empty(3, dtype=F32, device=score.device)
     ws = _bytes(nws)
-    _lib.check(lib.pcl_score_weights(_ptr(score), _ptr(count), int(n), min_count, floor, _ptr(plane), _ptr(rng), _ptr(ws), nws, _stream()),
-               "pcl_score_weights")
+    _checked("pcl_score_weights", _ptr(score), _ptr(count), int(n), min_count, floor, _ptr(plane), _ptr(rng), _ptr(ws), nws, _stream())
     return plane, rng
 
 
@@ -1413,8 +1406,8 @@ class VoxelGrid:
                 raise ValueError("VoxelGrid: buffers must be contiguous GPU tensors (int32 count, int64 first) of N entries")
         self.cell = torch.empty(self.n, dtype=torch.int32, device=dev)
         words = torch.empty(2, dtype=torch.int32, device=dev)                     # (nvoxels, bad)
-        _lib.check(lib.pcl_voxel_grid(_ptr(xyz), self.n, self.voxel, _ptr(self.cell), _ptr(count), _ptr(first), _ptr(words),
-                                      ctypes.c_void_p(words.data_ptr() + 4), _ptr(ws), nws, _stream()), "pcl_voxel_grid")
+        _checked("pcl_voxel_grid", _ptr(xyz), self.n, self.voxel, _ptr(self.cell), _ptr(count), _ptr(first), _ptr(words), ctypes.c_void_p(words.data_ptr() + 4),
+                 _ptr(ws), nws, _stream())
         nvoxels, bad = (int(v) for v in words.tolist())
         _voxel_bad("VoxelGrid: xyz holds", bad)
         self.nvoxels = nvoxels
@@ -1436,8 +1429,8 @@ class VoxelGrid:
         dev = self.xyz.device
         xyz_out, rgb_out = torch.empty(self.nvoxels, 3, dtype=F32, device=dev), torch.empty(self.nvoxels, 3, dtype=F32, device=dev)
         bad = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.pcl_voxel_centroids(_ptr(self.xyz), _ptr(rgb), self.n, _ptr(self.cell), _ptr(self.count), self.nvoxels, _ptr(xyz_out),
-                                           _ptr(rgb_out), _ptr(bad), _ptr(ws), nws, _stream()), "pcl_voxel_centroids")
+        _checked("pcl_voxel_centroids", _ptr(self.xyz), _ptr(rgb), self.n, _ptr(self.cell), _ptr(self.count), self.nvoxels, _ptr(xyz_out), _ptr(rgb_out),
+                 _ptr(bad), _ptr(ws), nws, _stream())
         _voxel_bad("VoxelGrid.centroids: the cloud holds", bad.item())
         return xyz_out, rgb_out
 
@@ -1446,8 +1439,7 @@ class VoxelGrid:
         (float)((double)cap / count) (pcl_density_weights) — with cap = 1 every occupied voxel has total weight 1."""
         cap = density_cap(cap)
         w = torch.empty(self.n, dtype=F32, device=self.cell.device)
-        _lib.check(_lib.load().pcl_density_weights(_ptr(self.cell), _ptr(self.count), self.n, self.nvoxels, cap, _ptr(w), _stream()),
-                   "pcl_density_weights")
+        _checked("pcl_density_weights", _ptr(self.cell), _ptr(self.count), self.n, self.nvoxels, cap, _ptr(w), _stream())
         return w
 
     def moments(self, out=None):
@@ -1464,8 +1456,7 @@ class VoxelGrid:
         elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (self.nvoxels, 9)):
             raise ValueError("VoxelGrid.moments: out must be a contiguous (V, 9) int64 GPU tensor")
         bad = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().pcl_voxel_moments(_ptr(self.xyz), self.n, self.voxel, _ptr(self.cell), _ptr(self.first), self.nvoxels, _ptr(out),
-                                                 _ptr(bad), _stream()), "pcl_voxel_moments")
+        _checked("pcl_voxel_moments", _ptr(self.xyz), self.n, self.voxel, _ptr(self.cell), _ptr(self.first), self.nvoxels, _ptr(out), _ptr(bad), _stream())
         _voxel_bad("VoxelGrid.moments: xyz holds", bad.item())
         return out
 
@@ -1507,8 +1498,7 @@ def voxel_normals_of(moments, count, min_count=8, return_eig=False):
     dev = moments.device
     normal, planarity = torch.empty(V, 3, dtype=F32, device=dev), torch.empty(V, dtype=F32, device=dev)
     eig = torch.empty(V, 3, dtype=F32, device=dev) if return_eig else None
-    _lib.check(_lib.load().pcl_voxel_normals(_ptr(moments), _ptr(count), V, min_count, _ptr(normal), _ptr(planarity), _ptr(eig), _stream()),
-               "pcl_voxel_normals")
+    _checked("pcl_voxel_normals", _ptr(moments), _ptr(count), V, min_count, _ptr(normal), _ptr(planarity), _ptr(eig), _stream())
     return (normal, planarity, eig) if return_eig else (normal, planarity)
 
 
@@ -1541,8 +1531,7 @@ def align_vote(normal, planarity, count, max_tilt=40.0, yaw=False, ws=None):
         raise ValueError("ws must be a contiguous uint8 GPU tensor of at least pcl_align_workspace_bytes(V) = %d bytes" % nws)
     out = torch.empty(_lib.ALIGN_OUT_WORDS, dtype=torch.float64, device=normal.device)
     params = _lib.AlignParams(max_tilt, int(yaw), 0)
-    _lib.check(lib.pcl_align_vote(_ptr(normal), _ptr(planarity), _ptr(count), V, ctypes.byref(params), _ptr(out), _ptr(ws), nws, _stream()),
-               "pcl_align_vote")
+    _checked("pcl_align_vote", _ptr(normal), _ptr(planarity), _ptr(count), V, ctypes.byref(params), _ptr(out), _ptr(ws), nws, _stream())
     rec = out.cpu()
     d, w = rec[:16].numpy(), rec[16:].view(torch.int64).tolist()
     return {"up": d[0:3].copy(), "rot": d[3:12].reshape(3, 3).copy(), "cos_tilt": float(d[12]), "sin_tilt": float(d[13]), "cos_yaw": float(d[14]),
@@ -1565,7 +1554,7 @@ def align_transform_cloud(xyz, rot, trans):
     if t.numel() != 3:
         raise ValueError("trans must hold 3 values")
     out = torch.empty_like(x)
-    _lib.check(_lib.load().pcl_align_transform_cloud(_ptr(x), int(x.shape[0]), _ptr(r), _ptr(t), _ptr(out), _stream()), "pcl_align_transform_cloud")
+    _checked("pcl_align_transform_cloud", _ptr(x), int(x.shape[0]), _ptr(r), _ptr(t), _ptr(out), _stream())
     return out
 
 
@@ -1591,8 +1580,7 @@ def depth_mask(cloud, trans, rot, resolution, tau=None, stride=1):
     vis = torch.empty(B, cloud.n, dtype=torch.uint8, device=trans.device)
     nws = lib.pcl_depth_workspace_bytes(B, H, W)
     ws = _bytes(nws)
-    _lib.check(lib.pcl_depth_mask(_ptr(cloud.data), cloud.n, _ptr(trans), _ptr(rot), B, H, W, float(tau), int(stride), _ptr(vis), _ptr(ws), nws,
-                                  _stream()), "pcl_depth_mask")
+    _checked("pcl_depth_mask", _ptr(cloud.data), cloud.n, _ptr(trans), _ptr(rot), B, H, W, float(tau), int(stride), _ptr(vis), _ptr(ws), nws, _stream())
     return vis
 
 
@@ -1606,8 +1594,7 @@ class ColorTemplate:
         self.data = torch.empty(3, self.n, dtype=F32, device=rgb.device)
         nws = lib.pcl_color_template_workspace_bytes(self.n)
         ws = _bytes(nws)
-        _lib.check(lib.pcl_color_template_build(_ptr(rgb), self.n, _ptr(self.data), _ptr(ws), nws, _stream()),
-                   "pcl_color_template_build")
+        _checked("pcl_color_template_build", _ptr(rgb), self.n, _ptr(self.data), _ptr(ws), nws, _stream())
 
 
 def color_match(img, template):
@@ -1621,8 +1608,7 @@ def color_match(img, template):
     flag = torch.zeros(1, dtype=torch.int32, device=img.device)
     nws = lib.pcl_color_workspace_bytes()
     ws = _bytes(nws)
-    _lib.check(lib.pcl_color_match(_ptr(img), H, W, _ptr(template.data), template.n, _ptr(out), _ptr(flag), _ptr(ws), nws,
-                                   _stream()), "pcl_color_match")
+    _checked("pcl_color_match", _ptr(img), H, W, _ptr(template.data), template.n, _ptr(out), _ptr(flag), _ptr(ws), nws, _stream())
     if not known and int(flag.item()):
         raise ValueError("color_match: the panorama must hold levels k/255 (an image file's uint8 / 255); "
                          "found a non-black pixel channel in between")
@@ -1637,8 +1623,7 @@ def color_mod(img, rgb, num_bins=256):
     out_img, out_rgb = torch.empty_like(img), torch.empty_like(rgb)
     nws = lib.pcl_color_workspace_bytes()
     ws = _bytes(nws)
-    _lib.check(lib.pcl_color_mod(_ptr(img), H, W, _ptr(rgb), int(rgb.shape[0]), int(num_bins), _ptr(out_img), _ptr(out_rgb),
-                                 _ptr(ws), nws, _stream()), "pcl_color_mod")
+    _checked("pcl_color_mod", _ptr(img), H, W, _ptr(rgb), int(rgb.shape[0]), int(num_bins), _ptr(out_img), _ptr(out_rgb), _ptr(ws), nws, _stream())
     return out_img, out_rgb
 
 
@@ -1657,21 +1642,19 @@ def histogram(img, mask, channels, normalize=True, eps=0.0):
     ws = _bytes(nws)
     hist = torch.empty(max(B, 1) * c0 * c1 * c2, dtype=F32, device=img.device)
     if B:
-        _lib.check(lib.pcl_histogram_batch(_ptr(img), _ptr(mask), B, int(img.shape[0]) // B, c0, c1, c2, int(bool(normalize)), float(eps),
-                                           _ptr(hist), _ptr(ws), nws, _stream()), "pcl_histogram_batch")
+        _checked("pcl_histogram_batch", _ptr(img), _ptr(mask), B, int(img.shape[0]) // B, c0, c1, c2, int(bool(normalize)), float(eps), _ptr(hist), _ptr(ws),
+                 nws, _stream())
         return hist.reshape(B, -1)
-    _lib.check(lib.pcl_histogram(_ptr(img), _ptr(mask), int(img.shape[0]), c0, c1, c2, int(bool(normalize)), float(eps),
-                                 _ptr(hist), _ptr(ws), nws, _stream()), "pcl_histogram")
+    _checked("pcl_histogram", _ptr(img), _ptr(mask), int(img.shape[0]), c0, c1, c2, int(bool(normalize)), float(eps), _ptr(hist), _ptr(ws), nws, _stream())
     return hist
 
 
 def histogram_intersection(h1, h2):
     """(B, nbins) x (B, nbins) -> (B,) sums of element-wise minima (color_utils.py:122-144)."""
-    lib = _lib.load()
     h1, h2 = _dev(h1), _dev(h2)
     B, nbins = int(h1.shape[0]), int(h1.shape[1])
     out = torch.empty(B, dtype=F32, device=h1.device)
-    _lib.check(lib.pcl_histogram_intersection(_ptr(h1), _ptr(h2), B, nbins, _ptr(out), _stream()), "pcl_histogram_intersection")
+    _checked("pcl_histogram_intersection", _ptr(h1), _ptr(h2), B, nbins, _ptr(out), _stream())
     return out
 
 
@@ -1681,13 +1664,8 @@ def quantile_box(xyz, q):
     xyz = _dev(xyz)
     box = torch.empty(6, dtype=F32, device=xyz.device)
     ws = _bytes(lib.pcl_quantile_workspace_bytes())
-    _lib.check(lib.pcl_quantile_box(_ptr(xyz), int(xyz.shape[0]), float(q), _ptr(box), _ptr(ws), _stream()), "pcl_quantile_box")
+    _checked("pcl_quantile_box", _ptr(xyz), int(xyz.shape[0]), float(q), _ptr(box), _ptr(ws), _stream())
     return box
-
-
-def _checked(name, *args):
-    """call the C entry point `name`, which returns an error code, and raise on failure"""
-    _lib.check(getattr(_lib.load(), name)(*args), name)
 
 
 def _gd_hyper(lr, patience, factor, batch_mode, fuse, depth=None, color_sets=0):
@@ -1785,7 +1763,7 @@ class _GdEngine:
         _same_texels(panos, self.pano)
         self._panos = list(panos)                      # keep them alive
         arr = (ctypes.c_uint64 * I)(*[p.data.data_ptr() for p in panos])
-        _lib.check(_lib.load().pcl_gd_set_pano_groups(_ptr(self.state), arr, I, self.B // I, _stream()), "pcl_gd_set_pano_groups")
+        _checked("pcl_gd_set_pano_groups", _ptr(self.state), arr, I, self.B // I, _stream())
 
     def winners(self, groups, leaf_trans=None, leaf_rot=None):
         """(groups, 16) GPU tensor, per group of B / groups candidates the one omniloc_batch returns (omniloc.py:271-277):
@@ -1795,14 +1773,13 @@ class _GdEngine:
             raise ValueError("winner: %d candidates do not split into %d images" % (self.B, groups))
         out = torch.empty(groups, 16, dtype=F32, device=self.state.device)
         self._leaf_check("winner", leaf_trans, leaf_rot)
-        _lib.check(_lib.load().pcl_gd_winner(_ptr(self.state), groups, self.B // groups, _ptr(out), _ptr(leaf_trans), _ptr(leaf_rot), _stream()),
-                   "pcl_gd_winner")
+        _checked("pcl_gd_winner", _ptr(self.state), groups, self.B // groups, _ptr(out), _ptr(leaf_trans), _ptr(leaf_rot), _stream())
         return out
 
     def result(self):
         """(B, 16): fwd t(3), fwd ypr(3), leaf t(3), leaf ypr(3), last loss, lr, scheduler num_bad_epochs, scheduler best."""
         out = torch.empty(self.B, _lib.GD_RESULT_STRIDE, dtype=F32, device=self.state.device)
-        _lib.check(_lib.load().pcl_gd_result(_ptr(self.state), self.B, _ptr(out), _stream()), "pcl_gd_result")
+        _checked("pcl_gd_result", _ptr(self.state), self.B, _ptr(out), _stream())
         return out
 
     def pruned(self, keep, leaf_trans=None, leaf_rot=None):
@@ -1824,8 +1801,8 @@ class _GdEngine:
         if self.B // groups > _lib.GD_PRUNE_MAX:
             raise ValueError("prune: at most %d candidates per group" % _lib.GD_PRUNE_MAX)
         survivors = torch.empty(child.B, dtype=torch.int32, device=self.state.device)
-        _lib.check(_lib.load().pcl_gd_prune(_ptr(self.state), groups, self.B // groups, child.B // groups, _ptr(child.state), _ptr(survivors),
-                                            _ptr(leaf_trans), _ptr(leaf_rot), _stream()), "pcl_gd_prune")
+        _checked("pcl_gd_prune", _ptr(self.state), groups, self.B // groups, child.B // groups, _ptr(child.state), _ptr(survivors), _ptr(leaf_trans),
+                 _ptr(leaf_rot), _stream())
         # the survivors' records name the parent's panoramas: keep them alive, and the mapping hint with them
         child.hyper.images = self.hyper.images
         for name in ("_panos", "_pano_table"):
@@ -1897,22 +1874,18 @@ class GradientDescent(_GdEngine):
         weights = self._run_weights()
         if self.weight_sets:
             # (planes at a stable address, like the one plane below; None: the unweighted loss under the same single-image plan)
-            _lib.check(_lib.load().pcl_gd_run_weight_sets(_ptr(self.cloud.data), _ptr(weights), self.weight_sets, self.cloud.n, _ptr(self.pano.data),
-                                                          self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state), self.B, _ptr(self.box),
-                                                          ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
-                                                          timer.handle if timer else None, _stream()), "pcl_gd_run_weight_sets")
+            _checked("pcl_gd_run_weight_sets", _ptr(self.cloud.data), _ptr(weights), self.weight_sets, self.cloud.n, _ptr(self.pano.data), self.pano.fmt,
+                     self.pano.H, self.pano.W, _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws),
+                     self.ws_bytes, timer.handle if timer else None, _stream())
             return hist
         if weights is not None:
             # (the plane's address is the cloud's for good — Cloud.set_weights packs in place — so a captured graph reads the current weights)
-            _lib.check(_lib.load().pcl_gd_run_weighted(_ptr(self.cloud.data), _ptr(weights), self.cloud.n, _ptr(self.pano.data), self.pano.fmt,
-                                                       self.pano.H, self.pano.W, _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper),
-                                                       int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None,
-                                                       _stream()), "pcl_gd_run_weighted")
+            _checked("pcl_gd_run_weighted", _ptr(self.cloud.data), _ptr(weights), self.cloud.n, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
+                     _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes,
+                     timer.handle if timer else None, _stream())
             return hist
-        _lib.check(_lib.load().pcl_gd_run(_ptr(self.cloud.data), self.cloud.n, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W,
-                                          _ptr(self.state), self.B, _ptr(self.box), ctypes.byref(self.hyper), int(num_iter),
-                                          _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None, _stream()),
-                   "pcl_gd_run")
+        _checked("pcl_gd_run", _ptr(self.cloud.data), self.cloud.n, _ptr(self.pano.data), self.pano.fmt, self.pano.H, self.pano.W, _ptr(self.state), self.B,
+                 _ptr(self.box), ctypes.byref(self.hyper), int(num_iter), _ptr(hist), _ptr(self.ws), self.ws_bytes, timer.handle if timer else None, _stream())
         return hist
 
     def _run_weights(self):
@@ -2037,7 +2010,7 @@ class GradientDescent(_GdEngine):
             self.pano = kept.setdefault(level[0].texels, level[0])
             self.set_pano_groups(level)
             if s and reset_plateau:
-                _lib.check(_lib.load().pcl_gd_plateau_reset(_ptr(self.state), self.B, _stream()), "pcl_gd_plateau_reset")
+                _checked("pcl_gd_plateau_reset", _ptr(self.state), self.B, _stream())
             if graph:
                 self.run_graph(end - done)
             else:
@@ -2053,10 +2026,9 @@ class GradientDescent(_GdEngine):
         trans, rot = _dev(trans).reshape(-1, 3), _dev(rot).reshape(-1, 3)
         assert trans.shape[0] == self.B
         if self.weight_sets:
-            _lib.check(_lib.load().pcl_gd_init_weight_sets(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, self.weight_sets, ctypes.byref(self.hyper),
-                                                           _stream()), "pcl_gd_init_weight_sets")
+            _checked("pcl_gd_init_weight_sets", _ptr(self.state), _ptr(trans), _ptr(rot), self.B, self.weight_sets, ctypes.byref(self.hyper), _stream())
             return
-        _lib.check(_lib.load().pcl_gd_init(_ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream()), "pcl_gd_init")
+        _checked("pcl_gd_init", _ptr(self.state), _ptr(trans), _ptr(rot), self.B, ctypes.byref(self.hyper), _stream())
 
     def set_panos(self, panos):
         """Candidate b samples panos[b] (a list of B Pano objects, all the size / texel format of self.pano): lets the
@@ -2073,7 +2045,7 @@ class GradientDescent(_GdEngine):
         a contiguous range) — a hint for the block -> XCD mapping of the launches, results do not depend on it."""
         self.hyper.images = int(images)
         assert table.dtype == torch.int64 and table.numel() == self.B and table.is_cuda
-        _lib.check(_lib.load().pcl_gd_set_panos(_ptr(self.state), _ptr(table), self.B, _stream()), "pcl_gd_set_panos")
+        _checked("pcl_gd_set_panos", _ptr(self.state), _ptr(table), self.B, _stream())
         self._pano_table = table
 
     def set_pano_groups(self, panos):
@@ -2103,8 +2075,7 @@ class GradientDescent(_GdEngine):
         dL/d(t0, t1, t2, yaw, pitch, roll) through the epilogue's own Adam / ReduceLROnPlateau / clamp code (pcl_gd_step_from_grads)."""
         loss, grad = _dev(loss).reshape(self.B), _dev(grad).reshape(self.B, 6)
         scratch = torch.empty(self.B * 8, dtype=F32, device=self.state.device)
-        _lib.check(_lib.load().pcl_gd_step_from_grads(_ptr(self.state), self.B, _ptr(loss), _ptr(grad), _ptr(self.box), ctypes.byref(self.hyper),
-                                                      _ptr(scratch), _stream()), "pcl_gd_step_from_grads")
+        _checked("pcl_gd_step_from_grads", _ptr(self.state), self.B, _ptr(loss), _ptr(grad), _ptr(self.box), ctypes.byref(self.hyper), _ptr(scratch), _stream())
 
 
 class GradientDescentRoomsImages(_GdEngine):
@@ -2236,14 +2207,14 @@ class KernelTimer:
     def read(self):
         """(total kernel ms, launches) since the last reset; synchronises on the recorded events."""
         ms, cnt = ctypes.c_double(0), ctypes.c_int(0)
-        _lib.check(_lib.load().pcl_timer_read(self.handle, ctypes.byref(ms), ctypes.byref(cnt)), "pcl_timer_read")
+        _checked("pcl_timer_read", self.handle, ctypes.byref(ms), ctypes.byref(cnt))
         return ms.value, cnt.value
 
     def calibrate(self, reps=64):
         """Median reading (ms) of an event pair with NOTHING between its two records, on the current stream: what a pair around
         a kernel over-reads.  Synchronises."""
         ms = ctypes.c_double(0)
-        _lib.check(_lib.load().pcl_timer_calibrate(self.handle, int(reps), ctypes.byref(ms), _stream()), "pcl_timer_calibrate")
+        _checked("pcl_timer_calibrate", self.handle, int(reps), ctypes.byref(ms), _stream())
         return ms.value
 
     def __del__(self):
@@ -2256,44 +2227,39 @@ class KernelTimer:
 
 
 def cloud2idx(xyz):
-    lib = _lib.load()
     x = _dev(xyz)
     shp = x.shape
     flat = x.reshape(-1, 3)
     out = torch.empty(flat.shape[0], 2, dtype=F32, device=x.device)
     if flat.shape[0]:
-        _lib.check(lib.pcl_cloud2idx(_ptr(flat), int(flat.shape[0]), _ptr(out), _stream()), "pcl_cloud2idx")
+        _checked("pcl_cloud2idx", _ptr(flat), int(flat.shape[0]), _ptr(out), _stream())
     return out.reshape(shp[:-1] + (2,))
 
 
 def sample_from_img(pano, coord):
-    lib = _lib.load()
     c = _dev(coord)
     shp = c.shape
     flat = c.reshape(-1, 2)
     out = torch.empty(flat.shape[0], 3, dtype=F32, device=c.device)
     if flat.shape[0]:
-        _lib.check(lib.pcl_sample_from_img(_ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(flat), int(flat.shape[0]), _ptr(out), _stream()),
-                   "pcl_sample_from_img")
+        _checked("pcl_sample_from_img", _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(flat), int(flat.shape[0]), _ptr(out), _stream())
     return out.reshape(shp[:-1] + (3,))
 
 
 def cloud2idx_backward(xyz, grad_coord):
     """grad w.r.t. xyz (.., 3) of cloud2idx for the incoming gradient grad_coord (.., 2)."""
-    lib = _lib.load()
     x, g = _dev(xyz), _dev(grad_coord)
     flat, gflat = x.reshape(-1, 3), g.reshape(-1, 2)
     if gflat.shape[0] != flat.shape[0]:
         raise ValueError("grad_coord must have one (gx, gy) per point")
     out = torch.empty_like(flat)
     if flat.shape[0]:
-        _lib.check(lib.pcl_cloud2idx_backward(_ptr(flat), _ptr(gflat), int(flat.shape[0]), _ptr(out), _stream()), "pcl_cloud2idx_backward")
+        _checked("pcl_cloud2idx_backward", _ptr(flat), _ptr(gflat), int(flat.shape[0]), _ptr(out), _stream())
     return out.reshape(x.shape)
 
 
 def sample_from_img_backward(pano, coord, grad_rgb, want_coord=True, want_img=False):
     """(grad_coord (.., 2) or None, grad_img (H, W, 3) or None) of sample_from_img for the incoming gradient grad_rgb (.., 3)."""
-    lib = _lib.load()
     c, g = _dev(coord), _dev(grad_rgb)
     flat, gflat = c.reshape(-1, 2), g.reshape(-1, 3)
     if gflat.shape[0] != flat.shape[0]:
@@ -2301,50 +2267,46 @@ def sample_from_img_backward(pano, coord, grad_rgb, want_coord=True, want_img=Fa
     gc = torch.empty_like(flat) if want_coord else None
     gi = torch.zeros(pano.H, pano.W, 3, dtype=F32, device=c.device) if want_img else None
     if flat.shape[0] and (want_coord or want_img):
-        _lib.check(lib.pcl_sample_from_img_backward(_ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(flat), _ptr(gflat), int(flat.shape[0]),
-                                                    _ptr(gc), _ptr(gi), _stream()), "pcl_sample_from_img_backward")
+        _checked("pcl_sample_from_img_backward", _ptr(pano.data), pano.fmt, pano.H, pano.W, _ptr(flat), _ptr(gflat), int(flat.shape[0]), _ptr(gc), _ptr(gi),
+                 _stream())
     elif gc is not None:
         gc.zero_()
     return (gc.reshape(c.shape) if gc is not None else None), gi
 
 
 def rot_from_ypr(rot):
-    lib = _lib.load()
     r = _dev(rot).reshape(-1, 3)
     out = torch.empty(r.shape[0], 9, dtype=F32, device=r.device)
-    _lib.check(lib.pcl_rot_from_ypr(_ptr(r), int(r.shape[0]), _ptr(out), _stream()), "pcl_rot_from_ypr")
+    _checked("pcl_rot_from_ypr", _ptr(r), int(r.shape[0]), _ptr(out), _stream())
     return out.reshape(-1, 3, 3)
 
 
 def transform_cloud(xyz, trans, rot):
-    lib = _lib.load()
     x = _dev(xyz)
     t, r = _dev(trans).reshape(3), _dev(rot).reshape(3)
     out = torch.empty_like(x)
-    _lib.check(lib.pcl_transform_cloud(_ptr(x), int(x.shape[0]), _ptr(t), _ptr(r), _ptr(out), _stream()), "pcl_transform_cloud")
+    _checked("pcl_transform_cloud", _ptr(x), int(x.shape[0]), _ptr(t), _ptr(r), _ptr(out), _stream())
     return out
 
 
 def make_pano(xyz_cam, rgb, resolution):
     """(H, W, 3) float GPU tensor = rgb*255 of the winning point per pixel (utils.py:134-205 semantics)."""
-    lib = _lib.load()
     x, c = _dev(xyz_cam), _dev(rgb)
     H, W = int(resolution[0]), int(resolution[1])
     img = torch.empty(H, W, 3, dtype=F32, device=x.device)
     ws = _bytes(H * W * 8)
-    _lib.check(lib.pcl_make_pano(_ptr(x), _ptr(c), int(x.shape[0]), H, W, _ptr(img), _ptr(ws), _stream()), "pcl_make_pano")
+    _checked("pcl_make_pano", _ptr(x), _ptr(c), int(x.shape[0]), H, W, _ptr(img), _ptr(ws), _stream())
     return img
 
 
 def scatter_min_depth(xyz_cam, resolution):
     """torch_scatter-style (zmin (H*W,), argmin (H*W,)) of point depth per make_pano pixel; empty -> (0, n)."""
-    lib = _lib.load()
     x = _dev(xyz_cam)
     H, W = int(resolution[0]), int(resolution[1])
     n = int(x.shape[0])
     zbuf = _bytes(H * W * 8)
     zmin = torch.empty(H * W, dtype=F32, device=x.device)
     arg = torch.empty(H * W, dtype=torch.int64, device=x.device)
-    _lib.check(lib.pcl_scatter_min_depth(_ptr(x), n, H, W, _ptr(zbuf), _stream()), "pcl_scatter_min_depth")
-    _lib.check(lib.pcl_scatter_min_unpack(_ptr(zbuf), n, H, W, _ptr(zmin), _ptr(arg), _stream()), "pcl_scatter_min_unpack")
+    _checked("pcl_scatter_min_depth", _ptr(x), n, H, W, _ptr(zbuf), _stream())
+    _checked("pcl_scatter_min_unpack", _ptr(zbuf), n, H, W, _ptr(zmin), _ptr(arg), _stream())
     return zmin, arg
